@@ -9,7 +9,11 @@ on one per-GPU batch of synthetic ADNI-shaped volumes already resident in HBM.  
 configs[1]: ViT3D-base (128^3, patch 16, dim 768, depth 12, heads 12, mlp 3072), bf16 MFMA operands with
 fp32 accumulate / master weights, batch 4 per GPU (weak scaling: configs[2] = 32 over 8 GPUs).
 
-Prints ONE JSON line on rank 0 (fields documented in DESIGN.md "Measurement").
+Prints ONE JSON line on rank 0 (fields documented in DESIGN.md "Measurement").  A plain run sets up, warms up, times the K steps
+and prints the headline; --full adds the host enqueue figure, the secondary lines (forward-only, fwd+bwd, dropout, fp16 operands,
+batch 20, the 4D step), the per-kernel roofline leg and the CPU baseline.  --dump-outputs DIR writes what the last timed step
+computed (loss, logits, sampled parameters and gradients; logits of a --forward-only run) as .npy files: the inputs are seeded,
+so two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -64,8 +68,12 @@ def parse():
     ap.add_argument("--operands", default="bf16", choices=["bf16", "fp16"],
                     help="16-bit MFMA operand format of the timed model (TRAINING_VIT_OPERANDS): bf16 = BASELINE.json's dtype (headline); fp16 = the "
                          "reference's autocast arithmetic (logits within 1e-3 of its fp32 CPU forward), trained with the device-side dynamic loss scale")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary lines (forward-only, fwd+bwd, dropout)")
+    ap.add_argument("--full", action="store_true", help="after the headline: the host enqueue figure, the secondary lines, the per-kernel roofline leg and "
+                                                        "the CPU baseline (off: the run times only the headline's steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary lines (forward-only, fwd+bwd, dropout)")
     ap.add_argument("--cpu-steps", type=int, default=5)
     ap.add_argument("--cpu-leg", type=int, default=0, help="internal: run only the CPU baseline's train steps on this many threads and print a JSON value")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
@@ -264,6 +272,26 @@ def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_SAMPLE = 1 << 22           # elements kept of a flat arena larger than this (16 MB of float32 per array)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs DIR: each array as DIR/<name>.npy in float32 (float64 stays float64).  A flat arena of more than DUMP_SAMPLE
+    elements is reduced to the elements at a fixed sample of positions (sorted, torch.Generator seed 1234), the same in every run of
+    the same preset."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() == 1 and t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator(device="cpu").manual_seed(1234)).sort().values
+            t = t[idx.to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(d, f"{name}.npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+    log(f"outputs of the last timed step written to {d}: {', '.join(sorted(arrays))}")
+
+
 def dry_run(a, world, rank):
     """--dry-run: the N-rank plumbing of the timed region (process group, barrier, max over ranks, one JSON line) with an
     empty step - runs without a GPU (gloo)."""
@@ -319,6 +347,8 @@ def forward_only_bench(a, model, x, size, S, p, B, world, rank, device, dist):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"logits": out})
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -431,23 +461,59 @@ def main():
     enqueued = time.perf_counter() - t0          # host time to enqueue the K steps: far below `elapsed` = the GPU is the limiter
     barrier()
     elapsed = time.perf_counter() - t0
-    # host cost of enqueueing ONE step, measured from an idle queue (over the K timed steps the host runs into the runtime's queue
-    # depth and is throttled to the GPU's pace, so `enqueued` only bounds it from above)
-    t1 = time.perf_counter()
-    step(x, y)
-    host_step_ms = (time.perf_counter() - t1) * 1e3
-    torch.cuda.synchronize()
+    if a.dump_outputs and rank == 0:
+        # what a caller of the train step receives: the loss, the logits (TrainStep.last_outputs), and the updated parameters and
+        # their gradients (flat fp32 arenas, sampled)
+        vit = model.volume_encoder.vit3d
+        dump_outputs(a.dump_outputs, {"loss": loss, "logits": step.last_outputs, "parameters": vit.flat_parameters()[0],
+                                      "gradients": vit.flat_gradients()})
     log(f"rank {rank}: step path: {step.last_path} (native = nv_vit_train_step; native-dp = the same call with RCCL all-reduce per bucket from native code"
         f"{' ' + str(getattr(step, 'last_dp', '')) if step.last_path == 'native-dp' else ''}; general = autograd-driven stages), AdamW placement fuse_update = {step.last_fuse_update}, "
         f"loss scale: {'dynamic (device-side GradScaler)' if step.scaler is not None else (step.static_scale or 'none')}")
-    log(f"host enqueue {host_step_ms:.3f} ms for one step from an idle queue ({enqueued / a.steps * 1e3:.3f} ms/step inside the timed loop) "
-        f"of {elapsed / a.steps * 1e3:.3f} ms/step")
+    fuse_mode = getattr(step, "last_fuse_update", 0)
+    loss = float(loss)
+    if a.full:
+        # host cost of enqueueing ONE step, measured from an idle queue (over the K timed steps the host runs into the runtime's queue
+        # depth and is throttled to the GPU's pace, so `enqueued` only bounds it from above)
+        t1 = time.perf_counter()
+        step(x, y)
+        host_step_ms = (time.perf_counter() - t1) * 1e3
+        torch.cuda.synchronize()
+        log(f"host enqueue {host_step_ms:.3f} ms for one step from an idle queue ({enqueued / a.steps * 1e3:.3f} ms/step inside the timed loop) "
+            f"of {elapsed / a.steps * 1e3:.3f} ms/step")
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
     ms = elapsed / a.steps * 1e3
     value = B * world * a.steps / elapsed
+
+    from neurovit_amd.engine import flops_forward, make_config
+    vcfg = dict(image_size=S, image_patch_size=p, frames=S, frame_patch_size=p, num_classes=2, dim=size["TRAINING_VIT_DIM"],
+                depth=size["TRAINING_VIT_DEPTH"], heads=size["TRAINING_VIT_HEADS"], mlp_dim=size["TRAINING_VIT_MLP_DIM"], channels=1, dim_head=64)
+    f_fwd = flops_forward(make_config(**vcfg))
+    f_step = 3.0 * f_fwd                                    # fwd + bwd = 3 x fwd algorithmic FLOPs (SURVEY 8d)
+
+    # BASELINE.json's metric is "fMRI volumes/sec (fwd+bwd) ViT3D 128^3 p16 d768 L12"; the timed step is the reference's whole train
+    # step (Trainer.py:65-79), i.e. it also contains the AdamW update - said in the string so the number is not read as fwd+bwd only
+    metric = (f"fMRI volumes/sec (fwd+bwd) ViT3D {S}^3 p{p} d{size['TRAINING_VIT_DIM']} L{size['TRAINING_VIT_DEPTH']}"
+              " [timed step = fwd+bwd+AdamW update]")
+    out = {"metric": metric, "value": round(value, 2), "unit": "volumes/s",
+           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None,
+           "dtype": "fp8 forward (e4m3 qkv/FC1/FC2 operands, fp32 accumulate), bf16 backward" if a.fp8 else a.operands, "data": "synthetic",
+           "config": {"workload": f"ViT3D-{a.preset} {S}^3 patch {p}, train step (fwd+bwd+AdamW), batch {B}/GPU, dropout {a.dropout:g}",
+                      "global_batch": B * world, "parallelism": f"dp{world}", "grad_buckets": a.buckets,
+                      "grad_allreduce": ("none (1 GPU)" if world == 1 else f"{a.grad_comm} messages, sum, overlapped with backward"),
+                      "step_path": step.last_path, "dp": getattr(step, "last_dp", None),
+                      "adamw": ({1: "layers' Linear weights updated in their weight-gradient GEMM epilogues, the rest in one launch",
+                                 2: "layers' Linear weights updated in their weight-gradient GEMM epilogues (gradients kept), the rest in one launch",
+                                 3: "layers' Linear weights updated per layer on the auxiliary stream behind their weight-gradient GEMMs, the rest in one launch"}.get(
+                                     fuse_mode, "one launch over the arena behind the backward pass" if world == 1 else "per arena range behind the gradient all-reduce"))},
+           "mfma_frac_step": round(value / world * f_step / (PEAK_BF16_TFLOPS * 1e12), 4),
+           "loss": round(loss, 5)}
+    if not a.full:
+        return finish(out, rank, world, dist, rccl_log)
 
     # ---- secondary lines SURVEY 8(d) asks for (single rank; not the headline): forward-only (validate, Trainer.py:101-118),
     #      fwd+bwd without the optimizer, and the full step with the config's default dropout 0.1
@@ -588,7 +654,6 @@ def main():
     #     one launch behind the backward pass (the definition of rounds 1-3), for comparison:
     achieved_unfused = None
     fused_was = getattr(step, "fuse_update", 0)
-    fuse_mode = getattr(step, "last_fuse_update", 0)
     if fuse_mode:
         step.fuse_update = 0
         step(x, y)
@@ -662,42 +727,25 @@ def main():
                 "by_kernel": by_kernel}
     executed_flops_step = sum(v["flops"] for v in kinds.values()) / prof_steps       # what the MFMA kernels of a step really execute
 
-    from neurovit_amd.engine import flops_forward, make_config
-    vcfg = dict(image_size=S, image_patch_size=p, frames=S, frame_patch_size=p, num_classes=2, dim=size["TRAINING_VIT_DIM"],
-                depth=size["TRAINING_VIT_DEPTH"], heads=size["TRAINING_VIT_HEADS"], mlp_dim=size["TRAINING_VIT_MLP_DIM"], channels=1, dim_head=64)
-    f_fwd = flops_forward(make_config(**vcfg))
-    f_step = 3.0 * f_fwd                                    # fwd + bwd = 3 x fwd algorithmic FLOPs (SURVEY 8d)
-
-    # BASELINE.json's metric is "fMRI volumes/sec (fwd+bwd) ViT3D 128^3 p16 d768 L12"; the timed step is the reference's whole train
-    # step (Trainer.py:65-79), i.e. it also contains the AdamW update - said in the string so the number is not read as fwd+bwd only
-    metric = (f"fMRI volumes/sec (fwd+bwd) ViT3D {S}^3 p{p} d{size['TRAINING_VIT_DIM']} L{size['TRAINING_VIT_DEPTH']}"
-              " [timed step = fwd+bwd+AdamW update]")
-    out = {"metric": metric, "value": round(value, 2), "unit": "volumes/s",
-           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None,
-           "dtype": "fp8 forward (e4m3 qkv/FC1/FC2 operands, fp32 accumulate), bf16 backward" if a.fp8 else a.operands, "data": "synthetic",
-           "config": {"workload": f"ViT3D-{a.preset} {S}^3 patch {p}, train step (fwd+bwd+AdamW), batch {B}/GPU, dropout {a.dropout:g}",
-                      "global_batch": B * world, "parallelism": f"dp{world}", "grad_buckets": a.buckets,
-                      "grad_allreduce": ("none (1 GPU)" if world == 1 else f"{a.grad_comm} messages, sum, overlapped with backward"),
-                      "step_path": step.last_path, "dp": getattr(step, "last_dp", None),
-                      "adamw": ({1: "layers' Linear weights updated in their weight-gradient GEMM epilogues, the rest in one launch",
-                                 2: "layers' Linear weights updated in their weight-gradient GEMM epilogues (gradients kept), the rest in one launch",
-                                 3: "layers' Linear weights updated per layer on the auxiliary stream behind their weight-gradient GEMMs, the rest in one launch"}.get(
-                                     fuse_mode, "one launch over the arena behind the backward pass" if world == 1 else "per arena range behind the gradient all-reduce"))},
-           "mfma_frac_step": round(value / world * f_step / (PEAK_BF16_TFLOPS * 1e12), 4),
+    out.update({
            # the last block runs on its B cls rows (pool='cls': the other rows never reach the head; tests prove identical logits and
            # gradients), so ~5 % of the ALGORITHMIC FLOPs above are not executed: this is the fraction over the FLOPs the step's MFMA
            # kernels really ran (GEMM + attention launches as counted by the per-launch profiler; skinny cls-row kernels excluded)
            "mfma_frac_step_executed": round(executed_flops_step / (ms * 1e-3) / (PEAK_BF16_TFLOPS * 1e12), 4),
            "executed_over_algorithmic_flops": round(executed_flops_step / (B * f_step), 4),
            "host_enqueue_ms_per_step": round(host_step_ms, 3),
-           "loss": round(float(loss), 5), "roofline": roofline}
+           "roofline": roofline})
     if also is not None:
         also["forward_only_mfma_frac"] = round(also["forward_only_eval_volumes_s"] * f_fwd / (PEAK_BF16_TFLOPS * 1e12), 4)
         out["also"] = also
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         log("cpu baseline leg")
         out["cpu_baseline"] = cpu_baseline(model, vcfg, B, S, a.cpu_steps, preset=a.preset)
+    finish(out, rank, world, dist, rccl_log)
+
+
+def finish(out, rank, world, dist, rccl_log):
+    """The result line (rank 0), then the process group's teardown and rank 0's RCCL summary."""
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

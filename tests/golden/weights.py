@@ -9,6 +9,7 @@ the regenerated weights).
 """
 from __future__ import annotations
 
+import math
 import zlib
 from collections import OrderedDict
 from typing import Dict, List, Tuple
@@ -87,8 +88,11 @@ def make_volume(shape, seed: int) -> torch.Tensor:
 
 
 def checksums(sd: Dict[str, torch.Tensor]) -> Dict[str, np.ndarray]:
-    """Per-tensor (sum, sum of squares) in float64 - stored in fixtures to prove regeneration."""
-    return {k: np.array([v.double().sum().item(), (v.double() ** 2).sum().item()]) for k, v in sd.items()}
+    """Per-tensor (sum, sum of squares) in float64 - stored in fixtures to prove regeneration.  Correctly rounded sums
+    (math.fsum; the square of a float32 is exact in float64): the same bits on any host and thread count."""
+    def fsum(t):
+        return math.fsum(t.detach().double().flatten().tolist())
+    return {k: np.array([fsum(v), fsum(v.detach().double() ** 2)]) for k, v in sd.items()}
 
 
 # Named configurations used by fixtures and tests -------------------------------------------------

@@ -47,7 +47,7 @@ def main():
     rows.sort(key=lambda r: -r["cycles"] * r["launches"])
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with open(os.path.join(root, "profiles", f"{tag}_pmc_sq.csv"), "w") as f:
-        f.write("# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE -- python3 bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-extras\n")
+        f.write("# rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAVES GRBM_GUI_ACTIVE -- python3 bench.py --steps 3 --warmup 2 --full --no-cpu-baseline --no-extras\n")
         f.write("# per-launch averages, every kernel ALONE on the chip (dispatches are serialised under --pmc); definitions: tools/pmc_sq_summary.py\n")
         f.write("kernel,nv_prof_kind,launches,kernel_cycles,mfma_busy,cu_busy,waves,wait_inst_share,wait_any_share,active_inst_share\n")
         for r in rows:
