@@ -254,12 +254,20 @@ long nv_patch_ln_bwd_workspace_bytes(int tokens, int P);
 int nv_patch_ln_bwd(const float* video, const long* strides5, int B, int C, int F, int H, int W, int p1, int p2, int pf,
                     const float* dxp, long ldd, const float* mean, const float* rstd, float* dgamma, float* dbeta,
                     int accumulate, void* workspace, long ws_bytes, void* stream);
+/* (revision 7) backward of LayerNorm(patch_dim) w.r.t. its input, scattered back into voxel layout: dvideo (f32, geometry of `video`,
+ * element strides dstrides5) = d loss / d video, from dxp [B*N, ldd] (the gradient at the LayerNorm's output; columns P .. ldd-1 are
+ * not read), the forward's token statistics and gamma.  The volume is re-gathered (fp32).  Every element of dvideo is written exactly
+ * once (the patches tile the volume): no clearing needed. */
+int nv_patch_ln_dx(const float* video, const long* strides5, int B, int C, int F, int H, int W, int p1, int p2, int pf,
+                   const float* dxp, long ldd, const float* mean, const float* rstd, const float* gamma,
+                   float* dvideo, const long* dstrides5, void* stream);
 
 /* ---- LayerNorm(dim) + cls token + positional embedding (vit_3d.py:95,116-118): t [B*N,d] -> x [B,N+1,d] */
 int nv_embed_finish_fwd(const float* t, long ldt, int B, int N, int d, const float* gamma, const float* beta, float eps,
                         const float* pos, const float* cls, float* x, long ldx, float* mean, float* rstd,
                         unsigned long drop_seed, float drop_p, void* stream);
 long nv_embed_finish_bwd_workspace_bytes(int B, int N, int d);
+/* dgamma, dbeta, dbias_pe, dpos, dcls: all given, or (revision 7) all NULL - then only dt / dt16 are produced (data-only backward) */
 int nv_embed_finish_bwd(const float* g, long ldg, const float* t, long ldt, const float* mean, const float* rstd,
                         const float* gamma, int B, int N, int d, float* dt, long lddt, void* dt16, long lddt16, float* dgamma,
                         float* dbeta, float* dbias_pe, float* dpos, float* dcls, int accumulate, void* workspace, long ws_bytes,
@@ -285,6 +293,7 @@ int nv_spin_us(int microseconds, void* stream);   /* one wave that keeps `stream
 int nv_head_fwd(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps,
                 const float* W, const float* bias, int C, float* xh, float* stats, float* logits, void* stream);
 long nv_head_bwd_workspace_bytes(int B, int d);
+/* dgamma, dbeta, dW, dbias: all given (dcolsum may be NULL), or (revision 7) all five NULL - then only g / g16 are produced */
 int nv_head_bwd(const float* dlogits, int B, int C, const float* W, const float* x, long row_stride, const float* stats,
                 const float* xh, const float* gamma, int d, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma,
                 float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
@@ -476,6 +485,27 @@ int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const float* video
                              const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                              int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                              unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form);
+/* (revision 7) options of nv_vit_backward_ex - the gradient w.r.t. the input volume, and the data-only backward.
+ * dvideo (may be NULL): f32 [B, C, F, H, W] with element strides dvideo_strides5 - receives d loss / d video (every element written
+ *   exactly once, by the call whose stage range contains the embedding stage, depth + 1; on the auxiliary stream behind the dxp GEMM,
+ *   ordered before `stream` by the final join).  Needs the plain input form of the forward (no vol_sigma, no time_points).
+ * weight_grads = 0: the data-only backward - none of the work that only produces parameter gradients runs (per-layer weight-gradient
+ *   GEMMs, bias / LayerNorm column reductions, the patch embedding's dW, nv_patch_ln_bwd); the data chain, the Grad-CAM hook gradient
+ *   (workspace "hookg") and dvideo are bit-identical to a backward with weight_grads = 1.  `grads` and `grads16` must then be NULL:
+ *   nothing is written to a gradient arena, and everything runs on `stream` (aux_stream is not used).
+ * struct_size = sizeof(nv_vit_backward_opts): checked. */
+typedef struct nv_vit_backward_opts {
+  int struct_size;
+  float* dvideo;
+  const long* dvideo_strides5;
+  int weight_grads;          /* 1 = parameter gradients as nv_vit_backward_stages16; 0 = data-only */
+} nv_vit_backward_opts;
+/* nv_vit_backward_stages16 with options (opts = NULL: exactly nv_vit_backward_stages16).  Not for the fused-update path of
+ * nv_vit_train_step, nor after a forward of the fused 4D input form (time_points). */
+int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                       const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                       int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                       unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts);
 int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, long* begin, long* end);
 /* pool='cls': the last block's out-projection / LayerNorm / FeedForward, forward and backward, on the B cls rows only (whenever the
  * block dropout is off; training additionally B <= 4).  Logits and every gradient are unchanged (the other rows never reach the
@@ -555,7 +585,7 @@ int nv_cu_census(unsigned* out, int blocks, int threads, int lds_bytes, int hold
 
 /* ABI revision of this header: bumped whenever a struct gains a field or an entry point changes its argument list (the list is in
  * INTEGRATION.md "ABI revisions").  A caller built against revision R must refuse a library whose nv_abi_version() != R. */
-#define NV_ABI_VERSION 6
+#define NV_ABI_VERSION 7
 int nv_abi_version(void);
 /* dst[b .. b + len) = bf16(src[b .. b + len)) for `count` element ranges (HOST arrays begins / lens; any count) */
 int nv_cast_ranges_bf16(const float* src, void* dst, const long* begins, const long* lens, int count, void* stream);

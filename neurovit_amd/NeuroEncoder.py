@@ -65,7 +65,8 @@ class NeuroEncoder(nn.Module):
         series = fmri.to(self.device)
         n_samples, n_time = series.shape[0], series.shape[-1]
         vit = self.volume_encoder.vit3d
-        frozen = not (torch.is_grad_enabled() and any(p.requires_grad for p in vit.parameters()))
+        # the fused form records no graph: only when neither the encoder's parameters nor the series (dL/d fMRI) want a gradient
+        frozen = not (torch.is_grad_enabled() and (series.requires_grad or any(p.requires_grad for p in vit.parameters())))
         if frozen and n_time % 4 == 0 and n_time <= 64 and series.dtype == torch.float32 and series.is_contiguous():
             # fused 4D gather (csrc/norm.hip::patch_ln_fwd_t_kernel): the B*T volumes are read in place, no regroup copy
             per_volume = vit(series, time_points=n_time).unflatten(0, (n_samples, n_time))

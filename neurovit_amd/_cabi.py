@@ -55,7 +55,13 @@ class AdamwArena(ctypes.Structure):
                 ("adam_v", ctypes.c_void_p), ("params16", ctypes.c_void_p)]
 
 
-ABI_VERSION = 6      # NV_ABI_VERSION of the header this binding was written against (checked at load time)
+class BackwardOpts(ctypes.Structure):
+    """struct nv_vit_backward_opts (neurovit_hip.h, revision 7): options of nv_vit_backward_ex - the gradient w.r.t. the input volume
+    (dvideo + its element strides) and the data-only backward (weight_grads = 0)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("dvideo", ctypes.c_void_p), ("dvideo_strides5", ctypes.c_void_p), ("weight_grads", ctypes.c_int)]
+
+
+ABI_VERSION = 7      # NV_ABI_VERSION of the header this binding was written against (checked at load time)
 
 
 def parse_header(path: str = HEADER) -> Dict[str, Tuple[object, List[object]]]:

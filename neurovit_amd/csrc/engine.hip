@@ -733,26 +733,44 @@ extern "C" int nv_vit_backward_stages(const nv_vit_config* cfg, int B, const flo
 static int backward_impl(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                          const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
-                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode);
+                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
+                         const nv_vit_backward_opts* opts);
 
 extern "C" int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                                         int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form) {
   return backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
-                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0);
+                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, nullptr);
+}
+
+extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                                  const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                                  int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                                  unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts) {
+  NV_CHECK_ARG(!opts || opts->struct_size == (int)sizeof(nv_vit_backward_opts), "nv_vit_backward_ex: opts->struct_size %d != %d (ABI revision mismatch)",
+               opts ? opts->struct_size : 0, (int)sizeof(nv_vit_backward_opts));
+  return backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, opts);
 }
 
 static int backward_impl(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                          const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
-                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode) {
+                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
+                         const nv_vit_backward_opts* opts) {
   Dims D; RUN(make_dims(cfg, B, D));
   NV_CHECK_ARG(!fuse || (!accumulate && !grads16 && fuse->grads == grads && first_stage <= 1 && last_stage == D.L + 1),
                "nv_vit_backward: the optimizer update during the backward pass needs accumulate = 0, no bf16 mirror, its own gradient arena and every stage in one call");
   ParamTab T; make_params(D, T);
   WS W; make_ws(D, 1, W);
-  NV_CHECK_ARG(video && strides5 && params && params16 && workspace && dlogits && grads, "nv_vit_backward: null pointer");
+  // opts (nv_vit_backward_ex): the input gradient, and the data-only form (weight_grads = 0: no gradient arena, nothing on [A])
+  const bool wg = !opts || opts->weight_grads;
+  float* const dvideo = opts ? opts->dvideo : nullptr;
+  NV_CHECK_ARG(!fuse || !opts, "nv_vit_backward: the optimizer update during the backward pass takes no input gradient / data-only options");
+  NV_CHECK_ARG(!dvideo || opts->dvideo_strides5, "nv_vit_backward_ex: dvideo needs dvideo_strides5");
+  NV_CHECK_ARG(wg || (!grads && !grads16), "nv_vit_backward_ex: the data-only backward (weight_grads = 0) writes no gradient arena - pass grads = grads16 = NULL");
+  NV_CHECK_ARG(video && strides5 && params && params16 && workspace && dlogits && (grads || !wg), "nv_vit_backward: null pointer");
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_backward: workspace too small (%ld < %ld) - forward must run with training=1", ws_bytes, W.total);
   NV_CHECK_ARG(nv_aligned16(grads) && nv_aligned16(grads16), "nv_vit_backward: grads / grads16 must be 16-byte aligned");
   const bool tail_fwd = cls_tail_wanted(D, 1, drop_p, rows_form);     // the form the (training) forward took, given the same arguments
@@ -762,6 +780,7 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   const float* p = params;
   const r16* p16 = (const r16*)params16;
   float* gr = grads;
+  auto GR = [&](long off) -> float* { return gr ? gr + off : nullptr; };   // (data-only: no arena, every parameter-gradient output NULL)
   const int M = D.M, d = D.d, acc = accumulate;
   float* g = (float*)(ws + W.g);
   // Buffers the auxiliary stream reads exist twice (even / odd layers): layer l's weight-gradient work runs while the main
@@ -780,7 +799,7 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   void* red = ws + W.red;
   const float scale = 1.0f / sqrtf((float)D.dh);
   hipStream_t S = (hipStream_t)stream;
-  hipStream_t A = aux_stream ? (hipStream_t)aux_stream : S;       // weight-gradient stream (== S: fully serial)
+  hipStream_t A = (aux_stream && wg) ? (hipStream_t)aux_stream : S;       // weight-gradient stream (== S: fully serial; always in the data-only form)
   void* sA = (void*)A;
   const bool forked = (A != S);
   // (no S -> A ordering here: everything the auxiliary stream does in this call is queued behind a signal of the main stream below)
@@ -791,13 +810,17 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   if (first_stage == 0)
   RUN(nv_head_bwd(dlogits, B, D.C, p + T.hw, D.pool_mean ? (const float*)(ws + W.xm) : xlast, D.pool_mean ? (long)d : (long)D.n * d,
                   (float*)(ws + W.hst), (float*)(ws + W.xh), p + T.hg, d, D.n, g, d, G16(D.L - 1), d,
-                  gr + T.hg, gr + T.hb, gr + T.hw, gr + T.hbias, gr + T.layer[D.L - 1].b2, acc, red, W.red_bytes,
+                  GR(T.hg), GR(T.hb), GR(T.hw), GR(T.hbias), GR(T.layer[D.L - 1].b2), acc, red, W.red_bytes,
                   site_seed(drop_seed, 4 * (D.L - 1) + 3), drop_p, D.pool_mean, stream));
 
   // One cross-stream event per layer in each direction (an event record costs several microseconds of queue time): the main
   // stream signals once, after the attention backward; the auxiliary stream then runs, one layer behind the main stream,
   // [db1 column sum, LN2 reduction, LN1 reduction of the layer above, grouped weight-gradient GEMMs] and signals back once.
   hipEvent_t prev_done = carry_take(workspace);     // everything the previous (higher) layer queued on [A] - in the previous, unjoined call
+  if (!wg && prev_done) {                           // data-only: serial, so the main stream takes that dependency up front
+    if (hipStreamWaitEvent(S, prev_done, 0) != hipSuccess) { nv_set_error("nv_vit_backward: event wait failed"); return NV_ERR_HIP; }
+    prev_done = nullptr;
+  }
   bool layers_here = false;
   int pending_ln1 = -1;               // layer whose LN1-backward partials still wait for their reduction
   int pending_adam = -1;              // fuse_mode 3: layer whose weights are updated at the NEXT signal - the main stream orders a layer's dxn1 GEMM (last
@@ -810,7 +833,7 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   };
   auto reduce_ln1 = [&](int lp) -> int {
     const LayerP& qp = T.layer[lp];
-    return nv_ln_bwd_reduce(RED3(lp), M, d, gr + qp.n1g, gr + qp.n1b, (lp > 0) ? gr + T.layer[lp - 1].b2 : nullptr, acc, sA);
+    return nv_ln_bwd_reduce(RED3(lp), M, d, GR(qp.n1g), GR(qp.n1b), (lp > 0) ? GR(T.layer[lp - 1].b2) : nullptr, acc, sA);
   };
   void* const ln_reduce = NV_LN_NO_REDUCE;   // every parameter-gradient reduction of a layer goes into ONE nv_reduce_multi launch
   for (int l = D.L - 1; l >= 0; --l) {
@@ -833,14 +856,14 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
     const long rs = tail ? (long)D.n : 1;
     // ---- FeedForward backward (vit_3d.py:16-26)
     if (tail) {
-      RUN(nv_skinny_nn(0, B, D.m, d, g16, d * rs, p16 + q.w2, D.m, ws + w.u, D.m * rs, du, D.m * rs, gr + q.b1, acc, site_seed(drop_seed, 4 * l + 2), drop_p, stream));   // dU = (g W2 * mask) * gelu'(u), db1 = column sums
+      RUN(nv_skinny_nn(0, B, D.m, d, g16, d * rs, p16 + q.w2, D.m, ws + w.u, D.m * rs, du, D.m * rs, GR(q.b1), acc, site_seed(drop_seed, 4 * l + 2), drop_p, stream));   // dU = (g W2 * mask) * gelu'(u), db1 = column sums
       RUN(nv_skinny_nn(1, B, d, D.m, du, D.m * rs, p16 + q.w1, d, nullptr, 0, dxn, d * rs, nullptr, 0, 0, 0.f, stream));             // dxn2 = dU W1
     } else {
     RUN(nv_gemm_bf16(1, du_tile_rows ? 6 : 5, M, D.m, d, g16, d, p16 + q.w2, D.m, du, D.m, nullptr, ws + w.u, D.m, du_tile_rows ? CS1(l) : nullptr, D.m, 0, 1.f,
                      site_seed(drop_seed, 4 * l + 2), drop_p, stream));   // dU = (g W2 * mask) * gelu'(u)  [+ per-tile column sums -> db1]
     RUN(nv_gemm_bf16(1, 1, M, d, D.m, du, D.m, p16 + q.w1, d, dxn, d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));                        // dxn2 = dU W1
     }
-    RUN(nv_ln_bwd(dxn, d * rs, (float*)(ws + w.x1), d * rs, st2, st2 + M, p + q.n2g, Mr, d, g, g, d * rs, g16b, d * rs, gr + q.n2g, gr + q.n2b, gr + q.bo, acc, RED(l),
+    RUN(nv_ln_bwd(dxn, d * rs, (float*)(ws + w.x1), d * rs, st2, st2 + M, p + q.n2g, Mr, d, g, g, d * rs, g16b, d * rs, GR(q.n2g), GR(q.n2b), GR(q.bo), acc, RED(l),
                   W.red_bytes, site_seed(drop_seed, 4 * l + 1), proj_drop_p(cfg, drop_p), stream, ln_reduce));                                   // g += dLN2 -> g16b
     // ---- Attention backward (vit_3d.py:48-60)
     if (tail) {
@@ -856,30 +879,30 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
     // ---- [A] everything of this layer that only finishes parameter gradients
     if (forked) RUN(stream_sync(S, A));                                                                                        // dU, g16b, dqkv (and the LN partials) ready
     if (pending_adam >= 0) { RUN(layer_update(pending_adam)); pending_adam = -1; }      // [A] fuse_mode 3: the layer above, whose last reader (its dxn1 GEMM) ran before this signal
-    {
+    if (wg) {
       // [A] ONE launch for every small parameter gradient that is final by now: db1 (column sums of dU), dLN2 affine + dbo
       // (= colsum(g)), and dLN1 affine + db2 of the layer above (whose partials were written after that layer's block ran)
       nv_reduce_job jobs[3];
       int nj = 0;
       if (tail) {}                                                  // db1 came out of the dU kernel
-      else if (du_tile_rows) jobs[nj++] = {CS1(l), (M + du_tile_rows - 1) / du_tile_rows, D.m, 1, {gr + q.b1, nullptr, nullptr}, acc};
-      else RUN(nv_colsum_bf16(du, D.m, M, D.m, gr + q.b1, acc, RED2(l), W.red2_bytes, sA));
-      jobs[nj++] = {(const float*)RED(l), nv_ln_bwd_partial_rows(Mr), d, 3, {gr + q.n2g, gr + q.n2b, gr + q.bo}, acc};
+      else if (du_tile_rows) jobs[nj++] = {CS1(l), (M + du_tile_rows - 1) / du_tile_rows, D.m, 1, {GR(q.b1), nullptr, nullptr}, acc};
+      else RUN(nv_colsum_bf16(du, D.m, M, D.m, GR(q.b1), acc, RED2(l), W.red2_bytes, sA));
+      jobs[nj++] = {(const float*)RED(l), nv_ln_bwd_partial_rows(Mr), d, 3, {GR(q.n2g), GR(q.n2b), GR(q.bo)}, acc};
       if (pending_ln1 >= 0) {
         const LayerP& qp = T.layer[pending_ln1];
-        jobs[nj++] = {(const float*)RED3(pending_ln1), ln_rows, d, 3, {gr + qp.n1g, gr + qp.n1b, (pending_ln1 > 0) ? gr + T.layer[pending_ln1 - 1].b2 : nullptr}, acc};
+        jobs[nj++] = {(const float*)RED3(pending_ln1), ln_rows, d, 3, {GR(qp.n1g), GR(qp.n1b), (pending_ln1 > 0) ? GR(T.layer[pending_ln1 - 1].b2) : nullptr}, acc};
         pending_ln1 = -1;
       }
       RUN(nv_reduce_multi(jobs, nj, sA));
     }
-    {
+    if (wg) {
       // the four weight gradients of the layer in ONE grouped launch (864 tiles keep two workgroups resident on every CU;
       // launched one by one their 72-288 tiles leave the CUs half empty and latency bound)
       nv_gemm_problem pr[4];
-      pr[0] = {d, D.m, Mr, g16, d * rs, ws + w.h, D.m * rs, gr + q.w2, D.m, acc, M16(q.w2), D.m};                     // dW2 = g^T h
-      pr[1] = {D.m, d, Mr, du, D.m * rs, ws + w.xn2, d * rs, gr + q.w1, d, acc, M16(q.w1), d};                        // dW1 = dU^T xn2
-      pr[2] = {d, D.inner, Mr, g16b, d * rs, ws + w.ao, D.inner * rs, gr + q.wo, D.inner, acc, M16(q.wo), D.inner};   // dWo = g^T ao
-      pr[3] = {3 * D.inner, d, M, dqkv, 3 * D.inner, ws + w.xn1, d, gr + q.wqkv, d, acc, M16(q.wqkv), d};  // dWqkv = dqkv^T xn1
+      pr[0] = {d, D.m, Mr, g16, d * rs, ws + w.h, D.m * rs, GR(q.w2), D.m, acc, M16(q.w2), D.m};                     // dW2 = g^T h
+      pr[1] = {D.m, d, Mr, du, D.m * rs, ws + w.xn2, d * rs, GR(q.w1), d, acc, M16(q.w1), d};                        // dW1 = dU^T xn2
+      pr[2] = {d, D.inner, Mr, g16b, d * rs, ws + w.ao, D.inner * rs, GR(q.wo), D.inner, acc, M16(q.wo), D.inner};   // dWo = g^T ao
+      pr[3] = {3 * D.inner, d, M, dqkv, 3 * D.inner, ws + w.xn1, d, GR(q.wqkv), d, acc, M16(q.wqkv), d};  // dWqkv = dqkv^T xn1
       if (fuse && fuse_mode == 3) {      // gradients stored as ever; the layer's update follows as a launch of its own, one signal later
         RUN(nv_gemm_bf16_grouped(2, 1, 4, pr, sA));
         pending_adam = l;
@@ -893,9 +916,9 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
     // LN1 backward writes the residual gradient of layer l-1 into the buffer copy layer l+1 used (and layer l-1 then rewrites
     // the rest of that copy): the auxiliary work of layer l+1 - a whole layer behind by now - must have finished with it.
     if (forked && prev_done && hipStreamWaitEvent(S, prev_done, 0) != hipSuccess) { nv_set_error("nv_vit_backward: event wait failed"); return NV_ERR_HIP; }
-    RUN(nv_ln_bwd(dxn1, d, xin, d, st1, st1 + M, p + q.n1g, M, d, g, g, d, G16(l - 1), d, gr + q.n1g, gr + q.n1b, (l > 0) ? gr + T.layer[l - 1].b2 : nullptr,
+    RUN(nv_ln_bwd(dxn1, d, xin, d, st1, st1 + M, p + q.n1g, M, d, g, g, d, G16(l - 1), d, GR(q.n1g), GR(q.n1b), (l > 0) ? GR(T.layer[l - 1].b2) : nullptr,
                   acc, RED3(l), nv_ln_bwd_workspace_bytes(M, d), site_seed(drop_seed, 4 * (l - 1) + 3), (l > 0) ? drop_p : 0.f, stream, ln_reduce));
-    pending_ln1 = l;
+    pending_ln1 = wg ? l : -1;
     prev_done = done;
     layers_here = true;
   }
@@ -917,8 +940,8 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   // released before the main stream was allowed into layer 0's LN1 backward.
   float* est = (float*)(ws + W.est);
   float* pst = (float*)(ws + W.pst);
-  RUN(nv_embed_finish_bwd(g, d, (float*)(ws + W.t), d, est, est + D.T, p + T.pe_g2, B, D.N, d, (float*)(ws + W.dt), d, ws + W.dt16, d, gr + T.pe_g2,
-                          gr + T.pe_b2, gr + T.pe_bias, gr + T.pos, gr + T.cls, acc, RED(1), W.red_bytes, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
+  RUN(nv_embed_finish_bwd(g, d, (float*)(ws + W.t), d, est, est + D.T, p + T.pe_g2, B, D.N, d, (float*)(ws + W.dt), d, ws + W.dt16, d, GR(T.pe_g2),
+                          GR(T.pe_b2), GR(T.pe_bias), GR(T.pos), GR(T.cls), acc, RED(1), W.red_bytes, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
   // patch_dim not a multiple of 8 (reference default 90^3 / p 9 -> P = 729): operands are zero padded to Ppad columns;
   // the weight gradient is produced in a padded scratch matrix and its valid columns copied / added into the arena.
   const void* wpe = (D.P != D.Ppad) ? (const void*)(ws + W.wpe16) : (const void*)(p16 + T.pe_w);
@@ -930,14 +953,18 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   if (pending_ln1 >= 0) RUN(reduce_ln1(pending_ln1));
   if (pending_adam >= 0) { RUN(layer_update(pending_adam)); pending_adam = -1; }                                                // [A] layer 0's weights
   RUN(nv_gemm_bf16(1, 1, D.T, D.Ppad, d, ws + W.dt16, d, wpe, D.Ppad, ws + W.dxp, D.Ppad, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, sA));              // [A] dxp = dt Wpe
+  if (dvideo)       // [A] the gradient w.r.t. the input volume: LayerNorm(P) backward w.r.t. its input, scattered into voxel layout
+    RUN(nv_patch_ln_dx(video, strides5, B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size, pat_w(cfg), cfg->frame_patch_size,
+                       (const float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, p + T.pe_g, dvideo, opts->dvideo_strides5, sA));
+  if (!wg) return NV_OK;      // data-only: serial, nothing to join
   RUN(nv_patch_ln_bwd(video, strides5, B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size,
-                      pat_w(cfg), cfg->frame_patch_size, (float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, gr + T.pe_g, gr + T.pe_b, acc, redA,
+                      pat_w(cfg), cfg->frame_patch_size, (float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, GR(T.pe_g), GR(T.pe_b), acc, redA,
                       redA_bytes, sA));                                                                                         // [A]
   if (D.P != D.Ppad) {
     RUN(nv_gemm_bf16(2, 1, d, D.Ppad, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, ws + W.dwpe, D.Ppad, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-    RUN(nv_copy_2d_f32((float*)(ws + W.dwpe), D.Ppad, d, D.P, gr + T.pe_w, D.P, acc, stream));
+    RUN(nv_copy_2d_f32((float*)(ws + W.dwpe), D.Ppad, d, D.P, GR(T.pe_w), D.P, acc, stream));
   } else {
-    RUN(nv_gemm_bf16(2, 1, d, D.P, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, gr + T.pe_w, D.P, nullptr, nullptr, 0, M16(T.pe_w), D.P, acc, 1.f, 0, 0.f, stream));   // dWpe = dt^T xp
+    RUN(nv_gemm_bf16(2, 1, d, D.P, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, GR(T.pe_w), D.P, nullptr, nullptr, 0, M16(T.pe_w), D.P, acc, 1.f, 0, 0.f, stream));   // dWpe = dt^T xp
   }
   if (forked) RUN(stream_sync(A, S));
   return NV_OK;
@@ -1103,7 +1130,7 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
     return dp_backward_update(cfg, B, video, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, dlogits, hp, dp, head_fused, lscale,
                               drop_p, emb_drop_p, drop_seed, stream, aux_stream);
   RUN(backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, nullptr, hp->accumulate ? 1 : 0, head_fused ? 1 : 0, cfg->depth + 1,
-                    drop_p, emb_drop_p, drop_seed, stream, aux_stream, 1, in ? in->rows_form : 0, fused ? &opt : nullptr, hp->fuse_update));
+                    drop_p, emb_drop_p, drop_seed, stream, aux_stream, 1, in ? in->rows_form : 0, fused ? &opt : nullptr, hp->fuse_update, nullptr));
   if (hp->update && !fused) {
     const long total = nv_vit_param_count(cfg);
     if (hp->loss_scale_state) {      // GradScaler.step / .update (Trainer.py:75-76) on the device: any inf / NaN gradient skips the update and halves the scale

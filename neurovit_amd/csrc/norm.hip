@@ -843,6 +843,112 @@ extern "C" int nv_patch_ln_bwd(const float* video, const long* strides5, int B, 
   return NV_OK;
 }
 
+// Backward of LayerNorm(patch_dim) w.r.t. its INPUT, scattered back into voxel layout (the inverse of the patch gather): the gradient of
+// the encoder's output w.r.t. the volume.  One wave per token, the layout of patch_ln_fwd_kernel: the token's patch is re-gathered from
+// the fp32 volume into registers (xhat from the forward's saved statistics, not from the 16-bit xp), g = dxp[tok, :P] * gamma, and
+//   dx = rstd * (g - mean_k(g) - xhat * mean_k(g * xhat))
+// is written where the forward read x.  Patches tile the volume (the extents are divisible by the patch), so every voxel of dvideo is
+// written exactly once: no clearing pass, no atomics.  dvideo has geometry gd (the volume's extents, its own strides).
+// VEC (the forward gather's conditions, on both views, and a float4-addressable dxp): float4 runs; the scalar form takes any geometry.
+template <bool VEC, int NS>
+__global__ __launch_bounds__(256) void patch_ln_dx_kernel(const float* __restrict__ video, PatchGeom g, PatchGeom gd,
+                                                          const float* __restrict__ dxp, long ldd, const float* __restrict__ mean_in,
+                                                          const float* __restrict__ rstd_in, const float* __restrict__ gamma,
+                                                          float* __restrict__ dvideo) {
+  const int lane = threadIdx.x & 63;
+  const int tok = blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+  if (tok >= g.B * g.N) return;
+  const int b = tok / g.N, n = tok - b * g.N;
+  const float mean = mean_in[tok], rstd = rstd_in[tok];
+  const float* drow = dxp + (long)tok * ldd;
+  const float* xt = video + patch_tok_offset(g, b, n);
+  float* ot = dvideo + patch_tok_offset(gd, b, n);
+  const float inv_p = 1.0f / (float)g.P;
+  if constexpr (VEC) {
+    constexpr int NV = 16;                       // 4 * 64 * 16 = 4096 features at most
+    f32x4 xh[NV], gv[NV];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int k = (lane + 64 * v) * 4;
+      if (k < g.P) {
+        xh[v] = (*reinterpret_cast<const f32x4*>(xt + patch_feat_offset(g, k)) - mean) * rstd;
+        gv[v] = *reinterpret_cast<const f32x4*>(drow + k) * *reinterpret_cast<const f32x4*>(gamma + k);
+      } else {
+        xh[v] = f32x4{0.f, 0.f, 0.f, 0.f};
+        gv[v] = xh[v];
+      }
+      const f32x4 gx = gv[v] * xh[v];
+      s1 += (gv[v][0] + gv[v][1]) + (gv[v][2] + gv[v][3]);
+      s2 += (gx[0] + gx[1]) + (gx[2] + gx[3]);
+    }
+    const float c1 = wave_sum(s1) * inv_p, c2 = wave_sum(s2) * inv_p;
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+      const int k = (lane + 64 * v) * 4;
+      if (k < g.P) *reinterpret_cast<f32x4*>(ot + patch_feat_offset(gd, k)) = (gv[v] - c1 - xh[v] * c2) * rstd;
+    }
+  } else if constexpr (NS > 0) {
+    // any geometry whose patch fits NS elements per lane (the reference's 9^3 = 729 features: NS = 16): one gather into registers
+    float xh[NS], gv[NS];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int v = 0; v < NS; ++v) {
+      const int k = lane + 64 * v;
+      const bool in = k < g.P;
+      xh[v] = in ? (xt[patch_feat_offset(g, k)] - mean) * rstd : 0.f;
+      gv[v] = in ? drow[k] * gamma[k] : 0.f;
+      s1 += gv[v];
+      s2 += gv[v] * xh[v];
+    }
+    const float c1 = wave_sum(s1) * inv_p, c2 = wave_sum(s2) * inv_p;
+#pragma unroll
+    for (int v = 0; v < NS; ++v) {
+      const int k = lane + 64 * v;
+      if (k < g.P) ot[patch_feat_offset(gd, k)] = (gv[v] - c1 - xh[v] * c2) * rstd;
+    }
+  } else {
+    // patches beyond 4096 features: two sweeps, the second gathers again
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = lane; k < g.P; k += 64) {
+      const float x = (xt[patch_feat_offset(g, k)] - mean) * rstd, gk = drow[k] * gamma[k];
+      s1 += gk;
+      s2 += gk * x;
+    }
+    const float c1 = wave_sum(s1) * inv_p, c2 = wave_sum(s2) * inv_p;
+    for (int k = lane; k < g.P; k += 64) {
+      const float x = (xt[patch_feat_offset(g, k)] - mean) * rstd, gk = drow[k] * gamma[k];
+      ot[patch_feat_offset(gd, k)] = (gk - c1 - x * c2) * rstd;
+    }
+  }
+}
+
+extern "C" int nv_patch_ln_dx(const float* video, const long* strides5, int B, int C, int F, int H, int W, int p1, int p2, int pf,
+                              const float* dxp, long ldd, const float* mean, const float* rstd, const float* gamma,
+                              float* dvideo, const long* dstrides5, void* stream) {
+  NV_CHECK_ARG(video && strides5 && dxp && mean && rstd && gamma && dvideo && dstrides5, "nv_patch_ln_dx: null pointer");
+  PatchGeom g, gd;
+  int rc = make_geom(g, strides5, B, C, F, H, W, p1, p2, pf);
+  if (rc) return rc;
+  rc = make_geom(gd, dstrides5, B, C, F, H, W, p1, p2, pf);
+  if (rc) return rc;
+  NV_CHECK_ARG(ldd >= g.P, "nv_patch_ln_dx: ldd=%ld must be >= patch_dim=%d", ldd, g.P);
+  const dim3 grid((g.B * g.N + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  // patch_vec_ok's last condition (a dense token matrix) concerns the forward's output; here dxp only needs float4 rows
+  const bool vec = patch_vec_ok(video, g, g.P) && patch_vec_ok(dvideo, gd, g.P) && nv_aligned16(dxp) && (ldd % 4) == 0 && nv_aligned16(gamma);
+  if (vec)
+    hipLaunchKernelGGL((patch_ln_dx_kernel<true, 0>), grid, block, 0, s, video, g, gd, dxp, ldd, mean, rstd, gamma, dvideo);
+  else if (g.P <= 64 * 16)
+    hipLaunchKernelGGL((patch_ln_dx_kernel<false, 16>), grid, block, 0, s, video, g, gd, dxp, ldd, mean, rstd, gamma, dvideo);
+  else if (g.P <= 64 * 64)
+    hipLaunchKernelGGL((patch_ln_dx_kernel<false, 64>), grid, block, 0, s, video, g, gd, dxp, ldd, mean, rstd, gamma, dvideo);
+  else
+    hipLaunchKernelGGL((patch_ln_dx_kernel<false, 0>), grid, block, 0, s, video, g, gd, dxp, ldd, mean, rstd, gamma, dvideo);
+  NV_CHECK_LAUNCH("nv_patch_ln_dx");
+  return NV_OK;
+}
+
 // --------------------------------------------------------------------------------------- embed finish (A4 + A5)
 // x[b, 0, :] = cls + pos[0];  x[b, 1+i, :] = LN(t[b*N+i]) * gamma + beta + pos[1+i]
 template <int NV>
@@ -949,12 +1055,16 @@ extern "C" int nv_embed_finish_bwd(const float* g, long ldg, const float* t, lon
   const int n = N + 1;
   const long need = nv_embed_finish_bwd_workspace_bytes(B, N, d);
   NV_CHECK_ARG(ws_bytes >= need, "nv_embed_finish_bwd: workspace too small");
+  // all parameter-gradient outputs NULL (the data-only backward): dt / dt16 only
+  const bool params_out = dgamma || dbeta || dbias_pe || dpos || dcls;
+  NV_CHECK_ARG(!params_out || (dgamma && dbeta && dbias_pe && dpos && dcls), "nv_embed_finish_bwd: the parameter gradients are all given or all NULL");
   // g's token rows (row b*n + 1 + i) form one segmented [B*N] row set: a single LN backward over all volumes
   {
     const int rc = ln_bwd_launch(g + ldg, ldg, t, ldt, mean, rstd, gamma, B * N, d, nullptr, dt, lddt, dt16, lddt16, dgamma, dbeta, dbias_pe,
-                                 accumulate, workspace, ws_bytes, 0, 0.f, stream, nullptr, N, 1);
+                                 accumulate, workspace, ws_bytes, 0, 0.f, stream, params_out ? nullptr : NV_LN_NO_REDUCE, N, 1);
     if (rc) return rc;
   }
+  if (!params_out) return NV_OK;
   const long tot = (long)n * d;
   hipLaunchKernelGGL(batch_sum_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, g, ldg, B, n, d, dpos, dcls, accumulate);
   NV_CHECK_LAUNCH("nv_embed_finish_bwd/batch_sum");
@@ -1139,6 +1249,9 @@ extern "C" int nv_head_bwd(const float* dlogits, int B, int C, const float* W, c
   hipLaunchKernelGGL(head_bwd_x_kernel, dim3(B + fill_blocks), dim3(256), (d + 8) * sizeof(float), s, dlogits, C, W, x, row_stride, stats, gamma, d, n,
                      g, ldg, (r16*)g16, ldg16, (float*)workspace, make_drop(drop_seed, drop_p), pool_mean, B, nv_operand_format() == NV_OPERAND_FP16);
   NV_CHECK_LAUNCH("nv_head_bwd/x");
+  // all parameter-gradient outputs NULL (the data-only backward): the data gradient g / g16 is all there is
+  if (!dgamma && !dbeta && !dcolsum && !dW && !dbias) return NV_OK;
+  NV_CHECK_ARG(dgamma && dbeta && dW && dbias, "nv_head_bwd: dgamma, dbeta, dW, dbias are all given or all NULL");
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((3 * d + 31) / 32), dim3(256), 0, s, (const float*)workspace, B, d, 3, dgamma, dbeta,
                      dcolsum, accumulate);
   NV_CHECK_LAUNCH("nv_head_bwd/reduce");

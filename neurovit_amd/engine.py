@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _cabi, ops
-from ._cabi import TrainHparams, VitConfig, VitInput, check, lib
+from ._cabi import BackwardOpts, TrainHparams, VitConfig, VitInput, check, lib
 
 _BYTES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
 
@@ -323,12 +323,15 @@ class VitRuntime:
         self.backward_done = False
         return logits
 
-    def backward(self, dlogits: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: torch.Tensor,
+    def backward(self, dlogits: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: Optional[torch.Tensor],
                  accumulate: bool, stages: Optional[Tuple[int, int]] = None, join_aux: bool = True,
-                 grads16: Optional[torch.Tensor] = None) -> None:
+                 grads16: Optional[torch.Tensor] = None, dvideo: Optional[torch.Tensor] = None, weight_grads: bool = True) -> None:
         """Whole backward, or only stages [first, last] (0 = head, 1+k = layer depth-1-k, depth+1 = embedding).
         join_aux=False (only for ranges before the last stage): the current stream is not made to wait for the auxiliary
-        stream - order the consumer of the range's gradients after `aux_stream_object()` as well."""
+        stream - order the consumer of the range's gradients after `aux_stream_object()` as well.
+        dvideo: fp32 tensor of the forward input's shape (any strides) that receives d loss / d video; written by the call whose
+        stages contain the embedding.  weight_grads=False: the data-only backward - no parameter gradient is produced, `grads`
+        and `grads16` must be None (nv_vit_backward_ex)."""
         rec = self._cur
         assert rec is not None, "backward needs a preceding forward(training=True)"
         if not self.pass_is_live(rec):
@@ -341,6 +344,27 @@ class VitRuntime:
         _cabi.set_operand_format(self.operands)
         if first == 0:
             rec.dlogits = dlogits.contiguous().float()
+        if dvideo is not None or not weight_grads:
+            if dvideo is not None:
+                if rec.keep[0] is not None:
+                    raise NotImplementedError("neurovit_amd: no input gradient of a forward on RAW volumes (vol_sigma): the folded z-score "
+                                              "treats sigma as a constant, so the gradient w.r.t. the raw volume would be wrong")
+                assert dvideo.is_cuda and dvideo.dtype == torch.float32 and dvideo.shape == video.shape and dvideo.device == video.device
+            if not weight_grads:
+                assert grads is None and grads16 is None, "the data-only backward writes no gradient arena"
+            dstrides = None if dvideo is None else ops.strides5(dvideo)      # (kept alive across the call)
+            opts = BackwardOpts(ctypes.sizeof(BackwardOpts), None if dvideo is None else dvideo.data_ptr(),
+                                None if dstrides is None else ctypes.cast(dstrides, ctypes.c_void_p), int(bool(weight_grads)))
+            check(lib.nv_vit_backward_ex(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
+                                         params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
+                                         None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
+                                         int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
+                                         torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
+                                         int(join_aux), int(rec.rows_form), ctypes.byref(opts)),
+                  "nv_vit_backward_ex")
+            if last == self.cfg.depth + 1:
+                rec.done = True
+            return
         # grads16: bf16 arena (element offsets of `grads`) that also receives the Linear weight gradients, rounded, straight from
         # their GEMMs - the data-parallel message buffer (mirrored_ranges() lists what lands there)
         check(lib.nv_vit_backward_stages16(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),

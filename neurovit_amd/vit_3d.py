@@ -209,7 +209,8 @@ class PatchRearrange(nn.Module):
 class _ViTFunction(torch.autograd.Function):
     """Whole-encoder autograd node.  Parameters are passed as inputs only so autograd knows the output
     depends on them; their gradients are written by the engine directly into the module's gradient
-    arena (which `param.grad` views), so backward returns None for them (no per-tensor accumulate copies)."""
+    arena (which `param.grad` views), so backward returns None for them (no per-tensor accumulate copies).
+    The gradient w.r.t. `video` is returned in its slot when autograd asks for it (ctx.needs_input_grad[1])."""
 
     @staticmethod
     def forward(ctx, module, video, need_grad, extra, *params):
@@ -229,10 +230,15 @@ class _ViTFunction(torch.autograd.Function):
                 "until one whole backward of it has run; a second backward (retain_graph) after another training forward or a train "
                 "step of the same module finds it refilled.")
         rt._cur = rec                 # several passes may be pending (siamese / two-forward losses): each runs against its own workspace
-        ctx.module._run_backward(dlogits)
+        dvideo = None
+        if ctx.needs_input_grad[1]:
+            # the input's own strides when they describe a dense, non-overlapping tensor (the [B, H, W, D] -> [B, 1, D, H, W] permute view
+            # of ViT3DEncoder: the kernel then writes the memory order it read), contiguous otherwise
+            dvideo = torch.empty_like(rec.video, memory_format=torch.preserve_format)
+        ctx.module._run_backward(dlogits, dvideo)
         if rt._last is not None and rt._last[2] is rec.ws:
             rt.backward_done = True   # the Grad-CAM taps read the MOST RECENT forward's workspace
-        return (None, None, None, None) + (None,) * len(ctx.module._plist)
+        return (None, dvideo, None, None) + (None,) * len(ctx.module._plist)
 
 
 class ViT(nn.Module):
@@ -496,19 +502,25 @@ class ViT(nn.Module):
                                              time_points=time_points)
         return self._last_logits
 
-    def _run_backward(self, dlogits):
-        grads = self.flat_gradients()
+    def _run_backward(self, dlogits, dvideo=None):
+        """Parameter gradients of every parameter that requires one; dvideo (or None): receives d loss / d video.  With no parameter
+        requiring a gradient (a frozen model fed an input that requires one) the data-only backward runs: no gradient arena, no p.grad."""
         trainable = [i for i, p in enumerate(self._plist) if p.requires_grad]
+        if not trainable:
+            if dvideo is not None:
+                self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False)
+            return
+        grads = self.flat_gradients()
         state = [self._plist[i].grad for i in trainable]
         if all(g is None for g in state):
-            self._backward_into(dlogits, grads, accumulate=False)
+            self._backward_into(dlogits, grads, accumulate=False, dvideo=dvideo)
             for i in trainable:
                 self._plist[i].grad = self._grad_view(i)
         elif all(g is not None and g.data_ptr() == self._grad_view(i).data_ptr() for g, i in zip(state, trainable)):
-            self._backward_into(dlogits, grads, accumulate=True)
+            self._backward_into(dlogits, grads, accumulate=True, dvideo=dvideo)
         else:   # foreign .grad tensors: compute into a scratch arena and add
             scratch = torch.empty_like(grads)
-            self._rt.backward(dlogits, self._arena, self._shadow, scratch, accumulate=False)
+            self._rt.backward(dlogits, self._arena, self._shadow, scratch, accumulate=False, dvideo=dvideo)
             off, num, _ = self._layout
             for i in trainable:
                 g = scratch[off[i]:off[i] + num[i]].view(self._plist[i].shape)
@@ -532,10 +544,10 @@ class ViT(nn.Module):
         self._mirrored = sorted(out)          # the layout never changes for a constructed module
         return self._mirrored
 
-    def _backward_into(self, dlogits, grads, accumulate):
+    def _backward_into(self, dlogits, grads, accumulate, dvideo=None):
         sync = self._grad_sync
         if sync is None:
-            self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate)
+            self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, dvideo=dvideo)
             return
         from .parallel import bucket_stages
         sync.begin()
@@ -551,7 +563,7 @@ class ViT(nn.Module):
             # intermediate buckets do not stall the main stream on the auxiliary (weight-gradient) stream: the bucket's
             # all-reduce is ordered after both streams instead
             self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, stages=(first, last),
-                              join_aux=(last == last_stage), grads16=msg)
+                              join_aux=(last == last_stage), grads16=msg, dvideo=dvideo if last == last_stage else None)
             sync.bucket_ready(grads, begin, end, also_after=None if last == last_stage else self._rt.aux_stream_object(grads.device))
         sync.finish()
 
@@ -577,9 +589,28 @@ class ViT(nn.Module):
     def forward(self, video, vol_sigma=None, time_points=0):
         """video [B, C, F, H, W] -> [B, num_classes] (vit_3d.py:112-126).  Beyond the reference (both optional):
         vol_sigma [B] marks `video` as RAW volumes whose per-volume z-score (std + 1e-8) is folded into the patch LayerNorm;
-        time_points = T > 0 takes a contiguous 4D batch [B, H, W, D, T] and encodes its B*T volumes without the regroup copy."""
+        time_points = T > 0 takes a contiguous 4D batch [B, H, W, D, T] and encodes its B*T volumes without the regroup copy.
+
+        Gradient w.r.t. the input: when `video` requires grad (and grad mode is on) the forward records a graph even if every
+        parameter is frozen, and backward returns d loss / d video (x.grad, torch.autograd.grad, captum).  It is computed in the
+        training arithmetic (16-bit operands: `operands`, bf16 or fp16; `eval_precision = "fp32"` does not apply to forwards that
+        record a graph), dropout masks replay as for parameter gradients.  Parameter gradients follow requires_grad as before -
+        torch.autograd.grad(out, video) on a trainable model still fills p.grad - so freeze the model for attribution: a model
+        without trainable parameters runs the cheaper data-only backward and touches no p.grad.  Not available (NotImplementedError)
+        with vol_sigma, time_points or the fp8 training forward."""
         self.check_video(video, time_points)
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._plist)
+        input_grad = torch.is_grad_enabled() and video.requires_grad
+        need_grad = input_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self._plist))
+        if input_grad:
+            if vol_sigma is not None:
+                raise NotImplementedError("neurovit_amd.ViT: no gradient w.r.t. RAW volumes (vol_sigma / forward_raw): the folded z-score treats "
+                                          "sigma as a constant - normalise the volume first and differentiate w.r.t. that")
+            if time_points:
+                raise NotImplementedError("neurovit_amd.ViT: no input gradient through the fused 4D input form (time_points) - pass the "
+                                          "[B*T, C, F, H, W] volumes instead")
+            if self._fp8 is not None and self.fp8_training:
+                raise NotImplementedError("neurovit_amd.ViT: no input gradient through the fp8 training forward - disable_fp8() or "
+                                          "enable_fp8(training=False) first")
         if time_points and need_grad:
             raise NotImplementedError("neurovit_amd.ViT: the fused 4D input form is forward-only (frozen encoder of the 4D model)")
         return _ViTFunction.apply(self, video.float(), need_grad, (vol_sigma, int(time_points)), *self._plist)
