@@ -286,6 +286,27 @@ int nv_attn_fwd_o8(const void* qkv, long ld_qkv, int B, int n, int heads, int di
 int nv_attn_bwd(const void* qkv, long ld_qkv, const void* out, const void* dout, long ld_out, const float* lse, int B, int n,
                 int heads, int dim_head, float scale, float* delta, void* dqkv, long ld_dqkv, unsigned long drop_seed,
                 float drop_p, void* stream);
+/* (revision 8) attention probabilities P = softmax(scale q k^T) of one layer, recomputed from its qkv - the output of the reference's
+ * `attend` (vit_3d.py:54) in its 'b h n d' head order.  qkv_f32 = 0: qkv in the 16-bit operand format (as nv_attn_fwd; dim_head a
+ * multiple of 8 up to 128), 1: fp32 (as nv_attn_fwd_f32; a multiple of 4 up to 128).  Row statistics are computed here from q and k
+ * (no lse needed).  out fp32, contiguous:
+ *   fusion NV_ATTN_PER_HEAD: [B, heads, R, n];  NV_ATTN_FUSE_MEAN / _MAX / _MIN: [B, R, n] = mean / max / min over the heads, one launch
+ *   rows NV_ATTN_ROWS_ALL: R = n;  NV_ATTN_ROWS_CLS: R = 1 (row 0, the cls token's)
+ * A probability has the same bits in every form (max / min fusion = the reduction of the per-head output, exactly). */
+#define NV_ATTN_PER_HEAD 0
+#define NV_ATTN_FUSE_MEAN 1
+#define NV_ATTN_FUSE_MAX 2
+#define NV_ATTN_FUSE_MIN 3
+#define NV_ATTN_ROWS_ALL 0
+#define NV_ATTN_ROWS_CLS 1
+int nv_attn_probs(int qkv_f32, const void* qkv, long ld_qkv, int B, int n, int heads, int dim_head, float scale, int fusion, int rows,
+                  float* out, void* stream);
+/* (revision 8) attention rollout: out [B, n - 1] = the patch-token entries (token order) of u A^_{L-1} ... A^_0 with
+ * A^_l = (A_l + I) / (rowsum(A_l) + 1) row-wise - the head-fused (A + I) / 2, row-renormalised rule, exact also for max / min fusion.
+ * maps: HOST array [L] of device pointers to head-fused all-rows maps [B, n, n] (nv_attn_probs).  u = e_0 (the cls row) or, with
+ * start_mean = 1, the mean of all rows (pool = 'mean').  Two memory-bound launches per layer; workspace nv_attn_rollout_workspace_bytes. */
+long nv_attn_rollout_workspace_bytes(int B, int n);
+int nv_attn_rollout(const float* const* maps, int L, int B, int n, int start_mean, float* out, void* workspace, long ws_bytes, void* stream);
 int nv_stream_sync(void* from, void* to);   /* stream `to` waits for everything enqueued so far on `from` (pooled events) */
 int nv_spin_us(int microseconds, void* stream);   /* one wave that keeps `stream` busy for the given time (<= 50 ms): stream-placement probes */
 
@@ -415,10 +436,23 @@ long nv_vit_workspace_offset(const nv_vit_config* cfg, int B, int training, cons
  *                        of sample b - no regroup copy (nv_patch_ln_fwd_4d; T % 4 == 0, channels = 1); strides5 is ignored;
  *   rows_form          : which rows of the LAST block's out-projection / LayerNorm / FeedForward are computed - see nv_vit_set_cls_tail.
  *                        A backward must be given the rows_form (and dropout) of its forward. */
+/* (revision 8) attention probabilities of the forward, exported behind each layer's attention launch (explainability: the output of
+ * the reference's `attend` = nn.Softmax, vit_3d.py:54, which the fused attention kernels never materialise; see nv_attn_probs).
+ * maps: HOST array [depth] of device pointers, NULL = that layer is not exported; each receives the nv_attn_probs output of the layer
+ * (fusion / rows below) for the forward's B volumes.  Pre-dropout probabilities, whatever the dropout of the forward.  The export only
+ * reads the layer's qkv buffer: logits, workspace and every later backward are bit-identical to a forward without it.
+ * struct_size = sizeof(nv_vit_attn_export): checked.  The fp8 forwards refuse an export (NV_ERR_ARG). */
+typedef struct nv_vit_attn_export {
+  int struct_size;
+  float** maps;
+  int fusion;      /* NV_ATTN_PER_HEAD, NV_ATTN_FUSE_MEAN / _MAX / _MIN */
+  int rows;        /* NV_ATTN_ROWS_ALL, NV_ATTN_ROWS_CLS */
+} nv_vit_attn_export;
 typedef struct nv_vit_input {
   const float* vol_sigma;
   int time_points;
   int rows_form;   /* last block under pool='cls': 0 = process default (nv_vit_set_cls_tail), 1 = every row, 2 = cls rows when eligible */
+  const nv_vit_attn_export* attn_export;   /* (revision 8) NULL = no export: exactly the launches of a forward without this field */
 } nv_vit_input;
 int nv_vit_forward_in(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5,
                       const nv_vit_input* in, const float* params, const void* params16, void* workspace, long ws_bytes,
@@ -585,7 +619,7 @@ int nv_cu_census(unsigned* out, int blocks, int threads, int lds_bytes, int hold
 
 /* ABI revision of this header: bumped whenever a struct gains a field or an entry point changes its argument list (the list is in
  * INTEGRATION.md "ABI revisions").  A caller built against revision R must refuse a library whose nv_abi_version() != R. */
-#define NV_ABI_VERSION 7
+#define NV_ABI_VERSION 8
 int nv_abi_version(void);
 /* dst[b .. b + len) = bf16(src[b .. b + len)) for `count` element ranges (HOST arrays begins / lens; any count) */
 int nv_cast_ranges_bf16(const float* src, void* dst, const long* begins, const long* lens, int count, void* stream);

@@ -137,10 +137,6 @@ class NeuroEncoder(nn.Module):
         The [B,n,d] activation and gradient never leave the device: `nv_gradcam_reduce` (csrc/gradcam.hip) turns them
         into the normalised G^3 map in one launch, and only those G^3 floats cross PCIe for the percentile / upsampling."""
         from . import ops
-        size = self.config['TRAINING_VIT_INPUT_SIZE']
-        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
-        keep_percent = self.config['GRADCAM_THRESHOLD']
-
         logits = self.forward(x)
         predicted = logits.argmax(dim=1)
         logits.backward(gradient=F.one_hot(predicted, logits.shape[1]).to(logits.dtype), retain_graph=True)
@@ -153,13 +149,35 @@ class NeuroEncoder(nn.Module):
         else:
             token_map, _ = ops.gradcam_reduce(vit.last_attn_norm_output_raw(), vit.last_attn_norm_grad_raw())
             token_map = token_map.cpu()
-        grid = token_map.reshape(1, cells, cells, cells)               # one sample, as in the reference
+        return self._token_map_to_volume(token_map), predicted
 
-        # keep the top `keep_percent` % of the cells (linear-interpolated percentile, as numpy.percentile), zero the rest
+    def _token_map_to_volume(self, token_map):
+        """[1, G^3] normalised CPU map of the patch tokens -> [S, S, S]: the top GRADCAM_THRESHOLD % of the cells (linear-interpolated
+        percentile, as numpy.percentile), the rest zeroed, trilinear upsampling to the volume (NeuroEncoder.py:120-131)."""
+        size = self.config['TRAINING_VIT_INPUT_SIZE']
+        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
+        keep_percent = self.config['GRADCAM_THRESHOLD']
+        grid = token_map.reshape(1, cells, cells, cells)               # one sample, as in the reference
         cut = torch.quantile(grid.double().flatten(), 1.0 - keep_percent / 100.0).to(grid.dtype)
         sparse = torch.where(grid >= cut, grid, torch.zeros_like(grid))
         volume = F.interpolate(sparse[None], size=(size,) * 3, mode='trilinear', align_corners=False)
-        return volume[0, 0], predicted
+        return volume[0, 0]
+
+    def get_attention_rollout(self, x):
+        """Attention rollout of the ViT3D encoder on the patch grid, in the form of get_attention_map: (map[S,S,S] on the CPU, class_idx),
+        so visualize_slice and Grad-CAM plotting code take it unchanged.  The cls row of the head-averaged, identity-augmented attention
+        multiplied over the layers (ViT.attention_rollout: one forward in the module's current mode and precision, no backward pass),
+        min-max normalised over the map, thresholded and upsampled as get_attention_map does."""
+        if self.config['TRAINING_DIM'] != 3:
+            raise NotImplementedError("get_attention_rollout: 3D model only (as get_attention_map, one volume [1, H, W, D])")
+        vit = self.volume_encoder.vit3d
+        volume = x.to(self.device)
+        with torch.no_grad():
+            logits, rollout = vit.attention_rollout(volume.permute(0, 3, 1, 2).unsqueeze(1))     # ViT3DEncoder.forward's view
+        predicted = logits.argmax(dim=1)
+        token_map = rollout.cpu()
+        token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
+        return self._token_map_to_volume(token_map), predicted
 
     def visualize_slice(self, cam_3d, original_volume):
         """One 2-D slice of the volume and of its CAM along GRADCAM_SLICE_DIM at GRADCAM_SLICE_IDX

@@ -29,8 +29,19 @@ class VitConfig(ctypes.Structure):
 
 
 class VitInput(ctypes.Structure):
-    """struct nv_vit_input (neurovit_hip.h): optional input forms of nv_vit_forward_in / nv_vit_forward_fp8."""
-    _fields_ = [("vol_sigma", ctypes.c_void_p), ("time_points", ctypes.c_int), ("rows_form", ctypes.c_int)]
+    """struct nv_vit_input (neurovit_hip.h): optional input forms of nv_vit_forward_in / nv_vit_forward_fp8, and (revision 8) the
+    attention-probability export (a pointer to an AttnExport, or None)."""
+    _fields_ = [("vol_sigma", ctypes.c_void_p), ("time_points", ctypes.c_int), ("rows_form", ctypes.c_int), ("attn_export", ctypes.c_void_p)]
+
+
+class AttnExport(ctypes.Structure):
+    """struct nv_vit_attn_export (neurovit_hip.h, revision 8): per-layer output pointers (a HOST array, NULL = layer not exported),
+    the head fusion (ATTN_FUSIONS) and the rows (ATTN_ROWS) of the probabilities a forward writes behind each attention launch."""
+    _fields_ = [("struct_size", ctypes.c_int), ("maps", ctypes.c_void_p), ("fusion", ctypes.c_int), ("rows", ctypes.c_int)]
+
+
+ATTN_FUSIONS = {None: 0, "mean": 1, "max": 2, "min": 3}     # NV_ATTN_PER_HEAD, NV_ATTN_FUSE_MEAN / _MAX / _MIN
+ATTN_ROWS = {"all": 0, "cls": 1}                            # NV_ATTN_ROWS_ALL / NV_ATTN_ROWS_CLS
 
 
 class TrainHparams(ctypes.Structure):
@@ -61,7 +72,7 @@ class BackwardOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("dvideo", ctypes.c_void_p), ("dvideo_strides5", ctypes.c_void_p), ("weight_grads", ctypes.c_int)]
 
 
-ABI_VERSION = 7      # NV_ABI_VERSION of the header this binding was written against (checked at load time)
+ABI_VERSION = 8      # NV_ABI_VERSION of the header this binding was written against (checked at load time)
 
 
 def parse_header(path: str = HEADER) -> Dict[str, Tuple[object, List[object]]]:

@@ -290,6 +290,25 @@ extern "C" int nv_vit_forward(const nv_vit_config* cfg, int B, const float* vide
   return nv_vit_forward_in(cfg, B, video, shape5, strides5, nullptr, params, params16, workspace, ws_bytes, training, drop_p, emb_drop_p, drop_seed, logits, stream);
 }
 
+// Attention-probability export (nv_vit_attn_export, revision 8): queued right behind a layer's attention launch, while its qkv buffer
+// still holds that layer's values (the inference layouts reuse one qkv buffer for every layer).  It only reads qkv.
+static const nv_vit_attn_export* attn_export_of(const nv_vit_input* in) { return in ? in->attn_export : nullptr; }
+static int check_attn_export(const nv_vit_input* in, const char* who) {
+  const nv_vit_attn_export* ex = attn_export_of(in);
+  if (!ex) return NV_OK;
+  NV_CHECK_ARG(ex->struct_size == (int)sizeof(nv_vit_attn_export), "%s: nv_vit_attn_export.struct_size=%d, expected %d (ABI revision %d)", who,
+               ex->struct_size, (int)sizeof(nv_vit_attn_export), NV_ABI_VERSION);
+  NV_CHECK_ARG(ex->maps, "%s: nv_vit_attn_export.maps is NULL", who);
+  NV_CHECK_ARG(ex->fusion >= NV_ATTN_PER_HEAD && ex->fusion <= NV_ATTN_FUSE_MIN && (ex->rows == NV_ATTN_ROWS_ALL || ex->rows == NV_ATTN_ROWS_CLS),
+               "%s: nv_vit_attn_export fusion=%d / rows=%d out of range", who, ex->fusion, ex->rows);
+  return NV_OK;
+}
+static int export_layer(const nv_vit_input* in, int l, int qkv_f32, const void* qkv, const Dims& D, int B, float scale, void* stream) {
+  const nv_vit_attn_export* ex = attn_export_of(in);
+  if (!ex || !ex->maps[l]) return NV_OK;
+  return nv_attn_probs(qkv_f32, qkv, 3L * D.inner, B, D.n, D.heads, D.dh, scale, ex->fusion, ex->rows, ex->maps[l], stream);
+}
+
 static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                            const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
                            unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16 = nullptr, const float* fold32 = nullptr);
@@ -346,6 +365,7 @@ static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, 
                shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward: workspace too small (%ld < %ld)", ws_bytes, W.total);
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params) && nv_aligned16(params16), "nv_vit_forward: alignment");
+  RUN(check_attn_export(in, "nv_vit_forward"));
   char* ws = (char*)workspace;
   const float* p = params;
   const r16* p16 = (const r16*)params16;
@@ -399,6 +419,7 @@ static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, 
     }
     have_in16 = false;
     RUN(nv_attn_fwd(ws + w.qkv, 3 * D.inner, B, D.n, D.heads, D.dh, scale, ws + w.ao, D.inner, (float*)(ws + w.lse), site_seed(drop_seed, 4 * l + 0), drop_p, stream));
+    RUN(export_layer(in, l, 0, ws + w.qkv, D, B, scale, stream));
     if (tail && l == D.L - 1) {
       // cls rows only (row b of the small problem = row b * n of the buffers); LN2 statistics land at st2[0 .. B) / st2[M .. M + B)
       const long rs = D.n;
@@ -461,6 +482,7 @@ extern "C" int nv_vit_forward_f32(const nv_vit_config* cfg, int B, const float* 
                  shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward_f32: workspace too small (%ld < %ld)", ws_bytes, W.total);
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params), "nv_vit_forward_f32: alignment");
+  RUN(check_attn_export(in, "nv_vit_forward_f32"));
   char* ws = (char*)workspace;
   const float* p = params;
   const float eps = cfg->ln_eps;
@@ -490,6 +512,7 @@ extern "C" int nv_vit_forward_f32(const nv_vit_config* cfg, int B, const float* 
     RUN(nv_ln_fwd_f32(xin, d, M, d, p + q.n1g, p + q.n1b, eps, F32(W.xn1), d, nullptr, nullptr, stream));
     RUN(nv_gemm_f32(0, M, 3 * D.inner, d, F32(W.xn1), d, p + q.wqkv, d, F32(W.qkv), 3 * D.inner, nullptr, nullptr, 0, stream));
     RUN(nv_attn_fwd_f32(F32(W.qkv), 3 * D.inner, B, D.n, D.heads, D.dh, scale, F32(W.ao), D.inner, stream));
+    RUN(export_layer(in, l, 1, F32(W.qkv), D, B, scale, stream));
     if (l == D.L - 1 && cls_tail_wanted(D, 0, 0.f, in ? in->rows_form : 0)) {
       // pool = 'cls' (NeuroEncoder.py:194): behind the last attention only the B cls rows reach the head - the last block's
       // out-projection, LayerNorm and FeedForward run on those rows as strided views (row stride n); same values for the logits
@@ -564,6 +587,7 @@ extern "C" int nv_vit_forward_fp8(const nv_vit_config* cfg, int B, const float* 
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward_fp8: workspace too small (%ld < %ld)", ws_bytes, W.total);
   NV_CHECK_ARG(D.d % 128 == 0 && D.m % 128 == 0, "nv_vit_forward_fp8: dim and mlp_dim must be multiples of 128");
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params) && nv_aligned16(params16) && nv_aligned16(params8), "nv_vit_forward_fp8: alignment");
+  NV_CHECK_ARG(!attn_export_of(in), "nv_vit_forward_fp8: no attention-probability export on the fp8 path");
   char* ws = (char*)workspace;
   const float* p = params;
   const r16* p16 = (const r16*)params16;
@@ -649,6 +673,7 @@ extern "C" int nv_vit_forward_fp8_train(const nv_vit_config* cfg, int B, const f
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward_fp8_train: workspace too small (%ld < %ld): the training layout is needed", ws_bytes, W.total);
   NV_CHECK_ARG(D.d % 128 == 0 && D.m % 128 == 0, "nv_vit_forward_fp8_train: dim and mlp_dim must be multiples of 128 (got %d, %d)", D.d, D.m);
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params) && nv_aligned16(params16) && nv_aligned16(params8), "nv_vit_forward_fp8_train: alignment");
+  NV_CHECK_ARG(!attn_export_of(in), "nv_vit_forward_fp8_train: no attention-probability export on the fp8 path");
   char* ws = (char*)workspace;
   const float* p = params;
   const r16* p16 = (const r16*)params16;

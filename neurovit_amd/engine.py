@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _cabi, ops
-from ._cabi import BackwardOpts, TrainHparams, VitConfig, VitInput, check, lib
+from ._cabi import AttnExport, BackwardOpts, TrainHparams, VitConfig, VitInput, check, lib
 
 _BYTES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
 
@@ -142,9 +142,10 @@ class VitRuntime:
         ref = self._holder.get(rec.ws.data_ptr())
         return ref is not None and ref() is rec
 
-    def _input_form(self, video: torch.Tensor, vol_sigma, time_points: int, rows_form: int = 0):
+    def _input_form(self, video: torch.Tensor, vol_sigma, time_points: int, rows_form: int = 0, attn_export: Optional[AttnExport] = None):
         """(B, nv_vit_input or None) after checking the extents: plain [B, C, F, H, W] view, or (time_points > 0) a contiguous
-        4D batch [B / T, H, W, D, T]; vol_sigma marks RAW volumes (z-score folded into the patch LayerNorm)."""
+        4D batch [B / T, H, W, D, T]; vol_sigma marks RAW volumes (z-score folded into the patch LayerNorm).
+        attn_export (make_attn_export): the attention probabilities this forward writes behind each attention launch."""
         if not video.is_cuda:
             raise RuntimeError("neurovit_amd: ViT forward needs a CUDA/HIP tensor on MI355X - there is no CPU fallback")
         assert video.dtype == torch.float32 and video.dim() == 5
@@ -161,14 +162,30 @@ class VitRuntime:
                 raise ValueError(f"neurovit_amd: video of shape {tuple(video.shape)} does not match the model's "
                                  f"[B, channels, frames, height, width] = [B, {', '.join(map(str, want))}]")
             B = video.shape[0]
-        if vol_sigma is None and not time_points and not rows_form:
+        if vol_sigma is None and not time_points and not rows_form and attn_export is None:
             return B, None
         if vol_sigma is not None:
             assert vol_sigma.is_cuda and vol_sigma.dtype == torch.float32 and vol_sigma.numel() == video.shape[0] and vol_sigma.is_contiguous()
-        return B, VitInput(None if vol_sigma is None else vol_sigma.data_ptr(), int(time_points), int(rows_form))
+        return B, VitInput(None if vol_sigma is None else vol_sigma.data_ptr(), int(time_points), int(rows_form),
+                           None if attn_export is None else ctypes.cast(ctypes.pointer(attn_export), ctypes.c_void_p))
+
+    def make_attn_export(self, B: int, layers, head_fusion: Optional[str], rows: str, device):
+        """(nv_vit_attn_export, {layer: fp32 map}) for a forward of B volumes: per head [B, heads, R, n] or head-fused [B, R, n],
+        R = n (rows "all") or 1 (rows "cls").  The struct holds raw pointers: keep the maps (and the struct) alive across the call."""
+        c = self.cfg
+        H, Wd, p1, p2 = image_hw(c)
+        n = (c.frames // c.frame_patch_size) * (H // p1) * (Wd // p2) + 1
+        R = 1 if rows == "cls" else n
+        shape = (B, c.heads, R, n) if head_fusion is None else (B, R, n)
+        maps = {int(l): torch.empty(shape, dtype=torch.float32, device=device) for l in layers}
+        ptrs = (ctypes.c_void_p * c.depth)(*[maps[l].data_ptr() if l in maps else None for l in range(c.depth)])
+        ex = AttnExport(ctypes.sizeof(AttnExport), ctypes.cast(ptrs, ctypes.c_void_p), _cabi.ATTN_FUSIONS[head_fusion], _cabi.ATTN_ROWS[rows])
+        ex._ptrs = ptrs                                   # the host pointer array lives as long as the struct
+        return ex, maps
 
     def forward(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, training: bool,
-                dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, time_points: int = 0, rows_form: Optional[int] = None) -> torch.Tensor:
+                dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, time_points: int = 0, rows_form: Optional[int] = None,
+                attn_export: Optional[AttnExport] = None) -> torch.Tensor:
         """video: [B, C, F, H, W] fp32 view (any strides).  Returns logits [B, num_classes] fp32.
         dropout = (p of the blocks, p of the embedding, seed) - (0, 0, *) in eval mode.
         vol_sigma / time_points: the optional input forms of nv_vit_forward_in (raw volumes; contiguous 4D batch).
@@ -176,7 +193,7 @@ class VitRuntime:
         None = this runtime's default (`self.rows_form`: the process default unless NEUROVIT_CLS_TAIL=0)."""
         rows_form = self.rows_form if rows_form is None else int(rows_form)
         _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, time_points, rows_form)
+        B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
         ws = self._training_workspace(B, video.device) if training else self.workspace(B, training, video.device)
         logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
         check(lib.nv_vit_forward_in(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
@@ -213,11 +230,11 @@ class VitRuntime:
         return dict(fold16=f16, fold32=f32)
 
     def forward_lnfold(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, fold, vol_sigma=None, time_points: int = 0,
-                       rows_form: Optional[int] = None) -> torch.Tensor:
+                       rows_form: Optional[int] = None, attn_export: Optional[AttnExport] = None) -> torch.Tensor:
         """Inference forward (no dropout) whose blocks run without LayerNorm launches: nv_vit_forward_lnfold."""
         rows_form = self.rows_form if rows_form is None else int(rows_form)
         _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, time_points, rows_form)
+        B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
         ws = self.workspace(B, False, video.device)
         logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
         check(lib.nv_vit_forward_lnfold(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
@@ -233,10 +250,11 @@ class VitRuntime:
         return logits
 
     # ------------------------------------------------------------------ fp32 inference (the reference's fp32 validate, Trainer.py:101-118)
-    def forward_f32(self, video: torch.Tensor, params: torch.Tensor, vol_sigma=None, time_points: int = 0) -> torch.Tensor:
+    def forward_f32(self, video: torch.Tensor, params: torch.Tensor, vol_sigma=None, time_points: int = 0,
+                    attn_export: Optional[AttnExport] = None) -> torch.Tensor:
         """Inference forward with every operand in fp32 (weights straight from the fp32 arena, contractions on the fp32 MFMA):
         logits within 1e-5 of the reference's CPU fp32 forward instead of the bf16 path's 1e-3 ... 7e-3.  Eval mode only."""
-        B, inp = self._input_form(video, vol_sigma, time_points, self.rows_form)
+        B, inp = self._input_form(video, vol_sigma, time_points, self.rows_form, attn_export)
         ws = self.workspace(B, 2, video.device)
         logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
         check(lib.nv_vit_forward_f32(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),

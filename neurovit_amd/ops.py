@@ -300,6 +300,39 @@ def attn_fwd_o8(qkv: torch.Tensor, B: int, n: int, heads: int, out_scale: float,
     return out
 
 
+def attn_probs(qkv: torch.Tensor, B: int, n: int, heads: int, dim_head: int = 64, head_fusion: Optional[str] = None, rows: str = "all",
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax(q k^T / sqrt(dh)) of a qkv buffer [B*n, 3*inner] (the operand format, or fp32) -> fp32 [B, heads, R, n] (head_fusion None)
+    or [B, R, n] (head_fusion "mean" / "max" / "min"), R = n (rows "all") or 1 (rows "cls"): nv_attn_probs."""
+    _need_cuda(qkv)
+    assert qkv.stride(1) == 1 and qkv.dtype in (torch.float32, op16())
+    fusion, form = _cabi.ATTN_FUSIONS[head_fusion], _cabi.ATTN_ROWS[rows]
+    R = 1 if rows == "cls" else n
+    shape = (B, heads, R, n) if head_fusion is None else (B, R, n)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=qkv.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    check(lib.nv_attn_probs(int(qkv.dtype == torch.float32), _p(qkv), qkv.stride(0), B, n, heads, dim_head, dim_head ** -0.5, fusion, form,
+                            _p(out), _stream()), "nv_attn_probs")
+    return out
+
+
+def attn_rollout(maps, start_mean: bool = False) -> torch.Tensor:
+    """Attention rollout over head-fused all-rows maps [B, n, n] (layer 0 first): [B, n - 1] = the patch-token entries of
+    u A^_{L-1} ... A^_0, A^ = (A + I) / (rowsum(A) + 1); u = the cls row, or the mean of the rows (start_mean): nv_attn_rollout."""
+    _need_cuda(*maps)
+    B, n, _ = maps[0].shape
+    for m in maps:
+        assert m.shape == (B, n, n) and m.dtype == torch.float32 and m.is_contiguous()
+    ptrs = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+    nb = lib.nv_attn_rollout_workspace_bytes(B, n)
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=maps[0].device)
+    out = torch.empty((B, n - 1), dtype=torch.float32, device=maps[0].device)
+    check(lib.nv_attn_rollout(ctypes.cast(ptrs, ctypes.c_void_p), len(maps), B, n, int(bool(start_mean)), _p(out), _p(ws), nb, _stream()),
+          "nv_attn_rollout")
+    return out
+
+
 def attn_bwd(qkv, out, dout, lse, B, n, heads, dim_head=64, drop_seed=0, drop_p=0.0):
     inner = heads * dim_head
     dqkv = torch.empty((B * n, 3 * inner), dtype=op16(), device=qkv.device)

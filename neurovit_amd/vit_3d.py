@@ -161,6 +161,7 @@ class Attention(nn.Module):
             raise NotImplementedError("neurovit_amd: dim_head must be a multiple of 8 up to 128 (64, the vit_3d.py:78 default and "
                                       "the only value the NeuroEncoder path uses, runs the MFMA attention kernels; the others scalar ones)")
         p = float(self.dropout.p)
+        self._attend_hooks(x)
         if isinstance(self.to_out, nn.Identity):
             # heads == 1, dim_head == dim: no projection and no trailing dropout (vit_3d.py:43-46) - the same kernels with the
             # identity as the weight (x I + 0 is exact) and the output-dropout site off
@@ -171,6 +172,31 @@ class Attention(nn.Module):
         seeds = (_new_seed(p, self.training), _new_seed(p, self.training))
         return _AttentionFn.apply(x, self.norm.weight, self.norm.bias, self.to_qkv.weight, self.to_out[0].weight, self.to_out[0].bias,
                                   self.heads, self.dim_head, p, seeds)
+
+
+    def _attend_hooks(self, x):
+        """Forward hooks on `attend` (nn.Softmax, vit_3d.py:54): the fused kernels never materialise its output, so with hooks registered
+        the probabilities are recomputed from the same qkv (nv_attn_probs, fp32 [B, heads, n, n], pre-dropout) and the hooks are called
+        with them as hook(attend, (), P), before the attention itself runs."""
+        from torch.nn.modules import module as _module
+        if self.attend._forward_pre_hooks:
+            raise NotImplementedError("neurovit_amd.Attention: forward pre-hooks on `attend` are not supported - the score matrix is never "
+                                      "materialised; register a forward hook to read the probabilities")
+        hooks = list(_module._global_forward_hooks.items()) + list(self.attend._forward_hooks.items())
+        if not hooks:
+            return
+        if x.dim() != 3:
+            raise ValueError("neurovit_amd.Attention: expected x of shape [batch, tokens, dim]")
+        B, n, _ = x.shape
+        x2, _ = _as_rows(x.detach())
+        xn, _ = ops.ln_fwd(x2, self.norm.weight.detach(), self.norm.bias.detach())
+        qkv = ops.gemm(ops.NT, ops.EPI_STORE_BF16, xn, _w16(self.to_qkv.weight))
+        P = ops.attn_probs(qkv, B, n, self.heads, self.dim_head)
+        for hid, hook in hooks:
+            result = hook(self.attend, (), {}, P) if hid in self.attend._forward_hooks_with_kwargs else hook(self.attend, (), P)
+            if result is not None:
+                raise RuntimeError("neurovit_amd.Attention: a forward hook on `attend` returned a value - it would replace the attention "
+                                   "probabilities, which the fused kernels cannot honour; return None")
 
 
 class Transformer(nn.Module):
@@ -480,13 +506,13 @@ class ViT(nn.Module):
             return (self._dropout_p[0], self._dropout_p[1], seed)
         return (0.0, 0.0, 0)
 
-    def _run_forward(self, video, need_grad, extra=(None, 0)):
-        vol_sigma, time_points = extra
+    def _run_forward(self, video, need_grad, extra=(None, 0, None)):
+        vol_sigma, time_points, export = (tuple(extra) + (None,))[:3]
         drop = self.draw_dropout()
         if self.eval_precision not in ("bf16", "fp16", "fp32"):
             raise ValueError(f"neurovit_amd.ViT: eval_precision must be 'bf16', 'fp16' or 'fp32', got {self.eval_precision!r}")
         if self.eval_precision == "fp32" and not need_grad and not self.training:
-            self._last_logits = self._rt.forward_f32(video, self._arena, vol_sigma=vol_sigma, time_points=time_points)
+            self._last_logits = self._rt.forward_f32(video, self._arena, vol_sigma=vol_sigma, time_points=time_points, attn_export=export)
             return self._last_logits
         self._refresh_shadow()
         if self._fp8 is not None and not need_grad and not self.training:
@@ -496,11 +522,68 @@ class ViT(nn.Module):
             self._last_logits = self._rt.forward_fp8_train(video, self._arena, self._shadow, self._fresh_fp8(), dropout=drop, vol_sigma=vol_sigma)
             return self._last_logits
         if self.fold_layernorm and not need_grad and drop[0] == 0.0 and drop[1] == 0.0:
-            self._last_logits = self._rt.forward_lnfold(video, self._arena, self._shadow, self._fresh_fold(), vol_sigma=vol_sigma, time_points=time_points)
+            self._last_logits = self._rt.forward_lnfold(video, self._arena, self._shadow, self._fresh_fold(), vol_sigma=vol_sigma, time_points=time_points,
+                                                        attn_export=export)
             return self._last_logits
         self._last_logits = self._rt.forward(video, self._arena, self._shadow, training=need_grad, dropout=drop, vol_sigma=vol_sigma,
-                                             time_points=time_points)
+                                             time_points=time_points, attn_export=export)
         return self._last_logits
+
+    # ------------------------------------------------------------------ attention probabilities (the output of every block's `attend`)
+    def _uses_fp8(self, need_grad: bool) -> bool:
+        """the forward about to run is one of the fp8 forwards (which export no attention probabilities)"""
+        if self._fp8 is None:
+            return False
+        return (self.fp8_training and need_grad) or (not need_grad and not self.training and self.eval_precision != "fp32")
+
+    def _attend_hooked_layers(self) -> List[int]:
+        """Blocks whose `attend` (nn.Softmax, vit_3d.py:54) has forward hooks - all of them while a global forward hook is registered.
+        The native attention never runs that module: the forward exports those layers' probabilities and fires the hooks itself."""
+        from torch.nn.modules import module as _module
+        layers = []
+        for l, (attn, _) in enumerate(self.transformer.layers):
+            if attn.attend._forward_pre_hooks:
+                raise NotImplementedError("neurovit_amd.ViT: forward pre-hooks on `attend` are not supported - its input, the score matrix "
+                                          "q k^T * scale, is never materialised; register a forward hook to read the probabilities")
+            if attn.attend._forward_hooks or _module._global_forward_hooks:
+                layers.append(l)
+        return layers
+
+    def _fire_attend_hooks(self, maps) -> None:
+        """hook(attend, (), P_l) for every exported layer, in layer order; P_l fp32 [B, heads, n, n], pre-dropout."""
+        from torch.nn.modules import module as _module
+        for l in sorted(maps):
+            attend = self.transformer.layers[l][0].attend
+            hooks = list(_module._global_forward_hooks.items()) + list(attend._forward_hooks.items())
+            for hid, hook in hooks:
+                if hid in attend._forward_hooks_with_kwargs:
+                    result = hook(attend, (), {}, maps[l])
+                else:
+                    result = hook(attend, (), maps[l])
+                if result is not None:
+                    raise RuntimeError("neurovit_amd.ViT: a forward hook on `attend` returned a value - in PyTorch it would replace the "
+                                       "attention probabilities, which the native forward cannot honour; return None")
+
+    def attention_maps(self, video, layers=None, head_fusion=None, rows="all", vol_sigma=None, time_points=0):
+        """One forward in the module's current mode and precision that also returns the attention probabilities of `layers` (default
+        all): (logits, {layer: fp32 map}).  Per head (head_fusion None): [B, heads, R, n] - the output of the block's `attend`
+        (vit_3d.py:54), pre-dropout; head_fusion "mean" / "max" / "min": [B, R, n].  rows "all": R = n, "cls": R = 1 (row 0).
+        Input forms as forward(); for the fused 4D form B counts the B*T volumes.  Hooks on `attend` fire as in forward()."""
+        if head_fusion not in _cabi.ATTN_FUSIONS or rows not in _cabi.ATTN_ROWS:
+            raise ValueError(f"neurovit_amd.ViT: head_fusion must be None, 'mean', 'max' or 'min' and rows 'all' or 'cls', got {head_fusion!r}, {rows!r}")
+        layers = list(range(self._cfg.depth)) if layers is None else sorted({int(l) for l in layers})
+        if any(not 0 <= l < self._cfg.depth for l in layers):
+            raise ValueError(f"neurovit_amd.ViT: layers must lie in [0, {self._cfg.depth}), got {layers}")
+        return self._forward_export(video, vol_sigma, time_points, (layers, head_fusion, rows))
+
+    def attention_rollout(self, video, head_fusion="mean", vol_sigma=None, time_points=0):
+        """Attention rollout (the head-fused (A + I) / 2, row-renormalised rule, multiplied over the layers): (logits, [B, N]) - the row
+        of the token the head reads (the cls row for pool='cls', the mean of all rows for pool='mean') over the N patch tokens, in
+        token order.  One forward exports the fused maps; nv_attn_rollout multiplies them (no [n, n] product is formed)."""
+        if head_fusion not in ("mean", "max", "min"):
+            raise ValueError(f"neurovit_amd.ViT: rollout fuses the heads by 'mean', 'max' or 'min', got {head_fusion!r}")
+        logits, maps = self.attention_maps(video, head_fusion=head_fusion, vol_sigma=vol_sigma, time_points=time_points)
+        return logits, ops.attn_rollout([maps[l] for l in range(self._cfg.depth)], start_mean=self.pool == "mean")
 
     def _run_backward(self, dlogits, dvideo=None):
         """Parameter gradients of every parameter that requires one; dvideo (or None): receives d loss / d video.  With no parameter
@@ -598,6 +681,14 @@ class ViT(nn.Module):
         torch.autograd.grad(out, video) on a trainable model still fills p.grad - so freeze the model for attribution: a model
         without trainable parameters runs the cheaper data-only backward and touches no p.grad.  Not available (NotImplementedError)
         with vol_sigma, time_points or the fp8 training forward."""
+        need_grad = self._check_forward(video, vol_sigma, time_points)
+        hooked = self._attend_hooked_layers()
+        if not hooked:
+            return _ViTFunction.apply(self, video.float(), need_grad, (vol_sigma, int(time_points)), *self._plist)
+        return self._forward_export(video, vol_sigma, time_points, None, checked=(need_grad, hooked))[0]
+
+    def _check_forward(self, video, vol_sigma, time_points) -> bool:
+        """forward()'s argument checks; returns whether the forward records a graph"""
         self.check_video(video, time_points)
         input_grad = torch.is_grad_enabled() and video.requires_grad
         need_grad = input_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self._plist))
@@ -613,7 +704,25 @@ class ViT(nn.Module):
                                           "enable_fp8(training=False) first")
         if time_points and need_grad:
             raise NotImplementedError("neurovit_amd.ViT: the fused 4D input form is forward-only (frozen encoder of the 4D model)")
-        return _ViTFunction.apply(self, video.float(), need_grad, (vol_sigma, int(time_points)), *self._plist)
+        return need_grad
+
+    def _forward_export(self, video, vol_sigma, time_points, request, checked=None):
+        """forward() with an attention-probability export: `request` = (layers, head_fusion, rows) of attention_maps or None; the layers
+        with `attend` hooks are exported per head with every row and their hooks fire once the forward has been queued.
+        Returns (logits, {layer: map} of the request)."""
+        need_grad, hooked = checked if checked is not None else (self._check_forward(video, vol_sigma, time_points), self._attend_hooked_layers())
+        if self._uses_fp8(need_grad):
+            raise NotImplementedError("neurovit_amd.ViT: no attention probabilities from the fp8 forwards (enable_fp8) - disable_fp8() first")
+        layers, fusion, rows = request if request is not None else ([], None, "all")
+        if hooked and request is not None and (fusion is not None or rows != "all"):
+            raise RuntimeError("neurovit_amd.ViT: forward hooks on `attend` receive per-head maps of every row - remove them, or ask "
+                               "attention_maps for head_fusion=None, rows='all'")
+        B = video.shape[0] * (int(time_points) or 1)
+        export, maps = self._rt.make_attn_export(B, sorted(set(layers) | set(hooked)), fusion, rows, video.device)
+        logits = _ViTFunction.apply(self, video.float(), need_grad, (vol_sigma, int(time_points), export), *self._plist)
+        if hooked:
+            self._fire_attend_hooks({l: maps[l] for l in hooked})
+        return logits, {l: maps[l] for l in layers}
 
     # activations / gradients of the last block's attention LayerNorm output (Grad-CAM contract, NeuroEncoder.py:70-82)
     def last_attn_norm_output_raw(self) -> torch.Tensor:
