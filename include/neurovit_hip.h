@@ -307,6 +307,25 @@ int nv_attn_probs(int qkv_f32, const void* qkv, long ld_qkv, int B, int n, int h
  * start_mean = 1, the mean of all rows (pool = 'mean').  Two memory-bound launches per layer; workspace nv_attn_rollout_workspace_bytes. */
 long nv_attn_rollout_workspace_bytes(int B, int n);
 int nv_attn_rollout(const float* const* maps, int L, int B, int n, int start_mean, float* out, void* workspace, long ws_bytes, void* stream);
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) gradient of the loss w.r.t. the attention
+ * probabilities of one layer, recomputed behind its attention backward from the layer's qkv (operand format, as nv_attn_probs with
+ * qkv_f32 = 0; dim_head a multiple of 8 up to 128) and dout = the 16-bit gradient of the attention output [B * n, ld_dout] (what
+ * nv_attn_bwd takes).  What a backward hook on the reference's `attend` (vit_3d.py:54), or attn.register_hook, delivers.  out fp32, contiguous:
+ *   form NV_ATTN_GRAD_PER_HEAD:  [B, heads, n, n] = dO_h V_h^T, the reference's 'b h n d' head order; no probabilities involved;
+ *   form NV_ATTN_GRAD_RELEVANCE: [B, n, n] = (1 / heads) sum_h max(dP_h * P_h, 0) - the layer term of gradient-weighted attention
+ *     relevance (Chefer et al., "Generic Attention-model Explainability"); P_h has the bits of the nv_attn_probs export.
+ * Both products run on the 16x16x32 MFMA with fp32 accumulation.  Rows of dout that are exact zeros give exact zero rows.  No dropout:
+ * the gradient is the one w.r.t. the output of `attend`, in front of the attention dropout, of a forward that had none. */
+#define NV_ATTN_GRAD_PER_HEAD 0
+#define NV_ATTN_GRAD_RELEVANCE 1
+int nv_attn_grad(const void* qkv, long ld_qkv, const void* dout, long ld_dout, int B, int n, int heads, int dim_head, float scale, int form,
+                 float* out, void* stream);
+/* class-specific token relevance: out [B, n - 1] = the patch-token entries (token order) of u (I + A_{L-1}) ... (I + A_0), evaluated as
+ * u <- u + u A_l from the last layer down - the row of R <- R + A_l R (R = I at the start, first layer first) that belongs to the token
+ * the head reads.  maps: HOST array [L] of device pointers to relevance-form maps [B, n, n] (nv_attn_grad).  u = e_0 (the cls row) or,
+ * with start_mean = 1, the mean of all rows (pool = 'mean').  No renormalisation.  One memory-bound launch per layer. */
+long nv_attn_relevance_workspace_bytes(int B, int n);
+int nv_attn_relevance(const float* const* maps, int L, int B, int n, int start_mean, float* out, void* workspace, long ws_bytes, void* stream);
 int nv_stream_sync(void* from, void* to);   /* stream `to` waits for everything enqueued so far on `from` (pooled events) */
 int nv_spin_us(int microseconds, void* stream);   /* one wave that keeps `stream` busy for the given time (<= 50 ms): stream-placement probes */
 
@@ -540,6 +559,24 @@ int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* video, cons
                        const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                        int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                        unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts);
+/* (added within revision 8 - a new symbol and a new struct, nothing existing changes) nv_vit_backward_ex that also exports the gradient
+ * w.r.t. the attention probabilities: for every layer inside the call's stage range whose maps[l] is not NULL, nv_attn_grad (form below)
+ * is queued on `stream` right behind that layer's nv_attn_bwd, while the workspace still holds its dAO and qkv.  maps: HOST array [depth]
+ * of device pointers, NULL = that layer is not exported; each receives [B, heads, n, n] (per head) or [B, n, n] (relevance) fp32.
+ * Works in the full and in the data-only backward (opts->weight_grads = 0), whole or staged; every other output is bit-identical to a
+ * backward without it, and attn_grad = NULL is exactly nv_vit_backward_ex.  Under pool = 'cls' with the last block on its cls rows the
+ * last layer's map is zero outside row 0 (only the cls row reaches the head).
+ * Refused (NV_ERR_ARG): drop_p > 0 (the attention-dropout mask is not replayed into dP), a wrong struct_size, a NULL maps array. */
+typedef struct nv_vit_attn_grad_export {
+  int struct_size;           /* sizeof(nv_vit_attn_grad_export) */
+  float** maps;
+  int form;                  /* NV_ATTN_GRAD_PER_HEAD, NV_ATTN_GRAD_RELEVANCE */
+} nv_vit_attn_grad_export;
+int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                         int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
+                         const nv_vit_attn_grad_export* attn_grad);
 int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, long* begin, long* end);
 /* pool='cls': the last block's out-projection / LayerNorm / FeedForward, forward and backward, on the B cls rows only (whenever the
  * block dropout is off; training additionally B <= 4).  Logits and every gradient are unchanged (the other rows never reach the

@@ -179,6 +179,27 @@ class NeuroEncoder(nn.Module):
         token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
         return self._token_map_to_volume(token_map), predicted
 
+    def get_attention_relevance(self, x, target=None):
+        """Class-specific attention relevance of the ViT3D encoder on the patch grid (gradient-weighted attention relevance, Chefer et al.:
+        mean_h relu(grad A * A) accumulated over the layers), in the form of get_attention_map: (map[S,S,S] on the CPU, class_idx).  Unlike
+        the rollout it depends on the class: `target` None explains the predicted class (as get_attention_map), an int or a LongTensor
+        that class; class_idx is the explained class.  One forward and one data-only backward (ViT.attention_relevance: no p.grad is
+        touched, no autograd graph needed), min-max normalised over the map, thresholded and upsampled as get_attention_map does."""
+        if self.config['TRAINING_DIM'] != 3:
+            raise NotImplementedError("get_attention_relevance: 3D model only (as get_attention_map, one volume [1, H, W, D])")
+        vit = self.volume_encoder.vit3d
+        volume = x.to(self.device)
+        logits, relevance = vit.attention_relevance(volume.permute(0, 3, 1, 2).unsqueeze(1), target=target)   # ViT3DEncoder.forward's view
+        if target is None:
+            class_idx = logits.argmax(dim=1)
+        elif torch.is_tensor(target):
+            class_idx = target.to(logits.device).long().reshape(-1)
+        else:
+            class_idx = torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
+        token_map = relevance.cpu()
+        token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
+        return self._token_map_to_volume(token_map), class_idx
+
     def visualize_slice(self, cam_3d, original_volume):
         """One 2-D slice of the volume and of its CAM along GRADCAM_SLICE_DIM at GRADCAM_SLICE_IDX
         (contract of NeuroEncoder.py:135-168: returns (img, attn), or None after printing why not)."""

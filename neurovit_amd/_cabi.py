@@ -44,6 +44,15 @@ ATTN_FUSIONS = {None: 0, "mean": 1, "max": 2, "min": 3}     # NV_ATTN_PER_HEAD, 
 ATTN_ROWS = {"all": 0, "cls": 1}                            # NV_ATTN_ROWS_ALL / NV_ATTN_ROWS_CLS
 
 
+class AttnGradExport(ctypes.Structure):
+    """struct nv_vit_attn_grad_export (neurovit_hip.h, added within revision 8): per-layer output pointers (a HOST array, NULL = layer not
+    exported) and the form (ATTN_GRAD_FORMS) of the attention gradients nv_vit_backward_attn writes behind each attention backward."""
+    _fields_ = [("struct_size", ctypes.c_int), ("maps", ctypes.c_void_p), ("form", ctypes.c_int)]
+
+
+ATTN_GRAD_FORMS = {"per_head": 0, "relevance": 1}           # NV_ATTN_GRAD_PER_HEAD / NV_ATTN_GRAD_RELEVANCE
+
+
 class TrainHparams(ctypes.Structure):
     """struct nv_train_hparams (neurovit_hip.h): optimizer constants and accumulation flags of nv_vit_train_step."""
     _fields_ = [("struct_size", ctypes.c_int), ("step", ctypes.c_int), ("lr", ctypes.c_double), ("beta1", ctypes.c_double),

@@ -17,33 +17,17 @@
 //                         w_i = u_i / (rowsum_i + 1), the next v_j = sum_i w_i A_ij + w_j.
 //
 // A row's probabilities come out bit-identical in every form (same MFMA order, same statistics): max / min fusion equals the
-// reduction of the per-head export exactly, and the cls form equals row 0 of the all-rows form.
-#include "common.h"
+// reduction of the per-head export exactly, and the cls form equals row 0 of the all-rows form.  The fragment loads, the score tile, the
+// statistics sweep, the exp2 expression and the transposed store live in attn_probs.h: attn_grad.hip forms the same probabilities from them.
+#include "attn_probs.h"
 
 namespace {
-
-constexpr int PR_MAXH = 64;              // heads of a fused 16-bit launch (LDS row statistics)
-constexpr int PR_LD = 68;                // LDS row pitch of the transposed tile, floats (272 B: rows stay 16-byte aligned)
-constexpr float PR_LOG2E = 1.44269504088896340736f;
 
 __device__ __forceinline__ float pr_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-
-// (m, l) of two partial row sweeps in the exp2 domain: m = max, l = sum of exp2(u - m); m = -inf marks an empty sweep
-__device__ __forceinline__ void pr_merge(float& m, float& l, float mo, float lo) {
-  const float mn = fmaxf(m, mo);
-  const float a = (m == -INFINITY) ? 0.f : l * __builtin_amdgcn_exp2f(m - mn);
-  const float b = (mo == -INFINITY) ? 0.f : lo * __builtin_amdgcn_exp2f(mo - mn);
-  l = a + b;
-  m = mn;
-}
-
-// the tile a wave transposes through is its own: its LDS writes must land before its reads (and the reads before the next writes);
-// waves of one workgroup may run different numbers of chunks, so no workgroup barrier here
-__device__ __forceinline__ void wave_lds_order() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 template <int FUSE>
 __device__ __forceinline__ float pr_fuse(float acc, float p, bool first) {
@@ -53,41 +37,10 @@ __device__ __forceinline__ float pr_fuse(float acc, float p, bool first) {
   else return acc + p;                    // mean: the division by heads follows the last head
 }
 
-// Q fragments of row tile t: lane (row l & 15, k 8 (l >> 4) .. + 8) of the 16 x 32 A operand, zero outside [0, rows) x [0, dh)
-template <int KK, int RT>
-__device__ __forceinline__ void pr_load_q(r16x8 (&qf)[RT][KK], const r16* __restrict__ base, long ld, int i0, int rows, int col0, int dh, int lane) {
-#pragma unroll
-  for (int t = 0; t < RT; ++t) {
-    const int i = i0 + 16 * t + (lane & 15);
-#pragma unroll
-    for (int kk = 0; kk < KK; ++kk) {
-      const int k = 32 * kk + 8 * (lane >> 4);
-      qf[t][kk] = (i < rows && k < dh) ? *reinterpret_cast<const r16x8*>(base + (long)i * ld + col0 + k) : r16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
-  }
-}
-
-// S of the RT row tiles against keys j0 .. j0 + 15: C fragment (row 4 (l >> 4) + r, key j0 + (l & 15)); keys >= n read as zero
-template <typename T, int KK, int RT>
-__device__ __forceinline__ void pr_scores(f32x4 (&s)[RT], const r16x8 (&qf)[RT][KK], const r16* __restrict__ base, long ld, int n, int j0, int kcol,
-                                          int dh, int lane) {
-  const int j = j0 + (lane & 15);
-#pragma unroll
-  for (int t = 0; t < RT; ++t) s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int kk = 0; kk < KK; ++kk) {
-    const int k = 32 * kk + 8 * (lane >> 4);
-    const r16x8 kf = (j < n && k < dh) ? *reinterpret_cast<const r16x8*>(base + (long)j * ld + kcol + k) : r16x8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int t = 0; t < RT; ++t) s[t] = mfma16<T>(qf[t][kk], kf, s[t]);
-  }
-}
-
 // grid (ceil(rows / (16 RT)), B * heads [per head] or B [fused], KS), four waves.  The workgroup's waves share its 16 RT query rows and
 // split the keys: in pass 1 wave w sweeps the 16-key blocks w, w + 4, ... and the four partial statistics are merged through LDS in wave
 // order (every workgroup, every form: the same bits); in pass 2 wave w of key split z writes the 64-key chunks 4 z + w, + 4 KS, ...
 // out: [B, heads, rows, n] or [B, rows, n] fp32, rows = n or 1.
-constexpr int PR_WAVES = 4;
 template <typename T, int KK, int RT, int FUSE>
 __global__ __launch_bounds__(64 * PR_WAVES) void attn_probs16_kernel(const r16* __restrict__ qkv, long ld, int n, int heads, int dh, float c,
                                                                      int rows, float* __restrict__ out, int vec4) {
@@ -108,45 +61,13 @@ __global__ __launch_bounds__(64 * PR_WAVES) void attn_probs16_kernel(const r16* 
   // ---- pass 1: row max and sum of every head this workgroup serves
   for (int h = h0; h < h1; ++h) {
     pr_load_q<KK, RT>(qf, base, ld, i0, rows, h * dh, dh, lane);
-    float m[RT][4], l[RT][4];
+    pr_row_stats<T, KK, RT>(mrow, irow, qf, base, ld, n, inner + h * dh, dh, c, sPart, lane, wv);
+    if (FUSE != NV_ATTN_PER_HEAD && wv == 0 && (lane & 15) == 0) {
 #pragma unroll
-    for (int t = 0; t < RT; ++t)
+      for (int t = 0; t < RT; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { m[t][r] = -INFINITY; l[t][r] = 0.f; }
-    for (int j0 = 16 * wv; j0 < n; j0 += 16 * PR_WAVES) {
-      pr_scores<T, KK, RT>(s, qf, base, ld, n, j0, inner + h * dh, dh, lane);
-      if (j0 + (lane & 15) < n) {
-#pragma unroll
-        for (int t = 0; t < RT; ++t)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float u = s[t][r] * c;
-            if (u > m[t][r]) { l[t][r] = (m[t][r] == -INFINITY) ? 0.f : l[t][r] * __builtin_amdgcn_exp2f(m[t][r] - u); m[t][r] = u; }
-            l[t][r] += __builtin_amdgcn_exp2f(u - m[t][r]);
-          }
-      }
+        for (int r = 0; r < 4; ++r) { sSt[h][16 * t + 4 * g + r][0] = mrow[t][r]; sSt[h][16 * t + 4 * g + r][1] = irow[t][r]; }
     }
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) pr_merge(m[t][r], l[t][r], __shfl_xor(m[t][r], o, 64), __shfl_xor(l[t][r], o, 64));
-        if ((lane & 15) == 0) { sPart[wv][16 * t + 4 * g + r][0] = m[t][r]; sPart[wv][16 * t + 4 * g + r][1] = l[t][r]; }
-      }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < RT; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * t + 4 * g + r;
-        float mm = sPart[0][row][0], ll = sPart[0][row][1];
-#pragma unroll
-        for (int w = 1; w < PR_WAVES; ++w) pr_merge(mm, ll, sPart[w][row][0], sPart[w][row][1]);
-        mrow[t][r] = mm;
-        irow[t][r] = 1.0f / ll;
-        if (FUSE != NV_ATTN_PER_HEAD && wv == 0 && (lane & 15) == 0) { sSt[h][row][0] = mm; sSt[h][row][1] = irow[t][r]; }
-      }
     __syncthreads();                     // sPart is rewritten by the next head
   }
 
@@ -170,7 +91,7 @@ __global__ __launch_bounds__(64 * PR_WAVES) void attn_probs16_kernel(const r16* 
         for (int t = 0; t < RT; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float p = __builtin_amdgcn_exp2f(s[t][r] * c - mrow[t][r]) * irow[t][r];
+            const float p = pr_prob(s[t][r], c, mrow[t][r], irow[t][r]);
             acc[t][kb][r] = pr_fuse<FUSE>(acc[t][kb][r], p, h == h0);
           }
       }
@@ -186,17 +107,7 @@ __global__ __launch_bounds__(64 * PR_WAVES) void attn_probs16_kernel(const r16* 
           if (FUSE == NV_ATTN_FUSE_MEAN) v = v / (float)heads;
           tile[16 * t + 4 * g + r][16 * kb + (lane & 15)] = v;
         }
-    wave_lds_order();
-    if (vec4) {                          // n % 4 == 0: 16 lanes write one row's 64 keys as float4, four rows per instruction
-      const int jj = j0 + 4 * (lane & 15);
-      for (int rr = g; rr < valid_rows; rr += 4)
-        if (jj < n) *reinterpret_cast<float4*>(obase + (long)(i0 + rr) * n + jj) = *reinterpret_cast<const float4*>(&tile[rr][4 * (lane & 15)]);
-    } else {                             // odd n: one row's 64 keys per instruction
-      const int jj = j0 + lane;
-      if (jj < n)
-        for (int rr = 0; rr < valid_rows; ++rr) obase[(long)(i0 + rr) * n + jj] = tile[rr][lane];
-    }
-    wave_lds_order();
+    pr_store_tile(tile, obase, n, i0, valid_rows, j0, vec4, lane);
   }
 }
 

@@ -759,7 +759,7 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
                          const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                          unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
-                         const nv_vit_backward_opts* opts);
+                         const nv_vit_backward_opts* opts, const nv_vit_attn_grad_export* attn_grad = nullptr);
 
 extern "C" int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
@@ -769,21 +769,41 @@ extern "C" int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const f
                        drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, nullptr);
 }
 
+// Export of the gradient w.r.t. the attention probabilities (nv_vit_attn_grad_export): nv_attn_grad queued right behind a layer's
+// attention backward, while dAO and the layer's qkv still hold its values.  attn_grad = NULL: exactly the launches of nv_vit_backward_ex.
+extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                                    const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                                    int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                                    unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
+                                    const nv_vit_attn_grad_export* attn_grad) {
+  NV_CHECK_ARG(!opts || opts->struct_size == (int)sizeof(nv_vit_backward_opts), "nv_vit_backward_ex: opts->struct_size %d != %d (ABI revision mismatch)",
+               opts ? opts->struct_size : 0, (int)sizeof(nv_vit_backward_opts));
+  if (attn_grad) {
+    NV_CHECK_ARG(attn_grad->struct_size == (int)sizeof(nv_vit_attn_grad_export), "nv_vit_backward_attn: nv_vit_attn_grad_export.struct_size=%d, expected %d",
+                 attn_grad->struct_size, (int)sizeof(nv_vit_attn_grad_export));
+    NV_CHECK_ARG(attn_grad->maps, "nv_vit_backward_attn: nv_vit_attn_grad_export.maps is NULL");
+    NV_CHECK_ARG(attn_grad->form == NV_ATTN_GRAD_PER_HEAD || attn_grad->form == NV_ATTN_GRAD_RELEVANCE,
+                 "nv_vit_backward_attn: nv_vit_attn_grad_export.form=%d out of range", attn_grad->form);
+    NV_CHECK_ARG(!(drop_p > 0.f), "nv_vit_backward_attn: drop_p=%g - the attention-dropout mask is not replayed into the gradient of the probabilities; "
+                 "export from a forward without dropout (eval mode)", (double)drop_p);
+  }
+  return backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, opts, attn_grad);
+}
+
 extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                                   const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                                   int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                                   unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts) {
-  NV_CHECK_ARG(!opts || opts->struct_size == (int)sizeof(nv_vit_backward_opts), "nv_vit_backward_ex: opts->struct_size %d != %d (ABI revision mismatch)",
-               opts ? opts->struct_size : 0, (int)sizeof(nv_vit_backward_opts));
-  return backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
-                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, opts);
+  return nv_vit_backward_attn(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+                              drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, opts, nullptr);
 }
 
 static int backward_impl(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                          const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                          unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
-                         const nv_vit_backward_opts* opts) {
+                         const nv_vit_backward_opts* opts, const nv_vit_attn_grad_export* attn_grad) {
   Dims D; RUN(make_dims(cfg, B, D));
   NV_CHECK_ARG(!fuse || (!accumulate && !grads16 && fuse->grads == grads && first_stage <= 1 && last_stage == D.L + 1),
                "nv_vit_backward: the optimizer update during the backward pass needs accumulate = 0, no bf16 mirror, its own gradient arena and every stage in one call");
@@ -793,6 +813,7 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
   const bool wg = !opts || opts->weight_grads;
   float* const dvideo = opts ? opts->dvideo : nullptr;
   NV_CHECK_ARG(!fuse || !opts, "nv_vit_backward: the optimizer update during the backward pass takes no input gradient / data-only options");
+  NV_CHECK_ARG(!fuse || !attn_grad, "nv_vit_backward: the optimizer update during the backward pass exports no attention gradients");
   NV_CHECK_ARG(!dvideo || opts->dvideo_strides5, "nv_vit_backward_ex: dvideo needs dvideo_strides5");
   NV_CHECK_ARG(wg || (!grads && !grads16), "nv_vit_backward_ex: the data-only backward (weight_grads = 0) writes no gradient arena - pass grads = grads16 = NULL");
   NV_CHECK_ARG(video && strides5 && params && params16 && workspace && dlogits && (grads || !wg), "nv_vit_backward: null pointer");
@@ -897,6 +918,8 @@ static int backward_impl(const nv_vit_config* cfg, int B, const float* video, co
     RUN(nv_gemm_bf16(1, 0, M, D.inner, d, g16b, d, p16 + q.wo, D.inner, ws + W.dao, D.inner, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));  // dAO = g Wo
     RUN(nv_attn_bwd(ws + w.qkv, 3 * D.inner, ws + w.ao, ws + W.dao, D.inner, (float*)(ws + w.lse), B, D.n, D.heads, D.dh, scale,
                     (float*)(ws + W.delta), dqkv, 3 * D.inner, site_seed(drop_seed, 4 * l + 0), drop_p, stream));
+    if (attn_grad && attn_grad->maps[l])     // dP (or the relevance term) of this layer: dAO and qkv still hold its values
+      RUN(nv_attn_grad(ws + w.qkv, 3 * D.inner, ws + W.dao, D.inner, B, D.n, D.heads, D.dh, scale, attn_grad->form, attn_grad->maps[l], stream));
     float* dxn1 = (l == D.L - 1) ? (float*)(ws + W.hookg) : dxn;    // gradient of the last block's attention-LN output is kept (Grad-CAM hook)
     const bool dxn1_first = fuse && fuse_mode != 3;
     if (dxn1_first)      // the last reader of this layer's bf16 weights, ahead of the launch that rewrites them (see above)

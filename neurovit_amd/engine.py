@@ -17,7 +17,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _cabi, ops
-from ._cabi import AttnExport, BackwardOpts, TrainHparams, VitConfig, VitInput, check, lib
+from ._cabi import AttnExport, AttnGradExport, BackwardOpts, TrainHparams, VitConfig, VitInput, check, lib
 
 _BYTES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
 
@@ -183,6 +183,20 @@ class VitRuntime:
         ex._ptrs = ptrs                                   # the host pointer array lives as long as the struct
         return ex, maps
 
+    def make_attn_grad_export(self, B: int, layers, form: str, device):
+        """(nv_vit_attn_grad_export, {layer: fp32 map}) for a backward of B volumes: form "per_head" [B, heads, n, n] = the gradient
+        w.r.t. the output of the block's `attend`, or "relevance" [B, n, n] = mean_h relu(dP_h * P_h).  The struct holds raw pointers:
+        keep the maps (and the struct) alive across the call."""
+        c = self.cfg
+        H, Wd, p1, p2 = image_hw(c)
+        n = (c.frames // c.frame_patch_size) * (H // p1) * (Wd // p2) + 1
+        shape = (B, c.heads, n, n) if form == "per_head" else (B, n, n)
+        maps = {int(l): torch.empty(shape, dtype=torch.float32, device=device) for l in layers}
+        ptrs = (ctypes.c_void_p * c.depth)(*[maps[l].data_ptr() if l in maps else None for l in range(c.depth)])
+        ex = AttnGradExport(ctypes.sizeof(AttnGradExport), ctypes.cast(ptrs, ctypes.c_void_p), _cabi.ATTN_GRAD_FORMS[form])
+        ex._ptrs = ptrs                                   # the host pointer array lives as long as the struct
+        return ex, maps
+
     def forward(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, training: bool,
                 dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, time_points: int = 0, rows_form: Optional[int] = None,
                 attn_export: Optional[AttnExport] = None) -> torch.Tensor:
@@ -343,13 +357,16 @@ class VitRuntime:
 
     def backward(self, dlogits: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: Optional[torch.Tensor],
                  accumulate: bool, stages: Optional[Tuple[int, int]] = None, join_aux: bool = True,
-                 grads16: Optional[torch.Tensor] = None, dvideo: Optional[torch.Tensor] = None, weight_grads: bool = True) -> None:
+                 grads16: Optional[torch.Tensor] = None, dvideo: Optional[torch.Tensor] = None, weight_grads: bool = True,
+                 attn_grad: Optional[AttnGradExport] = None) -> None:
         """Whole backward, or only stages [first, last] (0 = head, 1+k = layer depth-1-k, depth+1 = embedding).
         join_aux=False (only for ranges before the last stage): the current stream is not made to wait for the auxiliary
         stream - order the consumer of the range's gradients after `aux_stream_object()` as well.
         dvideo: fp32 tensor of the forward input's shape (any strides) that receives d loss / d video; written by the call whose
         stages contain the embedding.  weight_grads=False: the data-only backward - no parameter gradient is produced, `grads`
-        and `grads16` must be None (nv_vit_backward_ex)."""
+        and `grads16` must be None (nv_vit_backward_ex).
+        attn_grad (make_attn_grad_export): the gradients w.r.t. the attention probabilities, written behind the attention backward of
+        every exported layer inside the stage range (nv_vit_backward_attn); needs a forward without block dropout."""
         rec = self._cur
         assert rec is not None, "backward needs a preceding forward(training=True)"
         if not self.pass_is_live(rec):
@@ -362,7 +379,10 @@ class VitRuntime:
         _cabi.set_operand_format(self.operands)
         if first == 0:
             rec.dlogits = dlogits.contiguous().float()
-        if dvideo is not None or not weight_grads:
+        if attn_grad is not None and rec.dropout[0] > 0:
+            raise NotImplementedError("neurovit_amd: no attention gradients of a forward with attention dropout (the mask is not replayed "
+                                      "into the gradient of the probabilities) - run the attribution in eval mode")
+        if dvideo is not None or not weight_grads or attn_grad is not None:
             if dvideo is not None:
                 if rec.keep[0] is not None:
                     raise NotImplementedError("neurovit_amd: no input gradient of a forward on RAW volumes (vol_sigma): the folded z-score "
@@ -373,13 +393,14 @@ class VitRuntime:
             dstrides = None if dvideo is None else ops.strides5(dvideo)      # (kept alive across the call)
             opts = BackwardOpts(ctypes.sizeof(BackwardOpts), None if dvideo is None else dvideo.data_ptr(),
                                 None if dstrides is None else ctypes.cast(dstrides, ctypes.c_void_p), int(bool(weight_grads)))
-            check(lib.nv_vit_backward_ex(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
-                                         params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
-                                         None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
-                                         int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
-                                         torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
-                                         int(join_aux), int(rec.rows_form), ctypes.byref(opts)),
-                  "nv_vit_backward_ex")
+            check(lib.nv_vit_backward_attn(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
+                                           params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
+                                           None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
+                                           int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
+                                           torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
+                                           int(join_aux), int(rec.rows_form), ctypes.byref(opts),
+                                           None if attn_grad is None else ctypes.byref(attn_grad)),
+                  "nv_vit_backward_attn")
             if last == self.cfg.depth + 1:
                 rec.done = True
             return

@@ -333,6 +333,38 @@ def attn_rollout(maps, start_mean: bool = False) -> torch.Tensor:
     return out
 
 
+def attn_grad(qkv: torch.Tensor, dout: torch.Tensor, B: int, n: int, heads: int, dim_head: int = 64, form: str = "per_head",
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient w.r.t. the attention probabilities from a layer's qkv [B*n, 3*inner] and the gradient of its attention output dout
+    [B*n, inner] (both in the operand format): fp32 [B, heads, n, n] = dO_h V_h^T (form "per_head") or [B, n, n] =
+    mean_h relu(dP_h * P_h) (form "relevance", P = softmax(q k^T / sqrt(dh)) with the bits of attn_probs): nv_attn_grad."""
+    _need_cuda(qkv, dout)
+    assert qkv.stride(1) == 1 and dout.stride(1) == 1 and qkv.dtype == op16() and dout.dtype == op16()
+    shape = (B, heads, n, n) if form == "per_head" else (B, n, n)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=qkv.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous()
+    check(lib.nv_attn_grad(_p(qkv), qkv.stride(0), _p(dout), dout.stride(0), B, n, heads, dim_head, dim_head ** -0.5,
+                           _cabi.ATTN_GRAD_FORMS[form], _p(out), _stream()), "nv_attn_grad")
+    return out
+
+
+def attn_relevance(maps, start_mean: bool = False) -> torch.Tensor:
+    """Class-specific token relevance over relevance-form maps [B, n, n] (layer 0 first): [B, n - 1] = the patch-token entries of
+    u (I + A_{L-1}) ... (I + A_0); u = the cls row, or the mean of the rows (start_mean): nv_attn_relevance."""
+    _need_cuda(*maps)
+    B, n, _ = maps[0].shape
+    for m in maps:
+        assert m.shape == (B, n, n) and m.dtype == torch.float32 and m.is_contiguous()
+    ptrs = (ctypes.c_void_p * len(maps))(*[m.data_ptr() for m in maps])
+    nb = lib.nv_attn_relevance_workspace_bytes(B, n)
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=maps[0].device)
+    out = torch.empty((B, n - 1), dtype=torch.float32, device=maps[0].device)
+    check(lib.nv_attn_relevance(ctypes.cast(ptrs, ctypes.c_void_p), len(maps), B, n, int(bool(start_mean)), _p(out), _p(ws), nb, _stream()),
+          "nv_attn_relevance")
+    return out
+
+
 def attn_bwd(qkv, out, dout, lse, B, n, heads, dim_head=64, drop_seed=0, drop_p=0.0):
     inner = heads * dim_head
     dqkv = torch.empty((B * n, 3 * inner), dtype=op16(), device=qkv.device)

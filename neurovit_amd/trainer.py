@@ -254,6 +254,10 @@ class TrainStep:
         return loss.reshape(())
 
     def _native_step(self, fmri: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        if self._vit._attend_backward_hooked_layers():
+            # (_native_ok routes a hooked model to the general path, whose backward fires the hooks; the one-call step has no place to)
+            raise NotImplementedError("neurovit_amd.TrainStep: the native one-call step exports no attention gradients - backward hooks on "
+                                      "`attend` need the general path (forward + backward through autograd)")
         got = self._graph_step(fmri, labels)
         if got is not None:
             return got

@@ -81,7 +81,8 @@ class _AttentionFn(torch.autograd.Function):
     """vit_3d.py:48-60 standalone: LayerNorm -> to_qkv -> softmax(q k^T * scale) (+Dropout) -> attn v -> to_out (+Dropout)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, wqkv, wo, bo, heads, dim_head, p, seeds):
+    def forward(ctx, x, gamma, beta, wqkv, wo, bo, heads, dim_head, p, seeds, attend=None):
+        ctx.attend = attend               # the module's nn.Softmax: its backward hooks are looked up when the backward runs
         if x.dim() != 3:
             raise ValueError("neurovit_amd.Attention: expected x of shape [batch, tokens, dim]")
         B, n, _ = x.shape
@@ -107,10 +108,40 @@ class _AttentionFn(torch.autograd.Function):
         dbo = ops.colsum_bf16(dy16)
         dao = ops.gemm(ops.NN, ops.EPI_STORE_BF16, dy16, wo16)
         dqkv, _ = ops.attn_bwd(qkv, ao, dao, lse, B, n, heads, dim_head, drop_seed=seeds[0], drop_p=p if seeds[0] else 0.0)
+        hooks = _attend_backward_hooks(ctx.attend) if ctx.attend is not None else []
+        if hooks:
+            if seeds[0]:
+                raise NotImplementedError("neurovit_amd.Attention: backward hooks on `attend` with attention dropout active - the mask is not "
+                                          "replayed into the gradient of the probabilities; run the attribution in eval mode")
+            _fire_attend_backward_hooks(ctx.attend, hooks, ops.attn_grad(qkv, dao, B, n, heads, dim_head), "neurovit_amd.Attention")
         dwqkv = ops.gemm(ops.TN, ops.EPI_STORE_F32, dqkv, xn)
         dxn = ops.gemm(ops.NN, ops.EPI_STORE_F32, dqkv, wqkv16)
         dx, _, dgamma, dbeta, _ = ops.ln_bwd(dxn, x2, st, gamma, want_g16=False)
-        return dx.view(shape), dgamma, dbeta, dwqkv, dwo, dbo, None, None, None, None
+        return dx.view(shape), dgamma, dbeta, dwqkv, dwo, dbo, None, None, None, None, None
+
+
+def _attend_backward_hooks(attend) -> list:
+    """The backward hooks registered on an `attend` module (register_full_backward_hook, or the legacy register_backward_hook), the global
+    module backward hooks first - looked up when the backward runs, as autograd does."""
+    from torch.nn.modules import module as _module
+    return list(_module._global_backward_hooks.values()) + list(attend._backward_hooks.values())
+
+
+def _check_no_backward_pre_hooks(attend, who: str) -> None:
+    from torch.nn.modules import module as _module
+    if getattr(attend, "_backward_pre_hooks", None) or getattr(_module, "_global_backward_pre_hooks", None):
+        raise NotImplementedError(f"{who}: backward pre-hooks on `attend` are not supported - they may replace the gradient w.r.t. the "
+                                  "attention probabilities, which the fused attention backward never reads back; register a full backward hook")
+
+
+def _fire_attend_backward_hooks(attend, hooks, dP, who: str) -> None:
+    """hook(attend, grad_input, grad_output) = hook(attend, (None,), (dP,)): dP fp32 [B, heads, n, n] on the device = the gradient w.r.t.
+    the output of `attend`.  grad_input is (None,): the input of `attend`, the score matrix q k^T * scale, is never an autograd input
+    here (the fused kernels form it tile by tile), so no gradient w.r.t. it exists to hand over."""
+    for hook in hooks:
+        if hook(attend, (None,), (dP,)) is not None:
+            raise RuntimeError(f"{who}: a backward hook on `attend` returned a value - in PyTorch it would replace the gradient w.r.t. the "
+                               "score matrix, which the native backward cannot honour; return None")
 
 
 class FeedForward(nn.Module):
@@ -168,10 +199,10 @@ class Attention(nn.Module):
             dim = self.heads * self.dim_head
             eye, zero = torch.eye(dim, device=x.device), torch.zeros(dim, device=x.device)
             return _AttentionFn.apply(x, self.norm.weight, self.norm.bias, self.to_qkv.weight, eye, zero, self.heads, self.dim_head, p,
-                                      (_new_seed(p, self.training), 0))
+                                      (_new_seed(p, self.training), 0), self.attend)
         seeds = (_new_seed(p, self.training), _new_seed(p, self.training))
         return _AttentionFn.apply(x, self.norm.weight, self.norm.bias, self.to_qkv.weight, self.to_out[0].weight, self.to_out[0].bias,
-                                  self.heads, self.dim_head, p, seeds)
+                                  self.heads, self.dim_head, p, seeds, self.attend)
 
 
     def _attend_hooks(self, x):
@@ -182,6 +213,7 @@ class Attention(nn.Module):
         if self.attend._forward_pre_hooks:
             raise NotImplementedError("neurovit_amd.Attention: forward pre-hooks on `attend` are not supported - the score matrix is never "
                                       "materialised; register a forward hook to read the probabilities")
+        _check_no_backward_pre_hooks(self.attend, "neurovit_amd.Attention")
         hooks = list(_module._global_forward_hooks.items()) + list(self.attend._forward_hooks.items())
         if not hooks:
             return
@@ -549,6 +581,13 @@ class ViT(nn.Module):
                 layers.append(l)
         return layers
 
+    def _attend_backward_hooked_layers(self) -> List[int]:
+        """Blocks whose `attend` has backward hooks - all of them while a global module backward hook is registered.  The native backward
+        never runs that module: it exports those layers' dP = dO V^T behind their attention backward (nv_vit_backward_attn) and fires the
+        hooks itself, in reverse layer order."""
+        from torch.nn.modules import module as _module
+        return [l for l, (attn, _) in enumerate(self.transformer.layers) if attn.attend._backward_hooks or _module._global_backward_hooks]
+
     def _fire_attend_hooks(self, maps) -> None:
         """hook(attend, (), P_l) for every exported layer, in layer order; P_l fp32 [B, heads, n, n], pre-dropout."""
         from torch.nn.modules import module as _module
@@ -585,25 +624,104 @@ class ViT(nn.Module):
         logits, maps = self.attention_maps(video, head_fusion=head_fusion, vol_sigma=vol_sigma, time_points=time_points)
         return logits, ops.attn_rollout([maps[l] for l in range(self._cfg.depth)], start_mean=self.pool == "mean")
 
+    def attention_gradients(self, video, target=None, layers=None, form="per_head", vol_sigma=None, time_points=0):
+        """The gradient of a class score w.r.t. the attention probabilities of `layers` (default all): (logits, {layer: fp32 map}).
+        form "per_head": [B, heads, n, n] = d logit_target / d P_l, the gradient w.r.t. the output of the block's `attend` (vit_3d.py:54)
+        that attn.register_hook / a backward hook on `attend` give on the reference; form "relevance": [B, n, n] =
+        mean_h relu(dP_l * P_l), the layer term of gradient-weighted attention relevance (Chefer et al.).
+        target: None = the arg-max class of each volume (as get_attention_map), an int, or a LongTensor [B].
+        Runs one graph-recording forward (the training arithmetic, 16-bit operands: precision("fp32") does not apply) and the data-only
+        backward of the one-hot of `target` itself, down to the lowest requested layer: it works under torch.no_grad(), touches no p.grad
+        and no gradient arena, and leaves last_attn_norm_grad as a normal backward would.  Forward hooks on `attend` fire as in forward();
+        backward hooks do not (no autograd backward runs).  Not available (NotImplementedError) with the fp8 training forward, the fused
+        4D input form (time_points) or attention dropout active (train mode with dropout > 0)."""
+        if form not in _cabi.ATTN_GRAD_FORMS:
+            raise ValueError(f"neurovit_amd.ViT: form must be 'per_head' or 'relevance', got {form!r}")
+        depth, C = self._cfg.depth, self._cfg.num_classes
+        layers = list(range(depth)) if layers is None else sorted({int(l) for l in layers})
+        if not layers or any(not 0 <= l < depth for l in layers):
+            raise ValueError(f"neurovit_amd.ViT: layers must be a non-empty subset of [0, {depth}), got {layers}")
+        if time_points:
+            raise NotImplementedError("neurovit_amd.ViT: no attention gradients through the fused 4D input form (time_points) - it is "
+                                      "forward-only; pass the [B*T, C, F, H, W] volumes instead")
+        if self._fp8 is not None and self.fp8_training:
+            raise NotImplementedError("neurovit_amd.ViT: no attention gradients through the fp8 training forward - disable_fp8() or "
+                                      "enable_fp8(training=False) first")
+        if self.training and self._dropout_p[0] > 0:
+            raise NotImplementedError("neurovit_amd.ViT: no attention gradients with attention dropout active (train mode, dropout > 0): the mask "
+                                      "is not replayed into the gradient of the probabilities - call eval() for attribution")
+        self.check_video(video)
+        hooked = self._attend_hooked_layers()
+        B = video.shape[0]
+        fwd_export, fwd_maps = self._rt.make_attn_export(B, hooked, None, "all", video.device) if hooked else (None, {})
+        with torch.no_grad():
+            logits = self._run_forward(video.detach().float(), True, (vol_sigma, 0, fwd_export))
+            if hooked:
+                self._fire_attend_hooks(fwd_maps)
+            if target is None:
+                cls = logits.argmax(dim=1)
+            elif torch.is_tensor(target):
+                cls = target.to(device=logits.device, dtype=torch.long).reshape(-1)
+                if cls.numel() != B:
+                    raise ValueError(f"neurovit_amd.ViT: target must hold one class per volume ({B}), got {tuple(target.shape)}")
+            else:
+                if not 0 <= int(target) < C:
+                    raise ValueError(f"neurovit_amd.ViT: target class {target} outside [0, {C})")
+                cls = torch.full((B,), int(target), dtype=torch.long, device=logits.device)
+            dlogits = torch.nn.functional.one_hot(cls, C).to(torch.float32)
+            rec = self._rt._cur
+            export, maps = self._rt.make_attn_grad_export(B, layers, form, video.device)
+            # stages 0 (head) .. depth - min(layers): the layers below the lowest requested one and the embedding add nothing
+            self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, stages=(0, depth - layers[0]), weight_grads=False,
+                              attn_grad=export)
+            rec.done = True                   # nothing more of this pass will run: its workspace may be refilled
+            self._rt.backward_done = True     # the last block's hook gradient (stage 1) is in the workspace
+        return logits, maps
+
+    def attention_relevance(self, video, target=None):
+        """Class-specific relevance of the patch tokens (gradient-weighted attention relevance, Chefer et al. "Generic Attention-model
+        Explainability": A_l = mean_h relu(dP_l * P_l), R <- R + A_l R from R = I): (logits, [B, N]) - the row of the token the head
+        reads (the cls row for pool='cls', the mean of all rows for pool='mean') over the N patch tokens, in token order.  One forward
+        and one data-only backward export the A_l (attention_gradients, form "relevance"); nv_attn_relevance accumulates
+        u <- u + u A_l from the last layer down (no [n, n] product is formed).  target as attention_gradients."""
+        logits, maps = self.attention_gradients(video, target=target, form="relevance")
+        return logits, ops.attn_relevance([maps[l] for l in range(self._cfg.depth)], start_mean=self.pool == "mean")
+
     def _run_backward(self, dlogits, dvideo=None):
         """Parameter gradients of every parameter that requires one; dvideo (or None): receives d loss / d video.  With no parameter
-        requiring a gradient (a frozen model fed an input that requires one) the data-only backward runs: no gradient arena, no p.grad."""
+        requiring a gradient (a frozen model fed an input that requires one) the data-only backward runs: no gradient arena, no p.grad.
+        Backward hooks on a block's `attend` are looked up here: the hooked layers' dP is exported by the same backward (without hooks
+        nothing extra is launched) and the hooks fire once it has been queued, in reverse layer order."""
+        hooked = self._attend_backward_hooked_layers()
+        export, dP = (None, {})
+        if hooked:
+            rec = self._rt._cur
+            if rec is not None and rec.dropout[0] > 0:
+                raise NotImplementedError("neurovit_amd.ViT: backward hooks on `attend` with attention dropout active (train mode, dropout > 0) - "
+                                          "the mask is not replayed into the gradient of the probabilities; run the attribution in eval mode")
+            export, dP = self._rt.make_attn_grad_export(rec.B, hooked, "per_head", rec.video.device)
+        self._run_backward_export(dlogits, dvideo, export)
+        for l in sorted(dP, reverse=True):
+            attend = self.transformer.layers[l][0].attend
+            _fire_attend_backward_hooks(attend, _attend_backward_hooks(attend), dP[l], "neurovit_amd.ViT")
+
+    def _run_backward_export(self, dlogits, dvideo, export):
         trainable = [i for i, p in enumerate(self._plist) if p.requires_grad]
         if not trainable:
-            if dvideo is not None:
-                self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False)
+            if dvideo is not None or export is not None:
+                self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False, attn_grad=export)
             return
         grads = self.flat_gradients()
         state = [self._plist[i].grad for i in trainable]
         if all(g is None for g in state):
-            self._backward_into(dlogits, grads, accumulate=False, dvideo=dvideo)
+            self._backward_into(dlogits, grads, accumulate=False, dvideo=dvideo, attn_grad=export)
             for i in trainable:
                 self._plist[i].grad = self._grad_view(i)
         elif all(g is not None and g.data_ptr() == self._grad_view(i).data_ptr() for g, i in zip(state, trainable)):
-            self._backward_into(dlogits, grads, accumulate=True, dvideo=dvideo)
+            self._backward_into(dlogits, grads, accumulate=True, dvideo=dvideo, attn_grad=export)
         else:   # foreign .grad tensors: compute into a scratch arena and add
             scratch = torch.empty_like(grads)
-            self._rt.backward(dlogits, self._arena, self._shadow, scratch, accumulate=False, dvideo=dvideo)
+            self._rt.backward(dlogits, self._arena, self._shadow, scratch, accumulate=False, dvideo=dvideo, attn_grad=export)
             off, num, _ = self._layout
             for i in trainable:
                 g = scratch[off[i]:off[i] + num[i]].view(self._plist[i].shape)
@@ -627,10 +745,10 @@ class ViT(nn.Module):
         self._mirrored = sorted(out)          # the layout never changes for a constructed module
         return self._mirrored
 
-    def _backward_into(self, dlogits, grads, accumulate, dvideo=None):
+    def _backward_into(self, dlogits, grads, accumulate, dvideo=None, attn_grad=None):
         sync = self._grad_sync
         if sync is None:
-            self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, dvideo=dvideo)
+            self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, dvideo=dvideo, attn_grad=attn_grad)
             return
         from .parallel import bucket_stages
         sync.begin()
@@ -646,7 +764,8 @@ class ViT(nn.Module):
             # intermediate buckets do not stall the main stream on the auxiliary (weight-gradient) stream: the bucket's
             # all-reduce is ordered after both streams instead
             self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, stages=(first, last),
-                              join_aux=(last == last_stage), grads16=msg, dvideo=dvideo if last == last_stage else None)
+                              join_aux=(last == last_stage), grads16=msg, dvideo=dvideo if last == last_stage else None,
+                              attn_grad=attn_grad)          # (each call exports the layers inside its stage range)
             sync.bucket_ready(grads, begin, end, also_after=None if last == last_stage else self._rt.aux_stream_object(grads.device))
         sync.finish()
 
@@ -692,6 +811,16 @@ class ViT(nn.Module):
         self.check_video(video, time_points)
         input_grad = torch.is_grad_enabled() and video.requires_grad
         need_grad = input_grad or (torch.is_grad_enabled() and any(p.requires_grad for p in self._plist))
+        for attn, _ in self.transformer.layers:
+            _check_no_backward_pre_hooks(attn.attend, "neurovit_amd.ViT")
+        if need_grad and self._attend_backward_hooked_layers():
+            # (the hooks themselves are looked up when the backward runs; what that backward could not serve is refused up front)
+            if self._fp8 is not None and self.fp8_training:
+                raise NotImplementedError("neurovit_amd.ViT: no backward hooks on `attend` through the fp8 training forward - disable_fp8() or "
+                                          "enable_fp8(training=False) first")
+            if self.training and self._dropout_p[0] > 0:
+                raise NotImplementedError("neurovit_amd.ViT: backward hooks on `attend` with attention dropout active (train mode, dropout > 0) - "
+                                          "the mask is not replayed into the gradient of the probabilities; run the attribution in eval mode")
         if input_grad:
             if vol_sigma is not None:
                 raise NotImplementedError("neurovit_amd.ViT: no gradient w.r.t. RAW volumes (vol_sigma / forward_raw): the folded z-score treats "
