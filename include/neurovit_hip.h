@@ -403,6 +403,27 @@ int nv_copy_2d_f32(const float* src, long ld_src, int rows, int cols, float* dst
 long nv_gradcam_workspace_bytes(int B, int n);
 int nv_gradcam_reduce(const void* act, const float* grad, int B, int n, int d, float* cam, float* minmax, void* workspace,
                       long ws_bytes, void* stream);
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) batched attribution volumes: every volume of the
+ * batch on its own, nothing leaves the device.
+ * nv_gradcam_reduce_per_volume: nv_gradcam_reduce with the min-max normalisation taken over each volume's own n - 1 cells; minmax
+ * (optional) [B, 2].  Volume b has the bits of nv_gradcam_reduce called with B = 1 on that volume's slice.  One launch.
+ * nv_token_map_to_volume: maps [B, G0 G1 G2] (token order, reshaped as is: NeuroEncoder.py:117-131) -> out [B, S0, S1, S2] fp32.
+ * grid3 / out3: HOST arrays {G0, G1, G2} / {S0, S1, S2}.  Per volume:
+ *   normalize = 1: (v - min) * (1 / (max - min + 1e-8)) over the volume's cells (0: the map is taken as it is);
+ *   cut = torch.quantile(cells.double(), 1 - keep_percent / 100, interpolation='linear') rounded to fp32: pos = q (N - 1), lo = floor(pos),
+ *     hi = min(lo + 1, N - 1), w = pos - lo, cut = s[lo] + w (s[hi] - s[lo]) for w < 0.5, else s[hi] - (s[hi] - s[lo]) (1 - w), in double,
+ *     s = the order statistics of the cells; cells >= cut are kept, the rest become 0 (keep_percent = 100 keeps everything);
+ *   trilinear upsampling G -> S with align_corners = False and ATen's index arithmetic: per axis src = max((dst + 0.5) (G / S) - 0.5, 0)
+ *     in fp32, i0 = floor(src), i1 = min(i0 + 1, G - 1), lambda1 = src - i0, lambda0 = 1 - lambda1.
+ * Maps hold finite values.  G0 G1 G2 <= 4096 (16^3) and G1 G2 + 2 S1 + 2 S2 <= 16384, NV_ERR_ARG beyond; out and workspace 16-byte aligned.
+ * Two launches: one workgroup per volume (selection in LDS), then a streaming kernel with 16-byte stores.  On return the workspace holds
+ * [B, N] normalised maps, [B, N] thresholded maps, [B] cuts (fp32, in this order), which a caller may read. */
+long nv_gradcam_per_volume_workspace_bytes(int B, int n);
+int nv_gradcam_reduce_per_volume(const void* act, const float* grad, int B, int n, int d, float* cam, float* minmax, void* workspace,
+                                 long ws_bytes, void* stream);
+long nv_token_map_to_volume_workspace_bytes(int B, const int* grid3);
+int nv_token_map_to_volume(const float* maps, int B, const int* grid3, const int* out3, int normalize, double keep_percent, float* out,
+                           void* workspace, long ws_bytes, void* stream);
 
 /* ---- the 4D model's temporal head (src/models/NeuroEncoder.py:60-66: temporal_transformer -> mean over time -> projection_head;
  * :207-217 TemporalTransformer = one nn.TransformerEncoderLayer(d_model 2, nhead 2, batch_first, post-norm, ReLU, dim_feedforward ff,

@@ -200,6 +200,73 @@ class NeuroEncoder(nn.Module):
         token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
         return self._token_map_to_volume(token_map), class_idx
 
+    # ---- batched attribution, on the device (csrc/attribution.hip): the three maps above for a whole batch, every volume on its own
+    def token_maps_to_volumes(self, token_maps, normalize=True, threshold=None):
+        """[B, G^3] maps of the patch tokens (device, token order) -> fp32 [B, S, S, S] on the device: what _token_map_to_volume does to
+        one CPU map, for every volume of the batch independently and without leaving the device (nv_token_map_to_volume) - min-max
+        normalisation over the volume's own cells (normalize), the top `threshold` % of its cells kept (None: GRADCAM_THRESHOLD;
+        torch.quantile's linear rule), trilinear upsampling to the volume.  The building block for any map on the patch grid."""
+        from . import ops
+        size = self.config['TRAINING_VIT_INPUT_SIZE']
+        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
+        keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
+        maps = token_maps.to(device=self.device, dtype=torch.float32).contiguous()
+        return ops.token_maps_to_volumes(maps, cells, size, normalize=normalize, keep_percent=keep_percent)
+
+    def attribution_volumes(self, x, method="gradcam", target=None, threshold=None, return_token_maps=False):
+        """Attribution volumes of a batch x [B, H, W, D]: (volumes fp32 [B, S, S, S] on the device, class_idx [B] on the device[, the
+        normalised token maps [B, G^3] on the device]).  method "gradcam" / "rollout" / "relevance" runs the GPU steps of
+        get_attention_map / get_attention_rollout / get_attention_relevance on the whole batch, in the module's current mode:
+          gradcam    one forward, logits.backward(one-hot) with one row per volume (the logits are per volume: volumes do not couple),
+                     the per-volume reduction nv_gradcam_reduce_per_volume.  As get_attention_map it runs the model's backward pass:
+                     a trainable model accumulates p.grad; a frozen one runs the data-only backward and touches none;
+          rollout    ViT.attention_rollout; `target` is ignored for the map, class_idx is the predicted class;
+          relevance  ViT.attention_relevance (one forward, one data-only backward; no p.grad is touched).
+        target: None = the predicted class of each volume, an int, or a LongTensor [B]; class_idx is the explained class.
+        Every volume is normalised, thresholded (threshold: percent of cells kept, None = GRADCAM_THRESHOLD) and upsampled on its own
+        (token_maps_to_volumes).  No tensor crosses PCIe and nothing synchronises with the host inside the call.
+        User-assigned `model.activations` / `model.gradients` overrides are NOT consulted (get_attention_map honours them)."""
+        from . import ops
+        if self.config['TRAINING_DIM'] != 3:
+            raise NotImplementedError("attribution_volumes: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
+        if method not in ("gradcam", "rollout", "relevance"):
+            raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout' or 'relevance', got {method!r}")
+        vit = self.volume_encoder.vit3d
+        volume = x.to(self.device)
+
+        def explained(logits):
+            if target is None:
+                return logits.argmax(dim=1)
+            if torch.is_tensor(target):
+                return target.to(logits.device).long().reshape(-1)
+            return torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
+
+        if method == "gradcam":
+            with torch.enable_grad():
+                if not (volume.requires_grad or any(p.requires_grad for p in vit.parameters())):
+                    volume = volume.detach().requires_grad_(True)       # a frozen model: the data-only backward delivers the hook gradient
+                logits = self.forward(volume)
+                class_idx = explained(logits.detach())
+                logits.backward(gradient=F.one_hot(class_idx, logits.shape[1]).to(logits.dtype))
+            token_maps, _ = ops.gradcam_reduce_per_volume(vit.last_attn_norm_output_raw(), vit.last_attn_norm_grad_raw())
+            normalize = False                                           # the reduction has normalised every volume
+        elif method == "rollout":
+            with torch.no_grad():
+                logits, token_maps = vit.attention_rollout(volume.permute(0, 3, 1, 2).unsqueeze(1))     # ViT3DEncoder.forward's view
+            class_idx, normalize = logits.argmax(dim=1), True
+        else:
+            logits, token_maps = vit.attention_relevance(volume.permute(0, 3, 1, 2).unsqueeze(1), target=target)
+            class_idx, normalize = explained(logits), True
+
+        size = self.config['TRAINING_VIT_INPUT_SIZE']
+        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
+        keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
+        volumes, (normalised, _, _) = ops.token_maps_to_volumes(token_maps.contiguous(), cells, size, normalize=normalize, keep_percent=keep_percent,
+                                                                return_maps=True)
+        if return_token_maps:
+            return volumes, class_idx, normalised
+        return volumes, class_idx
+
     def visualize_slice(self, cam_3d, original_volume):
         """One 2-D slice of the volume and of its CAM along GRADCAM_SLICE_DIM at GRADCAM_SLICE_IDX
         (contract of NeuroEncoder.py:135-168: returns (img, attn), or None after printing why not)."""

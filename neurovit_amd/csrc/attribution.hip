@@ -1,0 +1,320 @@
+// Batched, device-side attribution volumes: [B, n, d] taps or [B, N] token maps in, [B, S0, S1, S2] volumes out - the last step of
+// get_attention_map / get_attention_rollout / get_attention_relevance (src/models/NeuroEncoder.py:101-131) for a whole batch, every
+// volume on its own.
+//
+//   nv_gradcam_reduce_per_volume   the row arithmetic of nv_gradcam_reduce (gradcam.hip), min-max normalised over each volume's own cells
+//   nv_token_map_to_volume         per volume: min-max normalisation (optional) -> the percentile cut of torch.quantile(linear) ->
+//                                  threshold -> trilinear upsampling (align_corners = False, ATen's index arithmetic)
+//
+// The only real bytes are the B * S0 * S1 * S2 * 4 of the volumes: the upsampling is a streaming kernel with 16-byte stores along the
+// contiguous axis; everything in front of it works on <= 4096 cells per volume inside one workgroup's LDS.
+#include "common.h"
+
+namespace {
+// ------------------------------------------------------------------------------------------------ per-volume Grad-CAM reduction
+constexpr int GC_THREADS = 256;
+constexpr int GC_WAVES = GC_THREADS / 64;
+constexpr int GCV_MAX_BLOCKS = 128;      // workgroups per volume
+
+// Grid (blocks per volume, B).  The rows of volume b are dealt over its blocks; the volume's min / max crosses them through per-block
+// partials and ONE arrival ticket per volume (the agent-scope release / acquire of gradcam.hip): the last block of a volume to arrive
+// normalises that volume.  Row sums, min / max and the normalisation are the expressions of gradcam_reduce_kernel, so volume b has the
+// bits of nv_gradcam_reduce on its slice (min / max are exact in any order).
+template <typename T>
+__global__ __launch_bounds__(GC_THREADS) void gradcam_per_volume_kernel(const r16* __restrict__ act, const float* __restrict__ grad, int n, int d,
+                                                                        float* cam, float* __restrict__ part, unsigned* tickets, float* minmax) {
+  __shared__ float s_min[GC_WAVES], s_max[GC_WAVES];
+  __shared__ unsigned s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int N = n - 1, b = blockIdx.y, nb = gridDim.x;
+  float* vcam = cam + (long)b * N;
+  float* vpart = part + 2L * b * nb;
+  float lo = INFINITY, hi = 0.f;                         // relu output is >= 0
+  for (int r = blockIdx.x * GC_WAVES + wid; r < N; r += nb * GC_WAVES) {
+    const long base = ((long)b * n + r + 1) * d;         // token 0 is the cls token
+    float sg = 0.f, sa = 0.f;
+    for (int k = lane * 8; k < d; k += 64 * 8) {         // d % 8 == 0
+      const r16x8 a = *reinterpret_cast<const r16x8*>(act + base + k);
+      const f32x4 g0 = *reinterpret_cast<const f32x4*>(grad + base + k), g1 = *reinterpret_cast<const f32x4*>(grad + base + k + 4);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) sa += dec1<T>(a[j]);
+      sg += (g0[0] + g0[1]) + (g0[2] + g0[3]) + (g1[0] + g1[1]) + (g1[2] + g1[3]);
+    }
+    sg = wave_sum(sg); sa = wave_sum(sa);
+    const float v = fmaxf((sg / (float)d) * sa, 0.f);
+    if (lane == 0) vcam[r] = v;
+    lo = fminf(lo, v); hi = fmaxf(hi, v);
+  }
+  if (lane == 0) { s_min[wid] = lo; s_max[wid] = hi; }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < GC_WAVES; ++w) { lo = fminf(lo, s_min[w]); hi = fmaxf(hi, s_max[w]); }
+    vpart[2 * blockIdx.x] = lo; vpart[2 * blockIdx.x + 1] = hi;
+  }
+  // publish: every storing wave drains its stores, the workgroup meets, ONE lane releases at agent scope and takes a ticket
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned tk = __hip_atomic_fetch_add(tickets + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_last = (tk == (unsigned)nb - 1) ? 1u : 0u;
+    if (s_last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+  }
+  __syncthreads();
+  if (!s_last) return;
+  // last arriver of this volume: min / max of its partials, then normalise its map
+  lo = INFINITY; hi = 0.f;
+  for (int i = 0; i < nb; ++i) { lo = fminf(lo, vpart[2 * i]); hi = fmaxf(hi, vpart[2 * i + 1]); }
+  const float inv = 1.0f / (hi - lo + 1e-8f);
+  for (int i = tid; i < N; i += GC_THREADS) vcam[i] = (vcam[i] - lo) * inv;
+  if (tid == 0) {
+    if (minmax) { minmax[2 * b] = lo; minmax[2 * b + 1] = hi; }
+    tickets[b] = 0;                                       // self-reset (the caller also zeroes the tickets in front of every launch)
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ token maps -> thresholded maps
+constexpr int TM_THREADS = 256;
+constexpr int TM_MAX_CELLS = 4096;       // cells of one volume's grid: 16 KB of keys in LDS (16^3 = ViT3D-large)
+
+// order-preserving map of the fp32 bit patterns onto unsigned integers (and back)
+__device__ __forceinline__ unsigned key_of(float v) {
+  const unsigned u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+
+// The k-th smallest (0-based) of keys[0, N): radix select, eight bits per pass.  Every thread of the workgroup calls it and gets the key.
+__device__ unsigned select_kth(const unsigned* keys, int N, int k, unsigned* hist, unsigned* s_sel) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  unsigned prefix = 0, mask = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    hist[tid] = 0;                                         // TM_THREADS == 256 bins
+    __syncthreads();
+    for (int i = tid; i < N; i += TM_THREADS) {
+      const unsigned key = keys[i];
+      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {                                        // one wave: lane l owns bins 4l .. 4l + 3
+      const unsigned c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
+      const unsigned mine = c0 + c1 + c2 + c3;
+      unsigned incl = mine;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      const unsigned excl = incl - mine, kk = (unsigned)k;
+      if (excl <= kk && kk < incl) {                       // exactly one lane: the counts of the surviving keys sum to more than k
+        unsigned bin = 4 * lane, below = excl;
+        if (kk >= below + c0) { below += c0; ++bin;
+          if (kk >= below + c1) { below += c1; ++bin;
+            if (kk >= below + c2) { below += c2; ++bin; } } }
+        s_sel[0] = bin; s_sel[1] = kk - below;
+      }
+    }
+    __syncthreads();
+    prefix |= s_sel[0] << shift; mask |= 255u << shift;
+    k = (int)s_sel[1];
+    __syncthreads();                                       // s_sel and hist are rewritten by the next pass
+  }
+  return prefix;
+}
+
+// One workgroup per volume.  norm / sparse: [B, N] (the normalised map, and the same with the cells under the cut zeroed); cuts: [B].
+// (i_lo, i_hi, w): the position q (N - 1) of the quantile among the order statistics, split on the host in double.
+__global__ __launch_bounds__(TM_THREADS) void token_map_threshold_kernel(const float* __restrict__ maps, int N, int normalize, int i_lo, int i_hi, double w,
+                                                                         float* __restrict__ norm, float* __restrict__ sparse, float* __restrict__ cuts) {
+  __shared__ unsigned keys[TM_MAX_CELLS];
+  __shared__ unsigned hist[TM_THREADS];
+  __shared__ float s_red[2 * (TM_THREADS / 64)];
+  __shared__ unsigned s_sel[2], s_cnt, s_next;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const long off = (long)blockIdx.x * N;
+  float lo = INFINITY, hi = -INFINITY;
+  if (normalize) {
+    for (int i = tid; i < N; i += TM_THREADS) { const float v = maps[off + i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, 64)); hi = fmaxf(hi, __shfl_xor(hi, o, 64)); }
+    if (lane == 0) { s_red[2 * wid] = lo; s_red[2 * wid + 1] = hi; }
+    __syncthreads();
+    lo = s_red[0]; hi = s_red[1];
+    for (int v = 1; v < TM_THREADS / 64; ++v) { lo = fminf(lo, s_red[2 * v]); hi = fmaxf(hi, s_red[2 * v + 1]); }
+  }
+  const float inv = 1.0f / (hi - lo + 1e-8f);
+  for (int i = tid; i < N; i += TM_THREADS) {
+    float v = maps[off + i];
+    if (normalize) v = (v - lo) * inv;
+    norm[off + i] = v;
+    keys[i] = key_of(v);
+  }
+  if (tid == 0) { s_cnt = 0; s_next = 0xffffffffu; }
+  __syncthreads();
+  const unsigned k_lo = select_kth(keys, N, i_lo, hist, s_sel);
+  unsigned k_hi = k_lo;
+  if (i_hi != i_lo) {                                      // the next order statistic: k_lo again if it repeats, else the smallest key above it
+    unsigned cnt = 0, nxt = 0xffffffffu;
+    for (int i = tid; i < N; i += TM_THREADS) {
+      const unsigned key = keys[i];
+      if (key <= k_lo) ++cnt; else nxt = min(nxt, key);
+    }
+    atomicAdd(&s_cnt, cnt); atomicMin(&s_next, nxt);
+    __syncthreads();
+    k_hi = ((int)s_cnt > i_hi) ? k_lo : s_next;
+  }
+  // torch.quantile(interpolation='linear') = lerp(s[lo], s[hi], w) in double (ATen's lerp: two forms around w = 0.5), rounded to fp32
+  float cut;
+  {
+#pragma clang fp contract(off)
+    const double a = (double)value_of(k_lo), e = (double)value_of(k_hi);
+    const double c = (w < 0.5) ? a + w * (e - a) : e - (e - a) * (1.0 - w);
+    cut = (float)c;
+  }
+  for (int i = tid; i < N; i += TM_THREADS) {
+    const float v = value_of(keys[i]);
+    sparse[off + i] = (v >= cut) ? v : 0.f;
+  }
+  if (tid == 0) cuts[blockIdx.x] = cut;
+}
+
+// ------------------------------------------------------------------------------------------------ trilinear upsampling
+constexpr int UP_THREADS = 256;
+struct AxisTap { int i0, i1; float l0, l1; };
+
+// ATen's area_pixel_compute_source_index (align_corners = False) and linear taps of one output index; scale = (float)G / S
+__device__ __forceinline__ AxisTap axis_tap(int dst, float scale, int G) {
+#pragma clang fp contract(off)
+  AxisTap t;
+  const float src = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
+  t.i0 = min((int)src, G - 1);
+  t.i1 = min(t.i0 + 1, G - 1);
+  t.l1 = src - (float)t.i0;
+  t.l0 = 1.0f - t.l1;
+  return t;
+}
+
+// Grid (S0, B): one workgroup writes the S1 x S2 output plane (b, x).  It first collapses the x axis of the volume's grid into a
+// G1 x G2 plane in LDS and tabulates the y and z taps; every output then costs four LDS reads and three lerps.  The plane is written as
+// 16-byte stores over its flat extent (rows need not be multiples of four: the groups of four follow the alignment of `out`, the
+// few elements in front of the first / behind the last aligned group are stored singly).
+__global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const float* __restrict__ sparse, int G0, int G1, int G2, int S0, int S1, int S2,
+                                                                        float sc0, float sc1, float sc2, float* __restrict__ out) {
+  extern __shared__ float smem[];
+  float* plane = smem;                                     // [G1 * G2]
+  int* yi = reinterpret_cast<int*>(plane + G1 * G2);       // [S1]: i0 | i1 << 16
+  float* yl = reinterpret_cast<float*>(yi + S1);           // [S1]: lambda1
+  int* zi = reinterpret_cast<int*>(yl + S1);               // [S2]
+  float* zl = reinterpret_cast<float*>(zi + S2);           // [S2]
+  const int tid = threadIdx.x, x = blockIdx.x, b = blockIdx.y;
+  const AxisTap tx = axis_tap(x, sc0, G0);
+  const float* g0 = sparse + ((long)b * G0 + tx.i0) * G1 * G2;
+  const float* g1 = sparse + ((long)b * G0 + tx.i1) * G1 * G2;
+  for (int i = tid; i < G1 * G2; i += UP_THREADS) plane[i] = tx.l0 * g0[i] + tx.l1 * g1[i];
+  for (int i = tid; i < S1; i += UP_THREADS) { const AxisTap t = axis_tap(i, sc1, G1); yi[i] = (t.i0 * G2) | ((t.i1 * G2) << 16); yl[i] = t.l1; }
+  for (int i = tid; i < S2; i += UP_THREADS) { const AxisTap t = axis_tap(i, sc2, G2); zi[i] = t.i0 | (t.i1 << 16); zl[i] = t.l1; }
+  __syncthreads();
+
+  const long plane_elems = (long)S1 * S2;
+  const long base = ((long)b * S0 + x) * plane_elems;      // flat offset of the plane in `out`
+  float* o = out + base;
+  const int P = (int)plane_elems;
+  int head = (int)((4 - (base & 3)) & 3);                  // `out` is 16-byte aligned
+  if (head > P) head = P;
+  const int groups = (P - head) >> 2, tail = head + 4 * groups;
+
+  auto value = [&](int yy, float ly1, int z) -> float {     // (yy, ly1): the y taps of the row, read once per row
+    const int zz = zi[z];
+    const float lz1 = zl[z], ly0 = 1.0f - ly1, lz0 = 1.0f - lz1;
+    const int r0 = yy & 0xffff, r1 = yy >> 16, c0 = zz & 0xffff, c1 = zz >> 16;
+    const float a = lz0 * plane[r0 + c0] + lz1 * plane[r0 + c1];
+    const float c = lz0 * plane[r1 + c0] + lz1 * plane[r1 + c1];
+    return ly0 * a + ly1 * c;
+  };
+  for (int e = tid; e < head; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
+  for (int e = tail + tid; e < P; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
+  for (int g = tid; g < groups; g += UP_THREADS) {
+    const int e = head + 4 * g;
+    int y = e / S2, z = e - y * S2;
+    int yy = yi[y];
+    float ly1 = yl[y];
+    f32x4 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = value(yy, ly1, z);
+      if (++z == S2 && j < 3) { z = 0; ++y; yy = yi[y]; ly1 = yl[y]; }     // (a group may straddle rows; y < S1 because e + j < P)
+    }
+    *reinterpret_cast<f32x4*>(o + e) = v;
+  }
+}
+
+int gcv_blocks(int n) {
+  const int blocks = (n - 1 + GC_WAVES - 1) / GC_WAVES;
+  return blocks > GCV_MAX_BLOCKS ? GCV_MAX_BLOCKS : (blocks < 1 ? 1 : blocks);
+}
+long gcv_ticket_bytes(int B) { return ((4L * B + 15) / 16) * 16; }
+}  // namespace
+
+extern "C" long nv_gradcam_per_volume_workspace_bytes(int B, int n) {
+  if (B <= 0 || n <= 1) return -1;
+  return gcv_ticket_bytes(B) + 8L * B * gcv_blocks(n);
+}
+
+extern "C" int nv_gradcam_reduce_per_volume(const void* act, const float* grad, int B, int n, int d, float* cam, float* minmax, void* workspace,
+                                            long ws_bytes, void* stream) {
+  NV_CHECK_ARG(act && grad && cam && workspace && B > 0 && B <= 65535 && n > 1 && d > 0 && (d % 8) == 0,
+               "nv_gradcam_reduce_per_volume: bad arguments (d %% 8 == 0, n > 1, B <= 65535)");
+  NV_CHECK_ARG(nv_aligned16(act) && nv_aligned16(grad) && nv_aligned16(workspace), "nv_gradcam_reduce_per_volume: 16-byte alignment");
+  NV_CHECK_ARG(ws_bytes >= nv_gradcam_per_volume_workspace_bytes(B, n), "nv_gradcam_reduce_per_volume: workspace too small");
+  unsigned* tickets = (unsigned*)workspace;
+  float* part = (float*)((char*)workspace + gcv_ticket_bytes(B));
+  if (hipMemsetAsync(tickets, 0, gcv_ticket_bytes(B), (hipStream_t)stream) != hipSuccess) {
+    nv_set_error("nv_gradcam_reduce_per_volume: memset failed");
+    return NV_ERR_HIP;
+  }
+  NV_DISPATCH_OPERAND(T, hipLaunchKernelGGL(gradcam_per_volume_kernel<T>, dim3(gcv_blocks(n), B), dim3(GC_THREADS), 0, (hipStream_t)stream, (const r16*)act,
+                                            grad, n, d, cam, part, tickets, minmax));
+  NV_CHECK_LAUNCH("nv_gradcam_reduce_per_volume");
+  return NV_OK;
+}
+
+extern "C" long nv_token_map_to_volume_workspace_bytes(int B, const int* grid3) {
+  if (B <= 0 || !grid3 || grid3[0] <= 0 || grid3[1] <= 0 || grid3[2] <= 0) return -1;
+  const long N = (long)grid3[0] * grid3[1] * grid3[2];
+  return (2 * (long)B * N + B) * 4;
+}
+
+extern "C" int nv_token_map_to_volume(const float* maps, int B, const int* grid3, const int* out3, int normalize, double keep_percent, float* out,
+                                      void* workspace, long ws_bytes, void* stream) {
+  NV_CHECK_ARG(maps && grid3 && out3 && out && workspace && B > 0 && B <= 65535, "nv_token_map_to_volume: bad arguments (null pointer, or B outside [1, 65535])");
+  const int G0 = grid3[0], G1 = grid3[1], G2 = grid3[2], S0 = out3[0], S1 = out3[1], S2 = out3[2];
+  NV_CHECK_ARG(G0 > 0 && G1 > 0 && G2 > 0 && S0 > 0 && S1 > 0 && S2 > 0, "nv_token_map_to_volume: grid and output extents must be positive");
+  const long N = (long)G0 * G1 * G2;
+  NV_CHECK_ARG(N <= TM_MAX_CELLS, "nv_token_map_to_volume: grid %d x %d x %d has %ld cells, the kernel takes at most %d (16^3)", G0, G1, G2, N, TM_MAX_CELLS);
+  NV_CHECK_ARG(keep_percent >= 0.0 && keep_percent <= 100.0, "nv_token_map_to_volume: keep_percent %g outside [0, 100]", keep_percent);
+  const long lds = ((long)G1 * G2 + 2L * S1 + 2L * S2) * 4;
+  NV_CHECK_ARG(lds <= 65536 && (long)S1 * S2 < (1L << 31),
+               "nv_token_map_to_volume: output extents %d x %d x %d beyond the kernel's tables (G1 G2 + 2 S1 + 2 S2 <= 16384)", S0, S1, S2);
+  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned16(workspace) && (((uintptr_t)maps) & 3u) == 0, "nv_token_map_to_volume: out / workspace 16-byte aligned");
+  NV_CHECK_ARG(ws_bytes >= nv_token_map_to_volume_workspace_bytes(B, grid3), "nv_token_map_to_volume: workspace too small");
+  // position of the quantile among the N order statistics, as torch.quantile: q (N - 1) in double
+  const double q = 1.0 - keep_percent / 100.0, pos = q * (double)(N - 1);
+  int i_lo = (int)floor(pos);
+  if (i_lo > N - 1) i_lo = (int)N - 1;
+  const int i_hi = i_lo + 1 < N ? i_lo + 1 : (int)N - 1;
+  const double w = pos - (double)i_lo;
+  float* norm = (float*)workspace;
+  float* sparse = norm + (long)B * N;
+  float* cuts = sparse + (long)B * N;
+  hipLaunchKernelGGL(token_map_threshold_kernel, dim3(B), dim3(TM_THREADS), 0, (hipStream_t)stream, maps, (int)N, normalize ? 1 : 0, i_lo, i_hi, w, norm, sparse,
+                     cuts);
+  NV_CHECK_LAUNCH("nv_token_map_to_volume (threshold)");
+  hipLaunchKernelGGL(upsample_trilinear_kernel, dim3(S0, B), dim3(UP_THREADS), (size_t)lds, (hipStream_t)stream, sparse, G0, G1, G2, S0, S1, S2,
+                     (float)G0 / (float)S0, (float)G1 / (float)S1, (float)G2 / (float)S2, out);
+  NV_CHECK_LAUNCH("nv_token_map_to_volume (upsample)");
+  return NV_OK;
+}

@@ -484,6 +484,54 @@ def gradcam_reduce(act: torch.Tensor, grad: torch.Tensor):
     return cam, mm
 
 
+def gradcam_reduce_per_volume(act: torch.Tensor, grad: torch.Tensor):
+    """gradcam_reduce with every volume normalised over its own cells: act 16-bit [B, n, d], grad f32 [B, n, d] (device) ->
+    (cam f32 [B, n-1], minmax f32 [B, 2]); volume b has the bits of gradcam_reduce on that volume alone.  One launch."""
+    _need_cuda(act, grad)
+    assert act.dtype == op16() and grad.dtype == torch.float32 and act.shape == grad.shape and act.is_contiguous() and grad.is_contiguous()
+    B, n, d = act.shape
+    cam = torch.empty((B, n - 1), dtype=torch.float32, device=act.device)
+    mm = torch.empty((B, 2), dtype=torch.float32, device=act.device)
+    nb = lib.nv_gradcam_per_volume_workspace_bytes(B, n)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=act.device)
+    check(lib.nv_gradcam_reduce_per_volume(_p(act), _p(grad), B, n, d, _p(cam), _p(mm), _p(ws), nb, _stream()), "nv_gradcam_reduce_per_volume")
+    return cam, mm
+
+
+def _triple(v, what):
+    t = (int(v),) * 3 if isinstance(v, int) else tuple(int(e) for e in v)
+    if len(t) != 3:
+        raise ValueError(f"neurovit_amd: {what} must be an int or three ints, got {v!r}")
+    return t
+
+
+def token_maps_to_volumes(maps: torch.Tensor, grid, size, normalize: bool = True, keep_percent: float = 100.0, return_maps: bool = False,
+                          out: Optional[torch.Tensor] = None):
+    """maps f32 [B, G0*G1*G2] (device, token order) -> volumes f32 [B, S0, S1, S2]; grid / size: an int (cubic) or three.  Per volume:
+    min-max normalisation (normalize), the keep_percent % largest cells kept by torch.quantile's linear rule, trilinear upsampling
+    (align_corners=False): nv_token_map_to_volume, two launches.  return_maps: also (normalised maps [B, N], thresholded maps [B, N],
+    cuts [B]) - views of the call's workspace."""
+    _need_cuda(maps)
+    grid, size = _triple(grid, "grid"), _triple(size, "size")
+    N = grid[0] * grid[1] * grid[2]
+    assert maps.dim() == 2 and maps.shape[1] == N and maps.dtype == torch.float32 and maps.is_contiguous()
+    B = maps.shape[0]
+    g3, s3 = (ctypes.c_int * 3)(*grid), (ctypes.c_int * 3)(*size)
+    g3p, s3p = ctypes.cast(g3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p)
+    nb = lib.nv_token_map_to_volume_workspace_bytes(B, g3p)
+    if nb < 0:
+        raise ValueError(f"neurovit_amd: token_maps_to_volumes needs a non-empty batch and a positive grid, got B = {B}, grid = {grid}")
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=maps.device)
+    if out is None:
+        out = torch.empty((B,) + size, dtype=torch.float32, device=maps.device)
+    assert out.shape == (B,) + size and out.dtype == torch.float32 and out.is_contiguous() and out.device == maps.device
+    check(lib.nv_token_map_to_volume(_p(maps), B, g3p, s3p, int(bool(normalize)), float(keep_percent), _p(out), _p(ws), nb, _stream()),
+          "nv_token_map_to_volume")
+    if not return_maps:
+        return out
+    return out, (ws[:B * N].view(B, N), ws[B * N:2 * B * N].view(B, N), ws[2 * B * N:])
+
+
 def dropout_apply(x: torch.Tensor, drop_seed: int = 0, drop_p: float = 0.0, want16: bool = True, want32: bool = False):
     """x f32 [M, N] times the dropout mask of one site -> (bf16 copy or None, f32 copy or None)."""
     _need_cuda(x)
