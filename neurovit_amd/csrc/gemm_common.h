@@ -457,7 +457,9 @@ __device__ __forceinline__ void epilogue_lds(char* ctile, const GemmArgs& g, int
     const int lane = tid & 63, wave = tid >> 6;
     if (lane < CPR) *reinterpret_cast<f32x4*>(scr + wave * BN + lane * 4) = csum;
     __syncthreads();
-    if (tid < BN && n0 + tid < g.N) {
+    // m0 < M: the 256 x 256 kernel runs this once per 128-row pass, and the second pass of the last tile row may lie wholly beyond M -
+    // a partial row the caller's [ceil(M / tile rows), N] buffer does not have
+    if (tid < BN && n0 + tid < g.N && m0 < g.M) {
       float s = 0.f;
 #pragma unroll
       for (int w = 0; w < NT / 64; ++w) s += scr[w * BN + tid];

@@ -302,14 +302,14 @@ def site_seed(seed: int, site: int) -> int:
     return (seed ^ ((0x9E3779B97F4A7C15 * (site + 1)) & _M64)) & _M64
 
 
-def drop_mask(seed: int, p: float, shape) -> torch.Tensor:
-    """fp32 tensor of `shape` holding 0 or 1/(1-p); element index = row-major position (csrc/common.h::drop_factor4):
-    one 64-bit hash per group of four consecutive elements, one 16-bit field per element, keep iff field >= p * 2^16."""
+def drop_mask_at(seed: int, p: float, start: int, count: int) -> torch.Tensor:
+    """fp32 [count] holding 0 or 1/(1-p): the factors of the element indices start .. start + count - 1 of one site
+    (csrc/common.h::drop_factor4; the indices are 64-bit, so a range may lie beyond 2^32): one 64-bit hash per group of four
+    consecutive elements, one 16-bit field per element, keep iff field >= p * 2^16."""
     if p <= 0:
-        return torch.ones(shape)
-    n = int(np.prod(shape))
+        return torch.ones(count)
     with np.errstate(over="ignore"):
-        idx = np.arange(n, dtype=np.uint64)
+        idx = np.arange(count, dtype=np.uint64) + np.uint64(start)
         grp, lane = idx >> np.uint64(2), idx & np.uint64(3)
         x = ((grp + np.uint64(0x9E3779B97F4A7C15)) * np.uint64(0xBF58476D1CE4E5B9)) ^ np.uint64(seed)
         x ^= x >> np.uint64(30); x *= np.uint64(0xBF58476D1CE4E5B9)
@@ -318,7 +318,14 @@ def drop_mask(seed: int, p: float, shape) -> torch.Tensor:
         h = (x >> (np.uint64(16) * lane)) & np.uint64(0xFFFF)
     thresh = np.uint64(0x10000) if p >= 1 else np.uint64(int(np.float32(p).astype(np.float64) * 65536.0))
     scale = 0.0 if p >= 1 else float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
-    return torch.from_numpy(np.where(h >= thresh, np.float32(scale), np.float32(0)).astype(np.float32).reshape(shape))
+    return torch.from_numpy(np.where(h >= thresh, np.float32(scale), np.float32(0)).astype(np.float32))
+
+
+def drop_mask(seed: int, p: float, shape) -> torch.Tensor:
+    """fp32 tensor of `shape` holding 0 or 1/(1-p); element index = row-major position, from 0 (drop_mask_at)."""
+    if p <= 0:
+        return torch.ones(shape)
+    return drop_mask_at(seed, p, 0, int(np.prod(shape))).reshape(shape)
 
 
 def attn_drop_mask(seed: int, p: float, B: int, heads: int, n: int) -> torch.Tensor:

@@ -284,6 +284,26 @@ def test_gemm_256x256_kernel_forced(ops, M, N, K):
         lib.nv_gemm_set_tile(0, 0)
 
 
+@pytest.mark.parametrize("M", [257, 384, 2052])
+def test_gemm_256x256_column_sums_stay_inside_their_partial_rows(ops, M):
+    """The 256 x 256 kernel writes its fused column sums once per 128-row epilogue pass.  Where the second pass of the last tile row lies wholly
+    beyond M (M mod 256 in 1 .. 128) there is no partial row for it in the caller's [ceil(M / 128), N] buffer: rows placed behind the buffer
+    must stay untouched (the kernel used to write one row past it), and the rows inside it sum to the column sums of the stored values."""
+    from neurovit_amd._cabi import lib
+    N, K = 264, 64
+    A, Bt, u = dev(bf(rnd(M, K, seed=1))), dev(bf(rnd(K, N, seed=2, scale=K ** -0.5))), dev(bf(rnd(M, N, seed=3)))
+    lib.nv_gemm_set_tile(9, 0)
+    try:
+        rows = (M + 127) // 128
+        assert lib.nv_gemm_tile_rows(ops.NN, M, N, K, K, N) == 128
+        buf = torch.full((rows + 2, N), 7.0, device="cuda")
+        out = ops.gemm(ops.NN, ops.EPI_DGELU_COLSUM, A, Bt, aux_in=u, aux_out=buf[:rows])
+    finally:
+        lib.nv_gemm_set_tile(0, 0)
+    assert bool((buf[rows:] == 7.0).all())
+    assert_close_f32(buf[:rows].sum(0), out.double().sum(0), "pq.colsum", 1e-5)
+
+
 def test_weight_gradient_bf16_mirror_and_cast_ranges(ops):
     """Data-parallel message path: the fp32-store epilogue also writes a bf16 copy of what it stored (single TN launch, grouped
     launch, with accumulation: the mirror is the rounded SUM), bit-equal to casting the fp32 result; nv_cast_ranges_bf16 converts the

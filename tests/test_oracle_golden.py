@@ -295,3 +295,30 @@ def test_dropout_mask_generator_statistics():
     a = ref_cpu.attn_drop_mask(9, 0.3, 1, 2, 5)               # n = 5 -> rows padded to 8 in the index space
     full = ref_cpu.drop_mask(9, 0.3, (1, 2, 5, 8))
     assert a.shape == (1, 2, 5, 5) and torch.equal(a, full[..., :5])
+
+
+def test_drop_mask_at_is_drop_mask_on_an_index_range():
+    """ref_cpu.drop_mask_at (the hash over an index range that need not start at 0): equal to the matching slice of drop_mask for
+    starts inside and across a group of four, and - beyond 2^32, where no drop_mask can be built - equal to csrc/common.h::drop_factor
+    restated on Python integers (no fixed-width arithmetic to truncate)."""
+    seed, p = ref_cpu.site_seed(123456789, 5), 0.1
+    assert seed > 1 << 32
+    full = ref_cpu.drop_mask(seed, p, (4096,))
+    for start, count in ((0, 4096), (1000, 96), (1001, 7), (1003, 1), (4093, 3)):
+        assert torch.equal(ref_cpu.drop_mask_at(seed, p, start, count), full[start:start + count]), (start, count)
+    assert torch.equal(ref_cpu.drop_mask_at(seed, 0.0, 5, 3), torch.ones(3))
+
+    def factor(idx):
+        M = (1 << 64) - 1
+        x = ((((idx >> 2) + 0x9E3779B97F4A7C15) * 0xBF58476D1CE4E5B9) & M) ^ seed
+        x ^= x >> 30; x = (x * 0xBF58476D1CE4E5B9) & M
+        x ^= x >> 27; x = (x * 0x94D049BB133111EB) & M
+        x ^= x >> 31
+        field = (x >> (16 * (idx & 3))) & 0xFFFF
+        return float(np.float32(1) / (np.float32(1) - np.float32(p))) if field >= int(float(np.float32(p)) * 65536.0) else 0.0
+
+    for start in ((1 << 32) - 37, (1 << 32) + 2, 263 * 4097 * 4100 + 4096, (1 << 40) + 1):
+        got = ref_cpu.drop_mask_at(seed, p, start, 64)
+        assert got.tolist() == [factor(start + i) for i in range(64)], start
+    low = ref_cpu.drop_mask_at(seed, p, 2, 64)                                  # the index is not reduced modulo 2^32
+    assert not torch.equal(ref_cpu.drop_mask_at(seed, p, (1 << 32) + 2, 64), low)
