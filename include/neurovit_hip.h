@@ -386,6 +386,29 @@ int nv_head_step_scaled(const float* x, long row_stride, int B, int d, const flo
                         float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma,
                         float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
                         unsigned long drop_seed, float drop_p, void* stream);
+/* ---- global-norm gradient clipping on the device: scaler.unscale_(opt); torch.nn.utils.clip_grad_norm_(params, max_norm); scaler.step(opt)
+ * with the norm never read by the host.  `clip_state`: NV_GRAD_CLIP_BYTES of device memory owned by the caller, 8-byte aligned and
+ * ZEROED once before the first use.  As floats: [0..1] = one double, the running sum of squares; [2] = total_norm and [3] = coef of
+ * the last finished step; [4..15] reserved; from [16] on NV_GRAD_CLIP_MAX_BLOCKS doubles, one partial per workgroup (common.h GC_*).
+ * Per optimizer step:
+ *   nv_grad_sumsq(grad, is16, count, clip_state, scale_state, max_blocks)   once per gradient buffer (arena, 16-bit reduced message
+ *                        buffer, stock tensor; any count >= 1, element-aligned): running sum += sum x^2, every element widened to
+ *                        double first - finite fp32 gradients always give a finite sum, and bits reproduce from run to run (no
+ *                        atomics).  scale_state (may be NULL): found_inf is raised when the sum is not finite, so with a dynamic
+ *                        loss scale this pass REPLACES nv_loss_scale_check.  max_blocks > 0 caps the grid.
+ *   nv_loss_scale_update (only with a dynamic loss scale) - before the next call, which reads the 1 / scale it writes
+ *   nv_grad_clip_finish(clip_state, max_norm, grad_scale, scale_state)      total_norm = sqrt(sum) * |grad_scale| * (scale_state ?
+ *                        1 / scale : 1) as fp32;  coef = min(max_norm / (total_norm + 1e-6), 1) in fp32 as clip_grad_norm_ forms it
+ *                        (infinite norm: 0, NaN norm: NaN, exactly 1 when the bound does not bind);  running sum = 0
+ *   nv_adamw_step_clipped(..., scale_state, clip_state, stream)             nv_adamw_step_scaled (scale_state may be NULL) whose
+ *                        gradient factor is also multiplied by coef.  The gradients themselves are left as they are. */
+#define NV_GRAD_CLIP_MAX_BLOCKS 2048
+#define NV_GRAD_CLIP_BYTES (64 + 8 * NV_GRAD_CLIP_MAX_BLOCKS)
+int nv_grad_sumsq(const void* grad, int grad_16bit, long count, float* clip_state, float* scale_state, int max_blocks, void* stream);
+int nv_grad_clip_finish(float* clip_state, float max_norm, float grad_scale, const float* scale_state, void* stream);
+int nv_adamw_step_clipped(float* p, const void* grad, int grad_bf16, float* m, float* v, void* p16, long count, int step, double lr,
+                          double beta1, double beta2, double eps, double weight_decay, float grad_scale, int max_blocks,
+                          const float* scale_state, const float* clip_state, void* stream);
 /* grad_bf16 = 1: `grad` is a bf16 buffer (the gradient all-reduce ran on bf16 messages): no cast back to fp32 is needed. */
 /* max_blocks > 0 caps the grid (256-thread workgroups, grid-stride): used when the update of one gradient bucket runs on a
    side stream beside the backward pass, so that it takes a slice of the chip instead of queueing ahead of the GEMMs. */

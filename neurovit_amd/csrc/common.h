@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include <type_traits>
 
 // 16-bit MFMA operand formats.  Buffers, LDS images and register fragments carry RAW 16-bit words (r16 ...): loads, LDS-DMA, swizzles and
 // transposed reads are format-agnostic.  The element format T - bf16_t (default) or fp16_t (the reference's own autocast arithmetic,
@@ -247,6 +248,12 @@ enum { LS_SCALE = 0,       // what the NEXT loss gradient is multiplied by
        LS_STEPS = 5,       // optimizer updates applied so far (AdamW's t; skipped steps do not count - as with GradScaler + torch.optim)
        LS_STEP_SIZE = 6, LS_BC2_SQRT = 7,      // lr / (1 - beta1^t), sqrt(1 - beta2^t) of the current update
        LS_GROWTH = 8, LS_BACKOFF = 9, LS_INTERVAL = 10, LS_SKIPPED = 11 };
+
+// ---- gradient-norm clipping: FLOAT indices into the device block of nv_grad_sumsq / nv_grad_clip_finish (grad_clip.hip; NV_GRAD_CLIP_BYTES)
+enum { GC_SUMSQ = 0,       // a DOUBLE (floats 0 and 1): running sum of squares of the gradients summed since the last nv_grad_clip_finish
+       GC_TOTAL_NORM = 2,  // norm of the un-scaled gradient of the last finished step (what clip_grad_norm_ returns)
+       GC_COEF = 3,        // min(max_norm / (total_norm + 1e-6), 1) of that step: AdamW's extra grad factor
+       GC_PARTIALS = 16 }; // NV_GRAD_CLIP_MAX_BLOCKS doubles: one partial sum per workgroup of the last nv_grad_sumsq launch
 
 // ---- AdamW (torch.optim.AdamW, Trainer.py:31,75), shared by the streaming kernel (optim.hip) and the weight-gradient GEMM epilogue
 // that applies the update in place (gemm_common.h EPI_ADAMW): ONE definition, so both forms produce the same bits.

@@ -24,10 +24,15 @@ __device__ __forceinline__ bool adam_dyn(AdamArgs& a, const float* __restrict__ 
   a.step_size = dyn[LS_STEP_SIZE]; a.bc2_sqrt = dyn[LS_BC2_SQRT]; a.grad_scale *= dyn[LS_UNSCALE];
   return true;
 }
-template <bool G16, typename T>
+// CLIP: the gradient factor is also multiplied by the clipping coefficient of this step, read from the device block of
+// nv_grad_clip_finish (grad_clip.hip) - exactly 1.0f when the norm is inside the bound, so a clip that does not bind changes no bit.
+// (`clip` is not read without the flag: those instantiations are the kernels they were, with eight more bytes of arguments)
+template <bool G16, typename T, bool CLIP = false>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const void* __restrict__ grad, float* __restrict__ m,
-                                                    float* __restrict__ v, r16* __restrict__ p16, long n4, AdamArgs a, const float* __restrict__ dyn) {
+                                                    float* __restrict__ v, r16* __restrict__ p16, long n4, AdamArgs a, const float* __restrict__ dyn,
+                                                    const float* __restrict__ clip) {
   if (!adam_dyn(a, dyn)) return;
+  if constexpr (CLIP) a.grad_scale *= clip[GC_COEF];
   // grid-stride: a full-size grid runs one iteration per thread; a capped grid (max_blocks) streams the range with a
   // fraction of the chip's wave slots so that it can run beside compute-bound kernels of another stream
   constexpr int U = NV_ADAMW_UNROLL;
@@ -71,6 +76,13 @@ extern "C" int nv_adamw_step(float* p, const void* grad, int grad_bf16, float* m
 extern "C" int nv_adamw_step_scaled(float* p, const void* grad, int grad_bf16, float* m, float* v, void* p16, long count, int step, double lr,
                                     double beta1, double beta2, double eps, double weight_decay, float grad_scale, int max_blocks,
                                     const float* scale_state, void* stream) {
+  return nv_adamw_step_clipped(p, grad, grad_bf16, m, v, p16, count, step, lr, beta1, beta2, eps, weight_decay, grad_scale, max_blocks, scale_state, nullptr, stream);
+}
+
+// clip_state == NULL: the launches of nv_adamw_step_scaled.
+extern "C" int nv_adamw_step_clipped(float* p, const void* grad, int grad_bf16, float* m, float* v, void* p16, long count, int step, double lr,
+                                     double beta1, double beta2, double eps, double weight_decay, float grad_scale, int max_blocks,
+                                     const float* scale_state, const float* clip_state, void* stream) {
   NV_CHECK_ARG(count > 0 && (count % 4) == 0 && step >= 1, "nv_adamw_step: count=%ld must be a positive multiple of 4", count);
   NV_CHECK_ARG(nv_aligned16(p) && (grad_bf16 ? ((uintptr_t)grad & 7) == 0 : nv_aligned16(grad)) && nv_aligned16(m) && nv_aligned16(v) &&
                    (!p16 || ((uintptr_t)p16 & 7) == 0),
@@ -79,9 +91,13 @@ extern "C" int nv_adamw_step_scaled(float* p, const void* grad, int grad_bf16, f
   const long n4 = count / 4;
   long blocks = (n4 + 256L * NV_ADAMW_UNROLL - 1) / (256L * NV_ADAMW_UNROLL);
   if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+  const float* no_clip = nullptr;
+  const dim3 grid((unsigned)blocks), wg(256);
   NV_DISPATCH_OPERAND(T,
-    if (grad_bf16) hipLaunchKernelGGL((adamw_kernel<true, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state);
-    else hipLaunchKernelGGL((adamw_kernel<false, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state));
+    if (clip_state && grad_bf16) hipLaunchKernelGGL((adamw_kernel<true, T, true>), grid, wg, 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state, clip_state);
+    else if (clip_state) hipLaunchKernelGGL((adamw_kernel<false, T, true>), grid, wg, 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state, clip_state);
+    else if (grad_bf16) hipLaunchKernelGGL((adamw_kernel<true, T>), grid, wg, 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state, no_clip);
+    else hipLaunchKernelGGL((adamw_kernel<false, T>), grid, wg, 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state, no_clip));
   NV_CHECK_LAUNCH("nv_adamw_step");
   return NV_OK;
 }

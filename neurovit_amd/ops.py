@@ -433,13 +433,40 @@ def ce_loss(logits: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0,
     return loss, dl
 
 
-def adamw_step(p, grad, m, v, p16, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_blocks=0, scale_state=None):
+def adamw_step(p, grad, m, v, p16, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_blocks=0, scale_state=None,
+               clip_state=None):
     """grad may be fp32 or the 16-bit operand format (same numel as p).  scale_state: device block of a dynamic loss scale
     (optim.LossScaler.state) - the launch then does nothing when that step is skipped, un-scales the gradients and takes the step
-    count / bias corrections from the block (`step` is ignored)."""
+    count / bias corrections from the block (`step` is ignored).  clip_state: device block of optim.GradClipper - the gradients are
+    also multiplied by the clipping coefficient it holds (nv_adamw_step_clipped)."""
     assert grad.dtype in (torch.float32, op16()) and grad.numel() == p.numel()
-    check(lib.nv_adamw_step_scaled(_p(p), _p(grad), int(grad.dtype == op16()), _p(m), _p(v), _p(p16), p.numel(), max(int(step), 1), lr, betas[0], betas[1],
-                                   eps, weight_decay, grad_scale, int(max_blocks), _p(scale_state), _stream()), "nv_adamw_step")
+    if clip_state is None:
+        check(lib.nv_adamw_step_scaled(_p(p), _p(grad), int(grad.dtype == op16()), _p(m), _p(v), _p(p16), p.numel(), max(int(step), 1), lr, betas[0], betas[1],
+                                       eps, weight_decay, grad_scale, int(max_blocks), _p(scale_state), _stream()), "nv_adamw_step")
+    else:
+        check(lib.nv_adamw_step_clipped(_p(p), _p(grad), int(grad.dtype == op16()), _p(m), _p(v), _p(p16), p.numel(), max(int(step), 1), lr, betas[0], betas[1],
+                                        eps, weight_decay, grad_scale, int(max_blocks), _p(scale_state), _p(clip_state), _stream()), "nv_adamw_step_clipped")
+
+
+GRAD_CLIP_FLOATS = (64 + 8 * 2048) // 4      # NV_GRAD_CLIP_BYTES / 4 (include/neurovit_hip.h)
+GC_TOTAL_NORM, GC_COEF = 2, 3                # float indices into that block (csrc/common.h GC_*)
+
+
+def grad_sumsq(grad: torch.Tensor, clip_state: torch.Tensor, scale_state: Optional[torch.Tensor] = None, max_blocks: int = 0) -> None:
+    """clip_state's running sum of squares += sum of grad ** 2, summed in double (nv_grad_sumsq).  grad: contiguous, fp32 or the
+    16-bit operand format, any element alignment.  scale_state: found_inf is raised when the sum is not finite."""
+    _need_cuda(grad, clip_state, scale_state)
+    assert grad.dtype in (torch.float32, op16()) and grad.is_contiguous()
+    assert clip_state.dtype == torch.float32 and clip_state.numel() >= GRAD_CLIP_FLOATS and clip_state.is_contiguous()
+    if grad.numel():
+        check(lib.nv_grad_sumsq(_p(grad), int(grad.dtype != torch.float32), grad.numel(), _p(clip_state), _p(scale_state), int(max_blocks), _stream()),
+              "nv_grad_sumsq")
+
+
+def grad_clip_finish(clip_state: torch.Tensor, max_norm: float, grad_scale: float = 1.0, scale_state: Optional[torch.Tensor] = None) -> None:
+    """total_norm and coef of the gradients summed since the last call (nv_grad_clip_finish); clears the running sum."""
+    _need_cuda(clip_state, scale_state)
+    check(lib.nv_grad_clip_finish(_p(clip_state), float(max_norm), float(grad_scale), _p(scale_state), _stream()), "nv_grad_clip_finish")
 
 
 def loss_scale_init(state: torch.Tensor, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, start_step=0) -> None:

@@ -8,6 +8,7 @@ bf16 shadow the MFMA kernels read); the 4D model's temporal head is a second, 10
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List
 
 import torch
@@ -54,6 +55,43 @@ class LossScaler:
         return bool(self.state[3] != 0)
 
 
+def check_max_norm(max_norm) -> float:
+    """max_norm of gradient clipping: a finite number > 0 (ValueError otherwise)."""
+    try:
+        value = float(max_norm)
+    except (TypeError, ValueError):
+        raise ValueError(f"max_grad_norm must be a finite number > 0, got {max_norm!r}")
+    if isinstance(max_norm, bool) or not math.isfinite(value) or value <= 0.0:
+        raise ValueError(f"max_grad_norm must be a finite number > 0, got {max_norm!r}")
+    return value
+
+
+class GradClipper:
+    """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2) kept on the DEVICE, for the fused AdamW: the squares of every
+    gradient buffer are summed in double by one streaming pass each (`add`), `finish` turns the sum into the norm of the un-scaled
+    gradient and the coefficient min(max_norm / (norm + 1e-6), 1), and FusedAdamW.step(clip=...) multiplies the gradients by that
+    coefficient INSIDE the update - the gradient buffers keep the raw values.  Nothing is read back: `total_norm` and `coef` are 0-dim
+    fp32 views of the device block (csrc/grad_clip.hip), valid after `finish` in stream order.  With a LossScaler the summing pass also
+    raises its inf / NaN flag, so no separate overflow check reads the arena."""
+
+    def __init__(self, device, max_norm: float):
+        self.max_norm = check_max_norm(max_norm)
+        self.state = torch.zeros(ops.GRAD_CLIP_FLOATS, dtype=torch.float32, device=device)
+        self.total_norm = self.state[ops.GC_TOTAL_NORM]
+        self.coef = self.state[ops.GC_COEF]
+
+    def add(self, tensor: torch.Tensor, scaler: "LossScaler" = None, max_blocks: int = 0) -> None:
+        """Running sum of squares += sum of tensor ** 2 (fp32 or the current 16-bit operand format; any other dtype is widened to fp32)."""
+        if tensor.dtype not in (torch.float32, ops.op16()):
+            tensor = tensor.float()
+        ops.grad_sumsq(tensor.contiguous().view(-1), self.state, None if scaler is None else scaler.state, max_blocks)
+
+    def finish(self, grad_scale: float = 1.0, scaler: "LossScaler" = None) -> None:
+        """Norm and coefficient of what was added: the summed gradients carry 1 / grad_scale (data-parallel sum, static loss scale) and,
+        with `scaler`, its loss scale - call after scaler.update, which is what writes the 1 / scale of these gradients."""
+        ops.grad_clip_finish(self.state, self.max_norm, grad_scale, None if scaler is None else scaler.state)
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, model: torch.nn.Module = None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
@@ -97,17 +135,40 @@ class FusedAdamW(torch.optim.Optimizer):
         self._bound = True
 
     @torch.no_grad()
-    def step(self, closure=None, grad_scale: float = 1.0, reduced_bf16=None, scaler: "LossScaler" = None):
+    def step(self, closure=None, grad_scale: float = 1.0, reduced_bf16=None, scaler: "LossScaler" = None, clip: "GradClipper" = None):
         """reduced_bf16: {id(vit): flat bf16 gradient buffer} - when the data-parallel all-reduce ran on bf16 messages the
         optimizer reads the reduced gradients straight from that buffer (no cast back into the fp32 gradient arena).
         scaler: a LossScaler whose scale the gradients carry (GradScaler.step + GradScaler.update, Trainer.py:75-76): every arena's
-        gradients are checked for inf / NaN, then the update is applied - un-scaled - or skipped, all on the device."""
+        gradients are checked for inf / NaN, then the update is applied - un-scaled - or skipped, all on the device.
+        clip: a GradClipper (scaler.unscale_(opt); clip_grad_norm_(params, max_norm); scaler.step(opt)): the squares of every arena -
+        or of its reduced 16-bit buffer - and of every stock gradient are summed (with a scaler that pass is the inf / NaN check as
+        well), the scaler decides, the coefficient is formed from the norm of the un-scaled gradients (sqrt(sum) * |grad_scale| / loss
+        scale - every summed buffer is taken to carry the same factors) and each update multiplies its gradients by it.  The
+        gradient buffers themselves keep the raw values, except stock parameters' .grad, which is multiplied in place."""
         if not self._bound:
             self._bind()
         self._steps += 1
         g0 = self.param_groups[0]
         live = [h for h in self._arenas if not self._no_gradients(h)]
-        if scaler is not None:
+        if clip is not None:
+            for holder in live:
+                if hasattr(holder, "gather_foreign_grads"):
+                    holder.gather_foreign_grads()
+                red = None if reduced_bf16 is None else reduced_bf16.get(id(holder))
+                _cabi.set_operand_format(getattr(holder, "operands", "bf16"))      # what a 16-bit reduced buffer holds
+                summed = holder.flat_gradients() if red is None else red
+                for o, const in getattr(holder, "_phantom", ()):      # arena slots that are no parameter (the nn.Identity to_out of a heads == 1 ViT):
+                    summed[o:o + const.numel()].zero_()                # what the backward pass left there is no gradient of the model
+                clip.add(summed, scaler)
+            if self._rest is not None:
+                for g in self._rest.param_groups:
+                    for p in g["params"]:
+                        if p.grad is not None:
+                            clip.add(p.grad.float(), scaler)
+            if scaler is not None:
+                scaler.update(g0["lr"], g0["betas"])
+            clip.finish(grad_scale, scaler)
+        elif scaler is not None:
             for holder in live:
                 if hasattr(holder, "gather_foreign_grads"):
                     holder.gather_foreign_grads()
@@ -120,7 +181,7 @@ class FusedAdamW(torch.optim.Optimizer):
                             scaler.check(p.grad.contiguous().float())
             scaler.update(g0["lr"], g0["betas"])
         for holder in live:
-            self._step_arena(holder, grad_scale, None if reduced_bf16 is None else reduced_bf16.get(id(holder)), scaler)
+            self._step_arena(holder, grad_scale, None if reduced_bf16 is None else reduced_bf16.get(id(holder)), scaler, clip)
         if self._rest is not None:
             if scaler is not None:
                 if scaler.last_step_skipped():          # (stock parameters beside a scaled arena: the one place that reads the flag back)
@@ -129,6 +190,11 @@ class FusedAdamW(torch.optim.Optimizer):
                     for p in g["params"]:
                         if p.grad is not None:
                             p.grad.mul_(scaler.state[1])
+            if clip is not None:
+                for g in self._rest.param_groups:
+                    for p in g["params"]:
+                        if p.grad is not None:
+                            p.grad.mul_(clip.coef)
             for g in self._rest.param_groups:
                 g["lr"] = g0["lr"]
             self._rest.step()
@@ -175,7 +241,7 @@ class FusedAdamW(torch.optim.Optimizer):
         as a whole.  (A PARTIALLY populated arena is stepped with zeros for the missing gradients: see TemporalHead.gather_foreign_grads.)"""
         return all(p.grad is None for p in holder._plist)
 
-    def _step_arena(self, holder, grad_scale, reduced=None, scaler=None):
+    def _step_arena(self, holder, grad_scale, reduced=None, scaler=None, clip=None):
         arena, shadow = holder.flat_parameters()
         grads = holder.flat_gradients()
         if hasattr(holder, "gather_foreign_grads"):
@@ -184,7 +250,7 @@ class FusedAdamW(torch.optim.Optimizer):
         g0 = self.param_groups[0]
         _cabi.set_operand_format(getattr(holder, "operands", "bf16"))      # the format of the shadow this launch rewrites
         ops.adamw_step(arena, grads if reduced is None else reduced, m, v, shadow, self._steps, g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"], grad_scale,
-                       scale_state=None if scaler is None else scaler.state)
+                       scale_state=None if scaler is None else scaler.state, clip_state=None if clip is None else clip.state)
         holder.mark_shadow_fresh()
 
     @torch.no_grad()

@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from .NeuroEncoder import NeuroEncoder
 from .nn import CrossEntropyLoss
-from .optim import FusedAdamW, LossScaler
+from .optim import FusedAdamW, GradClipper, LossScaler, check_max_norm
 from .parallel import GradSync, NativeComm, broadcast_parameters
 
 
@@ -29,7 +29,18 @@ class TrainStep:
     def __init__(self, model: NeuroEncoder, lr: Optional[float] = None, weight_decay: Optional[float] = None, process_group=None,
                  n_buckets: int = 4, accumulation_steps: int = 1, overlap_optimizer: bool = False,
                  grad_comm_dtype: torch.dtype = torch.float32, grad_comm_algo: Optional[str] = None, fuse_update: Optional[int] = None,
-                 loss_scale=None, native_dp: Optional[bool] = None):
+                 loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None):
+        # max_grad_norm: None = off; a finite number > 0 = torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) between the
+        # backward pass and the update, on the device (optim.GradClipper): with a loss scale the norm is that of the UN-SCALED gradients
+        # (scaler.unscale_ before the clip), data parallel that of the world-averaged ones, with accumulation that of the window's sum.
+        # The clip is applied INSIDE the update, as the static loss scale's 1 / scale is: .grad and the gradient arena keep the raw,
+        # unclipped (and still scaled) gradients.  last_grad_norm (the pre-clip norm, what clip_grad_norm_ returns) and last_clip_coef
+        # are device tensors - reading them is the caller's synchronisation, the step has none.  The coefficient needs the whole norm
+        # before the first update: AdamW runs once behind the backward pass (fuse_update resolves to 0, no captured-graph replay, no
+        # overlap_optimizer), and world > 1 takes the Python-driven bucket pipeline instead of the native data-parallel plan.
+        if max_grad_norm is not None:
+            max_grad_norm = check_max_norm(max_grad_norm)
+            assert not overlap_optimizer, "max_grad_norm: the clipping coefficient needs the norm of ALL gradients before any update - no per-bucket optimizer updates"
         cfg = model.config
         # native_dp: world > 1 - the step stays ONE native call (nv_vit_train_step with an nv_dp_plan: RCCL all-reduce per bucket issued
         # from native code on a communicator of the library's own, AdamW behind it) instead of the Python-driven staged backward;
@@ -92,7 +103,7 @@ class TrainStep:
         self._dp_buckets, self._dp_msg16 = n_buckets, grad_comm_dtype != torch.float32
         want_native_dp = (os.environ.get("NEUROVIT_NATIVE_DP", "1") != "0") if native_dp is None else bool(native_dp)
         dev_ = next(model.parameters()).device
-        if want_native_dp and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev_.type == "cuda" \
+        if want_native_dp and max_grad_norm is None and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev_.type == "cuda" \
                 and (not dist.is_initialized() or dist.get_backend(process_group) == "nccl"):
             try:
                 self._ncomm = NativeComm(dev_, process_group)
@@ -129,6 +140,8 @@ class TrainStep:
         else:
             self.static_scale = float(loss_scale)
             assert self.static_scale >= 0.0, "loss_scale: None, 'dynamic' or a non-negative number"
+        self.max_grad_norm = max_grad_norm
+        self.clipper = None if max_grad_norm is None else GradClipper(dev0, max_grad_norm)
         self.last_path = None                          # "native" | "general": which path the most recent step took (last_fuse_update: where AdamW ran)
         self._all_modules = list(model.modules())
         self._head = getattr(model, "_temporal_head", None)            # 4D: its 16 parameters are one arena (temporal.TemporalHead)
@@ -136,6 +149,17 @@ class TrainStep:
         if self._head is not None:
             self._head.flat_parameters()
             self._head_ids = {id(p) for p in self._head._plist}
+
+    @property
+    def last_grad_norm(self) -> Optional[torch.Tensor]:
+        """Pre-clip norm of the un-scaled, world-averaged gradient of the most recent optimizer step (0-dim fp32 device tensor, a view
+        that the next step overwrites; None without max_grad_norm) - the value clip_grad_norm_ returns.  Non-finite on a skipped step."""
+        return None if self.clipper is None else self.clipper.total_norm
+
+    @property
+    def last_clip_coef(self) -> Optional[torch.Tensor]:
+        """min(max_grad_norm / (last_grad_norm + 1e-6), 1) of that step, the factor its update applied (device tensor; None when off)."""
+        return None if self.clipper is None else self.clipper.coef
 
     def _bucket_update(self, begin: int, end: int):
         gs = 1.0 / self.world
@@ -202,7 +226,7 @@ class TrainStep:
         for the graph.  The returned loss / logits tensors are the graph's own outputs: the next replay of the same graph overwrites
         them (clone what must outlive the next step - as with any captured graph)."""
         vit, opt = self._vit, self.optimizer
-        if not self._graphs_on or self.accumulation_steps != 1 or vit._dropout_p != (0.0, 0.0) or self.scaler is not None:
+        if not self._graphs_on or self.accumulation_steps != 1 or vit._dropout_p != (0.0, 0.0) or self.scaler is not None or self.clipper is not None:
             return None
         if vit._grads is None:
             vit._grads = torch.zeros_like(vit._arena)
@@ -278,8 +302,8 @@ class TrainStep:
         fuse = self.fuse_update
         if fuse is None:
             fuse = 3 if fmri.shape[0] * vit.pos_embedding.shape[1] <= self.FUSE_MAX_ROWS else 0
-        if self.accumulation_steps != 1 or vit._phantom or self.scaler is not None:
-            fuse = 0                        # (a dynamic loss scale decides after the backward pass whether the update is applied)
+        if self.accumulation_steps != 1 or vit._phantom or self.scaler is not None or self.clipper is not None:
+            fuse = 0                        # (a dynamic loss scale decides after the backward pass whether the update is applied; the clipping coefficient exists only then)
         dp = None
         if self._ncomm is not None:
             fuse = 0                        # the update follows the all-reduce: per bucket on the communication stream, or once at the end
@@ -288,10 +312,11 @@ class TrainStep:
         self.last_path = "native" if dp is None else "native-dp"
         accumulate = self._micro > 0        # the first micro-step of a window overwrites (zero_grad(set_to_none=True), Trainer.py:72), the others add
         loss, logits = vit._rt.train_step(video, labels.contiguous(), arena, shadow, grads, m, v, step=opt._steps + 1, lr=g0["lr"], betas=g0["betas"],
-                                          eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate, update=last_micro,
+                                          eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate,
+                                          update=last_micro and self.clipper is None,
                                           fuse_update=fuse, dropout=vit.draw_dropout(), loss_scale=self.static_scale,
                                           loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp)
-        if last_micro:
+        if last_micro and self.clipper is None:
             opt._steps += 1                 # (after the call: a refused step leaves the counter where it was)
         vit._last_logits = logits
         self.last_outputs = logits
@@ -308,7 +333,13 @@ class TrainStep:
             for i, p in enumerate(vit._plist):
                 p.grad = vit._grad_view(i)
         self._micro += 1
-        if last_micro:
+        if last_micro and self.clipper is not None:
+            # clipping: the call above ran no optimizer work (update = 0: with a loss-scale state only the scaling of the loss gradient);
+            # norm, coefficient, the scaler's decision and the one AdamW launch are queued behind it (FusedAdamW.step counts the step and
+            # marks the shadow fresh itself)
+            opt.step(grad_scale=1.0 / self.static_scale if self.static_scale > 0 else 1.0, scaler=self.scaler, clip=self.clipper)
+            self._micro = 0
+        elif last_micro:
             vit.mark_shadow_fresh()
             self._micro = 0
         return loss.reshape(())
@@ -393,7 +424,7 @@ class TrainStep:
                 self.optimizer.step_rest(grad_scale=scale)
             else:
                 red = self.sync.reduced_buffer() if (pipelined and not self.sync.write_back) else None
-                self.optimizer.step(grad_scale=scale, reduced_bf16=None if red is None else {id(vit): red}, scaler=self.scaler)
+                self.optimizer.step(grad_scale=scale, reduced_bf16=None if red is None else {id(vit): red}, scaler=self.scaler, clip=self.clipper)
             self._micro = 0
         return loss.detach()
 
@@ -468,7 +499,8 @@ class Trainer:
         self.dataloader = torch.utils.data.DataLoader(self.data, shuffle=True, **kw)
         self.val_dataloader = torch.utils.data.DataLoader(self.val_data, shuffle=False, **kw)
         self.criterion = CrossEntropyLoss()
-        self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1)
+        self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
+                              max_grad_norm=self.grad_clip_from_config(config))
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
         self._wandb = None
@@ -483,6 +515,15 @@ class Trainer:
         print(f'Model total parameters: {total_params/1e6:.2f}M (trainable {trainable_params/1e6:.2f}M and frozen {(total_params-trainable_params)/1e6:.2f}M)')
         self._os = _os
         self.validation_precision = config.get('VALIDATION_PRECISION', 'fp32')
+
+    @staticmethod
+    def grad_clip_from_config(config) -> Optional[float]:
+        """TRAINING_GRAD_CLIP (optional; the reference's config files have no such key): the max_grad_norm of TrainStep; absent, None
+        or 0 = no clipping."""
+        value = config.get('TRAINING_GRAD_CLIP', None)
+        if value is None or (not isinstance(value, bool) and isinstance(value, (int, float)) and value == 0):
+            return None
+        return check_max_norm(value)
 
     @staticmethod
     def _unpack(batch):
@@ -523,7 +564,10 @@ class Trainer:
                 lr = round(self.optimizer.param_groups[0]['lr'], 5)
                 duration = time.time() - start_time
                 print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| train_loss: {avg_loss:.5f}\t| train_accuracy: {accuracy:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
-                self._log({"epoch": epoch, "batch": i, "train_loss": avg_loss, "train_accuracy": accuracy, "learning_rate": lr, "duration": duration})
+                payload = {"epoch": epoch, "batch": i, "train_loss": avg_loss, "train_accuracy": accuracy, "learning_rate": lr, "duration": duration}
+                if self.step.last_grad_norm is not None:       # read back here only: the log line above has synchronised already
+                    payload["grad_norm"] = float(self.step.last_grad_norm)
+                self._log(payload)
                 correct, total, running_loss = 0, 0, 0.0
                 start_time = time.time()
 
