@@ -448,6 +448,39 @@ long nv_token_map_to_volume_workspace_bytes(int B, const int* grid3);
 int nv_token_map_to_volume(const float* maps, int B, const int* grid3, const int* out3, int normalize, double keep_percent, float* out,
                            void* workspace, long ws_bytes, void* stream);
 
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) perturbation attribution: the device steps around
+ * the forward of deletion / insertion curves and of patch occlusion sensitivity.  No call allocates or synchronises; every argument
+ * is checked first (NV_ERR_ARG).  `jobs` is a DEVICE array int32 [J, 3] of rows (b, lo, hi): b the source volume of the job.
+ * nv_token_ranks: maps fp32 [B, N] (finite values, N <= 4096) -> ranks int32 [B, N],
+ *     ranks[b, t] = #{ j : maps[b, j] > maps[b, t]  or  (maps[b, j] == maps[b, t] and j < t) }:
+ *   descending order, ties to the lower token index, -0.0 == +0.0 a tie; a permutation of 0 .. N - 1 and the inverse of
+ *   torch.sort(maps, descending=True, stable=True).indices.  One workgroup per volume, a counting pass over the keys in LDS.
+ * nv_mask_patches: x fp32 [B, S0, S1, S2] dense (NeuroEncoder.forward's [B, H, W, D]), labels int32 [B, N], size3 / patch3 HOST arrays
+ *   {S0, S1, S2} / {p0, p1, p2} (S_a a multiple of p_a, G_a = S_a / p_a, N = G0 G1 G2 <= 4096, N + S1 + S2 <= 16320)
+ *   -> out fp32 [J, S0, S1, S2] (16-byte aligned).  Voxel (i0, i1, i2) belongs to token t = (i2 / p2) G0 G1 + (i0 / p0) G1 + i1 / p1 (the
+ *   patchify order of the engine's gather, vit_3d.py:92 on the [B, 1, D, H, W] view).  For job j = (b, lo, hi):
+ *     out[j, i0, i1, i2] = lo <= labels[b, t] < hi ? baseline : x[b, i0, i1, i2]
+ *   with baseline = `value` (base NULL), or base[b * base_stride + (i0 S1 + i1) S2 + i2] (base_stride in elements; 0 = one volume shared
+ *   by every job).  A pure select: every bit of x and of the baseline passes through (NaN, Inf, -0.0).  A job with b outside [0, B)
+ *   reads nothing and writes nothing; lo >= hi copies x[b].  One launch, 16-byte stores whatever the alignment of the volumes (27^3).
+ *   nv_mask_patches_set_group (A/B aid, process-wide, 1 .. 16, default 4): consecutive jobs one workgroup serves from one read of x.
+ * nv_class_scores: logits fp32 [J, C], cls int64 [B] -> scores fp32 [J] of class c = cls[b_j]: NV_SCORE_LOGIT copies logits[j, c] bit for bit,
+ *   NV_SCORE_PROB is exp(l_c - max) / sum_i exp(l_i - max) in fp32 with the library expf.  b_j outside [0, B): nothing written; c outside
+ *   [0, C): NaN.
+ * nv_curve_auc: scores fp32 [B, K] with row stride ld (elements), K >= 2 -> auc fp32 [B]: the trapezoid rule on the uniform grid k / (K - 1),
+ *   (sum_k s_k - (s_0 + s_{K-1}) / 2) / (K - 1), summed in double in index order, stored as fp32.
+ * nv_occlusion_gather: ref fp32 [B], scores fp32 [B, NB], labels int32 [B, N] -> maps fp32 [B, N] = ref[b] - scores[b, labels[b, t]]
+ *   (a label outside [0, NB): NaN). */
+#define NV_SCORE_PROB 0
+#define NV_SCORE_LOGIT 1
+int nv_token_ranks(const float* maps, int B, int N, int* ranks, void* stream);
+int nv_mask_patches(const float* x, int B, const int* size3, const int* patch3, const int* labels, const int* jobs, int J, float value,
+                    const float* base, long base_stride, float* out, void* stream);
+int nv_mask_patches_set_group(int group);
+int nv_class_scores(const float* logits, int J, int C, const int* jobs, const long* cls, int B, int kind, float* scores, void* stream);
+int nv_curve_auc(const float* scores, int B, int K, long ld, float* auc, void* stream);
+int nv_occlusion_gather(const float* ref, const float* scores, const int* labels, int B, int N, int NB, float* maps, void* stream);
+
 /* ---- the 4D model's temporal head (src/models/NeuroEncoder.py:60-66: temporal_transformer -> mean over time -> projection_head;
  * :207-217 TemporalTransformer = one nn.TransformerEncoderLayer(d_model 2, nhead 2, batch_first, post-norm, ReLU, dim_feedforward ff,
  * dropout p at its four sites); :219-230 ProjectionHead = nn.Linear(2, 2)) - ONE launch per direction.

@@ -26,6 +26,13 @@ def _encoder_weights_of(checkpoint: dict, prefix: str = "volume_encoder.") -> di
     return {key[len(prefix):]: tensor for key, tensor in checkpoint.items() if key.startswith(wanted)}
 
 
+def perturbation_step_bounds(tokens: int, steps: int, device=None) -> torch.Tensor:
+    """int64 [steps + 1]: m_k = (2 k N + steps) // (2 steps), the number of top-ranked patches point k of a deletion / insertion curve has
+    removed / present - k N / steps rounded half up in integers, so m_0 = 0, m_steps = N and the bounds never decrease."""
+    k = torch.arange(steps + 1, device=device, dtype=torch.int64)
+    return (2 * k * tokens + steps) // (2 * steps)
+
+
 class NeuroEncoder(nn.Module):
     """3D or 4D encoder for MRI / fMRI volumes (NeuroEncoder.py:15-68).  Attribute names and the ORDER in which sub-modules are created
     are the contract (state_dict keys; the RNG stream of a seeded construction) - tests/test_boundary_cpu.py pins both."""
@@ -216,7 +223,8 @@ class NeuroEncoder(nn.Module):
     def attribution_volumes(self, x, method="gradcam", target=None, threshold=None, return_token_maps=False):
         """Attribution volumes of a batch x [B, H, W, D]: (volumes fp32 [B, S, S, S] on the device, class_idx [B] on the device[, the
         normalised token maps [B, G^3] on the device]).  method "gradcam" / "rollout" / "relevance" runs the GPU steps of
-        get_attention_map / get_attention_rollout / get_attention_relevance on the whole batch, in the module's current mode:
+        get_attention_map / get_attention_rollout / get_attention_relevance on the whole batch, in the module's current mode; "occlusion" is
+        relu(occlusion_sensitivity(x, target)) - G^3 + 1 forwards per volume, no gradient and no assumption about attention:
           gradcam    one forward, logits.backward(one-hot) with one row per volume (the logits are per volume: volumes do not couple),
                      the per-volume reduction nv_gradcam_reduce_per_volume.  As get_attention_map it runs the model's backward pass:
                      a trainable model accumulates p.grad; a frozen one runs the data-only backward and touches none;
@@ -229,8 +237,16 @@ class NeuroEncoder(nn.Module):
         from . import ops
         if self.config['TRAINING_DIM'] != 3:
             raise NotImplementedError("attribution_volumes: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
-        if method not in ("gradcam", "rollout", "relevance"):
-            raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout' or 'relevance', got {method!r}")
+        if method not in ("gradcam", "rollout", "relevance", "occlusion"):
+            raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout', 'relevance' or 'occlusion', got {method!r}")
+        if method == "occlusion":
+            # the signed occlusion map (one patch per job, zero baseline, probability score); the volume shows what SUPPORTS the class
+            signed, class_idx = self.occlusion_sensitivity(x, target=target)
+            size = self.config['TRAINING_VIT_INPUT_SIZE']
+            keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
+            volumes, (normalised, _, _) = ops.token_maps_to_volumes(torch.relu(signed), size // self.config['TRAINING_VIT_PATCH_SIZE'], size, normalize=True,
+                                                                    keep_percent=keep_percent, return_maps=True)
+            return (volumes, class_idx, normalised) if return_token_maps else (volumes, class_idx)
         vit = self.volume_encoder.vit3d
         volume = x.to(self.device)
 
@@ -266,6 +282,153 @@ class NeuroEncoder(nn.Module):
         if return_token_maps:
             return volumes, class_idx, normalised
         return volumes, class_idx
+
+    # ---- perturbation attribution, on the device (csrc/perturb.hip): how faithful a map is (deletion / insertion curves) and the
+    # gradient-free baseline among the maps (patch occlusion sensitivity)
+    def _perturbation_inputs(self, what, x, baseline, score, chunk):
+        """argument checks shared by perturbation_curves / occlusion_sensitivity (all before any device work) -> (S, G, chunk)"""
+        if self.config['TRAINING_DIM'] != 3:
+            raise NotImplementedError(f"{what}: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
+        if score not in ("prob", "logit"):
+            raise ValueError(f"{what}: score must be 'prob' or 'logit', got {score!r}")
+        S = self.config['TRAINING_VIT_INPUT_SIZE']
+        if x.dim() != 4 or tuple(x.shape[1:]) != (S, S, S) or x.shape[0] < 1:
+            raise ValueError(f"{what}: x must be [B, {S}, {S}, {S}], got {tuple(x.shape)}")
+        if torch.is_tensor(baseline):
+            if tuple(baseline.shape) not in (tuple(x.shape), (1, S, S, S)):
+                raise ValueError(f"{what}: baseline of shape {tuple(baseline.shape)}, expected {tuple(x.shape)} or {(1, S, S, S)}")
+        else:
+            float(baseline)
+        if chunk is None:
+            chunk = max(1, min(64, 2 ** 30 // (4 * S ** 3)))
+        elif int(chunk) != chunk or chunk < 1:
+            raise ValueError(f"{what}: chunk must be a positive integer, got {chunk!r}")
+        return S, S // self.config['TRAINING_VIT_PATCH_SIZE'], int(chunk)
+
+    def _perturbation_table(self, key, build):
+        """job tables / block labels: device tensors built once per geometry by integer arithmetic on torch.arange"""
+        cache = self.__dict__.setdefault("_perturbation_tables", {})
+        if key not in cache:
+            if len(cache) >= 16:
+                cache.clear()
+            cache[key] = build()
+        return cache[key]
+
+    def _explained_classes(self, logits, target):
+        if target is None:
+            return logits.argmax(dim=1)
+        if torch.is_tensor(target):
+            return target.to(logits.device).long().reshape(-1).contiguous()
+        return torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
+
+    def _perturbed_logits(self, volume, labels, jobs, baseline, chunk):
+        """logits [J, C] of the masked copies (ops.mask_patches) of `volume`: consecutive slices of `chunk` jobs, each masked into one
+        reused buffer and forwarded under no_grad in the module's current mode and precision"""
+        from . import ops
+        patch = self.config['TRAINING_VIT_PATCH_SIZE']
+        J = jobs.shape[0]
+        chunk = min(chunk, J)
+        if torch.is_tensor(baseline):
+            baseline = baseline.to(device=volume.device, dtype=torch.float32).contiguous()
+        masked = torch.empty((chunk,) + tuple(volume.shape[1:]), dtype=torch.float32, device=volume.device)
+        logits = None
+        with torch.no_grad():
+            for first in range(0, J, chunk):
+                count = min(chunk, J - first)
+                ops.mask_patches(volume, labels, jobs[first:first + count], patch, baseline=baseline, out=masked[:count])
+                part = self.forward(masked[:count])
+                if logits is None:
+                    logits = torch.empty((J, part.shape[1]), dtype=torch.float32, device=volume.device)
+                logits[first:first + count].copy_(part)
+        return logits
+
+    def perturbation_curves(self, x, token_maps, target=None, steps=20, mode="both", baseline=0.0, score="prob", chunk=None):
+        """Deletion / insertion curves of token maps [B, G^3] (token order, e.g. the third result of attribution_volumes(...,
+        return_token_maps=True)) for a batch x [B, H, W, D]: the class score while the patches are replaced by the baseline (deletion) or
+        restored into the baseline (insertion) in the order the map ranks them - a faithful map has a small deletion area and a large
+        insertion area.  target: None = the predicted class of the unperturbed volume, an int, or a LongTensor [B].
+          ranks      ops.token_ranks(token_maps): descending, ties to the lower token index (thresholded maps are mostly ties);
+          steps      K = steps + 1 points; point k has the m_k = (2 k N + steps) // (2 steps) top-ranked of the N patches removed (deletion)
+                     or present (insertion): m_0 = 0, m_steps = N;
+          jobs       volume-major; within a volume deletion k = 0 .. steps = (b, 0, m_k), then insertion k = 0 .. steps = (b, m_k, N), the
+                     labels being the ranks (ops.mask_patches); consecutive slices of `chunk` jobs (None: max(1, min(64, 2^30 // (4 S^3))))
+                     are masked into one reused buffer and forwarded under no_grad in the module's current mode and precision;
+          baseline   a float, or a tensor of x's shape or [1, S, S, S] (a blurred copy, a mean volume);
+          score      "prob" (softmax probability of the class) or "logit".
+        Returns a dict of device tensors: deletion / insertion [B, K], deletion_auc / insertion_auc [B] (trapezoid rule over
+        fractions = k / steps [K]), class_idx [B], ranks [B, N]; mode "deletion" / "insertion" computes and returns only that pair.
+        Nothing crosses PCIe and nothing synchronises with the host inside the call."""
+        from . import ops
+        S, G, chunk = self._perturbation_inputs("perturbation_curves", x, baseline, score, chunk)
+        if mode not in ("both", "deletion", "insertion"):
+            raise ValueError(f"perturbation_curves: mode must be 'both', 'deletion' or 'insertion', got {mode!r}")
+        if int(steps) != steps or steps < 1:
+            raise ValueError(f"perturbation_curves: steps must be a positive integer, got {steps!r}")
+        steps, N, B = int(steps), G ** 3, x.shape[0]
+        if tuple(token_maps.shape) != (B, N):
+            raise ValueError(f"perturbation_curves: token_maps must be [{B}, {N}] (one value per patch token), got {tuple(token_maps.shape)}")
+        K = steps + 1
+        volume = x.to(device=self.device, dtype=torch.float32).contiguous()
+        device = volume.device
+
+        def build():
+            m = perturbation_step_bounds(N, steps, device)
+            zero, full = torch.zeros_like(m), torch.full_like(m, N)
+            bounds = {"both": torch.cat([torch.stack([zero, m], 1), torch.stack([m, full], 1)]), "deletion": torch.stack([zero, m], 1),
+                      "insertion": torch.stack([m, full], 1)}[mode]                                  # [K or 2 K, 2]: (lo, hi)
+            source = torch.arange(B, device=device, dtype=torch.int64).repeat_interleave(bounds.shape[0])
+            return torch.cat([source[:, None], bounds.repeat(B, 1)], 1).to(torch.int32).contiguous(), (torch.arange(K, device=device, dtype=torch.float64) / steps).float()
+        jobs, fractions = self._perturbation_table(("curves", str(device), B, N, steps, mode), build)
+
+        with torch.no_grad():
+            class_idx = self._explained_classes(self.forward(volume), target)
+        ranks = ops.token_ranks(token_maps.to(device=device, dtype=torch.float32).contiguous())
+        logits = self._perturbed_logits(volume, ranks, jobs, baseline, chunk)
+        scores = ops.class_scores(logits, jobs, class_idx, kind=score).view(B, -1)
+        out = {"fractions": fractions, "class_idx": class_idx, "ranks": ranks}
+        for name, first in (("deletion", 0), ("insertion", K if mode == "both" else 0)):
+            if mode in ("both", name):
+                out[name] = scores[:, first:first + K]
+                out[name + "_auc"] = ops.curve_auc(out[name])
+        return out
+
+    def occlusion_sensitivity(self, x, target=None, window=1, baseline=0.0, score="prob", chunk=None):
+        """Patch occlusion sensitivity of a batch x [B, H, W, D]: (maps fp32 [B, G^3] in token order, class_idx [B]), both on the device.
+        maps[b, t] = score of x[b] - score of x[b] with the window^3-patch block that holds patch t replaced by the baseline: signed
+        (positive = the block supports the class), no gradient and no assumption about attention.  The blocks tile the patch grid from
+        its origin (the last block of an axis is smaller when window does not divide G): cell (c2, c0, c1) of token t = c2 G^2 + c0 G + c1
+        lies in block (c2 // w) Gb^2 + (c0 // w) Gb + c1 // w, Gb = ceil(G / w); one job (b, j, j + 1) per volume and block, volume-major,
+        masked and forwarded in slices of `chunk` jobs as perturbation_curves does.  One more forward of x gives the unperturbed score and,
+        with target None, the predicted class.  target / baseline / score / chunk: as perturbation_curves.  Costs Gb^3 + 1 forwards per
+        volume; nothing crosses PCIe and nothing synchronises with the host inside the call."""
+        from . import ops
+        S, G, chunk = self._perturbation_inputs("occlusion_sensitivity", x, baseline, score, chunk)
+        if int(window) != window or window < 1:
+            raise ValueError(f"occlusion_sensitivity: window must be a positive integer, got {window!r}")
+        w, N, B = int(window), G ** 3, x.shape[0]
+        Gb = -(-G // w)
+        NB = Gb ** 3
+        volume = x.to(device=self.device, dtype=torch.float32).contiguous()
+        device = volume.device
+
+        def build():
+            t = torch.arange(N, device=device, dtype=torch.int64)
+            c2, c0, c1 = t // (G * G), (t // G) % G, t % G
+            block = (c2 // w) * Gb * Gb + (c0 // w) * Gb + c1 // w
+            b = torch.arange(B, device=device, dtype=torch.int64)
+            j = torch.arange(NB, device=device, dtype=torch.int64).repeat(B)
+            jobs = torch.stack([b.repeat_interleave(NB), j, j + 1], 1).to(torch.int32).contiguous()
+            plain = torch.stack([b, torch.zeros_like(b), torch.zeros_like(b)], 1).to(torch.int32).contiguous()      # rows (b, 0, 0): x itself
+            return block.to(torch.int32).repeat(B, 1).contiguous(), jobs, plain
+        labels, jobs, plain = self._perturbation_table(("occlusion", str(device), B, G, w), build)
+
+        with torch.no_grad():
+            unperturbed = self.forward(volume).float().contiguous()
+        class_idx = self._explained_classes(unperturbed, target)
+        reference = ops.class_scores(unperturbed, plain, class_idx, kind=score)
+        logits = self._perturbed_logits(volume, labels, jobs, baseline, chunk)
+        scores = ops.class_scores(logits, jobs, class_idx, kind=score).view(B, NB)
+        return ops.occlusion_gather(reference, scores, labels), class_idx
 
     def visualize_slice(self, cam_3d, original_volume):
         """One 2-D slice of the volume and of its CAM along GRADCAM_SLICE_DIM at GRADCAM_SLICE_IDX

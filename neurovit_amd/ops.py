@@ -559,6 +559,90 @@ def token_maps_to_volumes(maps: torch.Tensor, grid, size, normalize: bool = True
     return out, (ws[:B * N].view(B, N), ws[B * N:2 * B * N].view(B, N), ws[2 * B * N:])
 
 
+SCORE_KINDS = {"prob": 0, "logit": 1}      # NV_SCORE_PROB / NV_SCORE_LOGIT
+
+
+def token_ranks(maps: torch.Tensor) -> torch.Tensor:
+    """maps f32 [B, N] (device, finite, N <= 4096) -> ranks int32 [B, N]: the position of every token in the descending order of its
+    volume's map, ties to the lower token index (-0.0 == +0.0) - the inverse of torch.sort(descending=True, stable=True).indices.  One launch."""
+    _need_cuda(maps)
+    assert maps.dim() == 2 and maps.dtype == torch.float32 and maps.is_contiguous()
+    B, N = maps.shape
+    ranks = torch.empty((B, N), dtype=torch.int32, device=maps.device)
+    check(lib.nv_token_ranks(_p(maps), B, N, _p(ranks), _stream()), "nv_token_ranks")
+    return ranks
+
+
+def mask_patches(x: torch.Tensor, labels: torch.Tensor, jobs: torch.Tensor, patch, baseline=0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x f32 [B, S0, S1, S2] (NeuroEncoder.forward's layout), labels int32 [B, N], jobs int32 [J, 3] of rows (b, lo, hi), all on the device
+    -> f32 [J, S0, S1, S2]: copy j is x[b] with every patch whose label lies in [lo, hi) replaced by the baseline - a float, or a tensor of
+    x's shape (one volume per source volume) or [1, S0, S1, S2] (shared).  patch: an int or three.  Tokens are numbered as the engine's
+    patch gather numbers them.  A pure select (bits pass through); a job with b outside [0, B) leaves its slot of `out` as it was.
+    nv_mask_patches, one launch."""
+    _need_cuda(x, labels, jobs, out, baseline if torch.is_tensor(baseline) else None)
+    patch = _triple(patch, "patch")
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()
+    B, size = x.shape[0], tuple(x.shape[1:])
+    if any(s % p for s, p in zip(size, patch)):
+        raise ValueError(f"neurovit_amd: mask_patches: volume {size} is not a whole number of {patch} patches")
+    N = (size[0] // patch[0]) * (size[1] // patch[1]) * (size[2] // patch[2])
+    assert labels.shape == (B, N) and labels.dtype == torch.int32 and labels.is_contiguous()
+    assert jobs.dim() == 2 and jobs.shape[1] == 3 and jobs.dtype == torch.int32 and jobs.is_contiguous()
+    J = jobs.shape[0]
+    value, base, stride = 0.0, None, 0
+    if torch.is_tensor(baseline):
+        if tuple(baseline.shape) not in ((B,) + size, (1,) + size):
+            raise ValueError(f"neurovit_amd: mask_patches: baseline of shape {tuple(baseline.shape)}, expected {(B,) + size} or {(1,) + size}")
+        assert baseline.dtype == torch.float32 and baseline.is_contiguous()
+        base, stride = baseline, (size[0] * size[1] * size[2] if baseline.shape[0] == B and B > 1 else 0)
+    else:
+        value = float(baseline)
+    if out is None:
+        out = torch.empty((J,) + size, dtype=torch.float32, device=x.device)
+    assert out.shape == (J,) + size and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
+    s3, p3 = (ctypes.c_int * 3)(*size), (ctypes.c_int * 3)(*patch)
+    check(lib.nv_mask_patches(_p(x), B, ctypes.cast(s3, ctypes.c_void_p), ctypes.cast(p3, ctypes.c_void_p), _p(labels), _p(jobs), J, value, _p(base),
+                              stride, _p(out), _stream()), "nv_mask_patches")
+    return out
+
+
+def class_scores(logits: torch.Tensor, jobs: torch.Tensor, cls: torch.Tensor, kind: str = "prob") -> torch.Tensor:
+    """logits f32 [J, C], jobs int32 [J, 3] (column 0: the source volume b_j), cls int64 [B] -> f32 [J]: the score of class cls[b_j] in row
+    j - "logit": the logit itself, bit for bit; "prob": its softmax probability in fp32.  nv_class_scores, one launch."""
+    _need_cuda(logits, jobs, cls)
+    if kind not in SCORE_KINDS:
+        raise ValueError(f"neurovit_amd: class_scores: kind must be 'prob' or 'logit', got {kind!r}")
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    J, C = logits.shape
+    assert jobs.shape == (J, 3) and jobs.dtype == torch.int32 and jobs.is_contiguous()
+    assert cls.dim() == 1 and cls.dtype == torch.int64 and cls.is_contiguous()
+    scores = torch.empty(J, dtype=torch.float32, device=logits.device)
+    check(lib.nv_class_scores(_p(logits), J, C, _p(jobs), _p(cls), cls.shape[0], SCORE_KINDS[kind], _p(scores), _stream()), "nv_class_scores")
+    return scores
+
+
+def curve_auc(scores: torch.Tensor) -> torch.Tensor:
+    """scores f32 [B, K] (rows may be strided, K >= 2) -> f32 [B]: the trapezoid area under each curve on the uniform grid k / (K - 1),
+    summed in double.  nv_curve_auc, one launch."""
+    _need_cuda(scores)
+    assert scores.dim() == 2 and scores.dtype == torch.float32 and scores.stride(1) == 1
+    B, K = scores.shape
+    auc = torch.empty(B, dtype=torch.float32, device=scores.device)
+    check(lib.nv_curve_auc(_p(scores), B, K, scores.stride(0) if B > 1 else K, _p(auc), _stream()), "nv_curve_auc")
+    return auc
+
+
+def occlusion_gather(ref: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """ref f32 [B], scores f32 [B, NB], labels int32 [B, N] -> f32 [B, N]: ref[b] - scores[b, labels[b, t]].  nv_occlusion_gather, one launch."""
+    _need_cuda(ref, scores, labels)
+    B, NB = scores.shape
+    assert ref.shape == (B,) and labels.dim() == 2 and labels.shape[0] == B and labels.dtype == torch.int32
+    assert ref.dtype == torch.float32 and scores.dtype == torch.float32 and ref.is_contiguous() and scores.is_contiguous() and labels.is_contiguous()
+    maps = torch.empty(labels.shape, dtype=torch.float32, device=scores.device)
+    check(lib.nv_occlusion_gather(_p(ref), _p(scores), _p(labels), B, labels.shape[1], NB, _p(maps), _stream()), "nv_occlusion_gather")
+    return maps
+
+
 def dropout_apply(x: torch.Tensor, drop_seed: int = 0, drop_p: float = 0.0, want16: bool = True, want32: bool = False):
     """x f32 [M, N] times the dropout mask of one site -> (bf16 copy or None, f32 copy or None)."""
     _need_cuda(x)
