@@ -481,6 +481,35 @@ int nv_class_scores(const float* logits, int J, int C, const int* jobs, const lo
 int nv_curve_auc(const float* scores, int B, int K, long ld, float* auc, void* stream);
 int nv_occlusion_gather(const float* ref, const float* scores, const int* labels, int B, int N, int NB, float* maps, void* stream);
 
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) path attribution: the device steps around the
+ * forward and the data-only backward of integrated gradients.  No call allocates or synchronises; every argument is checked first
+ * (NV_ERR_ARG).  `jobs` is a DEVICE array int32 [J, 2] of rows (b, k): b the source volume of the job, k its step on the path.
+ * The first four see a sample as V dense floats (no geometry); rows of a [rows, V] buffer may start at any 4-byte alignment (27^3), the
+ * buffer each call WRITES is 16-byte aligned.  Every sum and product below is one separately rounded fp32 operation (round to nearest
+ * even, no FMA), so the results are the bits of the same expressions evaluated as separate torch tensor operations on the CPU.  No
+ * atomics: every output element is owned by one thread, and two runs give the same bits.
+ * nv_path_points: x fp32 [B, V], alphas fp32 [K] -> out fp32 [J, V].  For job j = (b, k):
+ *     out[j, e] = bl + alphas[k] * (x[b, e] - bl)
+ *   with bl = `value` (base NULL), or base[b * base_stride + e] (base_stride in elements; 0 = one volume shared by every job).  NaN and
+ *   Inf propagate as the three operations propagate them.  A job with b outside [0, B) or k outside [0, K) reads nothing and writes
+ *   nothing.  One launch; consecutive jobs of one volume are served from one read of x and of the baseline.
+ * nv_class_score_grads: logits fp32 [J, C], cls int64 [B] -> dlogits fp32 [J, C], the gradient of the score of class c = cls[b_j] w.r.t.
+ *   row j: NV_SCORE_LOGIT the one-hot of c; NV_SCORE_PROB p_c (delta_ci - p_i) with p the fp32 softmax of nv_class_scores (max-subtracted,
+ *   the library expf).  b_j outside [0, B): nothing written; c outside [0, C): a row of NaN.
+ * nv_path_accumulate: g fp32 [J, V], weights fp32 [K], acc fp32 [B, V].  For every volume b that appears in `jobs` (with k in [0, K)):
+ *     acc[b] <- (..((acc[b] + w_k1 * g[j1]) + w_k2 * g[j2]) ..)   over that volume's jobs j1 < j2 < .. in job order.
+ *   The call always adds: the caller zero-fills acc once, on the same stream.  Volumes absent from `jobs` are not touched.  J <= 1024.
+ * nv_path_finish: attr[b, e] = (x[b, e] - bl) * acc[b, e]   (x, acc, attr fp32 [B, V]; the baseline as nv_path_points).
+ * nv_attr_token_sums: attr fp32 [B, S0, S1, S2] dense, size3 / patch3 HOST arrays and the token rule of nv_mask_patches
+ *   (t = (i2 / p2) G0 G1 + (i0 / p0) G1 + i1 / p1) -> sums fp32 [B, N, 2]: sums[b, t, 0] the sum and sums[b, t, 1] the sum of the absolute
+ *   values of the voxels of patch t, both accumulated in double in a fixed order (the same bits on every run) and stored as fp32. */
+int nv_path_points(const float* x, int B, long V, const int* jobs, int J, const float* alphas, int K, float value, const float* base,
+                   long base_stride, float* out, void* stream);
+int nv_class_score_grads(const float* logits, int J, int C, const int* jobs, const long* cls, int B, int kind, float* dlogits, void* stream);
+int nv_path_accumulate(const float* g, const int* jobs, int J, const float* weights, int K, float* acc, int B, long V, void* stream);
+int nv_path_finish(const float* acc, const float* x, int B, long V, float value, const float* base, long base_stride, float* attr, void* stream);
+int nv_attr_token_sums(const float* attr, int B, const int* size3, const int* patch3, float* sums, void* stream);
+
 /* ---- the 4D model's temporal head (src/models/NeuroEncoder.py:60-66: temporal_transformer -> mean over time -> projection_head;
  * :207-217 TemporalTransformer = one nn.TransformerEncoderLayer(d_model 2, nhead 2, batch_first, post-norm, ReLU, dim_feedforward ff,
  * dropout p at its four sites); :219-230 ProjectionHead = nn.Linear(2, 2)) - ONE launch per direction.

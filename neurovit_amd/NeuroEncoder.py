@@ -33,6 +33,35 @@ def perturbation_step_bounds(tokens: int, steps: int, device=None) -> torch.Tens
     return (2 * k * tokens + steps) // (2 * steps)
 
 
+PATH_METHODS = ("gausslegendre", "riemann_middle", "riemann_trapezoid")
+
+
+def path_quadrature(method: str, steps: int, device=None):
+    """(alphas fp32 [steps], weights fp32 [steps]) of a quadrature rule on [0, 1] for integrated gradients, computed in float64 on the host:
+      riemann_middle     alpha_k = (k + 1/2) / m, w_k = 1 / m;
+      riemann_trapezoid  m >= 2: alpha_k = k / (m - 1), w_k = 1 / (m - 1) with the two end weights halved;
+      gausslegendre      numpy.polynomial.legendre.leggauss(m) mapped from [-1, 1] to [0, 1] (captum's default rule; exact to degree 2 m - 1).
+    The weights sum to 1 within fp32 rounding.  Bad arguments raise ValueError."""
+    import numpy as np
+    if method not in PATH_METHODS:
+        raise ValueError(f"path_quadrature: method must be one of {', '.join(repr(m) for m in PATH_METHODS)}, got {method!r}")
+    if isinstance(steps, bool) or int(steps) != steps or steps < 1:
+        raise ValueError(f"path_quadrature: steps must be a positive integer, got {steps!r}")
+    m = int(steps)
+    if method == "riemann_middle":
+        alphas, weights = (np.arange(m, dtype=np.float64) + 0.5) / m, np.full(m, 1.0 / m, dtype=np.float64)
+    elif method == "riemann_trapezoid":
+        if m < 2:
+            raise ValueError(f"path_quadrature: the trapezoid rule needs at least 2 steps, got {steps!r}")
+        alphas, weights = np.arange(m, dtype=np.float64) / (m - 1), np.full(m, 1.0 / (m - 1), dtype=np.float64)
+        weights[0] *= 0.5
+        weights[-1] *= 0.5
+    else:
+        nodes, w = np.polynomial.legendre.leggauss(m)
+        alphas, weights = 0.5 * (nodes + 1.0), 0.5 * w
+    return (torch.from_numpy(alphas).to(dtype=torch.float32, device=device), torch.from_numpy(weights).to(dtype=torch.float32, device=device))
+
+
 class NeuroEncoder(nn.Module):
     """3D or 4D encoder for MRI / fMRI volumes (NeuroEncoder.py:15-68).  Attribute names and the ORDER in which sub-modules are created
     are the contract (state_dict keys; the RNG stream of a seeded construction) - tests/test_boundary_cpu.py pins both."""
@@ -224,7 +253,9 @@ class NeuroEncoder(nn.Module):
         """Attribution volumes of a batch x [B, H, W, D]: (volumes fp32 [B, S, S, S] on the device, class_idx [B] on the device[, the
         normalised token maps [B, G^3] on the device]).  method "gradcam" / "rollout" / "relevance" runs the GPU steps of
         get_attention_map / get_attention_rollout / get_attention_relevance on the whole batch, in the module's current mode; "occlusion" is
-        relu(occlusion_sensitivity(x, target)) - G^3 + 1 forwards per volume, no gradient and no assumption about attention:
+        relu(occlusion_sensitivity(x, target)) - G^3 + 1 forwards per volume, no gradient and no assumption about attention;
+        "integrated_gradients" is relu of the token_maps of integrated_gradients(x, target) with its defaults (zero baseline, 50
+        Gauss-Legendre points, the class logit: 50 forward + data-only backward passes per volume, no p.grad touched):
           gradcam    one forward, logits.backward(one-hot) with one row per volume (the logits are per volume: volumes do not couple),
                      the per-volume reduction nv_gradcam_reduce_per_volume.  As get_attention_map it runs the model's backward pass:
                      a trainable model accumulates p.grad; a frozen one runs the data-only backward and touches none;
@@ -237,11 +268,16 @@ class NeuroEncoder(nn.Module):
         from . import ops
         if self.config['TRAINING_DIM'] != 3:
             raise NotImplementedError("attribution_volumes: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
-        if method not in ("gradcam", "rollout", "relevance", "occlusion"):
-            raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout', 'relevance' or 'occlusion', got {method!r}")
-        if method == "occlusion":
-            # the signed occlusion map (one patch per job, zero baseline, probability score); the volume shows what SUPPORTS the class
-            signed, class_idx = self.occlusion_sensitivity(x, target=target)
+        if method not in ("gradcam", "rollout", "relevance", "occlusion", "integrated_gradients"):
+            raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout', 'relevance', 'occlusion' or 'integrated_gradients', got {method!r}")
+        if method in ("occlusion", "integrated_gradients"):
+            if method == "occlusion":
+                # the signed occlusion map (one patch per job, zero baseline, probability score); the volume shows what SUPPORTS the class
+                signed, class_idx = self.occlusion_sensitivity(x, target=target)
+            else:
+                # the signed patch sums of integrated gradients (zero baseline, 50 Gauss-Legendre points, the class logit)
+                result = self.integrated_gradients(x, target=target)
+                signed, class_idx = result["token_maps"], result["class_idx"]
             size = self.config['TRAINING_VIT_INPUT_SIZE']
             keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
             volumes, (normalised, _, _) = ops.token_maps_to_volumes(torch.relu(signed), size // self.config['TRAINING_VIT_PATCH_SIZE'], size, normalize=True,
@@ -429,6 +465,32 @@ class NeuroEncoder(nn.Module):
         logits = self._perturbed_logits(volume, labels, jobs, baseline, chunk)
         scores = ops.class_scores(logits, jobs, class_idx, kind=score).view(B, NB)
         return ops.occlusion_gather(reference, scores, labels), class_idx
+
+    # ---- path attribution, on the device (csrc/path_attr.hip): integrated gradients, the map the reference ships captum heat maps of
+    def integrated_gradients(self, x, target=None, baseline=0.0, steps=50, method="gausslegendre", score="logit", chunk=None):
+        """Integrated gradients of a batch x [B, H, W, D] (ViT.integrated_gradients on ViT3DEncoder.forward's view: the arguments, the
+        passes and the side effects - none: no p.grad, no gradient arena, no host synchronisation - are described there; call eval()
+        first).  baseline: a float, or a tensor of x's shape or [1, S, S, S].  steps / method: path_quadrature.  chunk None:
+        max(1, min(64, 2^29 // (4 S^3))) points per pass.  It runs in the training arithmetic (16-bit operands): precision("fp32") does
+        not apply.  Returns a dict of device tensors:
+          attributions [B, S, S, S]; token_maps [B, G^3] the sum and token_abs [B, G^3] the sum of absolute values of every patch's
+          attributions (nv_attr_token_sums; token order - what token_maps_to_volumes and perturbation_curves take); class_idx [B];
+          score_input / score_baseline [B]; delta [B] float64 = sum of token_maps in double - (score_input - score_baseline), the
+          completeness residual; alphas / weights [steps]."""
+        from . import ops
+        S, G, _ = self._perturbation_inputs("integrated_gradients", x, baseline, score, 1 if chunk is None else chunk)
+        path_quadrature(method, steps)                                 # (ValueError before any device work)
+        volume = x.to(device=self.device, dtype=torch.float32).contiguous()
+        if torch.is_tensor(baseline):
+            baseline = baseline.to(device=volume.device, dtype=torch.float32).permute(0, 3, 1, 2).unsqueeze(1)
+        vit = self.volume_encoder.vit3d
+        out = vit.integrated_gradients(volume.permute(0, 3, 1, 2).unsqueeze(1), target=target, baseline=baseline, steps=steps, method=method,
+                                       score=score, chunk=chunk)       # ViT3DEncoder.forward's view: the storage order stays [B, H, W, D]
+        attributions = out["attributions"].squeeze(1).permute(0, 2, 3, 1)
+        sums = ops.attr_token_sums(attributions, self.config['TRAINING_VIT_PATCH_SIZE'])
+        token_maps, token_abs = sums[:, :, 0].contiguous(), sums[:, :, 1].contiguous()
+        delta = token_maps.double().sum(1) - (out["score_input"].double() - out["score_baseline"].double())
+        return dict(out, attributions=attributions, token_maps=token_maps, token_abs=token_abs, delta=delta)
 
     def visualize_slice(self, cam_3d, original_volume):
         """One 2-D slice of the volume and of its CAM along GRADCAM_SLICE_DIM at GRADCAM_SLICE_IDX

@@ -643,6 +643,101 @@ def occlusion_gather(ref: torch.Tensor, scores: torch.Tensor, labels: torch.Tens
     return maps
 
 
+def _rows(t: torch.Tensor, rows: Optional[int] = None, V: Optional[int] = None) -> bool:
+    """t is a dense fp32 [rows, V] device buffer (one row after the other)"""
+    return (t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) == t.shape[1])
+            and (rows is None or t.shape[0] == rows) and (V is None or t.shape[1] == V))
+
+
+def _path_baseline(what: str, baseline, B: int, V: int):
+    """(value, base tensor or None, stride in elements) of a baseline that is a float, or a dense [B, V] / [1, V] tensor"""
+    if not torch.is_tensor(baseline):
+        return float(baseline), None, 0
+    if tuple(baseline.shape) not in ((B, V), (1, V)):
+        raise ValueError(f"neurovit_amd: {what}: baseline of shape {tuple(baseline.shape)}, expected {(B, V)} or {(1, V)}")
+    assert _rows(baseline)
+    return 0.0, baseline, (V if baseline.shape[0] == B and B > 1 else 0)
+
+
+def path_points(x: torch.Tensor, jobs: torch.Tensor, alphas: torch.Tensor, baseline=0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x f32 [B, V] (every sample as V dense floats), jobs int32 [J, 2] of rows (b, k), alphas f32 [K], all on the device -> f32 [J, V]:
+    point j is bl + alphas[k] * (x[b] - bl), three separately rounded fp32 operations (the bits of that torch expression on the CPU).
+    baseline: a float, or a tensor [B, V] (one per source volume) or [1, V] (shared).  A job with b or k out of range leaves its row of
+    `out` as it was.  nv_path_points, one launch."""
+    _need_cuda(x, jobs, alphas, out, baseline if torch.is_tensor(baseline) else None)
+    assert _rows(x) and jobs.dim() == 2 and jobs.shape[1] == 2 and jobs.dtype == torch.int32 and jobs.is_contiguous()
+    assert alphas.dim() == 1 and alphas.dtype == torch.float32 and alphas.is_contiguous()
+    (B, V), J = x.shape, jobs.shape[0]
+    value, base, stride = _path_baseline("path_points", baseline, B, V)
+    if out is None:
+        out = torch.empty((J, V), dtype=torch.float32, device=x.device)
+    assert _rows(out, J, V) and out.device == x.device
+    check(lib.nv_path_points(_p(x), B, V, _p(jobs), J, _p(alphas), alphas.shape[0], value, _p(base), stride, _p(out), _stream()), "nv_path_points")
+    return out
+
+
+def class_score_grads(logits: torch.Tensor, jobs: torch.Tensor, cls: torch.Tensor, kind: str = "logit") -> torch.Tensor:
+    """logits f32 [J, C], jobs int32 [J, 2] (column 0: the source volume b_j), cls int64 [B] -> f32 [J, C]: the gradient of the score of
+    class cls[b_j] w.r.t. row j - "logit": its one-hot; "prob": p_c (delta_ci - p_i) with the fp32 softmax of class_scores.  A class out of
+    range gives a row of NaN.  nv_class_score_grads, one launch."""
+    _need_cuda(logits, jobs, cls)
+    if kind not in SCORE_KINDS:
+        raise ValueError(f"neurovit_amd: class_score_grads: kind must be 'prob' or 'logit', got {kind!r}")
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous()
+    J, C = logits.shape
+    assert jobs.shape == (J, 2) and jobs.dtype == torch.int32 and jobs.is_contiguous()
+    assert cls.dim() == 1 and cls.dtype == torch.int64 and cls.is_contiguous()
+    dlogits = torch.empty((J, C), dtype=torch.float32, device=logits.device)
+    check(lib.nv_class_score_grads(_p(logits), J, C, _p(jobs), _p(cls), cls.shape[0], SCORE_KINDS[kind], _p(dlogits), _stream()),
+          "nv_class_score_grads")
+    return dlogits
+
+
+def path_accumulate(g: torch.Tensor, jobs: torch.Tensor, weights: torch.Tensor, acc: torch.Tensor) -> torch.Tensor:
+    """g f32 [J, V], jobs int32 [J, 2] of rows (b, k), weights f32 [K], acc f32 [B, V]: acc[b] += weights[k] * g[j] over the jobs of
+    volume b in job order (a rounded product, then a rounded sum); volumes absent from `jobs` keep their bits.  In place; at most 1024
+    jobs.  nv_path_accumulate, one launch."""
+    _need_cuda(g, jobs, weights, acc)
+    assert _rows(g) and _rows(acc, None, g.shape[1]) and g.device == acc.device
+    J, V = g.shape
+    assert jobs.shape == (J, 2) and jobs.dtype == torch.int32 and jobs.is_contiguous()
+    assert weights.dim() == 1 and weights.dtype == torch.float32 and weights.is_contiguous()
+    check(lib.nv_path_accumulate(_p(g), _p(jobs), J, _p(weights), weights.shape[0], _p(acc), acc.shape[0], V, _stream()), "nv_path_accumulate")
+    return acc
+
+
+def path_finish(acc: torch.Tensor, x: torch.Tensor, baseline=0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """acc, x f32 [B, V] -> f32 [B, V]: (x - bl) * acc, a rounded difference then a rounded product; baseline as path_points.
+    nv_path_finish, one launch."""
+    _need_cuda(acc, x, out, baseline if torch.is_tensor(baseline) else None)
+    assert _rows(x) and _rows(acc, *x.shape) and acc.device == x.device
+    B, V = x.shape
+    value, base, stride = _path_baseline("path_finish", baseline, B, V)
+    if out is None:
+        out = torch.empty((B, V), dtype=torch.float32, device=x.device)
+    assert _rows(out, B, V) and out.device == x.device
+    check(lib.nv_path_finish(_p(acc), _p(x), B, V, value, _p(base), stride, _p(out), _stream()), "nv_path_finish")
+    return out
+
+
+def attr_token_sums(attr: torch.Tensor, patch) -> torch.Tensor:
+    """attr f32 [B, S0, S1, S2] (NeuroEncoder.forward's layout, device), patch: an int or three -> f32 [B, N, 2]: per patch token (numbered
+    as the engine's patch gather numbers them) the sum and the sum of absolute values of its voxels, accumulated in double in a fixed
+    order.  nv_attr_token_sums, one launch."""
+    _need_cuda(attr)
+    patch = _triple(patch, "patch")
+    assert attr.dim() == 4 and attr.dtype == torch.float32 and attr.is_contiguous()
+    B, size = attr.shape[0], tuple(attr.shape[1:])
+    if any(s % p for s, p in zip(size, patch)):
+        raise ValueError(f"neurovit_amd: attr_token_sums: volume {size} is not a whole number of {patch} patches")
+    N = (size[0] // patch[0]) * (size[1] // patch[1]) * (size[2] // patch[2])
+    sums = torch.empty((B, N, 2), dtype=torch.float32, device=attr.device)
+    s3, p3 = (ctypes.c_int * 3)(*size), (ctypes.c_int * 3)(*patch)
+    check(lib.nv_attr_token_sums(_p(attr), B, ctypes.cast(s3, ctypes.c_void_p), ctypes.cast(p3, ctypes.c_void_p), _p(sums), _stream()),
+          "nv_attr_token_sums")
+    return sums
+
+
 def dropout_apply(x: torch.Tensor, drop_seed: int = 0, drop_p: float = 0.0, want16: bool = True, want32: bool = False):
     """x f32 [M, N] times the dropout mask of one site -> (bf16 copy or None, f32 copy or None)."""
     _need_cuda(x)

@@ -264,6 +264,18 @@ class PatchRearrange(nn.Module):
         return f"'b c (f pf) (h p1) (w p2) -> b (f h w) (p1 p2 pf c)', p1={self.p1}, p2={self.p2}, pf={self.pf}"
 
 
+def _batch_dense(t: torch.Tensor) -> bool:
+    """every sample of t is one run of t[0].numel() elements of its storage (in any axis order), one sample after the other"""
+    V, expect = t[0].numel(), 1
+    if t.shape[0] > 1 and t.stride(0) != V:
+        return False
+    for stride, size in sorted((st, sz) for sz, st in zip(t.shape[1:], t.stride()[1:]) if sz > 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
 class _ViTFunction(torch.autograd.Function):
     """Whole-encoder autograd node.  Parameters are passed as inputs only so autograd knows the output
     depends on them; their gradients are written by the engine directly into the module's gradient
@@ -686,6 +698,123 @@ class ViT(nn.Module):
         u <- u + u A_l from the last layer down (no [n, n] product is formed).  target as attention_gradients."""
         logits, maps = self.attention_gradients(video, target=target, form="relevance")
         return logits, ops.attn_relevance([maps[l] for l in range(self._cfg.depth)], start_mean=self.pool == "mean")
+
+    def integrated_gradients(self, video, target=None, baseline=0.0, steps=50, method="gausslegendre", score="logit", chunk=None,
+                             vol_sigma=None, time_points=0):
+        """Integrated gradients of a class score along the straight path from a baseline to the input (Sundararajan et al.; captum's
+        IntegratedGradients): attributions = (x - bl) * sum_k w_k dF/dx(bl + alpha_k (x - bl)), for every volume of the batch.
+          video      [B, C, F, H, W] fp32 on the device, non-overlapping and dense with the batch outermost (a contiguous tensor, or the
+                     permute view ViT3DEncoder.forward makes of a contiguous [B, H, W, D]); anything else raises ValueError.  The kernels work
+                     on the storage order: the point and gradient buffers have `video`'s strides;
+          target     None = the arg-max class of each input volume, an int, or a LongTensor [B];
+          baseline   a float, or a tensor of video's shape or [1, C, F, H, W] (shared);
+          steps, method   the K points and weights of NeuroEncoder.path_quadrature ("gausslegendre", captum's default, "riemann_middle",
+                     "riemann_trapezoid");
+          score      "logit" or "prob" (the fp32 softmax probability of ops.class_scores);
+          chunk      points per pass (None: max(1, min(64, 2^29 // (4 V))), V floats per volume - two [chunk, V] buffers live at once).
+        Jobs are volume-major (b, 0 .. K - 1).  Every slice of `chunk` jobs: nv_path_points into one reused buffer, one graph-recording
+        forward (as attention_gradients: the training arithmetic, 16-bit operands - precision("fp32") does not apply), nv_class_score_grads,
+        the data-only backward into one reused gradient buffer, nv_path_accumulate; nv_path_finish after the loop.  One plain forward of
+        cat(x, baseline), in the module's current mode and precision, gives class_idx and the two end scores.
+        Returns a dict of device tensors: attributions (video's shape and strides), class_idx [B], score_input / score_baseline [B],
+        delta [B] float64 = sum(attributions) - (score_input - score_baseline) with the sum in double (the completeness residual: the
+        quadrature error plus the 16-bit arithmetic), alphas / weights [K].
+        Works under torch.no_grad(); touches no p.grad and no gradient arena whether the model is trainable or frozen; no autograd
+        backward runs, so backward hooks do not fire, and forward hooks on `attend` fire for the plain forward only; nothing is read back
+        and nothing synchronises with the host.  Runs in the module's current mode - call eval() first: in train mode every pass
+        draws its own dropout masks.  Not available (NotImplementedError) with the fp8 training forward, the fused 4D input form
+        (time_points) or RAW volumes (vol_sigma)."""
+        from .NeuroEncoder import path_quadrature
+        if score not in ops.SCORE_KINDS:
+            raise ValueError(f"neurovit_amd.ViT: score must be 'prob' or 'logit', got {score!r}")
+        if chunk is not None and (isinstance(chunk, bool) or int(chunk) != chunk or chunk < 1):
+            raise ValueError(f"neurovit_amd.ViT: chunk must be a positive integer, got {chunk!r}")
+        alphas, weights = path_quadrature(method, steps)             # (ValueError for a bad rule or step count, before any device work)
+        if time_points:
+            raise NotImplementedError("neurovit_amd.ViT: no integrated gradients through the fused 4D input form (time_points) - it is "
+                                      "forward-only; pass the [B*T, C, F, H, W] volumes instead")
+        if vol_sigma is not None:
+            raise NotImplementedError("neurovit_amd.ViT: no integrated gradients of RAW volumes (vol_sigma / forward_raw): the folded z-score "
+                                      "treats sigma as a constant - normalise the volume first and attribute w.r.t. that")
+        if self._fp8 is not None and self.fp8_training:
+            raise NotImplementedError("neurovit_amd.ViT: no integrated gradients through the fp8 training forward - disable_fp8() or "
+                                      "enable_fp8(training=False) first")
+        self.check_video(video)
+        B, C = video.shape[0], self._cfg.num_classes
+        V = video[0].numel()
+        if video.dtype != torch.float32 or not _batch_dense(video):
+            raise ValueError(f"neurovit_amd.ViT: integrated_gradients needs an fp32 video that is non-overlapping and dense with the batch "
+                             f"outermost, got {video.dtype} with shape {tuple(video.shape)} and strides {tuple(video.stride())}")
+        if torch.is_tensor(baseline):
+            if tuple(baseline.shape) not in (tuple(video.shape), (1,) + tuple(video.shape[1:])):
+                raise ValueError(f"neurovit_amd.ViT: baseline of shape {tuple(baseline.shape)}, expected {tuple(video.shape)} or "
+                                 f"{(1,) + tuple(video.shape[1:])}")
+        else:
+            baseline = float(baseline)
+        if not torch.is_tensor(target) and target is not None and not 0 <= int(target) < C:
+            raise ValueError(f"neurovit_amd.ViT: target class {target} outside [0, {C})")
+        if torch.is_tensor(target) and target.numel() != B:
+            raise ValueError(f"neurovit_amd.ViT: target must hold one class per volume ({B}), got {tuple(target.shape)}")
+        K = alphas.shape[0]
+        chunk = min(max(1, min(64, 2 ** 29 // (4 * V))) if chunk is None else int(chunk), B * K)
+        device, inner = video.device, tuple(video.stride()[1:])
+
+        def like_video(rows):                                        # [rows, C, F, H, W] in the storage order of `video`
+            return torch.empty_strided((rows,) + tuple(video.shape[1:]), (V,) + inner, dtype=torch.float32, device=device)
+
+        def flat(t):                                                 # the same memory as dense [rows, V]
+            return t.as_strided((t.shape[0], V), (V, 1), t.storage_offset())
+
+        with torch.no_grad():
+            video = video.detach()
+            alphas, weights = alphas.to(device), weights.to(device)
+            ends = like_video(2 * B)
+            ends[:B].copy_(video)
+            if torch.is_tensor(baseline):
+                ends[B:].copy_(baseline.to(device=device, dtype=torch.float32).expand_as(video))
+                base = flat(ends[B:]) if baseline.shape[0] == B else flat(ends[B:B + 1])
+            else:
+                ends[B:].fill_(baseline)
+                base = baseline
+            x = flat(ends[:B])                                       # (a copy of the input: 16-byte aligned whatever `video` was)
+            end_logits = self(ends).float().contiguous()
+            if target is None:
+                cls = end_logits[:B].argmax(dim=1)
+            elif torch.is_tensor(target):
+                cls = target.to(device=device, dtype=torch.long).reshape(-1).contiguous()
+            else:
+                cls = torch.full((B,), int(target), dtype=torch.long, device=device)
+            tables = self.__dict__.setdefault("_path_tables", {})
+            key = (str(device), B, K)
+            if key not in tables:
+                if len(tables) >= 16:
+                    tables.clear()
+                b = torch.arange(B, device=device, dtype=torch.int64)
+                jobs = torch.stack([b.repeat_interleave(K), torch.arange(K, device=device, dtype=torch.int64).repeat(B)], 1).to(torch.int32).contiguous()
+                zero = torch.zeros(2 * B, device=device, dtype=torch.int64)
+                tables[key] = (jobs, torch.stack([b.repeat(2), zero, zero], 1).to(torch.int32).contiguous())      # rows (b, 0, 0): the end scores
+            jobs, end_jobs = tables[key]
+            end_scores = ops.class_scores(end_logits, end_jobs, cls, kind=score)
+
+            points, grads = like_video(chunk), like_video(chunk)
+            acc = torch.empty((B, V), dtype=torch.float32, device=device).zero_()
+            for first in range(0, B * K, chunk):
+                count = min(chunk, B * K - first)
+                part = jobs[first:first + count]
+                ops.path_points(x, part, alphas, base, out=flat(points[:count]))
+                logits = self._run_forward(points[:count], True, (None, 0, None))
+                rec = self._rt._cur
+                dlogits = ops.class_score_grads(logits.float().contiguous(), part, cls, kind=score)
+                self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=grads[:count], weight_grads=False)
+                rec.done = True                   # nothing more of this pass will run: its workspace may be refilled
+                self._rt.backward_done = True
+                ops.path_accumulate(flat(grads[:count]), part, weights, acc)
+            attributions = like_video(B)
+            ops.path_finish(acc, x, base, out=flat(attributions))
+            score_input, score_baseline = end_scores[:B], end_scores[B:]
+            delta = flat(attributions).sum(dim=1, dtype=torch.float64) - (score_input.double() - score_baseline.double())
+        return {"attributions": attributions, "class_idx": cls, "score_input": score_input, "score_baseline": score_baseline, "delta": delta,
+                "alphas": alphas, "weights": weights}
 
     def _run_backward(self, dlogits, dvideo=None):
         """Parameter gradients of every parameter that requires one; dvideo (or None): receives d loss / d video.  With no parameter
