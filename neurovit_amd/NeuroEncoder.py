@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .vit_3d import ViT
+from .vit_3d import ViT, cached_table, target_classes
 
 
 def _encoder_weights_of(checkpoint: dict, prefix: str = "volume_encoder.") -> dict:
@@ -31,6 +31,12 @@ def perturbation_step_bounds(tokens: int, steps: int, device=None) -> torch.Tens
     removed / present - k N / steps rounded half up in integers, so m_0 = 0, m_steps = N and the bounds never decrease."""
     k = torch.arange(steps + 1, device=device, dtype=torch.int64)
     return (2 * k * tokens + steps) // (2 * steps)
+
+
+def _grid_geometry(config, threshold=None):
+    """(size S of the volume, cells G per axis of its patch grid, percent of the cells a map keeps: `threshold`, None = GRADCAM_THRESHOLD)"""
+    size = config['TRAINING_VIT_INPUT_SIZE']
+    return size, size // config['TRAINING_VIT_PATCH_SIZE'], config['GRADCAM_THRESHOLD'] if threshold is None else threshold
 
 
 PATH_METHODS = ("gausslegendre", "riemann_middle", "riemann_trapezoid")
@@ -170,7 +176,7 @@ class NeuroEncoder(nn.Module):
         """Grad-CAM of the predicted class on the patch grid, thresholded and upsampled to the volume
         (same contract as NeuroEncoder.py:84-133: returns (cam[S,S,S] on the CPU, class_idx)).
 
-        The [B,n,d] activation and gradient never leave the device: `nv_gradcam_reduce` (csrc/gradcam.hip) turns them
+        The [B,n,d] activation and gradient never leave the device: `nv_gradcam_reduce` (csrc/attribution.hip) turns them
         into the normalised G^3 map in one launch, and only those G^3 floats cross PCIe for the percentile / upsampling."""
         from . import ops
         logits = self.forward(x)
@@ -187,12 +193,13 @@ class NeuroEncoder(nn.Module):
             token_map = token_map.cpu()
         return self._token_map_to_volume(token_map), predicted
 
-    def _token_map_to_volume(self, token_map):
-        """[1, G^3] normalised CPU map of the patch tokens -> [S, S, S]: the top GRADCAM_THRESHOLD % of the cells (linear-interpolated
-        percentile, as numpy.percentile), the rest zeroed, trilinear upsampling to the volume (NeuroEncoder.py:120-131)."""
-        size = self.config['TRAINING_VIT_INPUT_SIZE']
-        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
-        keep_percent = self.config['GRADCAM_THRESHOLD']
+    def _token_map_to_volume(self, token_map, normalize=False):
+        """[1, G^3] CPU map of the patch tokens -> [S, S, S]: min-max normalised over the map (normalize; else it arrives normalised), the
+        top GRADCAM_THRESHOLD % of the cells (linear-interpolated percentile, as numpy.percentile), the rest zeroed, trilinear upsampling
+        to the volume (NeuroEncoder.py:120-131)."""
+        size, cells, keep_percent = _grid_geometry(self.config)
+        if normalize:
+            token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
         grid = token_map.reshape(1, cells, cells, cells)               # one sample, as in the reference
         cut = torch.quantile(grid.double().flatten(), 1.0 - keep_percent / 100.0).to(grid.dtype)
         sparse = torch.where(grid >= cut, grid, torch.zeros_like(grid))
@@ -210,10 +217,7 @@ class NeuroEncoder(nn.Module):
         volume = x.to(self.device)
         with torch.no_grad():
             logits, rollout = vit.attention_rollout(volume.permute(0, 3, 1, 2).unsqueeze(1))     # ViT3DEncoder.forward's view
-        predicted = logits.argmax(dim=1)
-        token_map = rollout.cpu()
-        token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
-        return self._token_map_to_volume(token_map), predicted
+        return self._token_map_to_volume(rollout.cpu(), normalize=True), logits.argmax(dim=1)
 
     def get_attention_relevance(self, x, target=None):
         """Class-specific attention relevance of the ViT3D encoder on the patch grid (gradient-weighted attention relevance, Chefer et al.:
@@ -226,15 +230,7 @@ class NeuroEncoder(nn.Module):
         vit = self.volume_encoder.vit3d
         volume = x.to(self.device)
         logits, relevance = vit.attention_relevance(volume.permute(0, 3, 1, 2).unsqueeze(1), target=target)   # ViT3DEncoder.forward's view
-        if target is None:
-            class_idx = logits.argmax(dim=1)
-        elif torch.is_tensor(target):
-            class_idx = target.to(logits.device).long().reshape(-1)
-        else:
-            class_idx = torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
-        token_map = relevance.cpu()
-        token_map = (token_map - token_map.min()) / (token_map.max() - token_map.min() + 1e-8)
-        return self._token_map_to_volume(token_map), class_idx
+        return self._token_map_to_volume(relevance.cpu(), normalize=True), target_classes(target, logits)
 
     # ---- batched attribution, on the device (csrc/attribution.hip): the three maps above for a whole batch, every volume on its own
     def token_maps_to_volumes(self, token_maps, normalize=True, threshold=None):
@@ -243,9 +239,7 @@ class NeuroEncoder(nn.Module):
         normalisation over the volume's own cells (normalize), the top `threshold` % of its cells kept (None: GRADCAM_THRESHOLD;
         torch.quantile's linear rule), trilinear upsampling to the volume.  The building block for any map on the patch grid."""
         from . import ops
-        size = self.config['TRAINING_VIT_INPUT_SIZE']
-        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
-        keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
+        size, cells, keep_percent = _grid_geometry(self.config, threshold)
         maps = token_maps.to(device=self.device, dtype=torch.float32).contiguous()
         return ops.token_maps_to_volumes(maps, cells, size, normalize=normalize, keep_percent=keep_percent)
 
@@ -270,59 +264,46 @@ class NeuroEncoder(nn.Module):
             raise NotImplementedError("attribution_volumes: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
         if method not in ("gradcam", "rollout", "relevance", "occlusion", "integrated_gradients"):
             raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout', 'relevance', 'occlusion' or 'integrated_gradients', got {method!r}")
-        if method in ("occlusion", "integrated_gradients"):
-            if method == "occlusion":
-                # the signed occlusion map (one patch per job, zero baseline, probability score); the volume shows what SUPPORTS the class
-                signed, class_idx = self.occlusion_sensitivity(x, target=target)
-            else:
-                # the signed patch sums of integrated gradients (zero baseline, 50 Gauss-Legendre points, the class logit)
-                result = self.integrated_gradients(x, target=target)
-                signed, class_idx = result["token_maps"], result["class_idx"]
-            size = self.config['TRAINING_VIT_INPUT_SIZE']
-            keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
-            volumes, (normalised, _, _) = ops.token_maps_to_volumes(torch.relu(signed), size // self.config['TRAINING_VIT_PATCH_SIZE'], size, normalize=True,
-                                                                    keep_percent=keep_percent, return_maps=True)
-            return (volumes, class_idx, normalised) if return_token_maps else (volumes, class_idx)
         vit = self.volume_encoder.vit3d
-        volume = x.to(self.device)
-
-        def explained(logits):
-            if target is None:
-                return logits.argmax(dim=1)
-            if torch.is_tensor(target):
-                return target.to(logits.device).long().reshape(-1)
-            return torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
-
-        if method == "gradcam":
+        normalize = True
+        if method == "occlusion":
+            # the signed occlusion map (one patch per job, zero baseline, probability score); the volume shows what SUPPORTS the class
+            signed, class_idx = self.occlusion_sensitivity(x, target=target)
+            token_maps = torch.relu(signed)
+        elif method == "integrated_gradients":
+            # the signed patch sums of integrated gradients (zero baseline, 50 Gauss-Legendre points, the class logit)
+            result = self.integrated_gradients(x, target=target)
+            token_maps, class_idx = torch.relu(result["token_maps"]), result["class_idx"]
+        elif method == "gradcam":
+            volume = x.to(self.device)
             with torch.enable_grad():
                 if not (volume.requires_grad or any(p.requires_grad for p in vit.parameters())):
                     volume = volume.detach().requires_grad_(True)       # a frozen model: the data-only backward delivers the hook gradient
                 logits = self.forward(volume)
-                class_idx = explained(logits.detach())
+                class_idx = target_classes(target, logits.detach())
                 logits.backward(gradient=F.one_hot(class_idx, logits.shape[1]).to(logits.dtype))
             token_maps, _ = ops.gradcam_reduce_per_volume(vit.last_attn_norm_output_raw(), vit.last_attn_norm_grad_raw())
             normalize = False                                           # the reduction has normalised every volume
-        elif method == "rollout":
-            with torch.no_grad():
-                logits, token_maps = vit.attention_rollout(volume.permute(0, 3, 1, 2).unsqueeze(1))     # ViT3DEncoder.forward's view
-            class_idx, normalize = logits.argmax(dim=1), True
         else:
-            logits, token_maps = vit.attention_relevance(volume.permute(0, 3, 1, 2).unsqueeze(1), target=target)
-            class_idx, normalize = explained(logits), True
+            video = x.to(self.device).permute(0, 3, 1, 2).unsqueeze(1)     # ViT3DEncoder.forward's view
+            if method == "rollout":
+                with torch.no_grad():
+                    logits, token_maps = vit.attention_rollout(video)
+                class_idx = logits.argmax(dim=1)
+            else:
+                logits, token_maps = vit.attention_relevance(video, target=target)
+                class_idx = target_classes(target, logits)
 
-        size = self.config['TRAINING_VIT_INPUT_SIZE']
-        cells = size // self.config['TRAINING_VIT_PATCH_SIZE']
-        keep_percent = self.config['GRADCAM_THRESHOLD'] if threshold is None else threshold
+        size, cells, keep_percent = _grid_geometry(self.config, threshold)
         volumes, (normalised, _, _) = ops.token_maps_to_volumes(token_maps.contiguous(), cells, size, normalize=normalize, keep_percent=keep_percent,
                                                                 return_maps=True)
-        if return_token_maps:
-            return volumes, class_idx, normalised
-        return volumes, class_idx
+        return (volumes, class_idx, normalised) if return_token_maps else (volumes, class_idx)
 
     # ---- perturbation attribution, on the device (csrc/perturb.hip): how faithful a map is (deletion / insertion curves) and the
     # gradient-free baseline among the maps (patch occlusion sensitivity)
     def _perturbation_inputs(self, what, x, baseline, score, chunk):
         """argument checks shared by perturbation_curves / occlusion_sensitivity (all before any device work) -> (S, G, chunk)"""
+        from . import ops
         if self.config['TRAINING_DIM'] != 3:
             raise NotImplementedError(f"{what}: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
         if score not in ("prob", "logit"):
@@ -330,32 +311,12 @@ class NeuroEncoder(nn.Module):
         S = self.config['TRAINING_VIT_INPUT_SIZE']
         if x.dim() != 4 or tuple(x.shape[1:]) != (S, S, S) or x.shape[0] < 1:
             raise ValueError(f"{what}: x must be [B, {S}, {S}, {S}], got {tuple(x.shape)}")
-        if torch.is_tensor(baseline):
-            if tuple(baseline.shape) not in (tuple(x.shape), (1, S, S, S)):
-                raise ValueError(f"{what}: baseline of shape {tuple(baseline.shape)}, expected {tuple(x.shape)} or {(1, S, S, S)}")
-        else:
-            float(baseline)
+        ops.check_baseline(what, baseline, x.shape)
         if chunk is None:
             chunk = max(1, min(64, 2 ** 30 // (4 * S ** 3)))
         elif int(chunk) != chunk or chunk < 1:
             raise ValueError(f"{what}: chunk must be a positive integer, got {chunk!r}")
         return S, S // self.config['TRAINING_VIT_PATCH_SIZE'], int(chunk)
-
-    def _perturbation_table(self, key, build):
-        """job tables / block labels: device tensors built once per geometry by integer arithmetic on torch.arange"""
-        cache = self.__dict__.setdefault("_perturbation_tables", {})
-        if key not in cache:
-            if len(cache) >= 16:
-                cache.clear()
-            cache[key] = build()
-        return cache[key]
-
-    def _explained_classes(self, logits, target):
-        if target is None:
-            return logits.argmax(dim=1)
-        if torch.is_tensor(target):
-            return target.to(logits.device).long().reshape(-1).contiguous()
-        return torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
 
     def _perturbed_logits(self, volume, labels, jobs, baseline, chunk):
         """logits [J, C] of the masked copies (ops.mask_patches) of `volume`: consecutive slices of `chunk` jobs, each masked into one
@@ -414,10 +375,10 @@ class NeuroEncoder(nn.Module):
                       "insertion": torch.stack([m, full], 1)}[mode]                                  # [K or 2 K, 2]: (lo, hi)
             source = torch.arange(B, device=device, dtype=torch.int64).repeat_interleave(bounds.shape[0])
             return torch.cat([source[:, None], bounds.repeat(B, 1)], 1).to(torch.int32).contiguous(), (torch.arange(K, device=device, dtype=torch.float64) / steps).float()
-        jobs, fractions = self._perturbation_table(("curves", str(device), B, N, steps, mode), build)
+        jobs, fractions = cached_table(self, "_perturbation_tables", ("curves", str(device), B, N, steps, mode), build)
 
         with torch.no_grad():
-            class_idx = self._explained_classes(self.forward(volume), target)
+            class_idx = target_classes(target, self.forward(volume))
         ranks = ops.token_ranks(token_maps.to(device=device, dtype=torch.float32).contiguous())
         logits = self._perturbed_logits(volume, ranks, jobs, baseline, chunk)
         scores = ops.class_scores(logits, jobs, class_idx, kind=score).view(B, -1)
@@ -456,11 +417,11 @@ class NeuroEncoder(nn.Module):
             jobs = torch.stack([b.repeat_interleave(NB), j, j + 1], 1).to(torch.int32).contiguous()
             plain = torch.stack([b, torch.zeros_like(b), torch.zeros_like(b)], 1).to(torch.int32).contiguous()      # rows (b, 0, 0): x itself
             return block.to(torch.int32).repeat(B, 1).contiguous(), jobs, plain
-        labels, jobs, plain = self._perturbation_table(("occlusion", str(device), B, G, w), build)
+        labels, jobs, plain = cached_table(self, "_perturbation_tables", ("occlusion", str(device), B, G, w), build)
 
         with torch.no_grad():
             unperturbed = self.forward(volume).float().contiguous()
-        class_idx = self._explained_classes(unperturbed, target)
+        class_idx = target_classes(target, unperturbed)
         reference = ops.class_scores(unperturbed, plain, class_idx, kind=score)
         logits = self._perturbed_logits(volume, labels, jobs, baseline, chunk)
         scores = ops.class_scores(logits, jobs, class_idx, kind=score).view(B, NB)

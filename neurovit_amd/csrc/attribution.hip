@@ -2,38 +2,52 @@
 // get_attention_map / get_attention_rollout / get_attention_relevance (src/models/NeuroEncoder.py:101-131) for a whole batch, every
 // volume on its own.
 //
-//   nv_gradcam_reduce_per_volume   the row arithmetic of nv_gradcam_reduce (gradcam.hip), min-max normalised over each volume's own cells
+//   nv_gradcam_reduce              the Grad-CAM reduction of get_attention_map, min-max normalised over the whole [B, n-1] map
+//   nv_gradcam_reduce_per_volume   the same row arithmetic, min-max normalised over each volume's own cells
 //   nv_token_map_to_volume         per volume: min-max normalisation (optional) -> the percentile cut of torch.quantile(linear) ->
 //                                  threshold -> trilinear upsampling (align_corners = False, ATen's index arithmetic)
 //
 // The only real bytes are the B * S0 * S1 * S2 * 4 of the volumes: the upsampling is a streaming kernel with 16-byte stores along the
 // contiguous axis; everything in front of it works on <= 4096 cells per volume inside one workgroup's LDS.
-#include "common.h"
+#include "attr_common.h"
 
 namespace {
-// ------------------------------------------------------------------------------------------------ per-volume Grad-CAM reduction
+// ------------------------------------------------------------------------------------------------ Grad-CAM reduction
+// The reduction of the reference's NeuroEncoder.get_attention_map (src/models/NeuroEncoder.py:101-116) as ONE launch.
+//
+//   weights[b,t] = mean_d grad[b,t,:]          cam[b,t] = sum_d weights[b,t] * act[b,t,:] = weights[b,t] * sum_d act[b,t,:]
+//   cam = relu(cam[:, 1:])  (cls token dropped)  ->  (cam - min) / (max - min + 1e-8)  over a group of cells
+//
+// act = output of the last block's attention LayerNorm (16-bit, the engine's xn1 buffer), grad = its gradient (fp32, the engine's
+// hookg buffer): 2 x [B, n, d] on the device -> [B, n-1] floats.  HBM-bound (reads 6 B per element once).
 constexpr int GC_THREADS = 256;
 constexpr int GC_WAVES = GC_THREADS / 64;
-constexpr int GCV_MAX_BLOCKS = 128;      // workgroups per volume
+constexpr int GC_MAX_BLOCKS = 512;       // workgroups of the whole map (nv_gradcam_reduce)
+constexpr int GCV_MAX_BLOCKS = 128;      // workgroups per volume (nv_gradcam_reduce_per_volume)
 
-// Grid (blocks per volume, B).  The rows of volume b are dealt over its blocks; the volume's min / max crosses them through per-block
-// partials and ONE arrival ticket per volume (the agent-scope release / acquire of gradcam.hip): the last block of a volume to arrive
-// normalises that volume.  Row sums, min / max and the normalisation are the expressions of gradcam_reduce_kernel, so volume b has the
-// bits of nv_gradcam_reduce on its slice (min / max are exact in any order).
+// Grid (blocks per group, groups).  A group is `R` consecutive rows of the flat [B * (n-1)] map that share one min / max: the whole map
+// (one group of B (n-1) rows) or one volume (B groups of n-1 rows).  Flat row r is token r % N + 1 of volume r / N (token 0 is the cls
+// token).  One wave per row (two row reductions by wave shuffles); the rows of a group are dealt over its blocks, its min / max
+// crosses them through per-block partials and ONE arrival ticket per group: the LAST block of a group to arrive normalises that
+// group's (tiny) map.  The hand-off is the placement-independent agent-scope release / acquire of the CDNA4 guide (Guideline 16):
+// results do not depend on which workgroup is last, and min / max are exact in any order, so a volume has the same bits whether it
+// is reduced alone, as one group of a batch, or as part of a whole-batch group with the same extremes.
 template <typename T>
-__global__ __launch_bounds__(GC_THREADS) void gradcam_per_volume_kernel(const r16* __restrict__ act, const float* __restrict__ grad, int n, int d,
-                                                                        float* cam, float* __restrict__ part, unsigned* tickets, float* minmax) {
+__global__ __launch_bounds__(GC_THREADS) void gradcam_reduce_kernel(const r16* __restrict__ act, const float* __restrict__ grad, int n, int d, int R,
+                                                                    float* cam, float* __restrict__ part, unsigned* tickets, float* minmax) {
   __shared__ float s_min[GC_WAVES], s_max[GC_WAVES];
   __shared__ unsigned s_last;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int N = n - 1, b = blockIdx.y, nb = gridDim.x;
-  float* vcam = cam + (long)b * N;
-  float* vpart = part + 2L * b * nb;
-  float lo = INFINITY, hi = 0.f;                         // relu output is >= 0
-  for (int r = blockIdx.x * GC_WAVES + wid; r < N; r += nb * GC_WAVES) {
-    const long base = ((long)b * n + r + 1) * d;         // token 0 is the cls token
+  const int N = n - 1, g = blockIdx.y, nb = gridDim.x;
+  const int b0 = g * (R / N), t0 = g * (R % N);          // the group's first flat row g R = b0 N + t0, in 32-bit arithmetic (t0 may pass N)
+  float* gcam = cam + (long)g * R;
+  float* gpart = part + 2L * g * nb;
+  float lo = INFINITY, hi = 0.f;                         // relu output is >= 0, every workgroup owns >= 0 rows
+  for (int i = blockIdx.x * GC_WAVES + wid; i < R; i += nb * GC_WAVES) {
+    const int q = t0 + i, b = b0 + q / N, t = q - (q / N) * N + 1;
+    const long base = ((long)b * n + t) * d;
     float sg = 0.f, sa = 0.f;
-    for (int k = lane * 8; k < d; k += 64 * 8) {         // d % 8 == 0
+    for (int k = lane * 8; k < d; k += 64 * 8) {         // d % 8 == 0 (engine requirement)
       const r16x8 a = *reinterpret_cast<const r16x8*>(act + base + k);
       const f32x4 g0 = *reinterpret_cast<const f32x4*>(grad + base + k), g1 = *reinterpret_cast<const f32x4*>(grad + base + k + 4);
 #pragma unroll
@@ -42,14 +56,14 @@ __global__ __launch_bounds__(GC_THREADS) void gradcam_per_volume_kernel(const r1
     }
     sg = wave_sum(sg); sa = wave_sum(sa);
     const float v = fmaxf((sg / (float)d) * sa, 0.f);
-    if (lane == 0) vcam[r] = v;
+    if (lane == 0) gcam[i] = v;
     lo = fminf(lo, v); hi = fmaxf(hi, v);
   }
   if (lane == 0) { s_min[wid] = lo; s_max[wid] = hi; }
   __syncthreads();
   if (tid == 0) {
     for (int w = 1; w < GC_WAVES; ++w) { lo = fminf(lo, s_min[w]); hi = fmaxf(hi, s_max[w]); }
-    vpart[2 * blockIdx.x] = lo; vpart[2 * blockIdx.x + 1] = hi;
+    gpart[2 * blockIdx.x] = lo; gpart[2 * blockIdx.x + 1] = hi;
   }
   // publish: every storing wave drains its stores, the workgroup meets, ONE lane releases at agent scope and takes a ticket
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -57,7 +71,7 @@ __global__ __launch_bounds__(GC_THREADS) void gradcam_per_volume_kernel(const r1
   if (tid == 0) {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned tk = __hip_atomic_fetch_add(tickets + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned tk = __hip_atomic_fetch_add(tickets + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s_last = (tk == (unsigned)nb - 1) ? 1u : 0u;
     if (s_last) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
@@ -66,27 +80,20 @@ __global__ __launch_bounds__(GC_THREADS) void gradcam_per_volume_kernel(const r1
   }
   __syncthreads();
   if (!s_last) return;
-  // last arriver of this volume: min / max of its partials, then normalise its map
+  // last arriver of this group: min / max of its partials (fixed order), then normalise its map
   lo = INFINITY; hi = 0.f;
-  for (int i = 0; i < nb; ++i) { lo = fminf(lo, vpart[2 * i]); hi = fmaxf(hi, vpart[2 * i + 1]); }
+  for (int i = 0; i < nb; ++i) { lo = fminf(lo, gpart[2 * i]); hi = fmaxf(hi, gpart[2 * i + 1]); }
   const float inv = 1.0f / (hi - lo + 1e-8f);
-  for (int i = tid; i < N; i += GC_THREADS) vcam[i] = (vcam[i] - lo) * inv;
+  for (int i = tid; i < R; i += GC_THREADS) gcam[i] = (gcam[i] - lo) * inv;
   if (tid == 0) {
-    if (minmax) { minmax[2 * b] = lo; minmax[2 * b + 1] = hi; }
-    tickets[b] = 0;                                       // self-reset (the caller also zeroes the tickets in front of every launch)
+    if (minmax) { minmax[2 * g] = lo; minmax[2 * g + 1] = hi; }
+    tickets[g] = 0;                                       // self-reset (the caller also zeroes the tickets in front of every launch)
   }
 }
 
 // ------------------------------------------------------------------------------------------------ token maps -> thresholded maps
 constexpr int TM_THREADS = 256;
 constexpr int TM_MAX_CELLS = 4096;       // cells of one volume's grid: 16 KB of keys in LDS (16^3 = ViT3D-large)
-
-// order-preserving map of the fp32 bit patterns onto unsigned integers (and back)
-__device__ __forceinline__ unsigned key_of(float v) {
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float value_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 // The k-th smallest (0-based) of keys[0, N): radix select, eight bits per pass.  Every thread of the workgroup calls it and gets the key.
 __device__ unsigned select_kth(const unsigned* keys, int N, int k, unsigned* hist, unsigned* s_sel) {
@@ -139,8 +146,7 @@ __global__ __launch_bounds__(TM_THREADS) void token_map_threshold_kernel(const f
   float lo = INFINITY, hi = -INFINITY;
   if (normalize) {
     for (int i = tid; i < N; i += TM_THREADS) { const float v = maps[off + i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { lo = fminf(lo, __shfl_xor(lo, o, 64)); hi = fmaxf(hi, __shfl_xor(hi, o, 64)); }
+    lo = wave_min(lo); hi = wave_max(hi);
     if (lane == 0) { s_red[2 * wid] = lo; s_red[2 * wid + 1] = hi; }
     __syncthreads();
     lo = s_red[0]; hi = s_red[1];
@@ -151,7 +157,7 @@ __global__ __launch_bounds__(TM_THREADS) void token_map_threshold_kernel(const f
     float v = maps[off + i];
     if (normalize) v = (v - lo) * inv;
     norm[off + i] = v;
-    keys[i] = key_of(v);
+    keys[i] = float_key(v);
   }
   if (tid == 0) { s_cnt = 0; s_next = 0xffffffffu; }
   __syncthreads();
@@ -171,12 +177,12 @@ __global__ __launch_bounds__(TM_THREADS) void token_map_threshold_kernel(const f
   float cut;
   {
 #pragma clang fp contract(off)
-    const double a = (double)value_of(k_lo), e = (double)value_of(k_hi);
+    const double a = (double)float_of_key(k_lo), e = (double)float_of_key(k_hi);
     const double c = (w < 0.5) ? a + w * (e - a) : e - (e - a) * (1.0 - w);
     cut = (float)c;
   }
   for (int i = tid; i < N; i += TM_THREADS) {
-    const float v = value_of(keys[i]);
+    const float v = float_of_key(keys[i]);
     sparse[off + i] = (v >= cut) ? v : 0.f;
   }
   if (tid == 0) cuts[blockIdx.x] = cut;
@@ -200,8 +206,7 @@ __device__ __forceinline__ AxisTap axis_tap(int dst, float scale, int G) {
 
 // Grid (S0, B): one workgroup writes the S1 x S2 output plane (b, x).  It first collapses the x axis of the volume's grid into a
 // G1 x G2 plane in LDS and tabulates the y and z taps; every output then costs four LDS reads and three lerps.  The plane is written as
-// 16-byte stores over its flat extent (rows need not be multiples of four: the groups of four follow the alignment of `out`, the
-// few elements in front of the first / behind the last aligned group are stored singly).
+// 16-byte stores over its flat extent (rows need not be multiples of four: split_span, the groups of four follow the alignment of `out`).
 __global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const float* __restrict__ sparse, int G0, int G1, int G2, int S0, int S1, int S2,
                                                                         float sc0, float sc1, float sc2, float* __restrict__ out) {
   extern __shared__ float smem[];
@@ -223,9 +228,7 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const fl
   const long base = ((long)b * S0 + x) * plane_elems;      // flat offset of the plane in `out`
   float* o = out + base;
   const int P = (int)plane_elems;
-  int head = (int)((4 - (base & 3)) & 3);                  // `out` is 16-byte aligned
-  if (head > P) head = P;
-  const int groups = (P - head) >> 2, tail = head + 4 * groups;
+  const Span s = split_span(base, P);                      // `out` is 16-byte aligned
 
   auto value = [&](int yy, float ly1, int z) -> float {     // (yy, ly1): the y taps of the row, read once per row
     const int zz = zi[z];
@@ -235,10 +238,10 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const fl
     const float c = lz0 * plane[r1 + c0] + lz1 * plane[r1 + c1];
     return ly0 * a + ly1 * c;
   };
-  for (int e = tid; e < head; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
-  for (int e = tail + tid; e < P; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
-  for (int g = tid; g < groups; g += UP_THREADS) {
-    const int e = head + 4 * g;
+  for (int e = tid; e < s.head; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
+  for (int e = s.tail + tid; e < P; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
+  for (int g = tid; g < s.groups; g += UP_THREADS) {
+    const int e = s.head + 4 * g;
     int y = e / S2, z = e - y * S2;
     int yy = yi[y];
     float ly1 = yl[y];
@@ -252,16 +255,41 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const fl
   }
 }
 
-int gcv_blocks(int n) {
-  const int blocks = (n - 1 + GC_WAVES - 1) / GC_WAVES;
-  return blocks > GCV_MAX_BLOCKS ? GCV_MAX_BLOCKS : (blocks < 1 ? 1 : blocks);
+int gc_blocks(long rows, int cap) {
+  const long blocks = (rows + GC_WAVES - 1) / GC_WAVES;
+  return blocks > cap ? cap : (blocks < 1 ? 1 : (int)blocks);
 }
-long gcv_ticket_bytes(int B) { return ((4L * B + 15) / 16) * 16; }
+long gc_ticket_bytes(int groups) { return ((4L * groups + 15) / 16) * 16; }
+
+// workspace: the groups' tickets (zeroed here), then 2 floats per block and group
+int gradcam_launch(const char* name, const void* act, const float* grad, int n, int d, int groups, int R, int blocks, float* cam, float* minmax,
+                   void* workspace, void* stream) {
+  unsigned* tickets = (unsigned*)workspace;
+  float* part = (float*)((char*)workspace + gc_ticket_bytes(groups));
+  if (hipMemsetAsync(tickets, 0, gc_ticket_bytes(groups), (hipStream_t)stream) != hipSuccess) {
+    nv_set_error("%s: memset failed", name);
+    return NV_ERR_HIP;
+  }
+  NV_DISPATCH_OPERAND(T, hipLaunchKernelGGL(gradcam_reduce_kernel<T>, dim3(blocks, groups), dim3(GC_THREADS), 0, (hipStream_t)stream, (const r16*)act, grad, n,
+                                            d, R, cam, part, tickets, minmax));
+  NV_CHECK_LAUNCH(name);
+  return NV_OK;
+}
 }  // namespace
+
+extern "C" long nv_gradcam_workspace_bytes(int B, int n) { return gc_ticket_bytes(1) + 8L * gc_blocks((long)B * (n - 1), GC_MAX_BLOCKS); }
+
+extern "C" int nv_gradcam_reduce(const void* act, const float* grad, int B, int n, int d, float* cam, float* minmax, void* workspace,
+                                 long ws_bytes, void* stream) {
+  NV_CHECK_ARG(act && grad && cam && workspace && B > 0 && n > 1 && d > 0 && (d % 8) == 0, "nv_gradcam_reduce: bad arguments (d %% 8 == 0, n > 1)");
+  NV_CHECK_ARG(nv_aligned16(act) && nv_aligned16(grad) && nv_aligned16(workspace), "nv_gradcam_reduce: 16-byte alignment");
+  NV_CHECK_ARG(ws_bytes >= nv_gradcam_workspace_bytes(B, n), "nv_gradcam_reduce: workspace too small");
+  return gradcam_launch("nv_gradcam_reduce", act, grad, n, d, 1, B * (n - 1), gc_blocks((long)B * (n - 1), GC_MAX_BLOCKS), cam, minmax, workspace, stream);
+}
 
 extern "C" long nv_gradcam_per_volume_workspace_bytes(int B, int n) {
   if (B <= 0 || n <= 1) return -1;
-  return gcv_ticket_bytes(B) + 8L * B * gcv_blocks(n);
+  return gc_ticket_bytes(B) + 8L * B * gc_blocks(n - 1, GCV_MAX_BLOCKS);
 }
 
 extern "C" int nv_gradcam_reduce_per_volume(const void* act, const float* grad, int B, int n, int d, float* cam, float* minmax, void* workspace,
@@ -270,16 +298,7 @@ extern "C" int nv_gradcam_reduce_per_volume(const void* act, const float* grad, 
                "nv_gradcam_reduce_per_volume: bad arguments (d %% 8 == 0, n > 1, B <= 65535)");
   NV_CHECK_ARG(nv_aligned16(act) && nv_aligned16(grad) && nv_aligned16(workspace), "nv_gradcam_reduce_per_volume: 16-byte alignment");
   NV_CHECK_ARG(ws_bytes >= nv_gradcam_per_volume_workspace_bytes(B, n), "nv_gradcam_reduce_per_volume: workspace too small");
-  unsigned* tickets = (unsigned*)workspace;
-  float* part = (float*)((char*)workspace + gcv_ticket_bytes(B));
-  if (hipMemsetAsync(tickets, 0, gcv_ticket_bytes(B), (hipStream_t)stream) != hipSuccess) {
-    nv_set_error("nv_gradcam_reduce_per_volume: memset failed");
-    return NV_ERR_HIP;
-  }
-  NV_DISPATCH_OPERAND(T, hipLaunchKernelGGL(gradcam_per_volume_kernel<T>, dim3(gcv_blocks(n), B), dim3(GC_THREADS), 0, (hipStream_t)stream, (const r16*)act,
-                                            grad, n, d, cam, part, tickets, minmax));
-  NV_CHECK_LAUNCH("nv_gradcam_reduce_per_volume");
-  return NV_OK;
+  return gradcam_launch("nv_gradcam_reduce_per_volume", act, grad, n, d, B, n - 1, gc_blocks(n - 1, GCV_MAX_BLOCKS), cam, minmax, workspace, stream);
 }
 
 extern "C" long nv_token_map_to_volume_workspace_bytes(int B, const int* grid3) {
@@ -299,7 +318,7 @@ extern "C" int nv_token_map_to_volume(const float* maps, int B, const int* grid3
   const long lds = ((long)G1 * G2 + 2L * S1 + 2L * S2) * 4;
   NV_CHECK_ARG(lds <= 65536 && (long)S1 * S2 < (1L << 31),
                "nv_token_map_to_volume: output extents %d x %d x %d beyond the kernel's tables (G1 G2 + 2 S1 + 2 S2 <= 16384)", S0, S1, S2);
-  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned16(workspace) && (((uintptr_t)maps) & 3u) == 0, "nv_token_map_to_volume: out / workspace 16-byte aligned");
+  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned16(workspace) && nv_aligned(maps, 4), "nv_token_map_to_volume: out / workspace 16-byte aligned");
   NV_CHECK_ARG(ws_bytes >= nv_token_map_to_volume_workspace_bytes(B, grid3), "nv_token_map_to_volume: workspace too small");
   // position of the quantile among the N order statistics, as torch.quantile: q (N - 1) in double
   const double q = 1.0 - keep_percent / 100.0, pos = q * (double)(N - 1);

@@ -53,7 +53,9 @@ unsigned nv_sync_event_flags();                            // hipEventCreateWith
     }                                                                                             \
   } while (0)
 
-static inline bool nv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// p is a multiple of `bytes` (a power of two); a null pointer - an optional buffer that is absent - is aligned to anything
+static inline bool nv_aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+static inline bool nv_aligned16(const void* p) { return nv_aligned(p, 16); }
 
 // ------------------------------------------------------------------------------------------------
 // LDS images.  All byte offsets are relative to a 16-byte aligned tile base.
@@ -161,9 +163,25 @@ __device__ __forceinline__ unsigned pack_fp8x4(f32x4 v) {
   return (unsigned)w;
 }
 
+// six-level butterflies over the 64 lanes of a wave: every lane returns the result
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
   return v;
 }
 

@@ -12,10 +12,10 @@
 //
 // The first, third and fourth stream dense [rows, V] buffers whose rows start at any 4-byte alignment (27^3 floats are no multiple of 16
 // bytes): a workgroup owns PA_SPAN consecutive elements of one row, the 16-byte groups follow the alignment of the buffer it WRITES
-// (upsample_trilinear_kernel's head / groups / tail) and every other buffer is read as 16-byte vectors when its row has that alignment
+// (split_span) and every other buffer is read as 16-byte vectors when its row has that alignment
 // too, element by element otherwise.  Every output element is owned by one thread; there are no atomics.  The arithmetic is written
 // as separately rounded fp32 operations: contraction is off for the whole file, so no product and sum below becomes an FMA.
-#include "common.h"
+#include "attr_common.h"
 
 #pragma clang fp contract(off)
 
@@ -24,21 +24,6 @@ constexpr int PA_THREADS = 256;
 constexpr int PA_SPAN = 4096;            // elements of one row a workgroup owns: four 16-byte groups per thread
 constexpr int PP_GROUP = 8;              // jobs one workgroup of path_points_kernel serves from one read of its span of x
 constexpr int AC_MAX_JOBS = 1024;        // jobs of one nv_path_accumulate call: 12 KB of LDS tables
-
-struct Span { int head, groups, tail; };
-
-// `first`: flat element offset of the span's first element from the 16-byte aligned base of the buffer that is written
-__device__ __forceinline__ Span split_span(long first, int len) {
-  int head = (int)((4 - (first & 3)) & 3);
-  if (head > len) head = len;
-  const int groups = (len - head) >> 2;
-  return Span{head, groups, head + 4 * groups};
-}
-__device__ __forceinline__ bool is_aligned16(const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-__device__ __forceinline__ f32x4 load4(const float* p, bool vec) {
-  if (vec) return *reinterpret_cast<const f32x4*>(p);
-  return f32x4{p[0], p[1], p[2], p[3]};
-}
 
 // ------------------------------------------------------------------------------------------------ path points
 // Grid (ceil(V / PA_SPAN), ceil(J / PP_GROUP)).  A workgroup owns one span of PP_GROUP consecutive jobs.  The jobs are taken in runs of
@@ -63,6 +48,7 @@ __global__ __launch_bounds__(PA_THREADS) void path_points_kernel(const float* __
   const int len = (int)min((long)PA_SPAN, V - e0);
   const bool same_alignment = (V & 3) == 0;
   int r0 = 0;
+  // (mask_patches_kernel of perturb.hip walks the same runs over its three-column jobs, which it validates as it goes)
   while (r0 < n_jobs) {                                    // (every condition below is uniform over the workgroup)
     const int b = s_b[r0];
     int r1 = r0 + 1;
@@ -102,24 +88,8 @@ __global__ __launch_bounds__(PA_THREADS) void path_points_kernel(const float* __
 constexpr int CS_THREADS = 256;
 constexpr int CS_WAVES = CS_THREADS / 64;
 
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// One wave per job.  kind 1: the one-hot of the class.  kind 0: p_c (delta_ci - p_i) with p = exp(l - max) / sum exp(l - max), the softmax
-// of class_scores_kernel (perturb.hip): fp32, the library expf, a lane-strided partial per lane and a six-level butterfly.
+// One wave per job.  kind 1: the one-hot of the class.  kind 0: p_c (delta_ci - p_i) with p = exp(l - max) / sum exp(l - max) in fp32
+// (wave_softmax_stats: the statistics nv_class_scores divides by).
 // A job whose source volume is outside [0, B) writes nothing; a class outside [0, C) gives a row of NaN.
 __global__ __launch_bounds__(CS_THREADS) void class_score_grads_kernel(const float* __restrict__ logits, int J, int C, const int* __restrict__ jobs,
                                                                        const long* __restrict__ cls, int B, int kind, float* __restrict__ dlogits) {
@@ -138,12 +108,8 @@ __global__ __launch_bounds__(CS_THREADS) void class_score_grads_kernel(const flo
     for (int i = lane; i < C; i += 64) drow[i] = (i == c) ? 1.f : 0.f;
     return;
   }
-  float mx = -INFINITY;
-  for (int i = lane; i < C; i += 64) mx = fmaxf(mx, row[i]);
-  mx = wave_max_f(mx);
-  float sum = 0.f;
-  for (int i = lane; i < C; i += 64) sum += expf(row[i] - mx);
-  sum = wave_sum_f(sum);
+  float mx, sum;
+  wave_softmax_stats(row, C, lane, mx, sum);
   const float pc = expf(row[c] - mx) / sum;
   for (int i = lane; i < C; i += 64) {
     const float pi = expf(row[i] - mx) / sum;
@@ -255,15 +221,13 @@ __global__ __launch_bounds__(CS_THREADS) void attr_token_sums_kernel(const float
     sum += v;
     mag += fabs(v);
   }
-  sum = wave_sum_d(sum);
-  mag = wave_sum_d(mag);
+  sum = wave_sum(sum);
+  mag = wave_sum(mag);
   if (lane == 0) {
     sums[2 * tok] = (float)sum;
     sums[2 * tok + 1] = (float)mag;
   }
 }
-
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 }  // namespace
 
 extern "C" int nv_path_points(const float* x, int B, long V, const int* jobs, int J, const float* alphas, int K, float value, const float* base,
@@ -272,7 +236,7 @@ extern "C" int nv_path_points(const float* x, int B, long V, const int* jobs, in
   const long spans = (V + PA_SPAN - 1) / PA_SPAN, job_groups = ((long)J + PP_GROUP - 1) / PP_GROUP;
   NV_CHECK_ARG(spans < (1L << 31) && job_groups <= 65535, "nv_path_points: %ld elements per volume or %d jobs beyond one launch (at most %d jobs)", V, J,
                65535 * PP_GROUP);
-  NV_CHECK_ARG(nv_aligned16(out) && aligned4(x) && aligned4(base) && aligned4(jobs) && aligned4(alphas),
+  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(x, 4) && nv_aligned(base, 4) && nv_aligned(jobs, 4) && nv_aligned(alphas, 4),
                "nv_path_points: out 16-byte aligned, every other buffer 4-byte aligned");
   NV_CHECK_ARG(base_stride == 0 || base_stride >= V, "nv_path_points: baseline stride %ld is neither 0 nor at least one volume", base_stride);
   hipLaunchKernelGGL(path_points_kernel, dim3((unsigned)spans, (unsigned)job_groups), dim3(PA_THREADS), 0, (hipStream_t)stream, x, B, V, jobs, J, alphas, K,
@@ -284,7 +248,7 @@ extern "C" int nv_path_points(const float* x, int B, long V, const int* jobs, in
 extern "C" int nv_class_score_grads(const float* logits, int J, int C, const int* jobs, const long* cls, int B, int kind, float* dlogits, void* stream) {
   NV_CHECK_ARG(logits && jobs && cls && dlogits && J > 0 && C > 0 && B > 0, "nv_class_score_grads: bad arguments (null pointer, or J / C / B not positive)");
   NV_CHECK_ARG(kind == NV_SCORE_PROB || kind == NV_SCORE_LOGIT, "nv_class_score_grads: kind %d is neither NV_SCORE_PROB nor NV_SCORE_LOGIT", kind);
-  NV_CHECK_ARG(aligned4(logits) && aligned4(jobs) && (((uintptr_t)cls) & 7u) == 0 && aligned4(dlogits), "nv_class_score_grads: element-aligned buffers");
+  NV_CHECK_ARG(nv_aligned(logits, 4) && nv_aligned(jobs, 4) && nv_aligned(cls, 8) && nv_aligned(dlogits, 4), "nv_class_score_grads: element-aligned buffers");
   hipLaunchKernelGGL(class_score_grads_kernel, dim3((J + CS_WAVES - 1) / CS_WAVES), dim3(CS_THREADS), 0, (hipStream_t)stream, logits, J, C, jobs, cls, B,
                      kind, dlogits);
   NV_CHECK_LAUNCH("nv_class_score_grads");
@@ -296,7 +260,7 @@ extern "C" int nv_path_accumulate(const float* g, const int* jobs, int J, const 
   NV_CHECK_ARG(J <= AC_MAX_JOBS, "nv_path_accumulate: %d jobs, at most %d in one call", J, AC_MAX_JOBS);
   const long spans = (V + PA_SPAN - 1) / PA_SPAN;
   NV_CHECK_ARG(spans < (1L << 31) && B <= 65535, "nv_path_accumulate: %ld elements per volume or %d volumes beyond one launch (at most 65535 volumes)", V, B);
-  NV_CHECK_ARG(nv_aligned16(acc) && aligned4(g) && aligned4(jobs) && aligned4(weights),
+  NV_CHECK_ARG(nv_aligned16(acc) && nv_aligned(g, 4) && nv_aligned(jobs, 4) && nv_aligned(weights, 4),
                "nv_path_accumulate: acc 16-byte aligned, every other buffer 4-byte aligned");
   hipLaunchKernelGGL(path_accumulate_kernel, dim3((unsigned)spans, (unsigned)B), dim3(PA_THREADS), 0, (hipStream_t)stream, g, jobs, J, weights, K, acc, V);
   NV_CHECK_LAUNCH("nv_path_accumulate");
@@ -307,7 +271,7 @@ extern "C" int nv_path_finish(const float* acc, const float* x, int B, long V, f
   NV_CHECK_ARG(acc && x && attr && B > 0 && V > 0, "nv_path_finish: bad arguments (null pointer, or B / V not positive)");
   const long spans = (V + PA_SPAN - 1) / PA_SPAN;
   NV_CHECK_ARG(spans < (1L << 31) && B <= 65535, "nv_path_finish: %ld elements per volume or %d volumes beyond one launch (at most 65535 volumes)", V, B);
-  NV_CHECK_ARG(nv_aligned16(attr) && aligned4(acc) && aligned4(x) && aligned4(base), "nv_path_finish: attr 16-byte aligned, every other buffer 4-byte aligned");
+  NV_CHECK_ARG(nv_aligned16(attr) && nv_aligned(acc, 4) && nv_aligned(x, 4) && nv_aligned(base, 4), "nv_path_finish: attr 16-byte aligned, every other buffer 4-byte aligned");
   NV_CHECK_ARG(base_stride == 0 || base_stride >= V, "nv_path_finish: baseline stride %ld is neither 0 nor at least one volume", base_stride);
   hipLaunchKernelGGL(path_finish_kernel, dim3((unsigned)spans, (unsigned)B), dim3(PA_THREADS), 0, (hipStream_t)stream, acc, x, V, value, base, base_stride, attr);
   NV_CHECK_LAUNCH("nv_path_finish");
@@ -323,7 +287,7 @@ extern "C" int nv_attr_token_sums(const float* attr, int B, const int* size3, co
   const long N = (long)(S0 / p0) * (S1 / p1) * (S2 / p2), P = (long)p0 * p1 * p2, tokens = (long)B * N;
   NV_CHECK_ARG(N < (1L << 31) && P < (1L << 31) && (tokens + CS_WAVES - 1) / CS_WAVES < (1L << 31),
                "nv_attr_token_sums: %ld patches of %ld voxels in %d volumes beyond one launch", N, P, B);
-  NV_CHECK_ARG(aligned4(attr) && aligned4(sums), "nv_attr_token_sums: element-aligned buffers");
+  NV_CHECK_ARG(nv_aligned(attr, 4) && nv_aligned(sums, 4), "nv_attr_token_sums: element-aligned buffers");
   hipLaunchKernelGGL(attr_token_sums_kernel, dim3((unsigned)((tokens + CS_WAVES - 1) / CS_WAVES)), dim3(CS_THREADS), 0, (hipStream_t)stream, attr, S0, S1, S2, p0,
                      p1, p2, tokens, sums);
   NV_CHECK_LAUNCH("nv_attr_token_sums");

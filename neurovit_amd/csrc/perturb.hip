@@ -10,30 +10,26 @@
 //   nv_occlusion_gather  maps[b, t] = ref[b] - scores[b, labels[b, t]]
 //
 // The only real bytes are the J * S0 * S1 * S2 * 4 of nv_mask_patches' output; everything else works on <= 4096 cells per volume.
-#include "common.h"
+#include "attr_common.h"
 
 namespace {
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 // ------------------------------------------------------------------------------------------------ ranks
 constexpr int RK_THREADS = 256;
 constexpr int RK_MAX_CELLS = 4096;       // 16 KB of keys in LDS (16^3 = ViT3D-large)
 
-// Order-preserving map of finite fp32 values onto unsigned integers; -0.0 and +0.0 share one key.  No finite value has key 0.
-__device__ __forceinline__ unsigned rank_key(float v) {
-  const unsigned u = (v == 0.f) ? 0u : __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// One workgroup per volume: a counting pass over the keys in LDS.  Every lane of a wave reads the same four keys (one broadcast
-// 16-byte LDS read) and compares them with its own token's key; the slots behind N hold key 0, which no comparison counts.
+// One workgroup per volume: a counting pass over the keys (float_key; -0.0 and +0.0 share one key) in LDS.  Every lane of a wave reads
+// the same four keys (one broadcast 16-byte LDS read) and compares them with its own token's key; the slots behind N hold key 0, which
+// no finite value has and no comparison counts.
 __global__ __launch_bounds__(RK_THREADS) void token_ranks_kernel(const float* __restrict__ maps, int N, int* __restrict__ ranks) {
   __shared__ u32x4 keys4[RK_MAX_CELLS / 4];
   unsigned* keys = reinterpret_cast<unsigned*>(keys4);
   const int tid = threadIdx.x;
   const long off = (long)blockIdx.x * N;
   const int N4 = (N + 3) >> 2;
-  for (int i = tid; i < 4 * N4; i += RK_THREADS) keys[i] = i < N ? rank_key(maps[off + i]) : 0u;
+  for (int i = tid; i < 4 * N4; i += RK_THREADS) {
+    const float v = i < N ? maps[off + i] : 0.f;
+    keys[i] = i < N ? float_key(v == 0.f ? 0.f : v) : 0u;      // -0.0 takes the key of +0.0
+  }
   __syncthreads();
   for (int t = tid; t < N; t += RK_THREADS) {
     const unsigned mine = keys[t];
@@ -59,7 +55,7 @@ int g_mask_group = 4;
 // of b are loaded into LDS once, and every 16-byte group of the plane reads x[b] (and the baseline), forms its four token indices and
 // looks their labels up ONCE, then selects and stores for each job of the run.  The token of voxel
 // (i0, i1, i2) is (i2 / p2) G0 G1 + (i0 / p0) G1 + i1 / p1: the row and column terms come from two LDS tables, so the stream divides once
-// per group (flat plane offset -> row).  Groups of four follow the alignment of `out` (upsample_trilinear_kernel's head / groups / tail);
+// per group (flat plane offset -> row).  Groups of four follow the alignment of `out` (split_span);
 // x and the baseline are read as 16-byte vectors when their plane has the same alignment as the output's (uniform per run), voxel by
 // voxel otherwise.  Everything moves as 32-bit patterns: no arithmetic touches a voxel.
 __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned* __restrict__ x, int B, int S0, int S1, int S2, int p0, int p1, int p2,
@@ -85,6 +81,7 @@ __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned
   const bool same_alignment = (vol & 3) == 0;              // else consecutive jobs' planes differ in alignment: runs of one job
   const int n_jobs = j_end - j_first;
   int r0 = 0, loaded_b = -1;
+  // (path_points_kernel of path_attr.hip walks the same runs over its pre-validated two-column jobs)
   while (r0 < n_jobs) {                                    // (every condition below is uniform over the workgroup)
     const int b = s_job[3 * r0];
     int r1 = r0 + 1;
@@ -100,29 +97,22 @@ __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned
     const unsigned* bp = base ? base + (long)b * base_stride + (long)i0 * P : nullptr;
     const long o_first = (long)(j_first + r0) * vol + (long)i0 * P;       // flat offset of the plane in `out`, first job of the run
     unsigned* o = out + o_first;                                          // (job r of the run: (r - r0) vol further, the same alignment)
-    int head = (int)((4 - (o_first & 3)) & 3);                            // `out` is 16-byte aligned
-    if (head > P) head = P;
-    const int groups = (P - head) >> 2, tail = head + 4 * groups;
+    const Span s = split_span(o_first, P);                                // `out` is 16-byte aligned
     auto single = [&](int e) {                                            // one voxel, every job of the run
       const int y = e / S2, z = e - y * S2;
       const int l = lab[plane_tok + row_tok[y] + col_tok[z]];
       const unsigned xv = xp[e], bv = bp ? bp[e] : value;
       for (int r = r0; r < r1; ++r) o[(long)(r - r0) * vol + e] = (l >= s_job[3 * r + 1] && l < s_job[3 * r + 2]) ? bv : xv;
     };
-    for (int e = tid; e < head; e += MK_THREADS) single(e);
-    for (int e = tail + tid; e < P; e += MK_THREADS) single(e);
-    const bool x_vec = (reinterpret_cast<uintptr_t>(xp + head) & 15u) == 0;
-    const bool b_vec = bp && (reinterpret_cast<uintptr_t>(bp + head) & 15u) == 0;
-    for (int g = tid; g < groups; g += MK_THREADS) {
-      const int e = head + 4 * g;
+    for (int e = tid; e < s.head; e += MK_THREADS) single(e);
+    for (int e = s.tail + tid; e < P; e += MK_THREADS) single(e);
+    const bool x_vec = is_aligned16(xp + s.head), b_vec = bp && is_aligned16(bp + s.head);
+    for (int g = tid; g < s.groups; g += MK_THREADS) {
+      const int e = s.head + 4 * g;
       int y = e / S2, z = e - y * S2;
       int rt = plane_tok + row_tok[y];
-      u32x4 xv, bv;
-      if (x_vec) xv = *reinterpret_cast<const u32x4*>(xp + e);
-      else { xv[0] = xp[e]; xv[1] = xp[e + 1]; xv[2] = xp[e + 2]; xv[3] = xp[e + 3]; }
-      if (!bp) bv = u32x4{value, value, value, value};
-      else if (b_vec) bv = *reinterpret_cast<const u32x4*>(bp + e);
-      else { bv[0] = bp[e]; bv[1] = bp[e + 1]; bv[2] = bp[e + 2]; bv[3] = bp[e + 3]; }
+      const u32x4 xv = load4(xp + e, x_vec);
+      const u32x4 bv = bp ? load4(bp + e, b_vec) : u32x4{value, value, value, value};
       int l[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -145,19 +135,7 @@ __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned
 constexpr int CS_THREADS = 256;
 constexpr int CS_WAVES = CS_THREADS / 64;
 
-__device__ __forceinline__ float wave_max_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// One wave per job.  kind 1: the class logit as it is.  kind 0: exp(l_c - max) / sum_i exp(l_i - max) in fp32 (the library expf; the sum
-// is a lane-strided partial per lane and a six-level butterfly, so a row of C <= 64 classes adds each term once in a balanced tree).
+// One wave per job.  kind 1: the class logit as it is.  kind 0: exp(l_c - max) / sum_i exp(l_i - max) in fp32 (wave_softmax_stats).
 // A job whose source volume is outside [0, B) writes nothing; a class outside [0, C) gives NaN.
 __global__ __launch_bounds__(CS_THREADS) void class_scores_kernel(const float* __restrict__ logits, int J, int C, const int* __restrict__ jobs,
                                                                   const long* __restrict__ cls, int B, int kind, float* __restrict__ scores) {
@@ -175,12 +153,8 @@ __global__ __launch_bounds__(CS_THREADS) void class_scores_kernel(const float* _
     if (lane == 0) scores[j] = row[c];
     return;
   }
-  float mx = -INFINITY;
-  for (int i = lane; i < C; i += 64) mx = fmaxf(mx, row[i]);
-  mx = wave_max_f(mx);
-  float sum = 0.f;
-  for (int i = lane; i < C; i += 64) sum += expf(row[i] - mx);
-  sum = wave_sum_f(sum);
+  float mx, sum;
+  wave_softmax_stats(row, C, lane, mx, sum);
   if (lane == 0) scores[j] = expf(row[c] - mx) / sum;
 }
 
@@ -207,7 +181,7 @@ __global__ void occlusion_gather_kernel(const float* __restrict__ ref, const flo
 extern "C" int nv_token_ranks(const float* maps, int B, int N, int* ranks, void* stream) {
   NV_CHECK_ARG(maps && ranks && B > 0 && N > 0, "nv_token_ranks: bad arguments (null pointer, or B / N not positive)");
   NV_CHECK_ARG(N <= RK_MAX_CELLS, "nv_token_ranks: %d tokens, the kernel takes at most %d (16^3)", N, RK_MAX_CELLS);
-  NV_CHECK_ARG((((uintptr_t)maps) & 3u) == 0 && (((uintptr_t)ranks) & 3u) == 0, "nv_token_ranks: maps / ranks 4-byte aligned");
+  NV_CHECK_ARG(nv_aligned(maps, 4) && nv_aligned(ranks, 4), "nv_token_ranks: maps / ranks 4-byte aligned");
   hipLaunchKernelGGL(token_ranks_kernel, dim3(B), dim3(RK_THREADS), 0, (hipStream_t)stream, maps, N, ranks);
   NV_CHECK_LAUNCH("nv_token_ranks");
   return NV_OK;
@@ -237,8 +211,7 @@ extern "C" int nv_mask_patches(const float* x, int B, const int* size3, const in
   const int group = g_mask_group;
   const long job_groups = ((long)J + group - 1) / group;
   NV_CHECK_ARG(job_groups <= 65535, "nv_mask_patches: %d jobs, at most %d in one call", J, 65535 * group);
-  NV_CHECK_ARG(nv_aligned16(out) && (((uintptr_t)x) & 3u) == 0 && (((uintptr_t)base) & 3u) == 0 && (((uintptr_t)labels) & 3u) == 0 &&
-                   (((uintptr_t)jobs) & 3u) == 0,
+  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(x, 4) && nv_aligned(base, 4) && nv_aligned(labels, 4) && nv_aligned(jobs, 4),
                "nv_mask_patches: out 16-byte aligned, every other buffer 4-byte aligned");
   NV_CHECK_ARG(base_stride == 0 || base_stride >= (long)S0 * S1 * S2, "nv_mask_patches: baseline stride %ld is neither 0 nor at least one volume", base_stride);
   union { float f; unsigned u; } vbits;
@@ -252,7 +225,7 @@ extern "C" int nv_mask_patches(const float* x, int B, const int* size3, const in
 extern "C" int nv_class_scores(const float* logits, int J, int C, const int* jobs, const long* cls, int B, int kind, float* scores, void* stream) {
   NV_CHECK_ARG(logits && jobs && cls && scores && J > 0 && C > 0 && B > 0, "nv_class_scores: bad arguments (null pointer, or J / C / B not positive)");
   NV_CHECK_ARG(kind == NV_SCORE_PROB || kind == NV_SCORE_LOGIT, "nv_class_scores: kind %d is neither NV_SCORE_PROB nor NV_SCORE_LOGIT", kind);
-  NV_CHECK_ARG((((uintptr_t)logits) & 3u) == 0 && (((uintptr_t)jobs) & 3u) == 0 && (((uintptr_t)cls) & 7u) == 0 && (((uintptr_t)scores) & 3u) == 0,
+  NV_CHECK_ARG(nv_aligned(logits, 4) && nv_aligned(jobs, 4) && nv_aligned(cls, 8) && nv_aligned(scores, 4),
                "nv_class_scores: element-aligned buffers");
   hipLaunchKernelGGL(class_scores_kernel, dim3((J + CS_WAVES - 1) / CS_WAVES), dim3(CS_THREADS), 0, (hipStream_t)stream, logits, J, C, jobs, cls, B, kind, scores);
   NV_CHECK_LAUNCH("nv_class_scores");
@@ -261,7 +234,7 @@ extern "C" int nv_class_scores(const float* logits, int J, int C, const int* job
 
 extern "C" int nv_curve_auc(const float* scores, int B, int K, long ld, float* auc, void* stream) {
   NV_CHECK_ARG(scores && auc && B > 0 && K >= 2 && ld >= K, "nv_curve_auc: bad arguments (null pointer, B < 1, K < 2 or ld < K)");
-  NV_CHECK_ARG((((uintptr_t)scores) & 3u) == 0 && (((uintptr_t)auc) & 3u) == 0, "nv_curve_auc: element-aligned buffers");
+  NV_CHECK_ARG(nv_aligned(scores, 4) && nv_aligned(auc, 4), "nv_curve_auc: element-aligned buffers");
   hipLaunchKernelGGL(curve_auc_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, scores, B, K, ld, auc);
   NV_CHECK_LAUNCH("nv_curve_auc");
   return NV_OK;
@@ -269,7 +242,7 @@ extern "C" int nv_curve_auc(const float* scores, int B, int K, long ld, float* a
 
 extern "C" int nv_occlusion_gather(const float* ref, const float* scores, const int* labels, int B, int N, int NB, float* maps, void* stream) {
   NV_CHECK_ARG(ref && scores && labels && maps && B > 0 && N > 0 && NB > 0, "nv_occlusion_gather: bad arguments (null pointer, or B / N / NB not positive)");
-  NV_CHECK_ARG((((uintptr_t)ref) & 3u) == 0 && (((uintptr_t)scores) & 3u) == 0 && (((uintptr_t)labels) & 3u) == 0 && (((uintptr_t)maps) & 3u) == 0,
+  NV_CHECK_ARG(nv_aligned(ref, 4) && nv_aligned(scores, 4) && nv_aligned(labels, 4) && nv_aligned(maps, 4),
                "nv_occlusion_gather: element-aligned buffers");
   const long total = (long)B * N;
   NV_CHECK_ARG((total + 255) / 256 < (1L << 31), "nv_occlusion_gather: B N too large");

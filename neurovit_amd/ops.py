@@ -525,6 +525,12 @@ def gradcam_reduce_per_volume(act: torch.Tensor, grad: torch.Tensor):
     return cam, mm
 
 
+def _int3_ptr(t):
+    """three C ints for a `const int*` argument: (the array, which the caller holds for the duration of the call, a void pointer to it)"""
+    a = (ctypes.c_int * 3)(*t)
+    return a, ctypes.cast(a, ctypes.c_void_p)
+
+
 def _triple(v, what):
     t = (int(v),) * 3 if isinstance(v, int) else tuple(int(e) for e in v)
     if len(t) != 3:
@@ -543,8 +549,7 @@ def token_maps_to_volumes(maps: torch.Tensor, grid, size, normalize: bool = True
     N = grid[0] * grid[1] * grid[2]
     assert maps.dim() == 2 and maps.shape[1] == N and maps.dtype == torch.float32 and maps.is_contiguous()
     B = maps.shape[0]
-    g3, s3 = (ctypes.c_int * 3)(*grid), (ctypes.c_int * 3)(*size)
-    g3p, s3p = ctypes.cast(g3, ctypes.c_void_p), ctypes.cast(s3, ctypes.c_void_p)
+    (g3, g3p), (s3, s3p) = _int3_ptr(grid), _int3_ptr(size)
     nb = lib.nv_token_map_to_volume_workspace_bytes(B, g3p)
     if nb < 0:
         raise ValueError(f"neurovit_amd: token_maps_to_volumes needs a non-empty batch and a positive grid, got B = {B}, grid = {grid}")
@@ -589,20 +594,12 @@ def mask_patches(x: torch.Tensor, labels: torch.Tensor, jobs: torch.Tensor, patc
     assert labels.shape == (B, N) and labels.dtype == torch.int32 and labels.is_contiguous()
     assert jobs.dim() == 2 and jobs.shape[1] == 3 and jobs.dtype == torch.int32 and jobs.is_contiguous()
     J = jobs.shape[0]
-    value, base, stride = 0.0, None, 0
-    if torch.is_tensor(baseline):
-        if tuple(baseline.shape) not in ((B,) + size, (1,) + size):
-            raise ValueError(f"neurovit_amd: mask_patches: baseline of shape {tuple(baseline.shape)}, expected {(B,) + size} or {(1,) + size}")
-        assert baseline.dtype == torch.float32 and baseline.is_contiguous()
-        base, stride = baseline, (size[0] * size[1] * size[2] if baseline.shape[0] == B and B > 1 else 0)
-    else:
-        value = float(baseline)
+    value, base, stride = _path_baseline("mask_patches", baseline, x.shape)
     if out is None:
         out = torch.empty((J,) + size, dtype=torch.float32, device=x.device)
     assert out.shape == (J,) + size and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
-    s3, p3 = (ctypes.c_int * 3)(*size), (ctypes.c_int * 3)(*patch)
-    check(lib.nv_mask_patches(_p(x), B, ctypes.cast(s3, ctypes.c_void_p), ctypes.cast(p3, ctypes.c_void_p), _p(labels), _p(jobs), J, value, _p(base),
-                              stride, _p(out), _stream()), "nv_mask_patches")
+    (s3, s3p), (p3, p3p) = _int3_ptr(size), _int3_ptr(patch)
+    check(lib.nv_mask_patches(_p(x), B, s3p, p3p, _p(labels), _p(jobs), J, value, _p(base), stride, _p(out), _stream()), "nv_mask_patches")
     return out
 
 
@@ -649,14 +646,25 @@ def _rows(t: torch.Tensor, rows: Optional[int] = None, V: Optional[int] = None) 
             and (rows is None or t.shape[0] == rows) and (V is None or t.shape[1] == V))
 
 
-def _path_baseline(what: str, baseline, B: int, V: int):
-    """(value, base tensor or None, stride in elements) of a baseline that is a float, or a dense [B, V] / [1, V] tensor"""
+def check_baseline(what: str, baseline, shape):
+    """A baseline is a float, or a tensor of `shape` (one per sample) or of (1,) + shape[1:] (shared): returns the float or the tensor,
+    ValueError for a tensor of any other shape."""
     if not torch.is_tensor(baseline):
-        return float(baseline), None, 0
-    if tuple(baseline.shape) not in ((B, V), (1, V)):
-        raise ValueError(f"neurovit_amd: {what}: baseline of shape {tuple(baseline.shape)}, expected {(B, V)} or {(1, V)}")
-    assert _rows(baseline)
-    return 0.0, baseline, (V if baseline.shape[0] == B and B > 1 else 0)
+        return float(baseline)
+    full, shared = tuple(shape), (1,) + tuple(shape[1:])
+    if tuple(baseline.shape) not in (full, shared):
+        raise ValueError(f"{what}: baseline of shape {tuple(baseline.shape)}, expected {full} or {shared}")
+    return baseline
+
+
+def _path_baseline(what: str, baseline, shape):
+    """(value, base tensor or None, stride in elements) for the kernels that take a baseline (check_baseline) of dense fp32 samples"""
+    baseline = check_baseline(f"neurovit_amd: {what}", baseline, shape)
+    if not torch.is_tensor(baseline):
+        return baseline, None, 0
+    assert baseline.dtype == torch.float32 and baseline.is_contiguous()
+    B = shape[0]
+    return 0.0, baseline, (baseline[0].numel() if baseline.shape[0] == B and B > 1 else 0)
 
 
 def path_points(x: torch.Tensor, jobs: torch.Tensor, alphas: torch.Tensor, baseline=0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -668,7 +676,7 @@ def path_points(x: torch.Tensor, jobs: torch.Tensor, alphas: torch.Tensor, basel
     assert _rows(x) and jobs.dim() == 2 and jobs.shape[1] == 2 and jobs.dtype == torch.int32 and jobs.is_contiguous()
     assert alphas.dim() == 1 and alphas.dtype == torch.float32 and alphas.is_contiguous()
     (B, V), J = x.shape, jobs.shape[0]
-    value, base, stride = _path_baseline("path_points", baseline, B, V)
+    value, base, stride = _path_baseline("path_points", baseline, x.shape)
     if out is None:
         out = torch.empty((J, V), dtype=torch.float32, device=x.device)
     assert _rows(out, J, V) and out.device == x.device
@@ -712,7 +720,7 @@ def path_finish(acc: torch.Tensor, x: torch.Tensor, baseline=0.0, out: Optional[
     _need_cuda(acc, x, out, baseline if torch.is_tensor(baseline) else None)
     assert _rows(x) and _rows(acc, *x.shape) and acc.device == x.device
     B, V = x.shape
-    value, base, stride = _path_baseline("path_finish", baseline, B, V)
+    value, base, stride = _path_baseline("path_finish", baseline, x.shape)
     if out is None:
         out = torch.empty((B, V), dtype=torch.float32, device=x.device)
     assert _rows(out, B, V) and out.device == x.device
@@ -732,9 +740,8 @@ def attr_token_sums(attr: torch.Tensor, patch) -> torch.Tensor:
         raise ValueError(f"neurovit_amd: attr_token_sums: volume {size} is not a whole number of {patch} patches")
     N = (size[0] // patch[0]) * (size[1] // patch[1]) * (size[2] // patch[2])
     sums = torch.empty((B, N, 2), dtype=torch.float32, device=attr.device)
-    s3, p3 = (ctypes.c_int * 3)(*size), (ctypes.c_int * 3)(*patch)
-    check(lib.nv_attr_token_sums(_p(attr), B, ctypes.cast(s3, ctypes.c_void_p), ctypes.cast(p3, ctypes.c_void_p), _p(sums), _stream()),
-          "nv_attr_token_sums")
+    (s3, s3p), (p3, p3p) = _int3_ptr(size), _int3_ptr(patch)
+    check(lib.nv_attr_token_sums(_p(attr), B, s3p, p3p, _p(sums), _stream()), "nv_attr_token_sums")
     return sums
 
 

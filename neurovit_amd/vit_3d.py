@@ -26,6 +26,37 @@ def pair(t):
     return t if isinstance(t, tuple) else (t, t)
 
 
+def check_target(target, B: int, C: int) -> None:
+    """ValueError for a `target` that cannot name one class per volume: an int outside [0, C), or a tensor that does not hold B classes"""
+    if torch.is_tensor(target):
+        if target.numel() != B:
+            raise ValueError(f"neurovit_amd.ViT: target must hold one class per volume ({B}), got {tuple(target.shape)}")
+    elif target is not None and not 0 <= int(target) < C:
+        raise ValueError(f"neurovit_amd.ViT: target class {target} outside [0, {C})")
+
+
+def target_classes(target, logits: torch.Tensor) -> torch.Tensor:
+    """The explained class of every volume as a contiguous LongTensor [B] on logits.device: `target` None = the arg-max of its logits,
+    an int = that class for all, a tensor = one class per volume.  Nothing is validated (check_target): a class outside [0, C) reaches
+    the kernels, which answer with NaN."""
+    if target is None:
+        return logits.argmax(dim=1)
+    if torch.is_tensor(target):
+        return target.to(device=logits.device, dtype=torch.long).reshape(-1).contiguous()
+    return torch.full((logits.shape[0],), int(target), dtype=torch.long, device=logits.device)
+
+
+def cached_table(owner, name: str, key, build):
+    """build() once per key, kept in the dict `owner.<name>`: the job tables and labels of one geometry - device tensors made by integer
+    arithmetic on torch.arange.  At most 16 entries; a 17th clears the cache first."""
+    cache = owner.__dict__.setdefault(name, {})
+    if key not in cache:
+        if len(cache) >= 16:
+            cache.clear()
+        cache[key] = build()
+    return cache[key]
+
+
 def _w16(w: torch.Tensor) -> torch.Tensor:
     """16-bit MFMA operand copy (the process's current operand format, _cabi.set_operand_format) of an fp32 [out, in] weight
     (standalone modules; inside a ViT the arena's shadow serves)."""
@@ -663,23 +694,15 @@ class ViT(nn.Module):
             raise NotImplementedError("neurovit_amd.ViT: no attention gradients with attention dropout active (train mode, dropout > 0): the mask "
                                       "is not replayed into the gradient of the probabilities - call eval() for attribution")
         self.check_video(video)
-        hooked = self._attend_hooked_layers()
         B = video.shape[0]
+        check_target(target, B, C)
+        hooked = self._attend_hooked_layers()
         fwd_export, fwd_maps = self._rt.make_attn_export(B, hooked, None, "all", video.device) if hooked else (None, {})
         with torch.no_grad():
             logits = self._run_forward(video.detach().float(), True, (vol_sigma, 0, fwd_export))
             if hooked:
                 self._fire_attend_hooks(fwd_maps)
-            if target is None:
-                cls = logits.argmax(dim=1)
-            elif torch.is_tensor(target):
-                cls = target.to(device=logits.device, dtype=torch.long).reshape(-1)
-                if cls.numel() != B:
-                    raise ValueError(f"neurovit_amd.ViT: target must hold one class per volume ({B}), got {tuple(target.shape)}")
-            else:
-                if not 0 <= int(target) < C:
-                    raise ValueError(f"neurovit_amd.ViT: target class {target} outside [0, {C})")
-                cls = torch.full((B,), int(target), dtype=torch.long, device=logits.device)
+            cls = target_classes(target, logits)
             dlogits = torch.nn.functional.one_hot(cls, C).to(torch.float32)
             rec = self._rt._cur
             export, maps = self._rt.make_attn_grad_export(B, layers, form, video.device)
@@ -745,16 +768,8 @@ class ViT(nn.Module):
         if video.dtype != torch.float32 or not _batch_dense(video):
             raise ValueError(f"neurovit_amd.ViT: integrated_gradients needs an fp32 video that is non-overlapping and dense with the batch "
                              f"outermost, got {video.dtype} with shape {tuple(video.shape)} and strides {tuple(video.stride())}")
-        if torch.is_tensor(baseline):
-            if tuple(baseline.shape) not in (tuple(video.shape), (1,) + tuple(video.shape[1:])):
-                raise ValueError(f"neurovit_amd.ViT: baseline of shape {tuple(baseline.shape)}, expected {tuple(video.shape)} or "
-                                 f"{(1,) + tuple(video.shape[1:])}")
-        else:
-            baseline = float(baseline)
-        if not torch.is_tensor(target) and target is not None and not 0 <= int(target) < C:
-            raise ValueError(f"neurovit_amd.ViT: target class {target} outside [0, {C})")
-        if torch.is_tensor(target) and target.numel() != B:
-            raise ValueError(f"neurovit_amd.ViT: target must hold one class per volume ({B}), got {tuple(target.shape)}")
+        baseline = ops.check_baseline("neurovit_amd.ViT", baseline, video.shape)
+        check_target(target, B, C)
         K = alphas.shape[0]
         chunk = min(max(1, min(64, 2 ** 29 // (4 * V))) if chunk is None else int(chunk), B * K)
         device, inner = video.device, tuple(video.stride()[1:])
@@ -778,22 +793,14 @@ class ViT(nn.Module):
                 base = baseline
             x = flat(ends[:B])                                       # (a copy of the input: 16-byte aligned whatever `video` was)
             end_logits = self(ends).float().contiguous()
-            if target is None:
-                cls = end_logits[:B].argmax(dim=1)
-            elif torch.is_tensor(target):
-                cls = target.to(device=device, dtype=torch.long).reshape(-1).contiguous()
-            else:
-                cls = torch.full((B,), int(target), dtype=torch.long, device=device)
-            tables = self.__dict__.setdefault("_path_tables", {})
-            key = (str(device), B, K)
-            if key not in tables:
-                if len(tables) >= 16:
-                    tables.clear()
+            cls = target_classes(target, end_logits[:B])
+
+            def build():
                 b = torch.arange(B, device=device, dtype=torch.int64)
                 jobs = torch.stack([b.repeat_interleave(K), torch.arange(K, device=device, dtype=torch.int64).repeat(B)], 1).to(torch.int32).contiguous()
                 zero = torch.zeros(2 * B, device=device, dtype=torch.int64)
-                tables[key] = (jobs, torch.stack([b.repeat(2), zero, zero], 1).to(torch.int32).contiguous())      # rows (b, 0, 0): the end scores
-            jobs, end_jobs = tables[key]
+                return jobs, torch.stack([b.repeat(2), zero, zero], 1).to(torch.int32).contiguous()      # rows (b, 0, 0): the end scores
+            jobs, end_jobs = cached_table(self, "_path_tables", (str(device), B, K), build)
             end_scores = ops.class_scores(end_logits, end_jobs, cls, kind=score)
 
             points, grads = like_video(chunk), like_video(chunk)

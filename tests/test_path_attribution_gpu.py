@@ -77,7 +77,7 @@ def test_path_points_bit_equal(vol, kind, bad):
     assert torch.isnan(got[4].cpu()).all()               # the job out of range left its row as it was
 
 
-@pytest.mark.parametrize("C", [2, 5])
+@pytest.mark.parametrize("C", [2, 5, 64, 65, 130])              # 65 and 130: the lane-strided loops take a second and a third turn
 def test_class_score_grads(C):
     from neurovit_amd import ops
     B, J = 3, 9
@@ -95,6 +95,11 @@ def test_class_score_grads(C):
     report(f"nv_class_score_grads C = {C}: max abs error vs float64 autograd {err:.3e}")
     assert err <= 2e-6, err
     assert (R.class_score_grads_ref(logits, jobs, cls, "prob").double() - want).abs().max().item() <= 2e-6
+    # one softmax for the score and its gradient: d p_c / d l_c = p_c (1 - p_c) with the p_c of nv_class_scores, bit for bit
+    jobs3 = torch.cat([jobs[:, :1], torch.zeros(J, 2, dtype=torch.int32)], 1)
+    s = ops.class_scores(logits.cuda(), jobs3.cuda(), cls.cuda(), "prob").cpu()
+    own = got[torch.arange(J), cls[jobs[:, 0].long()]]
+    assert same_bits(own, s * (1 - s))
     bad = torch.tensor([1, C, -1])                          # volumes 1 and 2: a class outside [0, C)
     for kind in ("logit", "prob"):
         got = ops.class_score_grads(logits.cuda(), jobs.cuda(), bad.cuda(), kind=kind).cpu()

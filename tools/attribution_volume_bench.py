@@ -32,7 +32,7 @@ PRESETS = {
 }
 HBM_TBS = 6.3          # achievable HBM bandwidth of the MI355X (TB/s)
 METHODS = ("gradcam", "rollout", "relevance")
-KERNELS = {"threshold": "token_map_threshold_kernel", "upsample": "upsample_trilinear_kernel", "gradcam_per_volume": "gradcam_per_volume_kernel"}
+KERNELS = {"threshold": "token_map_threshold_kernel", "upsample": "upsample_trilinear_kernel", "gradcam_per_volume": "gradcam_reduce_kernel"}      # (a --trace run launches it per volume only)
 
 
 def config_of(preset):
