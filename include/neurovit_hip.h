@@ -510,6 +510,40 @@ int nv_path_accumulate(const float* g, const int* jobs, int J, const float* weig
 int nv_path_finish(const float* acc, const float* x, int B, long V, float value, const float* base, long base_stride, float* attr, void* stream);
 int nv_attr_token_sums(const float* attr, int B, const int* size3, const int* patch3, float* sums, void* stream);
 
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) attribution for the 4D model: the steps that see a
+ * series of T volumes per sample.  No call allocates or synchronises; every argument is checked first (NV_ERR_ARG).
+ * nv_gradcam_reduce_grouped: nv_gradcam_reduce over V volumes with the min-max normalisation taken over each `group` consecutive volumes
+ *   (V a multiple of group; a sample's T timepoints); minmax (optional) [V / group, 2].  group = 1 gives the bits of
+ *   nv_gradcam_reduce_per_volume, group = V those of nv_gradcam_reduce.  One launch.
+ * nv_series_map_to_volumes: maps [B, T, N] (N = G0 G1 G2, every volume in token order as nv_token_map_to_volume takes it) -> out fp32
+ *   [B, S0, S1, S2, T] (NV_SERIES_LAYOUT_SERIES: time innermost, the layout of the model's input) or [B, T, S0, S1, S2]
+ *   (NV_SERIES_LAYOUT_FRAMES).  Normalisation, cut and threshold by the rules of nv_token_map_to_volume, taken
+ *     NV_SERIES_SCOPE_SERIES  over the T N cells of a sample jointly: one min, one max, one cut (the quantile at position q (T N - 1)) per
+ *                             sample, so relative importance across time survives; one workgroup per sample, the keys in LDS;
+ *     NV_SERIES_SCOPE_VOLUME  over every volume on its own: the bits of nv_token_map_to_volume on the B T volumes.
+ *   The upsampling of layout SERIES writes each output plane (b, x) - S1 S2 T contiguous floats - from one workgroup, with the taps and the
+ *   operation order of nv_token_map_to_volume's: out[b, x, y, z, t] of layout SERIES has the bits of out[b, t, x, y, z] of layout FRAMES.
+ *   Limits (NV_ERR_ARG beyond): 1 <= T <= 64; N <= 4096; scope SERIES: T N <= 32768 (128 KiB of keys; one workgroup may hold 160 KiB);
+ *   layout SERIES: G1 G2 T + 2 S1 + 2 S2 <= 40960 floats of LDS (160 KiB); layout FRAMES: G1 G2 + 2 S1 + 2 S2 <= 16384 and B T <= 65535.
+ *   out and workspace 16-byte aligned.  Two launches.  On return the workspace holds [B, T, N] normalised maps, [B, T, N] thresholded maps
+ *   and the cuts ([B] for scope SERIES, [B, T] for scope VOLUME), fp32 in this order, which a caller may read.
+ * nv_series_leave_one_out: z fp32 [B, T, 2], z_base fp32 [2] -> out fp32 [B (T + 1), T, 2]: row b (T + 1) is z[b], row b (T + 1) + 1 + t is
+ *   z[b] with timepoint t replaced by z_base.  A pure select: every bit passes through.
+ * nv_temporal_grad_x_input: dx, z fp32 [B, T, 2] -> out fp32 [B, T] = dx[b, t, 0] z[b, t, 0] + dx[b, t, 1] z[b, t, 1], two products and one
+ *   sum, each a separately rounded fp32 operation (no FMA). */
+#define NV_SERIES_SCOPE_SERIES 0
+#define NV_SERIES_SCOPE_VOLUME 1
+#define NV_SERIES_LAYOUT_SERIES 0
+#define NV_SERIES_LAYOUT_FRAMES 1
+long nv_gradcam_grouped_workspace_bytes(int V, int n, int group);
+int nv_gradcam_reduce_grouped(const void* act, const float* grad, int V, int n, int d, int group, float* cam, float* minmax, void* workspace,
+                              long ws_bytes, void* stream);
+long nv_series_map_to_volumes_workspace_bytes(int B, int T, const int* grid3, int scope);
+int nv_series_map_to_volumes(const float* maps, int B, int T, const int* grid3, const int* out3, int normalize, int scope, double keep_percent,
+                             int layout, float* out, void* workspace, long ws_bytes, void* stream);
+int nv_series_leave_one_out(const float* z, const float* z_base, int B, int T, float* out, void* stream);
+int nv_temporal_grad_x_input(const float* dx, const float* z, int B, int T, float* out, void* stream);
+
 /* ---- the 4D model's temporal head (src/models/NeuroEncoder.py:60-66: temporal_transformer -> mean over time -> projection_head;
  * :207-217 TemporalTransformer = one nn.TransformerEncoderLayer(d_model 2, nhead 2, batch_first, post-norm, ReLU, dim_feedforward ff,
  * dropout p at its four sites); :219-230 ProjectionHead = nn.Linear(2, 2)) - ONE launch per direction.

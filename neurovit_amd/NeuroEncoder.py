@@ -104,23 +104,27 @@ class NeuroEncoder(nn.Module):
             raise ValueError(f"TRAINING_DIM must be 3 or 4, got {self.config['TRAINING_DIM']!r}")
         # 4D (NeuroEncoder.py:53-66): every timepoint is an independent volume for the frozen ViT3D, so the time axis is
         # folded into the batch; the B*T logit pairs then form a length-T sequence for the temporal transformer.
-        series = fmri.to(self.device)
-        n_samples, n_time = series.shape[0], series.shape[-1]
-        vit = self.volume_encoder.vit3d
-        # the fused form records no graph: only when neither the encoder's parameters nor the series (dL/d fMRI) want a gradient
-        frozen = not (torch.is_grad_enabled() and (series.requires_grad or any(p.requires_grad for p in vit.parameters())))
-        if frozen and n_time % 4 == 0 and n_time <= 64 and series.dtype == torch.float32 and series.is_contiguous():
-            # fused 4D gather (csrc/norm.hip::patch_ln_fwd_t_kernel): the B*T volumes are read in place, no regroup copy
-            per_volume = vit(series, time_points=n_time).unflatten(0, (n_samples, n_time))
-        else:
-            as_volumes = series.movedim(-1, 1).flatten(0, 1)          # [B, H, W, D, T] -> [B*T, H, W, D]  (strided copy)
-            per_volume = self.volume_encoder(as_volumes).unflatten(0, (n_samples, n_time))
+        per_volume = self._volume_logits(fmri.to(self.device))
         head = self._temporal_head
         if head.supported(per_volume):                                # NeuroEncoder.py:60-66 in one launch
             return head(per_volume)
         # geometries outside the kernel's (more than 64 timepoints, an edited encoder layer): the stock modules, on the device
         pooled = self.temporal_transformer(per_volume).mean(dim=1)
         return self.projection_head(pooled)
+
+    def _volume_logits(self, series):
+        """[B, H, W, D, T] on the device -> the frozen encoder's logits of every timepoint [B, T, 2]"""
+        n_samples, n_time = series.shape[0], series.shape[-1]
+        vit = self.volume_encoder.vit3d
+        # the fused form records no graph: only when neither the encoder's parameters nor the series (dL/d fMRI) want a gradient
+        frozen = not (torch.is_grad_enabled() and (series.requires_grad or any(p.requires_grad for p in vit.parameters())))
+        patch_dim = self.config['TRAINING_VIT_PATCH_SIZE'] ** 3
+        if frozen and n_time % 4 == 0 and n_time <= 64 and patch_dim % 4 == 0 and series.dtype == torch.float32 and series.is_contiguous():
+            # fused 4D gather (csrc/norm.hip::patch_ln_fwd_t_kernel: float4 groups, so not for the 9^3 patches of the reference's 90^3
+            # geometry): the B*T volumes are read in place, no regroup copy
+            return vit(series, time_points=n_time).unflatten(0, (n_samples, n_time))
+        as_volumes = series.movedim(-1, 1).flatten(0, 1)              # [B, H, W, D, T] -> [B*T, H, W, D]  (strided copy)
+        return self.volume_encoder(as_volumes).unflatten(0, (n_samples, n_time))
 
     def precision(self, mode: str):
         """Context manager: eval-mode no-grad forwards of the ViT3D encoder inside it run in `mode` ("bf16" / "fp16": the 16-bit
@@ -452,6 +456,175 @@ class NeuroEncoder(nn.Module):
         token_maps, token_abs = sums[:, :, 0].contiguous(), sums[:, :, 1].contiguous()
         delta = token_maps.double().sum(1) - (out["score_input"].double() - out["score_baseline"].double())
         return dict(out, attributions=attributions, token_maps=token_maps, token_abs=token_abs, delta=delta)
+
+    # ---- spatio-temporal attribution of the 4D model (csrc/series_attr.hip): which timepoints drove a class, and which regions at each
+    SERIES_METHODS = ("gradcam", "rollout", "relevance")
+
+    def _series_inputs(self, what, x, target, chunk):
+        """argument checks and refusals shared by attribution_series / temporal_importance (all before any device work) -> (S, G, T, chunk)"""
+        from .vit_3d import check_target
+        if self.config['TRAINING_DIM'] != 4:
+            raise NotImplementedError(f"{what}: 4D model only (a 3D model has no time axis: attribution_volumes serves it)")
+        S = self.config['TRAINING_VIT_INPUT_SIZE']
+        if x.dim() != 5 or tuple(x.shape[1:4]) != (S, S, S) or x.shape[0] < 1 or x.shape[4] < 1:
+            raise ValueError(f"{what}: x must be [B, {S}, {S}, {S}, T], got {tuple(x.shape)}")
+        if chunk is None:
+            chunk = 64
+        elif isinstance(chunk, bool) or int(chunk) != chunk or chunk < 1:
+            raise ValueError(f"{what}: chunk must be a positive integer, got {chunk!r}")
+        check_target(target, x.shape[0], 2)
+        T = x.shape[4]
+        vit, head = self.volume_encoder.vit3d, self._temporal_head
+        if not head.supports(T):
+            raise NotImplementedError(f"{what}: the temporal head is outside what the native kernel computes (TemporalHead.supported: at most 64 "
+                                      "timepoints, the stock encoder layer) - its input gradient comes from that kernel")
+        if self.temporal_transformer.training and float(head._layer.dropout.p) > 0:
+            raise NotImplementedError(f"{what}: the temporal head is in train mode with dropout > 0 - call eval() for attribution")
+        if vit.training and max(vit._dropout_p) > 0:
+            raise NotImplementedError(f"{what}: the encoder is in train mode with dropout > 0 - call eval() for attribution")
+        if vit._fp8 is not None:
+            raise NotImplementedError(f"{what}: not through the fp8 forwards (enable_fp8) - disable_fp8() first")
+        return S, S // self.config['TRAINING_VIT_PATCH_SIZE'], T, int(chunk)
+
+    def _head_seed(self, z, target):
+        """z [B, T, 2] -> (logits [B, 2], class_idx [B], dx [B, T, 2] = d logit_class / d z): one forward and one backward launch of the
+        temporal head; the parameter gradients of that backward go to a scratch arena, so no p.grad of the head is touched"""
+        from . import ops
+        head = self._temporal_head
+        arena, _ = head.flat_parameters()
+        with torch.no_grad():
+            logits = ops.temporal_head_fwd(z, arena, head.ff, head.eps)
+            class_idx = target_classes(target, logits)
+            dx = ops.temporal_head_bwd(z, arena, head.ff, F.one_hot(class_idx, 2).to(torch.float32), torch.empty_like(arena), accumulate=False,
+                                       want_dx=True, eps=head.eps)
+        return logits, class_idx, dx
+
+    def attribution_series(self, x, method="gradcam", target=None, threshold=None, scope="series", layout="series", chunk=None):
+        """Spatio-temporal attribution of a batch of series x [B, H, W, D, T] (4D model): which regions drove a class at every timepoint.
+        The explained class is that of the FINAL logits (temporal head and projection): target None = their arg-max, an int, or a
+        LongTensor [B].  Volume (b, t) is seeded with dx[b, t, :] = d logit_class[b] / d volume_logits[b, t, :], from one backward launch of
+        the temporal head (its parameter gradients go to a scratch arena):
+          gradcam    the encoder's data-only backward from dlogits = dx (ViT.recording_forward / data_backward: no autograd graph, no input
+                     gradient), then the Grad-CAM reduction of the taps (nv_gradcam_reduce_grouped);
+          relevance  the attention relevance terms of the same backward (form "relevance"), accumulated by nv_attn_relevance;
+          rollout    ViT.attention_rollout of every timepoint, as for the 3D model: class-agnostic - `target` only sets class_idx, and the
+                     magnitudes it shows across time carry NO class information (they compare how peaked the attention of two timepoints is,
+                     not how much either matters for the class).
+        scope "series" normalises (min-max) and cuts (the top `threshold` % of the cells, None = GRADCAM_THRESHOLD) over the T G^3 cells of a
+        sample jointly, so relative importance across time survives; "volume" treats every timepoint on its own, with the bits of the 3D
+        path (attribution_volumes).  layout "series": volumes [B, S, S, S, T], time innermost as x and a 4D NIfTI; "frames": [B, T, S, S, S].
+        chunk: volumes per encoder pass (None = 64).  With B T > chunk the volume logits of all timepoints are needed before any seed
+        exists: the recording forwards run twice with the same arithmetic, the second run keeps the activations (Grad-CAM then gathers the
+        taps of all chunks, 6 bytes per element of [B T, n, d]).
+        "Normalised" is the reference's (v - min) / (max - min + 1e-8): a map peaks at r / (r + 1e-8) of its raw range r.  The seed passes
+        the head's two-feature LayerNorms, which volume logits of order 1 saturate (~1e-11 of a gradient gets through): Grad-CAM and
+        relevance maps then peak at 1e-6 .. 1e-4, in effect raw * 1e8 - the kept cells and their ranking are right, rescale by the map's
+        maximum for display.
+        Returns a dict of device tensors: volumes fp32; token_maps [B, T, G^3] normalised; class_idx [B]; logits [B, 2]; volume_logits
+        [B, T, 2]; temporal [B, T] = sum_c dx * volume_logits (temporal_importance's grad_x_input); cuts [B] (scope "series") or [B, T].
+        No p.grad is touched, it works under no_grad and needs no requires_grad on x; nothing crosses PCIe and nothing synchronises with
+        the host.  Refused (NotImplementedError, before any device work): a 3D model, a temporal head the native kernel does not compute,
+        head or encoder in train mode with dropout > 0, the fp8 forwards, T G^3 > 32768 with scope "series" (use scope="volume")."""
+        from . import ops
+        if method not in self.SERIES_METHODS:
+            raise ValueError(f"attribution_series: method must be 'gradcam', 'rollout' or 'relevance', got {method!r}")
+        if scope not in ops.SERIES_SCOPES:
+            raise ValueError(f"attribution_series: scope must be 'series' or 'volume', got {scope!r}")
+        if layout not in ops.SERIES_LAYOUTS:
+            raise ValueError(f"attribution_series: layout must be 'series' or 'frames', got {layout!r}")
+        S, G, T, chunk = self._series_inputs("attribution_series", x, target, chunk)
+        N = G ** 3
+        if scope == "series" and T * N > ops.SERIES_MAX_CELLS:
+            raise NotImplementedError(f"attribution_series: {T} timepoints of {N} cells are more than the {ops.SERIES_MAX_CELLS} cells one sample may "
+                                      'have under scope="series" - use scope="volume"')
+        keep_percent = _grid_geometry(self.config, threshold)[2]
+        vit = self.volume_encoder.vit3d
+        if method != "rollout":
+            vit._check_data_backward()
+        series = x.detach().to(device=self.device, dtype=torch.float32)
+        B = series.shape[0]
+        V = B * T
+        # [B, H, W, D, T] -> [B T, H, W, D] (one strided copy: the fused 4D gather is forward-only) in ViT3DEncoder.forward's view
+        video = series.movedim(-1, 1).reshape(V, S, S, S).permute(0, 3, 1, 2).unsqueeze(1)
+        vit.check_video(video)
+        spans = [(first, min(chunk, V - first)) for first in range(0, V, chunk)]
+        part = lambda first, count: video[first:first + count]
+
+        with torch.no_grad():
+            if method == "rollout":
+                passes = [vit.attention_rollout(part(*span)) for span in spans]
+                z = torch.cat([logits for logits, _ in passes]).view(B, T, 2)
+                raw = torch.cat([maps for _, maps in passes]).view(B, T, N)
+                logits, class_idx, dx = self._head_seed(z, target)
+            else:
+                # every seed needs the volume logits of all T timepoints of its sample
+                z = torch.cat([vit.recording_forward(part(*span)) for span in spans]).view(B, T, 2)
+                logits, class_idx, dx = self._head_seed(z, target)
+                seeds = dx.view(V, 2)
+                layers = list(range(vit._cfg.depth)) if method == "relevance" else None
+                taps, rows = None, []
+                for first, count in spans:
+                    if len(spans) > 1:
+                        vit.recording_forward(part(first, count))          # the same arithmetic again; this run's activations are kept
+                    terms = vit.data_backward(seeds[first:first + count], layers, "relevance")
+                    if method == "relevance":
+                        rows.append(ops.attn_relevance([terms[l] for l in layers], start_mean=vit.pool == "mean"))
+                        continue
+                    act, grad = vit.last_attn_norm_output_raw(), vit.last_attn_norm_grad_raw()
+                    if len(spans) == 1:
+                        taps = (act, grad)
+                    else:
+                        if taps is None:
+                            taps = (act.new_empty((V,) + tuple(act.shape[1:])), grad.new_empty((V,) + tuple(grad.shape[1:])))
+                        taps[0][first:first + count].copy_(act)
+                        taps[1][first:first + count].copy_(grad)
+                if method == "relevance":
+                    raw = torch.cat(rows).view(B, T, N)
+                else:
+                    raw = ops.gradcam_reduce_grouped(taps[0], taps[1], T if scope == "series" else 1)[0].view(B, T, N)
+            volumes, (token_maps, _, cuts) = ops.series_maps_to_volumes(raw.contiguous(), G, S, normalize=method != "gradcam", scope=scope,
+                                                                       keep_percent=keep_percent, layout=layout, return_maps=True)
+            temporal = ops.temporal_grad_x_input(dx, z.contiguous())
+        return {"volumes": volumes, "token_maps": token_maps, "class_idx": class_idx, "logits": logits, "volume_logits": z, "temporal": temporal,
+                "cuts": cuts}
+
+    def temporal_importance(self, x, target=None, baseline=0.0, score="prob"):
+        """Which timepoints of a series x [B, H, W, D, T] drove a class of the 4D model, two ways, from ONE encoder pass over the B T
+        volumes (the model's own no-grad forward: the fused no-copy 4D gather when T % 4 == 0) plus one forward of a single constant
+        volume filled with `baseline` (a float):
+          occlusion     [B, T] = score(z) - score(z with z[b, t] replaced by z_base): z the encoder's logits per timepoint, z_base the
+                        baseline volume's; the B (T + 1) sequences (nv_series_leave_one_out) go through ONE launch of the temporal head;
+                        score "prob" (softmax probability of the class) or "logit";
+          grad_x_input  [B, T] = sum_c dx[b, t, c] z[b, t, c] with dx = d logit_class / d z (one backward launch of the head, parameter
+                        gradients to a scratch arena).
+        target: None = the arg-max of the final logits, an int, or a LongTensor [B].  Returns a dict of device tensors: occlusion,
+        grad_x_input, class_idx [B], scores [B, T + 1] (column 0: the unperturbed series, column 1 + t: timepoint t replaced), logits
+        [B, 2], volume_logits [B, T, 2].  Refusals and side effects (none) as attribution_series."""
+        from . import ops
+        if score not in ops.SCORE_KINDS:
+            raise ValueError(f"temporal_importance: score must be 'prob' or 'logit', got {score!r}")
+        if torch.is_tensor(baseline) or isinstance(baseline, bool) or not isinstance(baseline, (int, float)):
+            raise ValueError(f"temporal_importance: baseline must be a float (one constant volume), got {type(baseline).__name__}")
+        S, _, T, _ = self._series_inputs("temporal_importance", x, target, None)
+        series = x.detach().to(device=self.device, dtype=torch.float32)
+        B, device = series.shape[0], series.device
+        head = self._temporal_head
+        arena, _ = head.flat_parameters()
+
+        def build():
+            b = torch.arange(B, device=device, dtype=torch.int64).repeat_interleave(T + 1)
+            return torch.stack([b, torch.zeros_like(b), torch.zeros_like(b)], 1).to(torch.int32).contiguous()
+        jobs = cached_table(self, "_perturbation_tables", ("temporal", str(device), B, T), build)
+
+        with torch.no_grad():
+            z = self._volume_logits(series).float().contiguous()
+            z_base = self.volume_encoder(torch.full((1, S, S, S), float(baseline), dtype=torch.float32, device=device))[0].float().contiguous()
+            logits, class_idx, dx = self._head_seed(z, target)
+            out = ops.temporal_head_fwd(ops.series_leave_one_out(z, z_base), arena, head.ff, head.eps)
+            scores = ops.class_scores(out, jobs, class_idx, kind=score).view(B, T + 1)
+            occlusion = scores[:, :1] - scores[:, 1:]
+            grad_x_input = ops.temporal_grad_x_input(dx, z)
+        return {"occlusion": occlusion, "grad_x_input": grad_x_input, "class_idx": class_idx, "scores": scores, "logits": logits, "volume_logits": z}
 
     def visualize_slice(self, cam_3d, original_volume):
         """One 2-D slice of the volume and of its CAM along GRADCAM_SLICE_DIM at GRADCAM_SLICE_IDX

@@ -95,115 +95,19 @@ __global__ __launch_bounds__(GC_THREADS) void gradcam_reduce_kernel(const r16* _
 constexpr int TM_THREADS = 256;
 constexpr int TM_MAX_CELLS = 4096;       // cells of one volume's grid: 16 KB of keys in LDS (16^3 = ViT3D-large)
 
-// The k-th smallest (0-based) of keys[0, N): radix select, eight bits per pass.  Every thread of the workgroup calls it and gets the key.
-__device__ unsigned select_kth(const unsigned* keys, int N, int k, unsigned* hist, unsigned* s_sel) {
-  const int tid = threadIdx.x, lane = tid & 63;
-  unsigned prefix = 0, mask = 0;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    hist[tid] = 0;                                         // TM_THREADS == 256 bins
-    __syncthreads();
-    for (int i = tid; i < N; i += TM_THREADS) {
-      const unsigned key = keys[i];
-      if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid < 64) {                                        // one wave: lane l owns bins 4l .. 4l + 3
-      const unsigned c0 = hist[4 * lane], c1 = hist[4 * lane + 1], c2 = hist[4 * lane + 2], c3 = hist[4 * lane + 3];
-      const unsigned mine = c0 + c1 + c2 + c3;
-      unsigned incl = mine;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      const unsigned excl = incl - mine, kk = (unsigned)k;
-      if (excl <= kk && kk < incl) {                       // exactly one lane: the counts of the surviving keys sum to more than k
-        unsigned bin = 4 * lane, below = excl;
-        if (kk >= below + c0) { below += c0; ++bin;
-          if (kk >= below + c1) { below += c1; ++bin;
-            if (kk >= below + c2) { below += c2; ++bin; } } }
-        s_sel[0] = bin; s_sel[1] = kk - below;
-      }
-    }
-    __syncthreads();
-    prefix |= s_sel[0] << shift; mask |= 255u << shift;
-    k = (int)s_sel[1];
-    __syncthreads();                                       // s_sel and hist are rewritten by the next pass
-  }
-  return prefix;
-}
-
 // One workgroup per volume.  norm / sparse: [B, N] (the normalised map, and the same with the cells under the cut zeroed); cuts: [B].
-// (i_lo, i_hi, w): the position q (N - 1) of the quantile among the order statistics, split on the host in double.
-__global__ __launch_bounds__(TM_THREADS) void token_map_threshold_kernel(const float* __restrict__ maps, int N, int normalize, int i_lo, int i_hi, double w,
+// pos: the position q (N - 1) of the quantile among the order statistics (quantile_pos); the work is threshold_block's.
+__global__ __launch_bounds__(TM_THREADS) void token_map_threshold_kernel(const float* __restrict__ maps, int N, int normalize, QuantilePos pos,
                                                                          float* __restrict__ norm, float* __restrict__ sparse, float* __restrict__ cuts) {
   __shared__ unsigned keys[TM_MAX_CELLS];
-  __shared__ unsigned hist[TM_THREADS];
-  __shared__ float s_red[2 * (TM_THREADS / 64)];
-  __shared__ unsigned s_sel[2], s_cnt, s_next;
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ ThresholdScratch scratch;
   const long off = (long)blockIdx.x * N;
-  float lo = INFINITY, hi = -INFINITY;
-  if (normalize) {
-    for (int i = tid; i < N; i += TM_THREADS) { const float v = maps[off + i]; lo = fminf(lo, v); hi = fmaxf(hi, v); }
-    lo = wave_min(lo); hi = wave_max(hi);
-    if (lane == 0) { s_red[2 * wid] = lo; s_red[2 * wid + 1] = hi; }
-    __syncthreads();
-    lo = s_red[0]; hi = s_red[1];
-    for (int v = 1; v < TM_THREADS / 64; ++v) { lo = fminf(lo, s_red[2 * v]); hi = fmaxf(hi, s_red[2 * v + 1]); }
-  }
-  const float inv = 1.0f / (hi - lo + 1e-8f);
-  for (int i = tid; i < N; i += TM_THREADS) {
-    float v = maps[off + i];
-    if (normalize) v = (v - lo) * inv;
-    norm[off + i] = v;
-    keys[i] = float_key(v);
-  }
-  if (tid == 0) { s_cnt = 0; s_next = 0xffffffffu; }
-  __syncthreads();
-  const unsigned k_lo = select_kth(keys, N, i_lo, hist, s_sel);
-  unsigned k_hi = k_lo;
-  if (i_hi != i_lo) {                                      // the next order statistic: k_lo again if it repeats, else the smallest key above it
-    unsigned cnt = 0, nxt = 0xffffffffu;
-    for (int i = tid; i < N; i += TM_THREADS) {
-      const unsigned key = keys[i];
-      if (key <= k_lo) ++cnt; else nxt = min(nxt, key);
-    }
-    atomicAdd(&s_cnt, cnt); atomicMin(&s_next, nxt);
-    __syncthreads();
-    k_hi = ((int)s_cnt > i_hi) ? k_lo : s_next;
-  }
-  // torch.quantile(interpolation='linear') = lerp(s[lo], s[hi], w) in double (ATen's lerp: two forms around w = 0.5), rounded to fp32
-  float cut;
-  {
-#pragma clang fp contract(off)
-    const double a = (double)float_of_key(k_lo), e = (double)float_of_key(k_hi);
-    const double c = (w < 0.5) ? a + w * (e - a) : e - (e - a) * (1.0 - w);
-    cut = (float)c;
-  }
-  for (int i = tid; i < N; i += TM_THREADS) {
-    const float v = float_of_key(keys[i]);
-    sparse[off + i] = (v >= cut) ? v : 0.f;
-  }
-  if (tid == 0) cuts[blockIdx.x] = cut;
+  const float cut = threshold_block<TM_THREADS>(maps + off, N, normalize, pos, norm + off, sparse + off, keys, scratch);
+  if (threadIdx.x == 0) cuts[blockIdx.x] = cut;
 }
 
 // ------------------------------------------------------------------------------------------------ trilinear upsampling
 constexpr int UP_THREADS = 256;
-struct AxisTap { int i0, i1; float l0, l1; };
-
-// ATen's area_pixel_compute_source_index (align_corners = False) and linear taps of one output index; scale = (float)G / S
-__device__ __forceinline__ AxisTap axis_tap(int dst, float scale, int G) {
-#pragma clang fp contract(off)
-  AxisTap t;
-  const float src = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
-  t.i0 = min((int)src, G - 1);
-  t.i1 = min(t.i0 + 1, G - 1);
-  t.l1 = src - (float)t.i0;
-  t.l0 = 1.0f - t.l1;
-  return t;
-}
-
 // Grid (S0, B): one workgroup writes the S1 x S2 output plane (b, x).  It first collapses the x axis of the volume's grid into a
 // G1 x G2 plane in LDS and tabulates the y and z taps; every output then costs four LDS reads and three lerps.  The plane is written as
 // 16-byte stores over its flat extent (rows need not be multiples of four: split_span, the groups of four follow the alignment of `out`).
@@ -219,9 +123,9 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const fl
   const AxisTap tx = axis_tap(x, sc0, G0);
   const float* g0 = sparse + ((long)b * G0 + tx.i0) * G1 * G2;
   const float* g1 = sparse + ((long)b * G0 + tx.i1) * G1 * G2;
-  for (int i = tid; i < G1 * G2; i += UP_THREADS) plane[i] = tx.l0 * g0[i] + tx.l1 * g1[i];
-  for (int i = tid; i < S1; i += UP_THREADS) { const AxisTap t = axis_tap(i, sc1, G1); yi[i] = (t.i0 * G2) | ((t.i1 * G2) << 16); yl[i] = t.l1; }
-  for (int i = tid; i < S2; i += UP_THREADS) { const AxisTap t = axis_tap(i, sc2, G2); zi[i] = t.i0 | (t.i1 << 16); zl[i] = t.l1; }
+  for (int i = tid; i < G1 * G2; i += UP_THREADS) plane[i] = blend(tx.l0, g0[i], tx.l1, g1[i]);
+  fill_axis_table(yi, yl, S1, sc1, G1, G2, tid, UP_THREADS);
+  fill_axis_table(zi, zl, S2, sc2, G2, 1, tid, UP_THREADS);
   __syncthreads();
 
   const long plane_elems = (long)S1 * S2;
@@ -230,14 +134,8 @@ __global__ __launch_bounds__(UP_THREADS) void upsample_trilinear_kernel(const fl
   const int P = (int)plane_elems;
   const Span s = split_span(base, P);                      // `out` is 16-byte aligned
 
-  auto value = [&](int yy, float ly1, int z) -> float {     // (yy, ly1): the y taps of the row, read once per row
-    const int zz = zi[z];
-    const float lz1 = zl[z], ly0 = 1.0f - ly1, lz0 = 1.0f - lz1;
-    const int r0 = yy & 0xffff, r1 = yy >> 16, c0 = zz & 0xffff, c1 = zz >> 16;
-    const float a = lz0 * plane[r0 + c0] + lz1 * plane[r0 + c1];
-    const float c = lz0 * plane[r1 + c0] + lz1 * plane[r1 + c1];
-    return ly0 * a + ly1 * c;
-  };
+  // (yy, ly1): the y taps of the row, read once per row
+  auto value = [&](int yy, float ly1, int z) -> float { return plane_value(plane, 1, yy, ly1, zi[z], zl[z]); };
   for (int e = tid; e < s.head; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
   for (int e = s.tail + tid; e < P; e += UP_THREADS) { const int y = e / S2; o[e] = value(yi[y], yl[y], e - y * S2); }
   for (int g = tid; g < s.groups; g += UP_THREADS) {
@@ -261,9 +159,11 @@ int gc_blocks(long rows, int cap) {
 }
 long gc_ticket_bytes(int groups) { return ((4L * groups + 15) / 16) * 16; }
 
+}  // namespace
+
 // workspace: the groups' tickets (zeroed here), then 2 floats per block and group
-int gradcam_launch(const char* name, const void* act, const float* grad, int n, int d, int groups, int R, int blocks, float* cam, float* minmax,
-                   void* workspace, void* stream) {
+int nv_attr_gradcam_launch(const char* name, const void* act, const float* grad, int n, int d, int groups, int R, int blocks, float* cam, float* minmax,
+                           void* workspace, void* stream) {
   unsigned* tickets = (unsigned*)workspace;
   float* part = (float*)((char*)workspace + gc_ticket_bytes(groups));
   if (hipMemsetAsync(tickets, 0, gc_ticket_bytes(groups), (hipStream_t)stream) != hipSuccess) {
@@ -275,7 +175,6 @@ int gradcam_launch(const char* name, const void* act, const float* grad, int n, 
   NV_CHECK_LAUNCH(name);
   return NV_OK;
 }
-}  // namespace
 
 extern "C" long nv_gradcam_workspace_bytes(int B, int n) { return gc_ticket_bytes(1) + 8L * gc_blocks((long)B * (n - 1), GC_MAX_BLOCKS); }
 
@@ -284,7 +183,7 @@ extern "C" int nv_gradcam_reduce(const void* act, const float* grad, int B, int 
   NV_CHECK_ARG(act && grad && cam && workspace && B > 0 && n > 1 && d > 0 && (d % 8) == 0, "nv_gradcam_reduce: bad arguments (d %% 8 == 0, n > 1)");
   NV_CHECK_ARG(nv_aligned16(act) && nv_aligned16(grad) && nv_aligned16(workspace), "nv_gradcam_reduce: 16-byte alignment");
   NV_CHECK_ARG(ws_bytes >= nv_gradcam_workspace_bytes(B, n), "nv_gradcam_reduce: workspace too small");
-  return gradcam_launch("nv_gradcam_reduce", act, grad, n, d, 1, B * (n - 1), gc_blocks((long)B * (n - 1), GC_MAX_BLOCKS), cam, minmax, workspace, stream);
+  return nv_attr_gradcam_launch("nv_gradcam_reduce", act, grad, n, d, 1, B * (n - 1), gc_blocks((long)B * (n - 1), GC_MAX_BLOCKS), cam, minmax, workspace, stream);
 }
 
 extern "C" long nv_gradcam_per_volume_workspace_bytes(int B, int n) {
@@ -298,7 +197,7 @@ extern "C" int nv_gradcam_reduce_per_volume(const void* act, const float* grad, 
                "nv_gradcam_reduce_per_volume: bad arguments (d %% 8 == 0, n > 1, B <= 65535)");
   NV_CHECK_ARG(nv_aligned16(act) && nv_aligned16(grad) && nv_aligned16(workspace), "nv_gradcam_reduce_per_volume: 16-byte alignment");
   NV_CHECK_ARG(ws_bytes >= nv_gradcam_per_volume_workspace_bytes(B, n), "nv_gradcam_reduce_per_volume: workspace too small");
-  return gradcam_launch("nv_gradcam_reduce_per_volume", act, grad, n, d, B, n - 1, gc_blocks(n - 1, GCV_MAX_BLOCKS), cam, minmax, workspace, stream);
+  return nv_attr_gradcam_launch("nv_gradcam_reduce_per_volume", act, grad, n, d, B, n - 1, gc_blocks(n - 1, GCV_MAX_BLOCKS), cam, minmax, workspace, stream);
 }
 
 extern "C" long nv_token_map_to_volume_workspace_bytes(int B, const int* grid3) {
@@ -320,20 +219,31 @@ extern "C" int nv_token_map_to_volume(const float* maps, int B, const int* grid3
                "nv_token_map_to_volume: output extents %d x %d x %d beyond the kernel's tables (G1 G2 + 2 S1 + 2 S2 <= 16384)", S0, S1, S2);
   NV_CHECK_ARG(nv_aligned16(out) && nv_aligned16(workspace) && nv_aligned(maps, 4), "nv_token_map_to_volume: out / workspace 16-byte aligned");
   NV_CHECK_ARG(ws_bytes >= nv_token_map_to_volume_workspace_bytes(B, grid3), "nv_token_map_to_volume: workspace too small");
-  // position of the quantile among the N order statistics, as torch.quantile: q (N - 1) in double
-  const double q = 1.0 - keep_percent / 100.0, pos = q * (double)(N - 1);
-  int i_lo = (int)floor(pos);
-  if (i_lo > N - 1) i_lo = (int)N - 1;
-  const int i_hi = i_lo + 1 < N ? i_lo + 1 : (int)N - 1;
-  const double w = pos - (double)i_lo;
   float* norm = (float*)workspace;
   float* sparse = norm + (long)B * N;
   float* cuts = sparse + (long)B * N;
-  hipLaunchKernelGGL(token_map_threshold_kernel, dim3(B), dim3(TM_THREADS), 0, (hipStream_t)stream, maps, (int)N, normalize ? 1 : 0, i_lo, i_hi, w, norm, sparse,
-                     cuts);
-  NV_CHECK_LAUNCH("nv_token_map_to_volume (threshold)");
-  hipLaunchKernelGGL(upsample_trilinear_kernel, dim3(S0, B), dim3(UP_THREADS), (size_t)lds, (hipStream_t)stream, sparse, G0, G1, G2, S0, S1, S2,
+  const int rc = nv_attr_threshold_launch("nv_token_map_to_volume (threshold)", maps, B, (int)N, normalize, keep_percent, norm, sparse, cuts, stream);
+  if (rc != NV_OK) return rc;
+  return nv_attr_upsample_launch("nv_token_map_to_volume (upsample)", sparse, B, grid3, out3, out, stream);
+}
+
+// ---- what series_attr.hip reuses (attr_common.h)
+int nv_attr_gc_blocks(long rows, int groups) { return gc_blocks(rows, groups == 1 ? GC_MAX_BLOCKS : GCV_MAX_BLOCKS); }
+long nv_attr_gc_workspace_bytes(int groups, int blocks) { return gc_ticket_bytes(groups) + 8L * groups * blocks; }
+
+int nv_attr_threshold_launch(const char* name, const float* maps, int V, int N, int normalize, double keep_percent, float* norm, float* sparse, float* cuts,
+                             void* stream) {
+  hipLaunchKernelGGL(token_map_threshold_kernel, dim3(V), dim3(TM_THREADS), 0, (hipStream_t)stream, maps, N, normalize ? 1 : 0, quantile_pos(keep_percent, N),
+                     norm, sparse, cuts);
+  NV_CHECK_LAUNCH(name);
+  return NV_OK;
+}
+
+int nv_attr_upsample_launch(const char* name, const float* sparse, int V, const int* grid3, const int* out3, float* out, void* stream) {
+  const int G0 = grid3[0], G1 = grid3[1], G2 = grid3[2], S0 = out3[0], S1 = out3[1], S2 = out3[2];
+  const long lds = ((long)G1 * G2 + 2L * S1 + 2L * S2) * 4;
+  hipLaunchKernelGGL(upsample_trilinear_kernel, dim3(S0, V), dim3(UP_THREADS), (size_t)lds, (hipStream_t)stream, sparse, G0, G1, G2, S0, S1, S2,
                      (float)G0 / (float)S0, (float)G1 / (float)S1, (float)G2 / (float)S2, out);
-  NV_CHECK_LAUNCH("nv_token_map_to_volume (upsample)");
+  NV_CHECK_LAUNCH(name);
   return NV_OK;
 }

@@ -564,6 +564,84 @@ def token_maps_to_volumes(maps: torch.Tensor, grid, size, normalize: bool = True
     return out, (ws[:B * N].view(B, N), ws[B * N:2 * B * N].view(B, N), ws[2 * B * N:])
 
 
+SERIES_SCOPES = {"series": 0, "volume": 1}      # NV_SERIES_SCOPE_SERIES / NV_SERIES_SCOPE_VOLUME
+SERIES_LAYOUTS = {"series": 0, "frames": 1}     # NV_SERIES_LAYOUT_SERIES / NV_SERIES_LAYOUT_FRAMES
+SERIES_MAX_TIMEPOINTS = 64                      # csrc/series_attr.hip: SS_MAX_T
+SERIES_MAX_CELLS = 32768                        # SS_MAX_CELLS: T * N cells of one sample under scope "series"
+
+
+def gradcam_reduce_grouped(act: torch.Tensor, grad: torch.Tensor, group: int):
+    """gradcam_reduce with the min-max taken over every `group` consecutive volumes (a sample's T timepoints): act 16-bit [V, n, d],
+    grad f32 [V, n, d] (device) -> (cam f32 [V, n-1], minmax f32 [V / group, 2]).  group = 1 has the bits of gradcam_reduce_per_volume,
+    group = V those of gradcam_reduce.  nv_gradcam_reduce_grouped, one launch."""
+    _need_cuda(act, grad)
+    assert act.dtype == op16() and grad.dtype == torch.float32 and act.shape == grad.shape and act.is_contiguous() and grad.is_contiguous()
+    V, n, d = act.shape
+    nb = lib.nv_gradcam_grouped_workspace_bytes(V, n, int(group))
+    if nb < 0:
+        raise ValueError(f"neurovit_amd: gradcam_reduce_grouped: {V} volumes are no whole number of groups of {group}")
+    cam = torch.empty((V, n - 1), dtype=torch.float32, device=act.device)
+    mm = torch.empty((V // int(group), 2), dtype=torch.float32, device=act.device)
+    ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=act.device)
+    check(lib.nv_gradcam_reduce_grouped(_p(act), _p(grad), V, n, d, int(group), _p(cam), _p(mm), _p(ws), nb, _stream()), "nv_gradcam_reduce_grouped")
+    return cam, mm
+
+
+def series_maps_to_volumes(maps: torch.Tensor, grid, size, normalize: bool = True, scope: str = "series", keep_percent: float = 100.0,
+                           layout: str = "series", return_maps: bool = False, out: Optional[torch.Tensor] = None):
+    """maps f32 [B, T, G0*G1*G2] (device, token order per timepoint) -> volumes f32 [B, S0, S1, S2, T] (layout "series": time innermost, as
+    the model's input) or [B, T, S0, S1, S2] (layout "frames"); grid / size: an int (cubic) or three.  token_maps_to_volumes with the
+    normalisation and the percentile cut taken over the sample's T N cells jointly (scope "series": one min, max and cut per sample) or
+    over every volume on its own (scope "volume").  nv_series_map_to_volumes, two launches.  return_maps: also (normalised maps [B, T, N],
+    thresholded maps [B, T, N], cuts [B] or [B, T]) - views of the call's workspace."""
+    _need_cuda(maps)
+    if scope not in SERIES_SCOPES or layout not in SERIES_LAYOUTS:
+        raise ValueError(f"neurovit_amd: series_maps_to_volumes: scope must be 'series' or 'volume' and layout 'series' or 'frames', got {scope!r}, {layout!r}")
+    grid, size = _triple(grid, "grid"), _triple(size, "size")
+    N = grid[0] * grid[1] * grid[2]
+    assert maps.dim() == 3 and maps.shape[2] == N and maps.dtype == torch.float32 and maps.is_contiguous()
+    B, T = maps.shape[:2]
+    (g3, g3p), (s3, s3p) = _int3_ptr(grid), _int3_ptr(size)
+    nb = lib.nv_series_map_to_volumes_workspace_bytes(B, T, g3p, SERIES_SCOPES[scope])
+    if nb < 0:
+        raise ValueError(f"neurovit_amd: series_maps_to_volumes needs a non-empty batch, 1 .. {SERIES_MAX_TIMEPOINTS} timepoints and a positive grid, "
+                         f"got B = {B}, T = {T}, grid = {grid}")
+    ws = torch.empty(nb // 4, dtype=torch.float32, device=maps.device)
+    shape = (B,) + size + (T,) if layout == "series" else (B, T) + size
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=maps.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == maps.device
+    check(lib.nv_series_map_to_volumes(_p(maps), B, T, g3p, s3p, int(bool(normalize)), SERIES_SCOPES[scope], float(keep_percent), SERIES_LAYOUTS[layout],
+                                       _p(out), _p(ws), nb, _stream()), "nv_series_map_to_volumes")
+    if not return_maps:
+        return out
+    V = B * T
+    return out, (ws[:V * N].view(B, T, N), ws[V * N:2 * V * N].view(B, T, N), ws[2 * V * N:] if scope == "series" else ws[2 * V * N:].view(B, T))
+
+
+def series_leave_one_out(z: torch.Tensor, z_base: torch.Tensor) -> torch.Tensor:
+    """z f32 [B, T, 2], z_base f32 [2] (device) -> f32 [B (T + 1), T, 2]: row b (T + 1) is z[b], row b (T + 1) + 1 + t is z[b] with timepoint t
+    replaced by z_base - the sequences of temporal occlusion, a pure select.  nv_series_leave_one_out, one launch."""
+    _need_cuda(z, z_base)
+    assert z.dim() == 3 and z.shape[2] == 2 and z.dtype == torch.float32 and z.is_contiguous()
+    assert z_base.shape == (2,) and z_base.dtype == torch.float32 and z_base.is_contiguous()
+    B, T, _ = z.shape
+    out = torch.empty((B * (T + 1), T, 2), dtype=torch.float32, device=z.device)
+    check(lib.nv_series_leave_one_out(_p(z), _p(z_base), B, T, _p(out), _stream()), "nv_series_leave_one_out")
+    return out
+
+
+def temporal_grad_x_input(dx: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
+    """dx, z f32 [B, T, 2] (device) -> f32 [B, T] = sum_c dx[b, t, c] z[b, t, c], every product and the sum rounded on its own: the bits of
+    (dx * z).sum(-1).  nv_temporal_grad_x_input, one launch."""
+    _need_cuda(dx, z)
+    assert z.dim() == 3 and z.shape[2] == 2 and dx.shape == z.shape and dx.dtype == z.dtype == torch.float32 and dx.is_contiguous() and z.is_contiguous()
+    B, T, _ = z.shape
+    out = torch.empty((B, T), dtype=torch.float32, device=z.device)
+    check(lib.nv_temporal_grad_x_input(_p(dx), _p(z), B, T, _p(out), _stream()), "nv_temporal_grad_x_input")
+    return out
+
+
 SCORE_KINDS = {"prob": 0, "logit": 1}      # NV_SCORE_PROB / NV_SCORE_LOGIT
 
 

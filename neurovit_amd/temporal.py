@@ -54,9 +54,13 @@ class TemporalHead:
 
     # ------------------------------------------------------------------ what the kernel implements
     def supported(self, x: torch.Tensor) -> bool:
+        return x.is_cuda and x.dim() == 3 and x.shape[2] == 2 and self.supports(x.shape[1])
+
+    def supports(self, timepoints: int) -> bool:
+        """the modules are what the kernel computes, for sequences of `timepoints` elements (no tensor needed: decided before any device work)"""
         lay, mha, proj = self._layer, self._layer.self_attn, self.projection_head.projection_head
         drops = {float(lay.dropout.p), float(lay.dropout1.p), float(lay.dropout2.p), float(mha.dropout)}
-        return (x.is_cuda and x.dim() == 3 and x.shape[2] == 2 and 1 <= x.shape[1] <= MAX_TIMEPOINTS and self.ff <= MAX_FEEDFORWARD
+        return (1 <= timepoints <= MAX_TIMEPOINTS and self.ff <= MAX_FEEDFORWARD
                 and self.ff % 4 == 0 and len(self.temporal_transformer.transformer.layers) == 1
                 and self.temporal_transformer.transformer.norm is None
                 and mha.embed_dim == 2 and mha.num_heads == 2 and mha._qkv_same_embed_dim and mha.in_proj_bias is not None

@@ -667,12 +667,15 @@ class ViT(nn.Module):
         logits, maps = self.attention_maps(video, head_fusion=head_fusion, vol_sigma=vol_sigma, time_points=time_points)
         return logits, ops.attn_rollout([maps[l] for l in range(self._cfg.depth)], start_mean=self.pool == "mean")
 
-    def attention_gradients(self, video, target=None, layers=None, form="per_head", vol_sigma=None, time_points=0):
+    def attention_gradients(self, video, target=None, layers=None, form="per_head", vol_sigma=None, time_points=0, score_grad=None):
         """The gradient of a class score w.r.t. the attention probabilities of `layers` (default all): (logits, {layer: fp32 map}).
         form "per_head": [B, heads, n, n] = d logit_target / d P_l, the gradient w.r.t. the output of the block's `attend` (vit_3d.py:54)
         that attn.register_hook / a backward hook on `attend` give on the reference; form "relevance": [B, n, n] =
         mean_h relu(dP_l * P_l), the layer term of gradient-weighted attention relevance (Chefer et al.).
         target: None = the arg-max class of each volume (as get_attention_map), an int, or a LongTensor [B].
+        score_grad (instead of `target`): fp32 [B, C] on the device, the gradient of ANY score w.r.t. the logits, one row per volume - the
+        backward is seeded with it in place of the one-hot (the 4D model's seed through its temporal head); the one-hot of c gives the bits
+        of target = c.
         Runs one graph-recording forward (the training arithmetic, 16-bit operands: precision("fp32") does not apply) and the data-only
         backward of the one-hot of `target` itself, down to the lowest requested layer: it works under torch.no_grad(), touches no p.grad
         and no gradient arena, and leaves last_attn_norm_grad as a normal backward would.  Forward hooks on `attend` fire as in forward();
@@ -684,6 +687,17 @@ class ViT(nn.Module):
         layers = list(range(depth)) if layers is None else sorted({int(l) for l in layers})
         if not layers or any(not 0 <= l < depth for l in layers):
             raise ValueError(f"neurovit_amd.ViT: layers must be a non-empty subset of [0, {depth}), got {layers}")
+        self._check_data_backward(time_points)
+        self.check_video(video)
+        B = video.shape[0]
+        check_target(target, B, C)
+        self._check_score_grad(target, score_grad, B, video.device)
+        logits = self.recording_forward(video, vol_sigma)
+        maps = self.data_backward(target_classes(target, logits) if score_grad is None else score_grad, layers, form)
+        return logits, maps
+
+    def _check_data_backward(self, time_points=0):
+        """what the recording forward + data-only backward pair cannot serve (NotImplementedError), decided before any device work"""
         if time_points:
             raise NotImplementedError("neurovit_amd.ViT: no attention gradients through the fused 4D input form (time_points) - it is "
                                       "forward-only; pass the [B*T, C, F, H, W] volumes instead")
@@ -693,33 +707,68 @@ class ViT(nn.Module):
         if self.training and self._dropout_p[0] > 0:
             raise NotImplementedError("neurovit_amd.ViT: no attention gradients with attention dropout active (train mode, dropout > 0): the mask "
                                       "is not replayed into the gradient of the probabilities - call eval() for attribution")
-        self.check_video(video)
+
+    def _check_score_grad(self, target, score_grad, B: int, device) -> None:
+        """ValueError for a `score_grad` that is not fp32 [B, C] on the input's device, or that comes together with a `target`"""
+        if score_grad is None:
+            return
+        if target is not None:
+            raise ValueError("neurovit_amd.ViT: score_grad and target are mutually exclusive (score_grad IS the gradient of the explained score)")
+        C = self._cfg.num_classes
+        if not torch.is_tensor(score_grad) or tuple(score_grad.shape) != (B, C) or score_grad.dtype != torch.float32 or score_grad.device != device:
+            raise ValueError(f"neurovit_amd.ViT: score_grad must be fp32 [{B}, {C}] on {device} (one row of d score / d logits per volume)")
+
+    def recording_forward(self, video, vol_sigma=None):
+        """The forward half of the attribution passes: one graph-recording forward (the training arithmetic) under no_grad, `attend`
+        forward hooks fired; returns the logits.  data_backward() runs against it.  The caller has done the checks (_check_data_backward,
+        check_video)."""
         B = video.shape[0]
-        check_target(target, B, C)
         hooked = self._attend_hooked_layers()
         fwd_export, fwd_maps = self._rt.make_attn_export(B, hooked, None, "all", video.device) if hooked else (None, {})
         with torch.no_grad():
             logits = self._run_forward(video.detach().float(), True, (vol_sigma, 0, fwd_export))
             if hooked:
                 self._fire_attend_hooks(fwd_maps)
-            cls = target_classes(target, logits)
-            dlogits = torch.nn.functional.one_hot(cls, C).to(torch.float32)
+        return logits
+
+    def data_backward(self, seed, layers=None, form="per_head"):
+        """The data-only backward of the most recent recording_forward(), seeded with `seed`: a LongTensor [B] of classes (their one-hot)
+        or fp32 [B, C] rows of d score / d logits.  With `layers` it runs down to the lowest of them and returns their attention gradients
+        {layer: map} in `form` (attention_gradients); without, through the head and the last block only - enough for the Grad-CAM hook
+        gradient - and returns {}.  No p.grad, no gradient arena; leaves last_attn_norm_grad as a normal backward would."""
+        depth, C = self._cfg.depth, self._cfg.num_classes
+        with torch.no_grad():
+            dlogits = torch.nn.functional.one_hot(seed, C).to(torch.float32) if seed.dtype == torch.long else seed
             rec = self._rt._cur
-            export, maps = self._rt.make_attn_grad_export(B, layers, form, video.device)
+            export, maps = self._rt.make_attn_grad_export(rec.B, layers, form, rec.video.device) if layers else (None, {})
             # stages 0 (head) .. depth - min(layers): the layers below the lowest requested one and the embedding add nothing
-            self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, stages=(0, depth - layers[0]), weight_grads=False,
-                              attn_grad=export)
+            self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, stages=(0, depth - layers[0] if layers else 1),
+                              weight_grads=False, attn_grad=export)
             rec.done = True                   # nothing more of this pass will run: its workspace may be refilled
             self._rt.backward_done = True     # the last block's hook gradient (stage 1) is in the workspace
-        return logits, maps
+        return maps
 
-    def attention_relevance(self, video, target=None):
+    def gradcam_taps(self, video, score_grad, vol_sigma=None):
+        """The Grad-CAM taps for a given gradient of the logits, without an autograd graph and without an input gradient: one
+        recording forward and the data-only backward of score_grad (fp32 [B, C] on the device) through the head and the last block.
+        Returns the logits; last_attn_norm_output_raw() / last_attn_norm_grad_raw() then hold the activation and the hook gradient.
+        Exports no attention; refusals and side effects (none) as attention_gradients."""
+        self._check_data_backward()
+        self.check_video(video)
+        self._check_score_grad(None, score_grad, video.shape[0], video.device)
+        if score_grad is None:
+            raise ValueError("neurovit_amd.ViT: gradcam_taps needs score_grad, fp32 [B, C] on the device")
+        logits = self.recording_forward(video, vol_sigma)
+        self.data_backward(score_grad)
+        return logits
+
+    def attention_relevance(self, video, target=None, score_grad=None):
         """Class-specific relevance of the patch tokens (gradient-weighted attention relevance, Chefer et al. "Generic Attention-model
         Explainability": A_l = mean_h relu(dP_l * P_l), R <- R + A_l R from R = I): (logits, [B, N]) - the row of the token the head
         reads (the cls row for pool='cls', the mean of all rows for pool='mean') over the N patch tokens, in token order.  One forward
         and one data-only backward export the A_l (attention_gradients, form "relevance"); nv_attn_relevance accumulates
-        u <- u + u A_l from the last layer down (no [n, n] product is formed).  target as attention_gradients."""
-        logits, maps = self.attention_gradients(video, target=target, form="relevance")
+        u <- u + u A_l from the last layer down (no [n, n] product is formed).  target / score_grad as attention_gradients."""
+        logits, maps = self.attention_gradients(video, target=target, form="relevance", score_grad=score_grad)
         return logits, ops.attn_relevance([maps[l] for l in range(self._cfg.depth)], start_mean=self.pool == "mean")
 
     def integrated_gradients(self, video, target=None, baseline=0.0, steps=50, method="gausslegendre", score="logit", chunk=None,
