@@ -205,15 +205,20 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, const int bid) {
     ws_wait_tiles_in_flight<PIECES>(pre - 1);
     __builtin_amdgcn_s_barrier();                       // barrier -1: stage 0 is in LDS
     int fs = D % S;                                     // ring slot of stage kt + D
-    for (int kt = 0; kt < nk; ++kt) {
+    for (int kt = 0; kt + 1 < nk; ++kt) {
       if (kt + D < nk) issue_stage(kt + D, smem + fs * STAGE);   // slot of stage kt-1: every consumer read retired at barrier kt-1
       const int last = (kt + D < nk) ? kt + D : nk - 1; // newest stage issued so far
       ws_wait_tiles_in_flight<PIECES>(last - (kt + 1) > 0 ? last - (kt + 1) : 0);   // stage kt+1 landed (this wave's share)
       __builtin_amdgcn_s_barrier();                     // barrier kt
       fs = (fs + 1 == S) ? 0 : fs + 1;
     }
+    // Every stage has landed (the last counted wait was for zero stages in flight), so ordinary loads can no longer disturb a hand-counted
+    // vmcnt(N): the epilogue's global operands are requested here, a whole stage of the consumers' MFMAs ahead of their use.
+    EpiRegs<EPI, BM, BN, WS_THREADS> er;
+    epilogue_lds_request<EPI, BM, BN, WS_THREADS>(er, g, m0, n0, tid);
+    __builtin_amdgcn_s_barrier();                       // barrier nk-1
     __builtin_amdgcn_s_barrier();                       // barrier E: the consumers have parked the C tile in LDS
-    epilogue_lds<EPI, T, BM, BN, WS_THREADS>(smem, g, m0, n0, tid, reinterpret_cast<const float*>(smem + S * STAGE));
+    epilogue_lds_finish<EPI, T, BM, BN, WS_THREADS>(smem, g, m0, n0, tid, er, reinterpret_cast<const float*>(smem + S * STAGE));
     return;
   }
 
@@ -301,10 +306,12 @@ __device__ __forceinline__ void gemm_ws_body(const GemmArgs& g, const int bid) {
 #undef SB
 #undef WS_ADVANCE
   static_assert(BM * cpitch<BN>() + colsum_scratch_bytes<BM, BN, WS_THREADS>() <= S * STAGE, "C tile (+ column-sum scratch) must fit in the ring");
+  EpiRegs<EPI, BM, BN, WS_THREADS> er;                  // the fragments are dead: request the epilogue's global operands ahead of the park
+  epilogue_lds_request<EPI, BM, BN, WS_THREADS>(er, g, m0, n0, tid);
   park_acc<MI, NI, BN>(acc, smem, wm * TM, wn * TN, lane);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the raw barrier carries no wait: the parked tile must be written first
   __builtin_amdgcn_s_barrier();                         // barrier E
-  epilogue_lds<EPI, T, BM, BN, WS_THREADS>(smem, g, m0, n0, tid, reinterpret_cast<const float*>(smem + S * STAGE));
+  epilogue_lds_finish<EPI, T, BM, BN, WS_THREADS>(smem, g, m0, n0, tid, er, reinterpret_cast<const float*>(smem + S * STAGE));
 }
 
 template <typename T, int BM, int BN, int S, int KS, bool A_T, bool B_T, int EPI>

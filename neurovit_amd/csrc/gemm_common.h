@@ -204,12 +204,51 @@ __device__ __forceinline__ r16x8 read_frag(const char* img, int rc0, int ks, int
   }
 }
 
+// ---- global operands of the fused epilogues -------------------------------------------------------------------------------
+// What a chunk of four output columns reads from global memory besides its accumulators, as values: the caller loads them (the LDS epilogue
+// for all chunks of a thread at once, ahead of the arithmetic - epilogue_lds_request) and epilogue4 only computes and stores.
+struct EpiCols {        // per column group: bias[n .. n+3] and colscale[n .. n+3]
+  f32x4 bias, scale;
+  bool scaled;          // g.colscale != null (fp8 operands)
+};
+struct EpiNone {};
+template <int EPI> constexpr bool epi_has_bias() {
+  return EPI == EPI_BIAS_F32 || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_GELU_F8 || EPI == EPI_BIAS_GELU_F8T || EPI == EPI_BIAS_RESID_LN;
+}
+// per chunk: the residual (f32), the pre-activation u (16-bit) or, for an accumulating fp32 store, the old C
+template <int EPI> constexpr int epi_aux_kind() {
+  return (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_RESID_LN || EPI == EPI_STORE_F32) ? 1 : (EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM) ? 2 : 0;
+}
+template <int KIND> struct epi_aux_sel { typedef EpiNone type; };
+template <> struct epi_aux_sel<1> { typedef f32x4 type; };
+template <> struct epi_aux_sel<2> { typedef r16x4 type; };
+template <int EPI> using epi_aux_t = typename epi_aux_sel<epi_aux_kind<EPI>()>::type;
+
+template <int EPI>
+__device__ __forceinline__ EpiCols epi_load_cols(const GemmArgs& g, int n) {      // n < N
+  EpiCols cc = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{1.f, 1.f, 1.f, 1.f}, g.colscale != nullptr};
+  if (cc.scaled) cc.scale = *reinterpret_cast<const f32x4*>(g.colscale + n);
+  if constexpr (epi_has_bias<EPI>()) cc.bias = *reinterpret_cast<const f32x4*>(g.bias + n);
+  return cc;
+}
+// EPI_STORE_F32 reads C only when it accumulates: a launch-uniform condition the callers test once, outside their loops
+template <int EPI> __device__ __forceinline__ bool epi_aux_wanted(const GemmArgs& g) {
+  if constexpr (EPI == EPI_STORE_F32) return g.accumulate != 0;
+  else return epi_aux_kind<EPI>() != 0;
+}
+template <int EPI>
+__device__ __forceinline__ epi_aux_t<EPI> epi_load_aux(const GemmArgs& g, int m, int n) {      // m < M, n < N, epi_aux_wanted
+  if constexpr (EPI == EPI_STORE_F32) return *reinterpret_cast<const f32x4*>((const float*)g.C + (long)m * g.ldc + n);
+  else if constexpr (epi_aux_kind<EPI>() == 1) return *reinterpret_cast<const f32x4*>((const float*)g.aux_in + (long)m * g.ld_aux_in + n);
+  else if constexpr (epi_aux_kind<EPI>() == 2) return *reinterpret_cast<const r16x4*>((const r16*)g.aux_in + (long)m * g.ld_aux_in + n);
+  else return EpiNone{};
+}
+
 // ---- epilogue core: four consecutive output columns (m, n .. n+3) ----------------------------------------------------
 template <int EPI, typename T>
-__device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& g, int m, int n) {
-  if (g.colscale) v *= *reinterpret_cast<const f32x4*>(g.colscale + n);
-  if constexpr (EPI == EPI_BIAS_F32 || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_GELU_F8 || EPI == EPI_BIAS_GELU_F8T || EPI == EPI_BIAS_RESID_LN)
-    v += *reinterpret_cast<const f32x4*>(g.bias + n);
+__device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& g, int m, int n, const EpiCols& cc, const epi_aux_t<EPI>& ax) {
+  if (cc.scaled) v *= cc.scale;
+  if constexpr (epi_has_bias<EPI>()) v += cc.bias;
   f32x4 keep = f32x4{1.f, 1.f, 1.f, 1.f};
   if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM || EPI == EPI_BIAS_GELU_F8T) {
     if (g.drop.thresh) {
@@ -220,7 +259,7 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& g, int m, in
     *reinterpret_cast<r16x4*>((r16*)g.C + (long)m * g.ldc + n) = cvt4<T>(v[0], v[1], v[2], v[3]);
   } else if constexpr (EPI == EPI_STORE_F32) {
     float* c = (float*)g.C + (long)m * g.ldc + n;
-    if (g.accumulate) v += *reinterpret_cast<const f32x4*>(c);
+    if (g.accumulate) v += ax;
     *reinterpret_cast<f32x4*>(c) = v;
     // optional bf16 mirror of what was stored (data-parallel gradient messages: the weight gradient leaves its GEMM already in the
     // wire format, no cast pass over the arena afterwards)
@@ -254,14 +293,14 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& g, int m, in
     *reinterpret_cast<r16x4*>((r16*)g.aux_out2 + (long)m * g.ld_aux_out2 + n) = cvt4<T>(h[0], h[1], h[2], h[3]);
     *reinterpret_cast<unsigned*>((char*)g.C + (long)m * g.ldc + n) = pack_fp8x4(h * g.alpha);
   } else if constexpr (EPI == EPI_BIAS_RESID) {
-    v = v * keep + *reinterpret_cast<const f32x4*>((const float*)g.aux_in + (long)m * g.ld_aux_in + n);
+    v = v * keep + ax;
     *reinterpret_cast<f32x4*>((float*)g.C + (long)m * g.ldc + n) = v;
   } else if constexpr (EPI == EPI_BIAS_RESID_LN) {
-    v += *reinterpret_cast<const f32x4*>((const float*)g.aux_in + (long)m * g.ld_aux_in + n);
+    v += ax;
     *reinterpret_cast<f32x4*>((float*)g.C + (long)m * g.ldc + n) = v;
     *reinterpret_cast<r16x4*>((r16*)g.aux_out + (long)m * g.ld_aux_out + n) = cvt4<T>(v[0], v[1], v[2], v[3]);      // (the row statistics: epilogue_lds)
   } else if constexpr (EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM) {
-    const f32x4 u = dec4<T>(*reinterpret_cast<const r16x4*>((const r16*)g.aux_in + (long)m * g.ld_aux_in + n));
+    const f32x4 u = dec4<T>(ax);
     const r16x4 o = cvt4<T>(v[0] * keep[0] * gelu_grad_f(u[0]), v[1] * keep[1] * gelu_grad_f(u[1]),
                             v[2] * keep[2] * gelu_grad_f(u[2]), v[3] * keep[3] * gelu_grad_f(u[3]));
     *reinterpret_cast<r16x4*>((r16*)g.C + (long)m * g.ldc + n) = o;
@@ -283,7 +322,9 @@ __device__ __forceinline__ void epilogue(const f32x4 (&acc)[MI][NI], const GemmA
     for (int j = 0; j < NI; ++j) {
       const int n = nb + 16 * j + 4 * lg;
       if (n >= g.N) continue;
-      epilogue4<EPI, T>(acc[i][j], g, m, n);
+      epi_aux_t<EPI> ax{};
+      if (epi_aux_wanted<EPI>(g)) ax = epi_load_aux<EPI>(g, m, n);
+      epilogue4<EPI, T>(acc[i][j], g, m, n, epi_load_cols<EPI>(g, n), ax);
     }
   }
 }
@@ -410,19 +451,61 @@ __device__ __forceinline__ void ln_cols_to_lds(const GemmArgs& g, int n0, float*
   }
 }
 
+// The global operands of one thread's share of a parked [BM][BN] tile.  A thread walks chunks c = tid, tid + NT, ...: always the same column group
+// (NT % CPR == 0), one row every NT / CPR, so its bias / colscale vectors are loaded once and its residual / u / old-C chunks fill a
+// compile-time-sized register array.  Written chunk by chunk - load, wait, compute, store - every chunk cost a full memory round trip: the operand
+// pointers are not `restrict` and sit behind run-time guards, so hipcc kept each chunk's loads behind the stores of the one before and waited
+// vmcnt(0), which on this ISA also counts those stores, per chunk (11 dependent round trips per wave in the 256 x 128 kernel, from HBM for the u
+// that FC1 wrote a millisecond earlier).
+template <int EPI, int BM, int BN, int NT>
+struct EpiRegs {
+  static constexpr int CPR = BN / 4, RPS = NT / CPR, SLOTS = (BM + RPS - 1) / RPS;      // 16-byte chunks per row, rows per step, chunks per thread
+  EpiCols cols;
+  epi_aux_t<EPI> aux[SLOTS];
+};
+template <int EPI> constexpr bool epi_requests() { return !epi_is_fold<EPI>() && EPI != EPI_ADAMW; }
+
+// Phase 1: request everything.  No load depends on the parked tile, so the kernels call this before they park it (the park and its barrier
+// then cover the latency).  Rows / columns beyond M / N are clamped to the last valid ones - an unconditional load batches, a guarded one gets
+// a branch and a wait of its own - and their values are never used; a thread otherwise reads exactly the elements it later writes, so
+// in-place use (C == aux_in, accumulate) stays legal.
+template <int EPI, int BM, int BN, int NT>
+__device__ __forceinline__ void epilogue_lds_request(EpiRegs<EPI, BM, BN, NT>& er, const GemmArgs& g, int m0, int n0, int tid) {
+  typedef EpiRegs<EPI, BM, BN, NT> R;
+  static_assert(NT % R::CPR == 0 && 64 % R::CPR == 0, "every thread keeps one column group");
+  if constexpr (epi_requests<EPI>()) {
+    const int n = min(n0 + (tid % R::CPR) * 4, g.N - 4);      // N % 8 == 0
+    er.cols = epi_load_cols<EPI>(g, n);
+    if constexpr (epi_aux_kind<EPI>() != 0) {
+      if (epi_aux_wanted<EPI>(g)) {
+#pragma unroll
+        for (int s = 0; s < R::SLOTS; ++s) er.aux[s] = epi_load_aux<EPI>(g, min(m0 + tid / R::CPR + s * R::RPS, g.M - 1), n);
+      }
+    }
+  }
+}
+
+// Phase 2: walk the chunks - parked cell from LDS, arithmetic, stores; no wait between the stores of one chunk and the arithmetic of the next.
 template <int EPI, typename T, int BM, int BN, int NT>
-__device__ __forceinline__ void epilogue_lds(char* ctile, const GemmArgs& g, int m0, int n0, int tid, const float* lnrow = nullptr) {
+__device__ __forceinline__ void epilogue_lds_finish(char* ctile, const GemmArgs& g, int m0, int n0, int tid, const EpiRegs<EPI, BM, BN, NT>& er,
+                                                    const float* lnrow = nullptr) {
   if constexpr (EPI == EPI_ADAMW) { epilogue_lds_adamw<T, BM, BN, NT>(ctile, g, m0, n0, tid); return; }
-  constexpr int CPR = BN / 4;                 // 16-byte chunks per row
-  static_assert(NT % CPR == 0 && 64 % CPR == 0, "every thread keeps one column group");
+  typedef EpiRegs<EPI, BM, BN, NT> R;
+  constexpr int CPR = R::CPR;                 // 16-byte chunks per row
   constexpr bool FOLD = epi_is_fold<EPI>();
   float* scr = reinterpret_cast<float*>(ctile + BM * cpitch<BN>());       // scratch behind the parked tile (column sums)
   f32x4 csum = f32x4{0.f, 0.f, 0.f, 0.f};
   static_assert(EPI != EPI_BIAS_RESID_LN || ((BM * CPR) % 64 == 0 && NT % 64 == 0 && CPR == 32 && BN == 128), "whole waves leave the loop together; 32 lanes share a row");
-#pragma unroll 4
-  for (int c = tid; c < BM * CPR; c += NT) {
-    const int row = c / CPR, col = (c % CPR) * 4;
-    const int m = m0 + row, n = n0 + col;
+  const int col = (tid % CPR) * 4, n = n0 + col;
+  // One wait for everything requested, as an instruction the compiler's own wait bookkeeping sees (vmcnt(0), the other counters left alone).  The chunks
+  // below sit behind run-time guards, and behind those it would otherwise wait for each operand again at every chunk, with counts that take the
+  // stores of the chunks before for loads still in flight: the serial round trips all over again, on the stores.
+  if constexpr (epi_requests<EPI>()) __builtin_amdgcn_s_waitcnt(0x0F70);
+#pragma unroll
+  for (int s = 0; s < R::SLOTS; ++s) {
+    const int row = tid / CPR + s * R::RPS;
+    if (BM % R::RPS != 0 && row >= BM) break;      // (only the last step can be partial)
+    const int m = m0 + row;
     f32x4 r = f32x4{0.f, 0.f, 0.f, 0.f};
     if (m < g.M && n < g.N) {
       const f32x4 cell = *reinterpret_cast<const f32x4*>(ctile + row * cpitch<BN>() + col * 4);
@@ -432,13 +515,15 @@ __device__ __forceinline__ void epilogue_lds(char* ctile, const GemmArgs& g, int
         if constexpr (EPI == EPI_LNFOLD_GELU) *reinterpret_cast<r16x4*>((r16*)g.C + (long)m * g.ldc + n) = cvt4<T>(gelu_f(y[0]), gelu_f(y[1]), gelu_f(y[2]), gelu_f(y[3]));
         else *reinterpret_cast<r16x4*>((r16*)g.C + (long)m * g.ldc + n) = cvt4<T>(y[0], y[1], y[2], y[3]);
       } else {
-        r = epilogue4<EPI, T>(cell, g, m, n);
+        r = epilogue4<EPI, T>(cell, g, m, n, er.cols, er.aux[s]);
         if constexpr (EPI == EPI_DGELU_COLSUM) csum += r;
       }
     }
     if constexpr (EPI == EPI_BIAS_RESID_LN) {
       // sum and sum of squares of this tile's columns of the row: the 32 lanes of a half-wave hold one row (4 finished values each; zeros beyond N / M)
-      float s1 = (r[0] + r[1]) + (r[2] + r[3]), s2 = (r[0] * r[0] + r[1] * r[1]) + (r[2] * r[2] + r[3] * r[3]);
+      // (the fused multiply-adds written out: left to the compiler, one chunk of the unrolled walk got separate multiplies and adds and its sums
+      // of squares differed in the last bit from those of the others)
+      float s1 = (r[0] + r[1]) + (r[2] + r[3]), s2 = __builtin_fmaf(r[0], r[0], r[1] * r[1]) + __builtin_fmaf(r[2], r[2], r[3] * r[3]);
       s1 = half_wave_sum(s1); s2 = half_wave_sum(s2);
       if ((tid & 31) == 0 && m < g.M) {
         float* out = (float*)g.aux_out2 + ((long)(n0 / BN) * g.M + m) * 2;
@@ -466,6 +551,14 @@ __device__ __forceinline__ void epilogue_lds(char* ctile, const GemmArgs& g, int
       ((float*)g.aux_out)[(long)(m0 / BM) * g.ld_aux_out + n0 + tid] = s;
     }
   }
+}
+
+// both phases back to back, for the kernels that have nothing to put between them
+template <int EPI, typename T, int BM, int BN, int NT>
+__device__ __forceinline__ void epilogue_lds(char* ctile, const GemmArgs& g, int m0, int n0, int tid, const float* lnrow = nullptr) {
+  EpiRegs<EPI, BM, BN, NT> er;
+  epilogue_lds_request<EPI, BM, BN, NT>(er, g, m0, n0, tid);
+  epilogue_lds_finish<EPI, T, BM, BN, NT>(ctile, g, m0, n0, tid, er, lnrow);
 }
 
 

@@ -157,17 +157,23 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& g, const int bid) {
       PP_VMCNT(0);
     }
     int slot2 = 2;
-    for (int kt = 0; kt < nk; ++kt) {
+    for (int kt = 0; kt + 1 < nk; ++kt) {
       __builtin_amdgcn_s_barrier();                                // B_kt
       if (!(DBG & 1)) {
         if (kt + 2 < nk) issue_tile(kt + 2, smem + slot2 * STAGE);
-        if (kt + 1 < nk) { if (kt + 2 < nk) PP_VMCNT(NP); else PP_VMCNT(0); }     // K tile kt+1 landed (this wave's share)
+        if (kt + 2 < nk) PP_VMCNT(NP); else PP_VMCNT(0);           // K tile kt+1 landed (this wave's share)
       }
       slot2 = (slot2 + 1 == PP_S) ? 0 : slot2 + 1;
     }
+    // The last counted wait is behind this wave (vmcnt(0): the last K tile has landed): from here on ordinary loads cannot disturb a hand-counted
+    // vmcnt(N), nor make the compiler drain an LDS-DMA early.  The epilogue's global operands are requested now - the compute waves' last K tile,
+    // the park and three barriers cover their latency.
+    EpiRegs<EPI, BM, BN, PP_THREADS> er;
+    epilogue_lds_request<EPI, BM, BN, PP_THREADS>(er, g, m0, n0, tid);
+    __builtin_amdgcn_s_barrier();                                  // B_nk-1
     __builtin_amdgcn_s_barrier();                                  // B_nk: every fragment read has returned
     __builtin_amdgcn_s_barrier();                                  // accumulators parked
-    epilogue_lds<EPI, T, BM, BN, PP_THREADS>(smem, g, m0, n0, tid, reinterpret_cast<const float*>(smem + PP_S * STAGE));
+    epilogue_lds_finish<EPI, T, BM, BN, PP_THREADS>(smem, g, m0, n0, tid, er, reinterpret_cast<const float*>(smem + PP_S * STAGE));
     return;
   }
 
@@ -233,6 +239,11 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& g, const int bid) {
     ln_cols_to_lds<BM, BN>(g, n0, reinterpret_cast<float*>(smem + PP_S * STAGE), 64 * PP_CWAVES - 1 - tid);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
+  // The epilogue's global operands, requested as soon as the registers are there: 16-bit operands (u of the dGELU epilogues: 22 registers) and the
+  // column constants once the fragments of the last K tile are dead; fp32 operands (residual, old C: 44 registers beside 64 accumulators and the
+  // addresses - over the 168 of three waves per SIMD) once the accumulators are parked.
+  constexpr bool EARLY = epi_aux_kind<EPI>() != 1;
+  EpiRegs<EPI, BM, BN, PP_THREADS> er;
   int slot = 0;
   if (grp == 0) {
     for (int kt = 0; kt < nk; ++kt) {
@@ -273,6 +284,9 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& g, const int bid) {
   }
   __builtin_amdgcn_s_barrier();                         // B_nk
   if (grp == 1) { PP_MFMA(MH) }                         // lower half of the last tile
+  // (one request site for both groups: two would meet in register copies, and a copy waits for its load.  The compute waves issue no other
+  // vector-memory instruction.)
+  if constexpr (EARLY) epilogue_lds_request<EPI, BM, BN, PP_THREADS>(er, g, m0, n0, tid);
 #undef PP_READ_A
 #undef PP_READ_B
 #undef PP_MFMA
@@ -293,8 +307,9 @@ __device__ __forceinline__ void gemm_pp_body(const GemmArgs& g, const int bid) {
     park_acc<MI, NI, BN>(acc, smem, wm * TM, wn * TN, lane);
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if constexpr (!EARLY) epilogue_lds_request<EPI, BM, BN, PP_THREADS>(er, g, m0, n0, tid);
   __builtin_amdgcn_s_barrier();
-  epilogue_lds<EPI, T, BM, BN, PP_THREADS>(smem, g, m0, n0, tid, reinterpret_cast<const float*>(smem + PP_S * STAGE));
+  epilogue_lds_finish<EPI, T, BM, BN, PP_THREADS>(smem, g, m0, n0, tid, er, reinterpret_cast<const float*>(smem + PP_S * STAGE));
 #endif
 }
 
