@@ -219,6 +219,15 @@ int carry_record(void* workspace, hipStream_t on) {
     if (rc__) return rc__;   \
   } while (0)
 
+// Everything a call derives from (config, B, layout): built once per C-ABI call (nv_vit_train_step: once per step) and handed down.
+struct Layout { Dims D; ParamTab T; WS W; };
+int make_layout(const nv_vit_config* c, int B, int training, Layout& Y) {
+  RUN(make_dims(c, B, Y.D));
+  make_params(Y.D, Y.T);
+  make_ws(Y.D, training, Y.W);
+  return NV_OK;
+}
+
 }  // namespace
 
 extern "C" long nv_vit_param_count(const nv_vit_config* cfg) {
@@ -270,18 +279,76 @@ extern "C" long nv_vit_workspace_offset(const nv_vit_config* cfg, int B, int tra
   return -1;
 }
 
-// Patch front end shared by the bf16 and fp8 forwards: the three input forms of nv_vit_input (see the header).
-static int patch_front(const nv_vit_config* cfg, const Dims& D, const ParamTab& T, int B, const float* video, const long* strides5, const nv_vit_input* in,
-                       const float* p, float eps, void* xp, float* pst, void* stream) {
-  const float* sigma = in ? in->vol_sigma : nullptr;
+// ---- host stages shared by the forwards ------------------------------------------------------------------
+// Extents of the input, checked before anything else looks at it: the gather kernels take their extents from the config, so a volume of
+// another size must never reach them.  3D: [B, C, F, H, W]; 4D (nv_vit_input.time_points > 0): contiguous [B / T, H, W, D, T].
+static int check_video(const char* who, const nv_vit_config* cfg, int B, const long* shape5, const nv_vit_input* in, bool allow_4d) {
   if (in && in->time_points > 0) {
-    NV_CHECK_ARG(B % in->time_points == 0 && cfg->channels == 1, "nv_vit_forward: time_points=%d must divide B=%d (channels = 1)", in->time_points, B);
-    // video = contiguous [B / T, H, W, D, T]: (H, W, D) of the dataset = (image, image, frames) of the ViT (NeuroEncoder.py:200-202)
-    return nv_patch_ln_fwd_4d(video, B / in->time_points, cfg->image_size, img_w(cfg), cfg->frames, in->time_points, cfg->image_patch_size,
-                              pat_w(cfg), cfg->frame_patch_size, p + T.pe_g, p + T.pe_b, eps, xp, D.Ppad, pst, pst + D.T, sigma, stream);
+    NV_CHECK_ARG(allow_4d, "%s: the fused 4D input form is forward-only", who);
+    NV_CHECK_ARG(shape5[0] * shape5[4] == B && shape5[4] == in->time_points && shape5[1] == cfg->image_size && shape5[2] == img_w(cfg) && shape5[3] == cfg->frames &&
+                     B % in->time_points == 0 && cfg->channels == 1,
+                 "%s: 4D input is [%ld,%ld,%ld,%ld,%ld], expected [B/T, %d, %d, %d, T=%d] with B = %d", who, shape5[0], shape5[1], shape5[2], shape5[3],
+                 shape5[4], cfg->image_size, img_w(cfg), cfg->frames, in->time_points, B);
+    return NV_OK;
   }
-  return nv_patch_ln_fwd(video, strides5, B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size,
-                         pat_w(cfg), cfg->frame_patch_size, p + T.pe_g, p + T.pe_b, eps, xp, D.Ppad, pst, pst + D.T, sigma, stream);
+  NV_CHECK_ARG(shape5[0] == B && shape5[1] == cfg->channels && shape5[2] == cfg->frames && shape5[3] == cfg->image_size && shape5[4] == img_w(cfg),
+               "%s: video is [%ld,%ld,%ld,%ld,%ld], the model was built for [%d,%d,%d,%d,%d] (B, channels, frames, height, width)", who,
+               shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
+  return NV_OK;
+}
+
+// Embedding front of the 16-bit forwards (bf16 / fp16 operands, and the fp8 forwards, whose patch embedding stays 16-bit): x0 = tokens of the
+// three input forms of nv_vit_input (see the header).  emb_seed / emb_drop_p: the embedding dropout's site seed and probability.
+static int embed_front16(const nv_vit_config* cfg, const Layout& Y, int B, const float* video, const long* strides5, const nv_vit_input* in, const float* p,
+                         const r16* p16, char* ws, unsigned long emb_seed, float emb_drop_p, void* stream) {
+  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
+  const float eps = cfg->ln_eps;
+  const int d = D.d;
+  // A1+A2: gather + LayerNorm(patch_dim) -> bf16
+  float* pst = (float*)(ws + W.pst);
+  const float* sigma = in ? in->vol_sigma : nullptr;
+  if (in && in->time_points > 0)
+    // video = contiguous [B / T, H, W, D, T]: (H, W, D) of the dataset = (image, image, frames) of the ViT (NeuroEncoder.py:200-202)
+    RUN(nv_patch_ln_fwd_4d(video, B / in->time_points, cfg->image_size, img_w(cfg), cfg->frames, in->time_points, cfg->image_patch_size,
+                           pat_w(cfg), cfg->frame_patch_size, p + T.pe_g, p + T.pe_b, eps, ws + W.xp, D.Ppad, pst, pst + D.T, sigma, stream));
+  else
+    RUN(nv_patch_ln_fwd(video, strides5, B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size,
+                        pat_w(cfg), cfg->frame_patch_size, p + T.pe_g, p + T.pe_b, eps, ws + W.xp, D.Ppad, pst, pst + D.T, sigma, stream));
+  // A3: Linear(patch_dim, dim)
+  const void* wpe = p16 + T.pe_w;
+  if (D.P != D.Ppad) {
+    RUN(nv_cast_bf16_2d(p + T.pe_w, D.P, d, D.P, ws + W.wpe16, D.Ppad, stream));
+    wpe = ws + W.wpe16;
+  }
+  RUN(nv_gemm_bf16(0, 2, D.T, d, D.Ppad, ws + W.xp, D.Ppad, wpe, D.Ppad, ws + W.t, d, p + T.pe_bias, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
+  // A4+A5: LayerNorm(dim) + cls + pos
+  float* est = (float*)(ws + W.est);
+  return nv_embed_finish_fwd((float*)(ws + W.t), d, B, D.N, d, p + T.pe_g2, p + T.pe_b2, eps, p + T.pos, p + T.cls, (float*)(ws + W.x0), d, est,
+                             est + D.T, emb_seed, emb_drop_p, stream);
+}
+
+// Block l behind its attention on the B cls rows only (see g_cls_tail), 16-bit operands through the weight-streaming kernels: row b of the
+// small problem = row b * n of the buffers; LN2 statistics land at st2[0 .. B) / st2[M .. M + B).  u: the pre-GELU values for a backward, or NULL.
+static int cls_rows_block16(const Dims& D, const LayerP& q, const LayerW& w, int l, const float* p, const r16* p16, char* ws, float eps, const float* xin,
+                            float* x1, float* x2, float* st2, void* u, unsigned long drop_seed, float drop_p, float proj_p, void* stream) {
+  const int B = D.B, d = D.d;
+  const long rs = D.n;
+  RUN(nv_skinny_nt(0, B, d, D.inner, ws + w.ao, D.inner * rs, p16 + q.wo, D.inner, p + q.bo, xin, d * rs, x1, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 1), proj_p, stream));
+  RUN(nv_ln_fwd(x1, d * rs, B, d, p + q.n2g, p + q.n2b, eps, ws + w.xn2, d * rs, st2, st2 + D.M, stream));
+  RUN(nv_skinny_nt(1, B, D.m, d, ws + w.xn2, d * rs, p16 + q.w1, d, p + q.b1, nullptr, 0, ws + w.h, D.m * rs, u, D.m * rs, site_seed(drop_seed, 4 * l + 2), drop_p, stream));
+  return nv_skinny_nt(0, B, d, D.m, ws + w.h, D.m * rs, p16 + q.w2, D.m, p + q.b2, x1, d * rs, x2, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 3), drop_p, stream);
+}
+
+// A9: cls pooling (or the token mean, pool = 'mean') + LayerNorm + Linear(dim, C).  xm / xh / hst: workspace offsets of either layout.
+static int pool_head(const Dims& D, const ParamTab& T, const float* p, float eps, const float* xin, char* ws, long xm, long xh, long hst, float* logits,
+                     void* stream) {
+  const float* pooled = xin;
+  long pooled_stride = (long)D.n * D.d;
+  if (D.pool_mean) {
+    RUN(nv_token_mean(xin, D.B, D.n, D.d, (float*)(ws + xm), stream));
+    pooled = (float*)(ws + xm); pooled_stride = D.d;
+  }
+  return nv_head_fwd(pooled, pooled_stride, D.B, D.d, p + T.hg, p + T.hb, eps, p + T.hw, p + T.hbias, D.C, (float*)(ws + xh), (float*)(ws + hst), logits, stream);
 }
 
 extern "C" int nv_vit_forward(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5,
@@ -309,7 +376,7 @@ static int export_layer(const nv_vit_input* in, int l, int qkv_f32, const void* 
   return nv_attn_probs(qkv_f32, qkv, 3L * D.inner, B, D.n, D.heads, D.dh, scale, ex->fusion, ex->rows, ex->maps[l], stream);
 }
 
-static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+static int forward_in_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                            const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
                            unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16 = nullptr, const float* fold32 = nullptr);
 
@@ -338,31 +405,24 @@ extern "C" int nv_vit_forward_lnfold(const nv_vit_config* cfg, int B, const floa
                                      const float* params, const void* params16, const void* fold16, const float* fold32, void* workspace, long ws_bytes,
                                      float* logits, void* stream) {
   NV_CHECK_ARG(fold16 && fold32 && nv_aligned16(fold16) && nv_aligned16(fold32), "nv_vit_forward_lnfold: null / unaligned fold arenas (nv_vit_lnfold_prepare)");
-  return forward_in_impl(cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 0, 0.f, 0.f, 0, logits, stream, false, fold16, fold32);
+  Layout Y; RUN(make_layout(cfg, B, 0, Y));
+  return forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 0, 0.f, 0.f, 0, logits, stream, false, fold16, fold32);
 }
 
 extern "C" int nv_vit_forward_in(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                                  const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
                                  unsigned long drop_seed, float* logits, void* stream) {
-  return forward_in_impl(cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, training, drop_p, emb_drop_p, drop_seed, logits, stream, false);
+  Layout Y; RUN(make_layout(cfg, B, training, Y));
+  return forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, training, drop_p, emb_drop_p, drop_seed, logits, stream, false);
 }
 
 // skip_head: everything up to the last block's output; the caller runs the head itself (nv_vit_train_step: nv_head_step)
-static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+static int forward_in_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                            const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
                            unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16, const float* fold32) {
-  Dims D; RUN(make_dims(cfg, B, D));
-  ParamTab T; make_params(D, T);
-  WS W; make_ws(D, training, W);
+  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
   NV_CHECK_ARG(video && shape5 && strides5 && params && params16 && workspace && logits, "nv_vit_forward: null pointer");
-  if (in && in->time_points > 0)
-    NV_CHECK_ARG(shape5[0] * shape5[4] == B && shape5[4] == in->time_points && shape5[1] == cfg->image_size && shape5[2] == img_w(cfg) && shape5[3] == cfg->frames,
-                 "nv_vit_forward: 4D input is [%ld,%ld,%ld,%ld,%ld], expected [B/T, %d, %d, %d, T=%d] with B = %d", shape5[0], shape5[1], shape5[2], shape5[3],
-                 shape5[4], cfg->image_size, img_w(cfg), cfg->frames, in->time_points, B);
-  else
-  NV_CHECK_ARG(shape5[0] == B && shape5[1] == cfg->channels && shape5[2] == cfg->frames && shape5[3] == cfg->image_size && shape5[4] == img_w(cfg),
-               "nv_vit_forward: video is [%ld,%ld,%ld,%ld,%ld], the model was built for [%d,%d,%d,%d,%d] (B, channels, frames, height, width)",
-               shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
+  RUN(check_video("nv_vit_forward", cfg, B, shape5, in, true));
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward: workspace too small (%ld < %ld)", ws_bytes, W.total);
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params) && nv_aligned16(params16), "nv_vit_forward: alignment");
   RUN(check_attn_export(in, "nv_vit_forward"));
@@ -372,21 +432,7 @@ static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, 
   const float eps = cfg->ln_eps;
   const int M = D.M, d = D.d;
 
-  // A1+A2: gather + LayerNorm(patch_dim) -> bf16
-  float* pst = (float*)(ws + W.pst);
-  RUN(patch_front(cfg, D, T, B, video, strides5, in, p, eps, ws + W.xp, pst, stream));
-  // A3: Linear(patch_dim, dim)
-  const void* wpe = p16 + T.pe_w;
-  if (D.P != D.Ppad) {
-    RUN(nv_cast_bf16_2d(p + T.pe_w, D.P, d, D.P, ws + W.wpe16, D.Ppad, stream));
-    wpe = ws + W.wpe16;
-  }
-  RUN(nv_gemm_bf16(0, 2, D.T, d, D.Ppad, ws + W.xp, D.Ppad, wpe, D.Ppad, ws + W.t, d, p + T.pe_bias, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-  // A4+A5: LayerNorm(dim) + cls + pos
-  float* est = (float*)(ws + W.est);
-  RUN(nv_embed_finish_fwd((float*)(ws + W.t), d, B, D.N, d, p + T.pe_g2, p + T.pe_b2, eps, p + T.pos, p + T.cls, (float*)(ws + W.x0), d, est,
-                          est + D.T, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
-
+  RUN(embed_front16(cfg, Y, B, video, strides5, in, p, p16, ws, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
   const float scale = 1.0f / sqrtf((float)D.dh);
   const float* xin = (float*)(ws + W.x0);
   const bool tail = cls_tail_wanted(D, training, drop_p, in ? in->rows_form : 0);
@@ -421,12 +467,7 @@ static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, 
     RUN(nv_attn_fwd(ws + w.qkv, 3 * D.inner, B, D.n, D.heads, D.dh, scale, ws + w.ao, D.inner, (float*)(ws + w.lse), site_seed(drop_seed, 4 * l + 0), drop_p, stream));
     RUN(export_layer(in, l, 0, ws + w.qkv, D, B, scale, stream));
     if (tail && l == D.L - 1) {
-      // cls rows only (row b of the small problem = row b * n of the buffers); LN2 statistics land at st2[0 .. B) / st2[M .. M + B)
-      const long rs = D.n;
-      RUN(nv_skinny_nt(0, B, d, D.inner, ws + w.ao, D.inner * rs, p16 + q.wo, D.inner, p + q.bo, xin, d * rs, x1, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 1), proj_drop_p(cfg, drop_p), stream));
-      RUN(nv_ln_fwd(x1, d * rs, B, d, p + q.n2g, p + q.n2b, eps, ws + w.xn2, d * rs, st2, st2 + M, stream));
-      RUN(nv_skinny_nt(1, B, D.m, d, ws + w.xn2, d * rs, p16 + q.w1, d, p + q.b1, nullptr, 0, ws + w.h, D.m * rs, training ? ws + w.u : nullptr, D.m * rs, site_seed(drop_seed, 4 * l + 2), drop_p, stream));
-      RUN(nv_skinny_nt(0, B, d, D.m, ws + w.h, D.m * rs, p16 + q.w2, D.m, p + q.b2, x1, d * rs, x2, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 3), drop_p, stream));
+      RUN(cls_rows_block16(D, q, w, l, p, p16, ws, eps, xin, x1, x2, st2, training ? ws + w.u : nullptr, drop_seed, drop_p, proj_drop_p(cfg, drop_p), stream));
       xin = x2;
       continue;
     }
@@ -451,16 +492,7 @@ static int forward_in_impl(const nv_vit_config* cfg, int B, const float* video, 
     xin = x2;
   }
   if (skip_head) return NV_OK;
-  // A9: cls pooling + LayerNorm + Linear(dim, C)
-  const float* pooled = xin;
-  long pooled_stride = (long)D.n * d;
-  if (D.pool_mean) {
-    RUN(nv_token_mean(xin, B, D.n, d, (float*)(ws + W.xm), stream));
-    pooled = (float*)(ws + W.xm); pooled_stride = d;
-  }
-  RUN(nv_head_fwd(pooled, pooled_stride, B, d, p + T.hg, p + T.hb, eps, p + T.hw, p + T.hbias, D.C, (float*)(ws + W.xh), (float*)(ws + W.hst),
-                  logits, stream));
-  return NV_OK;
+  return pool_head(D, T, p, eps, xin, ws, W.xm, W.xh, W.hst, logits, stream);
 }
 
 // ---- fp32 inference forward (precise.hip): what the reference's fp32 validate computes (Trainer.py:101-118), every operand fp32,
@@ -471,15 +503,7 @@ extern "C" int nv_vit_forward_f32(const nv_vit_config* cfg, int B, const float* 
   ParamTab T; make_params(D, T);
   WSF W; make_wsf(D, W);
   NV_CHECK_ARG(video && shape5 && strides5 && params && workspace && logits, "nv_vit_forward_f32: null pointer");
-  if (in && in->time_points > 0)
-    NV_CHECK_ARG(shape5[0] * shape5[4] == B && shape5[4] == in->time_points && shape5[1] == cfg->image_size && shape5[2] == img_w(cfg) && shape5[3] == cfg->frames &&
-                     B % in->time_points == 0 && cfg->channels == 1,
-                 "nv_vit_forward_f32: 4D input is [%ld,%ld,%ld,%ld,%ld], expected [B/T, %d, %d, %d, T=%d] with B = %d", shape5[0], shape5[1], shape5[2], shape5[3],
-                 shape5[4], cfg->image_size, img_w(cfg), cfg->frames, in->time_points, B);
-  else
-    NV_CHECK_ARG(shape5[0] == B && shape5[1] == cfg->channels && shape5[2] == cfg->frames && shape5[3] == cfg->image_size && shape5[4] == img_w(cfg),
-                 "nv_vit_forward_f32: video is [%ld,%ld,%ld,%ld,%ld], the model was built for [%d,%d,%d,%d,%d] (B, channels, frames, height, width)",
-                 shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
+  RUN(check_video("nv_vit_forward_f32", cfg, B, shape5, in, true));
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward_f32: workspace too small (%ld < %ld)", ws_bytes, W.total);
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params), "nv_vit_forward_f32: alignment");
   RUN(check_attn_export(in, "nv_vit_forward_f32"));
@@ -505,6 +529,7 @@ extern "C" int nv_vit_forward_f32(const nv_vit_config* cfg, int B, const float* 
   RUN(nv_embed_finish_fwd(F32(W.t), d, B, D.N, d, p + T.pe_g2, p + T.pe_b2, eps, p + T.pos, p + T.cls, F32(W.x0), d, est, est + D.T, 0, 0.f, stream));
   const float scale = 1.0f / sqrtf((float)D.dh);
   const float* xin = F32(W.x0);
+  const bool tail = cls_tail_wanted(D, 0, 0.f, in ? in->rows_form : 0);
   for (int l = 0; l < D.L; ++l) {
     const LayerP& q = T.layer[l];
     float* x1 = F32(W.x1);
@@ -513,31 +538,18 @@ extern "C" int nv_vit_forward_f32(const nv_vit_config* cfg, int B, const float* 
     RUN(nv_gemm_f32(0, M, 3 * D.inner, d, F32(W.xn1), d, p + q.wqkv, d, F32(W.qkv), 3 * D.inner, nullptr, nullptr, 0, stream));
     RUN(nv_attn_fwd_f32(F32(W.qkv), 3 * D.inner, B, D.n, D.heads, D.dh, scale, F32(W.ao), D.inner, stream));
     RUN(export_layer(in, l, 1, F32(W.qkv), D, B, scale, stream));
-    if (l == D.L - 1 && cls_tail_wanted(D, 0, 0.f, in ? in->rows_form : 0)) {
-      // pool = 'cls' (NeuroEncoder.py:194): behind the last attention only the B cls rows reach the head - the last block's
-      // out-projection, LayerNorm and FeedForward run on those rows as strided views (row stride n); same values for the logits
-      const long rs = D.n;
-      RUN(nv_gemm_f32(4, B, d, D.inner, F32(W.ao), D.inner * rs, p + q.wo, D.inner, x1, d * rs, p + q.bo, xin, d * rs, stream));
-      RUN(nv_ln_fwd_f32(x1, d * rs, B, d, p + q.n2g, p + q.n2b, eps, F32(W.xn2), d * rs, nullptr, nullptr, stream));
-      RUN(nv_gemm_f32(3, B, D.m, d, F32(W.xn2), d * rs, p + q.w1, d, F32(W.h), D.m * rs, p + q.b1, nullptr, 0, stream));
-      RUN(nv_gemm_f32(4, B, d, D.m, F32(W.h), D.m * rs, p + q.w2, D.m, x2, d * rs, p + q.b2, x1, d * rs, stream));
-      xin = x2;
-      continue;
-    }
-    RUN(nv_gemm_f32(4, M, d, D.inner, F32(W.ao), D.inner, p + q.wo, D.inner, x1, d, p + q.bo, xin, d, stream));
-    RUN(nv_ln_fwd_f32(x1, d, M, d, p + q.n2g, p + q.n2b, eps, F32(W.xn2), d, nullptr, nullptr, stream));
-    RUN(nv_gemm_f32(3, M, D.m, d, F32(W.xn2), d, p + q.w1, d, F32(W.h), D.m, p + q.b1, nullptr, 0, stream));
-    RUN(nv_gemm_f32(4, M, d, D.m, F32(W.h), D.m, p + q.w2, D.m, x2, d, p + q.b2, x1, d, stream));
+    // pool = 'cls' (NeuroEncoder.py:194): behind the last attention only the B cls rows reach the head - the last block's out-projection,
+    // LayerNorm and FeedForward then run on those rows as strided views (row r of the small problem = row r * rs of the buffers); same logits
+    const bool cls_rows = tail && l == D.L - 1;
+    const int Mr = cls_rows ? B : M;
+    const long rs = cls_rows ? (long)D.n : 1;
+    RUN(nv_gemm_f32(4, Mr, d, D.inner, F32(W.ao), D.inner * rs, p + q.wo, D.inner, x1, d * rs, p + q.bo, xin, d * rs, stream));
+    RUN(nv_ln_fwd_f32(x1, d * rs, Mr, d, p + q.n2g, p + q.n2b, eps, F32(W.xn2), d * rs, nullptr, nullptr, stream));
+    RUN(nv_gemm_f32(3, Mr, D.m, d, F32(W.xn2), d * rs, p + q.w1, d, F32(W.h), D.m * rs, p + q.b1, nullptr, 0, stream));
+    RUN(nv_gemm_f32(4, Mr, d, D.m, F32(W.h), D.m * rs, p + q.w2, D.m, x2, d * rs, p + q.b2, x1, d * rs, stream));
     xin = x2;
   }
-  const float* pooled = xin;
-  long pooled_stride = (long)D.n * d;
-  if (D.pool_mean) {
-    RUN(nv_token_mean(xin, B, D.n, d, F32(W.xm), stream));
-    pooled = F32(W.xm); pooled_stride = d;
-  }
-  RUN(nv_head_fwd(pooled, pooled_stride, B, d, p + T.hg, p + T.hb, eps, p + T.hw, p + T.hbias, D.C, F32(W.xh), F32(W.hst), logits, stream));
-  return NV_OK;
+  return pool_head(D, T, p, eps, xin, ws, W.xm, W.xh, W.hst, logits, stream);
 }
 
 // ---- fp8 inference path (BASELINE.json configs[4]): qkv, FC1 and FC2 of every block on OCP e4m3 operands (92 % of the linear
@@ -576,14 +588,11 @@ extern "C" int nv_vit_quantize_fp8(const nv_vit_config* cfg, const float* params
 extern "C" int nv_vit_forward_fp8(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                                   const float* params, const void* params16, const void* params8, const float* colscales, const float* act_scales, void* workspace,
                                   long ws_bytes, float* logits, void* stream) {
-  Dims D; RUN(make_dims(cfg, B, D));
-  ParamTab T; make_params(D, T);
-  WS W; make_ws(D, 0, W);
+  Layout Y; RUN(make_layout(cfg, B, 0, Y));
+  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
   NV_CHECK_ARG(nv_operand_format() == NV_OPERAND_BF16, "nv_vit_forward_fp8: the fp8 path is built beside bf16 operands (nv_set_operand_format(NV_OPERAND_BF16))");
   NV_CHECK_ARG(video && shape5 && strides5 && params && params16 && params8 && colscales && act_scales && workspace && logits, "nv_vit_forward_fp8: null pointer");
-  NV_CHECK_ARG((in && in->time_points > 0) || (shape5[0] == B && shape5[1] == cfg->channels && shape5[2] == cfg->frames && shape5[3] == cfg->image_size && shape5[4] == img_w(cfg)),
-               "nv_vit_forward_fp8: video is [%ld,%ld,%ld,%ld,%ld], the model was built for [%d,%d,%d,%d,%d] (B, channels, frames, height, width)",
-               shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
+  RUN(check_video("nv_vit_forward_fp8", cfg, B, shape5, in, true));
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward_fp8: workspace too small (%ld < %ld)", ws_bytes, W.total);
   NV_CHECK_ARG(D.d % 128 == 0 && D.m % 128 == 0, "nv_vit_forward_fp8: dim and mlp_dim must be multiples of 128");
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params) && nv_aligned16(params16) && nv_aligned16(params8), "nv_vit_forward_fp8: alignment");
@@ -596,17 +605,7 @@ extern "C" int nv_vit_forward_fp8(const nv_vit_config* cfg, int B, const float* 
   const int M = D.M, d = D.d;
   const long per = 3L * D.inner + D.m + 2L * D.d;
 
-  float* pst = (float*)(ws + W.pst);
-  RUN(patch_front(cfg, D, T, B, video, strides5, in, p, eps, ws + W.xp, pst, stream));
-  const void* wpe = p16 + T.pe_w;
-  if (D.P != D.Ppad) {
-    RUN(nv_cast_bf16_2d(p + T.pe_w, D.P, d, D.P, ws + W.wpe16, D.Ppad, stream));
-    wpe = ws + W.wpe16;
-  }
-  RUN(nv_gemm_bf16(0, 2, D.T, d, D.Ppad, ws + W.xp, D.Ppad, wpe, D.Ppad, ws + W.t, d, p + T.pe_bias, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-  float* est = (float*)(ws + W.est);
-  RUN(nv_embed_finish_fwd((float*)(ws + W.t), d, B, D.N, d, p + T.pe_g2, p + T.pe_b2, eps, p + T.pos, p + T.cls, (float*)(ws + W.x0), d, est,
-                          est + D.T, 0, 0.f, stream));
+  RUN(embed_front16(cfg, Y, B, video, strides5, in, p, p16, ws, 0, 0.f, stream));     // (eval mode: no embedding dropout)
   const float scale = 1.0f / sqrtf((float)D.dh);
   const float* xin = (float*)(ws + W.x0);
   const bool tail8 = cls_tail_wanted(D, 0, 0.f, in ? in->rows_form : 0);
@@ -627,12 +626,7 @@ extern "C" int nv_vit_forward_fp8(const nv_vit_config* cfg, int B, const float* 
     if (tail_here) {
       // the last block's out-projection / LayerNorm / FeedForward on the B cls rows (see g_cls_tail): bf16 operands through the
       // weight-streaming kernels - these few rows gain nothing from fp8 and lose nothing by staying in bf16
-      const long rs = D.n;
-      float* st = (float*)(ws + w.st2);
-      RUN(nv_skinny_nt(0, B, d, D.inner, ws + w.ao, D.inner * rs, p16 + q.wo, D.inner, p + q.bo, xin, d * rs, x1, d * rs, nullptr, 0, 0, 0.f, stream));
-      RUN(nv_ln_fwd(x1, d * rs, B, d, p + q.n2g, p + q.n2b, eps, ws + w.xn2, d * rs, st, st + M, stream));
-      RUN(nv_skinny_nt(1, B, D.m, d, ws + w.xn2, d * rs, p16 + q.w1, d, p + q.b1, nullptr, 0, ws + w.h, D.m * rs, nullptr, 0, 0, 0.f, stream));
-      RUN(nv_skinny_nt(0, B, d, D.m, ws + w.h, D.m * rs, p16 + q.w2, D.m, p + q.b2, x1, d * rs, x2, d * rs, nullptr, 0, 0, 0.f, stream));
+      RUN(cls_rows_block16(D, q, w, l, p, p16, ws, eps, xin, x1, x2, (float*)(ws + w.st2), nullptr, 0, 0.f, 0.f, stream));
       xin = x2;
       continue;
     }
@@ -643,15 +637,7 @@ extern "C" int nv_vit_forward_fp8(const nv_vit_config* cfg, int B, const float* 
     RUN(nv_gemm_f8(4, M, d, D.m, ws + w.h, D.m, p8 + q.w2, D.m, x2, d, cs + 3L * D.inner + D.m, p + q.b2, x1, d, 1.f, stream));
     xin = x2;
   }
-  const float* pooled = xin;
-  long pooled_stride = (long)D.n * d;
-  if (D.pool_mean) {
-    RUN(nv_token_mean(xin, B, D.n, d, (float*)(ws + W.xm), stream));
-    pooled = (float*)(ws + W.xm); pooled_stride = d;
-  }
-  RUN(nv_head_fwd(pooled, pooled_stride, B, d, p + T.hg, p + T.hb, eps, p + T.hw, p + T.hbias, D.C, (float*)(ws + W.xh), (float*)(ws + W.hst),
-                  logits, stream));
-  return NV_OK;
+  return pool_head(D, T, p, eps, xin, ws, W.xm, W.xh, W.hst, logits, stream);
 }
 
 // ---- fp8 TRAINING forward (BASELINE.json configs[4] is quoted "fwd / fwd+bwd"): the forward of the train step with qkv / FC1 / FC2 of
@@ -662,14 +648,10 @@ extern "C" int nv_vit_forward_fp8(const nv_vit_config* cfg, int B, const float* 
 extern "C" int nv_vit_forward_fp8_train(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                                         const float* params, const void* params16, const void* params8, const float* colscales, const float* act_scales,
                                         void* workspace, long ws_bytes, float drop_p, float emb_drop_p, unsigned long drop_seed, float* logits, void* stream) {
-  Dims D; RUN(make_dims(cfg, B, D));
-  ParamTab T; make_params(D, T);
-  WS W; make_ws(D, 1, W);
+  Layout Y; RUN(make_layout(cfg, B, 1, Y));
+  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
   NV_CHECK_ARG(video && shape5 && strides5 && params && params16 && params8 && colscales && act_scales && workspace && logits, "nv_vit_forward_fp8_train: null pointer");
-  NV_CHECK_ARG(!(in && in->time_points > 0), "nv_vit_forward_fp8_train: the fused 4D input form is forward-only");
-  NV_CHECK_ARG(shape5[0] == B && shape5[1] == cfg->channels && shape5[2] == cfg->frames && shape5[3] == cfg->image_size && shape5[4] == img_w(cfg),
-               "nv_vit_forward_fp8_train: video is [%ld,%ld,%ld,%ld,%ld], the model was built for [%d,%d,%d,%d,%d] (B, channels, frames, height, width)",
-               shape5[0], shape5[1], shape5[2], shape5[3], shape5[4], B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg));
+  RUN(check_video("nv_vit_forward_fp8_train", cfg, B, shape5, in, false));
   NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_forward_fp8_train: workspace too small (%ld < %ld): the training layout is needed", ws_bytes, W.total);
   NV_CHECK_ARG(D.d % 128 == 0 && D.m % 128 == 0, "nv_vit_forward_fp8_train: dim and mlp_dim must be multiples of 128 (got %d, %d)", D.d, D.m);
   NV_CHECK_ARG(((uintptr_t)workspace & 255) == 0 && nv_aligned16(params) && nv_aligned16(params16) && nv_aligned16(params8), "nv_vit_forward_fp8_train: alignment");
@@ -682,17 +664,7 @@ extern "C" int nv_vit_forward_fp8_train(const nv_vit_config* cfg, int B, const f
   const int M = D.M, d = D.d;
   const long per = 3L * D.inner + D.m + 2L * D.d;
 
-  float* pst = (float*)(ws + W.pst);
-  RUN(patch_front(cfg, D, T, B, video, strides5, in, p, eps, ws + W.xp, pst, stream));
-  const void* wpe = p16 + T.pe_w;
-  if (D.P != D.Ppad) {
-    RUN(nv_cast_bf16_2d(p + T.pe_w, D.P, d, D.P, ws + W.wpe16, D.Ppad, stream));
-    wpe = ws + W.wpe16;
-  }
-  RUN(nv_gemm_bf16(0, 2, D.T, d, D.Ppad, ws + W.xp, D.Ppad, wpe, D.Ppad, ws + W.t, d, p + T.pe_bias, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-  float* est = (float*)(ws + W.est);
-  RUN(nv_embed_finish_fwd((float*)(ws + W.t), d, B, D.N, d, p + T.pe_g2, p + T.pe_b2, eps, p + T.pos, p + T.cls, (float*)(ws + W.x0), d, est,
-                          est + D.T, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
+  RUN(embed_front16(cfg, Y, B, video, strides5, in, p, p16, ws, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
   const float scale = 1.0f / sqrtf((float)D.dh);
   const float* xin = (float*)(ws + W.x0);
   const bool tail = cls_tail_wanted(D, 1, drop_p, in ? in->rows_form : 0);
@@ -712,11 +684,7 @@ extern "C" int nv_vit_forward_fp8_train(const nv_vit_config* cfg, int B, const f
     RUN(nv_gemm_f8(0, M, 3 * D.inner, d, x8, d, p8 + q.wqkv, d, ws + w.qkv, 3 * D.inner, cs, nullptr, nullptr, 0, 1.f, stream));
     RUN(nv_attn_fwd(ws + w.qkv, 3 * D.inner, B, D.n, D.heads, D.dh, scale, ws + w.ao, D.inner, (float*)(ws + w.lse), site_seed(drop_seed, 4 * l + 0), drop_p, stream));
     if (tail && l == D.L - 1) {       // the last block on its B cls rows: the bf16 weight-streaming kernels, as in nv_vit_forward_in
-      const long rs = D.n;
-      RUN(nv_skinny_nt(0, B, d, D.inner, ws + w.ao, D.inner * rs, p16 + q.wo, D.inner, p + q.bo, xin, d * rs, x1, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 1), proj_drop_p(cfg, drop_p), stream));
-      RUN(nv_ln_fwd(x1, d * rs, B, d, p + q.n2g, p + q.n2b, eps, ws + w.xn2, d * rs, st2, st2 + M, stream));
-      RUN(nv_skinny_nt(1, B, D.m, d, ws + w.xn2, d * rs, p16 + q.w1, d, p + q.b1, nullptr, 0, ws + w.h, D.m * rs, ws + w.u, D.m * rs, site_seed(drop_seed, 4 * l + 2), drop_p, stream));
-      RUN(nv_skinny_nt(0, B, d, D.m, ws + w.h, D.m * rs, p16 + q.w2, D.m, p + q.b2, x1, d * rs, x2, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 3), drop_p, stream));
+      RUN(cls_rows_block16(D, q, w, l, p, p16, ws, eps, xin, x1, x2, st2, ws + w.u, drop_seed, drop_p, proj_drop_p(cfg, drop_p), stream));
       xin = x2;
       continue;
     }
@@ -727,15 +695,7 @@ extern "C" int nv_vit_forward_fp8_train(const nv_vit_config* cfg, int B, const f
     RUN(nv_gemm_f8_resid_drop(M, d, D.m, h8, D.m, p8 + q.w2, D.m, x2, d, cs + 3L * D.inner + D.m, p + q.b2, x1, d, site_seed(drop_seed, 4 * l + 3), drop_p, stream));
     xin = x2;
   }
-  const float* pooled = xin;
-  long pooled_stride = (long)D.n * d;
-  if (D.pool_mean) {
-    RUN(nv_token_mean(xin, B, D.n, d, (float*)(ws + W.xm), stream));
-    pooled = (float*)(ws + W.xm); pooled_stride = d;
-  }
-  RUN(nv_head_fwd(pooled, pooled_stride, B, d, p + T.hg, p + T.hb, eps, p + T.hw, p + T.hbias, D.C, (float*)(ws + W.xh), (float*)(ws + W.hst),
-                  logits, stream));
-  return NV_OK;
+  return pool_head(D, T, p, eps, xin, ws, W.xm, W.xh, W.hst, logits, stream);
 }
 
 // Backward in stages so the caller can overlap the data-parallel gradient all-reduce with it:
@@ -755,7 +715,7 @@ extern "C" int nv_vit_backward_stages(const nv_vit_config* cfg, int B, const flo
 // GEMMs; fuse_mode 1 / 2: by those GEMMs themselves (nv_gemm_bf16_grouped_adamw).  Either rewrites the bf16 shadow of W_qkv, which
 // the layer's last data-gradient GEMM (dxn1 = dqkv W_qkv) reads: in these modes that GEMM is queued BEFORE the main stream signals
 // the auxiliary one.
-static int backward_impl(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+static int backward_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                          const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                          unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
@@ -765,7 +725,8 @@ extern "C" int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const f
                                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                                         int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form) {
-  return backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+  Layout Y; RUN(make_layout(cfg, B, 1, Y));
+  return backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
                        drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, nullptr);
 }
 
@@ -787,7 +748,8 @@ extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float
     NV_CHECK_ARG(!(drop_p > 0.f), "nv_vit_backward_attn: drop_p=%g - the attention-dropout mask is not replayed into the gradient of the probabilities; "
                  "export from a forward without dropout (eval mode)", (double)drop_p);
   }
-  return backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+  Layout Y; RUN(make_layout(cfg, B, 1, Y));
+  return backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
                        drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, opts, attn_grad);
 }
 
@@ -799,16 +761,14 @@ extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* 
                               drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, opts, nullptr);
 }
 
-static int backward_impl(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+static int backward_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                          const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                          unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
                          const nv_vit_backward_opts* opts, const nv_vit_attn_grad_export* attn_grad) {
-  Dims D; RUN(make_dims(cfg, B, D));
+  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
   NV_CHECK_ARG(!fuse || (!accumulate && !grads16 && fuse->grads == grads && first_stage <= 1 && last_stage == D.L + 1),
                "nv_vit_backward: the optimizer update during the backward pass needs accumulate = 0, no bf16 mirror, its own gradient arena and every stage in one call");
-  ParamTab T; make_params(D, T);
-  WS W; make_ws(D, 1, W);
   // opts (nv_vit_backward_ex): the input gradient, and the data-only form (weight_grads = 0: no gradient arena, nothing on [A])
   const bool wg = !opts || opts->weight_grads;
   float* const dvideo = opts ? opts->dvideo : nullptr;
@@ -1027,9 +987,7 @@ extern "C" int nv_vit_backward(const nv_vit_config* cfg, int B, const float* vid
 
 // Element range [begin, end) of the parameter / gradient arena that is FINAL once backward stage `stage` has run.
 // (stage 0: head; stage 1+k: layer depth-1-k - its FC2 bias was already written by the stage before; last stage: embedding.)
-extern "C" int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, long* begin, long* end) {
-  Dims D; RUN(make_dims(cfg, 1, D));
-  ParamTab T; make_params(D, T);
+static int stage_param_range(const Dims& D, const ParamTab& T, int stage, long* begin, long* end) {
   NV_CHECK_ARG(stage >= 0 && stage <= D.L + 1 && begin && end, "nv_vit_stage_param_range: bad stage %d", stage);
   if (stage == 0) { *begin = T.hg; *end = T.total; return NV_OK; }
   if (stage == D.L + 1) { *begin = 0; *end = T.layer[0].n1g; return NV_OK; }
@@ -1038,16 +996,20 @@ extern "C" int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, lon
   *end = (l + 1 < D.L) ? T.layer[l + 1].n1g : T.hg;
   return NV_OK;
 }
+extern "C" int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, long* begin, long* end) {
+  Dims D; RUN(make_dims(cfg, 1, D));
+  ParamTab T; make_params(D, T);
+  return stage_param_range(D, T, stage, begin, end);
+}
 
 // ---- data-parallel backward + update of nv_vit_train_step (nv_dp_plan): the backward pass in groups of stages; behind each group the
 // communication stream all-reduces the group's gradient range (RCCL, comm.cpp) - and, with update_per_bucket, applies AdamW to it -
 // while the main stream is already in the next group.  The same launches as the single-process step otherwise.
-static int dp_backward_update(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const nv_vit_input* in, float* params, void* params16,
+static int dp_backward_update(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* strides5, const nv_vit_input* in, float* params, void* params16,
                               float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes, const float* dlogits, const nv_train_hparams* hp,
                               const nv_dp_plan* dp, bool head_fused, float lscale, float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream,
                               void* aux_stream) {
-  Dims D; RUN(make_dims(cfg, B, D));
-  ParamTab T; make_params(D, T);
+  const Dims& D = Y.D; const ParamTab& T = Y.T;
   const int n_stages = D.L + 2, last_stage = D.L + 1;
   const int nb = dp->n_buckets < n_stages ? dp->n_buckets : n_stages;
   const bool forked = aux_stream && aux_stream != stream;
@@ -1084,12 +1046,12 @@ static int dp_backward_update(const nv_vit_config* cfg, int B, const float* vide
     const int first = (head_fused && s0 == 0) ? 1 : s0;                                  // (the fused head step has run stage 0 already)
     const bool joined = (s1 == last_stage);
     if (first <= s1)
-      RUN(nv_vit_backward_stages16(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, msg, hp->accumulate ? 1 : 0, first, s1, drop_p,
-                                   emb_drop_p, drop_seed, stream, aux_stream, joined ? 1 : 0, in ? in->rows_form : 0));
+      RUN(backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, msg, hp->accumulate ? 1 : 0, first, s1, drop_p,
+                        emb_drop_p, drop_seed, stream, aux_stream, joined ? 1 : 0, in ? in->rows_form : 0, nullptr, 0, nullptr));
     long begin = -1, end = -1;
     for (int s = s0; s <= s1; ++s) {
       long lo, hi;
-      RUN(nv_vit_stage_param_range(cfg, s, &lo, &hi));
+      RUN(stage_param_range(D, T, s, &lo, &hi));
       begin = (begin < 0 || lo < begin) ? lo : begin; end = hi > end ? hi : end;
     }
     RUN(stream_sync((hipStream_t)stream, (hipStream_t)C));                                  // the bucket's gradients: complete on the main stream ...
@@ -1156,11 +1118,10 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
   // the head's forward, the loss and the head's backward as two launches instead of five (nv_head_step: bit-identical to the three calls;
   // it needs num_classes <= dim and dim % 8 == 0 - other heads take the five-launch path, which has no such limit)
   const bool head_fused = g_head_step && !cfg->pool_mean && cfg->num_classes <= cfg->dim && cfg->dim % 8 == 0;
-  RUN(forward_in_impl(cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 1, drop_p, emb_drop_p, drop_seed, logits, stream, head_fused));
+  Layout Y; RUN(make_layout(cfg, B, 1, Y));          // one layout for the whole step: forward, head step, backward, update ranges
+  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
+  RUN(forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 1, drop_p, emb_drop_p, drop_seed, logits, stream, head_fused));
   if (head_fused) {
-    Dims D; RUN(make_dims(cfg, B, D));
-    ParamTab T; make_params(D, T);
-    WS W; make_ws(D, 1, W);
     char* ws = (char*)workspace;
     const int Ll = D.L - 1;
     RUN(nv_head_step_scaled((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
@@ -1175,12 +1136,12 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
   opt.weight_decay = hp->weight_decay; opt.grad_scale = hp->grad_scale / lscale; opt.keep_grads = hp->fuse_update == 2;
   opt.params = params; opt.grads = grads; opt.adam_m = adam_m; opt.adam_v = adam_v; opt.params16 = params16;
   if (dp && hp->update)
-    return dp_backward_update(cfg, B, video, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, dlogits, hp, dp, head_fused, lscale,
+    return dp_backward_update(Y, cfg, B, video, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, dlogits, hp, dp, head_fused, lscale,
                               drop_p, emb_drop_p, drop_seed, stream, aux_stream);
-  RUN(backward_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, nullptr, hp->accumulate ? 1 : 0, head_fused ? 1 : 0, cfg->depth + 1,
+  RUN(backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, nullptr, hp->accumulate ? 1 : 0, head_fused ? 1 : 0, cfg->depth + 1,
                     drop_p, emb_drop_p, drop_seed, stream, aux_stream, 1, in ? in->rows_form : 0, fused ? &opt : nullptr, hp->fuse_update, nullptr));
   if (hp->update && !fused) {
-    const long total = nv_vit_param_count(cfg);
+    const long total = T.total;
     if (hp->loss_scale_state) {      // GradScaler.step / .update (Trainer.py:75-76) on the device: any inf / NaN gradient skips the update and halves the scale
       RUN(nv_loss_scale_check(grads, total, hp->loss_scale_state, stream));
       RUN(nv_loss_scale_update(hp->loss_scale_state, hp->lr, hp->beta1, hp->beta2, stream));
@@ -1190,8 +1151,6 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
   } else if (fused) {
     // what was not updated during the backward pass: the arena minus the four Linear weights of every layer (arena order:
     // ... n1b | wqkv | wo | bo n2g n2b | w1 | b1 | w2 | b2 n1g' ...), one launch
-    Dims D; RUN(make_dims(cfg, B, D));
-    ParamTab T; make_params(D, T);
     std::vector<long> begins, lens;
     long cur = 0;
     auto skip = [&](long off, long numel) { if (off > cur) { begins.push_back(cur); lens.push_back(off - cur); } cur = align_up(off + numel, 8); };

@@ -64,6 +64,11 @@ def flops_forward(cfg: VitConfig) -> float:
     return 2.0 * N * P * d + cfg.depth * per_layer + 2 * d * cfg.num_classes
 
 
+def _inp_ptr(inp):
+    """the optional nv_vit_input argument of the forwards and the train step (`inp` must outlive the call)"""
+    return None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p)
+
+
 class _Pass:
     """One training-layout forward whose activations a backward may still read: its workspace, its input (the backward re-gathers
     the patches), the form of the last block, the dropout draw.  `done`: a whole backward has run - the workspace may be refilled."""
@@ -137,6 +142,23 @@ class VitRuntime:
         self._cur = rec
         return rec
 
+    def _buffers(self, B: int, layout, device):
+        """(workspace, logits) of a forward of B volumes.  layout as in workspace(); the training layout takes a workspace no pending pass needs."""
+        ws = self._training_workspace(B, device) if int(layout) == 1 else self.workspace(B, layout, device)
+        return ws, torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=device)
+
+    def _forward_done(self, B, layout, ws, video, form=None, dropout=(0.0, 0.0, 0)) -> None:
+        """What every forward records behind its C call.  form = (vol_sigma, inp, rows_form) on the 16-bit forwards: a backward re-gathers the
+        same (raw) input and takes the same form of the last block, and a replayed train step inherits both (note_step_replayed).  The fp32 and
+        the fp8 inference forwards pass none: nothing runs a backward against them, and they must not replace what a captured step recorded."""
+        if form is not None:
+            self._keep, self._rows_form, self._dropout = form[:2], form[2], dropout
+        self._last = (B, layout, ws, video)
+        if int(layout) == 1:
+            self._open_pass(B, ws, video, self._keep, self._rows_form, dropout)
+        self.generation += 1
+        self.backward_done = False
+
     def pass_is_live(self, rec: _Pass) -> bool:
         """the workspace still holds THIS pass's activations (no later forward or train step has refilled it)"""
         ref = self._holder.get(rec.ws.data_ptr())
@@ -208,21 +230,13 @@ class VitRuntime:
         rows_form = self.rows_form if rows_form is None else int(rows_form)
         _cabi.set_operand_format(self.operands)
         B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
-        ws = self._training_workspace(B, video.device) if training else self.workspace(B, training, video.device)
-        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
+        ws, logits = self._buffers(B, training, video.device)
         check(lib.nv_vit_forward_in(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                    None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p),
+                                    _inp_ptr(inp),
                                     params.data_ptr(), params16.data_ptr(), ws.data_ptr(), ws.numel(), int(training), float(dropout[0]),
                                  float(dropout[1]), int(dropout[2]), logits.data_ptr(),
                                  torch.cuda.current_stream().cuda_stream), "nv_vit_forward_in")
-        self._keep = (vol_sigma, inp)                    # the backward re-gathers the same (raw) input
-        self._rows_form = rows_form                      # ... and takes the same form of the last block
-        self._last = (B, training, ws, video)
-        if training:
-            self._open_pass(B, ws, video, self._keep, rows_form, dropout)
-        self.generation += 1
-        self.backward_done = False
-        self._dropout = dropout
+        self._forward_done(B, training, ws, video, (vol_sigma, inp, rows_form), dropout)
         return logits
 
     # ------------------------------------------------------------------ inference forward with the LayerNorms folded into the GEMMs around them
@@ -249,18 +263,12 @@ class VitRuntime:
         rows_form = self.rows_form if rows_form is None else int(rows_form)
         _cabi.set_operand_format(self.operands)
         B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
-        ws = self.workspace(B, False, video.device)
-        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
+        ws, logits = self._buffers(B, False, video.device)
         check(lib.nv_vit_forward_lnfold(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                        None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p), params.data_ptr(), params16.data_ptr(),
+                                        _inp_ptr(inp), params.data_ptr(), params16.data_ptr(),
                                         fold["fold16"].data_ptr(), fold["fold32"].data_ptr(), ws.data_ptr(), ws.numel(), logits.data_ptr(),
                                         torch.cuda.current_stream().cuda_stream), "nv_vit_forward_lnfold")
-        self._keep = (vol_sigma, inp)
-        self._rows_form = rows_form
-        self._last = (B, False, ws, video)
-        self.generation += 1
-        self.backward_done = False
-        self._dropout = (0.0, 0.0, 0)
+        self._forward_done(B, False, ws, video, (vol_sigma, inp, rows_form))
         return logits
 
     # ------------------------------------------------------------------ fp32 inference (the reference's fp32 validate, Trainer.py:101-118)
@@ -269,14 +277,11 @@ class VitRuntime:
         """Inference forward with every operand in fp32 (weights straight from the fp32 arena, contractions on the fp32 MFMA):
         logits within 1e-5 of the reference's CPU fp32 forward instead of the bf16 path's 1e-3 ... 7e-3.  Eval mode only."""
         B, inp = self._input_form(video, vol_sigma, time_points, self.rows_form, attn_export)
-        ws = self.workspace(B, 2, video.device)
-        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
+        ws, logits = self._buffers(B, 2, video.device)
         check(lib.nv_vit_forward_f32(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                     None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p), params.data_ptr(),
+                                     _inp_ptr(inp), params.data_ptr(),
                                      ws.data_ptr(), ws.numel(), logits.data_ptr(), torch.cuda.current_stream().cuda_stream), "nv_vit_forward_f32")
-        self._last = (B, 2, ws, video)          # 2 = fp32 inference layout (truthy as `training` only for the layout queries)
-        self.generation += 1
-        self.backward_done = False
+        self._forward_done(B, 2, ws, video)     # 2 = fp32 inference layout (truthy as `training` only for the layout queries)
         return logits
 
     # ------------------------------------------------------------------ fp8 inference (BASELINE.json configs[4])
@@ -324,35 +329,25 @@ class VitRuntime:
         rows_form = self.rows_form if rows_form is None else int(rows_form)
         _cabi.set_operand_format(self.operands)
         B, inp = self._input_form(video, vol_sigma, 0, rows_form)
-        ws = self._training_workspace(B, video.device)
-        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
+        ws, logits = self._buffers(B, True, video.device)
         check(lib.nv_vit_forward_fp8_train(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                           None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p), params.data_ptr(),
+                                           _inp_ptr(inp), params.data_ptr(),
                                            params16.data_ptr(), f8["params8"].data_ptr(), f8["colscales"].data_ptr(),
                                            ctypes.cast(f8["act_scales"], ctypes.c_void_p), ws.data_ptr(), ws.numel(), float(dropout[0]), float(dropout[1]), int(dropout[2]),
                                            logits.data_ptr(), torch.cuda.current_stream().cuda_stream), "nv_vit_forward_fp8_train")
-        self._keep = (vol_sigma, inp)
-        self._rows_form = rows_form
-        self._last = (B, True, ws, video)
-        self._open_pass(B, ws, video, self._keep, rows_form, dropout)
-        self.generation += 1
-        self.backward_done = False
-        self._dropout = dropout
+        self._forward_done(B, True, ws, video, (vol_sigma, inp, rows_form), dropout)
         return logits
 
     def forward_fp8(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, f8, vol_sigma=None, time_points: int = 0) -> torch.Tensor:
         _cabi.set_operand_format(self.operands)
         B, inp = self._input_form(video, vol_sigma, time_points, self.rows_form)
-        ws = self.workspace(B, False, video.device)
-        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=video.device)
+        ws, logits = self._buffers(B, False, video.device)
         check(lib.nv_vit_forward_fp8(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                     None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p), params.data_ptr(),
+                                     _inp_ptr(inp), params.data_ptr(),
                                      params16.data_ptr(), f8["params8"].data_ptr(), f8["colscales"].data_ptr(),
                                      ctypes.cast(f8["act_scales"], ctypes.c_void_p), ws.data_ptr(), ws.numel(), logits.data_ptr(),
                                      torch.cuda.current_stream().cuda_stream), "nv_vit_forward_fp8")
-        self._last = (B, False, ws, video)
-        self.generation += 1
-        self.backward_done = False
+        self._forward_done(B, False, ws, video)
         return logits
 
     def backward(self, dlogits: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: Optional[torch.Tensor],
@@ -441,7 +436,7 @@ class VitRuntime:
                           None if dp is None else ctypes.cast(ctypes.pointer(dp), ctypes.c_void_p),      # _cabi.DpPlan (kept alive by the caller)
                           None if loss_scale_state is None else loss_scale_state.data_ptr())
         check(lib.nv_vit_train_step(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                    None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p),
+                                    _inp_ptr(inp),
                                     params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr(),
                                     ws.data_ptr(), ws.numel(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(), dlogits.data_ptr(),
                                     ctypes.byref(hp), float(dropout[0]), float(dropout[1]), int(dropout[2]),

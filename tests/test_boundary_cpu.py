@@ -192,18 +192,40 @@ def test_device_prefetcher_preserves_order_and_passthrough():
 
 def test_nv_vit_forward_rejects_wrong_extents_before_touching_memory():
     """the gather kernel takes its extents from the config, so a volume of another size must be refused
-    (the reference raises in einops / the pos_embedding add, vit_3d.py:92,118).  Host-side check: runs without a GPU."""
+    (the reference raises in einops / the pos_embedding add, vit_3d.py:92,118).  Host-side check: runs without a GPU.
+    Every forward of the C ABI makes this check first - ahead of the workspace, `% 128`, alignment and export checks - so every other
+    argument below is a dummy that would fail one of those (or fault, if a launch were reached)."""
     from neurovit_amd import engine
-    from neurovit_amd._cabi import last_error, lib
-    cfg = engine.make_config(**W.MICRO)                      # 32^3 volumes, 1 channel
-    dummy = (ctypes.c_char * 64)()
-    ptr = ctypes.addressof(dummy)
-    for shape in ((2, 1, 16, 16, 16), (2, 3, 32, 32, 32), (2, 1, 33, 51, 33), (3, 1, 32, 32, 32)):
-        shp = (ctypes.c_long * 5)(*shape)
-        strides = (ctypes.c_long * 5)(1, 1, 1, 1, 1)
-        rc = lib.nv_vit_forward(ctypes.byref(cfg), 2, ptr, shp, strides, ptr, ptr, ptr, 1 << 40, 0, 0.0, 0.0, 0, ptr, None)
-        assert rc == -1, shape
-        assert "the model was built for" in last_error()
+    from neurovit_amd._cabi import VitInput, last_error, lib
+    cfg = engine.make_config(**W.MICRO)                      # 32^3 volumes, 1 channel; dim 128 / mlp_dim 256 pass the fp8 `% 128` check
+    c = ctypes.byref(cfg)
+    dummy = (ctypes.c_char * 80)()
+    ptr = (ctypes.addressof(dummy) + 15) & ~15               # (the fold arenas are checked for alignment before the extents)
+    strides = (ctypes.c_long * 5)(1, 1, 1, 1, 1)
+    big = 1 << 40
+    forwards = {           # name -> (prefix of its messages, call(B, shape5, in))
+        "nv_vit_forward": ("nv_vit_forward", lambda B, s, i: lib.nv_vit_forward(c, B, ptr, s, strides, ptr, ptr, ptr, big, 0, 0.0, 0.0, 0, ptr, None)),
+        "nv_vit_forward_in": ("nv_vit_forward", lambda B, s, i: lib.nv_vit_forward_in(c, B, ptr, s, strides, i, ptr, ptr, ptr, big, 0, 0.0, 0.0, 0, ptr, None)),
+        "nv_vit_forward_lnfold": ("nv_vit_forward", lambda B, s, i: lib.nv_vit_forward_lnfold(c, B, ptr, s, strides, i, ptr, ptr, ptr, ptr, ptr, big, ptr, None)),
+        "nv_vit_forward_f32": ("nv_vit_forward_f32", lambda B, s, i: lib.nv_vit_forward_f32(c, B, ptr, s, strides, i, ptr, ptr, big, ptr, None)),
+        "nv_vit_forward_fp8": ("nv_vit_forward_fp8", lambda B, s, i: lib.nv_vit_forward_fp8(c, B, ptr, s, strides, i, ptr, ptr, ptr, ptr, ptr, ptr, big, ptr, None)),
+        "nv_vit_forward_fp8_train": ("nv_vit_forward_fp8_train",
+                                     lambda B, s, i: lib.nv_vit_forward_fp8_train(c, B, ptr, s, strides, i, ptr, ptr, ptr, ptr, ptr, ptr, big, 0.0, 0.0, 0, ptr, None)),
+    }
+    for name, (who, call) in forwards.items():
+        for shape in ((2, 1, 16, 16, 16), (2, 3, 32, 32, 32), (2, 1, 33, 51, 33), (3, 1, 32, 32, 32)):
+            rc = call(2, (ctypes.c_long * 5)(*shape), None)
+            assert rc == -1, (name, shape)
+            assert last_error().startswith(who + ": video is") and "the model was built for" in last_error(), (name, shape, last_error())
+    # the 4D form [B / T, H, W, D, T] (nv_vit_input.time_points = 4; B = 8 volumes): wrong in the volume count, in one spatial extent, in T
+    inp = VitInput(None, 4, 0, None)
+    four_d = ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p)
+    for name in ("nv_vit_forward_in", "nv_vit_forward_lnfold", "nv_vit_forward_f32", "nv_vit_forward_fp8"):
+        who, call = forwards[name]
+        for shape in ((3, 32, 32, 32, 4), (2, 32, 16, 32, 4), (2, 32, 32, 32, 8)):
+            rc = call(8, (ctypes.c_long * 5)(*shape), four_d)
+            assert rc == -1, (name, shape)
+            assert last_error().startswith(who + ": 4D input is") and "expected [B/T" in last_error(), (name, shape, last_error())
 
 
 def test_flops_formula_in_package_equals_survey_numbers():
