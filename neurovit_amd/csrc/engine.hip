@@ -102,14 +102,20 @@ void make_params(const Dims& D, ParamTab& T) {
 
 // ---- workspace layout -------------------------------------------------------------------------------
 struct LayerW { long xn1, st1, qkv, lse, ao, x1, xn2, st2, u, h, x2; };
+// g16 / g16b: bf16 residual gradient entering the layer / after its LN2 backward; red, red2, red3: partials of the LN2 backward / scratch of the auxiliary
+// stream's column sums / partials of the LN1 backward (reduced one layer late); cs1: per-tile column sums of dU (bias gradient of FC1), <= M / 64 tile rows
+struct LayerScratch { long g16, g16b, du, dqkv, red, red2, red3, cs1; };
 struct WS {
   long xp, pst, t, est, x0, xh, hst, wpe16, xm;
   long fst1, fst2; // partial row statistics of the LayerNorm-folded inference forward (nv_gemm_resid_ln -> nv_gemm_lnfold): of a block's input / of x1
   long f8x, f8h;   // training layout: transient e4m3 operands of an fp8 training forward (LayerNorm output [M, d], GELU output [M, m])
   std::vector<LayerW> layer;
   // backward scratch
-  long g, g16, g16b, dxn, hookg, du, dao, dqkv, delta, dt, dt16, dxp, dwpe, red, red2, red3, cs1;
-  long alt[8];   // second copy (odd layers) of g16, g16b, du, dqkv, red, red2, red3, cs1: the auxiliary stream works one layer behind
+  long g, dxn, hookg, dao, delta, dt, dt16, dxp, dwpe;
+  // Buffers the auxiliary stream reads exist twice (even / odd layers): layer l's weight-gradient work runs while the main
+  // stream is already in layer l-1, which writes the other copy.
+  LayerScratch sc[2];
+  const LayerScratch& scratch(int l) const { return sc[l & 1]; }
   long red_bytes, red2_bytes, total;
 };
 
@@ -133,26 +139,27 @@ void make_ws(const Dims& D, int training, WS& W) {
   for (int l = nl; l < D.L; ++l) W.layer[l] = W.layer[0];
   W.f8x = W.f8h = -1;
   if (training) {
-    W.g = add(M * d * 4); W.g16 = add(M * d * 2); W.dxn = add(M * d * 4); W.hookg = add(M * d * 4); W.du = add(M * D.m * 2);
-    W.dao = add(M * D.inner * 2); W.dqkv = add(M * 3 * D.inner * 2); W.delta = add((long)D.B * D.heads * D.n * 4);
+    LayerScratch& e = W.sc[0]; LayerScratch& o = W.sc[1];     // even / odd layers
+    W.g = add(M * d * 4); e.g16 = add(M * d * 2); W.dxn = add(M * d * 4); W.hookg = add(M * d * 4); e.du = add(M * D.m * 2);
+    W.dao = add(M * D.inner * 2); e.dqkv = add(M * 3 * D.inner * 2); W.delta = add((long)D.B * D.heads * D.n * 4);
     W.dt = add(T * d * 4); W.dt16 = add(T * d * 2); W.dxp = add(T * D.Ppad * 4);
     W.dwpe = (D.P != D.Ppad) ? add(d * D.Ppad * 4) : -1;
     long r = nv_ln_bwd_workspace_bytes(D.M, D.d);
     const long r2 = nv_patch_ln_bwd_workspace_bytes(D.T, D.P), r3 = nv_head_step_workspace_bytes(D.B, D.d),
                r4 = nv_colsum_workspace_bytes(D.M, D.m);
     r = r > r2 ? r : r2; r = r > r3 ? r : r3; r = r > r4 ? r : r4;
-    W.red_bytes = r; W.red = add(r);
-    W.g16b = add(M * d * 2);
-    W.red2_bytes = r4 > r2 ? r4 : r2; W.red2 = add(W.red2_bytes);       // reduction scratch of the auxiliary stream (column sums, patch-LN backward)
-    W.red3 = add(nv_ln_bwd_workspace_bytes(D.M, D.d));   // LN1-backward partials (reduced on the auxiliary stream one layer late)
-    W.alt[0] = add(M * d * 2); W.alt[1] = add(M * d * 2); W.alt[2] = add(M * D.m * 2); W.alt[3] = add(M * 3 * D.inner * 2);
-    W.alt[4] = add(W.red_bytes); W.alt[5] = add(W.red2_bytes); W.alt[6] = add(nv_ln_bwd_workspace_bytes(D.M, D.d));
-    const long cs1_bytes = (long)((M + 63) / 64) * D.m * 4;          // per-tile column sums of dU (bias gradient of FC1), <= M / 64 tile rows
-    W.cs1 = add(cs1_bytes); W.alt[7] = add(cs1_bytes);
+    W.red_bytes = r; e.red = add(r);           // (the even copy also serves the head)
+    e.g16b = add(M * d * 2);
+    W.red2_bytes = r4 > r2 ? r4 : r2; e.red2 = add(W.red2_bytes);       // (the even copy also serves the patch-LN backward)
+    e.red3 = add(nv_ln_bwd_workspace_bytes(D.M, D.d));
+    o.g16 = add(M * d * 2); o.g16b = add(M * d * 2); o.du = add(M * D.m * 2); o.dqkv = add(M * 3 * D.inner * 2);
+    o.red = add(W.red_bytes); o.red2 = add(W.red2_bytes); o.red3 = add(nv_ln_bwd_workspace_bytes(D.M, D.d));
+    const long cs1_bytes = (long)((M + 63) / 64) * D.m * 4;
+    e.cs1 = add(cs1_bytes); o.cs1 = add(cs1_bytes);
     W.f8x = add(M * d); W.f8h = add(M * (long)D.m);
   } else {
-    W.g = W.g16 = W.dxn = W.hookg = W.du = W.dao = W.dqkv = W.delta = W.dt = W.dt16 = W.dxp = W.dwpe = W.red = W.g16b = W.red2 = W.red3 = W.cs1 = -1;
-    for (int i = 0; i < 8; ++i) W.alt[i] = -1;
+    W.g = W.dxn = W.hookg = W.dao = W.delta = W.dt = W.dt16 = W.dxp = W.dwpe = -1;
+    W.sc[0] = W.sc[1] = {-1, -1, -1, -1, -1, -1, -1, -1};
     W.red_bytes = W.red2_bytes = 0;
   }
   W.total = cur;
@@ -180,6 +187,9 @@ inline unsigned long site_seed(unsigned long seed, int site) { return seed ^ (0x
 // buffers the data-gradient chain has already produced, and the chain's kernels - 198-tile GEMMs, attention backward,
 // LayerNorm backward - leave LDS and CUs idle).  Events are pooled (created once, outside any capture).
 inline int stream_sync(hipStream_t from, hipStream_t to) { return nv_stream_sync((void*)from, (void*)to); }
+inline int event_failed(const char* what) { nv_set_error("nv_vit_backward: event %s failed", what); return NV_ERR_HIP; }
+inline int wait_event(hipStream_t s, hipEvent_t e) { return hipStreamWaitEvent(s, e, 0) == hipSuccess ? NV_OK : event_failed("wait"); }
+inline int record_event(hipEvent_t e, hipStream_t s) { return (e && hipEventRecord(e, s) == hipSuccess) ? NV_OK : event_failed("record"); }
 // deferred join: record a point on the auxiliary stream now, make the main stream wait for it later
 inline hipEvent_t deferred_event() {
   static std::vector<hipEvent_t> pool;
@@ -207,8 +217,8 @@ hipEvent_t carry_take(void* workspace) {                 // the pending dependen
 }
 int carry_record(void* workspace, hipStream_t on) {
   Carry& c = carry_map()[workspace];
-  if (!c.ev && hipEventCreateWithFlags(&c.ev, nv_sync_event_flags()) != hipSuccess) { nv_set_error("nv_vit_backward: event create failed"); return NV_ERR_HIP; }
-  if (hipEventRecord(c.ev, on) != hipSuccess) { nv_set_error("nv_vit_backward: event record failed"); return NV_ERR_HIP; }
+  if (!c.ev && hipEventCreateWithFlags(&c.ev, nv_sync_event_flags()) != hipSuccess) return event_failed("create");
+  if (const int rc = record_event(c.ev, on)) return rc;
   c.pending = true;
   return NV_OK;
 }
@@ -218,6 +228,13 @@ int carry_record(void* workspace, hipStream_t on) {
     const int rc__ = (call); \
     if (rc__) return rc__;   \
   } while (0)
+
+// The four Linear weights of a layer (to_qkv, to_out, FC1, FC2) as (arena offset, numel), in arena order: what the weight-gradient GEMMs
+// produce, mirror into a 16-bit message arena, and - in the fused train step - update.
+struct LinearW { long off[4], numel[4]; };
+inline LinearW linear_weights(const Dims& D, const LayerP& q) {
+  return {{q.wqkv, q.wo, q.w1, q.w2}, {3L * D.inner * D.d, (long)D.d * D.inner, (long)D.m * D.d, (long)D.d * D.m}};
+}
 
 // Everything a call derives from (config, B, layout): built once per C-ABI call (nv_vit_train_step: once per step) and handed down.
 struct Layout { Dims D; ParamTab T; WS W; };
@@ -274,7 +291,7 @@ extern "C" long nv_vit_workspace_offset(const nv_vit_config* cfg, int B, int tra
   }
   if (!strcmp(name, "xp")) return W.xp; if (!strcmp(name, "pst")) return W.pst; if (!strcmp(name, "t")) return W.t;
   if (!strcmp(name, "est")) return W.est; if (!strcmp(name, "x0")) return W.x0; if (!strcmp(name, "xh")) return W.xh;
-  if (!strcmp(name, "g")) return W.g; if (!strcmp(name, "hookg")) return W.hookg; if (!strcmp(name, "dqkv")) return W.dqkv;
+  if (!strcmp(name, "g")) return W.g; if (!strcmp(name, "hookg")) return W.hookg; if (!strcmp(name, "dqkv")) return W.sc[0].dqkv;
   if (!strcmp(name, "dt")) return W.dt; if (!strcmp(name, "dxp")) return W.dxp;
   return -1;
 }
@@ -698,10 +715,263 @@ extern "C" int nv_vit_forward_fp8_train(const nv_vit_config* cfg, int B, const f
   return pool_head(D, T, p, eps, xin, ws, W.xm, W.xh, W.hst, logits, stream);
 }
 
-// Backward in stages so the caller can overlap the data-parallel gradient all-reduce with it:
+// ---- backward ----------------------------------------------------------------------------------------------
+// In stages so the caller can overlap the data-parallel gradient all-reduce with it:
 //   stage 0 = classification head, stage 1+k = transformer layer (depth-1-k), stage depth+1 = patch embedding.
 // Stages must be run in increasing order over [0, depth+1]; the running residual gradient lives in the workspace.
 // When stage s has run, the gradient-arena range of its parameters is final (see nv_vit_stage_param_range).
+namespace {
+
+// Every per-call argument of a backward: the C entry points fill one, nv_vit_train_step one per step.
+struct BwdCall {
+  const float* video; const long* strides5; const float* params; const void* params16; void* workspace; long ws_bytes; const float* dlogits;
+  float* grads; void* grads16;                      // grads16: optional bf16 mirror of the Linear weight gradients (data-parallel messages)
+  int accumulate, first_stage, last_stage; float drop_p, emb_drop_p; unsigned long drop_seed; void* stream; void* aux_stream; int join_aux, rows_form;
+  const nv_adamw_arena* fuse; int fuse_mode;        // nv_vit_train_step, fuse_update (see backward_impl)
+  const nv_vit_backward_opts* opts;                 // nv_vit_backward_ex: the input gradient, and the data-only form (weight_grads = 0: no gradient arena, nothing on [A])
+  const nv_vit_attn_grad_export* attn_grad;
+};
+
+// Last block in the cls-rows form (see g_cls_tail): the residual gradient is zero outside the B cls rows until the attention
+// backward mixes the rows, so dU, dxn2, the LN2 backward, dAO and three of the four weight gradients are products of B rows
+struct BwdLayer { int l; bool tail; int Mr; long rs; };      // Mr: rows that carry a gradient; row r of the small problem is row r * rs of the buffers
+
+// The stages of one backward call, over what they share: the call, its layout, and what is derived from both once.  A stage goes to the
+// main stream S unless it is marked [A]: those go to the weight-gradient stream A (== S: fully serial; always in the data-only form).
+// Every parameter-gradient reduction of a layer goes into ONE nv_reduce_multi launch on [A]: the LayerNorm backwards take NV_LN_NO_REDUCE.
+struct Bwd {
+  const nv_vit_config* cfg; const BwdCall& c; const Dims& D; const ParamTab& T; const WS& W;
+  char* ws; const float* p; const r16* p16; float* g;      // g: the running fp32 residual gradient
+  bool wg, tail_fwd;         // parameter gradients wanted (false: the data-only form); the form the (training) forward took, given the same arguments
+  int M, d, acc, du_tile_rows;   // du_tile_rows: rows of the GEMM tile that will compute dU: > 0 when the fused column-sum epilogue (bias gradient of FC1) is available
+  float scale;
+  hipStream_t S, A;
+  float* GR(long off) const { return c.grads ? c.grads + off : nullptr; }   // (data-only: no arena, every parameter-gradient output NULL)
+  void* M16(long off) const { return c.grads16 ? (void*)((r16*)c.grads16 + off) : nullptr; }
+  float* dxn1(int l) const { return (float*)(ws + (l == D.L - 1 ? W.hookg : W.dxn)); }   // gradient of the last block's attention-LN output is kept (Grad-CAM hook)
+
+  // head: writes g (zeros + cls rows) and the last layer's FC2 bias gradient (colsum of g)
+  int bwd_head() const {
+    const float* xlast = (float*)(ws + W.layer[D.L - 1].x2);
+    return nv_head_bwd(c.dlogits, D.B, D.C, p + T.hw, D.pool_mean ? (const float*)(ws + W.xm) : xlast, D.pool_mean ? (long)d : (long)D.n * d,
+                       (float*)(ws + W.hst), (float*)(ws + W.xh), p + T.hg, d, D.n, g, d, ws + W.scratch(D.L - 1).g16, d,
+                       GR(T.hg), GR(T.hb), GR(T.hw), GR(T.hbias), GR(T.layer[D.L - 1].b2), acc, ws + W.sc[0].red, W.red_bytes,
+                       site_seed(c.drop_seed, 4 * (D.L - 1) + 3), c.drop_p, D.pool_mean, S);
+  }
+
+  // FeedForward backward (vit_3d.py:16-26) and the LN2 backward behind it
+  int bwd_ffn(const BwdLayer& R) const {
+    const int l = R.l; const long rs = R.rs;
+    const LayerP& q = T.layer[l]; const LayerW& w = W.layer[l]; const LayerScratch& sc = W.scratch(l);
+    float* dxn = (float*)(ws + W.dxn); float* st2 = (float*)(ws + w.st2);
+    void* g16 = ws + sc.g16; void* du = ws + sc.du;
+    if (R.tail) {
+      RUN(nv_skinny_nn(0, D.B, D.m, d, g16, d * rs, p16 + q.w2, D.m, ws + w.u, D.m * rs, du, D.m * rs, GR(q.b1), acc, site_seed(c.drop_seed, 4 * l + 2), c.drop_p, S));   // dU = (g W2 * mask) * gelu'(u), db1 = column sums
+      RUN(nv_skinny_nn(1, D.B, d, D.m, du, D.m * rs, p16 + q.w1, d, nullptr, 0, dxn, d * rs, nullptr, 0, 0, 0.f, S));             // dxn2 = dU W1
+    } else {
+      RUN(nv_gemm_bf16(1, du_tile_rows ? 6 : 5, M, D.m, d, g16, d, p16 + q.w2, D.m, du, D.m, nullptr, ws + w.u, D.m, du_tile_rows ? (float*)(ws + sc.cs1) : nullptr, D.m, 0, 1.f,
+                       site_seed(c.drop_seed, 4 * l + 2), c.drop_p, S));   // dU = (g W2 * mask) * gelu'(u)  [+ per-tile column sums -> db1]
+      RUN(nv_gemm_bf16(1, 1, M, d, D.m, du, D.m, p16 + q.w1, d, dxn, d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, S));                        // dxn2 = dU W1
+    }
+    return nv_ln_bwd(dxn, d * rs, (float*)(ws + w.x1), d * rs, st2, st2 + M, p + q.n2g, R.Mr, d, g, g, d * rs, ws + sc.g16b, d * rs, GR(q.n2g), GR(q.n2b), GR(q.bo), acc, ws + sc.red,
+                     W.red_bytes, site_seed(c.drop_seed, 4 * l + 1), proj_drop_p(cfg, c.drop_p), S, NV_LN_NO_REDUCE);                                 // g += dLN2 -> g16b
+  }
+
+  // Attention backward (vit_3d.py:48-60): dAO, dqkv, and the exported gradient of the probabilities
+  int bwd_attn(const BwdLayer& R) const {
+    const int l = R.l;
+    const LayerP& q = T.layer[l]; const LayerW& w = W.layer[l]; const LayerScratch& sc = W.scratch(l);
+    if (R.tail)
+      RUN(nv_skinny_nn_sparse(D.B, D.inner, d, ws + sc.g16b, d * R.rs, p16 + q.wo, D.inner, ws + W.dao, M, D.n, S));                       // dAO = g Wo on the cls rows, zeros elsewhere
+    else
+      RUN(nv_gemm_bf16(1, 0, M, D.inner, d, ws + sc.g16b, d, p16 + q.wo, D.inner, ws + W.dao, D.inner, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, S));  // dAO = g Wo
+    RUN(nv_attn_bwd(ws + w.qkv, 3 * D.inner, ws + w.ao, ws + W.dao, D.inner, (float*)(ws + w.lse), D.B, D.n, D.heads, D.dh, scale,
+                    (float*)(ws + W.delta), ws + sc.dqkv, 3 * D.inner, site_seed(c.drop_seed, 4 * l + 0), c.drop_p, S));
+    if (c.attn_grad && c.attn_grad->maps[l])     // dP (or the relevance term) of this layer: dAO and qkv still hold its values
+      RUN(nv_attn_grad(ws + w.qkv, 3 * D.inner, ws + W.dao, D.inner, D.B, D.n, D.heads, D.dh, scale, c.attn_grad->form, c.attn_grad->maps[l], S));
+    return NV_OK;
+  }
+
+  // dxn1 = dqkv W_qkv: the last reader of the layer's bf16 W_qkv
+  int bwd_dxn1(int l) const {
+    return nv_gemm_bf16(1, 1, M, d, 3 * D.inner, ws + W.scratch(l).dqkv, 3 * D.inner, p16 + T.layer[l].wqkv, d, dxn1(l), d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, S);
+  }
+
+  // LN1 backward: g += dLN1, and the bf16 residual gradient entering layer l-1 - into THAT layer's copy of the doubled buffers
+  int bwd_ln1(int l) const {
+    const LayerP& q = T.layer[l];
+    const float* xin = (l == 0) ? (float*)(ws + W.x0) : (float*)(ws + W.layer[l - 1].x2);
+    float* st1 = (float*)(ws + W.layer[l].st1);
+    return nv_ln_bwd(dxn1(l), d, xin, d, st1, st1 + M, p + q.n1g, M, d, g, g, d, ws + W.scratch(l - 1).g16, d, GR(q.n1g), GR(q.n1b), (l > 0) ? GR(T.layer[l - 1].b2) : nullptr,
+                     acc, ws + W.scratch(l).red3, nv_ln_bwd_workspace_bytes(M, d), site_seed(c.drop_seed, 4 * (l - 1) + 3), (l > 0) ? c.drop_p : 0.f, S, NV_LN_NO_REDUCE);
+  }
+
+  // [A] reduction of layer lp's LN1-backward partials, where no later layer's nv_reduce_multi takes it along
+  int bwd_reduce_ln1(int lp) const {
+    const LayerP& qp = T.layer[lp];
+    return nv_ln_bwd_reduce(ws + W.scratch(lp).red3, M, d, GR(qp.n1g), GR(qp.n1b), (lp > 0) ? GR(T.layer[lp - 1].b2) : nullptr, acc, A);
+  }
+
+  // [A] fuse_mode 3: AdamW over the four Linear weights of layer lu (W_qkv and W_o are neighbours in the arena: one range)
+  int bwd_layer_update(int lu) const {
+    const LinearW lw = linear_weights(D, T.layer[lu]);
+    const long b[3] = {lw.off[0], lw.off[2], lw.off[3]};
+    const long n[3] = {align_up(lw.numel[0], 8) + lw.numel[1], lw.numel[2], lw.numel[3]};
+    return nv_adamw_ranges(c.fuse, b, n, 3, A);
+  }
+
+  // [A] everything of a layer that only finishes parameter gradients.  ln1_of: the layer above when its LN1 partials still wait (else -1)
+  int bwd_layer_params(const BwdLayer& R, int ln1_of) const {
+    const int l = R.l, Mr = R.Mr; const long rs = R.rs;
+    const LayerP& q = T.layer[l]; const LayerW& w = W.layer[l]; const LayerScratch& sc = W.scratch(l);
+    void* g16 = ws + sc.g16; void* g16b = ws + sc.g16b; void* du = ws + sc.du; void* dqkv = ws + sc.dqkv;
+    // ONE launch for every small parameter gradient that is final by now: db1 (column sums of dU), dLN2 affine + dbo
+    // (= colsum(g)), and dLN1 affine + db2 of the layer above (whose partials were written after that layer's block ran)
+    nv_reduce_job jobs[3];
+    int nj = 0;
+    if (R.tail) {}                                                  // db1 came out of the dU kernel
+    else if (du_tile_rows) jobs[nj++] = {(float*)(ws + sc.cs1), (M + du_tile_rows - 1) / du_tile_rows, D.m, 1, {GR(q.b1), nullptr, nullptr}, acc};
+    else RUN(nv_colsum_bf16(du, D.m, M, D.m, GR(q.b1), acc, ws + sc.red2, W.red2_bytes, A));
+    jobs[nj++] = {(const float*)(ws + sc.red), nv_ln_bwd_partial_rows(Mr), d, 3, {GR(q.n2g), GR(q.n2b), GR(q.bo)}, acc};
+    if (ln1_of >= 0) {
+      const LayerP& qp = T.layer[ln1_of];
+      jobs[nj++] = {(const float*)(ws + W.scratch(ln1_of).red3), nv_ln_bwd_partial_rows(M), d, 3, {GR(qp.n1g), GR(qp.n1b), (ln1_of > 0) ? GR(T.layer[ln1_of - 1].b2) : nullptr}, acc};
+    }
+    RUN(nv_reduce_multi(jobs, nj, A));
+    // the four weight gradients of the layer in ONE grouped launch (864 tiles keep two workgroups resident on every CU;
+    // launched one by one their 72-288 tiles leave the CUs half empty and latency bound)
+    nv_gemm_problem pr[4];
+    pr[0] = {d, D.m, Mr, g16, d * rs, ws + w.h, D.m * rs, GR(q.w2), D.m, acc, M16(q.w2), D.m};                     // dW2 = g^T h
+    pr[1] = {D.m, d, Mr, du, D.m * rs, ws + w.xn2, d * rs, GR(q.w1), d, acc, M16(q.w1), d};                        // dW1 = dU^T xn2
+    pr[2] = {d, D.inner, Mr, g16b, d * rs, ws + w.ao, D.inner * rs, GR(q.wo), D.inner, acc, M16(q.wo), D.inner};   // dWo = g^T ao
+    pr[3] = {3 * D.inner, d, M, dqkv, 3 * D.inner, ws + w.xn1, d, GR(q.wqkv), d, acc, M16(q.wqkv), d};  // dWqkv = dqkv^T xn1
+    if (c.fuse && c.fuse_mode != 3) return nv_gemm_bf16_grouped_adamw(4, pr, c.fuse, A);      // fuse_mode 1 / 2: the GEMMs update the weights themselves
+    return nv_gemm_bf16_grouped(2, 1, 4, pr, A);     // (fuse_mode 3: gradients stored as ever; the layer's update follows as a launch of its own, one signal later)
+  }
+
+  // Patch embedding backward (vit_3d.py:91-96,116-118), main-stream front: LayerNorm(d) / position / cls gradients, dt and its bf16 copy.
+  // Its reduction scratch is the odd copy, which the auxiliary stream released before the main stream was allowed into layer 0's LN1 backward.
+  int bwd_embed_tokens() const {
+    float* est = (float*)(ws + W.est);
+    return nv_embed_finish_bwd(g, d, (float*)(ws + W.t), d, est, est + D.T, p + T.pe_g2, D.B, D.N, d, (float*)(ws + W.dt), d, ws + W.dt16, d, GR(T.pe_g2),
+                               GR(T.pe_b2), GR(T.pe_bias), GR(T.pos), GR(T.cls), acc, ws + W.sc[1].red, W.red_bytes, site_seed(c.drop_seed, 4 * D.L), c.emb_drop_p, S);
+  }
+
+  // ... and the rest: [A] gradient of the patch LayerNorm's affine parameters (needs dxp = dt Wpe and a second gather of the volume) and the
+  // input gradient; the main stream meanwhile produces the patch-embedding weight gradient
+  int bwd_embed() const {
+    float* pst = (float*)(ws + W.pst);
+    float* const dvideo = c.opts ? c.opts->dvideo : nullptr;
+    // patch_dim not a multiple of 8 (reference default 90^3 / p 9 -> P = 729): operands are zero padded to Ppad columns;
+    // the weight gradient is produced in a padded scratch matrix and its valid columns copied / added into the arena.
+    const void* wpe = (D.P != D.Ppad) ? (const void*)(ws + W.wpe16) : (const void*)(p16 + T.pe_w);
+    void* redA = ws + (A != S ? W.sc[0].red2 : W.sc[0].red);
+    const long redA_bytes = A != S ? W.red2_bytes : W.red_bytes;
+    RUN(nv_gemm_bf16(1, 1, D.T, D.Ppad, d, ws + W.dt16, d, wpe, D.Ppad, ws + W.dxp, D.Ppad, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, A));              // [A] dxp = dt Wpe
+    if (dvideo)       // [A] the gradient w.r.t. the input volume: LayerNorm(P) backward w.r.t. its input, scattered into voxel layout
+      RUN(nv_patch_ln_dx(c.video, c.strides5, D.B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size, pat_w(cfg), cfg->frame_patch_size,
+                         (const float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, p + T.pe_g, dvideo, c.opts->dvideo_strides5, A));
+    if (!wg) return NV_OK;      // data-only: serial, nothing more
+    RUN(nv_patch_ln_bwd(c.video, c.strides5, D.B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size,
+                        pat_w(cfg), cfg->frame_patch_size, (float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, GR(T.pe_g), GR(T.pe_b), acc, redA, redA_bytes, A));   // [A]
+    if (D.P != D.Ppad) {
+      RUN(nv_gemm_bf16(2, 1, d, D.Ppad, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, ws + W.dwpe, D.Ppad, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, S));
+      return nv_copy_2d_f32((float*)(ws + W.dwpe), D.Ppad, d, D.P, GR(T.pe_w), D.P, acc, S);
+    }
+    return nv_gemm_bf16(2, 1, d, D.P, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, GR(T.pe_w), D.P, nullptr, nullptr, 0, M16(T.pe_w), D.P, acc, 1.f, 0, 0.f, S);   // dWpe = dt^T xp
+  }
+};
+
+}  // namespace
+
+// The argument checks and the protocol between the main stream [S] and the auxiliary stream [A]: the stages above say what is launched, this says where and when.
+// fuse != null (nv_vit_train_step, fuse_update): the four Linear weights of every layer are updated on the auxiliary stream while the
+// backward pass is still running - fuse_mode 3: by an AdamW launch over those weights queued behind the layer's weight-gradient
+// GEMMs; fuse_mode 1 / 2: by those GEMMs themselves (nv_gemm_bf16_grouped_adamw).  Either rewrites the bf16 shadow of W_qkv, which
+// the layer's last data-gradient GEMM (dxn1 = dqkv W_qkv) reads: in these modes that GEMM is queued BEFORE the main stream signals
+// the auxiliary one.
+static int backward_impl(const Layout& Y, const nv_vit_config* cfg, const BwdCall& c) {
+  const Dims& D = Y.D; const WS& W = Y.W;
+  const nv_adamw_arena* fuse = c.fuse; const nv_vit_backward_opts* opts = c.opts;
+  NV_CHECK_ARG(!fuse || (!c.accumulate && !c.grads16 && fuse->grads == c.grads && c.first_stage <= 1 && c.last_stage == D.L + 1),
+               "nv_vit_backward: the optimizer update during the backward pass needs accumulate = 0, no bf16 mirror, its own gradient arena and every stage in one call");
+  const bool wg = !opts || opts->weight_grads;
+  NV_CHECK_ARG(!fuse || !opts, "nv_vit_backward: the optimizer update during the backward pass takes no input gradient / data-only options");
+  NV_CHECK_ARG(!fuse || !c.attn_grad, "nv_vit_backward: the optimizer update during the backward pass exports no attention gradients");
+  NV_CHECK_ARG(!opts || !opts->dvideo || opts->dvideo_strides5, "nv_vit_backward_ex: dvideo needs dvideo_strides5");
+  NV_CHECK_ARG(wg || (!c.grads && !c.grads16), "nv_vit_backward_ex: the data-only backward (weight_grads = 0) writes no gradient arena - pass grads = grads16 = NULL");
+  NV_CHECK_ARG(c.video && c.strides5 && c.params && c.params16 && c.workspace && c.dlogits && (c.grads || !wg), "nv_vit_backward: null pointer");
+  NV_CHECK_ARG(c.ws_bytes >= W.total, "nv_vit_backward: workspace too small (%ld < %ld) - forward must run with training=1", c.ws_bytes, W.total);
+  NV_CHECK_ARG(nv_aligned16(c.grads) && nv_aligned16(c.grads16), "nv_vit_backward: grads / grads16 must be 16-byte aligned");
+  NV_CHECK_ARG(c.first_stage >= 0 && c.last_stage <= D.L + 1 && c.first_stage <= c.last_stage, "nv_vit_backward_stages: bad stage range [%d, %d]", c.first_stage, c.last_stage);
+  hipStream_t S = (hipStream_t)c.stream;
+  hipStream_t A = (c.aux_stream && wg) ? (hipStream_t)c.aux_stream : S;
+  const bool forked = (A != S);
+  char* ws = (char*)c.workspace;
+  const Bwd X{cfg, c, D, Y.T, W, ws, c.params, (const r16*)c.params16, (float*)(ws + W.g), wg, cls_tail_wanted(D, 1, c.drop_p, c.rows_form), D.M, D.d, c.accumulate,
+              nv_gemm_tile_rows(1, D.M, D.m, D.d, D.d, D.m), 1.0f / sqrtf((float)D.dh), S, A};
+  // (no S -> A ordering here: everything the auxiliary stream does in this call is queued behind a signal of the main stream below)
+  if (c.first_stage == 0) RUN(X.bwd_head());
+
+  // One cross-stream event per layer in each direction (an event record costs several microseconds of queue time): the main
+  // stream signals once, after the attention backward; the auxiliary stream then runs, one layer behind the main stream,
+  // [db1 column sum, LN2 reduction, LN1 reduction of the layer above, grouped weight-gradient GEMMs] and signals back once.
+  hipEvent_t prev_done = carry_take(c.workspace);   // everything the previous (higher) layer queued on [A] - in the previous, unjoined call
+  if (!wg && prev_done) { RUN(wait_event(S, prev_done)); prev_done = nullptr; }   // data-only: serial, so the main stream takes that dependency up front
+  bool layers_here = false;
+  int pending_ln1 = -1;               // layer whose LN1-backward partials still wait for their reduction
+  int pending_adam = -1;              // fuse_mode 3: layer whose weights are updated at the NEXT signal - the main stream orders a layer's dxn1 GEMM (last
+                                      // reader of its bf16 weights) behind the signal of that layer, so the update waits for the one after it
+  const bool dxn1_first = fuse && c.fuse_mode != 3;    // the last reader of a layer's bf16 weights goes ahead of the launch that rewrites them (see above)
+  for (int l = D.L - 1; l >= 0; --l) {
+    const int stage = D.L - l;
+    if (stage < c.first_stage || stage > c.last_stage) continue;
+    const bool tail = X.tail_fwd && l == D.L - 1;
+    const BwdLayer R{l, tail, tail ? D.B : D.M, tail ? (long)D.n : 1};
+    RUN(X.bwd_ffn(R));                                                           // [S]
+    RUN(X.bwd_attn(R));                                                          // [S]
+    if (dxn1_first) RUN(X.bwd_dxn1(l));                                          // [S]
+    if (forked) RUN(stream_sync(S, A));                                           // S -> A: dU, g16b, dqkv (and the LN partials) ready
+    if (pending_adam >= 0) { RUN(X.bwd_layer_update(pending_adam)); pending_adam = -1; }   // [A] the layer above, whose last reader (its dxn1 GEMM) ran before this signal
+    if (wg) {
+      RUN(X.bwd_layer_params(R, pending_ln1));                                   // [A]
+      pending_ln1 = -1;
+      if (fuse && c.fuse_mode == 3) pending_adam = l;
+    }
+    hipEvent_t done = nullptr;
+    if (forked) { done = deferred_event(); RUN(record_event(done, A)); }          // A -> S, waited for one layer later
+    if (!dxn1_first) RUN(X.bwd_dxn1(l));                                         // [S]
+    // LN1 backward writes the residual gradient of layer l-1 into the buffer copy layer l+1 used (and layer l-1 then rewrites
+    // the rest of that copy): the auxiliary work of layer l+1 - a whole layer behind by now - must have finished with it.
+    if (forked && prev_done) RUN(wait_event(S, prev_done));
+    RUN(X.bwd_ln1(l));                                                           // [S]
+    pending_ln1 = wg ? l : -1;
+    prev_done = done;
+    layers_here = true;
+  }
+  if (c.last_stage < D.L + 1) {
+    if (pending_ln1 >= 0) { if (forked) RUN(stream_sync(S, A)); RUN(X.bwd_reduce_ln1(pending_ln1)); }
+    if (forked) {
+      if (c.join_aux) {
+        RUN(stream_sync(A, S));   // every gradient written on [A] (weight GEMMs, reductions) is ordered before what follows on the main stream
+      } else {                    // the caller orders the consumer of this range after BOTH streams; the next call inherits the dependency
+        RUN(carry_record(c.workspace, A));
+      }
+    }
+    return NV_OK;
+  }
+  // a call that starts at the embedding stage behind an unjoined call: its scratch may still be in use over there
+  if (forked && !layers_here && prev_done) RUN(wait_event(S, prev_done));
+  // The main stream does NOT join the auxiliary one first: layer 0's grouped weight gradients keep running beside the embedding stage.
+  RUN(X.bwd_embed_tokens());                                                       // [S]
+  if (forked) RUN(stream_sync(S, A));                                             // S -> A: dt16 and layer 0's LN1 partials ready
+  if (pending_ln1 >= 0) RUN(X.bwd_reduce_ln1(pending_ln1));                      // [A]
+  if (pending_adam >= 0) RUN(X.bwd_layer_update(pending_adam));                  // [A] layer 0's weights
+  RUN(X.bwd_embed());                                                              // [A] and [S]
+  if (forked) RUN(stream_sync(A, S));                                             // the final join (data-only: serial, nothing to join)
+  return NV_OK;
+}
+
 extern "C" int nv_vit_backward_stages(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                                       const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads,
                                       int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
@@ -710,28 +980,17 @@ extern "C" int nv_vit_backward_stages(const nv_vit_config* cfg, int B, const flo
                                   last_stage, drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, 0);
 }
 
-// fuse != null (nv_vit_train_step, fuse_update): the four Linear weights of every layer are updated on the auxiliary stream while the
-// backward pass is still running - fuse_mode 3: by an AdamW launch over those weights queued behind the layer's weight-gradient
-// GEMMs; fuse_mode 1 / 2: by those GEMMs themselves (nv_gemm_bf16_grouped_adamw).  Either rewrites the bf16 shadow of W_qkv, which
-// the layer's last data-gradient GEMM (dxn1 = dqkv W_qkv) reads: in these modes that GEMM is queued BEFORE the main stream signals
-// the auxiliary one.
-static int backward_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
-                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
-                         int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
-                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
-                         const nv_vit_backward_opts* opts, const nv_vit_attn_grad_export* attn_grad = nullptr);
-
 extern "C" int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                                         int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form) {
-  Layout Y; RUN(make_layout(cfg, B, 1, Y));
-  return backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
-                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, nullptr);
+  return nv_vit_backward_attn(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+                              drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, nullptr);
 }
 
 // Export of the gradient w.r.t. the attention probabilities (nv_vit_attn_grad_export): nv_attn_grad queued right behind a layer's
-// attention backward, while dAO and the layer's qkv still hold its values.  attn_grad = NULL: exactly the launches of nv_vit_backward_ex.
+// attention backward, while dAO and the layer's qkv still hold its values.  attn_grad = NULL: exactly the launches of nv_vit_backward_ex;
+// opts = NULL as well: exactly those of nv_vit_backward_stages16.
 extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
                                     const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
                                     int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
@@ -749,8 +1008,12 @@ extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float
                  "export from a forward without dropout (eval mode)", (double)drop_p);
   }
   Layout Y; RUN(make_layout(cfg, B, 1, Y));
-  return backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
-                       drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, nullptr, 0, opts, attn_grad);
+  BwdCall c{};
+  c.video = video; c.strides5 = strides5; c.params = params; c.params16 = params16; c.workspace = workspace; c.ws_bytes = ws_bytes;
+  c.dlogits = dlogits; c.grads = grads; c.grads16 = grads16; c.accumulate = accumulate; c.first_stage = first_stage; c.last_stage = last_stage;
+  c.drop_p = drop_p; c.emb_drop_p = emb_drop_p; c.drop_seed = drop_seed; c.stream = stream; c.aux_stream = aux_stream;
+  c.join_aux = join_aux; c.rows_form = rows_form; c.opts = opts; c.attn_grad = attn_grad;
+  return backward_impl(Y, cfg, c);
 }
 
 extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
@@ -759,223 +1022,6 @@ extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* 
                                   unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts) {
   return nv_vit_backward_attn(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
                               drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, opts, nullptr);
-}
-
-static int backward_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
-                         const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
-                         int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
-                         unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_adamw_arena* fuse, int fuse_mode,
-                         const nv_vit_backward_opts* opts, const nv_vit_attn_grad_export* attn_grad) {
-  const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
-  NV_CHECK_ARG(!fuse || (!accumulate && !grads16 && fuse->grads == grads && first_stage <= 1 && last_stage == D.L + 1),
-               "nv_vit_backward: the optimizer update during the backward pass needs accumulate = 0, no bf16 mirror, its own gradient arena and every stage in one call");
-  // opts (nv_vit_backward_ex): the input gradient, and the data-only form (weight_grads = 0: no gradient arena, nothing on [A])
-  const bool wg = !opts || opts->weight_grads;
-  float* const dvideo = opts ? opts->dvideo : nullptr;
-  NV_CHECK_ARG(!fuse || !opts, "nv_vit_backward: the optimizer update during the backward pass takes no input gradient / data-only options");
-  NV_CHECK_ARG(!fuse || !attn_grad, "nv_vit_backward: the optimizer update during the backward pass exports no attention gradients");
-  NV_CHECK_ARG(!dvideo || opts->dvideo_strides5, "nv_vit_backward_ex: dvideo needs dvideo_strides5");
-  NV_CHECK_ARG(wg || (!grads && !grads16), "nv_vit_backward_ex: the data-only backward (weight_grads = 0) writes no gradient arena - pass grads = grads16 = NULL");
-  NV_CHECK_ARG(video && strides5 && params && params16 && workspace && dlogits && (grads || !wg), "nv_vit_backward: null pointer");
-  NV_CHECK_ARG(ws_bytes >= W.total, "nv_vit_backward: workspace too small (%ld < %ld) - forward must run with training=1", ws_bytes, W.total);
-  NV_CHECK_ARG(nv_aligned16(grads) && nv_aligned16(grads16), "nv_vit_backward: grads / grads16 must be 16-byte aligned");
-  const bool tail_fwd = cls_tail_wanted(D, 1, drop_p, rows_form);     // the form the (training) forward took, given the same arguments
-  r16* gr16 = (r16*)grads16;                     // optional bf16 mirror of the Linear weight gradients (data-parallel messages)
-  auto M16 = [&](long off) -> void* { return gr16 ? (void*)(gr16 + off) : nullptr; };
-  char* ws = (char*)workspace;
-  const float* p = params;
-  const r16* p16 = (const r16*)params16;
-  float* gr = grads;
-  auto GR = [&](long off) -> float* { return gr ? gr + off : nullptr; };   // (data-only: no arena, every parameter-gradient output NULL)
-  const int M = D.M, d = D.d, acc = accumulate;
-  float* g = (float*)(ws + W.g);
-  // Buffers the auxiliary stream reads exist twice (even / odd layers): layer l's weight-gradient work runs while the main
-  // stream is already in layer l-1, which writes the other copy.
-  auto G16 = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[0] : W.g16); };     // bf16 residual gradient entering layer l
-  auto G16B = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[1] : W.g16b); };   // ... after LN2 backward
-  auto DU = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[2] : W.du); };
-  auto DQKV = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[3] : W.dqkv); };
-  auto RED = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[4] : W.red); };
-  auto RED2 = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[5] : W.red2); };
-  auto RED3 = [&](int l) -> void* { return ws + ((l & 1) ? W.alt[6] : W.red3); };
-  auto CS1 = [&](int l) -> float* { return (float*)(ws + ((l & 1) ? W.alt[7] : W.cs1)); };
-  // rows of the GEMM tile that will compute dU: > 0 when the fused column-sum epilogue (bias gradient of FC1) is available
-  const int du_tile_rows = nv_gemm_tile_rows(1, M, D.m, d, d, D.m);
-  const int ln_rows = nv_ln_bwd_partial_rows(M);
-  void* red = ws + W.red;
-  const float scale = 1.0f / sqrtf((float)D.dh);
-  hipStream_t S = (hipStream_t)stream;
-  hipStream_t A = (aux_stream && wg) ? (hipStream_t)aux_stream : S;       // weight-gradient stream (== S: fully serial; always in the data-only form)
-  void* sA = (void*)A;
-  const bool forked = (A != S);
-  // (no S -> A ordering here: everything the auxiliary stream does in this call is queued behind a signal of the main stream below)
-
-  NV_CHECK_ARG(first_stage >= 0 && last_stage <= D.L + 1 && first_stage <= last_stage, "nv_vit_backward_stages: bad stage range [%d, %d]", first_stage, last_stage);
-  // head: writes g (zeros + cls rows) and the last layer's FC2 bias gradient (colsum of g)
-  const float* xlast = (float*)(ws + W.layer[D.L - 1].x2);
-  if (first_stage == 0)
-  RUN(nv_head_bwd(dlogits, B, D.C, p + T.hw, D.pool_mean ? (const float*)(ws + W.xm) : xlast, D.pool_mean ? (long)d : (long)D.n * d,
-                  (float*)(ws + W.hst), (float*)(ws + W.xh), p + T.hg, d, D.n, g, d, G16(D.L - 1), d,
-                  GR(T.hg), GR(T.hb), GR(T.hw), GR(T.hbias), GR(T.layer[D.L - 1].b2), acc, red, W.red_bytes,
-                  site_seed(drop_seed, 4 * (D.L - 1) + 3), drop_p, D.pool_mean, stream));
-
-  // One cross-stream event per layer in each direction (an event record costs several microseconds of queue time): the main
-  // stream signals once, after the attention backward; the auxiliary stream then runs, one layer behind the main stream,
-  // [db1 column sum, LN2 reduction, LN1 reduction of the layer above, grouped weight-gradient GEMMs] and signals back once.
-  hipEvent_t prev_done = carry_take(workspace);     // everything the previous (higher) layer queued on [A] - in the previous, unjoined call
-  if (!wg && prev_done) {                           // data-only: serial, so the main stream takes that dependency up front
-    if (hipStreamWaitEvent(S, prev_done, 0) != hipSuccess) { nv_set_error("nv_vit_backward: event wait failed"); return NV_ERR_HIP; }
-    prev_done = nullptr;
-  }
-  bool layers_here = false;
-  int pending_ln1 = -1;               // layer whose LN1-backward partials still wait for their reduction
-  int pending_adam = -1;              // fuse_mode 3: layer whose weights are updated at the NEXT signal - the main stream orders a layer's dxn1 GEMM (last
-                                      // reader of its bf16 weights) behind the signal of that layer, so the update waits for the one after it
-  auto layer_update = [&](int lu) -> int {
-    const LayerP& qu = T.layer[lu];
-    const long b[3] = {qu.wqkv, qu.w1, qu.w2};
-    const long n[3] = {align_up(3L * D.inner * d, 8) + (long)d * D.inner, (long)D.m * d, (long)d * D.m};
-    return nv_adamw_ranges(fuse, b, n, 3, sA);
-  };
-  auto reduce_ln1 = [&](int lp) -> int {
-    const LayerP& qp = T.layer[lp];
-    return nv_ln_bwd_reduce(RED3(lp), M, d, GR(qp.n1g), GR(qp.n1b), (lp > 0) ? GR(T.layer[lp - 1].b2) : nullptr, acc, sA);
-  };
-  void* const ln_reduce = NV_LN_NO_REDUCE;   // every parameter-gradient reduction of a layer goes into ONE nv_reduce_multi launch
-  for (int l = D.L - 1; l >= 0; --l) {
-    const int stage = D.L - l;
-    if (stage < first_stage || stage > last_stage) continue;
-    const LayerP& q = T.layer[l];
-    const LayerW& w = W.layer[l];
-    const float* xin = (l == 0) ? (float*)(ws + W.x0) : (float*)(ws + W.layer[l - 1].x2);
-    float* st1 = (float*)(ws + w.st1);
-    float* st2 = (float*)(ws + w.st2);
-    float* dxn = (float*)(ws + W.dxn);
-    void* g16 = G16(l);
-    void* g16b = G16B(l);
-    void* du = DU(l);
-    void* dqkv = DQKV(l);
-    // last block in the cls-rows form (see g_cls_tail): the residual gradient is zero outside the B cls rows until the attention
-    // backward mixes the rows, so dU, dxn2, the LN2 backward, dAO and three of the four weight gradients are products of B rows
-    const bool tail = tail_fwd && l == D.L - 1;
-    const int Mr = tail ? B : M;                 // rows that carry a gradient; row r of the small problem is row r * rs of the buffers
-    const long rs = tail ? (long)D.n : 1;
-    // ---- FeedForward backward (vit_3d.py:16-26)
-    if (tail) {
-      RUN(nv_skinny_nn(0, B, D.m, d, g16, d * rs, p16 + q.w2, D.m, ws + w.u, D.m * rs, du, D.m * rs, GR(q.b1), acc, site_seed(drop_seed, 4 * l + 2), drop_p, stream));   // dU = (g W2 * mask) * gelu'(u), db1 = column sums
-      RUN(nv_skinny_nn(1, B, d, D.m, du, D.m * rs, p16 + q.w1, d, nullptr, 0, dxn, d * rs, nullptr, 0, 0, 0.f, stream));             // dxn2 = dU W1
-    } else {
-    RUN(nv_gemm_bf16(1, du_tile_rows ? 6 : 5, M, D.m, d, g16, d, p16 + q.w2, D.m, du, D.m, nullptr, ws + w.u, D.m, du_tile_rows ? CS1(l) : nullptr, D.m, 0, 1.f,
-                     site_seed(drop_seed, 4 * l + 2), drop_p, stream));   // dU = (g W2 * mask) * gelu'(u)  [+ per-tile column sums -> db1]
-    RUN(nv_gemm_bf16(1, 1, M, d, D.m, du, D.m, p16 + q.w1, d, dxn, d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));                        // dxn2 = dU W1
-    }
-    RUN(nv_ln_bwd(dxn, d * rs, (float*)(ws + w.x1), d * rs, st2, st2 + M, p + q.n2g, Mr, d, g, g, d * rs, g16b, d * rs, GR(q.n2g), GR(q.n2b), GR(q.bo), acc, RED(l),
-                  W.red_bytes, site_seed(drop_seed, 4 * l + 1), proj_drop_p(cfg, drop_p), stream, ln_reduce));                                   // g += dLN2 -> g16b
-    // ---- Attention backward (vit_3d.py:48-60)
-    if (tail) {
-      RUN(nv_skinny_nn_sparse(B, D.inner, d, g16b, d * rs, p16 + q.wo, D.inner, ws + W.dao, M, D.n, stream));                       // dAO = g Wo on the cls rows, zeros elsewhere
-    } else
-    RUN(nv_gemm_bf16(1, 0, M, D.inner, d, g16b, d, p16 + q.wo, D.inner, ws + W.dao, D.inner, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));  // dAO = g Wo
-    RUN(nv_attn_bwd(ws + w.qkv, 3 * D.inner, ws + w.ao, ws + W.dao, D.inner, (float*)(ws + w.lse), B, D.n, D.heads, D.dh, scale,
-                    (float*)(ws + W.delta), dqkv, 3 * D.inner, site_seed(drop_seed, 4 * l + 0), drop_p, stream));
-    if (attn_grad && attn_grad->maps[l])     // dP (or the relevance term) of this layer: dAO and qkv still hold its values
-      RUN(nv_attn_grad(ws + w.qkv, 3 * D.inner, ws + W.dao, D.inner, B, D.n, D.heads, D.dh, scale, attn_grad->form, attn_grad->maps[l], stream));
-    float* dxn1 = (l == D.L - 1) ? (float*)(ws + W.hookg) : dxn;    // gradient of the last block's attention-LN output is kept (Grad-CAM hook)
-    const bool dxn1_first = fuse && fuse_mode != 3;
-    if (dxn1_first)      // the last reader of this layer's bf16 weights, ahead of the launch that rewrites them (see above)
-      RUN(nv_gemm_bf16(1, 1, M, d, 3 * D.inner, dqkv, 3 * D.inner, p16 + q.wqkv, d, dxn1, d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-    // ---- [A] everything of this layer that only finishes parameter gradients
-    if (forked) RUN(stream_sync(S, A));                                                                                        // dU, g16b, dqkv (and the LN partials) ready
-    if (pending_adam >= 0) { RUN(layer_update(pending_adam)); pending_adam = -1; }      // [A] fuse_mode 3: the layer above, whose last reader (its dxn1 GEMM) ran before this signal
-    if (wg) {
-      // [A] ONE launch for every small parameter gradient that is final by now: db1 (column sums of dU), dLN2 affine + dbo
-      // (= colsum(g)), and dLN1 affine + db2 of the layer above (whose partials were written after that layer's block ran)
-      nv_reduce_job jobs[3];
-      int nj = 0;
-      if (tail) {}                                                  // db1 came out of the dU kernel
-      else if (du_tile_rows) jobs[nj++] = {CS1(l), (M + du_tile_rows - 1) / du_tile_rows, D.m, 1, {GR(q.b1), nullptr, nullptr}, acc};
-      else RUN(nv_colsum_bf16(du, D.m, M, D.m, GR(q.b1), acc, RED2(l), W.red2_bytes, sA));
-      jobs[nj++] = {(const float*)RED(l), nv_ln_bwd_partial_rows(Mr), d, 3, {GR(q.n2g), GR(q.n2b), GR(q.bo)}, acc};
-      if (pending_ln1 >= 0) {
-        const LayerP& qp = T.layer[pending_ln1];
-        jobs[nj++] = {(const float*)RED3(pending_ln1), ln_rows, d, 3, {GR(qp.n1g), GR(qp.n1b), (pending_ln1 > 0) ? GR(T.layer[pending_ln1 - 1].b2) : nullptr}, acc};
-        pending_ln1 = -1;
-      }
-      RUN(nv_reduce_multi(jobs, nj, sA));
-    }
-    if (wg) {
-      // the four weight gradients of the layer in ONE grouped launch (864 tiles keep two workgroups resident on every CU;
-      // launched one by one their 72-288 tiles leave the CUs half empty and latency bound)
-      nv_gemm_problem pr[4];
-      pr[0] = {d, D.m, Mr, g16, d * rs, ws + w.h, D.m * rs, GR(q.w2), D.m, acc, M16(q.w2), D.m};                     // dW2 = g^T h
-      pr[1] = {D.m, d, Mr, du, D.m * rs, ws + w.xn2, d * rs, GR(q.w1), d, acc, M16(q.w1), d};                        // dW1 = dU^T xn2
-      pr[2] = {d, D.inner, Mr, g16b, d * rs, ws + w.ao, D.inner * rs, GR(q.wo), D.inner, acc, M16(q.wo), D.inner};   // dWo = g^T ao
-      pr[3] = {3 * D.inner, d, M, dqkv, 3 * D.inner, ws + w.xn1, d, GR(q.wqkv), d, acc, M16(q.wqkv), d};  // dWqkv = dqkv^T xn1
-      if (fuse && fuse_mode == 3) {      // gradients stored as ever; the layer's update follows as a launch of its own, one signal later
-        RUN(nv_gemm_bf16_grouped(2, 1, 4, pr, sA));
-        pending_adam = l;
-      } else if (fuse) RUN(nv_gemm_bf16_grouped_adamw(4, pr, fuse, sA));
-      else RUN(nv_gemm_bf16_grouped(2, 1, 4, pr, sA));
-    }
-    hipEvent_t done = nullptr;
-    if (forked) { done = deferred_event(); if (!done || hipEventRecord(done, A) != hipSuccess) { nv_set_error("nv_vit_backward: event record failed"); return NV_ERR_HIP; } }
-    if (!dxn1_first)
-      RUN(nv_gemm_bf16(1, 1, M, d, 3 * D.inner, dqkv, 3 * D.inner, p16 + q.wqkv, d, dxn1, d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-    // LN1 backward writes the residual gradient of layer l-1 into the buffer copy layer l+1 used (and layer l-1 then rewrites
-    // the rest of that copy): the auxiliary work of layer l+1 - a whole layer behind by now - must have finished with it.
-    if (forked && prev_done && hipStreamWaitEvent(S, prev_done, 0) != hipSuccess) { nv_set_error("nv_vit_backward: event wait failed"); return NV_ERR_HIP; }
-    RUN(nv_ln_bwd(dxn1, d, xin, d, st1, st1 + M, p + q.n1g, M, d, g, g, d, G16(l - 1), d, GR(q.n1g), GR(q.n1b), (l > 0) ? GR(T.layer[l - 1].b2) : nullptr,
-                  acc, RED3(l), nv_ln_bwd_workspace_bytes(M, d), site_seed(drop_seed, 4 * (l - 1) + 3), (l > 0) ? drop_p : 0.f, stream, ln_reduce));
-    pending_ln1 = wg ? l : -1;
-    prev_done = done;
-    layers_here = true;
-  }
-  if (last_stage < D.L + 1) {
-    if (pending_ln1 >= 0) { if (forked) RUN(stream_sync(S, A)); RUN(reduce_ln1(pending_ln1)); }
-    if (forked) {
-      if (join_aux) {
-        RUN(stream_sync(A, S));   // every gradient written on [A] (weight GEMMs, reductions) is ordered before what follows on the main stream
-      } else {                    // the caller orders the consumer of this range after BOTH streams; the next call inherits the dependency
-        RUN(carry_record(workspace, A));
-      }
-    }
-    return NV_OK;
-  }
-  // a call that starts at the embedding stage behind an unjoined call: its scratch may still be in use over there
-  if (forked && !layers_here && prev_done && hipStreamWaitEvent(S, prev_done, 0) != hipSuccess) { nv_set_error("nv_vit_backward: event wait failed"); return NV_ERR_HIP; }
-  // ---- patch embedding backward (vit_3d.py:91-96,116-118).  The main stream does NOT join the auxiliary one first: layer 0's
-  // grouped weight gradients keep running beside it.  Its reduction scratch is the odd copy, which the auxiliary stream
-  // released before the main stream was allowed into layer 0's LN1 backward.
-  float* est = (float*)(ws + W.est);
-  float* pst = (float*)(ws + W.pst);
-  RUN(nv_embed_finish_bwd(g, d, (float*)(ws + W.t), d, est, est + D.T, p + T.pe_g2, B, D.N, d, (float*)(ws + W.dt), d, ws + W.dt16, d, GR(T.pe_g2),
-                          GR(T.pe_b2), GR(T.pe_bias), GR(T.pos), GR(T.cls), acc, RED(1), W.red_bytes, site_seed(drop_seed, 4 * D.L), emb_drop_p, stream));
-  // patch_dim not a multiple of 8 (reference default 90^3 / p 9 -> P = 729): operands are zero padded to Ppad columns;
-  // the weight gradient is produced in a padded scratch matrix and its valid columns copied / added into the arena.
-  const void* wpe = (D.P != D.Ppad) ? (const void*)(ws + W.wpe16) : (const void*)(p16 + T.pe_w);
-  void* redA = forked ? (void*)(ws + W.red2) : red;
-  const long redA_bytes = forked ? W.red2_bytes : W.red_bytes;
-  // [A] gradient of the patch LayerNorm's affine parameters (needs dxp = dt Wpe and a second gather of the volume);
-  // the main stream meanwhile produces the patch-embedding weight gradient
-  if (forked) RUN(stream_sync(S, A));                                                                                          // dt16 and layer 0's LN1 partials ready
-  if (pending_ln1 >= 0) RUN(reduce_ln1(pending_ln1));
-  if (pending_adam >= 0) { RUN(layer_update(pending_adam)); pending_adam = -1; }                                                // [A] layer 0's weights
-  RUN(nv_gemm_bf16(1, 1, D.T, D.Ppad, d, ws + W.dt16, d, wpe, D.Ppad, ws + W.dxp, D.Ppad, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, sA));              // [A] dxp = dt Wpe
-  if (dvideo)       // [A] the gradient w.r.t. the input volume: LayerNorm(P) backward w.r.t. its input, scattered into voxel layout
-    RUN(nv_patch_ln_dx(video, strides5, B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size, pat_w(cfg), cfg->frame_patch_size,
-                       (const float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, p + T.pe_g, dvideo, opts->dvideo_strides5, sA));
-  if (!wg) return NV_OK;      // data-only: serial, nothing to join
-  RUN(nv_patch_ln_bwd(video, strides5, B, cfg->channels, cfg->frames, cfg->image_size, img_w(cfg), cfg->image_patch_size,
-                      pat_w(cfg), cfg->frame_patch_size, (float*)(ws + W.dxp), D.Ppad, pst, pst + D.T, GR(T.pe_g), GR(T.pe_b), acc, redA,
-                      redA_bytes, sA));                                                                                         // [A]
-  if (D.P != D.Ppad) {
-    RUN(nv_gemm_bf16(2, 1, d, D.Ppad, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, ws + W.dwpe, D.Ppad, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, stream));
-    RUN(nv_copy_2d_f32((float*)(ws + W.dwpe), D.Ppad, d, D.P, GR(T.pe_w), D.P, acc, stream));
-  } else {
-    RUN(nv_gemm_bf16(2, 1, d, D.P, D.T, ws + W.dt16, d, ws + W.xp, D.Ppad, GR(T.pe_w), D.P, nullptr, nullptr, 0, M16(T.pe_w), D.P, acc, 1.f, 0, 0.f, stream));   // dWpe = dt^T xp
-  }
-  if (forked) RUN(stream_sync(A, S));
-  return NV_OK;
 }
 
 extern "C" int nv_vit_backward(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
@@ -1005,25 +1051,37 @@ extern "C" int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, lon
 // ---- data-parallel backward + update of nv_vit_train_step (nv_dp_plan): the backward pass in groups of stages; behind each group the
 // communication stream all-reduces the group's gradient range (RCCL, comm.cpp) - and, with update_per_bucket, applies AdamW to it -
 // while the main stream is already in the next group.  The same launches as the single-process step otherwise.
-static int dp_backward_update(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* strides5, const nv_vit_input* in, float* params, void* params16,
-                              float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes, const float* dlogits, const nv_train_hparams* hp,
-                              const nv_dp_plan* dp, bool head_fused, float lscale, float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream,
-                              void* aux_stream) {
+// The update behind a whole backward: GradScaler.step / .update (Trainer.py:75-76) on the device when the loss scale is dynamic (any inf / NaN
+// gradient skips the update and halves the scale), then AdamW over the arena.  grads16: the reduced 16-bit messages, when those hold the gradients.
+static int final_update(const nv_train_hparams* hp, float* params, void* params16, const float* grads, const void* grads16, float* adam_m, float* adam_v, long total,
+                        float grad_scale, void* stream) {
+  if (hp->loss_scale_state) {
+    RUN(nv_loss_scale_check(grads, total, hp->loss_scale_state, stream));
+    RUN(nv_loss_scale_update(hp->loss_scale_state, hp->lr, hp->beta1, hp->beta2, stream));
+  }
+  return nv_adamw_step_scaled(params, grads16 ? grads16 : (const void*)grads, grads16 ? 1 : 0, adam_m, adam_v, params16, total, hp->step, hp->lr, hp->beta1, hp->beta2,
+                              hp->eps, hp->weight_decay, grad_scale, 0, hp->loss_scale_state, stream);
+}
+
+// bc: the step's backward call; every group runs it over its own stage range.
+static int dp_backward_update(const Layout& Y, const nv_vit_config* cfg, BwdCall bc, float* params, void* params16, float* adam_m, float* adam_v,
+                              const nv_train_hparams* hp, const nv_dp_plan* dp, bool head_fused, float lscale) {
   const Dims& D = Y.D; const ParamTab& T = Y.T;
+  float* const grads = bc.grads; void* const stream = bc.stream; void* const aux_stream = bc.aux_stream;
   const int n_stages = D.L + 2, last_stage = D.L + 1;
   const int nb = dp->n_buckets < n_stages ? dp->n_buckets : n_stages;
   const bool forked = aux_stream && aux_stream != stream;
   void* C = dp->comm_stream;
   r16* msg = (r16*)dp->grads16;
+  bc.grads16 = msg;
   const float gs = hp->grad_scale / lscale / (float)dp->world;
   // gradient ranges the GEMMs write into the 16-bit message arena themselves (nv_vit_backward_stages16): everything else of a bucket is converted here
   std::vector<std::pair<long, long>> mirrored;
   if (msg) {
     if (D.P % 8 == 0) mirrored.push_back({T.pe_w, T.pe_w + (long)D.d * D.P});
     for (int l = 0; l < D.L; ++l) {
-      const LayerP& q = T.layer[l];
-      mirrored.push_back({q.wqkv, q.wqkv + 3L * D.inner * D.d}); mirrored.push_back({q.wo, q.wo + (long)D.d * D.inner});
-      mirrored.push_back({q.w1, q.w1 + (long)D.m * D.d}); mirrored.push_back({q.w2, q.w2 + (long)D.d * D.m});
+      const LinearW lw = linear_weights(D, T.layer[l]);
+      for (int i = 0; i < 4; ++i) mirrored.push_back({lw.off[i], lw.off[i] + lw.numel[i]});
     }
   }
   // update_per_bucket: 1 = AdamW of a bucket on the communication stream right behind its all-reduce; 2 = on the AUXILIARY stream, one bucket late
@@ -1045,9 +1103,8 @@ static int dp_backward_update(const Layout& Y, const nv_vit_config* cfg, int B, 
     }
     const int first = (head_fused && s0 == 0) ? 1 : s0;                                  // (the fused head step has run stage 0 already)
     const bool joined = (s1 == last_stage);
-    if (first <= s1)
-      RUN(backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, msg, hp->accumulate ? 1 : 0, first, s1, drop_p,
-                        emb_drop_p, drop_seed, stream, aux_stream, joined ? 1 : 0, in ? in->rows_form : 0, nullptr, 0, nullptr));
+    bc.first_stage = first; bc.last_stage = s1; bc.join_aux = joined ? 1 : 0;
+    if (first <= s1) RUN(backward_impl(Y, cfg, bc));
     long begin = -1, end = -1;
     for (int s = s0; s <= s1; ++s) {
       long lo, hi;
@@ -1076,14 +1133,7 @@ static int dp_backward_update(const Layout& Y, const nv_vit_config* cfg, int B, 
   }
   RUN(stream_sync((hipStream_t)C, (hipStream_t)stream));                                    // every bucket reduced (and updated) before what follows on the main stream
   if (late_begin >= 0) RUN(adamw_range(late_begin, late_end, stream));                       // the last bucket (layer 0 + embedding): nothing left to overlap with
-  if (!upd) {
-    if (hp->loss_scale_state) {
-      RUN(nv_loss_scale_check(grads, T.total, hp->loss_scale_state, stream));
-      RUN(nv_loss_scale_update(hp->loss_scale_state, hp->lr, hp->beta1, hp->beta2, stream));
-    }
-    RUN(nv_adamw_step_scaled(params, msg ? (const void*)msg : (const void*)grads, msg ? 1 : 0, adam_m, adam_v, params16, T.total, hp->step, hp->lr, hp->beta1, hp->beta2,
-                             hp->eps, hp->weight_decay, gs, 0, hp->loss_scale_state, stream));
-  }
+  if (!upd) RUN(final_update(hp, params, params16, grads, msg, adam_m, adam_v, T.total, gs, stream));
   return NV_OK;
 }
 
@@ -1126,8 +1176,8 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
     const int Ll = D.L - 1;
     RUN(nv_head_step_scaled((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
                             labels, lscale, hp->loss_scale_state, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
-                            ws + ((Ll & 1) ? W.alt[0] : W.g16), D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
-                            hp->accumulate ? 1 : 0, ws + W.red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream));
+                            ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
+                            hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream));
   } else {
     RUN(nv_ce_loss_scaled(logits, labels, B, cfg->num_classes, lscale, hp->loss_scale_state, loss, dlogits, stream));
   }
@@ -1135,19 +1185,16 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
   opt.struct_size = (int)sizeof(opt); opt.step = hp->step; opt.lr = hp->lr; opt.beta1 = hp->beta1; opt.beta2 = hp->beta2; opt.eps = hp->eps;
   opt.weight_decay = hp->weight_decay; opt.grad_scale = hp->grad_scale / lscale; opt.keep_grads = hp->fuse_update == 2;
   opt.params = params; opt.grads = grads; opt.adam_m = adam_m; opt.adam_v = adam_v; opt.params16 = params16;
-  if (dp && hp->update)
-    return dp_backward_update(Y, cfg, B, video, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, dlogits, hp, dp, head_fused, lscale,
-                              drop_p, emb_drop_p, drop_seed, stream, aux_stream);
-  RUN(backward_impl(Y, cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, nullptr, hp->accumulate ? 1 : 0, head_fused ? 1 : 0, cfg->depth + 1,
-                    drop_p, emb_drop_p, drop_seed, stream, aux_stream, 1, in ? in->rows_form : 0, fused ? &opt : nullptr, hp->fuse_update, nullptr));
+  BwdCall bc{};
+  bc.video = video; bc.strides5 = strides5; bc.params = params; bc.params16 = params16; bc.workspace = workspace; bc.ws_bytes = ws_bytes;
+  bc.dlogits = dlogits; bc.grads = grads; bc.accumulate = hp->accumulate ? 1 : 0; bc.drop_p = drop_p; bc.emb_drop_p = emb_drop_p; bc.drop_seed = drop_seed;
+  bc.stream = stream; bc.aux_stream = aux_stream; bc.join_aux = 1; bc.rows_form = in ? in->rows_form : 0;
+  if (dp && hp->update) return dp_backward_update(Y, cfg, bc, params, params16, adam_m, adam_v, hp, dp, head_fused, lscale);
+  bc.first_stage = head_fused ? 1 : 0; bc.last_stage = cfg->depth + 1;      // (the fused head step has run stage 0 already)
+  bc.fuse = fused ? &opt : nullptr; bc.fuse_mode = hp->fuse_update;
+  RUN(backward_impl(Y, cfg, bc));
   if (hp->update && !fused) {
-    const long total = T.total;
-    if (hp->loss_scale_state) {      // GradScaler.step / .update (Trainer.py:75-76) on the device: any inf / NaN gradient skips the update and halves the scale
-      RUN(nv_loss_scale_check(grads, total, hp->loss_scale_state, stream));
-      RUN(nv_loss_scale_update(hp->loss_scale_state, hp->lr, hp->beta1, hp->beta2, stream));
-    }
-    RUN(nv_adamw_step_scaled(params, grads, 0, adam_m, adam_v, params16, total, hp->step, hp->lr, hp->beta1, hp->beta2, hp->eps, hp->weight_decay, hp->grad_scale / lscale, 0,
-                             hp->loss_scale_state, stream));
+    RUN(final_update(hp, params, params16, grads, nullptr, adam_m, adam_v, T.total, hp->grad_scale / lscale, stream));
   } else if (fused) {
     // what was not updated during the backward pass: the arena minus the four Linear weights of every layer (arena order:
     // ... n1b | wqkv | wo | bo n2g n2b | w1 | b1 | w2 | b2 n1g' ...), one launch
@@ -1155,8 +1202,8 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
     long cur = 0;
     auto skip = [&](long off, long numel) { if (off > cur) { begins.push_back(cur); lens.push_back(off - cur); } cur = align_up(off + numel, 8); };
     for (int l = 0; l < D.L; ++l) {
-      const LayerP& q = T.layer[l];
-      skip(q.wqkv, 3L * D.inner * D.d); skip(q.wo, (long)D.d * D.inner); skip(q.w1, (long)D.m * D.d); skip(q.w2, (long)D.d * D.m);
+      const LinearW lw = linear_weights(D, T.layer[l]);
+      for (int i = 0; i < 4; ++i) skip(lw.off[i], lw.numel[i]);
     }
     if (T.total > cur) { begins.push_back(cur); lens.push_back(T.total - cur); }
     RUN(nv_adamw_ranges(&opt, begins.data(), lens.data(), (int)begins.size(), stream));

@@ -377,36 +377,28 @@ class VitRuntime:
         if attn_grad is not None and rec.dropout[0] > 0:
             raise NotImplementedError("neurovit_amd: no attention gradients of a forward with attention dropout (the mask is not replayed "
                                       "into the gradient of the probabilities) - run the attribution in eval mode")
-        if dvideo is not None or not weight_grads or attn_grad is not None:
-            if dvideo is not None:
-                if rec.keep[0] is not None:
-                    raise NotImplementedError("neurovit_amd: no input gradient of a forward on RAW volumes (vol_sigma): the folded z-score "
-                                              "treats sigma as a constant, so the gradient w.r.t. the raw volume would be wrong")
-                assert dvideo.is_cuda and dvideo.dtype == torch.float32 and dvideo.shape == video.shape and dvideo.device == video.device
-            if not weight_grads:
-                assert grads is None and grads16 is None, "the data-only backward writes no gradient arena"
+        if dvideo is not None:
+            if rec.keep[0] is not None:
+                raise NotImplementedError("neurovit_amd: no input gradient of a forward on RAW volumes (vol_sigma): the folded z-score "
+                                          "treats sigma as a constant, so the gradient w.r.t. the raw volume would be wrong")
+            assert dvideo.is_cuda and dvideo.dtype == torch.float32 and dvideo.shape == video.shape and dvideo.device == video.device
+        if not weight_grads:
+            assert grads is None and grads16 is None, "the data-only backward writes no gradient arena"
+        opts = None          # nv_vit_backward_opts: only for the input gradient or the data-only form
+        if dvideo is not None or not weight_grads:
             dstrides = None if dvideo is None else ops.strides5(dvideo)      # (kept alive across the call)
             opts = BackwardOpts(ctypes.sizeof(BackwardOpts), None if dvideo is None else dvideo.data_ptr(),
                                 None if dstrides is None else ctypes.cast(dstrides, ctypes.c_void_p), int(bool(weight_grads)))
-            check(lib.nv_vit_backward_attn(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
-                                           params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
-                                           None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
-                                           int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
-                                           torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
-                                           int(join_aux), int(rec.rows_form), ctypes.byref(opts),
-                                           None if attn_grad is None else ctypes.byref(attn_grad)),
-                  "nv_vit_backward_attn")
-            if last == self.cfg.depth + 1:
-                rec.done = True
-            return
         # grads16: bf16 arena (element offsets of `grads`) that also receives the Linear weight gradients, rounded, straight from
         # their GEMMs - the data-parallel message buffer (mirrored_ranges() lists what lands there)
-        check(lib.nv_vit_backward_stages16(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
-                                           params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
-                                           grads.data_ptr(), None if grads16 is None else grads16.data_ptr(), int(accumulate), first, last,
-                                           float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
-                                           torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device), int(join_aux), int(rec.rows_form)),
-              "nv_vit_backward_stages16")
+        check(lib.nv_vit_backward_attn(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
+                                       params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
+                                       None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
+                                       int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
+                                       torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
+                                       int(join_aux), int(rec.rows_form), None if opts is None else ctypes.byref(opts),
+                                       None if attn_grad is None else ctypes.byref(attn_grad)),
+              "nv_vit_backward_attn")
         if last == self.cfg.depth + 1:
             rec.done = True              # the workspace may be refilled by the next training forward
 
