@@ -789,6 +789,43 @@ int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* video, const
                       const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp,
                       float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream);
 
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) training augmentation on the device: a per-sample
+ * random crop (monai's RandSpatialCrop with a fixed size: the reference's DATASET_TRANSFORMS), integer translation, axis flips and an affine
+ * intensity change, for 3D volumes and 4D series.  No call allocates, synchronises or reads anything back, and the host draws no random
+ * number; every argument is checked first (NV_ERR_ARG: a NULL pointer, sizes that are not positive, a roi larger than the input, a wrong
+ * struct_size, a probability outside [0, 1], lo > hi, a negative max_shift or rank).
+ * nv_augment_params: writes params int32 [B, 8] (DEVICE), row b = {ox, oy, oz, flips (bit 0 / 1 / 2 = x / y / z), bits of the fp32 scale,
+ *   bits of the fp32 shift, 0, 0}.  The draw rule, with nv_hash64 the 64-bit hash of the dropout masks
+ *   (x = (c + 0x9E3779B97F4A7C15) * 0xBF58476D1CE4E5B9 ^ seed; x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27;
+ *   x *= 0x94D049BB133111EB; x ^= x >> 31, all mod 2^64, for nv_hash64(seed, c)):
+ *     seed_r = nv_hash64(seed, rank);  draw d of sample b at step s:  h = nv_hash64(seed_r, ((s 2^32 + b) 16 + d) mod 2^64)
+ *     an integer on [0, n):        ((h >> 32) n) >> 32        (no rejection; the bias is below 2^-32 n)
+ *     crop offset, axis a (d = a):             uniform on [0, in_size[a] - roi[a]]
+ *     translation, axis a (d = 3 + a):         uniform on [-max_shift[a], max_shift[a]] (an integer on [0, 2 m + 1) minus m), ADDED to the
+ *                                              crop offset: the window may leave the volume
+ *     flip, axis a (d = 6 + a):                (h >> 48) < (unsigned)(flip_prob[a] * 65536), the product in double: never for 0, always for 1
+ *     scale (d = 9), shift (d = 10):           u = (h >> 40) 2^-24 (exact in fp32); lo + ((hi - lo) u), the difference, the product and the
+ *                                              sum each rounded to fp32 on its own (no FMA)
+ * nv_augment_apply: src fp32 [B, X, Y, Z, T] with the element strides strides5 (HOST array of 5; any strides, T = 1 for volumes), in3 =
+ *   {X, Y, Z} and roi3 = {Sx, Sy, Sz} HOST arrays, params int32 [B, 8] (DEVICE, rows as above; offsets may be anything)
+ *   -> out fp32 [B, Sx, Sy, Sz, T] dense, 16-byte aligned.  With s_a = o_a + (flip_a ? S_a - 1 - i_a : i_a) per axis:
+ *     out[b, i, j, k, t] = (src[b, sx, sy, sz, t] * scale) + shift   inside the volume (two roundings, no FMA)
+ *                        = fill, verbatim                            outside it
+ *   The T timepoints of a sample share its row.  A sample whose scale is exactly 1.0f and whose shift is exactly 0.0f is a bit copy (NaN
+ *   payloads, -0.0).  Every output element is written exactly once, nothing else is written; one launch whose grid follows the output
+ *   rows (B Sx planes), 16-byte stores whatever the alignment of the rows.  Limits (NV_ERR_ARG beyond): B Sx < 2^31, Sy Sz T <= 65535 * 4096. */
+typedef struct {
+  int struct_size;            /* sizeof(nv_augment_config): checked */
+  int in_size[3];             /* X, Y, Z of the input volume */
+  int roi[3];                 /* Sx, Sy, Sz of the window */
+  int max_shift[3];
+  double flip_prob[3];
+  float scale_lo, scale_hi, shift_lo, shift_hi;
+} nv_augment_config;
+int nv_augment_params(const nv_augment_config* cfg, unsigned long seed, unsigned long step, int rank, int B, int* params, void* stream);
+int nv_augment_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* params, const int* roi3, float fill,
+                     float* out, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

@@ -5,3 +5,11 @@ reference's src/models/vit_3d.py and src/models/NeuroEncoder.py) over hand-writt
 through a C-ABI shared library (include/neurovit_hip.h).  There is no CPU / eager fallback.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # `from neurovit_amd import VolumeAugment`, resolved on first use: importing the package itself stays free of torch
+    if name == "VolumeAugment":
+        from .augment import VolumeAugment
+        return VolumeAugment
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

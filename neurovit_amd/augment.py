@@ -1,0 +1,200 @@
+"""Training augmentation on the device: per-sample random crop, integer translation, axis flips and an affine intensity change.
+
+The reference has one augmentation switch: `DATASET_TRANSFORMS` makes `ADNIDataset.__getitem__` apply monai's
+`RandSpatialCrop(roi_size=(80, 80, 80), random_center=True, random_size=False)` to the z-scored 90^3 volume on the host
+(src/data/DatasetADNI.py:27-31, 216-218).  `VolumeAugment` is that crop - and the flips, shifts and intensity changes usually added to
+it - as two HIP launches on the batch that is already on the device (csrc/augment.hip): the parameters are drawn on the device from
+(seed, rank, step, sample) by the counter hash of the dropout masks, so nothing is read back and the host draws no random number; the
+draw rule is part of the C-ABI (include/neurovit_hip.h) and tests/augment_ref.py restates it bit for bit.
+
+Exact transforms only: no noise, no resampling.  No gradient flows through it.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+import struct
+from typing import Optional, Sequence
+
+import torch
+
+from ._cabi import check, lib
+
+
+class AugmentConfig(ctypes.Structure):
+    """struct nv_augment_config (neurovit_hip.h, added within revision 8)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("in_size", ctypes.c_int * 3), ("roi", ctypes.c_int * 3), ("max_shift", ctypes.c_int * 3),
+                ("flip_prob", ctypes.c_double * 3), ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float), ("shift_lo", ctypes.c_float),
+                ("shift_hi", ctypes.c_float)]
+
+
+def _triple(value, name, kind):
+    if isinstance(value, (int, float)) and not isinstance(value, bool):
+        value = (value,) * 3
+    try:
+        value = tuple(value)
+    except TypeError:
+        raise TypeError(f"VolumeAugment: {name} must be a number or three numbers, got {value!r}") from None
+    if len(value) != 3:
+        raise ValueError(f"VolumeAugment: {name} must have three entries (x, y, z), got {value!r}")
+    if kind is int:
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in value):
+            raise TypeError(f"VolumeAugment: {name} must hold integers, got {value!r}")
+        return value
+    if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value):
+        raise TypeError(f"VolumeAugment: {name} must hold numbers, got {value!r}")
+    return tuple(float(v) for v in value)
+
+
+def _range(value, name):
+    try:
+        lo, hi = (float(v) for v in value)
+    except (TypeError, ValueError):
+        raise TypeError(f"VolumeAugment: {name} must be a pair (lo, hi) of numbers, got {value!r}") from None
+    if not (math.isfinite(lo) and math.isfinite(hi)):
+        raise ValueError(f"VolumeAugment: {name} must be finite, got {value!r}")
+    if lo > hi:
+        raise ValueError(f"VolumeAugment: {name} has lo > hi: {value!r}")
+    as_f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]      # what the kernel sees
+    return as_f32(lo), as_f32(hi)
+
+
+class VolumeAugment:
+    """roi: (Sx, Sy, Sz) of the output window (an int = a cube).  Per sample and per axis: a crop offset uniform on [0, X - S] (monai's
+    RandSpatialCrop with a fixed size), plus an integer translation uniform on [-max_shift, max_shift] (cells of the window that leave
+    the volume get `fill`), a flip with probability flip_prob; per sample an intensity change x * scale + shift with scale / shift
+    uniform on their (lo, hi) ranges.  The T timepoints of a 4D sample share its parameters.  Every option at its default switches that
+    transform off; with the roi equal to the input size as well, the instance is the identity and `__call__` launches nothing.
+
+    seed, rank and the step index decide every draw (see nv_augment_params in the header): the same triple reproduces a batch, two
+    ranks with one seed draw different parameters.  `step` counts the calls of this instance unless it is given."""
+
+    def __init__(self, roi, flip_prob=(0, 0, 0), max_shift=(0, 0, 0), scale=(1, 1), shift=(0, 0), fill: float = 0.0, seed: int = 0,
+                 rank: int = 0):
+        self.roi = _triple(roi, "roi", int)
+        if any(s <= 0 for s in self.roi):
+            raise ValueError(f"VolumeAugment: roi must be positive, got {self.roi}")
+        self.flip_prob = _triple(flip_prob, "flip_prob", float)
+        if any(not (0.0 <= p <= 1.0) for p in self.flip_prob):
+            raise ValueError(f"VolumeAugment: flip probabilities must lie in [0, 1], got {self.flip_prob}")
+        self.max_shift = _triple(max_shift, "max_shift", int)
+        if any(m < 0 or m >= 2 ** 30 for m in self.max_shift):
+            raise ValueError(f"VolumeAugment: max_shift must lie in [0, 2^30), got {self.max_shift}")
+        self.scale = _range(scale, "scale")
+        self.shift = _range(shift, "shift")
+        self.fill = float(fill)
+        for name, value, top in (("seed", seed, 2 ** 64), ("rank", rank, 2 ** 31)):
+            if isinstance(value, bool) or not isinstance(value, int):
+                raise TypeError(f"VolumeAugment: {name} must be an integer, got {value!r}")
+            if not (0 <= value < top):
+                raise ValueError(f"VolumeAugment: {name} {value} outside [0, {top})")
+        self.seed, self.rank = seed, rank
+        self.step = 0                      # the step index the next __call__ without `step=` draws for
+        self.last_params: Optional[torch.Tensor] = None
+
+    # ------------------------------------------------------------------ checks
+    def _transforms_off(self) -> bool:
+        return (all(p == 0.0 for p in self.flip_prob) and all(m == 0 for m in self.max_shift) and self.scale == (1.0, 1.0)
+                and self.shift == (0.0, 0.0))
+
+    def _check_input(self, x: torch.Tensor):
+        if not torch.is_tensor(x):
+            raise TypeError(f"VolumeAugment: expected a tensor, got {type(x).__name__}")
+        if x.dim() not in (4, 5):
+            raise ValueError(f"VolumeAugment: expected [B, X, Y, Z] or [B, X, Y, Z, T], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"VolumeAugment: dtype {x.dtype} unsupported (float32)")
+        if x.requires_grad:
+            raise ValueError("VolumeAugment: the input requires grad - no gradient flows through the augmentation (detach it)")
+        if any(n == 0 for n in x.shape):
+            raise ValueError(f"VolumeAugment: empty input {tuple(x.shape)}")
+        if any(s > n for s, n in zip(self.roi, x.shape[1:4])):
+            raise ValueError(f"VolumeAugment: roi {self.roi} is larger than the input {tuple(x.shape[1:4])}")
+        if not x.is_cuda:
+            raise RuntimeError("neurovit_amd.augment.VolumeAugment: input must live on the MI355X (cuda) device - there is no CPU fallback")
+
+    @staticmethod
+    def _check_step(step) -> int:
+        if isinstance(step, bool) or not isinstance(step, int):
+            raise TypeError(f"VolumeAugment: step must be an integer, got {step!r}")
+        if not (0 <= step < 2 ** 64):
+            raise ValueError(f"VolumeAugment: step {step} outside [0, 2^64)")
+        return step
+
+    def is_identity(self, x: torch.Tensor) -> bool:
+        """No transform is on and the roi is the input's spatial size: __call__ returns x itself."""
+        return self._transforms_off() and tuple(x.shape[1:4]) == self.roi
+
+    # ------------------------------------------------------------------ the two launches
+    def params(self, B: int, step: int, in_size: Optional[Sequence[int]] = None, device=None) -> torch.Tensor:
+        """int32 [B, 8] on the device: {ox, oy, oz, flip bits, bits of scale, bits of shift, 0, 0} per sample for step `step`.
+        in_size: (X, Y, Z) of the volumes the window is cut from (default: the roi itself - no room to crop)."""
+        step = self._check_step(step)
+        if isinstance(B, bool) or not isinstance(B, int) or B <= 0:
+            raise ValueError(f"VolumeAugment.params: B must be a positive integer, got {B!r}")
+        in_size = self.roi if in_size is None else _triple(in_size, "in_size", int)
+        if any(s > n for s, n in zip(self.roi, in_size)):
+            raise ValueError(f"VolumeAugment: roi {self.roi} is larger than the input {tuple(in_size)}")
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError("neurovit_amd.augment.VolumeAugment: parameters are drawn on the MI355X (cuda) device - there is no CPU fallback")
+        out = torch.empty((B, 8), dtype=torch.int32, device=device)
+        cfg = AugmentConfig(ctypes.sizeof(AugmentConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi),
+                            (ctypes.c_int * 3)(*self.max_shift), (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1],
+                            self.shift[0], self.shift[1])
+        with torch.cuda.device(device):
+            check(lib.nv_augment_params(ctypes.byref(cfg), self.seed, step, self.rank, B, out.data_ptr(),
+                                        torch.cuda.current_stream().cuda_stream), "nv_augment_params")
+        return out
+
+    def apply(self, x: torch.Tensor, params: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B, X, Y, Z] or [B, X, Y, Z, T] float32 on the device, dense or a strided view; params int32 [B, 8] (as `params` returns them,
+        or written by hand).  Returns the dense [B, Sx, Sy, Sz(, T)] batch; a caller-supplied `out` of that shape is dense."""
+        self._check_input(x)
+        four_d = x.dim() == 5
+        v = x if four_d else x.unsqueeze(-1)
+        B, X, Y, Z, T = v.shape
+        if not (torch.is_tensor(params) and params.dtype == torch.int32 and tuple(params.shape) == (B, 8) and params.device == x.device):
+            raise ValueError(f"VolumeAugment.apply: params must be int32 [{B}, 8] on {x.device}")
+        params = params.contiguous()
+        shape = (B, *self.roi, T) if four_d else (B, *self.roi)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == x.device
+                  and out.is_contiguous() and out.data_ptr() % 16 == 0):
+            raise ValueError(f"VolumeAugment.apply: out must be a dense, 16-byte aligned float32 {shape} on {x.device}")
+        strides = (ctypes.c_long * 5)(*v.stride())
+        in3, roi3 = (ctypes.c_int * 3)(X, Y, Z), (ctypes.c_int * 3)(*self.roi)
+        with torch.cuda.device(x.device):
+            check(lib.nv_augment_apply(v.data_ptr(), ctypes.cast(strides, ctypes.c_void_p), B, ctypes.cast(in3, ctypes.c_void_p), T,
+                                       params.data_ptr(), ctypes.cast(roi3, ctypes.c_void_p), self.fill, out.data_ptr(),
+                                       torch.cuda.current_stream().cuda_stream), "nv_augment_apply")
+        return out
+
+    def __call__(self, x: torch.Tensor, step: Optional[int] = None) -> torch.Tensor:
+        """The augmented batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
+        The parameters used are kept in `last_params` (a device tensor; None for the identity)."""
+        self._check_input(x)
+        own = step is None
+        step = self.step if own else self._check_step(step)
+        if self.is_identity(x):
+            self.last_params = None
+            out = x
+        else:
+            params = self.params(x.shape[0], step, in_size=tuple(x.shape[1:4]), device=x.device)
+            out = self.apply(x, params)
+            self.last_params = params
+        if own:
+            self.step += 1
+        return out
+
+
+def center_window(x: torch.Tensor, roi: Sequence[int]) -> torch.Tensor:
+    """The centre window of x [B, X, Y, Z(, T)] at offset (X - S) // 2 per axis, as a strided VIEW (x itself when the sizes agree)."""
+    size = tuple(x.shape[1:4])
+    if any(s > n for s, n in zip(roi, size)):
+        raise ValueError(f"center_window: roi {tuple(roi)} is larger than the input {size}")
+    if tuple(roi) == size:
+        return x
+    (ox, oy, oz) = ((n - s) // 2 for s, n in zip(roi, size))
+    return x[:, ox:ox + roi[0], oy:oy + roi[1], oz:oz + roi[2]]

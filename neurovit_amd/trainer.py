@@ -480,7 +480,12 @@ class Trainer:
       * `validate` / `evaluate_samples` run the encoder in config['VALIDATION_PRECISION'] (default "fp32": the reference validates
         in fp32 without autocast, Trainer.py:101-118; "bf16" = the training arithmetic, about 3x faster);
       * `log_interval = len(dl)//10` is clamped to >= 1 (the reference divides by zero for < 10 batches,
-        Trainer.py:34,89); TRAINING_ACCUMULATION_STEP is honoured as in the commented block (Trainer.py:82-86).
+        Trainer.py:34,89); TRAINING_ACCUMULATION_STEP is honoured as in the commented block (Trainer.py:82-86);
+      * DATASET_TRANSFORMS (the reference's RandSpatialCrop inside Dataset.__getitem__, DatasetADNI.py:27-31,216-218) is applied to the
+        batch ON THE DEVICE (augment.VolumeAugment: the window is the model's input size, the datasets hand over the uncropped
+        volumes), with optional AUGMENT_* keys for flips, shifts and intensity changes; `train` draws a random window per sample,
+        while `validate` / `evaluate_samples` take the CENTRE window (offset (X - S) // 2 per axis, a strided view) - the reference
+        crops randomly at validation too, which makes its validation loss depend on the draw.
     """
 
     def __init__(self, config, model, dataset_train, dataset_val):
@@ -515,6 +520,30 @@ class Trainer:
         print(f'Model total parameters: {total_params/1e6:.2f}M (trainable {trainable_params/1e6:.2f}M and frozen {(total_params-trainable_params)/1e6:.2f}M)')
         self._os = _os
         self.validation_precision = config.get('VALIDATION_PRECISION', 'fp32')
+        self.augment = self.augment_from_config(config)
+        self.global_step = 0                           # batches `train` has taken so far, over all epochs: the augmentation's step index
+
+    @staticmethod
+    def augment_from_config(config):
+        """DATASET_TRANSFORMS (configs/config4D.yaml of the reference ships it True): false or absent = None, batches reach the step
+        untouched.  True = a VolumeAugment whose window is the model's input size; crop only, unless the optional keys (which the
+        reference's config files do not have) switch more on: AUGMENT_FLIP_PROB, AUGMENT_MAX_SHIFT (a number or three, per axis),
+        AUGMENT_INTENSITY_SCALE, AUGMENT_INTENSITY_SHIFT ((lo, hi) pairs), AUGMENT_FILL, AUGMENT_SEED.  The rank is the process
+        group's when there is one."""
+        if not config.get('DATASET_TRANSFORMS', False):
+            return None
+        from .augment import VolumeAugment
+        S = config['TRAINING_VIT_INPUT_SIZE']
+        return VolumeAugment((S, S, S), flip_prob=config.get('AUGMENT_FLIP_PROB', (0, 0, 0)), max_shift=config.get('AUGMENT_MAX_SHIFT', (0, 0, 0)),
+                             scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)), shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)),
+                             fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
+                             rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+
+    def _center(self, fMRI):
+        if self.augment is None:
+            return fMRI
+        from .augment import center_window
+        return center_window(fMRI, self.augment.roi)
 
     @staticmethod
     def grad_clip_from_config(config) -> Optional[float]:
@@ -552,6 +581,9 @@ class Trainer:
         start_time = time.time()
         for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):     # H2D of batch i+1 under step i
             fMRI, label = self._unpack(batch)
+            if self.augment is not None:
+                fMRI = self.augment(fMRI, step=self.global_step)
+            self.global_step += 1
             loss = self.step(fMRI, label)
             # the reference syncs twice per step (.item()); here statistics stay on the device until a log line is due
             running_loss = running_loss + loss
@@ -577,7 +609,7 @@ class Trainer:
         with torch.no_grad(), self.model.precision(self.validation_precision):
             for i, batch in enumerate(self.val_dataloader):
                 fMRI, label = self._unpack(batch)
-                fMRI, label = fMRI.to(self.device), label.to(self.device)
+                fMRI, label = self._center(fMRI.to(self.device)), label.to(self.device)
                 outputs = self.model(fMRI)
                 val_loss += self.criterion(outputs, label).item()
                 correct += (outputs.argmax(dim=1) == label).sum().item()
@@ -596,7 +628,7 @@ class Trainer:
         with torch.no_grad(), self.model.precision(self.validation_precision):
             for batch in loader:
                 fMRI, label = self._unpack(batch)
-                prediction = self.model(fMRI.to(self.device)).argmax(dim=1).item()
+                prediction = self.model(self._center(fMRI.to(self.device))).argmax(dim=1).item()
                 actual = int(label.item())
                 if prediction != actual:
                     wrong.append((batch[0][0] if isinstance(batch[0], (list, tuple)) else batch[0], prediction, actual))
