@@ -74,7 +74,8 @@ int nv_gemm_tile_rows(int layout, int M, int N, int K, long lda, long ldb);   /*
  * nv_quant_rows_f8: out8[r, :] = sat(W[r, :] * sw[r]) with sw[r] = 448 / max|W[r, :]|; colscale[r] = 1 / (act_scale * sw[r]).
  * nv_ln_fwd_f8: LayerNorm(d) (vit_3d.py:18,37) -> sat(y * out_scale) as e4m3 (inference: no statistics saved).
  * nv_gemm_f8 (NT): C = epi((A8 . B8^T) * colscale[n]); epi 0 bf16 store, 1 f32 store, 4 f32 = aux_in + acc + bias,
- * 7 e4m3 = sat(gelu(acc + bias) * out_scale) (FC1 feeding FC2).  K % 128 == 0. */
+ * 7 e4m3 = sat(gelu(acc + bias) * out_scale) (FC1 feeding FC2).  K % 128 == 0.
+ * sat: finite values and infinities beyond +-448 become +-448 (0x7E / 0xFE); a NaN stays a NaN (0x7F / 0xFF) in every e4m3 writer. */
 int nv_quant_rows_f8(const float* W, long ldw, int rows, int cols, void* out8, long ld8, float act_scale, float* colscale, void* stream);
 int nv_ln_fwd_f8(const float* x, long ldx, int M, int d, const float* gamma, const float* beta, float eps, float out_scale, void* y8,
                  long ldy, void* stream);

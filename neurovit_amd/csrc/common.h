@@ -154,10 +154,16 @@ __device__ __forceinline__ float gelu_grad_f(float u) {
   return 0.5f * (1.0f + e) + u * g * 0.39894228040143267794f;
 }
 
-// OCP e4m3 (gfx950's fp8: v_cvt_pk_fp8_f32), saturating: four floats -> four bytes
+// OCP e4m3 (gfx950's fp8: v_cvt_pk_fp8_f32), saturating: four floats -> four bytes.  Finite values and infinities clamp to +-448; a NaN
+// stays a NaN (0x7F / 0xFF), as in the bf16 copy written beside it: fminf / fmaxf return the OTHER operand for a NaN and made it -448,
+// finite garbage that the loss check cannot see.  IEEE 754-2019 minimum / maximum propagate it.  The price: two VALU ops per value
+// (v_maximum3_f32 + v_minimum3_f32) where the old clamp folded into one v_med3_f32 - 8 instead of 4 per packed word in every e4m3 writer,
+// measured as -0.4 % on the ViT3D-large fp8 inference forward (212.65 -> 211.80 volumes/s, batch 4) and nothing outside the spread on
+// the fp8 train step.  Nothing cheaper is known: v_med3_f32 returns min3 for a NaN operand, gfx950 has no NaN-propagating median, and
+// v_cvt_pk_fp8_f32 does not saturate by itself (HIP's own saturating conversion, hip/amd_detail/amd_hip_fp8.h, puts a v_med3_f32 behind
+// an exponent test in front of it).
 __device__ __forceinline__ unsigned pack_fp8x4(f32x4 v) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = fminf(fmaxf(v[i], -448.f), 448.f);
+  v = __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, f32x4{-448.f, -448.f, -448.f, -448.f}), f32x4{448.f, 448.f, 448.f, 448.f});
   int w = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], 0, false);
   w = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], w, true);
   return (unsigned)w;

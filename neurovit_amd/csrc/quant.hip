@@ -52,7 +52,13 @@ __global__ __launch_bounds__(64 * QW) void ln_fwd_f8_kernel(const float* __restr
     const int c = (lane + 64 * v) * 4;
     if (c < d) {
       const f32x4 t = xv[v] - mean;
-      q += (t[0] * t[0] + t[1] * t[1]) + (t[2] * t[2] + t[3] * t[3]);
+      // the fused multiply-adds written out, in the shapes the compiler gives norm.hip::row_stats / ln_fwd_kernel (both instantiations): left to
+      // it, this kernel got packed multiplies and separate adds here, and rstd differed from nv_ln_fwd's in the last bits.  The durable form is
+      // one helper with explicit fmas used by both kernels; writing them out in norm.hip reschedules every kernel of that file, and nv_ln_fwd's
+      // bits (the bf16 train step's) must not move in a change that cannot re-prove them all - so this side follows that one, and
+      // tests/test_fp8_kernels_gpu.py holds the two to each other bit for bit at d <= 1024 and d = 2048: a compiler that contracts
+      // norm.hip differently fails there.
+      q += __builtin_fmaf(t[0], t[0], t[1] * t[1]) + __builtin_fmaf(t[2], t[2], t[3] * t[3]);
     }
   }
   const float rstd = 1.0f / sqrtf(wave_sum(q) / (float)d + eps);
@@ -61,7 +67,7 @@ __global__ __launch_bounds__(64 * QW) void ln_fwd_f8_kernel(const float* __restr
     const int c = (lane + 64 * v) * 4;
     if (c < d) {
       const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
-      const f32x4 o = (xv[v] - mean) * rstd * gm + bt;
+      const f32x4 o = __builtin_elementwise_fma((xv[v] - mean) * rstd, gm, bt);
       if (y16) *reinterpret_cast<r16x4*>(y16 + (long)row * ldy16 + c) = cvt4<bf16_t>(o[0], o[1], o[2], o[3]);      // (the fp8 path sits beside bf16 operands: nv_set_operand_format)
       *reinterpret_cast<unsigned*>(y + (long)row * ldy + c) = pack_fp8x4(o * out_scale);
     }

@@ -864,38 +864,92 @@ def gemm_dgelu_colsum(A: torch.Tensor, B: torch.Tensor, u: torch.Tensor, drop_se
     return out, part
 
 
-EPI_BIAS_GELU_F8 = 7
+EPI_BIAS_GELU_F8, EPI_BIAS_GELU_F8T = 7, 8
 
 
-def quant_rows_f8(W: torch.Tensor, act_scale: float):
+def _out2d(out: Optional[torch.Tensor], rows: int, cols: int, dtype: torch.dtype, like: torch.Tensor) -> torch.Tensor:
+    """A preallocated 2-D output (any row stride: a column slice of a wider buffer passes its own leading dimension) or a fresh dense one."""
+    if out is None:
+        return torch.empty((rows, cols), dtype=dtype, device=like.device)
+    _need_cuda(out)
+    assert out.dtype == dtype and out.shape == (rows, cols) and out.stride(1) == 1
+    return out
+
+
+def quant_rows_f8(W: torch.Tensor, act_scale: float, *, out: Optional[torch.Tensor] = None, colscale: Optional[torch.Tensor] = None):
     """fp32 [rows, cols] -> (e4m3 bytes uint8 [rows, cols], colscale f32 [rows] = 1 / (act_scale * row scale))."""
     _need_cuda(W)
     rows, cols = W.shape
-    out = torch.empty((rows, cols), dtype=torch.uint8, device=W.device)
-    cs = torch.empty(rows, dtype=torch.float32, device=W.device)
-    check(lib.nv_quant_rows_f8(_p(W), W.stride(0), rows, cols, _p(out), cols, float(act_scale), _p(cs), _stream()), "nv_quant_rows_f8")
+    assert W.dtype == torch.float32 and W.stride(1) == 1
+    out = _out2d(out, rows, cols, torch.uint8, W)
+    cs = torch.empty(rows, dtype=torch.float32, device=W.device) if colscale is None else colscale
+    assert cs.dtype == torch.float32 and cs.shape == (rows,) and cs.is_contiguous()
+    check(lib.nv_quant_rows_f8(_p(W), W.stride(0), rows, cols, _p(out), out.stride(0), float(act_scale), _p(cs), _stream()), "nv_quant_rows_f8")
     return out, cs
 
 
-def ln_fwd_f8(x: torch.Tensor, gamma, beta, out_scale: float, eps: float = 1e-5) -> torch.Tensor:
+def ln_fwd_f8(x: torch.Tensor, gamma, beta, out_scale: float, eps: float = 1e-5, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     _need_cuda(x)
     M, d = x.shape
-    y = torch.empty((M, d), dtype=torch.uint8, device=x.device)
-    check(lib.nv_ln_fwd_f8(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, float(out_scale), _p(y), d, _stream()), "nv_ln_fwd_f8")
+    assert x.dtype == torch.float32 and x.stride(1) == 1
+    y = _out2d(out, M, d, torch.uint8, x)
+    check(lib.nv_ln_fwd_f8(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, float(out_scale), _p(y), y.stride(0), _stream()), "nv_ln_fwd_f8")
     return y
 
 
-def gemm_f8(epi: int, A8: torch.Tensor, B8: torch.Tensor, colscale: torch.Tensor, *, bias=None, aux_in=None, out_scale: float = 1.0, out=None):
-    """C = epi((A8 B8^T) * colscale[n]); A8 [M, K], B8 [N, K] e4m3 bytes (uint8 tensors)."""
+def ln_fwd_f8_train(x: torch.Tensor, gamma, beta, out_scale: float, eps: float = 1e-5, *, y8: Optional[torch.Tensor] = None,
+                    y16: Optional[torch.Tensor] = None, st: Optional[torch.Tensor] = None):
+    """LayerNorm of a training forward on fp8 operands -> (y8 e4m3 bytes as ln_fwd_f8, y16 bf16 and st = (mean, rstd) f32 [2, M] as ln_fwd)."""
+    _need_cuda(x)
+    M, d = x.shape
+    assert x.dtype == torch.float32 and x.stride(1) == 1
+    y8 = _out2d(y8, M, d, torch.uint8, x)
+    y16 = _out2d(y16, M, d, torch.bfloat16, x)
+    st = torch.empty((2, M), dtype=torch.float32, device=x.device) if st is None else st
+    assert st.dtype == torch.float32 and st.shape == (2, M) and st.stride(1) == 1
+    check(lib.nv_ln_fwd_f8_train(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, float(out_scale), _p(y8), y8.stride(0), _p(y16), y16.stride(0),
+                                 _p(st[0]), _p(st[1]), _stream()), "nv_ln_fwd_f8_train")
+    return y8, y16, st
+
+
+def _f8_operands(A8: torch.Tensor, B8: torch.Tensor):
     _need_cuda(A8, B8)
-    assert A8.dtype == torch.uint8 and B8.dtype == torch.uint8
-    M, K = A8.shape
-    N = B8.shape[0]
+    assert A8.dtype == torch.uint8 and B8.dtype == torch.uint8 and A8.stride(1) == 1 and B8.stride(1) == 1 and A8.shape[1] == B8.shape[1]
+    return A8.shape[0], B8.shape[0], A8.shape[1]
+
+
+def gemm_f8(epi: int, A8: torch.Tensor, B8: torch.Tensor, colscale: torch.Tensor, *, bias=None, aux_in=None, out_scale: float = 1.0, out=None):
+    """C = epi((A8 B8^T) * colscale[n]); A8 [M, K], B8 [N, K] e4m3 bytes (uint8 tensors, row-strided views allowed)."""
+    M, N, K = _f8_operands(A8, B8)
     odt = {EPI_STORE_BF16: op16(), EPI_STORE_F32: torch.float32, EPI_BIAS_RESID: torch.float32, EPI_BIAS_GELU_F8: torch.uint8}[epi]
-    if out is None:
-        out = torch.empty((M, N), dtype=odt, device=A8.device)
+    out = _out2d(out, M, N, odt, A8)
     check(lib.nv_gemm_f8(epi, M, N, K, _p(A8), A8.stride(0), _p(B8), B8.stride(0), _p(out), out.stride(0), _p(colscale), _p(bias), _p(aux_in),
                          0 if aux_in is None else aux_in.stride(0), float(out_scale), _stream()), "nv_gemm_f8")
+    return out
+
+
+def gemm_f8_gelu_train(A8: torch.Tensor, B8: torch.Tensor, colscale: torch.Tensor, bias: torch.Tensor, out_scale: float, *,
+                       h8: Optional[torch.Tensor] = None, h16: Optional[torch.Tensor] = None, u16=None, drop_seed: int = 0, drop_p: float = 0.0):
+    """FC1 of a training forward on fp8 operands (epilogue EPI_BIAS_GELU_F8T): u = (A8 B8^T) * colscale[n] + bias[n] ->
+    (h8 e4m3 = sat(gelu(u) * mask * out_scale), h16 bf16 = gelu(u) * mask, u16 bf16 = u).  Every output: None allocates it, a tensor is
+    written in place; u16=False skips the store of u (the third result is None then)."""
+    M, N, K = _f8_operands(A8, B8)
+    h8 = _out2d(h8, M, N, torch.uint8, A8)
+    h16 = _out2d(h16, M, N, torch.bfloat16, A8)
+    u16 = None if u16 is False else _out2d(u16, M, N, torch.bfloat16, A8)
+    check(lib.nv_gemm_f8_gelu_train(M, N, K, _p(A8), A8.stride(0), _p(B8), B8.stride(0), _p(colscale), _p(bias), float(out_scale), _p(h8), h8.stride(0),
+                                    _p(h16), h16.stride(0), _p(u16), 0 if u16 is None else u16.stride(0), int(drop_seed), float(drop_p), _stream()),
+          "nv_gemm_f8_gelu_train")
+    return h8, h16, u16
+
+
+def gemm_f8_resid_drop(A8: torch.Tensor, B8: torch.Tensor, colscale: torch.Tensor, bias: torch.Tensor, aux_in: torch.Tensor, *,
+                       out: Optional[torch.Tensor] = None, drop_seed: int = 0, drop_p: float = 0.0) -> torch.Tensor:
+    """FC2 of a training forward on fp8 operands: f32 = aux_in + ((A8 B8^T) * colscale[n] + bias[n]) * mask (the mask of gemm(NT, EPI_BIAS_RESID))."""
+    M, N, K = _f8_operands(A8, B8)
+    out = _out2d(out, M, N, torch.float32, A8)
+    check(lib.nv_gemm_f8_resid_drop(M, N, K, _p(A8), A8.stride(0), _p(B8), B8.stride(0), _p(out), out.stride(0), _p(colscale), _p(bias), _p(aux_in),
+                                    aux_in.stride(0), int(drop_seed), float(drop_p), _stream()), "nv_gemm_f8_resid_drop")
     return out
 
 

@@ -742,11 +742,12 @@ def test_attention_resident_equals_streaming(ops, B, n, heads, drop):
     assert torch.isfinite(res[2][2].float()).all()
 
 
-@pytest.mark.parametrize("B,n,heads,mode", [(2, 513, 2, 2), (1, 700, 2, 1), (2, 1001, 2, 3), (20, 513, 12, 0)])
+@pytest.mark.parametrize("B,n,heads,mode", [(2, 513, 2, 2), (1, 700, 2, 1), (2, 1001, 2, 3), (20, 513, 12, 0), (1, 65, 2, 0)])
 def test_attention_forward_fp8_output(ops, B, n, heads, mode):
     """nv_attn_fwd_o8 (the fp8 path's out-projection operand written by the attention kernel itself): every forward kernel
     (2 resident, 1 streaming, 3 wide, 0 the dispatcher's choice) - the e4m3 bytes decode to the bf16 output within e4m3's rounding
-    (2^-4 relative, half an ulp of the 3-bit mantissa) plus the bf16 rounding of the comparison value; saturating scale handled."""
+    (2^-4 relative, half an ulp of the 3-bit mantissa) plus the bf16 rounding of the comparison value; saturating scale handled.
+    The small case also plants a NaN in one value row: every output of that batch is the e4m3 NaN code, not a saturated -448."""
     from neurovit_amd._cabi import lib
     qkv = dev(bf(rnd(B * n, 3 * heads * 64, seed=n + heads)))
     lib.nv_attn_set_mode(mode)
@@ -754,6 +755,11 @@ def test_attention_forward_fp8_output(ops, B, n, heads, mode):
         ref, _ = ops.attn_fwd(qkv, B, n, heads)
         scale = 448.0 / (2.0 * float(ref.float().abs().max()))
         o8 = ops.attn_fwd_o8(qkv, B, n, heads, scale)
+        if n == 65:
+            poisoned = qkv.clone()
+            poisoned[10, 2 * heads * 64:] = float("nan")       # the value row of key 10, every head: P . V is NaN in every query row
+            nan8 = ops.attn_fwd_o8(poisoned, B, n, heads, scale)
+            assert bool(((nan8 & 0x7F) == 0x7F).all()), f"{int(((nan8 & 0x7F) != 0x7F).sum())} of {nan8.numel()} outputs behind a NaN value row are finite codes"
     finally:
         lib.nv_attn_set_mode(0)
     deq = o8.view(torch.float8_e4m3fn).float() / scale
