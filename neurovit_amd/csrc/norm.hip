@@ -635,8 +635,8 @@ extern "C" int nv_patch_ln_fwd_f32(const float* video, const long* strides5, int
 // (T innermost, as DatasetADNI_4D returns it).  The reference regroups the sample into T volumes with a strided copy
 // (NeuroEncoder.py:54-56: 168 MB per sample); a T-strided gather per volume would touch every cache line of the sample once per
 // timepoint.  Here one workgroup owns a patch position for all T: its p1*p2 runs of pf*T contiguous floats are read coalesced
-// (float4 = four timepoints of one voxel), the per-timepoint statistics are reduced deterministically through LDS, a second
-// sweep (L2 / Infinity-Cache hits) normalises, and an LDS transpose turns the [voxel][t] order into T token rows written in
+// (float4 = four timepoints of one voxel), the per-timepoint statistics are reduced deterministically through LDS (two rounds: a first mean, then sums centred on
+// it), a last sweep (L2 / Infinity-Cache hits) normalises, and an LDS transpose turns the [voxel][t] order into T token rows written in
 // 8-byte pieces.  Token (bo*T + t)*N + n is bit-for-bit what a volume-by-volume call would address.  Needs C = 1, T % 4 == 0.
 struct PatchTGeom {
   int Bo, H, W, D, T, p1, p2, pf, gf, gh, gw, N, P;
@@ -663,13 +663,33 @@ __global__ __launch_bounds__(256) void patch_ln_fwd_t_kernel(const float* __rest
     const long base = ((((long)bo * g.H + ht * g.p1 + i1) * g.W + wt * g.p2 + i2) * g.D + (long)ft * g.pf) * g.T;
     return x + base + (long)ifr * g.T + 4 * tg;
   };
-  // ---- sweep 1: shifted sums (pivot = voxel 0) per timepoint
+  // ---- sweep 1: the statistics per timepoint, in two rounds over the patch (the second one hits L2).  Round a: the sum shifted by voxel 0
+  // gives a first mean m0.  Round b: sums of d = v - m0 and d^2.  With the pivot AT the mean the one-pass form var = q/P - ms^2 has nothing
+  // to cancel (ms is the rounding residue of m0).  It used to be taken with voxel 0 as the only pivot: a background voxel in front of a patch
+  // of tissue (0 against 8000 +- 20) left var as the difference of two numbers 1.6e5 times its size - 3e-4 relative on rstd, 5000 units of 2^-24
+  // where the wave-per-row kernels lose 3 (tests/test_hard_values_gpu.py).  Cost of the second round: 150.8 -> 192.3 us at 128^3 x 20, p = 16.
   f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
-  f32x4 pv = {0.f, 0.f, 0.f, 0.f};
+  float* m0s = reinterpret_cast<float*>(tile);           // [T] first means; the transposed rounds start after the statistics are done
   if (act) {
-    pv = *reinterpret_cast<const f32x4*>(item_ptr(0));
+    const f32x4 pv = *reinterpret_cast<const f32x4*>(item_ptr(0));
+    for (int k = kk; k < g.P; k += KR) s1 += *reinterpret_cast<const f32x4*>(item_ptr(k)) - pv;
+    *reinterpret_cast<f32x4*>(red + tid * 8) = s1;
+  }
+  __syncthreads();
+  float mean0 = 0.f;
+  if (tid < g.T) {                                       // fixed summation order: deterministic
+    const int mytg = tid >> 2, c = tid & 3;
+    float a = 0.f;
+    for (int j = 0; j < KR; ++j) a += red[(j * TG + mytg) * 8 + c];
+    mean0 = x[(item_ptr(0) - 4 * tg - x) + tid] + a / (float)g.P;       // voxel 0, timepoint tid
+    m0s[tid] = mean0;
+  }
+  __syncthreads();                                       // round a's partial sums consumed, m0 visible
+  if (act) {
+    const f32x4 m0 = *reinterpret_cast<const f32x4*>(m0s + 4 * tg);
+    s1 = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int k = kk; k < g.P; k += KR) {
-      const f32x4 v = *reinterpret_cast<const f32x4*>(item_ptr(k)) - pv;
+      const f32x4 v = *reinterpret_cast<const f32x4*>(item_ptr(k)) - m0;
       s1 += v;
       s2 += v * v;
     }
@@ -678,20 +698,23 @@ __global__ __launch_bounds__(256) void patch_ln_fwd_t_kernel(const float* __rest
   }
   __syncthreads();
   float mean_t = 0.f, rstd_t = 0.f;
-  if (tid < g.T) {                                       // fixed summation order: deterministic
+  if (tid < g.T) {
     const int mytg = tid >> 2, c = tid & 3;
-    float a = 0.f, q = 0.f;
+    // compensated (Kahan) sums: the partial that holds an outlier's square comes first, and up to 255 small ones added to it one by one would
+    // each lose their low bits - 7 units of 2^-24 on the variance where the wave-per-row kernels' tree of sums loses 2
+    float a = 0.f, q = 0.f, ca = 0.f, cq = 0.f;
     for (int j = 0; j < KR; ++j) {
-      a += red[(j * TG + mytg) * 8 + c];
-      q += red[(j * TG + mytg) * 8 + 4 + c];
+      const float ya = red[(j * TG + mytg) * 8 + c] - ca, yq = red[(j * TG + mytg) * 8 + 4 + c] - cq;
+      const float ta = a + ya, tq = q + yq;
+      ca = (ta - a) - ya; cq = (tq - q) - yq;
+      a = ta; q = tq;
     }
-    const float pivot = x[(item_ptr(0) - 4 * tg - x) + tid];            // voxel 0, timepoint tid
     const float ms = a / (float)g.P;
     float var = q / (float)g.P - ms * ms;
     var = var < 0.f ? 0.f : var;
     float e = eps;
     if (vol_sigma) { const float sg = vol_sigma[bo]; e *= sg * sg; }
-    mean_t = pivot + ms;
+    mean_t = mean0 + ms;
     rstd_t = 1.0f / sqrtf(var + e);
   }
   __syncthreads();                                       // partial sums consumed

@@ -23,6 +23,10 @@
 namespace {
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+// v_mfma_f64_16x16x4_f64: A / B one value per lane as in the f32 form, but lane (col = lane & 15, g = lane >> 4) holds rows g + 4 r of the result (the f32
+// form: rows 4 g + r)
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f64x4 mfma4d(double a, double b, f64x4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 
 __device__ __forceinline__ float gelu_exact(float u) { return 0.5f * u * (1.0f + erff(u * 0.70710678118654752440f)); }
 
@@ -232,8 +236,12 @@ void launch_gemm_f32(int epi, int M, int N, int K, const float* A, long lda, con
 // One workgroup = 4 waves = 64 query rows of one (batch, head); keys in tiles of 64 staged through LDS (K row-major, V transposed),
 // online softmax in base e.  Orientation: S^T = K Q^T (MFMA A = K rows, B = Q rows) leaves lane (j, q) with the scores of QUERY j
 // against keys 4q .. 4q+3 of each 16-key block - exactly the B-operand layout of the second product O^T = V^T P^T, whose result
-// gives lane (j, q) four consecutive head-dim columns of query j: row statistics are per lane, the output store is a float4.
+// gives lane (j, q) four head-dim columns of query j: row statistics are per lane.
 // DHB = ceil(dim_head / 16); columns beyond dim_head are zero-filled.
+// The second product accumulates in float64 (v_mfma_f64_16x16x4_f64 on the fp32 probabilities and values, converted exactly).  As an fp32 fmaf chain it
+// rounded once per key at the size of the RUNNING sum: value rows that cancel under a flat softmax (+-8 alternating, results of 0.01) left 2e-7 absolute =
+// 2e-5 of such a row, twice the path's 1e-5 tolerance taken per row (plain float32 attention on a CPU loses the same).  With the chain in float64 what is
+// left is the rounding of the probabilities themselves: 4e-6 on those rows (tests/test_hard_values_gpu.py).
 constexpr int ATK = 64;                      // keys per tile
 // AW waves (16 query rows each) per workgroup: 4 (64 rows); 2 is a tuning aid (more, smaller workgroups: measured slower).
 template <int DHB, int AW>
@@ -261,9 +269,9 @@ __global__ __launch_bounds__(64 * AW) void attn_f32_fwd_kernel(const float* __re
       qf[s] = (c < dh) ? *reinterpret_cast<const f32x4*>(qrow + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
-  f32x4 o[DHB];
+  f64x4 o[DHB];                              // lane (j, g): head-dim columns 16 s + g + 4 r of query j
 #pragma unroll
-  for (int s = 0; s < DHB; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int s = 0; s < DHB; ++s) o[s] = f64x4{0., 0., 0., 0.};
   float m_run = -INFINITY, l_part = 0.f;     // l_part: this lane's share of the row sum (its own key columns)
   const int c4n = dh >> 2;                   // float4 chunks per row that exist
   // staging of one 64-key tile: thread t handles elements t + NT u (u < 256 DHB / NT) of K (key e / (4 DHB), chunk e % (4 DHB): whole rows
@@ -350,7 +358,7 @@ __global__ __launch_bounds__(64 * AW) void attn_f32_fwd_kernel(const float* __re
       }
     l_part = l_part * alpha + ps;
 #pragma unroll
-    for (int s = 0; s < DHB; ++s) o[s] *= alpha;
+    for (int s = 0; s < DHB; ++s) o[s] *= (double)alpha;
     // O^T += V^T P^T: MFMA A = V^T rows (lane (i = head-dim column, g): keys 16 kb + 4 g .. + 3), B = P (lane (j, g): the same keys)
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
@@ -358,20 +366,22 @@ __global__ __launch_bounds__(64 * AW) void attn_f32_fwd_kernel(const float* __re
       for (int s = 0; s < DHB; ++s) {
         const f32x4 vf = *reinterpret_cast<const f32x4*>(svt + (16 * s + j) * KP + 16 * kb + 4 * g);
 #pragma unroll
-        for (int t = 0; t < 4; ++t) o[s] = mfma4(vf[t], st[kb][t], o[s]);
+        for (int t = 0; t < 4; ++t) o[s] = mfma4d((double)vf[t], (double)st[kb][t], o[s]);
       }
   }
   float l = l_part + __shfl_xor(l_part, 16, 64);
   l += __shfl_xor(l, 32, 64);
-  const float inv = 1.0f / l;
+  const double inv = 1.0 / (double)l;
   const int row = q0 + j;
   if (row < n) {
     float* orow = out + ((long)b * n + row) * ldo + (long)h * dh;
 #pragma unroll
-    for (int s = 0; s < DHB; ++s) {
-      const int c = 16 * s + 4 * g;
-      if (c < dh) *reinterpret_cast<f32x4*>(orow + c) = o[s] * inv;
-    }
+    for (int s = 0; s < DHB; ++s)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = 16 * s + g + 4 * r;
+        if (c < dh) orow[c] = (float)(o[s][r] * inv);
+      }
   }
 }
 
