@@ -827,6 +827,82 @@ int nv_augment_params(const nv_augment_config* cfg, unsigned long seed, unsigned
 int nv_augment_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* params, const int* roi3, float fill,
                      float* out, void* stream);
 
+/* (added within revision 8 - new symbols and new structs only, nothing existing changes) the other half of a ViT training recipe:
+ * a soft-target cross-entropy (label smoothing, class weights, a Mixup / CutMix target) and the mixing pass itself.
+ *
+ * ---- the loss.  With y_a = labels[b], y_b = labels[partner_b] and lam_b the row's label lambda (fp32), both read from row b of `mix`
+ * (y_b = y_a, lam_b = 1 without one):
+ *     q_b  = lam_b onehot(y_a) + (1 - lam_b) onehot(y_b)         q'_b = (1 - eps) q_b + eps / C         p_b = softmax(z_b)
+ *     loss = ( sum_b sum_c w_c q'_bc (-log p_bc) ) / D
+ *     D    = sum_b sum_c w_c q_bc                                (UNsmoothed: sum_b w[y_b] without a mix, B without weights)
+ *     dloss/dz_bc = ( p_bc S_b - w_c q'_bc ) / D,  S_b = sum_c w_c q'_bc      (times grad_scale, times state[0] with a loss-scale state)
+ *   Without a mix this is F.cross_entropy(z, y, weight=w, label_smoothing=eps) (torch's index-target form, which divides by sum w[y]);
+ *   without weights and with a mix it is F.cross_entropy(z, q, label_smoothing=eps) (torch's probability-target form, which divides by
+ *   B).  With both, torch's two forms disagree about the denominator; THE RULE ABOVE IS THIS PROJECT'S: the unsmoothed weight of the
+ *   mixed target.  D is formed in double in a fixed order; D == 0 gives a NaN loss.  A label - the row's own or its partner's - outside
+ *   [0, C), or a partner outside [0, B), gives a NaN loss; nothing is read through an unchecked index.
+ *   opts == NULL, or every option off (label_smoothing 0, both pointers NULL), IS nv_ce_loss_scaled / nv_head_step_scaled /
+ *   nv_vit_train_step: the call is handed to them (same launches, same bits).  nv_ce_loss_soft and nv_head_step_soft share one row
+ *   body and give the same bits.  Refused (NV_ERR_ARG) before any launch: a wrong struct_size, label_smoothing outside [0, 1).
+ *   nv_vit_train_step_ex takes every nv_train_hparams form of nv_vit_train_step, on both head routes. */
+#define NV_MIX_COLS 12
+typedef struct nv_loss_opts {
+  int struct_size;              /* sizeof(nv_loss_opts): checked */
+  float label_smoothing;        /* eps in [0, 1) */
+  const float* class_weight;    /* device f32 [C] or NULL (= all ones) */
+  const int* mix;               /* device int32 [B, NV_MIX_COLS] rows of nv_mix_params or NULL: partner (column 0) and label lambda (column 3) are read */
+} nv_loss_opts;
+int nv_ce_loss_soft(const float* logits, const long* target, int B, int C, float grad_scale, const float* scale_state, const nv_loss_opts* opts,
+                    float* loss, float* dlogits, void* stream);
+int nv_head_step_soft(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                      const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, const nv_loss_opts* opts,
+                      float* xh, float* stats, float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16,
+                      float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                      unsigned long drop_seed, float drop_p, void* stream);
+int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                         float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                         const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
+                         float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream);
+
+/* ---- nv_mix_params: writes mix int32 [B, NV_MIX_COLS] (DEVICE), row b = {partner, mode (0 none, 1 mixup, 2 cutmix), bits of the pixel
+ *   lambda, bits of the label lambda, tries, x0, x1, y0, y1, z0, z1, 0}.  One thread per sample, nothing is read back, the host draws no
+ *   random number.  The draws live in a domain of their own (no augmentation draw is reused), with nv_hash64 as for nv_augment_params:
+ *     seed_m = nv_hash64(nv_hash64(seed, rank), 0x4D4958);  draw d of sample b at step s:  h_d = nv_hash64(seed_m, ((s 2^32 + b) 256 + d) mod 2^64)
+ *     partner = B - 1 - b (timm's flip(0)); a sample that is its own partner (the middle of an odd batch, B = 1) has mode 0.
+ *     applied (d = 0):  (h >> 48) < (unsigned)(prob * 65536), the product in double; otherwise mode 0.
+ *     mode (d = 1):     with both alphas set, cutmix iff (h >> 48) < (unsigned)(switch_prob * 65536), else mixup; with one alpha, its mode;
+ *                       with none, mode 0.  alpha = 0 means "not set"; a set alpha lies in [0.05, 1].
+ *     lambda ~ Beta(alpha, alpha) by Joehnk's rule in DOUBLE: try t < 64 uses u from d = 16 + 2 t and v from d = 17 + 2 t,
+ *                       u = ((h >> 12) + 0.5) 2^-52 (exact, never 0); x = pow(u, 1 / alpha), y = pow(v, 1 / alpha); the first t with
+ *                       x + y <= 1 is accepted (after 64 rejections the last pair is used: probability <= 2^-64);
+ *                       lambda = (float)(x / (x + y)), tries = t + 1.  This is the pixel lambda.
+ *     mixup:            label lambda = pixel lambda, the box columns are 0.
+ *     cutmix box, in FP32, in output-window coordinates, shared by the T timepoints: r = sqrt(1.0f - lambda) (correctly rounded);
+ *                       per axis a: e_a = (int)((float)S_a * r), centre c_a = ((h >> 32) S_a) >> 32 with d = 2 + a,
+ *                       lo_a = max(c_a - e_a / 2, 0), hi_a = min(c_a + e_a / 2, S_a) (integer division);
+ *                       label lambda = (float)(1 - cells / (Sx Sy Sz)) with cells = prod (hi_a - lo_a), in double, rounded once (an empty box: 1).
+ *     mode 0 rows:      {partner, 0, bits of 1.0f, bits of 1.0f, 0, 0 ...}.
+ *   Refused (NV_ERR_ARG): NULL pointers, B < 1, a negative rank, a wrong struct_size, a roi that is not positive, a set alpha outside
+ *   [0.05, 1] (above 1 Joehnk's acceptance rate falls below one half, below 0.05 u^(1/alpha) underflows), prob / switch_prob outside [0, 1].
+ * ---- nv_augment_mix: nv_augment_apply and the mix in ONE streaming launch.  src, strides5, in3, T, roi3, fill, out as for
+ *   nv_augment_apply; aug = the rows [B, 8] of nv_augment_params, or NULL for identity rows (offset 0, no flip, scale 1, shift 0); mix =
+ *   the rows above (DEVICE).  Write A_b(i, j, k, t) for the cell nv_augment_apply writes for sample b (own crop, flip, fill, (x scale) +
+ *   shift in two roundings) and A_p for the same cell of the PARTNER under the partner's own row.  Then out[b, i, j, k, t] is
+ *     mode 0, pixel lambda == 1.0f, or a partner outside [0, B):   A_b, a bit copy; the partner is not read
+ *     mixup:    (lambda A_b) + (mu A_p), mu = 1.0f - lambda rounded once per sample; two products and one sum, each rounded (no FMA)
+ *     cutmix:   A_p verbatim for x0 <= i < x1, y0 <= j < y1, z0 <= k < z1 and A_b verbatim elsewhere (bit moves: NaN payloads, -0.0)
+ *   Every output element is written exactly once, nothing else is written; layout, limits and refusals as nv_augment_apply. */
+typedef struct nv_mix_config {
+  int struct_size;            /* sizeof(nv_mix_config): checked */
+  int roi[3];                 /* Sx, Sy, Sz of the output window: the cutmix box lives in it */
+  double mixup_alpha;         /* 0 = off, else [0.05, 1] */
+  double cutmix_alpha;        /* 0 = off, else [0.05, 1] */
+  double prob, switch_prob;
+} nv_mix_config;
+int nv_mix_params(const nv_mix_config* cfg, unsigned long seed, unsigned long step, int rank, int B, int* mix, void* stream);
+int nv_augment_mix(const float* src, const long* strides5, int B, const int* in3, int T, const int* aug, const int* mix, const int* roi3, float fill,
+                   float* out, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

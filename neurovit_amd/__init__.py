@@ -8,8 +8,11 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # `from neurovit_amd import VolumeAugment`, resolved on first use: importing the package itself stays free of torch
+    # `from neurovit_amd import VolumeAugment` (or VolumeMix), resolved on first use: importing the package itself stays free of torch
     if name == "VolumeAugment":
         from .augment import VolumeAugment
         return VolumeAugment
+    if name == "VolumeMix":
+        from .augment import VolumeMix
+        return VolumeMix
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

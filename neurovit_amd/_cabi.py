@@ -81,6 +81,15 @@ class BackwardOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("dvideo", ctypes.c_void_p), ("dvideo_strides5", ctypes.c_void_p), ("weight_grads", ctypes.c_int)]
 
 
+class LossOpts(ctypes.Structure):
+    """struct nv_loss_opts (neurovit_hip.h, added within revision 8): label smoothing, class weights and the mix table of the
+    soft-target cross-entropy (nv_ce_loss_soft / nv_head_step_soft / nv_vit_train_step_ex)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("label_smoothing", ctypes.c_float), ("class_weight", ctypes.c_void_p), ("mix", ctypes.c_void_p)]
+
+
+MIX_COLS = 12        # NV_MIX_COLS: int32 columns of a row of nv_mix_params
+
+
 ABI_VERSION = 8      # NV_ABI_VERSION of the header this binding was written against (checked at load time)
 
 

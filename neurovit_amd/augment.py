@@ -198,3 +198,157 @@ def center_window(x: torch.Tensor, roi: Sequence[int]) -> torch.Tensor:
         return x
     (ox, oy, oz) = ((n - s) // 2 for s, n in zip(roi, size))
     return x[:, ox:ox + roi[0], oy:oy + roi[1], oz:oz + roi[2]]
+
+
+class MixConfig(ctypes.Structure):
+    """struct nv_mix_config (neurovit_hip.h, added within revision 8)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("roi", ctypes.c_int * 3), ("mixup_alpha", ctypes.c_double), ("cutmix_alpha", ctypes.c_double),
+                ("prob", ctypes.c_double), ("switch_prob", ctypes.c_double)]
+
+
+MIX_COLS = 12      # NV_MIX_COLS
+
+
+class VolumeMix:
+    """Mixup / CutMix on the device, per sample (timm's `elem` mode): sample b is paired with B - 1 - b (`flip(0)`), mixed with
+    probability `prob`, by CutMix rather than Mixup with probability `switch_prob` when both alphas are set; lambda ~ Beta(alpha, alpha)
+    with alpha in [0.05, 1].  Mixup writes lam * x + (1 - lam) * partner; CutMix pastes a box of the partner whose volume share is
+    1 - lam before clipping (the label lambda is the share actually kept).  The T timepoints of a 4D sample share its row.  Both
+    alphas None: the identity, nothing is launched.
+
+    `params` draws the table on the device (nv_mix_params: int32 [B, 12] = {partner, mode, bits of the pixel lambda, bits of the label
+    lambda, tries, x0, x1, y0, y1, z0, z1, 0}; the rule is in include/neurovit_hip.h and tests/mix_ref.py restates it); `apply` is ONE
+    streaming launch (nv_augment_mix) that also does the work of a VolumeAugment when one is handed in - each sample and its partner
+    under their own crop / flip / intensity rows - so that a batch is read and written once.  `last_mix` is what the loss needs
+    (nn.CrossEntropyLoss.forward(..., mix=) / TrainStep.__call__(..., mix=)).  No gradient flows through it."""
+
+    def __init__(self, mixup_alpha: Optional[float] = None, cutmix_alpha: Optional[float] = None, prob: float = 1.0, switch_prob: float = 0.5,
+                 seed: int = 0, rank: int = 0):
+        for name, a in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+            if a is None:
+                continue
+            if isinstance(a, bool) or not isinstance(a, (int, float)):
+                raise TypeError(f"VolumeMix: {name} must be a number or None, got {a!r}")
+            if not (0.05 <= float(a) <= 1.0):
+                raise ValueError(f"VolumeMix: {name} {a} outside [0.05, 1] (the Beta sampler's range)")
+        for name, p in (("prob", prob), ("switch_prob", switch_prob)):
+            if isinstance(p, bool) or not isinstance(p, (int, float)):
+                raise TypeError(f"VolumeMix: {name} must be a number, got {p!r}")
+            if not (0.0 <= float(p) <= 1.0):
+                raise ValueError(f"VolumeMix: {name} {p} outside [0, 1]")
+        for name, value, top in (("seed", seed, 2 ** 64), ("rank", rank, 2 ** 31)):
+            if isinstance(value, bool) or not isinstance(value, int):
+                raise TypeError(f"VolumeMix: {name} must be an integer, got {value!r}")
+            if not (0 <= value < top):
+                raise ValueError(f"VolumeMix: {name} {value} outside [0, {top})")
+        self.mixup_alpha = None if mixup_alpha is None else float(mixup_alpha)
+        self.cutmix_alpha = None if cutmix_alpha is None else float(cutmix_alpha)
+        self.prob, self.switch_prob = float(prob), float(switch_prob)
+        self.seed, self.rank = seed, rank
+        self.step = 0                      # the step index the next __call__ without `step=` draws for
+        self.last_mix: Optional[torch.Tensor] = None
+
+    def is_identity(self) -> bool:
+        return self.mixup_alpha is None and self.cutmix_alpha is None
+
+    @staticmethod
+    def _check_input(x: torch.Tensor):
+        if not torch.is_tensor(x):
+            raise TypeError(f"VolumeMix: expected a tensor, got {type(x).__name__}")
+        if x.dim() not in (4, 5):
+            raise ValueError(f"VolumeMix: expected [B, X, Y, Z] or [B, X, Y, Z, T], got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            raise TypeError(f"VolumeMix: dtype {x.dtype} unsupported (float32)")
+        if x.requires_grad:
+            raise ValueError("VolumeMix: the input requires grad - no gradient flows through the mix (detach it)")
+        if any(n == 0 for n in x.shape):
+            raise ValueError(f"VolumeMix: empty input {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError("neurovit_amd.augment.VolumeMix: input must live on the MI355X (cuda) device - there is no CPU fallback")
+
+    def params(self, B: int, step: int, roi, device=None) -> torch.Tensor:
+        """int32 [B, 12] on the device for step `step`; roi: (Sx, Sy, Sz) of the batch that will be mixed (the CutMix box lives in it)."""
+        step = VolumeAugment._check_step(step)
+        if isinstance(B, bool) or not isinstance(B, int) or B <= 0:
+            raise ValueError(f"VolumeMix.params: B must be a positive integer, got {B!r}")
+        roi = _triple(roi, "roi", int)
+        if any(s <= 0 for s in roi):
+            raise ValueError(f"VolumeMix: roi must be positive, got {roi}")
+        device = torch.device("cuda" if device is None else device)
+        if device.type != "cuda":
+            raise RuntimeError("neurovit_amd.augment.VolumeMix: parameters are drawn on the MI355X (cuda) device - there is no CPU fallback")
+        out = torch.empty((B, MIX_COLS), dtype=torch.int32, device=device)
+        cfg = MixConfig(ctypes.sizeof(MixConfig), (ctypes.c_int * 3)(*roi), self.mixup_alpha or 0.0, self.cutmix_alpha or 0.0, self.prob, self.switch_prob)
+        with torch.cuda.device(device):
+            check(lib.nv_mix_params(ctypes.byref(cfg), self.seed, step, self.rank, B, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                  "nv_mix_params")
+        return out
+
+    def apply(self, x: torch.Tensor, mix: torch.Tensor, augment: Optional[VolumeAugment] = None, augment_params: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B, X, Y, Z(, T)] float32 on the device, dense or a strided view; mix int32 [B, 12].  With `augment` (a VolumeAugment: its
+        roi and fill) and `augment_params` (int32 [B, 8], its rows) the crop / flips / intensity change happen in the same pass; without,
+        the window is the whole volume and every row the identity.  Returns the dense [B, Sx, Sy, Sz(, T)] batch."""
+        if augment is not None and not isinstance(augment, VolumeAugment):
+            raise TypeError(f"VolumeMix.apply: augment must be a VolumeAugment, got {type(augment).__name__}")
+        if (augment is None) != (augment_params is None):
+            raise ValueError("VolumeMix.apply: augment and augment_params come together")
+        self._check_input(x)
+        four_d = x.dim() == 5
+        v = x if four_d else x.unsqueeze(-1)
+        B, X, Y, Z, T = v.shape
+        roi = (X, Y, Z) if augment is None else augment.roi
+        if any(s > n for s, n in zip(roi, (X, Y, Z))):
+            raise ValueError(f"VolumeMix: roi {roi} is larger than the input {(X, Y, Z)}")
+        if not (torch.is_tensor(mix) and mix.dtype == torch.int32 and tuple(mix.shape) == (B, MIX_COLS) and mix.device == x.device):
+            raise ValueError(f"VolumeMix.apply: mix must be int32 [{B}, {MIX_COLS}] on {x.device}")
+        mix = mix.contiguous()
+        if augment_params is not None:
+            if not (torch.is_tensor(augment_params) and augment_params.dtype == torch.int32 and tuple(augment_params.shape) == (B, 8)
+                    and augment_params.device == x.device):
+                raise ValueError(f"VolumeMix.apply: augment_params must be int32 [{B}, 8] on {x.device}")
+            augment_params = augment_params.contiguous()
+        shape = (B, *roi, T) if four_d else (B, *roi)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=x.device)
+        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == x.device
+                  and out.is_contiguous() and out.data_ptr() % 16 == 0):
+            raise ValueError(f"VolumeMix.apply: out must be a dense, 16-byte aligned float32 {shape} on {x.device}")
+        strides = (ctypes.c_long * 5)(*v.stride())
+        in3, roi3 = (ctypes.c_int * 3)(X, Y, Z), (ctypes.c_int * 3)(*roi)
+        with torch.cuda.device(x.device):
+            check(lib.nv_augment_mix(v.data_ptr(), ctypes.cast(strides, ctypes.c_void_p), B, ctypes.cast(in3, ctypes.c_void_p), T,
+                                     None if augment_params is None else augment_params.data_ptr(), mix.data_ptr(),
+                                     ctypes.cast(roi3, ctypes.c_void_p), 0.0 if augment is None else augment.fill, out.data_ptr(),
+                                     torch.cuda.current_stream().cuda_stream), "nv_augment_mix")
+        return out
+
+    def __call__(self, x: torch.Tensor, step: Optional[int] = None, augment: Optional[VolumeAugment] = None) -> torch.Tensor:
+        """The mixed batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
+        augment: a VolumeAugment to apply in the same pass, with ITS draws for the same step index (its last_params is set; its own
+        counter is not touched).  The table used is kept in `last_mix` (a device tensor; None for the identity)."""
+        if augment is not None and not isinstance(augment, VolumeAugment):
+            raise TypeError(f"VolumeMix: augment must be a VolumeAugment, got {type(augment).__name__}")
+        own = step is None
+        step = self.step if own else VolumeAugment._check_step(step)
+        self._check_input(x)
+        if self.is_identity():
+            self.last_mix = None
+            out = x if augment is None else augment(x, step=step)
+        else:
+            B = x.shape[0]
+            if augment is None or augment.is_identity(x):
+                aug, rows, roi = None, None, tuple(x.shape[1:4])
+                if augment is not None:
+                    augment._check_input(x)
+                    augment.last_params = None
+            else:
+                augment._check_input(x)
+                aug, roi = augment, augment.roi
+                rows = augment.last_params = augment.params(B, step, in_size=tuple(x.shape[1:4]), device=x.device)
+            mix = self.params(B, step, roi, device=x.device)
+            out = self.apply(x, mix, augment=aug, augment_params=rows)
+            self.last_mix = mix
+        if own:
+            self.step += 1
+        return out

@@ -266,6 +266,109 @@ __device__ __forceinline__ float ce_row_term(const float* __restrict__ row, long
   return term;
 }
 
+// ---- the soft-target cross-entropy of nv_loss_opts (label smoothing, class weights, a mixed target; the definition is in the header):
+// a second row body beside ce_row_term, shared by ce_loss_soft_kernel (optim.hip) and the soft head step (norm.hip) so that both
+// produce the same bits.  The existing kernels keep ce_row_term.
+struct CeSoft {
+  float eps;                 // label smoothing
+  const float* w;            // class weights [C] or null
+  const int* mix;            // rows of nv_mix_params [B, NV_MIX_COLS] or null
+};
+// a row's two labels and its label lambda.  Nothing is read through an index that was not checked: a partner outside [0, B) or a label
+// outside [0, C) leaves ok = false, and the row's term is NaN.
+struct CeTarget { int ya, yb; float lam; bool ok; };
+__device__ __forceinline__ CeTarget ce_soft_target(const long* __restrict__ labels, const CeSoft& o, int b, int B, int C) {
+  CeTarget t;
+  const long la = labels[b];
+  long lb = la;
+  t.lam = 1.f;
+  bool ok = true;
+  if (o.mix) {
+    const int p = o.mix[(long)NV_MIX_COLS * b];
+    t.lam = __int_as_float(o.mix[(long)NV_MIX_COLS * b + 3]);
+    ok = p >= 0 && p < B;
+    lb = ok ? labels[p] : -1;
+  }
+  t.ok = ok && la >= 0 && la < (long)C && lb >= 0 && lb < (long)C;
+  t.ya = t.ok ? (int)la : -1;
+  t.yb = t.ok ? (int)lb : -1;
+  return t;
+}
+// D = sum_b sum_c w_c q_bc = sum_b (lam_b w[ya] + (1 - lam_b) w[yb]): labels, lambdas and weights only.  Formed in double by every
+// workgroup that needs it (256 threads), in one fixed order: thread t sums the rows t, t + 256, ..., then the wave butterflies, then
+// the four waves in order.  redd: 4 doubles of LDS.  NaN for a bad label; the caller turns D == 0 into NaN.
+__device__ __forceinline__ double ce_soft_denominator(const long* __restrict__ labels, const CeSoft& o, int B, int C, double* redd) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  double part = 0.0;
+  for (int b = tid; b < B; b += 256) {
+    const CeTarget t = ce_soft_target(labels, o, b, B, C);
+    if (!t.ok) { part += (double)__builtin_nanf(""); continue; }
+    const double wa = o.w ? (double)o.w[t.ya] : 1.0, wb = o.w ? (double)o.w[t.yb] : 1.0, lam = (double)t.lam;
+    part += lam * wa + (1.0 - lam) * wb;
+  }
+  part = wave_sum(part);
+  if (lane == 0) redd[wid] = part;
+  __syncthreads();
+  const double D = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+  __syncthreads();
+  return D == 0.0 ? (double)__builtin_nanf("") : D;
+}
+// One row (256 threads, every thread returns the row's numerator sum_c w_c q'_c (-log p_c)); dl (optional) = (p_c S - w_c q'_c) * gscale_over_D
+// with S = sum_c w_c q'_c.  red: 4 floats of LDS.
+__device__ __forceinline__ float ce_row_term_soft(const float* __restrict__ row, const CeTarget t, int C, const CeSoft& o, float gscale_over_D, float* red,
+                                                  float* __restrict__ dl) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  float mx = -INFINITY;
+  for (int c = tid; c < C; c += 256) mx = fmaxf(mx, row[c]);
+  mx = wave_max(mx);
+  if (lane == 0) red[wid] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+  __syncthreads();
+  float se = 0.f;
+  for (int c = tid; c < C; c += 256) se += expf(row[c] - mx);
+  se = wave_sum(se);
+  if (lane == 0) red[wid] = se;
+  __syncthreads();
+  se = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  const float lse = mx + logf(se), mu = 1.0f - t.lam, keep = 1.0f - o.eps, even = o.eps / (float)C;
+  auto wq = [&](int c) {                                  // w_c q'_c
+    const float q = (c == t.ya ? t.lam : 0.f) + (c == t.yb ? mu : 0.f);
+    return (o.w ? o.w[c] : 1.f) * (keep * q + even);
+  };
+  float S = 0.f, num = 0.f;
+  for (int c = tid; c < C; c += 256) {
+    const float v = wq(c);
+    S += v;
+    if (v != 0.f) num += v * (lse - row[c]);              // (a class of no weight and no target adds nothing, whatever its logit)
+  }
+  S = wave_sum(S);
+  if (lane == 0) red[wid] = S;
+  __syncthreads();
+  S = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  num = wave_sum(num);
+  if (lane == 0) red[wid] = num;
+  __syncthreads();
+  num = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  if (dl)
+    for (int c = tid; c < C; c += 256) dl[c] = ((expf(row[c] - mx) / se) * S - wq(c)) * gscale_over_D;
+  return t.ok ? num : __builtin_nanf("");
+}
+// nv_loss_opts as the kernels take it, and whether any option is on (off: the callers dispatch to the index-target kernels)
+static inline bool loss_opts_on(const nv_loss_opts* lo) { return lo && (lo->label_smoothing != 0.f || lo->class_weight || lo->mix); }
+static inline int check_loss_opts(const nv_loss_opts* lo, const char* who) {
+  if (!lo) return NV_OK;
+  NV_CHECK_ARG(lo->struct_size == (int)sizeof(nv_loss_opts), "%s: nv_loss_opts.struct_size = %d, this library's nv_loss_opts has %d bytes", who, lo->struct_size,
+               (int)sizeof(nv_loss_opts));
+  NV_CHECK_ARG(lo->label_smoothing >= 0.f && lo->label_smoothing < 1.f, "%s: label_smoothing %g outside [0, 1)", who, (double)lo->label_smoothing);
+  NV_CHECK_ARG(nv_aligned(lo->class_weight, 4) && nv_aligned(lo->mix, 4), "%s: class_weight and mix 4-byte aligned", who);
+  return NV_OK;
+}
+static inline CeSoft make_ce_soft(const nv_loss_opts* lo) { return CeSoft{lo->label_smoothing, lo->class_weight, lo->mix}; }
+
 // ---- dynamic loss scale: indices into the device state block of nv_loss_scale_* (optim.hip; NV_LOSS_SCALE_FLOATS floats)
 enum { LS_SCALE = 0,       // what the NEXT loss gradient is multiplied by
        LS_UNSCALE = 1,     // 1 / (scale of the gradients now in the arena): AdamW's extra grad factor

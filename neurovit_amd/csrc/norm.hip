@@ -1401,6 +1401,88 @@ extern "C" int nv_head_step_scaled(const float* x, long row_stride, int B, int d
   return NV_OK;
 }
 
+// ---- nv_head_step with nv_loss_opts: the two launches of nv_head_step with ce_row_term_soft in place of ce_row_term.  Every workgroup
+// of launch 1 forms the denominator D itself (labels, lambdas and weights only: no atomics, no extra launch) and stores its row's term
+// already divided by D, so launch 2 only adds the terms up - in ce_loss_soft_kernel's order.  head_rows_kernel / head_sums_kernel stay
+// as they are; what differs from them is the loss line of each.
+__global__ __launch_bounds__(256) void head_rows_soft_kernel(const HeadStep a, const CeSoft o) {
+  extern __shared__ __attribute__((aligned(16))) float sh[];   // d floats + 8 scratch + 4 (loss reductions) + 4 doubles (the denominator)
+  if ((int)blockIdx.x >= a.B) {
+    const int part = blockIdx.x - a.B, nparts = gridDim.x - a.B;
+    zero_rows_except(reinterpret_cast<char*>(a.g), (long)a.B * a.n, (long)a.d * 4, a.n, part, nparts);
+    if (a.g16) zero_rows_except(reinterpret_cast<char*>(a.g16), (long)a.B * a.n, (long)a.d * 2, a.n, part, nparts);
+    return;
+  }
+  const int b = blockIdx.x;
+  const float D = (float)ce_soft_denominator(a.labels, o, a.B, a.C, reinterpret_cast<double*>(sh + a.d + 12));   // (d % 8 == 0: 8-byte aligned)
+  head_fwd_row(b, sh, a.x, a.row_stride, a.d, a.gamma, a.beta, a.eps, a.W, a.bias, a.C, a.xh, a.stats, a.logits);
+  __syncthreads();
+  const float gs = a.scale_state ? a.grad_scale * a.scale_state[0] : a.grad_scale;
+  const float term = ce_row_term_soft(a.logits + (long)b * a.C, ce_soft_target(a.labels, o, b, a.B, a.C), a.C, o, gs / D, sh + a.d + 8, a.dlogits + (long)b * a.C) / D;
+  if (threadIdx.x == 0) a.terms[b] = term;
+  __syncthreads();
+  head_bwd_x_row(b, sh, a.dlogits, a.C, a.W, a.x, a.row_stride, a.stats, a.gamma, a.d, a.n, a.g, a.ldg, a.g16, a.ldg16, a.partials, a.drop, 0, a.fp16);
+}
+__global__ __launch_bounds__(256) void head_sums_soft_kernel(const HeadStep a) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx == 0) {
+    float total = 0.f;
+    for (int b = 0; b < a.B; ++b) total += a.terms[b];
+    a.loss[0] = total;
+  }
+  if (idx < 3L * a.d) {
+    const int i = (int)idx;
+    const float s = partial_column_sum(a.partials, a.B, 3L * a.d, i);
+    const int seg = i / a.d, c = i - seg * a.d;
+    float* o = seg == 0 ? a.dgamma : (seg == 1 ? a.dbeta : a.dcolsum);
+    if (o) o[c] = a.accumulate ? o[c] + s : s;
+    return;
+  }
+  const long j = idx - 3L * a.d;
+  if (j < (long)a.C * a.d) {
+    const int c = (int)(j / a.d), k = (int)(j - (long)c * a.d);
+    float s = 0.f;
+    for (int b = 0; b < a.B; ++b) s += a.dlogits[(long)b * a.C + c] * a.xh[(long)b * a.d + k];
+    a.dW[j] = a.accumulate ? a.dW[j] + s : s;
+    if (j < a.C) {
+      float t = 0.f;
+      for (int b = 0; b < a.B; ++b) t += a.dlogits[(long)b * a.C + j];
+      a.dbias[j] = a.accumulate ? a.dbias[j] + t : t;
+    }
+  }
+}
+
+extern "C" int nv_head_step_soft(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                                 const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, const nv_loss_opts* opts,
+                                 float* xh, float* stats, float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16,
+                                 float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                                 unsigned long drop_seed, float drop_p, void* stream) {
+  if (int rc = check_loss_opts(opts, "nv_head_step_soft")) return rc;
+  if (!loss_opts_on(opts))
+    return nv_head_step_scaled(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, xh, stats, logits, loss, dlogits, n, g, ldg, g16,
+                               ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
+  NV_CHECK_ARG(B > 0 && d > 0 && C > 0 && C <= d && n > 0, "nv_head_step_soft: B = %d, d = %d, C = %d, n = %d", B, d, C, n);
+  NV_CHECK_ARG(x && gamma && beta && W && bias && labels && xh && stats && logits && loss && dlogits && g && dgamma && dbeta && dW && dbias && workspace,
+               "nv_head_step_soft: null pointer");
+  NV_CHECK_ARG(ws_bytes >= nv_head_step_workspace_bytes(B, d), "nv_head_step_soft: workspace too small");
+  NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d) && (d % 8) == 0 && nv_aligned16(g) && (!g16 || nv_aligned16(g16)), "nv_head_step_soft: g / g16 must be dense [B*n, d], 16-byte aligned, d a multiple of 8");
+  HeadStep a;
+  a.x = x; a.row_stride = row_stride; a.B = B; a.d = d; a.C = C; a.n = n; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias;
+  a.labels = labels; a.grad_scale = grad_scale; a.xh = xh; a.stats = stats; a.logits = logits; a.loss = loss; a.dlogits = dlogits;
+  a.g = g; a.ldg = ldg; a.g16 = (r16*)g16; a.ldg16 = ldg16; a.dgamma = dgamma; a.dbeta = dbeta; a.dW = dW; a.dbias = dbias; a.dcolsum = dcolsum;
+  a.accumulate = accumulate; a.partials = (float*)workspace; a.terms = (float*)workspace + (long)B * 3 * d; a.drop = make_drop(drop_seed, drop_p);
+  a.fp16 = nv_operand_format() == NV_OPERAND_FP16; a.scale_state = scale_state;
+  const long fill_bytes = (long)B * n * d * (g16 ? 6 : 4);
+  int fill_blocks = (int)((fill_bytes + (1 << 16) - 1) >> 16);
+  if (fill_blocks > 1024) fill_blocks = 1024;
+  hipLaunchKernelGGL(head_rows_soft_kernel, dim3(B + fill_blocks), dim3(256), (d + 12 + 8) * sizeof(float), (hipStream_t)stream, a, make_ce_soft(opts));
+  NV_CHECK_LAUNCH("nv_head_step_soft/rows");
+  const long outs = 3L * d + (long)C * d;
+  hipLaunchKernelGGL(head_sums_soft_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+  NV_CHECK_LAUNCH("nv_head_step_soft");
+  return NV_OK;
+}
+
 // --------------------------------------------------------------------------------------- column sum of a bf16 matrix (bias grads)
 // partial[chunk][c] = sum over the chunk's rows of X[r, c]; 8 columns per lane (16-byte loads).
 template <typename T>

@@ -294,6 +294,32 @@ extern "C" int nv_ce_loss_scaled(const float* logits, const long* target, int B,
   return NV_OK;
 }
 
+// nn.CrossEntropyLoss with nv_loss_opts (the definition is in the header): one workgroup forms the denominator D, then walks the rows
+// with ce_row_term_soft - the body and the order of the soft head step (norm.hip), so both give the same bits.
+__global__ __launch_bounds__(256) void ce_loss_soft_kernel(const float* __restrict__ logits, const long* __restrict__ target, int B, int C,
+                                                           float grad_scale, const float* __restrict__ scale_state, const CeSoft o,
+                                                           float* __restrict__ loss, float* __restrict__ dlogits) {
+  __shared__ float red[4];
+  __shared__ double redd[4];
+  if (scale_state) grad_scale *= scale_state[LS_SCALE];
+  const float D = (float)ce_soft_denominator(target, o, B, C, redd);
+  float total = 0.f;
+  for (int b = 0; b < B; ++b)
+    total += ce_row_term_soft(logits + (long)b * C, ce_soft_target(target, o, b, B, C), C, o, grad_scale / D, red, dlogits ? dlogits + (long)b * C : nullptr) / D;
+  if (threadIdx.x == 0) loss[0] = total;
+}
+
+extern "C" int nv_ce_loss_soft(const float* logits, const long* target, int B, int C, float grad_scale, const float* scale_state, const nv_loss_opts* opts,
+                               float* loss, float* dlogits, void* stream) {
+  NV_CHECK_ARG(B > 0 && C > 0 && logits && target && loss, "nv_ce_loss_soft: bad args (null pointer, or B / C not positive)");
+  if (int rc = check_loss_opts(opts, "nv_ce_loss_soft")) return rc;
+  if (!loss_opts_on(opts)) return nv_ce_loss_scaled(logits, target, B, C, grad_scale, scale_state, loss, dlogits, stream);
+  hipLaunchKernelGGL(ce_loss_soft_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, target, B, C, grad_scale, scale_state, make_ce_soft(opts), loss,
+                     dlogits);
+  NV_CHECK_LAUNCH("nv_ce_loss_soft");
+  return NV_OK;
+}
+
 // dst[r, c] (=|+=) src[r, c] for c < cols: strips the column padding of a [rows, ld_src] fp32 scratch matrix
 // (weight gradient of the patch embedding when patch_dim is not a multiple of 8, e.g. the reference default p = 9).
 __global__ __launch_bounds__(256) void copy_2d_f32_kernel(const float* __restrict__ src, long ld_src, int rows, int cols, float* __restrict__ dst,

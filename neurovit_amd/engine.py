@@ -406,14 +406,16 @@ class VitRuntime:
                    adam_m: torch.Tensor, adam_v: torch.Tensor, *, step: int, lr: float, betas, eps: float, weight_decay: float,
                    grad_scale: float = 1.0, accumulate: bool = False, update: bool = True, fuse_update: int = 0,
                    dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, rows_form: Optional[int] = None,
-                   loss_scale: float = 0.0, loss_scale_state: Optional[torch.Tensor] = None, dp=None):
+                   loss_scale: float = 0.0, loss_scale_state: Optional[torch.Tensor] = None, dp=None, loss_opts=None):
         """The reference's whole train step (Trainer.py:65-79) as ONE native call (nv_vit_train_step): forward, CrossEntropyLoss,
         backward of every stage, AdamW over the arena + bf16 shadow refresh.  Returns (loss [1], logits [B, C]) on the device.
         Same launches, streams and arithmetic as forward() + ops.ce_loss + backward() + ops.adamw_step.
         fuse_update (only with update and not accumulate): 1 = the transformer layers' Linear weights are updated by their
         weight-gradient GEMMs (their gradients are then not left in `grads`), 2 = the same but they are; same bits either way.
         loss_scale: static factor on d(loss)/d(logits), divided out again by the update; loss_scale_state: the device block of a
-        dynamic loss scale (optim.LossScaler) - GradScaler semantics on the device, needs fuse_update = 0."""
+        dynamic loss scale (optim.LossScaler) - GradScaler semantics on the device, needs fuse_update = 0.
+        loss_opts: None, or a _cabi.LossOpts (ops.loss_opts: label smoothing, class weights, a mix table) - the step then goes
+        through nv_vit_train_step_ex; the tensors it points to are the caller's to keep alive."""
         rows_form = self.rows_form if rows_form is None else int(rows_form)
         _cabi.set_operand_format(self.operands)
         B, inp = self._input_form(video, vol_sigma, 0, rows_form)
@@ -427,12 +429,20 @@ class VitRuntime:
                           float(grad_scale), int(bool(accumulate)), int(bool(update)), int(fuse_update), float(loss_scale),
                           None if dp is None else ctypes.cast(ctypes.pointer(dp), ctypes.c_void_p),      # _cabi.DpPlan (kept alive by the caller)
                           None if loss_scale_state is None else loss_scale_state.data_ptr())
-        check(lib.nv_vit_train_step(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                    _inp_ptr(inp),
-                                    params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr(),
-                                    ws.data_ptr(), ws.numel(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(), dlogits.data_ptr(),
-                                    ctypes.byref(hp), float(dropout[0]), float(dropout[1]), int(dropout[2]),
-                                    torch.cuda.current_stream().cuda_stream, self._aux_stream(dev)), "nv_vit_train_step")
+        if loss_opts is None:
+            check(lib.nv_vit_train_step(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
+                                        _inp_ptr(inp),
+                                        params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr(),
+                                        ws.data_ptr(), ws.numel(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(), dlogits.data_ptr(),
+                                        ctypes.byref(hp), float(dropout[0]), float(dropout[1]), int(dropout[2]),
+                                        torch.cuda.current_stream().cuda_stream, self._aux_stream(dev)), "nv_vit_train_step")
+        else:
+            check(lib.nv_vit_train_step_ex(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
+                                           _inp_ptr(inp),
+                                           params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(), dlogits.data_ptr(),
+                                           ctypes.byref(hp), ctypes.byref(loss_opts), float(dropout[0]), float(dropout[1]), int(dropout[2]),
+                                           torch.cuda.current_stream().cuda_stream, self._aux_stream(dev)), "nv_vit_train_step_ex")
         self._keep = (vol_sigma, inp)
         self._rows_form = rows_form
         self._last = (B, True, ws, video)

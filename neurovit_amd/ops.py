@@ -433,6 +433,67 @@ def ce_loss(logits: torch.Tensor, target: torch.Tensor, grad_scale: float = 1.0,
     return loss, dl
 
 
+def loss_opts(label_smoothing: float = 0.0, class_weight: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None, B: Optional[int] = None,
+              C: Optional[int] = None, device=None):
+    """_cabi.LossOpts for the soft-target cross-entropy, or None when every option is off (the callers then make the calls they
+    make without one).  class_weight: float32 [C] on the device; mix: int32 [B, 12] on the device (rows of nv_mix_params).  The
+    tensors must outlive the call that reads them (the struct holds their addresses)."""
+    from ._cabi import LossOpts, MIX_COLS
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float)):
+        raise TypeError(f"label_smoothing must be a number, got {label_smoothing!r}")
+    if not (0.0 <= float(label_smoothing) < 1.0):
+        raise ValueError(f"label_smoothing {label_smoothing} outside [0, 1)")
+    if class_weight is not None:
+        if not (torch.is_tensor(class_weight) and class_weight.dtype == torch.float32 and class_weight.dim() == 1 and class_weight.is_contiguous()):
+            raise ValueError("class_weight must be a dense float32 vector [C]")
+        if C is not None and class_weight.numel() != C:
+            raise ValueError(f"class_weight has {class_weight.numel()} entries for {C} classes")
+        if not class_weight.is_cuda or (device is not None and class_weight.device != torch.device(device)):
+            raise RuntimeError("class_weight must live on the logits' MI355X (cuda) device - there is no CPU fallback")
+    if mix is not None:
+        if not (torch.is_tensor(mix) and mix.dtype == torch.int32 and mix.dim() == 2 and mix.shape[1] == MIX_COLS and mix.is_contiguous()):
+            raise ValueError(f"mix must be a dense int32 [B, {MIX_COLS}] table (VolumeMix.params / last_mix)")
+        if B is not None and mix.shape[0] != B:
+            raise ValueError(f"mix has {mix.shape[0]} rows for a batch of {B}")
+        if not mix.is_cuda or (device is not None and mix.device != torch.device(device)):
+            raise RuntimeError("mix must live on the logits' MI355X (cuda) device - there is no CPU fallback")
+    if float(label_smoothing) == 0.0 and class_weight is None and mix is None:
+        return None
+    return LossOpts(ctypes.sizeof(LossOpts), float(label_smoothing), _p(class_weight), _p(mix))
+
+
+def ce_loss_soft(logits: torch.Tensor, target: torch.Tensor, label_smoothing: float = 0.0, class_weight: Optional[torch.Tensor] = None,
+                 mix: Optional[torch.Tensor] = None, grad_scale: float = 1.0, want_grad=True, scale_state=None):
+    """nv_ce_loss_soft: cross-entropy with label smoothing, class weights and a mixed target (the definition is in the header).
+    With every option off it is ce_loss, bit for bit (the library hands the call over)."""
+    B, C = logits.shape
+    lo = loss_opts(label_smoothing, class_weight, mix, B, C, logits.device)
+    loss = torch.empty(1, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    check(lib.nv_ce_loss_soft(_p(logits), _p(target), B, C, grad_scale, _p(scale_state), None if lo is None else ctypes.byref(lo), _p(loss), _p(dl),
+                              _stream()), "nv_ce_loss_soft")
+    return loss, dl
+
+
+def head_step_soft(x, gamma, beta, W, bias, labels, label_smoothing=0.0, class_weight=None, mix=None, eps=1e-5, grad_scale=1.0, scale_state=None):
+    """nv_head_step_soft: head_step with the soft-target cross-entropy.  Returns what head_step returns."""
+    B, n, d = x.shape
+    C = W.shape[0]
+    dev = x.device
+    lo = loss_opts(label_smoothing, class_weight, mix, B, C, dev)
+    xh = torch.empty((B, d), device=dev); st = torch.empty((B, 2), device=dev)
+    logits = torch.empty((B, C), device=dev); dl = torch.empty((B, C), device=dev); loss = torch.empty(1, device=dev)
+    g = torch.full((B, n, d), float("nan"), device=dev); g16 = torch.full((B, n, d), float("nan"), dtype=op16(), device=dev)
+    dgamma, dbeta, dcol = (torch.empty(d, device=dev) for _ in range(3))
+    dW = torch.empty((C, d), device=dev); db = torch.empty(C, device=dev)
+    nb = lib.nv_head_step_workspace_bytes(B, d)
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    check(lib.nv_head_step_soft(_p(x), n * d, B, d, _p(gamma), _p(beta), eps, _p(W), _p(bias), C, _p(labels), grad_scale, _p(scale_state),
+                                None if lo is None else ctypes.byref(lo), _p(xh), _p(st), _p(logits), _p(loss), _p(dl), n, _p(g), d, _p(g16), d, _p(dgamma),
+                                _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), nb, 0, 0.0, _stream()), "nv_head_step_soft")
+    return logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol
+
+
 def adamw_step(p, grad, m, v, p16, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_blocks=0, scale_state=None,
                clip_state=None):
     """grad may be fp32 or the 16-bit operand format (same numel as p).  scale_state: device block of a dynamic loss scale

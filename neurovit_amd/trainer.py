@@ -29,7 +29,11 @@ class TrainStep:
     def __init__(self, model: NeuroEncoder, lr: Optional[float] = None, weight_decay: Optional[float] = None, process_group=None,
                  n_buckets: int = 4, accumulation_steps: int = 1, overlap_optimizer: bool = False,
                  grad_comm_dtype: torch.dtype = torch.float32, grad_comm_algo: Optional[str] = None, fuse_update: Optional[int] = None,
-                 loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None):
+                 loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None, label_smoothing: float = 0.0,
+                 class_weight=None):
+        # label_smoothing / class_weight: nn.CrossEntropyLoss(weight=, label_smoothing=) on every path; __call__'s `mix` (VolumeMix.last_mix)
+        # trains against the Mixup / CutMix target.  With all three off every path makes the calls it makes without them.  Data parallel,
+        # each rank normalises its loss by its own denominator and the gradients are averaged over ranks (what torch DDP does).
         # max_grad_norm: None = off; a finite number > 0 = torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) between the
         # backward pass and the update, on the device (optim.GradClipper): with a loss scale the norm is that of the UN-SCALED gradients
         # (scaler.unscale_ before the clip), data parallel that of the world-averaged ones, with accumulation that of the window's sum.
@@ -62,7 +66,9 @@ class TrainStep:
         assert self.fuse_update in (None, 0, 1, 2, 3), "fuse_update: None (by batch), 0, 1, 2 or 3"
         self.last_fuse_update = 0          # what the most recent native step did
         self.model = model
-        self.criterion = CrossEntropyLoss()
+        self.criterion = CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)
+        if self.criterion.weight is not None:
+            self.criterion.to(next(model.parameters()).device)
         lr = cfg.get("TRAINING_LEARNING_RATE", 1e-4) if lr is None else lr
         wd = cfg.get("TRAINING_WEIGHT_DECAY", 1e-2) if weight_decay is None else weight_decay
         self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=wd, model=model)
@@ -167,14 +173,21 @@ class TrainStep:
             gs /= self.static_scale
         self.optimizer.step_range(self._vit, begin, end, grad_scale=gs, max_blocks=self._opt_blocks)
 
-    def __call__(self, fmri: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def __call__(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if mix is not None:
+            if not (torch.is_tensor(mix) and mix.dtype == torch.int32 and mix.dim() == 2 and tuple(mix.shape) == (labels.shape[0], 12)):
+                raise ValueError(f"TrainStep: mix must be the int32 [{labels.shape[0]}, 12] table of VolumeMix (last_mix)")
+            if not mix.is_cuda:
+                raise RuntimeError("TrainStep: mix must live on the MI355X (cuda) device - there is no CPU fallback")
+            mix = mix.contiguous()
+        run = self._step if mix is None else (lambda f, l: self._step(f, l, mix))      # (without a mix: the call as it always was)
         cs = self._compute_stream
         if cs is None:
-            return self._step(fmri, labels)
+            return run(fmri, labels)
         cur = torch.cuda.current_stream(cs.device)
         cs.wait_stream(cur)
         with torch.cuda.stream(cs):
-            loss = self._step(fmri, labels)
+            loss = run(fmri, labels)
         cur.wait_stream(cs)
         for t in (loss, self.last_outputs):
             if t is not None:
@@ -277,12 +290,23 @@ class TrainStep:
                 p.grad = vit._grad_view(i)
         return loss.reshape(())
 
-    def _native_step(self, fmri: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def _loss_opts(self, labels, mix):
+        """_cabi.LossOpts of this step, or None when label smoothing, class weights and the mix are all off"""
+        crit = self.criterion
+        if crit.label_smoothing == 0.0 and crit.weight is None and mix is None:
+            return None
+        from . import ops
+        if crit.weight is not None and crit.weight.device != labels.device:
+            crit.to(labels.device)
+        return ops.loss_opts(crit.label_smoothing, crit.weight, mix, labels.shape[0], self._vit._cfg.num_classes, labels.device)
+
+    def _native_step(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self._vit._attend_backward_hooked_layers():
             # (_native_ok routes a hooked model to the general path, whose backward fires the hooks; the one-call step has no place to)
             raise NotImplementedError("neurovit_amd.TrainStep: the native one-call step exports no attention gradients - backward hooks on "
                                       "`attend` need the general path (forward + backward through autograd)")
-        got = self._graph_step(fmri, labels)
+        lo = self._loss_opts(labels, mix)
+        got = self._graph_step(fmri, labels) if lo is None else None     # (the captured graphs hold the plain loss: a step with an option on is eager)
         if got is not None:
             return got
         vit, opt = self._vit, self.optimizer
@@ -315,7 +339,7 @@ class TrainStep:
                                           eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate,
                                           update=last_micro and self.clipper is None,
                                           fuse_update=fuse, dropout=vit.draw_dropout(), loss_scale=self.static_scale,
-                                          loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp)
+                                          loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo)
         if last_micro and self.clipper is None:
             opt._steps += 1                 # (after the call: a refused step leaves the counter where it was)
         vit._last_logits = logits
@@ -370,9 +394,9 @@ class TrainStep:
                                None if msg is None else msg.data_ptr())
         return self._dp_keep
 
-    def _step(self, fmri: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    def _step(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
         if self._native_ok(fmri, labels):
-            return self._native_step(fmri, labels)
+            return self._native_step(fmri, labels) if mix is None else self._native_step(fmri, labels, mix)
         model, vit = self.model, self._vit
         last_micro = (self._micro + 1) % self.accumulation_steps == 0
         pipelined = self.sync is not None and last_micro
@@ -383,7 +407,7 @@ class TrainStep:
         self.last_path = "general"
         outputs = model(fmri)
         self.last_outputs = outputs.detach()           # the Trainer shell counts accuracy from these (3D and 4D alike)
-        loss = self.criterion(outputs, labels)
+        loss = self.criterion(outputs, labels) if mix is None else self.criterion(outputs, labels, mix)
         if self._micro == 0:
             self.optimizer.zero_grad(set_to_none=True)
         if self.scaler is not None:
@@ -503,9 +527,10 @@ class Trainer:
             kw["prefetch_factor"] = 2
         self.dataloader = torch.utils.data.DataLoader(self.data, shuffle=True, **kw)
         self.val_dataloader = torch.utils.data.DataLoader(self.val_data, shuffle=False, **kw)
-        self.criterion = CrossEntropyLoss()
+        smoothing, class_weights = self.loss_options_from_config(config)
+        self.criterion = CrossEntropyLoss(weight=class_weights)          # validation: never smoothed, never mixed; it carries the class weights
         self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
-                              max_grad_norm=self.grad_clip_from_config(config))
+                              max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights)
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
         self._wandb = None
@@ -521,6 +546,7 @@ class Trainer:
         self._os = _os
         self.validation_precision = config.get('VALIDATION_PRECISION', 'fp32')
         self.augment = self.augment_from_config(config)
+        self.mix = self.mix_from_config(config)
         self.global_step = 0                           # batches `train` has taken so far, over all epochs: the augmentation's step index
 
     @staticmethod
@@ -538,6 +564,35 @@ class Trainer:
                              scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)), shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)),
                              fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
                              rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+
+    @staticmethod
+    def mix_from_config(config):
+        """AUGMENT_MIXUP_ALPHA / AUGMENT_CUTMIX_ALPHA (optional; the reference's config files have no such keys): with neither, None -
+        batches reach the step unmixed.  Otherwise a VolumeMix with AUGMENT_MIX_PROB (default 1), AUGMENT_MIX_SWITCH_PROB (default 0.5),
+        AUGMENT_SEED and the process group's rank."""
+        mixup, cutmix = config.get('AUGMENT_MIXUP_ALPHA', None), config.get('AUGMENT_CUTMIX_ALPHA', None)
+        if mixup is None and cutmix is None:
+            return None
+        from .augment import VolumeMix
+        return VolumeMix(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=config.get('AUGMENT_MIX_PROB', 1.0),
+                         switch_prob=config.get('AUGMENT_MIX_SWITCH_PROB', 0.5), seed=config.get('AUGMENT_SEED', 0),
+                         rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+
+    @staticmethod
+    def loss_options_from_config(config):
+        """(label smoothing, class weights or None) from the optional keys TRAINING_LABEL_SMOOTHING (default 0) and
+        TRAINING_CLASS_WEIGHTS (a list of C numbers, e.g. class_weights_from_counts of the training set; default None)."""
+        smoothing = config.get('TRAINING_LABEL_SMOOTHING', 0.0)
+        weights = config.get('TRAINING_CLASS_WEIGHTS', None)
+        if weights is not None:
+            try:
+                weights = [float(w) for w in weights]
+            except (TypeError, ValueError):
+                raise TypeError(f"TRAINING_CLASS_WEIGHTS must be a list of numbers, got {weights!r}") from None
+            if any(not (w >= 0.0) or w == float("inf") for w in weights):
+                raise ValueError(f"TRAINING_CLASS_WEIGHTS must be finite and non-negative, got {weights!r}")
+            weights = torch.tensor(weights, dtype=torch.float32)
+        return smoothing, weights
 
     def _center(self, fMRI):
         if self.augment is None:
@@ -581,10 +636,12 @@ class Trainer:
         start_time = time.time()
         for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):     # H2D of batch i+1 under step i
             fMRI, label = self._unpack(batch)
-            if self.augment is not None:
+            if self.mix is not None:
+                fMRI = self.mix(fMRI, step=self.global_step, augment=self.augment)      # crop / flips / intensity and the mix in one pass
+            elif self.augment is not None:
                 fMRI = self.augment(fMRI, step=self.global_step)
             self.global_step += 1
-            loss = self.step(fMRI, label)
+            loss = self.step(fMRI, label) if self.mix is None else self.step(fMRI, label, mix=self.mix.last_mix)
             # the reference syncs twice per step (.item()); here statistics stay on the device until a log line is due
             running_loss = running_loss + loss
             with torch.no_grad():                      # Trainer.py:78-79, from the step's own outputs (no second forward, no sync)
@@ -637,3 +694,13 @@ class Trainer:
         print(f"Accuracy: {acc:.2f}%")
         print(f"Wrong predictions: {wrong}")
         return acc, wrong
+
+
+def class_weights_from_counts(counts):
+    """Balanced class weights N / (C * count_c) (sklearn's `balanced`), formed in double: what TRAINING_CLASS_WEIGHTS is usually set to
+    for cohorts whose groups are far from balanced.  counts: C positive sample counts."""
+    counts = [float(c) for c in counts]
+    if not counts or any(not (c > 0.0) or c == float("inf") for c in counts):
+        raise ValueError(f"class_weights_from_counts: counts must be positive and finite, got {counts!r}")
+    total, C = sum(counts), len(counts)
+    return [total / (C * c) for c in counts]
