@@ -18,7 +18,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from ._cabi import check, lib
+from ._cabi import MIX_COLS, check, lib
 
 
 class AugmentConfig(ctypes.Structure):
@@ -26,6 +26,84 @@ class AugmentConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("in_size", ctypes.c_int * 3), ("roi", ctypes.c_int * 3), ("max_shift", ctypes.c_int * 3),
                 ("flip_prob", ctypes.c_double * 3), ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float), ("shift_lo", ctypes.c_float),
                 ("shift_hi", ctypes.c_float)]
+
+
+# ---------------------------------------------------------------------- what VolumeAugment and VolumeMix check alike (`who` names the class)
+def _check_seed_rank(who, seed, rank):
+    for name, value, top in (("seed", seed, 2 ** 64), ("rank", rank, 2 ** 31)):
+        if isinstance(value, bool) or not isinstance(value, int):
+            raise TypeError(f"{who}: {name} must be an integer, got {value!r}")
+        if not (0 <= value < top):
+            raise ValueError(f"{who}: {name} {value} outside [0, {top})")
+
+
+def _check_step(step) -> int:
+    if isinstance(step, bool) or not isinstance(step, int):
+        raise TypeError(f"VolumeAugment: step must be an integer, got {step!r}")
+    if not (0 <= step < 2 ** 64):
+        raise ValueError(f"VolumeAugment: step {step} outside [0, 2^64)")
+    return step
+
+
+def _check_volume(who, what, x, roi=None):
+    """x is a float32 batch [B, X, Y, Z(, T)] on the device that needs no gradient; `what` is the transform, for the message; roi: a
+    window that must fit into it"""
+    if not torch.is_tensor(x):
+        raise TypeError(f"{who}: expected a tensor, got {type(x).__name__}")
+    if x.dim() not in (4, 5):
+        raise ValueError(f"{who}: expected [B, X, Y, Z] or [B, X, Y, Z, T], got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise TypeError(f"{who}: dtype {x.dtype} unsupported (float32)")
+    if x.requires_grad:
+        raise ValueError(f"{who}: the input requires grad - no gradient flows through the {what} (detach it)")
+    if any(n == 0 for n in x.shape):
+        raise ValueError(f"{who}: empty input {tuple(x.shape)}")
+    if roi is not None and any(s > n for s, n in zip(roi, x.shape[1:4])):
+        raise ValueError(f"{who}: roi {roi} is larger than the input {tuple(x.shape[1:4])}")
+    if not x.is_cuda:
+        raise RuntimeError(f"neurovit_amd.augment.{who}: input must live on the MI355X (cuda) device - there is no CPU fallback")
+
+
+def _draw_target(who, B, device) -> torch.device:
+    """the batch size and the device of a parameter draw"""
+    if isinstance(B, bool) or not isinstance(B, int) or B <= 0:
+        raise ValueError(f"{who}.params: B must be a positive integer, got {B!r}")
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise RuntimeError(f"neurovit_amd.augment.{who}: parameters are drawn on the MI355X (cuda) device - there is no CPU fallback")
+    return device
+
+
+def _check_rows(who, name, rows, B, cols, device) -> torch.Tensor:
+    """a parameter table: int32 [B, cols] on x's device"""
+    if not (torch.is_tensor(rows) and rows.dtype == torch.int32 and tuple(rows.shape) == (B, cols) and rows.device == device):
+        raise ValueError(f"{who}.apply: {name} must be int32 [{B}, {cols}] on {device}")
+    return rows.contiguous()
+
+
+def _run_pass(who, x, roi, fill, rows, mix, out):
+    """The streaming pass over x [B, X, Y, Z(, T)] into the dense [B, *roi(, T)] batch: nv_augment_apply under the checked rows [B, 8]
+    without a mix table, nv_augment_mix under rows (or None: identity rows) and the checked mix table with one."""
+    four_d = x.dim() == 5
+    v = x if four_d else x.unsqueeze(-1)
+    B, X, Y, Z, T = v.shape
+    shape = (B, *roi, T) if four_d else (B, *roi)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == x.device
+              and out.is_contiguous() and out.data_ptr() % 16 == 0):
+        raise ValueError(f"{who}.apply: out must be a dense, 16-byte aligned float32 {shape} on {x.device}")
+    strides = (ctypes.c_long * 5)(*v.stride())
+    in3, roi3 = (ctypes.c_int * 3)(X, Y, Z), (ctypes.c_int * 3)(*roi)
+    src = (v.data_ptr(), ctypes.cast(strides, ctypes.c_void_p), B, ctypes.cast(in3, ctypes.c_void_p), T)
+    dst = (ctypes.cast(roi3, ctypes.c_void_p), fill, out.data_ptr())
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream().cuda_stream
+        if mix is None:
+            check(lib.nv_augment_apply(*src, rows.data_ptr(), *dst, stream), "nv_augment_apply")
+        else:
+            check(lib.nv_augment_mix(*src, None if rows is None else rows.data_ptr(), mix.data_ptr(), *dst, stream), "nv_augment_mix")
+    return out
 
 
 def _triple(value, name, kind):
@@ -83,11 +161,7 @@ class VolumeAugment:
         self.scale = _range(scale, "scale")
         self.shift = _range(shift, "shift")
         self.fill = float(fill)
-        for name, value, top in (("seed", seed, 2 ** 64), ("rank", rank, 2 ** 31)):
-            if isinstance(value, bool) or not isinstance(value, int):
-                raise TypeError(f"VolumeAugment: {name} must be an integer, got {value!r}")
-            if not (0 <= value < top):
-                raise ValueError(f"VolumeAugment: {name} {value} outside [0, {top})")
+        _check_seed_rank("VolumeAugment", seed, rank)
         self.seed, self.rank = seed, rank
         self.step = 0                      # the step index the next __call__ without `step=` draws for
         self.last_params: Optional[torch.Tensor] = None
@@ -98,28 +172,7 @@ class VolumeAugment:
                 and self.shift == (0.0, 0.0))
 
     def _check_input(self, x: torch.Tensor):
-        if not torch.is_tensor(x):
-            raise TypeError(f"VolumeAugment: expected a tensor, got {type(x).__name__}")
-        if x.dim() not in (4, 5):
-            raise ValueError(f"VolumeAugment: expected [B, X, Y, Z] or [B, X, Y, Z, T], got {tuple(x.shape)}")
-        if x.dtype != torch.float32:
-            raise TypeError(f"VolumeAugment: dtype {x.dtype} unsupported (float32)")
-        if x.requires_grad:
-            raise ValueError("VolumeAugment: the input requires grad - no gradient flows through the augmentation (detach it)")
-        if any(n == 0 for n in x.shape):
-            raise ValueError(f"VolumeAugment: empty input {tuple(x.shape)}")
-        if any(s > n for s, n in zip(self.roi, x.shape[1:4])):
-            raise ValueError(f"VolumeAugment: roi {self.roi} is larger than the input {tuple(x.shape[1:4])}")
-        if not x.is_cuda:
-            raise RuntimeError("neurovit_amd.augment.VolumeAugment: input must live on the MI355X (cuda) device - there is no CPU fallback")
-
-    @staticmethod
-    def _check_step(step) -> int:
-        if isinstance(step, bool) or not isinstance(step, int):
-            raise TypeError(f"VolumeAugment: step must be an integer, got {step!r}")
-        if not (0 <= step < 2 ** 64):
-            raise ValueError(f"VolumeAugment: step {step} outside [0, 2^64)")
-        return step
+        _check_volume("VolumeAugment", "augmentation", x, self.roi)
 
     def is_identity(self, x: torch.Tensor) -> bool:
         """No transform is on and the roi is the input's spatial size: __call__ returns x itself."""
@@ -129,15 +182,11 @@ class VolumeAugment:
     def params(self, B: int, step: int, in_size: Optional[Sequence[int]] = None, device=None) -> torch.Tensor:
         """int32 [B, 8] on the device: {ox, oy, oz, flip bits, bits of scale, bits of shift, 0, 0} per sample for step `step`.
         in_size: (X, Y, Z) of the volumes the window is cut from (default: the roi itself - no room to crop)."""
-        step = self._check_step(step)
-        if isinstance(B, bool) or not isinstance(B, int) or B <= 0:
-            raise ValueError(f"VolumeAugment.params: B must be a positive integer, got {B!r}")
+        step = _check_step(step)
         in_size = self.roi if in_size is None else _triple(in_size, "in_size", int)
         if any(s > n for s, n in zip(self.roi, in_size)):
             raise ValueError(f"VolumeAugment: roi {self.roi} is larger than the input {tuple(in_size)}")
-        device = torch.device("cuda" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError("neurovit_amd.augment.VolumeAugment: parameters are drawn on the MI355X (cuda) device - there is no CPU fallback")
+        device = _draw_target("VolumeAugment", B, device)
         out = torch.empty((B, 8), dtype=torch.int32, device=device)
         cfg = AugmentConfig(ctypes.sizeof(AugmentConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi),
                             (ctypes.c_int * 3)(*self.max_shift), (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1],
@@ -151,32 +200,15 @@ class VolumeAugment:
         """x [B, X, Y, Z] or [B, X, Y, Z, T] float32 on the device, dense or a strided view; params int32 [B, 8] (as `params` returns them,
         or written by hand).  Returns the dense [B, Sx, Sy, Sz(, T)] batch; a caller-supplied `out` of that shape is dense."""
         self._check_input(x)
-        four_d = x.dim() == 5
-        v = x if four_d else x.unsqueeze(-1)
-        B, X, Y, Z, T = v.shape
-        if not (torch.is_tensor(params) and params.dtype == torch.int32 and tuple(params.shape) == (B, 8) and params.device == x.device):
-            raise ValueError(f"VolumeAugment.apply: params must be int32 [{B}, 8] on {x.device}")
-        params = params.contiguous()
-        shape = (B, *self.roi, T) if four_d else (B, *self.roi)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == x.device
-                  and out.is_contiguous() and out.data_ptr() % 16 == 0):
-            raise ValueError(f"VolumeAugment.apply: out must be a dense, 16-byte aligned float32 {shape} on {x.device}")
-        strides = (ctypes.c_long * 5)(*v.stride())
-        in3, roi3 = (ctypes.c_int * 3)(X, Y, Z), (ctypes.c_int * 3)(*self.roi)
-        with torch.cuda.device(x.device):
-            check(lib.nv_augment_apply(v.data_ptr(), ctypes.cast(strides, ctypes.c_void_p), B, ctypes.cast(in3, ctypes.c_void_p), T,
-                                       params.data_ptr(), ctypes.cast(roi3, ctypes.c_void_p), self.fill, out.data_ptr(),
-                                       torch.cuda.current_stream().cuda_stream), "nv_augment_apply")
-        return out
+        params = _check_rows("VolumeAugment", "params", params, x.shape[0], 8, x.device)
+        return _run_pass("VolumeAugment", x, self.roi, self.fill, params, None, out)
 
     def __call__(self, x: torch.Tensor, step: Optional[int] = None) -> torch.Tensor:
         """The augmented batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
         The parameters used are kept in `last_params` (a device tensor; None for the identity)."""
         self._check_input(x)
         own = step is None
-        step = self.step if own else self._check_step(step)
+        step = self.step if own else _check_step(step)
         if self.is_identity(x):
             self.last_params = None
             out = x
@@ -206,9 +238,6 @@ class MixConfig(ctypes.Structure):
                 ("prob", ctypes.c_double), ("switch_prob", ctypes.c_double)]
 
 
-MIX_COLS = 12      # NV_MIX_COLS
-
-
 class VolumeMix:
     """Mixup / CutMix on the device, per sample (timm's `elem` mode): sample b is paired with B - 1 - b (`flip(0)`), mixed with
     probability `prob`, by CutMix rather than Mixup with probability `switch_prob` when both alphas are set; lambda ~ Beta(alpha, alpha)
@@ -236,11 +265,7 @@ class VolumeMix:
                 raise TypeError(f"VolumeMix: {name} must be a number, got {p!r}")
             if not (0.0 <= float(p) <= 1.0):
                 raise ValueError(f"VolumeMix: {name} {p} outside [0, 1]")
-        for name, value, top in (("seed", seed, 2 ** 64), ("rank", rank, 2 ** 31)):
-            if isinstance(value, bool) or not isinstance(value, int):
-                raise TypeError(f"VolumeMix: {name} must be an integer, got {value!r}")
-            if not (0 <= value < top):
-                raise ValueError(f"VolumeMix: {name} {value} outside [0, {top})")
+        _check_seed_rank("VolumeMix", seed, rank)
         self.mixup_alpha = None if mixup_alpha is None else float(mixup_alpha)
         self.cutmix_alpha = None if cutmix_alpha is None else float(cutmix_alpha)
         self.prob, self.switch_prob = float(prob), float(switch_prob)
@@ -253,30 +278,15 @@ class VolumeMix:
 
     @staticmethod
     def _check_input(x: torch.Tensor):
-        if not torch.is_tensor(x):
-            raise TypeError(f"VolumeMix: expected a tensor, got {type(x).__name__}")
-        if x.dim() not in (4, 5):
-            raise ValueError(f"VolumeMix: expected [B, X, Y, Z] or [B, X, Y, Z, T], got {tuple(x.shape)}")
-        if x.dtype != torch.float32:
-            raise TypeError(f"VolumeMix: dtype {x.dtype} unsupported (float32)")
-        if x.requires_grad:
-            raise ValueError("VolumeMix: the input requires grad - no gradient flows through the mix (detach it)")
-        if any(n == 0 for n in x.shape):
-            raise ValueError(f"VolumeMix: empty input {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("neurovit_amd.augment.VolumeMix: input must live on the MI355X (cuda) device - there is no CPU fallback")
+        _check_volume("VolumeMix", "mix", x)
 
     def params(self, B: int, step: int, roi, device=None) -> torch.Tensor:
         """int32 [B, 12] on the device for step `step`; roi: (Sx, Sy, Sz) of the batch that will be mixed (the CutMix box lives in it)."""
-        step = VolumeAugment._check_step(step)
-        if isinstance(B, bool) or not isinstance(B, int) or B <= 0:
-            raise ValueError(f"VolumeMix.params: B must be a positive integer, got {B!r}")
+        step = _check_step(step)
         roi = _triple(roi, "roi", int)
         if any(s <= 0 for s in roi):
             raise ValueError(f"VolumeMix: roi must be positive, got {roi}")
-        device = torch.device("cuda" if device is None else device)
-        if device.type != "cuda":
-            raise RuntimeError("neurovit_amd.augment.VolumeMix: parameters are drawn on the MI355X (cuda) device - there is no CPU fallback")
+        device = _draw_target("VolumeMix", B, device)
         out = torch.empty((B, MIX_COLS), dtype=torch.int32, device=device)
         cfg = MixConfig(ctypes.sizeof(MixConfig), (ctypes.c_int * 3)(*roi), self.mixup_alpha or 0.0, self.cutmix_alpha or 0.0, self.prob, self.switch_prob)
         with torch.cuda.device(device):
@@ -293,35 +303,13 @@ class VolumeMix:
             raise TypeError(f"VolumeMix.apply: augment must be a VolumeAugment, got {type(augment).__name__}")
         if (augment is None) != (augment_params is None):
             raise ValueError("VolumeMix.apply: augment and augment_params come together")
-        self._check_input(x)
-        four_d = x.dim() == 5
-        v = x if four_d else x.unsqueeze(-1)
-        B, X, Y, Z, T = v.shape
-        roi = (X, Y, Z) if augment is None else augment.roi
-        if any(s > n for s, n in zip(roi, (X, Y, Z))):
-            raise ValueError(f"VolumeMix: roi {roi} is larger than the input {(X, Y, Z)}")
-        if not (torch.is_tensor(mix) and mix.dtype == torch.int32 and tuple(mix.shape) == (B, MIX_COLS) and mix.device == x.device):
-            raise ValueError(f"VolumeMix.apply: mix must be int32 [{B}, {MIX_COLS}] on {x.device}")
-        mix = mix.contiguous()
+        roi = None if augment is None else augment.roi
+        _check_volume("VolumeMix", "mix", x, roi)
+        B = x.shape[0]
+        mix = _check_rows("VolumeMix", "mix", mix, B, MIX_COLS, x.device)
         if augment_params is not None:
-            if not (torch.is_tensor(augment_params) and augment_params.dtype == torch.int32 and tuple(augment_params.shape) == (B, 8)
-                    and augment_params.device == x.device):
-                raise ValueError(f"VolumeMix.apply: augment_params must be int32 [{B}, 8] on {x.device}")
-            augment_params = augment_params.contiguous()
-        shape = (B, *roi, T) if four_d else (B, *roi)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float32, device=x.device)
-        elif not (torch.is_tensor(out) and out.dtype == torch.float32 and tuple(out.shape) == shape and out.device == x.device
-                  and out.is_contiguous() and out.data_ptr() % 16 == 0):
-            raise ValueError(f"VolumeMix.apply: out must be a dense, 16-byte aligned float32 {shape} on {x.device}")
-        strides = (ctypes.c_long * 5)(*v.stride())
-        in3, roi3 = (ctypes.c_int * 3)(X, Y, Z), (ctypes.c_int * 3)(*roi)
-        with torch.cuda.device(x.device):
-            check(lib.nv_augment_mix(v.data_ptr(), ctypes.cast(strides, ctypes.c_void_p), B, ctypes.cast(in3, ctypes.c_void_p), T,
-                                     None if augment_params is None else augment_params.data_ptr(), mix.data_ptr(),
-                                     ctypes.cast(roi3, ctypes.c_void_p), 0.0 if augment is None else augment.fill, out.data_ptr(),
-                                     torch.cuda.current_stream().cuda_stream), "nv_augment_mix")
-        return out
+            augment_params = _check_rows("VolumeMix", "augment_params", augment_params, B, 8, x.device)
+        return _run_pass("VolumeMix", x, roi or tuple(x.shape[1:4]), 0.0 if augment is None else augment.fill, augment_params, mix, out)
 
     def __call__(self, x: torch.Tensor, step: Optional[int] = None, augment: Optional[VolumeAugment] = None) -> torch.Tensor:
         """The mixed batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
@@ -330,7 +318,7 @@ class VolumeMix:
         if augment is not None and not isinstance(augment, VolumeAugment):
             raise TypeError(f"VolumeMix: augment must be a VolumeAugment, got {type(augment).__name__}")
         own = step is None
-        step = self.step if own else VolumeAugment._check_step(step)
+        step = self.step if own else _check_step(step)
         self._check_input(x)
         if self.is_identity():
             self.last_mix = None

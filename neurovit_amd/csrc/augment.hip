@@ -1,18 +1,23 @@
 // Training augmentation on the device (neurovit_amd.augment.VolumeAugment): a per-sample random crop (monai's RandSpatialCrop with a fixed
 // size, the reference's DATASET_TRANSFORMS switch), integer translation, axis flips and an affine intensity change, for 3D volumes and
-// 4D series.  Every sample has its own offset, so the crop is no strided view: one streaming pass copies it.
+// 4D series, and Mixup / CutMix (neurovit_amd.augment.VolumeMix) fused with it.  Every sample has its own offset, so the crop is no
+// strided view: one streaming pass copies it, and a mixed batch is still read once and written once.
 //
 //   nv_augment_params   (config, seed, step, rank) -> params int32 [B, 8]: {ox, oy, oz, flip bits, bits of scale, bits of shift, 0, 0},
 //                       drawn on the device with nv_hash64 (the rule is in the header; tests/augment_ref.py restates it)
-//   nv_augment_apply    src fp32 [B, X, Y, Z, T] (any strides) + params -> out fp32 [B, Sx, Sy, Sz, T] dense
+//   nv_augment_apply    src fp32 [B, X, Y, Z, T] (any strides) + params -> out fp32 [B, Sx, Sy, Sz, T] dense: A_b, sample b under its row
+//   nv_augment_mix      the same + mix rows (nv_mix_params, mix.hip; the augmentation rows may be missing) -> out = A_b, (lambda A_b) +
+//                       (mu A_p), or A_p inside the box and A_b outside, each sample under its OWN row
 //
-// The copy is laid out like nv_mask_patches: a workgroup owns AG_SPAN consecutive elements of one output plane (b, i) - Sy Sz T contiguous
-// floats - so the grid follows the rows, not the batch; the 16-byte groups follow the alignment of the plane in `out` (split_span).  A
-// group whose four cells lie in one source row that is contiguous in memory is read with one 16-byte load when the address allows it
-// (load4), backwards under a z flip of a 3D volume; every other group (row ends, window edges, strided sources, a flipped series) is
-// gathered cell by cell.  Voxels move as 32-bit patterns and the intensity change is two separately rounded operations (contraction is
-// off for the whole file), skipped altogether for scale 1 / shift 0: that sample is a bit copy.  No atomics, every output element is
-// written once by one thread.
+// Both are one pass body (augment_pass), laid out like nv_mask_patches: a workgroup owns AG_SPAN consecutive elements of one output plane
+// (b, i) - Sy Sz T contiguous floats - so the grid follows the rows, not the batch; the 16-byte groups follow the alignment of the plane
+// in `out` (split_span).  A group whose four cells lie in one source row that is contiguous in memory is read with one 16-byte load when
+// the address allows it (load4), backwards under a z flip of a 3D volume; every other group (row ends, window edges, strided sources, a
+// flipped series) is gathered cell by cell.  A sample and its partner have rows of their own, so each side decides on its own whether a
+// group is one load.  A CutMix group in a row outside the box is the sample's own; in a row that crosses the box both sides' groups are
+// fetched and every cell takes its side (x and y are uniform over a group, z is not).  Voxels move as 32-bit patterns; the intensity
+// change and the Mixup blend are separately rounded operations (contraction is off for the whole file), the intensity change skipped
+// altogether for scale 1 / shift 0: that sample is a bit copy.  No atomics, every output element is written once by one thread.
 #include "attr_common.h"
 
 #pragma clang fp contract(off)
@@ -57,88 +62,206 @@ __global__ __launch_bounds__(AG_THREADS) void augment_params_kernel(AugDraw cfg,
   for (int i = 0; i < 8; ++i) params[8L * b + i] = row[i];
 }
 
-// ------------------------------------------------------------------------------------------------ apply
-struct AugGeom {
-  int X, Y, Z, T, Sx, Sy, Sz;
+// ------------------------------------------------------------------------------------------------ the pass
+struct PassGeom {
+  int B, X, Y, Z, T, Sx, Sy, Sz;
   long st_b, st_x, st_y, st_z, st_t;     // element strides of src
 };
 
-// Grid (B Sx, ceil(Sy Sz T / AG_SPAN)).  The offsets of a parameter row may be anything: every read is bounds-checked against the volume,
-// and a cell outside it gets `fill`.
-__global__ __launch_bounds__(AG_THREADS) void augment_apply_kernel(const unsigned* __restrict__ src, AugGeom g, const int* __restrict__ params, unsigned fill,
-                                                                   unsigned* __restrict__ out) {
+// What the pass writes for one sample on output plane i: the cells of A_s, singly or four at a time.  The offsets of a parameter row
+// may be anything: every read is bounds-checked against the volume, and a cell outside it gets `fill`.
+struct Side {
+  const unsigned* xp;                    // the source plane (valid when plane_in)
+  long oy, oz;
+  bool fy, fz, plane_in, copy, run;
+  float scale, shift;
+  unsigned fill;
+
+  __device__ __forceinline__ void init(const unsigned* src, const PassGeom& g, const int* aug, int s, int i, unsigned fill_bits) {
+    long ox = 0;
+    int flips = 0;
+    oy = 0; oz = 0; scale = 1.0f; shift = 0.0f;
+    if (aug) {                                             // (a NULL table is identity rows)
+      const int* row = aug + 8L * s;
+      ox = row[0]; oy = row[1]; oz = row[2]; flips = row[3];
+      scale = __int_as_float(row[4]); shift = __int_as_float(row[5]);
+    }
+    fy = flips & 2; fz = flips & 4;
+    copy = scale == 1.0f && shift == 0.0f;
+    fill = fill_bits;
+    const long sx = ox + ((flips & 1) ? g.Sx - 1 - i : i);
+    plane_in = sx >= 0 && sx < g.X;
+    xp = src + (long)s * g.st_b + (plane_in ? sx : 0) * g.st_x;
+    // a source row is one run of memory: ascending for a series with time innermost, in either direction for a volume
+    run = g.T > 1 ? (g.st_t == 1 && g.st_z == g.T && !fz) : g.st_z == 1;
+  }
+  __device__ __forceinline__ unsigned shade(unsigned u) const {
+    if (copy) return u;
+    const float m = __uint_as_float(u) * scale;
+    return __float_as_uint(m + shift);
+  }
+  // output cell (j, k, t) of the plane
+  __device__ __forceinline__ unsigned cell(const PassGeom& g, int j, int k, int t) const {
+    const long sy = oy + (fy ? g.Sy - 1 - j : j), sz = oz + (fz ? g.Sz - 1 - k : k);
+    if (!plane_in || sy < 0 || sy >= g.Y || sz < 0 || sz >= g.Z) return fill;
+    return shade(xp[sy * g.st_y + sz * g.st_z + t * g.st_t]);
+  }
+  // the four cells c .. c + 3 of output row j (c + 3 < Sz T): one 16-byte load where the source allows it
+  __device__ __forceinline__ u32x4 group(const PassGeom& g, int j, int c) const {
+    const int T = g.T;
+    if (run) {
+      const long sy = oy + (fy ? g.Sy - 1 - j : j);
+      if (!plane_in || sy < 0 || sy >= g.Y) return u32x4{fill, fill, fill, fill};
+      const long lowest = fz ? oz + (g.Sz - 1 - c) - 3 : oz * T + c;          // source cell of the group's lowest address
+      if (lowest >= 0 && lowest + 3 < (long)g.Z * T) {
+        const unsigned* p = xp + sy * g.st_y + lowest;
+        const u32x4 w = load4(p, is_aligned16(p));
+        u32x4 v = fz ? u32x4{w[3], w[2], w[1], w[0]} : w;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) v[m] = shade(v[m]);
+        return v;
+      }
+    }
+    u32x4 v;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const int cc = c + m, k = T > 1 ? cc / T : cc;
+      v[m] = cell(g, j, k, cc - k * T);
+    }
+    return v;
+  }
+};
+
+// CutMix takes a cell from one side or the other: the side is SELECTED field by field and fetched through one code path, so that lanes
+// inside and outside the box do not run two fetches one after the other.
+__device__ __forceinline__ Side pick(bool partner, const Side& own, const Side& other) {
+  Side s;
+  s.xp = partner ? other.xp : own.xp;
+  s.oy = partner ? other.oy : own.oy; s.oz = partner ? other.oz : own.oz;
+  s.fy = partner ? other.fy : own.fy; s.fz = partner ? other.fz : own.fz;
+  s.plane_in = partner ? other.plane_in : own.plane_in; s.copy = partner ? other.copy : own.copy; s.run = partner ? other.run : own.run;
+  s.scale = partner ? other.scale : own.scale; s.shift = partner ? other.shift : own.shift;
+  s.fill = own.fill;
+  return s;
+}
+
+// One workgroup of the grid (B Sx, ceil(Sy Sz T / AG_SPAN)).  Mix = false is the apply pass: it reads no mix table and has one Side;
+// everything about a partner, the blend and the box exists for Mix = true alone.
+template <bool Mix>
+__device__ __forceinline__ void augment_pass(const unsigned* __restrict__ src, const PassGeom& g, const int* __restrict__ aug, const int* __restrict__ mix,
+                                             unsigned fill, unsigned* __restrict__ out) {
   const int tid = threadIdx.x;
   const int plane = blockIdx.x, b = plane / g.Sx, i = plane - b * g.Sx;
   const int T = g.T, L = g.Sz * T, P = g.Sy * L;           // cells of one output row (j) and of the plane
   const int e0 = blockIdx.y * AG_SPAN, len = min(AG_SPAN, P - e0);
-  const int* row = params + 8L * b;
-  const long ox = row[0], oy = row[1], oz = row[2];
-  const bool fx = row[3] & 1, fy = row[3] & 2, fz = row[3] & 4;
-  const float scale = __int_as_float(row[4]), shift = __int_as_float(row[5]);
-  const bool copy = scale == 1.0f && shift == 0.0f;
+  int mode = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0, partner = b;
+  float lam = 1.0f;
+  if constexpr (Mix) {
+    const int* mrow = mix + (long)NV_MIX_COLS * b;
+    partner = mrow[0];
+    lam = __int_as_float(mrow[2]);
+    mode = mrow[1];
+    if (mode < 0 || mode > 2 || lam == 1.0f || partner < 0 || partner >= g.B) mode = 0;        // A_b alone: the partner is not read
+    y0 = mrow[7]; y1 = mrow[8]; z0 = mrow[9]; z1 = mrow[10];
+    const bool x_in = i >= mrow[5] && i < mrow[6];         // (cutmix) this plane crosses the box
+    if (mode == 2 && !x_in) mode = 0;
+  }
+  const float mu = 1.0f - lam;
+  Side own, other;                                         // (other: the partner under its own row, Mix alone)
+  own.init(src, g, aug, b, i, fill);
+  if constexpr (Mix) other.init(src, g, aug, mode ? partner : b, i, fill);
   const long first = (long)plane * P + e0;
   unsigned* o = out + first;
   const Span s = split_span(first, len);
-  const u32x4 fill4 = {fill, fill, fill, fill};
-  const long sx = ox + (fx ? g.Sx - 1 - i : i);
-  if (sx < 0 || sx >= g.X) {                               // (uniform over the workgroup) the whole plane lies outside the volume
+  if (!Mix && !own.plane_in) {                             // (uniform over the workgroup) the whole plane lies outside the volume
+    const u32x4 fill4 = {fill, fill, fill, fill};
     for (int e = tid; e < s.head; e += AG_THREADS) o[e] = fill;
     for (int e = s.tail + tid; e < len; e += AG_THREADS) o[e] = fill;
     for (int q = tid; q < s.groups; q += AG_THREADS) *reinterpret_cast<u32x4*>(o + s.head + 4 * q) = fill4;
     return;
   }
-  const unsigned* xp = src + (long)b * g.st_b + sx * g.st_x;
-  auto shade = [&](unsigned u) {
-    if (copy) return u;
-    const float m = __uint_as_float(u) * scale;
-    return __float_as_uint(m + shift);
-  };
-  auto cell = [&](int j, int c) {                          // output cell (j, c = k T + t) of this plane
-    const int k = T > 1 ? c / T : c, t = c - k * T;
-    const long sy = oy + (fy ? g.Sy - 1 - j : j), sz = oz + (fz ? g.Sz - 1 - k : k);
-    if (sy < 0 || sy >= g.Y || sz < 0 || sz >= g.Z) return fill;
-    return shade(xp[sy * g.st_y + sz * g.st_z + t * g.st_t]);
+  auto blend = [&](unsigned a, unsigned p) {
+    const float l = lam * __uint_as_float(a), r = mu * __uint_as_float(p);
+    return __float_as_uint(l + r);
   };
   auto single = [&](int e) {
-    const int j = (e0 + e) / L;
-    o[e] = cell(j, (e0 + e) - j * L);
+    const int j = (e0 + e) / L, c = (e0 + e) - j * L, k = T > 1 ? c / T : c, t = c - k * T;
+    if (!Mix || mode == 0) return own.cell(g, j, k, t);
+    if (mode == 1) return blend(own.cell(g, j, k, t), other.cell(g, j, k, t));
+    return pick(j >= y0 && j < y1 && k >= z0 && k < z1, own, other).cell(g, j, k, t);
   };
-  for (int e = tid; e < s.head; e += AG_THREADS) single(e);
-  for (int e = s.tail + tid; e < len; e += AG_THREADS) single(e);
-  // a source row is one run of memory: ascending for a series with time innermost, in either direction for a volume
-  const bool run = T > 1 ? (g.st_t == 1 && g.st_z == T && !fz) : g.st_z == 1;
-  const long row_cells = (long)g.Z * T;
+  for (int e = tid; e < s.head; e += AG_THREADS) o[e] = single(e);
+  for (int e = s.tail + tid; e < len; e += AG_THREADS) o[e] = single(e);
   for (int q = tid; q < s.groups; q += AG_THREADS) {
     const int e = s.head + 4 * q;
-    int j = (e0 + e) / L, c = (e0 + e) - j * L;
+    const int j = (e0 + e) / L, c = (e0 + e) - j * L;
     u32x4 v;
-    bool done = false;
-    if (run && c + 3 < L) {                                // the four cells share the output row j
-      const long sy = oy + (fy ? g.Sy - 1 - j : j);
-      if (sy < 0 || sy >= g.Y) {
-        v = fill4;
-        done = true;
-      } else {
-        const long lowest = fz ? oz + (g.Sz - 1 - c) - 3 : oz * T + c;       // source cell of the group's lowest address
-        if (lowest >= 0 && lowest + 3 < row_cells) {
-          const unsigned* p = xp + sy * g.st_y + lowest;
-          const u32x4 w = load4(p, is_aligned16(p));
-          v = fz ? u32x4{w[3], w[2], w[1], w[0]} : w;
+    if (c + 3 < L) {                                       // the four cells share the output row j
+      if (!Mix || mode == 0) {
+        v = own.group(g, j, c);
+      } else if (mode == 1) {
+        const u32x4 a = own.group(g, j, c), p = other.group(g, j, c);
 #pragma unroll
-          for (int m = 0; m < 4; ++m) v[m] = shade(v[m]);
-          done = true;
+        for (int m = 0; m < 4; ++m) v[m] = blend(a[m], p[m]);
+      } else if (j < y0 || j >= y1) {
+        v = own.group(g, j, c);
+      } else {
+        // a row that crosses the box: both sides' groups are fetched side by side - unless the group lies wholly outside (inside) the
+        // box in z, then only the sample's (the partner's) - and every cell takes its side.  No cell-by-cell path for a group that a z
+        // face cuts: nearly every wave of such a row holds one, and would wait for it.
+        const int k_lo = T > 1 ? c / T : c, k_hi = T > 1 ? (c + 3) / T : c + 3;
+        const bool none_in = k_hi < z0 || k_lo >= z1, all_in = k_lo >= z0 && k_hi < z1;
+        u32x4 a = {0, 0, 0, 0}, p = {0, 0, 0, 0};
+        if (!all_in) a = own.group(g, j, c);
+        if (!none_in) p = other.group(g, j, c);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+          const int k = T > 1 ? (c + m) / T : c + m;
+          v[m] = (k >= z0 && k < z1) ? p[m] : a[m];
         }
       }
-    }
-    if (!done) {
+    } else {                                               // the group straddles output rows (e + m < len: every cell lies in the plane)
 #pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        v[m] = cell(j, c);
-        if (++c == L) { c = 0; ++j; }                      // (a group may straddle rows; j < Sy for every cell that is read, since e + m < len)
-      }
+      for (int m = 0; m < 4; ++m) v[m] = single(e + m);
     }
     *reinterpret_cast<u32x4*>(o + e) = v;
   }
+}
+
+__global__ __launch_bounds__(AG_THREADS) void augment_apply_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ params, unsigned fill,
+                                                                   unsigned* __restrict__ out) {
+  augment_pass<false>(src, g, params, nullptr, fill, out);
+}
+__global__ __launch_bounds__(AG_THREADS) void augment_mix_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ aug, const int* __restrict__ mix,
+                                                                 unsigned fill, unsigned* __restrict__ out) {
+  augment_pass<true>(src, g, aug, mix, fill, out);
+}
+
+// The checks, the geometry and the launch shape that the two entry points share; `who` is the entry point, for the messages.
+template <bool Mix>
+int launch_pass(const char* who, const float* src, const long* strides5, int B, const int* in3, int T, const int* aug, const int* mix, const int* roi3, float fill,
+                float* out, void* stream) {
+  NV_CHECK_ARG(src && strides5 && in3 && (Mix ? mix : aug) && roi3 && out && B > 0 && T > 0, "%s: bad arguments (null pointer, or B / T not positive)", who);
+  PassGeom g;
+  g.B = B; g.X = in3[0]; g.Y = in3[1]; g.Z = in3[2]; g.T = T; g.Sx = roi3[0]; g.Sy = roi3[1]; g.Sz = roi3[2];
+  NV_CHECK_ARG(g.X > 0 && g.Y > 0 && g.Z > 0 && g.Sx > 0 && g.Sy > 0 && g.Sz > 0, "%s: input %d x %d x %d and roi %d x %d x %d must be positive", who, g.X, g.Y,
+               g.Z, g.Sx, g.Sy, g.Sz);
+  NV_CHECK_ARG(g.Sx <= g.X && g.Sy <= g.Y && g.Sz <= g.Z, "%s: roi %d x %d x %d is larger than the input %d x %d x %d", who, g.Sx, g.Sy, g.Sz, g.X, g.Y, g.Z);
+  const long planes = (long)B * g.Sx, P = (long)g.Sy * g.Sz * T, spans = (P + AG_SPAN - 1) / AG_SPAN;
+  NV_CHECK_ARG(planes < (1L << 31) && spans <= 65535 && (long)g.Z * T < (1L << 31),
+               "%s: %ld output planes of %ld cells beyond one launch (at most 2^31 - 1 planes of %ld cells)", who, planes, P, 65535L * AG_SPAN);
+  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(src, 4) && nv_aligned(aug, 4) && nv_aligned(mix, 4), "%s: out 16-byte aligned, src and %s 4-byte aligned", who,
+               Mix ? "the two tables" : "params");
+  g.st_b = strides5[0]; g.st_x = strides5[1]; g.st_y = strides5[2]; g.st_z = strides5[3]; g.st_t = strides5[4];
+  union { float f; unsigned u; } fbits;
+  fbits.f = fill;
+  const dim3 grid((unsigned)planes, (unsigned)spans);
+  if constexpr (Mix)
+    hipLaunchKernelGGL(augment_mix_kernel, grid, dim3(AG_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, aug, mix, fbits.u, (unsigned*)out);
+  else
+    hipLaunchKernelGGL(augment_apply_kernel, grid, dim3(AG_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, aug, fbits.u, (unsigned*)out);
+  NV_CHECK_LAUNCH(who);
+  return NV_OK;
 }
 }  // namespace
 
@@ -172,22 +295,10 @@ extern "C" int nv_augment_params(const nv_augment_config* cfg, unsigned long see
 
 extern "C" int nv_augment_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* params, const int* roi3, float fill,
                                 float* out, void* stream) {
-  NV_CHECK_ARG(src && strides5 && in3 && params && roi3 && out && B > 0 && T > 0, "nv_augment_apply: bad arguments (null pointer, or B / T not positive)");
-  AugGeom g;
-  g.X = in3[0]; g.Y = in3[1]; g.Z = in3[2]; g.T = T; g.Sx = roi3[0]; g.Sy = roi3[1]; g.Sz = roi3[2];
-  NV_CHECK_ARG(g.X > 0 && g.Y > 0 && g.Z > 0 && g.Sx > 0 && g.Sy > 0 && g.Sz > 0, "nv_augment_apply: input %d x %d x %d and roi %d x %d x %d must be positive",
-               g.X, g.Y, g.Z, g.Sx, g.Sy, g.Sz);
-  NV_CHECK_ARG(g.Sx <= g.X && g.Sy <= g.Y && g.Sz <= g.Z, "nv_augment_apply: roi %d x %d x %d is larger than the input %d x %d x %d", g.Sx, g.Sy, g.Sz, g.X,
-               g.Y, g.Z);
-  const long planes = (long)B * g.Sx, P = (long)g.Sy * g.Sz * T, spans = (P + AG_SPAN - 1) / AG_SPAN;
-  NV_CHECK_ARG(planes < (1L << 31) && spans <= 65535 && (long)g.Z * T < (1L << 31),
-               "nv_augment_apply: %ld output planes of %ld cells beyond one launch (at most 2^31 - 1 planes of %ld cells)", planes, P, 65535L * AG_SPAN);
-  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(src, 4) && nv_aligned(params, 4), "nv_augment_apply: out 16-byte aligned, src and params 4-byte aligned");
-  g.st_b = strides5[0]; g.st_x = strides5[1]; g.st_y = strides5[2]; g.st_z = strides5[3]; g.st_t = strides5[4];
-  union { float f; unsigned u; } fbits;
-  fbits.f = fill;
-  hipLaunchKernelGGL(augment_apply_kernel, dim3((unsigned)planes, (unsigned)spans), dim3(AG_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, params,
-                     fbits.u, (unsigned*)out);
-  NV_CHECK_LAUNCH("nv_augment_apply");
-  return NV_OK;
+  return launch_pass<false>("nv_augment_apply", src, strides5, B, in3, T, params, nullptr, roi3, fill, out, stream);
+}
+
+extern "C" int nv_augment_mix(const float* src, const long* strides5, int B, const int* in3, int T, const int* aug, const int* mix, const int* roi3, float fill,
+                              float* out, void* stream) {
+  return launch_pass<true>("nv_augment_mix", src, strides5, B, in3, T, aug, mix, roi3, fill, out, stream);
 }

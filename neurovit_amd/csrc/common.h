@@ -237,27 +237,33 @@ __device__ __forceinline__ float drop_factor(const DropCfg& d, unsigned long lon
   return (field >= d.thresh) ? d.scale : 0.f;
 }
 
-// ---- nn.CrossEntropyLoss of ONE row (256 threads, every thread returns the row's loss term): shared by ce_loss_kernel (optim.hip) and the
-// fused head step (norm.hip) so that both produce the same bits.  red: 4 floats of LDS.  dl (optional): d(loss)/d(logits) of the row.
-// torch raises a device-side assert for a label outside [0, C); here nothing may read out of bounds or abort the stream: the term is
-// NaN (visible at the first .item()) and the row's gradient is that of no target.
-__device__ __forceinline__ float ce_row_term(const float* __restrict__ row, long tl, int C, float gscale_over_B, float* red, float* __restrict__ dl) {
+// The row's maximum and the sum of exp(row - max), in every thread: the wave butterflies, then the four waves through red[0 .. 3].
+__device__ __forceinline__ void ce_row_max_sumexp(const float* __restrict__ row, int C, float* red, float& mx, float& se) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  float mx = -INFINITY;
+  mx = -INFINITY;
   for (int c = tid; c < C; c += 256) mx = fmaxf(mx, row[c]);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  mx = wave_max(mx);
   if (lane == 0) red[wid] = mx;
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   __syncthreads();
-  float se = 0.f;
+  se = 0.f;
   for (int c = tid; c < C; c += 256) se += expf(row[c] - mx);
   se = wave_sum(se);
   if (lane == 0) red[wid] = se;
   __syncthreads();
   se = (red[0] + red[1]) + (red[2] + red[3]);
   __syncthreads();
+}
+
+// ---- nn.CrossEntropyLoss of ONE row (256 threads, every thread returns the row's loss term): shared by ce_loss_kernel (optim.hip) and the
+// fused head step (norm.hip) so that both produce the same bits.  red: 4 floats of LDS.  dl (optional): d(loss)/d(logits) of the row.
+// torch raises a device-side assert for a label outside [0, C); here nothing may read out of bounds or abort the stream: the term is
+// NaN (visible at the first .item()) and the row's gradient is that of no target.
+__device__ __forceinline__ float ce_row_term(const float* __restrict__ row, long tl, int C, float gscale_over_B, float* red, float* __restrict__ dl) {
+  const int tid = threadIdx.x;
+  float mx, se;
+  ce_row_max_sumexp(row, C, red, mx, se);
   const bool t_ok = tl >= 0 && tl < (long)C;
   const int t = t_ok ? (int)tl : -1;
   const float term = t_ok ? (mx + logf(se)) - row[t] : __builtin_nanf("");
@@ -267,8 +273,8 @@ __device__ __forceinline__ float ce_row_term(const float* __restrict__ row, long
 }
 
 // ---- the soft-target cross-entropy of nv_loss_opts (label smoothing, class weights, a mixed target; the definition is in the header):
-// a second row body beside ce_row_term, shared by ce_loss_soft_kernel (optim.hip) and the soft head step (norm.hip) so that both
-// produce the same bits.  The existing kernels keep ce_row_term.
+// the row body of ce_loss_soft_kernel (optim.hip) and of the head step's soft form (norm.hip), so that both produce the same bits.  It
+// opens like ce_row_term (ce_row_max_sumexp); the arithmetic behind that differs by design.
 struct CeSoft {
   float eps;                 // label smoothing
   const float* w;            // class weights [C] or null
@@ -318,20 +324,8 @@ __device__ __forceinline__ double ce_soft_denominator(const long* __restrict__ l
 __device__ __forceinline__ float ce_row_term_soft(const float* __restrict__ row, const CeTarget t, int C, const CeSoft& o, float gscale_over_D, float* red,
                                                   float* __restrict__ dl) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  float mx = -INFINITY;
-  for (int c = tid; c < C; c += 256) mx = fmaxf(mx, row[c]);
-  mx = wave_max(mx);
-  if (lane == 0) red[wid] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  float se = 0.f;
-  for (int c = tid; c < C; c += 256) se += expf(row[c] - mx);
-  se = wave_sum(se);
-  if (lane == 0) red[wid] = se;
-  __syncthreads();
-  se = (red[0] + red[1]) + (red[2] + red[3]);
-  __syncthreads();
+  float mx, se;
+  ce_row_max_sumexp(row, C, red, mx, se);
   const float lse = mx + logf(se), mu = 1.0f - t.lam, keep = 1.0f - o.eps, even = o.eps / (float)C;
   auto wq = [&](int c) {                                  // w_c q'_c
     const float q = (c == t.ya ? t.lam : 0.f) + (c == t.yb ? mu : 0.f);

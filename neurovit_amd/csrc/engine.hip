@@ -1148,8 +1148,8 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
                               nullptr, drop_p, emb_drop_p, drop_seed, stream, aux_stream);
 }
 
-// lo: nv_loss_opts (label smoothing, class weights, a mixed target) or NULL.  With no option on, the loss calls below are the ones of
-// nv_vit_train_step; with one, their soft forms (nv_head_step_soft / nv_ce_loss_soft) stand in their place and nothing else differs.
+// lo: nv_loss_opts (label smoothing, class weights, a mixed target) or NULL.  The loss calls below are nv_head_step_soft / nv_ce_loss_soft,
+// which run the index-target kernels of nv_vit_train_step when no option is on; nothing else differs.
 extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                                     float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
                                     const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
@@ -1175,7 +1175,6 @@ extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float
     NV_CHECK_ARG(dp->comm_stream != stream && dp->comm_stream != aux_stream, "nv_vit_train_step: nv_dp_plan.comm_stream must be a stream of its own");
   }
   if (int rc = check_loss_opts(lo, "nv_vit_train_step_ex")) return rc;
-  const bool soft = loss_opts_on(lo);
   const float lscale = hp->loss_scale > 0.f ? hp->loss_scale : 1.f;      // static loss scale: folded into d(loss)/d(logits), undone by the update's grad_scale
   // the head's forward, the loss and the head's backward as two launches instead of five (nv_head_step: bit-identical to the three calls;
   // it needs num_classes <= dim and dim % 8 == 0 - other heads take the five-launch path, which has no such limit)
@@ -1186,20 +1185,12 @@ extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float
   if (head_fused) {
     char* ws = (char*)workspace;
     const int Ll = D.L - 1;
-    if (soft)
-      RUN(nv_head_step_soft((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
-                            labels, lscale, hp->loss_scale_state, lo, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
-                            ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
-                            hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream));
-    else
-      RUN(nv_head_step_scaled((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
-                              labels, lscale, hp->loss_scale_state, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
-                              ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
-                              hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream));
-  } else if (soft) {
-    RUN(nv_ce_loss_soft(logits, labels, B, cfg->num_classes, lscale, hp->loss_scale_state, lo, loss, dlogits, stream));
+    RUN(nv_head_step_soft((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
+                          labels, lscale, hp->loss_scale_state, lo, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
+                          ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
+                          hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream));
   } else {
-    RUN(nv_ce_loss_scaled(logits, labels, B, cfg->num_classes, lscale, hp->loss_scale_state, loss, dlogits, stream));
+    RUN(nv_ce_loss_soft(logits, labels, B, cfg->num_classes, lscale, hp->loss_scale_state, lo, loss, dlogits, stream));
   }
   nv_adamw_arena opt;
   opt.struct_size = (int)sizeof(opt); opt.step = hp->step; opt.lr = hp->lr; opt.beta1 = hp->beta1; opt.beta2 = hp->beta2; opt.eps = hp->eps;

@@ -1316,9 +1316,17 @@ __device__ __forceinline__ float partial_column_sum(const float* part, int R, lo
   }
   return ((grp[0] + grp[1]) + (grp[2] + grp[3])) + ((grp[4] + grp[5]) + (grp[6] + grp[7]));
 }
+// The loss form is a template argument of both launches.  Soft = false: ce_row_term over the labels, the mean taken in launch 2.
+// Soft = true (nv_loss_opts): ce_row_term_soft; every workgroup of launch 1 forms the denominator D itself (labels, lambdas and weights
+// only: no atomics, no extra launch) and stores its row's term already divided by D, so launch 2 only adds the terms up - in
+// ce_loss_soft_kernel's order.  The CeSoft argument and the LDS of the denominator exist for Soft = true alone.
+struct NoSoft {};
+template <bool Soft> using SoftArg = std::conditional_t<Soft, CeSoft, NoSoft>;
+
 // launch 1: workgroup b = volume b (forward, loss term, backward to the cls row of g), the others clear g / g16 outside the cls rows
-__global__ __launch_bounds__(256) void head_rows_kernel(const HeadStep a) {
-  extern __shared__ __attribute__((aligned(16))) float sh[];   // d floats + 8 scratch + 4 (loss reductions)
+template <bool Soft>
+__global__ __launch_bounds__(256) void head_rows_kernel(const HeadStep a, const SoftArg<Soft> o) {
+  extern __shared__ __attribute__((aligned(16))) float sh[];   // d floats + 8 scratch + 4 (loss reductions) (+ 4 doubles, Soft: the denominator)
   if ((int)blockIdx.x >= a.B) {
     const int part = blockIdx.x - a.B, nparts = gridDim.x - a.B;
     zero_rows_except(reinterpret_cast<char*>(a.g), (long)a.B * a.n, (long)a.d * 4, a.n, part, nparts);
@@ -1326,20 +1334,29 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const HeadStep a) {
     return;
   }
   const int b = blockIdx.x;
+  float D = (float)a.B;
+  if constexpr (Soft) D = (float)ce_soft_denominator(a.labels, o, a.B, a.C, reinterpret_cast<double*>(sh + a.d + 12));   // (d % 8 == 0: 8-byte aligned)
   head_fwd_row(b, sh, a.x, a.row_stride, a.d, a.gamma, a.beta, a.eps, a.W, a.bias, a.C, a.xh, a.stats, a.logits);
   __syncthreads();                                   // logits[b], stats[b] (global, written by this workgroup) are visible to all of it
-  const float term = ce_row_term(a.logits + (long)b * a.C, a.labels[b], a.C, (a.scale_state ? a.grad_scale * a.scale_state[0] : a.grad_scale) / (float)a.B, sh + a.d + 8, a.dlogits + (long)b * a.C);
+  const float gs = (a.scale_state ? a.grad_scale * a.scale_state[0] : a.grad_scale) / D;
+  const float* row = a.logits + (long)b * a.C;
+  float* red = sh + a.d + 8;
+  float* dl = a.dlogits + (long)b * a.C;
+  float term;
+  if constexpr (Soft) term = ce_row_term_soft(row, ce_soft_target(a.labels, o, b, a.B, a.C), a.C, o, gs, red, dl) / D;
+  else term = ce_row_term(row, a.labels[b], a.C, gs, red, dl);
   if (threadIdx.x == 0) a.terms[b] = term;
   __syncthreads();
   head_bwd_x_row(b, sh, a.dlogits, a.C, a.W, a.x, a.row_stride, a.stats, a.gamma, a.d, a.n, a.g, a.ldg, a.g16, a.ldg16, a.partials, a.drop, 0, a.fp16);
 }
 // launch 2: everything that sums over the volumes - the loss, (dgamma, dbeta, column sum of the cls-row gradient), dW, dbias
+template <bool Soft>
 __global__ __launch_bounds__(256) void head_sums_kernel(const HeadStep a) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx == 0) {
     float total = 0.f;
     for (int b = 0; b < a.B; ++b) total += a.terms[b];
-    a.loss[0] = total / (float)a.B;
+    a.loss[0] = Soft ? total : total / (float)a.B;
   }
   if (idx < 3L * a.d) {
     const int i = (int)idx;
@@ -1365,25 +1382,20 @@ __global__ __launch_bounds__(256) void head_sums_kernel(const HeadStep a) {
 
 extern "C" long nv_head_step_workspace_bytes(int B, int d) { return nv_head_bwd_workspace_bytes(B, d) + (long)((B + 3) / 4 * 4) * sizeof(float); }
 
-extern "C" int nv_head_step(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
-                            const float* bias, int C, const long* labels, float grad_scale, float* xh, float* stats, float* logits, float* loss,
-                            float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta, float* dW, float* dbias,
-                            float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p, void* stream) {
-  return nv_head_step_scaled(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, nullptr, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
-                             dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
-}
-
-// scale_state (may be NULL): the device block of nv_loss_scale_init - dlogits (and with them every gradient) carry its current scale
-extern "C" int nv_head_step_scaled(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
-                                   const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, float* xh, float* stats,
-                                   float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma,
-                                   float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
-                                   unsigned long drop_seed, float drop_p, void* stream) {
-  NV_CHECK_ARG(B > 0 && d > 0 && C > 0 && C <= d && n > 0, "nv_head_step: B = %d, d = %d, C = %d, n = %d", B, d, C, n);
+// The one host body of the three entry points.  scale_state (may be NULL): the device block of nv_loss_scale_init - dlogits (and with
+// them every gradient) carry its current scale.  opts (checked by the caller) with no option on, or NULL: the index-target loss.
+static int head_step(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W, const float* bias, int C,
+                     const long* labels, float grad_scale, const float* scale_state, const nv_loss_opts* opts, float* xh, float* stats, float* logits,
+                     float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta, float* dW, float* dbias,
+                     float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p, void* stream) {
+  const bool soft = loss_opts_on(opts);
+  const char* who = soft ? "nv_head_step_soft" : "nv_head_step";
+  NV_CHECK_ARG(B > 0 && d > 0 && C > 0 && C <= d && n > 0, "%s: B = %d, d = %d, C = %d, n = %d", who, B, d, C, n);
   NV_CHECK_ARG(x && gamma && beta && W && bias && labels && xh && stats && logits && loss && dlogits && g && dgamma && dbeta && dW && dbias && workspace,
-               "nv_head_step: null pointer");
-  NV_CHECK_ARG(ws_bytes >= nv_head_step_workspace_bytes(B, d), "nv_head_step: workspace too small");
-  NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d) && (d % 8) == 0 && nv_aligned16(g) && (!g16 || nv_aligned16(g16)), "nv_head_step: g / g16 must be dense [B*n, d], 16-byte aligned, d a multiple of 8");
+               "%s: null pointer", who);
+  NV_CHECK_ARG(ws_bytes >= nv_head_step_workspace_bytes(B, d), "%s: workspace too small", who);
+  NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d) && (d % 8) == 0 && nv_aligned16(g) && (!g16 || nv_aligned16(g16)),
+               "%s: g / g16 must be dense [B*n, d], 16-byte aligned, d a multiple of 8", who);
   HeadStep a;
   a.x = x; a.row_stride = row_stride; a.B = B; a.d = d; a.C = C; a.n = n; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias;
   a.labels = labels; a.grad_scale = grad_scale; a.xh = xh; a.stats = stats; a.logits = logits; a.loss = loss; a.dlogits = dlogits;
@@ -1393,63 +1405,32 @@ extern "C" int nv_head_step_scaled(const float* x, long row_stride, int B, int d
   const long fill_bytes = (long)B * n * d * (g16 ? 6 : 4);
   int fill_blocks = (int)((fill_bytes + (1 << 16) - 1) >> 16);            // ~64 KiB per workgroup
   if (fill_blocks > 1024) fill_blocks = 1024;
-  hipLaunchKernelGGL(head_rows_kernel, dim3(B + fill_blocks), dim3(256), (d + 12) * sizeof(float), (hipStream_t)stream, a);
-  NV_CHECK_LAUNCH("nv_head_step/rows");
-  const long outs = 3L * d + (long)C * d;
-  hipLaunchKernelGGL(head_sums_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  NV_CHECK_LAUNCH("nv_head_step");
+  const dim3 rows(B + fill_blocks), sums((unsigned)((3L * d + (long)C * d + 255) / 256));
+  const hipStream_t s = (hipStream_t)stream;
+  if (soft) hipLaunchKernelGGL(head_rows_kernel<true>, rows, dim3(256), (d + 12 + 8) * sizeof(float), s, a, make_ce_soft(opts));
+  else hipLaunchKernelGGL(head_rows_kernel<false>, rows, dim3(256), (d + 12) * sizeof(float), s, a, NoSoft{});
+  NV_CHECK_LAUNCH(soft ? "nv_head_step_soft/rows" : "nv_head_step/rows");
+  if (soft) hipLaunchKernelGGL(head_sums_kernel<true>, sums, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(head_sums_kernel<false>, sums, dim3(256), 0, s, a);
+  NV_CHECK_LAUNCH(who);
   return NV_OK;
 }
 
-// ---- nv_head_step with nv_loss_opts: the two launches of nv_head_step with ce_row_term_soft in place of ce_row_term.  Every workgroup
-// of launch 1 forms the denominator D itself (labels, lambdas and weights only: no atomics, no extra launch) and stores its row's term
-// already divided by D, so launch 2 only adds the terms up - in ce_loss_soft_kernel's order.  head_rows_kernel / head_sums_kernel stay
-// as they are; what differs from them is the loss line of each.
-__global__ __launch_bounds__(256) void head_rows_soft_kernel(const HeadStep a, const CeSoft o) {
-  extern __shared__ __attribute__((aligned(16))) float sh[];   // d floats + 8 scratch + 4 (loss reductions) + 4 doubles (the denominator)
-  if ((int)blockIdx.x >= a.B) {
-    const int part = blockIdx.x - a.B, nparts = gridDim.x - a.B;
-    zero_rows_except(reinterpret_cast<char*>(a.g), (long)a.B * a.n, (long)a.d * 4, a.n, part, nparts);
-    if (a.g16) zero_rows_except(reinterpret_cast<char*>(a.g16), (long)a.B * a.n, (long)a.d * 2, a.n, part, nparts);
-    return;
-  }
-  const int b = blockIdx.x;
-  const float D = (float)ce_soft_denominator(a.labels, o, a.B, a.C, reinterpret_cast<double*>(sh + a.d + 12));   // (d % 8 == 0: 8-byte aligned)
-  head_fwd_row(b, sh, a.x, a.row_stride, a.d, a.gamma, a.beta, a.eps, a.W, a.bias, a.C, a.xh, a.stats, a.logits);
-  __syncthreads();
-  const float gs = a.scale_state ? a.grad_scale * a.scale_state[0] : a.grad_scale;
-  const float term = ce_row_term_soft(a.logits + (long)b * a.C, ce_soft_target(a.labels, o, b, a.B, a.C), a.C, o, gs / D, sh + a.d + 8, a.dlogits + (long)b * a.C) / D;
-  if (threadIdx.x == 0) a.terms[b] = term;
-  __syncthreads();
-  head_bwd_x_row(b, sh, a.dlogits, a.C, a.W, a.x, a.row_stride, a.stats, a.gamma, a.d, a.n, a.g, a.ldg, a.g16, a.ldg16, a.partials, a.drop, 0, a.fp16);
+extern "C" int nv_head_step(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                            const float* bias, int C, const long* labels, float grad_scale, float* xh, float* stats, float* logits, float* loss,
+                            float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta, float* dW, float* dbias,
+                            float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p, void* stream) {
+  return head_step(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, nullptr, nullptr, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
+                   dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
 }
-__global__ __launch_bounds__(256) void head_sums_soft_kernel(const HeadStep a) {
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  if (idx == 0) {
-    float total = 0.f;
-    for (int b = 0; b < a.B; ++b) total += a.terms[b];
-    a.loss[0] = total;
-  }
-  if (idx < 3L * a.d) {
-    const int i = (int)idx;
-    const float s = partial_column_sum(a.partials, a.B, 3L * a.d, i);
-    const int seg = i / a.d, c = i - seg * a.d;
-    float* o = seg == 0 ? a.dgamma : (seg == 1 ? a.dbeta : a.dcolsum);
-    if (o) o[c] = a.accumulate ? o[c] + s : s;
-    return;
-  }
-  const long j = idx - 3L * a.d;
-  if (j < (long)a.C * a.d) {
-    const int c = (int)(j / a.d), k = (int)(j - (long)c * a.d);
-    float s = 0.f;
-    for (int b = 0; b < a.B; ++b) s += a.dlogits[(long)b * a.C + c] * a.xh[(long)b * a.d + k];
-    a.dW[j] = a.accumulate ? a.dW[j] + s : s;
-    if (j < a.C) {
-      float t = 0.f;
-      for (int b = 0; b < a.B; ++b) t += a.dlogits[(long)b * a.C + j];
-      a.dbias[j] = a.accumulate ? a.dbias[j] + t : t;
-    }
-  }
+
+extern "C" int nv_head_step_scaled(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                                   const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, float* xh, float* stats,
+                                   float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma,
+                                   float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                                   unsigned long drop_seed, float drop_p, void* stream) {
+  return head_step(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, nullptr, xh, stats, logits, loss, dlogits, n, g, ldg, g16,
+                   ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
 }
 
 extern "C" int nv_head_step_soft(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
@@ -1458,29 +1439,8 @@ extern "C" int nv_head_step_soft(const float* x, long row_stride, int B, int d, 
                                  float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
                                  unsigned long drop_seed, float drop_p, void* stream) {
   if (int rc = check_loss_opts(opts, "nv_head_step_soft")) return rc;
-  if (!loss_opts_on(opts))
-    return nv_head_step_scaled(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, xh, stats, logits, loss, dlogits, n, g, ldg, g16,
-                               ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
-  NV_CHECK_ARG(B > 0 && d > 0 && C > 0 && C <= d && n > 0, "nv_head_step_soft: B = %d, d = %d, C = %d, n = %d", B, d, C, n);
-  NV_CHECK_ARG(x && gamma && beta && W && bias && labels && xh && stats && logits && loss && dlogits && g && dgamma && dbeta && dW && dbias && workspace,
-               "nv_head_step_soft: null pointer");
-  NV_CHECK_ARG(ws_bytes >= nv_head_step_workspace_bytes(B, d), "nv_head_step_soft: workspace too small");
-  NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d) && (d % 8) == 0 && nv_aligned16(g) && (!g16 || nv_aligned16(g16)), "nv_head_step_soft: g / g16 must be dense [B*n, d], 16-byte aligned, d a multiple of 8");
-  HeadStep a;
-  a.x = x; a.row_stride = row_stride; a.B = B; a.d = d; a.C = C; a.n = n; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias;
-  a.labels = labels; a.grad_scale = grad_scale; a.xh = xh; a.stats = stats; a.logits = logits; a.loss = loss; a.dlogits = dlogits;
-  a.g = g; a.ldg = ldg; a.g16 = (r16*)g16; a.ldg16 = ldg16; a.dgamma = dgamma; a.dbeta = dbeta; a.dW = dW; a.dbias = dbias; a.dcolsum = dcolsum;
-  a.accumulate = accumulate; a.partials = (float*)workspace; a.terms = (float*)workspace + (long)B * 3 * d; a.drop = make_drop(drop_seed, drop_p);
-  a.fp16 = nv_operand_format() == NV_OPERAND_FP16; a.scale_state = scale_state;
-  const long fill_bytes = (long)B * n * d * (g16 ? 6 : 4);
-  int fill_blocks = (int)((fill_bytes + (1 << 16) - 1) >> 16);
-  if (fill_blocks > 1024) fill_blocks = 1024;
-  hipLaunchKernelGGL(head_rows_soft_kernel, dim3(B + fill_blocks), dim3(256), (d + 12 + 8) * sizeof(float), (hipStream_t)stream, a, make_ce_soft(opts));
-  NV_CHECK_LAUNCH("nv_head_step_soft/rows");
-  const long outs = 3L * d + (long)C * d;
-  hipLaunchKernelGGL(head_sums_soft_kernel, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  NV_CHECK_LAUNCH("nv_head_step_soft");
-  return NV_OK;
+  return head_step(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, opts, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
+                   dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
 }
 
 // --------------------------------------------------------------------------------------- column sum of a bf16 matrix (bias grads)

@@ -398,22 +398,30 @@ def head_bwd(dlogits, W, x, st, xh, gamma, drop_seed=0, drop_p=0.0):
     return g, g16, dgamma, dbeta, dW, db, dcol
 
 
+def _head_step_outputs(B, n, d, C, dev):
+    """what a head step writes, in the order it is returned, and its workspace: (logits, xh, st, loss, dlogits, g, g16, dgamma, dbeta, dW,
+    db, dcol), ws.  g / g16 start as NaN: the step must write every row."""
+    logits, xh, st = torch.empty((B, C), device=dev), torch.empty((B, d), device=dev), torch.empty((B, 2), device=dev)
+    loss, dl = torch.empty(1, device=dev), torch.empty((B, C), device=dev)
+    g = torch.full((B, n, d), float("nan"), device=dev)
+    g16 = torch.full((B, n, d), float("nan"), dtype=op16(), device=dev)
+    dgamma, dbeta, dcol = (torch.empty(d, device=dev) for _ in range(3))
+    dW, db = torch.empty((C, d), device=dev), torch.empty(C, device=dev)
+    ws = torch.empty(lib.nv_head_step_workspace_bytes(B, d), dtype=torch.uint8, device=dev)
+    return (logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol), ws
+
+
 def head_step(x, gamma, beta, W, bias, labels, eps=1e-5, drop_seed=0, drop_p=0.0):
     """nv_head_step: head forward + CrossEntropyLoss + head backward in two launches.  Returns what head_fwd, ce_loss and head_bwd return together:
     (logits, xh, st, loss, dlogits, g, g16, dgamma, dbeta, dW, db, dcol)."""
     B, n, d = x.shape
     C = W.shape[0]
-    dev = x.device
-    xh = torch.empty((B, d), device=dev); st = torch.empty((B, 2), device=dev)
-    logits = torch.empty((B, C), device=dev); dl = torch.empty((B, C), device=dev); loss = torch.empty(1, device=dev)
-    g = torch.full((B, n, d), float("nan"), device=dev); g16 = torch.full((B, n, d), float("nan"), dtype=op16(), device=dev)
-    dgamma, dbeta, dcol = (torch.empty(d, device=dev) for _ in range(3))
-    dW = torch.empty((C, d), device=dev); db = torch.empty(C, device=dev)
-    nb = lib.nv_head_step_workspace_bytes(B, d)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    outs, ws = _head_step_outputs(B, n, d, C, x.device)
+    logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol = outs
     check(lib.nv_head_step(_p(x), n * d, B, d, _p(gamma), _p(beta), eps, _p(W), _p(bias), C, _p(labels), 1.0, _p(xh), _p(st), _p(logits), _p(loss), _p(dl),
-                           n, _p(g), d, _p(g16), d, _p(dgamma), _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), nb, drop_seed, drop_p, _stream()), "nv_head_step")
-    return logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol
+                           n, _p(g), d, _p(g16), d, _p(dgamma), _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), ws.numel(), drop_seed, drop_p, _stream()),
+          "nv_head_step")
+    return outs
 
 
 def colsum_bf16(X: torch.Tensor, accumulate=False, out=None):
@@ -479,19 +487,13 @@ def head_step_soft(x, gamma, beta, W, bias, labels, label_smoothing=0.0, class_w
     """nv_head_step_soft: head_step with the soft-target cross-entropy.  Returns what head_step returns."""
     B, n, d = x.shape
     C = W.shape[0]
-    dev = x.device
-    lo = loss_opts(label_smoothing, class_weight, mix, B, C, dev)
-    xh = torch.empty((B, d), device=dev); st = torch.empty((B, 2), device=dev)
-    logits = torch.empty((B, C), device=dev); dl = torch.empty((B, C), device=dev); loss = torch.empty(1, device=dev)
-    g = torch.full((B, n, d), float("nan"), device=dev); g16 = torch.full((B, n, d), float("nan"), dtype=op16(), device=dev)
-    dgamma, dbeta, dcol = (torch.empty(d, device=dev) for _ in range(3))
-    dW = torch.empty((C, d), device=dev); db = torch.empty(C, device=dev)
-    nb = lib.nv_head_step_workspace_bytes(B, d)
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    lo = loss_opts(label_smoothing, class_weight, mix, B, C, x.device)
+    outs, ws = _head_step_outputs(B, n, d, C, x.device)
+    logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol = outs
     check(lib.nv_head_step_soft(_p(x), n * d, B, d, _p(gamma), _p(beta), eps, _p(W), _p(bias), C, _p(labels), grad_scale, _p(scale_state),
                                 None if lo is None else ctypes.byref(lo), _p(xh), _p(st), _p(logits), _p(loss), _p(dl), n, _p(g), d, _p(g16), d, _p(dgamma),
-                                _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), nb, 0, 0.0, _stream()), "nv_head_step_soft")
-    return logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol
+                                _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), ws.numel(), 0, 0.0, _stream()), "nv_head_step_soft")
+    return outs
 
 
 def adamw_step(p, grad, m, v, p16, step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, max_blocks=0, scale_state=None,

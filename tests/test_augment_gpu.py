@@ -159,6 +159,51 @@ def test_series_share_their_samples_parameters(VA, T):
             assert torch.equal(R.bits(aug.apply(x[..., t], params.cuda())), R.bits(got[..., t])), (rows, t)
 
 
+# ------------------------------------------------------------------ a plane of more than one span
+# A workgroup owns 4096 cells of an output plane.  The smallest planes that reach a second one: 65 x 67 = 4355 cells (4355 mod 4 = 3, so
+# consecutive planes start at every 16-byte alignment; the second span is 259 cells from output row 61, column 9) and, for a series,
+# 9 x 10 x 47 = 4230 cells (rows of 470; the second span is 134 cells from row 8, k = 7).
+SPAN_SHAPES = {"3d": ((3, 5, 68, 70), (3, 65, 67)), "4d": ((3, 4, 12, 13, 47), (2, 9, 10))}
+
+
+def span_rows():
+    """for both shapes (X - Sx, Y - Sy, Z - Sz) = (2, 3, 3): z flips, windows that leave the volume on the low and on the high side of
+    every axis (one plane wholly outside), an intensity change on some samples"""
+    return [[[1, 2, 1, 4, ONE, ZERO, 0, 0], [-1, -2, -3, 0, SCALE, SHIFT, 0, 0], [3, 5, 5, 7, ONE, ZERO, 0, 0]],
+            [[0, 0, 0, 0, ONE, ZERO, 0, 0], [2, 3, 3, 4, SCALE, SHIFT, 0, 0], [1, -2, 6, 6, SCALE, SHIFT, 0, 0]]]
+
+
+def sentinel_out(shape):
+    """a dense `out` of that shape with 64 sentinel floats on both sides"""
+    n = int(np.prod(shape))
+    buf = torch.full((64 + n + 64,), 0x7FC0BEEF, dtype=torch.int32, device="cuda").view(torch.float32)
+    return buf, buf[64:64 + n].view(shape)
+
+
+def sentinels_intact(buf):
+    return bool((R.bits(torch.cat([buf[:64], buf[-64:]]).cpu()) == 0x7FC0BEEF).all())
+
+
+@pytest.mark.parametrize("case", sorted(SPAN_SHAPES))
+def test_apply_reaches_a_second_span(VA, case):
+    shape, roi = SPAN_SHAPES[case]
+    host = special_volume(shape, 61)
+    x = host.cuda()
+    aug = VA(roi, fill=-2.5)
+    buf, out = sentinel_out((3, *roi, *shape[4:]))
+    assert int(np.prod(out.shape[2:])) > 4096
+    for rows in span_rows():
+        params = torch.tensor(rows, dtype=torch.int32)
+        assert aug.apply(x, params.cuda(), out=out) is out
+        assert sentinels_intact(buf), rows
+        got, want = out.cpu(), R.apply_ref(host, params, roi, -2.5)
+        for b, row in enumerate(rows):
+            if row[4:6] == [ONE, ZERO]:
+                assert torch.equal(R.bits(got[b]), R.bits(want[b])), (rows, b)                       # a bit copy: payloads, -0.0
+            else:
+                assert same_bits_or_both_nan(got[b], want[b]), (rows, b)
+
+
 # ------------------------------------------------------------------ the call protocol
 def test_call_draws_applies_and_counts(VA):
     g = torch.Generator().manual_seed(8)

@@ -1,4 +1,4 @@
-"""Mixup / CutMix and the soft-target cross-entropy on MI355X: the kernels of csrc/mix.hip (nv_mix_params, nv_augment_mix) and the soft
+"""Mixup / CutMix and the soft-target cross-entropy on MI355X: the kernels of csrc/mix.hip and csrc/augment.hip (nv_mix_params, nv_augment_mix) and the soft
 loss (nv_ce_loss_soft, nv_head_step_soft, nv_vit_train_step_ex) against their CPU restatement (tests/mix_ref.py, itself proved in
 tests/test_mix_cpu.py), VolumeMix's call protocol, TrainStep with the options on every path, and the Trainer shell with the new keys.
 
@@ -17,6 +17,7 @@ import augment_ref as R
 import mix_ref as M
 import weights as W
 from conftest import rel_err
+from test_augment_gpu import SPAN_SHAPES, sentinel_out, sentinels_intact, span_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -209,6 +210,30 @@ def test_series_share_their_samples_rows(VM, T, B):
         assert torch.equal(R.bits(mixer.apply(strided, mix.cuda(), augment=aug, augment_params=params.cuda())), R.bits(got))
         for t in range(T):                                                                          # the 3D pass of each timepoint, same rows
             assert torch.equal(R.bits(mixer.apply(x[..., t], mix.cuda(), augment=aug, augment_params=params.cuda())), R.bits(got[..., t])), (rows, t)
+
+
+@pytest.mark.parametrize("case", sorted(SPAN_SHAPES))
+def test_mix_reaches_a_second_span(VM, case):
+    """tests/test_augment_gpu.py's planes of more than 4096 cells: one Mixup row, one mode-0 row and one CutMix row whose box crosses the
+    span boundary in y (3D: the second span starts in output row 61; 4D: in row 8) and whose z faces cut 16-byte groups behind it"""
+    from neurovit_amd.augment import VolumeAugment
+    shape, roi = SPAN_SHAPES[case]
+    box = (0, roi[0], 60, 64, 6, 59) if case == "3d" else (0, roi[0], 7, 9, 5, 9)
+    host = special_volume(shape, 61)
+    x = host.cuda()
+    aug, mixer = VolumeAugment(roi, fill=-2.5), VM(mixup_alpha=0.4, cutmix_alpha=1.0)
+    buf, out = sentinel_out((3, *roi, *shape[4:]))
+    tables = [[mix_row(2, 1, 0.3), mix_row(0, 2, 0.5, box=box), mix_row(0)],
+              [mix_row(1, 2, 0.5, box=box), mix_row(1), mix_row(0, 1, 0.75)],
+              [mix_row(2), mix_row(1), mix_row(0)]]                              # mode 0 everywhere
+    for rows, table in itertools.product(span_rows(), tables):
+        params, mix = torch.tensor(rows, dtype=torch.int32), torch.tensor(table, dtype=torch.int32)
+        assert mixer.apply(x, mix.cuda(), augment=aug, augment_params=params.cuda(), out=out) is out
+        assert sentinels_intact(buf), (rows, table)
+        want, moved = M.mix_apply_ref(host, params, mix, roi, -2.5)
+        assert M.same_bits(out.cpu(), want, moved), (rows, table)
+        if all(r[1] == 0 for r in table):                                    # mode 0 everywhere: nv_augment_apply, bit for bit
+            assert torch.equal(R.bits(out), R.bits(aug.apply(x, params.cuda()))), rows
 
 
 def test_call_draws_applies_and_counts(VM):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of Mixup / CutMix on the device (neurovit_amd.augment.VolumeMix, csrc/mix.hip), fused with the crop + flips + intensity of
+"""Cost of Mixup / CutMix on the device (neurovit_amd.augment.VolumeMix, csrc/mix.hip for the draws, csrc/augment.hip for the pass), fused with the crop + flips + intensity of
 VolumeAugment:
 
     kernel     nv_augment_mix into a preallocated output, both tables already on the device (ONE pass)
