@@ -413,6 +413,13 @@ int nv_adamw_step_clipped(float* p, const void* grad, int grad_bf16, float* m, f
 /* grad_bf16 = 1: `grad` is a bf16 buffer (the gradient all-reduce ran on bf16 messages): no cast back to fp32 is needed. */
 /* max_blocks > 0 caps the grid (256-thread workgroups, grid-stride): used when the update of one gradient bucket runs on a
    side stream beside the backward pass, so that it takes a slice of the chip instead of queueing ahead of the GEMMs. */
+/* ---- exponential moving average of a parameter arena (neurovit_amd.ModelEma; added within revision 8):
+ *   ema[i] = ema[i] + (p[i] - ema[i]) * weight     for i in [0, count)
+ * in fp32, the difference, the product and the sum each rounded on their own (no fused multiply-add): bit-equal to the same torch
+ * expression on the CPU, and p[i] == ema[i] leaves ema[i] unchanged bit for bit (inf / NaN propagate as in that expression).
+ * weight = float32(1 - decay) is formed by the caller; 0 <= weight <= 1, NaN is refused.  count > 0 and a multiple of 4 (arena
+ * segments are padded); both pointers 16-byte aligned; p is only read; no 16-bit shadow of ema is written.  max_blocks as above. */
+int nv_ema_update(float* ema, const float* p, long count, float weight, int max_blocks, void* stream);
 int nv_cast_bf16_2d(const float* src, long ld_src, int rows, int cols, void* dst, long ld_dst, void* stream);
 /* out16 (bf16) / out32 (f32), either may be NULL: x[M,N] f32 times the nn.Dropout mask of one site (same mask as the GEMM
  * epilogues, element index m*N + n; drop_p = 0: plain cast / copy).  Standalone Attention / FeedForward modules (vit_3d.py:23,45). */

@@ -644,6 +644,29 @@ class NeuroEncoder(nn.Module):
         return volume[pick], cam_3d[pick]
 
 
+class _NeuroEncoderTwin(NeuroEncoder):
+    """NeuroEncoder(config) that reads no file: the 4D model's encoder is frozen as ever, its weights arrive with the load_state_dict
+    that twin_of does next."""
+
+    def _adopt_trained_encoder(self, checkpoint_path: str) -> None:
+        self.volume_encoder.requires_grad_(False)
+        self.volume_encoder.eval()
+
+
+def twin_of(model: NeuroEncoder) -> NeuroEncoder:
+    """A second NeuroEncoder of `model`'s config holding a copy of its parameters (optim.ModelEma's averaged model): built from the
+    config plus load_state_dict - engine.VitRuntime owns workspaces, streams and events that a deep copy must not share - with the
+    encoder's operand format, eval precision and LayerNorm-fold switch carried over.  `model` is not touched, no checkpoint is read
+    again, and torch's CPU generator is left where it was (the construction draws an initialisation that is overwritten at once)."""
+    with torch.random.fork_rng(devices=[]):
+        twin = _NeuroEncoderTwin(model.config)
+    src, dst = model.volume_encoder.vit3d, twin.volume_encoder.vit3d
+    dst.set_operands(src.operands)
+    dst.eval_precision, dst.fold_layernorm = src.eval_precision, src.fold_layernorm
+    twin.load_state_dict(model.state_dict(), strict=True)
+    return twin
+
+
 class ViT3DEncoder(nn.Module):
     """NeuroEncoder.py:171-205: config -> ViT, and the [B,H,W,D] -> [B,1,D,H,W] input view."""
 

@@ -8,11 +8,14 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # `from neurovit_amd import VolumeAugment` (or VolumeMix), resolved on first use: importing the package itself stays free of torch
+    # `from neurovit_amd import VolumeAugment` (or VolumeMix, ModelEma), resolved on first use: importing the package itself stays free of torch
     if name == "VolumeAugment":
         from .augment import VolumeAugment
         return VolumeAugment
     if name == "VolumeMix":
         from .augment import VolumeMix
         return VolumeMix
+    if name == "ModelEma":
+        from .optim import ModelEma
+        return ModelEma
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

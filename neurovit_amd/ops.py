@@ -511,7 +511,16 @@ def adamw_step(p, grad, m, v, p16, step, lr, betas=(0.9, 0.999), eps=1e-8, weigh
                                         eps, weight_decay, grad_scale, int(max_blocks), _p(scale_state), _p(clip_state), _stream()), "nv_adamw_step_clipped")
 
 
-GRAD_CLIP_FLOATS = (64 + 8 * 2048) // 4      # NV_GRAD_CLIP_BYTES / 4 (include/neurovit_hip.h)
+def ema_update(ema: torch.Tensor, p: torch.Tensor, weight: float, max_blocks: int = 0) -> None:
+    """ema = ema + (p - ema) * weight in place, each fp32 operation rounded on its own (nv_ema_update): bit-equal to that torch expression
+    on the CPU, and p == ema is an exact fixed point.  Both flat fp32, contiguous, the same numel (a multiple of 4) and 16-byte aligned;
+    0 <= weight <= 1 - the library refuses anything else before the launch.  `p` is only read."""
+    _need_cuda(ema, p)
+    assert ema.dtype == torch.float32 and p.dtype == torch.float32 and ema.is_contiguous() and p.is_contiguous() and ema.numel() == p.numel()
+    check(lib.nv_ema_update(_p(ema), _p(p), ema.numel(), float(weight), int(max_blocks), _stream()), "nv_ema_update")
+
+
+GRAD_CLIP_FLOATS = (64 + 8 * 2048) // 4     # NV_GRAD_CLIP_BYTES / 4 (include/neurovit_hip.h)
 GC_TOTAL_NORM, GC_COEF = 2, 3                # float indices into that block (csrc/common.h GC_*)
 
 

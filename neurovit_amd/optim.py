@@ -5,9 +5,11 @@
 are views of a ViT arena are updated by ONE nv_adamw_step launch per arena (which also refreshes the
 bf16 shadow the MFMA kernels read); the 4D model's temporal head is a second, 10 k-parameter arena
 (temporal.TemporalHead, fp32 only) stepped the same way; any other parameter is delegated to torch.optim.AdamW.
+`ModelEma` averages the same arenas into a second model with one nv_ema_update launch each.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, List
 
@@ -90,6 +92,120 @@ class GradClipper:
         """Norm and coefficient of what was added: the summed gradients carry 1 / grad_scale (data-parallel sum, static loss scale) and,
         with `scaler`, its loss scale - call after scaler.update, which is what writes the 1 / scale of these gradients."""
         ops.grad_clip_finish(self.state, self.max_norm, grad_scale, None if scaler is None else scaler.state)
+
+
+def ema_decay_at(t: int, decay: float, warmup: bool = True, update_every: int = 1) -> float:
+    """Decay of the averaging that runs on update call `t` (t >= 1 counts the calls, this one included), formed in double:
+    d_t = min(decay, (1 + t) / (10 + t)) with `warmup` (timm's rule), else `decay`; with update_every = k the averaging runs on calls
+    k, 2k, ... and stands for k of them: d_t ** k."""
+    d = min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+    return d ** update_every
+
+
+def ema_weight(d: float) -> float:
+    """float32(1 - d) as a Python float: the `weight` nv_ema_update gets (the subtraction in double, one rounding to fp32)."""
+    return ctypes.c_float(1.0 - d).value
+
+
+def _flat_holders(model: torch.nn.Module) -> list:
+    """The objects of `model` that own a flat arena, in module order: every ViT, then the 4D model's TemporalHead."""
+    holders = [m for m in model.modules() if isinstance(m, ViT)]
+    for m in model.modules():
+        th = getattr(m, "_temporal_head", None)
+        if th is not None:
+            holders.append(th)
+    return holders
+
+
+class ModelEma:
+    """Exponential moving average of a NeuroEncoder's weights (timm's ModelEmaV2 / V3), kept on the DEVICE in a second model:
+    `module` is a NeuroEncoder of the same config - same state_dict keys, operand format and eval precision - in eval() with
+    requires_grad_(False), starting as a copy of `model`'s parameters.  `update()` averages every flat arena (the ViT's and, for the
+    4D model, the temporal head's) with ONE nv_ema_update launch each on the current stream,
+        ema = ema + (model - ema) * float32(1 - d_t),     d_t = ema_decay_at(t, decay, warmup, update_every),
+    each fp32 operation rounded on its own: a parameter that equals its average stays put bit for bit, so frozen parameters, the
+    frozen encoder of the 4D model and the constant slots of a ViT without output projection never drift.  Parameters outside any
+    arena are averaged by the same expression in torch.  Nothing is read back and nothing synchronises.  After an update the
+    averaged model's 16-bit shadow, folded and fp8 weights are stale and are rebuilt on their next use (mark_arena_rewritten).
+    Known limit of an fp32 average: an element stops following once |p - ema| * weight is below half an ulp of ema - at decay 0.9999
+    within about 6e-4 relative (timm's fp32 EMA has the same limit)."""
+
+    def __init__(self, model: torch.nn.Module, decay: float = 0.9999, warmup: bool = True, update_every: int = 1):
+        from .NeuroEncoder import NeuroEncoder, twin_of
+        self.check_args(decay, update_every)
+        if not isinstance(model, NeuroEncoder):
+            raise TypeError(f"ModelEma: model must be a neurovit_amd.NeuroEncoder, got {type(model).__name__}")
+        device = next(model.parameters()).device
+        if device.type != "cuda":
+            raise ValueError(f"ModelEma: the model must live on the MI355X (cuda) device, it is on {device} - there is no CPU fallback")
+        self.decay, self.warmup, self.update_every = float(decay), bool(warmup), int(update_every)
+        self.num_updates = 0
+        self._model = model
+        self.module = twin_of(model).to(device)
+        self.module.eval()
+        self.module.requires_grad_(False)
+        self._paired = None
+        self._pairs(model)
+
+    @staticmethod
+    def check_args(decay, update_every) -> None:
+        """decay: a number in [0, 1); update_every: an integer >= 1 (TypeError / ValueError otherwise)."""
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)):
+            raise TypeError(f"ModelEma: decay must be a number in [0, 1), got {decay!r}")
+        if not (0.0 <= float(decay) < 1.0):
+            raise ValueError(f"ModelEma: decay must be in [0, 1), got {decay!r}")
+        if isinstance(update_every, bool) or not isinstance(update_every, int):
+            raise TypeError(f"ModelEma: update_every must be an integer >= 1, got {update_every!r}")
+        if update_every < 1:
+            raise ValueError(f"ModelEma: update_every must be >= 1, got {update_every!r}")
+
+    def _pairs(self, model):
+        """[(the average's holder, the model's holder)] per flat arena, and [(average, parameter)] of what lies outside every arena -
+        found once per model; every arena size is checked before any device work."""
+        got = self._paired[1] if self._paired is not None and self._paired[0] is model else None
+        if got is None:
+            mine, theirs = _flat_holders(self.module), _flat_holders(model)
+            if len(mine) != len(theirs):
+                raise ValueError(f"ModelEma.update: the model has {len(theirs)} flat arenas, the average {len(mine)}")
+            inside = set()
+            for a, b in zip(mine, theirs):
+                na, nb = a.flat_parameters()[0].numel(), b.flat_parameters()[0].numel()
+                if na != nb:
+                    raise ValueError(f"ModelEma.update: arena sizes differ - the model's {type(b).__name__} arena has {nb} elements, the average's {na}")
+                inside.update(id(p) for p in a._plist)
+            ep, mp = list(self.module.parameters()), list(model.parameters())
+            if len(ep) != len(mp) or any(e.shape != p.shape for e, p in zip(ep, mp)):
+                raise ValueError("ModelEma.update: the model's parameters do not match the average's")
+            rest = [(e, p) for e, p in zip(ep, mp) if id(e) not in inside]
+            got = (list(zip(mine, theirs)), rest)
+            self._paired = (model, got)      # (the model itself is kept: the pairs are its, and only its)
+        return got
+
+    @torch.no_grad()
+    def update(self, model: torch.nn.Module = None) -> None:
+        """One averaging call (see the class): counts in num_updates whether or not this call averages (update_every)."""
+        arenas, rest = self._pairs(self._model if model is None else model)
+        self.num_updates += 1
+        if self.num_updates % self.update_every != 0:
+            return
+        weight = ema_weight(ema_decay_at(self.num_updates, self.decay, self.warmup, self.update_every))
+        for mine, theirs in arenas:
+            ops.ema_update(mine.flat_parameters()[0], theirs.flat_parameters()[0], weight)
+            mine.mark_arena_rewritten()
+        for e, p in rest:
+            e.copy_(e + (p.detach() - e) * weight)
+
+    def state_dict(self) -> dict:
+        return {"module": self.module.state_dict(), "num_updates": self.num_updates, "decay": self.decay, "warmup": self.warmup,
+                "update_every": self.update_every}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Copies state["module"] into the existing arenas in place (addresses do not change) and takes over num_updates; decay, warmup
+        and update_every stay those of the constructor."""
+        self.module.load_state_dict(state["module"], strict=True)
+        for holder in _flat_holders(self.module):
+            holder.mark_arena_rewritten()
+        self.num_updates = int(state["num_updates"])
 
 
 class FusedAdamW(torch.optim.Optimizer):

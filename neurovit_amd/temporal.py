@@ -121,6 +121,10 @@ class TemporalHead:
     def mark_shadow_fresh(self):
         self._param_generation += 1
 
+    def mark_arena_rewritten(self):
+        """ViT.mark_arena_rewritten for the head: no shadow to go stale (it computes in fp32), the generation counter moves."""
+        self._param_generation += 1
+
     def gather_foreign_grads(self):
         """Before a fused optimizer step: gradients that autograd produced outside the arena (the stock-module path of
         NeuroEncoder.forward) are moved into it; a parameter without a gradient contributes zeros - the fused step runs over the

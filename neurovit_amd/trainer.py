@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from .NeuroEncoder import NeuroEncoder
 from .nn import CrossEntropyLoss
-from .optim import FusedAdamW, GradClipper, LossScaler, check_max_norm
+from .optim import FusedAdamW, GradClipper, LossScaler, ModelEma, check_max_norm
 from .parallel import GradSync, NativeComm, broadcast_parameters
 
 
@@ -30,7 +30,15 @@ class TrainStep:
                  n_buckets: int = 4, accumulation_steps: int = 1, overlap_optimizer: bool = False,
                  grad_comm_dtype: torch.dtype = torch.float32, grad_comm_algo: Optional[str] = None, fuse_update: Optional[int] = None,
                  loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None, label_smoothing: float = 0.0,
-                 class_weight=None):
+                 class_weight=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_update_every: int = 1):
+        # ema_decay: None = off (no object is built, no call is added); a number in [0, 1) = `ema`, an optim.ModelEma(model, ema_decay,
+        # ema_warmup, ema_update_every) whose update() runs once per OPTIMIZER step, behind the update, on the stream the step runs on -
+        # on every path (native in every fuse_update mode, graph replay, clipping, native data-parallel plan, general path, side compute
+        # stream), with accumulation only on the micro-step that ends a window.  That stream has joined the auxiliary and the
+        # communication stream by then, so the launch reads finished parameters.  A step that a dynamic loss scale
+        # SKIPS is still averaged and still counts: the parameters did not move, the average moves towards them once more - what
+        # `scaler.step(opt); scaler.update(); ema.update(model)` does in the stock recipe.  Data parallel, every rank averages its own
+        # (identical) parameters: no collective.  The average changes no bit of parameters, moments, gradients or scaler state.
         # label_smoothing / class_weight: nn.CrossEntropyLoss(weight=, label_smoothing=) on every path; __call__'s `mix` (VolumeMix.last_mix)
         # trains against the Mixup / CutMix target.  With all three off every path makes the calls it makes without them.  Data parallel,
         # each rank normalises its loss by its own denominator and the gradients are averaged over ranks (what torch DDP does).
@@ -42,6 +50,8 @@ class TrainStep:
         # are device tensors - reading them is the caller's synchronisation, the step has none.  The coefficient needs the whole norm
         # before the first update: AdamW runs once behind the backward pass (fuse_update resolves to 0, no captured-graph replay, no
         # overlap_optimizer), and world > 1 takes the Python-driven bucket pipeline instead of the native data-parallel plan.
+        if ema_decay is not None:
+            ModelEma.check_args(ema_decay, ema_update_every)
         if max_grad_norm is not None:
             max_grad_norm = check_max_norm(max_grad_norm)
             assert not overlap_optimizer, "max_grad_norm: the clipping coefficient needs the norm of ALL gradients before any update - no per-bucket optimizer updates"
@@ -155,6 +165,8 @@ class TrainStep:
         if self._head is not None:
             self._head.flat_parameters()
             self._head_ids = {id(p) for p in self._head._plist}
+        # (last: the average starts from the parameters as they are now - after the data-parallel broadcast above)
+        self.ema = None if ema_decay is None else ModelEma(model, decay=ema_decay, warmup=ema_warmup, update_every=ema_update_every)
 
     @property
     def last_grad_norm(self) -> Optional[torch.Tensor]:
@@ -181,6 +193,8 @@ class TrainStep:
                 raise RuntimeError("TrainStep: mix must live on the MI355X (cuda) device - there is no CPU fallback")
             mix = mix.contiguous()
         run = self._step if mix is None else (lambda f, l: self._step(f, l, mix))      # (without a mix: the call as it always was)
+        if self.ema is not None:
+            run = self._averaged(run)
         cs = self._compute_stream
         if cs is None:
             return run(fmri, labels)
@@ -193,6 +207,89 @@ class TrainStep:
             if t is not None:
                 t.record_stream(cur)
         return loss
+
+    def _averaged(self, run):
+        """`run` followed by ema.update() when it ended an optimizer step: every path leaves _micro at 0 exactly then (the window's last
+        micro-step resets it; the graph replay runs only without accumulation).  Called inside the stream scope of the step, so the
+        launch goes on the stream the step ran on, behind its update."""
+        def step(fmri, labels):
+            loss = run(fmri, labels)
+            if self._micro == 0:
+                self.ema.update(self.model)
+            return loss
+        return step
+
+    # ------------------------------------------------------------------ resumable state (the model's own checkpoint stays the plain state_dict)
+    STATE_VERSION = 1
+
+    def state_dict(self) -> dict:
+        """Everything but the model parameters that a restarted run needs to continue bit for bit: the optimizer's step count and
+        hyper-parameters, the AdamW moment arenas (FusedAdamW keeps them outside Optimizer.state), the stock optimizer of parameters
+        outside every arena, the dynamic loss scale's device block, the static scale, and the weight average.  Clones: later steps do
+        not change what was returned.  Refused inside an open accumulation window (the gradients of its micro-steps are not saved)."""
+        if self._micro != 0:
+            raise RuntimeError(f"TrainStep.state_dict: inside an accumulation window ({self._micro} of {self.accumulation_steps} micro-steps taken) - "
+                               "save after the micro-step that ends it")
+        opt = self.optimizer
+        arenas = []
+        for holder in opt.arenas():
+            m, v = opt.arena_state(holder)
+            arenas.append({"numel": m.numel(), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()})
+        g0 = opt.param_groups[0]
+        return {"version": self.STATE_VERSION, "operands": self._vit.operands, "steps": int(opt._steps),
+                "hyper": {k: g0[k] for k in ("lr", "betas", "eps", "weight_decay")}, "arenas": arenas,
+                "rest": None if opt._rest is None else opt._rest.state_dict(),
+                "scaler": None if self.scaler is None else self.scaler.state.detach().clone(), "static_scale": self.static_scale,
+                "ema": None if self.ema is None else self.ema.state_dict()}
+
+    def load_state_dict(self, state: dict) -> None:
+        """Restore what state_dict returned into the EXISTING buffers, in place: addresses do not change, so .grad views and captured
+        graphs stay valid.  Everything is checked before the first copy (ValueError naming the mismatch; nothing has changed then):
+        version, operand format, arena count and sizes, a scaler on both sides or on neither, an average on both sides or on neither.
+        Load the model's parameters (model.load_state_dict) separately - they are not part of this state."""
+        opt = self.optimizer
+        if not isinstance(state, dict) or state.get("version") != self.STATE_VERSION:
+            raise ValueError(f"TrainStep.load_state_dict: state version {state.get('version') if isinstance(state, dict) else None!r}, this class reads version {self.STATE_VERSION}")
+        if state["operands"] != self._vit.operands:
+            raise ValueError(f"TrainStep.load_state_dict: the state was saved on {state['operands']} operands, this model runs on {self._vit.operands}")
+        holders = opt.arenas()
+        if len(state["arenas"]) != len(holders):
+            raise ValueError(f"TrainStep.load_state_dict: the state holds {len(state['arenas'])} moment arenas, this optimizer steps {len(holders)}")
+        for i, (saved, holder) in enumerate(zip(state["arenas"], holders)):
+            n = holder.flat_parameters()[0].numel()
+            if saved["numel"] != n or saved["exp_avg"].numel() != n or saved["exp_avg_sq"].numel() != n:
+                raise ValueError(f"TrainStep.load_state_dict: arena {i} has {n} elements, the state's has {saved['numel']}")
+        if (state["scaler"] is None) != (self.scaler is None):
+            raise ValueError("TrainStep.load_state_dict: a dynamic loss scale must be on both sides or on neither - the state has "
+                             f"{'one' if state['scaler'] is not None else 'none'}, this step has {'one' if self.scaler is not None else 'none'}")
+        if state["scaler"] is not None and state["scaler"].numel() != self.scaler.state.numel():
+            raise ValueError(f"TrainStep.load_state_dict: the loss-scale block has {state['scaler'].numel()} floats, expected {self.scaler.state.numel()}")
+        if (state["ema"] is None) != (self.ema is None):
+            raise ValueError("TrainStep.load_state_dict: a weight average (ema_decay) must be on both sides or on neither - the state has "
+                             f"{'one' if state['ema'] is not None else 'none'}, this step has {'one' if self.ema is not None else 'none'}")
+        if (state["rest"] is None) != (opt._rest is None):
+            raise ValueError("TrainStep.load_state_dict: parameters outside the arenas (a stock optimizer) must be on both sides or on neither")
+        if self.ema is not None:
+            mine, saved = self.ema.module.state_dict(), state["ema"]["module"]
+            if set(mine) != set(saved) or any(mine[k].shape != saved[k].shape for k in mine):
+                raise ValueError("TrainStep.load_state_dict: the averaged model of the state has other keys or shapes than this one")
+        with torch.no_grad():
+            for saved, holder in zip(state["arenas"], holders):
+                m, v = opt.arena_state(holder)
+                m.copy_(saved["exp_avg"])
+                v.copy_(saved["exp_avg_sq"])
+            if opt._rest is not None:
+                opt._rest.load_state_dict(state["rest"])
+            if self.scaler is not None:
+                self.scaler.state.copy_(state["scaler"])      # (AdamW's t under a dynamic scale is the block's own count of applied updates)
+        opt._steps = int(state["steps"])
+        for k, value in state["hyper"].items():
+            for g in opt.param_groups:
+                g[k] = value
+        self.static_scale = float(state["static_scale"])
+        if self.ema is not None:
+            self.ema.load_state_dict(state["ema"])
+        self._micro = 0
 
     # ------------------------------------------------------------------ the step as ONE native call (world = 1, 3D model)
     def _native_ok(self, fmri, labels) -> bool:
@@ -509,7 +606,11 @@ class Trainer:
         batch ON THE DEVICE (augment.VolumeAugment: the window is the model's input size, the datasets hand over the uncropped
         volumes), with optional AUGMENT_* keys for flips, shifts and intensity changes; `train` draws a random window per sample,
         while `validate` / `evaluate_samples` take the CENTRE window (offset (X - S) // 2 per axis, a strided view) - the reference
-        crops randomly at validation too, which makes its validation loss depend on the draw.
+        crops randomly at validation too, which makes its validation loss depend on the draw;
+      * optional keys the reference does not have: TRAINING_EMA_DECAY / _WARMUP / _UPDATE_EVERY keep a weight average (optim.ModelEma) that
+        `validate` evaluates behind the raw model (VALIDATION_EMA: false turns that off) and `run` saves as model-e{N}-ema.pth;
+        TRAINING_SAVE_STATE writes state-e{N}.pth / last_state.pth (TrainStep.state_dict, the batch counter, torch's CPU generator) beside
+        the model files, and TRAINING_RESUME_FROM continues such a run at the next epoch.  With none of them set nothing changes.
     """
 
     def __init__(self, config, model, dataset_train, dataset_val):
@@ -529,8 +630,11 @@ class Trainer:
         self.val_dataloader = torch.utils.data.DataLoader(self.val_data, shuffle=False, **kw)
         smoothing, class_weights = self.loss_options_from_config(config)
         self.criterion = CrossEntropyLoss(weight=class_weights)          # validation: never smoothed, never mixed; it carries the class weights
+        self.save_state, self.resume_from = self.state_options_from_config(config)
         self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
-                              max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights)
+                              max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights,
+                              **self.ema_from_config(config))
+        self.validate_ema = bool(config.get('VALIDATION_EMA', True))
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
         self._wandb = None
@@ -548,6 +652,59 @@ class Trainer:
         self.augment = self.augment_from_config(config)
         self.mix = self.mix_from_config(config)
         self.global_step = 0                           # batches `train` has taken so far, over all epochs: the augmentation's step index
+        self.start_epoch = 0
+        if self.resume_from is not None:
+            self._resume(self.resume_from)
+
+    @staticmethod
+    def ema_from_config(config) -> dict:
+        """TrainStep's ema_* arguments from the optional keys TRAINING_EMA_DECAY (absent or None = no average), TRAINING_EMA_WARMUP
+        (default True) and TRAINING_EMA_UPDATE_EVERY (default 1); the reference's config files have no such keys.  Bad values raise
+        (optim.ModelEma.check_args; a warmup that is no bool: TypeError)."""
+        decay = config.get('TRAINING_EMA_DECAY', None)
+        if decay is None:
+            return {}
+        warmup, every = config.get('TRAINING_EMA_WARMUP', True), config.get('TRAINING_EMA_UPDATE_EVERY', 1)
+        ModelEma.check_args(decay, every)
+        if not isinstance(warmup, bool):
+            raise TypeError(f"TRAINING_EMA_WARMUP must be true or false, got {warmup!r}")
+        return dict(ema_decay=float(decay), ema_warmup=warmup, ema_update_every=every)
+
+    @staticmethod
+    def state_options_from_config(config):
+        """(TRAINING_SAVE_STATE: bool, default False - `run` also writes the resumable state of the step beside every model file;
+        TRAINING_RESUME_FROM: path of such a state file, default None).  Anything else raises TypeError."""
+        save, resume = config.get('TRAINING_SAVE_STATE', False), config.get('TRAINING_RESUME_FROM', None)
+        save = False if save is None else save
+        if not isinstance(save, bool):
+            raise TypeError(f"TRAINING_SAVE_STATE must be true or false, got {save!r}")
+        if resume is not None and (not isinstance(resume, (str, os.PathLike)) or not str(resume)):
+            raise TypeError(f"TRAINING_RESUME_FROM must be the path of a state file, got {resume!r}")
+        return save, None if resume is None else str(resume)
+
+    @staticmethod
+    def model_file_of_state(state_path: str) -> str:
+        """The model file written with a state file, in the same directory: state-eN.pth -> model-eN.pth, last_state.pth -> last_model.pth."""
+        folder, name = os.path.split(state_path)
+        if name == "last_state.pth":
+            return os.path.join(folder, "last_model.pth")
+        if name.startswith("state-e") and name.endswith(".pth") and name[len("state-e"):-len(".pth")].isdigit():
+            return os.path.join(folder, "model-e" + name[len("state-e"):])
+        raise ValueError(f"TRAINING_RESUME_FROM: {name!r} is neither last_state.pth nor state-eN.pth - no model file to pair it with")
+
+    def _resume(self, state_path: str) -> None:
+        """Continue the run a state file was written by: the model's parameters (the paired model file), the step's state, the batch
+        counter and torch's CPU generator (dropout seeds and the loader's shuffle come from it); `run` goes on at the next epoch."""
+        model_path = self.model_file_of_state(state_path)
+        saved = torch.load(state_path, map_location='cpu', weights_only=True)
+        self.model.load_state_dict(torch.load(model_path, map_location='cpu', weights_only=True), strict=True)
+        self.step.load_state_dict(saved["step"])
+        self.global_step = int(saved["global_step"])
+        self.start_epoch = int(saved["epoch"]) + 1
+        torch.set_rng_state(saved["torch_rng"])
+
+    def _state_file(self, epoch: int) -> dict:
+        return {"epoch": epoch, "global_step": self.global_step, "step": self.step.state_dict(), "torch_rng": torch.get_rng_state()}
 
     @staticmethod
     def augment_from_config(config):
@@ -622,11 +779,18 @@ class Trainer:
         path = f"{self.output_dir}/{datetime.datetime.now().strftime('%Y-%m-%d_%H-%M-%S')}"
         self._os.makedirs(path, exist_ok=True)
         self._os.makedirs('./results', exist_ok=True)
-        for epoch in range(self.epochs):
+        for epoch in range(self.start_epoch, self.epochs):
             self.train(epoch)
             self.validate(epoch)
             torch.save(self.model.state_dict(), './results/last_model.pth')
             torch.save(self.model.state_dict(), f'{path}/model-e{epoch}.pth')
+            if self.step.ema is not None:              # the averaged weights: plain state_dicts, loadable like any checkpoint
+                torch.save(self.step.ema.module.state_dict(), './results/last_model_ema.pth')
+                torch.save(self.step.ema.module.state_dict(), f'{path}/model-e{epoch}-ema.pth')
+            if self.save_state:                        # what TRAINING_RESUME_FROM reads, beside the model file it pairs with
+                state = self._state_file(epoch)
+                torch.save(state, './results/last_state.pth')
+                torch.save(state, f'{path}/state-e{epoch}.pth')
             print(f"MODEL SAVED to .{path}/model-e{epoch}.pth")
 
     def train(self, epoch):
@@ -660,22 +824,31 @@ class Trainer:
                 correct, total, running_loss = 0, 0, 0.0
                 start_time = time.time()
 
-    def validate(self, epoch):
-        self.model.eval()
+    def _evaluate(self, model):
+        """(rounded mean loss, rounded accuracy, index of the last batch) of `model` over the validation set"""
+        model.eval()
         val_loss, correct, total, i = 0.0, 0, 0, 0
-        with torch.no_grad(), self.model.precision(self.validation_precision):
+        with torch.no_grad(), model.precision(self.validation_precision):
             for i, batch in enumerate(self.val_dataloader):
                 fMRI, label = self._unpack(batch)
                 fMRI, label = self._center(fMRI.to(self.device)), label.to(self.device)
-                outputs = self.model(fMRI)
+                outputs = model(fMRI)
                 val_loss += self.criterion(outputs, label).item()
                 correct += (outputs.argmax(dim=1) == label).sum().item()
                 total += label.size(0)
-        avg_val_loss = round(val_loss / max(1, len(self.val_dataloader)), 5)
+        return round(val_loss / max(1, len(self.val_dataloader)), 5), round(correct / max(1, total), 5), i
+
+    def validate(self, epoch):
+        avg_val_loss, accuracy, i = self._evaluate(self.model)
         self.val_loss = avg_val_loss
-        accuracy = round(correct / max(1, total), 5)
         print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss {avg_val_loss:.5f}\t| val_accuracy {accuracy:.5f}")
         self._log({"epoch": epoch, "val_loss": avg_val_loss, "val_accuracy": accuracy})
+        if self.step.ema is not None and self.validate_ema:
+            # the averaged weights under the same precision and centre crop (VALIDATION_EMA: false turns this second pass off)
+            loss_ema, accuracy_ema, i = self._evaluate(self.step.ema.module)
+            self.val_loss_ema = loss_ema
+            print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss_ema {loss_ema:.5f}\t| val_accuracy_ema {accuracy_ema:.5f}")
+            self._log({"epoch": epoch, "val_loss_ema": loss_ema, "val_accuracy_ema": accuracy_ema})
         return avg_val_loss, accuracy
 
     def evaluate_samples(self):

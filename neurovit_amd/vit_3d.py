@@ -516,6 +516,13 @@ class ViT(nn.Module):
         self._shadow_key = tuple(p._version for p in self._plist)
         self._param_generation += 1
 
+    def mark_arena_rewritten(self):
+        """Called by whatever rewrites the arena through raw pointers WITHOUT writing the 16-bit shadow (optim.ModelEma.update): the
+        shadow is stale and is cast again before its next use, and the generation counter tells the folded and the fp8 weights so.
+        (The constant slots need no repair: the average of a constant with itself is that constant, bit for bit.)"""
+        self._shadow_key = None
+        self._param_generation += 1
+
     def _param_key(self):
         return (self._param_generation, tuple(p._version for p in self._plist))
 
