@@ -16,7 +16,7 @@ from typing import Dict, List
 import torch
 
 from . import _cabi, ops
-from .vit_3d import ViT
+from .arena import FlatArena
 
 
 class LossScaler:
@@ -108,8 +108,8 @@ def ema_weight(d: float) -> float:
 
 
 def _flat_holders(model: torch.nn.Module) -> list:
-    """The objects of `model` that own a flat arena, in module order: every ViT, then the 4D model's TemporalHead."""
-    holders = [m for m in model.modules() if isinstance(m, ViT)]
+    """The FlatArena objects of `model`, in module order: every ViT, then the 4D model's TemporalHead (no module: hung on one)."""
+    holders = [m for m in model.modules() if isinstance(m, FlatArena)]
     for m in model.modules():
         th = getattr(m, "_temporal_head", None)
         if th is not None:
@@ -172,7 +172,7 @@ class ModelEma:
                 na, nb = a.flat_parameters()[0].numel(), b.flat_parameters()[0].numel()
                 if na != nb:
                     raise ValueError(f"ModelEma.update: arena sizes differ - the model's {type(b).__name__} arena has {nb} elements, the average's {na}")
-                inside.update(id(p) for p in a._plist)
+                inside.update(id(p) for p in a.arena_parameters())
             ep, mp = list(self.module.parameters()), list(model.parameters())
             if len(ep) != len(mp) or any(e.shape != p.shape for e, p in zip(ep, mp)):
                 raise ValueError("ModelEma.update: the model's parameters do not match the average's")
@@ -213,7 +213,8 @@ class FusedAdamW(torch.optim.Optimizer):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
         self._model = model
-        self._arenas: List[object] = []      # ViT modules and TemporalHead objects: flat_parameters() / flat_gradients() / mark_shadow_fresh()
+        self._arenas: List[FlatArena] = []   # ViT modules and TemporalHead objects
+        self._ranged = set()                 # ids of the arenas that step_range has stepped since the last step_rest
         self._state_mv: Dict[int, tuple] = {}
         self._rest = None
         self._bound = False
@@ -229,22 +230,11 @@ class FusedAdamW(torch.optim.Optimizer):
         mine = {id(p) for g in self.param_groups for p in g["params"]}
         claimed = set()
         self._arenas = []
-        if self._model is not None:
-            for m in self._model.modules():
-                if isinstance(m, ViT):
-                    m.flat_parameters()
-                    ids = [id(p) for p in m._plist]
-                    if all(i in mine for i in ids) and all(p.requires_grad for p in m._plist):
-                        self._arenas.append(m)
-                        claimed.update(ids)
-            for m in self._model.modules():             # the 4D model's temporal head: a second, small arena (temporal.TemporalHead)
-                th = getattr(m, "_temporal_head", None)
-                if th is not None:
-                    th.flat_parameters()
-                    ids = [id(p) for p in th._plist]
-                    if all(i in mine for i in ids) and all(p.requires_grad for p in th._plist):
-                        self._arenas.append(th)
-                        claimed.update(ids)
+        for holder in _flat_holders(self._model) if self._model is not None else ():
+            plist = holder.arena_parameters()
+            if all(id(p) in mine and p.requires_grad for p in plist):
+                self._arenas.append(holder)
+                claimed.update(id(p) for p in plist)
         rest = [p for g in self.param_groups for p in g["params"] if id(p) not in claimed and p.requires_grad]
         g0 = self.param_groups[0]
         self._rest = torch.optim.AdamW(rest, lr=g0["lr"], betas=g0["betas"], eps=g0["eps"], weight_decay=g0["weight_decay"]) if rest else None
@@ -265,15 +255,14 @@ class FusedAdamW(torch.optim.Optimizer):
             self._bind()
         self._steps += 1
         g0 = self.param_groups[0]
-        live = [h for h in self._arenas if not self._no_gradients(h)]
+        live = [h for h in self._arenas if not h.no_gradients()]
         if clip is not None:
             for holder in live:
-                if hasattr(holder, "gather_foreign_grads"):
-                    holder.gather_foreign_grads()
+                holder.gather_foreign_grads()
                 red = None if reduced_bf16 is None else reduced_bf16.get(id(holder))
-                _cabi.set_operand_format(getattr(holder, "operands", "bf16"))      # what a 16-bit reduced buffer holds
+                _cabi.set_operand_format(holder.operands)      # what a 16-bit reduced buffer holds
                 summed = holder.flat_gradients() if red is None else red
-                for o, const in getattr(holder, "_phantom", ()):      # arena slots that are no parameter (the nn.Identity to_out of a heads == 1 ViT):
+                for o, const in holder._phantom:      # arena slots that are no parameter (the nn.Identity to_out of a heads == 1 ViT):
                     summed[o:o + const.numel()].zero_()                # what the backward pass left there is no gradient of the model
                 clip.add(summed, scaler)
             if self._rest is not None:
@@ -286,8 +275,7 @@ class FusedAdamW(torch.optim.Optimizer):
             clip.finish(grad_scale, scaler)
         elif scaler is not None:
             for holder in live:
-                if hasattr(holder, "gather_foreign_grads"):
-                    holder.gather_foreign_grads()
+                holder.gather_foreign_grads()
                 red = None if reduced_bf16 is None else reduced_bf16.get(id(holder))
                 scaler.check(holder.flat_gradients() if red is None else red.float())
             if self._rest is not None:
@@ -316,7 +304,7 @@ class FusedAdamW(torch.optim.Optimizer):
             self._rest.step()
         return None
 
-    def step_range(self, vit: ViT, begin: int, end: int, grad_scale: float = 1.0, max_blocks: int = 0):
+    def step_range(self, vit: FlatArena, begin: int, end: int, grad_scale: float = 1.0, max_blocks: int = 0):
         """AdamW on arena elements [begin, end) only (DP: run per gradient bucket behind its all-reduce).
         The caller advances the step counter once per optimizer step with `begin_step()`."""
         arena, shadow = vit.flat_parameters()
@@ -326,10 +314,11 @@ class FusedAdamW(torch.optim.Optimizer):
             self._state_mv[key] = (torch.zeros_like(arena), torch.zeros_like(arena))
         m, v = self._state_mv[key]
         g0 = self.param_groups[0]
-        _cabi.set_operand_format(getattr(vit, "operands", "bf16"))
+        _cabi.set_operand_format(vit.operands)
         ops.adamw_step(arena[begin:end], grads[begin:end], m[begin:end], v[begin:end], shadow[begin:end], self._steps, g0["lr"],
                        g0["betas"], g0["eps"], g0["weight_decay"], grad_scale, max_blocks)
-        vit._param_generation += 1             # the arena changed under derived copies (fp8 weights re-quantise on their next use)
+        vit.bump_generation()                  # the arena changed under derived copies (fp8 weights re-quantise on their next use)
+        self._ranged.add(id(vit))
 
     def begin_step(self):
         if not self._bound:
@@ -350,32 +339,25 @@ class FusedAdamW(torch.optim.Optimizer):
             self._state_mv[key] = (torch.zeros_like(arena), torch.zeros_like(arena))
         return self._state_mv[key]
 
-    @staticmethod
-    def _no_gradients(holder) -> bool:
-        """torch.optim.AdamW skips a parameter whose .grad is None (no weight decay, no moment decay, no step count): an arena none of
-        whose parameters has a gradient - zero_grad(set_to_none=True) followed by step(), or a head no backward reached - is skipped
-        as a whole.  (A PARTIALLY populated arena is stepped with zeros for the missing gradients: see TemporalHead.gather_foreign_grads.)"""
-        return all(p.grad is None for p in holder._plist)
-
     def _step_arena(self, holder, grad_scale, reduced=None, scaler=None, clip=None):
         arena, shadow = holder.flat_parameters()
         grads = holder.flat_gradients()
-        if hasattr(holder, "gather_foreign_grads"):
-            holder.gather_foreign_grads()
+        holder.gather_foreign_grads()
         m, v = self.arena_state(holder)
         g0 = self.param_groups[0]
-        _cabi.set_operand_format(getattr(holder, "operands", "bf16"))      # the format of the shadow this launch rewrites
+        _cabi.set_operand_format(holder.operands)      # the format of the shadow this launch rewrites
         ops.adamw_step(arena, grads if reduced is None else reduced, m, v, shadow, self._steps, g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"], grad_scale,
                        scale_state=None if scaler is None else scaler.state, clip_state=None if clip is None else clip.state)
         holder.mark_shadow_fresh()
 
     @torch.no_grad()
     def step_rest(self, grad_scale: float = 1.0):
-        """Parameters outside the ViT arenas (after those ranges were stepped bucket by bucket): the temporal head's arena with
+        """What step_range has not stepped bucket by bucket since the last call: the other arenas (the temporal head's) with
         `grad_scale`, stock parameters as they are."""
         for holder in self._arenas:
-            if not isinstance(holder, ViT) and not self._no_gradients(holder):
+            if id(holder) not in self._ranged and not holder.no_gradients():
                 self._step_arena(holder, grad_scale)
+        self._ranged.clear()
         if self._rest is not None:
             g0 = self.param_groups[0]
             for g in self._rest.param_groups:

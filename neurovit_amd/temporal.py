@@ -11,12 +11,11 @@ AdamW steps the arena in one more.  `TemporalHead` is a plain object hung on the
 """
 from __future__ import annotations
 
-from typing import List, Optional
-
 import torch
 from torch import nn
 
 from . import ops
+from .arena import FlatArena
 
 MAX_TIMEPOINTS = 64      # csrc/temporal.hip: TH_MAXT
 MAX_FEEDFORWARD = 2048   # TH_THREADS * TH_KPT
@@ -40,14 +39,13 @@ class _TemporalHeadFunction(torch.autograd.Function):
         return (None, dx) + (None,) * len(ctx.head._plist)
 
 
-class TemporalHead:
+class TemporalHead(FlatArena):
+    _direct_when_partly_frozen = False     # a partially frozen head computes into scratch (FlatArena._backward_to_grads)
+
     def __init__(self, temporal_transformer: nn.Module, projection_head: nn.Module):
         self.temporal_transformer, self.projection_head = temporal_transformer, projection_head
         self._layer = temporal_transformer.transformer.layers[0]
-        self._arena: Optional[torch.Tensor] = None
-        self._grads: Optional[torch.Tensor] = None
-        self._plist: List[nn.Parameter] = []
-        self._param_generation = 0
+        self._init_arena()
         lay = self._layer
         self.ff = lay.linear1.out_features
         self.eps = float(lay.norm1.eps)
@@ -69,7 +67,7 @@ class TemporalHead:
                 and float(lay.norm2.eps) == self.eps and len(drops) == 1
                 and proj.in_features == 2 and proj.out_features == 2 and proj.bias is not None)
 
-    # ------------------------------------------------------------------ arena (same scheme as ViT._build_arena)
+    # ------------------------------------------------------------------ arena (arena.FlatArena; no 16-bit shadow - the head computes in fp32)
     def _params(self):
         return [p for _, p in self.temporal_transformer.named_parameters()] + [p for _, p in self.projection_head.named_parameters()]
 
@@ -80,43 +78,15 @@ class TemporalHead:
         assert [p.numel() for p in plist] == sizes, "temporal head: parameter list does not match csrc/temporal.hip's arena layout"
         total = ops.temporal_head_param_count(F)
         assert total == sum(sizes)
-        dev = plist[0].device
-        arena = torch.zeros(total, dtype=torch.float32, device=dev)
-        off = 0
-        self._offsets = []
-        with torch.no_grad():
-            for p, n in zip(plist, sizes):
-                arena[off:off + n].copy_(p.detach().reshape(-1).float())
-                p.data = arena[off:off + n].view(p.shape)
-                self._offsets.append(off)
-                off += n
-        if self._grads is not None and self._grads.device != dev:
-            self._grads = None
-        self._arena, self._plist = arena, plist
+        self._pack(plist, [sum(sizes[:i]) for i in range(len(sizes))], sizes, total)
+
+    def _packed(self):
         self._param_generation += 1
 
     def _arena_ok(self) -> bool:
-        if self._arena is None:
-            return False
-        base = self._arena.data_ptr()
+        """stricter than the base check: the modules' CURRENT parameters are the packed ones (a replaced nn.Parameter object is noticed)"""
         cur = self._params()
-        return len(cur) == len(self._plist) and all(p is q and p.data_ptr() == base + 4 * o for p, q, o in zip(cur, self._plist, self._offsets))
-
-    def flat_parameters(self):
-        """(arena fp32, None): the fused optimizer's interface (no bf16 shadow - the head computes in fp32)."""
-        if not self._arena_ok():
-            self._build_arena()
-        return self._arena, None
-
-    def flat_gradients(self) -> torch.Tensor:
-        self.flat_parameters()
-        if self._grads is None:
-            self._grads = torch.zeros_like(self._arena)
-        return self._grads
-
-    def _grad_view(self, i: int) -> torch.Tensor:
-        o, p = self._offsets[i], self._plist[i]
-        return self._grads[o:o + p.numel()].view(p.shape)
+        return len(cur) == len(self._plist) and all(p is q for p, q in zip(cur, self._plist)) and super()._arena_ok()
 
     def mark_shadow_fresh(self):
         self._param_generation += 1
@@ -124,22 +94,6 @@ class TemporalHead:
     def mark_arena_rewritten(self):
         """ViT.mark_arena_rewritten for the head: no shadow to go stale (it computes in fp32), the generation counter moves."""
         self._param_generation += 1
-
-    def gather_foreign_grads(self):
-        """Before a fused optimizer step: gradients that autograd produced outside the arena (the stock-module path of
-        NeuroEncoder.forward) are moved into it; a parameter without a gradient contributes zeros - the fused step runs over the
-        whole arena, so such a parameter still sees weight decay and moment decay where torch.optim.AdamW would skip it.  The
-        optimizer skips the arena altogether when NO parameter has a gradient (FusedAdamW._no_gradients: the case torch skips
-        entirely); a partially used head does not occur on the NeuroEncoder path (every parameter is on the forward path)."""
-        grads = self.flat_gradients()
-        for i, p in enumerate(self._plist):
-            view = self._grad_view(i)
-            if p.grad is None:
-                view.zero_()
-            elif p.grad.data_ptr() != view.data_ptr():
-                view.copy_(p.grad)
-                p.grad = view
-        return grads
 
     # ------------------------------------------------------------------ forward / backward
     def _draw_dropout(self):
@@ -157,21 +111,7 @@ class TemporalHead:
         return ops.temporal_head_fwd(x, self._arena, self.ff, self.eps, seed, p)
 
     def _run_backward(self, x, dout, drop, want_dx):
-        grads = self.flat_gradients()
-        trainable = [i for i, p in enumerate(self._plist) if p.requires_grad]
-        state = [self._plist[i].grad for i in trainable]
-        kw = dict(eps=self.eps, drop_seed=drop[1], drop_p=drop[0], want_dx=want_dx)
-        if len(trainable) == len(self._plist) and all(g is None for g in state):
-            dx = ops.temporal_head_bwd(x, self._arena, self.ff, dout, grads, accumulate=False, **kw)
-            for i in trainable:
-                self._plist[i].grad = self._grad_view(i)
-        elif len(trainable) == len(self._plist) and all(g is not None and g.data_ptr() == self._grad_view(i).data_ptr() for g, i in zip(state, trainable)):
-            dx = ops.temporal_head_bwd(x, self._arena, self.ff, dout, grads, accumulate=True, **kw)
-        else:   # foreign .grad tensors or a partially frozen head: compute into a scratch arena and add
-            scratch = torch.empty_like(grads)
-            dx = ops.temporal_head_bwd(x, self._arena, self.ff, dout, scratch, accumulate=False, **kw)
-            for i in trainable:
-                o, p = self._offsets[i], self._plist[i]
-                g = scratch[o:o + p.numel()].view(p.shape)
-                p.grad = g.clone() if p.grad is None else p.grad.add_(g)
-        return dx
+        def run(target, accumulate, scratch):
+            return ops.temporal_head_bwd(x, self._arena, self.ff, dout, target, accumulate=accumulate, eps=self.eps, drop_seed=drop[1],
+                                         drop_p=drop[0], want_dx=want_dx)
+        return self._backward_to_grads(run)

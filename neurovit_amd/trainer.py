@@ -109,7 +109,7 @@ class TrainStep:
             arena, _ = vit.flat_parameters()
             broadcast_parameters(arena, process_group)
             for p in model.parameters():               # parameters outside the arena (4D temporal head)
-                if not any(p is q for q in vit._plist):
+                if not any(p is q for q in vit.arena_parameters()):
                     dist.broadcast(p.data, src=0, group=process_group)
             vit._shadow_key = None
         self._pg = process_group
@@ -118,18 +118,17 @@ class TrainStep:
         self._dp_world = world                         # (tests force the collective path on one rank by raising it)
         self._dp_buckets, self._dp_msg16 = n_buckets, grad_comm_dtype != torch.float32
         want_native_dp = (os.environ.get("NEUROVIT_NATIVE_DP", "1") != "0") if native_dp is None else bool(native_dp)
-        dev_ = next(model.parameters()).device
-        if want_native_dp and max_grad_norm is None and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev_.type == "cuda" \
+        dev0 = next(model.parameters()).device
+        if want_native_dp and max_grad_norm is None and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev0.type == "cuda" \
                 and (not dist.is_initialized() or dist.get_backend(process_group) == "nccl"):
             try:
-                self._ncomm = NativeComm(dev_, process_group)
+                self._ncomm = NativeComm(dev0, process_group)
             except RuntimeError as e:
                 import warnings
                 warnings.warn(f"neurovit_amd: native data-parallel step unavailable ({e}); using the Python-driven bucket pipeline")
         # DP: if collectives would queue behind the current stream's kernels (shared hardware queue), run the step on a stream where
         # they do not, and give the engine an auxiliary stream with the same property (parallel.streams_beside_collectives)
         self._compute_stream = None
-        dev0 = next(model.parameters()).device
         if world > 1 and dev0.type == "cuda" and self._ncomm is None:      # (the native data-parallel step issues its collectives on a stream it names itself)
             from .parallel import streams_beside_collectives
             self._compute_stream, aux = streams_beside_collectives(dev0, process_group)
@@ -161,10 +160,7 @@ class TrainStep:
         self.last_path = None                          # "native" | "general": which path the most recent step took (last_fuse_update: where AdamW ran)
         self._all_modules = list(model.modules())
         self._head = getattr(model, "_temporal_head", None)            # 4D: its 16 parameters are one arena (temporal.TemporalHead)
-        self._head_ids = set()
-        if self._head is not None:
-            self._head.flat_parameters()
-            self._head_ids = {id(p) for p in self._head._plist}
+        self._head_ids = set() if self._head is None else {id(p) for p in self._head.arena_parameters()}
         # (last: the average starts from the parameters as they are now - after the data-parallel broadcast above)
         self.ema = None if ema_decay is None else ModelEma(model, decay=ema_decay, warmup=ema_warmup, update_every=ema_update_every)
 
@@ -315,13 +311,11 @@ class TrainStep:
         vit = self._vit
         if vit.fp8_training and vit._fp8 is not None:
             return False                                                 # fp8 training forwards go through ViT._run_forward (general path)
-        if not vit._arena_ok():
-            vit._build_arena()
+        vit.flat_parameters()
         # .grad tensors that are not views of the gradient arena (set by foreign code) need the general path's accumulate-and-copy;
         # the first and the last parameter stand for all (the arena path sets or clears every .grad together)
         for i in (0, len(vit._plist) - 1):
-            g = vit._plist[i].grad
-            if g is not None and (vit._grads is None or g.data_ptr() != vit._grad_view(i).data_ptr()):
+            if vit._plist[i].grad is not None and not vit.grads_are_views((i,)):
                 return False
         return True
 
@@ -338,13 +332,12 @@ class TrainStep:
         vit, opt = self._vit, self.optimizer
         if not self._graphs_on or self.accumulation_steps != 1 or vit._dropout_p != (0.0, 0.0) or self.scaler is not None or self.clipper is not None:
             return None
-        if vit._grads is None:
-            vit._grads = torch.zeros_like(vit._arena)
+        grads = vit.gradient_arena()
         m_, v_ = opt.arena_state(vit)
         # everything a captured launch holds by address: a rebuilt gradient arena, re-created optimizer state or another form of the
         # last block at the same input address must not replay a graph that writes stale or freed buffers
         key = (fmri.data_ptr(), labels.data_ptr(), tuple(fmri.shape), tuple(fmri.stride()), vit._arena.data_ptr(), vit._shadow.data_ptr(),
-               vit._grads.data_ptr(), m_.data_ptr(), v_.data_ptr(), vit._rt.workspace(fmri.shape[0], True, fmri.device).data_ptr(), vit._rt.rows_form,
+               grads.data_ptr(), m_.data_ptr(), v_.data_ptr(), vit._rt.workspace(fmri.shape[0], True, fmri.device).data_ptr(), vit._rt.rows_form,
                vit.operands, self.static_scale)
         ent = self._graphs.get(key)
         if ent is None:
@@ -356,15 +349,13 @@ class TrainStep:
                 return None
             video = fmri.permute(0, 3, 1, 2).unsqueeze(1)
             vit.check_video(video, arena_checked=True)
-            if vit._grads is None:
-                vit._grads = torch.zeros_like(vit._arena)
             m, v = opt.arena_state(vit)
             g0 = opt.param_groups[0]
             torch.cuda.synchronize(fmri.device)
             graph = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(graph):
-                    loss, logits = vit._rt.train_step(video, labels, vit._arena, vit._shadow, vit._grads, m, v, step=1, lr=g0["lr"], betas=g0["betas"],
+                    loss, logits = vit._rt.train_step(video, labels, vit._arena, vit._shadow, grads, m, v, step=1, lr=g0["lr"], betas=g0["betas"],
                                                       eps=g0["eps"], weight_decay=g0["weight_decay"], accumulate=False, update=False,
                                                       loss_scale=self.static_scale)
             except Exception as e:                                       # capture refused (an unsupported call inside it): eager from now on
@@ -382,9 +373,7 @@ class TrainStep:
         opt._step_arena(vit, 1.0 / self.static_scale if self.static_scale > 0 else 1.0)      # AdamW over the arena + 16-bit shadow (mark_shadow_fresh inside)
         vit._last_logits = logits
         self.last_outputs = logits
-        if vit._plist[0].grad is None:
-            for i, p in enumerate(vit._plist):
-                p.grad = vit._grad_view(i)
+        vit.ensure_grad_views()
         return loss.reshape(())
 
     def _loss_opts(self, labels, mix):
@@ -410,10 +399,7 @@ class TrainStep:
         last_micro = (self._micro + 1) % self.accumulation_steps == 0
         video = fmri.permute(0, 3, 1, 2).unsqueeze(1)                    # NeuroEncoder.py:200-202 as a VIEW (the gather kernel reads the strides)
         vit.check_video(video, arena_checked=True)                       # (_native_ok has just validated / rebuilt the arena)
-        arena, shadow = vit._arena, vit._shadow
-        if vit._grads is None:
-            vit._grads = torch.zeros_like(arena)
-        grads = vit._grads
+        arena, shadow, grads = vit._arena, vit._shadow, vit.gradient_arena()
         vit._refresh_shadow()
         if not opt._bound:
             opt._bind()
@@ -441,18 +427,8 @@ class TrainStep:
             opt._steps += 1                 # (after the call: a refused step leaves the counter where it was)
         vit._last_logits = logits
         self.last_outputs = logits
-        if vit._plist[0].grad is None:                                   # .grad = views of the gradient arena (once; they stay valid)
-            for i, p in enumerate(vit._plist):
-                p.grad = vit._grad_view(i)
-        if fuse == 1 and vit._plist[10].grad is not None:
-            # the layers' Linear weights were updated inside their gradient GEMMs and their gradients never written: no .grad rather
-            # than a stale one (entries 8 + 11 l + {2, 3, 7, 9} of the parameter table: to_qkv, to_out, FC1, FC2 weights of block l)
-            for l in range(vit._cfg.depth):
-                for k in (2, 3, 7, 9):
-                    vit._plist[8 + 11 * l + k].grad = None
-        elif fuse != 1 and vit._plist[10].grad is None:
-            for i, p in enumerate(vit._plist):
-                p.grad = vit._grad_view(i)
+        vit.ensure_grad_views()                                          # .grad = views of the gradient arena (once; they stay valid)
+        vit.linear_weight_grads(present=fuse != 1)                       # (fuse 1 never wrote the layers' Linear weight gradients)
         self._micro += 1
         if last_micro and self.clipper is not None:
             # clipping: the call above ran no optimizer work (update = 0: with a loss-scale state only the scaling of the loss gradient);
@@ -522,8 +498,7 @@ class TrainStep:
                 arena_synced = self.sync is not None
                 inline = self._outside if arena_synced else self._outside + self._inside
                 head = self._head
-                if head is not None and head._grads is not None and all(p.grad is not None and p.grad.data_ptr() == head._grad_view(i).data_ptr()
-                                                                        for i, p in enumerate(head._plist)):
+                if head is not None and head.grads_are_views():
                     dist.all_reduce(head._grads, group=self._pg)       # the temporal head's gradient arena: one message
                     if not arena_synced:
                         head._grads.mul_(scale)                        # (otherwise the fused step applies grad_scale)
@@ -614,7 +589,6 @@ class Trainer:
     """
 
     def __init__(self, config, model, dataset_train, dataset_val):
-        import os as _os
         self.config = config
         self.device = config['DEVICE']
         self.model = model.to(self.device)
@@ -647,7 +621,6 @@ class Trainer:
         total_params = sum(p.numel() for p in self.model.parameters())
         trainable_params = sum(p.numel() for p in self.model.parameters() if p.requires_grad)
         print(f'Model total parameters: {total_params/1e6:.2f}M (trainable {trainable_params/1e6:.2f}M and frozen {(total_params-trainable_params)/1e6:.2f}M)')
-        self._os = _os
         self.validation_precision = config.get('VALIDATION_PRECISION', 'fp32')
         self.augment = self.augment_from_config(config)
         self.mix = self.mix_from_config(config)
@@ -777,8 +750,8 @@ class Trainer:
     def run(self):
         import datetime
         path = f"{self.output_dir}/{datetime.datetime.now().strftime('%Y-%m-%d_%H-%M-%S')}"
-        self._os.makedirs(path, exist_ok=True)
-        self._os.makedirs('./results', exist_ok=True)
+        os.makedirs(path, exist_ok=True)
+        os.makedirs('./results', exist_ok=True)
         for epoch in range(self.start_epoch, self.epochs):
             self.train(epoch)
             self.validate(epoch)

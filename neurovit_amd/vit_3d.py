@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import _cabi, engine, ops
+from .arena import FlatArena
 
 
 def pair(t):
@@ -342,7 +343,7 @@ class _ViTFunction(torch.autograd.Function):
         return (None, dvideo, None, None) + (None,) * len(ctx.module._plist)
 
 
-class ViT(nn.Module):
+class ViT(FlatArena, nn.Module):
     """vit_3d.py:77-126, MI355X-native.  forward(video[B, C, F, H, W]) -> [B, num_classes] (fp32)."""
 
     def __init__(self, *, image_size, image_patch_size, frames, frame_patch_size, num_classes, dim, depth, heads, mlp_dim,
@@ -384,26 +385,21 @@ class ViT(nn.Module):
         # heads == 1 with dim_head == dim: the reference drops to_out (nn.Identity, vit_3d.py:32,43-46).  The engine's parameter
         # table always carries the projection, so the arena keeps those slots as CONSTANTS no nn.Parameter views - weight = identity,
         # bias = 0: x + I ao + 0 is exactly x + ao (products with 1.0 and sums with 0.0 are exact), its data gradient g I is
-        # exactly g, and the optimizer never sees them (see _build_arena / mark_shadow_fresh)
+        # exactly g, and the optimizer never sees them (see _packed / mark_shadow_fresh)
         self._no_proj = (heads == 1 and dim_head == dim)
-        self._phantom = []         # [(offset, fp32 constant)] of those slots
         self._dropout_p = (float(dropout), float(emb_dropout))
         self._cfg = engine.make_config(image_size=image_height, image_patch_size=patch_height, image_width=image_width, patch_width=patch_width, frames=frames,
                                        frame_patch_size=frame_patch_size, num_classes=num_classes, dim=dim, depth=depth,
                                        heads=heads, mlp_dim=mlp_dim, channels=channels, dim_head=dim_head,
                                        pool=pool)
         self._rt = engine.VitRuntime(self._cfg)
-        self._arena: Optional[torch.Tensor] = None      # flat fp32 master parameters
-        self._shadow: Optional[torch.Tensor] = None     # flat bf16 copy read by the MFMA kernels
-        self._grads: Optional[torch.Tensor] = None      # flat fp32 gradients (param.grad are views)
-        self._layout = None
-        self._plist: List[nn.Parameter] = []
+        self._init_arena()                              # arena.FlatArena: _arena, _grads, _plist, ...; _shadow and _phantom are set in _packed
+        self._layout = None                             # (offsets, numels, total) of engine.param_layout without the constant slots
         self._shadow_key = None
         self._last_logits = None   # most recent forward's logits (the Trainer shell reads them without a second forward)
         self._grad_sync = None     # parallel.GradSync: all-reduce gradient buckets while backward still runs
         self._fp8 = None           # enable_fp8(): e4m3 weights + scales for inference forwards
         self.fp8_training = False  # enable_fp8(training=True): training forwards on e4m3 operands too
-        self._param_generation = 0 # bumped whenever the fused optimizer rewrites the arena (FusedAdamW.step / step_range)
         # Arithmetic of eval-mode forwards that record no graph: "bf16" (bf16 MFMA operands, the training arithmetic) or "fp32"
         # (every operand fp32 on the fp32 MFMA: what the reference's validate computes, Trainer.py:101-118 - logits within 1e-5
         # of its CPU forward, about 3x the time).  Set directly, through `precision(...)`, or by the config key
@@ -444,68 +440,54 @@ class ViT(nn.Module):
         return torch.float16 if self.operands == "fp16" else torch.bfloat16
 
     # ------------------------------------------------------------------ arena management
+    # entries of the native parameter table (engine.param_layout): 8 ahead of the blocks, 11 per block l at 8 + 11 l + k
+    _QKV_W, _OUT_W, _OUT_B, _FC1_W, _FC2_W = 2, 3, 4, 7, 9
+
+    def _block_entries(self, *which):
+        return [8 + 11 * l + k for l in range(self._cfg.depth) for k in which]
+
     def _build_arena(self):
-        """(Re)pack all parameters into one contiguous fp32 arena on their current device and make every
-        nn.Parameter a view of it.  Called lazily: after construction, after .to(device), after foreign code
-        replaced a parameter's storage."""
+        """The layout is the engine's parameter table, less the constant slots (see __init__); FlatArena._pack does the rest."""
         plist = [p for _, p in self.named_parameters()]
         if self._layout is None:
             off, num, total = engine.param_layout(self._cfg)
-            self._phantom_slots = []
-            if self._no_proj:      # entries 8 + 11 l + {3, 4} of the table are to_out.0.weight / .bias of block l: no module parameter
-                d = self._cfg.dim
-                drop = {8 + 11 * l + k for l in range(self._cfg.depth) for k in (3, 4)}
-                for i in sorted(drop):
-                    self._phantom_slots.append((off[i], num[i], (i - 8) % 11 == 3))
-                off = [o for i, o in enumerate(off) if i not in drop]
-                num = [n for i, n in enumerate(num) if i not in drop]
-            assert len(off) == len(plist) and all(p.numel() == n for p, n in zip(plist, num)), \
+            # to_out.0.weight / .bias of every block are no module parameter without the projection
+            out_w, out_b = (self._block_entries(self._OUT_W), self._block_entries(self._OUT_B)) if self._no_proj else ([], [])
+            drop = sorted(out_w + out_b)
+            kept = [i for i in range(len(off)) if i not in drop]
+            self._phantom_slots = [(off[i], num[i], i in out_w) for i in drop]
+            assert len(kept) == len(plist) and all(p.numel() == num[i] for p, i in zip(plist, kept)), \
                 "parameter table of the native engine does not match the module tree"
-            self._layout = (off, num, total)
-        off, num, total = self._layout
-        dev = plist[0].device
-        arena = torch.zeros(total, dtype=torch.float32, device=dev)
+            self._layout = ([off[i] for i in kept], [num[i] for i in kept], total)
+            # positions in _plist of the blocks' Linear weights (linear_weight_grads)
+            self._linear_weights = [kept.index(i) for i in self._block_entries(self._QKV_W, self._OUT_W, self._FC1_W, self._FC2_W) if i in kept]
+        self._pack(plist, *self._layout)
+
+    def _packed(self):
+        """the constant slots, and a 16-bit shadow that is cast on its next use"""
+        arena = self._arena
         self._phantom = []
         for o, n, is_weight in self._phantom_slots:
             if is_weight:
-                arena[o:o + n].copy_(torch.eye(self._cfg.dim, dtype=torch.float32, device=dev).reshape(-1))
+                arena[o:o + n].copy_(torch.eye(self._cfg.dim, dtype=torch.float32, device=arena.device).reshape(-1))
             self._phantom.append((o, arena[o:o + n].clone()))
-        grads_alive = self._grads is not None and self._grads.device == dev
-        with torch.no_grad():
-            for p, o, n in zip(plist, off, num):
-                arena[o:o + n].copy_(p.detach().reshape(-1).float())
-                p.data = arena[o:o + n].view(p.shape)
-        self._arena, self._plist = arena, plist
-        self._shadow = torch.empty(total, dtype=self._dtype16(), device=dev)
+        self._shadow = torch.empty(arena.numel(), dtype=self._dtype16(), device=arena.device)
         self._shadow_key = None
-        if not grads_alive:
-            self._grads = None
 
-    def _arena_ok(self) -> bool:
-        if self._arena is None:
-            return False
-        off, num, _ = self._layout
-        base = self._arena.data_ptr()
-        for p, o in zip(self._plist, off):
-            if p.data_ptr() != base + 4 * o:
-                return False
-        return True
+    def gather_foreign_grads(self):
+        """Nothing is gathered for the encoder: the fused step applies what the gradient arena holds, which is what its backward
+        passes write unless foreign code has set a .grad of its own (FlatArena._backward_to_grads adds into such a tensor)."""
 
-    def flat_parameters(self):
-        """(arena fp32, shadow bf16) - used by the fused optimizer and the DP gradient all-reduce."""
-        if not self._arena_ok():
-            self._build_arena()
-        return self._arena, self._shadow
-
-    def flat_gradients(self) -> torch.Tensor:
-        self.flat_parameters()
-        if self._grads is None:
-            self._grads = torch.zeros_like(self._arena)
-        return self._grads
-
-    def _grad_view(self, i: int) -> torch.Tensor:
-        off, num, _ = self._layout
-        return self._grads[off[i]:off[i] + num[i]].view(self._plist[i].shape)
+    def linear_weight_grads(self, present: bool):
+        """.grad of the blocks' Linear weights (to_qkv, to_out, FC1, FC2): their views of the gradient arena, or - after a step
+        that updated them inside their weight-gradient GEMMs and never stored their gradients (TrainStep fuse_update = 1) - None
+        rather than a stale gradient.  The first of them stands for all: they are set and cleared together."""
+        have = self._plist[self._linear_weights[0]].grad is not None
+        if present and not have:
+            self.install_grad_views(self._linear_weights)
+        elif have and not present:
+            for i in self._linear_weights:
+                self._plist[i].grad = None
 
     def mark_shadow_fresh(self):
         """Called by the fused AdamW, which writes the arena and the bf16 shadow itself (through raw pointers: no tensor
@@ -898,27 +880,17 @@ class ViT(nn.Module):
             _fire_attend_backward_hooks(attend, _attend_backward_hooks(attend), dP[l], "neurovit_amd.ViT")
 
     def _run_backward_export(self, dlogits, dvideo, export):
-        trainable = [i for i, p in enumerate(self._plist) if p.requires_grad]
-        if not trainable:
+        if not any(p.requires_grad for p in self._plist):
             if dvideo is not None or export is not None:
                 self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False, attn_grad=export)
             return
-        grads = self.flat_gradients()
-        state = [self._plist[i].grad for i in trainable]
-        if all(g is None for g in state):
-            self._backward_into(dlogits, grads, accumulate=False, dvideo=dvideo, attn_grad=export)
-            for i in trainable:
-                self._plist[i].grad = self._grad_view(i)
-        elif all(g is not None and g.data_ptr() == self._grad_view(i).data_ptr() for g, i in zip(state, trainable)):
-            self._backward_into(dlogits, grads, accumulate=True, dvideo=dvideo, attn_grad=export)
-        else:   # foreign .grad tensors: compute into a scratch arena and add
-            scratch = torch.empty_like(grads)
-            self._rt.backward(dlogits, self._arena, self._shadow, scratch, accumulate=False, dvideo=dvideo, attn_grad=export)
-            off, num, _ = self._layout
-            for i in trainable:
-                g = scratch[off[i]:off[i] + num[i]].view(self._plist[i].shape)
-                p = self._plist[i]
-                p.grad = g.clone() if p.grad is None else p.grad.add_(g)
+
+        def run(target, accumulate, scratch):
+            if scratch:       # foreign .grad tensors: one plain backward, no gradient-bucket pipeline
+                self._rt.backward(dlogits, self._arena, self._shadow, target, accumulate=False, dvideo=dvideo, attn_grad=export)
+            else:
+                self._backward_into(dlogits, target, accumulate=accumulate, dvideo=dvideo, attn_grad=export)
+        self._backward_to_grads(run)
 
     def mirrored_ranges(self):
         """Arena element ranges whose gradients nv_vit_backward_stages16 also writes, rounded to bf16, into `grads16`: the weights of
@@ -975,8 +947,8 @@ class ViT(nn.Module):
             # takes its extents from the config, so a wrong-sized volume must never reach it
             raise ValueError(f"neurovit_amd.ViT: expected video [B, {c.channels}, {c.frames}, {c.image_size}, {width}] "
                              f"(channels, frames, height, width), got {tuple(video.shape)}")
-        if not arena_checked and not self._arena_ok():
-            self._build_arena()
+        if not arena_checked:
+            self.flat_parameters()
         if self._arena.device != video.device:
             raise RuntimeError(f"neurovit_amd.ViT: parameters on {self._arena.device}, input on {video.device}")
 

@@ -161,20 +161,131 @@ def test_constructions_off_the_neuroencoder_path():
         ViT(**dict(W.MICRO, image_size=30))              # vit_3d.py:83 divisibility assert
 
 
-def test_arena_views_survive_load_state_dict_and_track_to():
-    from neurovit_amd.vit_3d import ViT
-    m = ViT(**W.MICRO)
-    arena, shadow = m.flat_parameters()
-    sd = W.make_tensors(W.vit_param_spec(**W.MICRO), 1)
-    m.load_state_dict(sd)
-    assert m._arena_ok() and m.flat_parameters()[0] is arena
-    off, num, _ = m._layout
-    for (k, v), o, n in zip(sd.items(), off, num):
-        assert torch.equal(arena[o:o + n], v.reshape(-1)), k
-    m.double().float()                                    # storage replaced behind our back
-    assert not m._arena_ok()
-    a2, _ = m.flat_parameters()
-    assert m._arena_ok() and torch.equal(a2, arena)
+def _temporal_head():
+    """(the 4D model, its TemporalHead): built as m4 of test_state_dict_keys_and_shapes_match_reference, on a two-block encoder"""
+    import tempfile
+    from neurovit_amd.NeuroEncoder import NeuroEncoder
+    small = dict(TRAINING_VIT_DIM=128, TRAINING_VIT_DEPTH=2, TRAINING_VIT_HEADS=2, TRAINING_VIT_MLP_DIM=256)
+    with tempfile.TemporaryDirectory() as td:
+        torch.save(NeuroEncoder(W.neuro_config(16, 8, **small)).state_dict(), os.path.join(td, "c16.pth"))
+        m4 = NeuroEncoder(W.neuro_config(16, 8, dim=4, GLOBAL_BASE_PATH=td, BEST_MODEL_PATH="c16.pth", **small))
+    return m4, m4._temporal_head
+
+
+@pytest.fixture(params=["vit", "head"])
+def arena_holder(request):
+    """(holder, its parameters' modules, a state_dict of other values per module, arena size): the two owners of a flat arena"""
+    if request.param == "vit":
+        from neurovit_amd.vit_3d import ViT
+        m = ViT(**W.MICRO)
+        return m, [m], [W.make_tensors(W.vit_param_spec(**W.MICRO), 1)], None
+    m4, head = _temporal_head()
+    sd = W.make_tensors(W.temporal_param_spec(), 1)
+    parts = [dict((k[len(pre):], v) for k, v in sd.items() if k.startswith(pre)) for pre in ("temporal_transformer.", "projection_head.")]
+    return head, [m4.temporal_transformer, m4.projection_head], parts, 10280
+
+
+def _offsets(holder):
+    return holder._layout[0] if hasattr(holder, "_layout") else holder._offsets
+
+
+def test_arena_views_survive_load_state_dict_and_track_to(arena_holder):
+    holder, modules, parts, total = arena_holder
+    arena = holder.flat_parameters()[0]
+    assert total is None or arena.numel() == total
+    generation = holder._param_generation
+    for m, sd in zip(modules, parts):
+        m.load_state_dict(sd)
+    assert holder._arena_ok() and holder.flat_parameters()[0] is arena
+    values = [v for sd in parts for v in sd.values()]
+    assert len(values) == len(holder._plist)
+    for v, o in zip(values, _offsets(holder)):
+        assert torch.equal(arena[o:o + v.numel()], v.reshape(-1))
+    modules[0].double().float()                           # storage replaced behind our back
+    assert not holder._arena_ok()
+    a2, _ = holder.flat_parameters()
+    assert holder._arena_ok() and a2 is not arena and torch.equal(a2, arena)
+    assert all(q.data_ptr() == a2.data_ptr() + 4 * o for q, o in zip(holder._plist, _offsets(holder)))
+    if total is not None:                                 # the head counts its rebuilds (derived copies key on it)
+        assert holder._param_generation == generation + 1
+
+
+def test_backward_gradient_placement_three_ways(arena_holder):
+    """FlatArena._backward_to_grads with a fake backward that fills its target with 1, 2, 3, ...: where the gradients go in each of
+    the three states of .grad.  A partially frozen holder: the head computes into scratch (as before it shared this code); the ViT
+    keeps writing its gradient arena and installs views for the trainable parameters only (as before, too)."""
+    holder = arena_holder[0]
+    is_head = arena_holder[3] is not None
+    holder.flat_parameters()
+    plist, off = holder._plist, _offsets(holder)
+    calls = []
+
+    def fake(target, accumulate, scratch):
+        calls.append((target, accumulate, scratch))
+        fresh = torch.arange(1, target.numel() + 1, dtype=torch.float32)
+        target.copy_(target + fresh if accumulate else fresh)
+        return "dx"
+
+    def is_view(i):
+        return plist[i].grad is not None and plist[i].grad.data_ptr() == holder._grad_view(i).data_ptr()
+
+    def expect(i, times=1):
+        return (times * torch.arange(off[i] + 1, off[i] + plist[i].numel() + 1, dtype=torch.float32)).view(plist[i].shape)
+
+    # no .grad anywhere: the arena is written, every .grad becomes its view
+    assert holder._backward_to_grads(fake) == "dx"
+    grads = holder._grads
+    assert calls[-1][0] is grads and calls[-1][1:] == (False, False)
+    assert all(is_view(i) and torch.equal(plist[i].grad, expect(i)) for i in range(len(plist)))
+    # every .grad its view: accumulated in place, same views
+    holder._backward_to_grads(fake)
+    assert calls[-1][0] is grads and calls[-1][1:] == (True, False) and holder._grads is grads
+    assert all(is_view(i) and torch.equal(plist[i].grad, expect(i, 2)) for i in range(len(plist)))
+    # one foreign .grad, one missing: scratch, the arena is not written
+    before = grads.clone()
+    foreign = torch.full_like(plist[1], 5.0)
+    plist[1].grad, plist[2].grad = foreign, None
+    holder._backward_to_grads(fake)
+    assert calls[-1][0] is not grads and calls[-1][1:] == (False, True)
+    assert all(torch.equal(grads[off[i]:off[i] + plist[i].numel()], before[off[i]:off[i] + plist[i].numel()]) for i in (1, 2))
+    assert plist[1].grad is foreign and torch.equal(foreign, 5.0 + expect(1))             # added to in place
+    assert not is_view(2) and torch.equal(plist[2].grad, expect(2))                        # a clone of the scratch slot
+    assert plist[2].grad.data_ptr() != calls[-1][0][off[2]:].data_ptr()
+    assert is_view(0) and torch.equal(plist[0].grad, expect(0, 3))                         # (views are added to like any other .grad)
+    # one frozen parameter, nothing else set
+    for p in plist:
+        p.grad = None
+    plist[3].requires_grad_(False)
+    before = grads.clone()
+    holder._backward_to_grads(fake)
+    assert plist[3].grad is None
+    trainable = [i for i in range(len(plist)) if i != 3]
+    if is_head:
+        assert calls[-1][0] is not grads and calls[-1][1:] == (False, True) and torch.equal(grads, before)
+        assert all(not is_view(i) and torch.equal(plist[i].grad, expect(i)) for i in trainable)
+    else:
+        assert calls[-1][0] is grads and calls[-1][1:] == (False, False)
+        assert all(is_view(i) and torch.equal(plist[i].grad, expect(i)) for i in trainable)
+
+
+def test_temporal_head_gathers_foreign_gradients():
+    """None -> a zeroed slot (and .grad stays None), foreign -> copied and re-pointed, a view -> untouched"""
+    _, head = _temporal_head()
+    grads = head.flat_gradients()
+    grads.fill_(7.0)
+    plist = head._plist
+    foreign = [torch.full_like(p, float(i)) for i, p in enumerate(plist)]
+    for i, p in enumerate(plist):
+        p.grad = None if i % 3 == 0 else (foreign[i] if i % 3 == 1 else head._grad_view(i))
+    assert head.gather_foreign_grads() is grads
+    for i, (p, o) in enumerate(zip(plist, head._offsets)):
+        slot = grads[o:o + p.numel()]
+        if i % 3 == 0:
+            assert p.grad is None and not slot.any()
+        else:
+            assert p.grad.data_ptr() == head._grad_view(i).data_ptr() and p.grad.shape == p.shape
+            assert torch.equal(slot, torch.full_like(slot, float(i) if i % 3 == 1 else 7.0))
+    assert all(torch.equal(f, torch.full_like(f, float(i))) for i, f in enumerate(foreign))        # the foreign tensors themselves: read only
 
 
 def test_device_prefetcher_preserves_order_and_passthrough():
