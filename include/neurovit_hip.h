@@ -413,6 +413,43 @@ int nv_adamw_step_clipped(float* p, const void* grad, int grad_bf16, float* m, f
 /* grad_bf16 = 1: `grad` is a bf16 buffer (the gradient all-reduce ran on bf16 messages): no cast back to fp32 is needed. */
 /* max_blocks > 0 caps the grid (256-thread workgroups, grid-stride): used when the update of one gradient bucket runs on a
    side stream beside the backward pass, so that it takes a slice of the chip instead of queueing ahead of the GEMMs. */
+/* ---- parameter groups for the fused AdamW (neurovit_amd.FusedAdamW with more than one (lr, weight_decay); added within revision 8):
+ * nv_adamw_step_clipped over the flat arena [0, count) - the same pointers, fp32 or 16-bit gradients, optional 16-bit shadow in the
+ * current operand format, grad_scale, max_blocks, optional scale_state and clip_state - whose lr and weight_decay come from a table.
+ *   groups    G of them, 1 <= G <= NV_ADAMW_MAX_GROUPS, each with its own lr_g and weight_decay_g (finite, >= 0); beta1, beta2 and eps
+ *             are shared.  They travel with every call, in nv_adamw_groups: decay_g = float(1 - lr_g * weight_decay_g) and
+ *             step_size_g = float(lr_g / (1 - beta1^step)) are formed in double per call, as nv_adamw_step forms its own, and reach
+ *             the kernel as arguments - no copy, no synchronisation.  With scale_state the step count is the device block's: a
+ *             one-wave launch in front forms step_size_g from it with the expression of nv_loss_scale_update (`step` is ignored and
+ *             the block's own step size, formed from the lr that nv_loss_scale_update got, is not read).
+ *   segments  S of them, 1 <= S <= NV_ADAMW_MAX_SEGMENTS: segment s covers the elements [end[s-1], end[s]) (end[-1] = 0) and belongs
+ *             to group group[s].  Ends ascend strictly, the last is `count`; a boundary may fall at ANY element.  The table is static
+ *             for a model and lives in device memory that the caller owns: nv_adamw_segments_bytes(S) bytes, 16-byte aligned, filled
+ *             ONCE by nv_adamw_segments_build, which checks the host arrays (NV_ERR_ARG: S or G out of range, ends not ascending, last
+ *             end != count, a group index >= G, count no positive multiple of 4, a table too small), uploads them and returns when the
+ *             copy has finished (not inside a stream capture).  The library remembers the addresses it has built:
+ *             nv_adamw_step_grouped refuses a table it did not build, or one built for another G or count.  Call
+ *             nv_adamw_segments_release before freeing the memory (the address is forgotten; building again over it is also fine).
+ *             The tail of the buffer is scratch of the step under a scale_state: one table serves one stream at a time.
+ * Every element gets the bits nv_adamw_step_clipped gives it when called with its own group's lr and weight_decay.
+ * nv_adamw_step_grouped returns NV_ERR_ARG before any launch for: a null p / grad / m / v or the alignments nv_adamw_step asks for,
+ * count no positive multiple of 4, step < 1, a wrong struct_size, G out of range, a non-finite or negative lr_g / weight_decay_g,
+ * a segment table that was not built, or was built for another G or count. */
+#define NV_ADAMW_MAX_GROUPS 64
+#define NV_ADAMW_MAX_SEGMENTS 1024
+typedef struct nv_adamw_groups {
+  int struct_size;                              /* sizeof(nv_adamw_groups) */
+  int n_groups;                                 /* G */
+  const void* segments;                         /* device table filled by nv_adamw_segments_build */
+  double lr[NV_ADAMW_MAX_GROUPS];               /* [0, G) are read */
+  double weight_decay[NV_ADAMW_MAX_GROUPS];
+} nv_adamw_groups;
+long nv_adamw_segments_bytes(int segments);     /* 0 for a count outside 1 .. NV_ADAMW_MAX_SEGMENTS */
+int nv_adamw_segments_build(void* table, long table_bytes, const long* ends, const int* groups, int segments, int n_groups, long count, void* stream);
+int nv_adamw_segments_release(void* table);
+int nv_adamw_step_grouped(float* p, const void* grad, int grad_bf16, float* m, float* v, void* p16, long count, int step,
+                          const nv_adamw_groups* groups, double beta1, double beta2, double eps, float grad_scale, int max_blocks,
+                          const float* scale_state, const float* clip_state, void* stream);
 /* ---- exponential moving average of a parameter arena (neurovit_amd.ModelEma; added within revision 8):
  *   ema[i] = ema[i] + (p[i] - ema[i]) * weight     for i in [0, count)
  * in fp32, the difference, the product and the sum each rounded on their own (no fused multiply-add): bit-equal to the same torch

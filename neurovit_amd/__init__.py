@@ -18,4 +18,7 @@ def __getattr__(name):
     if name == "ModelEma":
         from .optim import ModelEma
         return ModelEma
+    if name in ("param_groups", "LRSchedule", "set_group_lrs"):      # the optimizer half of the fine-tuning recipe
+        from . import optim
+        return getattr(optim, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

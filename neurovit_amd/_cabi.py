@@ -87,6 +87,16 @@ class LossOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("label_smoothing", ctypes.c_float), ("class_weight", ctypes.c_void_p), ("mix", ctypes.c_void_p)]
 
 
+ADAMW_MAX_GROUPS, ADAMW_MAX_SEGMENTS = 64, 1024      # NV_ADAMW_MAX_GROUPS, NV_ADAMW_MAX_SEGMENTS
+
+
+class AdamwGroups(ctypes.Structure):
+    """struct nv_adamw_groups (neurovit_hip.h, added within revision 8): the per-call half of nv_adamw_step_grouped's table - lr and
+    weight_decay per group - and the device address of the segment table that nv_adamw_segments_build filled."""
+    _fields_ = [("struct_size", ctypes.c_int), ("n_groups", ctypes.c_int), ("segments", ctypes.c_void_p),
+                ("lr", ctypes.c_double * ADAMW_MAX_GROUPS), ("weight_decay", ctypes.c_double * ADAMW_MAX_GROUPS)]
+
+
 MIX_COLS = 12        # NV_MIX_COLS: int32 columns of a row of nv_mix_params
 
 

@@ -403,6 +403,16 @@ __device__ __forceinline__ void adamw_update4(f32x4& pv, const f32x4 gv, f32x4& 
 #pragma unroll
   for (int j = 0; j < 4; ++j) pv[j] -= a.step_size * (mv[j] / (sqrtf(vv[j]) / a.bc2_sqrt + a.eps));
 }
+// The sibling for a 16-byte group whose elements belong to different parameter groups (nv_adamw_step_grouped, optim.hip): `decay` and
+// `step_size` per element, every expression in the shape it has above, so an element gets the bits adamw_update4 gives it with its
+// own group's constants.
+__device__ __forceinline__ void adamw_update4_each(f32x4& pv, const f32x4 gv, f32x4& mv, f32x4& vv, const AdamArgs& a, const f32x4 decay, const f32x4 step_size) {
+  pv *= decay;
+  mv += (gv - mv) * a.one_minus_b1;
+  vv = vv * a.beta2 + (gv * a.one_minus_b2) * gv;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) pv[j] -= step_size[j] * (mv[j] / (sqrtf(vv[j]) / a.bc2_sqrt + a.eps));
+}
 
 // LDS-DMA issued by the waves that also read the tiles.  Two things the builtin form costs here:
 //   * descriptor: the bases come out of 64-bit VALU address arithmetic on blockIdx, the compiler treats them as divergent and wraps

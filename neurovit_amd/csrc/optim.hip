@@ -6,6 +6,8 @@
 //   cast_bf16_2d   fp32 -> bf16 with optional zero column padding (patch-embed weight at P % 8 != 0)
 //   ce_loss        nn.CrossEntropyLoss() (mean) forward + d(loss)/d(logits) in one tiny kernel
 #include "common.h"
+#include <mutex>
+#include <unordered_map>
 
 // Streaming kernel: every byte is touched once per step, so loads and stores carry the non-temporal hint (5.8 vs 5.4 TB/s
 // back to back on MI355X); the bf16 shadow is stored normally - the next forward pass reads it.
@@ -99,6 +101,206 @@ extern "C" int nv_adamw_step_clipped(float* p, const void* grad, int grad_bf16, 
     else if (grad_bf16) hipLaunchKernelGGL((adamw_kernel<true, T>), grid, wg, 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state, no_clip);
     else hipLaunchKernelGGL((adamw_kernel<false, T>), grid, wg, 0, (hipStream_t)stream, p, grad, m, v, (r16*)p16, n4, a, scale_state, no_clip));
   NV_CHECK_LAUNCH("nv_adamw_step");
+  return NV_OK;
+}
+
+// ---- parameter groups: nv_adamw_step_clipped whose `lr` and `weight_decay` come from a table (no weight decay on biases / LayerNorm /
+// embeddings, layer-wise learning-rate decay).  Two tables, split by how often they change:
+//   * the SEGMENTS - end offset and group index of each run of elements that shares one group - are static for a model: device
+//     memory, validated and uploaded once by nv_adamw_segments_build;
+//   * the per-group constants decay_g / step_size_g change every step (schedule, bias correction): formed on the host exactly as
+//     make_adam_args forms them and passed BY VALUE (512 bytes of kernel arguments: no copy, no synchronisation).  Under a dynamic
+//     loss scale the step count lives on the device: a one-wave launch forms step_size_g from LS_STEPS with the double expression of
+//     loss_scale_update_kernel into the tail of the segment table's buffer.
+// A workgroup's pass covers 256 * U * 4 contiguous elements, as in adamw_kernel.  It issues the loads of p / g / m / v first (they do
+// not depend on the group) and resolves the segment of its first element by a scalar binary search while they are in flight.  When the
+// last element lies in the same segment - at ViT3D-base all but ~150 of 43 000 spans - that group's two constants are all it needs.
+// Only a span that holds a boundary selects the constants per element (the temporal head's arena is densely packed: boundaries fall at
+// any element, inside a 16-byte group too), by a walk over the span's few segments that is itself workgroup-uniform.  Both cases
+// feed ONE copy of the arithmetic, adamw_update4_each: a second copy behind a branch cost 24 VGPRs and two waves per SIMD
+// (95 against 71 VGPRs; the plain kernel has 63).
+struct AdamGroupConsts { float decay[NV_ADAMW_MAX_GROUPS]; float step_size[NV_ADAMW_MAX_GROUPS]; };
+struct AdamGroupLr { double lr[NV_ADAMW_MAX_GROUPS]; };
+
+__global__ void adamw_group_steps_kernel(const float* __restrict__ st, const AdamGroupLr lr, int G, double beta1, float* __restrict__ out) {
+  if (st[LS_SKIP] != 0.f) return;                       // (a skipped first step has t = 0: nothing to form, nothing reads it)
+  const double t = (double)st[LS_STEPS];                // already counts the update that nv_loss_scale_update has just decided on
+  const int g = threadIdx.x;
+  if (g < G) out[g] = (float)(lr.lr[g] / (1.0 - pow(beta1, t)));
+}
+
+template <bool G16, typename T, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, const void* __restrict__ grad, float* __restrict__ m,
+                                                            float* __restrict__ v, r16* __restrict__ p16, long n4, AdamArgs a, const AdamGroupConsts gc,
+                                                            const long* __restrict__ seg_end, const int* __restrict__ seg_group, int S,
+                                                            const float* __restrict__ dyn_step, const float* __restrict__ dyn,
+                                                            const float* __restrict__ clip) {
+  if (!adam_dyn(a, dyn)) return;
+  if constexpr (CLIP) a.grad_scale *= clip[GC_COEF];
+  constexpr int U = NV_ADAMW_UNROLL;
+  constexpr long SPAN4 = 256L * U;
+  for (long b0 = (long)blockIdx.x * SPAN4; b0 < n4; b0 += (long)gridDim.x * SPAN4) {      // b0: workgroup-uniform
+    const long i0 = b0 + threadIdx.x;
+    f32x4 pv[U], gv[U], mv[U], vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + (long)u * 256;
+      if (i < n4) {
+        pv[u] = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(p) + i);
+        if constexpr (G16) {
+          const r16x4 g4 = reinterpret_cast<const r16x4*>(grad)[i];
+          gv[u] = dec4<T>(g4) * a.grad_scale;
+        } else {
+          gv[u] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(grad) + i) * a.grad_scale;
+        }
+        mv[u] = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(m) + i);
+        vv[u] = __builtin_nontemporal_load(reinterpret_cast<f32x4*>(v) + i);
+      }
+    }
+    // the segment of the span's first element: the first s with seg_end[s] > e_first (exists: seg_end[S - 1] = 4 * n4 > e_first)
+    const long e_first = 4 * b0, e_last = 4 * (b0 + SPAN4 < n4 ? b0 + SPAN4 : n4) - 1;
+    int lo = 0, hi = S - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (seg_end[mid] > e_first) hi = mid; else lo = mid + 1;
+    }
+    const int s0 = lo;
+    const int g0 = seg_group[s0];
+    const float d0 = gc.decay[g0], z0 = dyn ? dyn_step[g0] : gc.step_size[g0];
+    const bool one_group = seg_end[s0] > e_last;         // workgroup-uniform: the whole span is one segment's
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long i = i0 + (long)u * 256;
+      f32x4 dec = f32x4{d0, d0, d0, d0}, ss = f32x4{z0, z0, z0, z0};
+      if (!one_group) {
+        // a boundary inside the span: walk its segments (workgroup-uniform, scalar loads); every element takes the constants of the
+        // last segment that starts at or before it
+        const int r0 = 4 * ((int)threadIdx.x + u * 256);          // this lane's first element, counted from the span's
+        for (int s = s0 + 1; seg_end[s - 1] <= e_last; ++s) {      // (seg_end[S - 1] = 4 * n4 > e_last: s stays inside the table)
+          const int first = (int)(seg_end[s - 1] - e_first);
+          const int g = seg_group[s];
+          const float d = gc.decay[g], z = dyn ? dyn_step[g] : gc.step_size[g];
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (r0 + j >= first) { dec[j] = d; ss[j] = z; }
+        }
+      }
+      if (i < n4) {
+        adamw_update4_each(pv[u], gv[u], mv[u], vv[u], a, dec, ss);
+        __builtin_nontemporal_store(pv[u], reinterpret_cast<f32x4*>(p) + i);
+        __builtin_nontemporal_store(mv[u], reinterpret_cast<f32x4*>(m) + i);
+        __builtin_nontemporal_store(vv[u], reinterpret_cast<f32x4*>(v) + i);
+        if (p16) reinterpret_cast<r16x4*>(p16)[i] = cvt4<T>(pv[u][0], pv[u][1], pv[u][2], pv[u][3]);
+      }
+    }
+  }
+}
+
+// The device table of nv_adamw_segments_build: long end[S]; int group[S] (padded to 16 bytes); float dyn_step[NV_ADAMW_MAX_GROUPS].
+// The library remembers every table it has validated (address -> S, G, count): the step refuses any other address, so a table that
+// nobody checked never reaches a launch.
+namespace {
+struct SegTable { int S, G; long count; };
+std::mutex g_seg_mutex;
+std::unordered_map<const void*, SegTable> g_seg_tables;
+inline long seg_groups_offset(int S) { return 8L * S; }
+inline long seg_dyn_offset(int S) { return (8L * S + 4L * S + 15) / 16 * 16; }
+}  // namespace
+
+extern "C" long nv_adamw_segments_bytes(int segments) {
+  if (segments < 1 || segments > NV_ADAMW_MAX_SEGMENTS) return 0;
+  return seg_dyn_offset(segments) + 4L * NV_ADAMW_MAX_GROUPS;
+}
+
+extern "C" int nv_adamw_segments_build(void* table, long table_bytes, const long* ends, const int* groups, int segments, int n_groups, long count, void* stream) {
+  NV_CHECK_ARG(segments >= 1 && segments <= NV_ADAMW_MAX_SEGMENTS, "nv_adamw_segments_build: %d segments, 1 .. %d are supported", segments, NV_ADAMW_MAX_SEGMENTS);
+  NV_CHECK_ARG(n_groups >= 1 && n_groups <= NV_ADAMW_MAX_GROUPS, "nv_adamw_segments_build: %d groups, 1 .. %d are supported", n_groups, NV_ADAMW_MAX_GROUPS);
+  NV_CHECK_ARG(table && ends && groups && nv_aligned16(table), "nv_adamw_segments_build: null table / ends / groups, or a table that is not 16-byte aligned");
+  NV_CHECK_ARG(table_bytes >= nv_adamw_segments_bytes(segments), "nv_adamw_segments_build: the table has %ld bytes, %d segments need %ld", table_bytes, segments,
+               nv_adamw_segments_bytes(segments));
+  NV_CHECK_ARG(count > 0 && (count % 4) == 0, "nv_adamw_segments_build: count=%ld must be a positive multiple of 4", count);
+  long prev = 0;
+  for (int s = 0; s < segments; ++s) {
+    NV_CHECK_ARG(ends[s] > prev, "nv_adamw_segments_build: segment ends must ascend strictly from above 0 - end[%d] = %ld follows %ld", s, ends[s], prev);
+    NV_CHECK_ARG(groups[s] >= 0 && groups[s] < n_groups, "nv_adamw_segments_build: segment %d names group %d of %d", s, groups[s], n_groups);
+    prev = ends[s];
+  }
+  NV_CHECK_ARG(prev == count, "nv_adamw_segments_build: the last segment ends at %ld, the arena has %ld elements", prev, count);
+  {   // (forgotten first: a failed upload must not leave an address registered whose content is unknown)
+    std::lock_guard<std::mutex> lock(g_seg_mutex);
+    g_seg_tables.erase(table);
+  }
+  char* t = (char*)table;
+  hipError_t e = hipMemcpyAsync(t, ends, 8L * segments, hipMemcpyHostToDevice, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(t + seg_groups_offset(segments), groups, 4L * segments, hipMemcpyHostToDevice, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipMemsetAsync(t + seg_dyn_offset(segments), 0, 4L * NV_ADAMW_MAX_GROUPS, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);      // once per model: the host arrays are the caller's again on return
+  if (e != hipSuccess) {
+    nv_set_error("nv_adamw_segments_build: upload failed: %s", hipGetErrorString(e));
+    return NV_ERR_HIP;
+  }
+  std::lock_guard<std::mutex> lock(g_seg_mutex);
+  g_seg_tables[table] = SegTable{segments, n_groups, count};
+  return NV_OK;
+}
+
+extern "C" int nv_adamw_segments_release(void* table) {
+  std::lock_guard<std::mutex> lock(g_seg_mutex);
+  g_seg_tables.erase(table);
+  return NV_OK;
+}
+
+extern "C" int nv_adamw_step_grouped(float* p, const void* grad, int grad_bf16, float* m, float* v, void* p16, long count, int step,
+                                     const nv_adamw_groups* groups, double beta1, double beta2, double eps, float grad_scale, int max_blocks,
+                                     const float* scale_state, const float* clip_state, void* stream) {
+  NV_CHECK_ARG(count > 0 && (count % 4) == 0 && step >= 1, "nv_adamw_step_grouped: count=%ld must be a positive multiple of 4, step=%d >= 1", count, step);
+  NV_CHECK_ARG(p && grad && m && v, "nv_adamw_step_grouped: null p / grad / m / v");
+  NV_CHECK_ARG(nv_aligned16(p) && (grad_bf16 ? ((uintptr_t)grad & 7) == 0 : nv_aligned16(grad)) && nv_aligned16(m) && nv_aligned16(v) &&
+                   (!p16 || ((uintptr_t)p16 & 7) == 0),
+               "nv_adamw_step_grouped: alignment");
+  NV_CHECK_ARG(groups && groups->struct_size == (int)sizeof(nv_adamw_groups), "nv_adamw_step_grouped: nv_adamw_groups.struct_size = %d, this library expects %d (ABI revision %d)",
+               groups ? groups->struct_size : -1, (int)sizeof(nv_adamw_groups), NV_ABI_VERSION);
+  const int G = groups->n_groups;
+  NV_CHECK_ARG(G >= 1 && G <= NV_ADAMW_MAX_GROUPS, "nv_adamw_step_grouped: %d groups, 1 .. %d are supported", G, NV_ADAMW_MAX_GROUPS);
+  SegTable tab;
+  {
+    std::lock_guard<std::mutex> lock(g_seg_mutex);
+    auto it = g_seg_tables.find(groups->segments);
+    NV_CHECK_ARG(groups->segments && it != g_seg_tables.end(), "nv_adamw_step_grouped: the segment table %p was not built by nv_adamw_segments_build", groups->segments);
+    tab = it->second;
+  }
+  NV_CHECK_ARG(tab.G == G && tab.count == count, "nv_adamw_step_grouped: the segment table was built for %d groups over %ld elements, this call has %d over %ld",
+               tab.G, tab.count, G, count);
+  AdamGroupConsts gc;
+  AdamGroupLr glr;
+  for (int g = 0; g < NV_ADAMW_MAX_GROUPS; ++g) {
+    const double lr = g < G ? groups->lr[g] : 0.0, wd = g < G ? groups->weight_decay[g] : 0.0;
+    NV_CHECK_ARG(isfinite(lr) && lr >= 0.0 && isfinite(wd) && wd >= 0.0, "nv_adamw_step_grouped: group %d has lr = %g, weight_decay = %g - both must be finite and >= 0", g, lr, wd);
+    const AdamArgs ag = make_adam_args(step, lr, beta1, beta2, eps, wd, grad_scale);
+    gc.decay[g] = ag.decay; gc.step_size[g] = ag.step_size; glr.lr[g] = lr;
+  }
+  const AdamArgs a = make_adam_args(step, groups->lr[0], beta1, beta2, eps, groups->weight_decay[0], grad_scale);      // (decay / step_size: per group, above)
+  const char* t = (const char*)groups->segments;
+  const long* seg_end = (const long*)t;
+  const int* seg_group = (const int*)(t + seg_groups_offset(tab.S));
+  float* dyn_step = (float*)(const_cast<char*>(t) + seg_dyn_offset(tab.S));
+  if (scale_state) {
+    hipLaunchKernelGGL(adamw_group_steps_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, scale_state, glr, G, beta1, dyn_step);
+    NV_CHECK_LAUNCH("nv_adamw_step_grouped (step sizes)");
+  }
+  const long n4 = count / 4;
+  long blocks = (n4 + 256L * NV_ADAMW_UNROLL - 1) / (256L * NV_ADAMW_UNROLL);
+  if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+  const float* cdyn = dyn_step;
+  const dim3 grid((unsigned)blocks), wg(256);
+#define NV_GROUPED_ARGS p, grad, m, v, (r16*)p16, n4, a, gc, seg_end, seg_group, tab.S, cdyn, scale_state, clip_state
+  NV_DISPATCH_OPERAND(T,
+    if (clip_state && grad_bf16) hipLaunchKernelGGL((adamw_grouped_kernel<true, T, true>), grid, wg, 0, (hipStream_t)stream, NV_GROUPED_ARGS);
+    else if (clip_state) hipLaunchKernelGGL((adamw_grouped_kernel<false, T, true>), grid, wg, 0, (hipStream_t)stream, NV_GROUPED_ARGS);
+    else if (grad_bf16) hipLaunchKernelGGL((adamw_grouped_kernel<true, T, false>), grid, wg, 0, (hipStream_t)stream, NV_GROUPED_ARGS);
+    else hipLaunchKernelGGL((adamw_grouped_kernel<false, T, false>), grid, wg, 0, (hipStream_t)stream, NV_GROUPED_ARGS));
+#undef NV_GROUPED_ARGS
+  NV_CHECK_LAUNCH("nv_adamw_step_grouped");
   return NV_OK;
 }
 

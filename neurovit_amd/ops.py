@@ -511,6 +511,48 @@ def adamw_step(p, grad, m, v, p16, step, lr, betas=(0.9, 0.999), eps=1e-8, weigh
                                         eps, weight_decay, grad_scale, int(max_blocks), _p(scale_state), _p(clip_state), _stream()), "nv_adamw_step_clipped")
 
 
+class AdamwSegments:
+    """The static half of nv_adamw_step_grouped's table, on the device: segment s covers the arena elements [ends[s-1], ends[s]) and
+    belongs to group groups[s].  The library validates the lists (RuntimeError for anything it refuses) and uploads them once, here;
+    `table` is the device buffer, owned by this object and forgotten by the library when it goes."""
+
+    def __init__(self, ends, groups, n_groups: int, count: int, device):
+        ends, groups = [int(e) for e in ends], [int(g) for g in groups]
+        if len(ends) != len(groups):
+            raise ValueError(f"AdamwSegments: {len(ends)} ends, {len(groups)} group indices")
+        self.n_segments, self.n_groups, self.count = len(ends), int(n_groups), int(count)
+        nbytes = lib.nv_adamw_segments_bytes(self.n_segments)
+        self.table = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+        e = (ctypes.c_long * max(self.n_segments, 1))(*ends)
+        g = (ctypes.c_int * max(self.n_segments, 1))(*groups)
+        check(lib.nv_adamw_segments_build(self.table.data_ptr(), self.table.numel(), e, g, self.n_segments, self.n_groups, self.count, _stream()),
+              "nv_adamw_segments_build")
+
+    def __del__(self):
+        try:
+            lib.nv_adamw_segments_release(self.table.data_ptr())
+        except Exception:
+            pass
+
+
+def adamw_step_grouped(p, grad, m, v, p16, step, segments: AdamwSegments, lrs, weight_decays, betas=(0.9, 0.999), eps=1e-8, grad_scale=1.0, max_blocks=0,
+                       scale_state=None, clip_state=None):
+    """adamw_step whose lr and weight_decay come per parameter group (nv_adamw_step_grouped): element i of segment s is updated with
+    lrs[g], weight_decays[g], g = the segment's group - the bits adamw_step gives it when called with that pair.  Every other
+    argument as in adamw_step; `segments` is the AdamwSegments of this arena."""
+    from ._cabi import AdamwGroups
+    _need_cuda(p, grad, m, v, p16, scale_state, clip_state)
+    assert grad.dtype in (torch.float32, op16()) and grad.numel() == p.numel()
+    if len(lrs) != len(weight_decays) or not 1 <= len(lrs) <= len(AdamwGroups().lr):
+        raise ValueError(f"adamw_step_grouped: {len(lrs)} learning rates and {len(weight_decays)} weight decays, 1 .. {len(AdamwGroups().lr)} pairs are supported")
+    tab = AdamwGroups(ctypes.sizeof(AdamwGroups), len(lrs), segments.table.data_ptr())
+    for i, (lr, wd) in enumerate(zip(lrs, weight_decays)):
+        tab.lr[i], tab.weight_decay[i] = float(lr), float(wd)
+    check(lib.nv_adamw_step_grouped(_p(p), _p(grad), int(grad.dtype == op16()), _p(m), _p(v), _p(p16), p.numel(), max(int(step), 1), ctypes.byref(tab),
+                                    betas[0], betas[1], eps, float(grad_scale), int(max_blocks), _p(scale_state), _p(clip_state), _stream()),
+          "nv_adamw_step_grouped")
+
+
 def ema_update(ema: torch.Tensor, p: torch.Tensor, weight: float, max_blocks: int = 0) -> None:
     """ema = ema + (p - ema) * weight in place, each fp32 operation rounded on its own (nv_ema_update): bit-equal to that torch expression
     on the CPU, and p == ema is an exact fixed point.  Both flat fp32, contiguous, the same numel (a multiple of 4) and 16-byte aligned;

@@ -5,12 +5,17 @@
 are views of a ViT arena are updated by ONE nv_adamw_step launch per arena (which also refreshes the
 bf16 shadow the MFMA kernels read); the 4D model's temporal head is a second, 10 k-parameter arena
 (temporal.TemporalHead, fp32 only) stepped the same way; any other parameter is delegated to torch.optim.AdamW.
+Parameter groups are honoured: an arena whose groups carry two or more (lr, weight_decay) pairs is stepped by ONE nv_adamw_step_grouped
+launch; `param_groups` builds the fine-tuning recipe's groups (no weight decay on biases / norms / embeddings, layer-wise learning-rate
+decay) and `LRSchedule` is the warm-up / cosine / linear learning rate of a step.
 `ModelEma` averages the same arenas into a second model with one nv_ema_update launch each.
 """
 from __future__ import annotations
 
 import ctypes
+import fnmatch
 import math
+import re
 from typing import Dict, List
 
 import torch
@@ -208,10 +213,175 @@ class ModelEma:
         self.num_updates = int(state["num_updates"])
 
 
+MAX_ARENA_GROUPS, MAX_ARENA_SEGMENTS = _cabi.ADAMW_MAX_GROUPS, _cabi.ADAMW_MAX_SEGMENTS
+
+
+def arena_segments(offsets, numels, total: int, groups):
+    """The segment table of one flat arena for nv_adamw_step_grouped, as (ends, group indices): entry i of the arena - offsets[i],
+    numels[i], ascending - belongs to groups[i].  What lies between an entry and the next one (alignment padding, the constant slots
+    of a ViT without output projection) joins the entry in front of it, what lies in front of the first entry joins the first;
+    adjacent entries of one group are merged.  The segments cover [0, total) exactly, ends ascending strictly.  Pure Python."""
+    n = len(offsets)
+    if n == 0 or len(numels) != n or len(groups) != n:
+        raise ValueError(f"arena_segments: {n} offsets, {len(numels)} sizes, {len(groups)} group indices - the same number (>= 1) of each is needed")
+    ends, idx, at = [], [], 0
+    for i in range(n):
+        o, k = int(offsets[i]), int(numels[i])
+        if o < at or k < 0:
+            raise ValueError(f"arena_segments: entry {i} at offset {o} overlaps the one before it, which ends at {at}")
+        at = o + k
+        end = int(offsets[i + 1]) if i + 1 < n else int(total)
+        if end < at:
+            raise ValueError(f"arena_segments: entry {i} ends at {at}, beyond {'the next entry' if i + 1 < n else 'the arena'} at {end}")
+        if end == (ends[-1] if ends else 0):
+            continue                                   # (an empty entry with nothing behind it)
+        if idx and idx[-1] == int(groups[i]):
+            ends[-1] = end
+        else:
+            ends.append(end)
+            idx.append(int(groups[i]))
+    if not ends:
+        raise ValueError("arena_segments: the arena is empty")
+    return ends, idx
+
+
+_NO_DECAY_LEAVES = ("pos_embedding", "cls_token")
+
+
+def layer_id_of(name: str, depth: int) -> int:
+    """Layer id of the parameter `name` (as named_parameters gives it, on a NeuroEncoder or a bare ViT) for layer-wise learning-rate
+    decay: pos_embedding, cls_token and to_patch_embedding.* -> 0; transformer.layers.{l}.* -> l + 1; mlp_head.*, the 4D model's
+    temporal transformer and projection head, and whatever else sits behind the encoder -> depth + 1."""
+    if name.startswith(("temporal_transformer.", "projection_head.")):
+        return depth + 1
+    m = re.search(r"(?:^|\.)transformer\.layers\.(\d+)\.", name)
+    if m:
+        return int(m.group(1)) + 1
+    if name.rsplit(".", 1)[-1] in _NO_DECAY_LEAVES or re.search(r"(?:^|\.)to_patch_embedding\.", name):
+        return 0
+    return depth + 1
+
+
+def encoder_depth(model: torch.nn.Module) -> int:
+    """L: the number of transformer layers of the (3D) encoder in `model`, read from its parameter names (frozen ones included)."""
+    depth = 0
+    for name, _ in model.named_parameters():
+        if not name.startswith(("temporal_transformer.", "projection_head.")):
+            m = re.search(r"(?:^|\.)transformer\.layers\.(\d+)\.", name)
+            if m:
+                depth = max(depth, int(m.group(1)) + 1)
+    return depth
+
+
+def in_no_decay_set(name: str, param, extra_no_decay=()) -> bool:
+    """The no-decay rule: ndim <= 1 (biases, LayerNorm weights and biases), pos_embedding, cls_token, and names that contain or
+    fnmatch one of `extra_no_decay`."""
+    if param.ndim <= 1 or name.rsplit(".", 1)[-1] in _NO_DECAY_LEAVES:
+        return True
+    return any(pat in name or fnmatch.fnmatchcase(name, pat) for pat in extra_no_decay)
+
+
+def param_groups(model: torch.nn.Module, weight_decay: float, no_decay: bool = True, layer_decay=None, extra_no_decay=()) -> list:
+    """Torch-style parameter groups of the fine-tuning recipe (DeiT / BEiT / MAE; timm's param_groups_layer_decay), for FusedAdamW or
+    any torch optimizer: [{"params": [...], "weight_decay": w, "lr_scale": s, "names": [...]}].
+      no_decay     the no-decay set (in_no_decay_set) gets weight_decay 0.0, everything else `weight_decay`;
+      layer_decay  None = off; a number in (0, 1]: a parameter of layer id i (layer_id_of) gets lr_scale = layer_decay ** (L + 1 - i),
+                   formed in double, L = encoder_depth(model) - the head keeps the base learning rate, the embeddings get the smallest.
+    Frozen parameters (requires_grad False) are left out; every trainable one is in exactly one group.  The groups carry no "lr": the
+    optimizer's default is the base learning rate, and whoever schedules sets group["lr"] = base * group["lr_scale"] (set_group_lrs;
+    TrainStep does it every step).  With both features off the result is one group."""
+    if isinstance(weight_decay, bool) or not isinstance(weight_decay, (int, float)):
+        raise TypeError(f"param_groups: weight_decay must be a number >= 0, got {weight_decay!r}")
+    if not (math.isfinite(weight_decay) and weight_decay >= 0.0):
+        raise ValueError(f"param_groups: weight_decay must be finite and >= 0, got {weight_decay!r}")
+    if layer_decay is not None:
+        if isinstance(layer_decay, bool) or not isinstance(layer_decay, (int, float)):
+            raise TypeError(f"param_groups: layer_decay must be None or a number in (0, 1], got {layer_decay!r}")
+        if not (0.0 < float(layer_decay) <= 1.0):
+            raise ValueError(f"param_groups: layer_decay must be in (0, 1], got {layer_decay!r}")
+    if isinstance(extra_no_decay, str):
+        extra_no_decay = (extra_no_decay,)
+    depth = encoder_depth(model)
+    found = {}
+    for name, p in model.named_parameters():
+        if not p.requires_grad:
+            continue
+        lid = None if layer_decay is None else layer_id_of(name, depth)
+        skip = bool(no_decay) and in_no_decay_set(name, p, extra_no_decay)
+        g = found.get((lid, skip))
+        if g is None:
+            scale = 1.0 if lid is None else float(layer_decay) ** (depth + 1 - lid)
+            g = found[(lid, skip)] = {"params": [], "weight_decay": 0.0 if skip else float(weight_decay), "lr_scale": scale, "names": []}
+        g["params"].append(p)
+        g["names"].append(name)
+    return [found[k] for k in sorted(found, key=lambda k: (-1 if k[0] is None else k[0], k[1]))]
+
+
+def set_group_lrs(optimizer, base_lr: float) -> None:
+    """group["lr"] = base_lr * group["lr_scale"] (1.0 where a group has none) for every group of `optimizer`, in double."""
+    for g in optimizer.param_groups:
+        g["lr"] = float(base_lr) * float(g.get("lr_scale", 1.0))
+
+
+class LRSchedule:
+    """Learning rate of the k-th optimizer step, k >= 1, as a pure function in double (lr_at): linear warm-up
+        k <= warmup_steps:  base_lr * k / warmup_steps                     (so the first update never runs at lr = 0)
+    then, with q = (k - warmup_steps) / max(1, total_steps - warmup_steps) clamped to [0, 1],
+        "cosine":    min_lr + (base_lr - min_lr) * 0.5 * (1 + cos(pi q))
+        "linear":    base_lr + (min_lr - base_lr) * q
+        "constant":  base_lr
+    and min_lr itself, exactly, from total_steps on (q = 1).  Nothing is stored per step: a resumed run continues from its step count."""
+    KINDS = ("cosine", "linear", "constant")
+
+    def __init__(self, base_lr: float, total_steps: int, warmup_steps: int = 0, kind: str = "cosine", min_lr: float = 0.0):
+        for what, value in (("base_lr", base_lr), ("min_lr", min_lr)):
+            if isinstance(value, bool) or not isinstance(value, (int, float)):
+                raise TypeError(f"LRSchedule: {what} must be a number, got {value!r}")
+        for what, value in (("total_steps", total_steps), ("warmup_steps", warmup_steps)):
+            if isinstance(value, bool) or not isinstance(value, int):
+                raise TypeError(f"LRSchedule: {what} must be an integer, got {value!r}")
+        if not isinstance(kind, str):
+            raise TypeError(f"LRSchedule: kind must be one of {self.KINDS}, got {kind!r}")
+        if kind not in self.KINDS:
+            raise ValueError(f"LRSchedule: kind must be one of {self.KINDS}, got {kind!r}")
+        if not (math.isfinite(base_lr) and base_lr > 0.0):
+            raise ValueError(f"LRSchedule: base_lr must be finite and > 0, got {base_lr!r}")
+        if not (math.isfinite(min_lr) and 0.0 <= min_lr <= base_lr):
+            raise ValueError(f"LRSchedule: min_lr must be in [0, base_lr], got {min_lr!r}")
+        if total_steps < 1:
+            raise ValueError(f"LRSchedule: total_steps must be >= 1, got {total_steps!r}")
+        if not (0 <= warmup_steps <= total_steps):
+            raise ValueError(f"LRSchedule: warmup_steps must be in [0, total_steps], got {warmup_steps!r}")
+        self.base_lr, self.min_lr = float(base_lr), float(min_lr)
+        self.total_steps, self.warmup_steps, self.kind = total_steps, warmup_steps, kind
+
+    def lr_at(self, k: int) -> float:
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise TypeError(f"LRSchedule.lr_at: k must be an integer >= 1, got {k!r}")
+        if k < 1:
+            raise ValueError(f"LRSchedule.lr_at: k counts optimizer steps from 1, got {k!r}")
+        if k <= self.warmup_steps:
+            return self.base_lr * k / self.warmup_steps
+        if self.kind == "constant":
+            return self.base_lr
+        q = min(1.0, max(0.0, (k - self.warmup_steps) / max(1, self.total_steps - self.warmup_steps)))
+        if q >= 1.0:
+            return self.min_lr              # (exactly: base + (min - base) * 1 rounds in double)
+        if self.kind == "cosine":
+            return self.min_lr + (self.base_lr - self.min_lr) * 0.5 * (1.0 + math.cos(math.pi * q))
+        return self.base_lr + (self.min_lr - self.base_lr) * q
+
+
 class FusedAdamW(torch.optim.Optimizer):
+    """Parameter groups are honoured: at bind time every arena entry is mapped to the group that holds its parameter
+    (arena_segments).  An arena whose groups all carry one (lr, weight_decay) on a given step is stepped by ONE nv_adamw_step launch,
+    as without groups; one with two or more pairs by ONE nv_adamw_step_grouped launch.  lr and weight_decay are read from the groups
+    on every step, so any scheduler that writes group["lr"] works.  betas and eps must agree between the groups that touch one arena."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, *, model: torch.nn.Module = None):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         super().__init__(params, defaults)
+        self._arena_groups: Dict[int, dict] = {}     # id(holder) -> its groups and segment table (see _bind)
         self._model = model
         self._arenas: List[FlatArena] = []   # ViT modules and TemporalHead objects
         self._ranged = set()                 # ids of the arenas that step_range has stepped since the last step_rest
@@ -227,18 +397,69 @@ class FusedAdamW(torch.optim.Optimizer):
         return self
 
     def _bind(self):
-        mine = {id(p) for g in self.param_groups for p in g["params"]}
+        group_of = {}
+        for gi, g in enumerate(self.param_groups):
+            for p in g["params"]:
+                if id(p) in group_of:
+                    raise ValueError(f"FusedAdamW: a parameter of shape {tuple(p.shape)} appears in parameter groups {group_of[id(p)]} and {gi}")
+                group_of[id(p)] = gi
         claimed = set()
-        self._arenas = []
+        arenas, arena_groups = [], {}
         for holder in _flat_holders(self._model) if self._model is not None else ():
             plist = holder.arena_parameters()
-            if all(id(p) in mine and p.requires_grad for p in plist):
-                self._arenas.append(holder)
+            if all(id(p) in group_of and p.requires_grad for p in plist):
+                # the groups that touch this arena, in group order, and the arena's segments in terms of them - all on the host
+                used = sorted({group_of[id(p)] for p in plist})
+                if len(used) > MAX_ARENA_GROUPS:
+                    raise ValueError(f"FusedAdamW: {len(used)} parameter groups hold parameters of one {type(holder).__name__} arena, "
+                                     f"the fused launch takes {MAX_ARENA_GROUPS} (lr, weight_decay) pairs")
+                self._check_shared(used, type(holder).__name__)
+                local = {gi: k for k, gi in enumerate(used)}
+                ends, idx = arena_segments(holder._offsets, holder._numels, holder._arena.numel(), [local[group_of[id(p)]] for p in plist])
+                if len(ends) > MAX_ARENA_SEGMENTS:
+                    raise ValueError(f"FusedAdamW: the groups cut one {type(holder).__name__} arena into {len(ends)} segments, the fused launch takes {MAX_ARENA_SEGMENTS}")
+                arenas.append(holder)
+                arena_groups[id(holder)] = {"used": used, "ends": ends, "index": idx, "table": None}
                 claimed.update(id(p) for p in plist)
-        rest = [p for g in self.param_groups for p in g["params"] if id(p) not in claimed and p.requires_grad]
+        self._arenas, self._arena_groups = arenas, arena_groups
+        # the stock optimizer of what lies outside every arena gets the same groups (lr and weight_decay follow them on every step)
+        rest, self._rest_source = [], []
+        for gi, g in enumerate(self.param_groups):
+            ps = [p for p in g["params"] if id(p) not in claimed and p.requires_grad]
+            if ps:
+                rest.append({"params": ps, "lr": g["lr"], "betas": g["betas"], "eps": g["eps"], "weight_decay": g["weight_decay"]})
+                self._rest_source.append(gi)
         g0 = self.param_groups[0]
         self._rest = torch.optim.AdamW(rest, lr=g0["lr"], betas=g0["betas"], eps=g0["eps"], weight_decay=g0["weight_decay"]) if rest else None
         self._bound = True
+
+    def _check_shared(self, used, what: str) -> None:
+        """betas and eps are one per launch: the groups `used` (indices), which touch one arena, must agree on them"""
+        first = self.param_groups[used[0]]
+        for gi in used[1:]:
+            g = self.param_groups[gi]
+            if tuple(g["betas"]) != tuple(first["betas"]) or g["eps"] != first["eps"]:
+                raise ValueError(f"FusedAdamW: parameter groups {used[0]} and {gi} hold parameters of one {what} arena but differ in betas / eps "
+                                 f"({tuple(first['betas'])}, {first['eps']} against {tuple(g['betas'])}, {g['eps']}): one launch has one of each")
+
+    def _arena_pairs(self, holder):
+        """(the groups that touch `holder`'s arena, their (lr, weight_decay) pairs as they are now)"""
+        groups = [self.param_groups[gi] for gi in self._arena_groups[id(holder)]["used"]]
+        return groups, [(float(g["lr"]), float(g["weight_decay"])) for g in groups]
+
+    def is_grouped(self, holder=None) -> bool:
+        """Whether `holder`'s arena (None: any arena) carries two or more distinct (lr, weight_decay) pairs right now - then its
+        update is the one nv_adamw_step_grouped launch behind the backward pass, and nothing else can apply it."""
+        if not self._bound:
+            self._bind()
+        for h in self._arenas if holder is None else [holder]:
+            if id(h) in self._arena_groups and len(set(self._arena_pairs(h)[1])) > 1:
+                return True
+        return False
+
+    def _sync_rest(self):
+        for g, gi in zip(self._rest.param_groups, self._rest_source):
+            g["lr"], g["weight_decay"] = self.param_groups[gi]["lr"], self.param_groups[gi]["weight_decay"]
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0, reduced_bf16=None, scaler: "LossScaler" = None, clip: "GradClipper" = None):
@@ -299,21 +520,23 @@ class FusedAdamW(torch.optim.Optimizer):
                     for p in g["params"]:
                         if p.grad is not None:
                             p.grad.mul_(clip.coef)
-            for g in self._rest.param_groups:
-                g["lr"] = g0["lr"]
+            self._sync_rest()
             self._rest.step()
         return None
 
     def step_range(self, vit: FlatArena, begin: int, end: int, grad_scale: float = 1.0, max_blocks: int = 0):
         """AdamW on arena elements [begin, end) only (DP: run per gradient bucket behind its all-reduce).
         The caller advances the step counter once per optimizer step with `begin_step()`."""
+        if id(vit) in self._arena_groups and self.is_grouped(vit):
+            raise ValueError("FusedAdamW.step_range: this arena carries more than one (lr, weight_decay) pair - its update is one nv_adamw_step_grouped "
+                             "launch over the whole arena, not a launch per gradient bucket (no overlap_optimizer with parameter groups)")
         arena, shadow = vit.flat_parameters()
         grads = vit.flat_gradients()
         key = id(vit)
         if key not in self._state_mv:
             self._state_mv[key] = (torch.zeros_like(arena), torch.zeros_like(arena))
         m, v = self._state_mv[key]
-        g0 = self.param_groups[0]
+        g0 = self.param_groups[self._arena_groups[id(vit)]["used"][0]] if id(vit) in self._arena_groups else self.param_groups[0]
         _cabi.set_operand_format(vit.operands)
         ops.adamw_step(arena[begin:end], grads[begin:end], m[begin:end], v[begin:end], shadow[begin:end], self._steps, g0["lr"],
                        g0["betas"], g0["eps"], g0["weight_decay"], grad_scale, max_blocks)
@@ -344,10 +567,25 @@ class FusedAdamW(torch.optim.Optimizer):
         grads = holder.flat_gradients()
         holder.gather_foreign_grads()
         m, v = self.arena_state(holder)
-        g0 = self.param_groups[0]
+        if not self._bound:
+            self._bind()
+        info = self._arena_groups[id(holder)]
+        groups, pairs = self._arena_pairs(holder)
+        if len(groups) > 1:
+            self._check_shared(info["used"], type(holder).__name__)      # (a group's betas / eps may have been rewritten since _bind)
+        g0 = groups[0]
         _cabi.set_operand_format(holder.operands)      # the format of the shadow this launch rewrites
-        ops.adamw_step(arena, grads if reduced is None else reduced, m, v, shadow, self._steps, g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"], grad_scale,
-                       scale_state=None if scaler is None else scaler.state, clip_state=None if clip is None else clip.state)
+        scale_state, clip_state = None if scaler is None else scaler.state, None if clip is None else clip.state
+        # one pair: the launch without groups.  (Under a dynamic loss scale that launch takes its step size from the scaler's block,
+        # which LossScaler.update forms from group 0's lr: an arena whose one lr is another goes through the grouped launch.)
+        if len(set(pairs)) == 1 and (scaler is None or pairs[0][0] == float(self.param_groups[0]["lr"])):
+            ops.adamw_step(arena, grads if reduced is None else reduced, m, v, shadow, self._steps, g0["lr"], g0["betas"], g0["eps"], g0["weight_decay"], grad_scale,
+                           scale_state=scale_state, clip_state=clip_state)
+        else:
+            if info["table"] is None or info["table"].table.device != arena.device:
+                info["table"] = ops.AdamwSegments(info["ends"], info["index"], len(groups), arena.numel(), arena.device)
+            ops.adamw_step_grouped(arena, grads if reduced is None else reduced, m, v, shadow, self._steps, info["table"], [pr[0] for pr in pairs],
+                                   [pr[1] for pr in pairs], g0["betas"], g0["eps"], grad_scale, scale_state=scale_state, clip_state=clip_state)
         holder.mark_shadow_fresh()
 
     @torch.no_grad()
@@ -359,7 +597,5 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._step_arena(holder, grad_scale)
         self._ranged.clear()
         if self._rest is not None:
-            g0 = self.param_groups[0]
-            for g in self._rest.param_groups:
-                g["lr"] = g0["lr"]
+            self._sync_rest()
             self._rest.step()

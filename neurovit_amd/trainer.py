@@ -19,7 +19,7 @@ import torch.distributed as dist
 
 from .NeuroEncoder import NeuroEncoder
 from .nn import CrossEntropyLoss
-from .optim import FusedAdamW, GradClipper, LossScaler, ModelEma, check_max_norm
+from .optim import FusedAdamW, GradClipper, LRSchedule, LossScaler, ModelEma, check_max_norm, param_groups, set_group_lrs
 from .parallel import GradSync, NativeComm, broadcast_parameters
 
 
@@ -30,7 +30,17 @@ class TrainStep:
                  n_buckets: int = 4, accumulation_steps: int = 1, overlap_optimizer: bool = False,
                  grad_comm_dtype: torch.dtype = torch.float32, grad_comm_algo: Optional[str] = None, fuse_update: Optional[int] = None,
                  loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None, label_smoothing: float = 0.0,
-                 class_weight=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_update_every: int = 1):
+                 class_weight=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_update_every: int = 1,
+                 no_decay: bool = False, layer_decay: Optional[float] = None, lr_schedule: Optional[LRSchedule] = None):
+        # no_decay / layer_decay: the optimizer is built from optim.param_groups(model, weight_decay, no_decay, layer_decay) - no weight
+        # decay on biases, LayerNorm affines, pos_embedding and cls_token; lr_scale = layer_decay ** (L + 1 - layer id).  lr_schedule: an
+        # optim.LRSchedule.  With any of the three set, every optimizer step first writes group["lr"] = base * group["lr_scale"], base =
+        # lr_schedule.lr_at(k) for the k-th ATTEMPTED optimizer step (a step that the dynamic loss scale skips advances the schedule, as
+        # scheduler.step() behind scaler.step() does; accumulation micro-steps do not), or the constant lr without a schedule; last_lr
+        # is that base.  An arena with two or more (lr, weight_decay) pairs needs the one nv_adamw_step_grouped launch, so it takes the
+        # route clipping takes: AdamW once behind the backward pass (fuse_update resolves to 0; the graph replay launches it behind the
+        # replay as it always did), world > 1 on the Python-driven bucket pipeline, no overlap_optimizer.  A schedule alone - or groups
+        # that all carry one pair, layer_decay = 1.0 - changes only the scalar every path already passes and keeps every mode.
         # ema_decay: None = off (no object is built, no call is added); a number in [0, 1) = `ema`, an optim.ModelEma(model, ema_decay,
         # ema_warmup, ema_update_every) whose update() runs once per OPTIMIZER step, behind the update, on the stream the step runs on -
         # on every path (native in every fuse_update mode, graph replay, clipping, native data-parallel plan, general path, side compute
@@ -81,7 +91,25 @@ class TrainStep:
             self.criterion.to(next(model.parameters()).device)
         lr = cfg.get("TRAINING_LEARNING_RATE", 1e-4) if lr is None else lr
         wd = cfg.get("TRAINING_WEIGHT_DECAY", 1e-2) if weight_decay is None else weight_decay
-        self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=wd, model=model)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise TypeError(f"TrainStep: lr_schedule must be an optim.LRSchedule or None, got {type(lr_schedule).__name__}")
+        if not isinstance(no_decay, bool):
+            raise TypeError(f"TrainStep: no_decay must be True or False, got {no_decay!r}")
+        self.lr_schedule = lr_schedule
+        self._base_lr = float(lr)
+        self._recipe = bool(no_decay) or layer_decay is not None
+        self._sets_lr = self._recipe or lr_schedule is not None      # this step writes group["lr"] before every optimizer step
+        self.last_lr = lr_schedule.lr_at(1) if lr_schedule is not None else self._base_lr
+        if self._recipe:
+            self.optimizer = FusedAdamW(param_groups(model, wd, no_decay=no_decay, layer_decay=layer_decay), lr=lr, weight_decay=wd, model=model)
+            set_group_lrs(self.optimizer, self.last_lr)
+        else:
+            self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=wd, model=model)
+        # more than one (lr_scale, weight_decay) pair: the grouped launch's route, decided here for what is set up once (see above)
+        grouped = len({(float(g.get("lr_scale", 1.0)), float(g["weight_decay"])) for g in self.optimizer.param_groups}) > 1
+        if grouped and overlap_optimizer:
+            raise ValueError("TrainStep: overlap_optimizer updates the arena bucket by bucket, parameter groups (no_decay / layer_decay) need the one "
+                             "grouped launch over the whole arena - use one or the other")
         self.accumulation_steps = max(1, int(accumulation_steps))
         self._micro = 0
         vit = model.volume_encoder.vit3d
@@ -119,7 +147,7 @@ class TrainStep:
         self._dp_buckets, self._dp_msg16 = n_buckets, grad_comm_dtype != torch.float32
         want_native_dp = (os.environ.get("NEUROVIT_NATIVE_DP", "1") != "0") if native_dp is None else bool(native_dp)
         dev0 = next(model.parameters()).device
-        if want_native_dp and max_grad_norm is None and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev0.type == "cuda" \
+        if want_native_dp and max_grad_norm is None and not grouped and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev0.type == "cuda" \
                 and (not dist.is_initialized() or dist.get_backend(process_group) == "nccl"):
             try:
                 self._ncomm = NativeComm(dev0, process_group)
@@ -232,11 +260,16 @@ class TrainStep:
             m, v = opt.arena_state(holder)
             arenas.append({"numel": m.numel(), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()})
         g0 = opt.param_groups[0]
-        return {"version": self.STATE_VERSION, "operands": self._vit.operands, "steps": int(opt._steps),
-                "hyper": {k: g0[k] for k in ("lr", "betas", "eps", "weight_decay")}, "arenas": arenas,
-                "rest": None if opt._rest is None else opt._rest.state_dict(),
-                "scaler": None if self.scaler is None else self.scaler.state.detach().clone(), "static_scale": self.static_scale,
-                "ema": None if self.ema is None else self.ema.state_dict()}
+        state = {"version": self.STATE_VERSION, "operands": self._vit.operands, "steps": int(opt._steps),
+                 "hyper": {k: g0[k] for k in ("lr", "betas", "eps", "weight_decay")}, "arenas": arenas,
+                 "rest": None if opt._rest is None else opt._rest.state_dict(),
+                 "scaler": None if self.scaler is None else self.scaler.state.detach().clone(), "static_scale": self.static_scale,
+                 "ema": None if self.ema is None else self.ema.state_dict()}
+        if self._recipe or len(opt.param_groups) > 1:
+            # lr, lr_scale and weight_decay per parameter group ("hyper" is group 0's; a step with the one default group saves what it
+            # always saved).  The schedule is no state: it is a function of "steps".
+            state["groups"] = [{"lr": g["lr"], "lr_scale": g.get("lr_scale"), "weight_decay": g["weight_decay"]} for g in opt.param_groups]
+        return state
 
     def load_state_dict(self, state: dict) -> None:
         """Restore what state_dict returned into the EXISTING buffers, in place: addresses do not change, so .grad views and captured
@@ -255,6 +288,8 @@ class TrainStep:
             n = holder.flat_parameters()[0].numel()
             if saved["numel"] != n or saved["exp_avg"].numel() != n or saved["exp_avg_sq"].numel() != n:
                 raise ValueError(f"TrainStep.load_state_dict: arena {i} has {n} elements, the state's has {saved['numel']}")
+        if state.get("groups") is not None and len(state["groups"]) != len(opt.param_groups):
+            raise ValueError(f"TrainStep.load_state_dict: the state holds {len(state['groups'])} parameter groups, this optimizer has {len(opt.param_groups)}")
         if (state["scaler"] is None) != (self.scaler is None):
             raise ValueError("TrainStep.load_state_dict: a dynamic loss scale must be on both sides or on neither - the state has "
                              f"{'one' if state['scaler'] is not None else 'none'}, this step has {'one' if self.scaler is not None else 'none'}")
@@ -282,6 +317,12 @@ class TrainStep:
         for k, value in state["hyper"].items():
             for g in opt.param_groups:
                 g[k] = value
+        for g, saved in zip(opt.param_groups, state.get("groups") or ()):      # (a state from before parameter groups has no such key)
+            g["lr"], g["weight_decay"] = saved["lr"], saved["weight_decay"]
+            if saved.get("lr_scale") is not None:
+                g["lr_scale"] = saved["lr_scale"]
+        if not self._sets_lr:
+            self.last_lr = float(opt.param_groups[0]["lr"])
         self.static_scale = float(state["static_scale"])
         if self.ema is not None:
             self.ema.load_state_dict(state["ema"])
@@ -409,8 +450,13 @@ class TrainStep:
         fuse = self.fuse_update
         if fuse is None:
             fuse = 3 if fmri.shape[0] * vit.pos_embedding.shape[1] <= self.FUSE_MAX_ROWS else 0
-        if self.accumulation_steps != 1 or vit._phantom or self.scaler is not None or self.clipper is not None:
+        grouped = opt.is_grouped(vit)       # two or more (lr, weight_decay) pairs in the arena: the one grouped launch behind the backward pass
+        if self.accumulation_steps != 1 or vit._phantom or self.scaler is not None or self.clipper is not None or grouped:
             fuse = 0                        # (a dynamic loss scale decides after the backward pass whether the update is applied; the clipping coefficient exists only then)
+        if grouped and self._ncomm is not None:
+            raise ValueError("TrainStep: the native data-parallel plan applies one (lr, weight_decay) to the whole arena - parameter groups that "
+                             "differ need the Python-driven bucket pipeline (build the step with the groups, or native_dp=False)")
+        behind = self.clipper is not None or grouped      # FusedAdamW.step follows the call, which then runs no optimizer work
         dp = None
         if self._ncomm is not None:
             fuse = 0                        # the update follows the all-reduce: per bucket on the communication stream, or once at the end
@@ -420,18 +466,18 @@ class TrainStep:
         accumulate = self._micro > 0        # the first micro-step of a window overwrites (zero_grad(set_to_none=True), Trainer.py:72), the others add
         loss, logits = vit._rt.train_step(video, labels.contiguous(), arena, shadow, grads, m, v, step=opt._steps + 1, lr=g0["lr"], betas=g0["betas"],
                                           eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate,
-                                          update=last_micro and self.clipper is None,
+                                          update=last_micro and not behind,
                                           fuse_update=fuse, dropout=vit.draw_dropout(), loss_scale=self.static_scale,
                                           loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo)
-        if last_micro and self.clipper is None:
+        if last_micro and not behind:
             opt._steps += 1                 # (after the call: a refused step leaves the counter where it was)
         vit._last_logits = logits
         self.last_outputs = logits
         vit.ensure_grad_views()                                          # .grad = views of the gradient arena (once; they stay valid)
         vit.linear_weight_grads(present=fuse != 1)                       # (fuse 1 never wrote the layers' Linear weight gradients)
         self._micro += 1
-        if last_micro and self.clipper is not None:
-            # clipping: the call above ran no optimizer work (update = 0: with a loss-scale state only the scaling of the loss gradient);
+        if last_micro and behind:
+            # clipping, parameter groups: the call above ran no optimizer work (update = 0: with a loss-scale state only the scaling of the loss gradient);
             # norm, coefficient, the scaler's decision and the one AdamW launch are queued behind it (FusedAdamW.step counts the step and
             # marks the shadow fresh itself)
             opt.step(grad_scale=1.0 / self.static_scale if self.static_scale > 0 else 1.0, scaler=self.scaler, clip=self.clipper)
@@ -468,6 +514,12 @@ class TrainStep:
         return self._dp_keep
 
     def _step(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
+        opt = self.optimizer
+        if self._sets_lr:                   # (every micro-step of a window sees the same count: the value of the step that ends it)
+            self.last_lr = self._base_lr if self.lr_schedule is None else self.lr_schedule.lr_at(opt._steps + 1)
+            set_group_lrs(opt, self.last_lr)
+        else:
+            self.last_lr = float(opt.param_groups[0]["lr"])
         if self._native_ok(fmri, labels):
             return self._native_step(fmri, labels) if mix is None else self._native_step(fmri, labels, mix)
         model, vit = self.model, self._vit
@@ -607,7 +659,8 @@ class Trainer:
         self.save_state, self.resume_from = self.state_options_from_config(config)
         self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
                               max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights,
-                              **self.ema_from_config(config))
+                              **self.ema_from_config(config),
+                              **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
         self.validate_ema = bool(config.get('VALIDATION_EMA', True))
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
@@ -642,6 +695,40 @@ class Trainer:
         if not isinstance(warmup, bool):
             raise TypeError(f"TRAINING_EMA_WARMUP must be true or false, got {warmup!r}")
         return dict(ema_decay=float(decay), ema_warmup=warmup, ema_update_every=every)
+
+    @staticmethod
+    def schedule_from_config(config, epochs: int, batches_per_epoch: int) -> dict:
+        """TrainStep's no_decay / layer_decay / lr_schedule arguments from the optional keys (the reference's config files have none of
+        them; with none set the result is empty and nothing changes):
+          TRAINING_LR_SCHEDULE          "cosine" | "linear" | "constant" (absent or None: no schedule)
+          TRAINING_WARMUP_STEPS         optimizer steps of linear warm-up (default 0), TRAINING_MIN_LR (default 0.0) - only with a schedule
+          TRAINING_LAYER_DECAY          a number in (0, 1] (absent or None: off)
+          TRAINING_NO_DECAY_NORM_BIAS   true = no weight decay on biases, LayerNorm affines, pos_embedding and cls_token (default false)
+        The schedule runs over total_steps = epochs * ceil(batches_per_epoch / accumulation) optimizer steps at base
+        TRAINING_LEARNING_RATE.  Wrong types raise TypeError, wrong values ValueError (optim.LRSchedule, optim.param_groups)."""
+        out = {}
+        kind, warmup, min_lr = config.get('TRAINING_LR_SCHEDULE', None), config.get('TRAINING_WARMUP_STEPS', None), config.get('TRAINING_MIN_LR', None)
+        if kind is None:
+            if warmup is not None or min_lr is not None:
+                raise ValueError("TRAINING_WARMUP_STEPS / TRAINING_MIN_LR need TRAINING_LR_SCHEDULE ('cosine', 'linear' or 'constant')")
+        else:
+            accumulation = config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1
+            total = int(epochs) * -(-int(batches_per_epoch) // max(1, int(accumulation)))
+            out["lr_schedule"] = LRSchedule(config.get('TRAINING_LEARNING_RATE', 1e-4), total, 0 if warmup is None else warmup, kind, 0.0 if min_lr is None else min_lr)
+        decay = config.get('TRAINING_LAYER_DECAY', None)
+        if decay is not None:
+            if isinstance(decay, bool) or not isinstance(decay, (int, float)):
+                raise TypeError(f"TRAINING_LAYER_DECAY must be a number in (0, 1], got {decay!r}")
+            if not (0.0 < float(decay) <= 1.0):
+                raise ValueError(f"TRAINING_LAYER_DECAY must be in (0, 1], got {decay!r}")
+            out["layer_decay"] = float(decay)
+        no_decay = config.get('TRAINING_NO_DECAY_NORM_BIAS', None)
+        if no_decay is not None:
+            if not isinstance(no_decay, bool):
+                raise TypeError(f"TRAINING_NO_DECAY_NORM_BIAS must be true or false, got {no_decay!r}")
+            if no_decay:
+                out["no_decay"] = True
+        return out
 
     @staticmethod
     def state_options_from_config(config):
@@ -787,7 +874,7 @@ class Trainer:
             if i != 0 and i % self.log_interval == 0:
                 avg_loss = round(float(running_loss) / self.log_interval, 5)
                 accuracy = round(float(correct) / total, 5)
-                lr = round(self.optimizer.param_groups[0]['lr'], 5)
+                lr = round(self.step.last_lr, 5)
                 duration = time.time() - start_time
                 print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| train_loss: {avg_loss:.5f}\t| train_accuracy: {accuracy:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
                 payload = {"epoch": epoch, "batch": i, "train_loss": avg_loss, "train_accuracy": accuracy, "learning_rate": lr, "duration": duration}
