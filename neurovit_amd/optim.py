@@ -397,6 +397,8 @@ class FusedAdamW(torch.optim.Optimizer):
         return self
 
     def _bind(self):
+        if self._bound:
+            return
         group_of = {}
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
@@ -450,8 +452,7 @@ class FusedAdamW(torch.optim.Optimizer):
     def is_grouped(self, holder=None) -> bool:
         """Whether `holder`'s arena (None: any arena) carries two or more distinct (lr, weight_decay) pairs right now - then its
         update is the one nv_adamw_step_grouped launch behind the backward pass, and nothing else can apply it."""
-        if not self._bound:
-            self._bind()
+        self._bind()
         for h in self._arenas if holder is None else [holder]:
             if id(h) in self._arena_groups and len(set(self._arena_pairs(h)[1])) > 1:
                 return True
@@ -460,6 +461,13 @@ class FusedAdamW(torch.optim.Optimizer):
     def _sync_rest(self):
         for g, gi in zip(self._rest.param_groups, self._rest_source):
             g["lr"], g["weight_decay"] = self.param_groups[gi]["lr"], self.param_groups[gi]["weight_decay"]
+
+    def _rest_grads(self):
+        """.grad of every parameter of the stock optimizer that has one"""
+        for g in self._rest.param_groups if self._rest is not None else ():
+            for p in g["params"]:
+                if p.grad is not None:
+                    yield p.grad
 
     @torch.no_grad()
     def step(self, closure=None, grad_scale: float = 1.0, reduced_bf16=None, scaler: "LossScaler" = None, clip: "GradClipper" = None):
@@ -472,54 +480,44 @@ class FusedAdamW(torch.optim.Optimizer):
         well), the scaler decides, the coefficient is formed from the norm of the un-scaled gradients (sqrt(sum) * |grad_scale| / loss
         scale - every summed buffer is taken to carry the same factors) and each update multiplies its gradients by it.  The
         gradient buffers themselves keep the raw values, except stock parameters' .grad, which is multiplied in place."""
-        if not self._bound:
-            self._bind()
+        self._bind()
         self._steps += 1
         g0 = self.param_groups[0]
         live = [h for h in self._arenas if not h.no_gradients()]
-        if clip is not None:
+        reduced = reduced_bf16 or {}
+        if clip is not None or scaler is not None:
+            # the scan before the update, every gradient buffer once: summed for the clip (with a scaler that pass raises its flag too), else checked for the scaler
             for holder in live:
                 holder.gather_foreign_grads()
-                red = None if reduced_bf16 is None else reduced_bf16.get(id(holder))
+                buf = reduced.get(id(holder))
+                if clip is None:
+                    scaler.check(holder.flat_gradients() if buf is None else buf.float())
+                    continue
                 _cabi.set_operand_format(holder.operands)      # what a 16-bit reduced buffer holds
-                summed = holder.flat_gradients() if red is None else red
+                buf = holder.flat_gradients() if buf is None else buf
                 for o, const in holder._phantom:      # arena slots that are no parameter (the nn.Identity to_out of a heads == 1 ViT):
-                    summed[o:o + const.numel()].zero_()                # what the backward pass left there is no gradient of the model
-                clip.add(summed, scaler)
-            if self._rest is not None:
-                for g in self._rest.param_groups:
-                    for p in g["params"]:
-                        if p.grad is not None:
-                            clip.add(p.grad.float(), scaler)
+                    buf[o:o + const.numel()].zero_()                   # what the backward pass left there is no gradient of the model
+                clip.add(buf, scaler)
+            for grad in self._rest_grads():
+                if clip is None:
+                    scaler.check(grad.contiguous().float())
+                else:
+                    clip.add(grad.float(), scaler)
             if scaler is not None:
                 scaler.update(g0["lr"], g0["betas"])
-            clip.finish(grad_scale, scaler)
-        elif scaler is not None:
-            for holder in live:
-                holder.gather_foreign_grads()
-                red = None if reduced_bf16 is None else reduced_bf16.get(id(holder))
-                scaler.check(holder.flat_gradients() if red is None else red.float())
-            if self._rest is not None:
-                for g in self._rest.param_groups:
-                    for p in g["params"]:
-                        if p.grad is not None:
-                            scaler.check(p.grad.contiguous().float())
-            scaler.update(g0["lr"], g0["betas"])
+            if clip is not None:
+                clip.finish(grad_scale, scaler)
         for holder in live:
-            self._step_arena(holder, grad_scale, None if reduced_bf16 is None else reduced_bf16.get(id(holder)), scaler, clip)
+            self.step_arena(holder, grad_scale, reduced.get(id(holder)), scaler, clip)
         if self._rest is not None:
             if scaler is not None:
                 if scaler.last_step_skipped():          # (stock parameters beside a scaled arena: the one place that reads the flag back)
                     return None
-                for g in self._rest.param_groups:
-                    for p in g["params"]:
-                        if p.grad is not None:
-                            p.grad.mul_(scaler.state[1])
+                for grad in self._rest_grads():
+                    grad.mul_(scaler.state[1])
             if clip is not None:
-                for g in self._rest.param_groups:
-                    for p in g["params"]:
-                        if p.grad is not None:
-                            p.grad.mul_(clip.coef)
+                for grad in self._rest_grads():
+                    grad.mul_(clip.coef)
             self._sync_rest()
             self._rest.step()
         return None
@@ -532,10 +530,7 @@ class FusedAdamW(torch.optim.Optimizer):
                              "launch over the whole arena, not a launch per gradient bucket (no overlap_optimizer with parameter groups)")
         arena, shadow = vit.flat_parameters()
         grads = vit.flat_gradients()
-        key = id(vit)
-        if key not in self._state_mv:
-            self._state_mv[key] = (torch.zeros_like(arena), torch.zeros_like(arena))
-        m, v = self._state_mv[key]
+        m, v = self.arena_state(vit)
         g0 = self.param_groups[self._arena_groups[id(vit)]["used"][0]] if id(vit) in self._arena_groups else self.param_groups[0]
         _cabi.set_operand_format(vit.operands)
         ops.adamw_step(arena[begin:end], grads[begin:end], m[begin:end], v[begin:end], shadow[begin:end], self._steps, g0["lr"],
@@ -544,14 +539,18 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ranged.add(id(vit))
 
     def begin_step(self):
-        if not self._bound:
-            self._bind()
+        """Count one optimizer step whose launches the caller issues: step_range per bucket, step_arena, the native train step's own."""
+        self._bind()
         self._steps += 1
+
+    @property
+    def steps(self) -> int:
+        """optimizer steps counted so far (step and begin_step count; AdamW's t of the next one is steps + 1)"""
+        return self._steps
 
     def arenas(self):
         """The flat arenas (ViT modules, TemporalHead objects) this optimizer steps with one fused launch each."""
-        if not self._bound:
-            self._bind()
+        self._bind()
         return list(self._arenas)
 
     def arena_state(self, holder):
@@ -562,13 +561,59 @@ class FusedAdamW(torch.optim.Optimizer):
             self._state_mv[key] = (torch.zeros_like(arena), torch.zeros_like(arena))
         return self._state_mv[key]
 
-    def _step_arena(self, holder, grad_scale, reduced=None, scaler=None, clip=None):
+    # ------------------------------------------------------------------ the optimizer's part of a resumable state (TrainStep.state_dict)
+    def fused_state(self) -> dict:
+        """steps, group 0's hyper, clones of the moment arenas, the stock optimizer's state (rest) and, where there are any, the groups"""
+        arenas = []
+        for holder in self.arenas():
+            m, v = self.arena_state(holder)
+            arenas.append({"numel": m.numel(), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()})
+        g0 = self.param_groups[0]
+        state = {"steps": int(self._steps), "hyper": {k: g0[k] for k in ("lr", "betas", "eps", "weight_decay")}, "arenas": arenas,
+                 "rest": None if self._rest is None else self._rest.state_dict()}
+        if len(self.param_groups) > 1 or "lr_scale" in g0:      # (one default group saves what it always saved; a schedule is a function of "steps")
+            state["groups"] = [{"lr": g["lr"], "lr_scale": g.get("lr_scale"), "weight_decay": g["weight_decay"]} for g in self.param_groups]
+        return state
+
+    def check_fused_state(self, state: dict) -> None:
+        """ValueError naming the mismatch (arena count and sizes, group count, a stock optimizer on one side) unless the state fits"""
+        holders = self.arenas()
+        if len(state["arenas"]) != len(holders):
+            raise ValueError(f"FusedAdamW: the state holds {len(state['arenas'])} moment arenas, this optimizer steps {len(holders)}")
+        for i, (saved, holder) in enumerate(zip(state["arenas"], holders)):
+            n = holder.flat_parameters()[0].numel()
+            if saved["numel"] != n or saved["exp_avg"].numel() != n or saved["exp_avg_sq"].numel() != n:
+                raise ValueError(f"FusedAdamW: arena {i} has {n} elements, the state's has {saved['numel']}")
+        if state.get("groups") is not None and len(state["groups"]) != len(self.param_groups):
+            raise ValueError(f"FusedAdamW: the state holds {len(state['groups'])} parameter groups, this optimizer has {len(self.param_groups)}")
+        if (state["rest"] is None) != (self._rest is None):
+            raise ValueError("FusedAdamW: parameters outside the arenas (a stock optimizer) must be on both sides or on neither")
+
+    @torch.no_grad()
+    def load_fused_state(self, state: dict) -> None:
+        """Restore what fused_state returned into the existing buffers, in place (call check_fused_state first)."""
+        for saved, holder in zip(state["arenas"], self.arenas()):
+            m, v = self.arena_state(holder)
+            m.copy_(saved["exp_avg"])
+            v.copy_(saved["exp_avg_sq"])
+        if self._rest is not None:
+            self._rest.load_state_dict(state["rest"])
+        self._steps = int(state["steps"])
+        for k, value in state["hyper"].items():
+            for g in self.param_groups:
+                g[k] = value
+        for g, saved in zip(self.param_groups, state.get("groups") or ()):      # (a state from before parameter groups has no such key)
+            g["lr"], g["weight_decay"] = saved["lr"], saved["weight_decay"]
+            if saved.get("lr_scale") is not None:
+                g["lr_scale"] = saved["lr_scale"]
+
+    def step_arena(self, holder, grad_scale, reduced=None, scaler=None, clip=None):
+        """The one fused launch over `holder`'s arena (+ its 16-bit shadow) at the current step count, which the caller has advanced."""
         arena, shadow = holder.flat_parameters()
         grads = holder.flat_gradients()
         holder.gather_foreign_grads()
         m, v = self.arena_state(holder)
-        if not self._bound:
-            self._bind()
+        self._bind()
         info = self._arena_groups[id(holder)]
         groups, pairs = self._arena_pairs(holder)
         if len(groups) > 1:
@@ -594,7 +639,7 @@ class FusedAdamW(torch.optim.Optimizer):
         `grad_scale`, stock parameters as they are."""
         for holder in self._arenas:
             if id(holder) not in self._ranged and not holder.no_gradients():
-                self._step_arena(holder, grad_scale)
+                self.step_arena(holder, grad_scale)
         self._ranged.clear()
         if self._rest is not None:
             self._sync_rest()

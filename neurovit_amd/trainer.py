@@ -12,6 +12,7 @@ No host synchronisation happens inside a step; `loss` is returned as a device te
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -23,8 +24,47 @@ from .optim import FusedAdamW, GradClipper, LRSchedule, LossScaler, ModelEma, ch
 from .parallel import GradSync, NativeComm, broadcast_parameters
 
 
+@dataclass(frozen=True)
+class UpdatePlan:
+    """Where the optimizer update of one step runs: what TrainStep._plan decides, once, for every path ("Where the update runs")."""
+    whole_gradient: bool      # a scaler, a clipper or a grouped arena: every gradient must exist before the first update
+    fuse: int                 # the native step's fuse_update as resolved: 0 behind the backward pass, 1 / 2 / 3 during it
+    behind: bool              # FusedAdamW.step follows the native call, which runs no optimizer work (update = False)
+    graph_ok: bool            # the step may be replayed from a captured graph
+    dp_per_bucket: int        # native data-parallel plan: 0 = AdamW once when every bucket is in, 1 / 2 = per bucket behind its all-reduce
+    dp_msg16: bool            # native data-parallel plan: 16-bit messages
+
+
 class TrainStep:
-    FUSE_MAX_ROWS = 4096      # fuse_update=None: token rows (batch x tokens) up to which the layers' weights are updated during the backward pass
+    """TrainStep(model)(fmri, labels) is the module docstring's sequence.  Where AdamW runs under any combination of the options is
+    decided in one place, _plan (the table in DESIGN.md, "Where the update runs").
+    lr, weight_decay: None = the config's TRAINING_LEARNING_RATE (1e-4) / TRAINING_WEIGHT_DECAY (1e-2).
+    no_decay, layer_decay: the groups of optim.param_groups (no decay on biases, norms, pos_embedding, cls_token; lr_scale = layer_decay
+      ** (L + 1 - layer id)).  lr_schedule: an optim.LRSchedule.  With any of the three, every optimizer step first writes group["lr"] =
+      last_lr * lr_scale, last_lr = lr_schedule.lr_at(k) for the k-th ATTEMPTED optimizer step (one the dynamic scale skips counts,
+      accumulation micro-steps do not), else the constant lr.  Two or more (lr, weight_decay) pairs in the arena: one grouped launch.
+    process_group, n_buckets, grad_comm_dtype, grad_comm_algo: data parallel - gradient buckets are all-reduced on a side stream while
+      the backward pass continues; 16-bit messages travel in the model's operand format.  native_dp: the step stays ONE native call that
+      issues the collectives itself; None = on at world > 1 unless NEUROVIT_NATIVE_DP=0 (falls back, loudly, without a communicator).
+    overlap_optimizer: AdamW per bucket on the side stream (slower, off).  Not with clipping, groups or a dynamic loss scale.
+    accumulation_steps: the all-reduce and the update run on the micro-step that ends a window; the others add their gradients.
+    fuse_update: native step only, same bits in every mode - AdamW of the layers' Linear weights (96 % of the parameters) runs 0 with
+      the rest of the arena behind the backward pass, 3 per layer on the auxiliary stream behind that layer's weight-gradient GEMMs, 1
+      inside those GEMMs' epilogues (.grad of those weights is then None), 2 the same with the gradients still stored; None
+      (NEUROVIT_FUSE_UPDATE unset) = 3 up to FUSE_MAX_ROWS token rows per step, 0 above.
+    loss_scale: None = "dynamic" for fp16 operands (GradScaler semantics on the device, optim.LossScaler), none for bf16; "dynamic"; or
+      a number = a static scale (no overflow check, no skipped steps; a power of two changes no bit of a finite result).
+    max_grad_norm: clip_grad_norm_ on the device (optim.GradClipper) - the norm of the UN-SCALED, world-averaged gradients of the whole
+      window, applied INSIDE the update: .grad keeps the raw gradients.  last_grad_norm / last_clip_coef are device tensors.
+    label_smoothing, class_weight: nn.CrossEntropyLoss(weight=, label_smoothing=) on every path; __call__'s `mix` (VolumeMix.last_mix)
+      trains against the Mixup / CutMix target.  Data parallel, each rank normalises its loss by its own denominator.
+    ema_decay: a number in [0, 1) = `ema`, an optim.ModelEma(model, ema_decay, ema_warmup, ema_update_every) updated once per OPTIMIZER
+      step - a skipped one included - behind the update, on the step's stream, on every path; no collective."""
+    # fuse_update=None: token rows (batch x tokens) up to which the layers' weights are updated during the backward pass.  ViT3D-base,
+    # volumes/s mode 0 -> 3: batch 2 641 -> 655 (+2.3 %), 4: 1113 -> 1165 (+4.8 %), 5: 1055 -> 1132, 6: 1152 -> 1191, 7: 1268 -> 1322,
+    # 8: 1390 -> 1382, 16: 1780 -> 1749, 32: 1940 -> 1923; ViT3D-large 53.8 -> 53.3 - small batches leave wave slots and memory bandwidth
+    # idle beside the chain, large ones do not.  Mode 1 at batch 2 / 4: +8 % / +2.5 % (profiles/r04_adamw_in_wgrad_epilogue.log)
+    FUSE_MAX_ROWS = 4096
 
     def __init__(self, model: NeuroEncoder, lr: Optional[float] = None, weight_decay: Optional[float] = None, process_group=None,
                  n_buckets: int = 4, accumulation_steps: int = 1, overlap_optimizer: bool = False,
@@ -32,63 +72,40 @@ class TrainStep:
                  loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None, label_smoothing: float = 0.0,
                  class_weight=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_update_every: int = 1,
                  no_decay: bool = False, layer_decay: Optional[float] = None, lr_schedule: Optional[LRSchedule] = None):
-        # no_decay / layer_decay: the optimizer is built from optim.param_groups(model, weight_decay, no_decay, layer_decay) - no weight
-        # decay on biases, LayerNorm affines, pos_embedding and cls_token; lr_scale = layer_decay ** (L + 1 - layer id).  lr_schedule: an
-        # optim.LRSchedule.  With any of the three set, every optimizer step first writes group["lr"] = base * group["lr_scale"], base =
-        # lr_schedule.lr_at(k) for the k-th ATTEMPTED optimizer step (a step that the dynamic loss scale skips advances the schedule, as
-        # scheduler.step() behind scaler.step() does; accumulation micro-steps do not), or the constant lr without a schedule; last_lr
-        # is that base.  An arena with two or more (lr, weight_decay) pairs needs the one nv_adamw_step_grouped launch, so it takes the
-        # route clipping takes: AdamW once behind the backward pass (fuse_update resolves to 0; the graph replay launches it behind the
-        # replay as it always did), world > 1 on the Python-driven bucket pipeline, no overlap_optimizer.  A schedule alone - or groups
-        # that all carry one pair, layer_decay = 1.0 - changes only the scalar every path already passes and keeps every mode.
-        # ema_decay: None = off (no object is built, no call is added); a number in [0, 1) = `ema`, an optim.ModelEma(model, ema_decay,
-        # ema_warmup, ema_update_every) whose update() runs once per OPTIMIZER step, behind the update, on the stream the step runs on -
-        # on every path (native in every fuse_update mode, graph replay, clipping, native data-parallel plan, general path, side compute
-        # stream), with accumulation only on the micro-step that ends a window.  That stream has joined the auxiliary and the
-        # communication stream by then, so the launch reads finished parameters.  A step that a dynamic loss scale
-        # SKIPS is still averaged and still counts: the parameters did not move, the average moves towards them once more - what
-        # `scaler.step(opt); scaler.update(); ema.update(model)` does in the stock recipe.  Data parallel, every rank averages its own
-        # (identical) parameters: no collective.  The average changes no bit of parameters, moments, gradients or scaler state.
-        # label_smoothing / class_weight: nn.CrossEntropyLoss(weight=, label_smoothing=) on every path; __call__'s `mix` (VolumeMix.last_mix)
-        # trains against the Mixup / CutMix target.  With all three off every path makes the calls it makes without them.  Data parallel,
-        # each rank normalises its loss by its own denominator and the gradients are averaged over ranks (what torch DDP does).
-        # max_grad_norm: None = off; a finite number > 0 = torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) between the
-        # backward pass and the update, on the device (optim.GradClipper): with a loss scale the norm is that of the UN-SCALED gradients
-        # (scaler.unscale_ before the clip), data parallel that of the world-averaged ones, with accumulation that of the window's sum.
-        # The clip is applied INSIDE the update, as the static loss scale's 1 / scale is: .grad and the gradient arena keep the raw,
-        # unclipped (and still scaled) gradients.  last_grad_norm (the pre-clip norm, what clip_grad_norm_ returns) and last_clip_coef
-        # are device tensors - reading them is the caller's synchronisation, the step has none.  The coefficient needs the whole norm
-        # before the first update: AdamW runs once behind the backward pass (fuse_update resolves to 0, no captured-graph replay, no
-        # overlap_optimizer), and world > 1 takes the Python-driven bucket pipeline instead of the native data-parallel plan.
         if ema_decay is not None:
             ModelEma.check_args(ema_decay, ema_update_every)
-        if max_grad_norm is not None:
-            max_grad_norm = check_max_norm(max_grad_norm)
-            assert not overlap_optimizer, "max_grad_norm: the clipping coefficient needs the norm of ALL gradients before any update - no per-bucket optimizer updates"
-        cfg = model.config
-        # native_dp: world > 1 - the step stays ONE native call (nv_vit_train_step with an nv_dp_plan: RCCL all-reduce per bucket issued
-        # from native code on a communicator of the library's own, AdamW behind it) instead of the Python-driven staged backward;
-        # None = on unless NEUROVIT_NATIVE_DP=0 (falls back, loudly, when the communicator cannot be built: gloo groups, CPU tensors)
-        # loss_scale: None = by operand format - "dynamic" for fp16 operands (torch.amp.GradScaler semantics, on the device:
-        # optim.LossScaler), none for bf16; "dynamic"; or a number = a static scale (no overflow check, no skipped steps - keeps
-        # the optimizer update inside the backward pass, fuse_update).  A power of two changes no bit of a finite result.
-        # native step only - where AdamW runs for the layers' Linear weights (96 % of the parameters); same bits in every mode:
-        #   0  with the rest of the arena, one launch behind the backward pass
-        #   3  per layer on the auxiliary stream, behind that layer's weight-gradient GEMMs, beside the main stream's chain
-        #   1  inside those GEMMs' epilogues (nv_gemm_bf16_grouped_adamw; .grad of those weights is then None - torch's
-        #      optimizer-in-backward trade), 2 = the same with the gradients still stored
-        # None (default; NEUROVIT_FUSE_UPDATE unset) = by batch: 3 up to FUSE_MAX_ROWS token rows per step, 0 above.  ViT3D-base, same
-        # box, volumes/s mode 0 -> 3: batch 2 641 -> 655 (+2.3 %), 4: 1113 -> 1165 (+4.8 %), 5: 1055 -> 1132, 6: 1152 -> 1191, 7: 1268 -> 1322, 8: 1390 -> 1382, 16: 1780 -> 1749,
-        # 32: 1940 -> 1923; ViT3D-large 53.8 -> 53.3 - small batches leave wave slots and memory bandwidth idle beside the chain, large
-        # ones do not.  Mode 1 at batch 2 / 4: +8 % / +2.5 % (profiles/r04_adamw_in_wgrad_epilogue.log)
+        self.max_grad_norm = None if max_grad_norm is None else check_max_norm(max_grad_norm)
         env = os.environ.get("NEUROVIT_FUSE_UPDATE")
         self.fuse_update = (int(env) if env is not None else None) if fuse_update is None else int(fuse_update)
         assert self.fuse_update in (None, 0, 1, 2, 3), "fuse_update: None (by batch), 0, 1, 2 or 3"
         self.last_fuse_update = 0          # what the most recent native step did
+        self.last_path = None              # "native" | "native-dp" | "general": which path the most recent step took
+        self.last_outputs = None
         self.model = model
+        vit = self._vit = model.volume_encoder.vit3d
+        self._device = next(model.parameters()).device
+        self._arena_trainable = all(p.requires_grad for p in vit.parameters())
         self.criterion = CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)
         if self.criterion.weight is not None:
-            self.criterion.to(next(model.parameters()).device)
+            self.criterion.to(self._device)
+        self.accumulation_steps = max(1, int(accumulation_steps))
+        self._micro = 0
+        self._overlap_opt = bool(overlap_optimizer)
+        if loss_scale is None:
+            loss_scale = "dynamic" if (vit.operands == "fp16" and self._arena_trainable) else 0.0
+        grouped = self._setup_optimizer(lr, weight_decay, no_decay, layer_decay, lr_schedule)
+        self._refuse_conflicts(grouped, dynamic=loss_scale == "dynamic")
+        self._setup_parallel(process_group, n_buckets, grad_comm_dtype, grad_comm_algo, native_dp, loss_scale == "dynamic",
+                             behind=self.max_grad_norm is not None or grouped)
+        self.scaler, self.static_scale = (LossScaler(self._device), 0.0) if loss_scale == "dynamic" else (None, float(loss_scale))
+        assert self.static_scale >= 0.0, "loss_scale: None, 'dynamic' or a non-negative number"
+        self.clipper = None if self.max_grad_norm is None else GradClipper(self._device, self.max_grad_norm)
+        # (last: the average starts from the parameters as they are now - after the data-parallel broadcast)
+        self.ema = None if ema_decay is None else ModelEma(model, decay=ema_decay, warmup=ema_warmup, update_every=ema_update_every)
+
+    def _setup_optimizer(self, lr, weight_decay, no_decay, layer_decay, lr_schedule) -> bool:
+        """optimizer, schedule and last_lr; returns whether the groups carry more than one (lr_scale, weight_decay) pair"""
+        model, cfg = self.model, self.model.config
         lr = cfg.get("TRAINING_LEARNING_RATE", 1e-4) if lr is None else lr
         wd = cfg.get("TRAINING_WEIGHT_DECAY", 1e-2) if weight_decay is None else weight_decay
         if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
@@ -105,34 +122,42 @@ class TrainStep:
             set_group_lrs(self.optimizer, self.last_lr)
         else:
             self.optimizer = FusedAdamW(model.parameters(), lr=lr, weight_decay=wd, model=model)
-        # more than one (lr_scale, weight_decay) pair: the grouped launch's route, decided here for what is set up once (see above)
-        grouped = len({(float(g.get("lr_scale", 1.0)), float(g["weight_decay"])) for g in self.optimizer.param_groups}) > 1
-        if grouped and overlap_optimizer:
+        return len({(float(g.get("lr_scale", 1.0)), float(g["weight_decay"])) for g in self.optimizer.param_groups}) > 1
+
+    def _refuse_conflicts(self, grouped: bool, dynamic: bool = False, native_dp: bool = False) -> None:
+        """The options that exclude each other, each pair named once.  The constructor asks with the options as given; _plan asks on
+        every step for the one pair that can come about later (a scheduler rewrites the groups under a native data-parallel plan)."""
+        if self._overlap_opt and self.max_grad_norm is not None:
+            raise AssertionError("max_grad_norm: the clipping coefficient needs the norm of ALL gradients before any update - no per-bucket optimizer updates")
+        if self._overlap_opt and grouped:
             raise ValueError("TrainStep: overlap_optimizer updates the arena bucket by bucket, parameter groups (no_decay / layer_decay) need the one "
                              "grouped launch over the whole arena - use one or the other")
-        self.accumulation_steps = max(1, int(accumulation_steps))
-        self._micro = 0
-        vit = model.volume_encoder.vit3d
-        self._vit = vit
-        self._arena_trainable = all(p.requires_grad for p in vit.parameters())
+        if self._overlap_opt and dynamic:
+            raise AssertionError("a dynamic loss scale decides after the backward pass whether the step is applied: no per-bucket optimizer updates")
+        if grouped and native_dp:
+            raise ValueError("TrainStep: the native data-parallel plan applies one (lr, weight_decay) to the whole arena - parameter groups that "
+                             "differ need the Python-driven bucket pipeline (build the step with the groups, or native_dp=False)")
+
+    def _setup_parallel(self, process_group, n_buckets, grad_comm_dtype, grad_comm_algo, native_dp, dynamic: bool, behind: bool) -> None:
+        """The bucket pipeline (sync) or the native data-parallel plan (_ncomm), the broadcast of the parameters, and the streams.
+        behind: AdamW follows the whole backward pass from Python (clipping, groups) - no place for it in the native plan."""
+        model, vit, dev0, overlap = self.model, self._vit, self._device, self._overlap_opt
         world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.world = world
-        # Bucket pipeline: as soon as a group of backward stages has produced its (contiguous) gradient range, a side
-        # stream all-reduces it (world > 1) while the main stream continues the backward pass.  overlap_optimizer=True
-        # additionally runs the fused AdamW of that range on the side stream; measured on one MI355X this LOSES 5 %
-        # (740 vs 777 volumes/s: the HBM-bound optimizer slows the concurrent GEMMs more than it hides), so it is off.
         self.sync = None
-        self.last_outputs = None
-        self._overlap_opt = bool(overlap_optimizer)
         self._opt_blocks = int(os.environ.get("NEUROVIT_OPT_BLOCKS", "0"))
         if grad_comm_dtype != torch.float32:           # 16-bit messages travel in the model's operand format (what the GEMM epilogues write)
             grad_comm_dtype = vit._dtype16()
-        if self._arena_trainable and (world > 1 or overlap_optimizer):
-            self.sync = GradSync(process_group, n_buckets, after_bucket=self._bucket_update if overlap_optimizer else None,
+        # Bucket pipeline: as soon as a group of backward stages has produced its (contiguous) gradient range, a side stream all-reduces
+        # it (world > 1) while the main stream continues the backward pass.  overlap_optimizer additionally runs the fused AdamW of that
+        # range on the side stream; measured on one MI355X this LOSES 5 % (740 vs 777 volumes/s: the HBM-bound optimizer slows the
+        # concurrent GEMMs more than it hides), so it is off.
+        if self._arena_trainable and (world > 1 or overlap):
+            self.sync = GradSync(process_group, n_buckets, after_bucket=self._bucket_update if overlap else None,
                                  comm_dtype=grad_comm_dtype, algo=grad_comm_algo)
-            # bf16 messages: the fused AdamW reads the reduced bf16 gradients directly; param.grad then keeps the LOCAL
-            # (pre-reduction) gradients, which nothing downstream of this fused step reads
-            self.sync.write_back = bool(overlap_optimizer) or grad_comm_dtype == torch.float32
+            # 16-bit messages: the fused AdamW reads the reduced gradients directly and param.grad keeps the LOCAL (pre-reduction)
+            # gradients, which nothing downstream of this fused step reads; a dynamic scale's overflow check reads the fp32 arena
+            self.sync.write_back = overlap or grad_comm_dtype == torch.float32 or dynamic
         if world > 1:
             arena, _ = vit.flat_parameters()
             broadcast_parameters(arena, process_group)
@@ -145,9 +170,9 @@ class TrainStep:
         self._ncomm = None                             # NativeComm of the native data-parallel step
         self._dp_world = world                         # (tests force the collective path on one rank by raising it)
         self._dp_buckets, self._dp_msg16 = n_buckets, grad_comm_dtype != torch.float32
+        self._dp_msgbuf = self.last_dp = self._dp_keep = None
         want_native_dp = (os.environ.get("NEUROVIT_NATIVE_DP", "1") != "0") if native_dp is None else bool(native_dp)
-        dev0 = next(model.parameters()).device
-        if want_native_dp and max_grad_norm is None and not grouped and (world > 1 or native_dp) and self._arena_trainable and not overlap_optimizer and dev0.type == "cuda" \
+        if want_native_dp and not behind and (world > 1 or native_dp) and self._arena_trainable and not overlap and dev0.type == "cuda" \
                 and (not dist.is_initialized() or dist.get_backend(process_group) == "nccl"):
             try:
                 self._ncomm = NativeComm(dev0, process_group)
@@ -168,29 +193,44 @@ class TrainStep:
         ids = {id(q) for q in vit.parameters()}
         self._outside = [p for p in model.parameters() if id(p) not in ids]
         self._inside = [p for p in model.parameters() if id(p) in ids]
+        self._head = getattr(model, "_temporal_head", None)            # 4D: its 16 parameters are one arena (temporal.TemporalHead)
+        self._head_ids = set() if self._head is None else {id(p) for p in self._head.arena_parameters()}
+        self._all_modules = list(model.modules())
         self._native = None                                            # decided at the first step (see _native_ok)
         self._graphs_on = os.environ.get("NEUROVIT_GRAPH_STEP", "0") == "1"   # replay the native step from captured graphs (see _graph_step)
         self._graphs, self._graph_seen, self._graph_warm = {}, {}, 0
-        if loss_scale is None:
-            loss_scale = "dynamic" if (vit.operands == "fp16" and self._arena_trainable) else 0.0
-        self.scaler = None
-        self.static_scale = 0.0
-        if loss_scale == "dynamic":
-            assert not overlap_optimizer, "a dynamic loss scale decides after the backward pass whether the step is applied: no per-bucket optimizer updates"
-            self.scaler = LossScaler(dev0)
-            if self.sync is not None:
-                self.sync.write_back = True            # the overflow check reads the reduced gradients from the fp32 arena
-        else:
-            self.static_scale = float(loss_scale)
-            assert self.static_scale >= 0.0, "loss_scale: None, 'dynamic' or a non-negative number"
-        self.max_grad_norm = max_grad_norm
-        self.clipper = None if max_grad_norm is None else GradClipper(dev0, max_grad_norm)
-        self.last_path = None                          # "native" | "general": which path the most recent step took (last_fuse_update: where AdamW ran)
-        self._all_modules = list(model.modules())
-        self._head = getattr(model, "_temporal_head", None)            # 4D: its 16 parameters are one arena (temporal.TemporalHead)
-        self._head_ids = set() if self._head is None else {id(p) for p in self._head.arena_parameters()}
-        # (last: the average starts from the parameters as they are now - after the data-parallel broadcast above)
-        self.ema = None if ema_decay is None else ModelEma(model, decay=ema_decay, warmup=ema_warmup, update_every=ema_update_every)
+
+    def _plan(self, rows: int, dropout_live: bool, loss_opts_on: bool) -> UpdatePlan:
+        """Where the update of a step over `rows` token rows (batch x tokens) runs.  Reads the step's options and the groups as they are
+        now (a scheduler may have rewritten them) - no device work, nothing allocated but the record."""
+        scaler, clipper, native_dp = self.scaler is not None, self.clipper is not None, self._ncomm is not None
+        grouped = self.optimizer.is_grouped(self._vit)
+        self._refuse_conflicts(grouped, native_dp=native_dp)
+        single, small = self.accumulation_steps == 1, rows <= self.FUSE_MAX_ROWS
+        whole = scaler or clipper or grouped
+        fuse = (3 if small else 0) if self.fuse_update is None else self.fuse_update
+        if not single or self._vit._phantom or whole or native_dp:
+            fuse = 0      # the update in the weight-gradient GEMMs: only a step that overwrites its gradients, updates, and needs no other gradient first
+        per_bucket = int(single and small and not scaler)
+        if per_bucket and os.environ.get("NEUROVIT_DP_UPDATE_PER_BUCKET") is not None:      # A/B aid: 0 = once at the end, 1 = comm stream, 2 = auxiliary stream one bucket late
+            per_bucket = int(os.environ["NEUROVIT_DP_UPDATE_PER_BUCKET"])
+        # graph_ok: the masks' seeds are kernel arguments, the captured graph holds the plain loss and no collective; a grouped arena
+        # stays eligible (the replay ends in step_arena anyway).  behind: a scaler alone is not - its update stays inside the call.
+        return UpdatePlan(whole_gradient=whole, fuse=fuse, behind=clipper or grouped,
+                          graph_ok=self._graphs_on and single and not (dropout_live or scaler or clipper or loss_opts_on or native_dp),
+                          dp_per_bucket=per_bucket, dp_msg16=self._dp_msg16 and not scaler)
+
+    def _unscaled(self, scale: float = 1.0) -> float:
+        """`scale` with the static loss scale divided out: the grad_scale of an update"""
+        return scale / self.static_scale if self.static_scale > 0 else scale
+
+    @property
+    def _ends_window(self) -> bool:
+        """whether the micro-step about to run ends its accumulation window (the one that all-reduces and updates)"""
+        return (self._micro + 1) % self.accumulation_steps == 0
+
+    def _count_micro(self, ended_window: bool) -> None:
+        self._micro = 0 if ended_window else self._micro + 1
 
     @property
     def last_grad_norm(self) -> Optional[torch.Tensor]:
@@ -204,10 +244,7 @@ class TrainStep:
         return None if self.clipper is None else self.clipper.coef
 
     def _bucket_update(self, begin: int, end: int):
-        gs = 1.0 / self.world
-        if self.static_scale > 0:
-            gs /= self.static_scale
-        self.optimizer.step_range(self._vit, begin, end, grad_scale=gs, max_blocks=self._opt_blocks)
+        self.optimizer.step_range(self._vit, begin, end, grad_scale=self._unscaled(1.0 / self.world), max_blocks=self._opt_blocks)
 
     def __call__(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
         if mix is not None:
@@ -254,73 +291,34 @@ class TrainStep:
         if self._micro != 0:
             raise RuntimeError(f"TrainStep.state_dict: inside an accumulation window ({self._micro} of {self.accumulation_steps} micro-steps taken) - "
                                "save after the micro-step that ends it")
-        opt = self.optimizer
-        arenas = []
-        for holder in opt.arenas():
-            m, v = opt.arena_state(holder)
-            arenas.append({"numel": m.numel(), "exp_avg": m.detach().clone(), "exp_avg_sq": v.detach().clone()})
-        g0 = opt.param_groups[0]
-        state = {"version": self.STATE_VERSION, "operands": self._vit.operands, "steps": int(opt._steps),
-                 "hyper": {k: g0[k] for k in ("lr", "betas", "eps", "weight_decay")}, "arenas": arenas,
-                 "rest": None if opt._rest is None else opt._rest.state_dict(),
-                 "scaler": None if self.scaler is None else self.scaler.state.detach().clone(), "static_scale": self.static_scale,
-                 "ema": None if self.ema is None else self.ema.state_dict()}
-        if self._recipe or len(opt.param_groups) > 1:
-            # lr, lr_scale and weight_decay per parameter group ("hyper" is group 0's; a step with the one default group saves what it
-            # always saved).  The schedule is no state: it is a function of "steps".
-            state["groups"] = [{"lr": g["lr"], "lr_scale": g.get("lr_scale"), "weight_decay": g["weight_decay"]} for g in opt.param_groups]
-        return state
+        return {"version": self.STATE_VERSION, "operands": self._vit.operands, **self.optimizer.fused_state(),
+                "scaler": None if self.scaler is None else self.scaler.state.detach().clone(), "static_scale": self.static_scale,
+                "ema": None if self.ema is None else self.ema.state_dict()}
 
     def load_state_dict(self, state: dict) -> None:
         """Restore what state_dict returned into the EXISTING buffers, in place: addresses do not change, so .grad views and captured
         graphs stay valid.  Everything is checked before the first copy (ValueError naming the mismatch; nothing has changed then):
-        version, operand format, arena count and sizes, a scaler on both sides or on neither, an average on both sides or on neither.
-        Load the model's parameters (model.load_state_dict) separately - they are not part of this state."""
+        version, operand format, the optimizer's part (FusedAdamW.check_fused_state), a scaler on both sides or on neither, an average
+        on both sides or on neither.  Load the model's parameters (model.load_state_dict) separately - they are not part of this state."""
         opt = self.optimizer
         if not isinstance(state, dict) or state.get("version") != self.STATE_VERSION:
             raise ValueError(f"TrainStep.load_state_dict: state version {state.get('version') if isinstance(state, dict) else None!r}, this class reads version {self.STATE_VERSION}")
         if state["operands"] != self._vit.operands:
             raise ValueError(f"TrainStep.load_state_dict: the state was saved on {state['operands']} operands, this model runs on {self._vit.operands}")
-        holders = opt.arenas()
-        if len(state["arenas"]) != len(holders):
-            raise ValueError(f"TrainStep.load_state_dict: the state holds {len(state['arenas'])} moment arenas, this optimizer steps {len(holders)}")
-        for i, (saved, holder) in enumerate(zip(state["arenas"], holders)):
-            n = holder.flat_parameters()[0].numel()
-            if saved["numel"] != n or saved["exp_avg"].numel() != n or saved["exp_avg_sq"].numel() != n:
-                raise ValueError(f"TrainStep.load_state_dict: arena {i} has {n} elements, the state's has {saved['numel']}")
-        if state.get("groups") is not None and len(state["groups"]) != len(opt.param_groups):
-            raise ValueError(f"TrainStep.load_state_dict: the state holds {len(state['groups'])} parameter groups, this optimizer has {len(opt.param_groups)}")
-        if (state["scaler"] is None) != (self.scaler is None):
-            raise ValueError("TrainStep.load_state_dict: a dynamic loss scale must be on both sides or on neither - the state has "
-                             f"{'one' if state['scaler'] is not None else 'none'}, this step has {'one' if self.scaler is not None else 'none'}")
+        opt.check_fused_state(state)
+        for what, saved, mine in (("a dynamic loss scale", state["scaler"], self.scaler), ("a weight average (ema_decay)", state["ema"], self.ema)):
+            if (saved is None) != (mine is None):
+                raise ValueError(f"TrainStep.load_state_dict: {what} must be on both sides or on neither - the state has "
+                                 f"{'one' if saved is not None else 'none'}, this step has {'one' if mine is not None else 'none'}")
         if state["scaler"] is not None and state["scaler"].numel() != self.scaler.state.numel():
             raise ValueError(f"TrainStep.load_state_dict: the loss-scale block has {state['scaler'].numel()} floats, expected {self.scaler.state.numel()}")
-        if (state["ema"] is None) != (self.ema is None):
-            raise ValueError("TrainStep.load_state_dict: a weight average (ema_decay) must be on both sides or on neither - the state has "
-                             f"{'one' if state['ema'] is not None else 'none'}, this step has {'one' if self.ema is not None else 'none'}")
-        if (state["rest"] is None) != (opt._rest is None):
-            raise ValueError("TrainStep.load_state_dict: parameters outside the arenas (a stock optimizer) must be on both sides or on neither")
         if self.ema is not None:
             mine, saved = self.ema.module.state_dict(), state["ema"]["module"]
             if set(mine) != set(saved) or any(mine[k].shape != saved[k].shape for k in mine):
                 raise ValueError("TrainStep.load_state_dict: the averaged model of the state has other keys or shapes than this one")
-        with torch.no_grad():
-            for saved, holder in zip(state["arenas"], holders):
-                m, v = opt.arena_state(holder)
-                m.copy_(saved["exp_avg"])
-                v.copy_(saved["exp_avg_sq"])
-            if opt._rest is not None:
-                opt._rest.load_state_dict(state["rest"])
-            if self.scaler is not None:
-                self.scaler.state.copy_(state["scaler"])      # (AdamW's t under a dynamic scale is the block's own count of applied updates)
-        opt._steps = int(state["steps"])
-        for k, value in state["hyper"].items():
-            for g in opt.param_groups:
-                g[k] = value
-        for g, saved in zip(opt.param_groups, state.get("groups") or ()):      # (a state from before parameter groups has no such key)
-            g["lr"], g["weight_decay"] = saved["lr"], saved["weight_decay"]
-            if saved.get("lr_scale") is not None:
-                g["lr_scale"] = saved["lr_scale"]
+        opt.load_fused_state(state)
+        if self.scaler is not None:
+            self.scaler.state.copy_(state["scaler"])          # (AdamW's t under a dynamic scale is the block's own count of applied updates)
         if not self._sets_lr:
             self.last_lr = float(opt.param_groups[0]["lr"])
         self.static_scale = float(state["static_scale"])
@@ -360,6 +358,27 @@ class TrainStep:
                 return False
         return True
 
+    def _native_call(self, fmri, labels, step: int, accumulate=False, update=False, fuse=0, dp=None, lo=None):
+        """vit._rt.train_step on the model's arenas and the optimizer's moments with group 0's hyper-parameters: the one place that
+        forms its arguments, for the eager step and for the capture of _graph_step.  Returns (loss [1], logits)."""
+        vit, opt = self._vit, self.optimizer
+        video = fmri.permute(0, 3, 1, 2).unsqueeze(1)                    # NeuroEncoder.py:200-202 as a VIEW (the gather kernel reads the strides)
+        vit.check_video(video, arena_checked=True)                       # (_native_ok has just validated / rebuilt the arena)
+        m, v = opt.arena_state(vit)
+        g0 = opt.param_groups[0]
+        return vit._rt.train_step(video, labels, vit._arena, vit._shadow, vit.gradient_arena(), m, v, step=step, lr=g0["lr"], betas=g0["betas"],
+                                  eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate, update=update,
+                                  fuse_update=fuse, dropout=vit.draw_dropout(), loss_scale=self.static_scale,
+                                  loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo)
+
+    def _after_native(self, logits, fuse: int = 0) -> None:
+        """what follows the native call or its replay: the outputs, and .grad as views of the gradient arena (once; they stay valid)"""
+        vit = self._vit
+        vit._last_logits = logits
+        self.last_outputs = logits
+        vit.ensure_grad_views()
+        vit.linear_weight_grads(present=fuse != 1)                       # (fuse 1 never wrote the layers' Linear weight gradients)
+
     # ------------------------------------------------------------------ ... replayed from a captured graph
     def _graph_step(self, fmri: torch.Tensor, labels: torch.Tensor):
         """The native step's forward + loss + backward as a captured HIP graph, replayed with ONE host call (the ~225 launches of a step
@@ -367,12 +386,10 @@ class TrainStep:
         step, is launched behind it.  One graph per (input address, label address, shape): a loader that hands its batches over in a
         few recycled device buffers (DevicePrefetcher: two) hits the cache after the first pass over them; an address seen for the
         first time runs the step eagerly and is captured the NEXT time it shows up, so tensors that never repeat never pay a capture.
-        Only with dropout off (the masks' seeds are kernel arguments) and without accumulation.  Returns None when this step is not
-        for the graph.  The returned loss / logits tensors are the graph's own outputs: the next replay of the same graph overwrites
-        them (clone what must outlive the next step - as with any captured graph)."""
+        For steps whose plan says graph_ok only.  Returns None when this step is not for the graph.  The returned loss / logits tensors
+        are the graph's own outputs: the next replay of the same graph overwrites them (clone what must outlive the next step - as with
+        any captured graph)."""
         vit, opt = self._vit, self.optimizer
-        if not self._graphs_on or self.accumulation_steps != 1 or vit._dropout_p != (0.0, 0.0) or self.scaler is not None or self.clipper is not None:
-            return None
         grads = vit.gradient_arena()
         m_, v_ = opt.arena_state(vit)
         # everything a captured launch holds by address: a rebuilt gradient arena, re-created optimizer state or another form of the
@@ -388,17 +405,11 @@ class TrainStep:
                 if len(self._graph_seen) > 64:
                     self._graphs_on = False                              # addresses never repeat: stop looking
                 return None
-            video = fmri.permute(0, 3, 1, 2).unsqueeze(1)
-            vit.check_video(video, arena_checked=True)
-            m, v = opt.arena_state(vit)
-            g0 = opt.param_groups[0]
             torch.cuda.synchronize(fmri.device)
             graph = torch.cuda.CUDAGraph()
             try:
                 with torch.cuda.graph(graph):
-                    loss, logits = vit._rt.train_step(video, labels, vit._arena, vit._shadow, grads, m, v, step=1, lr=g0["lr"], betas=g0["betas"],
-                                                      eps=g0["eps"], weight_decay=g0["weight_decay"], accumulate=False, update=False,
-                                                      loss_scale=self.static_scale)
+                    loss, logits = self._native_call(fmri, labels, step=1)
             except Exception as e:                                       # capture refused (an unsupported call inside it): eager from now on
                 self._graphs_on = False
                 import warnings
@@ -410,11 +421,9 @@ class TrainStep:
         vit._refresh_shadow()
         graph.replay()
         vit._rt.note_step_replayed(fmri.shape[0], fmri.permute(0, 3, 1, 2).unsqueeze(1))
-        opt._steps += 1
-        opt._step_arena(vit, 1.0 / self.static_scale if self.static_scale > 0 else 1.0)      # AdamW over the arena + 16-bit shadow (mark_shadow_fresh inside)
-        vit._last_logits = logits
-        self.last_outputs = logits
-        vit.ensure_grad_views()
+        opt.begin_step()
+        opt.step_arena(vit, self._unscaled())                            # AdamW over the arena + 16-bit shadow (mark_shadow_fresh inside)
+        self._after_native(logits)
         return loss.reshape(())
 
     def _loss_opts(self, labels, mix):
@@ -428,69 +437,41 @@ class TrainStep:
         return ops.loss_opts(crit.label_smoothing, crit.weight, mix, labels.shape[0], self._vit._cfg.num_classes, labels.device)
 
     def _native_step(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
-        if self._vit._attend_backward_hooked_layers():
+        vit, opt = self._vit, self.optimizer
+        if vit._attend_backward_hooked_layers():
             # (_native_ok routes a hooked model to the general path, whose backward fires the hooks; the one-call step has no place to)
             raise NotImplementedError("neurovit_amd.TrainStep: the native one-call step exports no attention gradients - backward hooks on "
                                       "`attend` need the general path (forward + backward through autograd)")
         lo = self._loss_opts(labels, mix)
-        got = self._graph_step(fmri, labels) if lo is None else None     # (the captured graphs hold the plain loss: a step with an option on is eager)
+        plan = self._plan(fmri.shape[0] * vit.pos_embedding.shape[1], vit._dropout_p != (0.0, 0.0), lo is not None)
+        got = self._graph_step(fmri, labels) if plan.graph_ok else None
         if got is not None:
             return got
-        vit, opt = self._vit, self.optimizer
-        last_micro = (self._micro + 1) % self.accumulation_steps == 0
-        video = fmri.permute(0, 3, 1, 2).unsqueeze(1)                    # NeuroEncoder.py:200-202 as a VIEW (the gather kernel reads the strides)
-        vit.check_video(video, arena_checked=True)                       # (_native_ok has just validated / rebuilt the arena)
-        arena, shadow, grads = vit._arena, vit._shadow, vit.gradient_arena()
+        last_micro = self._ends_window
+        update = last_micro and not plan.behind                         # AdamW inside the call (plan.fuse: where)
         vit._refresh_shadow()
-        if not opt._bound:
-            opt._bind()
-        m, v = opt.arena_state(vit)
-        g0 = opt.param_groups[0]
-        # the update inside the weight-gradient GEMMs: only a step that overwrites its gradients AND updates (no accumulation window)
-        fuse = self.fuse_update
-        if fuse is None:
-            fuse = 3 if fmri.shape[0] * vit.pos_embedding.shape[1] <= self.FUSE_MAX_ROWS else 0
-        grouped = opt.is_grouped(vit)       # two or more (lr, weight_decay) pairs in the arena: the one grouped launch behind the backward pass
-        if self.accumulation_steps != 1 or vit._phantom or self.scaler is not None or self.clipper is not None or grouped:
-            fuse = 0                        # (a dynamic loss scale decides after the backward pass whether the update is applied; the clipping coefficient exists only then)
-        if grouped and self._ncomm is not None:
-            raise ValueError("TrainStep: the native data-parallel plan applies one (lr, weight_decay) to the whole arena - parameter groups that "
-                             "differ need the Python-driven bucket pipeline (build the step with the groups, or native_dp=False)")
-        behind = self.clipper is not None or grouped      # FusedAdamW.step follows the call, which then runs no optimizer work
-        dp = None
-        if self._ncomm is not None:
-            fuse = 0                        # the update follows the all-reduce: per bucket on the communication stream, or once at the end
-            dp = self._dp_plan(fmri, grads)
-        self.last_fuse_update = fuse
+        dp = None if self._ncomm is None else self._dp_plan(fmri, plan)
+        self.last_fuse_update = plan.fuse
         self.last_path = "native" if dp is None else "native-dp"
-        accumulate = self._micro > 0        # the first micro-step of a window overwrites (zero_grad(set_to_none=True), Trainer.py:72), the others add
-        loss, logits = vit._rt.train_step(video, labels.contiguous(), arena, shadow, grads, m, v, step=opt._steps + 1, lr=g0["lr"], betas=g0["betas"],
-                                          eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate,
-                                          update=last_micro and not behind,
-                                          fuse_update=fuse, dropout=vit.draw_dropout(), loss_scale=self.static_scale,
-                                          loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo)
-        if last_micro and not behind:
-            opt._steps += 1                 # (after the call: a refused step leaves the counter where it was)
-        vit._last_logits = logits
-        self.last_outputs = logits
-        vit.ensure_grad_views()                                          # .grad = views of the gradient arena (once; they stay valid)
-        vit.linear_weight_grads(present=fuse != 1)                       # (fuse 1 never wrote the layers' Linear weight gradients)
-        self._micro += 1
-        if last_micro and behind:
-            # clipping, parameter groups: the call above ran no optimizer work (update = 0: with a loss-scale state only the scaling of the loss gradient);
-            # norm, coefficient, the scaler's decision and the one AdamW launch are queued behind it (FusedAdamW.step counts the step and
-            # marks the shadow fresh itself)
-            opt.step(grad_scale=1.0 / self.static_scale if self.static_scale > 0 else 1.0, scaler=self.scaler, clip=self.clipper)
-            self._micro = 0
+        # the first micro-step of a window overwrites the gradients (zero_grad(set_to_none=True), Trainer.py:72), the others add
+        loss, logits = self._native_call(fmri, labels.contiguous(), step=opt.steps + 1, accumulate=self._micro > 0, update=update,
+                                         fuse=plan.fuse, dp=dp, lo=lo)
+        if update:
+            opt.begin_step()                # (after the call: a refused step leaves the counter where it was)
+        self._after_native(logits, plan.fuse)
+        if last_micro and plan.behind:
+            # clipping, parameter groups: the call ran no optimizer work (with a loss-scale state only the scaling of the loss gradient);
+            # norm, coefficient, the scaler's decision and the one AdamW launch are queued behind it (FusedAdamW.step counts the step
+            # and marks the shadow fresh itself)
+            opt.step(grad_scale=self._unscaled(), scaler=self.scaler, clip=self.clipper)
         elif last_micro:
             vit.mark_shadow_fresh()
-            self._micro = 0
+        self._count_micro(last_micro)
         return loss.reshape(())
 
-    def _dp_plan(self, fmri, grads):
-        """nv_dp_plan of this step: communicator, a communication stream with a hardware queue of its own, bucket count, message format,
-        and where AdamW runs - per bucket behind its all-reduce while the chip has room beside the backward pass (the same batch rule
-        as fuse_update), else once when every bucket is in; a dynamic loss scale needs the single update (and fp32 messages)."""
+    def _dp_plan(self, fmri, plan: UpdatePlan):
+        """nv_dp_plan of this step: communicator, a communication stream with a hardware queue of its own, bucket count, and from
+        `plan` the message format and where AdamW runs - per bucket behind its all-reduce, or once when every bucket is in."""
         import ctypes
         from ._cabi import DpPlan
         nc, vit = self._ncomm, self._vit
@@ -500,48 +481,44 @@ class TrainStep:
             aux = vit._rt._aux_stream(fmri.device) and vit._rt.aux_stream_object(fmri.device)
             nc.stream = independent_stream(fmri.device, [cur, aux])
         msg = None
-        if self._dp_msg16 and self.scaler is None:
-            if getattr(self, "_dp_msgbuf", None) is None or self._dp_msgbuf.numel() != grads.numel() or self._dp_msgbuf.dtype != vit._dtype16():
+        if plan.dp_msg16:
+            grads = vit.gradient_arena()
+            if self._dp_msgbuf is None or self._dp_msgbuf.numel() != grads.numel() or self._dp_msgbuf.dtype != vit._dtype16():
                 self._dp_msgbuf = torch.empty(grads.numel(), dtype=vit._dtype16(), device=grads.device)
             msg = self._dp_msgbuf
-        per_bucket = self.scaler is None and self.accumulation_steps == 1 and fmri.shape[0] * vit.pos_embedding.shape[1] <= self.FUSE_MAX_ROWS
-        per_bucket = int(per_bucket)
-        if os.environ.get("NEUROVIT_DP_UPDATE_PER_BUCKET") is not None and per_bucket:      # A/B aid: 0 = once at the end, 1 = comm stream, 2 = auxiliary stream one bucket late
-            per_bucket = int(os.environ["NEUROVIT_DP_UPDATE_PER_BUCKET"])
-        self.last_dp = dict(buckets=self._dp_buckets, messages="16-bit" if msg is not None else "fp32", update_per_bucket=per_bucket, world=self._dp_world)
-        self._dp_keep = DpPlan(ctypes.sizeof(DpPlan), int(self._dp_world), nc.handle, nc.stream.cuda_stream, int(self._dp_buckets), int(per_bucket),
+        self.last_dp = dict(buckets=self._dp_buckets, messages="16-bit" if msg is not None else "fp32", update_per_bucket=plan.dp_per_bucket, world=self._dp_world)
+        self._dp_keep = DpPlan(ctypes.sizeof(DpPlan), int(self._dp_world), nc.handle, nc.stream.cuda_stream, int(self._dp_buckets), plan.dp_per_bucket,
                                None if msg is None else msg.data_ptr())
         return self._dp_keep
 
     def _step(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
         opt = self.optimizer
         if self._sets_lr:                   # (every micro-step of a window sees the same count: the value of the step that ends it)
-            self.last_lr = self._base_lr if self.lr_schedule is None else self.lr_schedule.lr_at(opt._steps + 1)
+            self.last_lr = self._base_lr if self.lr_schedule is None else self.lr_schedule.lr_at(opt.steps + 1)
             set_group_lrs(opt, self.last_lr)
         else:
             self.last_lr = float(opt.param_groups[0]["lr"])
         if self._native_ok(fmri, labels):
             return self._native_step(fmri, labels) if mix is None else self._native_step(fmri, labels, mix)
         model, vit = self.model, self._vit
-        last_micro = (self._micro + 1) % self.accumulation_steps == 0
+        last_micro = self._ends_window
         pipelined = self.sync is not None and last_micro
         # the all-reduce / optimizer pipeline runs only on the micro-step that ends an accumulation window
         vit._grad_sync = self.sync if pipelined else None
         if pipelined and self._overlap_opt:
-            self.optimizer.begin_step()
+            opt.begin_step()
         self.last_path = "general"
         outputs = model(fmri)
         self.last_outputs = outputs.detach()           # the Trainer shell counts accuracy from these (3D and 4D alike)
         loss = self.criterion(outputs, labels) if mix is None else self.criterion(outputs, labels, mix)
         if self._micro == 0:
-            self.optimizer.zero_grad(set_to_none=True)
+            opt.zero_grad(set_to_none=True)
         if self.scaler is not None:
             self.scaler.scale(loss).backward()         # Trainer.py:74: scaler.scale(loss).backward()
         elif self.static_scale > 0:
             (loss * self.static_scale).backward()
         else:
             loss.backward()
-        self._micro += 1
         if last_micro:
             scale = 1.0 / self.world
             if self.world > 1:
@@ -557,7 +534,7 @@ class TrainStep:
                     inline = [p for p in inline if id(p) not in self._head_ids]
                 # a head parameter whose gradient is NOT an arena view (stock-module path) is copied into the head's arena by
                 # gather_foreign_grads and scaled there by the fused step's grad_scale: it must not be scaled here as well
-                fused_scales_head = arena_synced and head is not None and any(h is head for h in self.optimizer.arenas())
+                fused_scales_head = arena_synced and head is not None and any(h is head for h in opt.arenas())
                 for p in inline:
                     if p.grad is not None:
                         dist.all_reduce(p.grad, group=self._pg)
@@ -565,15 +542,14 @@ class TrainStep:
                             p.grad.mul_(scale)
                 if not arena_synced:
                     scale = 1.0                        # already averaged above
-            if self.static_scale > 0:
-                scale = scale / self.static_scale
+            scale = self._unscaled(scale)
             if pipelined and self._overlap_opt:
                 vit.mark_shadow_fresh()                # every range was updated (and its bf16 shadow refreshed) by the buckets
-                self.optimizer.step_rest(grad_scale=scale)
+                opt.step_rest(grad_scale=scale)
             else:
                 red = self.sync.reduced_buffer() if (pipelined and not self.sync.write_back) else None
-                self.optimizer.step(grad_scale=scale, reduced_bf16=None if red is None else {id(vit): red}, scaler=self.scaler, clip=self.clipper)
-            self._micro = 0
+                opt.step(grad_scale=scale, reduced_bf16=None if red is None else {id(vit): red}, scaler=self.scaler, clip=self.clipper)
+        self._count_micro(last_micro)
         return loss.detach()
 
 

@@ -256,3 +256,27 @@ def test_native_dp_step_on_a_one_rank_rccl_communicator_equals_the_single_proces
         assert torch.equal(model.volume_encoder.vit3d.flat_parameters()[0].detach().cpu(), ref)
     finally:
         _cabi.set_operand_format("bf16")
+
+
+def test_native_dp_plan_never_replays_a_captured_graph(monkeypatch):
+    """A captured step holds forward, loss and backward but no all-reduce, so under the native data-parallel plan NEUROVIT_GRAPH_STEP=1
+    must change nothing: six steps on two recycled input buffers (what a graph would be captured for on second sight) all take the
+    native-dp path, no graph is kept, and the parameters equal those of the same six steps without the variable, bit for bit."""
+    from neurovit_amd.trainer import TrainStep
+    buffers = [_data(7), _data(8)]
+
+    def run():
+        model = _model()
+        step = TrainStep(model, n_buckets=3, native_dp=True)
+        for i in range(6):
+            step(*buffers[i % 2])
+            assert step.last_path == "native-dp"
+        torch.cuda.synchronize()
+        return step, model.volume_encoder.vit3d.flat_parameters()[0].detach().cpu().clone()
+
+    monkeypatch.delenv("NEUROVIT_GRAPH_STEP", raising=False)
+    _, want = run()
+    monkeypatch.setenv("NEUROVIT_GRAPH_STEP", "1")
+    step, got = run()
+    assert step._graphs_on and step._graphs == {}
+    assert torch.equal(got, want)
