@@ -947,6 +947,71 @@ int nv_mix_params(const nv_mix_config* cfg, unsigned long seed, unsigned long st
 int nv_augment_mix(const float* src, const long* strides5, int B, const int* in3, int T, const int* aug, const int* mix, const int* roi3, float fill,
                    float* out, void* stream);
 
+/* (added within revision 8 - new symbols and one new struct only, nothing existing changes) random affine augmentation on the device:
+ * per sample a rotation about the centre of the window, a zoom and a sub-voxel translation on top of the crop, the flips and the
+ * intensity change of nv_augment_*, by ONE streaming gather pass with trilinear interpolation, for 3D volumes and 4D series (monai's
+ * RandAffine / RandRotate / RandZoom, the neighbours of the reference's RandSpatialCrop).  No call allocates, synchronises or reads
+ * anything back, and the host draws no random number; every argument is checked first.
+ *
+ * ---- nv_affine_params: writes table int32 [B, 16] (DEVICE).  Row b: columns 0 .. 11 the fp32 bit patterns of the 3 x 4 map, as
+ *   M_a0, M_a1, M_a2, m_a3 for axis a = x, y, z; column 12 / 13 the bits of the fp32 intensity scale / shift; column 14 flags (bit 0 / 1 / 2 =
+ *   flip of x / y / z, bit 3 = affine applied); column 15 zero.  The map takes output cell (i, j, k) of the window to a source coordinate
+ *   in voxel units of the input volume: s_a = M_a0 i + M_a1 j + M_a2 k + m_a3.
+ *   The draws live in a domain of their own (no draw of nv_augment_params or nv_mix_params is reused), with nv_hash64 as above:
+ *     seed_f = nv_hash64(nv_hash64(seed, rank), 0x414646);  draw d of sample b at step s:  h = nv_hash64(seed_f, ((s 2^32 + b) 32 + d) mod 2^64)
+ *     a real u = (h >> 11) 2^-53, exact in double
+ *     d = 0 .. 2     crop offset o_a: an integer on [0, in_size[a] - roi[a]], ((h >> 32) n) >> 32 as nv_augment_params
+ *     d = 3 .. 5     flip of axis a: (h >> 48) < (unsigned)(flip_prob[a] * 65536)
+ *     d = 6          applied iff (h >> 48) < (unsigned)(prob * 65536)
+ *     d = 7 .. 9     theta_a = (2 u - 1) rotate_deg[a] (pi / 180)
+ *     d = 10 .. 12   z_a = zoom_lo + (zoom_hi - zoom_lo) u; with `isotropic`, d = 10 serves all three axes
+ *     d = 13 .. 15   t_a = (2 u - 1) translate[a], in voxels
+ *     d = 16, 17     scale and shift: lo + ((hi - lo) u) in fp32 with u = (h >> 40) 2^-24, as nv_augment_params
+ *   A sample that is not applied has theta = 0, z = 1, t = 0 (its rotation is the identity matrix itself); its crop, flips and
+ *   intensity still hold.  Then, in DOUBLE, every product and sum rounded on its own, sums from the left:
+ *     R = Rz(theta_z) (Ry(theta_y) Rx(theta_x)),  M_ab = R_ab (f_b / z_b) with f_b = -1 for a flipped axis and +1 otherwise
+ *     c_a = (roi[a] - 1) / 2,  m_a3 = ((o_a + t_a) + c_a) - ((M_a0 c_x + M_a1 c_y) + M_a2 c_z)
+ *   and each of the twelve numbers is rounded to fp32 once (a zero is stored as +0.0).  Zoom z > 1 magnifies the content: the source
+ *   step is 1 / z.  The window turns about its own centre, which the crop offset and the translation place in the volume.
+ *   Refused (NV_ERR_ARG): NULL pointers, B < 1, a negative rank, a wrong struct_size, a roi that is not positive or larger than the input,
+ *   an input beyond 2^24 cells along an axis, |rotate_deg| > 180, zoom not 0 < lo <= hi <= 16, a negative or non-finite translate,
+ *   probabilities outside [0, 1], intensity ranges with lo > hi or not finite.
+ *
+ * ---- nv_affine_apply: src, strides5, B, in3, T, roi3, fill, out as for nv_augment_apply; table int32 [B, 16] (DEVICE) rows as above -
+ *   they may also be written by hand and hold anything (NaN, infinities, 1e30).  THE ARITHMETIC IS PART OF THE ABI: all fp32, every
+ *   operation rounded on its own, nothing contracted.  For output cell (i, j, k, t) of sample b:
+ *     coordinate   s_a = ((M_a0 i + M_a1 j) + M_a2 k) + m_a3, from the indices of every cell (never advanced incrementally)
+ *     fraction     f_a = floorf(s_a), w_a = s_a - f_a  (in [0, 1]; 1 is possible just below an integer)
+ *     corners      (f_x + dx, f_y + dy, f_z + dz), dx, dy, dz in {0, 1}: inside the volume the source value, outside it `fill`.  The range
+ *                  test is made on the FLOAT: a coordinate that is NaN, infinite or not in [-1, N_a) puts the corners it addresses
+ *                  outside; no index is formed from an unchecked value
+ *     lerp         lerp(a, b, w) = a + ((b - a) w); for w == 0 it is `a` VERBATIM: the upper corners along that axis are not used (a NaN or
+ *                  an infinity there does not reach the cell; a fetch of them is from an index clamped into the volume and is discarded)
+ *     order        along z first, then y, then x
+ *     all outside  a cell whose every USED corner lies outside the volume is `fill`, verbatim
+ *     intensity    every other cell becomes (v scale) + shift (two roundings), skipped for scale == 1.0f && shift == 0.0f
+ *   Hence a table with an integer map (no rotation, zoom 1, no translation) writes, bit for bit, what nv_augment_apply writes for the
+ *   row {m_x3, m_y3, m_z3 (minus S_a - 1 on a flipped axis), flips, scale, shift} - NaN payloads and -0.0 included - and an exact quarter
+ *   turn is an exact permutation.  The T timepoints of a sample share its row; each corner of a series cell is T floats.
+ *   Every output element is written exactly once, nothing else is written; one launch whose grid follows the output rows.  Limits and
+ *   refusals as nv_augment_apply; also refused: an input beyond 2^24 cells along an axis (indices are exact in fp32), an `out` that
+ *   overlaps the span of memory `src` and its strides reach (a gather must not overwrite its own source). */
+typedef struct nv_affine_config {
+  int struct_size;            /* sizeof(nv_affine_config): checked */
+  int in_size[3];             /* X, Y, Z of the input volume */
+  int roi[3];                 /* Sx, Sy, Sz of the window */
+  double rotate_deg[3];       /* theta_a uniform on [-rotate_deg[a], rotate_deg[a]] degrees, about axis a */
+  double zoom_lo, zoom_hi;    /* 0 < lo <= hi <= 16 */
+  int isotropic;              /* one zoom draw for the three axes */
+  double translate[3];        /* t_a uniform on [-translate[a], translate[a]] voxels */
+  double prob;                /* probability that rotation / zoom / translation apply to a sample */
+  double flip_prob[3];
+  float scale_lo, scale_hi, shift_lo, shift_hi;
+} nv_affine_config;
+int nv_affine_params(const nv_affine_config* cfg, unsigned long seed, unsigned long step, int rank, int B, int* table, void* stream);
+int nv_affine_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* table, const int* roi3, float fill,
+                    float* out, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

@@ -8,10 +8,13 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    # `from neurovit_amd import VolumeAugment` (or VolumeMix, ModelEma), resolved on first use: importing the package itself stays free of torch
+    # `from neurovit_amd import VolumeAugment` (or VolumeAffine, VolumeMix, ModelEma), resolved on first use: importing the package itself stays free of torch
     if name == "VolumeAugment":
         from .augment import VolumeAugment
         return VolumeAugment
+    if name == "VolumeAffine":
+        from .augment import VolumeAffine
+        return VolumeAffine
     if name == "VolumeMix":
         from .augment import VolumeMix
         return VolumeMix

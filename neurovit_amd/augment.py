@@ -1,4 +1,5 @@
-"""Training augmentation on the device: per-sample random crop, integer translation, axis flips and an affine intensity change.
+"""Training augmentation on the device: per-sample random crop, integer translation, axis flips and an affine intensity change
+(`VolumeAugment`), Mixup / CutMix (`VolumeMix`), and a random rotation, zoom and sub-voxel shift (`VolumeAffine`).
 
 The reference has one augmentation switch: `DATASET_TRANSFORMS` makes `ADNIDataset.__getitem__` apply monai's
 `RandSpatialCrop(roi_size=(80, 80, 80), random_center=True, random_size=False)` to the z-scored 90^3 volume on the host
@@ -7,14 +8,17 @@ it - as two HIP launches on the batch that is already on the device (csrc/augmen
 (seed, rank, step, sample) by the counter hash of the dropout masks, so nothing is read back and the host draws no random number; the
 draw rule is part of the C-ABI (include/neurovit_hip.h) and tests/augment_ref.py restates it bit for bit.
 
-Exact transforms only: no noise, no resampling.  No gradient flows through it.
+`VolumeAugment` moves whole voxels and is exact.  `VolumeAffine` (csrc/affine.hip) is the one transform that resamples: a streaming
+gather with trilinear interpolation under a per-sample 3 x 4 map that is drawn and formed on the device in the same way; its fp32
+arithmetic is part of the C-ABI and tests/affine_ref.py restates it bit for bit.  A sample it does not turn, zoom or shift is still the
+bit copy VolumeAugment would write.  No noise.  No gradient flows through any of them.
 """
 from __future__ import annotations
 
 import ctypes
 import math
 import struct
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -81,9 +85,10 @@ def _check_rows(who, name, rows, B, cols, device) -> torch.Tensor:
     return rows.contiguous()
 
 
-def _run_pass(who, x, roi, fill, rows, mix, out):
+def _run_pass(who, x, roi, fill, rows, mix, out, affine=False):
     """The streaming pass over x [B, X, Y, Z(, T)] into the dense [B, *roi(, T)] batch: nv_augment_apply under the checked rows [B, 8]
-    without a mix table, nv_augment_mix under rows (or None: identity rows) and the checked mix table with one."""
+    without a mix table, nv_augment_mix under rows (or None: identity rows) and the checked mix table with one; affine: the gather pass
+    nv_affine_apply under the checked rows [B, 16]."""
     four_d = x.dim() == 5
     v = x if four_d else x.unsqueeze(-1)
     B, X, Y, Z, T = v.shape
@@ -99,7 +104,9 @@ def _run_pass(who, x, roi, fill, rows, mix, out):
     dst = (ctypes.cast(roi3, ctypes.c_void_p), fill, out.data_ptr())
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream().cuda_stream
-        if mix is None:
+        if affine:
+            check(lib.nv_affine_apply(*src, rows.data_ptr(), *dst, stream), "nv_affine_apply")
+        elif mix is None:
             check(lib.nv_augment_apply(*src, rows.data_ptr(), *dst, stream), "nv_augment_apply")
         else:
             check(lib.nv_augment_mix(*src, None if rows is None else rows.data_ptr(), mix.data_ptr(), *dst, stream), "nv_augment_mix")
@@ -221,6 +228,127 @@ class VolumeAugment:
         return out
 
 
+class AffineConfig(ctypes.Structure):
+    """struct nv_affine_config (neurovit_hip.h, added within revision 8)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("in_size", ctypes.c_int * 3), ("roi", ctypes.c_int * 3), ("rotate_deg", ctypes.c_double * 3),
+                ("zoom_lo", ctypes.c_double), ("zoom_hi", ctypes.c_double), ("isotropic", ctypes.c_int), ("translate", ctypes.c_double * 3),
+                ("prob", ctypes.c_double), ("flip_prob", ctypes.c_double * 3), ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
+                ("shift_lo", ctypes.c_float), ("shift_hi", ctypes.c_float)]
+
+
+AFFINE_COLS = 16     # int32 columns of a row of nv_affine_params
+
+
+class VolumeAffine:
+    """Random rotation, zoom and sub-voxel translation on the device (monai's RandAffine / RandRotate / RandZoom), together with the crop,
+    the flips and the intensity change of VolumeAugment, as ONE trilinear gather pass (nv_affine_apply).  roi: (Sx, Sy, Sz) of the output
+    window (an int = a cube).  Per sample: a crop offset uniform on [0, X - S] per axis; with probability `prob` a rotation about the
+    centre of the window by angles uniform on [-rotate, rotate] degrees about the x, y and z axes (composed Rz Ry Rx), a zoom uniform on
+    `zoom` = (lo, hi) - one draw for the three axes when `isotropic`, one per axis otherwise; above 1 the content grows - and a
+    translation uniform on [-translate, translate] voxels per axis; a flip per axis with probability flip_prob; an intensity change
+    x * scale + shift.  Cells of the window whose source lies outside the volume blend towards `fill`.  The T timepoints of a 4D sample
+    share its parameters.  Every option at its default switches that transform off; with the roi equal to the input size as well the
+    instance is the identity and `__call__` launches nothing.  A sample that `prob` leaves out is the bit copy VolumeAugment would write.
+
+    seed, rank and the step index decide every draw (nv_affine_params in the header; a hash domain of its own, so a VolumeAugment or
+    VolumeMix with the same seed draws independently).  `step` counts the calls of this instance unless it is given."""
+
+    def __init__(self, roi, rotate=0.0, zoom=(1, 1), isotropic: bool = True, translate=0.0, prob: float = 1.0, flip_prob=(0, 0, 0), scale=(1, 1),
+                 shift=(0, 0), fill: float = 0.0, seed: int = 0, rank: int = 0):
+        self.roi = _triple(roi, "roi", int)
+        if any(s <= 0 for s in self.roi):
+            raise ValueError(f"VolumeAffine: roi must be positive, got {self.roi}")
+        self.rotate = _triple(rotate, "rotate", float)
+        if any(not (abs(r) <= 180.0) for r in self.rotate):
+            raise ValueError(f"VolumeAffine: rotate must lie in [-180, 180] degrees, got {self.rotate}")
+        try:
+            lo, hi = zoom
+        except (TypeError, ValueError):
+            raise TypeError(f"VolumeAffine: zoom must be a pair (lo, hi) of numbers, got {zoom!r}") from None
+        if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in (lo, hi)):
+            raise TypeError(f"VolumeAffine: zoom must be a pair (lo, hi) of numbers, got {zoom!r}")
+        if not (0.0 < lo <= hi <= 16.0):
+            raise ValueError(f"VolumeAffine: zoom must satisfy 0 < lo <= hi <= 16, got {zoom!r}")
+        self.zoom = (float(lo), float(hi))
+        if not isinstance(isotropic, bool):
+            raise TypeError(f"VolumeAffine: isotropic must be true or false, got {isotropic!r}")
+        self.isotropic = isotropic
+        self.translate = _triple(translate, "translate", float)
+        if any(not (0.0 <= t < math.inf) for t in self.translate):
+            raise ValueError(f"VolumeAffine: translate must be finite and not negative, got {self.translate}")
+        if isinstance(prob, bool) or not isinstance(prob, (int, float)):
+            raise TypeError(f"VolumeAffine: prob must be a number, got {prob!r}")
+        if not (0.0 <= float(prob) <= 1.0):
+            raise ValueError(f"VolumeAffine: prob {prob} outside [0, 1]")
+        self.prob = float(prob)
+        self.flip_prob = _triple(flip_prob, "flip_prob", float)
+        if any(not (0.0 <= p <= 1.0) for p in self.flip_prob):
+            raise ValueError(f"VolumeAffine: flip probabilities must lie in [0, 1], got {self.flip_prob}")
+        self.scale = _range(scale, "scale")
+        self.shift = _range(shift, "shift")
+        self.fill = float(fill)
+        _check_seed_rank("VolumeAffine", seed, rank)
+        self.seed, self.rank = seed, rank
+        self.step = 0                      # the step index the next __call__ without `step=` draws for
+        self.last_params: Optional[torch.Tensor] = None
+
+    # ------------------------------------------------------------------ checks
+    def _transforms_off(self) -> bool:
+        still = self.prob == 0.0 or (all(r == 0.0 for r in self.rotate) and self.zoom == (1.0, 1.0) and all(t == 0.0 for t in self.translate))
+        return still and all(p == 0.0 for p in self.flip_prob) and self.scale == (1.0, 1.0) and self.shift == (0.0, 0.0)
+
+    def _check_input(self, x: torch.Tensor):
+        _check_volume("VolumeAffine", "augmentation", x, self.roi)
+
+    def is_identity(self, x: torch.Tensor) -> bool:
+        """No transform is on and the roi is the input's spatial size: __call__ returns x itself."""
+        return self._transforms_off() and tuple(x.shape[1:4]) == self.roi
+
+    # ------------------------------------------------------------------ the two launches
+    def params(self, B: int, step: int, in_size: Optional[Sequence[int]] = None, device=None) -> torch.Tensor:
+        """int32 [B, 16] on the device for step `step`: the fp32 bits of the 3 x 4 map output cell -> source coordinate (M_a0, M_a1, M_a2,
+        m_a3 for a = x, y, z), the bits of scale and shift, flags (bits 0 .. 2 the flips, bit 3 "affine applied"), 0.
+        in_size: (X, Y, Z) of the volumes the window is cut from (default: the roi itself - no room to crop)."""
+        step = _check_step(step)
+        in_size = self.roi if in_size is None else _triple(in_size, "in_size", int)
+        if any(s > n for s, n in zip(self.roi, in_size)):
+            raise ValueError(f"VolumeAffine: roi {self.roi} is larger than the input {tuple(in_size)}")
+        device = _draw_target("VolumeAffine", B, device)
+        out = torch.empty((B, AFFINE_COLS), dtype=torch.int32, device=device)
+        cfg = AffineConfig(ctypes.sizeof(AffineConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi), (ctypes.c_double * 3)(*self.rotate),
+                           self.zoom[0], self.zoom[1], int(self.isotropic), (ctypes.c_double * 3)(*self.translate), self.prob,
+                           (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1], self.shift[0], self.shift[1])
+        with torch.cuda.device(device):
+            check(lib.nv_affine_params(ctypes.byref(cfg), self.seed, step, self.rank, B, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                  "nv_affine_params")
+        return out
+
+    def apply(self, x: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """x [B, X, Y, Z] or [B, X, Y, Z, T] float32 on the device, dense or a strided view; table int32 [B, 16] (as `params` returns it, or
+        written by hand: rows may hold anything).  Returns the dense [B, Sx, Sy, Sz(, T)] batch; a caller-supplied `out` of that shape is
+        dense and must not overlap x."""
+        self._check_input(x)
+        table = _check_rows("VolumeAffine", "table", table, x.shape[0], AFFINE_COLS, x.device)
+        return _run_pass("VolumeAffine", x, self.roi, self.fill, table, None, out, affine=True)
+
+    def __call__(self, x: torch.Tensor, step: Optional[int] = None) -> torch.Tensor:
+        """The augmented batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
+        The table used is kept in `last_params` (a device tensor; None for the identity)."""
+        self._check_input(x)
+        own = step is None
+        step = self.step if own else _check_step(step)
+        if self.is_identity(x):
+            self.last_params = None
+            out = x
+        else:
+            table = self.params(x.shape[0], step, in_size=tuple(x.shape[1:4]), device=x.device)
+            out = self.apply(x, table)
+            self.last_params = table
+        if own:
+            self.step += 1
+        return out
+
+
 def center_window(x: torch.Tensor, roi: Sequence[int]) -> torch.Tensor:
     """The centre window of x [B, X, Y, Z(, T)] at offset (X - S) // 2 per axis, as a strided VIEW (x itself when the sizes agree)."""
     size = tuple(x.shape[1:4])
@@ -248,7 +376,8 @@ class VolumeMix:
     `params` draws the table on the device (nv_mix_params: int32 [B, 12] = {partner, mode, bits of the pixel lambda, bits of the label
     lambda, tries, x0, x1, y0, y1, z0, z1, 0}; the rule is in include/neurovit_hip.h and tests/mix_ref.py restates it); `apply` is ONE
     streaming launch (nv_augment_mix) that also does the work of a VolumeAugment when one is handed in - each sample and its partner
-    under their own crop / flip / intensity rows - so that a batch is read and written once.  `last_mix` is what the loss needs
+    under their own crop / flip / intensity rows - so that a batch is read and written once.  With a VolumeAffine it is TWO launches: the
+    gather pass writes the dense window, the mix pass then runs on it with identity rows.  `last_mix` is what the loss needs
     (nn.CrossEntropyLoss.forward(..., mix=) / TrainStep.__call__(..., mix=)).  No gradient flows through it."""
 
     def __init__(self, mixup_alpha: Optional[float] = None, cutmix_alpha: Optional[float] = None, prob: float = 1.0, switch_prob: float = 0.5,
@@ -294,15 +423,20 @@ class VolumeMix:
                   "nv_mix_params")
         return out
 
-    def apply(self, x: torch.Tensor, mix: torch.Tensor, augment: Optional[VolumeAugment] = None, augment_params: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def apply(self, x: torch.Tensor, mix: torch.Tensor, augment: Union[VolumeAugment, VolumeAffine, None] = None,
+              augment_params: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x [B, X, Y, Z(, T)] float32 on the device, dense or a strided view; mix int32 [B, 12].  With `augment` (a VolumeAugment: its
         roi and fill) and `augment_params` (int32 [B, 8], its rows) the crop / flips / intensity change happen in the same pass; without,
-        the window is the whole volume and every row the identity.  Returns the dense [B, Sx, Sy, Sz(, T)] batch."""
-        if augment is not None and not isinstance(augment, VolumeAugment):
-            raise TypeError(f"VolumeMix.apply: augment must be a VolumeAugment, got {type(augment).__name__}")
+        the window is the whole volume and every row the identity.  With a VolumeAffine and its table (int32 [B, 16]) the gather pass
+        runs first and the mix pass on its dense output: two launches.  Returns the dense [B, Sx, Sy, Sz(, T)] batch."""
+        if augment is not None and not isinstance(augment, (VolumeAugment, VolumeAffine)):
+            raise TypeError(f"VolumeMix.apply: augment must be a VolumeAugment or a VolumeAffine, got {type(augment).__name__}")
         if (augment is None) != (augment_params is None):
             raise ValueError("VolumeMix.apply: augment and augment_params come together")
+        if isinstance(augment, VolumeAffine):
+            window = augment.apply(x, augment_params)
+            mix = _check_rows("VolumeMix", "mix", mix, x.shape[0], MIX_COLS, x.device)
+            return _run_pass("VolumeMix", window, augment.roi, 0.0, None, mix, out)
         roi = None if augment is None else augment.roi
         _check_volume("VolumeMix", "mix", x, roi)
         B = x.shape[0]
@@ -311,12 +445,13 @@ class VolumeMix:
             augment_params = _check_rows("VolumeMix", "augment_params", augment_params, B, 8, x.device)
         return _run_pass("VolumeMix", x, roi or tuple(x.shape[1:4]), 0.0 if augment is None else augment.fill, augment_params, mix, out)
 
-    def __call__(self, x: torch.Tensor, step: Optional[int] = None, augment: Optional[VolumeAugment] = None) -> torch.Tensor:
+    def __call__(self, x: torch.Tensor, step: Optional[int] = None, augment: Union[VolumeAugment, VolumeAffine, None] = None) -> torch.Tensor:
         """The mixed batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
-        augment: a VolumeAugment to apply in the same pass, with ITS draws for the same step index (its last_params is set; its own
-        counter is not touched).  The table used is kept in `last_mix` (a device tensor; None for the identity)."""
-        if augment is not None and not isinstance(augment, VolumeAugment):
-            raise TypeError(f"VolumeMix: augment must be a VolumeAugment, got {type(augment).__name__}")
+        augment: a VolumeAugment to apply in the same pass - or a VolumeAffine, whose gather pass runs in front of the mix pass - with ITS
+        draws for the same step index (its last_params is set; its own counter is not touched).  The table used is kept in `last_mix`
+        (a device tensor; None for the identity)."""
+        if augment is not None and not isinstance(augment, (VolumeAugment, VolumeAffine)):
+            raise TypeError(f"VolumeMix: augment must be a VolumeAugment or a VolumeAffine, got {type(augment).__name__}")
         own = step is None
         step = self.step if own else _check_step(step)
         self._check_input(x)

@@ -607,7 +607,8 @@ class Trainer:
         Trainer.py:34,89); TRAINING_ACCUMULATION_STEP is honoured as in the commented block (Trainer.py:82-86);
       * DATASET_TRANSFORMS (the reference's RandSpatialCrop inside Dataset.__getitem__, DatasetADNI.py:27-31,216-218) is applied to the
         batch ON THE DEVICE (augment.VolumeAugment: the window is the model's input size, the datasets hand over the uncropped
-        volumes), with optional AUGMENT_* keys for flips, shifts and intensity changes; `train` draws a random window per sample,
+        volumes), with optional AUGMENT_* keys for flips, shifts and intensity changes - and for a random rotation, zoom and sub-voxel
+        shift (AUGMENT_ROTATE_DEG / _ZOOM / _TRANSLATE ...: augment.VolumeAffine, a trilinear resampling pass); `train` draws a random window per sample,
         while `validate` / `evaluate_samples` take the CENTRE window (offset (X - S) // 2 per axis, a strided view) - the reference
         crops randomly at validation too, which makes its validation loss depend on the draw;
       * optional keys the reference does not have: TRAINING_EMA_DECAY / _WARMUP / _UPDATE_EVERY keep a weight average (optim.ModelEma) that
@@ -748,11 +749,27 @@ class Trainer:
         untouched.  True = a VolumeAugment whose window is the model's input size; crop only, unless the optional keys (which the
         reference's config files do not have) switch more on: AUGMENT_FLIP_PROB, AUGMENT_MAX_SHIFT (a number or three, per axis),
         AUGMENT_INTENSITY_SCALE, AUGMENT_INTENSITY_SHIFT ((lo, hi) pairs), AUGMENT_FILL, AUGMENT_SEED.  The rank is the process
-        group's when there is one."""
+        group's when there is one.
+        Any of AUGMENT_ROTATE_DEG (degrees, a number or three), AUGMENT_ZOOM ((lo, hi)), AUGMENT_ZOOM_ISOTROPIC (default true),
+        AUGMENT_TRANSLATE (voxels, a number or three) and AUGMENT_AFFINE_PROB (default 1) makes it a VolumeAffine instead - the
+        resampling pass - with the same flip, intensity, fill and seed keys; the integer AUGMENT_MAX_SHIFT does not go with them
+        (ValueError: AUGMENT_TRANSLATE is the shift of that pass)."""
         if not config.get('DATASET_TRANSFORMS', False):
             return None
-        from .augment import VolumeAugment
+        from .augment import VolumeAffine, VolumeAugment
         S = config['TRAINING_VIT_INPUT_SIZE']
+        affine_keys = ('AUGMENT_ROTATE_DEG', 'AUGMENT_ZOOM', 'AUGMENT_ZOOM_ISOTROPIC', 'AUGMENT_TRANSLATE', 'AUGMENT_AFFINE_PROB')
+        if any(config.get(k, None) is not None for k in affine_keys):
+            if config.get('AUGMENT_MAX_SHIFT', None) is not None:
+                raise ValueError("AUGMENT_MAX_SHIFT does not go with the affine keys (" + ", ".join(k for k in affine_keys if config.get(k, None) is not None)
+                                 + "): set AUGMENT_TRANSLATE, the (sub-voxel) shift of the resampling pass")
+            pick = lambda key, default: default if config.get(key, None) is None else config[key]
+            return VolumeAffine((S, S, S), rotate=pick('AUGMENT_ROTATE_DEG', 0.0), zoom=pick('AUGMENT_ZOOM', (1, 1)),
+                                isotropic=pick('AUGMENT_ZOOM_ISOTROPIC', True), translate=pick('AUGMENT_TRANSLATE', 0.0),
+                                prob=pick('AUGMENT_AFFINE_PROB', 1.0), flip_prob=config.get('AUGMENT_FLIP_PROB', (0, 0, 0)),
+                                scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)), shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)),
+                                fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
+                                rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
         return VolumeAugment((S, S, S), flip_prob=config.get('AUGMENT_FLIP_PROB', (0, 0, 0)), max_shift=config.get('AUGMENT_MAX_SHIFT', (0, 0, 0)),
                              scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)), shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)),
                              fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
@@ -837,7 +854,7 @@ class Trainer:
         for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):     # H2D of batch i+1 under step i
             fMRI, label = self._unpack(batch)
             if self.mix is not None:
-                fMRI = self.mix(fMRI, step=self.global_step, augment=self.augment)      # crop / flips / intensity and the mix in one pass
+                fMRI = self.mix(fMRI, step=self.global_step, augment=self.augment)      # crop / flips / intensity and the mix in one pass (two behind a VolumeAffine)
             elif self.augment is not None:
                 fMRI = self.augment(fMRI, step=self.global_step)
             self.global_step += 1
