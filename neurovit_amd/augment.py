@@ -32,7 +32,7 @@ class AugmentConfig(ctypes.Structure):
                 ("shift_hi", ctypes.c_float)]
 
 
-# ---------------------------------------------------------------------- what VolumeAugment and VolumeMix check alike (`who` names the class)
+# ---------------------------------------------------------------------- what the three transforms check alike (`who` names the class)
 def _check_seed_rank(who, seed, rank):
     for name, value, top in (("seed", seed, 2 ** 64), ("rank", rank, 2 ** 31)):
         if isinstance(value, bool) or not isinstance(value, int):
@@ -41,12 +41,22 @@ def _check_seed_rank(who, seed, rank):
             raise ValueError(f"{who}: {name} {value} outside [0, {top})")
 
 
-def _check_step(step) -> int:
+def _check_step(who, step) -> int:
     if isinstance(step, bool) or not isinstance(step, int):
-        raise TypeError(f"VolumeAugment: step must be an integer, got {step!r}")
+        raise TypeError(f"{who}: step must be an integer, got {step!r}")
     if not (0 <= step < 2 ** 64):
-        raise ValueError(f"VolumeAugment: step {step} outside [0, 2^64)")
+        raise ValueError(f"{who}: step {step} outside [0, 2^64)")
     return step
+
+
+def _at_step(who, obj, step, body):
+    """The running-step protocol of a __call__: body(step index) for obj's own counter, which then advances by one, unless `step` is
+    given: then for that index, and the counter stays."""
+    own = step is None
+    out = body(obj.step if own else _check_step(who, step))
+    if own:
+        obj.step += 1
+    return out
 
 
 def _check_volume(who, what, x, roi=None):
@@ -85,10 +95,9 @@ def _check_rows(who, name, rows, B, cols, device) -> torch.Tensor:
     return rows.contiguous()
 
 
-def _run_pass(who, x, roi, fill, rows, mix, out, affine=False):
-    """The streaming pass over x [B, X, Y, Z(, T)] into the dense [B, *roi(, T)] batch: nv_augment_apply under the checked rows [B, 8]
-    without a mix table, nv_augment_mix under rows (or None: identity rows) and the checked mix table with one; affine: the gather pass
-    nv_affine_apply under the checked rows [B, 16]."""
+def _run_pass(who, x, roi, fill, out, entry, *tables):
+    """The streaming pass `entry` (nv_augment_apply, nv_augment_mix or nv_affine_apply) over x [B, X, Y, Z(, T)] into the dense
+    [B, *roi(, T)] batch, under its checked tables in the order of its signature (None: a table the entry point lets be missing)."""
     four_d = x.dim() == 5
     v = x if four_d else x.unsqueeze(-1)
     B, X, Y, Z, T = v.shape
@@ -101,85 +110,79 @@ def _run_pass(who, x, roi, fill, rows, mix, out, affine=False):
     strides = (ctypes.c_long * 5)(*v.stride())
     in3, roi3 = (ctypes.c_int * 3)(X, Y, Z), (ctypes.c_int * 3)(*roi)
     src = (v.data_ptr(), ctypes.cast(strides, ctypes.c_void_p), B, ctypes.cast(in3, ctypes.c_void_p), T)
-    dst = (ctypes.cast(roi3, ctypes.c_void_p), fill, out.data_ptr())
+    rows = (None if t is None else t.data_ptr() for t in tables)
     with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream().cuda_stream
-        if affine:
-            check(lib.nv_affine_apply(*src, rows.data_ptr(), *dst, stream), "nv_affine_apply")
-        elif mix is None:
-            check(lib.nv_augment_apply(*src, rows.data_ptr(), *dst, stream), "nv_augment_apply")
-        else:
-            check(lib.nv_augment_mix(*src, None if rows is None else rows.data_ptr(), mix.data_ptr(), *dst, stream), "nv_augment_mix")
+        check(getattr(lib, entry)(*src, *rows, ctypes.cast(roi3, ctypes.c_void_p), fill, out.data_ptr(), torch.cuda.current_stream().cuda_stream), entry)
     return out
 
 
-def _triple(value, name, kind):
+def _triple(who, value, name, kind):
     if isinstance(value, (int, float)) and not isinstance(value, bool):
         value = (value,) * 3
     try:
         value = tuple(value)
     except TypeError:
-        raise TypeError(f"VolumeAugment: {name} must be a number or three numbers, got {value!r}") from None
+        raise TypeError(f"{who}: {name} must be a number or three numbers, got {value!r}") from None
     if len(value) != 3:
-        raise ValueError(f"VolumeAugment: {name} must have three entries (x, y, z), got {value!r}")
+        raise ValueError(f"{who}: {name} must have three entries (x, y, z), got {value!r}")
     if kind is int:
         if any(isinstance(v, bool) or not isinstance(v, int) for v in value):
-            raise TypeError(f"VolumeAugment: {name} must hold integers, got {value!r}")
+            raise TypeError(f"{who}: {name} must hold integers, got {value!r}")
         return value
     if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in value):
-        raise TypeError(f"VolumeAugment: {name} must hold numbers, got {value!r}")
+        raise TypeError(f"{who}: {name} must hold numbers, got {value!r}")
     return tuple(float(v) for v in value)
 
 
-def _range(value, name):
+def _range(who, value, name):
     try:
         lo, hi = (float(v) for v in value)
     except (TypeError, ValueError):
-        raise TypeError(f"VolumeAugment: {name} must be a pair (lo, hi) of numbers, got {value!r}") from None
+        raise TypeError(f"{who}: {name} must be a pair (lo, hi) of numbers, got {value!r}") from None
     if not (math.isfinite(lo) and math.isfinite(hi)):
-        raise ValueError(f"VolumeAugment: {name} must be finite, got {value!r}")
+        raise ValueError(f"{who}: {name} must be finite, got {value!r}")
     if lo > hi:
-        raise ValueError(f"VolumeAugment: {name} has lo > hi: {value!r}")
+        raise ValueError(f"{who}: {name} has lo > hi: {value!r}")
     as_f32 = lambda v: struct.unpack("f", struct.pack("f", v))[0]      # what the kernel sees
     return as_f32(lo), as_f32(hi)
 
 
-class VolumeAugment:
-    """roi: (Sx, Sy, Sz) of the output window (an int = a cube).  Per sample and per axis: a crop offset uniform on [0, X - S] (monai's
-    RandSpatialCrop with a fixed size), plus an integer translation uniform on [-max_shift, max_shift] (cells of the window that leave
-    the volume get `fill`), a flip with probability flip_prob; per sample an intensity change x * scale + shift with scale / shift
-    uniform on their (lo, hi) ranges.  The T timepoints of a 4D sample share its parameters.  Every option at its default switches that
-    transform off; with the roi equal to the input size as well, the instance is the identity and `__call__` launches nothing.
+class _WindowTransform:
+    """What VolumeAugment and VolumeAffine share: a window `roi` cut from the volume per sample, flips, an intensity change, and the two
+    launches - `params` draws a table of `_cols` int32 columns per sample (entry point `_draw`), `apply` is one streaming pass under
+    such a table (entry point `_pass`; `_rows` is its name in the messages).  A subclass checks its own options between `_set_window`
+    and `_set_shared`, says in `_transforms_off` whether all of them are off, and builds its ctypes config in `_config`."""
+    _cols = _rows = _draw = _pass = None
 
-    seed, rank and the step index decide every draw (see nv_augment_params in the header): the same triple reproduces a batch, two
-    ranks with one seed draw different parameters.  `step` counts the calls of this instance unless it is given."""
+    @property
+    def _who(self) -> str:
+        return type(self).__name__
 
-    def __init__(self, roi, flip_prob=(0, 0, 0), max_shift=(0, 0, 0), scale=(1, 1), shift=(0, 0), fill: float = 0.0, seed: int = 0,
-                 rank: int = 0):
-        self.roi = _triple(roi, "roi", int)
+    def _set_window(self, roi):
+        self.roi = _triple(self._who, roi, "roi", int)
         if any(s <= 0 for s in self.roi):
-            raise ValueError(f"VolumeAugment: roi must be positive, got {self.roi}")
-        self.flip_prob = _triple(flip_prob, "flip_prob", float)
+            raise ValueError(f"{self._who}: roi must be positive, got {self.roi}")
+
+    def _set_flips(self, flip_prob):
+        self.flip_prob = _triple(self._who, flip_prob, "flip_prob", float)
         if any(not (0.0 <= p <= 1.0) for p in self.flip_prob):
-            raise ValueError(f"VolumeAugment: flip probabilities must lie in [0, 1], got {self.flip_prob}")
-        self.max_shift = _triple(max_shift, "max_shift", int)
-        if any(m < 0 or m >= 2 ** 30 for m in self.max_shift):
-            raise ValueError(f"VolumeAugment: max_shift must lie in [0, 2^30), got {self.max_shift}")
-        self.scale = _range(scale, "scale")
-        self.shift = _range(shift, "shift")
+            raise ValueError(f"{self._who}: flip probabilities must lie in [0, 1], got {self.flip_prob}")
+
+    def _set_shared(self, scale, shift, fill, seed, rank):
+        self.scale = _range(self._who, scale, "scale")
+        self.shift = _range(self._who, shift, "shift")
         self.fill = float(fill)
-        _check_seed_rank("VolumeAugment", seed, rank)
+        _check_seed_rank(self._who, seed, rank)
         self.seed, self.rank = seed, rank
         self.step = 0                      # the step index the next __call__ without `step=` draws for
         self.last_params: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ checks
-    def _transforms_off(self) -> bool:
-        return (all(p == 0.0 for p in self.flip_prob) and all(m == 0 for m in self.max_shift) and self.scale == (1.0, 1.0)
-                and self.shift == (0.0, 0.0))
+    def _shared_off(self) -> bool:
+        return all(p == 0.0 for p in self.flip_prob) and self.scale == (1.0, 1.0) and self.shift == (0.0, 0.0)
 
     def _check_input(self, x: torch.Tensor):
-        _check_volume("VolumeAugment", "augmentation", x, self.roi)
+        _check_volume(self._who, "augmentation", x, self.roi)
 
     def is_identity(self, x: torch.Tensor) -> bool:
         """No transform is on and the roi is the input's spatial size: __call__ returns x itself."""
@@ -187,45 +190,72 @@ class VolumeAugment:
 
     # ------------------------------------------------------------------ the two launches
     def params(self, B: int, step: int, in_size: Optional[Sequence[int]] = None, device=None) -> torch.Tensor:
-        """int32 [B, 8] on the device: {ox, oy, oz, flip bits, bits of scale, bits of shift, 0, 0} per sample for step `step`.
-        in_size: (X, Y, Z) of the volumes the window is cut from (default: the roi itself - no room to crop)."""
-        step = _check_step(step)
-        in_size = self.roi if in_size is None else _triple(in_size, "in_size", int)
+        """The table for step `step`, int32 [B, 8] (VolumeAugment) or [B, 16] (VolumeAffine) on the device; the class says what a row
+        holds.  in_size: (X, Y, Z) of the volumes the window is cut from (default: the roi itself - no room to crop)."""
+        step = _check_step(self._who, step)
+        in_size = self.roi if in_size is None else _triple(self._who, in_size, "in_size", int)
         if any(s > n for s, n in zip(self.roi, in_size)):
-            raise ValueError(f"VolumeAugment: roi {self.roi} is larger than the input {tuple(in_size)}")
-        device = _draw_target("VolumeAugment", B, device)
-        out = torch.empty((B, 8), dtype=torch.int32, device=device)
-        cfg = AugmentConfig(ctypes.sizeof(AugmentConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi),
-                            (ctypes.c_int * 3)(*self.max_shift), (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1],
-                            self.shift[0], self.shift[1])
+            raise ValueError(f"{self._who}: roi {self.roi} is larger than the input {tuple(in_size)}")
+        device = _draw_target(self._who, B, device)
+        out = torch.empty((B, self._cols), dtype=torch.int32, device=device)
+        cfg = self._config(in_size)
         with torch.cuda.device(device):
-            check(lib.nv_augment_params(ctypes.byref(cfg), self.seed, step, self.rank, B, out.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream), "nv_augment_params")
+            check(getattr(lib, self._draw)(ctypes.byref(cfg), self.seed, step, self.rank, B, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                  self._draw)
         return out
 
     def apply(self, x: torch.Tensor, params: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B, X, Y, Z] or [B, X, Y, Z, T] float32 on the device, dense or a strided view; params int32 [B, 8] (as `params` returns them,
-        or written by hand).  Returns the dense [B, Sx, Sy, Sz(, T)] batch; a caller-supplied `out` of that shape is dense."""
+        """x [B, X, Y, Z] or [B, X, Y, Z, T] float32 on the device, dense or a strided view; params: the int32 table (as `params` returns
+        it, or written by hand: rows may hold anything).  Returns the dense [B, Sx, Sy, Sz(, T)] batch; a caller-supplied `out` of that
+        shape is dense and, for the gather pass of a VolumeAffine, must not overlap x."""
         self._check_input(x)
-        params = _check_rows("VolumeAugment", "params", params, x.shape[0], 8, x.device)
-        return _run_pass("VolumeAugment", x, self.roi, self.fill, params, None, out)
+        params = _check_rows(self._who, self._rows, params, x.shape[0], self._cols, x.device)
+        return _run_pass(self._who, x, self.roi, self.fill, out, self._pass, params)
 
     def __call__(self, x: torch.Tensor, step: Optional[int] = None) -> torch.Tensor:
         """The augmented batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
-        The parameters used are kept in `last_params` (a device tensor; None for the identity)."""
+        The table used is kept in `last_params` (a device tensor; None for the identity)."""
         self._check_input(x)
-        own = step is None
-        step = self.step if own else _check_step(step)
+        return _at_step(self._who, self, step, lambda step: self._augmented(x, step))
+
+    def _augmented(self, x, step):
         if self.is_identity(x):
             self.last_params = None
-            out = x
-        else:
-            params = self.params(x.shape[0], step, in_size=tuple(x.shape[1:4]), device=x.device)
-            out = self.apply(x, params)
-            self.last_params = params
-        if own:
-            self.step += 1
+            return x
+        params = self.params(x.shape[0], step, in_size=tuple(x.shape[1:4]), device=x.device)
+        out = self.apply(x, params)
+        self.last_params = params
         return out
+
+
+class VolumeAugment(_WindowTransform):
+    """roi: (Sx, Sy, Sz) of the output window (an int = a cube).  Per sample and per axis: a crop offset uniform on [0, X - S] (monai's
+    RandSpatialCrop with a fixed size), plus an integer translation uniform on [-max_shift, max_shift] (cells of the window that leave
+    the volume get `fill`), a flip with probability flip_prob; per sample an intensity change x * scale + shift with scale / shift
+    uniform on their (lo, hi) ranges.  The T timepoints of a 4D sample share its parameters.  Every option at its default switches that
+    transform off; with the roi equal to the input size as well, the instance is the identity and `__call__` launches nothing.
+
+    A row of `params` (int32 [B, 8]) is {ox, oy, oz, flip bits, bits of scale, bits of shift, 0, 0}.  seed, rank and the step index
+    decide every draw (see nv_augment_params in the header): the same triple reproduces a batch, two ranks with one seed draw different
+    parameters.  `step` counts the calls of this instance unless it is given."""
+    _cols, _rows, _draw, _pass = 8, "params", "nv_augment_params", "nv_augment_apply"
+
+    def __init__(self, roi, flip_prob=(0, 0, 0), max_shift=(0, 0, 0), scale=(1, 1), shift=(0, 0), fill: float = 0.0, seed: int = 0,
+                 rank: int = 0):
+        self._set_window(roi)
+        self._set_flips(flip_prob)
+        self.max_shift = _triple(self._who, max_shift, "max_shift", int)
+        if any(m < 0 or m >= 2 ** 30 for m in self.max_shift):
+            raise ValueError(f"{self._who}: max_shift must lie in [0, 2^30), got {self.max_shift}")
+        self._set_shared(scale, shift, fill, seed, rank)
+
+    def _transforms_off(self) -> bool:
+        return self._shared_off() and all(m == 0 for m in self.max_shift)
+
+    def _config(self, in_size):
+        return AugmentConfig(ctypes.sizeof(AugmentConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi),
+                             (ctypes.c_int * 3)(*self.max_shift), (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1],
+                             self.shift[0], self.shift[1])
 
 
 class AffineConfig(ctypes.Structure):
@@ -239,7 +269,7 @@ class AffineConfig(ctypes.Structure):
 AFFINE_COLS = 16     # int32 columns of a row of nv_affine_params
 
 
-class VolumeAffine:
+class VolumeAffine(_WindowTransform):
     """Random rotation, zoom and sub-voxel translation on the device (monai's RandAffine / RandRotate / RandZoom), together with the crop,
     the flips and the intensity change of VolumeAugment, as ONE trilinear gather pass (nv_affine_apply).  roi: (Sx, Sy, Sz) of the output
     window (an int = a cube).  Per sample: a crop offset uniform on [0, X - S] per axis; with probability `prob` a rotation about the
@@ -250,103 +280,49 @@ class VolumeAffine:
     share its parameters.  Every option at its default switches that transform off; with the roi equal to the input size as well the
     instance is the identity and `__call__` launches nothing.  A sample that `prob` leaves out is the bit copy VolumeAugment would write.
 
-    seed, rank and the step index decide every draw (nv_affine_params in the header; a hash domain of its own, so a VolumeAugment or
-    VolumeMix with the same seed draws independently).  `step` counts the calls of this instance unless it is given."""
+    A row of `params` (int32 [B, 16]) is the fp32 bits of the 3 x 4 map output cell -> source coordinate (M_a0, M_a1, M_a2, m_a3 for
+    a = x, y, z), the bits of scale and shift, flags (bits 0 .. 2 the flips, bit 3 "affine applied"), 0.  seed, rank and the step index
+    decide every draw (nv_affine_params in the header; a hash domain of its own, so a VolumeAugment or VolumeMix with the same seed
+    draws independently).  `step` counts the calls of this instance unless it is given."""
+    _cols, _rows, _draw, _pass = AFFINE_COLS, "table", "nv_affine_params", "nv_affine_apply"
 
     def __init__(self, roi, rotate=0.0, zoom=(1, 1), isotropic: bool = True, translate=0.0, prob: float = 1.0, flip_prob=(0, 0, 0), scale=(1, 1),
                  shift=(0, 0), fill: float = 0.0, seed: int = 0, rank: int = 0):
-        self.roi = _triple(roi, "roi", int)
-        if any(s <= 0 for s in self.roi):
-            raise ValueError(f"VolumeAffine: roi must be positive, got {self.roi}")
-        self.rotate = _triple(rotate, "rotate", float)
+        self._set_window(roi)
+        self.rotate = _triple(self._who, rotate, "rotate", float)
         if any(not (abs(r) <= 180.0) for r in self.rotate):
-            raise ValueError(f"VolumeAffine: rotate must lie in [-180, 180] degrees, got {self.rotate}")
+            raise ValueError(f"{self._who}: rotate must lie in [-180, 180] degrees, got {self.rotate}")
         try:
             lo, hi = zoom
         except (TypeError, ValueError):
-            raise TypeError(f"VolumeAffine: zoom must be a pair (lo, hi) of numbers, got {zoom!r}") from None
+            raise TypeError(f"{self._who}: zoom must be a pair (lo, hi) of numbers, got {zoom!r}") from None
         if any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in (lo, hi)):
-            raise TypeError(f"VolumeAffine: zoom must be a pair (lo, hi) of numbers, got {zoom!r}")
+            raise TypeError(f"{self._who}: zoom must be a pair (lo, hi) of numbers, got {zoom!r}")
         if not (0.0 < lo <= hi <= 16.0):
-            raise ValueError(f"VolumeAffine: zoom must satisfy 0 < lo <= hi <= 16, got {zoom!r}")
+            raise ValueError(f"{self._who}: zoom must satisfy 0 < lo <= hi <= 16, got {zoom!r}")
         self.zoom = (float(lo), float(hi))
         if not isinstance(isotropic, bool):
-            raise TypeError(f"VolumeAffine: isotropic must be true or false, got {isotropic!r}")
+            raise TypeError(f"{self._who}: isotropic must be true or false, got {isotropic!r}")
         self.isotropic = isotropic
-        self.translate = _triple(translate, "translate", float)
+        self.translate = _triple(self._who, translate, "translate", float)
         if any(not (0.0 <= t < math.inf) for t in self.translate):
-            raise ValueError(f"VolumeAffine: translate must be finite and not negative, got {self.translate}")
+            raise ValueError(f"{self._who}: translate must be finite and not negative, got {self.translate}")
         if isinstance(prob, bool) or not isinstance(prob, (int, float)):
-            raise TypeError(f"VolumeAffine: prob must be a number, got {prob!r}")
+            raise TypeError(f"{self._who}: prob must be a number, got {prob!r}")
         if not (0.0 <= float(prob) <= 1.0):
-            raise ValueError(f"VolumeAffine: prob {prob} outside [0, 1]")
+            raise ValueError(f"{self._who}: prob {prob} outside [0, 1]")
         self.prob = float(prob)
-        self.flip_prob = _triple(flip_prob, "flip_prob", float)
-        if any(not (0.0 <= p <= 1.0) for p in self.flip_prob):
-            raise ValueError(f"VolumeAffine: flip probabilities must lie in [0, 1], got {self.flip_prob}")
-        self.scale = _range(scale, "scale")
-        self.shift = _range(shift, "shift")
-        self.fill = float(fill)
-        _check_seed_rank("VolumeAffine", seed, rank)
-        self.seed, self.rank = seed, rank
-        self.step = 0                      # the step index the next __call__ without `step=` draws for
-        self.last_params: Optional[torch.Tensor] = None
+        self._set_flips(flip_prob)
+        self._set_shared(scale, shift, fill, seed, rank)
 
-    # ------------------------------------------------------------------ checks
     def _transforms_off(self) -> bool:
         still = self.prob == 0.0 or (all(r == 0.0 for r in self.rotate) and self.zoom == (1.0, 1.0) and all(t == 0.0 for t in self.translate))
-        return still and all(p == 0.0 for p in self.flip_prob) and self.scale == (1.0, 1.0) and self.shift == (0.0, 0.0)
+        return still and self._shared_off()
 
-    def _check_input(self, x: torch.Tensor):
-        _check_volume("VolumeAffine", "augmentation", x, self.roi)
-
-    def is_identity(self, x: torch.Tensor) -> bool:
-        """No transform is on and the roi is the input's spatial size: __call__ returns x itself."""
-        return self._transforms_off() and tuple(x.shape[1:4]) == self.roi
-
-    # ------------------------------------------------------------------ the two launches
-    def params(self, B: int, step: int, in_size: Optional[Sequence[int]] = None, device=None) -> torch.Tensor:
-        """int32 [B, 16] on the device for step `step`: the fp32 bits of the 3 x 4 map output cell -> source coordinate (M_a0, M_a1, M_a2,
-        m_a3 for a = x, y, z), the bits of scale and shift, flags (bits 0 .. 2 the flips, bit 3 "affine applied"), 0.
-        in_size: (X, Y, Z) of the volumes the window is cut from (default: the roi itself - no room to crop)."""
-        step = _check_step(step)
-        in_size = self.roi if in_size is None else _triple(in_size, "in_size", int)
-        if any(s > n for s, n in zip(self.roi, in_size)):
-            raise ValueError(f"VolumeAffine: roi {self.roi} is larger than the input {tuple(in_size)}")
-        device = _draw_target("VolumeAffine", B, device)
-        out = torch.empty((B, AFFINE_COLS), dtype=torch.int32, device=device)
-        cfg = AffineConfig(ctypes.sizeof(AffineConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi), (ctypes.c_double * 3)(*self.rotate),
-                           self.zoom[0], self.zoom[1], int(self.isotropic), (ctypes.c_double * 3)(*self.translate), self.prob,
-                           (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1], self.shift[0], self.shift[1])
-        with torch.cuda.device(device):
-            check(lib.nv_affine_params(ctypes.byref(cfg), self.seed, step, self.rank, B, out.data_ptr(), torch.cuda.current_stream().cuda_stream),
-                  "nv_affine_params")
-        return out
-
-    def apply(self, x: torch.Tensor, table: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x [B, X, Y, Z] or [B, X, Y, Z, T] float32 on the device, dense or a strided view; table int32 [B, 16] (as `params` returns it, or
-        written by hand: rows may hold anything).  Returns the dense [B, Sx, Sy, Sz(, T)] batch; a caller-supplied `out` of that shape is
-        dense and must not overlap x."""
-        self._check_input(x)
-        table = _check_rows("VolumeAffine", "table", table, x.shape[0], AFFINE_COLS, x.device)
-        return _run_pass("VolumeAffine", x, self.roi, self.fill, table, None, out, affine=True)
-
-    def __call__(self, x: torch.Tensor, step: Optional[int] = None) -> torch.Tensor:
-        """The augmented batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
-        The table used is kept in `last_params` (a device tensor; None for the identity)."""
-        self._check_input(x)
-        own = step is None
-        step = self.step if own else _check_step(step)
-        if self.is_identity(x):
-            self.last_params = None
-            out = x
-        else:
-            table = self.params(x.shape[0], step, in_size=tuple(x.shape[1:4]), device=x.device)
-            out = self.apply(x, table)
-            self.last_params = table
-        if own:
-            self.step += 1
-        return out
+    def _config(self, in_size):
+        return AffineConfig(ctypes.sizeof(AffineConfig), (ctypes.c_int * 3)(*in_size), (ctypes.c_int * 3)(*self.roi), (ctypes.c_double * 3)(*self.rotate),
+                            self.zoom[0], self.zoom[1], int(self.isotropic), (ctypes.c_double * 3)(*self.translate), self.prob,
+                            (ctypes.c_double * 3)(*self.flip_prob), self.scale[0], self.scale[1], self.shift[0], self.shift[1])
 
 
 def center_window(x: torch.Tensor, roi: Sequence[int]) -> torch.Tensor:
@@ -411,8 +387,8 @@ class VolumeMix:
 
     def params(self, B: int, step: int, roi, device=None) -> torch.Tensor:
         """int32 [B, 12] on the device for step `step`; roi: (Sx, Sy, Sz) of the batch that will be mixed (the CutMix box lives in it)."""
-        step = _check_step(step)
-        roi = _triple(roi, "roi", int)
+        step = _check_step("VolumeMix", step)
+        roi = _triple("VolumeMix", roi, "roi", int)
         if any(s <= 0 for s in roi):
             raise ValueError(f"VolumeMix: roi must be positive, got {roi}")
         device = _draw_target("VolumeMix", B, device)
@@ -436,14 +412,14 @@ class VolumeMix:
         if isinstance(augment, VolumeAffine):
             window = augment.apply(x, augment_params)
             mix = _check_rows("VolumeMix", "mix", mix, x.shape[0], MIX_COLS, x.device)
-            return _run_pass("VolumeMix", window, augment.roi, 0.0, None, mix, out)
+            return _run_pass("VolumeMix", window, augment.roi, 0.0, out, "nv_augment_mix", None, mix)
         roi = None if augment is None else augment.roi
         _check_volume("VolumeMix", "mix", x, roi)
         B = x.shape[0]
         mix = _check_rows("VolumeMix", "mix", mix, B, MIX_COLS, x.device)
         if augment_params is not None:
             augment_params = _check_rows("VolumeMix", "augment_params", augment_params, B, 8, x.device)
-        return _run_pass("VolumeMix", x, roi or tuple(x.shape[1:4]), 0.0 if augment is None else augment.fill, augment_params, mix, out)
+        return _run_pass("VolumeMix", x, roi or tuple(x.shape[1:4]), 0.0 if augment is None else augment.fill, out, "nv_augment_mix", augment_params, mix)
 
     def __call__(self, x: torch.Tensor, step: Optional[int] = None, augment: Union[VolumeAugment, VolumeAffine, None] = None) -> torch.Tensor:
         """The mixed batch for this instance's running step (which then advances by one), or for `step` if given (the counter stays).
@@ -452,26 +428,24 @@ class VolumeMix:
         (a device tensor; None for the identity)."""
         if augment is not None and not isinstance(augment, (VolumeAugment, VolumeAffine)):
             raise TypeError(f"VolumeMix: augment must be a VolumeAugment or a VolumeAffine, got {type(augment).__name__}")
-        own = step is None
-        step = self.step if own else _check_step(step)
+        return _at_step("VolumeMix", self, step, lambda step: self._mixed(x, step, augment))
+
+    def _mixed(self, x, step, augment):
         self._check_input(x)
         if self.is_identity():
             self.last_mix = None
-            out = x if augment is None else augment(x, step=step)
-        else:
-            B = x.shape[0]
-            if augment is None or augment.is_identity(x):
-                aug, rows, roi = None, None, tuple(x.shape[1:4])
-                if augment is not None:
-                    augment._check_input(x)
-                    augment.last_params = None
-            else:
+            return x if augment is None else augment(x, step=step)
+        B = x.shape[0]
+        if augment is None or augment.is_identity(x):
+            aug, rows, roi = None, None, tuple(x.shape[1:4])
+            if augment is not None:
                 augment._check_input(x)
-                aug, roi = augment, augment.roi
-                rows = augment.last_params = augment.params(B, step, in_size=tuple(x.shape[1:4]), device=x.device)
-            mix = self.params(B, step, roi, device=x.device)
-            out = self.apply(x, mix, augment=aug, augment_params=rows)
-            self.last_mix = mix
-        if own:
-            self.step += 1
+                augment.last_params = None
+        else:
+            augment._check_input(x)
+            aug, roi = augment, augment.roi
+            rows = augment.last_params = augment.params(B, step, in_size=tuple(x.shape[1:4]), device=x.device)
+        mix = self.params(B, step, roi, device=x.device)
+        out = self.apply(x, mix, augment=aug, augment_params=rows)
+        self.last_mix = mix
         return out

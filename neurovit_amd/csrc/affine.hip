@@ -7,7 +7,7 @@
 //                      (the rule is in the header; tests/affine_ref.py restates it)
 //   nv_affine_apply    src fp32 [B, X, Y, Z, T] (any strides) + table -> out fp32 [B, Sx, Sy, Sz, T] dense
 //
-// The work split is that of augment.hip: a workgroup owns AF_SPAN consecutive elements of one output plane (b, i), stores go out in 16-byte
+// The work split is that of augment.hip: a workgroup owns PASS_SPAN consecutive elements of one output plane (b, i), stores go out in 16-byte
 // groups at any alignment of the plane (split_span), and the coordinates of every cell are formed from its indices (never incrementally).
 // Corners are fetched straight through the vector cache - under the small rotations of real use neighbouring cells share most of
 // theirs - and all of a thread's corners before it looks at any: the fetch is free of branches, so the loads overlap.  Three paths:
@@ -22,13 +22,12 @@
 // The arithmetic is fp32, every operation rounded on its own (contraction is off for the whole file), in the order the header spells out;
 // voxels move as 32-bit patterns wherever no arithmetic touches them.  The range tests happen on the float coordinate BEFORE it is
 // converted: no index is formed from a NaN, an infinity or a value outside [-1, N).  No atomics, every output element is written once.
-#include "attr_common.h"
+// The draw rule, the intensity change, the geometry and the host-side checks are those of augment.hip: augment_common.h.
+#include "augment_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int AF_THREADS = 256;
-constexpr int AF_SPAN = 4096;            // elements of one output plane a workgroup owns: four 16-byte groups per thread
 constexpr int AF_COLS = 16;
 constexpr int AF_MAX_DIM = 1 << 24;      // every index of the volume is exact in fp32
 
@@ -42,13 +41,6 @@ struct AffDraw {
   float scale_lo, scale_hi, shift_lo, shift_hi;
 };
 
-__device__ __forceinline__ int aff_below(uint64_t h, unsigned n) { return (int)(((h >> 32) * (uint64_t)n) >> 32); }
-__device__ __forceinline__ float aff_between(uint64_t h, float lo, float hi) {
-  const float u = (float)(unsigned)(h >> 40) * 0x1p-24f;   // 24 bits: exact
-  const float width = hi - lo;
-  const float part = width * u;
-  return lo + part;
-}
 __device__ __forceinline__ double aff_real(uint64_t h) { return (double)(h >> 11) * 0x1p-53; }         // 53 bits: exact
 
 // c = a b, every sum from the left
@@ -60,22 +52,20 @@ __device__ __forceinline__ void mat3(const double (&a)[3][3], const double (&b)[
 }
 
 // One thread per sample: draw d of sample b at step s hashes the counter ((s 2^32 + b) 32 + d) mod 2^64 in the affine domain of the rank's seed.
-__global__ __launch_bounds__(AF_THREADS) void affine_params_kernel(AffDraw cfg, uint64_t seed, uint64_t step, uint64_t rank, int B, int* __restrict__ table) {
-  const int b = blockIdx.x * AF_THREADS + threadIdx.x;
+__global__ __launch_bounds__(PASS_THREADS) void affine_params_kernel(AffDraw cfg, uint64_t seed, uint64_t step, uint64_t rank, int B, int* __restrict__ table) {
+  const int b = blockIdx.x * PASS_THREADS + threadIdx.x;
   if (b >= B) return;
-  const uint64_t seed_f = nv_hash64(nv_hash64(seed, rank), 0x414646ull);
-  const uint64_t counter = ((step << 32) + (uint64_t)b) * 32u;
-  auto h = [&](int d) { return nv_hash64(seed_f, counter + (uint64_t)d); };
+  const SampleDraws h(seed, rank, AFFINE_DOMAIN, AFFINE_STRIDE, step, b);
   int flags = 0;
   double o[3], f[3], theta[3] = {0.0, 0.0, 0.0}, zoom[3] = {1.0, 1.0, 1.0}, t[3] = {0.0, 0.0, 0.0};
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    o[a] = (double)aff_below(h(a), cfg.crop_n[a]);
-    const bool flip = (unsigned)(h(3 + a) >> 48) < cfg.flip_thresh[a];
+    o[a] = (double)draw_below(h(a), cfg.crop_n[a]);
+    const bool flip = draw_chance(h(3 + a), cfg.flip_thresh[a]);
     if (flip) flags |= 1 << a;
     f[a] = flip ? -1.0 : 1.0;
   }
-  const bool applied = (unsigned)(h(6) >> 48) < cfg.prob_thresh;
+  const bool applied = draw_chance(h(6), cfg.prob_thresh);
   double R[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
   if (applied) {
     flags |= 8;
@@ -105,8 +95,8 @@ __global__ __launch_bounds__(AF_THREADS) void affine_params_kernel(AffDraw cfg, 
     for (int q = 0; q < 3; ++q) row[4 * a + q] = __float_as_int((float)(M[q] + 0.0));       // (+ 0.0: a zero is +0.0)
     row[4 * a + 3] = __float_as_int((float)(m3 + 0.0));
   }
-  row[12] = __float_as_int(aff_between(h(16), cfg.scale_lo, cfg.scale_hi));
-  row[13] = __float_as_int(aff_between(h(17), cfg.shift_lo, cfg.shift_hi));
+  row[12] = __float_as_int(draw_between(h(16), cfg.scale_lo, cfg.scale_hi));
+  row[13] = __float_as_int(draw_between(h(17), cfg.shift_lo, cfg.shift_hi));
   row[14] = flags;
   row[15] = 0;
 #pragma unroll
@@ -114,15 +104,11 @@ __global__ __launch_bounds__(AF_THREADS) void affine_params_kernel(AffDraw cfg, 
 }
 
 // ------------------------------------------------------------------------------------------------ the pass
-struct AffGeom {
-  int B, X, Y, Z, T, Sx, Sy, Sz;
-  long st_b, st_x, st_y, st_z, st_t;     // element strides of src
-};
-
 // A sample's row: the map, the intensity change, and whether all twelve numbers are integers (then no cell has a fraction)
 struct AffRow {
-  float m[12], scale, shift;
-  bool copy, integer;
+  float m[12];
+  Intensity tone;
+  bool integer;
 
   __device__ __forceinline__ void init(const int* table, int b) {
     const int* row = table + (long)AF_COLS * b;
@@ -132,8 +118,8 @@ struct AffRow {
       m[q] = __int_as_float(row[q]);
       integer = integer && fabsf(m[q]) <= 16777216.0f && m[q] == floorf(m[q]);
     }
-    scale = __int_as_float(row[12]); shift = __int_as_float(row[13]);
-    copy = scale == 1.0f && shift == 0.0f;
+    tone.scale = __int_as_float(row[12]); tone.shift = __int_as_float(row[13]);
+    tone.settle();
   }
   // the source coordinate along the axis of m[4 a ..] of output cell (i, j, k)
   __device__ __forceinline__ float coord(int a, int i, int j, int k) const {
@@ -141,11 +127,6 @@ struct AffRow {
     const float ij = pi + pj;
     const float ijk = ij + pk;
     return ijk + m[4 * a + 3];
-  }
-  __device__ __forceinline__ unsigned shade(unsigned u) const {
-    if (copy) return u;
-    const float v = __uint_as_float(u) * scale;
-    return __float_as_uint(v + shift);
   }
 };
 
@@ -180,7 +161,7 @@ __device__ __forceinline__ unsigned lerp_bits(unsigned a, unsigned b, float w) {
 // replaced by a select - so the loads of a thread's four cells are all in flight together instead of each waiting behind a branch
 // (a gather is bound by the latency of its loads long before it is bound by their bytes).  An integer row has one corner per cell.
 template <int N, bool Integer>
-__device__ __forceinline__ void sample(const unsigned* __restrict__ sb, const AffGeom& g, const AffRow& r, int i, int j, int k, int t0, unsigned fill,
+__device__ __forceinline__ void sample(const unsigned* __restrict__ sb, const PassGeom& g, const AffRow& r, int i, int j, int k, int t0, unsigned fill,
                                        bool run16, unsigned (&v)[N]) {
   constexpr int U = Integer ? 1 : 2;                       // corners per axis
   const AffAxis ax = axis_of<Integer>(r.coord(0, i, j, k), g.X), ay = axis_of<Integer>(r.coord(1, i, j, k), g.Y), az = axis_of<Integer>(r.coord(2, i, j, k), g.Z);
@@ -235,16 +216,16 @@ __device__ __forceinline__ void sample(const unsigned* __restrict__ sb, const Af
     }
   }
 #pragma unroll
-  for (int n = 0; n < N; ++n) v[n] = any_in ? r.shade(c[0][0][0][n]) : fill;
+  for (int n = 0; n < N; ++n) v[n] = any_in ? r.tone.shade(c[0][0][0][n]) : fill;
 }
 
-// One workgroup of the grid (B Sx, ceil(Sy Sz T / AF_SPAN)) under its sample's row
+// One workgroup of the grid (B Sx, ceil(Sy Sz T / PASS_SPAN)) under its sample's row
 template <bool Integer>
-__device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, const AffGeom& g, const AffRow& r, int b, int i, unsigned fill,
+__device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, const PassGeom& g, const AffRow& r, int b, int i, unsigned fill,
                                             unsigned* __restrict__ out, unsigned* tile) {
   const int tid = threadIdx.x;
   const int T = g.T, L = g.Sz * T, P = g.Sy * L;           // cells of one output row (j) and of the plane
-  const int e0 = blockIdx.y * AF_SPAN, len = min(AF_SPAN, P - e0);
+  const int e0 = blockIdx.y * PASS_SPAN, len = min(PASS_SPAN, P - e0);
   const long first = (long)blockIdx.x * P + e0;
   unsigned* o = out + first;
   const Span s = split_span(first, len);
@@ -261,8 +242,8 @@ __device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, co
     sample<1, Integer>(sb, g, r, i, j, k, c - k * T, fill, false, v);
     return v[0];
   };
-  for (int e = tid; e < s.head; e += AF_THREADS) o[e] = single(e);
-  for (int e = s.tail + tid; e < len; e += AF_THREADS) o[e] = single(e);
+  for (int e = tid; e < s.head; e += PASS_THREADS) o[e] = single(e);
+  for (int e = s.tail + tid; e < len; e += PASS_THREADS) o[e] = single(e);
   if (!Integer && T == 1) {
     // A resampled volume.  Four consecutive cells per lane would make every corner load of a wave a 16-byte-strided gather over a
     // kilobyte of each source row; instead lane l of a wave fetches cells l, l + 64, l + 128, l + 192 of the wave's 256 - neighbours in
@@ -270,7 +251,7 @@ __device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, co
     // count is uniform; a cell past the end is computed as the last one (no branch in front of the loads) and not stored.
     const int wave = tid >> 6, lane = tid & 63;
     unsigned* wt = tile + 256 * wave;
-    for (int q0 = 0; q0 < s.groups; q0 += AF_THREADS) {
+    for (int q0 = 0; q0 < s.groups; q0 += PASS_THREADS) {
       const int eb = s.head + 4 * (q0 + 64 * wave);        // the wave's first cell
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -286,7 +267,7 @@ __device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, co
     }
     return;
   }
-  for (int q = tid; q < s.groups; q += AF_THREADS) {
+  for (int q = tid; q < s.groups; q += PASS_THREADS) {
     const int e = s.head + 4 * q;
     const int j = (e0 + e) / L, c = (e0 + e) - j * L;
     u32x4 v;
@@ -309,7 +290,7 @@ __device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, co
           const u32x4 w = load4(p, is_aligned16(p));
           v = dz < 0 ? u32x4{w[3], w[2], w[1], w[0]} : w;
 #pragma unroll
-          for (int m = 0; m < 4; ++m) v[m] = r.shade(v[m]);
+          for (int m = 0; m < 4; ++m) v[m] = r.tone.shade(v[m]);
           done = true;
         }
       }
@@ -322,10 +303,10 @@ __device__ __forceinline__ void affine_pass(const unsigned* __restrict__ src, co
   }
 }
 
-__global__ __launch_bounds__(AF_THREADS) void affine_apply_kernel(const unsigned* __restrict__ src, AffGeom g, const int* __restrict__ table, unsigned fill,
-                                                                  unsigned* __restrict__ out) {
+__global__ __launch_bounds__(PASS_THREADS) void affine_apply_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ table, unsigned fill,
+                                                                    unsigned* __restrict__ out) {
   const int b = blockIdx.x / g.Sx, i = blockIdx.x - b * g.Sx;
-  __shared__ __attribute__((aligned(16))) unsigned tile[4 * AF_THREADS];      // a resampled volume's groups on their way from cell order to store order
+  __shared__ __attribute__((aligned(16))) unsigned tile[4 * PASS_THREADS];      // a resampled volume's groups on their way from cell order to store order
   AffRow r;
   r.init(table, b);
   if (r.integer) affine_pass<true>(src, g, r, b, i, fill, out, tile);      // (uniform over the workgroup)
@@ -340,33 +321,24 @@ extern "C" int nv_affine_params(const nv_affine_config* cfg, unsigned long seed,
                cfg->struct_size, (int)sizeof(nv_affine_config));
   NV_CHECK_ARG(nv_aligned(table, 4), "nv_affine_params: table 4-byte aligned");
   AffDraw d;
+  if (const int rc = window_draw_setup("nv_affine_params", *cfg, d)) return rc;
   for (int a = 0; a < 3; ++a) {
-    const int X = cfg->in_size[a], S = cfg->roi[a];
-    const double p = cfg->flip_prob[a], deg = cfg->rotate_deg[a], tr = cfg->translate[a];
-    NV_CHECK_ARG(S > 0 && X > 0, "nv_affine_params: axis %d: input %d and roi %d must be positive", a, X, S);
-    NV_CHECK_ARG(S <= X, "nv_affine_params: axis %d: roi %d is larger than the input %d", a, S, X);
+    const int X = cfg->in_size[a];
+    const double deg = cfg->rotate_deg[a], tr = cfg->translate[a];
     NV_CHECK_ARG(X <= AF_MAX_DIM, "nv_affine_params: axis %d: input %d beyond 2^24", a, X);
-    NV_CHECK_ARG(p >= 0.0 && p <= 1.0, "nv_affine_params: axis %d: flip probability %g outside [0, 1]", a, p);
     NV_CHECK_ARG(deg >= -180.0 && deg <= 180.0, "nv_affine_params: axis %d: rotate_deg %g outside [-180, 180]", a, deg);
     NV_CHECK_ARG(isfinite(tr) && tr >= 0.0, "nv_affine_params: axis %d: translate %g must be finite and not negative", a, tr);
-    d.crop_n[a] = (unsigned)(X - S) + 1u;
-    d.half[a] = (double)(S - 1) / 2.0;
+    d.half[a] = (double)(cfg->roi[a] - 1) / 2.0;
     d.rotate_deg[a] = deg;
     d.translate[a] = tr;
-    d.flip_thresh[a] = (unsigned)(p * 65536.0);
   }
   NV_CHECK_ARG(cfg->zoom_lo > 0.0 && cfg->zoom_lo <= cfg->zoom_hi && cfg->zoom_hi <= 16.0, "nv_affine_params: zoom [%g, %g] must satisfy 0 < lo <= hi <= 16",
                cfg->zoom_lo, cfg->zoom_hi);
   NV_CHECK_ARG(cfg->prob >= 0.0 && cfg->prob <= 1.0, "nv_affine_params: prob %g outside [0, 1]", cfg->prob);
-  NV_CHECK_ARG(cfg->scale_lo <= cfg->scale_hi && cfg->shift_lo <= cfg->shift_hi && isfinite(cfg->scale_lo) && isfinite(cfg->scale_hi) &&
-                   isfinite(cfg->shift_lo) && isfinite(cfg->shift_hi),
-               "nv_affine_params: intensity ranges must be finite with lo <= hi (scale [%g, %g], shift [%g, %g])", cfg->scale_lo, cfg->scale_hi,
-               cfg->shift_lo, cfg->shift_hi);
   d.zoom_lo = cfg->zoom_lo; d.zoom_hi = cfg->zoom_hi;
   d.isotropic = cfg->isotropic != 0;
-  d.prob_thresh = (unsigned)(cfg->prob * 65536.0);
-  d.scale_lo = cfg->scale_lo; d.scale_hi = cfg->scale_hi; d.shift_lo = cfg->shift_lo; d.shift_hi = cfg->shift_hi;
-  hipLaunchKernelGGL(affine_params_kernel, dim3((B + AF_THREADS - 1) / AF_THREADS), dim3(AF_THREADS), 0, (hipStream_t)stream, d, (uint64_t)seed,
+  d.prob_thresh = chance_thresh(cfg->prob);
+  hipLaunchKernelGGL(affine_params_kernel, dim3((B + PASS_THREADS - 1) / PASS_THREADS), dim3(PASS_THREADS), 0, (hipStream_t)stream, d, (uint64_t)seed,
                      (uint64_t)step, (uint64_t)rank, B, table);
   NV_CHECK_LAUNCH("nv_affine_params");
   return NV_OK;
@@ -375,18 +347,10 @@ extern "C" int nv_affine_params(const nv_affine_config* cfg, unsigned long seed,
 extern "C" int nv_affine_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* table, const int* roi3, float fill,
                                float* out, void* stream) {
   const char* who = "nv_affine_apply";
-  NV_CHECK_ARG(src && strides5 && in3 && table && roi3 && out && B > 0 && T > 0, "%s: bad arguments (null pointer, or B / T not positive)", who);
-  AffGeom g;
-  g.B = B; g.X = in3[0]; g.Y = in3[1]; g.Z = in3[2]; g.T = T; g.Sx = roi3[0]; g.Sy = roi3[1]; g.Sz = roi3[2];
-  NV_CHECK_ARG(g.X > 0 && g.Y > 0 && g.Z > 0 && g.Sx > 0 && g.Sy > 0 && g.Sz > 0, "%s: input %d x %d x %d and roi %d x %d x %d must be positive", who, g.X, g.Y,
-               g.Z, g.Sx, g.Sy, g.Sz);
-  NV_CHECK_ARG(g.Sx <= g.X && g.Sy <= g.Y && g.Sz <= g.Z, "%s: roi %d x %d x %d is larger than the input %d x %d x %d", who, g.Sx, g.Sy, g.Sz, g.X, g.Y, g.Z);
+  PassLaunch l;
+  if (const int rc = pass_setup(who, "table", src, strides5, B, in3, T, table, nullptr, roi3, fill, out, l)) return rc;
+  const PassGeom& g = l.g;
   NV_CHECK_ARG(g.X <= AF_MAX_DIM && g.Y <= AF_MAX_DIM && g.Z <= AF_MAX_DIM, "%s: input %d x %d x %d beyond 2^24 cells along an axis", who, g.X, g.Y, g.Z);
-  const long planes = (long)B * g.Sx, P = (long)g.Sy * g.Sz * T, spans = (P + AF_SPAN - 1) / AF_SPAN;
-  NV_CHECK_ARG(planes < (1L << 31) && spans <= 65535 && (long)g.Z * T < (1L << 31),
-               "%s: %ld output planes of %ld cells beyond one launch (at most 2^31 - 1 planes of %ld cells)", who, planes, P, 65535L * AF_SPAN);
-  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(src, 4) && nv_aligned(table, 4), "%s: out 16-byte aligned, src and table 4-byte aligned", who);
-  g.st_b = strides5[0]; g.st_x = strides5[1]; g.st_y = strides5[2]; g.st_z = strides5[3]; g.st_t = strides5[4];
   // the elements of src that the strides can reach against the dense output: a gather that overwrote its own source would race
   long lowest = 0, highest = 0;
   const long extent[5] = {B, g.X, g.Y, g.Z, T};
@@ -394,12 +358,9 @@ extern "C" int nv_affine_apply(const float* src, const long* strides5, int B, co
     const long reach = (extent[a] - 1) * strides5[a];
     if (reach < 0) lowest += reach; else highest += reach;
   }
-  const float* out_end = out + planes * P;
+  const float* out_end = out + (long)B * g.Sx * g.Sy * g.Sz * T;
   NV_CHECK_ARG(out_end <= src + lowest || src + highest < out, "%s: out aliases src", who);
-  union { float f; unsigned u; } fbits;
-  fbits.f = fill;
-  hipLaunchKernelGGL(affine_apply_kernel, dim3((unsigned)planes, (unsigned)spans), dim3(AF_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, table,
-                     fbits.u, (unsigned*)out);
+  hipLaunchKernelGGL(affine_apply_kernel, l.grid, dim3(PASS_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, table, l.fill, (unsigned*)out);
   NV_CHECK_LAUNCH(who);
   return NV_OK;
 }

@@ -9,7 +9,7 @@
 //   nv_augment_mix      the same + mix rows (nv_mix_params, mix.hip; the augmentation rows may be missing) -> out = A_b, (lambda A_b) +
 //                       (mu A_p), or A_p inside the box and A_b outside, each sample under its OWN row
 //
-// Both are one pass body (augment_pass), laid out like nv_mask_patches: a workgroup owns AG_SPAN consecutive elements of one output plane
+// Both are one pass body (augment_pass), laid out like nv_mask_patches: a workgroup owns PASS_SPAN consecutive elements of one output plane
 // (b, i) - Sy Sz T contiguous floats - so the grid follows the rows, not the batch; the 16-byte groups follow the alignment of the plane
 // in `out` (split_span).  A group whose four cells lie in one source row that is contiguous in memory is read with one 16-byte load when
 // the address allows it (load4), backwards under a z flip of a 3D volume; every other group (row ends, window edges, strided sources, a
@@ -18,14 +18,12 @@
 // fetched and every cell takes its side (x and y are uniform over a group, z is not).  Voxels move as 32-bit patterns; the intensity
 // change and the Mixup blend are separately rounded operations (contraction is off for the whole file), the intensity change skipped
 // altogether for scale 1 / shift 0: that sample is a bit copy.  No atomics, every output element is written once by one thread.
-#include "attr_common.h"
+// The draw rule, the intensity change, the geometry and the host-side checks are those of affine.hip and mix.hip: augment_common.h.
+#include "augment_common.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-constexpr int AG_THREADS = 256;
-constexpr int AG_SPAN = 4096;            // elements of one output plane a workgroup owns: four 16-byte groups per thread
-
 // ------------------------------------------------------------------------------------------------ parameters
 struct AugDraw {
   unsigned crop_n[3];                    // X - Sx + 1: the crop offset is uniform on [0, crop_n)
@@ -34,60 +32,46 @@ struct AugDraw {
   float scale_lo, scale_hi, shift_lo, shift_hi;
 };
 
-__device__ __forceinline__ int draw_below(uint64_t h, unsigned n) { return (int)(((h >> 32) * (uint64_t)n) >> 32); }
-__device__ __forceinline__ float draw_between(uint64_t h, float lo, float hi) {
-  const float u = (float)(unsigned)(h >> 40) * 0x1p-24f;   // 24 bits: exact
-  const float width = hi - lo;
-  const float part = width * u;
-  return lo + part;
-}
-
 // One thread per sample: draw d of sample b at step s hashes the counter ((s 2^32 + b) 16 + d) mod 2^64 under the rank's seed.
-__global__ __launch_bounds__(AG_THREADS) void augment_params_kernel(AugDraw cfg, uint64_t seed, uint64_t step, uint64_t rank, int B, int* __restrict__ params) {
-  const int b = blockIdx.x * AG_THREADS + threadIdx.x;
+__global__ __launch_bounds__(PASS_THREADS) void augment_params_kernel(AugDraw cfg, uint64_t seed, uint64_t step, uint64_t rank, int B, int* __restrict__ params) {
+  const int b = blockIdx.x * PASS_THREADS + threadIdx.x;
   if (b >= B) return;
-  const uint64_t seed_r = nv_hash64(seed, rank);
-  const uint64_t counter = ((step << 32) + (uint64_t)b) * 16u;
+  const SampleDraws h(seed, rank, AUGMENT_DOMAIN, AUGMENT_STRIDE, step, b);
   int row[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    const int crop = draw_below(nv_hash64(seed_r, counter + a), cfg.crop_n[a]);
-    const int move = draw_below(nv_hash64(seed_r, counter + 3 + a), 2u * (unsigned)cfg.max_shift[a] + 1u) - cfg.max_shift[a];
+    const int crop = draw_below(h(a), cfg.crop_n[a]);
+    const int move = draw_below(h(3 + a), 2u * (unsigned)cfg.max_shift[a] + 1u) - cfg.max_shift[a];
     row[a] = crop + move;
-    if ((unsigned)(nv_hash64(seed_r, counter + 6 + a) >> 48) < cfg.flip_thresh[a]) row[3] |= 1 << a;
+    if (draw_chance(h(6 + a), cfg.flip_thresh[a])) row[3] |= 1 << a;
   }
-  row[4] = __float_as_int(draw_between(nv_hash64(seed_r, counter + 9), cfg.scale_lo, cfg.scale_hi));
-  row[5] = __float_as_int(draw_between(nv_hash64(seed_r, counter + 10), cfg.shift_lo, cfg.shift_hi));
+  row[4] = __float_as_int(draw_between(h(9), cfg.scale_lo, cfg.scale_hi));
+  row[5] = __float_as_int(draw_between(h(10), cfg.shift_lo, cfg.shift_hi));
 #pragma unroll
   for (int i = 0; i < 8; ++i) params[8L * b + i] = row[i];
 }
 
 // ------------------------------------------------------------------------------------------------ the pass
-struct PassGeom {
-  int B, X, Y, Z, T, Sx, Sy, Sz;
-  long st_b, st_x, st_y, st_z, st_t;     // element strides of src
-};
-
 // What the pass writes for one sample on output plane i: the cells of A_s, singly or four at a time.  The offsets of a parameter row
 // may be anything: every read is bounds-checked against the volume, and a cell outside it gets `fill`.
 struct Side {
   const unsigned* xp;                    // the source plane (valid when plane_in)
   long oy, oz;
-  bool fy, fz, plane_in, copy, run;
-  float scale, shift;
+  bool fy, fz, plane_in, run;
+  Intensity tone;
   unsigned fill;
 
   __device__ __forceinline__ void init(const unsigned* src, const PassGeom& g, const int* aug, int s, int i, unsigned fill_bits) {
     long ox = 0;
     int flips = 0;
-    oy = 0; oz = 0; scale = 1.0f; shift = 0.0f;
+    oy = 0; oz = 0; tone.scale = 1.0f; tone.shift = 0.0f;
     if (aug) {                                             // (a NULL table is identity rows)
       const int* row = aug + 8L * s;
       ox = row[0]; oy = row[1]; oz = row[2]; flips = row[3];
-      scale = __int_as_float(row[4]); shift = __int_as_float(row[5]);
+      tone.scale = __int_as_float(row[4]); tone.shift = __int_as_float(row[5]);
     }
     fy = flips & 2; fz = flips & 4;
-    copy = scale == 1.0f && shift == 0.0f;
+    tone.settle();
     fill = fill_bits;
     const long sx = ox + ((flips & 1) ? g.Sx - 1 - i : i);
     plane_in = sx >= 0 && sx < g.X;
@@ -95,16 +79,11 @@ struct Side {
     // a source row is one run of memory: ascending for a series with time innermost, in either direction for a volume
     run = g.T > 1 ? (g.st_t == 1 && g.st_z == g.T && !fz) : g.st_z == 1;
   }
-  __device__ __forceinline__ unsigned shade(unsigned u) const {
-    if (copy) return u;
-    const float m = __uint_as_float(u) * scale;
-    return __float_as_uint(m + shift);
-  }
   // output cell (j, k, t) of the plane
   __device__ __forceinline__ unsigned cell(const PassGeom& g, int j, int k, int t) const {
     const long sy = oy + (fy ? g.Sy - 1 - j : j), sz = oz + (fz ? g.Sz - 1 - k : k);
     if (!plane_in || sy < 0 || sy >= g.Y || sz < 0 || sz >= g.Z) return fill;
-    return shade(xp[sy * g.st_y + sz * g.st_z + t * g.st_t]);
+    return tone.shade(xp[sy * g.st_y + sz * g.st_z + t * g.st_t]);
   }
   // the four cells c .. c + 3 of output row j (c + 3 < Sz T): one 16-byte load where the source allows it
   __device__ __forceinline__ u32x4 group(const PassGeom& g, int j, int c) const {
@@ -118,7 +97,7 @@ struct Side {
         const u32x4 w = load4(p, is_aligned16(p));
         u32x4 v = fz ? u32x4{w[3], w[2], w[1], w[0]} : w;
 #pragma unroll
-        for (int m = 0; m < 4; ++m) v[m] = shade(v[m]);
+        for (int m = 0; m < 4; ++m) v[m] = tone.shade(v[m]);
         return v;
       }
     }
@@ -133,19 +112,20 @@ struct Side {
 };
 
 // CutMix takes a cell from one side or the other: the side is SELECTED field by field and fetched through one code path, so that lanes
-// inside and outside the box do not run two fetches one after the other.
+// inside and outside the box do not run two fetches one after the other.  (The order of the selects, like the member-by-member writes of
+// `tone` in init, is part of how the kernel is scheduled: profiles/augment_shared_layer.txt.)
 __device__ __forceinline__ Side pick(bool partner, const Side& own, const Side& other) {
   Side s;
   s.xp = partner ? other.xp : own.xp;
   s.oy = partner ? other.oy : own.oy; s.oz = partner ? other.oz : own.oz;
   s.fy = partner ? other.fy : own.fy; s.fz = partner ? other.fz : own.fz;
-  s.plane_in = partner ? other.plane_in : own.plane_in; s.copy = partner ? other.copy : own.copy; s.run = partner ? other.run : own.run;
-  s.scale = partner ? other.scale : own.scale; s.shift = partner ? other.shift : own.shift;
+  s.plane_in = partner ? other.plane_in : own.plane_in; s.tone.copy = partner ? other.tone.copy : own.tone.copy; s.run = partner ? other.run : own.run;
+  s.tone.scale = partner ? other.tone.scale : own.tone.scale; s.tone.shift = partner ? other.tone.shift : own.tone.shift;
   s.fill = own.fill;
   return s;
 }
 
-// One workgroup of the grid (B Sx, ceil(Sy Sz T / AG_SPAN)).  Mix = false is the apply pass: it reads no mix table and has one Side;
+// One workgroup of the grid (B Sx, ceil(Sy Sz T / PASS_SPAN)).  Mix = false is the apply pass: it reads no mix table and has one Side;
 // everything about a partner, the blend and the box exists for Mix = true alone.
 template <bool Mix>
 __device__ __forceinline__ void augment_pass(const unsigned* __restrict__ src, const PassGeom& g, const int* __restrict__ aug, const int* __restrict__ mix,
@@ -153,7 +133,7 @@ __device__ __forceinline__ void augment_pass(const unsigned* __restrict__ src, c
   const int tid = threadIdx.x;
   const int plane = blockIdx.x, b = plane / g.Sx, i = plane - b * g.Sx;
   const int T = g.T, L = g.Sz * T, P = g.Sy * L;           // cells of one output row (j) and of the plane
-  const int e0 = blockIdx.y * AG_SPAN, len = min(AG_SPAN, P - e0);
+  const int e0 = blockIdx.y * PASS_SPAN, len = min(PASS_SPAN, P - e0);
   int mode = 0, y0 = 0, y1 = 0, z0 = 0, z1 = 0, partner = b;
   float lam = 1.0f;
   if constexpr (Mix) {
@@ -175,9 +155,9 @@ __device__ __forceinline__ void augment_pass(const unsigned* __restrict__ src, c
   const Span s = split_span(first, len);
   if (!Mix && !own.plane_in) {                             // (uniform over the workgroup) the whole plane lies outside the volume
     const u32x4 fill4 = {fill, fill, fill, fill};
-    for (int e = tid; e < s.head; e += AG_THREADS) o[e] = fill;
-    for (int e = s.tail + tid; e < len; e += AG_THREADS) o[e] = fill;
-    for (int q = tid; q < s.groups; q += AG_THREADS) *reinterpret_cast<u32x4*>(o + s.head + 4 * q) = fill4;
+    for (int e = tid; e < s.head; e += PASS_THREADS) o[e] = fill;
+    for (int e = s.tail + tid; e < len; e += PASS_THREADS) o[e] = fill;
+    for (int q = tid; q < s.groups; q += PASS_THREADS) *reinterpret_cast<u32x4*>(o + s.head + 4 * q) = fill4;
     return;
   }
   auto blend = [&](unsigned a, unsigned p) {
@@ -190,9 +170,9 @@ __device__ __forceinline__ void augment_pass(const unsigned* __restrict__ src, c
     if (mode == 1) return blend(own.cell(g, j, k, t), other.cell(g, j, k, t));
     return pick(j >= y0 && j < y1 && k >= z0 && k < z1, own, other).cell(g, j, k, t);
   };
-  for (int e = tid; e < s.head; e += AG_THREADS) o[e] = single(e);
-  for (int e = s.tail + tid; e < len; e += AG_THREADS) o[e] = single(e);
-  for (int q = tid; q < s.groups; q += AG_THREADS) {
+  for (int e = tid; e < s.head; e += PASS_THREADS) o[e] = single(e);
+  for (int e = s.tail + tid; e < len; e += PASS_THREADS) o[e] = single(e);
+  for (int q = tid; q < s.groups; q += PASS_THREADS) {
     const int e = s.head + 4 * q;
     const int j = (e0 + e) / L, c = (e0 + e) - j * L;
     u32x4 v;
@@ -228,40 +208,13 @@ __device__ __forceinline__ void augment_pass(const unsigned* __restrict__ src, c
   }
 }
 
-__global__ __launch_bounds__(AG_THREADS) void augment_apply_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ params, unsigned fill,
-                                                                   unsigned* __restrict__ out) {
+__global__ __launch_bounds__(PASS_THREADS) void augment_apply_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ params, unsigned fill,
+                                                                     unsigned* __restrict__ out) {
   augment_pass<false>(src, g, params, nullptr, fill, out);
 }
-__global__ __launch_bounds__(AG_THREADS) void augment_mix_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ aug, const int* __restrict__ mix,
-                                                                 unsigned fill, unsigned* __restrict__ out) {
+__global__ __launch_bounds__(PASS_THREADS) void augment_mix_kernel(const unsigned* __restrict__ src, PassGeom g, const int* __restrict__ aug, const int* __restrict__ mix,
+                                                                   unsigned fill, unsigned* __restrict__ out) {
   augment_pass<true>(src, g, aug, mix, fill, out);
-}
-
-// The checks, the geometry and the launch shape that the two entry points share; `who` is the entry point, for the messages.
-template <bool Mix>
-int launch_pass(const char* who, const float* src, const long* strides5, int B, const int* in3, int T, const int* aug, const int* mix, const int* roi3, float fill,
-                float* out, void* stream) {
-  NV_CHECK_ARG(src && strides5 && in3 && (Mix ? mix : aug) && roi3 && out && B > 0 && T > 0, "%s: bad arguments (null pointer, or B / T not positive)", who);
-  PassGeom g;
-  g.B = B; g.X = in3[0]; g.Y = in3[1]; g.Z = in3[2]; g.T = T; g.Sx = roi3[0]; g.Sy = roi3[1]; g.Sz = roi3[2];
-  NV_CHECK_ARG(g.X > 0 && g.Y > 0 && g.Z > 0 && g.Sx > 0 && g.Sy > 0 && g.Sz > 0, "%s: input %d x %d x %d and roi %d x %d x %d must be positive", who, g.X, g.Y,
-               g.Z, g.Sx, g.Sy, g.Sz);
-  NV_CHECK_ARG(g.Sx <= g.X && g.Sy <= g.Y && g.Sz <= g.Z, "%s: roi %d x %d x %d is larger than the input %d x %d x %d", who, g.Sx, g.Sy, g.Sz, g.X, g.Y, g.Z);
-  const long planes = (long)B * g.Sx, P = (long)g.Sy * g.Sz * T, spans = (P + AG_SPAN - 1) / AG_SPAN;
-  NV_CHECK_ARG(planes < (1L << 31) && spans <= 65535 && (long)g.Z * T < (1L << 31),
-               "%s: %ld output planes of %ld cells beyond one launch (at most 2^31 - 1 planes of %ld cells)", who, planes, P, 65535L * AG_SPAN);
-  NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(src, 4) && nv_aligned(aug, 4) && nv_aligned(mix, 4), "%s: out 16-byte aligned, src and %s 4-byte aligned", who,
-               Mix ? "the two tables" : "params");
-  g.st_b = strides5[0]; g.st_x = strides5[1]; g.st_y = strides5[2]; g.st_z = strides5[3]; g.st_t = strides5[4];
-  union { float f; unsigned u; } fbits;
-  fbits.f = fill;
-  const dim3 grid((unsigned)planes, (unsigned)spans);
-  if constexpr (Mix)
-    hipLaunchKernelGGL(augment_mix_kernel, grid, dim3(AG_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, aug, mix, fbits.u, (unsigned*)out);
-  else
-    hipLaunchKernelGGL(augment_apply_kernel, grid, dim3(AG_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, g, aug, fbits.u, (unsigned*)out);
-  NV_CHECK_LAUNCH(who);
-  return NV_OK;
 }
 }  // namespace
 
@@ -271,23 +224,13 @@ extern "C" int nv_augment_params(const nv_augment_config* cfg, unsigned long see
                cfg->struct_size, (int)sizeof(nv_augment_config));
   NV_CHECK_ARG(nv_aligned(params, 4), "nv_augment_params: params 4-byte aligned");
   AugDraw d;
+  if (const int rc = window_draw_setup("nv_augment_params", *cfg, d)) return rc;
   for (int a = 0; a < 3; ++a) {
-    const int X = cfg->in_size[a], S = cfg->roi[a], m = cfg->max_shift[a];
-    const double p = cfg->flip_prob[a];
-    NV_CHECK_ARG(S > 0 && X > 0, "nv_augment_params: axis %d: input %d and roi %d must be positive", a, X, S);
-    NV_CHECK_ARG(S <= X, "nv_augment_params: axis %d: roi %d is larger than the input %d", a, S, X);
+    const int m = cfg->max_shift[a];
     NV_CHECK_ARG(m >= 0 && m < (1 << 30), "nv_augment_params: axis %d: max_shift %d outside [0, 2^30)", a, m);
-    NV_CHECK_ARG(p >= 0.0 && p <= 1.0, "nv_augment_params: axis %d: flip probability %g outside [0, 1]", a, p);
-    d.crop_n[a] = (unsigned)(X - S) + 1u;
     d.max_shift[a] = m;
-    d.flip_thresh[a] = (unsigned)(p * 65536.0);
   }
-  NV_CHECK_ARG(cfg->scale_lo <= cfg->scale_hi && cfg->shift_lo <= cfg->shift_hi && isfinite(cfg->scale_lo) && isfinite(cfg->scale_hi) &&
-                   isfinite(cfg->shift_lo) && isfinite(cfg->shift_hi),
-               "nv_augment_params: intensity ranges must be finite with lo <= hi (scale [%g, %g], shift [%g, %g])", cfg->scale_lo, cfg->scale_hi,
-               cfg->shift_lo, cfg->shift_hi);
-  d.scale_lo = cfg->scale_lo; d.scale_hi = cfg->scale_hi; d.shift_lo = cfg->shift_lo; d.shift_hi = cfg->shift_hi;
-  hipLaunchKernelGGL(augment_params_kernel, dim3((B + AG_THREADS - 1) / AG_THREADS), dim3(AG_THREADS), 0, (hipStream_t)stream, d, (uint64_t)seed,
+  hipLaunchKernelGGL(augment_params_kernel, dim3((B + PASS_THREADS - 1) / PASS_THREADS), dim3(PASS_THREADS), 0, (hipStream_t)stream, d, (uint64_t)seed,
                      (uint64_t)step, (uint64_t)rank, B, params);
   NV_CHECK_LAUNCH("nv_augment_params");
   return NV_OK;
@@ -295,10 +238,20 @@ extern "C" int nv_augment_params(const nv_augment_config* cfg, unsigned long see
 
 extern "C" int nv_augment_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* params, const int* roi3, float fill,
                                 float* out, void* stream) {
-  return launch_pass<false>("nv_augment_apply", src, strides5, B, in3, T, params, nullptr, roi3, fill, out, stream);
+  const char* who = "nv_augment_apply";
+  PassLaunch l;
+  if (const int rc = pass_setup(who, "params", src, strides5, B, in3, T, params, nullptr, roi3, fill, out, l)) return rc;
+  hipLaunchKernelGGL(augment_apply_kernel, l.grid, dim3(PASS_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, l.g, params, l.fill, (unsigned*)out);
+  NV_CHECK_LAUNCH(who);
+  return NV_OK;
 }
 
 extern "C" int nv_augment_mix(const float* src, const long* strides5, int B, const int* in3, int T, const int* aug, const int* mix, const int* roi3, float fill,
                               float* out, void* stream) {
-  return launch_pass<true>("nv_augment_mix", src, strides5, B, in3, T, aug, mix, roi3, fill, out, stream);
+  const char* who = "nv_augment_mix";
+  PassLaunch l;                            // (the augmentation rows may be missing: identity rows)
+  if (const int rc = pass_setup(who, "the two tables", src, strides5, B, in3, T, mix, aug, roi3, fill, out, l)) return rc;
+  hipLaunchKernelGGL(augment_mix_kernel, l.grid, dim3(PASS_THREADS), 0, (hipStream_t)stream, (const unsigned*)src, l.g, aug, mix, l.fill, (unsigned*)out);
+  NV_CHECK_LAUNCH(who);
+  return NV_OK;
 }

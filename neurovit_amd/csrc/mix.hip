@@ -4,7 +4,8 @@
 //   nv_mix_params    (config, seed, step, rank) -> mix int32 [B, NV_MIX_COLS]: {partner, mode, bits of the pixel lambda, bits of the label
 //                    lambda, tries, x0, x1, y0, y1, z0, z1, 0}, drawn on the device with nv_hash64 in a domain of its own (the rule is in
 //                    the header; tests/mix_ref.py restates it).  lambda ~ Beta(alpha, alpha) by Joehnk's rule in double; the CutMix box in fp32.
-#include "attr_common.h"
+// The counter, the chance test and the box centre are the draw rule of augment.hip and affine.hip: augment_common.h.
+#include "augment_common.h"
 
 #pragma clang fp contract(off)
 
@@ -25,15 +26,13 @@ __device__ __forceinline__ double unit_open(uint64_t h) { return ((double)(h >> 
 __global__ __launch_bounds__(MX_THREADS) void mix_params_kernel(MixDraw cfg, uint64_t seed, uint64_t step, uint64_t rank, int B, int* __restrict__ mix) {
   const int b = blockIdx.x * MX_THREADS + threadIdx.x;
   if (b >= B) return;
-  const uint64_t seed_m = nv_hash64(nv_hash64(seed, rank), 0x4D4958ull);
-  const uint64_t counter = ((step << 32) + (uint64_t)b) * 256u;
-  auto h = [&](unsigned d) { return nv_hash64(seed_m, counter + d); };
+  const SampleDraws h(seed, rank, MIX_DOMAIN, MIX_STRIDE, step, b);
   const int partner = B - 1 - b;
   int row[NV_MIX_COLS] = {partner, 0, __float_as_int(1.0f), __float_as_int(1.0f), 0, 0, 0, 0, 0, 0, 0, 0};
   int mode = 0;
-  if (partner != b && (unsigned)(h(0) >> 48) < cfg.prob_thresh) {
+  if (partner != b && draw_chance(h(0), cfg.prob_thresh)) {
     const bool mixup = cfg.inv_alpha_mixup != 0.0, cutmix = cfg.inv_alpha_cutmix != 0.0;
-    if (mixup && cutmix) mode = (unsigned)(h(1) >> 48) < cfg.switch_thresh ? 2 : 1;
+    if (mixup && cutmix) mode = draw_chance(h(1), cfg.switch_thresh) ? 2 : 1;
     else mode = cutmix ? 2 : (mixup ? 1 : 0);
   }
   if (mode) {
@@ -57,7 +56,7 @@ __global__ __launch_bounds__(MX_THREADS) void mix_params_kernel(MixDraw cfg, uin
       for (int a = 0; a < 3; ++a) {
         const int S = cfg.S[a];
         const int e = (int)((float)S * r);
-        const int c = (int)(((h(2 + a) >> 32) * (uint64_t)S) >> 32);
+        const int c = draw_below(h(2 + a), S);
         const int lo = max(c - e / 2, 0), hi = min(c + e / 2, S);
         row[5 + 2 * a] = lo;
         row[6 + 2 * a] = hi;
@@ -90,8 +89,8 @@ extern "C" int nv_mix_params(const nv_mix_config* cfg, unsigned long seed, unsig
                cfg->prob, cfg->switch_prob);
   d.inv_alpha_mixup = alphas[0] != 0.0 ? 1.0 / alphas[0] : 0.0;
   d.inv_alpha_cutmix = alphas[1] != 0.0 ? 1.0 / alphas[1] : 0.0;
-  d.prob_thresh = (unsigned)(cfg->prob * 65536.0);
-  d.switch_thresh = (unsigned)(cfg->switch_prob * 65536.0);
+  d.prob_thresh = chance_thresh(cfg->prob);
+  d.switch_thresh = chance_thresh(cfg->switch_prob);
   hipLaunchKernelGGL(mix_params_kernel, dim3((B + MX_THREADS - 1) / MX_THREADS), dim3(MX_THREADS), 0, (hipStream_t)stream, d, (uint64_t)seed, (uint64_t)step,
                      (uint64_t)rank, B, mix);
   NV_CHECK_LAUNCH("nv_mix_params");

@@ -758,6 +758,9 @@ class Trainer:
             return None
         from .augment import VolumeAffine, VolumeAugment
         S = config['TRAINING_VIT_INPUT_SIZE']
+        shared = dict(flip_prob=config.get('AUGMENT_FLIP_PROB', (0, 0, 0)), scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)),
+                      shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)), fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
+                      rank=Trainer._rank())
         affine_keys = ('AUGMENT_ROTATE_DEG', 'AUGMENT_ZOOM', 'AUGMENT_ZOOM_ISOTROPIC', 'AUGMENT_TRANSLATE', 'AUGMENT_AFFINE_PROB')
         if any(config.get(k, None) is not None for k in affine_keys):
             if config.get('AUGMENT_MAX_SHIFT', None) is not None:
@@ -766,14 +769,13 @@ class Trainer:
             pick = lambda key, default: default if config.get(key, None) is None else config[key]
             return VolumeAffine((S, S, S), rotate=pick('AUGMENT_ROTATE_DEG', 0.0), zoom=pick('AUGMENT_ZOOM', (1, 1)),
                                 isotropic=pick('AUGMENT_ZOOM_ISOTROPIC', True), translate=pick('AUGMENT_TRANSLATE', 0.0),
-                                prob=pick('AUGMENT_AFFINE_PROB', 1.0), flip_prob=config.get('AUGMENT_FLIP_PROB', (0, 0, 0)),
-                                scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)), shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)),
-                                fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
-                                rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
-        return VolumeAugment((S, S, S), flip_prob=config.get('AUGMENT_FLIP_PROB', (0, 0, 0)), max_shift=config.get('AUGMENT_MAX_SHIFT', (0, 0, 0)),
-                             scale=config.get('AUGMENT_INTENSITY_SCALE', (1, 1)), shift=config.get('AUGMENT_INTENSITY_SHIFT', (0, 0)),
-                             fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0),
-                             rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+                                prob=pick('AUGMENT_AFFINE_PROB', 1.0), **shared)
+        return VolumeAugment((S, S, S), max_shift=config.get('AUGMENT_MAX_SHIFT', (0, 0, 0)), **shared)
+
+    @staticmethod
+    def _rank() -> int:
+        """the process group's rank when there is one: what separates the draws of two ranks with one AUGMENT_SEED"""
+        return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
     @staticmethod
     def mix_from_config(config):
@@ -786,7 +788,7 @@ class Trainer:
         from .augment import VolumeMix
         return VolumeMix(mixup_alpha=mixup, cutmix_alpha=cutmix, prob=config.get('AUGMENT_MIX_PROB', 1.0),
                          switch_prob=config.get('AUGMENT_MIX_SWITCH_PROB', 0.5), seed=config.get('AUGMENT_SEED', 0),
-                         rank=dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+                         rank=Trainer._rank())
 
     @staticmethod
     def loss_options_from_config(config):

@@ -314,6 +314,25 @@ def test_volume_affine_refuses_bad_configurations():
     assert full.isotropic is False and full.prob == 0.5 and full.fill == -1.0 and (full.seed, full.rank, full.step, full.last_params) == (3, 2, 0, None)
 
 
+def test_volume_affine_names_itself_in_the_refusals_it_shares():
+    """the checks VolumeAffine shares with VolumeAugment (a triple, a range, the step) report under the class the caller used"""
+    from neurovit_amd.augment import VolumeAffine
+    for refused in (lambda: VolumeAffine(8, rotate=(1, 2)), lambda: VolumeAffine(8, scale=(2, 1)), lambda: VolumeAffine(8).params(2, -1)):
+        with pytest.raises((TypeError, ValueError)) as err:
+            refused()
+        assert "VolumeAffine" in str(err.value) and "VolumeAugment" not in str(err.value)
+
+
+def test_the_windowed_transforms_share_one_base():
+    from neurovit_amd import augment
+    base = augment.VolumeAugment.__mro__[1]
+    assert base is not object and base is augment.VolumeAffine.__mro__[1]
+    for cls in (augment.VolumeAugment, augment.VolumeAffine):
+        assert isinstance(cls(8), base)
+        assert not {"__call__", "apply", "is_identity", "_check_input"} & set(vars(cls)), cls.__name__
+        assert all(callable(getattr(cls, name)) for name in ("__call__", "apply", "is_identity", "_check_input", "params", "_transforms_off"))
+
+
 def test_volume_affine_refuses_bad_inputs_before_any_device_work():
     from neurovit_amd.augment import VolumeAffine, VolumeAugment, VolumeMix
     aff = VolumeAffine(8, rotate=10)

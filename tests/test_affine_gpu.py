@@ -13,6 +13,7 @@ import torch
 import affine_ref as R
 import augment_ref as A
 import weights as W
+from augment_inputs import SPAN_SHAPES, layouts, sentinel_out, sentinels_intact, special_volume
 
 pytestmark = pytest.mark.gpu
 
@@ -70,19 +71,6 @@ def test_prob_zero_draws_the_rows_of_an_index_copy(VF):
 
 
 # ------------------------------------------------------------------ apply, bit for bit
-def layouts(host):
-    """host [B, X, Y, Z(, T)] -> {name: the same values on the device in that layout}"""
-    pad = [(1, 2), (2, 1), (3, 4)]
-    big = torch.zeros(host.shape[0], *(n + lo + hi for n, (lo, hi) in zip(host.shape[1:4], pad)), *host.shape[4:]).cuda()
-    view = big[:, 1:1 + host.shape[1], 2:2 + host.shape[2], 3:3 + host.shape[3]]
-    view.copy_(host)
-    flat = torch.zeros(host.numel() + 1).cuda()
-    moved = flat[1:].view(host.shape)                        # the base moved by one element: no source row starts a 16-byte group
-    moved.copy_(host)
-    assert not view.is_contiguous() and moved.data_ptr() % 16 == 4
-    return {"dense": host.cuda(), "view": view, "moved": moved}
-
-
 @pytest.fixture(scope="module")
 def volumes():
     return {T: R.volume(T=T) for T in (None, 4, 5)}
@@ -115,22 +103,7 @@ def test_apply_equals_the_restatement_bit_for_bit(VF, volumes, roi, T):
 
 
 # ------------------------------------------------------------------ a plane of more than one span, guard cells
-# A workgroup owns 4096 cells of an output plane.  The smallest planes that reach a second one: 65 x 67 = 4355 cells (4355 mod 4 = 3, so
-# consecutive planes start at every 16-byte alignment; the second span is a ragged 259 cells) and, for a series, 9 x 10 x 47 = 4230 cells.
-SPAN_SHAPES = {"3d": ((3, 5, 68, 70), (3, 65, 67)), "4d": ((3, 4, 12, 13, 47), (2, 9, 10))}
-
-
-def sentinel_out(shape):
-    """a dense `out` of that shape with 64 sentinel floats on both sides"""
-    n = int(np.prod(shape))
-    buf = torch.full((64 + n + 64,), 0x7FC0BEEF, dtype=torch.int32, device="cuda").view(torch.float32)
-    return buf, buf[64:64 + n].view(shape)
-
-
-def sentinels_intact(buf):
-    return bool((A.bits(torch.cat([buf[:64], buf[-64:]]).cpu()) == 0x7FC0BEEF).all())
-
-
+# (the planes of more than 4096 cells, one workgroup's span: SPAN_SHAPES in tests/augment_inputs.py)
 @pytest.mark.parametrize("case", sorted(SPAN_SHAPES))
 def test_apply_reaches_a_second_span_and_keeps_inside_out(VF, case):
     shape, roi = SPAN_SHAPES[case]
@@ -158,19 +131,6 @@ def test_apply_reaches_a_second_span_and_keeps_inside_out(VF, case):
 
 
 # ------------------------------------------------------------------ integer maps are what nv_augment_apply writes
-def special_volume(shape, seed):
-    """NaN (one with a payload), +-inf, -0.0 among normal values"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(shape, generator=g)
-    flat = x.view(shape[0], -1)
-    flat[:, 0::17] = float("nan")
-    flat[:, 1::19] = float("inf")
-    flat[:, 2::23] = float("-inf")
-    flat[:, 3::29] = -0.0
-    flat[:, 5::31] = torch.tensor([0x7fc01234], dtype=torch.int32).view(torch.float32)[0]
-    return x
-
-
 @pytest.mark.parametrize("T", [1, 4, 5])
 def test_integer_maps_equal_the_augmentation_pass_bit_for_bit(VF, T):
     from neurovit_amd.augment import VolumeAugment

@@ -9,6 +9,7 @@ import torch
 
 import augment_ref as R
 import weights as W
+from augment_inputs import SPAN_SHAPES, layouts, sentinel_out, sentinels_intact, special_volume
 
 pytestmark = pytest.mark.gpu
 
@@ -22,19 +23,6 @@ def VA():
     require_gpu()
     from neurovit_amd.augment import VolumeAugment
     return VolumeAugment
-
-
-def special_volume(shape, seed):
-    """tests/test_perturbation_gpu.py's recipe: NaN (one with a payload), +-inf, -0.0 among normal values"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(shape, generator=g)
-    flat = x.view(shape[0], -1)
-    flat[:, 0::17] = float("nan")
-    flat[:, 1::19] = float("inf")
-    flat[:, 2::23] = float("-inf")
-    flat[:, 3::29] = -0.0
-    flat[:, 5::31] = torch.tensor([0x7fc01234], dtype=torch.int32).view(torch.float32)[0]       # NaNs with a payload
-    return x
 
 
 def same_bits_or_both_nan(got, want):
@@ -76,15 +64,6 @@ def param_rows(roi):
     rows += [[*o, (r + f) % 8] for r, o in enumerate(part) for f in (0, 4, 7)]
     rows += [[*o, r % 8] for r, o in enumerate(whole)]
     return rows, len(whole)
-
-
-def layouts():
-    big = special_volume((3, 25, 24, 27), 23)
-    view = big[:, 1:24, 2:23, 3:25]                          # a sliced, non-contiguous view: rows of 22 floats at every alignment
-    dense = view.contiguous()
-    moved = view.permute(0, 3, 2, 1).contiguous().permute(0, 3, 2, 1)       # the same values with x innermost: no row is a run of memory
-    assert not view.is_contiguous() and not moved.is_contiguous() and torch.equal(R.bits(moved), R.bits(dense))
-    return dense, {"view": lambda d: d(big)[:, 1:24, 2:23, 3:25], "dense": lambda d: d(dense), "moved": lambda d: d(moved.permute(0, 3, 2, 1)).permute(0, 3, 2, 1)}
 
 
 @pytest.fixture(scope="module")
@@ -160,28 +139,12 @@ def test_series_share_their_samples_parameters(VA, T):
 
 
 # ------------------------------------------------------------------ a plane of more than one span
-# A workgroup owns 4096 cells of an output plane.  The smallest planes that reach a second one: 65 x 67 = 4355 cells (4355 mod 4 = 3, so
-# consecutive planes start at every 16-byte alignment; the second span is 259 cells from output row 61, column 9) and, for a series,
-# 9 x 10 x 47 = 4230 cells (rows of 470; the second span is 134 cells from row 8, k = 7).
-SPAN_SHAPES = {"3d": ((3, 5, 68, 70), (3, 65, 67)), "4d": ((3, 4, 12, 13, 47), (2, 9, 10))}
-
-
+# (the planes of more than 4096 cells, one workgroup's span: SPAN_SHAPES in tests/augment_inputs.py)
 def span_rows():
     """for both shapes (X - Sx, Y - Sy, Z - Sz) = (2, 3, 3): z flips, windows that leave the volume on the low and on the high side of
     every axis (one plane wholly outside), an intensity change on some samples"""
     return [[[1, 2, 1, 4, ONE, ZERO, 0, 0], [-1, -2, -3, 0, SCALE, SHIFT, 0, 0], [3, 5, 5, 7, ONE, ZERO, 0, 0]],
             [[0, 0, 0, 0, ONE, ZERO, 0, 0], [2, 3, 3, 4, SCALE, SHIFT, 0, 0], [1, -2, 6, 6, SCALE, SHIFT, 0, 0]]]
-
-
-def sentinel_out(shape):
-    """a dense `out` of that shape with 64 sentinel floats on both sides"""
-    n = int(np.prod(shape))
-    buf = torch.full((64 + n + 64,), 0x7FC0BEEF, dtype=torch.int32, device="cuda").view(torch.float32)
-    return buf, buf[64:64 + n].view(shape)
-
-
-def sentinels_intact(buf):
-    return bool((R.bits(torch.cat([buf[:64], buf[-64:]]).cpu()) == 0x7FC0BEEF).all())
 
 
 @pytest.mark.parametrize("case", sorted(SPAN_SHAPES))

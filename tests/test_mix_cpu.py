@@ -319,6 +319,9 @@ def test_volume_mix_validates_its_arguments():
         mix.params(2, 0, (8, 0, 8))
     with pytest.raises(ValueError, match="come together"):
         mix.apply(x, torch.zeros(2, 12, dtype=torch.int32), augment=VolumeAugment(8))
+    with pytest.raises(TypeError, match="step must be an integer") as err:      # a shared check reports under the class the caller used
+        VolumeMix(mixup_alpha=0.4)(x, step="0")
+    assert "VolumeMix" in str(err.value) and "VolumeAugment" not in str(err.value)
 
 
 def test_cross_entropy_loss_and_train_step_validate_their_arguments():

@@ -17,7 +17,8 @@ import augment_ref as R
 import mix_ref as M
 import weights as W
 from conftest import rel_err
-from test_augment_gpu import SPAN_SHAPES, sentinel_out, sentinels_intact, span_rows
+from augment_inputs import SPAN_SHAPES, layouts, sentinel_out, sentinels_intact, special_volume
+from test_augment_gpu import span_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -80,32 +81,9 @@ def test_params_equal_the_restatement(VM, B, name):
 IN = (23, 21, 22)
 
 
-def special_volume(shape, seed):
-    """tests/test_augment_gpu.py's recipe plus subnormals: NaN (one with a payload), +-inf, -0.0, +-subnormals among normal values"""
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(shape, generator=g)
-    flat = x.view(shape[0], -1)
-    flat[:, 0::17] = float("nan")
-    flat[:, 1::19] = float("inf")
-    flat[:, 2::23] = float("-inf")
-    flat[:, 3::29] = -0.0
-    flat[:, 5::31] = torch.tensor([0x7fc01234], dtype=torch.int32).view(torch.float32)[0]       # NaNs with a payload
-    flat[:, 7::37] = torch.tensor([0x00000123], dtype=torch.int32).view(torch.float32)[0]       # a subnormal
-    flat[:, 9::41] = torch.tensor([-0x7FFFFFFF - 1 + 0x00400001], dtype=torch.int32).view(torch.float32)[0]     # a negative subnormal (0x80400001)
-    return x
-
-
-def layouts():
-    big = special_volume((3, 25, 24, 27), 23)
-    view = big[:, 1:24, 2:23, 3:25]                          # a sliced, non-contiguous view: rows of 22 floats at every alignment
-    dense = view.contiguous()
-    moved = view.permute(0, 3, 2, 1).contiguous().permute(0, 3, 2, 1)       # the same values with x innermost: no row is a run of memory
-    return dense, {"view": lambda d: d(big)[:, 1:24, 2:23, 3:25], "dense": lambda d: d(dense), "moved": lambda d: d(moved.permute(0, 3, 2, 1)).permute(0, 3, 2, 1)}
-
-
 @pytest.fixture(scope="module")
 def volumes():
-    return layouts()
+    return layouts(subnormals=True)                          # (the recipe of tests/test_augment_gpu.py plus +-subnormals)
 
 
 def aug_tables(S):
@@ -219,7 +197,7 @@ def test_mix_reaches_a_second_span(VM, case):
     from neurovit_amd.augment import VolumeAugment
     shape, roi = SPAN_SHAPES[case]
     box = (0, roi[0], 60, 64, 6, 59) if case == "3d" else (0, roi[0], 7, 9, 5, 9)
-    host = special_volume(shape, 61)
+    host = special_volume(shape, 61, subnormals=True)
     x = host.cuda()
     aug, mixer = VolumeAugment(roi, fill=-2.5), VM(mixup_alpha=0.4, cutmix_alpha=1.0)
     buf, out = sentinel_out((3, *roi, *shape[4:]))

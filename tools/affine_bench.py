@@ -29,26 +29,19 @@ Prints one JSON line.
 --only NAME --sides affine` (one geometry and one side per traced run; tracing slows the host, so its event timings are not the ones to
 quote) and reports the kernel's OWN time against the floor.
 """
-import argparse
-import csv
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-HBM_TBS = 6.3          # achievable HBM bandwidth of the MI355X (TB/s)
+from augment_timing import HBM_TBS, base_step_config, floor_us, in_turns, parser, print_kernel_stats  # noqa: E402 (beside this script)
+
 GEOMETRIES = {"base": dict(B=4, X=136, S=128, T=1), "reference": dict(B=128, X=90, S=80, T=1), "series": dict(B=1, X=136, S=128, T=20),
               "series2": dict(B=2, X=136, S=128, T=20)}
-BASE = dict(size=128, patch=16, TRAINING_VIT_DIM=768, TRAINING_VIT_DEPTH=12, TRAINING_VIT_HEADS=12, TRAINING_VIT_MLP_DIM=3072)
 OPTIONS = dict(rotate=(10, 10, 10), zoom=(0.9, 1.1), translate=(4, 4, 4))
 SIDES = ("affine", "integer", "augment", "torch")
-
-
-def floor_us(B, S, T):
-    return 2 * 4.0 * B * S ** 3 * T / (HBM_TBS * 1e12) * 1e6
 
 
 def maps_of(table):
@@ -95,22 +88,12 @@ def share_of_bound(got, want, x, table, S):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="base,reference,series,series2,step", help="comma-separated: base, reference, series, series2, step")
+    ap = parser(GEOMETRIES, "kernel_stats.csv of a traced run with the same --only (one geometry)")
     ap.add_argument("--sides", default=",".join(SIDES), help="comma-separated: " + ", ".join(SIDES))
-    ap.add_argument("--steps", type=int, default=100, help="repetitions inside one timed window")
-    ap.add_argument("--rounds", type=int, default=5, help="timed windows per side, taken in turns")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--train-steps", type=int, default=20, help="train steps inside one timed window of `step`")
-    ap.add_argument("--stats", help="kernel_stats.csv of a traced run with the same --only (one geometry)")
     args = ap.parse_args()
     if args.stats:
         g = GEOMETRIES[args.only]
-        rows = [r for r in csv.DictReader(open(args.stats)) if "affine_apply_kernel" in r["Name"]]
-        calls, ns = sum(int(r["Calls"]) for r in rows), sum(float(r["TotalDurationNs"]) for r in rows)
-        fl = floor_us(g["B"], g["S"], g["T"])
-        print(json.dumps({"geometry": args.only, **g, "calls": calls, "kernel_avg_us": round(ns / calls / 1e3, 2), "floor_us": round(fl, 1),
-                          "share_of_floor": round(fl / (ns / calls / 1e3), 3)}))
+        print_kernel_stats(args.stats, "affine_apply_kernel", {"geometry": args.only, **g}, floor_us(g["B"], g["S"], g["T"]))
         return
 
     import torch
@@ -118,26 +101,6 @@ def main():
     from neurovit_amd.augment import VolumeAffine, VolumeAugment
     require_gpu()
     torch.manual_seed(0)
-
-    def window(fn, reps):
-        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        begin.record()
-        for _ in range(reps):
-            fn()
-        end.record()
-        torch.cuda.synchronize()
-        return begin.elapsed_time(end) / reps * 1e3          # us
-
-    def in_turns(sides, reps):
-        for fn in sides.values():
-            for _ in range(args.warmup):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in sides}
-        for _ in range(args.rounds):
-            for k, fn in sides.items():
-                times[k].append(window(fn, reps))
-        return {k: dict(median_us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2)) for k, v in times.items()}
 
     what = [w for w in args.only.split(",") if w]
     wanted = [s for s in args.sides.split(",") if s]
@@ -162,7 +125,7 @@ def main():
         if "torch" in sides and "affine" in sides:
             share = share_of_bound(aff.apply(x, table), torch_affine(x, theta, S), x, table, S)
             entry.update(torch_share_of_bound=round(share, 4), torch_agrees=bool(share <= 1.0))
-        t = in_turns(sides, args.steps)
+        t = in_turns(sides, args.steps, args)
         entry.update(t)
         for k in ("affine", "integer", "augment"):
             if k in t:
@@ -177,18 +140,14 @@ def main():
     if "step" in what:
         from neurovit_amd.NeuroEncoder import NeuroEncoder
         from neurovit_amd.trainer import TrainStep
-        p = dict(BASE)
-        S, patch = p.pop("size"), p.pop("patch")
-        cfg = dict(DEVICE="cuda:0", TRAINING_DIM=3, TRAINING_DROPOUT=0.0, TRAINING_VIT_INPUT_SIZE=S, TRAINING_VIT_PATCH_SIZE=patch, GRADCAM_CUBE_SIZE=8,
-                   DATASET_NAME="adni", GRADCAM_THRESHOLD=5, GRADCAM_SLICE_DIM=2, GRADCAM_SLICE_IDX=S // 2, GLOBAL_BASE_PATH="", BEST_MODEL_PATH="",
-                   TRAINING_LEARNING_RATE=1e-4, TRAINING_WEIGHT_DECAY=1e-2, **p)
+        cfg, S = base_step_config()
         model = NeuroEncoder(cfg).train()
         step = TrainStep(model)
         B, X = 4, 136
         big = torch.randn(B, X, X, X, device="cuda")
         labels = torch.randint(0, 2, (B,), device="cuda")
         aug, aff = VolumeAugment((S, S, S), seed=1), VolumeAffine((S, S, S), seed=1, **OPTIONS)
-        t = in_turns({"augment": lambda: step(aug(big), labels), "affine": lambda: step(aff(big), labels)}, args.train_steps)
+        t = in_turns({"augment": lambda: step(aug(big), labels), "affine": lambda: step(aff(big), labels)}, args.train_steps, args)
         result["step"] = {"batch": B, "input": X, "size": S, "train_steps": args.train_steps, "augment": t["augment"], "affine": t["affine"],
                           "delta_us": round(t["affine"]["median_us"] - t["augment"]["median_us"], 1),
                           "delta_share": round(t["affine"]["median_us"] / t["augment"]["median_us"] - 1.0, 4)}

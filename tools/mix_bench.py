@@ -22,26 +22,24 @@ Prints one JSON line.
 tools/mix_bench.py --only NAME --modes MODE` (one geometry and one mode per traced run, in a run of its own; tracing slows the host, so
 its event timings are not the ones to quote) and reports the kernel's OWN time against the floor.
 """
-import argparse
-import csv
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-HBM_TBS = 6.3          # achievable HBM bandwidth of the MI355X (TB/s)
+from augment_timing import HBM_TBS, base_step_config, in_turns, parser, print_kernel_stats  # noqa: E402 (beside this script)
+from augment_timing import floor_us as floor_of_reads  # noqa: E402 (beside this script)
+
 GEOMETRIES = {"base": dict(B=4, X=136, S=128, T=1), "reference": dict(B=128, X=90, S=80, T=1), "series": dict(B=2, X=136, S=128, T=20)}
-BASE = dict(size=128, patch=16, TRAINING_VIT_DIM=768, TRAINING_VIT_DEPTH=12, TRAINING_VIT_HEADS=12, TRAINING_VIT_MLP_DIM=3072)
 OPTIONS = dict(flip_prob=(0.5, 0.5, 0.5), max_shift=(4, 4, 4), scale=(0.9, 1.1), shift=(-0.1, 0.1))
 MODES = {"mixup": dict(mixup_alpha=0.4), "cutmix": dict(cutmix_alpha=1.0)}
 
 
 def floor_us(B, S, T, mode):
-    reads = 2 if mode == "mixup" else 1
-    return (1 + reads) * 4.0 * B * S ** 3 * T / (HBM_TBS * 1e12) * 1e6
+    """the output written plus the source read once (CutMix, mode 0) or twice (Mixup)"""
+    return floor_of_reads(B, S, T, reads=2 if mode == "mixup" else 1)
 
 
 def torch_mix(a, rows):
@@ -62,22 +60,12 @@ def torch_mix(a, rows):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="base,reference,series,step", help="comma-separated: base, reference, series, step")
+    ap = parser(GEOMETRIES, "kernel_stats.csv of a traced run with the same --only and --modes (one geometry, one mode)")
     ap.add_argument("--modes", default="mixup,cutmix", help="comma-separated: mixup, cutmix")
-    ap.add_argument("--steps", type=int, default=100, help="repetitions inside one timed window")
-    ap.add_argument("--rounds", type=int, default=5, help="timed windows per side, taken in turns")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--train-steps", type=int, default=20, help="train steps inside one timed window of `step`")
-    ap.add_argument("--stats", help="kernel_stats.csv of a traced run with the same --only and --modes (one geometry, one mode)")
     args = ap.parse_args()
     if args.stats:
         g = GEOMETRIES[args.only]
-        rows = [r for r in csv.DictReader(open(args.stats)) if "augment_mix_kernel" in r["Name"]]
-        calls, ns = sum(int(r["Calls"]) for r in rows), sum(float(r["TotalDurationNs"]) for r in rows)
-        fl = floor_us(g["B"], g["S"], g["T"], args.modes)
-        print(json.dumps({"geometry": args.only, "mode": args.modes, **g, "calls": calls, "kernel_avg_us": round(ns / calls / 1e3, 2),
-                          "floor_us": round(fl, 1), "share_of_floor": round(fl / (ns / calls / 1e3), 3)}))
+        print_kernel_stats(args.stats, "augment_mix_kernel", {"geometry": args.only, "mode": args.modes, **g}, floor_us(g["B"], g["S"], g["T"], args.modes))
         return
 
     import torch
@@ -85,26 +73,6 @@ def main():
     from neurovit_amd.augment import VolumeAugment, VolumeMix
     require_gpu()
     torch.manual_seed(0)
-
-    def window(fn, reps):
-        begin, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        begin.record()
-        for _ in range(reps):
-            fn()
-        end.record()
-        torch.cuda.synchronize()
-        return begin.elapsed_time(end) / reps * 1e3          # us
-
-    def in_turns(sides, reps):
-        for fn in sides.values():
-            for _ in range(args.warmup):
-                fn()
-        torch.cuda.synchronize()
-        times = {k: [] for k in sides}
-        for _ in range(args.rounds):
-            for k, fn in sides.items():
-                times[k].append(window(fn, reps))
-        return {k: dict(median_us=round(statistics.median(v), 2), min_us=round(min(v), 2), max_us=round(max(v), 2)) for k, v in times.items()}
 
     what = [w for w in args.only.split(",") if w]
     modes = [m for m in args.modes.split(",") if m]
@@ -127,7 +95,7 @@ def main():
             rows = [[*r[:2].tolist(), r[2:3].view(torch.float32).item(), r[3:4].view(torch.float32).item(), *r[4:].tolist()] for r in host]
             same = torch.allclose(mixer.apply(x, table, augment=aug, augment_params=params), torch_mix(aug.apply(x, params), rows), rtol=0, atol=1e-5)
             t = in_turns({"kernel": lambda: mixer.apply(x, table, augment=aug, augment_params=params, out=out),
-                          "torch": lambda: torch_mix(aug.apply(x, params, out=mid), rows)}, args.steps)
+                          "torch": lambda: torch_mix(aug.apply(x, params, out=mid), rows)}, args.steps, args)
             fl = floor_us(B, S, T, mode)
             result[name][mode] = {"floor_us": round(fl, 1), "kernel": t["kernel"], "torch": t["torch"], "torch_agrees": bool(same),
                                   "kernel_share_of_floor": round(fl / t["kernel"]["median_us"], 3),
@@ -135,11 +103,7 @@ def main():
     if "step" in what:
         from neurovit_amd.NeuroEncoder import NeuroEncoder
         from neurovit_amd.trainer import TrainStep
-        p = dict(BASE)
-        S, patch = p.pop("size"), p.pop("patch")
-        cfg = dict(DEVICE="cuda:0", TRAINING_DIM=3, TRAINING_DROPOUT=0.0, TRAINING_VIT_INPUT_SIZE=S, TRAINING_VIT_PATCH_SIZE=patch, GRADCAM_CUBE_SIZE=8,
-                   DATASET_NAME="adni", GRADCAM_THRESHOLD=5, GRADCAM_SLICE_DIM=2, GRADCAM_SLICE_IDX=S // 2, GLOBAL_BASE_PATH="", BEST_MODEL_PATH="",
-                   TRAINING_LEARNING_RATE=1e-4, TRAINING_WEIGHT_DECAY=1e-2, **p)
+        cfg, S = base_step_config()
         B, X = 4, 136
         big = torch.randn(B, X, X, X, device="cuda")
         labels = torch.randint(0, 2, (B,), device="cuda")
@@ -151,7 +115,7 @@ def main():
         def mixed_step():
             batch = mixer(big, augment=aug)
             return mixed(batch, labels, mix=mixer.last_mix)
-        t = in_turns({"augmented": lambda: plain(aug(big), labels), "mixed": mixed_step}, args.train_steps)
+        t = in_turns({"augmented": lambda: plain(aug(big), labels), "mixed": mixed_step}, args.train_steps, args)
         result["step"] = {"batch": B, "input": X, "size": S, "train_steps": args.train_steps, "augmented": t["augmented"], "mixed": t["mixed"],
                           "delta_us": round(t["mixed"]["median_us"] - t["augmented"]["median_us"], 1),
                           "delta_share": round(t["mixed"]["median_us"] / t["augmented"]["median_us"] - 1.0, 4)}
