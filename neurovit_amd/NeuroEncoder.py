@@ -154,7 +154,7 @@ class NeuroEncoder(nn.Module):
         if 'activations' in self._hook_override:
             return self._hook_override['activations']
         vit = self.volume_encoder.vit3d
-        if vit._rt._last is None:
+        if vit._rt.last is None:
             return {}
         return vit.last_attn_norm_output().detach().cpu()
 
@@ -168,7 +168,8 @@ class NeuroEncoder(nn.Module):
             return self._hook_override['gradients']
         vit = self.volume_encoder.vit3d
         # the buffer holds the gradient only once a backward pass of the most recent training-mode forward has run
-        if vit._rt._last is None or not vit._rt._last[1] or not vit._rt.backward_done:
+        last = vit._rt.last
+        if last is None or not last.layout or not last.grad_ready:
             return {}
         return vit.last_attn_norm_grad().detach().cpu()
 

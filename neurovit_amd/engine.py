@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import ctypes
 import os
-import sys
 import weakref
 from typing import Dict, List, Optional, Tuple
 
@@ -69,100 +68,143 @@ def _inp_ptr(inp):
     return None if inp is None else ctypes.cast(ctypes.pointer(inp), ctypes.c_void_p)
 
 
+def _drop(dropout):
+    """(p of the blocks, p of the embedding, seed) as the C arguments"""
+    return float(dropout[0]), float(dropout[1]), int(dropout[2])
+
+
 class _Pass:
-    """One training-layout forward whose activations a backward may still read: its workspace, its input (the backward re-gathers
-    the patches), the form of the last block, the dropout draw.  `done`: a whole backward has run - the workspace may be refilled."""
-    __slots__ = ("B", "ws", "video", "keep", "rows_form", "dropout", "dlogits", "done", "__weakref__")
+    """One forward and what a backward of it, or a tap into its workspace, needs: batch, layout (0 inference, 1 training, 2 fp32), workspace,
+    input (the backward re-gathers the patches), input form `keep` = (vol_sigma, nv_vit_input), form of the last block, dropout draw.
+    `done`: a whole backward has run - the workspace may be refilled.  `grad_ready`: a backward has left the hook gradient in the workspace."""
+    __slots__ = ("B", "layout", "ws", "video", "keep", "rows_form", "dropout", "dlogits", "done", "grad_ready", "_claim", "__weakref__")
 
-    def __init__(self, B, ws, video, keep, rows_form, dropout, done=False):
-        self.B, self.ws, self.video, self.keep, self.rows_form, self.dropout, self.dlogits, self.done = B, ws, video, keep, rows_form, dropout, None, done
+    class _Claim:
+        __slots__ = ("__weakref__",)
+
+    def __init__(self, B, layout, ws, video, keep=(None, None), rows_form=0, dropout=(0.0, 0.0, 0), done=False):
+        self.B, self.layout, self.ws, self.video, self.keep, self.rows_form, self.dropout = B, int(layout), ws, video, keep, rows_form, dropout
+        self.dlogits, self.done, self.grad_ready, self._claim = None, done, done, None
+
+    def claim(self):
+        """A token for whoever needs this pass's activations later (an autograd node keeps it on its ctx): the pass is held while it is alive."""
+        token = _Pass._Claim()
+        self._claim = weakref.ref(token)
+        return token
+
+    def finish(self) -> None:
+        """nothing more of this pass will run: the workspace may be refilled by the next training forward, the hook gradient is in it"""
+        self.done = self.grad_ready = True
+
+    @property
+    def held(self) -> bool:
+        return self._claim is not None and self._claim() is not None
 
 
-class VitRuntime:
-    """Executes ViT forward / backward through the native engine on caller-provided arenas.
-    Training-layout workspaces are handed out per forward pass: a pass whose backward has not run yet (and whose autograd node is still
-    alive) keeps its workspace, and the next training forward takes another one - as many live sets of activations as the caller's graph
-    holds, the reference's autograd semantics (siamese / two-forward losses); the usual forward-backward loop never needs a second."""
+class PassLedger:
+    """Which forward filled which workspace, and may it be overwritten.  Workspaces are cached per (B, layout, device); the training
+    layout hands them out per pass: a pass that is claimed and whose backward has not run keeps its workspace, and the next training
+    forward takes another one - as many live sets of activations as the caller's graph holds, the reference's autograd semantics
+    (siamese / two-forward losses); the usual forward-backward loop never needs a second.  `nbytes(B, layout)` sizes a workspace."""
 
-    def __init__(self, cfg: VitConfig):
-        self.cfg = cfg
-        self._ws: Dict[Tuple[int, int, str], torch.Tensor] = {}
-        self._last = None   # (B, training, workspace, video) of the most recent forward
-        self._pool: Dict[Tuple[int, int, str], list] = {}   # further training workspaces (beyond self._ws[key]) for overlapping passes
+    def __init__(self, nbytes):
+        self._nbytes = nbytes
+        self._ws: Dict[Tuple[int, int, str], List[torch.Tensor]] = {}   # [primary, further training workspaces for overlapping passes ...]
         self._holder = {}   # workspace address -> weakref of the _Pass that filled it last
-        self._cur: Optional[_Pass] = None     # the pass backward() runs against (the most recent training forward unless autograd names another)
-        self.generation = 0          # counts forwards: a backward may only run against the forward that filled the workspace
-        self.backward_done = False   # a backward of the most recent forward has run (gates the Grad-CAM gradient tap)
-        self._aux = {}      # device -> auxiliary stream for the weight-gradient GEMMs
-        self.use_aux_stream = os.environ.get("NEUROVIT_AUX_STREAM", "1") != "0"
-        # last block under pool='cls': 0 = the library's process default (cls rows), 1 = every row (A/B runs, debugging)
-        self.rows_form = 1 if os.environ.get("NEUROVIT_CLS_TAIL") == "0" else 0
-        self._rows_form = 0
-        self.operands = "bf16"       # 16-bit operand format of this runtime's calls (ViT.set_operands); set in the library before each of them
+        self.last: Optional[_Pass] = None      # the most recent forward of any layout (taps, Grad-CAM)
+        self.current: Optional[_Pass] = None   # the most recent training-layout pass: what a backward() that names none runs against
 
-    def workspace(self, B: int, training, device) -> torch.Tensor:
-        """training: False / True, or 2 for the fp32 inference layout."""
-        key = (B, int(training), str(device))
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = lib.nv_vit_workspace_bytes(ctypes.byref(self.cfg), B, int(training))
-            if nbytes < 0:
-                check(-1, "nv_vit_workspace_bytes")
+    def _workspaces(self, B: int, layout, device, more: bool = False) -> List[torch.Tensor]:
+        sets = self._ws.setdefault((B, int(layout), str(device)), [])
+        if more or not sets:
+            nbytes = self._nbytes(B, int(layout))
             ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
             pad = (-ws.data_ptr()) % 256
-            ws = ws[pad:pad + nbytes]
-            self._ws[key] = ws
-        return ws
+            sets.append(ws[pad:pad + nbytes])
+        return sets
 
-    def _training_workspace(self, B: int, device) -> torch.Tensor:
-        """A training-layout workspace no pending pass still needs: the first one whose last pass has had its backward or is gone."""
-        key = (B, 1, str(device))
-        first = self.workspace(B, True, device)
-        more = self._pool.setdefault(key, [])
-        for ws in [first] + more:
+    def workspace(self, B: int, training, device) -> torch.Tensor:
+        """The primary workspace.  training: False / True, or 2 for the fp32 inference layout."""
+        return self._workspaces(B, training, device)[0]
+
+    def extra_workspaces(self, B: int, device) -> int:
+        """how many training workspaces beyond the primary one overlapping passes have needed so far"""
+        return max(len(self._ws.get((B, 1, str(device)), ())) - 1, 0)
+
+    def acquire(self, B: int, layout, device) -> torch.Tensor:
+        """The workspace of the next forward: the primary one, or in the training layout the first whose last pass is gone, done or not held."""
+        if int(layout) != 1:
+            return self.workspace(B, layout, device)
+        for ws in self._workspaces(B, 1, device):
             ref = self._holder.get(ws.data_ptr())
             rec = ref() if ref is not None else None
-            if rec is None or rec.done:
+            if rec is None or rec.done or not rec.held:
                 return ws
-            # a pass only THIS runtime still refers to (self._cur, + `rec` here + the call's argument = 3): no autograd node holds it, and a direct
-            # rt.backward() always means the most recent forward - which the caller is about to replace: its workspace is free (forward-only loops in
-            # training layout, fp8 calibration: one workspace, not two)
-            if rec is self._cur and sys.getrefcount(rec) <= 3:
-                return ws
-        nbytes = first.numel()
-        ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        pad = (-ws.data_ptr()) % 256
-        ws = ws[pad:pad + nbytes]
-        more.append(ws)
-        return ws
+        return self._workspaces(B, 1, device, more=True)[-1]
 
-    def _open_pass(self, B, ws, video, keep, rows_form, dropout, done=False) -> _Pass:
-        rec = _Pass(B, ws, video, keep, rows_form, dropout, done)
-        self._holder[ws.data_ptr()] = weakref.ref(rec)
-        self._cur = rec
+    def open(self, rec: _Pass) -> _Pass:
+        """`rec` has just filled its workspace (whatever pass filled it before is stale now): it is the last pass, and the current one if it can be differentiated"""
+        self._holder[rec.ws.data_ptr()] = weakref.ref(rec)
+        self.last = rec
+        if rec.layout == 1:
+            self.current = rec
         return rec
-
-    def _buffers(self, B: int, layout, device):
-        """(workspace, logits) of a forward of B volumes.  layout as in workspace(); the training layout takes a workspace no pending pass needs."""
-        ws = self._training_workspace(B, device) if int(layout) == 1 else self.workspace(B, layout, device)
-        return ws, torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=device)
-
-    def _forward_done(self, B, layout, ws, video, form=None, dropout=(0.0, 0.0, 0)) -> None:
-        """What every forward records behind its C call.  form = (vol_sigma, inp, rows_form) on the 16-bit forwards: a backward re-gathers the
-        same (raw) input and takes the same form of the last block, and a replayed train step inherits both (note_step_replayed).  The fp32 and
-        the fp8 inference forwards pass none: nothing runs a backward against them, and they must not replace what a captured step recorded."""
-        if form is not None:
-            self._keep, self._rows_form, self._dropout = form[:2], form[2], dropout
-        self._last = (B, layout, ws, video)
-        if int(layout) == 1:
-            self._open_pass(B, ws, video, self._keep, self._rows_form, dropout)
-        self.generation += 1
-        self.backward_done = False
 
     def pass_is_live(self, rec: _Pass) -> bool:
         """the workspace still holds THIS pass's activations (no later forward or train step has refilled it)"""
         ref = self._holder.get(rec.ws.data_ptr())
         return ref is not None and ref() is rec
+
+    def backward_pass(self, of: Optional[_Pass] = None) -> _Pass:
+        """the pass a backward runs against: `of`, or the most recent training pass - whose activations must still be in its workspace"""
+        rec = self.current if of is None else of
+        assert rec is not None, "backward needs a preceding forward(training=True)"
+        if not self.pass_is_live(rec):
+            raise RuntimeError("neurovit_amd: backward() of a forward pass whose activations have been overwritten - a later forward or train step "
+                               "has refilled its workspace (a pass keeps its workspace only until a whole backward of it has run)")
+        return rec
+
+    def note_step_replayed(self, rec: _Pass) -> _Pass:
+        """A captured train step (trainer.py) has been replayed: the workspace of the pass its capture opened holds ITS activations and gradient taps again."""
+        return self.open(rec)
+
+
+class VitRuntime(PassLedger):
+    """Executes ViT forward / backward through the native engine on caller-provided arenas; its PassLedger keeps the passes' workspaces."""
+
+    def __init__(self, cfg: VitConfig):
+        super().__init__(self._workspace_bytes)
+        self.cfg = cfg
+        self._aux = {}      # device -> auxiliary stream for the weight-gradient GEMMs
+        self.use_aux_stream = os.environ.get("NEUROVIT_AUX_STREAM", "1") != "0"
+        # last block under pool='cls': 0 = the library's process default (cls rows), 1 = every row (A/B runs, debugging)
+        self.rows_form = 1 if os.environ.get("NEUROVIT_CLS_TAIL") == "0" else 0
+        self.operands = "bf16"       # 16-bit operand format of this runtime's calls (ViT.set_operands); set in the library before each of them
+
+    def _workspace_bytes(self, B: int, layout: int) -> int:
+        nbytes = lib.nv_vit_workspace_bytes(ctypes.byref(self.cfg), B, layout)
+        if nbytes < 0:
+            check(-1, "nv_vit_workspace_bytes")
+        return nbytes
+
+    def _forward(self, entry: str, video, layout, weights, mid=(), after=(), *, vol_sigma=None, time_points: int = 0, rows_form=None,
+                 attn_export=None, dropout=(0.0, 0.0, 0), operands: bool = True, step: bool = False):
+        """What every forward shares: checks, input form, workspace and logits, the C call
+        `entry`(cfg, B, video, shape, strides, input, *weights, workspace, bytes, *mid, logits, *after, stream[, aux stream]), the pass record.
+        step: the one-call train step - the primary training workspace (a pending pass in it goes stale), the auxiliary stream, a done pass.
+        Returns (pass, logits)."""
+        rows_form = self.rows_form if rows_form is None else int(rows_form)
+        if operands:
+            _cabi.set_operand_format(self.operands)
+        B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
+        dev = video.device
+        ws = self.workspace(B, True, dev) if step else self.acquire(B, layout, dev)
+        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
+        check(getattr(lib, entry)(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video), _inp_ptr(inp), *weights,
+                                  ws.data_ptr(), ws.numel(), *mid, logits.data_ptr(), *after, torch.cuda.current_stream().cuda_stream,
+                                  *((self._aux_stream(dev),) if step else ())), entry)
+        # a backward re-gathers the same (raw) input and takes the same form of the last block
+        return self.open(_Pass(B, layout, ws, video, (vol_sigma, inp), rows_form, dropout, done=step)), logits
 
     def _input_form(self, video: torch.Tensor, vol_sigma, time_points: int, rows_form: int = 0, attn_export: Optional[AttnExport] = None):
         """(B, nv_vit_input or None) after checking the extents: plain [B, C, F, H, W] view, or (time_points > 0) a contiguous
@@ -227,17 +269,8 @@ class VitRuntime:
         vol_sigma / time_points: the optional input forms of nv_vit_forward_in (raw volumes; contiguous 4D batch).
         rows_form: 1 = the last block on every row (as the reference computes it), 2 = on the cls rows when eligible,
         None = this runtime's default (`self.rows_form`: the process default unless NEUROVIT_CLS_TAIL=0)."""
-        rows_form = self.rows_form if rows_form is None else int(rows_form)
-        _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
-        ws, logits = self._buffers(B, training, video.device)
-        check(lib.nv_vit_forward_in(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                    _inp_ptr(inp),
-                                    params.data_ptr(), params16.data_ptr(), ws.data_ptr(), ws.numel(), int(training), float(dropout[0]),
-                                 float(dropout[1]), int(dropout[2]), logits.data_ptr(),
-                                 torch.cuda.current_stream().cuda_stream), "nv_vit_forward_in")
-        self._forward_done(B, training, ws, video, (vol_sigma, inp, rows_form), dropout)
-        return logits
+        return self._forward("nv_vit_forward_in", video, training, (params.data_ptr(), params16.data_ptr()), (int(training),) + _drop(dropout),
+                             vol_sigma=vol_sigma, time_points=time_points, rows_form=rows_form, attn_export=attn_export, dropout=dropout)[1]
 
     # ------------------------------------------------------------------ inference forward with the LayerNorms folded into the GEMMs around them
     def lnfold_prepare(self, params: torch.Tensor, reuse=None):
@@ -260,29 +293,16 @@ class VitRuntime:
     def forward_lnfold(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, fold, vol_sigma=None, time_points: int = 0,
                        rows_form: Optional[int] = None, attn_export: Optional[AttnExport] = None) -> torch.Tensor:
         """Inference forward (no dropout) whose blocks run without LayerNorm launches: nv_vit_forward_lnfold."""
-        rows_form = self.rows_form if rows_form is None else int(rows_form)
-        _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
-        ws, logits = self._buffers(B, False, video.device)
-        check(lib.nv_vit_forward_lnfold(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                        _inp_ptr(inp), params.data_ptr(), params16.data_ptr(),
-                                        fold["fold16"].data_ptr(), fold["fold32"].data_ptr(), ws.data_ptr(), ws.numel(), logits.data_ptr(),
-                                        torch.cuda.current_stream().cuda_stream), "nv_vit_forward_lnfold")
-        self._forward_done(B, False, ws, video, (vol_sigma, inp, rows_form))
-        return logits
+        return self._forward("nv_vit_forward_lnfold", video, 0, (params.data_ptr(), params16.data_ptr(), fold["fold16"].data_ptr(), fold["fold32"].data_ptr()),
+                             vol_sigma=vol_sigma, time_points=time_points, rows_form=rows_form, attn_export=attn_export)[1]
 
     # ------------------------------------------------------------------ fp32 inference (the reference's fp32 validate, Trainer.py:101-118)
     def forward_f32(self, video: torch.Tensor, params: torch.Tensor, vol_sigma=None, time_points: int = 0,
                     attn_export: Optional[AttnExport] = None) -> torch.Tensor:
         """Inference forward with every operand in fp32 (weights straight from the fp32 arena, contractions on the fp32 MFMA):
         logits within 1e-5 of the reference's CPU fp32 forward instead of the bf16 path's 1e-3 ... 7e-3.  Eval mode only."""
-        B, inp = self._input_form(video, vol_sigma, time_points, self.rows_form, attn_export)
-        ws, logits = self._buffers(B, 2, video.device)
-        check(lib.nv_vit_forward_f32(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                     _inp_ptr(inp), params.data_ptr(),
-                                     ws.data_ptr(), ws.numel(), logits.data_ptr(), torch.cuda.current_stream().cuda_stream), "nv_vit_forward_f32")
-        self._forward_done(B, 2, ws, video)     # 2 = fp32 inference layout (truthy as `training` only for the layout queries)
-        return logits
+        return self._forward("nv_vit_forward_f32", video, 2, (params.data_ptr(),), vol_sigma=vol_sigma, time_points=time_points,
+                             attn_export=attn_export, operands=False)[1]     # (no 16-bit operand anywhere: the format is left as it is)
 
     # ------------------------------------------------------------------ fp8 inference (BASELINE.json configs[4])
     def calibrate_fp8(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, headroom: float = 2.0, out_proj: bool = True):
@@ -326,35 +346,24 @@ class VitRuntime:
                           vol_sigma=None, rows_form: Optional[int] = None) -> torch.Tensor:
         """TRAINING forward with qkv / FC1 / FC2 of every block on e4m3 operands (nv_vit_forward_fp8_train): fills the training
         workspace exactly as forward(training=True) does, so backward() follows as usual (on bf16 operands); dropout as in forward()."""
-        rows_form = self.rows_form if rows_form is None else int(rows_form)
-        _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, 0, rows_form)
-        ws, logits = self._buffers(B, True, video.device)
-        check(lib.nv_vit_forward_fp8_train(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                           _inp_ptr(inp), params.data_ptr(),
-                                           params16.data_ptr(), f8["params8"].data_ptr(), f8["colscales"].data_ptr(),
-                                           ctypes.cast(f8["act_scales"], ctypes.c_void_p), ws.data_ptr(), ws.numel(), float(dropout[0]), float(dropout[1]), int(dropout[2]),
-                                           logits.data_ptr(), torch.cuda.current_stream().cuda_stream), "nv_vit_forward_fp8_train")
-        self._forward_done(B, True, ws, video, (vol_sigma, inp, rows_form), dropout)
-        return logits
+        return self._forward("nv_vit_forward_fp8_train", video, 1, self._fp8_weights(params, params16, f8), _drop(dropout), vol_sigma=vol_sigma,
+                             rows_form=rows_form, dropout=dropout)[1]
 
     def forward_fp8(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, f8, vol_sigma=None, time_points: int = 0) -> torch.Tensor:
-        _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, time_points, self.rows_form)
-        ws, logits = self._buffers(B, False, video.device)
-        check(lib.nv_vit_forward_fp8(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                     _inp_ptr(inp), params.data_ptr(),
-                                     params16.data_ptr(), f8["params8"].data_ptr(), f8["colscales"].data_ptr(),
-                                     ctypes.cast(f8["act_scales"], ctypes.c_void_p), ws.data_ptr(), ws.numel(), logits.data_ptr(),
-                                     torch.cuda.current_stream().cuda_stream), "nv_vit_forward_fp8")
-        self._forward_done(B, False, ws, video)
-        return logits
+        return self._forward("nv_vit_forward_fp8", video, 0, self._fp8_weights(params, params16, f8), vol_sigma=vol_sigma, time_points=time_points)[1]
+
+    @staticmethod
+    def _fp8_weights(params, params16, f8):
+        return (params.data_ptr(), params16.data_ptr(), f8["params8"].data_ptr(), f8["colscales"].data_ptr(), ctypes.cast(f8["act_scales"], ctypes.c_void_p))
 
     def backward(self, dlogits: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: Optional[torch.Tensor],
                  accumulate: bool, stages: Optional[Tuple[int, int]] = None, join_aux: bool = True,
                  grads16: Optional[torch.Tensor] = None, dvideo: Optional[torch.Tensor] = None, weight_grads: bool = True,
-                 attn_grad: Optional[AttnGradExport] = None) -> None:
+                 attn_grad: Optional[AttnGradExport] = None, *, of: Optional[_Pass] = None, final: bool = False) -> None:
         """Whole backward, or only stages [first, last] (0 = head, 1+k = layer depth-1-k, depth+1 = embedding).
+        of: the pass to run against (several may be pending: siamese / two-forward losses), by default the most recent training forward.
+        final: nothing more of this pass will run although the stages stop short of the embedding - like a whole backward, the call
+        then marks the pass done (its workspace may be refilled) and its hook gradient ready.
         join_aux=False (only for ranges before the last stage): the current stream is not made to wait for the auxiliary
         stream - order the consumer of the range's gradients after `aux_stream_object()` as well.
         dvideo: fp32 tensor of the forward input's shape (any strides) that receives d loss / d video; written by the call whose
@@ -362,11 +371,7 @@ class VitRuntime:
         and `grads16` must be None (nv_vit_backward_ex).
         attn_grad (make_attn_grad_export): the gradients w.r.t. the attention probabilities, written behind the attention backward of
         every exported layer inside the stage range (nv_vit_backward_attn); needs a forward without block dropout."""
-        rec = self._cur
-        assert rec is not None, "backward needs a preceding forward(training=True)"
-        if not self.pass_is_live(rec):
-            raise RuntimeError("neurovit_amd: backward() of a forward pass whose activations have been overwritten - a later forward or train step "
-                               "has refilled its workspace (a pass keeps its workspace only until a whole backward of it has run)")
+        rec = self.backward_pass(of)
         B, ws, video = rec.B, rec.ws, rec.video
         if rec.keep[1] is not None and rec.keep[1].time_points:
             raise NotImplementedError("neurovit_amd: the fused 4D input form is forward-only (the 4D model's encoder is frozen, NeuroEncoder.py:34-36)")
@@ -399,8 +404,8 @@ class VitRuntime:
                                        int(join_aux), int(rec.rows_form), None if opts is None else ctypes.byref(opts),
                                        None if attn_grad is None else ctypes.byref(attn_grad)),
               "nv_vit_backward_attn")
-        if last == self.cfg.depth + 1:
-            rec.done = True              # the workspace may be refilled by the next training forward
+        if final or last == self.cfg.depth + 1:
+            rec.finish()
 
     def train_step(self, video: torch.Tensor, labels: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: torch.Tensor,
                    adam_m: torch.Tensor, adam_v: torch.Tensor, *, step: int, lr: float, betas, eps: float, weight_decay: float,
@@ -416,12 +421,7 @@ class VitRuntime:
         dynamic loss scale (optim.LossScaler) - GradScaler semantics on the device, needs fuse_update = 0.
         loss_opts: None, or a _cabi.LossOpts (ops.loss_opts: label smoothing, class weights, a mix table) - the step then goes
         through nv_vit_train_step_ex; the tensors it points to are the caller's to keep alive."""
-        rows_form = self.rows_form if rows_form is None else int(rows_form)
-        _cabi.set_operand_format(self.operands)
-        B, inp = self._input_form(video, vol_sigma, 0, rows_form)
-        ws = self.workspace(B, True, video.device)
-        dev = video.device
-        logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
+        B, dev = video.shape[0], video.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dlogits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
         assert labels.is_cuda and labels.dtype == torch.int64 and labels.numel() == B and labels.is_contiguous()
@@ -429,37 +429,13 @@ class VitRuntime:
                           float(grad_scale), int(bool(accumulate)), int(bool(update)), int(fuse_update), float(loss_scale),
                           None if dp is None else ctypes.cast(ctypes.pointer(dp), ctypes.c_void_p),      # _cabi.DpPlan (kept alive by the caller)
                           None if loss_scale_state is None else loss_scale_state.data_ptr())
-        if loss_opts is None:
-            check(lib.nv_vit_train_step(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                        _inp_ptr(inp),
-                                        params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr(),
-                                        ws.data_ptr(), ws.numel(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(), dlogits.data_ptr(),
-                                        ctypes.byref(hp), float(dropout[0]), float(dropout[1]), int(dropout[2]),
-                                        torch.cuda.current_stream().cuda_stream, self._aux_stream(dev)), "nv_vit_train_step")
-        else:
-            check(lib.nv_vit_train_step_ex(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video),
-                                           _inp_ptr(inp),
-                                           params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr(),
-                                           ws.data_ptr(), ws.numel(), labels.data_ptr(), logits.data_ptr(), loss.data_ptr(), dlogits.data_ptr(),
-                                           ctypes.byref(hp), ctypes.byref(loss_opts), float(dropout[0]), float(dropout[1]), int(dropout[2]),
-                                           torch.cuda.current_stream().cuda_stream, self._aux_stream(dev)), "nv_vit_train_step_ex")
-        self._keep = (vol_sigma, inp)
-        self._rows_form = rows_form
-        self._last = (B, True, ws, video)
-        self._open_pass(B, ws, video, self._keep, rows_form, dropout, done=True).dlogits = dlogits     # (a pending pass in this workspace is now stale)
-        self.generation += 1
-        self.backward_done = True                        # the Grad-CAM gradient tap holds this step's gradient
-        self._dropout = dropout
+        extra = () if loss_opts is None else (ctypes.byref(loss_opts),)
+        rec, logits = self._forward("nv_vit_train_step_ex" if extra else "nv_vit_train_step", video, 1,
+                                    (params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr()), (labels.data_ptr(),),
+                                    (loss.data_ptr(), dlogits.data_ptr(), ctypes.byref(hp)) + extra + _drop(dropout),
+                                    vol_sigma=vol_sigma, rows_form=rows_form, dropout=dropout, step=True)
+        rec.dlogits = dlogits
         return loss, logits
-
-    def note_step_replayed(self, B: int, video: torch.Tensor) -> None:
-        """A captured train step (trainer.py) has been replayed: the primary training workspace holds ITS activations and gradient taps."""
-        ws = self.workspace(B, True, video.device)
-        self._last = (B, True, ws, video)
-        self._open_pass(B, ws, video, getattr(self, "_keep", (None, None)), self._rows_form, (0.0, 0.0, 0), done=True)
-        self.generation += 1
-        self.backward_done = True
-        self._dropout = (0.0, 0.0, 0)
 
     def aux_stream_object(self, device) -> Optional[torch.cuda.Stream]:
         """The torch stream object behind the engine's auxiliary stream (None when the engine runs single-stream)."""
@@ -486,8 +462,8 @@ class VitRuntime:
 
     def tap(self, name: str, layer: int, shape, dtype) -> torch.Tensor:
         """View of a named activation inside the last forward's workspace (tests, Grad-CAM hooks)."""
-        B, training, ws, _ = self._last
-        off = lib.nv_vit_workspace_offset(ctypes.byref(self.cfg), B, int(training), name.encode(), layer)
+        B, layout, ws = self.last.B, self.last.layout, self.last.ws
+        off = lib.nv_vit_workspace_offset(ctypes.byref(self.cfg), B, layout, name.encode(), layer)
         if off < 0:
             raise KeyError(f"no workspace buffer {name!r} (layer {layer})")
         n = 1

@@ -415,12 +415,13 @@ class TrainStep:
                 import warnings
                 warnings.warn(f"neurovit_amd: the train step could not be captured as a graph ({e}); continuing with eager launches")
                 return None
-            ent = self._graphs[key] = (graph, loss, logits, fmri, labels)     # (the tensors are kept alive with the graph that reads them)
+            # (the tensors are kept alive with the graph that reads them; the pass record the captured call opened comes back with every replay)
+            ent = self._graphs[key] = (graph, loss, logits, vit._rt.last, fmri, labels)
             # the capture itself executed nothing: fall through to the replay below
-        graph, loss, logits = ent[0], ent[1], ent[2]
+        graph, loss, logits, rec = ent[:4]
         vit._refresh_shadow()
         graph.replay()
-        vit._rt.note_step_replayed(fmri.shape[0], fmri.permute(0, 3, 1, 2).unsqueeze(1))
+        vit._rt.note_step_replayed(rec)
         opt.begin_step()
         opt.step_arena(vit, self._unscaled())                            # AdamW over the arena + 16-bit shadow (mark_shadow_fresh inside)
         self._after_native(logits)

@@ -320,7 +320,8 @@ class _ViTFunction(torch.autograd.Function):
         # reflects requires_grad alone (it stays True under torch.no_grad()), so neither tells whether a graph is being built
         ctx.module = module
         out = module._run_forward(video, need_grad, extra)
-        ctx.rec = module._rt._cur if need_grad else None      # THIS pass's workspace and input: kept until its backward has run
+        ctx.rec = module._rt.current if need_grad else None   # THIS pass's workspace and input ...
+        ctx.claim = ctx.rec.claim() if need_grad else None    # ... held until its backward has run or the graph is gone
         return out
 
     @staticmethod
@@ -331,15 +332,12 @@ class _ViTFunction(torch.autograd.Function):
                 "neurovit_amd.ViT: backward() of a forward pass whose activations have been overwritten - a pass keeps its workspace "
                 "until one whole backward of it has run; a second backward (retain_graph) after another training forward or a train "
                 "step of the same module finds it refilled.")
-        rt._cur = rec                 # several passes may be pending (siamese / two-forward losses): each runs against its own workspace
         dvideo = None
         if ctx.needs_input_grad[1]:
             # the input's own strides when they describe a dense, non-overlapping tensor (the [B, H, W, D] -> [B, 1, D, H, W] permute view
             # of ViT3DEncoder: the kernel then writes the memory order it read), contiguous otherwise
             dvideo = torch.empty_like(rec.video, memory_format=torch.preserve_format)
-        ctx.module._run_backward(dlogits, dvideo)
-        if rt._last is not None and rt._last[2] is rec.ws:
-            rt.backward_done = True   # the Grad-CAM taps read the MOST RECENT forward's workspace
+        ctx.module._run_backward(rec, dlogits, dvideo)     # several passes may be pending (siamese / two-forward losses): each runs against its own workspace
         return (None, dvideo, None, None) + (None,) * len(ctx.module._plist)
 
 
@@ -728,13 +726,12 @@ class ViT(FlatArena, nn.Module):
         depth, C = self._cfg.depth, self._cfg.num_classes
         with torch.no_grad():
             dlogits = torch.nn.functional.one_hot(seed, C).to(torch.float32) if seed.dtype == torch.long else seed
-            rec = self._rt._cur
+            rec = self._rt.current
             export, maps = self._rt.make_attn_grad_export(rec.B, layers, form, rec.video.device) if layers else (None, {})
-            # stages 0 (head) .. depth - min(layers): the layers below the lowest requested one and the embedding add nothing
+            # stages 0 (head) .. depth - min(layers): the layers below the lowest requested one and the embedding add nothing; nothing more
+            # of this pass will run, and the last block's hook gradient (stage 1) is in the workspace (final)
             self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, stages=(0, depth - layers[0] if layers else 1),
-                              weight_grads=False, attn_grad=export)
-            rec.done = True                   # nothing more of this pass will run: its workspace may be refilled
-            self._rt.backward_done = True     # the last block's hook gradient (stage 1) is in the workspace
+                              weight_grads=False, attn_grad=export, final=True)
         return maps
 
     def gradcam_taps(self, video, score_grad, vol_sigma=None):
@@ -848,11 +845,8 @@ class ViT(FlatArena, nn.Module):
                 part = jobs[first:first + count]
                 ops.path_points(x, part, alphas, base, out=flat(points[:count]))
                 logits = self._run_forward(points[:count], True, (None, 0, None))
-                rec = self._rt._cur
                 dlogits = ops.class_score_grads(logits.float().contiguous(), part, cls, kind=score)
                 self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=grads[:count], weight_grads=False)
-                rec.done = True                   # nothing more of this pass will run: its workspace may be refilled
-                self._rt.backward_done = True
                 ops.path_accumulate(flat(grads[:count]), part, weights, acc)
             attributions = like_video(B)
             ops.path_finish(acc, x, base, out=flat(attributions))
@@ -861,35 +855,34 @@ class ViT(FlatArena, nn.Module):
         return {"attributions": attributions, "class_idx": cls, "score_input": score_input, "score_baseline": score_baseline, "delta": delta,
                 "alphas": alphas, "weights": weights}
 
-    def _run_backward(self, dlogits, dvideo=None):
-        """Parameter gradients of every parameter that requires one; dvideo (or None): receives d loss / d video.  With no parameter
-        requiring a gradient (a frozen model fed an input that requires one) the data-only backward runs: no gradient arena, no p.grad.
+    def _run_backward(self, rec, dlogits, dvideo=None):
+        """The backward of pass `rec` (the engine's record of the forward): parameter gradients of every parameter that requires one;
+        dvideo (or None): receives d loss / d video.  With no parameter requiring a gradient (a frozen model fed an input that requires one) the data-only backward runs: no gradient arena, no p.grad.
         Backward hooks on a block's `attend` are looked up here: the hooked layers' dP is exported by the same backward (without hooks
         nothing extra is launched) and the hooks fire once it has been queued, in reverse layer order."""
         hooked = self._attend_backward_hooked_layers()
         export, dP = (None, {})
         if hooked:
-            rec = self._rt._cur
-            if rec is not None and rec.dropout[0] > 0:
+            if rec.dropout[0] > 0:
                 raise NotImplementedError("neurovit_amd.ViT: backward hooks on `attend` with attention dropout active (train mode, dropout > 0) - "
                                           "the mask is not replayed into the gradient of the probabilities; run the attribution in eval mode")
             export, dP = self._rt.make_attn_grad_export(rec.B, hooked, "per_head", rec.video.device)
-        self._run_backward_export(dlogits, dvideo, export)
+        self._run_backward_export(rec, dlogits, dvideo, export)
         for l in sorted(dP, reverse=True):
             attend = self.transformer.layers[l][0].attend
             _fire_attend_backward_hooks(attend, _attend_backward_hooks(attend), dP[l], "neurovit_amd.ViT")
 
-    def _run_backward_export(self, dlogits, dvideo, export):
+    def _run_backward_export(self, rec, dlogits, dvideo, export):
         if not any(p.requires_grad for p in self._plist):
             if dvideo is not None or export is not None:
-                self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False, attn_grad=export)
+                self._rt.backward(dlogits, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False, attn_grad=export, of=rec)
             return
 
         def run(target, accumulate, scratch):
             if scratch:       # foreign .grad tensors: one plain backward, no gradient-bucket pipeline
-                self._rt.backward(dlogits, self._arena, self._shadow, target, accumulate=False, dvideo=dvideo, attn_grad=export)
+                self._rt.backward(dlogits, self._arena, self._shadow, target, accumulate=False, dvideo=dvideo, attn_grad=export, of=rec)
             else:
-                self._backward_into(dlogits, target, accumulate=accumulate, dvideo=dvideo, attn_grad=export)
+                self._backward_into(dlogits, target, accumulate=accumulate, dvideo=dvideo, attn_grad=export, of=rec)
         self._backward_to_grads(run)
 
     def mirrored_ranges(self):
@@ -909,10 +902,10 @@ class ViT(FlatArena, nn.Module):
         self._mirrored = sorted(out)          # the layout never changes for a constructed module
         return self._mirrored
 
-    def _backward_into(self, dlogits, grads, accumulate, dvideo=None, attn_grad=None):
+    def _backward_into(self, dlogits, grads, accumulate, dvideo=None, attn_grad=None, of=None):
         sync = self._grad_sync
         if sync is None:
-            self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, dvideo=dvideo, attn_grad=attn_grad)
+            self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, dvideo=dvideo, attn_grad=attn_grad, of=of)
             return
         from .parallel import bucket_stages
         sync.begin()
@@ -929,7 +922,7 @@ class ViT(FlatArena, nn.Module):
             # all-reduce is ordered after both streams instead
             self._rt.backward(dlogits, self._arena, self._shadow, grads, accumulate=accumulate, stages=(first, last),
                               join_aux=(last == last_stage), grads16=msg, dvideo=dvideo if last == last_stage else None,
-                              attn_grad=attn_grad)          # (each call exports the layers inside its stage range)
+                              attn_grad=attn_grad, of=of)   # (each call exports the layers inside its stage range)
             sync.bucket_ready(grads, begin, end, also_after=None if last == last_stage else self._rt.aux_stream_object(grads.device))
         sync.finish()
 
@@ -1020,17 +1013,17 @@ class ViT(FlatArena, nn.Module):
     # activations / gradients of the last block's attention LayerNorm output (Grad-CAM contract, NeuroEncoder.py:70-82)
     def last_attn_norm_output_raw(self) -> torch.Tensor:
         """[B, n, d] view into the workspace of the most recent forward (no copy): the operand format, or fp32 after an fp32 inference forward."""
-        B = self._rt._last[0]
+        last = self._rt.last
         n, d = self.pos_embedding.shape[1], self.pos_embedding.shape[2]
-        return self._rt.tap("xn1", self._cfg.depth - 1, (B, n, d), torch.float32 if self._rt._last[1] == 2 else self._dtype16())
+        return self._rt.tap("xn1", self._cfg.depth - 1, (last.B, n, d), torch.float32 if last.layout == 2 else self._dtype16())
 
     def last_attn_norm_grad_raw(self) -> torch.Tensor:
         """fp32 [B, n, d] view into the workspace; valid once a backward of the most recent training forward has run."""
-        if not self._rt.backward_done:
+        last = self._rt.last
+        if last is None or not last.grad_ready:
             raise RuntimeError("neurovit_amd.ViT: no backward pass has run for the most recent forward - the hook gradient is not available")
-        B = self._rt._last[0]
         n, d = self.pos_embedding.shape[1], self.pos_embedding.shape[2]
-        return self._rt.tap("hookg", -1, (B, n, d), torch.float32)
+        return self._rt.tap("hookg", -1, (last.B, n, d), torch.float32)
 
     def last_attn_norm_output(self) -> torch.Tensor:
         return self.last_attn_norm_output_raw().float()

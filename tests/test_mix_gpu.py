@@ -412,7 +412,7 @@ def test_native_step_with_the_options_equals_the_general_path_bitwise(VM, case):
         # the step's own d(loss)/d(logits) against the float64 formula on the step's own logits
         x, y, table = step_batch()
         want_loss, want_dl = M.ce_soft_ref(a["logits"].cpu().double().numpy(), y.cpu().numpy(), 0.1, STEP_WEIGHTS, table.cpu().numpy())
-        dl = a["vit"]._rt._cur.dlogits
+        dl = a["vit"]._rt.current.dlogits
         assert abs(a["losses"][-1].item() - want_loss) < FP32_GATE * abs(want_loss) and rel_err(dl, want_dl) < FP32_GATE
     finally:
         lib.nv_vit_set_head_step(1)

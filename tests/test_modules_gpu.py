@@ -960,8 +960,7 @@ def test_two_forward_passes_before_one_backward(nv):
     y1 = model(x1)
     assert model.gradients == {}                                             # forward only: the hook gradient does not exist yet
     y2 = model(x2)                                                           # y1's pass is pending: this one takes a second workspace
-    more = rt._pool[(2, 1, str(x1.device))]
-    assert len(more) == 1
+    assert rt.extra_workspaces(2, x1.device) == 1
     (y1.square().sum() + y2.sum()).backward()
     joint = vit.flat_gradients().clone()
     assert model.gradients.shape == (2, (S // p) ** 3 + 1, 128)              # the most recent forward's (x2's) hook gradient
@@ -973,10 +972,10 @@ def test_two_forward_passes_before_one_backward(nv):
         model(x1).square().sum().backward()
         for q in model.parameters():
             q.grad = None
-    assert len(more) == 1 and rt._cur.ws is rt.workspace(2, True, x1.device)
+    assert rt.extra_workspaces(2, x1.device) == 1 and rt.current.ws is rt.workspace(2, True, x1.device)
     for _ in range(3):                                                       # training forwards whose outputs are dropped unused: still one workspace
         model(x1)
-    assert len(more) == 1 and rt._cur.ws is rt.workspace(2, True, x1.device)
+    assert rt.extra_workspaces(2, x1.device) == 1 and rt.current.ws is rt.workspace(2, True, x1.device)
     model(x1).square().sum().backward()
     model(x2).sum().backward()                                               # accumulates into the same arena
     assert rel_err(joint, vit.flat_gradients()) < 1e-6

@@ -225,10 +225,10 @@ def test_eval_precision_switch_on_the_module(eng):
     vit = model.volume_encoder.vit3d
     with torch.no_grad():
         b16 = model(x.cuda()).clone()
-        assert vit._rt._last[1] == 0
+        assert vit._rt.last.layout == 0
         with model.precision("fp32"):
             f32 = model(x.cuda()).clone()
-            assert vit._rt._last[1] == 2
+            assert vit._rt.last.layout == 2
             act = model.activations                              # hook contract: last block's attention-LN output, fp32 here
         again = model(x.cuda())
     assert torch.equal(again, b16) and vit.eval_precision == "bf16"
@@ -241,7 +241,7 @@ def test_eval_precision_switch_on_the_module(eng):
     assert rel_l2(act, taps["transformer.layers.1.0.norm.out"]) < STAGE_TOL
     with model.precision("fp32"):                                 # a forward that records a graph is a training-arithmetic forward
         out = model(x.cuda())
-        assert out.requires_grad and vit._rt._last[1] == 1
+        assert out.requires_grad and vit._rt.last.layout == 1
     model2, _, _ = _neuro(ne, TRAINING_VIT_EVAL_PRECISION="fp32")
     model2.eval()
     with torch.no_grad():
@@ -272,16 +272,16 @@ def test_trainer_validate_runs_in_fp32_by_default(eng, tmp_path, monkeypatch):
     tr = Trainer(cfg, model, DS(8, 1), val)
     loss32, acc32 = tr.validate(0)
     vit = model.volume_encoder.vit3d
-    assert vit._rt._last[1] == 2 and vit.eval_precision == "bf16"
+    assert vit._rt.last.layout == 2 and vit.eval_precision == "bf16"
     with torch.no_grad():
         lg = ref_cpu.neuro_forward({k: v for k, v in sd.items()}, dict(cfg, DEVICE="cpu"), val.x)
         want = 0.5 * (float(train_step.cross_entropy(lg[:4], val.y[:4])) + float(train_step.cross_entropy(lg[4:], val.y[4:])))
     assert abs(loss32 - want) < 2e-5 * max(1.0, abs(want)) + 1e-5          # validate() rounds to 5 decimals
     tr.evaluate_samples()
-    assert vit._rt._last[1] == 2
+    assert vit._rt.last.layout == 2
     tr.validation_precision = "bf16"
     tr.validate(0)
-    assert vit._rt._last[1] == 0
+    assert vit._rt.last.layout == 0
 
 
 def _neuro_sd(S, p, seed):
@@ -326,7 +326,7 @@ def test_neuro4d_fp32_eval(eng, golden):
     vit = model.volume_encoder.vit3d
     with torch.no_grad(), model.precision("fp32"):
         logits = model(x)
-        assert vit._rt._last[1] == 2
+        assert vit._rt.last.layout == 2
         vols = x.permute(0, 4, 1, 2, 3).reshape(2 * T, S, S, S)
         ev = rel_err(model.volume_encoder(vols), g["volume_logits"])
         x8 = W.make_volume((2, S, S, S, 8), 24).cuda()

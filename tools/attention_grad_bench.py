@@ -110,10 +110,8 @@ def main():
     def plain():
         """what attention_gradients runs, without the export: training-layout forward + data-only backward of the layers"""
         logits = model._run_forward(video, True)
-        rec = rt._cur
         dlogits = torch.nn.functional.one_hot(logits.argmax(dim=1), cfg["num_classes"]).float()
-        rt.backward(dlogits, model._arena, model._shadow, None, accumulate=False, stages=(0, depth), weight_grads=False)
-        rec.done = True
+        rt.backward(dlogits, model._arena, model._shadow, None, accumulate=False, stages=(0, depth), weight_grads=False, final=True)
 
     forms = {
         "plain": plain,
