@@ -762,6 +762,22 @@ int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float* video, co
                          int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
                          unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
                          const nv_vit_attn_grad_export* attn_grad);
+/* (added within revision 8 - a new symbol, nothing existing changes) the backward from a gradient on the FINAL TOKENS instead of the
+ * logits: nv_vit_backward_ex's arguments with dtokens fp32 [B n, dim] dense (16-byte aligned) in the place of dlogits - the gradient
+ * w.r.t. the last block's output, cls rows included.  Any token-level objective (masked reconstruction, distillation on tokens,
+ * contrastive patch losses) differentiates the encoder through it.  Stage 0 of the range is a seeding launch (nv_token_grad_seed) in
+ * the head's place: it leaves what nv_head_bwd leaves for stage 1 - the running residual gradient g = dtokens, the last layer's 16-bit
+ * gradient cvt(dtokens * mask) under the dropout mask of site 4 (depth - 1) + 3, and the last layer's FC2 bias gradient = the column sums
+ * of dtokens * mask (per-workgroup partials, then nv_reduce_multi: a fixed order) - and stages 1 .. depth + 1 are those of nv_vit_backward_ex.
+ * The head takes no part: its gradient range (nv_vit_stage_param_range of stage 0) is written as zeros with accumulate = 0 and left
+ * alone with accumulate = 1 (the full form; the data-only form writes no arena).  opts and grads16 behave as in nv_vit_backward_ex.
+ * The forward must have run its last block on EVERY row (nv_vit_input.rows_form = 1) and the same value must arrive here: refused
+ * (NV_ERR_ARG) when these arguments select the cls-rows form, and for a NULL or misaligned dtokens.  Not after a forward of the fused 4D
+ * input form (as nv_vit_backward_ex). */
+int nv_vit_backward_tokens(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                           const void* params16, void* workspace, long ws_bytes, const float* dtokens, float* grads, void* grads16,
+                           int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                           unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts);
 int nv_vit_stage_param_range(const nv_vit_config* cfg, int stage, long* begin, long* end);
 /* pool='cls': the last block's out-projection / LayerNorm / FeedForward, forward and backward, on the B cls rows only (whenever the
  * block dropout is off; training additionally B <= 4).  Logits and every gradient are unchanged (the other rows never reach the
@@ -1011,6 +1027,49 @@ typedef struct nv_affine_config {
 int nv_affine_params(const nv_affine_config* cfg, unsigned long seed, unsigned long step, int rank, int B, int* table, void* stream);
 int nv_affine_apply(const float* src, const long* strides5, int B, const int* in3, int T, const int* table, const int* roi3, float fill,
                     float* out, void* stream);
+
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) masked-volume pretraining (SimMIM / MAE on volumes): the
+ * device steps around the encoder's forward and its token-level backward (nv_vit_backward_tokens).  No call allocates, synchronises or reads
+ * anything back, and the host draws no random number; every argument is checked first (NV_ERR_ARG).
+ * nv_mim_labels: writes labels int32 [B, N] (DEVICE), N = G0 G1 G2 <= 4096 patches of the grid grid3 = {G0, G1, G2} (HOST array; patch
+ *   indices by nv_mask_patches' token rule, t = g2 G0 G1 + g0 G1 + g1).  Per sample a permutation of 0 .. N - 1 in which label < m means
+ *   masked: nv_mask_patches with the job (b, 0, m) writes the masked batch.  A mask unit is a cube of u^3 patches (`unit` = u divides
+ *   G0, G1 and G2; U_a = G_a / u, U = U0 U1 U2 >= 2 units, indexed q = (g2 / u) U0 U1 + (g0 / u) U1 + g1 / u).  The draw rule, with
+ *   nv_hash64 as for nv_augment_params, in a domain of its own (no augmentation draw is reused):
+ *     seed_p = nv_hash64(nv_hash64(seed, rank), 0x4D494D);  h_q = nv_hash64(seed_p, ((s 2^32 + b) 4096 + q) mod 2^64)  for unit q of sample b at step s
+ *     key_q = (h_q >> 40) 2^-24 (exact in fp32);  rank_q = #{ j : key_j > key_q or (key_j == key_q and j < q) }   (nv_token_ranks' rule)
+ *     labels[b, t] = rank_q(t) u^3 + ((g2 mod u) u + g0 mod u) u + g1 mod u
+ *   so the first m_u = clamp(floor(ratio U + 0.5), 1, U - 1) units in rank order are masked, as whole cubes, and the masked-patch count
+ *   m = m_u u^3 is exact and known on the host: nv_mim_masked_count (ratio in (0, 1); NV_ERR_ARG = -1 otherwise).  A step can be replayed
+ *   from (seed, rank, step); ranks and steps draw different masks.  One workgroup per sample, keys ranked in LDS.
+ * nv_recon_loss: pred fp32 [B n, ldp] (n = N + 1 token rows per sample, row 0 the cls row; ldp >= P8 = 8 ceil(P / 8), P = p0 p1 p2, a
+ *   multiple of 4, 16-byte aligned), the ORIGINAL dense volume x fp32 [B, S0, S1, S2] (size3 / patch3 HOST arrays as for nv_mask_patches,
+ *   P <= 4096), labels int32 [B, N] and m as above, kind NV_RECON_L1 / NV_RECON_L2, norm_pix 0 / 1, loss_scale > 0.
+ *   For every masked row (labels[b, t] < m, row b n + 1 + t) the target is patch t in the engine's patchify order - element
+ *   (a0 p1 + a1) p2 + a2 is voxel (g0 p0 + a0, g1 p1 + a1, g2 p2 + a2), the '(p1 p2 pf c)' order of vit_3d.py:92 with c = 1 - and with
+ *   norm_pix it is standardised by the patch mean and the UNBIASED variance, (v - mean) / sqrt(var + 1e-6) (MAE's rule), the statistics
+ *   and everything behind them in double.  With diff = pred - target:
+ *     loss  = sum |diff| / (B m P)  or  sum diff^2 / (B m P)
+ *     dpred = loss_scale sign(diff) / (B m P)  or  loss_scale 2 diff / (B m P), rounded ONCE to the operand format (nv_operand_format)
+ *   dpred [B n, ldd] (16-bit, ldd >= P8 a multiple of 8, 16-byte aligned): every other cell - cls rows, rows that are not masked, columns
+ *   P .. ldd - 1 - is written as zero, every cell exactly once; pred is not read on those rows.  partials double [B n]: the rows' loss
+ *   terms (0 for rows that are not masked); a second launch of one workgroup sums them in index order into loss fp32 [1] (the loss is
+ *   NOT multiplied by loss_scale).  One workgroup per row; the patch is read once (16-byte loads when x is 16-byte aligned and S2 and p2
+ *   are multiples of 4, dwords otherwise) and kept in LDS between the statistics and the loss pass.  No atomics: the same bits on every run.
+ * nv_token_grad_seed: dtokens fp32 [M, d] dense -> g fp32 [M, d] = dtokens, g16 [M, d] (operand format) = cvt(dtokens * mask) with the
+ *   dropout mask (drop_seed, drop_p) of the dense [M, d] tensor (element row d + col, as nv_ln_bwd applies it; drop_p = 0: none), and
+ *   partials fp32 [nv_token_grad_seed_rows(M), d] (may be NULL) = per-workgroup column sums of dtokens * mask, to be summed by
+ *   nv_reduce_multi.  The launch in front of the encoder's backward when the loss sits on its tokens (nv_vit_backward_tokens). */
+#define NV_RECON_L1 0
+#define NV_RECON_L2 1
+int nv_mim_masked_count(const int* grid3, int unit, double ratio);
+int nv_mim_labels(unsigned long seed, unsigned long step, int rank, int B, const int* grid3, int unit, int* labels, void* stream);
+int nv_recon_loss(const float* pred, long ldp, const float* x, int B, const int* size3, const int* patch3, const int* labels, int m, int kind,
+                  int norm_pix, float loss_scale, void* dpred, long ldd, double* partials, float* loss, void* stream);
+long nv_token_grad_seed_workspace_bytes(int M, int d);
+int nv_token_grad_seed_rows(int M);
+int nv_token_grad_seed(const float* dtokens, int M, int d, float* g, void* g16, float* partials, long partial_bytes, unsigned long drop_seed,
+                       float drop_p, void* stream);
 
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a

@@ -24,4 +24,7 @@ def __getattr__(name):
     if name in ("param_groups", "LRSchedule", "set_group_lrs"):      # the optimizer half of the fine-tuning recipe
         from . import optim
         return getattr(optim, name)
+    if name in ("MaskedPretrainStep", "ReconstructionHead"):         # masked-volume pretraining of the 3D encoder
+        from . import pretrain
+        return getattr(pretrain, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -730,6 +730,7 @@ struct BwdCall {
   const nv_adamw_arena* fuse; int fuse_mode;        // nv_vit_train_step, fuse_update (see backward_impl)
   const nv_vit_backward_opts* opts;                 // nv_vit_backward_ex: the input gradient, and the data-only form (weight_grads = 0: no gradient arena, nothing on [A])
   const nv_vit_attn_grad_export* attn_grad;
+  const float* dtokens;                             // nv_vit_backward_tokens: the gradient on the final tokens; stage 0 is then seed_tokens, not the head
 };
 
 // Last block in the cls-rows form (see g_cls_tail): the residual gradient is zero outside the B cls rows until the attention
@@ -882,6 +883,25 @@ struct Bwd {
   }
 };
 
+
+// Stage 0 of nv_vit_backward_tokens, in the head's place: g = dtokens, the last layer's g16 = cvt(dtokens * mask) and its FC2 bias gradient
+// (column sums of dtokens * mask: per-workgroup partials, then nv_reduce_multi).  The partials (at most M rows of d floats) go into the dxn
+// buffer, [M, d] fp32, which only the main stream uses and which the last layer's FeedForward backward rewrites behind the reduction.
+// The head's own gradient range is zeros unless the call accumulates.
+int seed_tokens(const Bwd& X) {
+  const BwdCall& c = X.c; const Dims& D = X.D; const ParamTab& T = X.T; const WS& W = X.W;
+  float* partials = X.wg ? (float*)(X.ws + W.dxn) : nullptr;
+  RUN(nv_token_grad_seed(c.dtokens, X.M, X.d, X.g, X.ws + W.scratch(D.L - 1).g16, partials, (long)X.M * X.d * 4, site_seed(c.drop_seed, 4 * (D.L - 1) + 3), c.drop_p, X.S));
+  if (!X.wg) return NV_OK;
+  const nv_reduce_job job = {partials, nv_token_grad_seed_rows(X.M), X.d, 1, {X.GR(T.layer[D.L - 1].b2), nullptr, nullptr}, X.acc};
+  RUN(nv_reduce_multi(&job, 1, X.S));
+  if (!X.acc && hipMemsetAsync(X.GR(T.hg), 0, (size_t)(T.total - T.hg) * sizeof(float), X.S) != hipSuccess) {
+    nv_set_error("nv_vit_backward_tokens: clearing the head's gradient range failed");
+    return NV_ERR_HIP;
+  }
+  return NV_OK;
+}
+
 }  // namespace
 
 // The argument checks and the protocol between the main stream [S] and the auxiliary stream [A]: the stages above say what is launched, this says where and when.
@@ -900,7 +920,7 @@ static int backward_impl(const Layout& Y, const nv_vit_config* cfg, const BwdCal
   NV_CHECK_ARG(!fuse || !c.attn_grad, "nv_vit_backward: the optimizer update during the backward pass exports no attention gradients");
   NV_CHECK_ARG(!opts || !opts->dvideo || opts->dvideo_strides5, "nv_vit_backward_ex: dvideo needs dvideo_strides5");
   NV_CHECK_ARG(wg || (!c.grads && !c.grads16), "nv_vit_backward_ex: the data-only backward (weight_grads = 0) writes no gradient arena - pass grads = grads16 = NULL");
-  NV_CHECK_ARG(c.video && c.strides5 && c.params && c.params16 && c.workspace && c.dlogits && (c.grads || !wg), "nv_vit_backward: null pointer");
+  NV_CHECK_ARG(c.video && c.strides5 && c.params && c.params16 && c.workspace && (c.dlogits || c.dtokens) && (c.grads || !wg), "nv_vit_backward: null pointer");
   NV_CHECK_ARG(c.ws_bytes >= W.total, "nv_vit_backward: workspace too small (%ld < %ld) - forward must run with training=1", c.ws_bytes, W.total);
   NV_CHECK_ARG(nv_aligned16(c.grads) && nv_aligned16(c.grads16), "nv_vit_backward: grads / grads16 must be 16-byte aligned");
   NV_CHECK_ARG(c.first_stage >= 0 && c.last_stage <= D.L + 1 && c.first_stage <= c.last_stage, "nv_vit_backward_stages: bad stage range [%d, %d]", c.first_stage, c.last_stage);
@@ -911,7 +931,7 @@ static int backward_impl(const Layout& Y, const nv_vit_config* cfg, const BwdCal
   const Bwd X{cfg, c, D, Y.T, W, ws, c.params, (const r16*)c.params16, (float*)(ws + W.g), wg, cls_tail_wanted(D, 1, c.drop_p, c.rows_form), D.M, D.d, c.accumulate,
               nv_gemm_tile_rows(1, D.M, D.m, D.d, D.d, D.m), 1.0f / sqrtf((float)D.dh), S, A};
   // (no S -> A ordering here: everything the auxiliary stream does in this call is queued behind a signal of the main stream below)
-  if (c.first_stage == 0) RUN(X.bwd_head());
+  if (c.first_stage == 0) RUN(c.dtokens ? seed_tokens(X) : X.bwd_head());
 
   // One cross-stream event per layer in each direction (an event record costs several microseconds of queue time): the main
   // stream signals once, after the attention backward; the auxiliary stream then runs, one layer behind the main stream,
@@ -1022,6 +1042,24 @@ extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* 
                                   unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts) {
   return nv_vit_backward_attn(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
                               drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, opts, nullptr);
+}
+
+extern "C" int nv_vit_backward_tokens(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                                      const void* params16, void* workspace, long ws_bytes, const float* dtokens, float* grads, void* grads16,
+                                      int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                                      unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts) {
+  NV_CHECK_ARG(!opts || opts->struct_size == (int)sizeof(nv_vit_backward_opts), "nv_vit_backward_tokens: opts->struct_size %d != %d (ABI revision mismatch)",
+               opts ? opts->struct_size : 0, (int)sizeof(nv_vit_backward_opts));
+  NV_CHECK_ARG(dtokens && nv_aligned16(dtokens), "nv_vit_backward_tokens: dtokens is NULL or not 16-byte aligned");
+  Layout Y; RUN(make_layout(cfg, B, 1, Y));
+  NV_CHECK_ARG(!cls_tail_wanted(Y.D, 1, drop_p, rows_form), "nv_vit_backward_tokens: rows_form = %d selects the cls-rows form of the last block for B = %d - the "
+               "forward must run every row (nv_vit_input.rows_form = 1) and this call must be given the same value", rows_form, B);
+  BwdCall c{};
+  c.video = video; c.strides5 = strides5; c.params = params; c.params16 = params16; c.workspace = workspace; c.ws_bytes = ws_bytes;
+  c.dtokens = dtokens; c.grads = grads; c.grads16 = grads16; c.accumulate = accumulate; c.first_stage = first_stage; c.last_stage = last_stage;
+  c.drop_p = drop_p; c.emb_drop_p = emb_drop_p; c.drop_seed = drop_seed; c.stream = stream; c.aux_stream = aux_stream;
+  c.join_aux = join_aux; c.rows_form = rows_form; c.opts = opts;
+  return backward_impl(Y, cfg, c);
 }
 
 extern "C" int nv_vit_backward(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,

@@ -77,14 +77,14 @@ class _Pass:
     """One forward and what a backward of it, or a tap into its workspace, needs: batch, layout (0 inference, 1 training, 2 fp32), workspace,
     input (the backward re-gathers the patches), input form `keep` = (vol_sigma, nv_vit_input), form of the last block, dropout draw.
     `done`: a whole backward has run - the workspace may be refilled.  `grad_ready`: a backward has left the hook gradient in the workspace."""
-    __slots__ = ("B", "layout", "ws", "video", "keep", "rows_form", "dropout", "dlogits", "done", "grad_ready", "_claim", "__weakref__")
+    __slots__ = ("B", "layout", "ws", "video", "keep", "rows_form", "dropout", "dlogits", "dtokens", "done", "grad_ready", "_claim", "__weakref__")
 
     class _Claim:
         __slots__ = ("__weakref__",)
 
     def __init__(self, B, layout, ws, video, keep=(None, None), rows_form=0, dropout=(0.0, 0.0, 0), done=False):
         self.B, self.layout, self.ws, self.video, self.keep, self.rows_form, self.dropout = B, int(layout), ws, video, keep, rows_form, dropout
-        self.dlogits, self.done, self.grad_ready, self._claim = None, done, done, None
+        self.dlogits, self.dtokens, self.done, self.grad_ready, self._claim = None, None, done, done, None
 
     def claim(self):
         """A token for whoever needs this pass's activations later (an autograd node keeps it on its ctx): the pass is held while it is alive."""
@@ -356,10 +356,11 @@ class VitRuntime(PassLedger):
     def _fp8_weights(params, params16, f8):
         return (params.data_ptr(), params16.data_ptr(), f8["params8"].data_ptr(), f8["colscales"].data_ptr(), ctypes.cast(f8["act_scales"], ctypes.c_void_p))
 
-    def backward(self, dlogits: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, grads: Optional[torch.Tensor],
+    def backward(self, dlogits: Optional[torch.Tensor], params: torch.Tensor, params16: torch.Tensor, grads: Optional[torch.Tensor],
                  accumulate: bool, stages: Optional[Tuple[int, int]] = None, join_aux: bool = True,
                  grads16: Optional[torch.Tensor] = None, dvideo: Optional[torch.Tensor] = None, weight_grads: bool = True,
-                 attn_grad: Optional[AttnGradExport] = None, *, of: Optional[_Pass] = None, final: bool = False) -> None:
+                 attn_grad: Optional[AttnGradExport] = None, *, of: Optional[_Pass] = None, final: bool = False,
+                 dtokens: Optional[torch.Tensor] = None) -> None:
         """Whole backward, or only stages [first, last] (0 = head, 1+k = layer depth-1-k, depth+1 = embedding).
         of: the pass to run against (several may be pending: siamese / two-forward losses), by default the most recent training forward.
         final: nothing more of this pass will run although the stages stop short of the embedding - like a whole backward, the call
@@ -370,13 +371,20 @@ class VitRuntime(PassLedger):
         stages contain the embedding.  weight_grads=False: the data-only backward - no parameter gradient is produced, `grads`
         and `grads16` must be None (nv_vit_backward_ex).
         attn_grad (make_attn_grad_export): the gradients w.r.t. the attention probabilities, written behind the attention backward of
-        every exported layer inside the stage range (nv_vit_backward_attn); needs a forward without block dropout."""
+        every exported layer inside the stage range (nv_vit_backward_attn); needs a forward without block dropout.
+        dtokens (instead of dlogits, which is then None): fp32 [B, n, dim] or [B n, dim], the gradient w.r.t. the last block's output, cls rows
+        included - the backward of a loss on the tokens (nv_vit_backward_tokens).  The head takes no part: its gradient range is zeroed
+        (left alone when accumulating).  The forward must have run with rows_form=1; no attention-gradient export in this form."""
+        if (dlogits is None) == (dtokens is None):
+            raise ValueError("neurovit_amd: backward() takes dlogits or dtokens, not both and not neither")
         rec = self.backward_pass(of)
         B, ws, video = rec.B, rec.ws, rec.video
         if rec.keep[1] is not None and rec.keep[1].time_points:
             raise NotImplementedError("neurovit_amd: the fused 4D input form is forward-only (the 4D model's encoder is frozen, NeuroEncoder.py:34-36)")
         first, last = (0, self.cfg.depth + 1) if stages is None else stages
         _cabi.set_operand_format(self.operands)
+        if dtokens is not None:
+            return self._backward_tokens(rec, dtokens, params, params16, grads, accumulate, first, last, join_aux, grads16, dvideo, weight_grads, attn_grad, final)
         if first == 0:
             rec.dlogits = dlogits.contiguous().float()
         if attn_grad is not None and rec.dropout[0] > 0:
@@ -404,6 +412,41 @@ class VitRuntime(PassLedger):
                                        int(join_aux), int(rec.rows_form), None if opts is None else ctypes.byref(opts),
                                        None if attn_grad is None else ctypes.byref(attn_grad)),
               "nv_vit_backward_attn")
+        if final or last == self.cfg.depth + 1:
+            rec.finish()
+
+    def _backward_tokens(self, rec, dtokens, params, params16, grads, accumulate, first, last, join_aux, grads16, dvideo, weight_grads, attn_grad, final) -> None:
+        """backward(dtokens=...): the checks that belong to this form, then nv_vit_backward_tokens"""
+        B, ws, video, c = rec.B, rec.ws, rec.video, self.cfg
+        if attn_grad is not None:
+            raise NotImplementedError("neurovit_amd: backward(dtokens=...) exports no attention gradients")
+        if rec.rows_form != 1:
+            raise ValueError("neurovit_amd: backward(dtokens=...) needs a forward whose last block ran on every row - forward(..., rows_form=1)")
+        H, Wd, p1, p2 = image_hw(c)
+        n = (c.frames // c.frame_patch_size) * (H // p1) * (Wd // p2) + 1
+        if not dtokens.is_cuda or dtokens.numel() != B * n * c.dim or dtokens.shape[-1] != c.dim:
+            raise ValueError(f"neurovit_amd: dtokens of shape {tuple(dtokens.shape)} on {dtokens.device}, expected a device tensor [{B}, {n}, {c.dim}]")
+        if dvideo is not None:
+            if rec.keep[0] is not None:
+                raise NotImplementedError("neurovit_amd: no input gradient of a forward on RAW volumes (vol_sigma)")
+            assert dvideo.is_cuda and dvideo.dtype == torch.float32 and dvideo.shape == video.shape and dvideo.device == video.device
+        if not weight_grads:
+            assert grads is None and grads16 is None, "the data-only backward writes no gradient arena"
+        if first == 0:
+            rec.dtokens = dtokens.contiguous().float()      # (kept with the pass: a staged backward's later calls pass the same pointer)
+        elif rec.dtokens is None:
+            raise RuntimeError("neurovit_amd: backward(dtokens=...) of stages that start behind stage 0, whose seeding launch has not run for this pass")
+        opts = None
+        if dvideo is not None or not weight_grads:
+            dstrides = None if dvideo is None else ops.strides5(dvideo)
+            opts = BackwardOpts(ctypes.sizeof(BackwardOpts), None if dvideo is None else dvideo.data_ptr(),
+                                None if dstrides is None else ctypes.cast(dstrides, ctypes.c_void_p), int(bool(weight_grads)))
+        check(lib.nv_vit_backward_tokens(ctypes.byref(c), B, video.data_ptr(), ops.strides5(video), params.data_ptr(), params16.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), rec.dtokens.data_ptr(), None if grads is None else grads.data_ptr(),
+                                         None if grads16 is None else grads16.data_ptr(), int(accumulate), first, last, float(rec.dropout[0]),
+                                         float(rec.dropout[1]), int(rec.dropout[2]), torch.cuda.current_stream().cuda_stream,
+                                         self._aux_stream(video.device) if weight_grads else None, int(join_aux), int(rec.rows_form),
+                                         None if opts is None else ctypes.byref(opts)), "nv_vit_backward_tokens")
         if final or last == self.cfg.depth + 1:
             rec.finish()
 

@@ -1144,3 +1144,79 @@ def gemm_lnfold(X16: torch.Tensor, Wg16: torch.Tensor, stats: torch.Tensor, cols
     check(lib.nv_gemm_lnfold(int(gelu), M, N, K, _p(X16), X16.stride(0), _p(Wg16), Wg16.stride(0), _p(stats), _p(colsum), _p(fbias), float(eps), _p(out), out.stride(0),
                              _stream()), "nv_gemm_lnfold")
     return out
+
+
+# ---- masked-volume pretraining (csrc/pretrain.hip)
+RECON_KINDS = {"l1": 0, "l2": 1}        # NV_RECON_L1 / NV_RECON_L2
+
+
+def mim_masked_count(grid, unit: int, ratio: float) -> int:
+    """Patches per volume that nv_mim_labels' tables mask for (grid, unit, ratio): clamp(floor(ratio U + 0.5), 1, U - 1) u^3 with U the number
+    of mask units.  A host-side function of the library (nv_mim_masked_count); ValueError for a unit that does not divide the grid or a
+    ratio outside (0, 1)."""
+    (g3, g3p) = _int3_ptr(_triple(grid, "grid"))
+    m = lib.nv_mim_masked_count(g3p, int(unit), float(ratio))
+    if m < 0:
+        raise ValueError(f"neurovit_amd: mim_masked_count: {_cabi.last_error()}")
+    return m
+
+
+def mim_labels(B: int, grid, unit: int, seed: int, step: int, rank: int = 0, device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [B, N] label tables of a fresh random mask per sample, drawn and ranked on the device from (seed, rank, step, sample, unit):
+    label < mim_masked_count(grid, unit, ratio) means masked, so mask_patches with the jobs (b, 0, m) writes the masked batch.
+    nv_mim_labels, one launch; nothing is read back."""
+    grid = _triple(grid, "grid")
+    N = grid[0] * grid[1] * grid[2]
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.int32, device=device)
+    _need_cuda(out)
+    assert out.shape == (B, N) and out.dtype == torch.int32 and out.is_contiguous()
+    (g3, g3p) = _int3_ptr(grid)
+    check(lib.nv_mim_labels(int(seed), int(step), int(rank), B, g3p, int(unit), _p(out), _stream()), "nv_mim_labels")
+    return out
+
+
+def recon_loss(pred: torch.Tensor, x: torch.Tensor, labels: torch.Tensor, m: int, patch, kind: str = "l1", norm_pix: bool = True,
+               loss_scale: float = 1.0, dpred: Optional[torch.Tensor] = None):
+    """pred f32 [B n, >= P8] (row-strided 2-D view, n = N + 1 rows per volume, the cls row first), the ORIGINAL volumes x f32 [B, S0, S1, S2],
+    labels int32 [B, N] (mim_labels) and the masked-patch count m -> (loss f32 [1], dpred [B n, ldd] in the operand format, partials f64 [B n]):
+    the L1 / L2 reconstruction loss over the masked patches (norm_pix: targets standardised per patch, MAE's rule) and its gradient times
+    loss_scale; every cell of dpred outside the masked rows' first P columns is written as zero.  nv_recon_loss, two launches."""
+    _need_cuda(pred, x, labels, dpred)
+    patch = _triple(patch, "patch")
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()
+    B, size = x.shape[0], tuple(x.shape[1:])
+    if any(s % p for s, p in zip(size, patch)):
+        raise ValueError(f"neurovit_amd: recon_loss: volume {size} is not a whole number of {patch} patches")
+    N = (size[0] // patch[0]) * (size[1] // patch[1]) * (size[2] // patch[2])
+    P = patch[0] * patch[1] * patch[2]
+    P8 = (P + 7) // 8 * 8
+    rows = B * (N + 1)
+    assert pred.dim() == 2 and pred.dtype == torch.float32 and pred.shape[0] == rows and pred.shape[1] >= P8 and pred.stride(1) == 1
+    assert labels.shape == (B, N) and labels.dtype == torch.int32 and labels.is_contiguous()
+    if dpred is None:
+        dpred = torch.empty((rows, P8), dtype=op16(), device=x.device)
+    assert dpred.dim() == 2 and dpred.dtype == op16() and dpred.shape[0] == rows and dpred.shape[1] >= P8 and dpred.stride(1) == 1 and dpred.stride(0) == dpred.shape[1]
+    partials = torch.empty(rows, dtype=torch.float64, device=x.device)
+    loss = torch.empty(1, dtype=torch.float32, device=x.device)
+    (s3, s3p), (p3, p3p) = _int3_ptr(size), _int3_ptr(patch)
+    check(lib.nv_recon_loss(_p(pred), pred.stride(0), _p(x), B, s3p, p3p, _p(labels), int(m), RECON_KINDS[kind], int(bool(norm_pix)), float(loss_scale),
+                            _p(dpred), dpred.stride(0), _p(partials), _p(loss), _stream()), "nv_recon_loss")
+    return loss, dpred, partials
+
+
+def token_grad_seed(dtokens: torch.Tensor, drop_seed: int = 0, drop_p: float = 0.0):
+    """dtokens f32 [M, d] -> (g f32 = dtokens, g16 = cvt(dtokens * mask), colsum f32 [d] of dtokens * mask): what nv_vit_backward_tokens
+    queues in the head's place (nv_token_grad_seed + nv_reduce_multi)."""
+    _need_cuda(dtokens)
+    assert dtokens.dim() == 2 and dtokens.dtype == torch.float32 and dtokens.is_contiguous()
+    M, d = dtokens.shape
+    g = torch.empty_like(dtokens)
+    g16 = torch.empty((M, d), dtype=op16(), device=dtokens.device)
+    nb = lib.nv_token_grad_seed_workspace_bytes(M, d)
+    part = torch.empty((lib.nv_token_grad_seed_rows(M), d), dtype=torch.float32, device=dtokens.device)
+    assert part.numel() * 4 == nb
+    check(lib.nv_token_grad_seed(_p(dtokens), M, d, _p(g), _p(g16), _p(part), nb, int(drop_seed), float(drop_p), _stream()), "nv_token_grad_seed")
+    colsum = torch.empty(d, dtype=torch.float32, device=dtokens.device)
+    reduce_multi([(part, d, (colsum,), False)])
+    return g, g16, colsum

@@ -616,6 +616,9 @@ class Trainer:
         `validate` evaluates behind the raw model (VALIDATION_EMA: false turns that off) and `run` saves as model-e{N}-ema.pth;
         TRAINING_SAVE_STATE writes state-e{N}.pth / last_state.pth (TrainStep.state_dict, the batch counter, torch's CPU generator) beside
         the model files, and TRAINING_RESUME_FROM continues such a run at the next epoch.  With none of them set nothing changes.
+      * TRAINING_OBJECTIVE: "mim" (with PRETRAIN_MASK_RATIO / _MASK_UNIT / _LOSS / _NORM_PIX) pre-trains the 3D encoder on the volumes alone
+        (pretrain.MaskedPretrainStep): labels are ignored, `validate` reports the reconstruction loss under fixed masks, and `run` writes
+        recon-head-e{N}.pth beside model-e{N}.pth, which loads into a NeuroEncoder for fine-tuning.  Absent: the labelled step.
     """
 
     def __init__(self, config, model, dataset_train, dataset_val):
@@ -635,10 +638,14 @@ class Trainer:
         smoothing, class_weights = self.loss_options_from_config(config)
         self.criterion = CrossEntropyLoss(weight=class_weights)          # validation: never smoothed, never mixed; it carries the class weights
         self.save_state, self.resume_from = self.state_options_from_config(config)
-        self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
-                              max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights,
-                              **self.ema_from_config(config),
-                              **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
+        self.pretrain = self.objective_from_config(config)             # None: the supervised step, as ever
+        if self.pretrain is None:
+            self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
+                                  max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights,
+                                  **self.ema_from_config(config),
+                                  **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
+        else:
+            self.step = self._pretrain_step(config, model)
         self.validate_ema = bool(config.get('VALIDATION_EMA', True))
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
@@ -659,6 +666,36 @@ class Trainer:
         self.start_epoch = 0
         if self.resume_from is not None:
             self._resume(self.resume_from)
+
+    @staticmethod
+    def objective_from_config(config):
+        """TRAINING_OBJECTIVE (optional; the reference's config files have no such key): absent, None or "supervised" = None, the
+        labelled step.  "mim" = masked-volume pretraining (pretrain.MaskedPretrainStep): the labels of the batches are ignored, and the
+        result is its arguments from PRETRAIN_MASK_RATIO (default 0.6), PRETRAIN_MASK_UNIT (1), PRETRAIN_LOSS ("l1") and
+        PRETRAIN_NORM_PIX (true), checked here (pretrain.check_mask_options)"""
+        objective = config.get('TRAINING_OBJECTIVE', None)
+        if objective is None or objective == "supervised":
+            return None
+        if objective != "mim":
+            raise ValueError(f"TRAINING_OBJECTIVE must be 'supervised' or 'mim', got {objective!r}")
+        from .pretrain import check_mask_options
+        pick = lambda key, default: default if config.get(key, None) is None else config[key]
+        out = dict(mask_ratio=pick('PRETRAIN_MASK_RATIO', 0.6), mask_unit=pick('PRETRAIN_MASK_UNIT', 1), loss=pick('PRETRAIN_LOSS', "l1"),
+                   norm_pix=pick('PRETRAIN_NORM_PIX', True))
+        check_mask_options(config['TRAINING_VIT_INPUT_SIZE'] // config['TRAINING_VIT_PATCH_SIZE'], **out)
+        return out
+
+    def _pretrain_step(self, config, model):
+        """The step of TRAINING_OBJECTIVE "mim".  What belongs to the labelled objective does not go with it (ValueError): Mixup / CutMix,
+        label smoothing, class weights, a weight average, clipping, accumulation."""
+        from .pretrain import MaskedPretrainStep
+        clash = [k for k in ('AUGMENT_MIXUP_ALPHA', 'AUGMENT_CUTMIX_ALPHA', 'TRAINING_CLASS_WEIGHTS', 'TRAINING_EMA_DECAY', 'TRAINING_GRAD_CLIP')
+                 if config.get(k, None) is not None]
+        clash += [k for k in ('TRAINING_LABEL_SMOOTHING', 'USE_ACCUMULATION') if config.get(k, None)]
+        if clash:
+            raise ValueError("TRAINING_OBJECTIVE 'mim' does not go with " + ", ".join(clash))
+        return MaskedPretrainStep(model, fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0), rank=self._rank(), **self.pretrain,
+                                  **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
 
     @staticmethod
     def ema_from_config(config) -> dict:
@@ -840,6 +877,9 @@ class Trainer:
             self.validate(epoch)
             torch.save(self.model.state_dict(), './results/last_model.pth')
             torch.save(self.model.state_dict(), f'{path}/model-e{epoch}.pth')
+            if self.pretrain is not None:              # the decoder beside the encoder (which is the plain model file above)
+                torch.save(self.step.head.state_dict(), './results/last_recon_head.pth')
+                torch.save(self.step.head.state_dict(), f'{path}/recon-head-e{epoch}.pth')
             if self.step.ema is not None:              # the averaged weights: plain state_dicts, loadable like any checkpoint
                 torch.save(self.step.ema.module.state_dict(), './results/last_model_ema.pth')
                 torch.save(self.step.ema.module.state_dict(), f'{path}/model-e{epoch}-ema.pth')
@@ -849,8 +889,40 @@ class Trainer:
                 torch.save(state, f'{path}/state-e{epoch}.pth')
             print(f"MODEL SAVED to .{path}/model-e{epoch}.pth")
 
+    def _train_pretrain(self, epoch):
+        """`train` under TRAINING_OBJECTIVE "mim": the configured augmentation, then the masked-reconstruction step; labels are ignored"""
+        import time
+        self.model.train()
+        running_loss, start_time = 0.0, time.time()
+        for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):
+            fMRI, _ = self._unpack(batch)
+            if self.augment is not None:
+                fMRI = self.augment(fMRI, step=self.global_step)
+            self.global_step += 1
+            running_loss = running_loss + self.step(fMRI)
+            if i != 0 and i % self.log_interval == 0:
+                avg_loss, lr, duration = round(float(running_loss) / self.log_interval, 5), round(self.step.last_lr, 5), time.time() - start_time
+                print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| recon_loss: {avg_loss:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
+                self._log({"epoch": epoch, "batch": i, "recon_loss": avg_loss, "learning_rate": lr, "duration": duration})
+                running_loss, start_time = 0.0, time.time()
+
+    def _validate_pretrain(self, epoch):
+        """`validate` under TRAINING_OBJECTIVE "mim": the reconstruction loss of the centre windows under the masks of a fixed seed (batch
+        i always meets the same masks), in the training arithmetic, without dropout"""
+        self.model.eval()
+        total, i = 0.0, 0
+        for i, batch in enumerate(self.val_dataloader):
+            fMRI, _ = self._unpack(batch)
+            total = total + self.step.validation_loss(self._center(fMRI.to(self.device)), index=i)
+        self.val_loss = round(float(total) / max(1, len(self.val_dataloader)), 5)
+        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_recon_loss {self.val_loss:.5f}")
+        self._log({"epoch": epoch, "val_recon_loss": self.val_loss})
+        return self.val_loss, None
+
     def train(self, epoch):
         import time
+        if self.pretrain is not None:
+            return self._train_pretrain(epoch)
         self.model.train()
         running_loss, correct, total = 0.0, 0, 0
         start_time = time.time()
@@ -895,6 +967,8 @@ class Trainer:
         return round(val_loss / max(1, len(self.val_dataloader)), 5), round(correct / max(1, total), 5), i
 
     def validate(self, epoch):
+        if self.pretrain is not None:
+            return self._validate_pretrain(epoch)
         avg_val_loss, accuracy, i = self._evaluate(self.model)
         self.val_loss = avg_val_loss
         print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss {avg_val_loss:.5f}\t| val_accuracy {accuracy:.5f}")

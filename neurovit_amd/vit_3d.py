@@ -341,6 +341,29 @@ class _ViTFunction(torch.autograd.Function):
         return (None, dvideo, None, None) + (None,) * len(ctx.module._plist)
 
 
+class _ViTTokensFunction(torch.autograd.Function):
+    """_ViTFunction's sibling for ViT.forward_tokens: the output is the last block's tokens, and backward hands their gradient to the
+    engine's token-level entry (nv_vit_backward_tokens).  Parameter gradients land in the gradient arena; the head gets zeros."""
+
+    @staticmethod
+    def forward(ctx, module, video, need_grad, *params):
+        ctx.module = module
+        out = module._run_forward_tokens(video)
+        ctx.rec = module._rt.current if need_grad else None
+        ctx.claim = ctx.rec.claim() if need_grad else None
+        return out
+
+    @staticmethod
+    def backward(ctx, dtokens):
+        rt, rec = ctx.module._rt, ctx.rec
+        if rec is None or not rt.pass_is_live(rec):
+            raise RuntimeError("neurovit_amd.ViT: backward() of a forward_tokens pass whose activations have been overwritten - a pass keeps its "
+                               "workspace until one whole backward of it has run")
+        dvideo = torch.empty_like(rec.video, memory_format=torch.preserve_format) if ctx.needs_input_grad[1] else None
+        ctx.module._run_backward_tokens(rec, dtokens, dvideo)
+        return (None, dvideo, None) + (None,) * len(ctx.module._plist)
+
+
 class ViT(FlatArena, nn.Module):
     """vit_3d.py:77-126, MI355X-native.  forward(video[B, C, F, H, W]) -> [B, num_classes] (fp32)."""
 
@@ -962,6 +985,42 @@ class ViT(FlatArena, nn.Module):
         if not hooked:
             return _ViTFunction.apply(self, video.float(), need_grad, (vol_sigma, int(time_points)), *self._plist)
         return self._forward_export(video, vol_sigma, time_points, None, checked=(need_grad, hooked))[0]
+
+    # ------------------------------------------------------------------ token-level objectives (masked reconstruction, distillation, patch contrast)
+    def forward_tokens(self, video):
+        """video [B, C, F, H, W] -> fp32 [B, n, dim]: the output of the last transformer block, cls token first - what the reference's
+        `self.transformer(x)` returns (vit_3d.py:121), in front of pooling and mlp_head.  A VIEW of the pass's workspace (clone what must
+        outlive the next forward of this module); the forward is the training one with the last block on every row, with this module's
+        dropout in train mode.  Under autograd any torch loss on the tokens differentiates the native encoder: backward runs
+        nv_vit_backward_tokens, parameter gradients land in .grad as after forward() - mlp_head takes no part and gets zeros - and a
+        `video` that requires grad receives its gradient.  16-bit operand arithmetic (`operands`); not with the fp8 training forward,
+        data parallel gradient buckets or backward hooks on `attend`."""
+        self.check_video(video)
+        if self._fp8 is not None and self.fp8_training:
+            raise NotImplementedError("neurovit_amd.ViT: forward_tokens runs the 16-bit training forward - disable_fp8() or enable_fp8(training=False) first")
+        need_grad = torch.is_grad_enabled() and (video.requires_grad or any(p.requires_grad for p in self._plist))
+        if need_grad and self._attend_backward_hooked_layers():
+            raise NotImplementedError("neurovit_amd.ViT: forward_tokens exports no attention gradients - remove the backward hooks on `attend`")
+        return _ViTTokensFunction.apply(self, video.float(), need_grad, *self._plist)
+
+    def _run_forward_tokens(self, video):
+        self._refresh_shadow()
+        self._last_logits = self._rt.forward(video, self._arena, self._shadow, training=True, dropout=self.draw_dropout(), rows_form=1)
+        B, (n, d) = video.shape[0], self.pos_embedding.shape[1:]
+        return self._rt.tap("x2", self._cfg.depth - 1, (B, n, d), torch.float32)
+
+    def _run_backward_tokens(self, rec, dtokens, dvideo=None):
+        """The backward of pass `rec` from the gradient on its tokens; see _run_backward for where the parameter gradients go."""
+        if self._grad_sync is not None:
+            raise NotImplementedError("neurovit_amd.ViT: the token-level backward is not pipelined over data-parallel gradient buckets")
+        if not any(p.requires_grad for p in self._plist):
+            if dvideo is not None:
+                self._rt.backward(None, self._arena, self._shadow, None, accumulate=False, dvideo=dvideo, weight_grads=False, of=rec, dtokens=dtokens)
+            return
+
+        def run(target, accumulate, scratch):
+            self._rt.backward(None, self._arena, self._shadow, target, accumulate=accumulate and not scratch, dvideo=dvideo, of=rec, dtokens=dtokens)
+        self._backward_to_grads(run)
 
     def _check_forward(self, video, vol_sigma, time_points) -> bool:
         """forward()'s argument checks; returns whether the forward records a graph"""
