@@ -1071,6 +1071,73 @@ int nv_token_grad_seed_rows(int M);
 int nv_token_grad_seed(const float* dtokens, int M, int d, float* g, void* g16, float* partials, long partial_bytes, unsigned long drop_seed,
                        float drop_p, void* stream);
 
+/* (added within revision 8 - new symbols and one new struct only, nothing existing changes) stochastic depth (drop path; timm's DropPath, the
+ * drop_path_rate of the DeiT / BEiT / MAE recipes) in the training forward, the backward and the one-call train step.  For block l (0-based),
+ * branch c (0 attention, 1 FeedForward) and sample b:   x <- x + f[l, c, b] * Dropout(branch(LN(x)))   with f a DEVICE table of fp32
+ * factors [depth][2][B], each 0 or 1 / (1 - q_l).  A site has an element-dropout factor e (0 or 1 / (1 - p), the rule of nv_gemm_bf16) and
+ * the sample's path factor f: every kernel forms k = e * f FIRST, as one fp32 product, and uses k exactly where it uses e without a table -
+ * so f == 1.0f gives the bits of the call without a table, f == 0 gives resid + 0, and forward and backward see the same k.  In the
+ * backward the 16-bit gradient handed to a branch and the column sums that become its bias gradient are formed from g * k; the fp32
+ * running residual gradient g is not scaled.  Dropped branches are still computed (skipping them would need a host read of the draw).
+ * nv_drop_path_draw: writes factors[depth][2][B] on the device; nothing is read back, the host draws nothing.
+ *   q_l: NV_DROP_PATH_LINEAR  rate * l / (depth - 1) in double (timm's linspace(0, rate, depth); 0 when depth == 1), NV_DROP_PATH_CONSTANT  rate
+ *   seed_p = nv_hash64(seed, 0x50415448);  h = nv_hash64(seed_p, ((uint64)(2 l + c) << 32) + b)          (a hash domain of its own)
+ *   kept iff (h >> 48) >= (unsigned)(q_l * 65536.0) (the product in double, truncated);  f = 1.0f / (1.0f - (float)q_l) when kept, else 0;
+ *   a site whose threshold is 0 writes 1.0f without hashing.  NV_ERR_ARG: rate outside [0, 1), an unknown schedule, B or depth <= 0, factors NULL.
+ * Kernel level: the argument lists of nv_gemm_bf16 / nv_skinny_nt / nv_ln_bwd / nv_head_bwd / nv_head_step_soft plus (path, path_rows): path
+ *   = the [samples] factors of ONE site, path_rows = token rows per sample.  Row r of a launch is dense row r * (ld / width) of the tensor it
+ *   writes (a view of) - ldo / N for nv_skinny_nt_path, ldg / d for nv_ln_bwd_path, 1 for the GEMM - and its sample is that dense row /
+ *   path_rows (samples * path_rows < 2^31).  nv_gemm_bf16_path: layout 0, epilogue 4 only; nv_skinny_nt_path: epilogue 0 only; the head forms:
+ *   path_rows == n.  nv_head_step_path serves nv_head_step (scale_state = opts = NULL), _scaled (opts = NULL) and _soft.  path == NULL: the
+ *   call is handed to the existing symbol (same launches, same bits).  The path-aware kernels are instantiations of their own: what the
+ *   existing symbols launch is unchanged.
+ * Engine level: nv_vit_drop_path.factors = the whole table.  nv_vit_forward_sd = nv_vit_forward_in + sd (training == 1 only, not the fused
+ *   4D input form); nv_vit_backward_sd = nv_vit_backward_attn + sd - it MUST be given the forward's table; nv_vit_train_step_sd =
+ *   nv_vit_train_step_ex + sd, every nv_train_hparams form of that call (all fuse_update modes, accumulation, static and dynamic loss scale,
+ *   nv_dp_plan, both head routes).  Sites: out-projection of block l f[l, 0], FC2 f[l, 1] (forward, also in the cls-rows form of the last
+ *   block); LN2 backward of block l f[l, 0], LN1 backward of block l (l > 0) f[l - 1, 1], the head's backward f[depth - 1, 1].  sd == NULL IS
+ *   the existing entry point (same launches, same bits); a wrong struct_size or NULL factors is refused before any launch.  Not in the fp8
+ *   training forward and not in nv_vit_backward_tokens. */
+#define NV_DROP_PATH_LINEAR 0
+#define NV_DROP_PATH_CONSTANT 1
+typedef struct nv_vit_drop_path {
+  int struct_size;        /* sizeof(nv_vit_drop_path) */
+  const float* factors;   /* device [depth][2][B] */
+} nv_vit_drop_path;
+int nv_drop_path_draw(unsigned long seed, int B, int depth, float rate, int schedule, float* factors, void* stream);
+int nv_gemm_bf16_path(int layout, int epi, int M, int N, int K, const void* A, long lda, const void* B, long ldb, void* C,
+                      long ldc, const float* bias, const void* aux_in, long ld_aux_in, void* aux_out, long ld_aux_out,
+                      int accumulate, float alpha, unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows);
+int nv_skinny_nt_path(int epi, int R, int N, int K, const void* A, long lda, const void* W, long ldw, const float* bias, const float* resid,
+                      long ldr, void* out, long ldo, void* u_out, long ldu, unsigned long drop_seed, float drop_p, void* stream,
+                      const float* path, int path_rows);
+int nv_ln_bwd_path(const float* dy, long lddy, const float* x, long ldx, const float* mean, const float* rstd, const float* gamma,
+                   int M, int d, const float* g_in, float* g_out, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta,
+                   float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p, void* stream,
+                   void* reduce_stream, const float* path, int path_rows);
+int nv_head_bwd_path(const float* dlogits, int B, int C, const float* W, const float* x, long row_stride, const float* stats,
+                     const float* xh, const float* gamma, int d, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma,
+                     float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                     unsigned long drop_seed, float drop_p, int pool_mean, void* stream, const float* path, int path_rows);
+int nv_head_step_path(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                      const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, const nv_loss_opts* opts,
+                      float* xh, float* stats, float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16,
+                      float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                      unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows);
+int nv_vit_forward_sd(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5,
+                      const nv_vit_input* in, const float* params, const void* params16, void* workspace, long ws_bytes,
+                      int training, float drop_p, float emb_drop_p, unsigned long drop_seed, float* logits, void* stream,
+                      const nv_vit_drop_path* sd);
+int nv_vit_backward_sd(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                       const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                       int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p, unsigned long drop_seed,
+                       void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
+                       const nv_vit_attn_grad_export* attn_grad, const nv_vit_drop_path* sd);
+int nv_vit_train_step_sd(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                         float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                         const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
+                         float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const nv_vit_drop_path* sd);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

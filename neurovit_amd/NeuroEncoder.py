@@ -687,10 +687,14 @@ class ViT3DEncoder(nn.Module):
         cubes_per_axis = self.grid_size // self.cube_size
         classes = cubes_per_axis ** 3 if config['DATASET_NAME'] == 'gradcam' else 2
         # a cubic single-channel volume: frames (depth) and image sides share one extent and one patch edge
+        # stochastic depth (timm's drop_path_rate, linear over the blocks; 0.1 in the DeiT-B / MAE fine-tuning recipes): optional key, absent = 0
+        self.drop_path = config.get('TRAINING_DROP_PATH', 0.0)
+        if config['TRAINING_DIM'] == 4 and self.drop_path:
+            raise NotImplementedError("TRAINING_DROP_PATH: stochastic depth is for the 3D model - the 4D model's encoder is frozen and kept in eval mode")
         self.vit3d = ViT(image_size=self.grid_size, image_patch_size=self.patch_size, frames=self.grid_size, frame_patch_size=self.patch_size,
                          channels=1, num_classes=classes, dim=size['TRAINING_VIT_DIM'], depth=size['TRAINING_VIT_DEPTH'],
                          heads=size['TRAINING_VIT_HEADS'], dim_head=size['TRAINING_VIT_DIM_HEAD'], mlp_dim=size['TRAINING_VIT_MLP_DIM'],
-                         pool='cls', dropout=self.dropout, emb_dropout=self.dropout).to(self.device)
+                         pool='cls', dropout=self.dropout, emb_dropout=self.dropout, drop_path_rate=self.drop_path).to(self.device)
         # arithmetic of eval-mode no-grad forwards: "bf16" (default; the training arithmetic) or "fp32" (the reference's validate,
         # Trainer.py:101-118).  The Trainer shell's validate / evaluate_samples use VALIDATION_PRECISION (default "fp32").
         self.vit3d.eval_precision = config.get('TRAINING_VIT_EVAL_PRECISION', 'bf16')

@@ -87,6 +87,15 @@ class LossOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("label_smoothing", ctypes.c_float), ("class_weight", ctypes.c_void_p), ("mix", ctypes.c_void_p)]
 
 
+class DropPath(ctypes.Structure):
+    """struct nv_vit_drop_path (neurovit_hip.h, added within revision 8): the device table of stochastic-depth factors [depth][2][B] of
+    nv_vit_forward_sd / nv_vit_backward_sd / nv_vit_train_step_sd."""
+    _fields_ = [("struct_size", ctypes.c_int), ("factors", ctypes.c_void_p)]
+
+
+DROP_PATH_SCHEDULES = {"linear": 0, "constant": 1}          # NV_DROP_PATH_LINEAR / NV_DROP_PATH_CONSTANT
+
+
 ADAMW_MAX_GROUPS, ADAMW_MAX_SEGMENTS = 64, 1024      # NV_ADAMW_MAX_GROUPS, NV_ADAMW_MAX_SEGMENTS
 
 

@@ -237,6 +237,23 @@ __device__ __forceinline__ float drop_factor(const DropCfg& d, unsigned long lon
   return (field >= d.thresh) ? d.scale : 0.f;
 }
 
+// Stochastic depth (drop path) of one residual branch: f[b] = 0 or 1 / (1 - q) per SAMPLE, written by nv_drop_path_draw (drop_path.hip).
+// A site multiplies its element-dropout factor e and the sample's f into ONE fp32 product k = e * f and uses k where it used e: f == 1 gives
+// the bits of the call without a table, f == 0 gives resid + 0, and the backward forms the same k.  Passed only to the path-aware
+// instantiations of the four kernels that own a residual branch (their other instantiations, and DropCfg, are as they were).
+// Row r of the launch is dense row r * step of the [samples * rows, width] tensor the launch writes (a view of); its sample = r * step / rows.
+struct PathCfg {
+  const float* f;
+  int rows;      // token rows per sample
+  int step;      // dense rows between two rows of the launch (1: dense)
+};
+// The path-aware kernels are the PATH = true instantiations of the kernels themselves; their last argument is the table, or - PATH = false, what every
+// call without a table launches - an empty struct
+struct NoPath {};
+template <bool PATH> using PathArg = std::conditional_t<PATH, PathCfg, NoPath>;
+// (the hosts check samples * rows < 2^31: dense row indices are 32-bit).  One 32-bit division per ROW a thread or wave handles, never per element.
+__device__ __forceinline__ float path_factor(const PathCfg& p, int row) { return p.f[(unsigned)(row * p.step) / (unsigned)p.rows]; }
+
 // The row's maximum and the sum of exp(row - max), in every thread: the wave butterflies, then the four waves through red[0 .. 3].
 __device__ __forceinline__ void ce_row_max_sumexp(const float* __restrict__ row, int C, float* red, float& mx, float& se) {
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;

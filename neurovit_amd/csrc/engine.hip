@@ -183,6 +183,17 @@ void make_wsf(const Dims& D, WSF& W) {
 // per-site dropout seeds: site = 4*layer + {0 attention probs, 1 to_out, 2 FF hidden, 3 FF out}; 4*depth = embedding
 inline unsigned long site_seed(unsigned long seed, int site) { return seed ^ (0x9E3779B97F4A7C15ul * (unsigned long)(site + 1)); }
 
+// Stochastic depth (nv_vit_drop_path): the [B] factors of branch c (0 attention, 1 FeedForward) of block l inside the table [depth][2][B]; no table: NULL,
+// and the *_path entry points below hand the call to the symbol they extend (same launches, same bits)
+inline const float* path_of(const float* sd, int l, int c, int B) { return sd ? sd + ((long)l * 2 + c) * B : nullptr; }
+int check_drop_path(const nv_vit_drop_path* sd, const char* who) {
+  if (!sd) return NV_OK;
+  NV_CHECK_ARG(sd->struct_size == (int)sizeof(nv_vit_drop_path), "%s: nv_vit_drop_path.struct_size=%d, expected %d (ABI revision %d)", who, sd->struct_size,
+               (int)sizeof(nv_vit_drop_path), NV_ABI_VERSION);
+  NV_CHECK_ARG(sd->factors && nv_aligned(sd->factors, 4), "%s: nv_vit_drop_path.factors is NULL or not 4-byte aligned", who);
+  return NV_OK;
+}
+
 // Fork/join between the main stream and the auxiliary stream that runs the weight-gradient GEMMs (they depend only on
 // buffers the data-gradient chain has already produced, and the chain's kernels - 198-tile GEMMs, attention backward,
 // LayerNorm backward - leave LDS and CUs idle).  Events are pooled (created once, outside any capture).
@@ -347,13 +358,15 @@ static int embed_front16(const nv_vit_config* cfg, const Layout& Y, int B, const
 // Block l behind its attention on the B cls rows only (see g_cls_tail), 16-bit operands through the weight-streaming kernels: row b of the
 // small problem = row b * n of the buffers; LN2 statistics land at st2[0 .. B) / st2[M .. M + B).  u: the pre-GELU values for a backward, or NULL.
 static int cls_rows_block16(const Dims& D, const LayerP& q, const LayerW& w, int l, const float* p, const r16* p16, char* ws, float eps, const float* xin,
-                            float* x1, float* x2, float* st2, void* u, unsigned long drop_seed, float drop_p, float proj_p, void* stream) {
+                            float* x1, float* x2, float* st2, void* u, unsigned long drop_seed, float drop_p, float proj_p, void* stream, const float* sd = nullptr) {
   const int B = D.B, d = D.d;
   const long rs = D.n;
-  RUN(nv_skinny_nt(0, B, d, D.inner, ws + w.ao, D.inner * rs, p16 + q.wo, D.inner, p + q.bo, xin, d * rs, x1, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 1), proj_p, stream));
+  RUN(nv_skinny_nt_path(0, B, d, D.inner, ws + w.ao, D.inner * rs, p16 + q.wo, D.inner, p + q.bo, xin, d * rs, x1, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 1), proj_p, stream,
+                        path_of(sd, l, 0, B), D.n));
   RUN(nv_ln_fwd(x1, d * rs, B, d, p + q.n2g, p + q.n2b, eps, ws + w.xn2, d * rs, st2, st2 + D.M, stream));
   RUN(nv_skinny_nt(1, B, D.m, d, ws + w.xn2, d * rs, p16 + q.w1, d, p + q.b1, nullptr, 0, ws + w.h, D.m * rs, u, D.m * rs, site_seed(drop_seed, 4 * l + 2), drop_p, stream));
-  return nv_skinny_nt(0, B, d, D.m, ws + w.h, D.m * rs, p16 + q.w2, D.m, p + q.b2, x1, d * rs, x2, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 3), drop_p, stream);
+  return nv_skinny_nt_path(0, B, d, D.m, ws + w.h, D.m * rs, p16 + q.w2, D.m, p + q.b2, x1, d * rs, x2, d * rs, nullptr, 0, site_seed(drop_seed, 4 * l + 3), drop_p, stream,
+                           path_of(sd, l, 1, B), D.n);
 }
 
 // A9: cls pooling (or the token mean, pool = 'mean') + LayerNorm + Linear(dim, C).  xm / xh / hst: workspace offsets of either layout.
@@ -395,7 +408,8 @@ static int export_layer(const nv_vit_input* in, int l, int qkv_f32, const void* 
 
 static int forward_in_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                            const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
-                           unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16 = nullptr, const float* fold32 = nullptr);
+                           unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16 = nullptr, const float* fold32 = nullptr,
+                           const float* sd = nullptr);
 
 // ---- LayerNorm folded into the GEMMs around it (inference forwards; gemm_common.h EPI_BIAS_RESID_LN / EPI_LNFOLD_*).
 // fold16: 16-bit arena with the parameter arena's element offsets holding W_qkv diag(gamma1) and W_1 diag(gamma2) of every block; fold32: per block
@@ -433,10 +447,23 @@ extern "C" int nv_vit_forward_in(const nv_vit_config* cfg, int B, const float* v
   return forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, training, drop_p, emb_drop_p, drop_seed, logits, stream, false);
 }
 
+// nv_vit_forward_in(training = 1) under stochastic depth: the residual adds of every block carry the table's factors (see the header)
+extern "C" int nv_vit_forward_sd(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                                 const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
+                                 unsigned long drop_seed, float* logits, void* stream, const nv_vit_drop_path* sd) {
+  if (!sd) return nv_vit_forward_in(cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, training, drop_p, emb_drop_p, drop_seed, logits, stream);
+  RUN(check_drop_path(sd, "nv_vit_forward_sd"));
+  NV_CHECK_ARG(training == 1, "nv_vit_forward_sd: stochastic depth belongs to training forwards (training = %d)", training);
+  NV_CHECK_ARG(!(in && in->time_points > 0), "nv_vit_forward_sd: not with the fused 4D input form (time_points > 0)");
+  Layout Y; RUN(make_layout(cfg, B, 1, Y));
+  return forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 1, drop_p, emb_drop_p, drop_seed, logits, stream, false, nullptr, nullptr,
+                         sd->factors);
+}
+
 // skip_head: everything up to the last block's output; the caller runs the head itself (nv_vit_train_step: nv_head_step)
 static int forward_in_impl(const Layout& Y, const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                            const float* params, const void* params16, void* workspace, long ws_bytes, int training, float drop_p, float emb_drop_p,
-                           unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16, const float* fold32) {
+                           unsigned long drop_seed, float* logits, void* stream, bool skip_head, const void* fold16, const float* fold32, const float* sd) {
   const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
   NV_CHECK_ARG(video && shape5 && strides5 && params && params16 && workspace && logits, "nv_vit_forward: null pointer");
   RUN(check_video("nv_vit_forward", cfg, B, shape5, in, true));
@@ -484,7 +511,7 @@ static int forward_in_impl(const Layout& Y, const nv_vit_config* cfg, int B, con
     RUN(nv_attn_fwd(ws + w.qkv, 3 * D.inner, B, D.n, D.heads, D.dh, scale, ws + w.ao, D.inner, (float*)(ws + w.lse), site_seed(drop_seed, 4 * l + 0), drop_p, stream));
     RUN(export_layer(in, l, 0, ws + w.qkv, D, B, scale, stream));
     if (tail && l == D.L - 1) {
-      RUN(cls_rows_block16(D, q, w, l, p, p16, ws, eps, xin, x1, x2, st2, training ? ws + w.u : nullptr, drop_seed, drop_p, proj_drop_p(cfg, drop_p), stream));
+      RUN(cls_rows_block16(D, q, w, l, p, p16, ws, eps, xin, x1, x2, st2, training ? ws + w.u : nullptr, drop_seed, drop_p, proj_drop_p(cfg, drop_p), stream, sd));
       xin = x2;
       continue;
     }
@@ -502,10 +529,12 @@ static int forward_in_impl(const Layout& Y, const nv_vit_config* cfg, int B, con
       xin = x2;
       continue;
     }
-    RUN(nv_gemm_bf16(0, 4, M, d, D.inner, ws + w.ao, D.inner, p16 + q.wo, D.inner, x1, d, p + q.bo, xin, d, nullptr, 0, 0, 1.f, site_seed(drop_seed, 4 * l + 1), proj_drop_p(cfg, drop_p), stream));
+    RUN(nv_gemm_bf16_path(0, 4, M, d, D.inner, ws + w.ao, D.inner, p16 + q.wo, D.inner, x1, d, p + q.bo, xin, d, nullptr, 0, 0, 1.f, site_seed(drop_seed, 4 * l + 1), proj_drop_p(cfg, drop_p), stream,
+                          path_of(sd, l, 0, B), D.n));
     RUN(nv_ln_fwd(x1, d, M, d, p + q.n2g, p + q.n2b, eps, ws + w.xn2, d, st2, st2 + M, stream));
     RUN(nv_gemm_bf16(0, 3, M, D.m, d, ws + w.xn2, d, p16 + q.w1, d, ws + w.h, D.m, p + q.b1, nullptr, 0, training ? ws + w.u : nullptr, D.m, 0, 1.f, site_seed(drop_seed, 4 * l + 2), drop_p, stream));
-    RUN(nv_gemm_bf16(0, 4, M, d, D.m, ws + w.h, D.m, p16 + q.w2, D.m, x2, d, p + q.b2, x1, d, nullptr, 0, 0, 1.f, site_seed(drop_seed, 4 * l + 3), drop_p, stream));
+    RUN(nv_gemm_bf16_path(0, 4, M, d, D.m, ws + w.h, D.m, p16 + q.w2, D.m, x2, d, p + q.b2, x1, d, nullptr, 0, 0, 1.f, site_seed(drop_seed, 4 * l + 3), drop_p, stream,
+                          path_of(sd, l, 1, B), D.n));
     xin = x2;
   }
   if (skip_head) return NV_OK;
@@ -731,6 +760,7 @@ struct BwdCall {
   const nv_vit_backward_opts* opts;                 // nv_vit_backward_ex: the input gradient, and the data-only form (weight_grads = 0: no gradient arena, nothing on [A])
   const nv_vit_attn_grad_export* attn_grad;
   const float* dtokens;                             // nv_vit_backward_tokens: the gradient on the final tokens; stage 0 is then seed_tokens, not the head
+  const float* sd;                                  // nv_vit_backward_sd / nv_vit_train_step_sd: the forward's stochastic-depth factors [depth][2][B], or NULL
 };
 
 // Last block in the cls-rows form (see g_cls_tail): the residual gradient is zero outside the B cls rows until the attention
@@ -754,10 +784,10 @@ struct Bwd {
   // head: writes g (zeros + cls rows) and the last layer's FC2 bias gradient (colsum of g)
   int bwd_head() const {
     const float* xlast = (float*)(ws + W.layer[D.L - 1].x2);
-    return nv_head_bwd(c.dlogits, D.B, D.C, p + T.hw, D.pool_mean ? (const float*)(ws + W.xm) : xlast, D.pool_mean ? (long)d : (long)D.n * d,
+    return nv_head_bwd_path(c.dlogits, D.B, D.C, p + T.hw, D.pool_mean ? (const float*)(ws + W.xm) : xlast, D.pool_mean ? (long)d : (long)D.n * d,
                        (float*)(ws + W.hst), (float*)(ws + W.xh), p + T.hg, d, D.n, g, d, ws + W.scratch(D.L - 1).g16, d,
                        GR(T.hg), GR(T.hb), GR(T.hw), GR(T.hbias), GR(T.layer[D.L - 1].b2), acc, ws + W.sc[0].red, W.red_bytes,
-                       site_seed(c.drop_seed, 4 * (D.L - 1) + 3), c.drop_p, D.pool_mean, S);
+                       site_seed(c.drop_seed, 4 * (D.L - 1) + 3), c.drop_p, D.pool_mean, S, path_of(c.sd, D.L - 1, 1, D.B), D.n);
   }
 
   // FeedForward backward (vit_3d.py:16-26) and the LN2 backward behind it
@@ -774,8 +804,8 @@ struct Bwd {
                        site_seed(c.drop_seed, 4 * l + 2), c.drop_p, S));   // dU = (g W2 * mask) * gelu'(u)  [+ per-tile column sums -> db1]
       RUN(nv_gemm_bf16(1, 1, M, d, D.m, du, D.m, p16 + q.w1, d, dxn, d, nullptr, nullptr, 0, nullptr, 0, 0, 1.f, 0, 0.f, S));                        // dxn2 = dU W1
     }
-    return nv_ln_bwd(dxn, d * rs, (float*)(ws + w.x1), d * rs, st2, st2 + M, p + q.n2g, R.Mr, d, g, g, d * rs, ws + sc.g16b, d * rs, GR(q.n2g), GR(q.n2b), GR(q.bo), acc, ws + sc.red,
-                     W.red_bytes, site_seed(c.drop_seed, 4 * l + 1), proj_drop_p(cfg, c.drop_p), S, NV_LN_NO_REDUCE);                                 // g += dLN2 -> g16b
+    return nv_ln_bwd_path(dxn, d * rs, (float*)(ws + w.x1), d * rs, st2, st2 + M, p + q.n2g, R.Mr, d, g, g, d * rs, ws + sc.g16b, d * rs, GR(q.n2g), GR(q.n2b), GR(q.bo), acc, ws + sc.red,
+                          W.red_bytes, site_seed(c.drop_seed, 4 * l + 1), proj_drop_p(cfg, c.drop_p), S, NV_LN_NO_REDUCE, path_of(c.sd, l, 0, D.B), D.n);    // g += dLN2 -> g16b
   }
 
   // Attention backward (vit_3d.py:48-60): dAO, dqkv, and the exported gradient of the probabilities
@@ -803,8 +833,9 @@ struct Bwd {
     const LayerP& q = T.layer[l];
     const float* xin = (l == 0) ? (float*)(ws + W.x0) : (float*)(ws + W.layer[l - 1].x2);
     float* st1 = (float*)(ws + W.layer[l].st1);
-    return nv_ln_bwd(dxn1(l), d, xin, d, st1, st1 + M, p + q.n1g, M, d, g, g, d, ws + W.scratch(l - 1).g16, d, GR(q.n1g), GR(q.n1b), (l > 0) ? GR(T.layer[l - 1].b2) : nullptr,
-                     acc, ws + W.scratch(l).red3, nv_ln_bwd_workspace_bytes(M, d), site_seed(c.drop_seed, 4 * (l - 1) + 3), (l > 0) ? c.drop_p : 0.f, S, NV_LN_NO_REDUCE);
+    return nv_ln_bwd_path(dxn1(l), d, xin, d, st1, st1 + M, p + q.n1g, M, d, g, g, d, ws + W.scratch(l - 1).g16, d, GR(q.n1g), GR(q.n1b), (l > 0) ? GR(T.layer[l - 1].b2) : nullptr,
+                          acc, ws + W.scratch(l).red3, nv_ln_bwd_workspace_bytes(M, d), site_seed(c.drop_seed, 4 * (l - 1) + 3), (l > 0) ? c.drop_p : 0.f, S, NV_LN_NO_REDUCE,
+                          (l > 0) ? path_of(c.sd, l - 1, 1, D.B) : nullptr, D.n);
   }
 
   // [A] reduction of layer lp's LN1-backward partials, where no later layer's nv_reduce_multi takes it along
@@ -1011,11 +1042,12 @@ extern "C" int nv_vit_backward_stages16(const nv_vit_config* cfg, int B, const f
 // Export of the gradient w.r.t. the attention probabilities (nv_vit_attn_grad_export): nv_attn_grad queued right behind a layer's
 // attention backward, while dAO and the layer's qkv still hold its values.  attn_grad = NULL: exactly the launches of nv_vit_backward_ex;
 // opts = NULL as well: exactly those of nv_vit_backward_stages16.
-extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
-                                    const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
-                                    int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
-                                    unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
-                                    const nv_vit_attn_grad_export* attn_grad) {
+// sd: the forward's stochastic-depth factors (nv_vit_backward_sd), or NULL
+static int backward_attn_impl(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                              const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                              int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                              unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
+                              const nv_vit_attn_grad_export* attn_grad, const float* sd) {
   NV_CHECK_ARG(!opts || opts->struct_size == (int)sizeof(nv_vit_backward_opts), "nv_vit_backward_ex: opts->struct_size %d != %d (ABI revision mismatch)",
                opts ? opts->struct_size : 0, (int)sizeof(nv_vit_backward_opts));
   if (attn_grad) {
@@ -1032,8 +1064,29 @@ extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float
   c.video = video; c.strides5 = strides5; c.params = params; c.params16 = params16; c.workspace = workspace; c.ws_bytes = ws_bytes;
   c.dlogits = dlogits; c.grads = grads; c.grads16 = grads16; c.accumulate = accumulate; c.first_stage = first_stage; c.last_stage = last_stage;
   c.drop_p = drop_p; c.emb_drop_p = emb_drop_p; c.drop_seed = drop_seed; c.stream = stream; c.aux_stream = aux_stream;
-  c.join_aux = join_aux; c.rows_form = rows_form; c.opts = opts; c.attn_grad = attn_grad;
+  c.join_aux = join_aux; c.rows_form = rows_form; c.opts = opts; c.attn_grad = attn_grad; c.sd = sd;
   return backward_impl(Y, cfg, c);
+}
+
+extern "C" int nv_vit_backward_attn(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                                    const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                                    int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                                    unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
+                                    const nv_vit_attn_grad_export* attn_grad) {
+  return backward_attn_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+                            drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, opts, attn_grad, nullptr);
+}
+
+// nv_vit_backward_attn of a forward that ran under stochastic depth (nv_vit_forward_sd): sd must be that forward's table - the data gradient handed
+// to every branch, and the column sums that become the bias gradients of the out-projection and FC2, carry the same factors
+extern "C" int nv_vit_backward_sd(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
+                                  const void* params16, void* workspace, long ws_bytes, const float* dlogits, float* grads, void* grads16,
+                                  int accumulate, int first_stage, int last_stage, float drop_p, float emb_drop_p,
+                                  unsigned long drop_seed, void* stream, void* aux_stream, int join_aux, int rows_form, const nv_vit_backward_opts* opts,
+                                  const nv_vit_attn_grad_export* attn_grad, const nv_vit_drop_path* sd) {
+  RUN(check_drop_path(sd, "nv_vit_backward_sd"));
+  return backward_attn_impl(cfg, B, video, strides5, params, params16, workspace, ws_bytes, dlogits, grads, grads16, accumulate, first_stage, last_stage,
+                            drop_p, emb_drop_p, drop_seed, stream, aux_stream, join_aux, rows_form, opts, attn_grad, sd ? sd->factors : nullptr);
 }
 
 extern "C" int nv_vit_backward_ex(const nv_vit_config* cfg, int B, const float* video, const long* strides5, const float* params,
@@ -1188,10 +1241,11 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
 
 // lo: nv_loss_opts (label smoothing, class weights, a mixed target) or NULL.  The loss calls below are nv_head_step_soft / nv_ce_loss_soft,
 // which run the index-target kernels of nv_vit_train_step when no option is on; nothing else differs.
-extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
-                                    float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
-                                    const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
-                                    float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream) {
+// sd: the step's stochastic-depth factors (nv_vit_train_step_sd), or NULL: forward, head step and backward then run the launches they always ran
+static int train_step_impl(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                           float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                           const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
+                           float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const float* sd) {
   NV_CHECK_ARG(cfg && hp && hp->struct_size == (int)sizeof(nv_train_hparams), "nv_vit_train_step: nv_train_hparams.struct_size = %d, this library expects %d (ABI revision %d)",
                hp ? hp->struct_size : -1, (int)sizeof(nv_train_hparams), NV_ABI_VERSION);
   NV_CHECK_ARG(labels && loss && dlogits && grads && (!hp->update || (adam_m && adam_v && hp->step >= 1)), "nv_vit_train_step: null pointer (labels / loss / dlogits / grads / optimizer state) or step < 1");
@@ -1219,14 +1273,14 @@ extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float
   const bool head_fused = g_head_step && !cfg->pool_mean && cfg->num_classes <= cfg->dim && cfg->dim % 8 == 0;
   Layout Y; RUN(make_layout(cfg, B, 1, Y));          // one layout for the whole step: forward, head step, backward, update ranges
   const Dims& D = Y.D; const ParamTab& T = Y.T; const WS& W = Y.W;
-  RUN(forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 1, drop_p, emb_drop_p, drop_seed, logits, stream, head_fused));
+  RUN(forward_in_impl(Y, cfg, B, video, shape5, strides5, in, params, params16, workspace, ws_bytes, 1, drop_p, emb_drop_p, drop_seed, logits, stream, head_fused, nullptr, nullptr, sd));
   if (head_fused) {
     char* ws = (char*)workspace;
     const int Ll = D.L - 1;
-    RUN(nv_head_step_soft((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
+    RUN(nv_head_step_path((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
                           labels, lscale, hp->loss_scale_state, lo, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
                           ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
-                          hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream));
+                          hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream, path_of(sd, Ll, 1, B), D.n));
   } else {
     RUN(nv_ce_loss_soft(logits, labels, B, cfg->num_classes, lscale, hp->loss_scale_state, lo, loss, dlogits, stream));
   }
@@ -1237,7 +1291,7 @@ extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float
   BwdCall bc{};
   bc.video = video; bc.strides5 = strides5; bc.params = params; bc.params16 = params16; bc.workspace = workspace; bc.ws_bytes = ws_bytes;
   bc.dlogits = dlogits; bc.grads = grads; bc.accumulate = hp->accumulate ? 1 : 0; bc.drop_p = drop_p; bc.emb_drop_p = emb_drop_p; bc.drop_seed = drop_seed;
-  bc.stream = stream; bc.aux_stream = aux_stream; bc.join_aux = 1; bc.rows_form = in ? in->rows_form : 0;
+  bc.stream = stream; bc.aux_stream = aux_stream; bc.join_aux = 1; bc.rows_form = in ? in->rows_form : 0; bc.sd = sd;
   if (dp && hp->update) return dp_backward_update(Y, cfg, bc, params, params16, adam_m, adam_v, hp, dp, head_fused, lscale);
   bc.first_stage = head_fused ? 1 : 0; bc.last_stage = cfg->depth + 1;      // (the fused head step has run stage 0 already)
   bc.fuse = fused ? &opt : nullptr; bc.fuse_mode = hp->fuse_update;
@@ -1258,4 +1312,22 @@ extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float
     RUN(nv_adamw_ranges(&opt, begins.data(), lens.data(), (int)begins.size(), stream));
   }
   return NV_OK;
+}
+
+extern "C" int nv_vit_train_step_ex(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                                    float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                                    const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
+                                    float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream) {
+  return train_step_impl(cfg, B, video, shape5, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, labels, logits, loss, dlogits, hp, lo,
+                         drop_p, emb_drop_p, drop_seed, stream, aux_stream, nullptr);
+}
+
+// nv_vit_train_step_ex under stochastic depth: one table for the step's forward, head step and backward; every nv_train_hparams form of that call
+extern "C" int nv_vit_train_step_sd(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                                    float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                                    const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
+                                    float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const nv_vit_drop_path* sd) {
+  RUN(check_drop_path(sd, "nv_vit_train_step_sd"));
+  return train_step_impl(cfg, B, video, shape5, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, labels, logits, loss, dlogits, hp, lo,
+                         drop_p, emb_drop_p, drop_seed, stream, aux_stream, sd ? sd->factors : nullptr);
 }

@@ -538,9 +538,10 @@ extern "C" int nv_gemm_tile_rows(int layout, int M, int N, int K, long lda, long
   return p.family == 0 ? 0 : p.bm;
 }
 
-extern "C" int nv_gemm_bf16(int layout, int epi, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
-                            void* C, long ldc, const float* bias, const void* aux_in, long ld_aux_in, void* aux_out,
-                            long ld_aux_out, int accumulate, float alpha, unsigned long drop_seed, float drop_p, void* stream) {
+// path != null (nv_gemm_bf16_path, checked there): epilogue 4 with the per-sample factors of stochastic depth, on its own instantiation
+static int gemm_bf16_impl(int layout, int epi, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                          void* C, long ldc, const float* bias, const void* aux_in, long ld_aux_in, void* aux_out,
+                          long ld_aux_out, int accumulate, float alpha, unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows) {
   NV_CHECK_ARG(M > 0 && N > 0 && K > 0, "nv_gemm_bf16: empty problem M=%d N=%d K=%d", M, N, K);
   NV_CHECK_ARG(A && B && C, "nv_gemm_bf16: null operand");
   NV_CHECK_ARG(nv_aligned16(A) && nv_aligned16(B) && nv_aligned16(C), "nv_gemm_bf16: operands must be 16-byte aligned");
@@ -570,12 +571,14 @@ extern "C" int nv_gemm_bf16(int layout, int epi, int M, int N, int K, const void
                "nv_gemm_bf16: epilogue 1: the optional bf16 mirror (aux_out) must be 8-byte aligned with ld_aux_out >= N, a multiple of 4");
   NV_CHECK_ARG(epi != EPI_BIAS_GELU || !aux_out || (nv_aligned16(aux_out) && (ld_aux_out % 4) == 0),
                "nv_gemm_bf16: EPI_BIAS_GELU: aux_out must be 16-byte aligned (or null: the pre-activation is not stored)");
+  if (path) { a.path = PathCfg{path, path_rows, 1}; epi = EPI_BIAS_RESID_PATH; }
   switch (layout * 16 + epi) {
     case 0 * 16 + EPI_STORE_BF16: return launch<false, false, EPI_STORE_BF16>(a, s);
     case 0 * 16 + EPI_STORE_F32: return launch<false, false, EPI_STORE_F32>(a, s);
     case 0 * 16 + EPI_BIAS_F32: return launch<false, false, EPI_BIAS_F32>(a, s);
     case 0 * 16 + EPI_BIAS_GELU: return launch<false, false, EPI_BIAS_GELU>(a, s);
     case 0 * 16 + EPI_BIAS_RESID: return launch<false, false, EPI_BIAS_RESID>(a, s);
+    case 0 * 16 + EPI_BIAS_RESID_PATH: return launch<false, false, EPI_BIAS_RESID_PATH>(a, s);
     case 1 * 16 + EPI_STORE_BF16: return launch<false, true, EPI_STORE_BF16>(a, s);
     case 1 * 16 + EPI_STORE_F32: return launch<false, true, EPI_STORE_F32>(a, s);
     case 1 * 16 + EPI_DGELU: return launch<false, true, EPI_DGELU>(a, s);
@@ -585,6 +588,22 @@ extern "C" int nv_gemm_bf16(int layout, int epi, int M, int N, int K, const void
   }
   nv_set_error("nv_gemm_bf16: unsupported layout/epilogue combination (%d, %d)", layout, epi);
   return NV_ERR_ARG;
+}
+
+extern "C" int nv_gemm_bf16(int layout, int epi, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                            void* C, long ldc, const float* bias, const void* aux_in, long ld_aux_in, void* aux_out,
+                            long ld_aux_out, int accumulate, float alpha, unsigned long drop_seed, float drop_p, void* stream) {
+  return gemm_bf16_impl(layout, epi, M, N, K, A, lda, B, ldb, C, ldc, bias, aux_in, ld_aux_in, aux_out, ld_aux_out, accumulate, alpha, drop_seed, drop_p, stream, nullptr, 0);
+}
+
+// nv_gemm_bf16 epilogue 4 under stochastic depth: C = aux_in + (acc + bias) * (dropout factor * path[m / path_rows]); path = NULL: nv_gemm_bf16 itself
+extern "C" int nv_gemm_bf16_path(int layout, int epi, int M, int N, int K, const void* A, long lda, const void* B, long ldb,
+                                 void* C, long ldc, const float* bias, const void* aux_in, long ld_aux_in, void* aux_out,
+                                 long ld_aux_out, int accumulate, float alpha, unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows) {
+  if (!path) return nv_gemm_bf16(layout, epi, M, N, K, A, lda, B, ldb, C, ldc, bias, aux_in, ld_aux_in, aux_out, ld_aux_out, accumulate, alpha, drop_seed, drop_p, stream);
+  NV_CHECK_ARG(layout == 0 && epi == EPI_BIAS_RESID, "nv_gemm_bf16_path: a factor table goes with layout 0, epilogue 4 (bias + residual) only, got (%d, %d)", layout, epi);
+  NV_CHECK_ARG(path_rows > 0 && nv_aligned(path, 4), "nv_gemm_bf16_path: path_rows = %d must be positive, path 4-byte aligned", path_rows);
+  return gemm_bf16_impl(layout, epi, M, N, K, A, lda, B, ldb, C, ldc, bias, aux_in, ld_aux_in, aux_out, ld_aux_out, accumulate, alpha, drop_seed, drop_p, stream, path, path_rows);
 }
 
 // fp8 (OCP e4m3) operands, NT layout: C = epilogue((A8 . B8^T) * colscale[n]).  Eight-wave 256 x 128 kernel only (the path exists for

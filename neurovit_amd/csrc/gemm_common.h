@@ -22,6 +22,8 @@ enum {
                            // tile's <= 128 columns of each row, as (sum, sum of squares) - converted per tile and merged pairwise by the consumer (Chan's update)
   EPI_LNFOLD_STORE = 11,   // C(16-bit) = rstd[m] (acc - mu[m] ln_cs[n]) + bias[n]; (mu, rstd) of row m from ln_stats (ln_tiles partials over K = the LayerNorm width)
   EPI_LNFOLD_GELU = 12,    // C(16-bit) = gelu(the same)
+  EPI_BIAS_RESID_PATH = 13, // EPI_BIAS_RESID with stochastic depth: C(f32) = aux_in + (acc + bias) * (dropout factor * path[m / rows]) - ONE fp32 product of the
+                            // two factors (common.h::PathCfg).  An instantiation of its own: EPI_BIAS_RESID's kernels are the ones every other caller launches
   EPI_ADAMW = 9,        // weight-gradient GEMM that applies torch.optim.AdamW to the weight it differentiates: acc is the gradient of
                         // opt.p[m, n] (same leading dimension as C); p, m, v are updated in place, p16 = bf16(p); C is only written when
                         // opt.keep_grad.  Saves the 4-byte store and the 4-byte re-read of every gradient (8 of 34 B/param per step)
@@ -53,6 +55,7 @@ struct GemmArgs {
   const float* ln_cs = nullptr;      //               colsum over k of W_g[n, k] (of the ROUNDED 16-bit values the MFMA reads)
   int ln_tiles = 0;
   float ln_eps = 0.f;
+  PathCfg path = {nullptr, 1, 1};    // EPI_BIAS_RESID_PATH only
 };
 
 // algorithmic bytes of one GEMM launch: both operands read once, every output written once, epilogue inputs read once
@@ -64,7 +67,7 @@ static inline double gemm_algo_bytes(const GemmArgs& a, int epi, int operand_byt
     case EPI_STORE_F32: b += mn * 4 * (a.accumulate ? 2 : 1) + (a.aux_out ? mn * 2 : 0); break;
     case EPI_BIAS_F32: b += mn * 4; break;
     case EPI_BIAS_GELU: b += mn * 2 + (a.aux_out ? mn * 2 : 0); break;
-    case EPI_BIAS_RESID: b += mn * 8; break;
+    case EPI_BIAS_RESID: case EPI_BIAS_RESID_PATH: b += mn * 8; break;
     case EPI_DGELU: case EPI_DGELU_COLSUM: b += mn * 4; break;
     case EPI_BIAS_GELU_F8: b += mn; break;
     case EPI_BIAS_GELU_F8T: b += mn * 5; break;
@@ -213,11 +216,12 @@ struct EpiCols {        // per column group: bias[n .. n+3] and colscale[n .. n+
 };
 struct EpiNone {};
 template <int EPI> constexpr bool epi_has_bias() {
-  return EPI == EPI_BIAS_F32 || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_GELU_F8 || EPI == EPI_BIAS_GELU_F8T || EPI == EPI_BIAS_RESID_LN;
+  return EPI == EPI_BIAS_F32 || EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_GELU_F8 || EPI == EPI_BIAS_GELU_F8T || EPI == EPI_BIAS_RESID_LN ||
+         EPI == EPI_BIAS_RESID_PATH;
 }
 // per chunk: the residual (f32), the pre-activation u (16-bit) or, for an accumulating fp32 store, the old C
 template <int EPI> constexpr int epi_aux_kind() {
-  return (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_RESID_LN || EPI == EPI_STORE_F32) ? 1 : (EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM) ? 2 : 0;
+  return (EPI == EPI_BIAS_RESID || EPI == EPI_BIAS_RESID_LN || EPI == EPI_STORE_F32 || EPI == EPI_BIAS_RESID_PATH) ? 1 : (EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM) ? 2 : 0;
 }
 template <int KIND> struct epi_aux_sel { typedef EpiNone type; };
 template <> struct epi_aux_sel<1> { typedef f32x4 type; };
@@ -250,7 +254,7 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& g, int m, in
   if (cc.scaled) v *= cc.scale;
   if constexpr (epi_has_bias<EPI>()) v += cc.bias;
   f32x4 keep = f32x4{1.f, 1.f, 1.f, 1.f};
-  if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM || EPI == EPI_BIAS_GELU_F8T) {
+  if constexpr (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RESID || EPI == EPI_DGELU || EPI == EPI_DGELU_COLSUM || EPI == EPI_BIAS_GELU_F8T || EPI == EPI_BIAS_RESID_PATH) {
     if (g.drop.thresh) {
       keep = drop_factor4(g.drop, (unsigned long long)m * g.N + n);      // N % 8 == 0, n % 4 == 0
     }
@@ -293,6 +297,11 @@ __device__ __forceinline__ f32x4 epilogue4(f32x4 v, const GemmArgs& g, int m, in
     *reinterpret_cast<r16x4*>((r16*)g.aux_out2 + (long)m * g.ld_aux_out2 + n) = cvt4<T>(h[0], h[1], h[2], h[3]);
     *reinterpret_cast<unsigned*>((char*)g.C + (long)m * g.ldc + n) = pack_fp8x4(h * g.alpha);
   } else if constexpr (EPI == EPI_BIAS_RESID) {
+    v = v * keep + ax;
+    *reinterpret_cast<f32x4*>((float*)g.C + (long)m * g.ldc + n) = v;
+  } else if constexpr (EPI == EPI_BIAS_RESID_PATH) {
+    // k = e * f first, then k where EPI_BIAS_RESID has e: f == 1 gives its bits.  (One call handles four columns of ONE row: the sample is derived once per row chunk.)
+    keep *= path_factor(g.path, m);
     v = v * keep + ax;
     *reinterpret_cast<f32x4*>((float*)g.C + (long)m * g.ldc + n) = v;
   } else if constexpr (EPI == EPI_BIAS_RESID_LN) {

@@ -434,6 +434,7 @@ static int launch_pp_fmt(int layout, int epi, const GemmArgs& a, hipStream_t s) 
       case EPI_BIAS_F32: return launch_pp_w32_t<T, EPI_BIAS_F32>(a, s);
       case EPI_BIAS_GELU: return launch_pp_w32_t<T, EPI_BIAS_GELU>(a, s);
       case EPI_BIAS_RESID: return launch_pp_w32_t<T, EPI_BIAS_RESID>(a, s);
+      case EPI_BIAS_RESID_PATH: return launch_pp_w32_t<T, EPI_BIAS_RESID_PATH>(a, s);
       default: break;
     }
   }
@@ -443,6 +444,7 @@ static int launch_pp_fmt(int layout, int epi, const GemmArgs& a, hipStream_t s) 
     case 0 * 16 + EPI_BIAS_F32: return launch_pp_t<T, false, false, EPI_BIAS_F32>(a, s);
     case 0 * 16 + EPI_BIAS_GELU: return launch_pp_t<T, false, false, EPI_BIAS_GELU>(a, s);
     case 0 * 16 + EPI_BIAS_RESID: return launch_pp_t<T, false, false, EPI_BIAS_RESID>(a, s);
+    case 0 * 16 + EPI_BIAS_RESID_PATH: return launch_pp_t<T, false, false, EPI_BIAS_RESID_PATH>(a, s);
     case 0 * 16 + EPI_BIAS_RESID_LN: return launch_pp_t<T, false, false, EPI_BIAS_RESID_LN>(a, s);
     case 0 * 16 + EPI_LNFOLD_STORE: return launch_pp_t<T, false, false, EPI_LNFOLD_STORE>(a, s);
     case 0 * 16 + EPI_LNFOLD_GELU: return launch_pp_t<T, false, false, EPI_LNFOLD_GELU>(a, s);

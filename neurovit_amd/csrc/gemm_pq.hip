@@ -220,6 +220,7 @@ int launch_pq_fmt(int layout, int epi, const GemmArgs& a, hipStream_t s) {
     case 0 * 16 + EPI_BIAS_F32: return launch_pq_t<false, false, EPI_BIAS_F32, false, T>(a, s);
     case 0 * 16 + EPI_BIAS_GELU: return launch_pq_t<false, false, EPI_BIAS_GELU, false, T>(a, s);
     case 0 * 16 + EPI_BIAS_RESID: return launch_pq_t<false, false, EPI_BIAS_RESID, false, T>(a, s);
+    case 0 * 16 + EPI_BIAS_RESID_PATH: return launch_pq_t<false, false, EPI_BIAS_RESID_PATH, false, T>(a, s);
     case 1 * 16 + EPI_STORE_BF16: return launch_pq_t<false, true, EPI_STORE_BF16, false, T>(a, s);
     case 1 * 16 + EPI_STORE_F32: return launch_pq_t<false, true, EPI_STORE_F32, false, T>(a, s);
     case 1 * 16 + EPI_DGELU: return launch_pq_t<false, true, EPI_DGELU, false, T>(a, s);

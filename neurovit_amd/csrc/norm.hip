@@ -110,12 +110,15 @@ extern "C" int nv_ln_fwd_f32(const float* x, long ldx, int M, int d, const float
 // g_out = g_in + LN'(dy);  g16 = bf16(g_out * dropmask);  partials[blk][0] = sum dy*xhat, [1] = sum dy, [2] = sum g_out * dropmask.
 // ROWS rows per wave are in flight together (x, dy and the incoming residual gradient are all requested before the first
 // use): the kernel is one dependent memory round trip, not 2 * ROWS of them.
-template <int NV, int ROWS, typename T>
+template <bool PATH> using HeadPath = std::conditional_t<PATH, const float*, NoPath>;      // the head's form of PathArg: path[b] is the factor of volume b
+// PATH: stochastic depth of the branch whose output was added to this residual stream - g16 and the third partial carry g_out * (dropmask *
+// path factor of the row's sample), ONE fp32 product of the two factors (common.h::PathCfg); g_out itself is not scaled.
+template <int NV, int ROWS, typename T, bool PATH>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
                                                      const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                                                      const float* __restrict__ gamma, int M, int d, const float* g_in, float* g_out,
                                                      long ldg, r16* __restrict__ g16, long ldg16, float* __restrict__ partials,
-                                                     DropCfg drop, int seg_rows, int seg_skip) {
+                                                     DropCfg drop, int seg_rows, int seg_skip, PathArg<PATH> path) {
   // seg_rows > 0: dy is segmented - after every seg_rows rows seg_skip rows are skipped (token rows of a [B, 1+N, d] tensor)
   extern __shared__ __attribute__((aligned(16))) float red[];   // [4 waves][d]
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -144,6 +147,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
     for (int r = 0; r < ROWS; ++r) {
       const int row = base + r * nw;
       if (row < M) {                              // wave-uniform
+        [[maybe_unused]] float pf = 1.f;
+        if constexpr (PATH) pf = path_factor(path, row);      // once per row
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -164,7 +169,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
             if (g_in) o += gi[r][v];
             *reinterpret_cast<f32x4*>(g_out + (long)row * ldg + c) = o;
             // g16 / colsum feed the backward of the Linear whose (dropped-out) output was added to this residual stream
-            if (drop.thresh) {
+            if constexpr (PATH) {
+              f32x4 k = f32x4{1.f, 1.f, 1.f, 1.f};
+              if (drop.thresh) k = drop_factor4(drop, (unsigned long long)row * ldg + c);
+              o *= k * pf;
+            } else if (drop.thresh) {
               o *= drop_factor4(drop, (unsigned long long)row * ldg + c);      // element index of the DENSE [M, d] tensor g is a (row-strided) view of: ldg = d x row spacing
             }
             if (g16) *reinterpret_cast<r16x4*>(g16 + (long)row * ldg16 + c) = cvt4<T>(o[0], o[1], o[2], o[3]);
@@ -326,8 +335,10 @@ extern "C" long nv_ln_bwd_workspace_bytes(int M, int d) { return (long)ln_bwd_bl
 static int ln_bwd_launch(const float* dy, long lddy, const float* x, long ldx, const float* mean, const float* rstd, const float* gamma,
                          int M, int d, const float* g_in, float* g_out, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta,
                          float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p,
-                         void* stream, void* reduce_stream, int seg_rows, int seg_skip) {
+                         void* stream, void* reduce_stream, int seg_rows, int seg_skip, const float* path = nullptr, int path_rows = 0) {
   NV_CHECK_ARG(M > 0 && d > 0 && (d % 4) == 0 && d <= 2048, "nv_ln_bwd: d=%d must be a multiple of 4 and <= 2048", d);
+  NV_CHECK_ARG(!path || (path_rows > 0 && nv_aligned(path, 4) && seg_rows == 0 && ldg >= d && (ldg % d) == 0 && (long)M * (ldg / d) < (1L << 31)),
+               "nv_ln_bwd_path: path_rows = %d must be positive and g a (row-strided) view of a dense [*, d] tensor (ldg a multiple of d)", path_rows);
   NV_CHECK_ARG(drop_p == 0.f || (ldg % d) == 0, "nv_ln_bwd: with dropout g must be a (row-strided) view of a dense [*, d] tensor (ldg a multiple of d)");
   const DropCfg drop = make_drop(drop_seed, drop_p);
   NV_CHECK_ARG(ws_bytes >= nv_ln_bwd_workspace_bytes(M, d), "nv_ln_bwd: workspace too small");
@@ -335,13 +346,24 @@ static int ln_bwd_launch(const float* dy, long lddy, const float* x, long ldx, c
   const int nb = ln_bwd_blocks(M);
   hipStream_t s = (hipStream_t)stream;
   const size_t lds = (size_t)WAVES_PER_BLOCK * d * sizeof(float);
-  NV_DISPATCH_OPERAND(T,
-    if (d <= 1024)
-      hipLaunchKernelGGL((ln_bwd_kernel<4, 2, T>), dim3(nb), dim3(256), lds, s, dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg,
-                         (r16*)g16, ldg16, (float*)workspace, drop, seg_rows, seg_skip);
-    else
-      hipLaunchKernelGGL((ln_bwd_kernel<8, 1, T>), dim3(nb), dim3(256), lds, s, dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg,
-                         (r16*)g16, ldg16, (float*)workspace, drop, seg_rows, seg_skip));
+  if (path) {
+    const PathCfg pc{path, path_rows, (int)(ldg / d)};
+    NV_DISPATCH_OPERAND(T,
+      if (d <= 1024)
+        hipLaunchKernelGGL((ln_bwd_kernel<4, 2, T, true>), dim3(nb), dim3(256), lds, s, dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg,
+                           (r16*)g16, ldg16, (float*)workspace, drop, 0, 0, pc);
+      else
+        hipLaunchKernelGGL((ln_bwd_kernel<8, 1, T, true>), dim3(nb), dim3(256), lds, s, dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg,
+                           (r16*)g16, ldg16, (float*)workspace, drop, 0, 0, pc));
+  } else {
+    NV_DISPATCH_OPERAND(T,
+      if (d <= 1024)
+        hipLaunchKernelGGL((ln_bwd_kernel<4, 2, T, false>), dim3(nb), dim3(256), lds, s, dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg,
+                           (r16*)g16, ldg16, (float*)workspace, drop, seg_rows, seg_skip, NoPath{});
+      else
+        hipLaunchKernelGGL((ln_bwd_kernel<8, 1, T, false>), dim3(nb), dim3(256), lds, s, dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg,
+                           (r16*)g16, ldg16, (float*)workspace, drop, seg_rows, seg_skip, NoPath{}));
+  }
   NV_CHECK_LAUNCH("nv_ln_bwd");
   // the parameter-gradient reduction is off the data path: it may run on another stream (the caller then owns `workspace`
   // until that stream has passed this point), or be left to a later nv_ln_bwd_reduce call (reduce_stream = NV_LN_NO_REDUCE)
@@ -371,6 +393,18 @@ extern "C" int nv_ln_bwd(const float* dy, long lddy, const float* x, long ldx, c
                          unsigned long drop_seed, float drop_p, void* stream, void* reduce_stream) {
   return ln_bwd_launch(dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg, g16, ldg16, dgamma, dbeta, dcolsum, accumulate, workspace,
                        ws_bytes, drop_seed, drop_p, stream, reduce_stream, 0, 0);
+}
+
+// nv_ln_bwd under stochastic depth: g16 = cvt(g_out * (dropmask * path[sample])) and dcolsum its column sums; g_out itself as nv_ln_bwd writes it.
+// Row r of the call is dense row r * (ldg / d), its sample that dense row / path_rows.  path = NULL: nv_ln_bwd itself
+extern "C" int nv_ln_bwd_path(const float* dy, long lddy, const float* x, long ldx, const float* mean, const float* rstd,
+                              const float* gamma, int M, int d, const float* g_in, float* g_out, long ldg, void* g16, long ldg16,
+                              float* dgamma, float* dbeta, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                              unsigned long drop_seed, float drop_p, void* stream, void* reduce_stream, const float* path, int path_rows) {
+  if (!path) return nv_ln_bwd(dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg, g16, ldg16, dgamma, dbeta, dcolsum, accumulate, workspace, ws_bytes,
+                              drop_seed, drop_p, stream, reduce_stream);
+  return ln_bwd_launch(dy, lddy, x, ldx, mean, rstd, gamma, M, d, g_in, g_out, ldg, g16, ldg16, dgamma, dbeta, dcolsum, accumulate, workspace,
+                       ws_bytes, drop_seed, drop_p, stream, reduce_stream, 0, 0, path, path_rows);
 }
 
 // --------------------------------------------------------------------------------------- patch gather + LN(patch_dim)
@@ -1153,15 +1187,21 @@ extern "C" int nv_head_fwd(const float* x, long row_stride, int B, int d, const 
 // token mean when pool_mean: then x is the [B, d] pooled matrix and every row of g gets dx / n);
 // writes g[b, 0, :] = dx (fp32 + bf16; the other rows were zeroed by a memset node in front) and per-volume
 // partials [b][3][d] = (dgamma, dbeta, dx) reduced afterwards.
+// PATH: stochastic depth of the last block's FeedForward branch - path[b] is the factor of volume b (every row of g that this workgroup writes
+// belongs to it); g16 and the third partial carry dx * (dropmask * path[b]), ONE fp32 product of the two factors, g itself is not scaled.
+template <bool PATH>
 __device__ __forceinline__ void head_bwd_x_row(int b, float* sh, const float* __restrict__ dlogits, int C, const float* __restrict__ Wt,
                                                const float* __restrict__ x, long row_stride, const float* __restrict__ stats,
                                                const float* __restrict__ gamma, int d, int n, float* __restrict__ g, long ldg,
-                                               r16* __restrict__ g16, long ldg16, float* __restrict__ partials, const DropCfg& drop, int pool_mean, int fp16) {
+                                               r16* __restrict__ g16, long ldg16, float* __restrict__ partials, const DropCfg& drop, int pool_mean, int fp16,
+                                               HeadPath<PATH> path) {
   float* dys = sh;             // dyh[d] + 8 scratch
   float* scratch = sh + d;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const float mean = stats[2 * b], rstd = stats[2 * b + 1];
   const float* row = x + (long)b * row_stride;
+  [[maybe_unused]] float pf = 1.f;
+  if constexpr (PATH) pf = path[b];
   float s1 = 0.f, s2 = 0.f;
   for (int c = tid; c < d; c += 256) {
     float dy = 0.f;
@@ -1188,7 +1228,9 @@ __device__ __forceinline__ void head_bwd_x_row(int b, float* sh, const float* __
       for (int t = 0; t < n; ++t) {
         const long r = (long)b * n + t;
         g[r * ldg + c] = dx;
-        const float dxm = drop.thresh ? dx * drop_factor(drop, (unsigned long long)r * d + c) : dx;
+        float dxm;
+        if constexpr (PATH) dxm = dx * ((drop.thresh ? drop_factor(drop, (unsigned long long)r * d + c) : 1.f) * pf);
+        else dxm = drop.thresh ? dx * drop_factor(drop, (unsigned long long)r * d + c) : dx;
         if (g16) g16[r * ldg16 + c] = cvt1_rt(dxm, fp16);
         cs += dxm;
       }
@@ -1196,17 +1238,20 @@ __device__ __forceinline__ void head_bwd_x_row(int b, float* sh, const float* __
       continue;
     }
     g[(long)b * n * ldg + c] = dx;
-    const float dxm = drop.thresh ? dx * drop_factor(drop, (unsigned long long)b * n * d + c) : dx;   // last block's FF output dropout
+    float dxm;
+    if constexpr (PATH) dxm = dx * ((drop.thresh ? drop_factor(drop, (unsigned long long)b * n * d + c) : 1.f) * pf);
+    else dxm = drop.thresh ? dx * drop_factor(drop, (unsigned long long)b * n * d + c) : dx;   // last block's FF output dropout
     if (g16) g16[(long)b * n * ldg16 + c] = cvt1_rt(dxm, fp16);
     partials[((long)b * 3 + 2) * d + c] = dxm;
   }
 }
 
+template <bool PATH>
 __global__ __launch_bounds__(256) void head_bwd_x_kernel(const float* __restrict__ dlogits, int C, const float* __restrict__ Wt,
                                                          const float* __restrict__ x, long row_stride, const float* __restrict__ stats,
                                                          const float* __restrict__ gamma, int d, int n, float* __restrict__ g, long ldg,
                                                          r16* __restrict__ g16, long ldg16, float* __restrict__ partials, DropCfg drop,
-                                                         int pool_mean, int nvol, int fp16) {
+                                                         int pool_mean, int nvol, int fp16, HeadPath<PATH> path) {
   extern __shared__ __attribute__((aligned(16))) float sh[];   // dyh[d] + 8 scratch
   if ((int)blockIdx.x >= nvol) {
     // pool = 'cls': the residual gradient is zero except for the cls rows the first nvol workgroups write - the rest of this grid
@@ -1216,7 +1261,7 @@ __global__ __launch_bounds__(256) void head_bwd_x_kernel(const float* __restrict
     if (g16) zero_rows_except(reinterpret_cast<char*>(g16), (long)nvol * n, (long)d * 2, n, part, nparts);
     return;
   }
-  head_bwd_x_row(blockIdx.x, sh, dlogits, C, Wt, x, row_stride, stats, gamma, d, n, g, ldg, g16, ldg16, partials, drop, pool_mean, fp16);
+  head_bwd_x_row<PATH>(blockIdx.x, sh, dlogits, C, Wt, x, row_stride, stats, gamma, d, n, g, ldg, g16, ldg16, partials, drop, pool_mean, fp16, path);
 }
 
 // dW[c, k] = sum_b dlogits[b, c] * xh[b, k];  dbias[c] = sum_b dlogits[b, c]
@@ -1257,10 +1302,10 @@ extern "C" int nv_token_mean(const float* x, int B, int n, int d, float* out, vo
 
 extern "C" long nv_head_bwd_workspace_bytes(int B, int d) { return (long)B * 3 * d * sizeof(float); }
 
-extern "C" int nv_head_bwd(const float* dlogits, int B, int C, const float* W, const float* x, long row_stride, const float* stats,
-                           const float* xh, const float* gamma, int d, int n, float* g, long ldg, void* g16, long ldg16,
-                           float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace,
-                           long ws_bytes, unsigned long drop_seed, float drop_p, int pool_mean, void* stream) {
+static int head_bwd_impl(const float* dlogits, int B, int C, const float* W, const float* x, long row_stride, const float* stats,
+                         const float* xh, const float* gamma, int d, int n, float* g, long ldg, void* g16, long ldg16,
+                         float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace,
+                         long ws_bytes, unsigned long drop_seed, float drop_p, int pool_mean, void* stream, const float* path) {
   NV_CHECK_ARG(ws_bytes >= nv_head_bwd_workspace_bytes(B, d), "nv_head_bwd: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d), "nv_head_bwd: g / g16 must be dense [B*n, d]");
@@ -1269,8 +1314,12 @@ extern "C" int nv_head_bwd(const float* dlogits, int B, int C, const float* W, c
   const long fill_bytes = pool_mean ? 0 : (long)B * n * d * (g16 ? 6 : 4);
   int fill_blocks = (int)((fill_bytes + (1 << 16) - 1) >> 16);            // ~64 KiB per workgroup
   if (fill_blocks > 1024) fill_blocks = 1024;
-  hipLaunchKernelGGL(head_bwd_x_kernel, dim3(B + fill_blocks), dim3(256), (d + 8) * sizeof(float), s, dlogits, C, W, x, row_stride, stats, gamma, d, n,
-                     g, ldg, (r16*)g16, ldg16, (float*)workspace, make_drop(drop_seed, drop_p), pool_mean, B, nv_operand_format() == NV_OPERAND_FP16);
+  if (path)
+    hipLaunchKernelGGL(head_bwd_x_kernel<true>, dim3(B + fill_blocks), dim3(256), (d + 8) * sizeof(float), s, dlogits, C, W, x, row_stride, stats, gamma, d, n,
+                       g, ldg, (r16*)g16, ldg16, (float*)workspace, make_drop(drop_seed, drop_p), pool_mean, B, nv_operand_format() == NV_OPERAND_FP16, path);
+  else
+    hipLaunchKernelGGL(head_bwd_x_kernel<false>, dim3(B + fill_blocks), dim3(256), (d + 8) * sizeof(float), s, dlogits, C, W, x, row_stride, stats, gamma, d, n,
+                       g, ldg, (r16*)g16, ldg16, (float*)workspace, make_drop(drop_seed, drop_p), pool_mean, B, nv_operand_format() == NV_OPERAND_FP16, NoPath{});
   NV_CHECK_LAUNCH("nv_head_bwd/x");
   // all parameter-gradient outputs NULL (the data-only backward): the data gradient g / g16 is all there is
   if (!dgamma && !dbeta && !dcolsum && !dW && !dbias) return NV_OK;
@@ -1282,6 +1331,27 @@ extern "C" int nv_head_bwd(const float* dlogits, int B, int C, const float* W, c
   hipLaunchKernelGGL(head_bwd_w_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, dlogits, xh, B, C, d, dW, dbias, accumulate);
   NV_CHECK_LAUNCH("nv_head_bwd/w");
   return NV_OK;
+}
+
+extern "C" int nv_head_bwd(const float* dlogits, int B, int C, const float* W, const float* x, long row_stride, const float* stats,
+                           const float* xh, const float* gamma, int d, int n, float* g, long ldg, void* g16, long ldg16,
+                           float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace,
+                           long ws_bytes, unsigned long drop_seed, float drop_p, int pool_mean, void* stream) {
+  return head_bwd_impl(dlogits, B, C, W, x, row_stride, stats, xh, gamma, d, n, g, ldg, g16, ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes,
+                       drop_seed, drop_p, pool_mean, stream, nullptr);
+}
+
+// nv_head_bwd under stochastic depth: g16 = cvt(dx * (dropmask * path[b])) and dcolsum its column sums, for the rows of volume b (path_rows = n: the
+// sample of dense row b n + t is b); g as nv_head_bwd writes it.  path = NULL: nv_head_bwd itself
+extern "C" int nv_head_bwd_path(const float* dlogits, int B, int C, const float* W, const float* x, long row_stride, const float* stats,
+                                const float* xh, const float* gamma, int d, int n, float* g, long ldg, void* g16, long ldg16,
+                                float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace,
+                                long ws_bytes, unsigned long drop_seed, float drop_p, int pool_mean, void* stream, const float* path, int path_rows) {
+  if (!path) return nv_head_bwd(dlogits, B, C, W, x, row_stride, stats, xh, gamma, d, n, g, ldg, g16, ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace,
+                                ws_bytes, drop_seed, drop_p, pool_mean, stream);
+  NV_CHECK_ARG(path_rows == n && nv_aligned(path, 4), "nv_head_bwd_path: path_rows = %d must be n = %d (the head's rows are grouped by volume), path 4-byte aligned", path_rows, n);
+  return head_bwd_impl(dlogits, B, C, W, x, row_stride, stats, xh, gamma, d, n, g, ldg, g16, ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes,
+                       drop_seed, drop_p, pool_mean, stream, path);
 }
 
 // ---- the head's forward, nn.CrossEntropyLoss and the head's backward in TWO launches instead of five (the train step as one call,
@@ -1324,8 +1394,8 @@ struct NoSoft {};
 template <bool Soft> using SoftArg = std::conditional_t<Soft, CeSoft, NoSoft>;
 
 // launch 1: workgroup b = volume b (forward, loss term, backward to the cls row of g), the others clear g / g16 outside the cls rows
-template <bool Soft>
-__global__ __launch_bounds__(256) void head_rows_kernel(const HeadStep a, const SoftArg<Soft> o) {
+template <bool Soft, bool PATH>
+__global__ __launch_bounds__(256) void head_rows_kernel(const HeadStep a, const SoftArg<Soft> o, HeadPath<PATH> path) {
   extern __shared__ __attribute__((aligned(16))) float sh[];   // d floats + 8 scratch + 4 (loss reductions) (+ 4 doubles, Soft: the denominator)
   if ((int)blockIdx.x >= a.B) {
     const int part = blockIdx.x - a.B, nparts = gridDim.x - a.B;
@@ -1347,7 +1417,7 @@ __global__ __launch_bounds__(256) void head_rows_kernel(const HeadStep a, const 
   else term = ce_row_term(row, a.labels[b], a.C, gs, red, dl);
   if (threadIdx.x == 0) a.terms[b] = term;
   __syncthreads();
-  head_bwd_x_row(b, sh, a.dlogits, a.C, a.W, a.x, a.row_stride, a.stats, a.gamma, a.d, a.n, a.g, a.ldg, a.g16, a.ldg16, a.partials, a.drop, 0, a.fp16);
+  head_bwd_x_row<PATH>(b, sh, a.dlogits, a.C, a.W, a.x, a.row_stride, a.stats, a.gamma, a.d, a.n, a.g, a.ldg, a.g16, a.ldg16, a.partials, a.drop, 0, a.fp16, path);
 }
 // launch 2: everything that sums over the volumes - the loss, (dgamma, dbeta, column sum of the cls-row gradient), dW, dbias
 template <bool Soft>
@@ -1387,9 +1457,9 @@ extern "C" long nv_head_step_workspace_bytes(int B, int d) { return nv_head_bwd_
 static int head_step(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W, const float* bias, int C,
                      const long* labels, float grad_scale, const float* scale_state, const nv_loss_opts* opts, float* xh, float* stats, float* logits,
                      float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta, float* dW, float* dbias,
-                     float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p, void* stream) {
+                     float* dcolsum, int accumulate, void* workspace, long ws_bytes, unsigned long drop_seed, float drop_p, void* stream, const float* path = nullptr) {
   const bool soft = loss_opts_on(opts);
-  const char* who = soft ? "nv_head_step_soft" : "nv_head_step";
+  const char* who = path ? "nv_head_step_path" : (soft ? "nv_head_step_soft" : "nv_head_step");
   NV_CHECK_ARG(B > 0 && d > 0 && C > 0 && C <= d && n > 0, "%s: B = %d, d = %d, C = %d, n = %d", who, B, d, C, n);
   NV_CHECK_ARG(x && gamma && beta && W && bias && labels && xh && stats && logits && loss && dlogits && g && dgamma && dbeta && dW && dbias && workspace,
                "%s: null pointer", who);
@@ -1407,8 +1477,10 @@ static int head_step(const float* x, long row_stride, int B, int d, const float*
   if (fill_blocks > 1024) fill_blocks = 1024;
   const dim3 rows(B + fill_blocks), sums((unsigned)((3L * d + (long)C * d + 255) / 256));
   const hipStream_t s = (hipStream_t)stream;
-  if (soft) hipLaunchKernelGGL(head_rows_kernel<true>, rows, dim3(256), (d + 12 + 8) * sizeof(float), s, a, make_ce_soft(opts));
-  else hipLaunchKernelGGL(head_rows_kernel<false>, rows, dim3(256), (d + 12) * sizeof(float), s, a, NoSoft{});
+  if (path && soft) hipLaunchKernelGGL((head_rows_kernel<true, true>), rows, dim3(256), (d + 12 + 8) * sizeof(float), s, a, make_ce_soft(opts), path);
+  else if (path) hipLaunchKernelGGL((head_rows_kernel<false, true>), rows, dim3(256), (d + 12) * sizeof(float), s, a, NoSoft{}, path);
+  else if (soft) hipLaunchKernelGGL((head_rows_kernel<true, false>), rows, dim3(256), (d + 12 + 8) * sizeof(float), s, a, make_ce_soft(opts), NoPath{});
+  else hipLaunchKernelGGL((head_rows_kernel<false, false>), rows, dim3(256), (d + 12) * sizeof(float), s, a, NoSoft{}, NoPath{});
   NV_CHECK_LAUNCH(soft ? "nv_head_step_soft/rows" : "nv_head_step/rows");
   if (soft) hipLaunchKernelGGL(head_sums_kernel<true>, sums, dim3(256), 0, s, a);
   else hipLaunchKernelGGL(head_sums_kernel<false>, sums, dim3(256), 0, s, a);
@@ -1441,6 +1513,21 @@ extern "C" int nv_head_step_soft(const float* x, long row_stride, int B, int d, 
   if (int rc = check_loss_opts(opts, "nv_head_step_soft")) return rc;
   return head_step(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, opts, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
                    dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
+}
+
+// The fused head step under stochastic depth, one form for the plain / scaled / soft variants (scale_state and opts may each be NULL, as for
+// nv_head_step_soft): g16 and dcolsum as nv_head_bwd_path leaves them.  path = NULL: nv_head_step_soft itself
+extern "C" int nv_head_step_path(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                                 const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, const nv_loss_opts* opts,
+                                 float* xh, float* stats, float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16,
+                                 float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                                 unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows) {
+  if (!path) return nv_head_step_soft(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, opts, xh, stats, logits, loss, dlogits, n, g, ldg,
+                                      g16, ldg16, dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream);
+  if (int rc = check_loss_opts(opts, "nv_head_step_path")) return rc;
+  NV_CHECK_ARG(path_rows == n && nv_aligned(path, 4), "nv_head_step_path: path_rows = %d must be n = %d (the head's rows are grouped by volume), path 4-byte aligned", path_rows, n);
+  return head_step(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, opts, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
+                   dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream, path);
 }
 
 // --------------------------------------------------------------------------------------- column sum of a bf16 matrix (bias grads)

@@ -20,10 +20,11 @@ constexpr int SK_R = 4;       // rows per launch slice (blockIdx.y walks slices)
 enum { SK_NT_RESID = 0, SK_NT_GELU = 1 };
 enum { SK_NN_DGELU = 0, SK_NN_F32 = 1, SK_NN_BF16 = 2 };
 
-template <int EPI, typename T>
+// PATH (SK_NT_RESID only): stochastic depth - the dropout factor is multiplied by the sample's path factor first (common.h::PathCfg)
+template <int EPI, typename T, bool PATH>
 __global__ __launch_bounds__(256) void skinny_nt_kernel(const r16* __restrict__ A, long lda, int R, const r16* __restrict__ W, long ldw, int N, int K,
                                                         const float* __restrict__ bias, const float* __restrict__ resid, long ldr,
-                                                        void* __restrict__ out, long ldo, r16* __restrict__ u_out, long ldu, DropCfg drop) {
+                                                        void* __restrict__ out, long ldo, r16* __restrict__ u_out, long ldu, DropCfg drop, PathArg<PATH> path) {
   const int lane = threadIdx.x & 63, n = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int r0 = blockIdx.y * SK_R, rows = (R - r0 < SK_R) ? R - r0 : SK_R;
   if (n >= N) return;
@@ -71,7 +72,8 @@ __global__ __launch_bounds__(256) void skinny_nt_kernel(const r16* __restrict__ 
     const float v = mine + bias[n];
     // nn.Dropout of the site (vit_3d.py:21,23,45): the mask of the DENSE [M, N] tensor this launch writes a few rows of - `out` is a strided view of it
     // (ldo = N x row spacing), so the element offset row * ldo + n IS the dense element index the tiled epilogues hash (gemm_common.h::epilogue4)
-    const float keep = drop.thresh ? drop_factor(drop, (unsigned long long)(row * ldo + n)) : 1.f;
+    float keep = drop.thresh ? drop_factor(drop, (unsigned long long)(row * ldo + n)) : 1.f;
+    if constexpr (PATH) keep *= path_factor(path, (int)row);      // (a lane holds one row: once per row)
     if constexpr (EPI == SK_NT_RESID) {
       ((float*)out)[row * ldo + n] = v * keep + resid[row * ldr + n];
     } else {
@@ -215,10 +217,30 @@ extern "C" int nv_skinny_nt(int epi, int R, int N, int K, const void* A, long ld
   hipStream_t s = (hipStream_t)stream;
   NV_DISPATCH_OPERAND(T,
     if (epi == SK_NT_RESID)
-      hipLaunchKernelGGL((skinny_nt_kernel<SK_NT_RESID, T>), grid, block, 0, s, (const r16*)A, lda, R, (const r16*)W, ldw, N, K, bias, resid, ldr, out, ldo, (r16*)nullptr, 0L, drop);
+      hipLaunchKernelGGL((skinny_nt_kernel<SK_NT_RESID, T, false>), grid, block, 0, s, (const r16*)A, lda, R, (const r16*)W, ldw, N, K, bias, resid, ldr, out, ldo, (r16*)nullptr, 0L, drop, NoPath{});
     else
-      hipLaunchKernelGGL((skinny_nt_kernel<SK_NT_GELU, T>), grid, block, 0, s, (const r16*)A, lda, R, (const r16*)W, ldw, N, K, bias, resid, ldr, out, ldo, (r16*)u_out, ldu, drop));
+      hipLaunchKernelGGL((skinny_nt_kernel<SK_NT_GELU, T, false>), grid, block, 0, s, (const r16*)A, lda, R, (const r16*)W, ldw, N, K, bias, resid, ldr, out, ldo, (r16*)u_out, ldu, drop, NoPath{}));
   NV_CHECK_LAUNCH("nv_skinny_nt");
+  return NV_OK;
+}
+
+// nv_skinny_nt epilogue 0 under stochastic depth: out = resid + (bias + A W^T) * (dropout factor * path[sample]); strided row r is dense row
+// r * (ldo / N) of the [samples * path_rows, N] tensor `out` is a view of, its sample that dense row / path_rows.  path = NULL: nv_skinny_nt itself
+extern "C" int nv_skinny_nt_path(int epi, int R, int N, int K, const void* A, long lda, const void* W, long ldw, const float* bias, const float* resid,
+                                 long ldr, void* out, long ldo, void* u_out, long ldu, unsigned long drop_seed, float drop_p, void* stream, const float* path,
+                                 int path_rows) {
+  if (!path) return nv_skinny_nt(epi, R, N, K, A, lda, W, ldw, bias, resid, ldr, out, ldo, u_out, ldu, drop_seed, drop_p, stream);
+  NV_CHECK_ARG(epi == SK_NT_RESID && resid, "nv_skinny_nt_path: a factor table goes with epilogue 0 (bias + residual) only, got %d", epi);
+  NV_CHECK_ARG(R > 0 && N > 0 && K > 0 && (K % 8) == 0 && (lda % 8) == 0 && (ldw % 8) == 0 && A && W && bias && out && nv_aligned16(A) && nv_aligned16(W),
+               "nv_skinny_nt_path: K, lda, ldw must be multiples of 8, operands 16-byte aligned");
+  NV_CHECK_ARG(path_rows > 0 && nv_aligned(path, 4) && ldo >= N && (ldo % N) == 0 && (long)R * (ldo / N) < (1L << 31),
+               "nv_skinny_nt_path: path_rows = %d must be positive and `out` a row-strided view of a dense [M, N] tensor (ldo a multiple of N)", path_rows);
+  const DropCfg drop = make_drop(drop_seed, drop_p);
+  const PathCfg pc{path, path_rows, (int)(ldo / N)};
+  const dim3 grid((N + 3) / 4, (R + SK_R - 1) / SK_R), block(256);
+  NV_DISPATCH_OPERAND(T, hipLaunchKernelGGL((skinny_nt_kernel<SK_NT_RESID, T, true>), grid, block, 0, (hipStream_t)stream, (const r16*)A, lda, R, (const r16*)W, ldw, N, K, bias,
+                                            resid, ldr, out, ldo, (r16*)nullptr, 0L, drop, pc));
+  NV_CHECK_LAUNCH("nv_skinny_nt_path");
   return NV_OK;
 }
 

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _cabi, ops
-from ._cabi import AttnExport, AttnGradExport, BackwardOpts, TrainHparams, VitConfig, VitInput, check, lib
+from ._cabi import AttnExport, AttnGradExport, BackwardOpts, DropPath, TrainHparams, VitConfig, VitInput, check, lib
 
 _BYTES = {torch.float32: 4, torch.bfloat16: 2, torch.float16: 2}
 
@@ -75,15 +75,17 @@ def _drop(dropout):
 
 class _Pass:
     """One forward and what a backward of it, or a tap into its workspace, needs: batch, layout (0 inference, 1 training, 2 fp32), workspace,
-    input (the backward re-gathers the patches), input form `keep` = (vol_sigma, nv_vit_input), form of the last block, dropout draw.
+    input (the backward re-gathers the patches), input form `keep` = (vol_sigma, nv_vit_input), form of the last block, dropout draw,
+    stochastic-depth table `drop_path` (device fp32 [depth, 2, B], or None: the backward of the pass must be given the same factors).
     `done`: a whole backward has run - the workspace may be refilled.  `grad_ready`: a backward has left the hook gradient in the workspace."""
-    __slots__ = ("B", "layout", "ws", "video", "keep", "rows_form", "dropout", "dlogits", "dtokens", "done", "grad_ready", "_claim", "__weakref__")
+    __slots__ = ("B", "layout", "ws", "video", "keep", "rows_form", "dropout", "drop_path", "dlogits", "dtokens", "done", "grad_ready", "_claim", "__weakref__")
 
     class _Claim:
         __slots__ = ("__weakref__",)
 
-    def __init__(self, B, layout, ws, video, keep=(None, None), rows_form=0, dropout=(0.0, 0.0, 0), done=False):
+    def __init__(self, B, layout, ws, video, keep=(None, None), rows_form=0, dropout=(0.0, 0.0, 0), done=False, drop_path=None):
         self.B, self.layout, self.ws, self.video, self.keep, self.rows_form, self.dropout = B, int(layout), ws, video, keep, rows_form, dropout
+        self.drop_path = drop_path
         self.dlogits, self.dtokens, self.done, self.grad_ready, self._claim = None, None, done, done, None
 
     def claim(self):
@@ -188,9 +190,10 @@ class VitRuntime(PassLedger):
         return nbytes
 
     def _forward(self, entry: str, video, layout, weights, mid=(), after=(), *, vol_sigma=None, time_points: int = 0, rows_form=None,
-                 attn_export=None, dropout=(0.0, 0.0, 0), operands: bool = True, step: bool = False):
+                 attn_export=None, dropout=(0.0, 0.0, 0), operands: bool = True, step: bool = False, drop_path=None):
         """What every forward shares: checks, input form, workspace and logits, the C call
-        `entry`(cfg, B, video, shape, strides, input, *weights, workspace, bytes, *mid, logits, *after, stream[, aux stream]), the pass record.
+        `entry`(cfg, B, video, shape, strides, input, *weights, workspace, bytes, *mid, logits, *after, stream[, aux stream][, drop path]), the pass record.
+        drop_path: the stochastic-depth table of an *_sd entry (checked here), kept with the pass for its backward.
         step: the one-call train step - the primary training workspace (a pending pass in it goes stale), the auxiliary stream, a done pass.
         Returns (pass, logits)."""
         rows_form = self.rows_form if rows_form is None else int(rows_form)
@@ -198,13 +201,26 @@ class VitRuntime(PassLedger):
             _cabi.set_operand_format(self.operands)
         B, inp = self._input_form(video, vol_sigma, time_points, rows_form, attn_export)
         dev = video.device
+        sd = self._path_struct(drop_path, B, dev)
         ws = self.workspace(B, True, dev) if step else self.acquire(B, layout, dev)
         logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
         check(getattr(lib, entry)(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video), _inp_ptr(inp), *weights,
                                   ws.data_ptr(), ws.numel(), *mid, logits.data_ptr(), *after, torch.cuda.current_stream().cuda_stream,
-                                  *((self._aux_stream(dev),) if step else ())), entry)
-        # a backward re-gathers the same (raw) input and takes the same form of the last block
-        return self.open(_Pass(B, layout, ws, video, (vol_sigma, inp), rows_form, dropout, done=step)), logits
+                                  *((self._aux_stream(dev),) if step else ()), *(() if sd is None else (ctypes.byref(sd),))), entry)
+        # a backward re-gathers the same (raw) input and takes the same form of the last block - and the same stochastic-depth factors
+        return self.open(_Pass(B, layout, ws, video, (vol_sigma, inp), rows_form, dropout, done=step, drop_path=drop_path)), logits
+
+    def _path_struct(self, drop_path, B: int, device) -> Optional[DropPath]:
+        """nv_vit_drop_path of a stochastic-depth table (None: none) after checking it: contiguous fp32 [depth, 2, B] on the input's device.
+        The struct holds a raw pointer: the table is kept alive by the pass record."""
+        if drop_path is None:
+            return None
+        want = (self.cfg.depth, 2, B)
+        if not (torch.is_tensor(drop_path) and drop_path.is_cuda and drop_path.device == device and drop_path.dtype == torch.float32
+                and tuple(drop_path.shape) == want and drop_path.is_contiguous()):
+            raise ValueError(f"neurovit_amd: drop_path must be a contiguous fp32 device tensor [depth, 2, B] = {list(want)} on {device}, got "
+                             f"{tuple(drop_path.shape) if torch.is_tensor(drop_path) else type(drop_path).__name__}")
+        return DropPath(ctypes.sizeof(DropPath), drop_path.data_ptr())
 
     def _input_form(self, video: torch.Tensor, vol_sigma, time_points: int, rows_form: int = 0, attn_export: Optional[AttnExport] = None):
         """(B, nv_vit_input or None) after checking the extents: plain [B, C, F, H, W] view, or (time_points > 0) a contiguous
@@ -263,14 +279,20 @@ class VitRuntime(PassLedger):
 
     def forward(self, video: torch.Tensor, params: torch.Tensor, params16: torch.Tensor, training: bool,
                 dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, time_points: int = 0, rows_form: Optional[int] = None,
-                attn_export: Optional[AttnExport] = None) -> torch.Tensor:
+                attn_export: Optional[AttnExport] = None, drop_path: Optional[torch.Tensor] = None) -> torch.Tensor:
         """video: [B, C, F, H, W] fp32 view (any strides).  Returns logits [B, num_classes] fp32.
+        drop_path: None, or the stochastic-depth factors of this forward, fp32 [depth, 2, B] on the device (0 or 1 / (1 - q) per block,
+        branch and sample; ops.drop_path_draw) - training forwards only, not the fused 4D form (nv_vit_forward_sd).  The pass keeps the
+        table: backward() hands the same factors to the engine.
         dropout = (p of the blocks, p of the embedding, seed) - (0, 0, *) in eval mode.
         vol_sigma / time_points: the optional input forms of nv_vit_forward_in (raw volumes; contiguous 4D batch).
         rows_form: 1 = the last block on every row (as the reference computes it), 2 = on the cls rows when eligible,
         None = this runtime's default (`self.rows_form`: the process default unless NEUROVIT_CLS_TAIL=0)."""
-        return self._forward("nv_vit_forward_in", video, training, (params.data_ptr(), params16.data_ptr()), (int(training),) + _drop(dropout),
-                             vol_sigma=vol_sigma, time_points=time_points, rows_form=rows_form, attn_export=attn_export, dropout=dropout)[1]
+        if drop_path is not None and (not training or time_points):
+            raise ValueError("neurovit_amd: drop_path belongs to training forwards (training=True) of the plain input form (no time_points)")
+        return self._forward("nv_vit_forward_in" if drop_path is None else "nv_vit_forward_sd", video, training, (params.data_ptr(), params16.data_ptr()),
+                             (int(training),) + _drop(dropout), vol_sigma=vol_sigma, time_points=time_points, rows_form=rows_form, attn_export=attn_export,
+                             dropout=dropout, drop_path=drop_path)[1]
 
     # ------------------------------------------------------------------ inference forward with the LayerNorms folded into the GEMMs around them
     def lnfold_prepare(self, params: torch.Tensor, reuse=None):
@@ -360,7 +382,7 @@ class VitRuntime(PassLedger):
                  accumulate: bool, stages: Optional[Tuple[int, int]] = None, join_aux: bool = True,
                  grads16: Optional[torch.Tensor] = None, dvideo: Optional[torch.Tensor] = None, weight_grads: bool = True,
                  attn_grad: Optional[AttnGradExport] = None, *, of: Optional[_Pass] = None, final: bool = False,
-                 dtokens: Optional[torch.Tensor] = None) -> None:
+                 dtokens: Optional[torch.Tensor] = None, drop_path: Optional[torch.Tensor] = None) -> None:
         """Whole backward, or only stages [first, last] (0 = head, 1+k = layer depth-1-k, depth+1 = embedding).
         of: the pass to run against (several may be pending: siamese / two-forward losses), by default the most recent training forward.
         final: nothing more of this pass will run although the stages stop short of the embedding - like a whole backward, the call
@@ -374,11 +396,17 @@ class VitRuntime(PassLedger):
         every exported layer inside the stage range (nv_vit_backward_attn); needs a forward without block dropout.
         dtokens (instead of dlogits, which is then None): fp32 [B, n, dim] or [B n, dim], the gradient w.r.t. the last block's output, cls rows
         included - the backward of a loss on the tokens (nv_vit_backward_tokens).  The head takes no part: its gradient range is zeroed
-        (left alone when accumulating).  The forward must have run with rows_form=1; no attention-gradient export in this form."""
+        (left alone when accumulating).  The forward must have run with rows_form=1; no attention-gradient export in this form.
+        drop_path: the stochastic-depth factors of the forward; None = the table the pass kept (forward(drop_path=...)), which is what a
+        backward must be given (nv_vit_backward_sd).  Not with dtokens."""
         if (dlogits is None) == (dtokens is None):
             raise ValueError("neurovit_amd: backward() takes dlogits or dtokens, not both and not neither")
         rec = self.backward_pass(of)
         B, ws, video = rec.B, rec.ws, rec.video
+        drop_path = rec.drop_path if drop_path is None else drop_path
+        if drop_path is not None and dtokens is not None:
+            raise NotImplementedError("neurovit_amd: backward(dtokens=...) of a forward under stochastic depth - the token-level backward carries no path factors")
+        sd = self._path_struct(drop_path, B, video.device)
         if rec.keep[1] is not None and rec.keep[1].time_points:
             raise NotImplementedError("neurovit_amd: the fused 4D input form is forward-only (the 4D model's encoder is frozen, NeuroEncoder.py:34-36)")
         first, last = (0, self.cfg.depth + 1) if stages is None else stages
@@ -404,14 +432,15 @@ class VitRuntime(PassLedger):
                                 None if dstrides is None else ctypes.cast(dstrides, ctypes.c_void_p), int(bool(weight_grads)))
         # grads16: bf16 arena (element offsets of `grads`) that also receives the Linear weight gradients, rounded, straight from
         # their GEMMs - the data-parallel message buffer (mirrored_ranges() lists what lands there)
-        check(lib.nv_vit_backward_attn(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
-                                       params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
-                                       None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
-                                       int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
-                                       torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
-                                       int(join_aux), int(rec.rows_form), None if opts is None else ctypes.byref(opts),
-                                       None if attn_grad is None else ctypes.byref(attn_grad)),
-              "nv_vit_backward_attn")
+        entry = "nv_vit_backward_attn" if sd is None else "nv_vit_backward_sd"
+        check(getattr(lib, entry)(ctypes.byref(self.cfg), B, video.data_ptr(), ops.strides5(video), params.data_ptr(),
+                                  params16.data_ptr(), ws.data_ptr(), ws.numel(), rec.dlogits.data_ptr(),
+                                  None if grads is None else grads.data_ptr(), None if grads16 is None else grads16.data_ptr(),
+                                  int(accumulate), first, last, float(rec.dropout[0]), float(rec.dropout[1]), int(rec.dropout[2]),
+                                  torch.cuda.current_stream().cuda_stream, self._aux_stream(video.device) if weight_grads else None,
+                                  int(join_aux), int(rec.rows_form), None if opts is None else ctypes.byref(opts),
+                                  None if attn_grad is None else ctypes.byref(attn_grad), *(() if sd is None else (ctypes.byref(sd),))),
+              entry)
         if final or last == self.cfg.depth + 1:
             rec.finish()
 
@@ -454,7 +483,8 @@ class VitRuntime(PassLedger):
                    adam_m: torch.Tensor, adam_v: torch.Tensor, *, step: int, lr: float, betas, eps: float, weight_decay: float,
                    grad_scale: float = 1.0, accumulate: bool = False, update: bool = True, fuse_update: int = 0,
                    dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, rows_form: Optional[int] = None,
-                   loss_scale: float = 0.0, loss_scale_state: Optional[torch.Tensor] = None, dp=None, loss_opts=None):
+                   loss_scale: float = 0.0, loss_scale_state: Optional[torch.Tensor] = None, dp=None, loss_opts=None,
+                   drop_path: Optional[torch.Tensor] = None):
         """The reference's whole train step (Trainer.py:65-79) as ONE native call (nv_vit_train_step): forward, CrossEntropyLoss,
         backward of every stage, AdamW over the arena + bf16 shadow refresh.  Returns (loss [1], logits [B, C]) on the device.
         Same launches, streams and arithmetic as forward() + ops.ce_loss + backward() + ops.adamw_step.
@@ -463,7 +493,8 @@ class VitRuntime(PassLedger):
         loss_scale: static factor on d(loss)/d(logits), divided out again by the update; loss_scale_state: the device block of a
         dynamic loss scale (optim.LossScaler) - GradScaler semantics on the device, needs fuse_update = 0.
         loss_opts: None, or a _cabi.LossOpts (ops.loss_opts: label smoothing, class weights, a mix table) - the step then goes
-        through nv_vit_train_step_ex; the tensors it points to are the caller's to keep alive."""
+        through nv_vit_train_step_ex; the tensors it points to are the caller's to keep alive.
+        drop_path: None, or the step's stochastic-depth factors fp32 [depth, 2, B] on the device (nv_vit_train_step_sd; every form above)."""
         B, dev = video.shape[0], video.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dlogits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
@@ -473,10 +504,13 @@ class VitRuntime(PassLedger):
                           None if dp is None else ctypes.cast(ctypes.pointer(dp), ctypes.c_void_p),      # _cabi.DpPlan (kept alive by the caller)
                           None if loss_scale_state is None else loss_scale_state.data_ptr())
         extra = () if loss_opts is None else (ctypes.byref(loss_opts),)
-        rec, logits = self._forward("nv_vit_train_step_ex" if extra else "nv_vit_train_step", video, 1,
+        entry = "nv_vit_train_step_ex" if extra else "nv_vit_train_step"
+        if drop_path is not None:
+            entry, extra = "nv_vit_train_step_sd", extra or (None,)
+        rec, logits = self._forward(entry, video, 1,
                                     (params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr()), (labels.data_ptr(),),
                                     (loss.data_ptr(), dlogits.data_ptr(), ctypes.byref(hp)) + extra + _drop(dropout),
-                                    vol_sigma=vol_sigma, rows_form=rows_form, dropout=dropout, step=True)
+                                    vol_sigma=vol_sigma, rows_form=rows_form, dropout=dropout, step=True, drop_path=drop_path)
         rec.dlogits = dlogits
         return loss, logits
 

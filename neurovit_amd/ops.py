@@ -54,16 +54,28 @@ def cast_ranges_bf16(src: torch.Tensor, dst: torch.Tensor, ranges) -> None:
     check(lib.nv_cast_ranges_bf16(_p(src), _p(dst), begins, lens, len(ranges), _stream()), "nv_cast_ranges_bf16")
 
 
+NO_PATH = object()      # `path` of the wrappers below: not given - the symbol without a factor table; None or a tensor - the *_path symbol (None = NULL)
+
+
+def _path_call(name: str, path, path_rows: int):
+    """(C function, trailing arguments) of a kernel-level call: `name`, or `name`_path with (path, path_rows) - path = the fp32 [samples]
+    stochastic-depth factors of one site, path_rows = token rows per sample"""
+    if path is NO_PATH:
+        return getattr(lib, name), ()
+    return getattr(lib, name + "_path"), (_p(path), int(path_rows))
+
+
 def skinny_nt(epi: int, A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, out: torch.Tensor, resid: Optional[torch.Tensor] = None,
-              u_out: Optional[torch.Tensor] = None, drop_seed: int = 0, drop_p: float = 0.0) -> torch.Tensor:
+              u_out: Optional[torch.Tensor] = None, drop_seed: int = 0, drop_p: float = 0.0, path=NO_PATH, path_rows: int = 0) -> torch.Tensor:
     """out[r] = epilogue(A[r] @ W.T) on a few rows; A / resid / out / u_out may be row-strided 2-D views (e.g. x[::n]).
     epi 0: out f32 = resid + (bias + A W^T) * mask; epi 1: u = bias + A W^T (bf16, optional), out bf16 = gelu(u) * mask.
     mask: nn.Dropout of the dense tensor `out` is a view of (element offsets are hashed), drop_p = 0: none."""
     _need_cuda(A, W)
     R, K = A.shape
     N = W.shape[0]
-    check(lib.nv_skinny_nt(epi, R, N, K, _p(A), A.stride(0), _p(W), W.stride(0), _p(bias), _p(resid), 0 if resid is None else resid.stride(0),
-                           _p(out), out.stride(0), _p(u_out), 0 if u_out is None else u_out.stride(0), int(drop_seed), float(drop_p), _stream()), "nv_skinny_nt")
+    fn, tail = _path_call("nv_skinny_nt", path, path_rows)
+    check(fn(epi, R, N, K, _p(A), A.stride(0), _p(W), W.stride(0), _p(bias), _p(resid), 0 if resid is None else resid.stride(0),
+             _p(out), out.stride(0), _p(u_out), 0 if u_out is None else u_out.stride(0), int(drop_seed), float(drop_p), _stream(), *tail), "nv_skinny_nt")
     return out
 
 
@@ -84,8 +96,9 @@ def strides5(video: torch.Tensor):
 
 
 def gemm(layout: int, epi: int, A: torch.Tensor, B: torch.Tensor, *, out: Optional[torch.Tensor] = None, bias=None,
-         aux_in=None, aux_out=None, accumulate: bool = False, alpha: float = 1.0, drop_seed: int = 0, drop_p: float = 0.0) -> torch.Tensor:
-    """C = op(A) op(B) with a fused epilogue; A, B bf16 2-D row-major (last stride 1)."""
+         aux_in=None, aux_out=None, accumulate: bool = False, alpha: float = 1.0, drop_seed: int = 0, drop_p: float = 0.0,
+         path=NO_PATH, path_rows: int = 0) -> torch.Tensor:
+    """C = op(A) op(B) with a fused epilogue; A, B bf16 2-D row-major (last stride 1).  path / path_rows: nv_gemm_bf16_path (epilogue 4)."""
     _need_cuda(A, B)
     assert A.dtype == op16() and B.dtype == op16() and A.stride(1) == 1 and B.stride(1) == 1
     if layout == NT:
@@ -98,9 +111,10 @@ def gemm(layout: int, epi: int, A: torch.Tensor, B: torch.Tensor, *, out: Option
     if out is None:
         out = torch.empty((M, N), dtype=odt, device=A.device)
     assert out.dtype == odt and out.shape == (M, N) and out.stride(1) == 1
-    check(lib.nv_gemm_bf16(layout, epi, M, N, K, _p(A), A.stride(0), _p(B), B.stride(0), _p(out), out.stride(0), _p(bias),
-                           _p(aux_in), 0 if aux_in is None else aux_in.stride(0), _p(aux_out),
-                           0 if aux_out is None else aux_out.stride(0), int(accumulate), float(alpha), drop_seed, drop_p, _stream()), "nv_gemm_bf16")
+    fn, tail = _path_call("nv_gemm_bf16", path, path_rows)
+    check(fn(layout, epi, M, N, K, _p(A), A.stride(0), _p(B), B.stride(0), _p(out), out.stride(0), _p(bias),
+             _p(aux_in), 0 if aux_in is None else aux_in.stride(0), _p(aux_out),
+             0 if aux_out is None else aux_out.stride(0), int(accumulate), float(alpha), drop_seed, drop_p, _stream(), *tail), "nv_gemm_bf16")
     return out
 
 
@@ -217,7 +231,8 @@ def ln_fwd(x: torch.Tensor, gamma, beta, eps: float = 1e-5):
     return y, st
 
 
-def ln_bwd(dy, x, st, gamma, g_in=None, want_g16=True, accumulate=False, dgamma=None, dbeta=None, dcolsum=None, drop_seed=0, drop_p=0.0):
+def ln_bwd(dy, x, st, gamma, g_in=None, want_g16=True, accumulate=False, dgamma=None, dbeta=None, dcolsum=None, drop_seed=0, drop_p=0.0,
+           path=NO_PATH, path_rows: int = 0):
     _need_cuda(dy, x)
     M, d = x.shape
     g_out = torch.empty((M, d), dtype=torch.float32, device=x.device) if g_in is None else g_in
@@ -227,8 +242,9 @@ def ln_bwd(dy, x, st, gamma, g_in=None, want_g16=True, accumulate=False, dgamma=
     dcolsum = torch.empty(d, device=x.device) if dcolsum is None else dcolsum
     nb = lib.nv_ln_bwd_workspace_bytes(M, d)
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
-    check(lib.nv_ln_bwd(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(st[0]), _p(st[1]), _p(gamma), M, d, _p(g_in), _p(g_out), d, _p(g16), d,
-                        _p(dgamma), _p(dbeta), _p(dcolsum), int(accumulate), _p(ws), nb, drop_seed, drop_p, _stream(), None), "nv_ln_bwd")
+    fn, tail = _path_call("nv_ln_bwd", path, path_rows)
+    check(fn(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(st[0]), _p(st[1]), _p(gamma), M, d, _p(g_in), _p(g_out), d, _p(g16), d,
+             _p(dgamma), _p(dbeta), _p(dcolsum), int(accumulate), _p(ws), nb, drop_seed, drop_p, _stream(), None, *tail), "nv_ln_bwd")
     return g_out, g16, dgamma, dbeta, dcolsum
 
 
@@ -384,7 +400,7 @@ def head_fwd(x: torch.Tensor, gamma, beta, W, bias, eps=1e-5):
     return logits, xh, st
 
 
-def head_bwd(dlogits, W, x, st, xh, gamma, drop_seed=0, drop_p=0.0):
+def head_bwd(dlogits, W, x, st, xh, gamma, drop_seed=0, drop_p=0.0, path=NO_PATH, path_rows: int = 0):
     B, n, d = x.shape
     C = W.shape[0]
     dev = x.device
@@ -393,8 +409,9 @@ def head_bwd(dlogits, W, x, st, xh, gamma, drop_seed=0, drop_p=0.0):
     dW = torch.empty((C, d), device=dev); db = torch.empty(C, device=dev)
     nb = lib.nv_head_bwd_workspace_bytes(B, d)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    check(lib.nv_head_bwd(_p(dlogits), B, C, _p(W), _p(x), n * d, _p(st), _p(xh), _p(gamma), d, n, _p(g), d, _p(g16), d, _p(dgamma), _p(dbeta),
-                          _p(dW), _p(db), _p(dcol), 0, _p(ws), nb, drop_seed, drop_p, 0, _stream()), "nv_head_bwd")
+    fn, tail = _path_call("nv_head_bwd", path, path_rows)
+    check(fn(_p(dlogits), B, C, _p(W), _p(x), n * d, _p(st), _p(xh), _p(gamma), d, n, _p(g), d, _p(g16), d, _p(dgamma), _p(dbeta),
+             _p(dW), _p(db), _p(dcol), 0, _p(ws), nb, drop_seed, drop_p, 0, _stream(), *tail), "nv_head_bwd")
     return g, g16, dgamma, dbeta, dW, db, dcol
 
 
@@ -411,13 +428,20 @@ def _head_step_outputs(B, n, d, C, dev):
     return (logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol), ws
 
 
-def head_step(x, gamma, beta, W, bias, labels, eps=1e-5, drop_seed=0, drop_p=0.0):
+def head_step(x, gamma, beta, W, bias, labels, eps=1e-5, drop_seed=0, drop_p=0.0, path=NO_PATH, path_rows: int = 0, scale_state=None, opts=None):
     """nv_head_step: head forward + CrossEntropyLoss + head backward in two launches.  Returns what head_fwd, ce_loss and head_bwd return together:
-    (logits, xh, st, loss, dlogits, g, g16, dgamma, dbeta, dW, db, dcol)."""
+    (logits, xh, st, loss, dlogits, g, g16, dgamma, dbeta, dW, db, dcol).  path given (None = NULL): nv_head_step_path, which also takes the
+    scale_state / opts of nv_head_step_scaled / _soft."""
     B, n, d = x.shape
     C = W.shape[0]
     outs, ws = _head_step_outputs(B, n, d, C, x.device)
     logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol = outs
+    if path is not NO_PATH:
+        check(lib.nv_head_step_path(_p(x), n * d, B, d, _p(gamma), _p(beta), eps, _p(W), _p(bias), C, _p(labels), 1.0, _p(scale_state),
+                                    None if opts is None else ctypes.byref(opts), _p(xh), _p(st), _p(logits), _p(loss), _p(dl), n, _p(g), d, _p(g16), d,
+                                    _p(dgamma), _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), ws.numel(), drop_seed, drop_p, _stream(), _p(path), int(path_rows)),
+              "nv_head_step_path")
+        return outs
     check(lib.nv_head_step(_p(x), n * d, B, d, _p(gamma), _p(beta), eps, _p(W), _p(bias), C, _p(labels), 1.0, _p(xh), _p(st), _p(logits), _p(loss), _p(dl),
                            n, _p(g), d, _p(g16), d, _p(dgamma), _p(dbeta), _p(dW), _p(db), _p(dcol), 0, _p(ws), ws.numel(), drop_seed, drop_p, _stream()),
           "nv_head_step")
@@ -1220,3 +1244,24 @@ def token_grad_seed(dtokens: torch.Tensor, drop_seed: int = 0, drop_p: float = 0
     colsum = torch.empty(d, dtype=torch.float32, device=dtokens.device)
     reduce_multi([(part, d, (colsum,), False)])
     return g, g16, colsum
+
+
+def check_drop_path(rate, schedule) -> None:
+    """ValueError for a stochastic-depth rate outside [0, 1) or a schedule that is not 'linear' / 'constant' (no device work)"""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
+        raise ValueError(f"neurovit_amd: drop_path_rate must be a number in [0, 1), got {rate!r}")
+    if schedule not in _cabi.DROP_PATH_SCHEDULES:
+        raise ValueError(f"neurovit_amd: drop_path_schedule must be 'linear' or 'constant', got {schedule!r}")
+
+
+def drop_path_draw(seed: int, B: int, depth: int, rate: float, schedule: str = "linear", device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [depth, 2, B] stochastic-depth factors (0 or 1 / (1 - q_l) per block, branch and sample), drawn on the device from the seed:
+    schedule "linear" q_l = rate * l / (depth - 1) (timm's linspace), "constant" q_l = rate.  nv_drop_path_draw, one launch; nothing is
+    read back.  The table VitRuntime.forward / backward / train_step take as drop_path=."""
+    check_drop_path(rate, schedule)
+    if out is None:
+        out = torch.empty((depth, 2, B), dtype=torch.float32, device=device)
+    _need_cuda(out)
+    assert out.shape == (depth, 2, B) and out.dtype == torch.float32 and out.is_contiguous()
+    check(lib.nv_drop_path_draw(int(seed), int(B), int(depth), float(rate), _cabi.DROP_PATH_SCHEDULES[schedule], _p(out), _stream()), "nv_drop_path_draw")
+    return out

@@ -169,6 +169,7 @@ class MaskedPretrainStep:
         if model.config.get('TRAINING_DIM') != 3:
             raise NotImplementedError("MaskedPretrainStep: pretraining is for the 3D model - the 4D model adopts a (pretrained, then fine-tuned) 3D encoder")
         vit = self._vit = model.volume_encoder.vit3d
+        vit.refuse_drop_path("MaskedPretrainStep")
         c = vit._cfg
         if c.channels != 1:
             raise ValueError(f"MaskedPretrainStep: the reconstruction target is a one-channel volume, the encoder has channels = {c.channels}")
@@ -251,6 +252,7 @@ class MaskedPretrainStep:
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         x = self._check_input(x)
         vit, opt, head = self._vit, self.optimizer, self.head
+        vit.refuse_drop_path("MaskedPretrainStep")        # (the rate is a plain attribute: it may have been set since the step was built)
         if head.operands != vit.operands:                  # (the model's operand format was switched after this step was built)
             head.set_operands(vit.operands)
         self.last_lr = self._base_lr if self.lr_schedule is None else self.lr_schedule.lr_at(opt.steps + 1)

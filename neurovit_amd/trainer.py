@@ -366,10 +366,12 @@ class TrainStep:
         vit.check_video(video, arena_checked=True)                       # (_native_ok has just validated / rebuilt the arena)
         m, v = opt.arena_state(vit)
         g0 = opt.param_groups[0]
+        drop = vit.draw_dropout()
+        table = vit.draw_drop_path(video.shape[0], drop[2], video.device)      # stochastic depth: the step's factor table, None unless the rate is positive
         return vit._rt.train_step(video, labels, vit._arena, vit._shadow, vit.gradient_arena(), m, v, step=step, lr=g0["lr"], betas=g0["betas"],
                                   eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate, update=update,
-                                  fuse_update=fuse, dropout=vit.draw_dropout(), loss_scale=self.static_scale,
-                                  loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo)
+                                  fuse_update=fuse, dropout=drop, loss_scale=self.static_scale,
+                                  loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo, drop_path=table)
 
     def _after_native(self, logits, fuse: int = 0) -> None:
         """what follows the native call or its replay: the outputs, and .grad as views of the gradient arena (once; they stay valid)"""
@@ -444,7 +446,8 @@ class TrainStep:
             raise NotImplementedError("neurovit_amd.TrainStep: the native one-call step exports no attention gradients - backward hooks on "
                                       "`attend` need the general path (forward + backward through autograd)")
         lo = self._loss_opts(labels, mix)
-        plan = self._plan(fmri.shape[0] * vit.pos_embedding.shape[1], vit._dropout_p != (0.0, 0.0), lo is not None)
+        # (a positive stochastic-depth rate counts as live dropout: the table is drawn per step from the step's seed, nothing a replay could carry)
+        plan = self._plan(fmri.shape[0] * vit.pos_embedding.shape[1], vit._dropout_p != (0.0, 0.0) or vit.drop_path_rate > 0, lo is not None)
         got = self._graph_step(fmri, labels) if plan.graph_ok else None
         if got is not None:
             return got

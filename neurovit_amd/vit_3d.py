@@ -275,8 +275,16 @@ class Transformer(nn.Module):
                 FeedForward(dim, mlp_dim, dropout=dropout)
             ]))
 
+    # stochastic depth of the ViT that owns this module (ViT.drop_path_rate / drop_path_schedule read and write these): the per-sample
+    # factors live in the native engine's residual adds, which a standalone call of this module does not run
+    drop_path_rate = 0.0
+    drop_path_schedule = "linear"
+
     def forward(self, x):
         """Standalone use (vit_3d.py:72-75): pre-norm residual blocks, no final LayerNorm."""
+        if self.training and self.drop_path_rate > 0:
+            raise NotImplementedError("neurovit_amd.Transformer: called on its own in train mode with drop_path_rate > 0 - stochastic depth is "
+                                      "applied by ViT.forward (the native engine's residual adds); call eval() or set the rate to 0")
         for attn, ff in self.layers:
             x = attn(x) + x
             x = ff(x) + x
@@ -319,7 +327,7 @@ class _ViTFunction(torch.autograd.Function):
         # need_grad is decided by the caller: grad mode is always off inside Function.forward, and ctx.needs_input_grad
         # reflects requires_grad alone (it stays True under torch.no_grad()), so neither tells whether a graph is being built
         ctx.module = module
-        out = module._run_forward(video, need_grad, extra)
+        out = module._run_forward(video, need_grad, extra, paths=True)
         ctx.rec = module._rt.current if need_grad else None   # THIS pass's workspace and input ...
         ctx.claim = ctx.rec.claim() if need_grad else None    # ... held until its backward has run or the graph is gone
         return out
@@ -368,8 +376,9 @@ class ViT(FlatArena, nn.Module):
     """vit_3d.py:77-126, MI355X-native.  forward(video[B, C, F, H, W]) -> [B, num_classes] (fp32)."""
 
     def __init__(self, *, image_size, image_patch_size, frames, frame_patch_size, num_classes, dim, depth, heads, mlp_dim,
-                 pool='cls', channels=3, dim_head=64, dropout=0., emb_dropout=0.):
+                 pool='cls', channels=3, dim_head=64, dropout=0., emb_dropout=0., drop_path_rate=0.0, drop_path_schedule="linear"):
         super().__init__()
+        ops.check_drop_path(drop_path_rate, drop_path_schedule)
         image_height, image_width = pair(image_size)
         patch_height, patch_width = pair(image_patch_size)
 
@@ -393,6 +402,11 @@ class ViT(FlatArena, nn.Module):
         self.dropout = nn.Dropout(emb_dropout)
 
         self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout)
+        # stochastic depth (beyond the reference; timm's drop_path_rate): in train mode branch c of block l is dropped per sample with probability
+        # q_l ("linear": rate * l / (depth - 1), "constant": rate) and kept samples are scaled by 1 / (1 - q_l).  Plain attributes, also of a loaded model.
+        self.drop_path_rate, self.drop_path_schedule = drop_path_rate, drop_path_schedule
+        self.last_drop_path = None      # the factor table [depth, 2, B] of the most recent training forward or native step (device; None before)
+        self._path_bufs = {}
 
         self.pool = pool
         self.to_latent = nn.Identity()
@@ -547,6 +561,8 @@ class ViT(FlatArena, nn.Module):
         enable_fp8 again to recalibrate.  Dropout works as in the bf16 forward (same masks).  Default: training forwards keep using bf16."""
         if self.operands != "bf16":
             raise RuntimeError("neurovit_amd.ViT: the fp8 path is built beside bf16 operands - set_operands('bf16') first")
+        if training:
+            self.refuse_drop_path("enable_fp8(training=True)")
         self.flat_parameters()
         self._refresh_shadow()
         scales = self._rt.calibrate_fp8(calibration_video.float(), self._arena, self._shadow, headroom, out_proj)
@@ -581,21 +597,75 @@ class ViT(FlatArena, nn.Module):
                 self.eval_precision = before
         return scope()
 
+    # ------------------------------------------------------------------ stochastic depth
+    @property
+    def drop_path_rate(self) -> float:
+        return self.transformer.drop_path_rate
+
+    @drop_path_rate.setter
+    def drop_path_rate(self, rate) -> None:
+        ops.check_drop_path(rate, self.transformer.drop_path_schedule)
+        self.transformer.drop_path_rate = float(rate)
+
+    @property
+    def drop_path_schedule(self) -> str:
+        return self.transformer.drop_path_schedule
+
+    @drop_path_schedule.setter
+    def drop_path_schedule(self, schedule) -> None:
+        ops.check_drop_path(self.transformer.drop_path_rate, schedule)
+        self.transformer.drop_path_schedule = schedule
+
+    def refuse_drop_path(self, who: str) -> None:
+        """NotImplementedError for the paths that carry no path factors, on a model whose rate is positive"""
+        if self.drop_path_rate > 0:
+            raise NotImplementedError(f"neurovit_amd.ViT: {who} runs without stochastic depth, this model has drop_path_rate = {self.drop_path_rate} - "
+                                      "set it to 0 for this path (it is a plain attribute)")
+
+    def draw_drop_path(self, B: int, seed: int, device):
+        """The factor table fp32 [depth, 2, B] of the next training forward of B volumes, drawn on the device from the step's dropout seed
+        (nv_drop_path_draw: nothing is read back) into a buffer kept per B; None in eval mode or at rate 0.  Also left in `last_drop_path`."""
+        if not (self.training and self.drop_path_rate > 0):
+            return None
+        buf = self._path_bufs.get((B, str(device)))
+        cur = self._rt.current
+        if buf is not None and cur is not None and cur.drop_path is buf and cur.held and not cur.done:
+            buf = None          # a pending pass (siamese / two-forward losses) still needs its table for its backward: this forward takes another
+        table = ops.drop_path_draw(seed, B, self._cfg.depth, self.drop_path_rate, self.drop_path_schedule, device=device, out=buf)
+        if len(self._path_bufs) >= 16:
+            self._path_bufs.clear()
+        self._path_bufs[(B, str(device))] = self.last_drop_path = table
+        return table
+
     # ------------------------------------------------------------------ execution
     def draw_dropout(self):
-        """(p of the blocks, p of the embedding, seed) of the next forward: (0, 0, 0) in eval mode or without dropout."""
-        if self.training and (self._dropout_p[0] > 0 or self._dropout_p[1] > 0):
+        """(p of the blocks, p of the embedding, seed) of the next forward: (0, 0, 0) in eval mode or without dropout and stochastic depth
+        (a positive drop_path_rate draws a seed - the table's - even when both dropout rates are 0)."""
+        if self.training and (self._dropout_p[0] > 0 or self._dropout_p[1] > 0 or self.drop_path_rate > 0):
             # nn.Dropout semantics (vit_3d.py:21,23,39,45,100) with a counter-based mask: a fresh seed per forward from
             # torch's CPU generator (so torch.manual_seed reproduces runs); backward recomputes the same masks.
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             return (self._dropout_p[0], self._dropout_p[1], seed)
         return (0.0, 0.0, 0)
 
-    def _run_forward(self, video, need_grad, extra=(None, 0, None)):
+    def _run_forward(self, video, need_grad, extra=(None, 0, None), paths=False):
+        """paths: the forward of ViT.forward - in train mode with a positive drop_path_rate it draws a factor table and runs under it; the
+        attribution passes (recording_forward, integrated_gradients) never do."""
         vol_sigma, time_points, export = (tuple(extra) + (None,))[:3]
         drop = self.draw_dropout()
         if self.eval_precision not in ("bf16", "fp16", "fp32"):
             raise ValueError(f"neurovit_amd.ViT: eval_precision must be 'bf16', 'fp16' or 'fp32', got {self.eval_precision!r}")
+        if paths and self.training and self.drop_path_rate > 0:
+            if time_points:
+                raise NotImplementedError("neurovit_amd.ViT: no stochastic depth through the fused 4D input form (time_points) - pass the [B*T, C, F, H, W] volumes")
+            if self._fp8 is not None and self.fp8_training:
+                raise NotImplementedError("neurovit_amd.ViT: no stochastic depth in the fp8 training forward - disable_fp8() / enable_fp8(training=False), or drop_path_rate = 0")
+            self._refresh_shadow()
+            table = self.draw_drop_path(video.shape[0], drop[2], video.device)
+            # (the training layout also without a graph: the factors live in the training forward's residual adds)
+            self._last_logits = self._rt.forward(video, self._arena, self._shadow, training=True, dropout=drop, vol_sigma=vol_sigma, attn_export=export,
+                                                 drop_path=table)
+            return self._last_logits
         if self.eval_precision == "fp32" and not need_grad and not self.training:
             self._last_logits = self._rt.forward_f32(video, self._arena, vol_sigma=vol_sigma, time_points=time_points, attn_export=export)
             return self._last_logits
@@ -996,6 +1066,7 @@ class ViT(FlatArena, nn.Module):
         `video` that requires grad receives its gradient.  16-bit operand arithmetic (`operands`); not with the fp8 training forward,
         data parallel gradient buckets or backward hooks on `attend`."""
         self.check_video(video)
+        self.refuse_drop_path("forward_tokens")
         if self._fp8 is not None and self.fp8_training:
             raise NotImplementedError("neurovit_amd.ViT: forward_tokens runs the 16-bit training forward - disable_fp8() or enable_fp8(training=False) first")
         need_grad = torch.is_grad_enabled() and (video.requires_grad or any(p.requires_grad for p in self._plist))
