@@ -227,7 +227,9 @@ int nv_zscore_crop(const void* raw, int dtype, const long* strides5, int B, cons
 
 /* ---- patch embedding front end (vit_3d.py:92-93 + the permute of NeuroEncoder.py:200-202)
  * video [B,C,F,H,W] f32 with arbitrary element strides (pass the strides of the permuted VIEW of the
- * [B,H,W,D] dataset tensor - no copy); out bf16 [B*N, ldo] = LayerNorm(patch_dim)(patches). */
+ * [B,H,W,D] dataset tensor - no copy); out bf16 [B*N, ldo] = LayerNorm(patch_dim)(patches).
+ * Columns patch_dim .. ldo-1 of every row: nv_patch_ln_fwd and nv_patch_ln_fwd_f32 WRITE THEM AS ZERO (the padded K of the patch-embedding GEMM);
+ * nv_patch_ln_fwd_4d and nv_patch_ln_fwd_4d_f32 leave them as they were.  No form writes a row it does not own. */
 int nv_patch_ln_fwd(const float* video, const long* strides5, int B, int C, int F, int H, int W, int p1, int p2, int pf,
                     const float* gamma, const float* beta, float eps, void* out, long ldo, float* mean, float* rstd,
                     const float* vol_sigma, void* stream);

@@ -137,33 +137,35 @@ def gemm_f32(epi: int, A: torch.Tensor, W: torch.Tensor, *, bias=None, resid=Non
     return out
 
 
-def attn_fwd_f32(qkv: torch.Tensor, B: int, n: int, heads: int, dim_head: int = 64) -> torch.Tensor:
-    """qkv f32 [B*n, 3*inner] -> out f32 [B*n, inner] (softmax(q k^T / sqrt(dh)) v per head, fp32 MFMA)."""
+def attn_fwd_f32(qkv: torch.Tensor, B: int, n: int, heads: int, dim_head: int = 64, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qkv f32 [B*n, 3*inner] -> out f32 [B*n, inner] (softmax(q k^T / sqrt(dh)) v per head, fp32 MFMA); out: a row-strided view to write."""
     _need_cuda(qkv)
     assert qkv.dtype == torch.float32 and qkv.stride(1) == 1
     inner = heads * dim_head
-    out = torch.empty((B * n, inner), dtype=torch.float32, device=qkv.device)
-    check(lib.nv_attn_fwd_f32(_p(qkv), qkv.stride(0), B, n, heads, dim_head, dim_head ** -0.5, _p(out), inner, _stream()), "nv_attn_fwd_f32")
+    out = _out2d(out, B * n, inner, torch.float32, qkv)
+    check(lib.nv_attn_fwd_f32(_p(qkv), qkv.stride(0), B, n, heads, dim_head, dim_head ** -0.5, _p(out), out.stride(0), _stream()), "nv_attn_fwd_f32")
     return out
 
 
-def ln_fwd_f32(x: torch.Tensor, gamma, beta, eps: float = 1e-5) -> torch.Tensor:
+def ln_fwd_f32(x: torch.Tensor, gamma, beta, eps: float = 1e-5, *, y: Optional[torch.Tensor] = None, st=None) -> torch.Tensor:
+    """y: a row-strided view to write; st: (mean, rstd) f32 [M] each, written when given"""
     _need_cuda(x)
     M, d = x.shape
-    y = torch.empty((M, d), dtype=torch.float32, device=x.device)
-    check(lib.nv_ln_fwd_f32(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, _p(y), d, None, None, _stream()), "nv_ln_fwd_f32")
+    y = _out2d(y, M, d, torch.float32, x)
+    mean, rstd = (None, None) if st is None else (st[0], st[1])
+    check(lib.nv_ln_fwd_f32(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, _p(y), y.stride(0), _p(mean), _p(rstd), _stream()), "nv_ln_fwd_f32")
     return y
 
 
-def patch_ln_fwd_f32(video: torch.Tensor, p1: int, p2: int, pf: int, gamma, beta, eps: float = 1e-5, vol_sigma=None):
+def patch_ln_fwd_f32(video: torch.Tensor, p1: int, p2: int, pf: int, gamma, beta, eps: float = 1e-5, vol_sigma=None, *, out=None, st=None):
     """As patch_ln_fwd with fp32 tokens [B*N, P] (fp32 inference path)."""
     _need_cuda(video)
     B, C, F, H, W = video.shape
     P = C * p1 * p2 * pf
     N = (F // pf) * (H // p1) * (W // p2)
-    out = torch.empty((B * N, P), dtype=torch.float32, device=video.device)
-    st = torch.empty((2, B * N), dtype=torch.float32, device=video.device)
-    check(lib.nv_patch_ln_fwd_f32(_p(video), strides5(video), B, C, F, H, W, p1, p2, pf, _p(gamma), _p(beta), eps, _p(out), P, _p(st[0]),
+    out = _out2d(out, B * N, P, torch.float32, video)
+    st = torch.empty((2, B * N), dtype=torch.float32, device=video.device) if st is None else st
+    check(lib.nv_patch_ln_fwd_f32(_p(video), strides5(video), B, C, F, H, W, p1, p2, pf, _p(gamma), _p(beta), eps, _p(out), out.stride(0), _p(st[0]),
                                   _p(st[1]), _p(vol_sigma), _stream()), "nv_patch_ln_fwd_f32")
     return out, st
 
@@ -222,51 +224,67 @@ def adamw_ranges(opt, ranges) -> None:
     check(lib.nv_adamw_ranges(ctypes.byref(opt), b, l, n, _stream()), "nv_adamw_ranges")
 
 
-def ln_fwd(x: torch.Tensor, gamma, beta, eps: float = 1e-5):
+def ln_fwd(x: torch.Tensor, gamma, beta, eps: float = 1e-5, *, y: Optional[torch.Tensor] = None, st=None):
+    """y: a row-strided 16-bit view to write (its leading dimension is passed on); st: [2, M], or a pair of f32 [M] (mean, rstd)"""
     _need_cuda(x)
     M, d = x.shape
-    y = torch.empty((M, d), dtype=op16(), device=x.device)
-    st = torch.empty((2, M), dtype=torch.float32, device=x.device)
-    check(lib.nv_ln_fwd(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, _p(y), d, _p(st[0]), _p(st[1]), _stream()), "nv_ln_fwd")
+    y = _out2d(y, M, d, op16(), x)
+    st = torch.empty((2, M), dtype=torch.float32, device=x.device) if st is None else st
+    check(lib.nv_ln_fwd(_p(x), x.stride(0), M, d, _p(gamma), _p(beta), eps, _p(y), y.stride(0), _p(st[0]), _p(st[1]), _stream()), "nv_ln_fwd")
     return y, st
 
 
 def ln_bwd(dy, x, st, gamma, g_in=None, want_g16=True, accumulate=False, dgamma=None, dbeta=None, dcolsum=None, drop_seed=0, drop_p=0.0,
-           path=NO_PATH, path_rows: int = 0):
+           path=NO_PATH, path_rows: int = 0, *, g_out: Optional[torch.Tensor] = None, g16: Optional[torch.Tensor] = None):
+    """g_out / g16: row-strided views to write (ldg / ldg16 = their .stride(0); g_in, read through ldg, must share g_out's).  Not given:
+    g_out is g_in (in place) or a fresh dense tensor, g16 a fresh dense tensor when want_g16."""
     _need_cuda(dy, x)
     M, d = x.shape
-    g_out = torch.empty((M, d), dtype=torch.float32, device=x.device) if g_in is None else g_in
-    g16 = torch.empty((M, d), dtype=op16(), device=x.device) if want_g16 else None
+    if g_out is None:
+        g_out = torch.empty((M, d), dtype=torch.float32, device=x.device) if g_in is None else g_in
+    assert g_out.dtype == torch.float32 and g_out.shape == (M, d) and g_out.stride(1) == 1
+    assert g_in is None or (g_in.shape == (M, d) and g_in.stride(1) == 1 and (M == 1 or g_in.stride(0) == g_out.stride(0))), "g_in and g_out share ldg"
+    if g16 is None:
+        g16 = torch.empty((M, d), dtype=op16(), device=x.device) if want_g16 else None
+    assert g16 is None or (g16.dtype == op16() and g16.shape == (M, d) and g16.stride(1) == 1)
     dgamma = torch.empty(d, device=x.device) if dgamma is None else dgamma
     dbeta = torch.empty(d, device=x.device) if dbeta is None else dbeta
     dcolsum = torch.empty(d, device=x.device) if dcolsum is None else dcolsum
     nb = lib.nv_ln_bwd_workspace_bytes(M, d)
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
     fn, tail = _path_call("nv_ln_bwd", path, path_rows)
-    check(fn(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(st[0]), _p(st[1]), _p(gamma), M, d, _p(g_in), _p(g_out), d, _p(g16), d,
-             _p(dgamma), _p(dbeta), _p(dcolsum), int(accumulate), _p(ws), nb, drop_seed, drop_p, _stream(), None, *tail), "nv_ln_bwd")
+    check(fn(_p(dy), dy.stride(0), _p(x), x.stride(0), _p(st[0]), _p(st[1]), _p(gamma), M, d, _p(g_in), _p(g_out), g_out.stride(0),
+             _p(g16), d if g16 is None else g16.stride(0), _p(dgamma), _p(dbeta), _p(dcolsum), int(accumulate), _p(ws), nb, drop_seed, drop_p, _stream(), None, *tail), "nv_ln_bwd")
     return g_out, g16, dgamma, dbeta, dcolsum
 
 
-def patch_ln_fwd(video: torch.Tensor, p1: int, p2: int, pf: int, gamma, beta, eps: float = 1e-5, ldo: Optional[int] = None, vol_sigma=None):
-    """video [B,C,F,H,W] (any strides, e.g. the permuted view of a [B,H,W,D] volume)."""
+def patch_ln_fwd(video: torch.Tensor, p1: int, p2: int, pf: int, gamma, beta, eps: float = 1e-5, ldo: Optional[int] = None, vol_sigma=None, *,
+                 out: Optional[torch.Tensor] = None, st=None):
+    """video [B,C,F,H,W] (any strides, e.g. the permuted view of a [B,H,W,D] volume).  out: a 16-bit [B*N, >= P] view to write - its
+    .stride(0) is ldo, and the kernel writes zeros in the columns P .. ldo-1 of every row, whatever the view's width."""
     _need_cuda(video)
     B, C, F, H, W = video.shape
     P = C * p1 * p2 * pf
     N = (F // pf) * (H // p1) * (W // p2)
-    ldo = (P + 7) // 8 * 8 if ldo is None else ldo
-    out = torch.empty((B * N, ldo), dtype=op16(), device=video.device)
-    st = torch.empty((2, B * N), dtype=torch.float32, device=video.device)
+    if out is None:
+        ldo = (P + 7) // 8 * 8 if ldo is None else ldo
+        out = torch.empty((B * N, ldo), dtype=op16(), device=video.device)
+    else:
+        assert out.dtype == op16() and out.shape[0] == B * N and out.shape[1] >= P and out.stride(1) == 1
+        ldo = out.stride(0)
+    st = torch.empty((2, B * N), dtype=torch.float32, device=video.device) if st is None else st
     check(lib.nv_patch_ln_fwd(_p(video), strides5(video), B, C, F, H, W, p1, p2, pf, _p(gamma), _p(beta), eps, _p(out), ldo, _p(st[0]),
                               _p(st[1]), _p(vol_sigma), _stream()), "nv_patch_ln_fwd")
     return out, st
 
 
-def patch_ln_bwd(video, p1, p2, pf, dxp, st, accumulate=False):
+def patch_ln_bwd(video, p1, p2, pf, dxp, st, accumulate=False, *, dgamma=None, dbeta=None):
+    """dxp f32 [B*N, >= P] with any row stride (ldd = dxp.stride(0)); dgamma / dbeta: f32 [P] to write (or add to, accumulate)"""
     B, C, F, H, W = video.shape
     P = C * p1 * p2 * pf
     T = dxp.shape[0]
-    dg = torch.empty(P, device=video.device); db = torch.empty(P, device=video.device)
+    dg = torch.empty(P, device=video.device) if dgamma is None else dgamma
+    db = torch.empty(P, device=video.device) if dbeta is None else dbeta
     nb = lib.nv_patch_ln_bwd_workspace_bytes(T, P)
     ws = torch.empty(nb, dtype=torch.uint8, device=video.device)
     check(lib.nv_patch_ln_bwd(_p(video), strides5(video), B, C, F, H, W, p1, p2, pf, _p(dxp), dxp.stride(0), _p(st[0]), _p(st[1]), _p(dg),
@@ -274,36 +292,69 @@ def patch_ln_bwd(video, p1, p2, pf, dxp, st, accumulate=False):
     return dg, db
 
 
-def embed_finish_fwd(t, B, N, gamma, beta, pos, cls, eps=1e-5, drop_seed=0, drop_p=0.0):
+def patch_ln_dx(video, p1, p2, pf, dxp, st, gamma, *, dvideo: Optional[torch.Tensor] = None):
+    """d loss / d video (f32, the geometry of `video`; dvideo: a [B,C,F,H,W] tensor of any strides to write) from dxp f32 [B*N, >= P] with any
+    row stride (ldd = dxp.stride(0); columns P .. ldd-1 are not read), the forward's token statistics and gamma: nv_patch_ln_dx."""
+    _need_cuda(video, dxp)
+    B, C, F, H, W = video.shape
+    dvideo = torch.empty(video.shape, dtype=torch.float32, device=video.device) if dvideo is None else dvideo
+    assert dvideo.shape == video.shape and dvideo.dtype == torch.float32 and dxp.dtype == torch.float32 and dxp.stride(1) == 1
+    check(lib.nv_patch_ln_dx(_p(video), strides5(video), B, C, F, H, W, p1, p2, pf, _p(dxp), dxp.stride(0), _p(st[0]), _p(st[1]), _p(gamma),
+                             _p(dvideo), strides5(dvideo), _stream()), "nv_patch_ln_dx")
+    return dvideo
+
+
+def embed_finish_fwd(t, B, N, gamma, beta, pos, cls, eps=1e-5, drop_seed=0, drop_p=0.0, *, x: Optional[torch.Tensor] = None, st=None):
+    """x: an f32 [B * (N + 1), d] row-strided view to write (ldx = its .stride(0)) instead of a fresh dense [B, N + 1, d]"""
     d = t.shape[1]
-    x = torch.empty((B, N + 1, d), dtype=torch.float32, device=t.device)
-    st = torch.empty((2, B * N), dtype=torch.float32, device=t.device)
-    check(lib.nv_embed_finish_fwd(_p(t), t.stride(0), B, N, d, _p(gamma), _p(beta), eps, _p(pos), _p(cls), _p(x), d, _p(st[0]), _p(st[1]),
+    ldx = d
+    if x is None:
+        x = torch.empty((B, N + 1, d), dtype=torch.float32, device=t.device)
+    else:
+        assert x.dtype == torch.float32 and x.shape == (B * (N + 1), d) and x.stride(1) == 1
+        ldx = x.stride(0)
+    st = torch.empty((2, B * N), dtype=torch.float32, device=t.device) if st is None else st
+    check(lib.nv_embed_finish_fwd(_p(t), t.stride(0), B, N, d, _p(gamma), _p(beta), eps, _p(pos), _p(cls), _p(x), ldx, _p(st[0]), _p(st[1]),
                                   drop_seed, drop_p, _stream()), "nv_embed_finish_fwd")
     return x, st
 
 
-def embed_finish_bwd(g, t, st, gamma, B, N, drop_seed=0, drop_p=0.0):
+def embed_finish_bwd(g, t, st, gamma, B, N, drop_seed=0, drop_p=0.0, *, dt: Optional[torch.Tensor] = None, dt16: Optional[torch.Tensor] = None,
+                     params=None, data_only: bool = False):
+    """g: f32 [B, N + 1, d] dense, or a 2-D [B * (N + 1), d] row-strided view (ldg = its .stride(0)).  dt / dt16: [B * N, d] row-strided
+    views to write.  params: (dgamma, dbeta, dbias, dpos, dcls) to write; data_only: all five NULL - only dt / dt16 are produced."""
     d = t.shape[1]
     dev = t.device
-    dt = torch.empty((B * N, d), device=dev); dt16 = torch.empty((B * N, d), dtype=op16(), device=dev)
-    dgamma, dbeta, dbias = (torch.empty(d, device=dev) for _ in range(3))
-    dpos = torch.empty((N + 1, d), device=dev); dcls = torch.empty(d, device=dev)
+    dt = _out2d(dt, B * N, d, torch.float32, t)
+    dt16 = _out2d(dt16, B * N, d, op16(), t)
+    if data_only:
+        assert params is None
+        dgamma = dbeta = dbias = dpos = dcls = None
+    elif params is not None:
+        dgamma, dbeta, dbias, dpos, dcls = params
+    else:
+        dgamma, dbeta, dbias = (torch.empty(d, device=dev) for _ in range(3))
+        dpos = torch.empty((N + 1, d), device=dev); dcls = torch.empty(d, device=dev)
     nb = lib.nv_embed_finish_bwd_workspace_bytes(B, N, d)
     ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    g2 = g.reshape(B * (N + 1), d)
-    check(lib.nv_embed_finish_bwd(_p(g2), d, _p(t), t.stride(0), _p(st[0]), _p(st[1]), _p(gamma), B, N, d, _p(dt), d, _p(dt16), d, _p(dgamma),
-                                  _p(dbeta), _p(dbias), _p(dpos), _p(dcls), 0, _p(ws), nb, drop_seed, drop_p, _stream()), "nv_embed_finish_bwd")
+    g2 = g.reshape(B * (N + 1), d) if g.dim() == 3 else g
+    assert g2.shape == (B * (N + 1), d) and g2.stride(1) == 1
+    check(lib.nv_embed_finish_bwd(_p(g2), g2.stride(0), _p(t), t.stride(0), _p(st[0]), _p(st[1]), _p(gamma), B, N, d, _p(dt), dt.stride(0), _p(dt16),
+                                  dt16.stride(0), _p(dgamma), _p(dbeta), _p(dbias), _p(dpos), _p(dcls), 0, _p(ws), nb, drop_seed, drop_p, _stream()),
+          "nv_embed_finish_bwd")
     return dt, dt16, dgamma, dbeta, dbias, dpos, dcls
 
 
-def attn_fwd(qkv: torch.Tensor, B: int, n: int, heads: int, dim_head: int = 64, drop_seed=0, drop_p=0.0):
-    """qkv bf16 [B*n, 3*inner] -> (out bf16 [B*n, inner], lse f32 [B, heads, n])."""
+def attn_fwd(qkv: torch.Tensor, B: int, n: int, heads: int, dim_head: int = 64, drop_seed=0, drop_p=0.0, *, out: Optional[torch.Tensor] = None,
+             lse: Optional[torch.Tensor] = None):
+    """qkv bf16 [B*n, 3*inner] -> (out bf16 [B*n, inner], lse f32 [B, heads, n]).  out: a row-strided view to write (ld_out = its .stride(0));
+    lse: contiguous f32 of B * heads * n cells to write."""
     _need_cuda(qkv)
     inner = heads * dim_head
-    out = torch.empty((B * n, inner), dtype=op16(), device=qkv.device)
-    lse = torch.empty((B, heads, n), dtype=torch.float32, device=qkv.device)
-    check(lib.nv_attn_fwd(_p(qkv), qkv.stride(0), B, n, heads, dim_head, dim_head ** -0.5, _p(out), inner, _p(lse), drop_seed, drop_p, _stream()), "nv_attn_fwd")
+    out = _out2d(out, B * n, inner, op16(), qkv)
+    lse = torch.empty((B, heads, n), dtype=torch.float32, device=qkv.device) if lse is None else lse
+    assert lse.dtype == torch.float32 and lse.numel() == B * heads * n and lse.is_contiguous()
+    check(lib.nv_attn_fwd(_p(qkv), qkv.stride(0), B, n, heads, dim_head, dim_head ** -0.5, _p(out), out.stride(0), _p(lse), drop_seed, drop_p, _stream()), "nv_attn_fwd")
     return out, lse
 
 
@@ -381,12 +432,18 @@ def attn_relevance(maps, start_mean: bool = False) -> torch.Tensor:
     return out
 
 
-def attn_bwd(qkv, out, dout, lse, B, n, heads, dim_head=64, drop_seed=0, drop_p=0.0):
+def attn_bwd(qkv, out, dout, lse, B, n, heads, dim_head=64, drop_seed=0, drop_p=0.0, *, dqkv: Optional[torch.Tensor] = None,
+             delta: Optional[torch.Tensor] = None):
+    """out / dout: [B*n, inner] views that share one row stride (the C call has a single ld_out for both); dqkv: a row-strided view to
+    write (ld_dqkv = its .stride(0)); delta: contiguous f32 of B * heads * n cells to write."""
     inner = heads * dim_head
-    dqkv = torch.empty((B * n, 3 * inner), dtype=op16(), device=qkv.device)
-    delta = torch.empty((B, heads, n), dtype=torch.float32, device=qkv.device)
-    check(lib.nv_attn_bwd(_p(qkv), qkv.stride(0), _p(out), _p(dout), inner, _p(lse), B, n, heads, dim_head, dim_head ** -0.5, _p(delta),
-                          _p(dqkv), 3 * inner, drop_seed, drop_p, _stream()), "nv_attn_bwd")
+    assert out.shape == (B * n, inner) and dout.shape == (B * n, inner) and out.stride(1) == 1 and dout.stride(1) == 1
+    assert out.stride(0) == dout.stride(0), "out and dout share ld_out"
+    dqkv = _out2d(dqkv, B * n, 3 * inner, op16(), qkv)
+    delta = torch.empty((B, heads, n), dtype=torch.float32, device=qkv.device) if delta is None else delta
+    assert delta.dtype == torch.float32 and delta.numel() == B * heads * n and delta.is_contiguous()
+    check(lib.nv_attn_bwd(_p(qkv), qkv.stride(0), _p(out), _p(dout), out.stride(0), _p(lse), B, n, heads, dim_head, dim_head ** -0.5, _p(delta),
+                          _p(dqkv), dqkv.stride(0), drop_seed, drop_p, _stream()), "nv_attn_bwd")
     return dqkv, delta
 
 
@@ -633,6 +690,15 @@ def cast_bf16(src: torch.Tensor, ld_dst: Optional[int] = None, out: Optional[tor
     ld_dst = (cols + 3) // 4 * 4 if ld_dst is None else ld_dst
     dst = torch.empty((rows, ld_dst), dtype=op16(), device=src.device) if out is None else out
     check(lib.nv_cast_bf16_2d(_p(src), src.stride(0), rows, cols, _p(dst), ld_dst, _stream()), "nv_cast_bf16_2d")
+    return dst
+
+
+def copy_2d_f32(src: torch.Tensor, dst: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+    """dst[rows, cols] (+)= src[rows, cols], both f32 and row-strided (nv_copy_2d_f32)."""
+    _need_cuda(src, dst)
+    assert src.dtype == torch.float32 and dst.dtype == torch.float32 and src.shape == dst.shape and src.stride(1) == 1 and dst.stride(1) == 1
+    rows, cols = src.shape
+    check(lib.nv_copy_2d_f32(_p(src), src.stride(0), rows, cols, _p(dst), dst.stride(0), int(bool(accumulate)), _stream()), "nv_copy_2d_f32")
     return dst
 
 
@@ -961,13 +1027,15 @@ def attr_token_sums(attr: torch.Tensor, patch) -> torch.Tensor:
     return sums
 
 
-def dropout_apply(x: torch.Tensor, drop_seed: int = 0, drop_p: float = 0.0, want16: bool = True, want32: bool = False):
-    """x f32 [M, N] times the dropout mask of one site -> (bf16 copy or None, f32 copy or None)."""
+def dropout_apply(x: torch.Tensor, drop_seed: int = 0, drop_p: float = 0.0, want16: bool = True, want32: bool = False, *,
+                  o16: Optional[torch.Tensor] = None, o32: Optional[torch.Tensor] = None):
+    """x f32 [M, N] times the dropout mask of one site -> (bf16 copy or None, f32 copy or None).  o16 / o32: row-strided views to write."""
     _need_cuda(x)
     M, N = x.shape
-    o16 = torch.empty((M, N), dtype=op16(), device=x.device) if want16 else None
-    o32 = torch.empty((M, N), dtype=torch.float32, device=x.device) if want32 else None
-    check(lib.nv_dropout_apply(_p(x), x.stride(0), M, N, drop_seed, drop_p, _p(o16), N, _p(o32), N, _stream()), "nv_dropout_apply")
+    o16 = _out2d(o16, M, N, op16(), x) if (want16 or o16 is not None) else None
+    o32 = _out2d(o32, M, N, torch.float32, x) if (want32 or o32 is not None) else None
+    check(lib.nv_dropout_apply(_p(x), x.stride(0), M, N, drop_seed, drop_p, _p(o16), N if o16 is None else o16.stride(0), _p(o32),
+                               N if o32 is None else o32.stride(0), _stream()), "nv_dropout_apply")
     return o16, o32
 
 
@@ -1091,17 +1159,18 @@ def gemm_f8_resid_drop(A8: torch.Tensor, B8: torch.Tensor, colscale: torch.Tenso
     return out
 
 
-def patch_ln_fwd_4d(x: torch.Tensor, p1: int, p2: int, pf: int, gamma, beta, eps: float = 1e-5, vol_sigma=None):
+def patch_ln_fwd_4d(x: torch.Tensor, p1: int, p2: int, pf: int, gamma, beta, eps: float = 1e-5, vol_sigma=None, *, out=None, st=None, f32: bool = False):
     """x f32 contiguous [Bo, H, W, D, T] -> tokens bf16 [Bo*T*N, P] of the T volumes of every sample (row (bo*T + t)*N + n)."""
     _need_cuda(x)
     assert x.dim() == 5 and x.is_contiguous() and x.dtype == torch.float32
     Bo, H, W, D, T = x.shape
     P = p1 * p2 * pf
     N = (D // pf) * (H // p1) * (W // p2)
-    out = torch.empty((Bo * T * N, P), dtype=op16(), device=x.device)
-    st = torch.empty((2, Bo * T * N), dtype=torch.float32, device=x.device)
-    check(lib.nv_patch_ln_fwd_4d(_p(x), Bo, H, W, D, T, p1, p2, pf, _p(gamma), _p(beta), eps, _p(out), P, _p(st[0]), _p(st[1]), _p(vol_sigma),
-                                 _stream()), "nv_patch_ln_fwd_4d")
+    out = _out2d(out, Bo * T * N, P, torch.float32 if f32 else op16(), x)        # out: a row-strided view to write; f32: nv_patch_ln_fwd_4d_f32
+    st = torch.empty((2, Bo * T * N), dtype=torch.float32, device=x.device) if st is None else st
+    fn = lib.nv_patch_ln_fwd_4d_f32 if f32 else lib.nv_patch_ln_fwd_4d
+    check(fn(_p(x), Bo, H, W, D, T, p1, p2, pf, _p(gamma), _p(beta), eps, _p(out), out.stride(0), _p(st[0]), _p(st[1]), _p(vol_sigma), _stream()),
+          "nv_patch_ln_fwd_4d")
     return out, st
 
 
@@ -1146,25 +1215,26 @@ def ln_fold_weight(W: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bia
     return Wg, cs, fb
 
 
-def gemm_resid_ln(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, resid: torch.Tensor):
+def gemm_resid_ln(A: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, resid: torch.Tensor, *, out=None, out16=None, stats=None):
     """x = resid + (A W^T + bias) as f32, the same rows in the operand format, and the per-tile row statistics (nv_gemm_resid_ln)."""
     _need_cuda(A, W)
     M, K = A.shape
     N = W.shape[0]
-    out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    out16 = torch.empty((M, N), dtype=op16(), device=A.device)
-    stats = torch.empty(lib.nv_ln_fold_stats_floats(M, N), dtype=torch.float32, device=A.device)
+    out = _out2d(out, M, N, torch.float32, A)
+    out16 = _out2d(out16, M, N, op16(), A)
+    stats = torch.empty(lib.nv_ln_fold_stats_floats(M, N), dtype=torch.float32, device=A.device) if stats is None else stats
+    assert stats.dtype == torch.float32 and stats.numel() == lib.nv_ln_fold_stats_floats(M, N) and stats.is_contiguous()
     check(lib.nv_gemm_resid_ln(M, N, K, _p(A), A.stride(0), _p(W), W.stride(0), _p(bias), _p(resid), resid.stride(0), _p(out), out.stride(0), _p(out16), out16.stride(0),
                                _p(stats), _stream()), "nv_gemm_resid_ln")
     return out, out16, stats
 
 
-def gemm_lnfold(X16: torch.Tensor, Wg16: torch.Tensor, stats: torch.Tensor, colsum: torch.Tensor, fbias: torch.Tensor, gelu: bool = False, eps: float = 1e-5):
+def gemm_lnfold(X16: torch.Tensor, Wg16: torch.Tensor, stats: torch.Tensor, colsum: torch.Tensor, fbias: torch.Tensor, gelu: bool = False, eps: float = 1e-5, *, out=None):
     """(gelu)(LayerNorm(x) W^T + b) from the un-normalised rows X16, their statistics and the folded weight (nv_gemm_lnfold)."""
     _need_cuda(X16, Wg16)
     M, K = X16.shape
     N = Wg16.shape[0]
-    out = torch.empty((M, N), dtype=op16(), device=X16.device)
+    out = _out2d(out, M, N, op16(), X16)
     check(lib.nv_gemm_lnfold(int(gelu), M, N, K, _p(X16), X16.stride(0), _p(Wg16), Wg16.stride(0), _p(stats), _p(colsum), _p(fbias), float(eps), _p(out), out.stride(0),
                              _stream()), "nv_gemm_lnfold")
     return out

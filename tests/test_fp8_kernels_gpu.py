@@ -22,13 +22,13 @@ import torch
 
 import fp8_ref as R
 from conftest import rel_err, report
+from ld_windows import SENTINEL, guards_intact, into_padded, padded         # noqa: F401  (shared with tests/test_ld_windows_gpu.py)
 from oracle import ref_cpu
 from test_dropout_masks_cpu import PS, SEED, check_readout, drop_scale, want_gelu
 
 pytestmark = pytest.mark.gpu
 
 FAMILIES = {"256 x 128": (0, 0), "256 x 256": (9, 0)}      # nv_gemm_set_tile: at these sizes the heuristic is the ping-pong family
-SENTINEL = 0xA5
 
 
 @pytest.fixture(scope="module")
@@ -200,27 +200,7 @@ def test_training_epilogues_apply_the_oracle_mask(ops, tally, family, M, N):
 
 
 # ------------------------------------------------------------------------------------------------------------ leading dimensions and guards
-def padded(rows, cols, dtype, pad_cols=8):
-    """([rows, cols] view of a sentinel-filled buffer with two spare rows - one above, one below - and pad_cols spare columns, the buffer)"""
-    esz = torch.empty((), dtype=dtype).element_size()
-    buf = torch.full((rows + 2, (cols + pad_cols) * esz), SENTINEL, dtype=torch.uint8, device="cuda")
-    return buf.view(dtype)[1:rows + 1, :cols], buf
-
-
-def guards_intact(view, buf):
-    rows, cols = view.shape
-    b = buf.clone()
-    b[1:rows + 1, :cols * view.element_size()] = SENTINEL
-    return bool((b == SENTINEL).all())
-
-
-def into_padded(t, pad_cols):
-    """a copy of the 2-D tensor t as a view into a wider sentinel-filled buffer"""
-    view, _ = padded(t.shape[0], t.shape[1], t.dtype, pad_cols)
-    view.copy_(t)
-    return view
-
-
+# (padded, into_padded, guards_intact: tests/ld_windows.py)
 @pytest.mark.parametrize("family", list(FAMILIES))
 def test_gemm_f8_honours_every_leading_dimension(ops, tally, gemm_case, family):
     """A8, B8, the residual and every output as column slices of wider buffers: same bits as the dense run inside, sentinel outside."""
