@@ -528,6 +528,43 @@ int nv_class_scores(const float* logits, int J, int C, const int* jobs, const lo
 int nv_curve_auc(const float* scores, int B, int K, long ld, float* auc, void* stream);
 int nv_occlusion_gather(const float* ref, const float* scores, const int* labels, int B, int N, int NB, float* maps, void* stream);
 
+/* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) Shapley value sampling over players on the patch
+ * grid (patch tokens, blocks of them, atlas regions): the device steps around the forward.  No call allocates, synchronises or reads
+ * anything back; every argument is checked first (NV_ERR_ARG).  No atomics: every output cell is owned by one thread and two runs give
+ * the same bits.  Every double operation is rounded on its own (no FMA contraction).
+ * nv_mask_patches_rows: nv_mask_patches (the same kernel body, token rule, baseline forms and 16-byte stores at any alignment) with
+ *   labels int32 [Rows, N] and jobs int32 [J, 4] of rows (b, row, lo, hi):
+ *     out[j, i0, i1, i2] = lo <= labels[row, t] < hi ? baseline : x[b, i0, i1, i2]
+ *   A job with b outside [0, B) or row outside [0, Rows) reads nothing and writes nothing; lo >= hi copies x[b].  Consecutive jobs of
+ *   one volume and one row share one read of x and of the labels.
+ * nv_shapley_ranks: writes ranks int32 [U R, B, F] (DEVICE), 2 <= F <= 4096 players, R = 1 or 2, U <= 65535 units per call.  For unit u,
+ *   sample b, player f:
+ *     seed_s = nv_hash64(seed, 0x53484150)     (a domain of its own: no dropout, augmentation, mix, affine, MIM or drop-path draw is reused)
+ *     h      = nv_hash64(seed_s, (((first_unit + u) 2^32 + b) 4096 + f) mod 2^64)
+ *     key_f  = (h >> 40) 2^-24 (exact in fp32);  rank_f = #{ j : key_j > key_f or (key_j == key_f and j < f) }   (nv_token_ranks' rule)
+ *   Row r = 0 of unit u (ranks[(u R + r), b, :]) holds rank, a permutation of 0 .. F - 1; with R = 2, row r = 1 holds the antithetic
+ *   permutation F - 1 - rank.  first_unit + U <= 2^32.  One workgroup per (unit, sample), the keys ranked in LDS.
+ * nv_shapley_labels: ranks int32 [Rows, F], features int32 [B, N] -> labels int32 [Rows, N]; row q belongs to volume q mod B:
+ *     labels[q, t] = ranks[q, features[q mod B, t]];   a feature id outside [0, F) (the convention is -1) gives label F: such a patch
+ *   is no player, and a job (b, row, k, F) leaves it as in x.
+ * nv_shapley_accumulate: interior fp32 [U R, B, F - 1], ends fp32 [B, 2], ranks int32 [U R, B, F] -> values fp32 [B, F], std_err fp32
+ *   [B, F], delta fp32 [B], sums double [B, F, 2].  The score row of permutation q = u R + r of volume b is s_0 = ends[b, 0] (nothing
+ *   present), s_k = interior[q, b, k - 1] for 0 < k < F (the k first-ranked players present), s_F = ends[b, 1].  Player f of rank rho has
+ *   the marginal m = double(s_{rho+1}) - double(s_rho); a unit's value v_u is m (R = 1) or (m_0 + m_1) / 2 (R = 2).  In unit order,
+ *     sums[b, f, 0] = sum_u v_u,  sums[b, f, 1] = sum_u v_u v_u;   values = fp32(sum / U);
+ *     std_err = fp32(sqrt(max((sumsq - sum sum / U) / (U - 1), 0) / U)),  NaN for U = 1;
+ *     delta[b] = fp32((sum_f sums[b, f, 0]) / U - (double(s_F) - double(s_0))),  the sum in player order: the efficiency residual.
+ *   A rank outside [0, F) is clamped (no read outside the row).  One thread owns (b, f).
+ * nv_shapley_token_maps: values fp32 [B, F], features int32 [B, N] (F, N <= 4096) -> maps fp32 [B, N]: a patch of player f gets
+ *   values[b, f] / (number of patches of f in volume b) (one fp32 division), a patch of no player 0: the map sums to the values. */
+int nv_mask_patches_rows(const float* x, int B, const int* size3, const int* patch3, const int* labels, int Rows, const int* jobs, int J,
+                         float value, const float* base, long base_stride, float* out, void* stream);
+int nv_shapley_ranks(unsigned long seed, unsigned long first_unit, int U, int R, int B, int F, int* ranks, void* stream);
+int nv_shapley_labels(const int* ranks, const int* features, int Rows, int B, int F, int N, int* labels, void* stream);
+int nv_shapley_accumulate(const float* interior, const float* ends, const int* ranks, int U, int R, int B, int F, float* values, float* std_err,
+                          float* delta, double* sums, void* stream);
+int nv_shapley_token_maps(const float* values, const int* features, int B, int F, int N, float* maps, void* stream);
+
 /* (added within revision 8 - new symbols only; a caller finds out by symbol lookup) path attribution: the device steps around the
  * forward and the data-only backward of integrated gradients.  No call allocates or synchronises; every argument is checked first
  * (NV_ERR_ARG).  `jobs` is a DEVICE array int32 [J, 2] of rows (b, k): b the source volume of the job, k its step on the path.

@@ -39,6 +39,42 @@ def _grid_geometry(config, threshold=None):
     return size, size // config['TRAINING_VIT_PATCH_SIZE'], config['GRADCAM_THRESHOLD'] if threshold is None else threshold
 
 
+def window_block_labels(cells: int, window: int, device=None) -> torch.Tensor:
+    """int64 [G^3]: the window^3-patch block of every patch token t = c2 G^2 + c0 G + c1, (c2 // w) Gb^2 + (c0 // w) Gb + c1 // w with
+    Gb = ceil(G / w) - the blocks tile the patch grid from its origin, the last block of an axis smaller when w does not divide G
+    (occlusion_sensitivity's blocks, shapley_values' default players)."""
+    G, w = cells, window
+    Gb = -(-G // w)
+    t = torch.arange(G ** 3, device=device, dtype=torch.int64)
+    c2, c0, c1 = t // (G * G), (t // G) % G, t % G
+    return (c2 // w) * Gb * Gb + (c0 // w) * Gb + c1 // w
+
+
+def atlas_to_patch_features(atlas: torch.Tensor, patch: int, background: int = 0):
+    """An integer atlas [S, S, S] in the layout of a volume x[b] ([H, W, D]) -> (features int32 [N], labels int64 [F]): the players of
+    shapley_values(features=...) on the patch grid, in token order.  Every patch takes the label most of its voxels carry (ties to the
+    lower label); a patch whose label is `background` gets -1 (no player); the other labels are renumbered densely in ascending order,
+    labels[f] being the atlas label of player f.  A one-off table builder in torch, on the atlas' device."""
+    if atlas.dim() != 3 or atlas.is_floating_point() or atlas.dtype == torch.bool:
+        raise ValueError(f"atlas_to_patch_features: atlas must be an integer tensor [S, S, S], got {atlas.dtype} {tuple(atlas.shape)}")
+    p = int(patch)
+    if p < 1 or any(s % p for s in atlas.shape):
+        raise ValueError(f"atlas_to_patch_features: atlas {tuple(atlas.shape)} is not a whole number of {p}^3 patches")
+    G0, G1, G2 = (s // p for s in atlas.shape)
+    known, index = torch.unique(atlas.long(), return_inverse=True)                       # ascending
+    rows = index.view(G0, p, G1, p, G2, p).permute(4, 0, 2, 1, 3, 5).reshape(G0 * G1 * G2, p ** 3)      # token order: axis 2 slowest, then 0, then 1
+    counts = torch.zeros((rows.shape[0], known.numel()), dtype=torch.int64, device=atlas.device)
+    counts.scatter_add_(1, rows, torch.ones_like(rows))
+    majority = known[counts.argmax(dim=1)]                                               # the first maximum: the lower label
+    players = torch.unique(majority[majority != background])
+    features = torch.searchsorted(players, majority)                                     # (a background label lands anywhere: replaced below)
+    features = torch.where(majority == background, torch.full_like(features, -1), features)
+    return features.to(torch.int32).contiguous(), players
+
+
+SHAPLEY_MAX_LABEL_CELLS = 2 ** 26
+
+
 PATH_METHODS = ("gausslegendre", "riemann_middle", "riemann_trapezoid")
 
 
@@ -254,7 +290,9 @@ class NeuroEncoder(nn.Module):
         get_attention_map / get_attention_rollout / get_attention_relevance on the whole batch, in the module's current mode; "occlusion" is
         relu(occlusion_sensitivity(x, target)) - G^3 + 1 forwards per volume, no gradient and no assumption about attention;
         "integrated_gradients" is relu of the token_maps of integrated_gradients(x, target) with its defaults (zero baseline, 50
-        Gauss-Legendre points, the class logit: 50 forward + data-only backward passes per volume, no p.grad touched):
+        Gauss-Legendre points, the class logit: 50 forward + data-only backward passes per volume, no p.grad touched); "shapley" is relu of
+        the token_maps of shapley_values(x, target) with its defaults (2^3-patch blocks, 16 antithetic permutations: 2 + 16 (F - 1) forwards
+        per volume):
           gradcam    one forward, logits.backward(one-hot) with one row per volume (the logits are per volume: volumes do not couple),
                      the per-volume reduction nv_gradcam_reduce_per_volume.  As get_attention_map it runs the model's backward pass:
                      a trainable model accumulates p.grad; a frozen one runs the data-only backward and touches none;
@@ -267,8 +305,9 @@ class NeuroEncoder(nn.Module):
         from . import ops
         if self.config['TRAINING_DIM'] != 3:
             raise NotImplementedError("attribution_volumes: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
-        if method not in ("gradcam", "rollout", "relevance", "occlusion", "integrated_gradients"):
-            raise ValueError(f"attribution_volumes: method must be 'gradcam', 'rollout', 'relevance', 'occlusion' or 'integrated_gradients', got {method!r}")
+        if method not in ("gradcam", "rollout", "relevance", "occlusion", "integrated_gradients", "shapley"):
+            raise ValueError("attribution_volumes: method must be 'gradcam', 'rollout', 'relevance', 'occlusion', 'integrated_gradients' or 'shapley', "
+                             f"got {method!r}")
         vit = self.volume_encoder.vit3d
         normalize = True
         if method == "occlusion":
@@ -278,6 +317,10 @@ class NeuroEncoder(nn.Module):
         elif method == "integrated_gradients":
             # the signed patch sums of integrated gradients (zero baseline, 50 Gauss-Legendre points, the class logit)
             result = self.integrated_gradients(x, target=target)
+            token_maps, class_idx = torch.relu(result["token_maps"]), result["class_idx"]
+        elif method == "shapley":
+            # the signed Shapley values of the 2^3-patch blocks (16 antithetic permutations, zero baseline, probability score), spread over the patches
+            result = self.shapley_values(x, target=target)
             token_maps, class_idx = torch.relu(result["token_maps"]), result["class_idx"]
         elif method == "gradcam":
             volume = x.to(self.device)
@@ -324,11 +367,13 @@ class NeuroEncoder(nn.Module):
         return S, S // self.config['TRAINING_VIT_PATCH_SIZE'], int(chunk)
 
     def _perturbed_logits(self, volume, labels, jobs, baseline, chunk):
-        """logits [J, C] of the masked copies (ops.mask_patches) of `volume`: consecutive slices of `chunk` jobs, each masked into one
-        reused buffer and forwarded under no_grad in the module's current mode and precision"""
+        """logits [J, C] of the masked copies of `volume`: consecutive slices of `chunk` jobs, each masked into one reused buffer and
+        forwarded under no_grad in the module's current mode and precision.  jobs [J, 3] = (b, lo, hi) with labels [B, N]
+        (ops.mask_patches), or jobs [J, 4] = (b, row, lo, hi) with labels [Rows, N] (ops.mask_patches_rows)"""
         from . import ops
         patch = self.config['TRAINING_VIT_PATCH_SIZE']
         J = jobs.shape[0]
+        mask = ops.mask_patches_rows if jobs.shape[1] == 4 else ops.mask_patches
         chunk = min(chunk, J)
         if torch.is_tensor(baseline):
             baseline = baseline.to(device=volume.device, dtype=torch.float32).contiguous()
@@ -337,7 +382,7 @@ class NeuroEncoder(nn.Module):
         with torch.no_grad():
             for first in range(0, J, chunk):
                 count = min(chunk, J - first)
-                ops.mask_patches(volume, labels, jobs[first:first + count], patch, baseline=baseline, out=masked[:count])
+                mask(volume, labels, jobs[first:first + count], patch, baseline=baseline, out=masked[:count])
                 part = self.forward(masked[:count])
                 if logits is None:
                     logits = torch.empty((J, part.shape[1]), dtype=torch.float32, device=volume.device)
@@ -414,9 +459,7 @@ class NeuroEncoder(nn.Module):
         device = volume.device
 
         def build():
-            t = torch.arange(N, device=device, dtype=torch.int64)
-            c2, c0, c1 = t // (G * G), (t // G) % G, t % G
-            block = (c2 // w) * Gb * Gb + (c0 // w) * Gb + c1 // w
+            block = window_block_labels(G, w, device)
             b = torch.arange(B, device=device, dtype=torch.int64)
             j = torch.arange(NB, device=device, dtype=torch.int64).repeat(B)
             jobs = torch.stack([b.repeat_interleave(NB), j, j + 1], 1).to(torch.int32).contiguous()
@@ -431,6 +474,116 @@ class NeuroEncoder(nn.Module):
         logits = self._perturbed_logits(volume, labels, jobs, baseline, chunk)
         scores = ops.class_scores(logits, jobs, class_idx, kind=score).view(B, NB)
         return ops.occlusion_gather(reference, scores, labels), class_idx
+
+    # ---- Shapley value sampling, on the device (csrc/shapley.hip): the one attribution that is efficient and order-free, over patches,
+    # blocks of patches or atlas regions
+    def shapley_values(self, x, target=None, permutations=16, window=2, features=None, antithetic=True, baseline=0.0, score="prob", seed=0,
+                       permutation_offset=0, ranks=None, chunk=None, return_scores=False):
+        """Shapley values of players on the patch grid for a batch x [B, H, W, D], by permutation sampling (Castro et al.; captum's
+        ShapleyValueSampling): the mean over random orders of the change in the class score when a player joins the players before it.
+        The values of a volume sum to score(x) - score(everything at the baseline) (efficiency), whatever the order of the players.
+          players    features None: the window^3-patch blocks of occlusion_sensitivity (window_block_labels; window 1 = one player per
+                     patch).  Otherwise an int tensor [N] or [B, N] of player ids in token order, -1 = no player (such a patch stays as in x
+                     in every copy), F = max + 1 (with ranks: its last dimension): an atlas on the patch grid (atlas_to_patch_features).
+                     F is read on the host: a CPU tensor costs nothing, a device tensor one read-back.  2 <= F <= 4096;
+          draw       nv_shapley_ranks (the rule is in the header): antithetic needs an even `permutations` P and draws U = P / 2 units of a
+                     permutation and its reverse (R = 2); otherwise U = P, R = 1.  The units drawn are permutation_offset ..
+                     permutation_offset + U - 1, so two calls can draw disjoint permutations.  ranks int [P, F] or [P, B, F] (rank of every
+                     player, a permutation per row) replaces the draw: R = 1, antithetic is ignored, and every row is checked to be a
+                     permutation in torch - the one host synchronisation of that path;
+          jobs       (b, row, lo, hi) for ops.mask_patches_rows over the labels ops.shapley_labels(ranks, features) [P B, N] (row q B + b:
+                     permutation q of volume b; label = the rank of the patch's player, F for no player), in one global order: first the
+                     ends, volume-major, (b, b, 0, F) - every player at the baseline - then (b, b, F, F) - x itself; then for permutation
+                     q = 0 .. P - 1, volume b, k = 1 .. F - 1: (b, q B + b, k, F) - the k first-ranked players present.  Consecutive slices
+                     of `chunk` jobs of this list are masked and forwarded as perturbation_curves does;
+          values     ops.shapley_accumulate: the marginal of player f of rank rho in a permutation is s_{rho+1} - s_rho; a unit's value is
+                     the mean of its R marginals; values = the mean over the units, stderr its standard error (NaN for U = 1).
+        target / baseline / score / chunk: as perturbation_curves.  Costs B (2 + P (F - 1)) forwards.  More than 2^26 label cells
+        (P B N) are refused: split the permutations over calls with permutation_offset and average.
+        Returns a dict of device tensors: values / stderr [B, F], token_maps [B, N] (a player's value spread evenly over its patches:
+        what token_maps_to_volumes and perturbation_curves take), class_idx [B], full_score / empty_score [B], delta [B] (sum of the values
+        - (full - empty), the efficiency residual: rounding only), feature_labels int32 [B, N], ranks int32 [P, B, F]; with return_scores
+        also interior [P, B, F - 1] and ends [B, 2] (empty, full).  Without ranks= nothing synchronises with the host inside the call."""
+        from . import ops
+        what = "shapley_values"
+        S, G, chunk = self._perturbation_inputs(what, x, baseline, score, chunk)
+        N, B = G ** 3, x.shape[0]
+        if ranks is not None:
+            if not torch.is_tensor(ranks) or ranks.is_floating_point() or ranks.dim() not in (2, 3) or (ranks.dim() == 3 and ranks.shape[1] != B):
+                raise ValueError(f"{what}: ranks must be an int tensor [P, F] or [P, {B}, F], got {tuple(ranks.shape) if torch.is_tensor(ranks) else ranks!r}")
+            P, F_given = ranks.shape[0], ranks.shape[-1]
+            U, R = P, 1
+        else:
+            if isinstance(permutations, bool) or int(permutations) != permutations or permutations < 1:
+                raise ValueError(f"{what}: permutations must be a positive integer, got {permutations!r}")
+            P, F_given = int(permutations), None
+            if antithetic and P % 2:
+                raise ValueError(f"{what}: antithetic sampling draws pairs of permutations and needs an even number, got permutations = {P}")
+            U, R = (P // 2, 2) if antithetic else (P, 1)
+            if int(permutation_offset) != permutation_offset or permutation_offset < 0 or permutation_offset + U > 2 ** 32:
+                raise ValueError(f"{what}: permutation_offset must be an integer in [0, 2^32 - {U}], got {permutation_offset!r}")
+        if features is None:
+            if int(window) != window or window < 1:
+                raise ValueError(f"{what}: window must be a positive integer, got {window!r}")
+            w = int(window)
+            F = (-(-G // w)) ** 3
+            feature_key = ("blocks", w)
+        else:
+            if not torch.is_tensor(features) or features.is_floating_point() or tuple(features.shape) not in ((N,), (B, N)):
+                raise ValueError(f"{what}: features must be an int tensor [{N}] or [{B}, {N}] of player ids, got "
+                                 f"{tuple(features.shape) if torch.is_tensor(features) else features!r}")
+            top = int(features.max())
+            F = top + 1 if F_given is None else F_given
+            if top >= F:
+                raise ValueError(f"{what}: features name player {top}, ranks has {F} players")
+            feature_key = None
+        if F_given is not None and F_given != F:
+            raise ValueError(f"{what}: ranks has {F_given} players, the window {window} gives {F}")
+        if F < 2 or F > ops.SHAPLEY_MAX_PLAYERS:
+            raise ValueError(f"{what}: {F} players, needs 2 <= F <= {ops.SHAPLEY_MAX_PLAYERS}")
+        if P * B * N > SHAPLEY_MAX_LABEL_CELLS:
+            raise ValueError(f"{what}: {P} permutations x {B} volumes x {N} patches = {P * B * N} label cells, more than 2^26: split the permutations "
+                             "over several calls with permutation_offset and average the values")
+        volume = x.to(device=self.device, dtype=torch.float32).contiguous()
+        device = volume.device
+
+        if feature_key is None:
+            feature_labels = features.to(device=device, dtype=torch.int32).expand(B, N).contiguous()
+        else:
+            feature_labels = cached_table(self, "_perturbation_tables", ("shapley players", str(device), B, G) + feature_key,
+                                          lambda: window_block_labels(G, w, device).to(torch.int32).repeat(B, 1).contiguous())
+
+        def build():
+            b = torch.arange(B, device=device, dtype=torch.int64)
+            full = torch.full_like(b, F)
+            ends = torch.stack([torch.stack([b, b, torch.zeros_like(b), full], 1), torch.stack([b, b, full, full], 1)], 1).view(2 * B, 4)
+            q = torch.arange(P, device=device, dtype=torch.int64).view(P, 1, 1).expand(P, B, F - 1)
+            bb = b.view(1, B, 1).expand(P, B, F - 1)
+            k = torch.arange(1, F, device=device, dtype=torch.int64).view(1, 1, F - 1).expand(P, B, F - 1)
+            inner = torch.stack([bb, q * B + bb, k, torch.full_like(k, F)], 3).view(P * B * (F - 1), 4)
+            jobs = torch.cat([ends, inner]).to(torch.int32).contiguous()
+            return jobs, jobs[:, [0, 2, 3]].contiguous()                       # the companion (b, lo, hi) table of nv_class_scores
+        jobs, score_jobs = cached_table(self, "_perturbation_tables", ("shapley", str(device), B, F, P), build)
+
+        if ranks is None:
+            order = ops.shapley_ranks(U, R, B, F, seed=seed, first_unit=int(permutation_offset), device=device)
+        else:
+            order = ranks.to(device=device, dtype=torch.int32)
+            order = (order if order.dim() == 3 else order[:, None, :].expand(P, B, F)).contiguous()
+            if not bool((torch.sort(order, dim=2).values == torch.arange(F, device=device, dtype=torch.int32)).all()):      # (the host synchronisation)
+                raise ValueError(f"{what}: every row of ranks must be a permutation of 0 .. {F - 1}")
+        with torch.no_grad():
+            class_idx = target_classes(target, self.forward(volume))
+        labels = ops.shapley_labels(order, feature_labels)
+        logits = self._perturbed_logits(volume, labels, jobs, baseline, chunk)
+        scores = ops.class_scores(logits, score_jobs, class_idx, kind=score)
+        ends, interior = scores[:2 * B].view(B, 2), scores[2 * B:].view(P, B, F - 1)
+        values, stderr, delta, _ = ops.shapley_accumulate(interior, ends, order, R=R)
+        out = {"values": values, "stderr": stderr, "token_maps": ops.shapley_token_maps(values, feature_labels), "class_idx": class_idx,
+               "full_score": ends[:, 1], "empty_score": ends[:, 0], "delta": delta, "feature_labels": feature_labels, "ranks": order}
+        if return_scores:
+            out.update(interior=interior, ends=ends)
+        return out
 
     # ---- path attribution, on the device (csrc/path_attr.hip): integrated gradients, the map the reference ships captum heat maps of
     def integrated_gradients(self, x, target=None, baseline=0.0, steps=50, method="gausslegendre", score="logit", chunk=None):

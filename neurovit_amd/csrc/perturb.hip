@@ -5,6 +5,8 @@
 //   nv_token_ranks       [B, N] maps -> [B, N] ranks (descending, ties to the lower token index): one workgroup per volume, keys in LDS
 //   nv_mask_patches      x [B, S0, S1, S2] + labels [B, N] + jobs [J, 3] -> out [J, S0, S1, S2]: a pure select between x and a baseline,
 //                        streamed with 16-byte stores; the volume's labels and the token index of every row / column sit in LDS
+//   nv_mask_patches_rows the same kernel body over jobs [J, 4] = (b, row, lo, hi) whose label row is named by the job (labels [Rows, N]):
+//                        many labellings of one volume in one call (NeuroEncoder.shapley_values)
 //   nv_class_scores      logits [J, C] -> scores [J] (the logit, or the softmax probability) of the class of each job's source volume
 //   nv_curve_auc         trapezoid area of [B, K] curves on the uniform grid k / (K - 1), summed in double
 //   nv_occlusion_gather  maps[b, t] = ref[b] - scores[b, labels[b, t]]
@@ -58,19 +60,22 @@ int g_mask_group = 4;
 // per group (flat plane offset -> row).  Groups of four follow the alignment of `out` (split_span);
 // x and the baseline are read as 16-byte vectors when their plane has the same alignment as the output's (uniform per run), voxel by
 // voxel otherwise.  Everything moves as 32-bit patterns: no arithmetic touches a voxel.
+// JC = 3: a job is (b, lo, hi) and its label row is b (nv_mask_patches).  JC = 4: a job is (b, row, lo, hi) with its label row one of
+// `rows` (nv_mask_patches_rows); a run then also shares the row, and a row outside [0, rows) skips the job as a volume outside [0, B) does.
+template <int JC>
 __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned* __restrict__ x, int B, int S0, int S1, int S2, int p0, int p1, int p2,
                                                                   const int* __restrict__ labels, const int* __restrict__ jobs, int J, int group,
                                                                   unsigned value, const unsigned* __restrict__ base, long base_stride,
-                                                                  unsigned* __restrict__ out) {
+                                                                  unsigned* __restrict__ out, int rows) {
   extern __shared__ int mk_smem[];
   const int G0 = S0 / p0, G1 = S1 / p1, G2 = S2 / p2, N = G0 * G1 * G2;
   int* lab = mk_smem;                                      // [N]
   int* row_tok = lab + N;                                  // [S1]: i1 / p1
   int* col_tok = row_tok + S1;                             // [S2]: (i2 / p2) G0 G1
-  __shared__ int s_job[3 * MK_MAX_GROUP];
+  __shared__ int s_job[JC * MK_MAX_GROUP];
   const int tid = threadIdx.x, i0 = blockIdx.x;
   const int j_first = blockIdx.y * group, j_end = min(j_first + group, J);
-  for (int i = tid; i < 3 * (j_end - j_first); i += MK_THREADS) s_job[i] = jobs[3L * j_first + i];
+  for (int i = tid; i < JC * (j_end - j_first); i += MK_THREADS) s_job[i] = jobs[(long)JC * j_first + i];
   for (int i = tid; i < S1; i += MK_THREADS) row_tok[i] = i / p1;
   for (int i = tid; i < S2; i += MK_THREADS) col_tok[i] = (i / p2) * G0 * G1;
   __syncthreads();
@@ -80,18 +85,19 @@ __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned
 
   const bool same_alignment = (vol & 3) == 0;              // else consecutive jobs' planes differ in alignment: runs of one job
   const int n_jobs = j_end - j_first;
-  int r0 = 0, loaded_b = -1;
+  int r0 = 0, loaded_row = -1;
   // (path_points_kernel of path_attr.hip walks the same runs over its pre-validated two-column jobs)
   while (r0 < n_jobs) {                                    // (every condition below is uniform over the workgroup)
-    const int b = s_job[3 * r0];
+    const int b = s_job[JC * r0];
+    const int row = JC == 4 ? s_job[JC * r0 + 1] : b;
     int r1 = r0 + 1;
-    while (same_alignment && r1 < n_jobs && s_job[3 * r1] == b) ++r1;
-    if (b < 0 || b >= B) { r0 = r1; continue; }            // such a job reads nothing and writes nothing
-    if (b != loaded_b) {
+    while (same_alignment && r1 < n_jobs && s_job[JC * r1] == b && (JC == 3 || s_job[JC * r1 + 1] == row)) ++r1;
+    if (b < 0 || b >= B || (JC == 4 && (row < 0 || row >= rows))) { r0 = r1; continue; }      // such a job reads nothing and writes nothing
+    if (row != loaded_row) {
       __syncthreads();                                     // the previous run has finished with `lab`
-      for (int i = tid; i < N; i += MK_THREADS) lab[i] = labels[(long)b * N + i];
+      for (int i = tid; i < N; i += MK_THREADS) lab[i] = labels[(long)row * N + i];
       __syncthreads();
-      loaded_b = b;
+      loaded_row = row;
     }
     const unsigned* xp = x + (long)b * vol + (long)i0 * P;
     const unsigned* bp = base ? base + (long)b * base_stride + (long)i0 * P : nullptr;
@@ -102,7 +108,7 @@ __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned
       const int y = e / S2, z = e - y * S2;
       const int l = lab[plane_tok + row_tok[y] + col_tok[z]];
       const unsigned xv = xp[e], bv = bp ? bp[e] : value;
-      for (int r = r0; r < r1; ++r) o[(long)(r - r0) * vol + e] = (l >= s_job[3 * r + 1] && l < s_job[3 * r + 2]) ? bv : xv;
+      for (int r = r0; r < r1; ++r) o[(long)(r - r0) * vol + e] = (l >= s_job[JC * r + JC - 2] && l < s_job[JC * r + JC - 1]) ? bv : xv;
     };
     for (int e = tid; e < s.head; e += MK_THREADS) single(e);
     for (int e = s.tail + tid; e < P; e += MK_THREADS) single(e);
@@ -120,7 +126,7 @@ __global__ __launch_bounds__(MK_THREADS) void mask_patches_kernel(const unsigned
         if (++z == S2 && k < 3) { z = 0; ++y; rt = plane_tok + row_tok[y]; }     // (a group may straddle rows; y < S1 because e + k < P)
       }
       for (int r = r0; r < r1; ++r) {
-        const int lo = s_job[3 * r + 1], hi = s_job[3 * r + 2];
+        const int lo = s_job[JC * r + JC - 2], hi = s_job[JC * r + JC - 1];
         u32x4 v;
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] = (l[k] >= lo && l[k] < hi) ? bv[k] : xv[k];
@@ -196,30 +202,43 @@ extern "C" int nv_mask_patches_set_group(int group) {
   return NV_OK;
 }
 
-extern "C" int nv_mask_patches(const float* x, int B, const int* size3, const int* patch3, const int* labels, const int* jobs, int J, float value,
-                               const float* base, long base_stride, float* out, void* stream) {
-  NV_CHECK_ARG(x && size3 && patch3 && labels && jobs && out && B > 0 && J > 0, "nv_mask_patches: bad arguments (null pointer, or B / J not positive)");
+// the checks and the launch of nv_mask_patches (JC = 3, rows unused) and nv_mask_patches_rows (JC = 4)
+template <int JC>
+static int mask_patches_launch(const char* name, const float* x, int B, const int* size3, const int* patch3, const int* labels, int rows, const int* jobs,
+                               int J, float value, const float* base, long base_stride, float* out, void* stream) {
+  NV_CHECK_ARG(x && size3 && patch3 && labels && jobs && out && B > 0 && J > 0 && rows > 0, "%s: bad arguments (null pointer, or B / J%s not positive)", name,
+               JC == 4 ? " / Rows" : "");
   const int S0 = size3[0], S1 = size3[1], S2 = size3[2], p0 = patch3[0], p1 = patch3[1], p2 = patch3[2];
-  NV_CHECK_ARG(S0 > 0 && S1 > 0 && S2 > 0 && p0 > 0 && p1 > 0 && p2 > 0, "nv_mask_patches: volume and patch extents must be positive");
-  NV_CHECK_ARG(S0 % p0 == 0 && S1 % p1 == 0 && S2 % p2 == 0, "nv_mask_patches: volume %d x %d x %d is not a whole number of %d x %d x %d patches", S0, S1, S2,
+  NV_CHECK_ARG(S0 > 0 && S1 > 0 && S2 > 0 && p0 > 0 && p1 > 0 && p2 > 0, "%s: volume and patch extents must be positive", name);
+  NV_CHECK_ARG(S0 % p0 == 0 && S1 % p1 == 0 && S2 % p2 == 0, "%s: volume %d x %d x %d is not a whole number of %d x %d x %d patches", name, S0, S1, S2,
                p0, p1, p2);
   const long N = (long)(S0 / p0) * (S1 / p1) * (S2 / p2);
-  NV_CHECK_ARG(N <= MK_MAX_CELLS, "nv_mask_patches: %ld patches, the kernel takes at most %d (16^3)", N, MK_MAX_CELLS);
+  NV_CHECK_ARG(N <= MK_MAX_CELLS, "%s: %ld patches, the kernel takes at most %d (16^3)", name, N, MK_MAX_CELLS);
   const long lds = (N + S1 + S2) * 4;
-  NV_CHECK_ARG(lds <= 65536 - 256 && (long)S1 * S2 < (1L << 31),
-               "nv_mask_patches: extents %d x %d x %d beyond the kernel's tables (patches + S1 + S2 <= 16320)", S0, S1, S2);
+  NV_CHECK_ARG(lds <= 65536 - 256 && (long)S1 * S2 < (1L << 31), "%s: extents %d x %d x %d beyond the kernel's tables (patches + S1 + S2 <= 16320)", name, S0,
+               S1, S2);
   const int group = g_mask_group;
   const long job_groups = ((long)J + group - 1) / group;
-  NV_CHECK_ARG(job_groups <= 65535, "nv_mask_patches: %d jobs, at most %d in one call", J, 65535 * group);
+  NV_CHECK_ARG(job_groups <= 65535, "%s: %d jobs, at most %d in one call", name, J, 65535 * group);
   NV_CHECK_ARG(nv_aligned16(out) && nv_aligned(x, 4) && nv_aligned(base, 4) && nv_aligned(labels, 4) && nv_aligned(jobs, 4),
-               "nv_mask_patches: out 16-byte aligned, every other buffer 4-byte aligned");
-  NV_CHECK_ARG(base_stride == 0 || base_stride >= (long)S0 * S1 * S2, "nv_mask_patches: baseline stride %ld is neither 0 nor at least one volume", base_stride);
+               "%s: out 16-byte aligned, every other buffer 4-byte aligned", name);
+  NV_CHECK_ARG(base_stride == 0 || base_stride >= (long)S0 * S1 * S2, "%s: baseline stride %ld is neither 0 nor at least one volume", name, base_stride);
   union { float f; unsigned u; } vbits;
   vbits.f = value;
-  hipLaunchKernelGGL(mask_patches_kernel, dim3(S0, (unsigned)job_groups), dim3(MK_THREADS), (size_t)lds, (hipStream_t)stream, (const unsigned*)x, B, S0, S1, S2,
-                     p0, p1, p2, labels, jobs, J, group, vbits.u, (const unsigned*)base, base_stride, (unsigned*)out);
-  NV_CHECK_LAUNCH("nv_mask_patches");
+  hipLaunchKernelGGL(mask_patches_kernel<JC>, dim3(S0, (unsigned)job_groups), dim3(MK_THREADS), (size_t)lds, (hipStream_t)stream, (const unsigned*)x, B, S0, S1,
+                     S2, p0, p1, p2, labels, jobs, J, group, vbits.u, (const unsigned*)base, base_stride, (unsigned*)out, rows);
+  NV_CHECK_LAUNCH(name);
   return NV_OK;
+}
+
+extern "C" int nv_mask_patches(const float* x, int B, const int* size3, const int* patch3, const int* labels, const int* jobs, int J, float value,
+                               const float* base, long base_stride, float* out, void* stream) {
+  return mask_patches_launch<3>("nv_mask_patches", x, B, size3, patch3, labels, B, jobs, J, value, base, base_stride, out, stream);
+}
+
+extern "C" int nv_mask_patches_rows(const float* x, int B, const int* size3, const int* patch3, const int* labels, int Rows, const int* jobs, int J, float value,
+                                    const float* base, long base_stride, float* out, void* stream) {
+  return mask_patches_launch<4>("nv_mask_patches_rows", x, B, size3, patch3, labels, Rows, jobs, J, value, base, base_stride, out, stream);
 }
 
 extern "C" int nv_class_scores(const float* logits, int J, int C, const int* jobs, const long* cls, int B, int kind, float* scores, void* stream) {

@@ -922,6 +922,94 @@ def occlusion_gather(ref: torch.Tensor, scores: torch.Tensor, labels: torch.Tens
     return maps
 
 
+SHAPLEY_MAX_PLAYERS = 4096
+
+
+def mask_patches_rows(x: torch.Tensor, labels: torch.Tensor, jobs: torch.Tensor, patch, baseline=0.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """mask_patches with labels int32 [Rows, N] and jobs int32 [J, 4] of rows (b, row, lo, hi): copy j is x[b] with every patch whose label
+    in row `row` lies in [lo, hi) replaced by the baseline - many labellings of one volume in one call.  A job with b outside [0, B) or row
+    outside [0, Rows) leaves its slot of `out` as it was.  nv_mask_patches_rows (the kernel body of nv_mask_patches), one launch."""
+    _need_cuda(x, labels, jobs, out, baseline if torch.is_tensor(baseline) else None)
+    patch = _triple(patch, "patch")
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()
+    B, size = x.shape[0], tuple(x.shape[1:])
+    if any(s % p for s, p in zip(size, patch)):
+        raise ValueError(f"neurovit_amd: mask_patches_rows: volume {size} is not a whole number of {patch} patches")
+    N = (size[0] // patch[0]) * (size[1] // patch[1]) * (size[2] // patch[2])
+    assert labels.dim() == 2 and labels.shape[1] == N and labels.dtype == torch.int32 and labels.is_contiguous()
+    assert jobs.dim() == 2 and jobs.shape[1] == 4 and jobs.dtype == torch.int32 and jobs.is_contiguous()
+    J = jobs.shape[0]
+    value, base, stride = _path_baseline("mask_patches_rows", baseline, x.shape)
+    if out is None:
+        out = torch.empty((J,) + size, dtype=torch.float32, device=x.device)
+    assert out.shape == (J,) + size and out.dtype == torch.float32 and out.is_contiguous() and out.device == x.device
+    (s3, s3p), (p3, p3p) = _int3_ptr(size), _int3_ptr(patch)
+    check(lib.nv_mask_patches_rows(_p(x), B, s3p, p3p, _p(labels), labels.shape[0], _p(jobs), J, value, _p(base), stride, _p(out), _stream()),
+          "nv_mask_patches_rows")
+    return out
+
+
+def shapley_ranks(U: int, R: int, B: int, F: int, seed: int = 0, first_unit: int = 0, device="cuda", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> ranks int32 [U R, B, F] on the device: for each of the units first_unit .. first_unit + U - 1 and each sample a random permutation
+    of the F players (row u R of the unit; the draw rule is in the header, tests/shapley_ref.py restates it) and, with R = 2, its
+    antithetic permutation F - 1 - rank behind it.  nv_shapley_ranks, one launch; nothing is read back."""
+    if R not in (1, 2) or not 2 <= F <= SHAPLEY_MAX_PLAYERS or U < 1 or B < 1:
+        raise ValueError(f"neurovit_amd: shapley_ranks: needs U, B >= 1, R in (1, 2) and 2 <= F <= {SHAPLEY_MAX_PLAYERS}, got U {U}, R {R}, B {B}, F {F}")
+    if out is None:
+        out = torch.empty((U * R, B, F), dtype=torch.int32, device=device)
+    _need_cuda(out)
+    assert out.shape == (U * R, B, F) and out.dtype == torch.int32 and out.is_contiguous()
+    check(lib.nv_shapley_ranks(int(seed) & (2 ** 64 - 1), int(first_unit), U, R, B, F, _p(out), _stream()), "nv_shapley_ranks")
+    return out
+
+
+def shapley_labels(ranks: torch.Tensor, features: torch.Tensor) -> torch.Tensor:
+    """ranks int32 [Q, B, F] (or [Q B, F]: row q of volume q mod B), features int32 [B, N] of player ids (outside [0, F), by convention -1: no
+    player) -> labels int32 [Q B, N]: the rank of every patch's player in that row, F for a patch of no player.  nv_shapley_labels, one launch."""
+    _need_cuda(ranks, features)
+    assert features.dim() == 2 and features.dtype == torch.int32 and features.is_contiguous()
+    B, N = features.shape
+    assert ranks.dtype == torch.int32 and ranks.is_contiguous() and ranks.dim() in (2, 3)
+    F = ranks.shape[-1]
+    rows = ranks.numel() // F
+    assert rows % B == 0 and (ranks.dim() == 2 or ranks.shape[1] == B)
+    labels = torch.empty((rows, N), dtype=torch.int32, device=ranks.device)
+    check(lib.nv_shapley_labels(_p(ranks), _p(features), rows, B, F, N, _p(labels), _stream()), "nv_shapley_labels")
+    return labels
+
+
+def shapley_accumulate(interior: torch.Tensor, ends: torch.Tensor, ranks: torch.Tensor, R: int = 1):
+    """interior f32 [U R, B, F - 1] (the score with the k = 1 .. F - 1 first-ranked players of each permutation present), ends f32 [B, 2]
+    (nothing present, everything present), ranks int32 [U R, B, F] -> (values f32 [B, F], stderr f32 [B, F], delta f32 [B], sums f64
+    [B, F, 2]): the mean over the U units of every player's marginal contribution (a unit: one permutation, or the mean of an antithetic
+    pair), its standard error (NaN for U = 1), the efficiency residual sum_f value_f - (full - empty), and the double sums behind them.
+    nv_shapley_accumulate; nothing is read back."""
+    _need_cuda(interior, ends, ranks)
+    assert ranks.dim() == 3 and ranks.dtype == torch.int32 and ranks.is_contiguous() and R in (1, 2)
+    Q, B, F = ranks.shape
+    assert Q % R == 0 and F >= 2
+    assert interior.shape == (Q, B, F - 1) and interior.dtype == torch.float32 and interior.is_contiguous()
+    assert ends.shape == (B, 2) and ends.dtype == torch.float32 and ends.is_contiguous()
+    dev = ranks.device
+    values, err = torch.empty((B, F), dtype=torch.float32, device=dev), torch.empty((B, F), dtype=torch.float32, device=dev)
+    delta, sums = torch.empty(B, dtype=torch.float32, device=dev), torch.empty((B, F, 2), dtype=torch.float64, device=dev)
+    check(lib.nv_shapley_accumulate(_p(interior), _p(ends), _p(ranks), Q // R, R, B, F, _p(values), _p(err), _p(delta), _p(sums), _stream()),
+          "nv_shapley_accumulate")
+    return values, err, delta, sums
+
+
+def shapley_token_maps(values: torch.Tensor, features: torch.Tensor) -> torch.Tensor:
+    """values f32 [B, F], features int32 [B, N] -> maps f32 [B, N]: a patch of player f gets values[b, f] / (patches of f in volume b), a patch
+    of no player 0 - the map sums to the values; what token_maps_to_volumes and perturbation_curves take.  nv_shapley_token_maps, one launch."""
+    _need_cuda(values, features)
+    assert values.dim() == 2 and values.dtype == torch.float32 and values.is_contiguous()
+    B, F = values.shape
+    assert features.dim() == 2 and features.shape[0] == B and features.dtype == torch.int32 and features.is_contiguous()
+    maps = torch.empty(features.shape, dtype=torch.float32, device=values.device)
+    check(lib.nv_shapley_token_maps(_p(values), _p(features), B, F, features.shape[1], _p(maps), _stream()), "nv_shapley_token_maps")
+    return maps
+
+
 def _rows(t: torch.Tensor, rows: Optional[int] = None, V: Optional[int] = None) -> bool:
     """t is a dense fp32 [rows, V] device buffer (one row after the other)"""
     return (t.dim() == 2 and t.dtype == torch.float32 and t.stride(1) == 1 and (t.shape[0] == 1 or t.stride(0) == t.shape[1])
