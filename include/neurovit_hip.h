@@ -1177,6 +1177,66 @@ int nv_vit_train_step_sd(const nv_vit_config* cfg, int B, const float* video, co
                          const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
                          float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const nv_vit_drop_path* sd);
 
+/* (added within revision 8 - new symbols and one new struct only, nothing existing changes) a regression objective for the head: brain age,
+ * a rating, a cognitive score - K = num_classes continuous targets per volume in the place of a class index.
+ *   z  = the head's output fp32 [B, K], on the standardised scale;   y = targets fp32 [B, K] on the raw scale; a non-finite y (NaN is the
+ *   "missing" marker) makes the cell invalid, m_bk = 0;   mean_k, std_k > 0: device fp32 [K] or NULL for 0 / 1;   w_k >= 0: device fp32 [K]
+ *   per-target weight or NULL for ones.
+ *     t_bk  = (y_bk - mean_k) / std_k                         (fp32, each operation rounded)
+ *     with a mix row (partner p, label lambda l: columns 0 and 3 of nv_mix_params, the columns nv_loss_opts.mix reads)
+ *     t_bk  = l t_bk + (1 - l) t_pk,   valid iff both cells are valid
+ *     r     = z_bk - t_bk
+ *     l(r)  = r^2                                   NV_REG_MSE
+ *           = |r|                                   NV_REG_L1      (l'(0) = 0)
+ *           = 0.5 r^2 if |r| <= delta, else delta (|r| - 0.5 delta)      NV_REG_HUBER, delta > 0 (F.huber_loss)
+ *     D     = sum_bk m_bk w_k                       in double, one fixed order
+ *     loss  = sum_bk m_bk w_k l(r_bk) / D
+ *     dloss/dz_bk = m_bk w_k l'(r_bk) / D * grad_scale * scale_state[0] (when given)
+ *   D == 0 (no observed target in the batch): loss 0 and an all-zero gradient - on purpose not the cross-entropy's NaN: a batch of missing
+ *   scores is ordinary data.  A non-finite z in a valid cell propagates (a non-finite loss; a non-finite gradient in every kind), so a dynamic
+ *   loss scale sees an overflow as before.  A partner outside [0, B) gives a NaN loss; nothing is read through an unchecked index.  An invalid
+ *   cell receives exactly 0.0f.  NV_ERR_ARG before any launch: a wrong struct_size, an unknown kind, delta <= 0 for huber, K > d in the fused
+ *   head step.
+ * nv_reg_loss: the standalone loss (one launch; dpred may be NULL).  nv_head_step_reg: nv_head_step_path with (targets, nv_reg_opts) in the
+ *   place of (labels, nv_loss_opts) - two launches; every workgroup forms D itself (no atomics, no extra launch); one row body with
+ *   nv_reg_loss, so head forward + nv_reg_loss + head backward give the same bits; path (may be NULL) as in nv_head_step_path.
+ * nv_vit_train_step_reg: nv_vit_train_step_sd with targets fp32 [B, num_classes] for labels and nv_reg_opts for lo; every nv_train_hparams
+ *   form of that call (all fuse_update modes, accumulation, static and dynamic loss scale, nv_dp_plan - each rank normalises by its own D -,
+ *   the drop-path table or NULL, both head routes).  Backward and update only see dlogits.
+ * nv_reg_metrics_update / _finish: validation metrics on the raw scale with no host read per batch.  yhat = (z * std) + mean, the fp32 product
+ *   and the fp32 sum each rounded on their own; e = yhat - y over the valid cells.  state: double [K, NV_REG_METRIC_SLOTS], zeroed by the
+ *   caller: n, sum e, sum |e|, sum e^2, sum a, sum p, sum a^2, sum p^2, sum a p with a = y - mean, p = yhat - mean (in double).  One
+ *   workgroup per target walks the rows in one fixed order: no atomics, the bits reproduce.  finish writes out fp32 [K, 6]: n, MAE, RMSE, bias
+ *   (mean e), Pearson r, R^2 = 1 - sum e^2 / sum (y - ybar)^2.  r / R^2 are NaN for n < 2 or zero variance (a sum of squares about the mean
+ *   not above 1e-12 of the raw one: the rounding of the double sums); MAE /
+ *   RMSE / bias are NaN for n = 0. */
+#define NV_REG_MSE 0
+#define NV_REG_L1 1
+#define NV_REG_HUBER 2
+#define NV_REG_METRIC_SLOTS 9
+typedef struct nv_reg_opts {
+  int struct_size;              /* sizeof(nv_reg_opts): checked */
+  int kind;                     /* NV_REG_MSE / NV_REG_L1 / NV_REG_HUBER */
+  float delta;                  /* huber's threshold (> 0); ignored by the other kinds */
+  const float* mean;            /* device fp32 [K] or NULL (0) */
+  const float* std;             /* device fp32 [K], > 0, or NULL (1) */
+  const float* weight;          /* device fp32 [K], >= 0, or NULL (ones) */
+  const int* mix;               /* device int32 [B, NV_MIX_COLS] rows of nv_mix_params or NULL: partner (column 0) and label lambda (column 3) are read */
+} nv_reg_opts;
+int nv_reg_loss(const float* pred, const float* target, int B, int K, float grad_scale, const float* scale_state, const nv_reg_opts* opts,
+                float* loss, float* dpred, void* stream);
+int nv_head_step_reg(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                     const float* bias, int C, const float* targets, float grad_scale, const float* scale_state, const nv_reg_opts* opts,
+                     float* xh, float* stats, float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16,
+                     float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                     unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows);
+int nv_vit_train_step_reg(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                          float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                          const float* targets, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_reg_opts* ro,
+                          float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const nv_vit_drop_path* sd);
+int nv_reg_metrics_update(const float* pred, const float* target, int B, int K, const float* mean, const float* std, double* state, void* stream);
+int nv_reg_metrics_finish(const double* state, int K, float* out, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

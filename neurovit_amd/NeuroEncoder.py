@@ -162,6 +162,19 @@ class NeuroEncoder(nn.Module):
         as_volumes = series.movedim(-1, 1).flatten(0, 1)              # [B, H, W, D, T] -> [B*T, H, W, D]  (strided copy)
         return self.volume_encoder(as_volumes).unflatten(0, (n_samples, n_time))
 
+    @property
+    def is_regression(self) -> bool:
+        return bool(getattr(self.volume_encoder, "regression", False))
+
+    def predict(self, x):
+        """Regression model (TRAINING_OBJECTIVE "regression"): predictions [B, K] on the RAW scale - the head's outputs times
+        REGRESSION_TARGET_STD plus REGRESSION_TARGET_MEAN - from a no-grad forward in the module's current mode."""
+        if not self.is_regression:
+            raise RuntimeError("NeuroEncoder.predict: the model is a classifier - build it with TRAINING_OBJECTIVE 'regression'")
+        enc = self.volume_encoder
+        with torch.no_grad():
+            return self(x).float() * enc.target_std + enc.target_mean
+
     def precision(self, mode: str):
         """Context manager: eval-mode no-grad forwards of the ViT3D encoder inside it run in `mode` ("bf16" / "fp16": the 16-bit
         operand path in the encoder's operand format, or "fp32")."""
@@ -303,6 +316,7 @@ class NeuroEncoder(nn.Module):
         (token_maps_to_volumes).  No tensor crosses PCIe and nothing synchronises with the host inside the call.
         User-assigned `model.activations` / `model.gradients` overrides are NOT consulted (get_attention_map honours them)."""
         from . import ops
+        target = self._resolve_target(target)             # (a regression model: output 0; the score-based methods resolve their score to "logit")
         if self.config['TRAINING_DIM'] != 3:
             raise NotImplementedError("attribution_volumes: 3D model only (as get_attention_map; the 4D model has no patch-grid attribution)")
         if method not in ("gradcam", "rollout", "relevance", "occlusion", "integrated_gradients", "shapley"):
@@ -349,6 +363,20 @@ class NeuroEncoder(nn.Module):
 
     # ---- perturbation attribution, on the device (csrc/perturb.hip): how faithful a map is (deletion / insertion curves) and the
     # gradient-free baseline among the maps (patch occlusion sensitivity)
+    def _resolve_score(self, what, score, default="prob"):
+        """score None = `default` on a classifier, "logit" on a regression model - where "prob" means nothing (the softmax of one output is
+        1, of several a competition between unrelated targets) and is refused"""
+        if score is None:
+            return "logit" if self.is_regression else default
+        if self.is_regression and score == "prob":
+            raise ValueError(f"{what}: score 'prob' is meaningless on a regression model (its outputs are predictions, not class logits) - use "
+                             "score='logit' (or None), the output itself")
+        return score
+
+    def _resolve_target(self, target):
+        """target None on a regression model = output 0 (there is no predicted class to fall back to)"""
+        return 0 if target is None and self.is_regression else target
+
     def _perturbation_inputs(self, what, x, baseline, score, chunk):
         """argument checks shared by perturbation_curves / occlusion_sensitivity (all before any device work) -> (S, G, chunk)"""
         from . import ops
@@ -389,7 +417,7 @@ class NeuroEncoder(nn.Module):
                 logits[first:first + count].copy_(part)
         return logits
 
-    def perturbation_curves(self, x, token_maps, target=None, steps=20, mode="both", baseline=0.0, score="prob", chunk=None):
+    def perturbation_curves(self, x, token_maps, target=None, steps=20, mode="both", baseline=0.0, score=None, chunk=None):
         """Deletion / insertion curves of token maps [B, G^3] (token order, e.g. the third result of attribution_volumes(...,
         return_token_maps=True)) for a batch x [B, H, W, D]: the class score while the patches are replaced by the baseline (deletion) or
         restored into the baseline (insertion) in the order the map ranks them - a faithful map has a small deletion area and a large
@@ -401,11 +429,13 @@ class NeuroEncoder(nn.Module):
                      labels being the ranks (ops.mask_patches); consecutive slices of `chunk` jobs (None: max(1, min(64, 2^30 // (4 S^3))))
                      are masked into one reused buffer and forwarded under no_grad in the module's current mode and precision;
           baseline   a float, or a tensor of x's shape or [1, S, S, S] (a blurred copy, a mean volume);
-          score      "prob" (softmax probability of the class) or "logit".
+          score      "prob" (softmax probability of the class) or "logit"; None = "prob" on a classifier, "logit" on a regression model
+                     (TRAINING_OBJECTIVE "regression": "prob" is refused there, and target None means output 0).
         Returns a dict of device tensors: deletion / insertion [B, K], deletion_auc / insertion_auc [B] (trapezoid rule over
         fractions = k / steps [K]), class_idx [B], ranks [B, N]; mode "deletion" / "insertion" computes and returns only that pair.
         Nothing crosses PCIe and nothing synchronises with the host inside the call."""
         from . import ops
+        score, target = self._resolve_score("perturbation_curves", score), self._resolve_target(target)
         S, G, chunk = self._perturbation_inputs("perturbation_curves", x, baseline, score, chunk)
         if mode not in ("both", "deletion", "insertion"):
             raise ValueError(f"perturbation_curves: mode must be 'both', 'deletion' or 'insertion', got {mode!r}")
@@ -439,7 +469,7 @@ class NeuroEncoder(nn.Module):
                 out[name + "_auc"] = ops.curve_auc(out[name])
         return out
 
-    def occlusion_sensitivity(self, x, target=None, window=1, baseline=0.0, score="prob", chunk=None):
+    def occlusion_sensitivity(self, x, target=None, window=1, baseline=0.0, score=None, chunk=None):
         """Patch occlusion sensitivity of a batch x [B, H, W, D]: (maps fp32 [B, G^3] in token order, class_idx [B]), both on the device.
         maps[b, t] = score of x[b] - score of x[b] with the window^3-patch block that holds patch t replaced by the baseline: signed
         (positive = the block supports the class), no gradient and no assumption about attention.  The blocks tile the patch grid from
@@ -449,6 +479,7 @@ class NeuroEncoder(nn.Module):
         with target None, the predicted class.  target / baseline / score / chunk: as perturbation_curves.  Costs Gb^3 + 1 forwards per
         volume; nothing crosses PCIe and nothing synchronises with the host inside the call."""
         from . import ops
+        score, target = self._resolve_score("occlusion_sensitivity", score), self._resolve_target(target)
         S, G, chunk = self._perturbation_inputs("occlusion_sensitivity", x, baseline, score, chunk)
         if int(window) != window or window < 1:
             raise ValueError(f"occlusion_sensitivity: window must be a positive integer, got {window!r}")
@@ -477,7 +508,7 @@ class NeuroEncoder(nn.Module):
 
     # ---- Shapley value sampling, on the device (csrc/shapley.hip): the one attribution that is efficient and order-free, over patches,
     # blocks of patches or atlas regions
-    def shapley_values(self, x, target=None, permutations=16, window=2, features=None, antithetic=True, baseline=0.0, score="prob", seed=0,
+    def shapley_values(self, x, target=None, permutations=16, window=2, features=None, antithetic=True, baseline=0.0, score=None, seed=0,
                        permutation_offset=0, ranks=None, chunk=None, return_scores=False):
         """Shapley values of players on the patch grid for a batch x [B, H, W, D], by permutation sampling (Castro et al.; captum's
         ShapleyValueSampling): the mean over random orders of the change in the class score when a player joins the players before it.
@@ -506,6 +537,7 @@ class NeuroEncoder(nn.Module):
         also interior [P, B, F - 1] and ends [B, 2] (empty, full).  Without ranks= nothing synchronises with the host inside the call."""
         from . import ops
         what = "shapley_values"
+        score, target = self._resolve_score(what, score), self._resolve_target(target)
         S, G, chunk = self._perturbation_inputs(what, x, baseline, score, chunk)
         N, B = G ** 3, x.shape[0]
         if ranks is not None:
@@ -597,6 +629,7 @@ class NeuroEncoder(nn.Module):
           score_input / score_baseline [B]; delta [B] float64 = sum of token_maps in double - (score_input - score_baseline), the
           completeness residual; alphas / weights [steps]."""
         from . import ops
+        score, target = self._resolve_score("integrated_gradients", score, "logit"), self._resolve_target(target)
         S, G, _ = self._perturbation_inputs("integrated_gradients", x, baseline, score, 1 if chunk is None else chunk)
         path_quadrature(method, steps)                                 # (ValueError before any device work)
         volume = x.to(device=self.device, dtype=torch.float32).contiguous()
@@ -742,7 +775,7 @@ class NeuroEncoder(nn.Module):
         return {"volumes": volumes, "token_maps": token_maps, "class_idx": class_idx, "logits": logits, "volume_logits": z, "temporal": temporal,
                 "cuts": cuts}
 
-    def temporal_importance(self, x, target=None, baseline=0.0, score="prob"):
+    def temporal_importance(self, x, target=None, baseline=0.0, score=None):
         """Which timepoints of a series x [B, H, W, D, T] drove a class of the 4D model, two ways, from ONE encoder pass over the B T
         volumes (the model's own no-grad forward: the fused no-copy 4D gather when T % 4 == 0) plus one forward of a single constant
         volume filled with `baseline` (a float):
@@ -755,6 +788,7 @@ class NeuroEncoder(nn.Module):
         grad_x_input, class_idx [B], scores [B, T + 1] (column 0: the unperturbed series, column 1 + t: timepoint t replaced), logits
         [B, 2], volume_logits [B, T, 2].  Refusals and side effects (none) as attribution_series."""
         from . import ops
+        score = self._resolve_score("temporal_importance", score)
         if score not in ops.SCORE_KINDS:
             raise ValueError(f"temporal_importance: score must be 'prob' or 'logit', got {score!r}")
         if torch.is_tensor(baseline) or isinstance(baseline, bool) or not isinstance(baseline, (int, float)):
@@ -839,6 +873,14 @@ class ViT3DEncoder(nn.Module):
         # the synthetic cube-localisation task has one class per cube position (NeuroEncoder.py:179); everything else is binary
         cubes_per_axis = self.grid_size // self.cube_size
         classes = cubes_per_axis ** 3 if config['DATASET_NAME'] == 'gradcam' else 2
+        # TRAINING_OBJECTIVE "regression" (optional key): the head predicts REGRESSION_TARGETS (default 1) continuous targets on the scale
+        # standardised by REGRESSION_TARGET_MEAN / _STD (lists of that many numbers, default 0 / 1) - non-persistent buffers: the
+        # state_dict keys stay the reference's
+        self.regression = config.get('TRAINING_OBJECTIVE', None) == "regression"
+        if self.regression:
+            if config['TRAINING_DIM'] == 4:
+                raise NotImplementedError("TRAINING_OBJECTIVE 'regression' is for the 3D model - the 4D model's temporal head is built around two features")
+            classes = self._regression_scale(config)
         # a cubic single-channel volume: frames (depth) and image sides share one extent and one patch edge
         # stochastic depth (timm's drop_path_rate, linear over the blocks; 0.1 in the DeiT-B / MAE fine-tuning recipes): optional key, absent = 0
         self.drop_path = config.get('TRAINING_DROP_PATH', 0.0)
@@ -854,6 +896,20 @@ class ViT3DEncoder(nn.Module):
         # 16-bit MFMA operand format of the training arithmetic: "bf16" (default) or "fp16" - what the reference's autocast(float16)
         # computes in (Trainer.py:68); TrainStep then scales the loss as its GradScaler does (Trainer.py:29,74-76)
         self.vit3d.set_operands(config.get('TRAINING_VIT_OPERANDS', 'bf16'))
+
+    def _regression_scale(self, config) -> int:
+        """REGRESSION_TARGETS, checked, and the buffers target_mean / target_std [K] of the raw scale"""
+        K = config.get('REGRESSION_TARGETS', 1)
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError(f"REGRESSION_TARGETS must be a positive integer, got {K!r}")
+        for key, name, default in (('REGRESSION_TARGET_MEAN', 'target_mean', 0.0), ('REGRESSION_TARGET_STD', 'target_std', 1.0)):
+            given = config.get(key, None)
+            given = [default] * K if given is None else ([given] if isinstance(given, (int, float)) else list(given))
+            t = torch.tensor([float(g) for g in given], dtype=torch.float32)
+            if t.numel() != K or not bool(torch.isfinite(t).all()) or (name == 'target_std' and not bool((t > 0).all())):
+                raise ValueError(f"{key} must be {K} finite numbers" + (" > 0" if name == 'target_std' else "") + f", got {given!r}")
+            self.register_buffer(name, t, persistent=False)
+        return K
 
     def forward_raw(self, raw, crop=None):
         from .preprocess import ADNI_CROP, crop_view, volume_sigma

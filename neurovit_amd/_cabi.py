@@ -93,6 +93,18 @@ class DropPath(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_int), ("factors", ctypes.c_void_p)]
 
 
+class RegOpts(ctypes.Structure):
+    """struct nv_reg_opts (neurovit_hip.h, added within revision 8): kind, huber's delta, the targets' mean / std, per-target weights and the
+    mix table of the regression loss (nv_reg_loss / nv_head_step_reg / nv_vit_train_step_reg)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("kind", ctypes.c_int), ("delta", ctypes.c_float), ("mean", ctypes.c_void_p), ("std", ctypes.c_void_p),
+                ("weight", ctypes.c_void_p), ("mix", ctypes.c_void_p)]
+
+
+REG_KINDS = {"mse": 0, "l1": 1, "huber": 2}                 # NV_REG_MSE / NV_REG_L1 / NV_REG_HUBER
+REG_METRIC_SLOTS = 9                                        # NV_REG_METRIC_SLOTS: doubles per target of the metrics' state
+REG_METRIC_NAMES = ("n", "mae", "rmse", "bias", "r", "r2")  # the columns nv_reg_metrics_finish writes
+
+
 DROP_PATH_SCHEDULES = {"linear": 0, "constant": 1}          # NV_DROP_PATH_LINEAR / NV_DROP_PATH_CONSTANT
 
 

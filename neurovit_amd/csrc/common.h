@@ -380,6 +380,102 @@ static inline int check_loss_opts(const nv_loss_opts* lo, const char* who) {
 }
 static inline CeSoft make_ce_soft(const nv_loss_opts* lo) { return CeSoft{lo->label_smoothing, lo->class_weight, lo->mix}; }
 
+// ---- the regression loss of nv_reg_opts (mse / l1 / huber on standardised targets, NaN = missing, per-target weights, a mixed target; the
+// definition is in the header): the row body of reg_loss_kernel (regression.hip) and of the head step's regression form (norm.hip), so that
+// both produce the same bits.  Every fp32 operation of the target is rounded on its own (no contraction into an fma).
+struct RegLoss {
+  int kind; float delta;
+  const float* mean; const float* std; const float* w;   // [K] each, or null (0 / 1 / 1)
+  const int* mix;                                        // rows of nv_mix_params [B, NV_MIX_COLS] or null
+};
+// a row's partner and label lambda.  Nothing is read through an index that was not checked: a partner outside [0, B) leaves ok = false,
+// and the row's term - with it the loss - is NaN.
+struct RegRow { int p; float lam; bool mixed, ok; };
+__device__ __forceinline__ RegRow reg_row(const RegLoss& o, int b, int B) {
+  RegRow r{b, 1.f, false, true};
+  if (o.mix) {
+    const int p = o.mix[(long)NV_MIX_COLS * b];
+    r.lam = __int_as_float(o.mix[(long)NV_MIX_COLS * b + 3]);
+    r.mixed = true;
+    r.ok = p >= 0 && p < B;
+    r.p = r.ok ? p : b;
+  }
+  return r;
+}
+// the target of cell (b, k) on the standardised scale; false: the cell is missing (a non-finite y, its own or its partner's)
+__device__ __forceinline__ bool reg_cell_target(const float* __restrict__ y, const RegLoss& o, const RegRow& r, int b, int k, int K, float& t) {
+  const float m = o.mean ? o.mean[k] : 0.f, s = o.std ? o.std[k] : 1.f;
+  const float ya = y[(long)b * K + k];
+  t = __fdiv_rn(__fsub_rn(ya, m), s);
+  bool ok = __builtin_isfinite(ya);
+  if (r.mixed) {
+    const float yb = y[(long)r.p * K + k];
+    ok = ok && __builtin_isfinite(yb);
+    const float tb = __fdiv_rn(__fsub_rn(yb, m), s);
+    t = __fadd_rn(__fmul_rn(r.lam, t), __fmul_rn(__fsub_rn(1.f, r.lam), tb));
+  }
+  return ok;
+}
+// D = sum_bk m_bk w_k: targets, lambdas' partners and weights only.  Formed in double by every workgroup that needs it (256 threads), in one
+// fixed order: thread t sums the cells t, t + 256, ... of the [B, K] matrix, then the wave butterflies, then the four waves in order.
+// redd: 4 doubles of LDS.  NaN for a partner outside the batch; D == 0 (nothing observed) is returned as it is: loss 0, gradient 0.
+__device__ __forceinline__ double reg_denominator(const float* __restrict__ y, const RegLoss& o, int B, int K, double* redd) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  double part = 0.0;
+  const long cells = (long)B * K;
+  for (long i = tid; i < cells; i += 256) {
+    const int b = (int)(i / K), k = (int)(i - (long)b * K);
+    const RegRow r = reg_row(o, b, B);
+    if (!r.ok) { part += (double)__builtin_nanf(""); continue; }
+    float t;
+    if (reg_cell_target(y, o, r, b, k, K, t)) part += o.w ? (double)o.w[k] : 1.0;
+  }
+  part = wave_sum(part);
+  if (lane == 0) redd[wid] = part;
+  __syncthreads();
+  const double D = (redd[0] + redd[1]) + (redd[2] + redd[3]);
+  __syncthreads();
+  return D;
+}
+// One row (256 threads, every thread returns the row's numerator sum_k m_k w_k l(r_k)); dl (optional) = m_k w_k l'(r_k) * gscale_over_D, exactly
+// 0.0f in a missing cell.  The callers pass gscale_over_D = 0 when D == 0.  red: 4 floats of LDS.
+__device__ __forceinline__ float reg_row_term(const float* __restrict__ z, const float* __restrict__ y, const RegLoss& o, int b, int B, int K,
+                                              float gscale_over_D, float* red, float* __restrict__ dl) {
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const RegRow row = reg_row(o, b, B);
+  float num = 0.f;
+  for (int k = tid; k < K; k += 256) {
+    float t, g = 0.f;
+    if (reg_cell_target(y, o, row, b, k, K, t)) {
+      const float w = o.w ? o.w[k] : 1.f, r = __fsub_rn(z[k], t), a = fabsf(r);
+      float l, d;
+      if (o.kind == NV_REG_MSE) { l = r * r; d = 2.f * r; }
+      else if (o.kind == NV_REG_L1) { l = a; d = r > 0.f ? 1.f : (r < 0.f ? -1.f : 0.f); }
+      else if (a <= o.delta) { l = 0.5f * r * r; d = r; }
+      else { l = o.delta * (a - 0.5f * o.delta); d = r > 0.f ? o.delta : -o.delta; }
+      if (!__builtin_isfinite(r)) d = r - r;             // a non-finite prediction propagates into the gradient in every kind (NaN)
+      num += w * l;
+      g = (w * d) * gscale_over_D;
+    }
+    if (dl) dl[k] = g;
+  }
+  num = wave_sum(num);
+  if (lane == 0) red[wid] = num;
+  __syncthreads();
+  num = (red[0] + red[1]) + (red[2] + red[3]);
+  __syncthreads();
+  return row.ok ? num : __builtin_nanf("");
+}
+static inline int check_reg_opts(const nv_reg_opts* ro, const char* who) {
+  NV_CHECK_ARG(ro && ro->struct_size == (int)sizeof(nv_reg_opts), "%s: nv_reg_opts is NULL or its struct_size = %d, this library's nv_reg_opts has %d bytes", who,
+               ro ? ro->struct_size : -1, (int)sizeof(nv_reg_opts));
+  NV_CHECK_ARG(ro->kind == NV_REG_MSE || ro->kind == NV_REG_L1 || ro->kind == NV_REG_HUBER, "%s: unknown nv_reg_opts.kind = %d", who, ro->kind);
+  NV_CHECK_ARG(ro->kind != NV_REG_HUBER || ro->delta > 0.f, "%s: huber needs delta > 0, got %g", who, (double)ro->delta);
+  NV_CHECK_ARG(nv_aligned(ro->mean, 4) && nv_aligned(ro->std, 4) && nv_aligned(ro->weight, 4) && nv_aligned(ro->mix, 4), "%s: mean, std, weight and mix 4-byte aligned", who);
+  return NV_OK;
+}
+static inline RegLoss make_reg_loss(const nv_reg_opts* ro) { return RegLoss{ro->kind, ro->delta, ro->mean, ro->std, ro->weight, ro->mix}; }
+
 // ---- dynamic loss scale: indices into the device state block of nv_loss_scale_* (optim.hip; NV_LOSS_SCALE_FLOATS floats)
 enum { LS_SCALE = 0,       // what the NEXT loss gradient is multiplied by
        LS_UNSCALE = 1,     // 1 / (scale of the gradients now in the arena): AdamW's extra grad factor

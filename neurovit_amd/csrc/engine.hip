@@ -1242,13 +1242,15 @@ extern "C" int nv_vit_train_step(const nv_vit_config* cfg, int B, const float* v
 // lo: nv_loss_opts (label smoothing, class weights, a mixed target) or NULL.  The loss calls below are nv_head_step_soft / nv_ce_loss_soft,
 // which run the index-target kernels of nv_vit_train_step when no option is on; nothing else differs.
 // sd: the step's stochastic-depth factors (nv_vit_train_step_sd), or NULL: forward, head step and backward then run the launches they always ran
+// targets + ro: the regression objective (nv_vit_train_step_reg) in the place of labels + lo - another loss at the one head / loss site, nothing else
 static int train_step_impl(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
                            float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
                            const long* labels, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_loss_opts* lo,
-                           float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const float* sd) {
+                           float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const float* sd,
+                           const float* targets = nullptr, const nv_reg_opts* ro = nullptr) {
   NV_CHECK_ARG(cfg && hp && hp->struct_size == (int)sizeof(nv_train_hparams), "nv_vit_train_step: nv_train_hparams.struct_size = %d, this library expects %d (ABI revision %d)",
                hp ? hp->struct_size : -1, (int)sizeof(nv_train_hparams), NV_ABI_VERSION);
-  NV_CHECK_ARG(labels && loss && dlogits && grads && (!hp->update || (adam_m && adam_v && hp->step >= 1)), "nv_vit_train_step: null pointer (labels / loss / dlogits / grads / optimizer state) or step < 1");
+  NV_CHECK_ARG((labels || (targets && ro)) && loss && dlogits && grads && (!hp->update || (adam_m && adam_v && hp->step >= 1)), "nv_vit_train_step: null pointer (labels / loss / dlogits / grads / optimizer state) or step < 1");
   NV_CHECK_ARG(!(in && in->time_points > 0), "nv_vit_train_step: the fused 4D input form is forward-only (the 4D model's encoder is frozen, NeuroEncoder.py:34-36)");
   // every argument check ahead of the first launch (a refused call must not leave half a step in the queue)
   NV_CHECK_ARG(hp->fuse_update >= 0 && hp->fuse_update <= 3, "nv_vit_train_step: fuse_update = %d (0 .. 3)", hp->fuse_update);
@@ -1267,6 +1269,7 @@ static int train_step_impl(const nv_vit_config* cfg, int B, const float* video, 
     NV_CHECK_ARG(dp->comm_stream != stream && dp->comm_stream != aux_stream, "nv_vit_train_step: nv_dp_plan.comm_stream must be a stream of its own");
   }
   if (int rc = check_loss_opts(lo, "nv_vit_train_step_ex")) return rc;
+  if (ro) RUN(check_reg_opts(ro, "nv_vit_train_step_reg"));
   const float lscale = hp->loss_scale > 0.f ? hp->loss_scale : 1.f;      // static loss scale: folded into d(loss)/d(logits), undone by the update's grad_scale
   // the head's forward, the loss and the head's backward as two launches instead of five (nv_head_step: bit-identical to the three calls;
   // it needs num_classes <= dim and dim % 8 == 0 - other heads take the five-launch path, which has no such limit)
@@ -1277,10 +1280,19 @@ static int train_step_impl(const nv_vit_config* cfg, int B, const float* video, 
   if (head_fused) {
     char* ws = (char*)workspace;
     const int Ll = D.L - 1;
-    RUN(nv_head_step_path((const float*)(ws + W.layer[Ll].x2), (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
-                          labels, lscale, hp->loss_scale_state, lo, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
-                          ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
-                          hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream, path_of(sd, Ll, 1, B), D.n));
+    const float* x2 = (const float*)(ws + W.layer[Ll].x2);
+    if (ro)      // the regression objective (nv_vit_train_step_reg): the third loss form of the same two launches
+      RUN(nv_head_step_reg(x2, (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
+                           targets, lscale, hp->loss_scale_state, ro, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
+                           ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
+                           hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream, path_of(sd, Ll, 1, B), D.n));
+    else
+      RUN(nv_head_step_path(x2, (long)D.n * D.d, B, D.d, params + T.hg, params + T.hb, cfg->ln_eps, params + T.hw, params + T.hbias, D.C,
+                            labels, lscale, hp->loss_scale_state, lo, (float*)(ws + W.xh), (float*)(ws + W.hst), logits, loss, dlogits, D.n, (float*)(ws + W.g), D.d,
+                            ws + W.scratch(Ll).g16, D.d, grads + T.hg, grads + T.hb, grads + T.hw, grads + T.hbias, grads + T.layer[Ll].b2,
+                            hp->accumulate ? 1 : 0, ws + W.sc[0].red, W.red_bytes, site_seed(drop_seed, 4 * Ll + 3), drop_p, stream, path_of(sd, Ll, 1, B), D.n));
+  } else if (ro) {
+    RUN(nv_reg_loss(logits, targets, B, cfg->num_classes, lscale, hp->loss_scale_state, ro, loss, dlogits, stream));
   } else {
     RUN(nv_ce_loss_soft(logits, labels, B, cfg->num_classes, lscale, hp->loss_scale_state, lo, loss, dlogits, stream));
   }
@@ -1330,4 +1342,16 @@ extern "C" int nv_vit_train_step_sd(const nv_vit_config* cfg, int B, const float
   RUN(check_drop_path(sd, "nv_vit_train_step_sd"));
   return train_step_impl(cfg, B, video, shape5, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, labels, logits, loss, dlogits, hp, lo,
                          drop_p, emb_drop_p, drop_seed, stream, aux_stream, sd ? sd->factors : nullptr);
+}
+
+// nv_vit_train_step_sd with the regression objective (nv_reg_opts; the definition is in the header): targets fp32 [B, num_classes] in the place
+// of the labels.  Forward, backward and update are those of every other step - they only see dlogits.  sd may be NULL
+extern "C" int nv_vit_train_step_reg(const nv_vit_config* cfg, int B, const float* video, const long* shape5, const long* strides5, const nv_vit_input* in,
+                                     float* params, void* params16, float* grads, float* adam_m, float* adam_v, void* workspace, long ws_bytes,
+                                     const float* targets, float* logits, float* loss, float* dlogits, const nv_train_hparams* hp, const nv_reg_opts* ro,
+                                     float drop_p, float emb_drop_p, unsigned long drop_seed, void* stream, void* aux_stream, const nv_vit_drop_path* sd) {
+  RUN(check_drop_path(sd, "nv_vit_train_step_reg"));
+  NV_CHECK_ARG(targets && ro, "nv_vit_train_step_reg: targets and nv_reg_opts must be given");
+  return train_step_impl(cfg, B, video, shape5, strides5, in, params, params16, grads, adam_m, adam_v, workspace, ws_bytes, nullptr, logits, loss, dlogits, hp, nullptr,
+                         drop_p, emb_drop_p, drop_seed, stream, aux_stream, sd ? sd->factors : nullptr, targets, ro);
 }

@@ -1452,6 +1452,23 @@ __global__ __launch_bounds__(256) void head_sums_kernel(const HeadStep a) {
 
 extern "C" long nv_head_step_workspace_bytes(int B, int d) { return nv_head_bwd_workspace_bytes(B, d) + (long)((B + 3) / 4 * 4) * sizeof(float); }
 
+// the argument record and the two grids of a head step, for every loss form (labels: NULL for the regression form, which has targets of its own)
+struct HeadGrid { dim3 rows, sums; };
+static void make_head_step(HeadStep& a, HeadGrid& grid, const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                           const float* bias, int C, const long* labels, float grad_scale, const float* scale_state, float* xh, float* stats, float* logits, float* loss,
+                           float* dlogits, int n, float* g, long ldg, void* g16, long ldg16, float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum,
+                           int accumulate, void* workspace, unsigned long drop_seed, float drop_p) {
+  a.x = x; a.row_stride = row_stride; a.B = B; a.d = d; a.C = C; a.n = n; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias;
+  a.labels = labels; a.grad_scale = grad_scale; a.xh = xh; a.stats = stats; a.logits = logits; a.loss = loss; a.dlogits = dlogits;
+  a.g = g; a.ldg = ldg; a.g16 = (r16*)g16; a.ldg16 = ldg16; a.dgamma = dgamma; a.dbeta = dbeta; a.dW = dW; a.dbias = dbias; a.dcolsum = dcolsum;
+  a.accumulate = accumulate; a.partials = (float*)workspace; a.terms = (float*)workspace + (long)B * 3 * d; a.drop = make_drop(drop_seed, drop_p);
+  a.fp16 = nv_operand_format() == NV_OPERAND_FP16; a.scale_state = scale_state;
+  const long fill_bytes = (long)B * n * d * (g16 ? 6 : 4);
+  int fill_blocks = (int)((fill_bytes + (1 << 16) - 1) >> 16);            // ~64 KiB per workgroup
+  if (fill_blocks > 1024) fill_blocks = 1024;
+  grid.rows = dim3(B + fill_blocks); grid.sums = dim3((unsigned)((3L * d + (long)C * d + 255) / 256));
+}
+
 // The one host body of the three entry points.  scale_state (may be NULL): the device block of nv_loss_scale_init - dlogits (and with
 // them every gradient) carry its current scale.  opts (checked by the caller) with no option on, or NULL: the index-target loss.
 static int head_step(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W, const float* bias, int C,
@@ -1466,16 +1483,10 @@ static int head_step(const float* x, long row_stride, int B, int d, const float*
   NV_CHECK_ARG(ws_bytes >= nv_head_step_workspace_bytes(B, d), "%s: workspace too small", who);
   NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d) && (d % 8) == 0 && nv_aligned16(g) && (!g16 || nv_aligned16(g16)),
                "%s: g / g16 must be dense [B*n, d], 16-byte aligned, d a multiple of 8", who);
-  HeadStep a;
-  a.x = x; a.row_stride = row_stride; a.B = B; a.d = d; a.C = C; a.n = n; a.gamma = gamma; a.beta = beta; a.eps = eps; a.W = W; a.bias = bias;
-  a.labels = labels; a.grad_scale = grad_scale; a.xh = xh; a.stats = stats; a.logits = logits; a.loss = loss; a.dlogits = dlogits;
-  a.g = g; a.ldg = ldg; a.g16 = (r16*)g16; a.ldg16 = ldg16; a.dgamma = dgamma; a.dbeta = dbeta; a.dW = dW; a.dbias = dbias; a.dcolsum = dcolsum;
-  a.accumulate = accumulate; a.partials = (float*)workspace; a.terms = (float*)workspace + (long)B * 3 * d; a.drop = make_drop(drop_seed, drop_p);
-  a.fp16 = nv_operand_format() == NV_OPERAND_FP16; a.scale_state = scale_state;
-  const long fill_bytes = (long)B * n * d * (g16 ? 6 : 4);
-  int fill_blocks = (int)((fill_bytes + (1 << 16) - 1) >> 16);            // ~64 KiB per workgroup
-  if (fill_blocks > 1024) fill_blocks = 1024;
-  const dim3 rows(B + fill_blocks), sums((unsigned)((3L * d + (long)C * d + 255) / 256));
+  HeadStep a; HeadGrid grid;
+  make_head_step(a, grid, x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
+                 dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, drop_seed, drop_p);
+  const dim3 rows = grid.rows, sums = grid.sums;
   const hipStream_t s = (hipStream_t)stream;
   if (path && soft) hipLaunchKernelGGL((head_rows_kernel<true, true>), rows, dim3(256), (d + 12 + 8) * sizeof(float), s, a, make_ce_soft(opts), path);
   else if (path) hipLaunchKernelGGL((head_rows_kernel<false, true>), rows, dim3(256), (d + 12) * sizeof(float), s, a, NoSoft{}, path);
@@ -1528,6 +1539,57 @@ extern "C" int nv_head_step_path(const float* x, long row_stride, int B, int d, 
   NV_CHECK_ARG(path_rows == n && nv_aligned(path, 4), "nv_head_step_path: path_rows = %d must be n = %d (the head's rows are grouped by volume), path 4-byte aligned", path_rows, n);
   return head_step(x, row_stride, B, d, gamma, beta, eps, W, bias, C, labels, grad_scale, scale_state, opts, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
                    dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, ws_bytes, drop_seed, drop_p, stream, path);
+}
+
+// ---- the regression form of the head step (nv_reg_opts; the definition is in the header): a kernel of its own around the shared row functions, so
+// that the instantiations of head_rows_kernel stay what they were.  Like the soft form, every workgroup of launch 1 forms the denominator D
+// itself (targets, partners and weights only) and stores its row's term already divided by D; launch 2 is head_sums_kernel<true>, which only
+// adds the terms up - reg_loss_kernel's order (regression.hip), the same bits.  D == 0: term 0, gradient 0.
+template <bool PATH>
+__global__ __launch_bounds__(256) void head_rows_reg_kernel(const HeadStep a, const float* __restrict__ targets, const RegLoss o, HeadPath<PATH> path) {
+  extern __shared__ __attribute__((aligned(16))) float sh[];   // d floats + 8 scratch + 4 (loss reduction) + 4 doubles (the denominator)
+  if ((int)blockIdx.x >= a.B) {
+    const int part = blockIdx.x - a.B, nparts = gridDim.x - a.B;
+    zero_rows_except(reinterpret_cast<char*>(a.g), (long)a.B * a.n, (long)a.d * 4, a.n, part, nparts);
+    if (a.g16) zero_rows_except(reinterpret_cast<char*>(a.g16), (long)a.B * a.n, (long)a.d * 2, a.n, part, nparts);
+    return;
+  }
+  const int b = blockIdx.x;
+  const float D = (float)reg_denominator(targets, o, a.B, a.C, reinterpret_cast<double*>(sh + a.d + 12));   // (d % 8 == 0: 8-byte aligned)
+  head_fwd_row(b, sh, a.x, a.row_stride, a.d, a.gamma, a.beta, a.eps, a.W, a.bias, a.C, a.xh, a.stats, a.logits);
+  __syncthreads();                                   // logits[b], stats[b] (global, written by this workgroup) are visible to all of it
+  const float scale = a.scale_state ? a.grad_scale * a.scale_state[0] : a.grad_scale;
+  const float num = reg_row_term(a.logits + (long)b * a.C, targets, o, b, a.B, a.C, D == 0.f ? 0.f : scale / D, sh + a.d + 8, a.dlogits + (long)b * a.C);
+  if (threadIdx.x == 0) a.terms[b] = D == 0.f ? 0.f : num / D;
+  __syncthreads();
+  head_bwd_x_row<PATH>(b, sh, a.dlogits, a.C, a.W, a.x, a.row_stride, a.stats, a.gamma, a.d, a.n, a.g, a.ldg, a.g16, a.ldg16, a.partials, a.drop, 0, a.fp16, path);
+}
+
+extern "C" int nv_head_step_reg(const float* x, long row_stride, int B, int d, const float* gamma, const float* beta, float eps, const float* W,
+                                const float* bias, int C, const float* targets, float grad_scale, const float* scale_state, const nv_reg_opts* opts,
+                                float* xh, float* stats, float* logits, float* loss, float* dlogits, int n, float* g, long ldg, void* g16, long ldg16,
+                                float* dgamma, float* dbeta, float* dW, float* dbias, float* dcolsum, int accumulate, void* workspace, long ws_bytes,
+                                unsigned long drop_seed, float drop_p, void* stream, const float* path, int path_rows) {
+  const char* who = "nv_head_step_reg";
+  if (int rc = check_reg_opts(opts, who)) return rc;
+  NV_CHECK_ARG(B > 0 && d > 0 && C > 0 && C <= d && n > 0, "%s: B = %d, d = %d, K = %d (at most d), n = %d", who, B, d, C, n);
+  NV_CHECK_ARG(x && gamma && beta && W && bias && targets && xh && stats && logits && loss && dlogits && g && dgamma && dbeta && dW && dbias && workspace,
+               "%s: null pointer", who);
+  NV_CHECK_ARG(nv_aligned(targets, 4) && ws_bytes >= nv_head_step_workspace_bytes(B, d), "%s: workspace too small, or targets not 4-byte aligned", who);
+  NV_CHECK_ARG(ldg == d && (!g16 || ldg16 == d) && (d % 8) == 0 && nv_aligned16(g) && (!g16 || nv_aligned16(g16)),
+               "%s: g / g16 must be dense [B*n, d], 16-byte aligned, d a multiple of 8", who);
+  NV_CHECK_ARG(!path || (path_rows == n && nv_aligned(path, 4)), "%s: path_rows = %d must be n = %d (the head's rows are grouped by volume), path 4-byte aligned", who, path_rows, n);
+  HeadStep a; HeadGrid grid;
+  make_head_step(a, grid, x, row_stride, B, d, gamma, beta, eps, W, bias, C, nullptr, grad_scale, scale_state, xh, stats, logits, loss, dlogits, n, g, ldg, g16, ldg16,
+                 dgamma, dbeta, dW, dbias, dcolsum, accumulate, workspace, drop_seed, drop_p);
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t lds = (d + 12 + 8) * sizeof(float);
+  if (path) hipLaunchKernelGGL(head_rows_reg_kernel<true>, grid.rows, dim3(256), lds, s, a, targets, make_reg_loss(opts), path);
+  else hipLaunchKernelGGL(head_rows_reg_kernel<false>, grid.rows, dim3(256), lds, s, a, targets, make_reg_loss(opts), NoPath{});
+  NV_CHECK_LAUNCH("nv_head_step_reg/rows");
+  hipLaunchKernelGGL(head_sums_kernel<true>, grid.sums, dim3(256), 0, s, a);
+  NV_CHECK_LAUNCH(who);
+  return NV_OK;
 }
 
 // --------------------------------------------------------------------------------------- column sum of a bf16 matrix (bias grads)

@@ -190,10 +190,12 @@ class VitRuntime(PassLedger):
         return nbytes
 
     def _forward(self, entry: str, video, layout, weights, mid=(), after=(), *, vol_sigma=None, time_points: int = 0, rows_form=None,
-                 attn_export=None, dropout=(0.0, 0.0, 0), operands: bool = True, step: bool = False, drop_path=None):
+                 attn_export=None, dropout=(0.0, 0.0, 0), operands: bool = True, step: bool = False, drop_path=None,
+                 path_arg: bool = False):
         """What every forward shares: checks, input form, workspace and logits, the C call
         `entry`(cfg, B, video, shape, strides, input, *weights, workspace, bytes, *mid, logits, *after, stream[, aux stream][, drop path]), the pass record.
         drop_path: the stochastic-depth table of an *_sd entry (checked here), kept with the pass for its backward.
+        path_arg: the entry takes the drop-path argument even without a table (NULL then).
         step: the one-call train step - the primary training workspace (a pending pass in it goes stale), the auxiliary stream, a done pass.
         Returns (pass, logits)."""
         rows_form = self.rows_form if rows_form is None else int(rows_form)
@@ -206,7 +208,7 @@ class VitRuntime(PassLedger):
         logits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
         check(getattr(lib, entry)(ctypes.byref(self.cfg), B, video.data_ptr(), ops.shape5(video), ops.strides5(video), _inp_ptr(inp), *weights,
                                   ws.data_ptr(), ws.numel(), *mid, logits.data_ptr(), *after, torch.cuda.current_stream().cuda_stream,
-                                  *((self._aux_stream(dev),) if step else ()), *(() if sd is None else (ctypes.byref(sd),))), entry)
+                                  *((self._aux_stream(dev),) if step else ()), *((ctypes.byref(sd),) if sd is not None else ((None,) if path_arg else ()))), entry)
         # a backward re-gathers the same (raw) input and takes the same form of the last block - and the same stochastic-depth factors
         return self.open(_Pass(B, layout, ws, video, (vol_sigma, inp), rows_form, dropout, done=step, drop_path=drop_path)), logits
 
@@ -484,7 +486,7 @@ class VitRuntime(PassLedger):
                    grad_scale: float = 1.0, accumulate: bool = False, update: bool = True, fuse_update: int = 0,
                    dropout: Tuple[float, float, int] = (0.0, 0.0, 0), vol_sigma=None, rows_form: Optional[int] = None,
                    loss_scale: float = 0.0, loss_scale_state: Optional[torch.Tensor] = None, dp=None, loss_opts=None,
-                   drop_path: Optional[torch.Tensor] = None):
+                   drop_path: Optional[torch.Tensor] = None, reg_opts=None):
         """The reference's whole train step (Trainer.py:65-79) as ONE native call (nv_vit_train_step): forward, CrossEntropyLoss,
         backward of every stage, AdamW over the arena + bf16 shadow refresh.  Returns (loss [1], logits [B, C]) on the device.
         Same launches, streams and arithmetic as forward() + ops.ce_loss + backward() + ops.adamw_step.
@@ -494,11 +496,17 @@ class VitRuntime(PassLedger):
         dynamic loss scale (optim.LossScaler) - GradScaler semantics on the device, needs fuse_update = 0.
         loss_opts: None, or a _cabi.LossOpts (ops.loss_opts: label smoothing, class weights, a mix table) - the step then goes
         through nv_vit_train_step_ex; the tensors it points to are the caller's to keep alive.
-        drop_path: None, or the step's stochastic-depth factors fp32 [depth, 2, B] on the device (nv_vit_train_step_sd; every form above)."""
+        drop_path: None, or the step's stochastic-depth factors fp32 [depth, 2, B] on the device (nv_vit_train_step_sd; every form above).
+        reg_opts: None, or a _cabi.RegOpts (ops.reg_opts) - the regression objective (nv_vit_train_step_reg; every form above): `labels` are
+          then the targets, fp32 [B, num_classes] on the device, and loss_opts must be None."""
         B, dev = video.shape[0], video.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dlogits = torch.empty((B, self.cfg.num_classes), dtype=torch.float32, device=dev)
-        assert labels.is_cuda and labels.dtype == torch.int64 and labels.numel() == B and labels.is_contiguous()
+        if reg_opts is not None:
+            assert loss_opts is None, "the regression objective has options of its own (reg_opts)"
+            assert labels.is_cuda and labels.dtype == torch.float32 and tuple(labels.shape) == (B, self.cfg.num_classes) and labels.is_contiguous()
+        else:
+            assert labels.is_cuda and labels.dtype == torch.int64 and labels.numel() == B and labels.is_contiguous()
         hp = TrainHparams(ctypes.sizeof(TrainHparams), int(step), float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay),
                           float(grad_scale), int(bool(accumulate)), int(bool(update)), int(fuse_update), float(loss_scale),
                           None if dp is None else ctypes.cast(ctypes.pointer(dp), ctypes.c_void_p),      # _cabi.DpPlan (kept alive by the caller)
@@ -507,10 +515,13 @@ class VitRuntime(PassLedger):
         entry = "nv_vit_train_step_ex" if extra else "nv_vit_train_step"
         if drop_path is not None:
             entry, extra = "nv_vit_train_step_sd", extra or (None,)
+        if reg_opts is not None:
+            entry, extra = "nv_vit_train_step_reg", (ctypes.byref(reg_opts),)
         rec, logits = self._forward(entry, video, 1,
                                     (params.data_ptr(), params16.data_ptr(), grads.data_ptr(), adam_m.data_ptr(), adam_v.data_ptr()), (labels.data_ptr(),),
                                     (loss.data_ptr(), dlogits.data_ptr(), ctypes.byref(hp)) + extra + _drop(dropout),
-                                    vol_sigma=vol_sigma, rows_form=rows_form, dropout=dropout, step=True, drop_path=drop_path)
+                                    vol_sigma=vol_sigma, rows_form=rows_form, dropout=dropout, step=True, drop_path=drop_path,
+                                    path_arg=reg_opts is not None)
         rec.dlogits = dlogits
         return loss, logits
 

@@ -564,6 +564,117 @@ def ce_loss_soft(logits: torch.Tensor, target: torch.Tensor, label_smoothing: fl
     return loss, dl
 
 
+def reg_opts(kind: str = "mse", delta: float = 1.0, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None,
+             weight: Optional[torch.Tensor] = None, mix: Optional[torch.Tensor] = None, B: Optional[int] = None, K: Optional[int] = None, device=None):
+    """_cabi.RegOpts for the regression loss (the definition is in the header).  kind: "mse", "l1" or "huber" (delta > 0); mean / std / weight:
+    float32 [K] on the device or None (0 / 1 / ones); mix: int32 [B, 12] on the device (rows of nv_mix_params).  The tensors must outlive the
+    call that reads them (the struct holds their addresses)."""
+    from ._cabi import REG_KINDS, MIX_COLS, RegOpts
+    if kind not in REG_KINDS:
+        raise ValueError(f"regression loss must be one of {sorted(REG_KINDS)}, got {kind!r}")
+    if isinstance(delta, bool) or not isinstance(delta, (int, float)):
+        raise TypeError(f"huber delta must be a number, got {delta!r}")
+    if kind == "huber" and not float(delta) > 0.0:
+        raise ValueError(f"huber delta must be > 0, got {delta}")
+    for name, t in (("target_mean", mean), ("target_std", std), ("target_weight", weight)):
+        if t is None:
+            continue
+        if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous()):
+            raise ValueError(f"{name} must be a dense float32 vector [K]")
+        if K is not None and t.numel() != K:
+            raise ValueError(f"{name} has {t.numel()} entries for {K} targets")
+        if not t.is_cuda or (device is not None and t.device != torch.device(device)):
+            raise RuntimeError(f"{name} must live on the predictions' MI355X (cuda) device - there is no CPU fallback")
+    if mix is not None:
+        if not (torch.is_tensor(mix) and mix.dtype == torch.int32 and mix.dim() == 2 and mix.shape[1] == MIX_COLS and mix.is_contiguous()):
+            raise ValueError(f"mix must be a dense int32 [B, {MIX_COLS}] table (VolumeMix.params / last_mix)")
+        if B is not None and mix.shape[0] != B:
+            raise ValueError(f"mix has {mix.shape[0]} rows for a batch of {B}")
+        if not mix.is_cuda or (device is not None and mix.device != torch.device(device)):
+            raise RuntimeError("mix must live on the predictions' MI355X (cuda) device - there is no CPU fallback")
+    return RegOpts(ctypes.sizeof(RegOpts), REG_KINDS[kind], float(delta), _p(mean), _p(std), _p(weight), _p(mix))
+
+
+def reg_targets(target: torch.Tensor, B: int, K: int) -> torch.Tensor:
+    """targets as the kernels read them: dense float32 [B, K] ([B] is [B, 1]); any real dtype is cast"""
+    if not torch.is_tensor(target) or target.is_complex() or target.dtype == torch.bool:
+        raise TypeError("regression targets must be a real-valued tensor")
+    if target.dim() == 1 and K == 1:
+        target = target.unsqueeze(1)
+    if tuple(target.shape) != (B, K):
+        raise ValueError(f"regression targets have shape {tuple(target.shape)}, the predictions are [{B}, {K}]")
+    return target.to(torch.float32).contiguous()
+
+
+def reg_loss(pred: torch.Tensor, target: torch.Tensor, opts=None, grad_scale: float = 1.0, want_grad=True, scale_state=None):
+    """nv_reg_loss: the regression loss of a _cabi.RegOpts (reg_opts(...); None = plain mse) over pred / target float32 [B, K].
+    Returns (loss [1], dpred or None)."""
+    B, K = pred.shape
+    ro = reg_opts() if opts is None else opts
+    loss = torch.empty(1, device=pred.device)
+    dp = torch.empty_like(pred) if want_grad else None
+    check(lib.nv_reg_loss(_p(pred), _p(target), B, K, grad_scale, _p(scale_state), ctypes.byref(ro), _p(loss), _p(dp), _stream()), "nv_reg_loss")
+    return loss, dp
+
+
+def head_step_reg(x, gamma, beta, W, bias, targets, opts=None, eps=1e-5, grad_scale=1.0, scale_state=None, drop_seed=0, drop_p=0.0, path=None, path_rows: int = 0):
+    """nv_head_step_reg: head_step with the regression loss over targets float32 [B, K].  Returns what head_step returns."""
+    B, n, d = x.shape
+    K = W.shape[0]
+    ro = reg_opts() if opts is None else opts
+    outs, ws = _head_step_outputs(B, n, d, K, x.device)
+    logits, xh, st, loss, dl, g, g16, dgamma, dbeta, dW, db, dcol = outs
+    check(lib.nv_head_step_reg(_p(x), n * d, B, d, _p(gamma), _p(beta), eps, _p(W), _p(bias), K, _p(targets), grad_scale, _p(scale_state), ctypes.byref(ro),
+                               _p(xh), _p(st), _p(logits), _p(loss), _p(dl), n, _p(g), d, _p(g16), d, _p(dgamma), _p(dbeta), _p(dW), _p(db), _p(dcol), 0,
+                               _p(ws), ws.numel(), drop_seed, drop_p, _stream(), _p(path), int(path_rows)), "nv_head_step_reg")
+    return outs
+
+
+class RegressionMetrics:
+    """Validation metrics of a regression model on the RAW scale, accumulated on the device (nv_reg_metrics_*): update() makes one launch and
+    no host read, compute() one launch and one read.  pred: the head's output [B, K] on the standardised scale (de-standardised with mean /
+    std here); target: raw values, NaN = missing.  compute() -> {"n", "mae", "rmse", "bias", "r", "r2"}: float32 [K] tensors on the host."""
+
+    def __init__(self, K: int, mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, device="cuda"):
+        from ._cabi import REG_METRIC_SLOTS
+        self.K, self.device = int(K), torch.device(device)
+        if self.K < 1:
+            raise ValueError(f"RegressionMetrics: K = {K}")
+        if self.device.type != "cuda":
+            raise RuntimeError("RegressionMetrics runs on the MI355X (cuda) device - there is no CPU fallback")
+
+        def vec(t, name):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            if t.numel() != self.K:
+                raise ValueError(f"RegressionMetrics: {name} has {t.numel()} entries for {self.K} targets")
+            return t
+        self.mean, self.std = vec(mean, "mean"), vec(std, "std")
+        self.state = torch.zeros((self.K, REG_METRIC_SLOTS), dtype=torch.float64, device=self.device)
+
+    def reset(self) -> None:
+        self.state.zero_()
+
+    def update(self, pred: torch.Tensor, target: torch.Tensor) -> None:
+        if pred.dim() != 2 or pred.shape[1] != self.K or pred.dtype != torch.float32 or not pred.is_cuda:
+            raise ValueError(f"RegressionMetrics.update: pred must be float32 [B, {self.K}] on the device")
+        B = pred.shape[0]
+        target = reg_targets(target, B, self.K).to(pred.device)
+        check(lib.nv_reg_metrics_update(_p(pred.contiguous()), _p(target), B, self.K, _p(self.mean), _p(self.std), _p(self.state), _stream()), "nv_reg_metrics_update")
+
+    def compute_device(self) -> torch.Tensor:
+        """float32 [K, 6] on the device (n, MAE, RMSE, bias, r, R^2): no host read"""
+        out = torch.empty((self.K, 6), device=self.device)
+        check(lib.nv_reg_metrics_finish(_p(self.state), self.K, _p(out), _stream()), "nv_reg_metrics_finish")
+        return out
+
+    def compute(self) -> dict:
+        from ._cabi import REG_METRIC_NAMES
+        out = self.compute_device().cpu()          # the one host read
+        return {name: out[:, i].clone() for i, name in enumerate(REG_METRIC_NAMES)}
+
+
 def head_step_soft(x, gamma, beta, W, bias, labels, label_smoothing=0.0, class_weight=None, mix=None, eps=1e-5, grad_scale=1.0, scale_state=None):
     """nv_head_step_soft: head_step with the soft-target cross-entropy.  Returns what head_step returns."""
     B, n, d = x.shape

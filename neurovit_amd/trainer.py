@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from .NeuroEncoder import NeuroEncoder
-from .nn import CrossEntropyLoss
+from .nn import CrossEntropyLoss, RegressionLoss
 from .optim import FusedAdamW, GradClipper, LRSchedule, LossScaler, ModelEma, check_max_norm, param_groups, set_group_lrs
 from .parallel import GradSync, NativeComm, broadcast_parameters
 
@@ -59,7 +59,13 @@ class TrainStep:
     label_smoothing, class_weight: nn.CrossEntropyLoss(weight=, label_smoothing=) on every path; __call__'s `mix` (VolumeMix.last_mix)
       trains against the Mixup / CutMix target.  Data parallel, each rank normalises its loss by its own denominator.
     ema_decay: a number in [0, 1) = `ema`, an optim.ModelEma(model, ema_decay, ema_warmup, ema_update_every) updated once per OPTIMIZER
-      step - a skipped one included - behind the update, on the step's stream, on every path; no collective."""
+      step - a skipped one included - behind the update, on the step's stream, on every path; no collective.
+    objective: "classification" (the default: everything above) or "regression" - the head's num_classes outputs are continuous
+      predictions on the standardised scale and the step is called as step(x, targets, mix=None) with targets [B] or [B, K] on the raw
+      scale, NaN = missing (nn.RegressionLoss; the rule is in include/neurovit_hip.h).  regression_loss: "mse", "l1" or "huber"
+      (huber_delta); target_mean / target_std / target_weight: K numbers each or None (0 / 1 / ones).  Every option above but
+      label_smoothing / class_weight goes with it, on the native step, the native data-parallel plan (each rank normalises by its own
+      count of observed targets) and the general path, which give the same bits; it is never replayed from a graph."""
     # fuse_update=None: token rows (batch x tokens) up to which the layers' weights are updated during the backward pass.  ViT3D-base,
     # volumes/s mode 0 -> 3: batch 2 641 -> 655 (+2.3 %), 4: 1113 -> 1165 (+4.8 %), 5: 1055 -> 1132, 6: 1152 -> 1191, 7: 1268 -> 1322,
     # 8: 1390 -> 1382, 16: 1780 -> 1749, 32: 1940 -> 1923; ViT3D-large 53.8 -> 53.3 - small batches leave wave slots and memory bandwidth
@@ -71,7 +77,12 @@ class TrainStep:
                  grad_comm_dtype: torch.dtype = torch.float32, grad_comm_algo: Optional[str] = None, fuse_update: Optional[int] = None,
                  loss_scale=None, native_dp: Optional[bool] = None, max_grad_norm: Optional[float] = None, label_smoothing: float = 0.0,
                  class_weight=None, ema_decay: Optional[float] = None, ema_warmup: bool = True, ema_update_every: int = 1,
-                 no_decay: bool = False, layer_decay: Optional[float] = None, lr_schedule: Optional[LRSchedule] = None):
+                 no_decay: bool = False, layer_decay: Optional[float] = None, lr_schedule: Optional[LRSchedule] = None,
+                 objective: str = "classification", regression_loss: str = "mse", huber_delta: float = 1.0, target_mean=None, target_std=None,
+                 target_weight=None):
+        if objective not in ("classification", "regression"):
+            raise ValueError(f"TrainStep: objective must be 'classification' or 'regression', got {objective!r}")
+        self.objective = objective
         if ema_decay is not None:
             ModelEma.check_args(ema_decay, ema_update_every)
         self.max_grad_norm = None if max_grad_norm is None else check_max_norm(max_grad_norm)
@@ -85,8 +96,11 @@ class TrainStep:
         vit = self._vit = model.volume_encoder.vit3d
         self._device = next(model.parameters()).device
         self._arena_trainable = all(p.requires_grad for p in vit.parameters())
-        self.criterion = CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)
-        if self.criterion.weight is not None:
+        if objective == "regression":
+            self.criterion = self._regression_criterion(label_smoothing, class_weight, regression_loss, huber_delta, target_mean, target_std, target_weight)
+        else:
+            self.criterion = CrossEntropyLoss(weight=class_weight, label_smoothing=label_smoothing)
+        if self.criterion.weight is not None or objective == "regression":
             self.criterion.to(self._device)
         self.accumulation_steps = max(1, int(accumulation_steps))
         self._micro = 0
@@ -102,6 +116,19 @@ class TrainStep:
         self.clipper = None if self.max_grad_norm is None else GradClipper(self._device, self.max_grad_norm)
         # (last: the average starts from the parameters as they are now - after the data-parallel broadcast)
         self.ema = None if ema_decay is None else ModelEma(model, decay=ema_decay, warmup=ema_warmup, update_every=ema_update_every)
+
+    def _regression_criterion(self, label_smoothing, class_weight, kind, delta, mean, std, weight) -> RegressionLoss:
+        """nn.RegressionLoss of the regression objective, its vectors checked against the head's outputs"""
+        if label_smoothing or class_weight is not None:
+            raise ValueError("TrainStep: label_smoothing / class_weight belong to the classification objective - a regression step takes "
+                             "regression_loss, huber_delta, target_mean, target_std and target_weight")
+        crit = RegressionLoss(kind, delta, target_mean=mean, target_std=std, weight=weight)
+        K = self._vit._cfg.num_classes
+        for name in ("target_mean", "target_std", "weight"):
+            t = getattr(crit, name)
+            if t is not None and t.numel() != K:
+                raise ValueError(f"TrainStep: {name} has {t.numel()} entries, the head has {K} outputs")
+        return crit
 
     def _setup_optimizer(self, lr, weight_decay, no_decay, layer_decay, lr_schedule) -> bool:
         """optimizer, schedule and last_lr; returns whether the groups carry more than one (lr_scale, weight_decay) pair"""
@@ -293,7 +320,29 @@ class TrainStep:
                                "save after the micro-step that ends it")
         return {"version": self.STATE_VERSION, "operands": self._vit.operands, **self.optimizer.fused_state(),
                 "scaler": None if self.scaler is None else self.scaler.state.detach().clone(), "static_scale": self.static_scale,
-                "ema": None if self.ema is None else self.ema.state_dict()}
+                "ema": None if self.ema is None else self.ema.state_dict(), **self._objective_state()}
+
+    def _objective_state(self) -> dict:
+        """what the regression objective adds to state_dict: its name, the loss and the scale the head's outputs live on"""
+        if self.objective != "regression":
+            return {}                               # (a classifier's state is what it always was)
+        crit = self.criterion
+        vec = lambda t: None if t is None else t.detach().cpu().clone()
+        return {"objective": self.objective, "kind": crit.kind, "delta": crit.delta, "mean": vec(crit.target_mean), "std": vec(crit.target_std)}
+
+    def _check_objective_state(self, state: dict) -> None:
+        """ValueError unless the state was saved under this step's objective (a state without the key: classification)"""
+        mine = self._objective_state()
+        if state.get("objective", "classification") != self.objective:
+            raise ValueError(f"TrainStep.load_state_dict: the state was saved under the {state.get('objective', 'classification')} objective, this step's is {self.objective}")
+        for k in mine:
+            a, b = state.get(k), mine[k]
+            if torch.is_tensor(a) or torch.is_tensor(b):
+                same = torch.is_tensor(a) and torch.is_tensor(b) and a.shape == b.shape and torch.equal(a.cpu(), b.cpu())
+            else:
+                same = a == b
+            if not same:
+                raise ValueError(f"TrainStep.load_state_dict: the state was saved with {k} = {a!r}, this step has {k} = {b!r}")
 
     def load_state_dict(self, state: dict) -> None:
         """Restore what state_dict returned into the EXISTING buffers, in place: addresses do not change, so .grad views and captured
@@ -305,6 +354,7 @@ class TrainStep:
             raise ValueError(f"TrainStep.load_state_dict: state version {state.get('version') if isinstance(state, dict) else None!r}, this class reads version {self.STATE_VERSION}")
         if state["operands"] != self._vit.operands:
             raise ValueError(f"TrainStep.load_state_dict: the state was saved on {state['operands']} operands, this model runs on {self._vit.operands}")
+        self._check_objective_state(state)
         opt.check_fused_state(state)
         for what, saved, mine in (("a dynamic loss scale", state["scaler"], self.scaler), ("a weight average (ema_decay)", state["ema"], self.ema)):
             if (saved is None) != (mine is None):
@@ -345,7 +395,10 @@ class TrainStep:
             return False
         if any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None) for m in self._all_modules):
             return False
-        if not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 1 and labels.shape[0] == fmri.shape[0]):
+        if self.objective == "regression":
+            if not (torch.is_tensor(labels) and labels.is_cuda and labels.dim() in (1, 2) and labels.shape[0] == fmri.shape[0]):
+                return False
+        elif not (torch.is_tensor(labels) and labels.is_cuda and labels.dtype == torch.int64 and labels.dim() == 1 and labels.shape[0] == fmri.shape[0]):
             return False
         vit = self._vit
         if vit.fp8_training and vit._fp8 is not None:
@@ -358,7 +411,7 @@ class TrainStep:
                 return False
         return True
 
-    def _native_call(self, fmri, labels, step: int, accumulate=False, update=False, fuse=0, dp=None, lo=None):
+    def _native_call(self, fmri, labels, step: int, accumulate=False, update=False, fuse=0, dp=None, lo=None, ro=None):
         """vit._rt.train_step on the model's arenas and the optimizer's moments with group 0's hyper-parameters: the one place that
         forms its arguments, for the eager step and for the capture of _graph_step.  Returns (loss [1], logits)."""
         vit, opt = self._vit, self.optimizer
@@ -371,7 +424,8 @@ class TrainStep:
         return vit._rt.train_step(video, labels, vit._arena, vit._shadow, vit.gradient_arena(), m, v, step=step, lr=g0["lr"], betas=g0["betas"],
                                   eps=g0["eps"], weight_decay=g0["weight_decay"], grad_scale=1.0, accumulate=accumulate, update=update,
                                   fuse_update=fuse, dropout=drop, loss_scale=self.static_scale,
-                                  loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo, drop_path=table)
+                                  loss_scale_state=None if self.scaler is None else self.scaler.state, dp=dp, loss_opts=lo, drop_path=table,
+                                  reg_opts=ro)
 
     def _after_native(self, logits, fuse: int = 0) -> None:
         """what follows the native call or its replay: the outputs, and .grad as views of the gradient arena (once; they stay valid)"""
@@ -439,15 +493,26 @@ class TrainStep:
             crit.to(labels.device)
         return ops.loss_opts(crit.label_smoothing, crit.weight, mix, labels.shape[0], self._vit._cfg.num_classes, labels.device)
 
+    def _reg_opts(self, targets, mix):
+        """(targets as the kernels read them - fp32 [B, K] -, _cabi.RegOpts of this step)"""
+        from . import ops
+        crit, K = self.criterion, self._vit._cfg.num_classes
+        targets = ops.reg_targets(targets, targets.shape[0], K)
+        return targets, ops.reg_opts(crit.kind, crit.delta, crit.target_mean, crit.target_std, crit.weight, mix, targets.shape[0], K, targets.device)
+
     def _native_step(self, fmri: torch.Tensor, labels: torch.Tensor, mix: Optional[torch.Tensor] = None) -> torch.Tensor:
         vit, opt = self._vit, self.optimizer
         if vit._attend_backward_hooked_layers():
             # (_native_ok routes a hooked model to the general path, whose backward fires the hooks; the one-call step has no place to)
             raise NotImplementedError("neurovit_amd.TrainStep: the native one-call step exports no attention gradients - backward hooks on "
                                       "`attend` need the general path (forward + backward through autograd)")
-        lo = self._loss_opts(labels, mix)
+        ro = None
+        if self.objective == "regression":          # (planned like a step with loss options: never replayed from a graph)
+            lo, (labels, ro) = None, self._reg_opts(labels, mix)
+        else:
+            lo = self._loss_opts(labels, mix)
         # (a positive stochastic-depth rate counts as live dropout: the table is drawn per step from the step's seed, nothing a replay could carry)
-        plan = self._plan(fmri.shape[0] * vit.pos_embedding.shape[1], vit._dropout_p != (0.0, 0.0) or vit.drop_path_rate > 0, lo is not None)
+        plan = self._plan(fmri.shape[0] * vit.pos_embedding.shape[1], vit._dropout_p != (0.0, 0.0) or vit.drop_path_rate > 0, lo is not None or ro is not None)
         got = self._graph_step(fmri, labels) if plan.graph_ok else None
         if got is not None:
             return got
@@ -459,7 +524,7 @@ class TrainStep:
         self.last_path = "native" if dp is None else "native-dp"
         # the first micro-step of a window overwrites the gradients (zero_grad(set_to_none=True), Trainer.py:72), the others add
         loss, logits = self._native_call(fmri, labels.contiguous(), step=opt.steps + 1, accumulate=self._micro > 0, update=update,
-                                         fuse=plan.fuse, dp=dp, lo=lo)
+                                         fuse=plan.fuse, dp=dp, lo=lo, ro=ro)
         if update:
             opt.begin_step()                # (after the call: a refused step leaves the counter where it was)
         self._after_native(logits, plan.fuse)
@@ -622,6 +687,12 @@ class Trainer:
       * TRAINING_OBJECTIVE: "mim" (with PRETRAIN_MASK_RATIO / _MASK_UNIT / _LOSS / _NORM_PIX) pre-trains the 3D encoder on the volumes alone
         (pretrain.MaskedPretrainStep): labels are ignored, `validate` reports the reconstruction loss under fixed masks, and `run` writes
         recon-head-e{N}.pth beside model-e{N}.pth, which loads into a NeuroEncoder for fine-tuning.  Absent: the labelled step.
+      * TRAINING_OBJECTIVE: "regression" (with REGRESSION_TARGETS / _TARGET_MEAN / _TARGET_STD, read by the model, and REGRESSION_LOSS /
+        _HUBER_DELTA / _TARGET_INDEX, read here) trains the head on continuous targets (nn.RegressionLoss; NaN = missing): the targets come
+        from batch[REGRESSION_TARGET_INDEX] (default -2: `age` in both ADNI tuples), `train` logs train_mae on the raw scale in the place of
+        the accuracy, `validate` reports val_loss, MAE, RMSE, Pearson r and R^2 (ops.RegressionMetrics: one host read per epoch) - also for
+        the weight average -, `evaluate_samples` returns the mean absolute error and (subject, prediction, actual) per sample.  Mixup /
+        CutMix blend the targets; TRAINING_LABEL_SMOOTHING / TRAINING_CLASS_WEIGHTS do not go with it.
     """
 
     def __init__(self, config, model, dataset_train, dataset_val):
@@ -638,14 +709,16 @@ class Trainer:
             kw["prefetch_factor"] = 2
         self.dataloader = torch.utils.data.DataLoader(self.data, shuffle=True, **kw)
         self.val_dataloader = torch.utils.data.DataLoader(self.val_data, shuffle=False, **kw)
+        self.regression = self.regression_from_config(config)          # None: the classifier's loss, as ever
         smoothing, class_weights = self.loss_options_from_config(config)
         self.criterion = CrossEntropyLoss(weight=class_weights)          # validation: never smoothed, never mixed; it carries the class weights
+        objective = {} if self.regression is None else self._regression_setup(model)
         self.save_state, self.resume_from = self.state_options_from_config(config)
         self.pretrain = self.objective_from_config(config)             # None: the supervised step, as ever
         if self.pretrain is None:
             self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
                                   max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights,
-                                  **self.ema_from_config(config),
+                                  **self.ema_from_config(config), **objective,
                                   **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
         else:
             self.step = self._pretrain_step(config, model)
@@ -677,16 +750,45 @@ class Trainer:
         result is its arguments from PRETRAIN_MASK_RATIO (default 0.6), PRETRAIN_MASK_UNIT (1), PRETRAIN_LOSS ("l1") and
         PRETRAIN_NORM_PIX (true), checked here (pretrain.check_mask_options)"""
         objective = config.get('TRAINING_OBJECTIVE', None)
-        if objective is None or objective == "supervised":
+        if objective is None or objective in ("supervised", "regression"):      # ("regression": the labelled step with another loss - regression_from_config)
             return None
         if objective != "mim":
-            raise ValueError(f"TRAINING_OBJECTIVE must be 'supervised' or 'mim', got {objective!r}")
+            raise ValueError(f"TRAINING_OBJECTIVE must be 'supervised', 'regression' or 'mim', got {objective!r}")
         from .pretrain import check_mask_options
         pick = lambda key, default: default if config.get(key, None) is None else config[key]
         out = dict(mask_ratio=pick('PRETRAIN_MASK_RATIO', 0.6), mask_unit=pick('PRETRAIN_MASK_UNIT', 1), loss=pick('PRETRAIN_LOSS', "l1"),
                    norm_pix=pick('PRETRAIN_NORM_PIX', True))
         check_mask_options(config['TRAINING_VIT_INPUT_SIZE'] // config['TRAINING_VIT_PATCH_SIZE'], **out)
         return out
+
+    @staticmethod
+    def regression_from_config(config):
+        """TRAINING_OBJECTIVE "regression": dict(kind, delta, index) from REGRESSION_LOSS ("mse" default, "l1", "huber"), REGRESSION_HUBER_DELTA
+        (1.0) and REGRESSION_TARGET_INDEX - the batch element that holds the targets, default -2 (`age` in both ADNI tuples; the Pain
+        tuple needs -3).  Anything else: None.  What belongs to the classifier's loss does not go with it (ValueError)."""
+        if config.get('TRAINING_OBJECTIVE', None) != "regression":
+            return None
+        clash = [k for k in ('TRAINING_CLASS_WEIGHTS',) if config.get(k, None) is not None] + [k for k in ('TRAINING_LABEL_SMOOTHING',) if config.get(k, None)]
+        if clash:
+            raise ValueError("TRAINING_OBJECTIVE 'regression' does not go with " + ", ".join(clash))
+        pick = lambda key, default: default if config.get(key, None) is None else config[key]
+        kind, delta, index = pick('REGRESSION_LOSS', "mse"), pick('REGRESSION_HUBER_DELTA', 1.0), pick('REGRESSION_TARGET_INDEX', -2)
+        from . import ops
+        ops.reg_opts(kind, delta)                      # (the checks that need no device)
+        if isinstance(index, bool) or not isinstance(index, int):
+            raise TypeError(f"REGRESSION_TARGET_INDEX must be an integer, got {index!r}")
+        return dict(kind=kind, delta=float(delta), index=index)
+
+    def _regression_setup(self, model) -> dict:
+        """TrainStep's arguments of the regression objective, and this shell's own loss (validation: never mixed) and metrics"""
+        from .ops import RegressionMetrics
+        if not getattr(model, "is_regression", False):
+            raise ValueError("TRAINING_OBJECTIVE 'regression': the model was built without that key (its head is a classifier's)")
+        enc, reg = model.volume_encoder, self.regression
+        self.criterion = RegressionLoss(reg["kind"], reg["delta"], target_mean=enc.target_mean, target_std=enc.target_std).to(self.device)
+        self.targets = enc.target_mean.numel()
+        self.metrics = RegressionMetrics(self.targets, enc.target_mean, enc.target_std, self.device) if torch.device(self.device).type == "cuda" else None
+        return dict(objective="regression", regression_loss=reg["kind"], huber_delta=reg["delta"], target_mean=enc.target_mean, target_std=enc.target_std)
 
     def _pretrain_step(self, config, model):
         """The step of TRAINING_OBJECTIVE "mim".  What belongs to the labelled objective does not go with it (ValueError): Mixup / CutMix,
@@ -862,9 +964,8 @@ class Trainer:
             return None
         return check_max_norm(value)
 
-    @staticmethod
-    def _unpack(batch):
-        return batch[2], batch[-1]
+    def _unpack(self, batch):
+        return batch[2], batch[-1 if self.regression is None else self.regression["index"]]
 
     def _log(self, payload):
         if self._wandb is not None:
@@ -926,6 +1027,8 @@ class Trainer:
         import time
         if self.pretrain is not None:
             return self._train_pretrain(epoch)
+        if self.regression is not None:
+            return self._train_regression(epoch)
         self.model.train()
         running_loss, correct, total = 0.0, 0, 0
         start_time = time.time()
@@ -955,6 +1058,105 @@ class Trainer:
                 correct, total, running_loss = 0, 0, 0.0
                 start_time = time.time()
 
+    def _raw_abs_error(self, outputs, target):
+        """(sum of |prediction - target| on the raw scale over the observed cells, their count): device tensors, no sync"""
+        enc = self.model.volume_encoder
+        target = target.to(outputs.device, torch.float32).reshape(outputs.shape[0], -1)
+        seen = torch.isfinite(target)
+        err = (outputs.float() * enc.target_std + enc.target_mean - torch.where(seen, target, torch.zeros_like(target))).abs()
+        return torch.where(seen, err, torch.zeros_like(err)).sum(), seen.sum()
+
+    def _train_regression(self, epoch):
+        """`train` under TRAINING_OBJECTIVE "regression": the same loop with the targets of REGRESSION_TARGET_INDEX, and train_mae - the mean
+        absolute error on the raw scale, from the step's own outputs (under Mixup / CutMix: against the unmixed targets), kept on the device
+        until a log line - in the place of the accuracy"""
+        import time
+        self.model.train()
+        running_loss, abs_err, seen = 0.0, 0.0, 0
+        start_time = time.time()
+        for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):
+            fMRI, target = self._unpack(batch)
+            if self.mix is not None:
+                fMRI = self.mix(fMRI, step=self.global_step, augment=self.augment)
+            elif self.augment is not None:
+                fMRI = self.augment(fMRI, step=self.global_step)
+            self.global_step += 1
+            loss = self.step(fMRI, target) if self.mix is None else self.step(fMRI, target, mix=self.mix.last_mix)
+            running_loss = running_loss + loss
+            with torch.no_grad():
+                e, n = self._raw_abs_error(self.step.last_outputs, target)
+                abs_err, seen = abs_err + e, seen + n
+            if i != 0 and i % self.log_interval == 0:
+                avg_loss, mae = round(float(running_loss) / self.log_interval, 5), round(float(abs_err) / max(1, int(seen)), 5)
+                lr, duration = round(self.step.last_lr, 5), time.time() - start_time
+                print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| train_loss: {avg_loss:.5f}\t| train_mae: {mae:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
+                payload = {"epoch": epoch, "batch": i, "train_loss": avg_loss, "train_mae": mae, "learning_rate": lr, "duration": duration}
+                if self.step.last_grad_norm is not None:
+                    payload["grad_norm"] = float(self.step.last_grad_norm)
+                self._log(payload)
+                self.train_mae = mae
+                running_loss, abs_err, seen = 0.0, 0.0, 0
+                start_time = time.time()
+
+    def _evaluate_regression(self, model):
+        """{"val_loss", "mae", "rmse", "r", "r2" (lists of K), "n"} of `model` over the validation set: the loss and the metrics accumulate on
+        the device (ops.RegressionMetrics), ONE host read at the end"""
+        if self.metrics is None:
+            raise RuntimeError("Trainer: the regression metrics run on the MI355X (cuda) device - there is no CPU fallback")
+        model.eval()
+        self.metrics.reset()
+        total, i = torch.zeros((), device=self.device), 0
+        with torch.no_grad(), model.precision(self.validation_precision):
+            for i, batch in enumerate(self.val_dataloader):
+                fMRI, target = self._unpack(batch)
+                fMRI, target = self._center(fMRI.to(self.device)), target.to(self.device)
+                outputs = model(fMRI).float()
+                total = total + self.criterion(outputs, target)
+                self.metrics.update(outputs, target)
+            got = torch.cat([self.metrics.compute_device().flatten(), total.reshape(1)]).cpu()      # the one host read
+        table = got[:-1].reshape(self.targets, 6)
+        out = {"val_loss": round(float(got[-1]) / max(1, len(self.val_dataloader)), 5), "batches": i}
+        for col, name in enumerate(("n", "mae", "rmse", "bias", "r", "r2")):
+            out[name] = [round(float(v), 5) for v in table[:, col]]
+        return out
+
+    def _validate_regression(self, epoch):
+        """`validate` under TRAINING_OBJECTIVE "regression": val_loss, MAE, RMSE, Pearson r and R^2 per target on the raw scale, for the model
+        and - when there is one - for its weight average"""
+        result = None
+        models = [("", self.model)] + ([("_ema", self.step.ema.module)] if self.step.ema is not None and self.validate_ema else [])
+        for tag, model in models:
+            got = self._evaluate_regression(model)
+            one = lambda v: v[0] if len(v) == 1 else v
+            print(f"[VALIDATION] epoch {epoch}\t| total_batch {got['batches']}\t| val_loss{tag} {got['val_loss']:.5f}\t| val_mae{tag} {one(got['mae'])}\t| "
+                  f"val_rmse{tag} {one(got['rmse'])}\t| val_r{tag} {one(got['r'])}\t| val_r2{tag} {one(got['r2'])}")
+            self._log({"epoch": epoch, **{f"val_{k}{tag}": (got[k] if k == "val_loss" else one(got[k])) for k in ("val_loss", "mae", "rmse", "r", "r2")}})
+            if tag:
+                self.val_loss_ema, self.val_metrics_ema = got["val_loss"], got
+            else:
+                self.val_loss, self.val_metrics = got["val_loss"], got
+                result = (got["val_loss"], got["mae"])
+        return result
+
+    def _evaluate_samples_regression(self):
+        """(mean absolute error over the observed targets, [(subject, prediction, actual)] per sample) on the raw scale"""
+        self.model.eval()
+        loader = torch.utils.data.DataLoader(self.val_data, batch_size=1, shuffle=False, num_workers=self.num_workers)
+        rows, total, seen = [], 0.0, 0
+        with self.model.precision(self.validation_precision):
+            for batch in loader:
+                fMRI, target = self._unpack(batch)
+                prediction = self.model.predict(self._center(fMRI.to(self.device)))[0].cpu().tolist()
+                actual = target.to(torch.float32).reshape(-1).tolist()
+                for p, a in zip(prediction, actual):
+                    if a == a and abs(a) != float("inf"):
+                        total, seen = total + abs(p - a), seen + 1
+                one = lambda v: v[0] if len(v) == 1 else v
+                rows.append((batch[0][0] if isinstance(batch[0], (list, tuple)) else batch[0], one(prediction), one(actual)))
+        mae = total / max(1, seen)
+        print(f"Mean absolute error: {mae:.4f}")
+        return mae, rows
+
     def _evaluate(self, model):
         """(rounded mean loss, rounded accuracy, index of the last batch) of `model` over the validation set"""
         model.eval()
@@ -972,6 +1174,8 @@ class Trainer:
     def validate(self, epoch):
         if self.pretrain is not None:
             return self._validate_pretrain(epoch)
+        if self.regression is not None:
+            return self._validate_regression(epoch)
         avg_val_loss, accuracy, i = self._evaluate(self.model)
         self.val_loss = avg_val_loss
         print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss {avg_val_loss:.5f}\t| val_accuracy {accuracy:.5f}")
@@ -985,6 +1189,8 @@ class Trainer:
         return avg_val_loss, accuracy
 
     def evaluate_samples(self):
+        if self.regression is not None:
+            return self._evaluate_samples_regression()
         self.model.eval()
         loader = torch.utils.data.DataLoader(self.val_data, batch_size=1, shuffle=False, num_workers=self.num_workers)
         accuracy, wrong = 0, []
@@ -1010,3 +1216,20 @@ def class_weights_from_counts(counts):
         raise ValueError(f"class_weights_from_counts: counts must be positive and finite, got {counts!r}")
     total, C = sum(counts), len(counts)
     return [total / (C * c) for c in counts]
+
+
+def target_stats(values):
+    """(mean, std) of regression targets per column, formed in double and ignoring NaN (missing) - what REGRESSION_TARGET_MEAN / _STD and
+    TrainStep's target_mean / target_std are usually set to.  values: [N] or [N, K]; the population std (ddof = 0); two lists of K floats."""
+    v = torch.as_tensor(values, dtype=torch.float64)
+    v = v.reshape(-1, 1) if v.dim() == 1 else v
+    if v.dim() != 2 or v.numel() == 0:
+        raise ValueError(f"target_stats: values must be [N] or [N, K], got {tuple(v.shape)}")
+    seen = ~torch.isnan(v)
+    n = seen.sum(dim=0)
+    if bool((n == 0).any()):
+        raise ValueError("target_stats: a target column has no observed value")
+    clean = torch.where(seen, v, torch.zeros_like(v))
+    mean = clean.sum(dim=0) / n
+    var = (torch.where(seen, v - mean, torch.zeros_like(v)) ** 2).sum(dim=0) / n
+    return mean.tolist(), var.sqrt().tolist()
