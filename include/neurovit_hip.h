@@ -1237,6 +1237,55 @@ int nv_vit_train_step_reg(const nv_vit_config* cfg, int B, const float* video, c
 int nv_reg_metrics_update(const float* pred, const float* target, int B, int K, const float* mean, const float* std, double* state, void* stream);
 int nv_reg_metrics_finish(const double* state, int K, float* out, void* stream);
 
+/* (added within revision 8 - new symbols only, nothing existing changes) frozen-feature evaluation: pooled features of the encoder, a fused
+ * similarity + top-k search over a feature bank, the weighted k-nearest-neighbour vote and per-segment (per-subject) means.  Every call takes
+ * a stream, reads nothing back and uses no atomics; every sum has one fixed order, so results are bit-identical from run to run.
+ * nv_pool_features: tokens fp32 [B, n, d], sample b at tokens + b * batch_stride, token row t at + t * row_stride (both in floats, row_stride
+ *   >= d) -> row row0 + b of out fp32 [*, ldo] (a preallocated bank is filled in place).  NV_POOL_CLS: row 0, copied.  NV_POOL_MEAN: the mean of
+ *   all n rows with the bits of nv_token_mean (fp32 partial sums over the rows t = g, g + 4, ..., g < 4; ((p0 + p1) + (p2 + p3)) / n).
+ *   NV_POOL_PATCH_MEAN: the mean of the rows 1 .. n - 1 (n >= 2), summed in double in ascending row order, divided in double, rounded once.
+ *   normalize != 0: F.normalize's rule on the pooled fp32 row x: ss = sum x_c^2 in double in ascending column order,
+ *   out_c = fp32(x_c / max(sqrt(ss), 1e-12)) formed in double.  d <= 8192.
+ * nv_knn_topk: for every row of Q fp32 [Nq, d] (ldq) the k (1 .. 128) rows of bank fp32 [Nb, d] (ldb) with the largest dot product; d, ldq, ldb
+ *   multiples of 4, Q and bank 16-byte aligned (as nv_gemm_f32).  INPUTS MUST BE FINITE: a NaN or an infinite similarity has no defined place in
+ *   the order.  idx int32 [Nq, k], sim fp32 [Nq, k], best first.  Order: larger sim first; equal sim (compared as floats, -0 == +0) to the
+ *   LOWER bank index.  q_group int32 [Nq] and b_group int32 [Nb] (both or neither): bank row j is skipped for query q when q_group[q] >= 0 and
+ *   q_group[q] == b_group[j].  With fewer than k eligible rows the remaining slots hold idx -1, sim -inf.  The similarities run on
+ *   v_mfma_f32_16x16x4_f32 in fp32 end to end; the Nq x Nb matrix is never written.  splits (0 = automatic, up to 64): the bank's 64-row tiles
+ *   are divided over that many workgroups per query tile and a second launch merges their lists under the same order; a dot product's
+ *   accumulation order depends on d alone, so every bit of sim and idx is independent of the split count.  More than one split needs a workspace
+ *   of nv_knn_topk_workspace_bytes(Nq, Nb, k, splits) bytes (0 for one split); nv_knn_topk_splits returns the count that splits = 0 resolves to
+ *   (0 for arguments nv_knn_topk refuses).
+ * nv_knn_vote: idx / sim [Nq, kmax] as nv_knn_topk wrote them, the first k <= kmax slots of each row are used.  Weights: NV_KNN_UNIFORM 1, or
+ *   NV_KNN_SOFTMAX w_i = expf((sim_i - sim_0) / temperature) (exp(sim / T) made overflow safe: the ratios are unchanged).  A slot is ignored when
+ *   idx is outside [0, Nb) (the -1 of an empty slot).  Give labels or targets, not both:
+ *   labels int32 [Nb] in [0, C) (any other label: that neighbour is ignored): scores fp32 [Nq, C] = class-wise weight sums / total, summed in
+ *   double over i = 0 .. k - 1 in that order; pred int32 [Nq] = arg-max of the double scores, ties to the lower class.  No usable neighbour:
+ *   scores 0, pred -1.
+ *   targets fp32 [Nb, K]: pred_reg fp32 [Nq, K] = the weighted mean per column over the neighbours whose target is not NaN (the missing-value
+ *   marker of nv_reg_loss), in double; NaN when there is none.
+ * nv_segment_mean: out[g] (fp32 [G, w], ldo) = the mean of the rows src[order[p]] (fp32 [N, w], lds), offsets[g] <= p < offsets[g + 1], summed
+ *   in double in that order and rounded once; an empty segment gives zeros.  order int32 [N] and offsets int32 [G + 1] are DEVICE arrays of a
+ *   CSR the caller built on the host; nv_segment_csr_check validates the HOST copies (offsets from 0, non-decreasing, at most N; every order
+ *   entry in [0, N)) - NV_ERR_ARG otherwise.  The kernel skips an entry outside [0, N) anyway: nothing is read through an unchecked index.
+ *   G <= 65535 per call. */
+#define NV_POOL_CLS 0
+#define NV_POOL_MEAN 1
+#define NV_POOL_PATCH_MEAN 2
+#define NV_KNN_UNIFORM 0
+#define NV_KNN_SOFTMAX 1
+#define NV_KNN_MAX_K 128
+int nv_pool_features(const float* tokens, long batch_stride, long row_stride, int B, int n, int d, int mode, int normalize, float* out, long ldo,
+                     long row0, void* stream);
+int nv_knn_topk_splits(int Nq, int Nb, int splits);
+long nv_knn_topk_workspace_bytes(int Nq, int Nb, int k, int splits);
+int nv_knn_topk(const float* Q, long ldq, int Nq, const float* bank, long ldb, int Nb, int d, int k, const int* q_group, const int* b_group,
+                int splits, int* idx, float* sim, void* workspace, long ws_bytes, void* stream);
+int nv_knn_vote(const int* idx, const float* sim, int Nq, int kmax, int k, int weighting, float temperature, int Nb, const int* labels, int C,
+                float* scores, int* pred, const float* targets, int K, float* pred_reg, void* stream);
+int nv_segment_csr_check(const int* order, const int* offsets, int N, int G);
+int nv_segment_mean(const float* src, long lds, int N, int w, const int* order, const int* offsets, int G, float* out, long ldo, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

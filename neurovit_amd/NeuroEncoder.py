@@ -175,6 +175,19 @@ class NeuroEncoder(nn.Module):
         with torch.no_grad():
             return self(x).float() * enc.target_std + enc.target_mean
 
+    def extract_features(self, x, pool=None, normalize=False, out=None, row0=0):
+        """x [B, H, W, D] -> fp32 [B, dim]: one frozen embedding per volume (ViT.forward_features behind this encoder's permute: the eval-mode
+        forward of the encoder's eval_precision, no graph, no .grad touched).  pool None = the model's own pooling, "cls", "mean" or
+        "patch_mean"; normalize = F.normalize's rule; out / row0 fill rows of a preallocated bank (features.FeatureBank).  3D model only: the
+        4D model's per-volume "encoding" is its two logits, not an embedding."""
+        if self.config['TRAINING_DIM'] != 3:
+            raise NotImplementedError("NeuroEncoder.extract_features: 3D model only - the 4D model's per-volume encoding is two logits, not an "
+                                      "embedding; extract features with its (3D) volume encoder's checkpoint")
+        if x.dim() != 4:
+            raise ValueError(f"NeuroEncoder.extract_features: expected volumes [B, H, W, D], got {tuple(x.shape)}")
+        volume = x.to(self.device)
+        return self.volume_encoder.vit3d.forward_features(volume.permute(0, 3, 1, 2).unsqueeze(1), pool=pool, normalize=normalize, out=out, row0=row0)
+
     def precision(self, mode: str):
         """Context manager: eval-mode no-grad forwards of the ViT3D encoder inside it run in `mode` ("bf16" / "fp16": the 16-bit
         operand path in the encoder's operand format, or "fp32")."""

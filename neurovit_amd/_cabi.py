@@ -105,6 +105,11 @@ REG_METRIC_SLOTS = 9                                        # NV_REG_METRIC_SLOT
 REG_METRIC_NAMES = ("n", "mae", "rmse", "bias", "r", "r2")  # the columns nv_reg_metrics_finish writes
 
 
+POOL_MODES = {"cls": 0, "mean": 1, "patch_mean": 2}         # NV_POOL_CLS / NV_POOL_MEAN / NV_POOL_PATCH_MEAN
+KNN_WEIGHTS = {"uniform": 0, "softmax": 1}                  # NV_KNN_UNIFORM / NV_KNN_SOFTMAX
+KNN_MAX_K = 128                                             # NV_KNN_MAX_K
+
+
 DROP_PATH_SCHEDULES = {"linear": 0, "constant": 1}          # NV_DROP_PATH_LINEAR / NV_DROP_PATH_CONSTANT
 
 

@@ -322,10 +322,10 @@ class VitRuntime(PassLedger):
 
     # ------------------------------------------------------------------ fp32 inference (the reference's fp32 validate, Trainer.py:101-118)
     def forward_f32(self, video: torch.Tensor, params: torch.Tensor, vol_sigma=None, time_points: int = 0,
-                    attn_export: Optional[AttnExport] = None) -> torch.Tensor:
+                    attn_export: Optional[AttnExport] = None, rows_form: Optional[int] = None) -> torch.Tensor:
         """Inference forward with every operand in fp32 (weights straight from the fp32 arena, contractions on the fp32 MFMA):
         logits within 1e-5 of the reference's CPU fp32 forward instead of the bf16 path's 1e-3 ... 7e-3.  Eval mode only."""
-        return self._forward("nv_vit_forward_f32", video, 2, (params.data_ptr(),), vol_sigma=vol_sigma, time_points=time_points,
+        return self._forward("nv_vit_forward_f32", video, 2, (params.data_ptr(),), vol_sigma=vol_sigma, time_points=time_points, rows_form=rows_form,
                              attn_export=attn_export, operands=False)[1]     # (no 16-bit operand anywhere: the format is left as it is)
 
     # ------------------------------------------------------------------ fp8 inference (BASELINE.json configs[4])

@@ -1,0 +1,242 @@
+"""Frozen-feature evaluation of the encoder: a bank of embeddings, the weighted k-nearest-neighbour probe (DINO's classifier) over it and
+subject-level pooling, on the native kernels of csrc/features.hip (ops.pool_features / knn_topk / knn_vote / segment_mean).
+
+    bank = FeatureBank(dim, capacity=len(train_set)).fill(model, train_loader)
+    out = knn_evaluate(bank, val_features, labels=val_labels, k=(5, 10, 20), query_groups=val_subjects)
+
+The similarity is the plain dot product of the stored rows: extract with normalize=True (the default here) for cosine similarity.  The volumes
+of one subject are near-duplicates: give the bank its rows' subjects (`groups`) and the queries theirs (`query_groups`, the same ids) and no
+query is answered by its own subject; scores are also reported per subject.  PyTorch owns the buffers; every FLOP of extraction, search, vote
+and pooling runs in libneurovit_hip.so.  There is no CPU fallback."""
+from __future__ import annotations
+
+from typing import Callable, Dict, Optional, Sequence, Tuple, Union
+
+import torch
+
+from . import ops
+
+
+def _extract(model, x, **kw) -> torch.Tensor:
+    """model.extract_features (NeuroEncoder: x [B, H, W, D]) or model.forward_features (ViT: x [B, C, F, H, W])"""
+    fn = getattr(model, "extract_features", None) or getattr(model, "forward_features", None)
+    if fn is None:
+        raise TypeError(f"{type(model).__name__} has neither extract_features nor forward_features")
+    return fn(x, **kw)
+
+
+def _host_ids(groups, n: int, what: str) -> torch.Tensor:
+    """integer ids [n] as an int32 HOST tensor (subject ids are host data: the CSR of a segment mean is built from them without a device read)"""
+    g = torch.as_tensor(groups)
+    if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool or g.numel() != n:
+        raise ValueError(f"{what}: {n} integer ids expected, got {tuple(g.shape)} {g.dtype}")
+    return g.detach().reshape(-1).to("cpu", torch.int32)
+
+
+class GroupIndex:
+    """Subjects (any hashable: the strings a dataset yields, ints) -> dense integer ids, shared by a bank and its queries."""
+
+    def __init__(self):
+        self.ids: Dict[object, int] = {}
+
+    def __call__(self, subjects) -> torch.Tensor:
+        if torch.is_tensor(subjects):
+            subjects = subjects.reshape(-1).tolist()
+        return torch.tensor([self.ids.setdefault(s, len(self.ids)) for s in subjects], dtype=torch.int32)
+
+    def __len__(self):
+        return len(self.ids)
+
+
+class FeatureBank:
+    """Preallocated device bank: `features` fp32 [capacity, dim], `labels` int32 [capacity] (-1 = none), `targets` fp32 [capacity, K] (NaN =
+    missing; allocated by num_targets) and `groups` int32 [capacity] (-1 = none), of which the first `size` rows are filled.  append() writes
+    the model's features straight into their rows (no cat); the host copy of the groups is kept for by_group()."""
+
+    def __init__(self, dim: int, capacity: int, device="cuda", num_targets: int = 0):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("FeatureBank lives on the MI355X (cuda) device - there is no CPU fallback")
+        if dim < 4 or dim % 4 or capacity < 1:
+            raise ValueError(f"FeatureBank: dim = {dim} must be a positive multiple of 4 (nv_knn_topk), capacity = {capacity} at least 1")
+        self.dim, self.capacity, self.size = int(dim), int(capacity), 0
+        self.features = torch.zeros((capacity, dim), dtype=torch.float32, device=self.device)
+        self.labels = torch.full((capacity,), -1, dtype=torch.int32, device=self.device)
+        self.targets = torch.full((capacity, num_targets), float("nan"), dtype=torch.float32, device=self.device) if num_targets else None
+        self.groups = torch.full((capacity,), -1, dtype=torch.int32, device=self.device)
+        self._host_groups = torch.full((capacity,), -1, dtype=torch.int32)
+        self.has_groups = False
+
+    @classmethod
+    def from_features(cls, features: torch.Tensor, labels=None, targets=None, groups=None) -> "FeatureBank":
+        """a full bank around features fp32 [N, dim] that exist already (copied)"""
+        N, dim = features.shape
+        bank = cls(dim, N, features.device, num_targets=0 if targets is None else targets.shape[1])
+        bank.features.copy_(features)
+        bank._annotate(0, N, labels, groups, targets)
+        bank.size = N
+        return bank
+
+    def _annotate(self, row0: int, B: int, labels, groups, targets) -> None:
+        if labels is not None:
+            self.labels[row0:row0 + B] = torch.as_tensor(labels).reshape(-1).to(self.device, torch.int32)
+        if targets is not None:
+            if self.targets is None:
+                raise ValueError("FeatureBank: built without targets - pass num_targets")
+            self.targets[row0:row0 + B] = torch.as_tensor(targets, dtype=torch.float32).reshape(B, -1).to(self.device)
+        if groups is not None:
+            g = _host_ids(groups, B, "FeatureBank groups")
+            self._host_groups[row0:row0 + B] = g
+            self.groups[row0:row0 + B] = g.to(self.device)
+            self.has_groups = True
+
+    def append(self, model, x, labels=None, groups=None, targets=None, pool=None, normalize: bool = True) -> torch.Tensor:
+        """The features of the batch x into the next rows (the extraction writes them in place: out / row0); returns those rows."""
+        B = x.shape[0]
+        if self.size + B > self.capacity:
+            raise ValueError(f"FeatureBank: {self.size} + {B} rows exceed the capacity {self.capacity}")
+        rows = _extract(model, x, pool=pool, normalize=normalize, out=self.features, row0=self.size)
+        self._annotate(self.size, B, labels, groups, targets)
+        self.size += B
+        return rows
+
+    def fill(self, model, loader, unpack: Optional[Callable] = None, transform: Optional[Callable] = None, pool=None, normalize: bool = True,
+             group_index: Optional[GroupIndex] = None) -> "FeatureBank":
+        """append() over a loader.  unpack(batch) -> (x, labels or None, subjects or None, targets or None); the default reads the dataset's
+        batches (subject first, volume third, label last).  transform: applied to x on the device (the Trainer's centre window).
+        group_index: maps the subjects to ids (shared with the queries); without one, integer subjects are taken as they are."""
+        unpack = unpack or (lambda b: (b[2], b[-1], b[0], None))
+        for batch in loader:
+            x, labels, subjects, targets = unpack(batch)
+            x = x.to(self.device)
+            if transform is not None:
+                x = transform(x)
+            groups = None if subjects is None else (group_index(subjects) if group_index is not None else subjects)
+            self.append(model, x, labels, groups, targets, pool=pool, normalize=normalize)
+        return self
+
+    def view(self) -> torch.Tensor:
+        return self.features[:self.size]
+
+    def by_group(self, normalize: bool = True) -> "FeatureBank":
+        """The subject-level bank: one row per group id 0 .. G - 1 = the mean of its rows' features (nv_segment_mean; re-normalised by default,
+        a group without rows stays zero), the label / targets of its first row, groups = arange."""
+        if not self.has_groups or self.size == 0:
+            raise ValueError("FeatureBank.by_group: the bank has no groups")
+        hg = self._host_groups[:self.size]
+        order, offsets = ops.segment_csr(hg)
+        G = offsets.numel() - 1
+        out = FeatureBank(self.dim, G, self.device, num_targets=0 if self.targets is None else self.targets.shape[1])
+        ops.segment_mean(self.view(), order, offsets, out=out.features)
+        if normalize:
+            ops.pool_features(out.features.view(G, 1, self.dim), "cls", True, out=out.features)
+        first = order[offsets[:-1].clamp(max=self.size - 1).long()].long()
+        filled = (offsets[1:] > offsets[:-1])
+        out.labels.copy_(torch.where(filled, self.labels[first], torch.full_like(self.labels[first], -1)))
+        if self.targets is not None:
+            out.targets.copy_(torch.where(filled[:, None], self.targets[first], torch.full_like(self.targets[first], float("nan"))))
+        out._annotate(0, G, None, torch.arange(G, dtype=torch.int32), None)
+        out.size = G
+        return out
+
+
+def _ks(k) -> Tuple[int, ...]:
+    ks = (int(k),) if isinstance(k, int) else tuple(int(v) for v in k)
+    if not ks or min(ks) < 1 or max(ks) > 128:
+        raise ValueError(f"k = {k!r}: one or several values in [1, 128]")
+    return ks
+
+
+def knn_predict(bank: FeatureBank, queries: torch.Tensor, k: Union[int, Sequence[int]] = 20, temperature: float = 0.07, weights: str = "softmax",
+                query_groups=None, task: str = "classification", num_classes: Optional[int] = None, splits: int = 0):
+    """The weighted kNN prediction of queries fp32 [Nq, dim] against the bank: one nv_knn_topk pass at max(k), one nv_knn_vote per k.
+    Returns (predictions, scores, idx, sim), device tensors: classification - predictions int32 [Nq] (-1: no usable neighbour), scores fp32
+    [Nq, C]; regression - predictions fp32 [Nq, K], scores None; for several k, predictions and scores are dicts {k: tensor}.  idx int32 / sim fp32
+    [Nq, max(k)], best first (equal sim to the lower bank row, unfilled slots -1 / -inf).  query_groups (ids as the bank's groups): a bank row of
+    the query's own group is never a neighbour.  num_classes: default the bank's largest label + 1 (one host read - pass it to avoid that)."""
+    if task not in ("classification", "regression"):
+        raise ValueError(f"knn_predict: task must be 'classification' or 'regression', got {task!r}")
+    if bank.size < 1:
+        raise ValueError("knn_predict: the bank is empty")
+    ks = _ks(k)
+    qg = bg = None
+    if query_groups is not None:
+        if not bank.has_groups:
+            raise ValueError("knn_predict: query_groups given, but the bank has no groups")
+        qg = _host_ids(query_groups, queries.shape[0], "query_groups").to(queries.device)
+        bg = bank.groups[:bank.size]
+    idx, sim = ops.knn_topk(queries, bank.view(), max(ks), qg, bg, splits=splits)
+    preds, scores = {}, {}
+    for kk in ks:
+        if task == "classification":
+            C = int(num_classes) if num_classes is not None else int(bank.labels[:bank.size].max().item()) + 1
+            scores[kk], preds[kk] = ops.knn_vote(idx, sim, kk, labels=bank.labels[:bank.size], num_classes=C, weights=weights, temperature=temperature)
+        else:
+            if bank.targets is None:
+                raise ValueError("knn_predict: a regression vote needs a bank with targets")
+            preds[kk], scores[kk] = ops.knn_vote(idx, sim, kk, targets=bank.targets[:bank.size], weights=weights, temperature=temperature), None
+    if isinstance(k, int):
+        return preds[ks[0]], scores[ks[0]], idx, sim
+    return preds, (scores if task == "classification" else None), idx, sim
+
+
+def knn_evaluate(bank: FeatureBank, queries: torch.Tensor, labels=None, targets=None, k: Union[int, Sequence[int]] = 20, temperature: float = 0.07,
+                 weights: str = "softmax", query_groups=None, num_classes: Optional[int] = None, splits: int = 0) -> dict:
+    """knn_predict plus its score against the truth; one host read at the end.  labels int [Nq] -> {"acc": {k: float}} per volume and, with
+    query_groups, {"subject_acc": {k: float}}: the volumes' scores averaged per subject (nv_segment_mean), arg-max, against the label of the
+    subject's first volume.  targets fp32 [Nq, K] (NaN = missing) -> {"mae": {k: [K floats]}} through ops.RegressionMetrics (raw scale), and
+    "subject_mae" likewise on the per-subject means of predictions and targets.  Also returns the device tensors under "predictions", "scores",
+    "idx", "sim" (of every k)."""
+    if (labels is None) == (targets is None):
+        raise ValueError("knn_evaluate: give labels (classification) or targets (regression), one of the two")
+    ks = _ks(k)
+    task = "classification" if labels is not None else "regression"
+    preds, scores, idx, sim = knn_predict(bank, queries, ks, temperature, weights, query_groups, task, num_classes, splits)
+    Nq, dev = queries.shape[0], queries.device
+    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, Nq, "query_groups"))
+    out = {"predictions": preds, "scores": scores, "idx": idx, "sim": sim}
+    if task == "classification":
+        y = torch.as_tensor(labels).reshape(-1).to(dev, torch.int32)
+        cells = [(preds[kk] == y).float().mean() for kk in ks]
+        if csr is not None:
+            order, offsets = csr
+            filled = offsets[1:] > offsets[:-1]
+            y_subject = y[order[offsets[:-1].clamp(max=Nq - 1).long()].long()]
+            for kk in ks:
+                pooled = ops.segment_mean(scores[kk], order, offsets)
+                best, cls = pooled.max(dim=1)
+                cls = torch.where(best > 0, cls.to(torch.int32), torch.full_like(y_subject, -1))
+                cells.append(((cls == y_subject) & filled).float().sum() / filled.float().sum().clamp(min=1))
+        host = torch.stack(cells).cpu().tolist()                 # the one host read
+        out["acc"] = dict(zip(ks, host[:len(ks)]))
+        if csr is not None:
+            out["subject_acc"] = dict(zip(ks, host[len(ks):]))
+        return out
+    t = ops.reg_targets(targets, Nq, bank.targets.shape[1]).to(dev)
+    K = t.shape[1]
+    tables = []
+    for kk in ks:
+        m = ops.RegressionMetrics(K, device=dev)
+        m.update(preds[kk], t)
+        tables.append(m.compute_device())
+    if csr is not None:
+        order, offsets = csr
+        t_subject = _nanmean_segments(t, order, offsets)
+        for kk in ks:
+            m = ops.RegressionMetrics(K, device=dev)
+            m.update(_nanmean_segments(preds[kk], order, offsets), t_subject)
+            tables.append(m.compute_device())
+    host = torch.stack(tables).cpu()                              # the one host read
+    out["mae"] = {kk: host[i, :, 1].tolist() for i, kk in enumerate(ks)}
+    if csr is not None:
+        out["subject_mae"] = {kk: host[len(ks) + i, :, 1].tolist() for i, kk in enumerate(ks)}
+    return out
+
+
+def _nanmean_segments(values: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """per-segment mean over the cells that are not NaN (NaN where a segment has none): two nv_segment_mean calls, on the values with zeros
+    for the missing cells and on the observed-cell mask"""
+    seen = ~torch.isnan(values)
+    total = ops.segment_mean(torch.where(seen, values, torch.zeros_like(values)), order, offsets)
+    share = ops.segment_mean(seen.float(), order, offsets)
+    return torch.where(share > 0, total / share.clamp(min=1e-30), torch.full_like(total, float("nan")))

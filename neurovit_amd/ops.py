@@ -1534,3 +1534,111 @@ def drop_path_draw(seed: int, B: int, depth: int, rate: float, schedule: str = "
     assert out.shape == (depth, 2, B) and out.dtype == torch.float32 and out.is_contiguous()
     check(lib.nv_drop_path_draw(int(seed), int(B), int(depth), float(rate), _cabi.DROP_PATH_SCHEDULES[schedule], _p(out), _stream()), "nv_drop_path_draw")
     return out
+
+
+# ---- frozen-feature evaluation (features.hip): pooled features, the fused similarity + top-k search, the kNN vote, per-segment means
+def _i32(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _need_cuda(t)
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 [{n}] tensor on the device")
+    return t
+
+
+def pool_features(tokens: torch.Tensor, mode, normalize: bool = False, *, out: Optional[torch.Tensor] = None, row0: int = 0) -> torch.Tensor:
+    """nv_pool_features: tokens f32 [B, n, d] (any batch / row stride, last stride 1) -> rows row0 .. row0 + B of `out` f32 [*, d] (any row
+    stride; a fresh [B, d] when None).  mode "cls" | "mean" | "patch_mean" (or 0 / 1 / 2).  Returns the B rows written."""
+    _need_cuda(tokens)
+    assert tokens.dtype == torch.float32 and tokens.dim() == 3 and tokens.stride(2) == 1
+    B, n, d = tokens.shape
+    if out is None:
+        out, row0 = torch.empty((B, d), dtype=torch.float32, device=tokens.device), 0
+    _need_cuda(out)
+    assert out.dtype == torch.float32 and out.dim() == 2 and out.shape[1] == d and out.stride(1) == 1
+    if row0 < 0 or row0 + B > out.shape[0]:
+        raise ValueError(f"pool_features: rows {row0} .. {row0 + B} do not fit an output of {out.shape[0]} rows")
+    mode = _cabi.POOL_MODES[mode] if isinstance(mode, str) else int(mode)
+    check(lib.nv_pool_features(_p(tokens), tokens.stride(0), tokens.stride(1), B, n, d, mode, int(bool(normalize)), _p(out), out.stride(0), int(row0),
+                               _stream()), "nv_pool_features")
+    return out[row0:row0 + B]
+
+
+def knn_topk(Q: torch.Tensor, bank: torch.Tensor, k: int, q_group: Optional[torch.Tensor] = None, b_group: Optional[torch.Tensor] = None, splits: int = 0):
+    """nv_knn_topk: the k rows of bank f32 [Nb, d] with the largest dot product for every row of Q f32 [Nq, d] (row-strided views pass their
+    leading dimension; d and both strides multiples of 4).  Larger sim first, equal sim to the lower bank index; bank row j is skipped for
+    query q when q_group[q] >= 0 and q_group[q] == b_group[j] (int32, both or neither); unfilled slots are (-1, -inf).  splits: 0 = automatic.
+    Returns (idx int32 [Nq, k], sim f32 [Nq, k])."""
+    _need_cuda(Q, bank)
+    assert Q.dtype == torch.float32 and bank.dtype == torch.float32 and Q.dim() == 2 and bank.dim() == 2 and Q.stride(1) == 1 and bank.stride(1) == 1
+    (Nq, d), Nb = Q.shape, bank.shape[0]
+    if bank.shape[1] != d:
+        raise ValueError(f"knn_topk: the queries have {d} columns, the bank {bank.shape[1]}")
+    if (q_group is None) != (b_group is None):
+        raise ValueError("knn_topk: q_group and b_group are given together or not at all")
+    q_group, b_group = _i32(q_group, Nq, "q_group"), _i32(b_group, Nb, "b_group")
+    idx = torch.empty((Nq, k), dtype=torch.int32, device=Q.device)
+    sim = torch.empty((Nq, k), dtype=torch.float32, device=Q.device)
+    nb = lib.nv_knn_topk_workspace_bytes(Nq, Nb, int(k), int(splits))
+    ws = torch.empty(nb, dtype=torch.uint8, device=Q.device) if nb else None
+    check(lib.nv_knn_topk(_p(Q), Q.stride(0), Nq, _p(bank), bank.stride(0), Nb, d, int(k), _p(q_group), _p(b_group), int(splits), _p(idx), _p(sim),
+                          _p(ws), nb, _stream()), "nv_knn_topk")
+    return idx, sim
+
+
+def knn_vote(idx: torch.Tensor, sim: torch.Tensor, k: int, *, labels: Optional[torch.Tensor] = None, num_classes: int = 0,
+             targets: Optional[torch.Tensor] = None, weights: str = "softmax", temperature: float = 0.07):
+    """nv_knn_vote over the first k slots of idx / sim [Nq, kmax].  labels int32 [Nb] + num_classes -> (scores f32 [Nq, C], pred int32 [Nq]);
+    targets f32 [Nb, K] -> pred f32 [Nq, K] (neighbours with a NaN target are left out per column)."""
+    _need_cuda(idx, sim)
+    assert idx.dtype == torch.int32 and sim.dtype == torch.float32 and idx.shape == sim.shape and idx.is_contiguous() and sim.is_contiguous()
+    Nq, kmax = idx.shape
+    if weights not in _cabi.KNN_WEIGHTS:
+        raise ValueError(f"knn_vote: weights must be 'softmax' or 'uniform', got {weights!r}")
+    w = _cabi.KNN_WEIGHTS[weights]
+    if (labels is None) == (targets is None):
+        raise ValueError("knn_vote: give labels (classification) or targets (regression), one of the two")
+    if labels is not None:
+        labels = _i32(labels, labels.numel(), "labels")
+        scores = torch.empty((Nq, int(num_classes)), dtype=torch.float32, device=idx.device)
+        pred = torch.empty(Nq, dtype=torch.int32, device=idx.device)
+        check(lib.nv_knn_vote(_p(idx), _p(sim), Nq, kmax, int(k), w, float(temperature), labels.numel(), _p(labels), int(num_classes), _p(scores), _p(pred),
+                              None, 0, None, _stream()), "nv_knn_vote")
+        return scores, pred
+    _need_cuda(targets)
+    assert targets.dtype == torch.float32 and targets.dim() == 2 and targets.is_contiguous()
+    Nb, K = targets.shape
+    pred = torch.empty((Nq, K), dtype=torch.float32, device=idx.device)
+    check(lib.nv_knn_vote(_p(idx), _p(sim), Nq, kmax, int(k), w, float(temperature), Nb, None, 0, None, None, _p(targets), K, _p(pred), _stream()), "nv_knn_vote")
+    return pred
+
+
+def segment_csr(groups, num_segments: Optional[int] = None):
+    """Host CSR of integer segment ids (a sequence or a tensor; a negative id = in no segment), validated by nv_segment_csr_check and uploaded:
+    (order int32 [N], offsets int32 [G + 1]) on the current device.  The rows of a segment keep their ascending order."""
+    g = torch.as_tensor(groups).detach().to("cpu", torch.int64).reshape(-1)
+    N = g.numel()
+    G = int(num_segments) if num_segments is not None else (int(g.max().item()) + 1 if N else 0)
+    if N < 1 or G < 1 or int(g.max().item()) >= G:
+        raise ValueError(f"segment_csr: {N} rows, {G} segments, largest id {int(g.max().item()) if N else None}")
+    keep = torch.nonzero(g >= 0).reshape(-1)
+    srt = torch.sort(g[keep], stable=True)
+    order = torch.zeros(N, dtype=torch.int32)
+    order[:keep.numel()] = keep[srt.indices].to(torch.int32)
+    offsets = torch.zeros(G + 1, dtype=torch.int32)
+    offsets[1:] = torch.cumsum(torch.bincount(srt.values, minlength=G), 0).to(torch.int32)
+    check(lib.nv_segment_csr_check(order.data_ptr(), offsets.data_ptr(), N, G), "nv_segment_csr_check")
+    return order.cuda(), offsets.cuda()
+
+
+def segment_mean(src: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nv_segment_mean: out[g] = mean of the rows src[order[offsets[g] : offsets[g + 1]]] of src f32 [N, w] (a row-strided view passes its leading
+    dimension), summed in double in that order; an empty segment gives zeros.  order / offsets: device int32, from segment_csr."""
+    _need_cuda(src, order, offsets)
+    assert src.dtype == torch.float32 and src.dim() == 2 and src.stride(1) == 1
+    N, w = src.shape
+    G = offsets.numel() - 1
+    order, offsets = _i32(order, N, "order"), _i32(offsets, G + 1, "offsets")
+    out = _out2d(out, G, w, torch.float32, src)
+    check(lib.nv_segment_mean(_p(src), src.stride(0), N, w, _p(order), _p(offsets), G, _p(out), out.stride(0), _stream()), "nv_segment_mean")
+    return out

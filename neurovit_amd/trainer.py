@@ -722,6 +722,7 @@ class Trainer:
                                   **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
         else:
             self.step = self._pretrain_step(config, model)
+        self.knn = self.knn_from_config(config)                        # None: no kNN validation beside the pretraining loss, as ever
         self.validate_ema = bool(config.get('VALIDATION_EMA', True))
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
@@ -1021,7 +1022,93 @@ class Trainer:
         self.val_loss = round(float(total) / max(1, len(self.val_dataloader)), 5)
         print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_recon_loss {self.val_loss:.5f}")
         self._log({"epoch": epoch, "val_recon_loss": self.val_loss})
+        if self.knn is not None and (epoch + 1) % self.knn["every"] == 0:
+            self.knn_validate(epoch)
         return self.val_loss, None
+
+    # ------------------------------------------------------------------ frozen-feature kNN validation (neurovit_amd.features)
+    @staticmethod
+    def knn_from_config(config) -> Optional[dict]:
+        """PRETRAIN_KNN_EVERY (epochs; absent, None or 0 = off: nothing changes), PRETRAIN_KNN_K (one k or a list, default 20),
+        PRETRAIN_KNN_TEMPERATURE (default 0.07), PRETRAIN_KNN_POOL (default "patch_mean": the cls token of a masked-pretrained encoder was
+        never trained) -> {"every", "k", "temperature", "pool"} or None.  The kNN pass itself is Trainer.knn_validate."""
+        every = config.get('PRETRAIN_KNN_EVERY', None)
+        if every is None or (not isinstance(every, bool) and every == 0):
+            return None
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"PRETRAIN_KNN_EVERY must be a positive number of epochs, got {every!r}")
+        return dict(every=every, **Trainer.knn_options_from_config(config))
+
+    @staticmethod
+    def knn_options_from_config(config) -> dict:
+        k = config.get('PRETRAIN_KNN_K', 20)
+        ks = [k] if isinstance(k, int) and not isinstance(k, bool) else list(k)
+        if not ks or any(isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 128 for v in ks):
+            raise ValueError(f"PRETRAIN_KNN_K must be an integer or a list of integers in [1, 128], got {k!r}")
+        temperature = float(config.get('PRETRAIN_KNN_TEMPERATURE', 0.07))
+        if not temperature > 0:
+            raise ValueError(f"PRETRAIN_KNN_TEMPERATURE must be positive, got {temperature!r}")
+        pool = config.get('PRETRAIN_KNN_POOL', 'patch_mean')
+        if pool not in (None, 'cls', 'mean', 'patch_mean'):
+            raise ValueError(f"PRETRAIN_KNN_POOL must be 'cls', 'mean', 'patch_mean' or None (the model's own pooling), got {pool!r}")
+        return dict(k=tuple(ks), temperature=temperature, pool=pool)
+
+    def _knn_features(self, dataset, index, opts):
+        """A FeatureBank of the centre windows of `dataset` in eval mode (features L2-normalised): labels or regression targets from the
+        batches, groups from their subjects when they carry any (a list of names or an integer vector in front of the volume)."""
+        from .features import FeatureBank
+        loader = torch.utils.data.DataLoader(dataset, batch_size=self.batch_size, shuffle=False, num_workers=self.num_workers)
+        bank, grouped = None, True
+        for batch in loader:
+            fMRI, truth = self._unpack(batch)
+            subjects = batch[0] if len(batch) >= 3 else None
+            if torch.is_tensor(subjects) and (subjects.dim() != 1 or subjects.is_floating_point()):
+                subjects = None
+            grouped = grouped and subjects is not None
+            x = self._center(fMRI.to(self.device))
+            if bank is None:
+                K = 0 if self.regression is None else truth.reshape(x.shape[0], -1).shape[1]
+                bank = FeatureBank(self.model.volume_encoder.vit3d.pos_embedding.shape[2], len(dataset), self.device, num_targets=K)
+            bank.append(self.model, x, labels=truth if self.regression is None else None, groups=index(subjects) if grouped else None,
+                        targets=truth if self.regression is not None else None, pool=opts["pool"], normalize=True)
+        if bank is not None and not grouped:
+            bank.has_groups = False
+        return bank
+
+    def knn_validate(self, epoch=None) -> dict:
+        """Frozen-feature kNN validation, on demand for any 3D model and every PRETRAIN_KNN_EVERY epochs under TRAINING_OBJECTIVE "mim": a bank
+        of the training set's features (centre windows, eval mode, VALIDATION_PRECISION), queried with the validation set's; a training
+        volume of the query's own subject is never its neighbour.  Logs val_knn_acc (and val_knn_subject_acc when the batches carry
+        subjects), or val_knn_mae under a regression target; with several k the first listed carries the plain name, the others `_k<k>`."""
+        from .features import GroupIndex, knn_evaluate
+        opts = self.knn if self.knn is not None else self.knn_options_from_config(self.config)
+        was_training = self.model.training
+        self.model.eval()
+        index = GroupIndex()
+        try:
+            with self.model.precision(self.validation_precision):
+                bank = self._knn_features(self.data, index, opts)
+                val = self._knn_features(self.val_data, index, opts)
+        finally:
+            self.model.train(was_training)
+        groups = val._host_groups[:val.size] if (bank.has_groups and val.has_groups) else None
+        truth = dict(labels=val.labels[:val.size]) if self.regression is None else dict(targets=val.targets[:val.size])
+        got = knn_evaluate(bank, val.view(), k=opts["k"], temperature=opts["temperature"], query_groups=groups, **truth)
+        payload = {} if epoch is None else {"epoch": epoch}
+        for j, kk in enumerate(opts["k"]):
+            tag = "" if j == 0 else f"_k{kk}"
+            if self.regression is None:
+                payload[f"val_knn_acc{tag}"] = round(got["acc"][kk], 5)
+                if groups is not None:
+                    payload[f"val_knn_subject_acc{tag}"] = round(got["subject_acc"][kk], 5)
+            else:
+                mae = got["mae"][kk]
+                payload[f"val_knn_mae{tag}"] = round(mae[0], 5) if len(mae) == 1 else [round(v, 5) for v in mae]
+        print(f"[VALIDATION] epoch {epoch}\t| kNN on {bank.size} training volumes, k {list(opts['k'])}\t| " +
+              "\t| ".join(f"{name} {value}" for name, value in payload.items() if name != "epoch"))
+        self._log(payload)
+        self.val_knn = payload
+        return payload
 
     def train(self, epoch):
         import time

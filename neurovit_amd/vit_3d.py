@@ -1074,6 +1074,56 @@ class ViT(FlatArena, nn.Module):
             raise NotImplementedError("neurovit_amd.ViT: forward_tokens exports no attention gradients - remove the backward hooks on `attend`")
         return _ViTTokensFunction.apply(self, video.float(), need_grad, *self._plist)
 
+    # ------------------------------------------------------------------ frozen features (kNN probe, feature export: neurovit_amd.features)
+    @torch.no_grad()
+    def forward_features(self, video, pool=None, normalize=False, out=None, row0=0, time_points=0):
+        """video [B, C, F, H, W] -> fp32 [B, dim]: one embedding per volume, from the EVAL-mode forward of this model's `eval_precision`
+        (whatever self.training says; no dropout, no stochastic depth), under no_grad - no graph is recorded and no .grad is touched, on a
+        frozen or a trainable model.
+          pool       None = the model's own pooling: the vector mlp_head reads (its cls row, or nv_token_mean's mean of a pool='mean' model) -
+                     ops.head_fwd on it returns forward()'s logits bit for bit; "cls" | "mean" (all n rows) | "patch_mean" (the n - 1 patch
+                     rows: MAE's global pool, the feature of a masked-pretrained model whose cls token no loss ever touched).  A pooling
+                     that needs every row of the last block on a cls-pooled model runs that forward with rows_form=1.
+          normalize  F.normalize's rule (nv_pool_features)
+          out, row0  write rows row0 .. row0 + B of a preallocated fp32 [*, dim] bank instead of a fresh tensor; returns those rows
+        Refused (NotImplementedError): the fused 4D input form (time_points), the fp8 forwards (enable_fp8 with a 16-bit eval_precision -
+        disable_fp8() or precision("fp32")), and forward hooks on `attend` (they expect per-head attention maps this forward does not export)."""
+        if time_points:
+            raise NotImplementedError("neurovit_amd.ViT: forward_features takes [B, C, F, H, W] volumes, not the fused 4D input form (time_points) - "
+                                      "pass the [B*T, C, F, H, W] volumes")
+        if pool not in (None, "cls", "mean", "patch_mean"):
+            raise ValueError(f"neurovit_amd.ViT: forward_features pool must be None, 'cls', 'mean' or 'patch_mean', got {pool!r}")
+        self.check_video(video)
+        if self.eval_precision not in ("bf16", "fp16", "fp32"):
+            raise ValueError(f"neurovit_amd.ViT: eval_precision must be 'bf16', 'fp16' or 'fp32', got {self.eval_precision!r}")
+        if self._fp8 is not None and self.eval_precision != "fp32":
+            raise NotImplementedError("neurovit_amd.ViT: no features from the fp8 forwards (enable_fp8) - disable_fp8() first, or run under precision('fp32')")
+        if self._attend_hooked_layers():
+            raise NotImplementedError("neurovit_amd.ViT: forward_features exports no attention probabilities - remove the forward hooks on `attend` "
+                                      "(they expect per-head maps)")
+        mode = self.pool if pool is None else pool
+        rows_form = 1 if mode != "cls" else None                 # every row of the last block, or this runtime's default form
+        video = video.float()
+        if self.eval_precision == "fp32":
+            self._last_logits = self._rt.forward_f32(video, self._arena, rows_form=rows_form)
+        else:
+            self._refresh_shadow()
+            if self.fold_layernorm:
+                self._last_logits = self._rt.forward_lnfold(video, self._arena, self._shadow, self._fresh_fold(), rows_form=rows_form)
+            else:
+                self._last_logits = self._rt.forward(video, self._arena, self._shadow, training=False, rows_form=rows_form)
+        return ops.pool_features(self._last_tokens(), mode, normalize, out=out, row0=row0)
+
+    def _last_tokens(self) -> torch.Tensor:
+        """fp32 [B, n, dim] view of the last block's output in the workspace of the most recent INFERENCE forward (valid until the next one).
+        The inference layouts ping-pong a block's output between two buffers: an odd last block leaves it in x0."""
+        last = self._rt.last
+        n, d = self.pos_embedding.shape[1], self.pos_embedding.shape[2]
+        L = self._cfg.depth
+        if last.layout == 0 and (L - 1) & 1:
+            return self._rt.tap("x0", -1, (last.B, n, d), torch.float32)
+        return self._rt.tap("x2", L - 1, (last.B, n, d), torch.float32)
+
     def _run_forward_tokens(self, video):
         self._refresh_shadow()
         self._last_logits = self._rt.forward(video, self._arena, self._shadow, training=True, dropout=self.draw_dropout(), rows_form=1)
