@@ -1286,6 +1286,70 @@ int nv_knn_vote(const int* idx, const float* sim, int Nq, int kmax, int k, int w
 int nv_segment_csr_check(const int* order, const int* offsets, int N, int G);
 int nv_segment_mean(const float* src, long lds, int N, int w, const int* order, const int* offsets, int G, float* out, long ldo, void* stream);
 
+/* (added within revision 8 - new symbols and one new struct only, nothing existing changes) a linear probe over the frozen-feature bank: H
+ * heads (one per regularisation strength) trained side by side by full-batch Adam steps over ONE read of the features.  Every call takes a
+ * stream, reads nothing back and uses no atomics; every sum has one fixed order, so results are bit-identical from run to run.
+ *   X fp32 [N, d] (ldx);  z = (x - mean) * rstd, formed in fp32 on load, each operation rounded (mean == NULL: z = x; both or neither).
+ *   W fp32 [M, d] dense, b fp32 [M], M = H * C <= NV_PROBE_MAX_M; head h owns the columns [h C, (h + 1) C).  logit = W z + b on
+ *   v_mfma_f32_16x16x4_f32, in fp32 end to end.  FEATURES MUST BE FINITE (as nv_knn_topk): a NaN feature reaches every sum it is part of.
+ *   Cost of head h: J_h = L_h + (l2_h / 2) |W_h|^2, the bias is not penalised; the L2 term is COUPLED (it is part of the gradient, so the
+ *   stationary point is the penalised-likelihood optimum; regression: the ridge solution), not AdamW's decoupled decay.
+ *   NV_PROBE_CLASSIFICATION: labels int32 [N]; a row whose label lies outside [0, C) carries no loss and no gradient; p = fp32 softmax over the
+ *     head's own C columns (max-subtracted, expf, summed in ascending column order); c_i = class_weight[y_i] (fp32 [C]) or 1;
+ *     D = sum_i c_i over the labelled rows;  L_h = sum_i c_i (-log p_i,y_i) / D;  dL_h / dlogit_ik = c_i (p_ik - [k == y_i]) / D.
+ *   NV_PROBE_REGRESSION: targets fp32 [N, C] (C = the number of targets), the same targets for every head; t = (y - target_mean_k) /
+ *     target_std_k in fp32, each operation rounded (NULL: 0 / 1); a NaN target is missing (the marker of nv_reg_loss) and receives exactly
+ *     zero gradient; every target column is a problem of its own: D_k = its count of observed cells, L_h = sum_k sum_i (logit - t)^2 / D_k,
+ *     dL_h / dlogit_ik = 2 (logit - t) / D_k.
+ *   Nothing observed (D == 0): loss 0 and data gradient 0, not NaN - dW is then l2 W exactly.
+ * nv_probe_stats: per column of X (features must be finite unless skip_nan != 0: NaN cells are then left out of sums and counts - the
+ *   targets): mean, rstd = 1 / sqrt(var + eps) and (optional) std = sqrt(var) with the population variance, and count fp64 [d] (optional)
+ *   = the observed cells.  Two passes (sum, then squared deviations from the fp64 mean), in fp64, each operation rounded: per-column
+ *   partials over the row chunks [c NV_PROBE_CHUNK, (c + 1) NV_PROBE_CHUNK) in ascending row order, the chunk partials added in ascending
+ *   chunk order, every result rounded once to fp32.  A column whose variance is exactly 0 gets rstd = 0 (the feature drops out instead of
+ *   exploding on a query); a column without an observed cell gets mean 0, rstd 0, std 0.  X may be NULL (d = 0) when only denom is wanted.
+ *   labels != NULL: denom[0] (fp64) = D of the classification loss above, per-chunk partials in ascending row order, added in ascending chunk
+ *   order.  The regression denominators are `count` of the targets under skip_nan.  workspace: nv_probe_stats_workspace_bytes(N, d).
+ * nv_probe_grad: one pass over X: logits, per-head loss and dlogits, and the product dlogits^T Z from a 32-row tile of Z staged in LDS for
+ *   both products (X is read from memory once).  A workgroup keeps the [M, d] partial of a row chunk in accumulator registers over the
+ *   chunk's tiles and writes it once to the workspace; chunk c covers the rows [c NV_PROBE_CHUNK, (c + 1) NV_PROBE_CHUNK) whatever the grid
+ *   (max_blocks workgroups walk the chunks; 0 = one per chunk).  A second launch adds the chunk partials in ascending chunk order in fp64
+ *   and writes dW[m, j] = fp32(S / D + l2_h W[m, j]) (the product formed in fp64), db[m] = fp32(S_b / D) and loss[h] = fp32(L_h): every bit
+ *   is independent of the grid and of the CU count.  denom: fp64 [1] (classification) or fp64 [C] (regression), as nv_probe_stats wrote
+ *   them.  d a multiple of 4 in [4, NV_PROBE_MAX_D]; ldx >= d a multiple of 4; X, W, mean, rstd 16-byte aligned; NV_ERR_ARG otherwise.
+ *   workspace: nv_probe_grad_workspace_bytes(N, d, M) bytes (0 for arguments nv_probe_grad refuses).
+ * nv_probe_step: Adam on W, b and their moments from dW / db in one launch, every fp32 operation rounded on its own (no contraction):
+ *     m = b1 m + (1 - b1) g;  v = b2 v + ((1 - b2) g) g;  p = p - step_h (m / (sqrt(v) / bc2_sqrt + eps))
+ *   with step_h = fp32(lr_h / (1 - b1^t)), bc2_sqrt = fp32(sqrt(1 - b2^t)) and one_minus_b1 / one_minus_b2 formed by the host in fp64 and
+ *   passed as floats: bit-equal to the same torch fp32 expressions.
+ * nv_probe_predict: Q fp32 [Nq, d] (ldq) -> logits fp32 [Nq, M] (ldl) under mean / rstd, with the bits nv_probe_grad's logits have;
+ *   probs (optional, ldp): the fp32 softmax over each head's own C columns. */
+#define NV_PROBE_CHUNK 256
+#define NV_PROBE_MAX_M 32
+#define NV_PROBE_MAX_D 1024
+#define NV_PROBE_CLASSIFICATION 0
+#define NV_PROBE_REGRESSION 1
+typedef struct nv_probe_heads {
+  int struct_size;              /* sizeof(nv_probe_heads): checked */
+  int H;                        /* heads, >= 1 */
+  int C;                        /* columns per head (classes or targets), >= 1; H * C <= NV_PROBE_MAX_M */
+  float l2[NV_PROBE_MAX_M];     /* per head, >= 0: read by nv_probe_grad */
+  float step[NV_PROBE_MAX_M];   /* per head, lr_h / (1 - b1^t): read by nv_probe_step */
+} nv_probe_heads;
+long nv_probe_stats_workspace_bytes(int N, int d);
+int nv_probe_stats(const float* X, long ldx, int N, int d, int skip_nan, float eps, float* mean, float* rstd, float* std, double* count,
+                   const int* labels, int C, const float* class_weight, double* denom, void* workspace, long ws_bytes, void* stream);
+long nv_probe_grad_workspace_bytes(int N, int d, int M);
+int nv_probe_grad(const float* X, long ldx, int N, int d, const float* mean, const float* rstd, const float* W, const float* b,
+                  const nv_probe_heads* heads, int task, const int* labels, const float* class_weight, const float* targets,
+                  const float* target_mean, const float* target_std, const double* denom, float* dW, float* db, float* loss, int max_blocks,
+                  void* workspace, long ws_bytes, void* stream);
+int nv_probe_step(float* W, float* b, const float* dW, const float* db, float* mW, float* vW, float* mb, float* vb, int d,
+                  const nv_probe_heads* heads, float beta1, float beta2, float one_minus_b1, float one_minus_b2, float bc2_sqrt, float eps,
+                  void* stream);
+int nv_probe_predict(const float* Q, long ldq, int Nq, int d, const float* mean, const float* rstd, const float* W, const float* b, int H, int C,
+                     float* logits, long ldl, float* probs, long ldp, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

@@ -27,7 +27,7 @@ def __getattr__(name):
     if name in ("MaskedPretrainStep", "ReconstructionHead"):         # masked-volume pretraining of the 3D encoder
         from . import pretrain
         return getattr(pretrain, name)
-    if name in ("FeatureBank", "GroupIndex", "knn_predict", "knn_evaluate"):      # frozen-feature evaluation: the kNN probe of a (pre)trained encoder
+    if name in ("FeatureBank", "GroupIndex", "knn_predict", "knn_evaluate", "LinearProbe", "linear_evaluate"):      # frozen-feature evaluation: the kNN and the linear probe of a (pre)trained encoder
         from . import features
         return getattr(features, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -110,6 +110,17 @@ KNN_WEIGHTS = {"uniform": 0, "softmax": 1}                  # NV_KNN_UNIFORM / N
 KNN_MAX_K = 128                                             # NV_KNN_MAX_K
 
 
+PROBE_CHUNK, PROBE_MAX_M, PROBE_MAX_D = 256, 32, 1024     # NV_PROBE_CHUNK, NV_PROBE_MAX_M, NV_PROBE_MAX_D
+PROBE_TASKS = {"classification": 0, "regression": 1}        # NV_PROBE_CLASSIFICATION / NV_PROBE_REGRESSION
+
+
+class ProbeHeads(ctypes.Structure):
+    """struct nv_probe_heads (neurovit_hip.h, added within revision 8): the heads of a linear probe - H heads of C columns, the L2 strength per
+    head (nv_probe_grad) and the Adam step size lr / (1 - beta1^t) per head (nv_probe_step)."""
+    _fields_ = [("struct_size", ctypes.c_int), ("H", ctypes.c_int), ("C", ctypes.c_int), ("l2", ctypes.c_float * PROBE_MAX_M),
+                ("step", ctypes.c_float * PROBE_MAX_M)]
+
+
 DROP_PATH_SCHEDULES = {"linear": 0, "constant": 1}          # NV_DROP_PATH_LINEAR / NV_DROP_PATH_CONSTANT
 
 

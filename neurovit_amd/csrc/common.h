@@ -117,6 +117,9 @@ __device__ __forceinline__ f32x16 mfma32(r16x8 a, r16x8 b, f32x16 c) {
   if constexpr (__is_same(T, fp16_t)) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(V, a), __builtin_bit_cast(V, b), c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(V, a), __builtin_bit_cast(V, b), c, 0, 0, 0);
 }
+// v_mfma_f32_16x16x4_f32 (fp32 operands, not an XDL op): lane (i = lane & 15, g = lane >> 4) gives a = A[i][g] (A 16 x 4) and b = B[g][i]
+// (B 4 x 16); its register r holds D[4 g + r][i].  precise.hip, features.hip and probe.hip share this one spelling.
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // Host side: the operand format of this process (nv_set_operand_format, api.cpp) and the dispatch of a templated launch on it.
 extern "C" int nv_operand_format(void);

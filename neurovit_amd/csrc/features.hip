@@ -7,8 +7,6 @@
 
 namespace {
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
 // ------------------------------------------------------------------------------------------------ pooling
 // One workgroup per sample.  The pooled row goes through LDS (d floats) so that the normalisation can walk it in column order.
 //   mode 0: the cls row, copied.   mode 1: nv_token_mean's order - four partial sums over the rows t = g, g + 4, ... in fp32,

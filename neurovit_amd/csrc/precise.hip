@@ -22,8 +22,7 @@
 
 namespace {
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// v_mfma_f64_16x16x4_f64: A / B one value per lane as in the f32 form, but lane (col = lane & 15, g = lane >> 4) holds rows g + 4 r of the result (the f32
+// v_mfma_f64_16x16x4_f64: A / B one value per lane as in the f32 form (mfma4, common.h), but lane (col = lane & 15, g = lane >> 4) holds rows g + 4 r of the result (the f32
 // form: rows 4 g + r)
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ f64x4 mfma4d(double a, double b, f64x4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }

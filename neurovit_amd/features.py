@@ -1,5 +1,6 @@
-"""Frozen-feature evaluation of the encoder: a bank of embeddings, the weighted k-nearest-neighbour probe (DINO's classifier) over it and
-subject-level pooling, on the native kernels of csrc/features.hip (ops.pool_features / knn_topk / knn_vote / segment_mean).
+"""Frozen-feature evaluation of the encoder: a bank of embeddings, the weighted k-nearest-neighbour probe (DINO's classifier) over it,
+subject-level pooling (csrc/features.hip: ops.pool_features / knn_topk / knn_vote / segment_mean) and the linear probe (LinearProbe /
+linear_evaluate at the end of this file; csrc/probe.hip).
 
     bank = FeatureBank(dim, capacity=len(train_set)).fill(model, train_loader)
     out = knn_evaluate(bank, val_features, labels=val_labels, k=(5, 10, 20), query_groups=val_subjects)
@@ -66,6 +67,7 @@ class FeatureBank:
         self.groups = torch.full((capacity,), -1, dtype=torch.int32, device=self.device)
         self._host_groups = torch.full((capacity,), -1, dtype=torch.int32)
         self.has_groups = False
+        self.has_labels = False               # any label was given (what a classification LinearProbe asks for)
 
     @classmethod
     def from_features(cls, features: torch.Tensor, labels=None, targets=None, groups=None) -> "FeatureBank":
@@ -80,6 +82,7 @@ class FeatureBank:
     def _annotate(self, row0: int, B: int, labels, groups, targets) -> None:
         if labels is not None:
             self.labels[row0:row0 + B] = torch.as_tensor(labels).reshape(-1).to(self.device, torch.int32)
+            self.has_labels = True
         if targets is not None:
             if self.targets is None:
                 raise ValueError("FeatureBank: built without targets - pass num_targets")
@@ -136,6 +139,7 @@ class FeatureBank:
         if self.targets is not None:
             out.targets.copy_(torch.where(filled[:, None], self.targets[first], torch.full_like(self.targets[first], float("nan"))))
         out._annotate(0, G, None, torch.arange(G, dtype=torch.int32), None)
+        out.has_labels = self.has_labels
         out.size = G
         return out
 
@@ -240,3 +244,213 @@ def _nanmean_segments(values: torch.Tensor, order: torch.Tensor, offsets: torch.
     total = ops.segment_mean(torch.where(seen, values, torch.zeros_like(values)), order, offsets)
     share = ops.segment_mean(seen.float(), order, offsets)
     return torch.where(share > 0, total / share.clamp(min=1e-30), torch.full_like(total, float("nan")))
+
+
+# ---------------------------------------------------------------------------------------------------- the linear probe
+def _l2s(l2) -> Tuple[float, ...]:
+    vals = (float(l2),) if isinstance(l2, (int, float)) and not isinstance(l2, bool) else tuple(float(v) for v in l2)
+    if not vals or any(not (v >= 0.0) or v == float("inf") for v in vals):
+        raise ValueError(f"LinearProbe: l2 = {l2!r}: one or several finite values >= 0 (the coupled L2 strength of each head)")
+    return vals
+
+
+class LinearProbe:
+    """H linear read-outs of frozen features, one per L2 strength, trained side by side over ONE read of the bank per step (DINOv2's grid of
+    probes), on the native kernels of csrc/probe.hip (ops.probe_stats / probe_grad / probe_step / probe_predict).  Head h minimises
+    J_h = L_h + (l2_h / 2) |W_h|^2 (bias not penalised, the L2 term COUPLED - inside the gradient, not AdamW's decay) with full-batch Adam:
+    softmax cross-entropy over the bank's labels (rows labelled outside [0, C) carry no loss) or, with num_targets, the squared error on the
+    standardised targets (NaN = missing, every target column with its own count of observed cells).
+
+        probe = LinearProbe(bank.dim, num_classes=2).fit(bank)            # .history: the loss per step and head, a device tensor
+        out = linear_evaluate(probe, val_features, labels=val_labels, query_groups=val_subjects)
+
+    weight [H, C, dim] and bias [H, C] are views of the [H C, dim] / [H C] arrays the kernels step.  There is no sampling and no seed: a fit
+    is a pure function of the bank, bit for bit.  No CPU fallback."""
+
+    def __init__(self, dim: int, num_classes: Optional[int] = None, num_targets: Optional[int] = None, l2=(1e-4, 1e-3, 1e-2, 1e-1), device="cuda"):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("LinearProbe lives on the MI355X (cuda) device - there is no CPU fallback")
+        if (num_classes is None) == (num_targets is None):
+            raise ValueError("LinearProbe: give num_classes (classification) or num_targets (regression), one of the two")
+        if int(dim) < 4 or int(dim) % 4 or int(dim) > 1024:
+            raise ValueError(f"LinearProbe: dim = {dim} must be a multiple of 4 up to 1024 (nv_probe_grad)")
+        self.task = "classification" if num_classes is not None else "regression"
+        self.dim, self.C = int(dim), int(num_classes if num_classes is not None else num_targets)
+        if self.C < 1 or self.C > 32 or (self.task == "classification" and self.C < 2):
+            raise ValueError(f"LinearProbe: C = {self.C} columns per head: 2 .. 32 classes or 1 .. 32 targets (one nv_probe_grad pass holds 32 columns)")
+        self.l2 = _l2s(l2)
+        self.H = len(self.l2)
+        self._W = torch.zeros((self.H * self.C, self.dim), device=self.device)
+        self._b = torch.zeros(self.H * self.C, device=self.device)
+        self.weight, self.bias = self._W.view(self.H, self.C, self.dim), self._b.view(self.H, self.C)
+        self.mean = self.rstd = self.target_mean = self.target_std = None
+        self.history: Optional[torch.Tensor] = None
+
+    def _passes(self):
+        """head ranges of at most 32 columns each: one nv_probe_grad call per range and step"""
+        per = 32 // self.C
+        return [(h, min(h + per, self.H)) for h in range(0, self.H, per)]
+
+    def fit(self, bank: FeatureBank, steps: int = 500, lr: float = 0.01, schedule: str = "cosine", standardize: bool = True, class_weight=None,
+            task: Optional[str] = None, target_mean=None, target_std=None, betas=(0.9, 0.999), eps: float = 1e-8, max_blocks: int = 0) -> "LinearProbe":
+        """Full-batch Adam over bank.view() from zero weights: `steps` steps at lr_at(k) of LRSchedule(lr, steps, kind=schedule) (cosine to 0).
+        standardize: z = (x - mean) rstd with the bank's own column statistics (kept for predict).  class_weight: fp32 [C], classification only.
+        target_mean / target_std: [K] (default: the statistics of the bank's observed targets; a constant target column gets std 1).  Three
+        launches per step and pass, no host read; self.history: fp32 [steps, H] on the device."""
+        from .optim import LRSchedule
+        task = self.task if task is None else task
+        if task not in ("classification", "regression"):
+            raise ValueError(f"LinearProbe.fit: task must be 'classification' or 'regression', got {task!r}")
+        if task != self.task:
+            raise ValueError(f"LinearProbe.fit: this probe was built for {self.task} (num_classes / num_targets), not {task}")
+        if bank.size < 1:
+            raise ValueError("LinearProbe.fit: the bank is empty")
+        if bank.dim != self.dim:
+            raise ValueError(f"LinearProbe.fit: the bank's features have {bank.dim} columns, the probe {self.dim}")
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"LinearProbe.fit: steps = {steps!r} must be an integer >= 1")
+        N, X, C = bank.size, bank.view(), self.C
+        sched = LRSchedule(lr, steps, kind=schedule)
+        labels = targets = cw = None
+        if task == "classification":
+            if not bank.has_labels:
+                raise ValueError("LinearProbe.fit: a classification probe needs a bank with labels, this one was given none")
+            labels = bank.labels[:N]
+            if class_weight is not None:
+                cw = torch.as_tensor(class_weight, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+                if cw.numel() != C:
+                    raise ValueError(f"LinearProbe.fit: class_weight has {cw.numel()} entries for {C} classes")
+            denom = ops.probe_stats(labels=labels, num_classes=C, class_weight=cw)["denom"]
+        else:
+            if class_weight is not None:
+                raise ValueError("LinearProbe.fit: class_weight belongs to classification, not to regression")
+            if bank.targets is None or bank.targets.shape[1] != C:
+                raise ValueError(f"LinearProbe.fit: a regression probe of {C} targets needs a bank with targets [*, {C}]")
+            targets = bank.targets[:N]
+            st = ops.probe_stats(targets, skip_nan=True, eps=0.0)
+            denom = st["count"]
+            vec = lambda t: torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device).contiguous()
+            self.target_mean = st["mean"] if target_mean is None else vec(target_mean)
+            self.target_std = torch.where(st["std"] > 0, st["std"], torch.ones_like(st["std"])) if target_std is None else vec(target_std)
+            if self.target_mean.numel() != C or self.target_std.numel() != C:
+                raise ValueError(f"LinearProbe.fit: target_mean / target_std must have {C} entries")
+        self.mean = self.rstd = None
+        if standardize:
+            st = ops.probe_stats(X)
+            self.mean, self.rstd = st["mean"], st["rstd"]
+        self._W.zero_()
+        self._b.zero_()
+        self.history = torch.empty((steps, self.H), device=self.device)
+        for h0, h1 in self._passes():
+            rows = slice(h0 * C, h1 * C)
+            W, b = self._W[rows], self._b[rows]
+            dW, db = torch.empty_like(W), torch.empty_like(b)
+            mW, vW, mb, vb = torch.zeros_like(W), torch.zeros_like(W), torch.zeros_like(b), torch.zeros_like(b)
+            ws = torch.empty(ops.probe_grad_workspace_bytes(N, self.dim, W.shape[0]), dtype=torch.uint8, device=self.device)
+            for k in range(1, steps + 1):
+                sizes, _ = ops.probe_adam_constants(k, [sched.lr_at(k)] * (h1 - h0), betas)
+                heads = ops.probe_heads(h1 - h0, C, self.l2[h0:h1], sizes)
+                ops.probe_grad(X, W, b, heads, denom, labels=labels, targets=targets, mean=self.mean, rstd=self.rstd, class_weight=cw,
+                               target_mean=self.target_mean if targets is not None else None, target_std=self.target_std if targets is not None else None,
+                               max_blocks=max_blocks, out=(dW, db, self.history[k - 1, h0:h1]), workspace=ws)
+                ops.probe_step(W, b, dW, db, mW, vW, mb, vb, heads, k, betas, eps)
+        return self
+
+    def logits(self, queries: torch.Tensor, want_probs: bool = False):
+        """(logits fp32 [Nq, H C], probs or None): one nv_probe_predict per pass, written into its column window"""
+        Nq = queries.shape[0]
+        logits = torch.empty((Nq, self.H * self.C), device=self.device)
+        probs = torch.empty_like(logits) if want_probs else None
+        for h0, h1 in self._passes():
+            rows = slice(h0 * self.C, h1 * self.C)
+            ops.probe_predict(queries, self._W[rows], self._b[rows], h1 - h0, self.C, mean=self.mean, rstd=self.rstd, logits=logits[:, rows],
+                              probs=None if probs is None else probs[:, rows])
+        return logits, probs
+
+    def predict(self, queries: torch.Tensor, head: Optional[int] = None):
+        """Classification: (pred int32 [H, Nq], probs fp32 [H, Nq, C]) - the fp32 softmax over each head's own columns, arg-max with ties to
+        the lower class; regression: predictions on the RAW scale fp32 [H, Nq, K].  head = h: that head alone ([Nq], [Nq, C] / [Nq, K])."""
+        if head is not None and not 0 <= int(head) < self.H:
+            raise ValueError(f"LinearProbe.predict: head = {head} outside [0, {self.H})")
+        Nq = queries.shape[0]
+        logits, probs = self.logits(queries, want_probs=self.task == "classification")
+        if self.task == "classification":
+            probs = probs.view(Nq, self.H, self.C).permute(1, 0, 2).contiguous()
+            pred = probs.argmax(dim=2).to(torch.int32)
+            return (pred, probs) if head is None else (pred[head], probs[head])
+        raw = logits.view(Nq, self.H, self.C)
+        if self.target_std is not None:
+            raw = raw * self.target_std + self.target_mean
+        raw = raw.permute(1, 0, 2).contiguous()
+        return raw if head is None else raw[head]
+
+    def state_dict(self) -> dict:
+        out = dict(weight=self.weight.clone(), bias=self.bias.clone(), l2=torch.tensor(self.l2, dtype=torch.float64), task=self.task)
+        for name in ("mean", "rstd", "target_mean", "target_std"):
+            t = getattr(self, name)
+            out[name] = None if t is None else t.clone()
+        return out
+
+    def load_state_dict(self, state: dict) -> "LinearProbe":
+        if state["task"] != self.task or tuple(state["weight"].shape) != (self.H, self.C, self.dim):
+            raise ValueError(f"LinearProbe.load_state_dict: a {state['task']} probe of shape {tuple(state['weight'].shape)} does not fit this "
+                             f"{self.task} probe of shape {(self.H, self.C, self.dim)}")
+        self.weight.copy_(state["weight"])
+        self.bias.copy_(state["bias"])
+        self.l2 = tuple(float(v) for v in state["l2"].tolist())
+        for name in ("mean", "rstd", "target_mean", "target_std"):
+            t = state.get(name)
+            setattr(self, name, None if t is None else t.to(self.device, torch.float32).contiguous().clone())
+        return self
+
+
+def linear_evaluate(probe: LinearProbe, queries: torch.Tensor, labels=None, targets=None, query_groups=None) -> dict:
+    """LinearProbe.predict plus its score against the truth, per head, keyed by the head's l2; one host read at the end.  labels int [Nq] ->
+    {"acc": {l2: float}} per volume and, with query_groups, {"subject_acc": {l2: float}}: the volumes' probabilities averaged per subject
+    (nv_segment_mean), arg-max, against the label of the subject's first volume.  targets fp32 [Nq, K] (NaN = missing) -> {"mae": {l2: [K
+    floats]}} through ops.RegressionMetrics (raw scale) and "subject_mae" on the per-subject means of predictions and targets.  Also returns
+    the device tensors under "predictions" (and "probs")."""
+    if (labels is None) == (targets is None):
+        raise ValueError("linear_evaluate: give labels (classification) or targets (regression), one of the two")
+    if (labels is not None) != (probe.task == "classification"):
+        raise ValueError(f"linear_evaluate: a {probe.task} probe, but {'labels' if labels is not None else 'targets'} were given")
+    Nq, dev, H = queries.shape[0], queries.device, probe.H
+    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, Nq, "query_groups"))
+    if labels is not None:
+        pred, probs = probe.predict(queries)
+        out = {"predictions": pred, "probs": probs}
+        y = torch.as_tensor(labels).reshape(-1).to(dev, torch.int32)
+        cells = [(pred[h] == y).float().mean() for h in range(H)]
+        if csr is not None:
+            order, offsets = csr
+            filled = offsets[1:] > offsets[:-1]
+            y_subject = y[order[offsets[:-1].clamp(max=Nq - 1).long()].long()]
+            for h in range(H):
+                cls = ops.segment_mean(probs[h], order, offsets).argmax(dim=1).to(torch.int32)
+                cells.append(((cls == y_subject) & filled).float().sum() / filled.float().sum().clamp(min=1))
+        host = torch.stack(cells).cpu().tolist()                  # the one host read
+        out["acc"] = dict(zip(probe.l2, host[:H]))
+        if csr is not None:
+            out["subject_acc"] = dict(zip(probe.l2, host[H:]))
+        return out
+    raw = probe.predict(queries)
+    K = probe.C
+    t = ops.reg_targets(targets, Nq, K).to(dev)
+    tables = []
+    for h in range(H):
+        m = ops.RegressionMetrics(K, device=dev)
+        m.update(raw[h], t)
+        tables.append(m.compute_device())
+    if csr is not None:
+        order, offsets = csr
+        t_subject = _nanmean_segments(t, order, offsets)
+        for h in range(H):
+            m = ops.RegressionMetrics(K, device=dev)
+            m.update(_nanmean_segments(raw[h], order, offsets), t_subject)
+            tables.append(m.compute_device())
+    host = torch.stack(tables).cpu()                               # the one host read
+    out = {"predictions": raw, "mae": {l2: host[h, :, 1].tolist() for h, l2 in enumerate(probe.l2)}}
+    if csr is not None:
+        out["subject_mae"] = {l2: host[H + h, :, 1].tolist() for h, l2 in enumerate(probe.l2)}
+    return out

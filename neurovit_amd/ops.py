@@ -1642,3 +1642,150 @@ def segment_mean(src: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, 
     out = _out2d(out, G, w, torch.float32, src)
     check(lib.nv_segment_mean(_p(src), src.stride(0), N, w, _p(order), _p(offsets), G, _p(out), out.stride(0), _stream()), "nv_segment_mean")
     return out
+
+
+# ---- the linear probe over a feature bank (probe.hip): column statistics, the fused loss + gradient pass, the Adam step, the prediction
+def _f32(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _need_cuda(t)
+    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on the device")
+    return t
+
+
+def _probe_x(X: torch.Tensor, what: str):
+    _need_cuda(X)
+    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.shape[0] < 1:
+        raise ValueError(f"{what}: float32 [N, d] with N >= 1 and unit column stride expected, got {tuple(X.shape)} {X.dtype}")
+    return X.shape
+
+
+def probe_heads(H: int, C: int, l2=None, step=None) -> "_cabi.ProbeHeads":
+    """A _cabi.ProbeHeads: H heads of C columns (H * C <= 32), l2 and step per head (one value for all, a sequence, or None for zeros)."""
+    H, C = int(H), int(C)
+    if H < 1 or C < 1 or H * C > _cabi.PROBE_MAX_M:
+        raise ValueError(f"probe_heads: H = {H} heads of C = {C} columns: H * C must lie in [1, {_cabi.PROBE_MAX_M}]")
+    hd = _cabi.ProbeHeads(ctypes.sizeof(_cabi.ProbeHeads), H, C)
+    for name, vals in (("l2", l2), ("step", step)):
+        vals = [0.0] * H if vals is None else ([float(vals)] * H if isinstance(vals, (int, float)) else [float(v) for v in vals])
+        if len(vals) != H:
+            raise ValueError(f"probe_heads: {len(vals)} values of {name} for {H} heads")
+        if name == "l2" and any(not v >= 0 for v in vals):
+            raise ValueError(f"probe_heads: l2 must be >= 0, got {vals}")
+        for h, v in enumerate(vals):
+            getattr(hd, name)[h] = v
+    return hd
+
+
+def probe_stats(X: Optional[torch.Tensor] = None, *, skip_nan: bool = False, eps: float = 1e-12, labels: Optional[torch.Tensor] = None, num_classes: int = 0,
+                class_weight: Optional[torch.Tensor] = None) -> dict:
+    """nv_probe_stats.  X f32 [N, d] (a row-strided view passes its leading dimension) -> "mean", "rstd" = 1 / sqrt(var + eps) (0 where the
+    variance is exactly 0), "std" (f32 [d]) and "count" (f64 [d], the observed cells; skip_nan leaves NaN cells out); labels int32 [N] +
+    num_classes (+ class_weight f32 [C]) -> "denom" f64 [1], the class-weighted count of the rows whose label lies in [0, C).  Fixed
+    256-row chunks, fp64, ascending order: the bits do not depend on the device."""
+    if X is None and labels is None:
+        raise ValueError("probe_stats: give X, labels or both")
+    out, dev = {}, (X if X is not None else labels).device
+    N, d = (labels.numel(), 0) if X is None else _probe_x(X, "probe_stats")
+    if X is not None:
+        out = dict(mean=torch.empty(d, device=dev), rstd=torch.empty(d, device=dev), std=torch.empty(d, device=dev), count=torch.empty(d, dtype=torch.float64, device=dev))
+    if labels is not None:
+        labels = _i32(labels, N, "labels")
+        class_weight = _f32(class_weight, int(num_classes), "class_weight")
+        out["denom"] = torch.empty(1, dtype=torch.float64, device=dev)
+    nb = lib.nv_probe_stats_workspace_bytes(N, d)
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=dev)
+    check(lib.nv_probe_stats(_p(X), X.stride(0) if X is not None else 0, N, d, int(bool(skip_nan)), float(eps), _p(out.get("mean")), _p(out.get("rstd")),
+                             _p(out.get("std")), _p(out.get("count")), _p(labels), int(num_classes), _p(class_weight), _p(out.get("denom")), _p(ws), nb,
+                             _stream()), "nv_probe_stats")
+    return out
+
+
+def probe_grad_workspace_bytes(N: int, d: int, M: int) -> int:
+    """nv_probe_grad_workspace_bytes: the chunk partials of nv_probe_grad (0 for a shape it refuses)"""
+    return int(lib.nv_probe_grad_workspace_bytes(int(N), int(d), int(M)))
+
+
+def probe_grad(X: torch.Tensor, W: torch.Tensor, b: torch.Tensor, heads, denom: torch.Tensor, *, labels: Optional[torch.Tensor] = None,
+               targets: Optional[torch.Tensor] = None, mean: Optional[torch.Tensor] = None, rstd: Optional[torch.Tensor] = None,
+               class_weight: Optional[torch.Tensor] = None, target_mean: Optional[torch.Tensor] = None, target_std: Optional[torch.Tensor] = None,
+               max_blocks: int = 0, out=None, workspace: Optional[torch.Tensor] = None):
+    """nv_probe_grad: loss and gradient of the H heads of `heads` (probe_heads) over X f32 [N, d] in one pass: W f32 [M, d], b f32 [M], M = H C;
+    labels int32 [N] (classification; outside [0, C) = unlabelled) or targets f32 [N, C] (regression; NaN = missing); denom f64 [1] / [C] from
+    probe_stats.  Returns (dW f32 [M, d], db f32 [M], loss f32 [H]) - `out` = such a triple to write into (loss may be a row of a history)."""
+    N, d = _probe_x(X, "probe_grad")
+    H, C = heads.H, heads.C
+    M = H * C
+    if d % 4 or d > _cabi.PROBE_MAX_D:
+        raise ValueError(f"probe_grad: d = {d} must be a multiple of 4 up to {_cabi.PROBE_MAX_D}")
+    if (labels is None) == (targets is None):
+        raise ValueError("probe_grad: give labels (classification) or targets (regression), one of the two")
+    if (mean is None) != (rstd is None):
+        raise ValueError("probe_grad: mean and rstd are given together or not at all")
+    _need_cuda(W, b, denom)
+    if W.dtype != torch.float32 or tuple(W.shape) != (M, d) or not W.is_contiguous():
+        raise ValueError(f"probe_grad: W must be a contiguous float32 [{M}, {d}], got {tuple(W.shape)} {W.dtype}")
+    b, mean, rstd = _f32(b, M, "b"), _f32(mean, d, "mean"), _f32(rstd, d, "rstd")
+    if denom.dtype != torch.float64 or denom.numel() != (1 if labels is not None else C) or not denom.is_contiguous():
+        raise ValueError(f"probe_grad: denom must be float64 [{1 if labels is not None else C}]")
+    if labels is not None:
+        if target_mean is not None or target_std is not None:
+            raise ValueError("probe_grad: target_mean / target_std belong to regression")
+        labels, class_weight, task = _i32(labels, N, "labels"), _f32(class_weight, C, "class_weight"), 0
+    else:
+        if class_weight is not None:
+            raise ValueError("probe_grad: class_weight belongs to classification")
+        targets, task = _f32(targets, N * C, "targets"), 1
+        target_mean, target_std = _f32(target_mean, C, "target_mean"), _f32(target_std, C, "target_std")
+    dW, db, loss = out if out is not None else (torch.empty_like(W), torch.empty_like(b), torch.empty(H, device=W.device))
+    _f32(dW, M * d, "dW"), _f32(db, M, "db"), _f32(loss, H, "loss")
+    nb = probe_grad_workspace_bytes(N, d, M)
+    ws = workspace if workspace is not None else torch.empty(nb, dtype=torch.uint8, device=X.device)
+    check(lib.nv_probe_grad(_p(X), X.stride(0), N, d, _p(mean), _p(rstd), _p(W), _p(b), ctypes.byref(heads), task, _p(labels), _p(class_weight), _p(targets),
+                            _p(target_mean), _p(target_std), _p(denom), _p(dW), _p(db), _p(loss), int(max_blocks), _p(ws), ws.numel(), _stream()), "nv_probe_grad")
+    return dW, db, loss
+
+
+def probe_adam_constants(step: int, lrs, betas=(0.9, 0.999)):
+    """what the host forms for step `step` (1-based) of nv_probe_step, in double: (lr_h / (1 - beta1^t) per head, sqrt(1 - beta2^t))"""
+    bc1, bc2 = 1.0 - betas[0] ** step, 1.0 - betas[1] ** step
+    return [float(lr) / bc1 for lr in lrs], bc2 ** 0.5
+
+
+def probe_step(W, b, dW, db, mW, vW, mb, vb, heads, step: int, betas=(0.9, 0.999), eps: float = 1e-8) -> None:
+    """nv_probe_step: one Adam step on W [M, d], b [M] and their moments from dW / db, in place; heads.step holds lr_h / (1 - beta1^t)
+    (probe_adam_constants); every fp32 operation rounded on its own - the bits of the same torch fp32 expressions."""
+    M, d = W.shape
+    _need_cuda(W)
+    for t, n, name in ((W, M * d, "W"), (dW, M * d, "dW"), (mW, M * d, "mW"), (vW, M * d, "vW"), (b, M, "b"), (db, M, "db"), (mb, M, "mb"), (vb, M, "vb")):
+        _f32(t, n, name)
+    if M != heads.H * heads.C:
+        raise ValueError(f"probe_step: W has {M} rows, the heads {heads.H} x {heads.C}")
+    check(lib.nv_probe_step(_p(W), _p(b), _p(dW), _p(db), _p(mW), _p(vW), _p(mb), _p(vb), d, ctypes.byref(heads), betas[0], betas[1], 1.0 - betas[0], 1.0 - betas[1],
+                            (1.0 - betas[1] ** int(step)) ** 0.5, eps, _stream()), "nv_probe_step")
+
+
+def probe_predict(Q: torch.Tensor, W: torch.Tensor, b: torch.Tensor, H: int, C: int, *, mean=None, rstd=None, want_probs: bool = False, logits=None, probs=None):
+    """nv_probe_predict: queries f32 [Nq, d] -> logits f32 [Nq, M] under mean / rstd (M = H C <= 32), and with want_probs the fp32 softmax over
+    each head's own C columns.  logits / probs: column windows of wider arrays to write into (their row stride is passed).  Returns (logits, probs or None)."""
+    Nq, d = _probe_x(Q, "probe_predict")
+    M = int(H) * int(C)
+    if d % 4 or d > _cabi.PROBE_MAX_D:
+        raise ValueError(f"probe_predict: d = {d} must be a multiple of 4 up to {_cabi.PROBE_MAX_D}")
+    if (mean is None) != (rstd is None):
+        raise ValueError("probe_predict: mean and rstd are given together or not at all")
+    _need_cuda(W, b)
+    if W.dtype != torch.float32 or tuple(W.shape) != (M, d) or not W.is_contiguous():
+        raise ValueError(f"probe_predict: W must be a contiguous float32 [{M}, {d}], got {tuple(W.shape)} {W.dtype}")
+    b, mean, rstd = _f32(b, M, "b"), _f32(mean, d, "mean"), _f32(rstd, d, "rstd")
+    if logits is None:
+        logits = torch.empty((Nq, M), device=Q.device)
+    if probs is None and want_probs:
+        probs = torch.empty((Nq, M), device=Q.device)
+    for t in (logits, probs):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (Nq, M) or t.stride(1) != 1 or not t.is_cuda):
+            raise ValueError(f"probe_predict: logits / probs must be float32 [{Nq}, {M}] windows with unit column stride on the device")
+    check(lib.nv_probe_predict(_p(Q), Q.stride(0), Nq, d, _p(mean), _p(rstd), _p(W), _p(b), int(H), int(C), _p(logits), logits.stride(0), _p(probs),
+                               probs.stride(0) if probs is not None else 0, _stream()), "nv_probe_predict")
+    return logits, probs

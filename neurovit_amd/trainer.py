@@ -723,6 +723,7 @@ class Trainer:
         else:
             self.step = self._pretrain_step(config, model)
         self.knn = self.knn_from_config(config)                        # None: no kNN validation beside the pretraining loss, as ever
+        self.linear = self.linear_from_config(config)                  # None: no linear-probe validation either
         self.validate_ema = bool(config.get('VALIDATION_EMA', True))
         self.optimizer = self.step.optimizer
         self.log_interval = max(1, len(self.dataloader) // 10)
@@ -1022,8 +1023,11 @@ class Trainer:
         self.val_loss = round(float(total) / max(1, len(self.val_dataloader)), 5)
         print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_recon_loss {self.val_loss:.5f}")
         self._log({"epoch": epoch, "val_recon_loss": self.val_loss})
+        banks = {}                                                     # the frozen-feature banks of this epoch, by pooling: extracted once, shared by both probes
         if self.knn is not None and (epoch + 1) % self.knn["every"] == 0:
-            self.knn_validate(epoch)
+            self.knn_validate(epoch, banks=banks)
+        if self.linear is not None and (epoch + 1) % self.linear["every"] == 0:
+            self.linear_validate(epoch, banks=banks)
         return self.val_loss, None
 
     # ------------------------------------------------------------------ frozen-feature kNN validation (neurovit_amd.features)
@@ -1075,23 +1079,35 @@ class Trainer:
             bank.has_groups = False
         return bank
 
-    def knn_validate(self, epoch=None) -> dict:
-        """Frozen-feature kNN validation, on demand for any 3D model and every PRETRAIN_KNN_EVERY epochs under TRAINING_OBJECTIVE "mim": a bank
-        of the training set's features (centre windows, eval mode, VALIDATION_PRECISION), queried with the validation set's; a training
-        volume of the query's own subject is never its neighbour.  Logs val_knn_acc (and val_knn_subject_acc when the batches carry
-        subjects), or val_knn_mae under a regression target; with several k the first listed carries the plain name, the others `_k<k>`."""
-        from .features import GroupIndex, knn_evaluate
-        opts = self.knn if self.knn is not None else self.knn_options_from_config(self.config)
+    def _frozen_banks(self, pool, banks=None):
+        """(bank of the training set, bank of the validation set, the validation rows' host subject ids or None) under `pool`: centre windows,
+        eval mode, VALIDATION_PRECISION, the mode the model was found in restored.  banks: a dict that keeps them by pooling, so that the kNN
+        and the linear validation of one epoch extract once."""
+        from .features import GroupIndex
+        if banks is not None and pool in banks:
+            return banks[pool]
         was_training = self.model.training
         self.model.eval()
         index = GroupIndex()
         try:
             with self.model.precision(self.validation_precision):
-                bank = self._knn_features(self.data, index, opts)
-                val = self._knn_features(self.val_data, index, opts)
+                bank = self._knn_features(self.data, index, dict(pool=pool))
+                val = self._knn_features(self.val_data, index, dict(pool=pool))
         finally:
             self.model.train(was_training)
         groups = val._host_groups[:val.size] if (bank.has_groups and val.has_groups) else None
+        if banks is not None:
+            banks[pool] = (bank, val, groups)
+        return bank, val, groups
+
+    def knn_validate(self, epoch=None, banks=None) -> dict:
+        """Frozen-feature kNN validation, on demand for any 3D model and every PRETRAIN_KNN_EVERY epochs under TRAINING_OBJECTIVE "mim": a bank
+        of the training set's features (centre windows, eval mode, VALIDATION_PRECISION), queried with the validation set's; a training
+        volume of the query's own subject is never its neighbour.  Logs val_knn_acc (and val_knn_subject_acc when the batches carry
+        subjects), or val_knn_mae under a regression target; with several k the first listed carries the plain name, the others `_k<k>`."""
+        from .features import knn_evaluate
+        opts = self.knn if self.knn is not None else self.knn_options_from_config(self.config)
+        bank, val, groups = self._frozen_banks(opts["pool"], banks)
         truth = dict(labels=val.labels[:val.size]) if self.regression is None else dict(targets=val.targets[:val.size])
         got = knn_evaluate(bank, val.view(), k=opts["k"], temperature=opts["temperature"], query_groups=groups, **truth)
         payload = {} if epoch is None else {"epoch": epoch}
@@ -1108,6 +1124,71 @@ class Trainer:
               "\t| ".join(f"{name} {value}" for name, value in payload.items() if name != "epoch"))
         self._log(payload)
         self.val_knn = payload
+        return payload
+
+    # ------------------------------------------------------------------ frozen-feature linear-probe validation (neurovit_amd.features.LinearProbe)
+    @staticmethod
+    def linear_from_config(config) -> Optional[dict]:
+        """PRETRAIN_LINEAR_EVERY (epochs; absent, None or 0 = off: nothing changes) -> {"every", "steps", "lr", "l2", "pool"} or None; the rest
+        of the keys: Trainer.linear_options_from_config.  The pass itself is Trainer.linear_validate."""
+        every = config.get('PRETRAIN_LINEAR_EVERY', None)
+        if every is None or (not isinstance(every, bool) and every == 0):
+            return None
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"PRETRAIN_LINEAR_EVERY must be a positive number of epochs, got {every!r}")
+        return dict(every=every, **Trainer.linear_options_from_config(config))
+
+    @staticmethod
+    def linear_options_from_config(config) -> dict:
+        """PRETRAIN_LINEAR_STEPS (default 500), PRETRAIN_LINEAR_LR (0.01), PRETRAIN_LINEAR_L2 (one value or a list: one head each, default
+        1e-4 .. 1e-1) and PRETRAIN_LINEAR_POOL (default "patch_mean", as the kNN validation)"""
+        steps = config.get('PRETRAIN_LINEAR_STEPS', 500)
+        if isinstance(steps, bool) or not isinstance(steps, int) or steps < 1:
+            raise ValueError(f"PRETRAIN_LINEAR_STEPS must be a positive integer, got {steps!r}")
+        lr = config.get('PRETRAIN_LINEAR_LR', 0.01)
+        if isinstance(lr, bool) or not isinstance(lr, (int, float)) or not lr > 0:
+            raise ValueError(f"PRETRAIN_LINEAR_LR must be positive, got {lr!r}")
+        l2 = config.get('PRETRAIN_LINEAR_L2', [1e-4, 1e-3, 1e-2, 1e-1])
+        l2s = [l2] if isinstance(l2, (int, float)) and not isinstance(l2, bool) else list(l2)
+        if not l2s or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf") for v in l2s) or len(set(map(float, l2s))) != len(l2s):
+            raise ValueError(f"PRETRAIN_LINEAR_L2 must be one finite value >= 0 or a list of distinct ones, got {l2!r}")
+        pool = config.get('PRETRAIN_LINEAR_POOL', 'patch_mean')
+        if pool not in (None, 'cls', 'mean', 'patch_mean'):
+            raise ValueError(f"PRETRAIN_LINEAR_POOL must be 'cls', 'mean', 'patch_mean' or None (the model's own pooling), got {pool!r}")
+        return dict(steps=steps, lr=float(lr), l2=tuple(float(v) for v in l2s), pool=pool)
+
+    def linear_validate(self, epoch=None, banks=None) -> dict:
+        """Frozen-feature linear-probe validation, on demand for any 3D model and every PRETRAIN_LINEAR_EVERY epochs under TRAINING_OBJECTIVE
+        "mim": a LinearProbe with one head per PRETRAIN_LINEAR_L2 is fitted on the training set's features and scored on the validation
+        set's - the route knn_validate takes (centre windows, eval mode, VALIDATION_PRECISION; `banks`: the features of this epoch when the
+        kNN validation extracted them already).  Logs val_linear_acc (and val_linear_subject_acc when the batches carry subjects), or
+        val_linear_mae under a regression target; the first listed l2 carries the plain name, the others `_l2<value>`."""
+        from .features import LinearProbe, linear_evaluate
+        opts = self.linear if self.linear is not None else self.linear_options_from_config(self.config)
+        bank, val, groups = self._frozen_banks(opts["pool"], banks)
+        if self.regression is None:
+            probe = LinearProbe(bank.dim, num_classes=max(2, self.model.volume_encoder.vit3d._cfg.num_classes), l2=opts["l2"], device=self.device)
+            truth = dict(labels=val.labels[:val.size])
+        else:
+            probe = LinearProbe(bank.dim, num_targets=bank.targets.shape[1], l2=opts["l2"], device=self.device)
+            truth = dict(targets=val.targets[:val.size])
+        probe.fit(bank, steps=opts["steps"], lr=opts["lr"])
+        got = linear_evaluate(probe, val.view(), query_groups=groups, **truth)
+        payload = {} if epoch is None else {"epoch": epoch}
+        for j, lam in enumerate(opts["l2"]):
+            tag = "" if j == 0 else f"_l2{lam:g}"
+            if self.regression is None:
+                payload[f"val_linear_acc{tag}"] = round(got["acc"][lam], 5)
+                if groups is not None:
+                    payload[f"val_linear_subject_acc{tag}"] = round(got["subject_acc"][lam], 5)
+            else:
+                mae = got["mae"][lam]
+                payload[f"val_linear_mae{tag}"] = round(mae[0], 5) if len(mae) == 1 else [round(v, 5) for v in mae]
+        print(f"[VALIDATION] epoch {epoch}\t| linear probe on {bank.size} training volumes, {opts['steps']} steps, l2 {list(opts['l2'])}\t| " +
+              "\t| ".join(f"{name} {value}" for name, value in payload.items() if name != "epoch"))
+        self._log(payload)
+        self.val_linear = payload
+        self.linear_probe = probe
         return payload
 
     def train(self, epoch):
