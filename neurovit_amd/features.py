@@ -196,44 +196,50 @@ def knn_evaluate(bank: FeatureBank, queries: torch.Tensor, labels=None, targets=
     ks = _ks(k)
     task = "classification" if labels is not None else "regression"
     preds, scores, idx, sim = knn_predict(bank, queries, ks, temperature, weights, query_groups, task, num_classes, splits)
-    Nq, dev = queries.shape[0], queries.device
-    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, Nq, "query_groups"))
-    out = {"predictions": preds, "scores": scores, "idx": idx, "sim": sim}
-    if task == "classification":
+    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, queries.shape[0], "query_groups"))
+    variants = [(kk, preds[kk], scores[kk] if scores is not None else None) for kk in ks]
+
+    def voted(pooled):                                           # a subject without a positive vote has no class: -1, a miss
+        best, cls = pooled.max(dim=1)
+        return torch.where(best > 0, cls.to(torch.int32), torch.full_like(cls, -1, dtype=torch.int32))
+    return {"predictions": preds, "scores": scores, "idx": idx, "sim": sim,
+            **_score(variants, queries, csr, labels, targets, None if bank.targets is None else bank.targets.shape[1], voted)}
+
+
+def _score(variants, queries, csr, labels, targets, K, subject_class) -> dict:
+    """The score of [(key, predictions, scores or None)] against labels int [Nq] -> {"acc": {key: float}} or targets fp32 [Nq, K] -> {"mae":
+    {key: [K floats]}} (ops.RegressionMetrics, raw scale); with csr = (order, offsets) of the queries' subjects also "subject_acc" - the
+    scores averaged per subject (nv_segment_mean), subject_class of them, against the label of the subject's first volume - or
+    "subject_mae" on the NaN-aware per-subject means of predictions and targets.  Device expressions throughout, ONE host read."""
+    keys, (Nq, dev) = [key for key, _, _ in variants], (queries.shape[0], queries.device)
+    if labels is not None:
         y = torch.as_tensor(labels).reshape(-1).to(dev, torch.int32)
-        cells = [(preds[kk] == y).float().mean() for kk in ks]
+        cells = [(pred == y).float().mean() for _, pred, _ in variants]
         if csr is not None:
             order, offsets = csr
             filled = offsets[1:] > offsets[:-1]
             y_subject = y[order[offsets[:-1].clamp(max=Nq - 1).long()].long()]
-            for kk in ks:
-                pooled = ops.segment_mean(scores[kk], order, offsets)
-                best, cls = pooled.max(dim=1)
-                cls = torch.where(best > 0, cls.to(torch.int32), torch.full_like(y_subject, -1))
+            for _, _, score in variants:
+                cls = subject_class(ops.segment_mean(score, order, offsets))
                 cells.append(((cls == y_subject) & filled).float().sum() / filled.float().sum().clamp(min=1))
         host = torch.stack(cells).cpu().tolist()                 # the one host read
-        out["acc"] = dict(zip(ks, host[:len(ks)]))
+        names = ("acc", "subject_acc")
+    else:
+        t = ops.reg_targets(targets, Nq, K).to(dev)
+
+        def table(pred, truth):
+            m = ops.RegressionMetrics(t.shape[1], device=dev)
+            m.update(pred, truth)
+            return m.compute_device()
+        tables = [table(pred, t) for _, pred, _ in variants]
         if csr is not None:
-            out["subject_acc"] = dict(zip(ks, host[len(ks):]))
-        return out
-    t = ops.reg_targets(targets, Nq, bank.targets.shape[1]).to(dev)
-    K = t.shape[1]
-    tables = []
-    for kk in ks:
-        m = ops.RegressionMetrics(K, device=dev)
-        m.update(preds[kk], t)
-        tables.append(m.compute_device())
+            t_subject = _nanmean_segments(t, *csr)
+            tables += [table(_nanmean_segments(pred, *csr), t_subject) for _, pred, _ in variants]
+        host = torch.stack(tables).cpu()[:, :, 1].tolist()       # the one host read; column 1: the mean absolute error
+        names = ("mae", "subject_mae")
+    out = {names[0]: dict(zip(keys, host[:len(keys)]))}
     if csr is not None:
-        order, offsets = csr
-        t_subject = _nanmean_segments(t, order, offsets)
-        for kk in ks:
-            m = ops.RegressionMetrics(K, device=dev)
-            m.update(_nanmean_segments(preds[kk], order, offsets), t_subject)
-            tables.append(m.compute_device())
-    host = torch.stack(tables).cpu()                              # the one host read
-    out["mae"] = {kk: host[i, :, 1].tolist() for i, kk in enumerate(ks)}
-    if csr is not None:
-        out["subject_mae"] = {kk: host[len(ks) + i, :, 1].tolist() for i, kk in enumerate(ks)}
+        out[names[1]] = dict(zip(keys, host[len(keys):]))
     return out
 
 
@@ -415,42 +421,13 @@ def linear_evaluate(probe: LinearProbe, queries: torch.Tensor, labels=None, targ
         raise ValueError("linear_evaluate: give labels (classification) or targets (regression), one of the two")
     if (labels is not None) != (probe.task == "classification"):
         raise ValueError(f"linear_evaluate: a {probe.task} probe, but {'labels' if labels is not None else 'targets'} were given")
-    Nq, dev, H = queries.shape[0], queries.device, probe.H
-    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, Nq, "query_groups"))
+    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, queries.shape[0], "query_groups"))
     if labels is not None:
         pred, probs = probe.predict(queries)
         out = {"predictions": pred, "probs": probs}
-        y = torch.as_tensor(labels).reshape(-1).to(dev, torch.int32)
-        cells = [(pred[h] == y).float().mean() for h in range(H)]
-        if csr is not None:
-            order, offsets = csr
-            filled = offsets[1:] > offsets[:-1]
-            y_subject = y[order[offsets[:-1].clamp(max=Nq - 1).long()].long()]
-            for h in range(H):
-                cls = ops.segment_mean(probs[h], order, offsets).argmax(dim=1).to(torch.int32)
-                cells.append(((cls == y_subject) & filled).float().sum() / filled.float().sum().clamp(min=1))
-        host = torch.stack(cells).cpu().tolist()                  # the one host read
-        out["acc"] = dict(zip(probe.l2, host[:H]))
-        if csr is not None:
-            out["subject_acc"] = dict(zip(probe.l2, host[H:]))
-        return out
-    raw = probe.predict(queries)
-    K = probe.C
-    t = ops.reg_targets(targets, Nq, K).to(dev)
-    tables = []
-    for h in range(H):
-        m = ops.RegressionMetrics(K, device=dev)
-        m.update(raw[h], t)
-        tables.append(m.compute_device())
-    if csr is not None:
-        order, offsets = csr
-        t_subject = _nanmean_segments(t, order, offsets)
-        for h in range(H):
-            m = ops.RegressionMetrics(K, device=dev)
-            m.update(_nanmean_segments(raw[h], order, offsets), t_subject)
-            tables.append(m.compute_device())
-    host = torch.stack(tables).cpu()                               # the one host read
-    out = {"predictions": raw, "mae": {l2: host[h, :, 1].tolist() for h, l2 in enumerate(probe.l2)}}
-    if csr is not None:
-        out["subject_mae"] = {l2: host[H + h, :, 1].tolist() for h, l2 in enumerate(probe.l2)}
-    return out
+        variants = [(l2, pred[h], probs[h]) for h, l2 in enumerate(probe.l2)]
+    else:
+        raw = probe.predict(queries)
+        out = {"predictions": raw}
+        variants = [(l2, raw[h], None) for h, l2 in enumerate(probe.l2)]
+    return {**out, **_score(variants, queries, csr, labels, targets, probe.C, lambda pooled: pooled.argmax(dim=1).to(torch.int32))}

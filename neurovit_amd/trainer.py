@@ -11,7 +11,10 @@ No host synchronisation happens inside a step; `loss` is returned as a device te
 """
 from __future__ import annotations
 
+import contextlib
+import datetime
 import os
+import time
 from dataclasses import dataclass
 from typing import Optional
 
@@ -661,6 +664,223 @@ class DevicePrefetcher:
             yield cur
 
 
+def _pick(config, key, default):
+    """config[key], or the default where the key is absent or None"""
+    return default if config.get(key, None) is None else config[key]
+
+
+def _accumulation(config):
+    return config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1
+
+
+def _one(values):
+    return values[0] if len(values) == 1 else values
+
+
+class _Supervised:
+    """What the labelled classifier brings to the Trainer's loops, and the base of the other two objectives: how a batch is unpacked and
+    stepped, the running training statistic (accuracy), how a validation pass accumulates (the reference's per-batch .item()) and is
+    reported, one row of evaluate_samples, what the probes score against and what `run` saves beside the model file."""
+    truth = "labels"                  # the FeatureBank / probe argument the batches' truth goes to
+    loss_name = "train_loss"
+    runs_probes = False
+    own_arithmetic = False            # True: validation runs in the training arithmetic, not in VALIDATION_PRECISION
+    step_options: dict = {}
+
+    def __init__(self, trainer):
+        self.t = trainer
+
+    def make_step(self, config, model, smoothing, class_weights):
+        t = self.t
+        return TrainStep(model, accumulation_steps=_accumulation(config), max_grad_norm=t.grad_clip_from_config(config), label_smoothing=smoothing,
+                         class_weight=class_weights, **t.ema_from_config(config), **self.step_options,
+                         **t.schedule_from_config(config, t.epochs, len(t.dataloader)))
+
+    def unpack(self, batch):
+        return batch[2], batch[-1]
+
+    # -- train: the statistic stays on the device until a log line is due (the reference syncs twice per step, .item())
+    def reset(self):
+        self.correct, self.total = 0, 0
+
+    def train_batch(self, fMRI, truth):
+        t = self.t
+        loss = t.step(fMRI, truth) if t.mix is None else t.step(fMRI, truth, mix=t.mix.last_mix)
+        with torch.no_grad():                          # Trainer.py:78-79, from the step's own outputs (no second forward, no sync)
+            self.update(t.step.last_outputs, truth)
+        return loss
+
+    def update(self, outputs, label):
+        self.correct = self.correct + (outputs.argmax(dim=1) == label.to(outputs.device)).sum()
+        self.total += label.size(0)
+
+    def statistic(self):
+        """[(name, value)] for the log line: the host reads of the statistic happen here"""
+        return [("train_accuracy", round(float(self.correct) / self.total, 5))]
+
+    # -- validate: begin, one call per batch, report
+    def begin(self):
+        self.val_loss, self.val_correct, self.val_total = 0.0, 0, 0
+
+    def batch(self, model, fMRI, label, i):
+        label = label.to(self.t.device)
+        outputs = model(fMRI)
+        self.val_loss += self.t.criterion(outputs, label).item()
+        self.val_correct += (outputs.argmax(dim=1) == label).sum().item()
+        self.val_total += label.size(0)
+
+    def report(self, epoch, tag, i):
+        t = self.t
+        loss, accuracy = round(self.val_loss / max(1, len(t.val_dataloader)), 5), round(self.val_correct / max(1, self.val_total), 5)
+        setattr(t, f"val_loss{tag}", loss)
+        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss{tag} {loss:.5f}\t| val_accuracy{tag} {accuracy:.5f}")
+        t._log({"epoch": epoch, f"val_loss{tag}": loss, f"val_accuracy{tag}": accuracy})
+        return loss, accuracy
+
+    # -- evaluate_samples: begin_samples, one call per volume, the summary
+    def begin_samples(self):
+        self.hits, self.rows = 0, []
+
+    def sample(self, subject, fMRI, label):
+        prediction, actual = self.t.model(fMRI).argmax(dim=1).item(), int(label.item())
+        if prediction != actual:
+            self.rows.append((subject, prediction, actual))
+        self.hits += prediction == actual
+
+    def samples(self, n):
+        acc = self.hits / max(1, n) * 100
+        print(f"Accuracy: {acc:.2f}%")
+        print(f"Wrong predictions: {self.rows}")
+        return acc, self.rows
+
+    def save_beside(self, path, epoch):
+        pass
+
+
+class _Regression(_Supervised):
+    """TRAINING_OBJECTIVE "regression": targets from batch[REGRESSION_TARGET_INDEX], train_mae on the raw scale (under Mixup / CutMix: against
+    the unmixed targets) in the place of the accuracy, validation through ops.RegressionMetrics - everything accumulates on the device and a
+    pass ends in ONE host read -, evaluate_samples as (subject, prediction, actual) rows"""
+    truth = "targets"
+
+    def __init__(self, trainer):
+        from .ops import RegressionMetrics
+        super().__init__(trainer)
+        t, reg = trainer, trainer.regression
+        if not getattr(t.model, "is_regression", False):
+            raise ValueError("TRAINING_OBJECTIVE 'regression': the model was built without that key (its head is a classifier's)")
+        self.enc = enc = t.model.volume_encoder
+        t.criterion = RegressionLoss(reg["kind"], reg["delta"], target_mean=enc.target_mean, target_std=enc.target_std).to(t.device)   # validation: never mixed
+        t.targets = enc.target_mean.numel()
+        t.metrics = RegressionMetrics(t.targets, enc.target_mean, enc.target_std, t.device) if torch.device(t.device).type == "cuda" else None
+        self.step_options = dict(objective="regression", regression_loss=reg["kind"], huber_delta=reg["delta"], target_mean=enc.target_mean,
+                                 target_std=enc.target_std)
+
+    def unpack(self, batch):
+        return batch[2], batch[self.t.regression["index"]]
+
+    def reset(self):
+        self.abs_err, self.seen = 0.0, 0
+
+    def update(self, outputs, target):
+        """adds the sum of |prediction - target| on the raw scale over the observed cells, and their count: device tensors, no sync"""
+        target = target.to(outputs.device, torch.float32).reshape(outputs.shape[0], -1)
+        seen = torch.isfinite(target)
+        err = (outputs.float() * self.enc.target_std + self.enc.target_mean - torch.where(seen, target, torch.zeros_like(target))).abs()
+        self.abs_err, self.seen = self.abs_err + torch.where(seen, err, torch.zeros_like(err)).sum(), self.seen + seen.sum()
+
+    def statistic(self):
+        self.t.train_mae = round(float(self.abs_err) / max(1, int(self.seen)), 5)
+        return [("train_mae", self.t.train_mae)]
+
+    def begin(self):
+        if self.t.metrics is None:
+            raise RuntimeError("Trainer: the regression metrics run on the MI355X (cuda) device - there is no CPU fallback")
+        self.t.metrics.reset()
+        self.val_loss = torch.zeros((), device=self.t.device)
+
+    def batch(self, model, fMRI, target, i):
+        target = target.to(self.t.device)
+        outputs = model(fMRI).float()
+        self.val_loss = self.val_loss + self.t.criterion(outputs, target)
+        self.t.metrics.update(outputs, target)
+
+    def report(self, epoch, tag, i):
+        t = self.t
+        host = torch.cat([t.metrics.compute_device().flatten(), self.val_loss.reshape(1)]).cpu()      # the one host read
+        table = host[:-1].reshape(t.targets, 6)
+        got = {"val_loss": round(float(host[-1]) / max(1, len(t.val_dataloader)), 5), "batches": i}
+        for col, name in enumerate(("n", "mae", "rmse", "bias", "r", "r2")):
+            got[name] = [round(float(v), 5) for v in table[:, col]]
+        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss{tag} {got['val_loss']:.5f}\t| val_mae{tag} {_one(got['mae'])}\t| "
+              f"val_rmse{tag} {_one(got['rmse'])}\t| val_r{tag} {_one(got['r'])}\t| val_r2{tag} {_one(got['r2'])}")
+        t._log({"epoch": epoch, **{f"val_{k}{tag}": (got[k] if k == "val_loss" else _one(got[k])) for k in ("val_loss", "mae", "rmse", "r", "r2")}})
+        setattr(t, f"val_loss{tag}", got["val_loss"])
+        setattr(t, f"val_metrics{tag}", got)
+        return got["val_loss"], got["mae"]
+
+    def begin_samples(self):
+        self.abs_total, self.observed, self.rows = 0.0, 0, []
+
+    def sample(self, subject, fMRI, target):
+        prediction = self.t.model.predict(fMRI)[0].cpu().tolist()
+        actual = target.to(torch.float32).reshape(-1).tolist()
+        for p, a in zip(prediction, actual):
+            if a == a and abs(a) != float("inf"):
+                self.abs_total, self.observed = self.abs_total + abs(p - a), self.observed + 1
+        self.rows.append((subject, _one(prediction), _one(actual)))
+
+    def samples(self, n):
+        mae = self.abs_total / max(1, self.observed)
+        print(f"Mean absolute error: {mae:.4f}")
+        return mae, self.rows
+
+
+class _Pretraining(_Supervised):
+    """TRAINING_OBJECTIVE "mim" (pretrain.MaskedPretrainStep): the step takes the volume alone and there is no running statistic; validation
+    is the reconstruction loss of the centre windows under the masks of a fixed seed (batch i always meets the same masks), in the training
+    arithmetic, followed by the frozen-feature probes; `run` saves the reconstruction head beside the encoder."""
+    loss_name = "recon_loss"
+    runs_probes = own_arithmetic = True
+
+    def make_step(self, config, model, smoothing, class_weights):
+        """What belongs to the labelled objective does not go with it (ValueError): Mixup / CutMix, label smoothing, class weights, a weight
+        average, clipping, accumulation."""
+        from .pretrain import MaskedPretrainStep
+        t = self.t
+        clash = [k for k in ('AUGMENT_MIXUP_ALPHA', 'AUGMENT_CUTMIX_ALPHA', 'TRAINING_CLASS_WEIGHTS', 'TRAINING_EMA_DECAY', 'TRAINING_GRAD_CLIP')
+                 if config.get(k, None) is not None]
+        clash += [k for k in ('TRAINING_LABEL_SMOOTHING', 'USE_ACCUMULATION') if config.get(k, None)]
+        if clash:
+            raise ValueError("TRAINING_OBJECTIVE 'mim' does not go with " + ", ".join(clash))
+        return MaskedPretrainStep(model, fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0), rank=t._rank(), **t.pretrain,
+                                  **t.schedule_from_config(config, t.epochs, len(t.dataloader)))
+
+    def train_batch(self, fMRI, truth):
+        return self.t.step(fMRI)
+
+    def statistic(self):
+        return []
+
+    def begin(self):
+        self.val_loss = 0.0
+
+    def batch(self, model, fMRI, truth, i):
+        self.val_loss = self.val_loss + self.t.step.validation_loss(fMRI, index=i)
+
+    def report(self, epoch, tag, i):
+        t = self.t
+        t.val_loss = round(float(self.val_loss) / max(1, len(t.val_dataloader)), 5)
+        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_recon_loss {t.val_loss:.5f}")
+        t._log({"epoch": epoch, "val_recon_loss": t.val_loss})
+        return t.val_loss, None
+
+    def save_beside(self, path, epoch):
+        """the decoder beside the encoder (which is the plain model file)"""
+        torch.save(self.t.step.head.state_dict(), './results/last_recon_head.pth')
+        torch.save(self.t.step.head.state_dict(), f'{path}/recon-head-e{epoch}.pth')
+
+
 class Trainer:
     """The reference's Trainer shell (src/Trainer.py:14-167) on the native path: same constructor and methods
     (`run`, `train`, `validate`, `evaluate_samples`), same checkpoint files (plain `state_dict`s, interchangeable
@@ -693,6 +913,9 @@ class Trainer:
         the accuracy, `validate` reports val_loss, MAE, RMSE, Pearson r and R^2 (ops.RegressionMetrics: one host read per epoch) - also for
         the weight average -, `evaluate_samples` returns the mean absolute error and (subject, prediction, actual) per sample.  Mixup /
         CutMix blend the targets; TRAINING_LABEL_SMOOTHING / TRAINING_CLASS_WEIGHTS do not go with it.
+    Structure: `__init__` picks ONE objective object (_Supervised, _Regression or _Pretraining above) that holds all the three differ in;
+    `train` is one loop, `validate` one pass routine (for the model, then its weight average, then the probes of "mim"), `evaluate_samples`
+    one loop - no other method asks which objective runs.
     """
 
     def __init__(self, config, model, dataset_train, dataset_val):
@@ -712,16 +935,11 @@ class Trainer:
         self.regression = self.regression_from_config(config)          # None: the classifier's loss, as ever
         smoothing, class_weights = self.loss_options_from_config(config)
         self.criterion = CrossEntropyLoss(weight=class_weights)          # validation: never smoothed, never mixed; it carries the class weights
-        objective = {} if self.regression is None else self._regression_setup(model)
-        self.save_state, self.resume_from = self.state_options_from_config(config)
         self.pretrain = self.objective_from_config(config)             # None: the supervised step, as ever
-        if self.pretrain is None:
-            self.step = TrainStep(model, accumulation_steps=config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1,
-                                  max_grad_norm=self.grad_clip_from_config(config), label_smoothing=smoothing, class_weight=class_weights,
-                                  **self.ema_from_config(config), **objective,
-                                  **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
-        else:
-            self.step = self._pretrain_step(config, model)
+        # the one place that chooses the objective: everything the three differ in lives in that object
+        self.objective = (_Pretraining if self.pretrain is not None else _Supervised if self.regression is None else _Regression)(self)
+        self.save_state, self.resume_from = self.state_options_from_config(config)
+        self.step = self.objective.make_step(config, model, smoothing, class_weights)
         self.knn = self.knn_from_config(config)                        # None: no kNN validation beside the pretraining loss, as ever
         self.linear = self.linear_from_config(config)                  # None: no linear-probe validation either
         self.validate_ema = bool(config.get('VALIDATION_EMA', True))
@@ -757,9 +975,8 @@ class Trainer:
         if objective != "mim":
             raise ValueError(f"TRAINING_OBJECTIVE must be 'supervised', 'regression' or 'mim', got {objective!r}")
         from .pretrain import check_mask_options
-        pick = lambda key, default: default if config.get(key, None) is None else config[key]
-        out = dict(mask_ratio=pick('PRETRAIN_MASK_RATIO', 0.6), mask_unit=pick('PRETRAIN_MASK_UNIT', 1), loss=pick('PRETRAIN_LOSS', "l1"),
-                   norm_pix=pick('PRETRAIN_NORM_PIX', True))
+        out = dict(mask_ratio=_pick(config, 'PRETRAIN_MASK_RATIO', 0.6), mask_unit=_pick(config, 'PRETRAIN_MASK_UNIT', 1),
+                   loss=_pick(config, 'PRETRAIN_LOSS', "l1"), norm_pix=_pick(config, 'PRETRAIN_NORM_PIX', True))
         check_mask_options(config['TRAINING_VIT_INPUT_SIZE'] // config['TRAINING_VIT_PATCH_SIZE'], **out)
         return out
 
@@ -773,36 +990,12 @@ class Trainer:
         clash = [k for k in ('TRAINING_CLASS_WEIGHTS',) if config.get(k, None) is not None] + [k for k in ('TRAINING_LABEL_SMOOTHING',) if config.get(k, None)]
         if clash:
             raise ValueError("TRAINING_OBJECTIVE 'regression' does not go with " + ", ".join(clash))
-        pick = lambda key, default: default if config.get(key, None) is None else config[key]
-        kind, delta, index = pick('REGRESSION_LOSS', "mse"), pick('REGRESSION_HUBER_DELTA', 1.0), pick('REGRESSION_TARGET_INDEX', -2)
+        kind, delta, index = _pick(config, 'REGRESSION_LOSS', "mse"), _pick(config, 'REGRESSION_HUBER_DELTA', 1.0), _pick(config, 'REGRESSION_TARGET_INDEX', -2)
         from . import ops
         ops.reg_opts(kind, delta)                      # (the checks that need no device)
         if isinstance(index, bool) or not isinstance(index, int):
             raise TypeError(f"REGRESSION_TARGET_INDEX must be an integer, got {index!r}")
         return dict(kind=kind, delta=float(delta), index=index)
-
-    def _regression_setup(self, model) -> dict:
-        """TrainStep's arguments of the regression objective, and this shell's own loss (validation: never mixed) and metrics"""
-        from .ops import RegressionMetrics
-        if not getattr(model, "is_regression", False):
-            raise ValueError("TRAINING_OBJECTIVE 'regression': the model was built without that key (its head is a classifier's)")
-        enc, reg = model.volume_encoder, self.regression
-        self.criterion = RegressionLoss(reg["kind"], reg["delta"], target_mean=enc.target_mean, target_std=enc.target_std).to(self.device)
-        self.targets = enc.target_mean.numel()
-        self.metrics = RegressionMetrics(self.targets, enc.target_mean, enc.target_std, self.device) if torch.device(self.device).type == "cuda" else None
-        return dict(objective="regression", regression_loss=reg["kind"], huber_delta=reg["delta"], target_mean=enc.target_mean, target_std=enc.target_std)
-
-    def _pretrain_step(self, config, model):
-        """The step of TRAINING_OBJECTIVE "mim".  What belongs to the labelled objective does not go with it (ValueError): Mixup / CutMix,
-        label smoothing, class weights, a weight average, clipping, accumulation."""
-        from .pretrain import MaskedPretrainStep
-        clash = [k for k in ('AUGMENT_MIXUP_ALPHA', 'AUGMENT_CUTMIX_ALPHA', 'TRAINING_CLASS_WEIGHTS', 'TRAINING_EMA_DECAY', 'TRAINING_GRAD_CLIP')
-                 if config.get(k, None) is not None]
-        clash += [k for k in ('TRAINING_LABEL_SMOOTHING', 'USE_ACCUMULATION') if config.get(k, None)]
-        if clash:
-            raise ValueError("TRAINING_OBJECTIVE 'mim' does not go with " + ", ".join(clash))
-        return MaskedPretrainStep(model, fill=config.get('AUGMENT_FILL', 0.0), seed=config.get('AUGMENT_SEED', 0), rank=self._rank(), **self.pretrain,
-                                  **self.schedule_from_config(config, self.epochs, len(self.dataloader)))
 
     @staticmethod
     def ema_from_config(config) -> dict:
@@ -834,8 +1027,7 @@ class Trainer:
             if warmup is not None or min_lr is not None:
                 raise ValueError("TRAINING_WARMUP_STEPS / TRAINING_MIN_LR need TRAINING_LR_SCHEDULE ('cosine', 'linear' or 'constant')")
         else:
-            accumulation = config.get('TRAINING_ACCUMULATION_STEP', 1) if config.get('USE_ACCUMULATION', False) else 1
-            total = int(epochs) * -(-int(batches_per_epoch) // max(1, int(accumulation)))
+            total = int(epochs) * -(-int(batches_per_epoch) // max(1, int(_accumulation(config))))
             out["lr_schedule"] = LRSchedule(config.get('TRAINING_LEARNING_RATE', 1e-4), total, 0 if warmup is None else warmup, kind, 0.0 if min_lr is None else min_lr)
         decay = config.get('TRAINING_LAYER_DECAY', None)
         if decay is not None:
@@ -911,10 +1103,9 @@ class Trainer:
             if config.get('AUGMENT_MAX_SHIFT', None) is not None:
                 raise ValueError("AUGMENT_MAX_SHIFT does not go with the affine keys (" + ", ".join(k for k in affine_keys if config.get(k, None) is not None)
                                  + "): set AUGMENT_TRANSLATE, the (sub-voxel) shift of the resampling pass")
-            pick = lambda key, default: default if config.get(key, None) is None else config[key]
-            return VolumeAffine((S, S, S), rotate=pick('AUGMENT_ROTATE_DEG', 0.0), zoom=pick('AUGMENT_ZOOM', (1, 1)),
-                                isotropic=pick('AUGMENT_ZOOM_ISOTROPIC', True), translate=pick('AUGMENT_TRANSLATE', 0.0),
-                                prob=pick('AUGMENT_AFFINE_PROB', 1.0), **shared)
+            return VolumeAffine((S, S, S), rotate=_pick(config, 'AUGMENT_ROTATE_DEG', 0.0), zoom=_pick(config, 'AUGMENT_ZOOM', (1, 1)),
+                                isotropic=_pick(config, 'AUGMENT_ZOOM_ISOTROPIC', True), translate=_pick(config, 'AUGMENT_TRANSLATE', 0.0),
+                                prob=_pick(config, 'AUGMENT_AFFINE_PROB', 1.0), **shared)
         return VolumeAugment((S, S, S), max_shift=config.get('AUGMENT_MAX_SHIFT', (0, 0, 0)), **shared)
 
     @staticmethod
@@ -967,14 +1158,13 @@ class Trainer:
         return check_max_norm(value)
 
     def _unpack(self, batch):
-        return batch[2], batch[-1 if self.regression is None else self.regression["index"]]
+        return self.objective.unpack(batch)
 
     def _log(self, payload):
         if self._wandb is not None:
             self._wandb.log(payload)
 
     def run(self):
-        import datetime
         path = f"{self.output_dir}/{datetime.datetime.now().strftime('%Y-%m-%d_%H-%M-%S')}"
         os.makedirs(path, exist_ok=True)
         os.makedirs('./results', exist_ok=True)
@@ -983,9 +1173,7 @@ class Trainer:
             self.validate(epoch)
             torch.save(self.model.state_dict(), './results/last_model.pth')
             torch.save(self.model.state_dict(), f'{path}/model-e{epoch}.pth')
-            if self.pretrain is not None:              # the decoder beside the encoder (which is the plain model file above)
-                torch.save(self.step.head.state_dict(), './results/last_recon_head.pth')
-                torch.save(self.step.head.state_dict(), f'{path}/recon-head-e{epoch}.pth')
+            self.objective.save_beside(path, epoch)
             if self.step.ema is not None:              # the averaged weights: plain state_dicts, loadable like any checkpoint
                 torch.save(self.step.ema.module.state_dict(), './results/last_model_ema.pth')
                 torch.save(self.step.ema.module.state_dict(), f'{path}/model-e{epoch}-ema.pth')
@@ -995,53 +1183,30 @@ class Trainer:
                 torch.save(state, f'{path}/state-e{epoch}.pth')
             print(f"MODEL SAVED to .{path}/model-e{epoch}.pth")
 
-    def _train_pretrain(self, epoch):
-        """`train` under TRAINING_OBJECTIVE "mim": the configured augmentation, then the masked-reconstruction step; labels are ignored"""
-        import time
-        self.model.train()
-        running_loss, start_time = 0.0, time.time()
-        for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):
-            fMRI, _ = self._unpack(batch)
-            if self.augment is not None:
-                fMRI = self.augment(fMRI, step=self.global_step)
-            self.global_step += 1
-            running_loss = running_loss + self.step(fMRI)
-            if i != 0 and i % self.log_interval == 0:
-                avg_loss, lr, duration = round(float(running_loss) / self.log_interval, 5), round(self.step.last_lr, 5), time.time() - start_time
-                print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| recon_loss: {avg_loss:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
-                self._log({"epoch": epoch, "batch": i, "recon_loss": avg_loss, "learning_rate": lr, "duration": duration})
-                running_loss, start_time = 0.0, time.time()
+    # ------------------------------------------------------------------ frozen-feature validation: the kNN and the linear probe (neurovit_amd.features)
+    @staticmethod
+    def _probe_every(config, key, options) -> Optional[dict]:
+        """PRETRAIN_{KNN,LINEAR}_EVERY (epochs; absent, None or 0 = off) -> dict(every=..., **options(config)) or None"""
+        every = config.get(key, None)
+        if every is None or (not isinstance(every, bool) and every == 0):
+            return None
+        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
+            raise ValueError(f"{key} must be a positive number of epochs, got {every!r}")
+        return dict(every=every, **options(config))
 
-    def _validate_pretrain(self, epoch):
-        """`validate` under TRAINING_OBJECTIVE "mim": the reconstruction loss of the centre windows under the masks of a fixed seed (batch
-        i always meets the same masks), in the training arithmetic, without dropout"""
-        self.model.eval()
-        total, i = 0.0, 0
-        for i, batch in enumerate(self.val_dataloader):
-            fMRI, _ = self._unpack(batch)
-            total = total + self.step.validation_loss(self._center(fMRI.to(self.device)), index=i)
-        self.val_loss = round(float(total) / max(1, len(self.val_dataloader)), 5)
-        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_recon_loss {self.val_loss:.5f}")
-        self._log({"epoch": epoch, "val_recon_loss": self.val_loss})
-        banks = {}                                                     # the frozen-feature banks of this epoch, by pooling: extracted once, shared by both probes
-        if self.knn is not None and (epoch + 1) % self.knn["every"] == 0:
-            self.knn_validate(epoch, banks=banks)
-        if self.linear is not None and (epoch + 1) % self.linear["every"] == 0:
-            self.linear_validate(epoch, banks=banks)
-        return self.val_loss, None
+    @staticmethod
+    def _probe_pool(config, key):
+        pool = config.get(key, 'patch_mean')
+        if pool not in (None, 'cls', 'mean', 'patch_mean'):
+            raise ValueError(f"{key} must be 'cls', 'mean', 'patch_mean' or None (the model's own pooling), got {pool!r}")
+        return pool
 
-    # ------------------------------------------------------------------ frozen-feature kNN validation (neurovit_amd.features)
     @staticmethod
     def knn_from_config(config) -> Optional[dict]:
         """PRETRAIN_KNN_EVERY (epochs; absent, None or 0 = off: nothing changes), PRETRAIN_KNN_K (one k or a list, default 20),
         PRETRAIN_KNN_TEMPERATURE (default 0.07), PRETRAIN_KNN_POOL (default "patch_mean": the cls token of a masked-pretrained encoder was
         never trained) -> {"every", "k", "temperature", "pool"} or None.  The kNN pass itself is Trainer.knn_validate."""
-        every = config.get('PRETRAIN_KNN_EVERY', None)
-        if every is None or (not isinstance(every, bool) and every == 0):
-            return None
-        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
-            raise ValueError(f"PRETRAIN_KNN_EVERY must be a positive number of epochs, got {every!r}")
-        return dict(every=every, **Trainer.knn_options_from_config(config))
+        return Trainer._probe_every(config, 'PRETRAIN_KNN_EVERY', Trainer.knn_options_from_config)
 
     @staticmethod
     def knn_options_from_config(config) -> dict:
@@ -1052,10 +1217,7 @@ class Trainer:
         temperature = float(config.get('PRETRAIN_KNN_TEMPERATURE', 0.07))
         if not temperature > 0:
             raise ValueError(f"PRETRAIN_KNN_TEMPERATURE must be positive, got {temperature!r}")
-        pool = config.get('PRETRAIN_KNN_POOL', 'patch_mean')
-        if pool not in (None, 'cls', 'mean', 'patch_mean'):
-            raise ValueError(f"PRETRAIN_KNN_POOL must be 'cls', 'mean', 'patch_mean' or None (the model's own pooling), got {pool!r}")
-        return dict(k=tuple(ks), temperature=temperature, pool=pool)
+        return dict(k=tuple(ks), temperature=temperature, pool=Trainer._probe_pool(config, 'PRETRAIN_KNN_POOL'))
 
     def _knn_features(self, dataset, index, opts):
         """A FeatureBank of the centre windows of `dataset` in eval mode (features L2-normalised): labels or regression targets from the
@@ -1071,10 +1233,9 @@ class Trainer:
             grouped = grouped and subjects is not None
             x = self._center(fMRI.to(self.device))
             if bank is None:
-                K = 0 if self.regression is None else truth.reshape(x.shape[0], -1).shape[1]
+                K = truth.reshape(x.shape[0], -1).shape[1] if self.objective.truth == "targets" else 0
                 bank = FeatureBank(self.model.volume_encoder.vit3d.pos_embedding.shape[2], len(dataset), self.device, num_targets=K)
-            bank.append(self.model, x, labels=truth if self.regression is None else None, groups=index(subjects) if grouped else None,
-                        targets=truth if self.regression is not None else None, pool=opts["pool"], normalize=True)
+            bank.append(self.model, x, groups=index(subjects) if grouped else None, pool=opts["pool"], normalize=True, **{self.objective.truth: truth})
         if bank is not None and not grouped:
             bank.has_groups = False
         return bank
@@ -1108,35 +1269,32 @@ class Trainer:
         from .features import knn_evaluate
         opts = self.knn if self.knn is not None else self.knn_options_from_config(self.config)
         bank, val, groups = self._frozen_banks(opts["pool"], banks)
-        truth = dict(labels=val.labels[:val.size]) if self.regression is None else dict(targets=val.targets[:val.size])
-        got = knn_evaluate(bank, val.view(), k=opts["k"], temperature=opts["temperature"], query_groups=groups, **truth)
+        got = knn_evaluate(bank, val.view(), k=opts["k"], temperature=opts["temperature"], query_groups=groups,
+                           **{self.objective.truth: getattr(val, self.objective.truth)[:val.size]})
+        return self._probe_report(epoch, "knn", f"kNN on {bank.size} training volumes, k {list(opts['k'])}", opts["k"], "_k{}".format, got, groups)
+
+    def _probe_report(self, epoch, name, headline, variants, tag, got, groups) -> dict:
+        """Forms, prints, logs and stores (self.val_<name>) a probe's payload: val_<name>_acc (and _subject_acc with groups) or val_<name>_mae
+        per variant - the first under the plain name, the others with the suffix tag(variant)"""
         payload = {} if epoch is None else {"epoch": epoch}
-        for j, kk in enumerate(opts["k"]):
-            tag = "" if j == 0 else f"_k{kk}"
-            if self.regression is None:
-                payload[f"val_knn_acc{tag}"] = round(got["acc"][kk], 5)
+        for j, v in enumerate(variants):
+            suffix = "" if j == 0 else tag(v)
+            if "acc" in got:
+                payload[f"val_{name}_acc{suffix}"] = round(got["acc"][v], 5)
                 if groups is not None:
-                    payload[f"val_knn_subject_acc{tag}"] = round(got["subject_acc"][kk], 5)
+                    payload[f"val_{name}_subject_acc{suffix}"] = round(got["subject_acc"][v], 5)
             else:
-                mae = got["mae"][kk]
-                payload[f"val_knn_mae{tag}"] = round(mae[0], 5) if len(mae) == 1 else [round(v, 5) for v in mae]
-        print(f"[VALIDATION] epoch {epoch}\t| kNN on {bank.size} training volumes, k {list(opts['k'])}\t| " +
-              "\t| ".join(f"{name} {value}" for name, value in payload.items() if name != "epoch"))
+                payload[f"val_{name}_mae{suffix}"] = _one([round(m, 5) for m in got["mae"][v]])
+        print(f"[VALIDATION] epoch {epoch}\t| {headline}\t| " + "\t| ".join(f"{key} {value}" for key, value in payload.items() if key != "epoch"))
         self._log(payload)
-        self.val_knn = payload
+        setattr(self, f"val_{name}", payload)
         return payload
 
-    # ------------------------------------------------------------------ frozen-feature linear-probe validation (neurovit_amd.features.LinearProbe)
     @staticmethod
     def linear_from_config(config) -> Optional[dict]:
         """PRETRAIN_LINEAR_EVERY (epochs; absent, None or 0 = off: nothing changes) -> {"every", "steps", "lr", "l2", "pool"} or None; the rest
         of the keys: Trainer.linear_options_from_config.  The pass itself is Trainer.linear_validate."""
-        every = config.get('PRETRAIN_LINEAR_EVERY', None)
-        if every is None or (not isinstance(every, bool) and every == 0):
-            return None
-        if isinstance(every, bool) or not isinstance(every, int) or every < 1:
-            raise ValueError(f"PRETRAIN_LINEAR_EVERY must be a positive number of epochs, got {every!r}")
-        return dict(every=every, **Trainer.linear_options_from_config(config))
+        return Trainer._probe_every(config, 'PRETRAIN_LINEAR_EVERY', Trainer.linear_options_from_config)
 
     @staticmethod
     def linear_options_from_config(config) -> dict:
@@ -1152,10 +1310,7 @@ class Trainer:
         l2s = [l2] if isinstance(l2, (int, float)) and not isinstance(l2, bool) else list(l2)
         if not l2s or any(isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < float("inf") for v in l2s) or len(set(map(float, l2s))) != len(l2s):
             raise ValueError(f"PRETRAIN_LINEAR_L2 must be one finite value >= 0 or a list of distinct ones, got {l2!r}")
-        pool = config.get('PRETRAIN_LINEAR_POOL', 'patch_mean')
-        if pool not in (None, 'cls', 'mean', 'patch_mean'):
-            raise ValueError(f"PRETRAIN_LINEAR_POOL must be 'cls', 'mean', 'patch_mean' or None (the model's own pooling), got {pool!r}")
-        return dict(steps=steps, lr=float(lr), l2=tuple(float(v) for v in l2s), pool=pool)
+        return dict(steps=steps, lr=float(lr), l2=tuple(float(v) for v in l2s), pool=Trainer._probe_pool(config, 'PRETRAIN_LINEAR_POOL'))
 
     def linear_validate(self, epoch=None, banks=None) -> dict:
         """Frozen-feature linear-probe validation, on demand for any 3D model and every PRETRAIN_LINEAR_EVERY epochs under TRAINING_OBJECTIVE
@@ -1166,214 +1321,79 @@ class Trainer:
         from .features import LinearProbe, linear_evaluate
         opts = self.linear if self.linear is not None else self.linear_options_from_config(self.config)
         bank, val, groups = self._frozen_banks(opts["pool"], banks)
-        if self.regression is None:
+        if self.objective.truth == "labels":
             probe = LinearProbe(bank.dim, num_classes=max(2, self.model.volume_encoder.vit3d._cfg.num_classes), l2=opts["l2"], device=self.device)
-            truth = dict(labels=val.labels[:val.size])
         else:
             probe = LinearProbe(bank.dim, num_targets=bank.targets.shape[1], l2=opts["l2"], device=self.device)
-            truth = dict(targets=val.targets[:val.size])
         probe.fit(bank, steps=opts["steps"], lr=opts["lr"])
-        got = linear_evaluate(probe, val.view(), query_groups=groups, **truth)
-        payload = {} if epoch is None else {"epoch": epoch}
-        for j, lam in enumerate(opts["l2"]):
-            tag = "" if j == 0 else f"_l2{lam:g}"
-            if self.regression is None:
-                payload[f"val_linear_acc{tag}"] = round(got["acc"][lam], 5)
-                if groups is not None:
-                    payload[f"val_linear_subject_acc{tag}"] = round(got["subject_acc"][lam], 5)
-            else:
-                mae = got["mae"][lam]
-                payload[f"val_linear_mae{tag}"] = round(mae[0], 5) if len(mae) == 1 else [round(v, 5) for v in mae]
-        print(f"[VALIDATION] epoch {epoch}\t| linear probe on {bank.size} training volumes, {opts['steps']} steps, l2 {list(opts['l2'])}\t| " +
-              "\t| ".join(f"{name} {value}" for name, value in payload.items() if name != "epoch"))
-        self._log(payload)
-        self.val_linear = payload
+        got = linear_evaluate(probe, val.view(), query_groups=groups, **{self.objective.truth: getattr(val, self.objective.truth)[:val.size]})
+        payload = self._probe_report(epoch, "linear", f"linear probe on {bank.size} training volumes, {opts['steps']} steps, l2 {list(opts['l2'])}",
+                                     opts["l2"], "_l2{:g}".format, got, groups)
         self.linear_probe = probe
         return payload
 
     def train(self, epoch):
-        import time
-        if self.pretrain is not None:
-            return self._train_pretrain(epoch)
-        if self.regression is not None:
-            return self._train_regression(epoch)
+        """One loop for every objective: prefetch (H2D of batch i+1 under step i), unpack, mix or augment, count the batch, step; the loss and
+        the objective's statistic stay on the device until a log line is due (the reference syncs twice per step, .item())."""
+        objective = self.objective
         self.model.train()
-        running_loss, correct, total = 0.0, 0, 0
-        start_time = time.time()
-        for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):     # H2D of batch i+1 under step i
-            fMRI, label = self._unpack(batch)
+        running_loss, start_time = 0.0, time.time()
+        objective.reset()
+        for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):
+            fMRI, truth = self._unpack(batch)
             if self.mix is not None:
                 fMRI = self.mix(fMRI, step=self.global_step, augment=self.augment)      # crop / flips / intensity and the mix in one pass (two behind a VolumeAffine)
             elif self.augment is not None:
                 fMRI = self.augment(fMRI, step=self.global_step)
             self.global_step += 1
-            loss = self.step(fMRI, label) if self.mix is None else self.step(fMRI, label, mix=self.mix.last_mix)
-            # the reference syncs twice per step (.item()); here statistics stay on the device until a log line is due
-            running_loss = running_loss + loss
-            with torch.no_grad():                      # Trainer.py:78-79, from the step's own outputs (no second forward, no sync)
-                correct = correct + (self.step.last_outputs.argmax(dim=1) == label.to(self.step.last_outputs.device)).sum()
-            total += label.size(0)
+            running_loss = running_loss + objective.train_batch(fMRI, truth)
             if i != 0 and i % self.log_interval == 0:
-                avg_loss = round(float(running_loss) / self.log_interval, 5)
-                accuracy = round(float(correct) / total, 5)
-                lr = round(self.step.last_lr, 5)
+                fields = [(objective.loss_name, round(float(running_loss) / self.log_interval, 5))] + objective.statistic()
+                fields.append(("learning_rate", round(self.step.last_lr, 5)))
                 duration = time.time() - start_time
-                print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| train_loss: {avg_loss:.5f}\t| train_accuracy: {accuracy:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
-                payload = {"epoch": epoch, "batch": i, "train_loss": avg_loss, "train_accuracy": accuracy, "learning_rate": lr, "duration": duration}
+                print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| " + "".join(f"{name}: {value:.5f}\t| " for name, value in fields) + f"duration: {duration:.2f}s")
+                payload = {"epoch": epoch, "batch": i, **dict(fields), "duration": duration}
                 if self.step.last_grad_norm is not None:       # read back here only: the log line above has synchronised already
                     payload["grad_norm"] = float(self.step.last_grad_norm)
                 self._log(payload)
-                correct, total, running_loss = 0, 0, 0.0
-                start_time = time.time()
+                objective.reset()
+                running_loss, start_time = 0.0, time.time()
 
-    def _raw_abs_error(self, outputs, target):
-        """(sum of |prediction - target| on the raw scale over the observed cells, their count): device tensors, no sync"""
-        enc = self.model.volume_encoder
-        target = target.to(outputs.device, torch.float32).reshape(outputs.shape[0], -1)
-        seen = torch.isfinite(target)
-        err = (outputs.float() * enc.target_std + enc.target_mean - torch.where(seen, target, torch.zeros_like(target))).abs()
-        return torch.where(seen, err, torch.zeros_like(err)).sum(), seen.sum()
-
-    def _train_regression(self, epoch):
-        """`train` under TRAINING_OBJECTIVE "regression": the same loop with the targets of REGRESSION_TARGET_INDEX, and train_mae - the mean
-        absolute error on the raw scale, from the step's own outputs (under Mixup / CutMix: against the unmixed targets), kept on the device
-        until a log line - in the place of the accuracy"""
-        import time
-        self.model.train()
-        running_loss, abs_err, seen = 0.0, 0.0, 0
-        start_time = time.time()
-        for i, batch in enumerate(DevicePrefetcher(self.dataloader, self.device)):
-            fMRI, target = self._unpack(batch)
-            if self.mix is not None:
-                fMRI = self.mix(fMRI, step=self.global_step, augment=self.augment)
-            elif self.augment is not None:
-                fMRI = self.augment(fMRI, step=self.global_step)
-            self.global_step += 1
-            loss = self.step(fMRI, target) if self.mix is None else self.step(fMRI, target, mix=self.mix.last_mix)
-            running_loss = running_loss + loss
-            with torch.no_grad():
-                e, n = self._raw_abs_error(self.step.last_outputs, target)
-                abs_err, seen = abs_err + e, seen + n
-            if i != 0 and i % self.log_interval == 0:
-                avg_loss, mae = round(float(running_loss) / self.log_interval, 5), round(float(abs_err) / max(1, int(seen)), 5)
-                lr, duration = round(self.step.last_lr, 5), time.time() - start_time
-                print(f"epoch {epoch}\t| batch {i}/{len(self.dataloader)}\t| train_loss: {avg_loss:.5f}\t| train_mae: {mae:.5f}\t| learning_rate: {lr:.5f}\t| duration: {duration:.2f}s")
-                payload = {"epoch": epoch, "batch": i, "train_loss": avg_loss, "train_mae": mae, "learning_rate": lr, "duration": duration}
-                if self.step.last_grad_norm is not None:
-                    payload["grad_norm"] = float(self.step.last_grad_norm)
-                self._log(payload)
-                self.train_mae = mae
-                running_loss, abs_err, seen = 0.0, 0.0, 0
-                start_time = time.time()
-
-    def _evaluate_regression(self, model):
-        """{"val_loss", "mae", "rmse", "r", "r2" (lists of K), "n"} of `model` over the validation set: the loss and the metrics accumulate on
-        the device (ops.RegressionMetrics), ONE host read at the end"""
-        if self.metrics is None:
-            raise RuntimeError("Trainer: the regression metrics run on the MI355X (cuda) device - there is no CPU fallback")
+    def _validation_pass(self, model, tag, epoch):
+        """One pass over the validation set (centre windows, eval mode) for `model`: the objective accumulates the batches and reports"""
+        objective, i = self.objective, 0
         model.eval()
-        self.metrics.reset()
-        total, i = torch.zeros((), device=self.device), 0
-        with torch.no_grad(), model.precision(self.validation_precision):
+        objective.begin()
+        with torch.no_grad(), contextlib.nullcontext() if objective.own_arithmetic else model.precision(self.validation_precision):
             for i, batch in enumerate(self.val_dataloader):
-                fMRI, target = self._unpack(batch)
-                fMRI, target = self._center(fMRI.to(self.device)), target.to(self.device)
-                outputs = model(fMRI).float()
-                total = total + self.criterion(outputs, target)
-                self.metrics.update(outputs, target)
-            got = torch.cat([self.metrics.compute_device().flatten(), total.reshape(1)]).cpu()      # the one host read
-        table = got[:-1].reshape(self.targets, 6)
-        out = {"val_loss": round(float(got[-1]) / max(1, len(self.val_dataloader)), 5), "batches": i}
-        for col, name in enumerate(("n", "mae", "rmse", "bias", "r", "r2")):
-            out[name] = [round(float(v), 5) for v in table[:, col]]
-        return out
-
-    def _validate_regression(self, epoch):
-        """`validate` under TRAINING_OBJECTIVE "regression": val_loss, MAE, RMSE, Pearson r and R^2 per target on the raw scale, for the model
-        and - when there is one - for its weight average"""
-        result = None
-        models = [("", self.model)] + ([("_ema", self.step.ema.module)] if self.step.ema is not None and self.validate_ema else [])
-        for tag, model in models:
-            got = self._evaluate_regression(model)
-            one = lambda v: v[0] if len(v) == 1 else v
-            print(f"[VALIDATION] epoch {epoch}\t| total_batch {got['batches']}\t| val_loss{tag} {got['val_loss']:.5f}\t| val_mae{tag} {one(got['mae'])}\t| "
-                  f"val_rmse{tag} {one(got['rmse'])}\t| val_r{tag} {one(got['r'])}\t| val_r2{tag} {one(got['r2'])}")
-            self._log({"epoch": epoch, **{f"val_{k}{tag}": (got[k] if k == "val_loss" else one(got[k])) for k in ("val_loss", "mae", "rmse", "r", "r2")}})
-            if tag:
-                self.val_loss_ema, self.val_metrics_ema = got["val_loss"], got
-            else:
-                self.val_loss, self.val_metrics = got["val_loss"], got
-                result = (got["val_loss"], got["mae"])
-        return result
-
-    def _evaluate_samples_regression(self):
-        """(mean absolute error over the observed targets, [(subject, prediction, actual)] per sample) on the raw scale"""
-        self.model.eval()
-        loader = torch.utils.data.DataLoader(self.val_data, batch_size=1, shuffle=False, num_workers=self.num_workers)
-        rows, total, seen = [], 0.0, 0
-        with self.model.precision(self.validation_precision):
-            for batch in loader:
-                fMRI, target = self._unpack(batch)
-                prediction = self.model.predict(self._center(fMRI.to(self.device)))[0].cpu().tolist()
-                actual = target.to(torch.float32).reshape(-1).tolist()
-                for p, a in zip(prediction, actual):
-                    if a == a and abs(a) != float("inf"):
-                        total, seen = total + abs(p - a), seen + 1
-                one = lambda v: v[0] if len(v) == 1 else v
-                rows.append((batch[0][0] if isinstance(batch[0], (list, tuple)) else batch[0], one(prediction), one(actual)))
-        mae = total / max(1, seen)
-        print(f"Mean absolute error: {mae:.4f}")
-        return mae, rows
-
-    def _evaluate(self, model):
-        """(rounded mean loss, rounded accuracy, index of the last batch) of `model` over the validation set"""
-        model.eval()
-        val_loss, correct, total, i = 0.0, 0, 0, 0
-        with torch.no_grad(), model.precision(self.validation_precision):
-            for i, batch in enumerate(self.val_dataloader):
-                fMRI, label = self._unpack(batch)
-                fMRI, label = self._center(fMRI.to(self.device)), label.to(self.device)
-                outputs = model(fMRI)
-                val_loss += self.criterion(outputs, label).item()
-                correct += (outputs.argmax(dim=1) == label).sum().item()
-                total += label.size(0)
-        return round(val_loss / max(1, len(self.val_dataloader)), 5), round(correct / max(1, total), 5), i
+                fMRI, truth = self._unpack(batch)
+                objective.batch(model, self._center(fMRI.to(self.device)), truth, i)
+        return objective.report(epoch, tag, i)
 
     def validate(self, epoch):
-        if self.pretrain is not None:
-            return self._validate_pretrain(epoch)
-        if self.regression is not None:
-            return self._validate_regression(epoch)
-        avg_val_loss, accuracy, i = self._evaluate(self.model)
-        self.val_loss = avg_val_loss
-        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss {avg_val_loss:.5f}\t| val_accuracy {accuracy:.5f}")
-        self._log({"epoch": epoch, "val_loss": avg_val_loss, "val_accuracy": accuracy})
+        result = self._validation_pass(self.model, "", epoch)
         if self.step.ema is not None and self.validate_ema:
             # the averaged weights under the same precision and centre crop (VALIDATION_EMA: false turns this second pass off)
-            loss_ema, accuracy_ema, i = self._evaluate(self.step.ema.module)
-            self.val_loss_ema = loss_ema
-            print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| val_loss_ema {loss_ema:.5f}\t| val_accuracy_ema {accuracy_ema:.5f}")
-            self._log({"epoch": epoch, "val_loss_ema": loss_ema, "val_accuracy_ema": accuracy_ema})
-        return avg_val_loss, accuracy
+            self._validation_pass(self.step.ema.module, "_ema", epoch)
+        if self.objective.runs_probes:
+            banks = {}                                                 # the frozen-feature banks of this epoch, by pooling: extracted once, shared by both probes
+            if self.knn is not None and (epoch + 1) % self.knn["every"] == 0:
+                self.knn_validate(epoch, banks=banks)
+            if self.linear is not None and (epoch + 1) % self.linear["every"] == 0:
+                self.linear_validate(epoch, banks=banks)
+        return result
 
     def evaluate_samples(self):
-        if self.regression is not None:
-            return self._evaluate_samples_regression()
+        objective = self.objective
         self.model.eval()
         loader = torch.utils.data.DataLoader(self.val_data, batch_size=1, shuffle=False, num_workers=self.num_workers)
-        accuracy, wrong = 0, []
+        objective.begin_samples()
         with torch.no_grad(), self.model.precision(self.validation_precision):
             for batch in loader:
-                fMRI, label = self._unpack(batch)
-                prediction = self.model(self._center(fMRI.to(self.device))).argmax(dim=1).item()
-                actual = int(label.item())
-                if prediction != actual:
-                    wrong.append((batch[0][0] if isinstance(batch[0], (list, tuple)) else batch[0], prediction, actual))
-                accuracy += prediction == actual
-        acc = accuracy / max(1, len(loader)) * 100
-        print(f"Accuracy: {acc:.2f}%")
-        print(f"Wrong predictions: {wrong}")
-        return acc, wrong
+                fMRI, truth = self._unpack(batch)
+                subject = batch[0][0] if isinstance(batch[0], (list, tuple)) else batch[0]
+                objective.sample(subject, self._center(fMRI.to(self.device)), truth)
+        return objective.samples(len(loader))
 
 
 def class_weights_from_counts(counts):
