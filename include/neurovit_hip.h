@@ -1350,6 +1350,69 @@ int nv_probe_step(float* W, float* b, const float* dW, const float* db, float* m
 int nv_probe_predict(const float* Q, long ldq, int Nq, int d, const float* mean, const float* rstd, const float* W, const float* b, int H, int C,
                      float* logits, long ldl, float* probs, long ldp, void* stream);
 
+/* (added within revision 8 - new symbols only, nothing existing changes) classification metrics on the device: what a validation pass of the
+ * classifier reports, accumulated with one launch per batch and no host read, an exact one-vs-rest ROC-AUC over a bank of probabilities and
+ * the labels of segments (subjects).  Every call takes a stream, reads nothing back and uses no atomics; every sum has one fixed order, so
+ * results are bit-identical from run to run.  Limits (NV_ERR_ARG before any launch): 2 <= C <= NV_CLS_MAX_C, 1 <= bins <= NV_CLS_MAX_BINS,
+ * B, N >= 1, lds / ldb >= C, state 8-byte aligned, row0 >= 0 and row0 + B <= capacity, N <= NV_CLS_AUC_MAX_N.
+ * nv_cls_metrics_update: scores fp32 [B, C] (lds), labels int32 [B], kind NV_CLS_LOGITS | NV_CLS_PROBS.  A row is VALID iff its label lies in
+ *   [0, C) (the probe's rule) and all its C scores are finite; any other row adds 1 to `skipped` and carries nothing else.  Per valid row, in
+ *   double from the fp32 inputs: pred = the lowest index of the maximal fp32 score (compared as floats: no rounding enters the arg-max);
+ *   LOGITS: p_c = exp(z_c - m) / S, m the row maximum, S = sum_c exp(z_c - m) in ascending c, nll = (m + log S) - z_y;  PROBS: p_c = score_c
+ *   as given (not renormalised), nll = -log p_y;  brier = sum_c (p_c - [c == y])^2;  conf = p_pred;  bin = min(bins - 1, int(conf * bins))
+ *   (a conf below 0 - possible under PROBS only - goes to bin 0).
+ *   state: double [nv_cls_metrics_state_doubles(C, bins)], zeroed by the caller; counts are exact integers held in doubles:
+ *     [0] n  [1] skipped  [2] sum nll  [3] sum over the calls of (sum nll / n_valid of the call)  [4] calls with a valid row  [5] sum brier
+ *     [NV_CLS_STATE_HEAD + t C + p] confusion, true class t x predicted class p
+ *     then per bin b: count [bins], sum conf [bins], sum correct [bins].
+ *   One workgroup per call: thread t takes the rows t, t + 256, ...; its double partials of nll and brier go through the wave butterfly and
+ *   the four waves in order; the confusion cells and the bins are counted from the rows' records in LDS, 256 rows at a time, each cell and
+ *   each bin by one owner thread in ascending row order.  The state is updated by plain read-modify-write: the stream orders the calls.
+ *   bank_probs fp32 [capacity, C] (ldb) and bank_labels int32 [capacity] (both or neither): rows row0 .. row0 + B - 1 receive float(p_c) and
+ *   the label; a skipped row gets zeros and label -1.
+ * nv_cls_auc: exact one-vs-rest ROC-AUC per class by counting pairs (the Mann-Whitney statistic, ties counted as a half) - no sort.
+ *   probs fp32 [N, C] (ldp), labels int32 [N]; a row whose label lies outside [0, C) (-1 as nv_cls_metrics_update writes it) is not used.
+ *     gt_c = #{(i, j): y_i = c, y_j usable and != c, p_ic > p_jc},  eq_c = the same with ==,  AUC_c = (gt_c + eq_c / 2) / (n_pos n_neg).
+ *   The comparisons are on the fp32 values, so every count is an exact integer (a NaN cell compares false both ways).  Workgroup (x, y):
+ *   rows i in [256 x, 256 x + 256), one per thread - a row is a positive of exactly its own class -, against the j range of split y, streamed
+ *   through LDS in tiles (16-byte loads when ldp == C and probs is 16-byte aligned).  A thread counts in 32 bits: its count is at most the rows
+ *   of one split <= N <= NV_CLS_AUC_MAX_N = 2^20 < 2^31 (enforced); the per-class totals of a workgroup (64-bit) go to the workspace of
+ *   nv_cls_auc_workspace_bytes(N, C, splits) bytes and a second launch adds them in 64 bits.  splits: 0 = automatic, up to
+ *   NV_CLS_AUC_MAX_SPLITS; the counts do not depend on it, on the grid or on the CU count.  out: double [C, NV_CLS_AUC_COLS] = auc, n_pos,
+ *   n_neg, gt, eq (all exact in a double: gt <= N^2 / 4 <= 2^38); auc is NaN where a class has no positive or no negative row.
+ *   The cost is quadratic: measured 1.35 ms at N = 78 820 (MI355X), i.e. about 0.25 s at NV_CLS_AUC_MAX_N - the limit is set by that run time,
+ *   not by the counters: larger banks belong to a sort.
+ * nv_segment_labels: out[g] (int32 [G]) = labels[order[offsets[g]]], the label of the segment's first row (order / offsets: the device CSR
+ *   of nv_segment_mean); an empty segment gets -1.  mixed (int32 [1], overwritten): the number of segments that hold a row whose label is >= 0
+ *   and differs from the segment's.  One workgroup; entries of order outside [0, N) are skipped.
+ * nv_cls_metrics_finish: state (+ auc, the table of nv_cls_auc, or NULL) -> out fp32 [nv_cls_metrics_table_floats(C)]:
+ *     [0 .. NV_CLS_SCALARS): n, skipped, accuracy, balanced_accuracy (mean recall over the classes with support), macro_f1 (mean of
+ *       2TP / (2TP + FP + FN) over the classes where that denominator is not 0), nll (mean over rows), val_loss (mean over the calls of the
+ *       calls' means), brier, ece = sum_b |sum correct_b - sum conf_b| / n, macro_auc (mean over the classes whose AUC is defined)
+ *     then [C, NV_CLS_CLASS_COLS]: support, recall, precision, f1, auc;  then the confusion matrix [C, C] as fp32 - exact up to 2^24 rows.
+ *   Undefined quantities are NaN, never 0: everything but n / skipped for n = 0, recall without support, precision without a prediction, f1
+ *   with a zero denominator, an AUC with one side empty or without a table, a mean over no class. */
+#define NV_CLS_LOGITS 0
+#define NV_CLS_PROBS 1
+#define NV_CLS_MAX_C 64
+#define NV_CLS_MAX_BINS 64
+#define NV_CLS_STATE_HEAD 6
+#define NV_CLS_SCALARS 10
+#define NV_CLS_CLASS_COLS 5
+#define NV_CLS_AUC_COLS 5
+#define NV_CLS_AUC_MAX_N (1 << 20)
+#define NV_CLS_AUC_MAX_SPLITS 256
+long nv_cls_metrics_state_doubles(int C, int bins);
+long nv_cls_metrics_table_floats(int C);
+int nv_cls_metrics_update(const float* scores, long lds, const int* labels, int B, int C, int bins, int kind, double* state, float* bank_probs,
+                          long ldb, int* bank_labels, long row0, long capacity, void* stream);
+int nv_cls_auc_splits(int N, int C, int splits);
+long nv_cls_auc_workspace_bytes(int N, int C, int splits);
+int nv_cls_auc(const float* probs, long ldp, const int* labels, int N, int C, int splits, double* out, void* workspace, long ws_bytes,
+               void* stream);
+int nv_segment_labels(const int* labels, int N, const int* order, const int* offsets, int G, int* out, int* mixed, void* stream);
+int nv_cls_metrics_finish(const double* state, int C, int bins, const double* auc, float* out, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

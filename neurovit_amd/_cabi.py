@@ -105,6 +105,15 @@ REG_METRIC_SLOTS = 9                                        # NV_REG_METRIC_SLOT
 REG_METRIC_NAMES = ("n", "mae", "rmse", "bias", "r", "r2")  # the columns nv_reg_metrics_finish writes
 
 
+CLS_KINDS = {"logits": 0, "probs": 1}                       # NV_CLS_LOGITS / NV_CLS_PROBS
+CLS_MAX_C, CLS_MAX_BINS, CLS_STATE_HEAD = 64, 64, 6         # NV_CLS_MAX_C, NV_CLS_MAX_BINS, NV_CLS_STATE_HEAD (doubles in front of the confusion matrix)
+CLS_STATE_NAMES = ("n", "skipped", "nll_sum", "batch_mean_sum", "batches", "brier_sum")      # the head of nv_cls_metrics_update's state
+CLS_METRIC_NAMES = ("n", "skipped", "accuracy", "balanced_accuracy", "macro_f1", "nll", "val_loss", "brier", "ece", "macro_auc")   # NV_CLS_SCALARS
+CLS_CLASS_METRIC_NAMES = ("support", "recall", "precision", "f1", "auc")                     # NV_CLS_CLASS_COLS: the per-class columns of the table
+CLS_AUC_NAMES = ("auc", "n_pos", "n_neg", "gt", "eq")       # NV_CLS_AUC_COLS: the columns of nv_cls_auc's double table
+CLS_AUC_MAX_N, CLS_AUC_MAX_SPLITS = 1 << 20, 256            # NV_CLS_AUC_MAX_N, NV_CLS_AUC_MAX_SPLITS
+
+
 POOL_MODES = {"cls": 0, "mean": 1, "patch_mean": 2}         # NV_POOL_CLS / NV_POOL_MEAN / NV_POOL_PATCH_MEAN
 KNN_WEIGHTS = {"uniform": 0, "softmax": 1}                  # NV_KNN_UNIFORM / NV_KNN_SOFTMAX
 KNN_MAX_K = 128                                             # NV_KNN_MAX_K

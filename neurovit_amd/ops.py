@@ -675,6 +675,160 @@ class RegressionMetrics:
         return {name: out[:, i].clone() for i, name in enumerate(REG_METRIC_NAMES)}
 
 
+def cls_auc(probs: torch.Tensor, labels: torch.Tensor, splits: int = 0) -> torch.Tensor:
+    """nv_cls_auc: the exact one-vs-rest ROC-AUC per class of probs f32 [N, C] (a row-strided view passes its leading dimension) under labels
+    int32 [N] (a label outside [0, C) = the row is not used), by counting pairs, ties as a half.  Returns float64 [C, 5] on the device:
+    auc (NaN where a class has no positive or no negative row), n_pos, n_neg, gt, eq (_cabi.CLS_AUC_NAMES); no host read."""
+    _need_cuda(probs, labels)
+    if probs.dtype != torch.float32 or probs.dim() != 2 or probs.stride(1) != 1 or probs.shape[0] < 1:
+        raise ValueError(f"cls_auc: float32 [N, C] with N >= 1 and unit column stride expected, got {tuple(probs.shape)} {probs.dtype}")
+    N, C = probs.shape
+    labels = _i32(labels, N, "cls_auc: labels")
+    nb = lib.nv_cls_auc_workspace_bytes(N, C, int(splits))
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=probs.device)
+    out = torch.empty((C, len(_cabi.CLS_AUC_NAMES)), dtype=torch.float64, device=probs.device)
+    check(lib.nv_cls_auc(_p(probs), probs.stride(0), _p(labels), N, C, int(splits), _p(out), _p(ws), nb, _stream()), "nv_cls_auc")
+    return out
+
+
+def segment_labels(labels: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor):
+    """nv_segment_labels: (the label of each segment's first row int32 [G] - an empty segment gets -1 -, mixed int32 [1] = the number of
+    segments that hold another valid label), device tensors; order / offsets from segment_csr."""
+    _need_cuda(labels, order, offsets)
+    N, G = labels.numel(), offsets.numel() - 1
+    labels, order, offsets = _i32(labels, N, "segment_labels: labels"), _i32(order, N, "order"), _i32(offsets, G + 1, "offsets")
+    out = torch.empty(G, dtype=torch.int32, device=labels.device)
+    mixed = torch.empty(1, dtype=torch.int32, device=labels.device)
+    check(lib.nv_segment_labels(_p(labels), N, _p(order), _p(offsets), G, _p(out), _p(mixed), _stream()), "nv_segment_labels")
+    return out, mixed
+
+
+class ClassificationMetrics:
+    """Validation metrics of a classifier, accumulated on the device (nv_cls_metrics_*, nv_cls_auc, nv_segment_labels): update() makes one
+    launch and no host read, compute() one host read.  scores: logits (kind "logits") or probabilities (kind "probs", e.g. what
+    LinearProbe.predict / knn_predict return) float32 [B, C]; labels: integers [B]; a row whose label lies outside [0, C) or that holds a
+    non-finite score is counted in "skipped" and nowhere else.
+    compute() -> {"n", "skipped", "accuracy", "balanced_accuracy", "macro_f1", "nll", "val_loss" (the mean over the updates of their mean
+    nll: the reference's validation loss), "brier", "ece": floats; "class_support", "class_recall", "class_precision", "class_f1": float32 [C];
+    "confusion": int64 [C, C], true x predicted}.  Undefined quantities are NaN.  With capacity > 0 update() also files the rows'
+    probabilities and labels in a preallocated bank, and compute() adds "macro_auc" and "class_auc" (exact one-vs-rest ROC-AUC, ties as a
+    half); with `groups` (host subject ids per row, as FeatureBank takes them) the same set once more under "subject_*" keys - the bank's
+    probabilities averaged per subject, the subject's label from its first row - and "subject_mixed_labels", the number of subjects that hold
+    another valid label.  With two classes also "sensitivity" (recall of class 1), "specificity" (recall of class 0) and "auc" (class 1's)."""
+
+    def __init__(self, num_classes: int, capacity: int = 0, bins: int = 15, device="cuda"):
+        self.C, self.capacity, self.bins, self.device = int(num_classes), int(capacity), int(bins), torch.device(device)
+        if not 2 <= self.C <= _cabi.CLS_MAX_C or not 1 <= self.bins <= _cabi.CLS_MAX_BINS or self.capacity < 0:
+            raise ValueError(f"ClassificationMetrics: num_classes = {num_classes} in [2, {_cabi.CLS_MAX_C}], bins = {bins} in [1, {_cabi.CLS_MAX_BINS}] and "
+                             f"capacity = {capacity} >= 0 expected")
+        if self.capacity > _cabi.CLS_AUC_MAX_N:
+            raise ValueError(f"ClassificationMetrics: capacity = {capacity} above {_cabi.CLS_AUC_MAX_N} rows (nv_cls_auc)")
+        if self.device.type != "cuda":
+            raise RuntimeError("ClassificationMetrics runs on the MI355X (cuda) device - there is no CPU fallback")
+        self.state = torch.zeros(lib.nv_cls_metrics_state_doubles(self.C, self.bins), dtype=torch.float64, device=self.device)
+        self.bank_probs = torch.zeros((self.capacity, self.C), dtype=torch.float32, device=self.device) if self.capacity else None
+        self.bank_labels = torch.full((self.capacity,), -1, dtype=torch.int32, device=self.device) if self.capacity else None
+        self._host_groups = torch.full((self.capacity,), -1, dtype=torch.int32)
+        self.size, self.has_groups = 0, False
+
+    def reset(self) -> None:
+        self.state.zero_()
+        self._host_groups.fill_(-1)
+        self.size, self.has_groups = 0, False
+
+    def update(self, scores: torch.Tensor, labels: torch.Tensor, groups=None, kind: str = "logits") -> None:
+        if kind not in _cabi.CLS_KINDS:
+            raise ValueError(f"ClassificationMetrics.update: kind must be 'logits' or 'probs', got {kind!r}")
+        if (not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[1] != self.C or scores.shape[0] < 1 or scores.dtype != torch.float32
+                or not scores.is_cuda or scores.stride(1) != 1):
+            raise ValueError(f"ClassificationMetrics.update: scores must be float32 [B, {self.C}] on the device (B >= 1, unit column stride)")
+        B = scores.shape[0]
+        labels = torch.as_tensor(labels)
+        if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool or labels.numel() != B:
+            raise ValueError(f"ClassificationMetrics.update: {B} integer labels expected, got {tuple(labels.shape)} {labels.dtype}")
+        labels = labels.reshape(-1).to(scores.device, torch.int32).contiguous()
+        host_groups = None
+        if groups is not None:
+            if not self.capacity:
+                raise ValueError("ClassificationMetrics.update: groups need the bank - construct with capacity > 0")
+            g = torch.as_tensor(groups)
+            if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool or g.numel() != B:
+                raise ValueError(f"ClassificationMetrics.update: {B} integer group ids expected, got {tuple(g.shape)} {g.dtype}")
+            host_groups = g.detach().reshape(-1).to("cpu", torch.int32)
+        if self.capacity and self.size + B > self.capacity:
+            raise ValueError(f"ClassificationMetrics.update: {self.size} + {B} rows exceed the capacity {self.capacity}")
+        check(lib.nv_cls_metrics_update(_p(scores), scores.stride(0), _p(labels), B, self.C, self.bins, _cabi.CLS_KINDS[kind], _p(self.state),
+                                        _p(self.bank_probs), self.C, _p(self.bank_labels), self.size, self.capacity, _stream()), "nv_cls_metrics_update")
+        if self.capacity:
+            if host_groups is not None:
+                self._host_groups[self.size:self.size + B] = host_groups
+                self.has_groups = True
+            self.size += B
+
+    def state_parts(self, state: Optional[torch.Tensor] = None) -> dict:
+        """views of the double state (no host read): "head" [6] (_cabi.CLS_STATE_NAMES), "confusion" [C, C], "bin_count" / "bin_conf" /
+        "bin_correct" [bins]"""
+        s = self.state if state is None else state
+        h, cc, nb = _cabi.CLS_STATE_HEAD, self.C * self.C, self.bins
+        return {"head": s[:h], "confusion": s[h:h + cc].view(self.C, self.C), "bin_count": s[h + cc:h + cc + nb],
+                "bin_conf": s[h + cc + nb:h + cc + 2 * nb], "bin_correct": s[h + cc + 2 * nb:h + cc + 3 * nb]}
+
+    def _finish(self, state, auc) -> torch.Tensor:
+        out = torch.empty(lib.nv_cls_metrics_table_floats(self.C), dtype=torch.float32, device=self.device)
+        check(lib.nv_cls_metrics_finish(_p(state), self.C, self.bins, _p(auc), _p(out), _stream()), "nv_cls_metrics_finish")
+        return out
+
+    def compute_device(self) -> dict:
+        """Device tensors, no host read: "table" float32 [10 + 5 C + C C] as nv_cls_metrics_finish writes it, "auc" float64 [C, 5] (nv_cls_auc;
+        with a bank), and with groups "subject_table", "subject_auc", "subject_labels" int32 [G], "subject_probs" float32 [G, C],
+        "subject_state" and "subject_mixed" int32 [1]."""
+        out = {}
+        filled = self.capacity and self.size > 0
+        if filled:
+            out["auc"] = cls_auc(self.bank_probs[:self.size], self.bank_labels[:self.size])
+        out["table"] = self._finish(self.state, out.get("auc"))
+        if filled and self.has_groups and int(self._host_groups[:self.size].max()) >= 0:
+            order, offsets = segment_csr(self._host_groups[:self.size])
+            G = offsets.numel() - 1
+            pooled = segment_mean(self.bank_probs[:self.size], order, offsets)
+            subject_labels, mixed = segment_labels(self.bank_labels[:self.size], order, offsets)
+            state = torch.zeros_like(self.state)
+            check(lib.nv_cls_metrics_update(_p(pooled), pooled.stride(0), _p(subject_labels), G, self.C, self.bins, _cabi.CLS_KINDS["probs"], _p(state),
+                                            None, 0, None, 0, 0, _stream()), "nv_cls_metrics_update")
+            out["subject_auc"] = cls_auc(pooled, subject_labels)
+            out["subject_table"] = self._finish(state, out["subject_auc"])
+            out.update(subject_labels=subject_labels, subject_probs=pooled, subject_state=state, subject_mixed=mixed)
+        return out
+
+    def _named(self, table: torch.Tensor, prefix: str, with_auc: bool) -> dict:
+        C, ns, nc = self.C, len(_cabi.CLS_METRIC_NAMES), len(_cabi.CLS_CLASS_METRIC_NAMES)
+        got = {prefix + name: float(table[i]) for i, name in enumerate(_cabi.CLS_METRIC_NAMES)}
+        per_class = table[ns:ns + C * nc].reshape(C, nc)
+        for j, name in enumerate(_cabi.CLS_CLASS_METRIC_NAMES):
+            got[f"{prefix}class_{name}"] = per_class[:, j].clone()
+        got[prefix + "confusion"] = table[ns + C * nc:ns + C * nc + C * C].reshape(C, C).to(torch.int64)
+        if not with_auc:
+            del got[prefix + "macro_auc"], got[prefix + "class_auc"]
+        if C == 2:
+            got[prefix + "sensitivity"], got[prefix + "specificity"] = float(per_class[1, 1]), float(per_class[0, 1])
+            if with_auc:
+                got[prefix + "auc"] = float(per_class[1, 4])
+        return got
+
+    def compute(self) -> dict:
+        dev = self.compute_device()
+        parts = [dev["table"]]
+        if "subject_table" in dev:
+            parts += [dev["subject_table"], dev["subject_mixed"].to(torch.float32)]
+        host = torch.cat(parts).cpu()              # the one host read
+        T = dev["table"].numel()
+        got = self._named(host[:T], "", bool(self.capacity))
+        if "subject_table" in dev:
+            got.update(self._named(host[T:2 * T], "subject_", True))
+            got["subject_mixed_labels"] = int(host[2 * T])
+        return got
+
+
 def head_step_soft(x, gamma, beta, W, bias, labels, label_smoothing=0.0, class_weight=None, mix=None, eps=1e-5, grad_scale=1.0, scale_state=None):
     """nv_head_step_soft: head_step with the soft-target cross-entropy.  Returns what head_step returns."""
     B, n, d = x.shape

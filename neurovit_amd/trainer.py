@@ -15,6 +15,7 @@ import contextlib
 import datetime
 import os
 import time
+import warnings
 from dataclasses import dataclass
 from typing import Optional
 
@@ -685,6 +686,7 @@ class _Supervised:
     loss_name = "train_loss"
     runs_probes = False
     own_arithmetic = False            # True: validation runs in the training arithmetic, not in VALIDATION_PRECISION
+    wants_subjects = False            # True: _validation_pass leaves the batch's subjects (or None) in `subjects` in front of every `batch`
     step_options: dict = {}
 
     def __init__(self, trainer):
@@ -755,6 +757,51 @@ class _Supervised:
 
     def save_beside(self, path, epoch):
         pass
+
+
+class _Measured(_Supervised):
+    """The classifier under VALIDATION_METRICS: training as _Supervised; a validation pass accumulates in ops.ClassificationMetrics - one launch
+    per batch from the logits, the batch's subjects as groups when it carries any, no host read - and reports from ONE host read: val_loss
+    (the mean of the batches' mean negative log-likelihood: _Supervised's number when no class weights are set - the metrics are unweighted),
+    accuracy, balanced accuracy, macro F1, ROC-AUC, nll, Brier score and calibration error, per volume and per subject."""
+    wants_subjects = True
+
+    def begin(self):
+        from .features import GroupIndex
+        if torch.device(self.t.device).type != "cuda":
+            raise RuntimeError("Trainer: VALIDATION_METRICS runs on the MI355X (cuda) device - there is no CPU fallback")
+        if getattr(self.t, "metrics", None) is not None:
+            self.t.metrics.reset()
+        self.index, self.grouped, self.subjects = GroupIndex(), True, None
+
+    def batch(self, model, fMRI, label, i):
+        from .ops import ClassificationMetrics
+        t = self.t
+        outputs = model(fMRI).float().contiguous()
+        if getattr(t, "metrics", None) is None:        # the class count is the logits' width, for the 3D and the 4D model alike
+            t.metrics = ClassificationMetrics(outputs.shape[1], capacity=len(t.val_data), bins=t.validation_metrics["bins"], device=t.device)
+        self.grouped = self.grouped and self.subjects is not None
+        t.metrics.update(outputs, label, groups=self.index(self.subjects) if self.grouped else None)
+
+    def report(self, epoch, tag, i):
+        t = self.t
+        if not self.grouped:
+            t.metrics.has_groups = False
+        got = t.metrics.compute()                      # the one host read
+        two = t.metrics.C == 2
+        fields = {"loss": got["val_loss"], "accuracy": got["accuracy"], "balanced_accuracy": got["balanced_accuracy"], "macro_f1": got["macro_f1"],
+                  "auc": got["auc"] if two else got["macro_auc"], "nll": got["nll"], "brier": got["brier"], "ece": got["ece"]}
+        if two:
+            fields.update(sensitivity=got["sensitivity"], specificity=got["specificity"])
+        if "subject_accuracy" in got:
+            fields.update(subject_accuracy=got["subject_accuracy"], subject_balanced_accuracy=got["subject_balanced_accuracy"],
+                          subject_auc=got["subject_auc"] if two else got["subject_macro_auc"])
+        fields = {name: round(value, 5) for name, value in fields.items()}
+        setattr(t, f"val_loss{tag}", fields["loss"])
+        setattr(t, f"val_metrics{tag}", got)
+        print(f"[VALIDATION] epoch {epoch}\t| total_batch {i}\t| " + "\t| ".join(f"val_{name}{tag} {value:.5f}" for name, value in fields.items()))
+        t._log({"epoch": epoch, **{f"val_{name}{tag}": value for name, value in fields.items()}})
+        return fields["loss"], fields["accuracy"]
 
 
 class _Regression(_Supervised):
@@ -913,7 +960,14 @@ class Trainer:
         the accuracy, `validate` reports val_loss, MAE, RMSE, Pearson r and R^2 (ops.RegressionMetrics: one host read per epoch) - also for
         the weight average -, `evaluate_samples` returns the mean absolute error and (subject, prediction, actual) per sample.  Mixup /
         CutMix blend the targets; TRAINING_LABEL_SMOOTHING / TRAINING_CLASS_WEIGHTS do not go with it.
-    Structure: `__init__` picks ONE objective object (_Supervised, _Regression or _Pretraining above) that holds all the three differ in;
+      * VALIDATION_METRICS: true (with VALIDATION_CALIBRATION_BINS, default 15, and VALIDATION_SUBJECT_INDEX, default 0) validates the
+        classifier through ops.ClassificationMetrics: one launch per batch and one host read per pass in the place of the reference's two
+        .item() per batch; `validate` logs val_loss (the reference's mean of batch means, unweighted), val_accuracy, val_balanced_accuracy,
+        val_macro_f1, val_auc (exact, ties as a half; macro over the classes for more than two), val_nll, val_brier, val_ece - for two
+        classes also val_sensitivity / val_specificity, and when the batches carry subjects val_subject_accuracy /
+        val_subject_balanced_accuracy / val_subject_auc from the subject-averaged probabilities - and keeps the whole dict, confusion
+        matrices included, as `val_metrics` (`val_metrics_ema` for the weight average).  Absent: the reference's pass, unchanged.
+    Structure: `__init__` picks ONE objective object (_Supervised, _Measured, _Regression or _Pretraining above) that holds all the three differ in;
     `train` is one loop, `validate` one pass routine (for the model, then its weight average, then the probes of "mim"), `evaluate_samples`
     one loop - no other method asks which objective runs.
     """
@@ -937,7 +991,9 @@ class Trainer:
         self.criterion = CrossEntropyLoss(weight=class_weights)          # validation: never smoothed, never mixed; it carries the class weights
         self.pretrain = self.objective_from_config(config)             # None: the supervised step, as ever
         # the one place that chooses the objective: everything the three differ in lives in that object
-        self.objective = (_Pretraining if self.pretrain is not None else _Supervised if self.regression is None else _Regression)(self)
+        self.validation_metrics = self.metrics_from_config(config)     # None: the reference's per-batch accuracy, as ever
+        self.objective = (_Pretraining if self.pretrain is not None else _Regression if self.regression is not None
+                          else _Supervised if self.validation_metrics is None else _Measured)(self)
         self.save_state, self.resume_from = self.state_options_from_config(config)
         self.step = self.objective.make_step(config, model, smoothing, class_weights)
         self.knn = self.knn_from_config(config)                        # None: no kNN validation beside the pretraining loss, as ever
@@ -996,6 +1052,26 @@ class Trainer:
         if isinstance(index, bool) or not isinstance(index, int):
             raise TypeError(f"REGRESSION_TARGET_INDEX must be an integer, got {index!r}")
         return dict(kind=kind, delta=float(delta), index=index)
+
+    @staticmethod
+    def metrics_from_config(config):
+        """VALIDATION_METRICS (optional; absent, None or false = None: the validation pass of the reference, nothing changes) -> dict(bins,
+        subject_index) from VALIDATION_CALIBRATION_BINS (default 15, 1 .. 64) and VALIDATION_SUBJECT_INDEX (the batch element that holds the
+        subjects, default 0).  With TRAINING_CLASS_WEIGHTS a UserWarning says that val_loss is then the unweighted one.  For the classifier only: "regression" has its own metrics and "mim" no classes (ValueError)."""
+        if not config.get('VALIDATION_METRICS', None):
+            return None
+        objective = config.get('TRAINING_OBJECTIVE', None)
+        if objective in ("regression", "mim"):
+            raise ValueError(f"VALIDATION_METRICS does not go with TRAINING_OBJECTIVE {objective!r}: the classification metrics belong to the classifier")
+        bins, index = _pick(config, 'VALIDATION_CALIBRATION_BINS', 15), _pick(config, 'VALIDATION_SUBJECT_INDEX', 0)
+        if isinstance(bins, bool) or not isinstance(bins, int) or not 1 <= bins <= 64:
+            raise ValueError(f"VALIDATION_CALIBRATION_BINS must be an integer in [1, 64], got {bins!r}")
+        if isinstance(index, bool) or not isinstance(index, int):
+            raise ValueError(f"VALIDATION_SUBJECT_INDEX must be an integer, got {index!r}")
+        if config.get('TRAINING_CLASS_WEIGHTS', None) is not None:
+            warnings.warn("VALIDATION_METRICS with TRAINING_CLASS_WEIGHTS: the metrics are unweighted, so val_loss is the plain mean of the batches' "
+                          "negative log-likelihood, not the class-weighted loss the validation pass reports without the key - the two curves are not comparable")
+        return dict(bins=bins, subject_index=index)
 
     @staticmethod
     def ema_from_config(config) -> dict:
@@ -1219,6 +1295,14 @@ class Trainer:
             raise ValueError(f"PRETRAIN_KNN_TEMPERATURE must be positive, got {temperature!r}")
         return dict(k=tuple(ks), temperature=temperature, pool=Trainer._probe_pool(config, 'PRETRAIN_KNN_POOL'))
 
+    @staticmethod
+    def _batch_subjects(batch, at: int = 0):
+        """the subjects a batch carries in front of the volume - a list of names or an integer vector at batch[at] - or None"""
+        subjects = batch[at] if len(batch) >= 3 else None
+        if torch.is_tensor(subjects) and (subjects.dim() != 1 or subjects.is_floating_point()):
+            subjects = None
+        return subjects
+
     def _knn_features(self, dataset, index, opts):
         """A FeatureBank of the centre windows of `dataset` in eval mode (features L2-normalised): labels or regression targets from the
         batches, groups from their subjects when they carry any (a list of names or an integer vector in front of the volume)."""
@@ -1227,9 +1311,7 @@ class Trainer:
         bank, grouped = None, True
         for batch in loader:
             fMRI, truth = self._unpack(batch)
-            subjects = batch[0] if len(batch) >= 3 else None
-            if torch.is_tensor(subjects) and (subjects.dim() != 1 or subjects.is_floating_point()):
-                subjects = None
+            subjects = self._batch_subjects(batch)
             grouped = grouped and subjects is not None
             x = self._center(fMRI.to(self.device))
             if bank is None:
@@ -1367,6 +1449,8 @@ class Trainer:
         with torch.no_grad(), contextlib.nullcontext() if objective.own_arithmetic else model.precision(self.validation_precision):
             for i, batch in enumerate(self.val_dataloader):
                 fMRI, truth = self._unpack(batch)
+                if objective.wants_subjects:
+                    objective.subjects = self._batch_subjects(batch, self.validation_metrics["subject_index"])
                 objective.batch(model, self._center(fMRI.to(self.device)), truth, i)
         return objective.report(epoch, tag, i)
 
