@@ -1413,6 +1413,64 @@ int nv_cls_auc(const float* probs, long ldp, const int* labels, int N, int C, in
 int nv_segment_labels(const int* labels, int N, const int* order, const int* offsets, int G, int* out, int* mixed, void* stream);
 int nv_cls_metrics_finish(const double* state, int C, int bins, const double* auc, float* out, void* stream);
 
+/* (added within revision 8 - new symbols only, nothing existing changes) group-level permutation tests with the maximum statistic (Nichols &
+ * Holmes): where are N maps fp32 [N, V] (ldx; one per subject) consistently non-zero (one sample, sign flips), or where do two groups differ
+ * (two samples, label permutation, pooled-variance Student t), with the family-wise error controlled over all voxels.  Every call takes a
+ * stream, reads nothing back and uses no atomics; every count is an exact integer and no output bit depends on the grid, the split count or
+ * the CU count.  Limits (NV_ERR_ARG before any launch): 2 <= N <= NV_PERM_MAX_N (3 and both groups non-empty for two samples),
+ * 1 <= R <= NV_PERM_MAX_R, V >= 1, ldx >= V, splits in [0, NV_PERM_MAX_SPLITS] (0 = automatic), exact enumeration only for one sample with
+ * R = 2^N <= NV_PERM_MAX_R.
+ * The statistic.  Per voxel, in double over the subjects in ascending order (every product and sum rounded on its own): T = sum x_i,
+ *   Q = sum x_i^2, and for two samples S_A = the sum over the subjects of label 1.
+ *     one sample:   a = 0,           c = 1 / sqrt(N Q),                     u = (S - a) c,  t = u sqrt((N - 1) / (1 - u^2))
+ *     two samples:  a = n_A T / N,   c = 1 / sqrt(n_A n_B SS / N), SS = Q - T^2 / N,        t = u sqrt((N - 2) / (1 - u^2))
+ *   with S = sum_i m_i x_i for a row m of the design (signs +-1; 0/1 marks of group A = label 1, so t > 0 where group 1 has the larger
+ *   mean).  t is strictly increasing in u on [-1, 1]; the permutation loop works on u alone.  a and c are rounded to fp32 once; in the loop
+ *   u = float(float(S - a) * c) with S accumulated in fp32 on the matrix unit, clamped to [-1, 1].  The statistic is |u| (NV_PERM_TAIL_TWO),
+ *   u (_GREATER) or -u (_LESS); ties count (>=).
+ * A voxel is INVALID when it lies outside mask (uint8 [V], 0 = outside; NULL = no mask), holds a non-finite value, has Q == 0 (one sample)
+ *   or SS <= 0 (two samples), or its c does not fit fp32: a = c = 0, t and both p-values NaN, both counts 0, counted in n_invalid, in no
+ *   maximum.  A voxel whose values are all equal and not zero has t = +-inf in the one-sample test.
+ * nv_perm_design: M fp32 [R, Npad], Npad = N rounded up to 4, pad columns 0.  Row 0 is the observed labelling (all +1; m_i = [labels_i == 1]).
+ *   One sample, exact (R = 2^N): subject i of row r is -1 iff bit i of r is set.  One sample, random, r >= 1: -1 iff bit (i & 63) of
+ *   nv_hash64(seed ^ 0x5045524D31, r ceil(N / 64) + (i >> 6)) is set.  Two samples, r >= 1: keys nv_hash64(seed ^ 0x5045524D32, r N + i);
+ *   subject i is in group A iff its ascending rank among the row's keys is below n_a (equal keys: the lower index first).  labels: device
+ *   int32 [N] (two samples only; n_a must be their number of ones).  nv_hash64 as for nv_augment_params.
+ * nv_perm_stats: a, c, t fp32 [V] (t: the observed statistic from the double u, rounded once) and n_invalid int32 [1].
+ * nv_perm_maxstat: P = M X is never written.  A workgroup stages the [Npad, NV_PERM_TILE_V] slab of its voxel tile in LDS once and walks its
+ *   rows of M (from L2) in tiles of NV_PERM_TILE_R on v_mfma_f32_16x16x4_f32 - fp32 operands on purpose: the comparisons stat_r >= stat_0
+ *   decide the p-values.  Fused epilogue: the row maxima of the tile's valid voxels go to a table [R, tiles of V], the per-voxel counts
+ *   #{r: stat_r(v) >= stat_0(v)} stay in registers over the whole walk (stat_0 comes from the same product of row 0, so the same bits).
+ *   The rows are split over the grid's second dimension (splits); the split partials of the counts are integers, added in split order.
+ * nv_perm_finish (two launches): max_stat fp32 [R] (-0 as +0), max_t fp32 [R] = the transform of max_stat, formed in double;
+ *   count_unc / count_fwe int32 [V] (count_fwe[v] = #{r: max_stat[r] >= stat_0(v)}, R V comparisons); p = float(count / R), row 0 counted,
+ *   so p >= 1 / R; critical_t fp32 [n_alphas] = the transform of the k-th smallest row maximum, k = nv_perm_rank(alpha, R) =
+ *   R - floor(alpha R + 1e-9), i.e. the smallest m with #{r: max_r <= m} >= ceil((1 - alpha) R), found by counting (alphas: HOST doubles in
+ *   (0, 1), at most NV_PERM_MAX_ALPHAS).  c: the array of nv_perm_stats (validity).
+ * The workspace (nv_perm_workspace_bytes(R, V, splits) bytes, 16-byte aligned) is shared by nv_perm_stats, nv_perm_maxstat and
+ *   nv_perm_finish of one test, called in that order on one stream with the same R, V and splits. */
+#define NV_PERM_ONE_SAMPLE 0
+#define NV_PERM_TWO_SAMPLE 1
+#define NV_PERM_TAIL_TWO 0
+#define NV_PERM_TAIL_GREATER 1
+#define NV_PERM_TAIL_LESS 2
+#define NV_PERM_MAX_N 256
+#define NV_PERM_MAX_R (1 << 20)
+#define NV_PERM_MAX_SPLITS 256
+#define NV_PERM_MAX_ALPHAS 8
+#define NV_PERM_TILE_V 64
+#define NV_PERM_TILE_R 64
+int nv_perm_splits(int R, int V, int splits);
+long nv_perm_workspace_bytes(int R, int V, int splits);
+int nv_perm_rank(double alpha, int R);
+int nv_perm_design(int kind, int N, int n_a, const int* labels, int R, int exact, unsigned long seed, float* M, void* stream);
+int nv_perm_stats(const float* X, long ldx, int N, int V, int kind, int n_a, const int* labels, const unsigned char* mask, float* a, float* c,
+                  float* t, int* n_invalid, void* workspace, long ws_bytes, void* stream);
+int nv_perm_maxstat(const float* X, long ldx, int N, int V, const float* M, int R, const float* a, const float* c, int tail, int splits,
+                    void* workspace, long ws_bytes, void* stream);
+int nv_perm_finish(int kind, int N, int R, int V, int splits, const float* c, const double* alphas, int n_alphas, float* max_stat, float* max_t,
+                   int* count_unc, int* count_fwe, float* p_unc, float* p_fwe, float* critical_t, void* workspace, long ws_bytes, void* stream);
+
 /* diagnostic: where do the workgroups of a grid run?  out u32 [blocks][2] = (HW_REG_HW_ID, HW_REG_XCC_ID) of each workgroup, which then
  * holds its CU for hold_us microseconds (threads per workgroup / dynamic LDS bytes shape its footprint).  Used to read the CU set of a
  * CU-masked stream (hipExtStreamCreateWithCUMask) and the XCD placement the 1-D grids rely on for speed. */

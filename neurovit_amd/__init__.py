@@ -30,4 +30,7 @@ def __getattr__(name):
     if name in ("FeatureBank", "GroupIndex", "knn_predict", "knn_evaluate", "LinearProbe", "linear_evaluate"):      # frozen-feature evaluation: the kNN and the linear probe of a (pre)trained encoder
         from . import features
         return getattr(features, name)
+    if name == "permutation_test":      # group-level permutation tests with max-statistic FWE maps over attribution maps
+        from .stats import permutation_test
+        return permutation_test
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -114,6 +114,12 @@ CLS_AUC_NAMES = ("auc", "n_pos", "n_neg", "gt", "eq")       # NV_CLS_AUC_COLS: t
 CLS_AUC_MAX_N, CLS_AUC_MAX_SPLITS = 1 << 20, 256            # NV_CLS_AUC_MAX_N, NV_CLS_AUC_MAX_SPLITS
 
 
+PERM_KINDS = {"one_sample": 0, "two_sample": 1}             # NV_PERM_ONE_SAMPLE / NV_PERM_TWO_SAMPLE
+PERM_TAILS = {"two": 0, "greater": 1, "less": 2}            # NV_PERM_TAIL_TWO / _GREATER / _LESS
+PERM_MAX_N, PERM_MAX_R, PERM_MAX_SPLITS, PERM_MAX_ALPHAS = 256, 1 << 20, 256, 8      # NV_PERM_MAX_N, NV_PERM_MAX_R, NV_PERM_MAX_SPLITS, NV_PERM_MAX_ALPHAS
+PERM_TILE_V, PERM_TILE_R = 64, 64                           # NV_PERM_TILE_V, NV_PERM_TILE_R: voxels and rows of one tile of nv_perm_maxstat
+
+
 POOL_MODES = {"cls": 0, "mean": 1, "patch_mean": 2}         # NV_POOL_CLS / NV_POOL_MEAN / NV_POOL_PATCH_MEAN
 KNN_WEIGHTS = {"uniform": 0, "softmax": 1}                  # NV_KNN_UNIFORM / NV_KNN_SOFTMAX
 KNN_MAX_K = 128                                             # NV_KNN_MAX_K
