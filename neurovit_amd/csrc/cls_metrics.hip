@@ -1,9 +1,9 @@
 // Classification metrics on the device: the per-batch accumulation (nv_cls_metrics_update), the exact one-vs-rest ROC-AUC by pair counting
-// (nv_cls_auc), the labels of segments (nv_segment_labels) and the finished table (nv_cls_metrics_finish).  The definitions are in the
+// (nv_cls_auc) and the finished table (nv_cls_metrics_finish); the labels of segments are in segments.hip.  The definitions are in the
 // header.  Nothing here reads back, nothing uses atomics; every sum has one fixed order, so the bits reproduce from run to run.
 #include <math.h>
 
-#include "common.h"
+#include "eval_common.h"
 
 namespace {
 
@@ -20,7 +20,7 @@ __global__ __launch_bounds__(256) void cls_update_kernel(const float* __restrict
   __shared__ int rcell[256], rbin[256], rhit[256];
   __shared__ double rconf[256];
   __shared__ double redd[4][4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int tid = threadIdx.x;
   double acc_n = 0.0, acc_skip = 0.0, acc_nll = 0.0, acc_brier = 0.0;
   for (int chunk = 0; chunk < B; chunk += 256) {
     const int b = chunk + tid;
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void cls_update_kernel(const float* __restrict
     if (b < B) {
       const float* z = scores + (long)b * lds;
       const int y = labels[b];
-      bool ok = y >= 0 && y < C;
+      bool ok = valid_label(y, C);
       float m = z[0];
       int pred = 0;
       for (int c = 0; c < C; ++c) {
@@ -87,13 +87,9 @@ __global__ __launch_bounds__(256) void cls_update_kernel(const float* __restrict
     }
     __syncthreads();      // the records are consumed before the next chunk overwrites them
   }
-  const double v[4] = {wave_sum(acc_n), wave_sum(acc_skip), wave_sum(acc_nll), wave_sum(acc_brier)};
-  if (lane == 0)
-    for (int i = 0; i < 4; ++i) redd[i][wid] = v[i];
-  __syncthreads();
+  double t[4] = {acc_n, acc_skip, acc_nll, acc_brier};
+  block_sum4(t, redd);
   if (tid == 0) {
-    double t[4];
-    for (int i = 0; i < 4; ++i) t[i] = (redd[i][0] + redd[i][1]) + (redd[i][2] + redd[i][3]);
     state[0] += t[0]; state[1] += t[1]; state[2] += t[2]; state[5] += t[3];
     if (t[0] > 0.0) { state[3] += t[2] / t[0]; state[4] += 1.0; }
   }
@@ -124,7 +120,7 @@ __global__ __launch_bounds__(256) void cls_auc_kernel(const float* __restrict__ 
   bool active = false;
   if (i < N) {
     const int y = labels[i];
-    if (y >= 0 && y < C) { c = y; p = probs[(long)i * ldp + c]; active = true; }
+    if (valid_label(y, C)) { c = y; p = probs[(long)i * ldp + c]; active = true; }
   }
   unsigned gt = 0u, eq = 0u;
   const int t_begin = blockIdx.y * tiles_per_split, t_end = min(t_begin + tiles_per_split, ntiles);
@@ -134,7 +130,7 @@ __global__ __launch_bounds__(256) void cls_auc_kernel(const float* __restrict__ 
     // labels first: every thread of the staging loop below reads its row's label from LDS
     for (int r = tid; r < TJ; r += 256) {
       int l = -1;
-      if (r < rows) { l = labels[j0 + r]; if (l < 0 || l >= C) l = -1; }
+      if (r < rows) { l = labels[j0 + r]; if (!valid_label(l, C)) l = -1; }
       tlab[r] = l;
     }
     __syncthreads();
@@ -186,16 +182,10 @@ __global__ __launch_bounds__(256) void cls_auc_kernel(const float* __restrict__ 
 
 // One workgroup per class: thread t adds the partials of the workgroups t, t + 256, ... and counts the labels t, t + 256, ... - integers, so
 // the order of the adds does not matter - then the wave butterfly and the four waves.
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned long long)__shfl_xor((long long)v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void cls_auc_merge_kernel(const unsigned long long* __restrict__ partial, int groups, const int* __restrict__ labels, int N,
                                                             int C, double* __restrict__ out) {
   __shared__ unsigned long long red[4][4];
-  const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int c = blockIdx.x, tid = threadIdx.x;
   unsigned long long g = 0ull, e = 0ull, pos = 0ull, use = 0ull;
   for (int w = tid; w < groups; w += 256) {
     g += partial[((long)w * C + c) * 2];
@@ -204,15 +194,11 @@ __global__ __launch_bounds__(256) void cls_auc_merge_kernel(const unsigned long 
   for (int r = tid; r < N; r += 256) {
     const int l = labels[r];
     pos += l == c;
-    use += l >= 0 && l < C;
+    use += valid_label(l, C);
   }
-  const unsigned long long v[4] = {wave_sum_u64(g), wave_sum_u64(e), wave_sum_u64(pos), wave_sum_u64(use)};
-  if (lane == 0)
-    for (int k = 0; k < 4; ++k) red[k][wid] = v[k];
-  __syncthreads();
+  unsigned long long t[4] = {g, e, pos, use};
+  block_sum4(t, red);
   if (tid == 0) {
-    unsigned long long t[4];
-    for (int k = 0; k < 4; ++k) t[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
     const double gt = (double)t[0], eq = (double)t[1], n_pos = (double)t[2], n_neg = (double)(t[3] - t[2]);
     double* o = out + (long)c * NV_CLS_AUC_COLS;
     o[0] = (n_pos > 0.0 && n_neg > 0.0) ? (gt + 0.5 * eq) / (n_pos * n_neg) : (double)__builtin_nanf("");
@@ -222,42 +208,10 @@ __global__ __launch_bounds__(256) void cls_auc_merge_kernel(const unsigned long 
 
 int auc_resolve_splits(int N, int C, int splits) {
   const int TJ = auc_tile_rows(C);
-  const int itiles = (N + 255) / 256, jtiles = (N + TJ - 1) / TJ;
-  int s = splits > 0 ? splits : (1024 + itiles - 1) / itiles;      // automatic: about four workgroups per CU
-  if (s > jtiles) s = jtiles;
-  if (s > NV_CLS_AUC_MAX_SPLITS) s = NV_CLS_AUC_MAX_SPLITS;
-  const int tps = (jtiles + s - 1) / s;
-  return (jtiles + tps - 1) / tps;      // no empty split
+  return nv_resolve_splits((N + 255) / 256, (N + TJ - 1) / TJ, splits, NV_CLS_AUC_MAX_SPLITS);
 }
 
 bool auc_shape_ok(int N, int C, int splits) { return N >= 1 && N <= NV_CLS_AUC_MAX_N && C >= 2 && C <= NV_CLS_MAX_C && splits >= 0 && splits <= NV_CLS_AUC_MAX_SPLITS; }
-
-// ------------------------------------------------------------------------------------------------ segment labels
-__global__ __launch_bounds__(256) void segment_labels_kernel(const int* __restrict__ labels, int N, const int* __restrict__ order, const int* __restrict__ offsets,
-                                                             int G, int* __restrict__ out, int* __restrict__ mixed) {
-  __shared__ int red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int cnt = 0;
-  for (int g = tid; g < G; g += 256) {
-    const int b = max(offsets[g], 0), e = min(offsets[g + 1], N);
-    int first = -1, differ = 0;
-    bool have = false;
-    for (int q = b; q < e; ++q) {
-      const int r = order[q];
-      if (r < 0 || r >= N) continue;      // (nv_segment_csr_check refuses such a table on the host; nothing is read through an unchecked index)
-      const int l = labels[r];
-      if (!have) { first = l; have = true; }
-      else if (l >= 0 && l != first) differ = 1;
-    }
-    out[g] = have ? first : -1;
-    cnt += differ;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-  if (lane == 0) red[wid] = cnt;
-  __syncthreads();
-  if (tid == 0) mixed[0] = (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // ------------------------------------------------------------------------------------------------ finish
 // One workgroup, thread c = class c (C <= 64: one wave would do; the block is 64 threads).  The means over classes are formed by thread 0
@@ -365,14 +319,6 @@ extern "C" int nv_cls_auc(const float* probs, long ldp, const int* labels, int N
   hipLaunchKernelGGL(cls_auc_kernel, dim3(itiles, S), dim3(256), 0, s, probs, ldp, labels, N, C, TJ, tps, jtiles, vec, partial);
   hipLaunchKernelGGL(cls_auc_merge_kernel, dim3(C), dim3(256), 0, s, partial, itiles * S, labels, N, C, out);
   NV_CHECK_LAUNCH("nv_cls_auc");
-  return NV_OK;
-}
-
-extern "C" int nv_segment_labels(const int* labels, int N, const int* order, const int* offsets, int G, int* out, int* mixed, void* stream) {
-  NV_CHECK_ARG(labels && order && offsets && out && mixed && N >= 1 && G >= 1, "nv_segment_labels: null pointer or bad shape N=%d G=%d", N, G);
-  NV_CHECK_ARG(nv_aligned(labels, 4) && nv_aligned(order, 4) && nv_aligned(offsets, 4) && nv_aligned(out, 4) && nv_aligned(mixed, 4), "nv_segment_labels: every array 4-byte aligned");
-  hipLaunchKernelGGL(segment_labels_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, labels, N, order, offsets, G, out, mixed);
-  NV_CHECK_LAUNCH("nv_segment_labels");
   return NV_OK;
 }
 

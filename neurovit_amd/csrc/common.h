@@ -57,6 +57,19 @@ unsigned nv_sync_event_flags();                            // hipEventCreateWith
 static inline bool nv_aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
 static inline bool nv_aligned16(const void* p) { return nv_aligned(p, 16); }
 
+// a kernel that declares more than 64 KiB of dynamic LDS asks for it once per process (`done`: a static flag of the call site, one per kernel)
+template <typename K>
+int allow_lds(K kernel, int bytes, bool& done, const char* name) {
+  if (done) return NV_OK;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    nv_set_error("%s: the device refuses %d bytes of LDS for one workgroup", name, bytes);
+    return NV_ERR_HIP;
+  }
+  done = true;
+  return NV_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // LDS images.  All byte offsets are relative to a 16-byte aligned tile base.
 //

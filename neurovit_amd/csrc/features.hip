@@ -1,9 +1,9 @@
 // Frozen-feature evaluation of the encoder: pooled features (nv_pool_features), a fused similarity + top-k search over a feature bank
-// (nv_knn_topk), the weighted k-nearest-neighbour vote (nv_knn_vote) and per-segment means (nv_segment_mean).  The definitions are in the
-// header.  Nothing here reads back, nothing uses atomics; every sum has one fixed order, so the bits reproduce from run to run.
+// (nv_knn_topk) and the weighted k-nearest-neighbour vote (nv_knn_vote); the per-segment means are in segments.hip.  The definitions are in
+// the header.  Nothing here reads back, nothing uses atomics; every sum has one fixed order, so the bits reproduce from run to run.
 #include <math.h>
 
-#include "common.h"
+#include "eval_common.h"
 
 namespace {
 
@@ -221,6 +221,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(const float* __restrict_
 }
 
 constexpr int KNN_MAX_K = 128, KNN_MAX_SPLITS = 64;
+// (not nv_resolve_splits, on purpose: an explicit request is returned as given, and a split holds at least two bank tiles)
 int knn_resolve_splits(int Nq, int Nb, int splits) {
   if (splits > 0) return splits;
   const int qtiles = (Nq + KT - 1) / KT, ntiles = (Nb + KT - 1) / KT;
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(64) void knn_vote_cls_kernel(const int* __restrict_
   for (int i = lane; i < k; i += 64) {
     const int j = idx[(long)q * kmax + i];
     int l = -1;
-    if (j >= 0 && j < Nb) { l = labels[j]; if (l < 0 || l >= C) l = -1; }
+    if (j >= 0 && j < Nb) { l = labels[j]; if (!valid_label(l, C)) l = -1; }
     lab[i] = l;
     w[i] = l >= 0 ? knn_weight(weighting, sim[(long)q * kmax + i], s0, T) : 0.f;
   }
@@ -297,25 +298,6 @@ __global__ __launch_bounds__(64) void knn_vote_reg_kernel(const int* __restrict_
   }
 }
 
-// ------------------------------------------------------------------------------------------------ segment mean
-__global__ __launch_bounds__(256) void segment_mean_kernel(const float* __restrict__ src, long lds, int N, int w, const int* __restrict__ order,
-                                                           const int* __restrict__ offsets, float* __restrict__ out, long ldo) {
-  const int gseg = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
-  if (c >= w) return;
-  int b = offsets[gseg], e = offsets[gseg + 1];
-  b = max(b, 0);
-  e = min(e, N);
-  double s = 0.0;
-  int cnt = 0;
-  for (int p = b; p < e; ++p) {
-    const int r = order[p];
-    if (r < 0 || r >= N) continue;      // (nv_segment_csr_check refuses such a table on the host; nothing is read through an unchecked index)
-    s += (double)src[(long)r * lds + c];
-    ++cnt;
-  }
-  out[(long)gseg * ldo + c] = cnt > 0 ? (float)(s / (double)cnt) : 0.f;
-}
-
 }  // namespace
 
 extern "C" int nv_pool_features(const float* tokens, long batch_stride, long row_stride, int B, int n, int d, int mode, int normalize, float* out,
@@ -360,11 +342,8 @@ extern "C" int nv_knn_topk(const float* Q, long ldq, int Nq, const float* bank, 
   static_assert((size_t)(2 * KBUF + 2 * KT * KNN_MAX_K) * sizeof(float) <= 160 * 1024, "LDS budget");
   static_assert(KT * KSL <= 2 * KBUF, "the sim tile lies over the staging buffers");
   if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(knn_topk_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((2 * KBUF + 2 * KT * KNN_MAX_K) * sizeof(float)));
-      attr_set = true;
-    }
+    static bool allowed = false;
+    if (int rc = allow_lds(knn_topk_kernel, (int)((2 * KBUF + 2 * KT * KNN_MAX_K) * sizeof(float)), allowed, "nv_knn_topk")) return rc;
   }
   hipStream_t s = (hipStream_t)stream;
   float* wsim = S == 1 ? sim : (float*)workspace;
@@ -391,22 +370,5 @@ extern "C" int nv_knn_vote(const int* idx, const float* sim, int Nq, int kmax, i
     hipLaunchKernelGGL(knn_vote_reg_kernel, dim3(Nq), dim3(64), 0, s, idx, sim, kmax, k, weighting, temperature, Nb, targets, K, pred_reg);
   }
   NV_CHECK_LAUNCH("nv_knn_vote");
-  return NV_OK;
-}
-
-extern "C" int nv_segment_csr_check(const int* order, const int* offsets, int N, int G) {
-  NV_CHECK_ARG(order && offsets && N > 0 && G > 0, "nv_segment_csr_check: null pointer or bad shape N=%d G=%d", N, G);
-  NV_CHECK_ARG(offsets[0] == 0 && offsets[G] <= N, "nv_segment_csr_check: offsets must run from 0 to at most N=%d, got %d .. %d", N, offsets[0], offsets[G]);
-  for (int gseg = 0; gseg < G; ++gseg)
-    NV_CHECK_ARG(offsets[gseg] <= offsets[gseg + 1], "nv_segment_csr_check: offsets decrease at segment %d (%d > %d)", gseg, offsets[gseg], offsets[gseg + 1]);
-  for (int p = 0; p < offsets[G]; ++p) NV_CHECK_ARG(order[p] >= 0 && order[p] < N, "nv_segment_csr_check: order[%d] = %d outside [0, %d)", p, order[p], N);
-  return NV_OK;
-}
-
-extern "C" int nv_segment_mean(const float* src, long lds, int N, int w, const int* order, const int* offsets, int G, float* out, long ldo, void* stream) {
-  NV_CHECK_ARG(src && order && offsets && out && N > 0 && w > 0 && G > 0, "nv_segment_mean: null pointer or bad shape N=%d w=%d G=%d", N, w, G);
-  NV_CHECK_ARG(lds >= w && ldo >= w && G <= 65535, "nv_segment_mean: lds=%ld and ldo=%ld must cover w=%d; at most 65535 segments per call, got %d", lds, ldo, w, G);
-  hipLaunchKernelGGL(segment_mean_kernel, dim3((w + 255) / 256, G), dim3(256), 0, (hipStream_t)stream, src, lds, N, w, order, offsets, out, ldo);
-  NV_CHECK_LAUNCH("nv_segment_mean");
   return NV_OK;
 }

@@ -4,7 +4,7 @@
 // floating-point sum has one fixed order and every count is an integer, so the bits do not depend on the grid, the split count or the CU count.
 #include <math.h>
 
-#include "common.h"
+#include "eval_common.h"
 
 #pragma clang fp contract(off)
 
@@ -15,9 +15,7 @@ constexpr uint64_t PERM_D2 = 0x5045524D32ull;      // "PERM2": the sort keys of 
 constexpr int TV = NV_PERM_TILE_V, TR = NV_PERM_TILE_R;
 constexpr int FIN_THREADS = 1024, FIN_CHUNK = 4096;
 
-// every operation rounded on its own (the pragma above): the numpy restatement repeats these expressions
-__device__ __forceinline__ float rsub(float a, float b) { return a - b; }
-__device__ __forceinline__ float rmul(float a, float b) { return a * b; }
+// every operation rounded on its own (the pragma above; rsub and rmul of eval_common.h): the numpy restatement repeats these expressions
 __device__ __forceinline__ double clamp1(double u) { return u > 1.0 ? 1.0 : (u < -1.0 ? -1.0 : u); }
 // t = u sqrt(df / (1 - u^2)), strictly increasing on [-1, 1]; +-inf at the ends
 __device__ __forceinline__ double t_of_u(double u, double df) {
@@ -83,8 +81,8 @@ __global__ __launch_bounds__(256) void perm_design_two_kernel(int N, int Npad, i
 __global__ __launch_bounds__(256) void perm_stats_kernel(const float* __restrict__ X, long ldx, int N, int V, int kind, int n_a, const int* __restrict__ labels,
                                                          const unsigned char* __restrict__ mask, float* __restrict__ av, float* __restrict__ cv,
                                                          float* __restrict__ tv, int* __restrict__ inval_part) {
-  __shared__ int red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ int red[1][4];
+  const int tid = threadIdx.x;
   const int v = blockIdx.x * 256 + tid;
   int bad = 0;
   if (v < V) {
@@ -124,23 +122,16 @@ __global__ __launch_bounds__(256) void perm_stats_kernel(const float* __restrict
     tv[v] = ok ? (float)t_of_u(clamp1(u0), df) : __builtin_nanf("");
     bad = ok ? 0 : 1;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
-  if (lane == 0) red[wid] = bad;
-  __syncthreads();
-  if (tid == 0) inval_part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  bad = block_sum4(bad, red);
+  if (tid == 0) inval_part[blockIdx.x] = bad;
 }
 
 __global__ __launch_bounds__(256) void perm_invalid_sum_kernel(const int* __restrict__ part, int n, int* __restrict__ out) {
-  __shared__ int red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ int red[1][4];
   int s = 0;
-  for (int b = tid; b < n; b += 256) s += part[b];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-  if (lane == 0) red[wid] = s;
-  __syncthreads();
-  if (tid == 0) out[0] = (red[0] + red[1]) + (red[2] + red[3]);
+  for (int b = threadIdx.x; b < n; b += 256) s += part[b];
+  s = block_sum4(s, red);
+  if (threadIdx.x == 0) out[0] = s;
 }
 
 // ------------------------------------------------------------------------------------------------ the hot path
@@ -343,14 +334,7 @@ __global__ __launch_bounds__(FIN_THREADS) void perm_pvalue_kernel(const float* _
 inline int perm_npad(int N) { return (N + 3) & ~3; }
 inline int perm_vtiles(int V) { return (V + TV - 1) / TV; }
 
-int perm_resolve_splits(int R, int V, int splits) {
-  const int nvt = perm_vtiles(V), rtiles = (R + TR - 1) / TR;
-  int s = splits > 0 ? splits : (1024 + nvt - 1) / nvt;      // automatic: about four workgroups per CU
-  if (s > rtiles) s = rtiles;
-  if (s > NV_PERM_MAX_SPLITS) s = NV_PERM_MAX_SPLITS;
-  const int tps = (rtiles + s - 1) / s;
-  return (rtiles + tps - 1) / tps;      // no empty split
-}
+int perm_resolve_splits(int R, int V, int splits) { return nv_resolve_splits(perm_vtiles(V), (R + TR - 1) / TR, splits, NV_PERM_MAX_SPLITS); }
 
 bool perm_shape_ok(int R, int V, int splits) { return R >= 1 && R <= NV_PERM_MAX_R && V >= 1 && splits >= 0 && splits <= NV_PERM_MAX_SPLITS; }
 
@@ -445,13 +429,18 @@ extern "C" int nv_perm_maxstat(const float* X, long ldx, int N, int V, const flo
   static_assert(NV_PERM_MAX_SPLITS <= 65535 && TR == 64 && TV == 64, "the grid's y extent; 4 waves x 16 rows, 4 blocks x 16 voxels");
   float* ws = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
-  auto launch = [&](auto kernel) {
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (NV_PERM_MAX_N * TV + 4 * TV) * (int)sizeof(float));
+  auto launch = [&](auto kernel) -> int {
+    if (lds > 64 * 1024) {
+      static bool allowed = false;      // (of this instantiation of the lambda: one per kernel)
+      if (int rc = allow_lds(kernel, (NV_PERM_MAX_N * TV + 4 * TV) * (int)sizeof(float), allowed, "nv_perm_maxstat")) return rc;
+    }
     hipLaunchKernelGGL(kernel, dim3(nvt, S), dim3(256), lds, s, X, ldx, N, Npad, V, M, R, a, c, rps, nvt, ws + w.stat0, (unsigned*)(ws + w.cnt), ws + w.pmax);
+    return NV_OK;
   };
-  if (tail == NV_PERM_TAIL_TWO) launch(perm_maxstat_kernel<NV_PERM_TAIL_TWO>);
-  else if (tail == NV_PERM_TAIL_GREATER) launch(perm_maxstat_kernel<NV_PERM_TAIL_GREATER>);
-  else launch(perm_maxstat_kernel<NV_PERM_TAIL_LESS>);
+  const int rc = tail == NV_PERM_TAIL_TWO       ? launch(perm_maxstat_kernel<NV_PERM_TAIL_TWO>)
+                 : tail == NV_PERM_TAIL_GREATER ? launch(perm_maxstat_kernel<NV_PERM_TAIL_GREATER>)
+                                                : launch(perm_maxstat_kernel<NV_PERM_TAIL_LESS>);
+  if (rc != NV_OK) return rc;
   NV_CHECK_LAUNCH("nv_perm_maxstat");
   return NV_OK;
 }

@@ -3,23 +3,13 @@
 // reads back, nothing uses atomics; every sum has one fixed order, so the bits reproduce from run to run and do not depend on the grid.
 #include <math.h>
 
-#include "common.h"
+#include "eval_common.h"
 
-// Every fp32 / fp64 operation below is rounded on its own.  The toolchain's rounded intrinsics are inline functions of a header that is
-// compiled under the default contraction mode, so a product of theirs feeding a sum of theirs still becomes a fused multiply-add after
-// inlining (the Adam step's p - step * q did, and lost its bit-equality with the torch expressions).  The helpers below are defined under
-// `contract(off)` instead, as ema.hip writes its operators.  The matrix products are MFMA builtins and are not affected.
+// Every fp32 / fp64 operation below is rounded on its own: through the operators of eval_common.h (which says why the toolchain's rounded
+// intrinsics do not do), and under the same mode for what is written out in place.  The matrix products are MFMA builtins and are not affected.
 #pragma clang fp contract(off)
 
 namespace {
-
-__device__ __forceinline__ float radd(float a, float b) { return a + b; }
-__device__ __forceinline__ float rsub(float a, float b) { return a - b; }
-__device__ __forceinline__ float rmul(float a, float b) { return a * b; }
-__device__ __forceinline__ float rdiv(float a, float b) { return a / b; }
-__device__ __forceinline__ double dadd(double a, double b) { return a + b; }
-__device__ __forceinline__ double dsub(double a, double b) { return a - b; }
-__device__ __forceinline__ double dmul(double a, double b) { return a * b; }
 
 constexpr int PT = 32;                      // rows of a tile: the k extent of the weight-gradient product, two 16-row blocks of the logits
 constexpr int PCH = NV_PROBE_CHUNK;         // rows of a chunk: one [M, d] partial in the workspace
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(256) void probe_tile_kernel(ProbeArgs a) {
           int y = -1;
           if (row < cend) {
             y = a.labels[row];
-            if (y < 0 || y >= a.C) y = -1;
+            if (!valid_label(y, a.C)) y = -1;
           }
           if (y < 0) {
             for (int k = 0; k < a.C; ++k) lg[k] = 0.f;
@@ -377,7 +367,7 @@ __global__ __launch_bounds__(256) void probe_denom_kernel(const int* __restrict_
     double s = 0.0;
     for (int row = rbeg; row < rend; ++row) {
       const int y = labels[row];
-      if (y >= 0 && y < C) s = dadd(s, cw ? (double)cw[y] : 1.0);
+      if (valid_label(y, C)) s = dadd(s, cw ? (double)cw[y] : 1.0);
     }
     lp[c] = s;
   }
@@ -404,26 +394,25 @@ size_t probe_lds_bytes(int MT, int NB) { return (size_t)(PT * (NB * 64 + 16) + 6
 static_assert((size_t)(PT * (16 * 64 + 16) + 6 * PT * (16 * 2 + 1)) * sizeof(float) <= 160 * 1024, "LDS budget");
 
 template <int MT, int NB, bool PREDICT>
-void probe_launch_one(const ProbeArgs& a, int grid, hipStream_t s) {
+int probe_launch_one(const ProbeArgs& a, int grid, hipStream_t s) {
   const size_t lds = probe_lds_bytes(MT, NB);
   if (lds > 64 * 1024) {
-    static bool attr_set = false;
-    if (!attr_set) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(probe_tile_kernel<MT, NB, PREDICT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_set = true;
-    }
+    static bool allowed = false;
+    if (int rc = allow_lds(probe_tile_kernel<MT, NB, PREDICT>, (int)lds, allowed, PREDICT ? "nv_probe_predict" : "nv_probe_grad")) return rc;
   }
   hipLaunchKernelGGL((probe_tile_kernel<MT, NB, PREDICT>), dim3(grid), dim3(256), lds, s, a);
+  return NV_OK;
 }
 
 template <bool PREDICT>
-void probe_launch(const ProbeArgs& a, int grid, hipStream_t s) {
+int probe_launch(const ProbeArgs& a, int grid, hipStream_t s) {
   const int MT = a.M > 16 ? 2 : 1, NB = probe_nb(a.d);
 #define NV_PROBE_CASE(mt, nb) \
   if (MT == mt && NB == nb) return probe_launch_one<mt, nb, PREDICT>(a, grid, s)
   NV_PROBE_CASE(1, 1); NV_PROBE_CASE(1, 2); NV_PROBE_CASE(1, 4); NV_PROBE_CASE(1, 8); NV_PROBE_CASE(1, 12); NV_PROBE_CASE(1, 16);
   NV_PROBE_CASE(2, 1); NV_PROBE_CASE(2, 2); NV_PROBE_CASE(2, 4); NV_PROBE_CASE(2, 8); NV_PROBE_CASE(2, 12); NV_PROBE_CASE(2, 16);
 #undef NV_PROBE_CASE
+  return NV_OK;      // (probe_nb covers every d that the entry points let through)
 }
 
 bool probe_shape_ok(int N, int d, int M) { return N > 0 && d >= 4 && d <= NV_PROBE_MAX_D && (d % 4) == 0 && M >= 1 && M <= PMAXM; }
@@ -519,7 +508,7 @@ extern "C" int nv_probe_grad(const float* X, long ldx, int N, int d, const float
   a.part = (float*)(a.dbc + (long)nc * PMAXM);
   a.nchunks = nc;
   hipStream_t s = (hipStream_t)stream;
-  probe_launch<false>(a, max_blocks > 0 && max_blocks < nc ? max_blocks : nc, s);
+  if (int rc = probe_launch<false>(a, max_blocks > 0 && max_blocks < nc ? max_blocks : nc, s)) return rc;
   const int eb = (int)(((long)M * d + 255) / 256);
   hipLaunchKernelGGL(probe_reduce_kernel, dim3(eb + 1), dim3(256), 0, s, (const float*)a.part, (const double*)a.lossc, (const double*)a.dbc, nc, M, d, W, *heads, task,
                      denom, dW, db, loss);
@@ -562,7 +551,7 @@ extern "C" int nv_probe_predict(const float* Q, long ldq, int Nq, int d, const f
   a.H = H; a.C = C; a.M = M; a.task = NV_PROBE_CLASSIFICATION;
   a.nchunks = probe_chunks(Nq);
   a.logits = logits; a.ldl = ldl; a.probs = probs; a.ldp = ldp;
-  probe_launch<true>(a, a.nchunks, (hipStream_t)stream);
+  if (int rc = probe_launch<true>(a, a.nchunks, (hipStream_t)stream)) return rc;
   NV_CHECK_LAUNCH("nv_probe_predict");
   return NV_OK;
 }

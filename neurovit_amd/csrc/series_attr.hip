@@ -115,19 +115,6 @@ __global__ __launch_bounds__(EW_THREADS) void grad_x_input_kernel(const float* _
   out[i] = p0 + p1;
 }
 
-// a kernel that declares more than 64 KiB of dynamic LDS asks for it once per process
-template <typename K>
-int allow_lds(K kernel, int bytes, bool& done, const char* name) {
-  if (done) return NV_OK;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    nv_set_error("%s: the device refuses %d bytes of LDS for one workgroup", name, bytes);
-    return NV_ERR_HIP;
-  }
-  done = true;
-  return NV_OK;
-}
-
 bool grid_ok(const int* g) { return g && g[0] > 0 && g[1] > 0 && g[2] > 0; }
 bool scope_ok(int scope) { return scope == NV_SERIES_SCOPE_SERIES || scope == NV_SERIES_SCOPE_VOLUME; }
 }  // namespace

@@ -1,5 +1,5 @@
 """Frozen-feature evaluation of the encoder: a bank of embeddings, the weighted k-nearest-neighbour probe (DINO's classifier) over it,
-subject-level pooling (csrc/features.hip: ops.pool_features / knn_topk / knn_vote / segment_mean) and the linear probe (LinearProbe /
+subject-level pooling (csrc/features.hip: ops.pool_features / knn_topk / knn_vote; csrc/segments.hip: ops.Segments) and the linear probe (LinearProbe /
 linear_evaluate at the end of this file; csrc/probe.hip).
 
     bank = FeatureBank(dim, capacity=len(train_set)).fill(model, train_loader)
@@ -24,14 +24,6 @@ def _extract(model, x, **kw) -> torch.Tensor:
     if fn is None:
         raise TypeError(f"{type(model).__name__} has neither extract_features nor forward_features")
     return fn(x, **kw)
-
-
-def _host_ids(groups, n: int, what: str) -> torch.Tensor:
-    """integer ids [n] as an int32 HOST tensor (subject ids are host data: the CSR of a segment mean is built from them without a device read)"""
-    g = torch.as_tensor(groups)
-    if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool or g.numel() != n:
-        raise ValueError(f"{what}: {n} integer ids expected, got {tuple(g.shape)} {g.dtype}")
-    return g.detach().reshape(-1).to("cpu", torch.int32)
 
 
 class GroupIndex:
@@ -88,7 +80,7 @@ class FeatureBank:
                 raise ValueError("FeatureBank: built without targets - pass num_targets")
             self.targets[row0:row0 + B] = torch.as_tensor(targets, dtype=torch.float32).reshape(B, -1).to(self.device)
         if groups is not None:
-            g = _host_ids(groups, B, "FeatureBank groups")
+            g = ops.host_ids(groups, B, "FeatureBank groups")
             self._host_groups[row0:row0 + B] = g
             self.groups[row0:row0 + B] = g.to(self.device)
             self.has_groups = True
@@ -126,17 +118,16 @@ class FeatureBank:
         a group without rows stays zero), the label / targets of its first row, groups = arange."""
         if not self.has_groups or self.size == 0:
             raise ValueError("FeatureBank.by_group: the bank has no groups")
-        hg = self._host_groups[:self.size]
-        order, offsets = ops.segment_csr(hg)
-        G = offsets.numel() - 1
+        subjects = ops.Segments(self._host_groups[:self.size])
+        G = subjects.G
         out = FeatureBank(self.dim, G, self.device, num_targets=0 if self.targets is None else self.targets.shape[1])
-        ops.segment_mean(self.view(), order, offsets, out=out.features)
+        subjects.mean(self.view(), out=out.features)
         if normalize:
             ops.pool_features(out.features.view(G, 1, self.dim), "cls", True, out=out.features)
-        first = order[offsets[:-1].clamp(max=self.size - 1).long()].long()
-        filled = (offsets[1:] > offsets[:-1])
-        out.labels.copy_(torch.where(filled, self.labels[first], torch.full_like(self.labels[first], -1)))
+        out.labels.copy_(subjects.labels(self.labels[:self.size])[0])
         if self.targets is not None:
+            first = subjects.order[subjects.offsets[:-1].clamp(max=self.size - 1).long()].long()
+            filled = subjects.offsets[1:] > subjects.offsets[:-1]
             out.targets.copy_(torch.where(filled[:, None], self.targets[first], torch.full_like(self.targets[first], float("nan"))))
         out._annotate(0, G, None, torch.arange(G, dtype=torch.int32), None)
         out.has_labels = self.has_labels
@@ -167,7 +158,7 @@ def knn_predict(bank: FeatureBank, queries: torch.Tensor, k: Union[int, Sequence
     if query_groups is not None:
         if not bank.has_groups:
             raise ValueError("knn_predict: query_groups given, but the bank has no groups")
-        qg = _host_ids(query_groups, queries.shape[0], "query_groups").to(queries.device)
+        qg = ops.host_ids(query_groups, queries.shape[0], "query_groups").to(queries.device)
         bg = bank.groups[:bank.size]
     idx, sim = ops.knn_topk(queries, bank.view(), max(ks), qg, bg, splits=splits)
     preds, scores = {}, {}
@@ -196,31 +187,30 @@ def knn_evaluate(bank: FeatureBank, queries: torch.Tensor, labels=None, targets=
     ks = _ks(k)
     task = "classification" if labels is not None else "regression"
     preds, scores, idx, sim = knn_predict(bank, queries, ks, temperature, weights, query_groups, task, num_classes, splits)
-    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, queries.shape[0], "query_groups"))
+    subjects = None if query_groups is None else ops.Segments(ops.host_ids(query_groups, queries.shape[0], "query_groups"))
     variants = [(kk, preds[kk], scores[kk] if scores is not None else None) for kk in ks]
 
     def voted(pooled):                                           # a subject without a positive vote has no class: -1, a miss
         best, cls = pooled.max(dim=1)
         return torch.where(best > 0, cls.to(torch.int32), torch.full_like(cls, -1, dtype=torch.int32))
     return {"predictions": preds, "scores": scores, "idx": idx, "sim": sim,
-            **_score(variants, queries, csr, labels, targets, None if bank.targets is None else bank.targets.shape[1], voted)}
+            **_score(variants, queries, subjects, labels, targets, None if bank.targets is None else bank.targets.shape[1], voted)}
 
 
-def _score(variants, queries, csr, labels, targets, K, subject_class) -> dict:
+def _score(variants, queries, subjects, labels, targets, K, subject_class) -> dict:
     """The score of [(key, predictions, scores or None)] against labels int [Nq] -> {"acc": {key: float}} or targets fp32 [Nq, K] -> {"mae":
-    {key: [K floats]}} (ops.RegressionMetrics, raw scale); with csr = (order, offsets) of the queries' subjects also "subject_acc" - the
+    {key: [K floats]}} (ops.RegressionMetrics, raw scale); with the ops.Segments of the queries' subjects also "subject_acc" - the
     scores averaged per subject (nv_segment_mean), subject_class of them, against the label of the subject's first volume - or
     "subject_mae" on the NaN-aware per-subject means of predictions and targets.  Device expressions throughout, ONE host read."""
     keys, (Nq, dev) = [key for key, _, _ in variants], (queries.shape[0], queries.device)
     if labels is not None:
         y = torch.as_tensor(labels).reshape(-1).to(dev, torch.int32)
         cells = [(pred == y).float().mean() for _, pred, _ in variants]
-        if csr is not None:
-            order, offsets = csr
-            filled = offsets[1:] > offsets[:-1]
-            y_subject = y[order[offsets[:-1].clamp(max=Nq - 1).long()].long()]
+        if subjects is not None:
+            filled = subjects.offsets[1:] > subjects.offsets[:-1]       # (an empty subject's label is -1, and so is the class of its zero votes)
+            y_subject = subjects.labels(y)[0]
             for _, _, score in variants:
-                cls = subject_class(ops.segment_mean(score, order, offsets))
+                cls = subject_class(subjects.mean(score))
                 cells.append(((cls == y_subject) & filled).float().sum() / filled.float().sum().clamp(min=1))
         host = torch.stack(cells).cpu().tolist()                 # the one host read
         names = ("acc", "subject_acc")
@@ -232,24 +222,15 @@ def _score(variants, queries, csr, labels, targets, K, subject_class) -> dict:
             m.update(pred, truth)
             return m.compute_device()
         tables = [table(pred, t) for _, pred, _ in variants]
-        if csr is not None:
-            t_subject = _nanmean_segments(t, *csr)
-            tables += [table(_nanmean_segments(pred, *csr), t_subject) for _, pred, _ in variants]
+        if subjects is not None:
+            t_subject = subjects.nanmean(t)
+            tables += [table(subjects.nanmean(pred), t_subject) for _, pred, _ in variants]
         host = torch.stack(tables).cpu()[:, :, 1].tolist()       # the one host read; column 1: the mean absolute error
         names = ("mae", "subject_mae")
     out = {names[0]: dict(zip(keys, host[:len(keys)]))}
-    if csr is not None:
+    if subjects is not None:
         out[names[1]] = dict(zip(keys, host[len(keys):]))
     return out
-
-
-def _nanmean_segments(values: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
-    """per-segment mean over the cells that are not NaN (NaN where a segment has none): two nv_segment_mean calls, on the values with zeros
-    for the missing cells and on the observed-cell mask"""
-    seen = ~torch.isnan(values)
-    total = ops.segment_mean(torch.where(seen, values, torch.zeros_like(values)), order, offsets)
-    share = ops.segment_mean(seen.float(), order, offsets)
-    return torch.where(share > 0, total / share.clamp(min=1e-30), torch.full_like(total, float("nan")))
 
 
 # ---------------------------------------------------------------------------------------------------- the linear probe
@@ -421,7 +402,7 @@ def linear_evaluate(probe: LinearProbe, queries: torch.Tensor, labels=None, targ
         raise ValueError("linear_evaluate: give labels (classification) or targets (regression), one of the two")
     if (labels is not None) != (probe.task == "classification"):
         raise ValueError(f"linear_evaluate: a {probe.task} probe, but {'labels' if labels is not None else 'targets'} were given")
-    csr = None if query_groups is None else ops.segment_csr(_host_ids(query_groups, queries.shape[0], "query_groups"))
+    subjects = None if query_groups is None else ops.Segments(ops.host_ids(query_groups, queries.shape[0], "query_groups"))
     if labels is not None:
         pred, probs = probe.predict(queries)
         out = {"predictions": pred, "probs": probs}
@@ -430,4 +411,4 @@ def linear_evaluate(probe: LinearProbe, queries: torch.Tensor, labels=None, targ
         raw = probe.predict(queries)
         out = {"predictions": raw}
         variants = [(l2, raw[h], None) for h, l2 in enumerate(probe.l2)]
-    return {**out, **_score(variants, queries, csr, labels, targets, probe.C, lambda pooled: pooled.argmax(dim=1).to(torch.int32))}
+    return {**out, **_score(variants, queries, subjects, labels, targets, probe.C, lambda pooled: pooled.argmax(dim=1).to(torch.int32))}

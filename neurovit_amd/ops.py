@@ -37,6 +37,33 @@ def _need_cuda(*ts):
             raise RuntimeError("neurovit_amd ops run on MI355X only (got a CPU tensor); there is no CPU fallback")
 
 
+def _i32(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _need_cuda(t)
+    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int32 [{n}] tensor on the device")
+    return t
+
+
+def _f32(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _need_cuda(t)
+    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on the device")
+    return t
+
+
+def _rows2d(X, what: str, exc=ValueError):
+    """the shape (N, w) of X, which must be float32 [N, w] on the device with N >= 1 and unit column stride (a row-strided view passes its
+    leading dimension); anything else raises `exc` - the type that the call site has always raised"""
+    if not torch.is_tensor(X) or X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.shape[0] < 1 or not X.is_cuda:
+        raise exc(f"{what}: float32 [N, w] on the device with N >= 1 and unit column stride expected, got "
+                  f"{(tuple(X.shape), X.dtype, X.device.type) if torch.is_tensor(X) else type(X).__name__}")
+    return X.shape
+
+
 def shape5(video: torch.Tensor):
     assert video.dim() == 5
     return (ctypes.c_long * 5)(*video.shape)
@@ -673,160 +700,6 @@ class RegressionMetrics:
         from ._cabi import REG_METRIC_NAMES
         out = self.compute_device().cpu()          # the one host read
         return {name: out[:, i].clone() for i, name in enumerate(REG_METRIC_NAMES)}
-
-
-def cls_auc(probs: torch.Tensor, labels: torch.Tensor, splits: int = 0) -> torch.Tensor:
-    """nv_cls_auc: the exact one-vs-rest ROC-AUC per class of probs f32 [N, C] (a row-strided view passes its leading dimension) under labels
-    int32 [N] (a label outside [0, C) = the row is not used), by counting pairs, ties as a half.  Returns float64 [C, 5] on the device:
-    auc (NaN where a class has no positive or no negative row), n_pos, n_neg, gt, eq (_cabi.CLS_AUC_NAMES); no host read."""
-    _need_cuda(probs, labels)
-    if probs.dtype != torch.float32 or probs.dim() != 2 or probs.stride(1) != 1 or probs.shape[0] < 1:
-        raise ValueError(f"cls_auc: float32 [N, C] with N >= 1 and unit column stride expected, got {tuple(probs.shape)} {probs.dtype}")
-    N, C = probs.shape
-    labels = _i32(labels, N, "cls_auc: labels")
-    nb = lib.nv_cls_auc_workspace_bytes(N, C, int(splits))
-    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=probs.device)
-    out = torch.empty((C, len(_cabi.CLS_AUC_NAMES)), dtype=torch.float64, device=probs.device)
-    check(lib.nv_cls_auc(_p(probs), probs.stride(0), _p(labels), N, C, int(splits), _p(out), _p(ws), nb, _stream()), "nv_cls_auc")
-    return out
-
-
-def segment_labels(labels: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor):
-    """nv_segment_labels: (the label of each segment's first row int32 [G] - an empty segment gets -1 -, mixed int32 [1] = the number of
-    segments that hold another valid label), device tensors; order / offsets from segment_csr."""
-    _need_cuda(labels, order, offsets)
-    N, G = labels.numel(), offsets.numel() - 1
-    labels, order, offsets = _i32(labels, N, "segment_labels: labels"), _i32(order, N, "order"), _i32(offsets, G + 1, "offsets")
-    out = torch.empty(G, dtype=torch.int32, device=labels.device)
-    mixed = torch.empty(1, dtype=torch.int32, device=labels.device)
-    check(lib.nv_segment_labels(_p(labels), N, _p(order), _p(offsets), G, _p(out), _p(mixed), _stream()), "nv_segment_labels")
-    return out, mixed
-
-
-class ClassificationMetrics:
-    """Validation metrics of a classifier, accumulated on the device (nv_cls_metrics_*, nv_cls_auc, nv_segment_labels): update() makes one
-    launch and no host read, compute() one host read.  scores: logits (kind "logits") or probabilities (kind "probs", e.g. what
-    LinearProbe.predict / knn_predict return) float32 [B, C]; labels: integers [B]; a row whose label lies outside [0, C) or that holds a
-    non-finite score is counted in "skipped" and nowhere else.
-    compute() -> {"n", "skipped", "accuracy", "balanced_accuracy", "macro_f1", "nll", "val_loss" (the mean over the updates of their mean
-    nll: the reference's validation loss), "brier", "ece": floats; "class_support", "class_recall", "class_precision", "class_f1": float32 [C];
-    "confusion": int64 [C, C], true x predicted}.  Undefined quantities are NaN.  With capacity > 0 update() also files the rows'
-    probabilities and labels in a preallocated bank, and compute() adds "macro_auc" and "class_auc" (exact one-vs-rest ROC-AUC, ties as a
-    half); with `groups` (host subject ids per row, as FeatureBank takes them) the same set once more under "subject_*" keys - the bank's
-    probabilities averaged per subject, the subject's label from its first row - and "subject_mixed_labels", the number of subjects that hold
-    another valid label.  With two classes also "sensitivity" (recall of class 1), "specificity" (recall of class 0) and "auc" (class 1's)."""
-
-    def __init__(self, num_classes: int, capacity: int = 0, bins: int = 15, device="cuda"):
-        self.C, self.capacity, self.bins, self.device = int(num_classes), int(capacity), int(bins), torch.device(device)
-        if not 2 <= self.C <= _cabi.CLS_MAX_C or not 1 <= self.bins <= _cabi.CLS_MAX_BINS or self.capacity < 0:
-            raise ValueError(f"ClassificationMetrics: num_classes = {num_classes} in [2, {_cabi.CLS_MAX_C}], bins = {bins} in [1, {_cabi.CLS_MAX_BINS}] and "
-                             f"capacity = {capacity} >= 0 expected")
-        if self.capacity > _cabi.CLS_AUC_MAX_N:
-            raise ValueError(f"ClassificationMetrics: capacity = {capacity} above {_cabi.CLS_AUC_MAX_N} rows (nv_cls_auc)")
-        if self.device.type != "cuda":
-            raise RuntimeError("ClassificationMetrics runs on the MI355X (cuda) device - there is no CPU fallback")
-        self.state = torch.zeros(lib.nv_cls_metrics_state_doubles(self.C, self.bins), dtype=torch.float64, device=self.device)
-        self.bank_probs = torch.zeros((self.capacity, self.C), dtype=torch.float32, device=self.device) if self.capacity else None
-        self.bank_labels = torch.full((self.capacity,), -1, dtype=torch.int32, device=self.device) if self.capacity else None
-        self._host_groups = torch.full((self.capacity,), -1, dtype=torch.int32)
-        self.size, self.has_groups = 0, False
-
-    def reset(self) -> None:
-        self.state.zero_()
-        self._host_groups.fill_(-1)
-        self.size, self.has_groups = 0, False
-
-    def update(self, scores: torch.Tensor, labels: torch.Tensor, groups=None, kind: str = "logits") -> None:
-        if kind not in _cabi.CLS_KINDS:
-            raise ValueError(f"ClassificationMetrics.update: kind must be 'logits' or 'probs', got {kind!r}")
-        if (not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[1] != self.C or scores.shape[0] < 1 or scores.dtype != torch.float32
-                or not scores.is_cuda or scores.stride(1) != 1):
-            raise ValueError(f"ClassificationMetrics.update: scores must be float32 [B, {self.C}] on the device (B >= 1, unit column stride)")
-        B = scores.shape[0]
-        labels = torch.as_tensor(labels)
-        if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool or labels.numel() != B:
-            raise ValueError(f"ClassificationMetrics.update: {B} integer labels expected, got {tuple(labels.shape)} {labels.dtype}")
-        labels = labels.reshape(-1).to(scores.device, torch.int32).contiguous()
-        host_groups = None
-        if groups is not None:
-            if not self.capacity:
-                raise ValueError("ClassificationMetrics.update: groups need the bank - construct with capacity > 0")
-            g = torch.as_tensor(groups)
-            if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool or g.numel() != B:
-                raise ValueError(f"ClassificationMetrics.update: {B} integer group ids expected, got {tuple(g.shape)} {g.dtype}")
-            host_groups = g.detach().reshape(-1).to("cpu", torch.int32)
-        if self.capacity and self.size + B > self.capacity:
-            raise ValueError(f"ClassificationMetrics.update: {self.size} + {B} rows exceed the capacity {self.capacity}")
-        check(lib.nv_cls_metrics_update(_p(scores), scores.stride(0), _p(labels), B, self.C, self.bins, _cabi.CLS_KINDS[kind], _p(self.state),
-                                        _p(self.bank_probs), self.C, _p(self.bank_labels), self.size, self.capacity, _stream()), "nv_cls_metrics_update")
-        if self.capacity:
-            if host_groups is not None:
-                self._host_groups[self.size:self.size + B] = host_groups
-                self.has_groups = True
-            self.size += B
-
-    def state_parts(self, state: Optional[torch.Tensor] = None) -> dict:
-        """views of the double state (no host read): "head" [6] (_cabi.CLS_STATE_NAMES), "confusion" [C, C], "bin_count" / "bin_conf" /
-        "bin_correct" [bins]"""
-        s = self.state if state is None else state
-        h, cc, nb = _cabi.CLS_STATE_HEAD, self.C * self.C, self.bins
-        return {"head": s[:h], "confusion": s[h:h + cc].view(self.C, self.C), "bin_count": s[h + cc:h + cc + nb],
-                "bin_conf": s[h + cc + nb:h + cc + 2 * nb], "bin_correct": s[h + cc + 2 * nb:h + cc + 3 * nb]}
-
-    def _finish(self, state, auc) -> torch.Tensor:
-        out = torch.empty(lib.nv_cls_metrics_table_floats(self.C), dtype=torch.float32, device=self.device)
-        check(lib.nv_cls_metrics_finish(_p(state), self.C, self.bins, _p(auc), _p(out), _stream()), "nv_cls_metrics_finish")
-        return out
-
-    def compute_device(self) -> dict:
-        """Device tensors, no host read: "table" float32 [10 + 5 C + C C] as nv_cls_metrics_finish writes it, "auc" float64 [C, 5] (nv_cls_auc;
-        with a bank), and with groups "subject_table", "subject_auc", "subject_labels" int32 [G], "subject_probs" float32 [G, C],
-        "subject_state" and "subject_mixed" int32 [1]."""
-        out = {}
-        filled = self.capacity and self.size > 0
-        if filled:
-            out["auc"] = cls_auc(self.bank_probs[:self.size], self.bank_labels[:self.size])
-        out["table"] = self._finish(self.state, out.get("auc"))
-        if filled and self.has_groups and int(self._host_groups[:self.size].max()) >= 0:
-            order, offsets = segment_csr(self._host_groups[:self.size])
-            G = offsets.numel() - 1
-            pooled = segment_mean(self.bank_probs[:self.size], order, offsets)
-            subject_labels, mixed = segment_labels(self.bank_labels[:self.size], order, offsets)
-            state = torch.zeros_like(self.state)
-            check(lib.nv_cls_metrics_update(_p(pooled), pooled.stride(0), _p(subject_labels), G, self.C, self.bins, _cabi.CLS_KINDS["probs"], _p(state),
-                                            None, 0, None, 0, 0, _stream()), "nv_cls_metrics_update")
-            out["subject_auc"] = cls_auc(pooled, subject_labels)
-            out["subject_table"] = self._finish(state, out["subject_auc"])
-            out.update(subject_labels=subject_labels, subject_probs=pooled, subject_state=state, subject_mixed=mixed)
-        return out
-
-    def _named(self, table: torch.Tensor, prefix: str, with_auc: bool) -> dict:
-        C, ns, nc = self.C, len(_cabi.CLS_METRIC_NAMES), len(_cabi.CLS_CLASS_METRIC_NAMES)
-        got = {prefix + name: float(table[i]) for i, name in enumerate(_cabi.CLS_METRIC_NAMES)}
-        per_class = table[ns:ns + C * nc].reshape(C, nc)
-        for j, name in enumerate(_cabi.CLS_CLASS_METRIC_NAMES):
-            got[f"{prefix}class_{name}"] = per_class[:, j].clone()
-        got[prefix + "confusion"] = table[ns + C * nc:ns + C * nc + C * C].reshape(C, C).to(torch.int64)
-        if not with_auc:
-            del got[prefix + "macro_auc"], got[prefix + "class_auc"]
-        if C == 2:
-            got[prefix + "sensitivity"], got[prefix + "specificity"] = float(per_class[1, 1]), float(per_class[0, 1])
-            if with_auc:
-                got[prefix + "auc"] = float(per_class[1, 4])
-        return got
-
-    def compute(self) -> dict:
-        dev = self.compute_device()
-        parts = [dev["table"]]
-        if "subject_table" in dev:
-            parts += [dev["subject_table"], dev["subject_mixed"].to(torch.float32)]
-        host = torch.cat(parts).cpu()              # the one host read
-        T = dev["table"].numel()
-        got = self._named(host[:T], "", bool(self.capacity))
-        if "subject_table" in dev:
-            got.update(self._named(host[T:2 * T], "subject_", True))
-            got["subject_mixed_labels"] = int(host[2 * T])
-        return got
 
 
 def head_step_soft(x, gamma, beta, W, bias, labels, label_smoothing=0.0, class_weight=None, mix=None, eps=1e-5, grad_scale=1.0, scale_state=None):
@@ -1690,16 +1563,8 @@ def drop_path_draw(seed: int, B: int, depth: int, rate: float, schedule: str = "
     return out
 
 
-# ---- frozen-feature evaluation (features.hip): pooled features, the fused similarity + top-k search, the kNN vote, per-segment means
-def _i32(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    _need_cuda(t)
-    if t.dtype != torch.int32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous int32 [{n}] tensor on the device")
-    return t
-
-
+# ---- the evaluation of a frozen encoder.  Frozen features (features.hip): pooled features, the fused similarity + top-k search, the kNN vote;
+# segments of rows (segments.hip)
 def pool_features(tokens: torch.Tensor, mode, normalize: bool = False, *, out: Optional[torch.Tensor] = None, row0: int = 0) -> torch.Tensor:
     """nv_pool_features: tokens f32 [B, n, d] (any batch / row stride, last stride 1) -> rows row0 .. row0 + B of `out` f32 [*, d] (any row
     stride; a fresh [B, d] when None).  mode "cls" | "mean" | "patch_mean" (or 0 / 1 / 2).  Returns the B rows written."""
@@ -1724,8 +1589,7 @@ def knn_topk(Q: torch.Tensor, bank: torch.Tensor, k: int, q_group: Optional[torc
     query q when q_group[q] >= 0 and q_group[q] == b_group[j] (int32, both or neither); unfilled slots are (-1, -inf).  splits: 0 = automatic.
     Returns (idx int32 [Nq, k], sim f32 [Nq, k])."""
     _need_cuda(Q, bank)
-    assert Q.dtype == torch.float32 and bank.dtype == torch.float32 and Q.dim() == 2 and bank.dim() == 2 and Q.stride(1) == 1 and bank.stride(1) == 1
-    (Nq, d), Nb = Q.shape, bank.shape[0]
+    (Nq, d), Nb = _rows2d(Q, "knn_topk: Q", AssertionError), _rows2d(bank, "knn_topk: bank", AssertionError)[0]
     if bank.shape[1] != d:
         raise ValueError(f"knn_topk: the queries have {d} columns, the bank {bank.shape[1]}")
     if (q_group is None) != (b_group is None):
@@ -1767,9 +1631,16 @@ def knn_vote(idx: torch.Tensor, sim: torch.Tensor, k: int, *, labels: Optional[t
     return pred
 
 
-def segment_csr(groups, num_segments: Optional[int] = None):
-    """Host CSR of integer segment ids (a sequence or a tensor; a negative id = in no segment), validated by nv_segment_csr_check and uploaded:
-    (order int32 [N], offsets int32 [G + 1]) on the current device.  The rows of a segment keep their ascending order."""
+def host_ids(values, n: int, what: str) -> torch.Tensor:
+    """integer ids or labels [n] as an int32 HOST tensor (subject ids are host data: the CSR of a segment mean is built from them without a
+    device read)"""
+    g = torch.as_tensor(values)
+    if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool or g.numel() != n:
+        raise ValueError(f"{what}: {n} integer ids expected, got {tuple(g.shape)} {g.dtype}")
+    return g.detach().reshape(-1).to("cpu", torch.int32)
+
+
+def _segment_csr_host(groups, num_segments: Optional[int] = None):
     g = torch.as_tensor(groups).detach().to("cpu", torch.int64).reshape(-1)
     N = g.numel()
     G = int(num_segments) if num_segments is not None else (int(g.max().item()) + 1 if N else 0)
@@ -1782,6 +1653,13 @@ def segment_csr(groups, num_segments: Optional[int] = None):
     offsets = torch.zeros(G + 1, dtype=torch.int32)
     offsets[1:] = torch.cumsum(torch.bincount(srt.values, minlength=G), 0).to(torch.int32)
     check(lib.nv_segment_csr_check(order.data_ptr(), offsets.data_ptr(), N, G), "nv_segment_csr_check")
+    return order, offsets
+
+
+def segment_csr(groups, num_segments: Optional[int] = None):
+    """Host CSR of integer segment ids (a sequence or a tensor; a negative id = in no segment), validated by nv_segment_csr_check and uploaded:
+    (order int32 [N], offsets int32 [G + 1]) on the current device.  The rows of a segment keep their ascending order."""
+    order, offsets = _segment_csr_host(groups, num_segments)
     return order.cuda(), offsets.cuda()
 
 
@@ -1789,8 +1667,7 @@ def segment_mean(src: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, 
     """nv_segment_mean: out[g] = mean of the rows src[order[offsets[g] : offsets[g + 1]]] of src f32 [N, w] (a row-strided view passes its leading
     dimension), summed in double in that order; an empty segment gives zeros.  order / offsets: device int32, from segment_csr."""
     _need_cuda(src, order, offsets)
-    assert src.dtype == torch.float32 and src.dim() == 2 and src.stride(1) == 1
-    N, w = src.shape
+    N, w = _rows2d(src, "segment_mean: src", AssertionError)
     G = offsets.numel() - 1
     order, offsets = _i32(order, N, "order"), _i32(offsets, G + 1, "offsets")
     out = _out2d(out, G, w, torch.float32, src)
@@ -1798,23 +1675,203 @@ def segment_mean(src: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor, 
     return out
 
 
+def segment_labels(labels: torch.Tensor, order: torch.Tensor, offsets: torch.Tensor):
+    """nv_segment_labels: (the label of each segment's first row int32 [G] - an empty segment gets -1 -, mixed int32 [1] = the number of
+    segments that hold another valid label), device tensors; order / offsets from segment_csr."""
+    _need_cuda(labels, order, offsets)
+    N, G = labels.numel(), offsets.numel() - 1
+    labels, order, offsets = _i32(labels, N, "segment_labels: labels"), _i32(order, N, "order"), _i32(offsets, G + 1, "offsets")
+    out = torch.empty(G, dtype=torch.int32, device=labels.device)
+    mixed = torch.empty(1, dtype=torch.int32, device=labels.device)
+    check(lib.nv_segment_labels(_p(labels), N, _p(order), _p(offsets), G, _p(out), _p(mixed), _stream()), "nv_segment_labels")
+    return out, mixed
+
+
+class Segments:
+    """The segments (subjects) of N rows from their host ids [N] (a negative id = in no segment; num_segments: default the largest id + 1),
+    and what is computed per segment.  `ids` int32 [N], `sizes` int64 [G] (the rows of each segment) and `G` are host data and settled by the
+    constructor without touching the device; `order` / `offsets` are segment_csr's device tensors, uploaded at their first use."""
+
+    def __init__(self, ids, num_segments: Optional[int] = None, what: str = "segment ids"):
+        self.ids = host_ids(ids, torch.as_tensor(ids).numel(), what)
+        self._host_csr = _segment_csr_host(self.ids, num_segments)
+        self.sizes = (self._host_csr[1][1:] - self._host_csr[1][:-1]).long()
+        self.N, self.G, self._csr = self.ids.numel(), self.sizes.numel(), None
+
+    def _device_csr(self):
+        if self._csr is None:
+            self._csr = tuple(t.cuda() for t in self._host_csr)
+        return self._csr
+
+    order = property(lambda self: self._device_csr()[0])
+    offsets = property(lambda self: self._device_csr()[1])
+
+    def mean(self, src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """segment_mean of src f32 [N, w]: f32 [G, w], zeros for an empty segment"""
+        return segment_mean(src, self.order, self.offsets, out=out)
+
+    def nanmean(self, values: torch.Tensor) -> torch.Tensor:
+        """per-segment mean over the cells that are not NaN (NaN where a segment has none): two nv_segment_mean calls, on the values with
+        zeros for the missing cells and on the observed-cell mask"""
+        seen = ~torch.isnan(values)
+        total, share = self.mean(torch.where(seen, values, torch.zeros_like(values))), self.mean(seen.float())
+        return torch.where(share > 0, total / share.clamp(min=1e-30), torch.full_like(total, float("nan")))
+
+    def labels(self, device_labels: torch.Tensor):
+        """segment_labels of device labels int32 [N]: (the label of each segment's first row int32 [G], -1 for an empty segment; mixed int32
+        [1], the segments that hold another valid label) - device tensors, no host read"""
+        return segment_labels(device_labels, self.order, self.offsets)
+
+    def host_first_labels(self, host_labels: torch.Tensor):
+        """The same rule on the host, for labels that are host data: (the label of each segment's first row [G], -1 for an empty segment;
+        the number of segments that hold another valid label).  No device work."""
+        order, offsets = (t.long() for t in self._host_csr)
+        filled = self.sizes > 0
+        first = torch.where(filled, host_labels[order[offsets[:-1].clamp(max=self.N - 1)]], torch.full((self.G,), -1, dtype=host_labels.dtype))
+        rows = order[:int(offsets[-1])]
+        segment = self.ids[rows].long()
+        differ = (host_labels[rows] >= 0) & (host_labels[rows] != first[segment])
+        return first, int(torch.unique(segment[differ]).numel())
+
+
+# ---- classification metrics over scores and, with a bank, exact AUC and subject pooling (cls_metrics.hip)
+def cls_auc(probs: torch.Tensor, labels: torch.Tensor, splits: int = 0) -> torch.Tensor:
+    """nv_cls_auc: the exact one-vs-rest ROC-AUC per class of probs f32 [N, C] (a row-strided view passes its leading dimension) under labels
+    int32 [N] (a label outside [0, C) = the row is not used), by counting pairs, ties as a half.  Returns float64 [C, 5] on the device:
+    auc (NaN where a class has no positive or no negative row), n_pos, n_neg, gt, eq (_cabi.CLS_AUC_NAMES); no host read."""
+    _need_cuda(probs, labels)
+    N, C = _rows2d(probs, "cls_auc: probs")
+    labels = _i32(labels, N, "cls_auc: labels")
+    nb = lib.nv_cls_auc_workspace_bytes(N, C, int(splits))
+    ws = torch.empty(max(nb, 8), dtype=torch.uint8, device=probs.device)
+    out = torch.empty((C, len(_cabi.CLS_AUC_NAMES)), dtype=torch.float64, device=probs.device)
+    check(lib.nv_cls_auc(_p(probs), probs.stride(0), _p(labels), N, C, int(splits), _p(out), _p(ws), nb, _stream()), "nv_cls_auc")
+    return out
+
+
+class ClassificationMetrics:
+    """Validation metrics of a classifier, accumulated on the device (nv_cls_metrics_*, nv_cls_auc, nv_segment_labels): update() makes one
+    launch and no host read, compute() one host read.  scores: logits (kind "logits") or probabilities (kind "probs", e.g. what
+    LinearProbe.predict / knn_predict return) float32 [B, C]; labels: integers [B]; a row whose label lies outside [0, C) or that holds a
+    non-finite score is counted in "skipped" and nowhere else.
+    compute() -> {"n", "skipped", "accuracy", "balanced_accuracy", "macro_f1", "nll", "val_loss" (the mean over the updates of their mean
+    nll: the reference's validation loss), "brier", "ece": floats; "class_support", "class_recall", "class_precision", "class_f1": float32 [C];
+    "confusion": int64 [C, C], true x predicted}.  Undefined quantities are NaN.  With capacity > 0 update() also files the rows'
+    probabilities and labels in a preallocated bank, and compute() adds "macro_auc" and "class_auc" (exact one-vs-rest ROC-AUC, ties as a
+    half); with `groups` (host subject ids per row, as FeatureBank takes them) the same set once more under "subject_*" keys - the bank's
+    probabilities averaged per subject, the subject's label from its first row - and "subject_mixed_labels", the number of subjects that hold
+    another valid label.  With two classes also "sensitivity" (recall of class 1), "specificity" (recall of class 0) and "auc" (class 1's)."""
+
+    def __init__(self, num_classes: int, capacity: int = 0, bins: int = 15, device="cuda"):
+        self.C, self.capacity, self.bins, self.device = int(num_classes), int(capacity), int(bins), torch.device(device)
+        if not 2 <= self.C <= _cabi.CLS_MAX_C or not 1 <= self.bins <= _cabi.CLS_MAX_BINS or self.capacity < 0:
+            raise ValueError(f"ClassificationMetrics: num_classes = {num_classes} in [2, {_cabi.CLS_MAX_C}], bins = {bins} in [1, {_cabi.CLS_MAX_BINS}] and "
+                             f"capacity = {capacity} >= 0 expected")
+        if self.capacity > _cabi.CLS_AUC_MAX_N:
+            raise ValueError(f"ClassificationMetrics: capacity = {capacity} above {_cabi.CLS_AUC_MAX_N} rows (nv_cls_auc)")
+        if self.device.type != "cuda":
+            raise RuntimeError("ClassificationMetrics runs on the MI355X (cuda) device - there is no CPU fallback")
+        self.state = torch.zeros(lib.nv_cls_metrics_state_doubles(self.C, self.bins), dtype=torch.float64, device=self.device)
+        self.bank_probs = torch.zeros((self.capacity, self.C), dtype=torch.float32, device=self.device) if self.capacity else None
+        self.bank_labels = torch.full((self.capacity,), -1, dtype=torch.int32, device=self.device) if self.capacity else None
+        self._host_groups = torch.full((self.capacity,), -1, dtype=torch.int32)
+        self.size, self.has_groups = 0, False
+
+    def reset(self) -> None:
+        self.state.zero_()
+        self._host_groups.fill_(-1)
+        self.size, self.has_groups = 0, False
+
+    def update(self, scores: torch.Tensor, labels: torch.Tensor, groups=None, kind: str = "logits") -> None:
+        if kind not in _cabi.CLS_KINDS:
+            raise ValueError(f"ClassificationMetrics.update: kind must be 'logits' or 'probs', got {kind!r}")
+        if (not torch.is_tensor(scores) or scores.dim() != 2 or scores.shape[1] != self.C or scores.shape[0] < 1 or scores.dtype != torch.float32
+                or not scores.is_cuda or scores.stride(1) != 1):
+            raise ValueError(f"ClassificationMetrics.update: scores must be float32 [B, {self.C}] on the device (B >= 1, unit column stride)")
+        B = scores.shape[0]
+        labels = torch.as_tensor(labels)
+        if labels.is_floating_point() or labels.is_complex() or labels.dtype == torch.bool or labels.numel() != B:
+            raise ValueError(f"ClassificationMetrics.update: {B} integer labels expected, got {tuple(labels.shape)} {labels.dtype}")
+        labels = labels.reshape(-1).to(scores.device, torch.int32).contiguous()
+        host_groups = None
+        if groups is not None:
+            if not self.capacity:
+                raise ValueError("ClassificationMetrics.update: groups need the bank - construct with capacity > 0")
+            host_groups = host_ids(groups, B, "ClassificationMetrics.update: groups")
+        if self.capacity and self.size + B > self.capacity:
+            raise ValueError(f"ClassificationMetrics.update: {self.size} + {B} rows exceed the capacity {self.capacity}")
+        check(lib.nv_cls_metrics_update(_p(scores), scores.stride(0), _p(labels), B, self.C, self.bins, _cabi.CLS_KINDS[kind], _p(self.state),
+                                        _p(self.bank_probs), self.C, _p(self.bank_labels), self.size, self.capacity, _stream()), "nv_cls_metrics_update")
+        if self.capacity:
+            if host_groups is not None:
+                self._host_groups[self.size:self.size + B] = host_groups
+                self.has_groups = True
+            self.size += B
+
+    def state_parts(self, state: Optional[torch.Tensor] = None) -> dict:
+        """views of the double state (no host read): "head" [6] (_cabi.CLS_STATE_NAMES), "confusion" [C, C], "bin_count" / "bin_conf" /
+        "bin_correct" [bins]"""
+        s = self.state if state is None else state
+        h, cc, nb = _cabi.CLS_STATE_HEAD, self.C * self.C, self.bins
+        return {"head": s[:h], "confusion": s[h:h + cc].view(self.C, self.C), "bin_count": s[h + cc:h + cc + nb],
+                "bin_conf": s[h + cc + nb:h + cc + 2 * nb], "bin_correct": s[h + cc + 2 * nb:h + cc + 3 * nb]}
+
+    def _finish(self, state, auc) -> torch.Tensor:
+        out = torch.empty(lib.nv_cls_metrics_table_floats(self.C), dtype=torch.float32, device=self.device)
+        check(lib.nv_cls_metrics_finish(_p(state), self.C, self.bins, _p(auc), _p(out), _stream()), "nv_cls_metrics_finish")
+        return out
+
+    def compute_device(self) -> dict:
+        """Device tensors, no host read: "table" float32 [10 + 5 C + C C] as nv_cls_metrics_finish writes it, "auc" float64 [C, 5] (nv_cls_auc;
+        with a bank), and with groups "subject_table", "subject_auc", "subject_labels" int32 [G], "subject_probs" float32 [G, C],
+        "subject_state" and "subject_mixed" int32 [1]."""
+        out = {}
+        filled = self.capacity and self.size > 0
+        if filled:
+            out["auc"] = cls_auc(self.bank_probs[:self.size], self.bank_labels[:self.size])
+        out["table"] = self._finish(self.state, out.get("auc"))
+        if filled and self.has_groups and int(self._host_groups[:self.size].max()) >= 0:
+            subjects = Segments(self._host_groups[:self.size])
+            pooled = subjects.mean(self.bank_probs[:self.size])
+            subject_labels, mixed = subjects.labels(self.bank_labels[:self.size])
+            state = torch.zeros_like(self.state)
+            check(lib.nv_cls_metrics_update(_p(pooled), pooled.stride(0), _p(subject_labels), subjects.G, self.C, self.bins, _cabi.CLS_KINDS["probs"], _p(state),
+                                            None, 0, None, 0, 0, _stream()), "nv_cls_metrics_update")
+            out["subject_auc"] = cls_auc(pooled, subject_labels)
+            out["subject_table"] = self._finish(state, out["subject_auc"])
+            out.update(subject_labels=subject_labels, subject_probs=pooled, subject_state=state, subject_mixed=mixed)
+        return out
+
+    def _named(self, table: torch.Tensor, prefix: str, with_auc: bool) -> dict:
+        C, ns, nc = self.C, len(_cabi.CLS_METRIC_NAMES), len(_cabi.CLS_CLASS_METRIC_NAMES)
+        got = {prefix + name: float(table[i]) for i, name in enumerate(_cabi.CLS_METRIC_NAMES)}
+        per_class = table[ns:ns + C * nc].reshape(C, nc)
+        for j, name in enumerate(_cabi.CLS_CLASS_METRIC_NAMES):
+            got[f"{prefix}class_{name}"] = per_class[:, j].clone()
+        got[prefix + "confusion"] = table[ns + C * nc:ns + C * nc + C * C].reshape(C, C).to(torch.int64)
+        if not with_auc:
+            del got[prefix + "macro_auc"], got[prefix + "class_auc"]
+        if C == 2:
+            got[prefix + "sensitivity"], got[prefix + "specificity"] = float(per_class[1, 1]), float(per_class[0, 1])
+            if with_auc:
+                got[prefix + "auc"] = float(per_class[1, 4])
+        return got
+
+    def compute(self) -> dict:
+        dev = self.compute_device()
+        parts = [dev["table"]]
+        if "subject_table" in dev:
+            parts += [dev["subject_table"], dev["subject_mixed"].to(torch.float32)]
+        host = torch.cat(parts).cpu()              # the one host read
+        T = dev["table"].numel()
+        got = self._named(host[:T], "", bool(self.capacity))
+        if "subject_table" in dev:
+            got.update(self._named(host[T:2 * T], "subject_", True))
+            got["subject_mixed_labels"] = int(host[2 * T])
+        return got
+
+
 # ---- the linear probe over a feature bank (probe.hip): column statistics, the fused loss + gradient pass, the Adam step, the prediction
-def _f32(t: Optional[torch.Tensor], n: int, what: str) -> Optional[torch.Tensor]:
-    if t is None:
-        return None
-    _need_cuda(t)
-    if t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous():
-        raise ValueError(f"{what} must be a contiguous float32 tensor of {n} elements on the device")
-    return t
-
-
-def _probe_x(X: torch.Tensor, what: str):
-    _need_cuda(X)
-    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or X.shape[0] < 1:
-        raise ValueError(f"{what}: float32 [N, d] with N >= 1 and unit column stride expected, got {tuple(X.shape)} {X.dtype}")
-    return X.shape
-
-
 def probe_heads(H: int, C: int, l2=None, step=None) -> "_cabi.ProbeHeads":
     """A _cabi.ProbeHeads: H heads of C columns (H * C <= 32), l2 and step per head (one value for all, a sequence, or None for zeros)."""
     H, C = int(H), int(C)
@@ -1840,8 +1897,9 @@ def probe_stats(X: Optional[torch.Tensor] = None, *, skip_nan: bool = False, eps
     256-row chunks, fp64, ascending order: the bits do not depend on the device."""
     if X is None and labels is None:
         raise ValueError("probe_stats: give X, labels or both")
+    _need_cuda(X)
     out, dev = {}, (X if X is not None else labels).device
-    N, d = (labels.numel(), 0) if X is None else _probe_x(X, "probe_stats")
+    N, d = (labels.numel(), 0) if X is None else _rows2d(X, "probe_stats: X")
     if X is not None:
         out = dict(mean=torch.empty(d, device=dev), rstd=torch.empty(d, device=dev), std=torch.empty(d, device=dev), count=torch.empty(d, dtype=torch.float64, device=dev))
     if labels is not None:
@@ -1868,7 +1926,8 @@ def probe_grad(X: torch.Tensor, W: torch.Tensor, b: torch.Tensor, heads, denom: 
     """nv_probe_grad: loss and gradient of the H heads of `heads` (probe_heads) over X f32 [N, d] in one pass: W f32 [M, d], b f32 [M], M = H C;
     labels int32 [N] (classification; outside [0, C) = unlabelled) or targets f32 [N, C] (regression; NaN = missing); denom f64 [1] / [C] from
     probe_stats.  Returns (dW f32 [M, d], db f32 [M], loss f32 [H]) - `out` = such a triple to write into (loss may be a row of a history)."""
-    N, d = _probe_x(X, "probe_grad")
+    _need_cuda(X, W, b, denom)
+    N, d = _rows2d(X, "probe_grad: X")
     H, C = heads.H, heads.C
     M = H * C
     if d % 4 or d > _cabi.PROBE_MAX_D:
@@ -1877,7 +1936,6 @@ def probe_grad(X: torch.Tensor, W: torch.Tensor, b: torch.Tensor, heads, denom: 
         raise ValueError("probe_grad: give labels (classification) or targets (regression), one of the two")
     if (mean is None) != (rstd is None):
         raise ValueError("probe_grad: mean and rstd are given together or not at all")
-    _need_cuda(W, b, denom)
     if W.dtype != torch.float32 or tuple(W.shape) != (M, d) or not W.is_contiguous():
         raise ValueError(f"probe_grad: W must be a contiguous float32 [{M}, {d}], got {tuple(W.shape)} {W.dtype}")
     b, mean, rstd = _f32(b, M, "b"), _f32(mean, d, "mean"), _f32(rstd, d, "rstd")
@@ -1923,13 +1981,13 @@ def probe_step(W, b, dW, db, mW, vW, mb, vb, heads, step: int, betas=(0.9, 0.999
 def probe_predict(Q: torch.Tensor, W: torch.Tensor, b: torch.Tensor, H: int, C: int, *, mean=None, rstd=None, want_probs: bool = False, logits=None, probs=None):
     """nv_probe_predict: queries f32 [Nq, d] -> logits f32 [Nq, M] under mean / rstd (M = H C <= 32), and with want_probs the fp32 softmax over
     each head's own C columns.  logits / probs: column windows of wider arrays to write into (their row stride is passed).  Returns (logits, probs or None)."""
-    Nq, d = _probe_x(Q, "probe_predict")
+    _need_cuda(Q, W, b)
+    Nq, d = _rows2d(Q, "probe_predict: Q")
     M = int(H) * int(C)
     if d % 4 or d > _cabi.PROBE_MAX_D:
         raise ValueError(f"probe_predict: d = {d} must be a multiple of 4 up to {_cabi.PROBE_MAX_D}")
     if (mean is None) != (rstd is None):
         raise ValueError("probe_predict: mean and rstd are given together or not at all")
-    _need_cuda(W, b)
     if W.dtype != torch.float32 or tuple(W.shape) != (M, d) or not W.is_contiguous():
         raise ValueError(f"probe_predict: W must be a contiguous float32 [{M}, {d}], got {tuple(W.shape)} {W.dtype}")
     b, mean, rstd = _f32(b, M, "b"), _f32(mean, d, "mean"), _f32(rstd, d, "rstd")

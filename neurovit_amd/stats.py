@@ -21,20 +21,7 @@ import torch
 
 from . import _cabi
 from ._cabi import check, lib
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _maps2d(X: torch.Tensor, what: str):
-    if not torch.is_tensor(X) or X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1 or not X.is_cuda:
-        raise ValueError(f"{what}: float32 [N, V] on the device with unit column stride expected")
-    return X.shape
+from .ops import Segments, _p, _rows2d, _stream, host_ids
 
 
 def perm_workspace(R: int, V: int, splits: int = 0, device="cuda") -> torch.Tensor:
@@ -60,7 +47,7 @@ def perm_design(kind: str, N: int, R: int, *, labels: Optional[torch.Tensor] = N
 def perm_stats(X: torch.Tensor, kind: str, workspace: torch.Tensor, *, labels: Optional[torch.Tensor] = None, n_a: int = 0,
                mask: Optional[torch.Tensor] = None, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """nv_perm_stats: {"a", "c", "t": fp32 [V], "n_invalid": int32 [1]} of the maps X fp32 [N, V] (a row-strided view passes its leading dimension)"""
-    N, V = _maps2d(X, "perm_stats")
+    N, V = _rows2d(X, "perm_stats: X")
     out = out or {}
     for key in ("a", "c", "t"):
         out.setdefault(key, torch.empty(V, dtype=torch.float32, device=X.device))
@@ -74,7 +61,7 @@ def perm_stats(X: torch.Tensor, kind: str, workspace: torch.Tensor, *, labels: O
 
 def perm_maxstat(X: torch.Tensor, M: torch.Tensor, a: torch.Tensor, c: torch.Tensor, workspace: torch.Tensor, *, tail: str = "two", splits: int = 0) -> None:
     """nv_perm_maxstat: the fused product + reduction of all R rows of M against the maps; the partials stay in the workspace for perm_finish"""
-    N, V = _maps2d(X, "perm_maxstat")
+    N, V = _rows2d(X, "perm_maxstat: X")
     R = M.shape[0]
     check(lib.nv_perm_maxstat(_p(X), X.stride(0), N, V, _p(M), R, _p(a), _p(c), _cabi.PERM_TAILS[tail], int(splits), _p(workspace), workspace.numel(), _stream()),
           "nv_perm_maxstat")
@@ -105,9 +92,7 @@ def _host_labels(labels, n: int) -> torch.Tensor:
     if torch.is_tensor(labels) and labels.is_cuda:
         raise ValueError("permutation_test: labels are host data (a sequence, an array or a CPU tensor) - a device tensor would cost a read-back")
     lab = torch.as_tensor(labels)
-    if lab.is_floating_point() or lab.is_complex() or lab.numel() != n:
-        raise ValueError(f"permutation_test: {n} integer labels of 0 / 1 expected, got {tuple(lab.shape)} {lab.dtype}")
-    lab = lab.detach().reshape(-1).to(torch.int32)
+    lab = host_ids(lab.to(torch.int32) if lab.dtype == torch.bool else lab, n, "permutation_test: labels of 0 / 1")
     if not bool(((lab == 0) | (lab == 1)).all()):
         raise ValueError("permutation_test: labels must be 0 or 1")
     return lab
@@ -151,23 +136,16 @@ def permutation_test(maps: torch.Tensor, labels=None, permutations: int = 10000,
     if mask is not None and (not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != shape):
         raise ValueError(f"permutation_test: mask must be a bool tensor of shape {shape}")
     lab = None if labels is None else _host_labels(labels, rows)
-    order = offsets = None
     N = rows
     if subjects is not None:
-        from .features import _host_ids
-        ids = _host_ids(subjects, rows, "permutation_test subjects").to(torch.int64)
-        used = ids[ids >= 0]
-        if used.numel() == 0:
-            raise ValueError("permutation_test: no row belongs to a subject")
-        N = int(used.max()) + 1
-        if bool((torch.bincount(used, minlength=N) == 0).any()):
+        subjects = Segments(host_ids(subjects, rows, "permutation_test subjects"))      # (no row in a subject: refused there)
+        N = subjects.G
+        if bool((subjects.sizes == 0).any()):
             raise ValueError("permutation_test: subject ids must be dense (0 .. G - 1, each with a row); GroupIndex makes such ids")
         if lab is not None:
-            first = torch.full((N,), rows, dtype=torch.int64).scatter_reduce(0, used, torch.nonzero(ids >= 0).reshape(-1), "amin")
-            per_subject = lab[first]
-            if bool((lab[ids >= 0] != per_subject[used]).any()):
+            lab, mixed = subjects.host_first_labels(lab)
+            if mixed:
                 raise ValueError("permutation_test: mixed labels - the rows of a subject carry different labels")
-            lab = per_subject
     kind = "one_sample" if lab is None else "two_sample"
     n_a = 0 if lab is None else int((lab == 1).sum())
     if N < 2 or N > _cabi.PERM_MAX_N:
@@ -190,9 +168,7 @@ def permutation_test(maps: torch.Tensor, labels=None, permutations: int = 10000,
     if X.stride(1) != 1:
         X = X.contiguous()
     if subjects is not None:
-        from . import ops
-        order, offsets = ops.segment_csr(ids, N)
-        X = ops.segment_mean(X, order, offsets)
+        X = subjects.mean(X)
     lab_dev = None if lab is None else lab.to(dev)
     mask_dev = None if mask is None else mask.reshape(V).contiguous()
     ws = perm_workspace(R, V, S, dev)

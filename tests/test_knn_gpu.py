@@ -305,6 +305,39 @@ def test_bank_predict_and_evaluate_equal_the_composition_of_the_ops(ops):
     assert out["mae"][5] == m.compute()["mae"].tolist() and len(out["subject_mae"][5]) == 2
 
 
+def test_subject_label_of_the_score_with_empty_unassigned_and_mixed_subjects(ops):
+    """knn_evaluate takes a subject's label from ops.Segments.labels (nv_segment_labels).  Held to the gather it replaced - the label of the
+    subject's first row, the subjects without a row masked - on ids that use every branch: subject 3 of the 6 has no query, two queries
+    belong to no subject (-1), subject 2 carries two labels."""
+    from neurovit_amd.features import FeatureBank, knn_evaluate
+    Nq, Nb, d, k, G, C = 40, 64, 16, 5, 6, 3
+    gen = torch.Generator().manual_seed(55)
+    centres = 2.0 * torch.randn(C, d, generator=gen)
+    bl, ql = torch.arange(Nb) % C, torch.arange(Nq) % C
+    bank = FeatureBank.from_features((centres[bl] + torch.randn(Nb, d, generator=gen)).cuda(), labels=bl, groups=torch.arange(Nb) % G)
+    q = (centres[ql] + 1.5 * torch.randn(Nq, d, generator=gen)).cuda()
+    qs = torch.tensor([0, 1, 2, 4, 5])[torch.arange(Nq) % 5]
+    qs[7], qs[23] = -1, -1
+    ql[qs == 0], ql[qs == 1], ql[qs == 4], ql[qs == 5] = 0, 1, 2, 0          # one label per subject ...
+    ql[qs == 2] = torch.tensor([1, 1, 2, 1, 1, 1, 1])                         # ... but for subject 2, whose third row differs from its first
+    got = knn_evaluate(bank, q, labels=ql, k=k, query_groups=qs, num_classes=C)
+    order, offsets = ops.segment_csr(qs)
+    assert offsets.numel() - 1 == G
+    filled = offsets[1:] > offsets[:-1]
+    assert filled.tolist() == [True, True, True, False, True, True]
+    y = ql.to(torch.int32).cuda()
+    y_subject = y[order[offsets[:-1].clamp(max=Nq - 1).long()].long()]
+    best, cls = ops.segment_mean(got["scores"][k], order, offsets).max(dim=1)
+    cls = torch.where(best > 0, cls.to(torch.int32), torch.full_like(cls, -1, dtype=torch.int32))
+    want = (((cls == y_subject) & filled).float().sum() / filled.float().sum().clamp(min=1)).item()
+    print(f"subject label: subject_acc {got['subject_acc'][k]!r}, by the gather {want!r}, acc {got['acc'][k]!r}")
+    assert got["subject_acc"][k] == want and 0.0 < want <= 1.0
+    assert int(cls[3]) == -1 and int(y_subject[3]) != -1                      # the empty subject: no class, a label from the clamped gather - masked, not a hit
+    metrics = ops.ClassificationMetrics(C, capacity=Nq)
+    metrics.update(got["scores"][k], ql, groups=qs, kind="probs")
+    assert metrics.compute()["subject_mixed_labels"] == 1
+
+
 def test_trainer_logs_the_knn_validation_only_when_asked(tmp_path, monkeypatch):
     import neurovit_amd.NeuroEncoder as ne
     from neurovit_amd.trainer import Trainer

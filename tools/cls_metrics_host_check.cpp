@@ -2,26 +2,11 @@
 // refusals and the sizing helpers.  Every call carries bad arguments (or is host-only), so nothing is launched and no GPU is needed.
 // Built by `make -C neurovit_amd/csrc cls-metrics-host-check` with -Xarch_host -fsanitize=address,undefined; run by
 // tests/test_cls_metrics_cpu.py.
-#include <stdio.h>
-#include <string.h>
-
-#include "../include/neurovit_hip.h"
-
-extern "C" const char* nv_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                                                          \
-  do {                                                                                        \
-    if (!(cond)) {                                                                            \
-      printf("cls_metrics_host_check: FAILED %s (line %d): %s\n", #cond, __LINE__, nv_last_error()); \
-      ++failures;                                                                             \
-    }                                                                                         \
-  } while (0)
+#define HOST_CHECK_NAME "cls_metrics_host_check"
+#include "host_check.h"
 
 int main() {
-  alignas(16) float f[64] = {0};
   alignas(16) double d[64] = {0};
-  int idx[64] = {0};
   char* odd = reinterpret_cast<char*>(d) + 4;      // 4-byte but not 8-byte aligned
   // sizing
   EXPECT(nv_cls_metrics_state_doubles(2, 15) == NV_CLS_STATE_HEAD + 4 + 45);
@@ -79,7 +64,5 @@ int main() {
   EXPECT(nv_cls_metrics_finish(d, 3, 0, nullptr, f, nullptr) == NV_ERR_ARG);
   EXPECT(nv_cls_metrics_finish(d, 3, 15, reinterpret_cast<double*>(odd), f, nullptr) == NV_ERR_ARG);
   EXPECT(nv_cls_metrics_finish(reinterpret_cast<double*>(odd), 3, 15, nullptr, f, nullptr) == NV_ERR_ARG);
-  if (failures) return 1;
-  printf("cls_metrics_host_check: ok\n");
-  return 0;
+  return host_check_result();
 }

@@ -1,27 +1,12 @@
 // Host-side checks of the frozen-feature entry points (neurovit_amd/csrc/features.hip) under the host sanitizers: argument refusals,
 // workspace sizing and the CSR validation.  Every call carries bad arguments (or is host-only), so nothing is launched and no GPU is needed.
 // Built by `make -C neurovit_amd/csrc host-check` with -Xarch_host -fsanitize=address,undefined; run by tests/test_knn_cpu.py.
-#include <stdio.h>
-#include <string.h>
-
 #include <vector>
 
-#include "../include/neurovit_hip.h"
-
-extern "C" const char* nv_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                                                  \
-  do {                                                                                \
-    if (!(cond)) {                                                                    \
-      printf("knn_host_check: FAILED %s (line %d): %s\n", #cond, __LINE__, nv_last_error()); \
-      ++failures;                                                                     \
-    }                                                                                 \
-  } while (0)
+#define HOST_CHECK_NAME "knn_host_check"
+#include "host_check.h"
 
 int main() {
-  alignas(16) float f[64] = {0};
-  int idx[64] = {0};
   // nv_knn_topk: k, multiples of 4, alignment, group pairing, splits, workspace
   EXPECT(nv_knn_topk(f, 8, 4, f, 8, 4, 8, 0, nullptr, nullptr, 0, idx, f, nullptr, 0, nullptr) == NV_ERR_ARG);
   EXPECT(nv_knn_topk(f, 8, 4, f, 8, 4, 8, NV_KNN_MAX_K + 1, nullptr, nullptr, 0, idx, f, nullptr, 0, nullptr) == NV_ERR_ARG);
@@ -83,7 +68,5 @@ int main() {
   EXPECT(nv_segment_mean(f, 4, 4, 8, idx, idx, 2, f, 8, nullptr) == NV_ERR_ARG);
   EXPECT(nv_segment_mean(f, 8, 4, 8, idx, idx, 70000, f, 8, nullptr) == NV_ERR_ARG);
   EXPECT(nv_segment_mean(f, 8, 4, 8, nullptr, idx, 2, f, 8, nullptr) == NV_ERR_ARG);
-  if (failures) return 1;
-  printf("knn_host_check: ok\n");
-  return 0;
+  return host_check_result();
 }

@@ -2,26 +2,11 @@
 // the sizing helpers.  Every call carries bad arguments (or is host-only), so nothing is launched and no GPU is needed.
 // Built by `make -C neurovit_amd/csrc perm-test-host-check` with -Xarch_host -fsanitize=address,undefined; run by
 // tests/test_perm_test_cpu.py.
-#include <stdio.h>
-#include <string.h>
-
-#include "../include/neurovit_hip.h"
-
-extern "C" const char* nv_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                                                          \
-  do {                                                                                        \
-    if (!(cond)) {                                                                            \
-      printf("perm_test_host_check: FAILED %s (line %d): %s\n", #cond, __LINE__, nv_last_error()); \
-      ++failures;                                                                             \
-    }                                                                                         \
-  } while (0)
+#define HOST_CHECK_NAME "perm_test_host_check"
+#include "host_check.h"
 
 int main() {
-  alignas(16) float f[64] = {0};
   alignas(16) float ws[64] = {0};
-  int idx[64] = {0};
   unsigned char mask[64] = {0};
   const double alphas[2] = {0.05, 0.01}, bad_alpha[1] = {1.0}, zero_alpha[1] = {0.0};
   float* odd = f + 1;      // 4-byte but not 16-byte aligned
@@ -90,7 +75,5 @@ int main() {
   EXPECT(nv_perm_finish(ONE, 5, 32, 8, 0, f, bad_alpha, 1, f, f, idx, idx, f, f, f, ws, 256, nullptr) == NV_ERR_ARG);
   EXPECT(nv_perm_finish(ONE, 5, 32, 8, 0, f, zero_alpha, 1, f, f, idx, idx, f, f, f, ws, 256, nullptr) == NV_ERR_ARG);
   EXPECT(nv_perm_finish(ONE, 5, 32, 8, 0, f, alphas, 2, f, f, idx, idx, f, f, f, ws, nv_perm_workspace_bytes(32, 8, 0) - 1, nullptr) == NV_ERR_ARG);
-  if (failures) return 1;
-  printf("perm_test_host_check: ok\n");
-  return 0;
+  return host_check_result();
 }

@@ -1,21 +1,8 @@
 // Host-side checks of the linear-probe entry points (neurovit_amd/csrc/probe.hip) under the host sanitizers: argument refusals and workspace
 // sizing.  Every call carries bad arguments (or is host-only), so nothing is launched and no GPU is needed.
 // Built by `make -C neurovit_amd/csrc probe-host-check` with -Xarch_host -fsanitize=address,undefined; run by tests/test_probe_cpu.py.
-#include <stdio.h>
-#include <string.h>
-
-#include "../include/neurovit_hip.h"
-
-extern "C" const char* nv_last_error(void);
-
-static int failures = 0;
-#define EXPECT(cond)                                                                    \
-  do {                                                                                  \
-    if (!(cond)) {                                                                      \
-      printf("probe_host_check: FAILED %s (line %d): %s\n", #cond, __LINE__, nv_last_error()); \
-      ++failures;                                                                       \
-    }                                                                                   \
-  } while (0)
+#define HOST_CHECK_NAME "probe_host_check"
+#include "host_check.h"
 
 static nv_probe_heads heads(int H, int C) {
   nv_probe_heads h;
@@ -27,7 +14,6 @@ static nv_probe_heads heads(int H, int C) {
 }
 
 int main() {
-  alignas(16) float f[64] = {0};
   alignas(16) double dbl[64] = {0};
   int lab[64] = {0};
   alignas(16) char ws[1 << 16];
@@ -98,7 +84,5 @@ int main() {
   EXPECT(nv_probe_stats(nullptr, 0, 4, 0, 0, 0.f, nullptr, nullptr, nullptr, nullptr, lab, 0, nullptr, dbl, ws, big, nullptr) == NV_ERR_ARG);         // C = 0
   EXPECT(nv_probe_stats(f, 8, 4, 8, 0, 0.f, f, f, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ws, 8, nullptr) == NV_ERR_ARG);                     // workspace too small
   EXPECT(nv_probe_stats(f, 8, 4, 8, 0, 0.f, f, f, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr) == NV_ERR_ARG);
-  if (failures) return 1;
-  printf("probe_host_check: ok\n");
-  return 0;
+  return host_check_result();
 }
